@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- Gibbs sweeps/sec (both entities) + test RMSE, BPMF on MovieLens-1M, D=32, fp64 (BASELINE.json config 2).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run does only what the headline needs: set-up, W warm-up steps, K timed steps, the result line.  --full adds every
+other measurement described below (the cold-device value, the K1 roofline, the CPU baselines and the blocks c4, c4_uniform,
+c5, c3 and mref); the --no-* switches and the --c4-* / --c5-* / --k1-* sizes apply to those.  --dump-outputs DIR leaves what
+the last timed step computed in DIR/<name>.npy (float64): every entity's sample, mu and Lambda, and the held-out predictions'
+running mean and sum of squares -- written before anything else advances the chain, so a plain run and a --full run with the
+same arguments leave the same arrays.
 
 A step is one Gibbs iteration of src/macau.jl:80 on the device: latent rows of users, hyperprior of users, latent rows of
 movies, hyperprior of movies, and the test-set prediction update of macau.jl:142-184 (inside the timed region; the
@@ -14,14 +21,14 @@ The JSON line has two measurements:
  * value / ms_per_step: the BASELINE metric.  N = 1 is exactly the BASELINE configuration.  N > 1 is WEAK scaling of it:
    MovieLens is a ~120 us sweep, far too small to split, so the N-GPU workload is N MovieLens-sized units -- the rating
    matrix stacked over N disjoint user blocks that rate the same movies (datasets.replicate_users) -- value = N x sweeps/s.
- * "c4": STRONG scaling on BASELINE configuration 4, the synthetic 10M x 1M relation with 100M observations at D = 64
+ * "c4" (--full): STRONG scaling on BASELINE configuration 4, the synthetic 10M x 1M relation with 100M observations at D = 64
    (datasets.c4_relation_data / bdf_synth_ratings): the same relation on 1, 2, 4, 8 GPUs, c4.sweeps_per_s.  (--c4-nnz etc.
    shrink it; --no-c4 skips it.)
 In both, with N > 1: one process per GPU; every rank holds the observations of its own rows and a replica of both factor
 matrices (rows shared out by bdf_layout_build), samples its rows and takes part in an in-place RCCL all-gather per
 half-sweep (bdf_allgather_rows); the test ratings are split over the ranks.
 
-roofline: K1 (k_rows) algorithmic bytes per launch over its mean launch duration from HIP events attached to
+(--full) roofline: K1 (k_rows) algorithmic bytes per launch over its mean launch duration from HIP events attached to
 the kernel dispatches (on the launch stream), from the timed region and -- so that at least 200 launches are averaged --
 from further sweeps after it; `avg_launch_us_alone` / `frac_alone`: the same kernel with nothing beside it (back-to-back
 launches on the row stream, wall clock).  cpu_baseline: the CPU oracle (a C port of the reference algorithm, OpenMP over rows like
@@ -419,6 +426,10 @@ def main():
                                                      "Lambda of the main workload and of the C4 / C5 blocks in PREFIX.<block>.rank<r>.npz")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="test hook: every rank joins the process group, all-reduces its rank, rank 0 prints it; no GPU is touched")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: cold-device value, K1 roofline, CPU baselines, blocks c4, c4_uniform, c5, c3, mref")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -501,6 +512,30 @@ def main():
                 st[f"beta{j}"] = e.host("beta")
         np.savez(f"{args.dump_state}.{block}.rank{rank}.npz", **st)
 
+    def dump_outputs(engine, entities, test):
+        """--dump-outputs DIR: what a caller of the timed step holds after the last one -- every entity's sample (D x N, the
+        reference's row order), mu and Lambda, the held-out predictions' running mean and sum of squares (this rank's share, in
+        test_vec's order) and the reporting stats.  Over 64 MB in all (many user blocks): every large array keeps the same
+        fixed, seeded sample of positions along its longest axis (np.random.default_rng(12345), sorted)."""
+        if not args.dump_outputs:
+            return
+        arrs = {}
+        for en, st in zip(entities, engine.ent):
+            for k in ("sample", "mu", "Lambda"):
+                arrs[f"{en.name}_{k}"] = np.asarray(st.host(k), dtype=np.float64)
+        avg, sq = test.state()
+        arrs["test_pred_mean"], arrs["test_pred_sumsq"] = avg.astype(np.float64), sq.astype(np.float64)
+        arrs["test_stats"] = test.stats.cpu().numpy().astype(np.float64)
+        keep = min(1.0, 0.95 * 64 * 2 ** 20 / max(1, sum(a.nbytes for a in arrs.values())))
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        suffix = f".rank{rank}" if world > 1 else ""
+        for name, a in arrs.items():
+            if keep < 1.0 and a.size > 4096:
+                ax = int(np.argmax(a.shape))
+                idx = np.sort(np.random.default_rng(12345).choice(a.shape[ax], max(1, int(a.shape[ax] * keep)), replace=False))
+                a = np.take(a, idx, axis=ax)
+            np.save(os.path.join(args.dump_outputs, f"{name}{suffix}.npy"), a)
+
     # ---- the BASELINE metric: MovieLens (N > 1: N stacked units) ------------------------------------------------------------
     D = args.num_latent
     replicas = args.replicas if args.replicas > 0 else world
@@ -509,7 +544,7 @@ def main():
     # continuity with the rounds before the set-up warm-up existed: the same --warmup + --steps on a throw-away
     # engine WITHOUT it, first thing in the process -- a cold device, as those rounds' driver lines were measured
     value_cold = None
-    if world == 1 and args.device_warmup_ms > 0 and not os.environ.get("BDF_BENCH_NO_COLD"):
+    if args.full and world == 1 and args.device_warmup_ms > 0 and not os.environ.get("BDF_BENCH_NO_COLD"):
         eng0 = B.GibbsEngine(rd, D, seed=args.seed, device=local_rank)
         eng0.test_pairs()
         eng0.register_test([1.0, 5.0], rel.class_cut)
@@ -567,57 +602,84 @@ def main():
         dist.all_reduce(sse)                       # every rank holds the squared error of its share of the test ratings
     rmse = float(np.sqrt(float(sse.item()) / n_test_total))
     dump_state(eng, "main")
+    dump_outputs(eng, rd.entities, test)
 
-    # K1 roofline: the launches timed inside the timed region, then further sweeps (every launch timed) up to the minimum
-    # (i) device-side spans: first wave's start to last wave's end of every row launch (s_memrealtime, K1c only), no event packets
-    it = args.warmup + args.steps
-    span_us = []
-    if eng.native and args.k1_min_launches > 0:
-        eng.k1_span_begin(args.k1_min_launches)
-        for _ in range((args.k1_min_launches + len(eng.ent) - 1) // len(eng.ent)):
+    def k1_roofline():
+        """(--full) the K1 roofline measured on further sweeps after the timed region (they advance the chain)"""
+        # K1 roofline: the launches timed inside the timed region, then further sweeps (every launch timed) up to the minimum
+        # (i) device-side spans: first wave's start to last wave's end of every row launch (s_memrealtime, K1c only), no event packets
+        it = args.warmup + args.steps
+        span_us = []
+        if eng.native and args.k1_min_launches > 0:
+            eng.k1_span_begin(args.k1_min_launches)
+            for _ in range((args.k1_min_launches + len(eng.ent) - 1) // len(eng.ent)):
+                it += 1
+                eng.sweep(it, 2)
+            span_us = eng.k1_span_result()
+        # (ii) HIP events on the kernels' dispatch packets (every K1 variant; the events themselves lengthen the launch)
+        eng.k1_events = []
+        eng.k1_event_every = 1
+        t_ev = time.perf_counter()
+        it_ev0 = it
+        while len(eng.k1_events) < args.k1_min_launches and it < it_ev0 + 2000:
             it += 1
             eng.sweep(it, 2)
-        span_us = eng.k1_span_result()
-    # (ii) HIP events on the kernels' dispatch packets (every K1 variant; the events themselves lengthen the launch)
-    eng.k1_events = []
-    eng.k1_event_every = 1
-    t_ev = time.perf_counter()
-    it_ev0 = it
-    while len(eng.k1_events) < args.k1_min_launches and it < it_ev0 + 2000:
-        it += 1
-        eng.sweep(it, 2)
-    eng.sync()
-    k1_ms = sum(t.elapsed_us() for (_, t) in eng.k1_events) / 1e3
-    k1_bytes = sum(eng.k1_algorithmic_bytes(j) for (j, _) in eng.k1_events) / max(world, 1)
-    k1_flops = sum(eng.k1_algorithmic_flops(j) for (j, _) in eng.k1_events) / max(world, 1)
-    n_launch = max(len(eng.k1_events), 1)
-    launch_us_events = 1e3 * k1_ms / n_launch
-    launch_us = (sum(u for _, u in span_us) / len(span_us)) if span_us else launch_us_events
-    pipe = recorded_pipe(launch_us)
-    achieved = (k1_bytes / n_launch / 1e9) / (launch_us / 1e6) if launch_us > 0 else 0.0
-    eng.k1_events = None
-    traffic, traffic_source = recorded_traffic() if (world == 1 and replicas == 1 and D == 32) else (None, None)
-    # the same kernel with nothing beside it: back-to-back launches alternating the entities on the row stream, wall clock (one
-    # GPU only; in the sweep a launch also holds the wait for the prior inside the kernel and shares the CUs with the prediction
-    # update).  After the timed region: the chain's state is no longer used.
-    alone_us = None
-    if world == 1 and args.k1_min_launches > 0:
         eng.sync()
-        torch.cuda.synchronize()
-        n_alone = 200
-        ta = time.perf_counter()
-        from bdf_amd._lib import check as _check, lib as _lib
-        for i in range(n_alone):
-            if eng.native:          # the launch the sweep makes (same kernel variant), alone
-                _check(_lib().bdf_gibbs_rows_only(eng.gibbs, i % len(eng.ent), 1_000_000 + i))
-            else:
-                eng.ctx.set_sweep(1_000_000 + i)
-                eng.sample_entity(i % len(eng.ent))
-        enq_us = 1e6 * (time.perf_counter() - ta) / n_alone
-        eng.sync()
-        alone_us = 1e6 * (time.perf_counter() - ta) / n_alone
-        if os.environ.get("BDF_BENCH_DEBUG"):
-            print(f"[bench] K1 alone: enqueue {enq_us:.1f} us per launch, total {alone_us:.1f} us", file=sys.stderr)
+        k1_ms = sum(t.elapsed_us() for (_, t) in eng.k1_events) / 1e3
+        k1_bytes = sum(eng.k1_algorithmic_bytes(j) for (j, _) in eng.k1_events) / max(world, 1)
+        k1_flops = sum(eng.k1_algorithmic_flops(j) for (j, _) in eng.k1_events) / max(world, 1)
+        n_launch = max(len(eng.k1_events), 1)
+        launch_us_events = 1e3 * k1_ms / n_launch
+        launch_us = (sum(u for _, u in span_us) / len(span_us)) if span_us else launch_us_events
+        pipe = recorded_pipe(launch_us)
+        achieved = (k1_bytes / n_launch / 1e9) / (launch_us / 1e6) if launch_us > 0 else 0.0
+        eng.k1_events = None
+        traffic, traffic_source = recorded_traffic() if (world == 1 and replicas == 1 and D == 32) else (None, None)
+        # the same kernel with nothing beside it: back-to-back launches alternating the entities on the row stream, wall clock (one
+        # GPU only; in the sweep a launch also holds the wait for the prior inside the kernel and shares the CUs with the prediction
+        # update).  After the timed region: the chain's state is no longer used.
+        alone_us = None
+        if world == 1 and args.k1_min_launches > 0:
+            eng.sync()
+            torch.cuda.synchronize()
+            n_alone = 200
+            ta = time.perf_counter()
+            from bdf_amd._lib import check as _check, lib as _lib
+            for i in range(n_alone):
+                if eng.native:          # the launch the sweep makes (same kernel variant), alone
+                    _check(_lib().bdf_gibbs_rows_only(eng.gibbs, i % len(eng.ent), 1_000_000 + i))
+                else:
+                    eng.ctx.set_sweep(1_000_000 + i)
+                    eng.sample_entity(i % len(eng.ent))
+            enq_us = 1e6 * (time.perf_counter() - ta) / n_alone
+            eng.sync()
+            alone_us = 1e6 * (time.perf_counter() - ta) / n_alone
+            if os.environ.get("BDF_BENCH_DEBUG"):
+                print(f"[bench] K1 alone: enqueue {enq_us:.1f} us per launch, total {alone_us:.1f} us", file=sys.stderr)
+        return {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
+                "kernel": "k_rows_col (k_rows_col.hip: K1c) when D in 17..32, else k_rows (k_sample_rows.hip)", "launches_timed": n_launch,
+                # avg_launch_us: first wave's start to last wave's end of the launch, stamped BY THE KERNEL (s_memrealtime, one
+                # atomic min / max per wave: bdf_gibbs_span_rows) on sweeps after the timed region -- what rocprofv3 reports as
+                # the kernel's duration, with no event packets around the dispatch; by_events: HIP events riding on the dispatch
+                # packets (what rounds 1-4 quoted: the events lengthen the launch by a few us)
+                "avg_launch_us": round(launch_us, 2), "avg_launch_us_timer": "in-kernel s_memrealtime span" if span_us else "HIP events",
+                "launches_spanned": len(span_us), "avg_launch_us_by_events": round(launch_us_events, 2),
+                "fp64_pipe": pipe,
+                # the same as scalars (what a parser that keeps only numbers and strings sees): the FP64 pipe's busy share of the
+                # launch from the committed counters, the launch's flops by the reference's map against the 78.6 TF peak, and the
+                # counters' HBM traffic over the algorithmic bytes (<< 1: the gathered factor is L2-resident, nothing re-read)
+                "fp64_valu_busy_frac": None if pipe is None else pipe["frac"],
+                "fp64_flops_frac": (round(k1_flops / n_launch / (launch_us * 1e-6) / (FP64_PEAK_TFLOPS * 1e12), 4)
+                                    if n_launch and launch_us > 0 else None),
+                "traffic_over_algorithmic": None if traffic is None or not k1_bytes else round(traffic / (k1_bytes / n_launch), 3),
+                "counters_schedule": "the committed PMC passes ran with BDF_RESERVE_CUS=0 BDF_NO_POLL=1 (rocprofv3 serialises the streams; CU-masked "
+                                     "streams crash its teardown): all 1,024 SIMDs, event hand-overs -- the launch time they are divided by is this run's",
+                "algorithmic_bytes_per_launch": int(k1_bytes / n_launch),
+                "avg_launch_us_alone": None if alone_us is None else round(alone_us, 2),
+                "frac_alone": None if alone_us is None else round((k1_bytes / n_launch / 1e9) / (alone_us / 1e6) / HBM_PEAK_GBS, 4)}
+
+    roofline = k1_roofline() if args.full else None
 
     if full_affinity:
         os.sched_setaffinity(0, full_affinity)            # the CPU baseline and the C4 generator use every core
@@ -639,8 +701,8 @@ def main():
             "config": {"workload": f"BPMF MovieLens-1M 6040x3952, 500209 training ratings (500000 held out), D={D}, alpha=1.5, "
                                    f"step = rows of both entities + hyperpriors + test prediction update (one native call); "
                                    f"BEFORE the --warmup steps the engine's set-up runs {args.device_warmup_ms:g} ms of full "
-                                   f"iterations whose results are discarded (device_warmup_ms; the value without it: "
-                                   f"value_without_device_warmup)"
+                                   f"iterations whose results are discarded (device_warmup_ms"
+                                   + ("; the value without it: value_without_device_warmup)" if args.full else ")")
                                    + (f"; {replicas} such units: the ratings stacked over {replicas} disjoint user blocks, "
                                       f"value = {replicas} x sweeps/s" if replicas > 1 else ""),
                        "num_latent": D, "burnin": args.warmup, "psamples": args.steps, "units_per_sweep": replicas,
@@ -652,31 +714,12 @@ def main():
                                        f"transport: {eng.comm.transport if eng.comm is not None else 'none'}")
                        if world > 1 else "1 GPU"},
             "test_rmse": None if rmse is None else round(rmse, 5),
-            "value_without_device_warmup": None if value_cold is None else round(value_cold, 3),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": "k_rows_col (k_rows_col.hip: K1c) when D in 17..32, else k_rows (k_sample_rows.hip)", "launches_timed": n_launch,
-                         # avg_launch_us: first wave's start to last wave's end of the launch, stamped BY THE KERNEL (s_memrealtime, one
-                         # atomic min / max per wave: bdf_gibbs_span_rows) on sweeps after the timed region -- what rocprofv3 reports as
-                         # the kernel's duration, with no event packets around the dispatch; by_events: HIP events riding on the dispatch
-                         # packets (what rounds 1-4 quoted: the events lengthen the launch by a few us)
-                         "avg_launch_us": round(launch_us, 2), "avg_launch_us_timer": "in-kernel s_memrealtime span" if span_us else "HIP events",
-                         "launches_spanned": len(span_us), "avg_launch_us_by_events": round(launch_us_events, 2),
-                         "fp64_pipe": pipe,
-                         # the same as scalars (what a parser that keeps only numbers and strings sees): the FP64 pipe's busy share of the
-                         # launch from the committed counters, the launch's flops by the reference's map against the 78.6 TF peak, and the
-                         # counters' HBM traffic over the algorithmic bytes (<< 1: the gathered factor is L2-resident, nothing re-read)
-                         "fp64_valu_busy_frac": None if pipe is None else pipe["frac"],
-                         "fp64_flops_frac": (round(k1_flops / n_launch / (launch_us * 1e-6) / (FP64_PEAK_TFLOPS * 1e12), 4)
-                                             if n_launch and launch_us > 0 else None),
-                         "traffic_over_algorithmic": None if traffic is None or not k1_bytes else round(traffic / (k1_bytes / n_launch), 3),
-                         "counters_schedule": "the committed PMC passes ran with BDF_RESERVE_CUS=0 BDF_NO_POLL=1 (rocprofv3 serialises the streams; CU-masked "
-                                              "streams crash its teardown): all 1,024 SIMDs, event hand-overs -- the launch time they are divided by is this run's",
-                         "algorithmic_bytes_per_launch": int(k1_bytes / n_launch),
-                         "avg_launch_us_alone": None if alone_us is None else round(alone_us, 2),
-                         "frac_alone": None if alone_us is None else round((k1_bytes / n_launch / 1e9) / (alone_us / 1e6) / HBM_PEAK_GBS, 4)},
+            "full": bool(args.full),
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out["value_without_device_warmup"] = None if value_cold is None else round(value_cold, 3)
+            out["roofline"] = roofline
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(rd, D, args.seed)
     eng.close()
     del eng, rd, rel, test
@@ -743,7 +786,7 @@ def main():
             print(f"[bench] rank {rank}: the C4 block failed: {c4['error']}", file=sys.stderr, flush=True)
         return c4
 
-    if not args.no_c4:
+    if args.full and not args.no_c4:
         c4 = c4_variant(100.0, "Zipf-like", True)
         if out is not None:
             out["c4"] = c4
@@ -753,7 +796,7 @@ def main():
             if out is not None:
                 out["c4_uniform"] = c4u
     # ---- configuration C5: tensor + matrix sharing an entity with binary sparse features (strong scaling) -------------------
-    if not args.no_c5:
+    if args.full and not args.no_c5:
         z5 = dict(zip(("nA", "nB", "nC", "nT", "n1", "n2", "n_feat", "feat_per_row"),
                       [int(x) for x in (args.c5_sizes or "100000,64,1000,500,5000000,1000000,50000,50").split(",")]))
         c5 = {"workload": f"entity A ({z5['nA']} rows, binary sparse features {z5['nA']} x {z5['n_feat']}, {z5['feat_per_row']} per row) shared by a "
@@ -808,7 +851,7 @@ def main():
         if out is not None:
             out["c5"] = c5
     # ---- configuration C3 and the reference's own benchmark shape (one GPU) ------------------------------------------------
-    if world == 1 and out is not None:
+    if args.full and world == 1 and out is not None:
         for name, skip, fn in (("c3", args.no_c3, lambda: c3_block(B, datasets, D, local_rank)),
                                ("mref", args.no_mref, lambda: mref_block(B, local_rank, not args.no_cpu_baseline))):
             if skip:

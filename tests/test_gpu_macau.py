@@ -566,11 +566,11 @@ def test_two_ranks_match_one(B, tmp_path):
     env["BDF_COMM_PEER"] = "1"          # (opt-in: unmeasured on a node with several GPUs)
     c5_sizes = "3000,16,60,40,120000,30000,400,8"
     # `python bench.py --gpus 2` as typed: bench.py starts its two ranks itself (torch's launcher, as a child process)
-    two = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "6", "--dump-state", str(tmp_path / "two"),
+    two = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "6", "--dump-state", str(tmp_path / "two"),
                           "--c4-rows", "20000", "--c4-cols", "3000", "--c4-nnz", "300000", "--c4-latent", "64", "--c5-sizes", c5_sizes, "--c5-sweeps", "6"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert two.returncode == 0, two.stdout[-2000:] + two.stderr[-2000:]
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--replicas", "2", "--steps", "4", "--warmup", "6", "--no-cpu-baseline", "--no-c3", "--no-mref",
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--replicas", "2", "--steps", "4", "--warmup", "6", "--no-cpu-baseline", "--no-c3", "--no-mref",
                           "--dump-state", str(tmp_path / "one"),
                           "--c4-rows", "20000", "--c4-cols", "3000", "--c4-nnz", "300000", "--c4-latent", "64", "--c5-sizes", c5_sizes, "--c5-sweeps", "6"],
                          capture_output=True, text=True, timeout=600)
@@ -597,7 +597,7 @@ def test_two_ranks_match_one(B, tmp_path):
     # ... and the transport changes nothing: the same two ranks with the blocks staged through the host (BDF_COMM_PEER unset)
     # leave the C4-shaped block's factors bit for bit
     env.pop("BDF_COMM_PEER")
-    host = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "2", "--dump-state", str(tmp_path / "host"),
+    host = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "2", "--dump-state", str(tmp_path / "host"),
                            "--no-c5", "--c4-rows", "20000", "--c4-cols", "3000", "--c4-nnz", "300000", "--c4-latent", "64"],
                           env=env, capture_output=True, text=True, timeout=600)
     assert host.returncode == 0, host.stdout[-2000:] + host.stderr[-2000:]
@@ -628,7 +628,7 @@ def test_two_ranks_match_one_with_four_rows_per_wave():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    args = ["--steps", "4", "--warmup", "6", "--num-latent", "10", "--no-cpu-baseline", "--no-c3", "--no-mref", "--no-c5",
+    args = ["--full", "--steps", "4", "--warmup", "6", "--num-latent", "10", "--no-cpu-baseline", "--no-c3", "--no-mref", "--no-c5",
             "--c4-rows", "20000", "--c4-cols", "3000", "--c4-nnz", "300000", "--c4-latent", "12"]
     base = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = {}
@@ -642,6 +642,42 @@ def test_two_ranks_match_one_with_four_rows_per_wave():
     for name in ("one", "old"):
         assert abs(out["two"]["test_rmse"] - out[name]["test_rmse"]) < 2e-5, (name, out["two"]["test_rmse"], out[name]["test_rmse"])
         assert abs(out["two"]["c4"]["test_rmse"] - out[name]["c4"]["test_rmse"]) < 1e-4, (name, out["two"]["c4"], out[name]["c4"])
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """bench.py as the driver runs it: a plain run prints the headline over exactly --steps timed steps and nothing that takes
+    runs of its own; --dump-outputs leaves the last timed step's arrays (float64, the workload's shapes, under 64 MB); a second
+    plain run and a --full run with the same arguments leave the same arrays bit for bit (--full measures after the dump)"""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "BDF_DIST_BACKEND")}
+    full = ["--full", "--no-cpu-baseline", "--no-c4", "--no-c3", "--no-c5", "--no-mref", "--k1-min-launches", "4"]
+    lines = {}
+    for name, extra in (("a", []), ("b", []), ("full", full)):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / name)] + extra, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines[name] = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    d = lines["a"]
+    assert d["unit"] == "sweeps/s" and d["higher_is_better"] is True and d["dtype"] == "f64" and d["steps"] == 3
+    assert d["ms_per_step"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 2e-3, d
+    assert not {"roofline", "cpu_baseline", "value_without_device_warmup", "c3", "c4", "c4_uniform", "c5", "mref"} & set(d), sorted(d)
+    assert lines["full"]["roofline"]["launches_timed"] >= 4 and "value_without_device_warmup" in lines["full"]
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b")) == sorted(os.listdir(tmp_path / "full"))
+    shapes = {"users_sample.npy": (32, 6040), "movies_sample.npy": (32, 3952), "users_Lambda.npy": (32, 32), "movies_mu.npy": (32,),
+              "test_pred_mean.npy": (500_000,), "test_pred_sumsq.npy": (500_000,), "test_stats.npy": (4,)}
+    assert set(shapes) <= set(files), files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 2 ** 20
+    for f in files:
+        a = np.load(tmp_path / "a" / f)
+        assert a.dtype == np.float64 and np.isfinite(a).all() and a.shape == shapes.get(f, a.shape), (f, a.dtype, a.shape)
+        for other in ("b", "full"):
+            assert np.array_equal(a, np.load(tmp_path / other / f)), (f, other)
+    stats = np.load(tmp_path / "a" / "test_stats.npy")
+    assert abs(np.sqrt(stats[0] / 500_000) - d["test_rmse"]) < 1e-5, (stats, d["test_rmse"])
 
 
 @pytest.mark.parametrize("mode", ["plain", "rccl"])

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 o=$GRAFT_REPO_ROOT/gpurun_out/r06B; mkdir -p $o
 V=$GRAFT_REPO_ROOT/bayesiandatafusion.jl_amd/csrc/variants
-B="--no-cpu-baseline --no-c4 --no-c3 --no-c5 --no-mref"
+B="--full --no-cpu-baseline --no-c4 --no-c3 --no-c5 --no-mref"
 bench() { echo "== $*" >> $o/bench.txt; env "$@" python3 bench.py --gpus 1 --steps 20 --warmup 5 $B 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']; print(d['value'], d['ms_per_step'], r.get('frac'), r.get('avg_launch_us'), r.get('avg_launch_us_alone'), d.get('value_without_device_warmup'))" >> $o/bench.txt; }

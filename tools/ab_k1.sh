@@ -29,7 +29,7 @@ else
   steps=${2:-200}
   for so in $var/libbdf_*.so; do
     echo "== $(basename $so)"
-    BDF_LIB_PATH=$so python3 $root/bench.py --steps $steps --warmup 20 --no-cpu-baseline 2>&1 | tail -1 | python3 -c "
+    BDF_LIB_PATH=$so python3 $root/bench.py --full --steps $steps --warmup 20 --no-cpu-baseline 2>&1 | tail -1 | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline'])"
   done

@@ -8,7 +8,7 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA S
            "SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_ANY SQ_INSTS_VMEM" \
            "FETCH_SIZE" "WRITE_SIZE" "GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR"; do
   i=$((i+1)); rm -rf /tmp/c4p$i
-  rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/c4p$i -- python3 $R/bench.py --steps 2 --warmup 2 --k1-min-launches 0 --no-cpu-baseline --no-c3 --no-c5 --no-mref --c4-sweeps 2 > /tmp/c4p$i.log 2>&1
+  rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/c4p$i -- python3 $R/bench.py --full --steps 2 --warmup 2 --k1-min-launches 0 --no-cpu-baseline --no-c3 --no-c5 --no-mref --c4-sweeps 2 > /tmp/c4p$i.log 2>&1
   tail -2 /tmp/c4p$i.log | cut -c1-300
 done
 python3 - <<PY

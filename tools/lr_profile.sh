@@ -6,7 +6,7 @@ export BDF_RESERVE_CUS=0
 for what in c4 mref; do
   rm -rf /tmp/lrp_$what
   if [ $what = c4 ]; then extra="--no-mref"; else extra="--no-c4"; fi
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/lrp_$what -- python3 $R/bench.py --steps 4 --warmup 4 --no-cpu-baseline --no-c3 --no-c5 $extra --k1-min-launches 0 > /tmp/lrp_$what.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/lrp_$what -- python3 $R/bench.py --full --steps 4 --warmup 4 --no-cpu-baseline --no-c3 --no-c5 $extra --k1-min-launches 0 > /tmp/lrp_$what.log 2>&1
   echo "== $what"
   tail -1 /tmp/lrp_$what.log | python3 -c "
 import json,sys

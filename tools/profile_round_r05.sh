@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/profile_$tag
 mkdir -p $out
-B="--no-cpu-baseline --no-c4 --no-c3 --no-c5 --no-mref"
+B="--full --no-cpu-baseline --no-c4 --no-c3 --no-c5 --no-mref"
 for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 $B > $out/bench_driver_cmd_$i.json 2> $out/bench_driver_cmd_$i.err; done
 python3 bench.py $B > $out/bench_long.json 2> $out/bench_long.err
 (cd /tmp && rm -rf /tmp/prof_stats && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 $R/bench.py --steps 200 --warmup 300 $B > $out/bench_under_rocprof.log 2>&1)
@@ -67,7 +67,7 @@ done
 cp $(find /tmp/c5prof -name "*kernel_stats.csv" | head -1) $out/c5_kernel_stats.csv
 (cd /tmp && rm -rf /tmp/mr && BDF_RESERVE_CUS=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/mr -- python3 $R/tools/mref_probe.py > $out/mref_prof.txt 2>&1)
 cp $(find /tmp/mr -name "*kernel_stats.csv" | head -1) $out/mref_kernel_stats.csv
-(cd /tmp && rm -rf /tmp/c4prof && BDF_RESERVE_CUS=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c4prof -- python3 $R/bench.py --steps 4 --warmup 4 --no-cpu-baseline --no-c3 --no-c5 --no-mref --no-c4-uniform --k1-min-launches 0 > $out/c4_prof.txt 2>&1)
+(cd /tmp && rm -rf /tmp/c4prof && BDF_RESERVE_CUS=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c4prof -- python3 $R/bench.py --full --steps 4 --warmup 4 --no-cpu-baseline --no-c3 --no-c5 --no-mref --no-c4-uniform --k1-min-launches 0 > $out/c4_prof.txt 2>&1)
 cp $(find /tmp/c4prof -name "*kernel_stats.csv" | head -1) $out/c4_kernel_stats.csv
 python3 - <<PY
 import csv, json

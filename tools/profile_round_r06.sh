@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/profile_$tag
 mkdir -p $out
-B="--no-cpu-baseline --no-c4 --no-c3 --no-c5 --no-mref"
+B="--full --no-cpu-baseline --no-c4 --no-c3 --no-c5 --no-mref"
 for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 $B > $out/bench_driver_cmd_$i.json 2> $out/bench_driver_cmd_$i.err; done
 python3 bench.py $B > $out/bench_long.json 2> $out/bench_long.err
 (cd /tmp && rm -rf /tmp/prof_stats && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -- python3 $R/bench.py --steps 200 --warmup 300 $B > $out/bench_under_rocprof.log 2>&1)
@@ -69,7 +69,7 @@ for d in 10 30; do
   (cd /tmp && rm -rf /tmp/mr$d && MREF_D=$d BDF_RESERVE_CUS=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/mr$d -- python3 $R/tools/mref_probe.py > $out/mref_d${d}_prof.txt 2>&1)
   cp $(find /tmp/mr$d -name "*kernel_stats.csv" | head -1) $out/mref_d${d}_kernel_stats.csv
 done
-(cd /tmp && rm -rf /tmp/c4prof && BDF_RESERVE_CUS=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c4prof -- python3 $R/bench.py --steps 4 --warmup 4 --no-cpu-baseline --no-c3 --no-c5 --no-mref --no-c4-uniform --k1-min-launches 0 > $out/c4_prof.txt 2>&1)
+(cd /tmp && rm -rf /tmp/c4prof && BDF_RESERVE_CUS=0 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/c4prof -- python3 $R/bench.py --full --steps 4 --warmup 4 --no-cpu-baseline --no-c3 --no-c5 --no-mref --no-c4-uniform --k1-min-launches 0 > $out/c4_prof.txt 2>&1)
 cp $(find /tmp/c4prof -name "*kernel_stats.csv" | head -1) $out/c4_kernel_stats.csv
 python3 - <<PY
 import csv, json
@@ -102,5 +102,5 @@ if [ -f $R/bayesiandatafusion.jl_amd/csrc/variants/libbdf_cgst.so ]; then
 fi
 timeout 900 bash tools/peer_overlap_trace.sh profile_$tag > $out/peer_overlap.log 2>&1
 # ---- the driver's own command, everything in it (the line the round's BENCH record will hold)
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_full.json 2> $out/bench_driver_full.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_driver_full.json 2> $out/bench_driver_full.err
 tail -c 600 $out/bench_driver_full.json
