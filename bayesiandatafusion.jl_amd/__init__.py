@@ -33,6 +33,9 @@ def __getattr__(name):
     if name in ("Block", "sample_users_blocked"):
         import importlib
         return getattr(importlib.import_module(__name__ + ".blocked"), name)
+    if name in ("bpmf_vb", "VBModel"):
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".vb"), name)
     if name in ("GibbsEngine", "Context", "DeviceRelation", "DevicePairs", "FeatOperator"):
         import importlib
         return getattr(importlib.import_module(__name__ + ".engine"), name)

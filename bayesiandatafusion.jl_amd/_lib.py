@@ -204,6 +204,13 @@ _SIGS = {
     "bdf_gibbs_warm_device": (C.c_int, [C.c_void_p, C.c_double]),
     "bdf_synth_ratings": (C.c_int, [C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_double, C.c_double, c_i32p, c_i32p,
                                     c_dp, C.c_void_p]),
+    "bdf_vb_create": (C.c_int, [C.c_void_p, C.c_int, c_i64p, C.c_int64, C.c_void_p, C.c_int, c_dp, C.c_double, c_dp, c_dp,
+                                C.POINTER(C.c_void_p)]),
+    "bdf_vb_destroy": (C.c_int, [C.c_void_p]),
+    "bdf_vb_set_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
+    "bdf_vb_iterate": (C.c_int, [C.c_void_p, C.c_int]),
+    "bdf_vb_stats": (C.c_int, [C.c_void_p, c_dp]),
+    "bdf_vb_model": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp]),
 }
 
 _LIB = None

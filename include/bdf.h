@@ -538,6 +538,38 @@ int bdf_synth_ratings(uint64_t seed, int64_t n_rows, int64_t n_cols, int64_t k_b
                       double zipf_offset, double test_fraction, int32_t *rows_out, int32_t *cols_out,
                       double *vals_out, uint8_t *held_out);
 
+/* ---- variational BPMF (src/macau_vb.jl: bpmf_vb, VBModel) ---------------------------------------------------------
+ * The deterministic mean-field variant of BPMF on ONE two-mode relation (data.relations[1]; side information ignored, as in
+ * the reference).  One GPU, matrices only: VB on several GPUs and on tensors is out of scope.  Every row of a VB model is kept
+ * on the device as mu (D doubles) and Euu = inv(L) + mu mu' as a packed upper triangle (D (D + 1) / 2 doubles), in a record
+ * padded to whole 128-byte lines; the host's VBModel.Euu (D x D x N) is unpacked only by bdf_vb_model.  Results are the same
+ * bits from run to run (no floating-point atomics).  The two entities' records take 2 x N x D (D + 1) / 2 x 8 bytes and more:
+ * a C4-sized relation (10^7 + 10^6 rows) does not fit at D = 64. */
+typedef struct bdf_vb bdf_vb;
+/* bpmf_vb's set-up (macau_vb.jl:46-65) and two VBModel(D, N) (:20-37) with the caller's random means.  dims[2]: N_u, N_v;
+ * ids: nnz x 2 column-major 1-based (df[:,1], df[:,2]), id_bytes 4|8; values: nnz (df[:,end]); alpha: relations[1].model.alpha
+ * (fixed, never sampled).  mean_value = mean(values); values are centred and duplicate (u, v) pairs summed into one entry as
+ * sparse() does; the raw pairs are kept for the train RMSE.  mu_init_u / mu_init_v: host D x N_u / D x N_v (randn(D, N)).
+ * Errors: BDF_ERR_BOUNDS for an id outside 1..dims; BDF_ERR_ARG for D outside 1..BDF_MAX_D or when the device memory the
+ * model needs (the byte count is in bdf_last_error()) exceeds what is free. */
+int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t nnz, const void *ids, int id_bytes, const double *values,
+                  double alpha, const double *mu_init_u, const double *mu_init_v, bdf_vb **out);
+int bdf_vb_destroy(bdf_vb *vb);
+/* test_vec of relations[1] (macau_vb.jl:56-58) as pairs (borrowed, NULL: none -- the test RMSE is NaN) and the clamp of
+ * clamp!(yhat, clamp) (src/sampling.jl:108-114) for both RMSEs: clamp_lo > clamp_hi means no clamping */
+int bdf_vb_set_test(bdf_vb *vb, bdf_pairs *test, double clamp_lo, double clamp_hi);
+/* n iterations of macau_vb.jl:61-77, enqueued on the context's stream with no host round trip: update_u!(U, V),
+ * update_u!(V, U) (:103-130), update_prior!(U), update_prior!(V) (:132-140), then the test and train squared errors of
+ * clamp!(mean_value + <mu_u, mu_v>) (:73-76, :142-148).  A precision that fails to factor is reported by the next
+ * bdf_vb_stats / bdf_ctx_sync as BDF_ERR_NOTPD. */
+int bdf_vb_iterate(bdf_vb *vb, int n);
+/* waits for the stream; out[4] = {rmse, rmse_train, vecnorm(U.mu_u), vecnorm(V.mu_u)} of the last iteration (:80); rmse and
+ * rmse_train are NaN before the first iteration and rmse without test pairs */
+int bdf_vb_stats(bdf_vb *vb, double *out);
+/* host copy of a model (entity 0 = U, 1 = V), every output nullable: mu_host D x N (mu_u), Euu_host D x D x N (Euu, full),
+ * prior_host D + D x D + 2 doubles (mu_N, W_N, nu_N, b_N) */
+int bdf_vb_model(bdf_vb *vb, int entity, double *mu_host, double *Euu_host, double *prior_host);
+
 #ifdef __cplusplus
 }
 #endif

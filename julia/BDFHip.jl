@@ -5,6 +5,8 @@
 # exercised from Python (ctypes) by tests/.  Device buffers are owned through bdf_dev_alloc / bdf_h2d / bdf_d2h.
 module BDFHip
 
+using Printf
+
 const lib = get(ENV, "BDF_HIP_LIB", "libbdf_hip.so")
 
 struct BDFError <: Exception
@@ -507,6 +509,89 @@ function set_relations!(g::Gibbs, rels::Vector{GibbsRelation}; keep::Vector=Any[
     check(ccall((:bdf_gibbs_set_relations, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{GibbsRelation}), g.h, length(rels), rels))
     append!(g.keep, keep)
     nothing
+end
+
+# ---- variational BPMF (src/macau_vb.jl; bdf_vb_*) --------------------------------------------------------------------------
+"The device side of bpmf_vb: both entities' VB models of relations[1] (bdf_vb_create, macau_vb.jl:20-58)."
+mutable struct VB
+    h::Ptr{Cvoid}
+    ctx::Context
+    D::Int
+    N::Tuple{Int,Int}
+    test::Any                         # the test pairs it borrows
+    function VB(c::Context, D::Integer, ids::Matrix{Int64}, values::Vector{Float64}, dims::Vector{Int64}, alpha::Float64,
+                mu_u::Matrix{Float64}, mu_v::Matrix{Float64})
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:bdf_vb_create, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Int64}, Int64, Ptr{Cvoid}, Cint, Ptr{Float64}, Float64, Ptr{Float64}, Ptr{Float64}, Ref{Ptr{Cvoid}}),
+                    c.h, D, dims, size(ids, 1), ids, 8, values, alpha, mu_u, mu_v, out))
+        v = new(out[], c, Int(D), (Int(dims[1]), Int(dims[2])), nothing)
+        finalizer(x -> ccall((:bdf_vb_destroy, lib), Cint, (Ptr{Cvoid},), x.h), v)
+        v
+    end
+end
+"test_vec (macau_vb.jl:56-58) as DevPairs (C_NULL: none; `keep` holds them) and the clamp of clamp! (src/sampling.jl:108-114)"
+function vb_set_test!(v::VB, pairs::Ptr{Cvoid}, clamp::Vector{Float64}; keep=nothing)
+    lo, hi = isempty(clamp) ? (1.0, 0.0) : (clamp[1], clamp[2])
+    v.test = keep
+    check(ccall((:bdf_vb_set_test, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64), v.h, pairs, lo, hi))
+end
+"n iterations of macau_vb.jl:61-77 (update_u! twice, update_prior! twice, the two RMSEs), enqueued without a host round trip"
+vb_iterate!(v::VB, n::Integer) = check(ccall((:bdf_vb_iterate, lib), Cint, (Ptr{Cvoid}, Cint), v.h, n))
+"(rmse, rmse_train, vecnorm(U.mu_u), vecnorm(V.mu_u)) of the last iteration (macau_vb.jl:80); waits for the device"
+function vb_stats(v::VB)
+    out = zeros(4)
+    check(ccall((:bdf_vb_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}), v.h, out))
+    (out[1], out[2], out[3], out[4])
+end
+"host copy of entity e's model (1 = U, 2 = V): mu_u (D x N), Euu (D x D x N), mu_N, W_N, nu_N, b_N"
+function vb_model(v::VB, e::Integer)
+    D, N = v.D, v.N[e]
+    mu, Euu, prior = zeros(D, N), zeros(D, D, N), zeros(D + D * D + 2)
+    check(ccall((:bdf_vb_model, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}), v.h, e - 1, mu, Euu, prior))
+    (mu, Euu, prior[1:D], reshape(prior[D+1:D+D*D], D, D), prior[D+D*D+1], prior[D+D*D+2])
+end
+
+"""
+    bpmf_vb(data; num_latent=10, verbose=true, niter=100, clamp=Float64[])
+
+Replaces `bpmf_vb` (src/macau_vb.jl:39-90): the same set-up (VBModel draws its means with randn, U first), the iterations on
+the device, and the reference's Dict of host VBModels.  The VBModel type is the reference's.
+"""
+function bpmf_vb(data; num_latent::Int=10, verbose::Bool=true, niter::Int=100, clamp::Vector{Float64}=Float64[], device::Integer=0)
+    rel = data.relations[1]
+    size(rel.data.df, 2) == 3 || throw(ArgumentError("bpmf_vb works on a matrix relation (2 modes)"))
+    1 <= num_latent <= 64 || throw(ArgumentError("num_latent must be in 1..64"))
+    Umodel = Main.BayesianDataFusion.VBModel(num_latent, data.entities[1].count)
+    Vmodel = Main.BayesianDataFusion.VBModel(num_latent, data.entities[2].count)
+    alpha = rel.model.alpha
+    result = Dict("Umodel" => Umodel, "Vmodel" => Vmodel, "rmse" => NaN, "rmse_train" => NaN, "alpha" => alpha)
+    niter > 0 || return result
+    df = rel.data.df
+    ids = hcat(convert(Vector{Int64}, df[:, 1]), convert(Vector{Int64}, df[:, 2]))
+    c = Context(device)
+    v = VB(c, num_latent, ids, convert(Vector{Float64}, df[:, 3]), Int64[size(Umodel.mu_u, 2), size(Vmodel.mu_u, 2)],
+           alpha, Umodel.mu_u, Vmodel.mu_u)
+    tv = rel.test_vec
+    if size(tv, 1) > 0
+        tids = hcat(convert(Vector{Int64}, tv[:, 1]), convert(Vector{Int64}, tv[:, 2]))
+        test = DevPairs(c, tids, convert(Vector{Float64}, tv[:, 3]))
+        vb_set_test!(v, test.h, clamp; keep=test)
+    else
+        vb_set_test!(v, C_NULL, clamp)
+    end
+    st = (NaN, NaN, 0.0, 0.0)
+    for i in 1:(verbose ? niter : 1)
+        time0 = time()
+        vb_iterate!(v, verbose ? 1 : niter)
+        st = vb_stats(v)
+        verbose && @printf("% 3d: |U|=%.4e  |V|=%.4e  RMSE=%.4f  RMSE(train)=%.4f  [took %.2fs]\n", i, st[3], st[4], st[1], st[2], time() - time0)
+    end
+    for (e, m) in ((1, Umodel), (2, Vmodel))
+        m.mu_u, m.Euu, m.mu_N, m.W_N, m.nu_N, m.b_N = vb_model(v, e)
+    end
+    result["rmse"], result["rmse_train"] = st[1], st[2]
+    result
 end
 
 end # module
