@@ -36,6 +36,9 @@ def __getattr__(name):
     if name in ("bpmf_vb", "VBModel"):
         import importlib
         return getattr(importlib.import_module(__name__ + ".vb"), name)
+    if name in ("macau_hmc", "HMCModel"):
+        import importlib
+        return getattr(importlib.import_module(__name__ + ".hmc"), name)
     if name in ("GibbsEngine", "Context", "DeviceRelation", "DevicePairs", "FeatOperator"):
         import importlib
         return getattr(importlib.import_module(__name__ + ".engine"), name)

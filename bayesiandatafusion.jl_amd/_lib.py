@@ -15,6 +15,7 @@ BDF_MAX_TERMS = 4
 BDF_MAX_D = 64
 
 P_ROW, P_BETA_E1, P_BETA_E2, P_NW_NORMAL, P_GAMMA_N, P_GAMMA_U, P_NW_MEAN, P_BETA_REL1, P_BETA_REL2 = 1, 2, 3, 4, 5, 6, 7, 8, 9
+P_HMC_MOMENTUM, P_HMC_ACCEPT = 10, 11
 
 
 class ArgumentError(ValueError):
@@ -211,6 +212,14 @@ _SIGS = {
     "bdf_vb_iterate": (C.c_int, [C.c_void_p, C.c_int]),
     "bdf_vb_stats": (C.c_int, [C.c_void_p, c_dp]),
     "bdf_vb_model": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp]),
+    "bdf_hmc_create": (C.c_int, [C.c_void_p, C.c_int, c_i64p, C.c_int64, C.c_void_p, C.c_int, c_dp, C.c_double,
+                                 C.POINTER(C.c_void_p)]),
+    "bdf_hmc_destroy": (C.c_int, [C.c_void_p]),
+    "bdf_hmc_set_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double]),
+    "bdf_hmc_set_params": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]),
+    "bdf_hmc_iterate": (C.c_int, [C.c_void_p, C.c_int]),
+    "bdf_hmc_stats": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int]),
+    "bdf_hmc_model": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp]),
 }
 
 _LIB = None

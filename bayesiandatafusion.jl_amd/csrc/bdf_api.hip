@@ -268,6 +268,10 @@ extern "C" int bdf_ctx_sync(bdf_ctx *ctx)
             bdf_set_error("row sampler: a split row's pieces did not all arrive in time (flag %d)", flag);
             return BDF_ERR_HIP;
         }
+        if (flag & 32) {
+            bdf_set_error("macau_hmc: an energy of the Hamiltonian was not finite (flag %d)", flag);
+            return BDF_ERR_NOTPD;
+        }
         // bits: 1 a row's P_i, 2 the Normal-Wishart draw, 4 Lambda of the beta noise, 8 FF + lambda I of the direct solve
         bdf_set_error("a matrix that must be positive definite was not (flag %d: %s%s%s%s)", flag, flag & 1 ? "row system " : "",
                       flag & 2 ? "hyperprior " : "", flag & 4 ? "noise precision " : "", flag & 8 ? "FF + lambda I" : "");

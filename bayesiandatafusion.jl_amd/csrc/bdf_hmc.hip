@@ -1,0 +1,334 @@
+// bdf_hmc.hip -- C ABI of Hamiltonian Monte Carlo BPMF (src/macau_hmc.jl): the host-side set-up that macau_hmc does in
+// Julia (reset!, the mean, centring, sparse() with its summed duplicates for both modes, HMCModel's mass) and the iteration
+// loop, enqueued on the context's stream.  The kernels are in k_hmc.hip; the prior reuses bdf_hyper_sums / bdf_hyper_sample.
+#include "hmc.h"
+#include <algorithm>
+#include <cmath>
+#include <numeric>
+
+#define HMC_MAX_L (1 << 20)        // the adaptation ceil(1.6 L) is uncapped in the reference; past this the launches' partial
+                                   // sums alone would take gigabytes
+
+struct bdf_hmc {
+    bdf_ctx *ctx;
+    int D;
+    int64_t N[2], nnz, nb[2];
+    double mean_value, alpha;
+    double *sample[2], *mom[2], *start[2], *G[2], *mu[2], *Lambda[2], *mu0[2], *WI[2], *sumU[2], *UUt[2];
+    int64_t *rowptr[2]; int32_t *colidx[2]; double *vals[2], *cs[2]; int32_t *order[2];
+    double *partial; int partial_L;        // room for the launches of an iteration with L <= partial_L
+    double *rec; double *rec_host; int rec_L;
+    hipEvent_t decided; bool pending;      // the record of the last iteration is on its way to rec_host
+    bdf_pairs *test; double clamp_lo, clamp_hi; double *avg, *tpart; int64_t tnb;
+    int L, L_inner, prior_freq, burnin; double eps;
+    int64_t iters;
+};
+
+namespace {
+
+void hmc_free(bdf_hmc *h)
+{
+    for (int e = 0; e < 2; e++) {
+        void *p[] = {h->sample[e], h->mom[e], h->start[e], h->G[e], h->mu[e], h->Lambda[e], h->mu0[e], h->WI[e], h->sumU[e],
+                     h->UUt[e], h->rowptr[e], h->colidx[e], h->vals[e], h->cs[e], h->order[e]};
+        for (void *q : p) if (q) hipFree(q);
+    }
+    if (h->partial) hipFree(h->partial);
+    if (h->rec) hipFree(h->rec);
+    if (h->rec_host) hipHostFree(h->rec_host);
+    if (h->avg) hipFree(h->avg);
+    if (h->tpart) hipFree(h->tpart);
+    if (h->decided) hipEventDestroy(h->decided);
+    delete h;
+}
+
+template <typename T>
+int upload(T **dst, const std::vector<T> &src)
+{
+    BDF_HIP(hipMalloc((void **)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
+    if (!src.empty()) BDF_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return BDF_OK;
+}
+
+size_t partial_bytes(const bdf_hmc *h, int L) { return (size_t)((L + 1) * h->nb[0] + L * h->nb[1]) * HMC_PW * 8; }
+size_t rec_bytes(int L) { return (size_t)(HMC_REC_LOG + 2 * L + 1) * 8; }
+
+// room for an iteration with this L (the previous iteration's kernels are done: its decision has been read)
+int hmc_reserve(bdf_hmc *h, int L)
+{
+    if (L > h->partial_L) {
+        if (h->partial) { BDF_HIP(hipFree(h->partial)); h->partial = nullptr; h->partial_L = 0; }
+        BDF_HIP(hipMalloc((void **)&h->partial, partial_bytes(h, L)));
+        h->partial_L = L;
+    }
+    if (L > h->rec_L) {
+        double *rec = nullptr, *host = nullptr;
+        BDF_HIP(hipMalloc((void **)&rec, rec_bytes(L)));
+        BDF_HIP(hipMemset(rec, 0, rec_bytes(L)));
+        BDF_HIP(hipHostMalloc((void **)&host, rec_bytes(L), hipHostMallocDefault));
+        if (h->rec_host) memcpy(host, h->rec_host, rec_bytes(h->rec_L));
+        else memset(host, 0, rec_bytes(L));
+        if (h->rec) hipFree(h->rec);
+        if (h->rec_host) hipHostFree(h->rec_host);
+        h->rec = rec; h->rec_host = host; h->rec_L = L;
+    }
+    return BDF_OK;
+}
+
+// the decision of the last iteration: its eps and L become the next iteration's
+int hmc_settle(bdf_hmc *h)
+{
+    if (!h->pending) return BDF_OK;
+    BDF_HIP(hipEventSynchronize(h->decided));
+    h->pending = false;
+    h->eps = h->rec_host[HMC_REC_EPS_NEW];
+    const double L = h->rec_host[HMC_REC_L_NEW];
+    BDF_REQUIRE(L >= 1.0 && L <= (double)HMC_MAX_L, BDF_ERR_ARG,
+                "bdf_hmc_iterate: the adapted number of leapfrog steps L = %.0f exceeds %d (eps = %.3e)", L, HMC_MAX_L, h->eps);
+    h->L = (int)L;
+    return BDF_OK;
+}
+
+}  // namespace
+
+extern "C" int bdf_hmc_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t nnz, const void *ids, int id_bytes,
+                              const double *values, double alpha, bdf_hmc **out)
+{
+    BDF_REQUIRE(ctx && dims && out, BDF_ERR_ARG, "bdf_hmc_create: NULL argument");
+    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_hmc_create: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
+    BDF_REQUIRE(id_bytes == 4 || id_bytes == 8, BDF_ERR_ARG, "bdf_hmc_create: id_bytes must be 4 or 8");
+    BDF_REQUIRE(nnz >= 1 && ids && values, BDF_ERR_ARG, "bdf_hmc_create: the relation has no observations");
+    BDF_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[0] < 0x7fffffff && dims[1] < 0x7fffffff, BDF_ERR_ARG,
+                "bdf_hmc_create: entity sizes %lld, %lld", (long long)dims[0], (long long)dims[1]);
+    BDF_HIP(hipSetDevice(ctx->device));
+    int64_t nb[2];
+    for (int e = 0; e < 2; e++) nb[e] = hmc_row_blocks(D, dims[e]);
+
+    // ---- device-memory budget, before anything is allocated (the partial sums for the default L = 10)
+    size_t need = 0;
+    for (int e = 0; e < 2; e++)
+        need += (size_t)dims[e] * D * 3 * 8 + (size_t)(dims[e] + 1) * 8 + (size_t)dims[e] * 4 + (size_t)(4 * D * D + 5 * D) * 8 +
+                (size_t)nb[e] * 11 * HMC_PW * 8;
+    need += (size_t)nnz * 2 * (4 + 3 * 8);
+    size_t mem_free = 0, mem_total = 0;
+    BDF_HIP(hipMemGetInfo(&mem_free, &mem_total));
+    BDF_REQUIRE(need <= mem_free, BDF_ERR_ARG, "bdf_hmc_create: the model needs %zu bytes of device memory, %zu are free", need,
+                mem_free);
+
+    // ---- ids, mean, centred values (macau_hmc.jl:41-46)
+    std::vector<int32_t> id[2];
+    for (int m = 0; m < 2; m++) {
+        id[m].resize(nnz);
+        for (int64_t k = 0; k < nnz; k++) {
+            const int64_t v = id_bytes == 8 ? ((const int64_t *)ids)[m * nnz + k] : (int64_t)((const int32_t *)ids)[m * nnz + k];
+            BDF_REQUIRE(v >= 1 && v <= dims[m], BDF_ERR_BOUNDS, "bdf_hmc_create: id %lld of mode %d outside 1..%lld", (long long)v,
+                        m + 1, (long long)dims[m]);
+            id[m][k] = (int32_t)(v - 1);
+        }
+    }
+    double sum = 0.0;
+    for (int64_t k = 0; k < nnz; k++) sum += values[k];
+    const double mean = sum / (double)nnz;
+
+    bdf_hmc *h = new bdf_hmc();
+    memset((void *)h, 0, sizeof(*h));
+    struct Guard { bdf_hmc *h; ~Guard() { if (h) hmc_free(h); } } guard{h};
+    h->ctx = ctx; h->D = D; h->nnz = nnz; h->mean_value = mean; h->alpha = alpha;
+    h->clamp_lo = 1.0; h->clamp_hi = 0.0;
+    h->L = 10; h->L_inner = 1; h->prior_freq = 8; h->eps = 0.01; h->burnin = 100;
+    BDF_HIP(hipEventCreateWithFlags(&h->decided, hipEventDisableTiming));
+
+    // ---- Udata = sparse(vid, uid, val): column u holds the v's in ascending order, duplicates summed in input order; Vdata = Udata'.
+    // Beside every entry: its multiplicity c and sum(val^2), so that c d^2 - 2 d sum(val) + sum(val^2) is the energy's
+    // sum over the duplicates (d - val)^2 (computePotential does not sum them, :224-227)
+    for (int e = 0; e < 2; e++) {
+        const std::vector<int32_t> &own = id[e], &oth = id[1 - e];
+        const int64_t N = dims[e];
+        h->N[e] = N; h->nb[e] = nb[e];
+        std::vector<int64_t> perm(nnz);
+        std::iota(perm.begin(), perm.end(), 0);
+        std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) {
+            return own[a] != own[b] ? own[a] < own[b] : oth[a] < oth[b];
+        });
+        std::vector<int64_t> rowptr(N + 1, 0);
+        std::vector<int32_t> col;
+        std::vector<double> val, cs;
+        col.reserve(nnz); val.reserve(nnz); cs.reserve(2 * nnz);
+        for (int64_t q = 0; q < nnz; q++) {
+            const int64_t k = perm[q];
+            const double x = values[k] - mean;
+            if (q > 0 && own[perm[q - 1]] == own[k] && oth[perm[q - 1]] == oth[k]) {
+                val.back() += x;
+                cs[cs.size() - 2] += 1.0;
+                cs.back() += x * x;
+                continue;
+            }
+            col.push_back(oth[k]); val.push_back(x); cs.push_back(1.0); cs.push_back(x * x);
+            rowptr[own[k] + 1]++;
+        }
+        for (int64_t i = 0; i < N; i++) rowptr[i + 1] += rowptr[i];
+        std::vector<int32_t> order(N);
+        std::iota(order.begin(), order.end(), 0);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+            return rowptr[a + 1] - rowptr[a] > rowptr[b + 1] - rowptr[b];
+        });
+        // reset! (RelationData.jl:66-90): sample 0, mu 0, Lambda 5 I, mu0 0, WI I; HMCModel's G = repmat(diag(Lambda), 1, N)
+        std::vector<double> zeros((size_t)N * D, 0.0), zd(D, 0.0), G(D, 5.0), Lam((size_t)D * D, 0.0), WI((size_t)D * D, 0.0);
+        for (int i = 0; i < D; i++) { Lam[i * D + i] = 5.0; WI[i * D + i] = 1.0; }
+        int rc;
+        if ((rc = upload(&h->rowptr[e], rowptr)) || (rc = upload(&h->colidx[e], col)) || (rc = upload(&h->vals[e], val)) ||
+            (rc = upload(&h->cs[e], cs)) || (rc = upload(&h->order[e], order)) || (rc = upload(&h->sample[e], zeros)) ||
+            (rc = upload(&h->mom[e], zeros)) || (rc = upload(&h->start[e], zeros)) || (rc = upload(&h->G[e], G)) ||
+            (rc = upload(&h->mu[e], zd)) || (rc = upload(&h->Lambda[e], Lam)) || (rc = upload(&h->mu0[e], zd)) ||
+            (rc = upload(&h->WI[e], WI)) || (rc = upload(&h->sumU[e], zd)) || (rc = upload(&h->UUt[e], Lam)))
+            return rc;
+    }
+    int rc = hmc_reserve(h, h->L);
+    if (rc) return rc;
+    BDF_HIP(hipDeviceSynchronize());
+    guard.h = nullptr;
+    *out = h;
+    return BDF_OK;
+}
+
+extern "C" int bdf_hmc_destroy(bdf_hmc *hmc)
+{
+    if (!hmc) return BDF_OK;
+    hipSetDevice(hmc->ctx->device);
+    hipStreamSynchronize(hmc->ctx->stream);
+    hmc_free(hmc);
+    return BDF_OK;
+}
+
+extern "C" int bdf_hmc_set_test(bdf_hmc *hmc, bdf_pairs *test, double clamp_lo, double clamp_hi)
+{
+    BDF_REQUIRE(hmc, BDF_ERR_ARG, "bdf_hmc_set_test: hmc is NULL");
+    BDF_REQUIRE(!test || test->n_modes == 2, BDF_ERR_ARG, "bdf_hmc_set_test: the test pairs must have two modes");
+    BDF_REQUIRE(hmc->iters == 0, BDF_ERR_ARG, "bdf_hmc_set_test: call before the first iteration");
+    BDF_HIP(hipSetDevice(hmc->ctx->device));
+    if (hmc->avg) { BDF_HIP(hipFree(hmc->avg)); hmc->avg = nullptr; }
+    if (hmc->tpart) { BDF_HIP(hipFree(hmc->tpart)); hmc->tpart = nullptr; }
+    hmc->test = test && test->n > 0 ? test : nullptr;
+    hmc->clamp_lo = clamp_lo; hmc->clamp_hi = clamp_hi;
+    if (hmc->test) {
+        hmc->tnb = hmc_predict_blocks(test->n);
+        BDF_HIP(hipMalloc((void **)&hmc->avg, (size_t)test->n * 8));
+        BDF_HIP(hipMalloc((void **)&hmc->tpart, (size_t)hmc->tnb * 2 * 8));
+    }
+    return BDF_OK;
+}
+
+extern "C" int bdf_hmc_set_params(bdf_hmc *hmc, int L, int L_inner, int prior_freq, double eps, int burnin)
+{
+    BDF_REQUIRE(hmc, BDF_ERR_ARG, "bdf_hmc_set_params: hmc is NULL");
+    BDF_REQUIRE(L >= 1 && L <= HMC_MAX_L && L_inner >= 1 && prior_freq >= 1, BDF_ERR_ARG,
+                "bdf_hmc_set_params: L=%d, L_inner=%d and prior_freq=%d must be at least 1", L, L_inner, prior_freq);
+    BDF_REQUIRE(eps > 0.0 && std::isfinite(eps), BDF_ERR_ARG, "bdf_hmc_set_params: eps=%g must be positive and finite", eps);
+    BDF_REQUIRE(burnin >= 0, BDF_ERR_ARG, "bdf_hmc_set_params: burnin=%d must not be negative", burnin);
+    int rc = hmc_settle(hmc);
+    if (rc) return rc;
+    hmc->L = L; hmc->L_inner = L_inner; hmc->prior_freq = prior_freq; hmc->eps = eps; hmc->burnin = burnin;
+    return BDF_OK;
+}
+
+extern "C" int bdf_hmc_iterate(bdf_hmc *hmc, int n)
+{
+    BDF_REQUIRE(hmc && n >= 0, BDF_ERR_ARG, "bdf_hmc_iterate: bad argument");
+    bdf_ctx *ctx = hmc->ctx;
+    BDF_HIP(hipSetDevice(ctx->device));
+    const int D = hmc->D;
+    for (int it = 0; it < n; it++) {
+        int rc;
+        if ((rc = hmc_settle(hmc)) || (rc = hmc_reserve(hmc, hmc->L))) return rc;
+        const int L = hmc->L;
+        const int64_t i = hmc->iters + 1;
+        const uint32_t sweep = (uint32_t)i;
+        // the leapfrog (macau_hmc.jl:77-85): U(eps/2), then L times V(eps) and, but for the last, U(eps); U(eps/2).
+        // Launch s (U for even s) writes its partial sums at slot s.
+        int64_t off = 0;
+        for (int s = 0; s <= 2 * L; s++) {
+            const int e = s & 1;
+            HMCLeapArgs a;
+            a.D = D; a.L_inner = hmc->L_inner; a.tag = (uint32_t)e; a.N = hmc->N[e];
+            a.flags = (e == 0 ? HMC_DATA : 0) | (s <= 1 ? HMC_DRAW : 0) | (s >= 2 * L - 1 ? HMC_FINAL : 0);
+            a.order = hmc->order[e]; a.rowptr = hmc->rowptr[e]; a.colidx = hmc->colidx[e]; a.vals = hmc->vals[e]; a.cs = hmc->cs[e];
+            a.other = hmc->sample[1 - e]; a.sample = hmc->sample[e]; a.mom = hmc->mom[e]; a.start = hmc->start[e];
+            a.G = hmc->G[e]; a.mu = hmc->mu[e]; a.Lambda = hmc->Lambda[e];
+            a.alpha = hmc->alpha; a.eps = (s == 0 || s == 2 * L) ? hmc->eps / 2 : hmc->eps;
+            a.seed = ctx->seed; a.sweep = sweep; a.partial = hmc->partial + off;
+            if ((rc = hmc_launch_leap(ctx->stream, a))) return rc;
+            off += hmc->nb[e] * HMC_PW;
+        }
+        // dH, the Metropolis step and the adaptation (:88-105); the decision goes to the host for the next L
+        HMCAcceptArgs acc;
+        acc.partial = hmc->partial; acc.nb[0] = hmc->nb[0]; acc.nb[1] = hmc->nb[1]; acc.L = L; acc.eps = hmc->eps;
+        acc.alpha = hmc->alpha; acc.seed = ctx->seed; acc.sweep = sweep; acc.rec = hmc->rec; acc.flag = ctx->flag_dev;
+        if ((rc = hmc_launch_accept(ctx->stream, acc))) return rc;
+        BDF_HIP(hipMemcpyAsync(hmc->rec_host, hmc->rec, rec_bytes(L), hipMemcpyDeviceToHost, ctx->stream));
+        BDF_HIP(hipEventRecord(hmc->decided, ctx->stream));
+        hmc->pending = true;
+        HMCRestoreArgs rs;
+        for (int e = 0; e < 2; e++) { rs.n[e] = hmc->N[e] * D; rs.sample[e] = hmc->sample[e]; rs.start[e] = hmc->start[e]; }
+        rs.rec = hmc->rec;
+        if ((rc = hmc_launch_restore(ctx->stream, rs))) return rc;
+        // update_latent_prior!(en, true) for both entities every prior_freq-th iteration (:108-113)
+        if (i % hmc->prior_freq == 0) {
+            if ((rc = bdf_ctx_set_sweep(ctx, sweep))) return rc;
+            for (int e = 0; e < 2; e++)
+                if ((rc = bdf_hyper_sums(ctx, D, hmc->N[e], hmc->sample[e], nullptr, hmc->sumU[e], hmc->UUt[e])) ||
+                    (rc = bdf_hyper_sample(ctx, D, hmc->N[e], hmc->sumU[e], hmc->UUt[e], hmc->mu0[e], 2.0, hmc->WI[e], (double)D,
+                                           (uint32_t)e, hmc->mu[e], hmc->Lambda[e], nullptr, nullptr, nullptr)))
+                    return rc;
+        }
+        // yhat = clamp!(pred(test)), update_yhat_post! (:115-121)
+        if (hmc->test) {
+            HMCPredictArgs p;
+            p.D = D; p.n = hmc->test->n; p.ids = hmc->test->ids_dev; p.values = hmc->test->values_dev;
+            p.U = hmc->sample[0]; p.V = hmc->sample[1]; p.mean = hmc->mean_value; p.lo = hmc->clamp_lo; p.hi = hmc->clamp_hi;
+            p.copy = i <= hmc->burnin + 1; p.count = (double)(i - hmc->burnin - 1); p.avg = hmc->avg; p.partial = hmc->tpart;
+            if ((rc = hmc_launch_predict(ctx->stream, p))) return rc;
+        }
+        hmc->iters++;
+    }
+    return BDF_OK;
+}
+
+extern "C" int bdf_hmc_stats(bdf_hmc *hmc, double *out, double *log, int log_cap)
+{
+    BDF_REQUIRE(hmc && out, BDF_ERR_ARG, "bdf_hmc_stats: NULL argument");
+    BDF_HIP(hipSetDevice(hmc->ctx->device));
+    int rc = bdf_ctx_sync(hmc->ctx);
+    if (rc) return rc;
+    const double *r = hmc->rec_host;
+    for (int k = 0; k < 14; k++) out[k] = hmc->iters > 0 ? r[k] : (k <= HMC_REC_L ? 0.0 : NAN);
+    out[14] = out[15] = NAN;
+    if (hmc->iters > 0 && hmc->test) {
+        std::vector<double> part((size_t)hmc->tnb * 2);
+        BDF_HIP(hipMemcpy(part.data(), hmc->tpart, part.size() * 8, hipMemcpyDeviceToHost));
+        double s1 = 0.0, s2 = 0.0;
+        for (int64_t b = 0; b < hmc->tnb; b++) { s1 += part[2 * b]; s2 += part[2 * b + 1]; }
+        out[14] = std::sqrt(s1 / (double)hmc->test->n);
+        out[15] = std::sqrt(s2 / (double)hmc->test->n);
+    }
+    if (log) {
+        const int nlog = hmc->iters > 0 ? 2 * (int)r[HMC_REC_L] + 1 : 0;
+        for (int k = 0; k < log_cap; k++) log[k] = k < nlog ? r[HMC_REC_LOG + k] : NAN;
+    }
+    return BDF_OK;
+}
+
+extern "C" int bdf_hmc_model(bdf_hmc *hmc, int entity, double *sample, double *momentum, double *mu, double *Lambda)
+{
+    BDF_REQUIRE(hmc, BDF_ERR_ARG, "bdf_hmc_model: hmc is NULL");
+    BDF_REQUIRE(entity == 0 || entity == 1, BDF_ERR_ARG, "bdf_hmc_model: entity %d must be 0 (U) or 1 (V)", entity);
+    BDF_HIP(hipSetDevice(hmc->ctx->device));
+    int rc = bdf_ctx_sync(hmc->ctx);
+    if (rc) return rc;
+    const int D = hmc->D;
+    const size_t nd = (size_t)hmc->N[entity] * D * 8;
+    if (sample) BDF_HIP(hipMemcpy(sample, hmc->sample[entity], nd, hipMemcpyDeviceToHost));
+    if (momentum) BDF_HIP(hipMemcpy(momentum, hmc->mom[entity], nd, hipMemcpyDeviceToHost));
+    if (mu) BDF_HIP(hipMemcpy(mu, hmc->mu[entity], (size_t)D * 8, hipMemcpyDeviceToHost));
+    if (Lambda) BDF_HIP(hipMemcpy(Lambda, hmc->Lambda[entity], (size_t)D * D * 8, hipMemcpyDeviceToHost));
+    return BDF_OK;
+}

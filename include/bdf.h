@@ -51,6 +51,8 @@ extern "C" {
 #define BDF_P_NW_MEAN   7
 #define BDF_P_BETA_REL1 8   /* sample_beta_rel: noise per observation (row = observation)  */
 #define BDF_P_BETA_REL2 9   /* sample_beta_rel: noise per feature    (row = feature)        */
+#define BDF_P_HMC_MOMENTUM 10  /* macau_hmc momentum: entity 0 (U) / 1 (V), row = 0-based row, normal k = latent index */
+#define BDF_P_HMC_ACCEPT   11  /* macau_hmc Metropolis uniform: entity 0, row 0, pair 0                                */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -569,6 +571,41 @@ int bdf_vb_stats(bdf_vb *vb, double *out);
 /* host copy of a model (entity 0 = U, 1 = V), every output nullable: mu_host D x N (mu_u), Euu_host D x D x N (Euu, full),
  * prior_host D + D x D + 2 doubles (mu_N, W_N, nu_N, b_N) */
 int bdf_vb_model(bdf_vb *vb, int entity, double *mu_host, double *Euu_host, double *prior_host);
+
+/* ---- Hamiltonian Monte Carlo BPMF (src/macau_hmc.jl: macau_hmc, HMCModel) -------------------------------------------
+ * The leapfrog sampler on ONE two-mode relation (data.relations[1]; side information out of scope), one GPU.  Samples,
+ * momenta and start copies are N x D row-major on the device (the host's D x N column-major).  Iteration i draws its momenta
+ * from (BDF_P_HMC_MOMENTUM, entity 0 | 1, row, normal k), its Metropolis uniform from (BDF_P_HMC_ACCEPT, 0, 0, pair 0) and
+ * the prior from bdf_hyper_sample's streams with entity tags 0 (U) and 1 (V), all at sweep i.  Results are the same bits
+ * from run to run (no floating-point atomics). */
+typedef struct bdf_hmc bdf_hmc;
+/* macau_hmc's set-up (macau_hmc.jl:33-57) after reset!: samples 0, mu 0, Lambda 5 I, mu0 0, b0 2, WI I, nu0 D, and the mass
+ * G = diag(Lambda) = 5 (HMCModel, :13-18; it never follows Lambda).  dims[2]: N_u, N_v; ids: nnz x 2 column-major 1-based,
+ * id_bytes 4|8; values: nnz; alpha: relations[1].model.alpha (fixed).  mean_value = mean(values); values are centred; the
+ * gradient's CSRs (both modes) sum duplicate (u, v) pairs as sparse() does, and keep per entry the multiplicity and the sum of
+ * the squared values for the energy, which sums the observations one by one.  Errors as bdf_vb_create's. */
+int bdf_hmc_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t nnz, const void *ids, int id_bytes, const double *values,
+                   double alpha, bdf_hmc **out);
+int bdf_hmc_destroy(bdf_hmc *hmc);
+/* test_vec of relations[1] as pairs (borrowed, NULL: none -- the RMSEs are NaN) and the clamp: clamp_lo > clamp_hi: none.
+ * Call before the first iteration. */
+int bdf_hmc_set_test(bdf_hmc *hmc, bdf_pairs *test, double clamp_lo, double clamp_hi);
+/* the keyword arguments (L, L_inner, prior_freq >= 1, eps > 0 finite, burnin >= 0); eps and L are then adapted by the
+ * iterations (a rejection with dH < -6 halves eps and sets L = ceil(1.6 L)).  Defaults: 10, 1, 8, 0.01, 100. */
+int bdf_hmc_set_params(bdf_hmc *hmc, int L, int L_inner, int prior_freq, double eps, int burnin);
+/* n iterations of macau_hmc.jl:60-132: momenta, 2 L + 1 leapfrog launches (hmc_update_u!), the energies, the Metropolis
+ * step, the restore on rejection, update_latent_prior! every prior_freq-th iteration, and yhat = clamp!(pred(test)) with
+ * update_yhat_post!'s running mean (of the clamped predictions, as clamp! works in place).  The host needs the adapted L
+ * before it can enqueue the next leapfrog: every iteration waits for the previous one's decision (one small device-to-host
+ * copy).  A non-finite energy or a prior that fails to factor is reported by the next bdf_hmc_stats / bdf_ctx_sync. */
+int bdf_hmc_iterate(bdf_hmc *hmc, int n);
+/* waits for the stream; out[16] = the last iteration's record: {i, eps, L (both used), kinetic start, kinetic final,
+ * potential start, potential final, dH, accepted (0 | 1), new eps, new L, vecnorm(U), vecnorm(V), the uniform, rmse,
+ * rmse_avg}; all 0 / NaN before the first iteration.  log (nullable, log_cap doubles): the momentum norms after each of
+ * the 2 L + 1 launches in launch order |r_U|, |r_V|, |r_U|, ..., |r_V|, |r_U|. */
+int bdf_hmc_stats(bdf_hmc *hmc, double *out, double *log, int log_cap);
+/* host copy of an entity's state (0 = U, 1 = V), every output nullable: sample D x N, momentum D x N, mu D, Lambda D x D */
+int bdf_hmc_model(bdf_hmc *hmc, int entity, double *sample, double *momentum, double *mu, double *Lambda);
 
 #ifdef __cplusplus
 }

@@ -594,4 +594,114 @@ function bpmf_vb(data; num_latent::Int=10, verbose::Bool=true, niter::Int=100, c
     result
 end
 
+
+# ---- Hamiltonian Monte Carlo BPMF (src/macau_hmc.jl; bdf_hmc_*) -------------------------------------------------------------
+"The device side of macau_hmc: both entities' samples, momenta and priors of relations[1] after reset! (bdf_hmc_create)."
+mutable struct HMC
+    h::Ptr{Cvoid}
+    ctx::Context
+    D::Int
+    N::Tuple{Int,Int}
+    test::Any                         # the test pairs it borrows
+    function HMC(c::Context, D::Integer, ids::Matrix{Int64}, values::Vector{Float64}, dims::Vector{Int64}, alpha::Float64)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:bdf_hmc_create, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Int64}, Int64, Ptr{Cvoid}, Cint, Ptr{Float64}, Float64, Ref{Ptr{Cvoid}}),
+                    c.h, D, dims, size(ids, 1), ids, 8, values, alpha, out))
+        v = new(out[], c, Int(D), (Int(dims[1]), Int(dims[2])), nothing)
+        finalizer(x -> ccall((:bdf_hmc_destroy, lib), Cint, (Ptr{Cvoid},), x.h), v)
+        v
+    end
+end
+"test_vec (macau_hmc.jl:48-52) as DevPairs (C_NULL: none; `keep` holds them) and the clamp of clamp! (src/sampling.jl:108-114)"
+function hmc_set_test!(v::HMC, pairs::Ptr{Cvoid}, clamp::Vector{Float64}; keep=nothing)
+    lo, hi = isempty(clamp) ? (1.0, 0.0) : (clamp[1], clamp[2])
+    v.test = keep
+    check(ccall((:bdf_hmc_set_test, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64), v.h, pairs, lo, hi))
+end
+"macau_hmc's keyword arguments L, L_inner, prior_freq, eps, burnin (eps and L then adapt)"
+hmc_set_params!(v::HMC, L::Integer, L_inner::Integer, prior_freq::Integer, eps::Float64, burnin::Integer) =
+    check(ccall((:bdf_hmc_set_params, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Cint, Float64, Cint), v.h, L, L_inner, prior_freq, eps, burnin))
+"n iterations of macau_hmc.jl:60-132 (one small device-to-host read per iteration for the adapted L)"
+hmc_iterate!(v::HMC, n::Integer) = check(ccall((:bdf_hmc_iterate, lib), Cint, (Ptr{Cvoid}, Cint), v.h, n))
+"the last iteration's record (16 doubles, include/bdf.h) and its momentum-norm log (2L + 1 values); waits for the device"
+function hmc_stats(v::HMC)
+    out = zeros(16)
+    check(ccall((:bdf_hmc_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), v.h, out, C_NULL, 0))
+    log = zeros(2 * Int(out[3]) + 1)
+    check(ccall((:bdf_hmc_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Cint), v.h, out, log, length(log)))
+    (out, log)
+end
+"host copy of entity e (1 = U, 2 = V): sample (D x N), momentum (D x N), mu, Lambda"
+function hmc_model(v::HMC, e::Integer)
+    D, N = v.D, v.N[e]
+    sample, momentum, mu, Lambda = zeros(D, N), zeros(D, N), zeros(D), zeros(D, D)
+    check(ccall((:bdf_hmc_model, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                v.h, e - 1, sample, momentum, mu, Lambda))
+    (sample, momentum, mu, Lambda)
+end
+
+"""
+    macau_hmc(data; num_latent=10, verbose=true, burnin=100, psamples=100, L=10, L_inner=1, prior_freq=8, eps=0.01,
+              reset_model=true, clamp=Float64[])
+
+Replaces `macau_hmc` (src/macau_hmc.jl:20-137): the iterations on the device (from reset!), the reference's verbose lines,
+the entities' samples, mu and Lambda written back, and the reference's Dict.
+"""
+function macau_hmc(data; num_latent::Int=10, verbose::Bool=true, burnin::Int=100, psamples::Int=100, L::Int=10, L_inner::Int=1,
+                   prior_freq::Int=8, eps::Float64=0.01, reset_model=true, clamp::Vector{Float64}=Float64[], device::Integer=0)
+    rel = data.relations[1]
+    size(rel.data.df, 2) == 3 || throw(ArgumentError("macau_hmc works on a matrix relation (2 modes)"))
+    1 <= num_latent <= 64 || throw(ArgumentError("num_latent must be in 1..64"))
+    reset_model || throw(ArgumentError("macau_hmc starts from reset!: reset_model=false is not supported"))
+    verbose && println("Model setup")
+    df = rel.data.df
+    ids = hcat(convert(Vector{Int64}, df[:, 1]), convert(Vector{Int64}, df[:, 2]))
+    alpha = rel.model.alpha
+    c = Context(device)
+    v = HMC(c, num_latent, ids, convert(Vector{Float64}, df[:, 3]), Int64[data.entities[1].count, data.entities[2].count], alpha)
+    tv = rel.test_vec
+    if size(tv, 1) > 0
+        tids = hcat(convert(Vector{Int64}, tv[:, 1]), convert(Vector{Int64}, tv[:, 2]))
+        test = DevPairs(c, tids, convert(Vector{Float64}, tv[:, 3]))
+        hmc_set_test!(v, test.h, clamp; keep=test)
+    else
+        hmc_set_test!(v, C_NULL, clamp)
+    end
+    hmc_set_params!(v, L, L_inner, prior_freq, eps, burnin)
+    st = fill(NaN, 16)
+    for i in 1:(burnin + psamples)
+        time0 = time()
+        hmc_iterate!(v, 1)
+        st, lg = hmc_stats(v)
+        if verbose
+            Lu = Int(st[3])
+            i == burnin + 1 && print("================== Burnin complete ===================\n")
+            @printf("======= Step %d =======\n", i)
+            @printf("eps = %.2e\n", st[2])
+            for l in 1:Lu
+                @printf("  Momentum %d: |r_U| = %.4e, |r_V| = %.4e\n", l, lg[l < Lu ? 2l + 1 : 2l - 1], lg[2l])
+            end
+            @printf("  Momentum L: |r_U| = %.4e, |r_V| = %.4e\n", lg[2Lu + 1], lg[2Lu])
+            @printf("  ΔH = %.4e  ΔKin = %.4e  ΔPot = %.4e\n", -st[8], st[5] - st[4], st[7] - st[6])
+            if st[9] != 0
+                print("-> ACCEPTED!\n")
+            else
+                print("-> REJECTED!\n")
+                if st[8] < -6
+                    @printf("Reducing eps from %.2e to %.2e.\n", st[2], st[10])
+                    @printf("Increasing L from %d to %d.\n", Lu, Int(st[11]))
+                end
+            end
+            i % prior_freq == 0 && println("Updating priors...")
+            @printf("% 3d: |U|=%.4e  |V|=%.4e  RMSE=%.4f  RMSE(avg)=%.4f [took %.2fs]\n", i, st[12], st[13], st[15], st[16], time() - time0)
+        end
+    end
+    for e in 1:2
+        m = data.entities[e].model
+        m.sample, _, m.mu, m.Lambda = hmc_model(v, e)
+    end
+    Dict("rmse" => st[15], "rmse_train" => NaN, "alpha" => alpha)
+end
+
 end # module
