@@ -220,6 +220,10 @@ _SIGS = {
     "bdf_hmc_iterate": (C.c_int, [C.c_void_p, C.c_int]),
     "bdf_hmc_stats": (C.c_int, [C.c_void_p, c_dp, c_dp, C.c_int]),
     "bdf_hmc_model": (C.c_int, [C.c_void_p, C.c_int, c_dp, c_dp, c_dp, c_dp]),
+    "bdf_auc_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "bdf_auc_roc": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_pairs_auc": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]),
+    "bdf_norm2": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
 }
 
 _LIB = None

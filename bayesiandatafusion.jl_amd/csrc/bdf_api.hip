@@ -69,6 +69,7 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     c->cg_gen = 0;
     c->cg_bar = nullptr;
     c->rows_dispatch = nullptr;
+    c->norm_part = nullptr;
     c->scratch = nullptr;
     c->scratch2 = nullptr;
     c->scratch2_bytes = 0;
@@ -114,6 +115,7 @@ extern "C" int bdf_ctx_destroy(bdf_ctx *ctx)
     if (ctx->lr_T) hipFree(ctx->lr_T);
     if (ctx->lr_vt) hipFree(ctx->lr_vt);
     if (ctx->lr_mrows) hipFree(ctx->lr_mrows);
+    if (ctx->norm_part) hipFree(ctx->norm_part);
     if (ctx->own_stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return BDF_OK;

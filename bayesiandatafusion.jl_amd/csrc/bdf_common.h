@@ -96,6 +96,7 @@ struct bdf_ctx {
     unsigned *cg_bar;                   // the hand-over counter of the one-launch CG solve (k_cg_resident), allocated at first use
     // bdf_ctx_rows_dispatch: per entity tag {iteration number, rows by K1-lr, K1s, K1c, K1, K1's items, K1c's waves} of the latest launch
     std::map<uint32_t, std::array<int64_t, 7>> *rows_dispatch;
+    double *norm_part;                  // bdf_norm2's per-workgroup partial sums (k_auc.hip), allocated at first use
 };
 
 int bdf_scratch(bdf_ctx *ctx, size_t bytes, void **out);
@@ -156,6 +157,7 @@ struct bdf_pairs {
     int sorted_mode;              // the mode bdf_pairs_sort sorted by, -1: caller's order
     std::vector<int32_t> ids_host, orig_host;
     std::vector<double> values_host;
+    void *auc_ws;                 // bdf_pairs_auc's workspace (bdf_auc_workspace_bytes(n)), allocated at first use
 };
 
 struct bdf_feat {

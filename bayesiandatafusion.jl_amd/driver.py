@@ -6,6 +6,7 @@ cg_pids) are accepted for drop-in compatibility; the GPU replaces the worker poo
 """
 import math
 import struct
+import sys
 import time
 
 import numpy as np
@@ -17,7 +18,11 @@ from .relation_data import hasFeatures, numTest, toStr
 
 
 def AUC_ROC(Ytrue, scores):
-    """src/ROC.jl:1-11"""
+    """src/ROC.jl:1-11.  Scores in a GPU torch tensor (float64; labels a bool or uint8 tensor) are ranked on the device
+    (bdf_auc_roc, csrc/k_auc.hip) and give a float; anything else takes the host path below."""
+    if _on_gpu(scores):
+        from .engine import device_auc_roc
+        return device_auc_roc(Ytrue, scores)[0]
     Ytrue = np.asarray(Ytrue, dtype=bool)
     perm = np.argsort(scores, kind="stable")
     roc_y = Ytrue[perm]
@@ -26,6 +31,11 @@ def AUC_ROC(Ytrue, scores):
     stack_x = np.cumsum(roc_y) / roc_y.sum()
     stack_y = np.cumsum(~roc_y) / (~roc_y).sum()
     return float(np.sum((stack_x[1:] - stack_x[:-1]) * stack_y[1:]))
+
+
+def _on_gpu(x):
+    torch = sys.modules.get("torch")          # (a tensor exists only if torch is loaded: numpy callers do not import it)
+    return torch is not None and torch.is_tensor(x) and x.device.type == "cuda"
 
 
 def makeClamped(x, clamp):
@@ -76,7 +86,6 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         import torch
         yhat_full = torch.zeros(tuple(rel.data.dims), dtype=torch.float64, device=eng.ctx.device)
     rmse_avg = roc_avg = err_avg = float("nan")
-    probe_avg = None
 
     verbose and print("Sampling")
     for i in range(1, burnin + psamples + 1):
@@ -84,9 +93,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         # relation models (alpha, relation beta) first, then rows, hyperpriors, beta (macau.jl:83-140), then the reporting
         # step on the test pairs (macau.jl:142-184); without side information all of it is one native call
         phase = 0 if i <= burnin else (1 if i == burnin + 1 else 2)
-        stats = None
         if haveTest:
-            stats = eng.step(i, phase, clamp, rel.class_cut)
+            eng.step(i, phase, clamp, rel.class_cut)
         else:
             eng.sweep(i)
         facs = eng.factors_of(rel)
@@ -117,15 +125,19 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 f_output.append(f(data))
 
         if verbose or i == burnin + psamples:
+            if haveTest:
+                # roc_avg = AUC_ROC(test_label, -probe_avg) (macau.jl:200) on the device, behind this iteration's prediction update
+                # on the same stream; it lands beside the 4 stats (test.report), read back together after the one sync
+                test.auc(rel.class_cut, eng.ctx_p)
             eng.sync()
             eng.sync_host_scalars()
             if haveTest:
-                s = stats.cpu().numpy()
+                rep = test.report.cpu().numpy()
+                s = rep[:4]
                 n = numTest(rel)
                 rmse_avg = math.sqrt(s[0] / n)
                 err_avg = s[2] / n
-                probe_avg, _ = test.state()
-                roc_avg = AUC_ROC(rel.test_label, -probe_avg)
+                roc_avg = float(rep[4])
             if verbose:
                 estr = " ".join(toStr(en) for en in data.entities)
                 rstr = " ".join(toStr(r) for r in data.relations)

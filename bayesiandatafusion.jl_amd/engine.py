@@ -279,7 +279,9 @@ class DevicePairs:
         self.n, self.n_modes = ids.shape
         check(lib().bdf_pairs_create(ctx.handle, self.n_modes, self.n, ids.ctypes.data_as(C.c_void_p), 8,
                                      values.ctypes.data_as(_lib.c_dp), C.byref(self.handle)))
-        self.stats = ctx.zeros(4)
+        # the reporting step's device scalars, read back together: bdf_predict_update's 4 stats, then roc_avg (auc)
+        self.report = ctx.zeros(5)
+        self.stats = self.report[:4]
         self._order = None
         ctx.adopt(self)
 
@@ -332,6 +334,15 @@ class DevicePairs:
                                        class_cut, _ptr(self.stats)))
         return self.stats
 
+    def auc(self, class_cut, ctx=None, counts=None):
+        """roc_avg of macau.jl:200, AUC_ROC(values .< class_cut, -avg) over the running average in the caller's order
+        (bdf_pairs_auc), as a device scalar (report[4]).  ctx: the context whose stream ran the prediction update (default: the
+        pairs' own); counts: nullable int64 device tensor of 3 that receives {C, P, Nn}"""
+        ctx = ctx or self.ctx
+        check(lib().bdf_pairs_auc(ctx.handle, self.handle, float(class_cut), C.c_void_p(self.report.data_ptr() + 32),
+                                  _ptr(counts)))
+        return self.report[4]
+
     def state(self):
         """(avg, sq) as host arrays"""
         a, s, n = C.c_void_p(), C.c_void_p(), C.c_int64()
@@ -357,6 +368,38 @@ class DevicePairs:
             self.close()
         except Exception:
             pass
+
+
+_AUC_CONTEXTS = {}          # (device, stream) -> Context of device_auc_roc
+
+
+def device_auc_roc(labels, scores):
+    """AUC_ROC(labels, scores) (src/ROC.jl:1-11) of GPU tensors through bdf_auc_roc, on torch's current stream ->
+    (auc, C, P, Nn): C the exact number of (negative, positive) pairs ranked in that order, P / Nn the class sizes"""
+    if not (torch.is_tensor(scores) and scores.device.type == "cuda"):
+        raise ArgumentError("device_auc_roc: scores must be a GPU tensor")
+    dev = scores.device
+    labels = torch.as_tensor(labels, device=dev)
+    if scores.dtype != torch.float64:
+        raise ArgumentError(f"AUC_ROC: scores must be float64 on the device, not {scores.dtype}")
+    if labels.dtype not in (torch.bool, torch.uint8):
+        raise ArgumentError(f"AUC_ROC: labels must be bool or uint8 on the device, not {labels.dtype}")
+    if labels.device != dev or labels.numel() != scores.numel():
+        raise _lib.DimensionMismatch(f"AUC_ROC: {labels.numel()} labels on {labels.device} for {scores.numel()} scores on {dev}")
+    stream = torch.cuda.current_stream(dev)
+    ctx = _AUC_CONTEXTS.get((dev.index, stream.cuda_stream))
+    if ctx is None:
+        with torch.cuda.device(dev):
+            ctx = _AUC_CONTEXTS[(dev.index, stream.cuda_stream)] = Context(dev.index, stream=stream)
+    labels = labels.reshape(-1).contiguous()
+    labels = labels.view(torch.uint8) if labels.dtype == torch.bool else labels
+    scores = scores.reshape(-1).contiguous()
+    n = scores.numel()
+    ws = torch.empty(max(1, lib().bdf_auc_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+    res = torch.empty(4, dtype=torch.int64, device=dev)          # the auc's bits, then C, P, Nn: one read-back
+    check(lib().bdf_auc_roc(ctx.handle, n, _ptr(labels), _ptr(scores), _ptr(ws), _ptr(res), C.c_void_p(res.data_ptr() + 8)))
+    h = res.cpu().numpy()
+    return float(h[:1].view(np.float64)[0]), int(h[1]), int(h[2]), int(h[3])
 
 
 class FeatOperator:
@@ -519,6 +562,17 @@ class EntityState:
 
     def rotate(self):
         self.cur = (self.cur + 1) % 3
+
+    def norm(self, name):
+        """vecnorm of a device array (bdf_norm2: the squares summed in a fixed order) as a float, with no host copy of the array.
+        On the row context's stream, where the samples and beta are written."""
+        t = getattr(self, name)
+        if t is None or t.numel() == 0:
+            return 0.0
+        with torch.cuda.stream(self.ctx.stream):
+            out = torch.empty(1, dtype=torch.float64, device=self.ctx.device)
+            check(lib().bdf_norm2(self.ctx.handle, t.numel(), _ptr(t), _ptr(out)))
+            return float(out.item())
 
     def host(self, name):
         t = getattr(self, name)

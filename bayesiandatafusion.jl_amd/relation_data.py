@@ -71,9 +71,10 @@ def toStr(x):
     if isinstance(x, Entity):
         if x.model is None or x.model._dev is None:
             return x.name[:3] + "[]"
-        s = f"U:{np.linalg.norm(x.model.sample):6.2f}"
+        st = x.model._dev            # device state: the norms are reduced there (bdf_norm2), not on a host copy
+        s = f"U:{st.norm('sample'):6.2f}"
         if hasFeatures(x):
-            s += f" β:{np.linalg.norm(x.model.beta):3.2f}"
+            s += f" β:{st.norm('beta'):3.2f}"
             if x.lambda_beta_sample:
                 s += f" λ={x.lambda_beta:1.1f}"
         return f"{x.name[:3]}[{s}]"

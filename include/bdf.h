@@ -327,6 +327,24 @@ int bdf_predict_update(bdf_ctx *ctx, bdf_pairs *p, int D, const double *const *f
 /* running state: avg (dev n), sq (dev n) */
 int bdf_pairs_state(const bdf_pairs *p, double **avg, double **sq, int64_t *n);
 
+/* ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device (csrc/k_auc.hip) ------------ */
+/* bytes of the workspace bdf_auc_roc needs for n scores (-1: n < 0) */
+int64_t bdf_auc_workspace_bytes(int64_t n);
+/* AUC_ROC(labels, scores) over n scores, every pointer a device pointer: labels n bytes (nonzero = positive), scores n
+ * doubles, workspace bdf_auc_workspace_bytes(n) bytes.  The scores are sorted stably (ties keep the caller's order; -0.0 ties
+ * with +0.0; NaNs sort last and tie among themselves) and C = the number of (negative, positive) pairs with the negative sorted
+ * first, an exact integer; *auc_out = C / (P Nn) with P positives and Nn negatives, NaN when P = 0 or Nn = 0.  counts_out
+ * (nullable, 3 int64): {C, P, Nn}.  Enqueued on the context's stream; n < 2^31 - 4096. */
+int bdf_auc_roc(bdf_ctx *ctx, int64_t n, const uint8_t *labels, const double *scores, void *workspace, double *auc_out,
+                int64_t *counts_out);
+/* roc_avg of macau.jl:200: AUC_ROC(values .< class_cut, -avg) over the pairs' running average, in the caller's order (sorted
+ * pairs break ties by the caller's index).  The pairs own the workspace (allocated at first use, freed by bdf_pairs_destroy).
+ * Enqueued on ctx's stream: pass the context whose stream ran the prediction update (bdf_gibbs_contexts' pred for the native
+ * iteration) to have it ordered after that update.  auc_out (dev 1 double), counts_out as bdf_auc_roc's. */
+int bdf_pairs_auc(bdf_ctx *ctx, bdf_pairs *p, double class_cut, double *auc_out, int64_t *counts_out);
+/* *out (dev 1 double) = ||x||_2 of x (dev n doubles), the squares summed in a fixed order (bit-identical reruns) */
+int bdf_norm2(bdf_ctx *ctx, int64_t n, const double *x, double *out);
+
 /* ---- a8-a14: side information (Entity.F operator contract) ------------- */
 /* dense: F host N x numF column-major (RelationData.jl:66-90 `F`) */
 int bdf_feat_create_dense(bdf_ctx *ctx, int64_t m, int64_t n, const double *F, bdf_feat **out);

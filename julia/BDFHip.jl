@@ -465,6 +465,25 @@ function pairs_state(c::Context, p::DevPairs)
     return avg, sq
 end
 
+# ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device ------------------------------------------------------------------
+"AUC_ROC(Ytrue, scores) of device arrays (labels: UInt8, nonzero = positive): (auc, C, P, Nn), C the exact pair count"
+function auc_roc(c::Context, labels::DevArray{UInt8}, scores::DevArray{Float64})
+    n = prod(scores.dims)
+    ws = DevArray(c, zeros(UInt8, max(ccall((:bdf_auc_workspace_bytes, lib), Int64, (Int64,), n), 1)))
+    out, counts = DevArray(c, zeros(1)), DevArray(c, zeros(Int64, 3))
+    check(ccall((:bdf_auc_roc, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, n, labels.p, scores.p, ws.p, out.p, counts.p))
+    k = Array(counts)
+    (Array(out)[1], k[1], k[2], k[3])
+end
+"roc_avg of macau.jl:200, AUC_ROC(values .< class_cut, -avg), over the pairs' running mean -> out (DevArray of 1 double);
+ `c` is the context whose stream ran the prediction update"
+pairs_auc!(c::Context, p::DevPairs, class_cut, out::DevArray{Float64}) =
+    check(ccall((:bdf_pairs_auc, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}), c.h, p.h, class_cut, out.p, C_NULL))
+"vecnorm(x) of a device array, summed in a fixed order -> out (DevArray of 1 double)"
+norm2!(c::Context, x::DevArray{Float64}, out::DevArray{Float64}) =
+    check(ccall((:bdf_norm2, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}), c.h, prod(x.dims), x.p, out.p))
+
 # ---- feature operators on several ranks; the hyperprior's sums over the ranks ----------------------------------------------
 "original id (0-based) of every row of F: rows moved to an entity's internal positions keep their noise streams (several GPUs)"
 feat_set_row_ids!(f::Ptr{Cvoid}, row_ids::Vector{Int32}) = check(ccall((:bdf_feat_set_row_ids, lib), Cint, (Ptr{Cvoid}, Ptr{Int32}), f, row_ids))
