@@ -370,15 +370,6 @@ extern "C" int bdf_d2h(bdf_ctx *ctx, void *dst, const void *src, size_t bytes)
     return BDF_OK;
 }
 
-template <typename T>
-static int upload(bdf_ctx *ctx, const std::vector<T> &v, T **dptr)
-{
-    size_t bytes = std::max<size_t>(v.size() * sizeof(T), 8);
-    BDF_HIP(hipMalloc((void **)dptr, bytes));
-    if (!v.empty()) BDF_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return BDF_OK;
-}
-
 // ---- a1: IndexedDF / FastIDF ------------------------------------------------------------
 // IndexedDF.jl:10-19 pushes COO row i onto index[mode][id] in row order: a stable counting sort.
 static inline int64_t id_at(const void *ids, int id_bytes, int64_t nnz, int64_t i, int m)
@@ -427,9 +418,7 @@ extern "C" int bdf_layout_build(int64_t N, const int64_t *degree, int world, int
     const int64_t per_rank = (N + world - 1) / world;
     const int64_t cmax = std::max<int64_t>(1, (per_rank + chunks - 1) / chunks);
     BDF_REQUIRE(cmax * world * chunks < (int64_t)0x7fffffff, BDF_ERR_ARG, "bdf_layout_build: layout too large");
-    std::vector<int32_t> ord((size_t)N);
-    std::iota(ord.begin(), ord.end(), 0);
-    std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return degree[x] > degree[y]; });
+    const std::vector<int32_t> ord = rows_by_degree(N, [&](int32_t x) { return degree[x]; });
     for (int64_t s = 0; s < N; s++) {
         const int64_t p = s % world, r = s / world, c = r % chunks, i = r / chunks;
         pos_out[ord[(size_t)s]] = (int32_t)((c * world + p) * cmax + i);
@@ -497,7 +486,7 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
             code_by_row[(size_t)i] = (uint8_t)(std::lower_bound(table.begin(), table.end(), values[i]) - table.begin());
         std::vector<double> t256(256, 0.0);
         std::copy(table.begin(), table.end(), t256.begin());
-        int rct = upload(ctx, t256, &r->table_dev);
+        int rct = bdf_upload(&r->table_dev, t256);
         if (rct) return rct;
         r->n_codes = (int)table.size();
     }
@@ -516,11 +505,7 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
     for (int m = 0; m < n_modes; m++) {
         bdf_mode_index &ix = r->idx[m];
         const int64_t N = dims[m];
-        ix.order.resize((size_t)N);
-        std::iota(ix.order.begin(), ix.order.end(), 0);
-        std::stable_sort(ix.order.begin(), ix.order.end(), [&](int32_t x, int32_t y) {
-            return (ix.rowptr[(size_t)x + 1] - ix.rowptr[(size_t)x]) > (ix.rowptr[(size_t)y + 1] - ix.rowptr[(size_t)y]);
-        });
+        ix.order = rows_by_degree(N, [&](int32_t x) { return ix.rowptr[(size_t)x + 1] - ix.rowptr[(size_t)x]; });
         int rc;
         if (!sharded) {
             std::vector<int32_t> colidx((size_t)nnz * (size_t)(n_modes - 1) + 1, 0);       // (+1: the row kernel reads ids and values in pairs)
@@ -537,15 +522,15 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
                     plane++;
                 }
             }
-            if ((rc = upload(ctx, ix.rowptr, &ix.rowptr_dev))) return rc;
-            if ((rc = upload(ctx, colidx, &ix.colidx_dev))) return rc;
-            if ((rc = upload(ctx, vals, &ix.vals_dev))) return rc;
-            if ((rc = upload(ctx, perm, &ix.perm_dev))) return rc;
-            if ((rc = upload(ctx, ix.order, &ix.order_dev))) return rc;
+            if ((rc = bdf_upload(&ix.rowptr_dev, ix.rowptr))) return rc;
+            if ((rc = bdf_upload(&ix.colidx_dev, colidx))) return rc;
+            if ((rc = bdf_upload(&ix.vals_dev, vals))) return rc;
+            if ((rc = bdf_upload(&ix.perm_dev, perm))) return rc;
+            if ((rc = bdf_upload(&ix.order_dev, ix.order))) return rc;
             if (r->n_codes && r->nint[1 - m] < (1 << 24)) {
                 std::vector<uint32_t> packed((size_t)nnz + 1, 0u);          // (+1: the row kernel reads the words in pairs)
                 for (int64_t q = 0; q < nnz; q++) packed[(size_t)q] = ((uint32_t)code_by_row[(size_t)perm[(size_t)q]] << 24) | (uint32_t)colidx[(size_t)q];
-                if ((rc = upload(ctx, packed, &ix.packed_dev))) return rc;
+                if ((rc = bdf_upload(&ix.packed_dev, packed))) return rc;
             }
             ix.own_nnz = nnz;
             continue;
@@ -592,13 +577,13 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
                 }
             }
         }
-        if ((rc = upload(ctx, colidx, &ix.colidx_dev))) return rc;
-        if ((rc = upload(ctx, vals, &ix.vals_dev))) return rc;
-        if ((rc = upload(ctx, perm, &ix.perm_dev))) return rc;
+        if ((rc = bdf_upload(&ix.colidx_dev, colidx))) return rc;
+        if ((rc = bdf_upload(&ix.vals_dev, vals))) return rc;
+        if ((rc = bdf_upload(&ix.perm_dev, perm))) return rc;
         if (r->n_codes && r->nint[1 - m] < (1 << 24)) {
             std::vector<uint32_t> packed((size_t)on + 1, 0u);
             for (int64_t q = 0; q < on; q++) packed[(size_t)q] = ((uint32_t)code_by_row[(size_t)perm[(size_t)q]] << 24) | (uint32_t)colidx[(size_t)q];
-            if ((rc = upload(ctx, packed, &ix.packed_dev))) return rc;
+            if ((rc = bdf_upload(&ix.packed_dev, packed))) return rc;
         }
     }
     guard.r = nullptr;

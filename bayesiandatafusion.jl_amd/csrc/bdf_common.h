@@ -2,6 +2,8 @@
 #pragma once
 #include <map>
 #include <array>
+#include <algorithm>
+#include <numeric>
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <cstdint>
@@ -26,6 +28,25 @@ void bdf_set_error(const char *fmt, ...);
     do {                                                                                   \
         if (!(cond)) { bdf_set_error(__VA_ARGS__); return (code); }                        \
     } while (0)
+
+// a device copy of a host vector (at least 16 bytes: an empty vector still gets an address)
+template <typename T>
+int bdf_upload(T **dst, const std::vector<T> &src)
+{
+    BDF_HIP(hipMalloc((void **)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
+    if (!src.empty()) BDF_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    return BDF_OK;
+}
+
+// rows 0..N-1 by falling degree(row), rows of equal degree in row order (a stable sort)
+template <typename Degree>
+std::vector<int32_t> rows_by_degree(int64_t N, Degree degree)
+{
+    std::vector<int32_t> ord((size_t)N);
+    std::iota(ord.begin(), ord.end(), 0);
+    std::stable_sort(ord.begin(), ord.end(), [&](int32_t x, int32_t y) { return degree(x) > degree(y); });
+    return ord;
+}
 
 struct bdf_ctx {
     int device;

@@ -1,10 +1,9 @@
 // bdf_hmc.hip -- C ABI of Hamiltonian Monte Carlo BPMF (src/macau_hmc.jl): the host-side set-up that macau_hmc does in
-// Julia (reset!, the mean, centring, sparse() with its summed duplicates for both modes, HMCModel's mass) and the iteration
-// loop, enqueued on the context's stream.  The kernels are in k_hmc.hip; the prior reuses bdf_hyper_sums / bdf_hyper_sample.
+// Julia (reset!, the CSR of both modes through two_mode.hip, HMCModel's mass) and the iteration loop, enqueued on the
+// context's stream.  The kernels are in k_hmc.hip; the prior reuses bdf_hyper_sums / bdf_hyper_sample.
 #include "hmc.h"
-#include <algorithm>
+#include "two_mode.h"
 #include <cmath>
-#include <numeric>
 
 #define HMC_MAX_L (1 << 20)        // the adaptation ceil(1.6 L) is uncapped in the reference; past this the launches' partial
                                    // sums alone would take gigabytes
@@ -15,7 +14,7 @@ struct bdf_hmc {
     int64_t N[2], nnz, nb[2];
     double mean_value, alpha;
     double *sample[2], *mom[2], *start[2], *G[2], *mu[2], *Lambda[2], *mu0[2], *WI[2], *sumU[2], *UUt[2];
-    int64_t *rowptr[2]; int32_t *colidx[2]; double *vals[2], *cs[2]; int32_t *order[2];
+    TwoModeCsr csr[2];
     double *partial; int partial_L;        // room for the launches of an iteration with L <= partial_L
     double *rec; double *rec_host; int rec_L;
     hipEvent_t decided; bool pending;      // the record of the last iteration is on its way to rec_host
@@ -30,8 +29,9 @@ void hmc_free(bdf_hmc *h)
 {
     for (int e = 0; e < 2; e++) {
         void *p[] = {h->sample[e], h->mom[e], h->start[e], h->G[e], h->mu[e], h->Lambda[e], h->mu0[e], h->WI[e], h->sumU[e],
-                     h->UUt[e], h->rowptr[e], h->colidx[e], h->vals[e], h->cs[e], h->order[e]};
+                     h->UUt[e]};
         for (void *q : p) if (q) hipFree(q);
+        two_mode_free(h->csr[e]);
     }
     if (h->partial) hipFree(h->partial);
     if (h->rec) hipFree(h->rec);
@@ -40,14 +40,6 @@ void hmc_free(bdf_hmc *h)
     if (h->tpart) hipFree(h->tpart);
     if (h->decided) hipEventDestroy(h->decided);
     delete h;
-}
-
-template <typename T>
-int upload(T **dst, const std::vector<T> &src)
-{
-    BDF_HIP(hipMalloc((void **)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
-    if (!src.empty()) BDF_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return BDF_OK;
 }
 
 size_t partial_bytes(const bdf_hmc *h, int L) { return (size_t)((L + 1) * h->nb[0] + L * h->nb[1]) * HMC_PW * 8; }
@@ -95,11 +87,8 @@ extern "C" int bdf_hmc_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t 
                               const double *values, double alpha, bdf_hmc **out)
 {
     BDF_REQUIRE(ctx && dims && out, BDF_ERR_ARG, "bdf_hmc_create: NULL argument");
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_hmc_create: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    BDF_REQUIRE(id_bytes == 4 || id_bytes == 8, BDF_ERR_ARG, "bdf_hmc_create: id_bytes must be 4 or 8");
-    BDF_REQUIRE(nnz >= 1 && ids && values, BDF_ERR_ARG, "bdf_hmc_create: the relation has no observations");
-    BDF_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[0] < 0x7fffffff && dims[1] < 0x7fffffff, BDF_ERR_ARG,
-                "bdf_hmc_create: entity sizes %lld, %lld", (long long)dims[0], (long long)dims[1]);
+    int rc = two_mode_check("bdf_hmc_create", D, dims, nnz, ids, id_bytes, values);
+    if (rc) return rc;
     BDF_HIP(hipSetDevice(ctx->device));
     int64_t nb[2];
     for (int e = 0; e < 2; e++) nb[e] = hmc_row_blocks(D, dims[e]);
@@ -115,76 +104,29 @@ extern "C" int bdf_hmc_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t 
     BDF_REQUIRE(need <= mem_free, BDF_ERR_ARG, "bdf_hmc_create: the model needs %zu bytes of device memory, %zu are free", need,
                 mem_free);
 
-    // ---- ids, mean, centred values (macau_hmc.jl:41-46)
-    std::vector<int32_t> id[2];
-    for (int m = 0; m < 2; m++) {
-        id[m].resize(nnz);
-        for (int64_t k = 0; k < nnz; k++) {
-            const int64_t v = id_bytes == 8 ? ((const int64_t *)ids)[m * nnz + k] : (int64_t)((const int32_t *)ids)[m * nnz + k];
-            BDF_REQUIRE(v >= 1 && v <= dims[m], BDF_ERR_BOUNDS, "bdf_hmc_create: id %lld of mode %d outside 1..%lld", (long long)v,
-                        m + 1, (long long)dims[m]);
-            id[m][k] = (int32_t)(v - 1);
-        }
-    }
-    double sum = 0.0;
-    for (int64_t k = 0; k < nnz; k++) sum += values[k];
-    const double mean = sum / (double)nnz;
-
     bdf_hmc *h = new bdf_hmc();
     memset((void *)h, 0, sizeof(*h));
     struct Guard { bdf_hmc *h; ~Guard() { if (h) hmc_free(h); } } guard{h};
-    h->ctx = ctx; h->D = D; h->nnz = nnz; h->mean_value = mean; h->alpha = alpha;
+    h->ctx = ctx; h->D = D; h->nnz = nnz; h->alpha = alpha;
     h->clamp_lo = 1.0; h->clamp_hi = 0.0;
     h->L = 10; h->L_inner = 1; h->prior_freq = 8; h->eps = 0.01; h->burnin = 100;
     BDF_HIP(hipEventCreateWithFlags(&h->decided, hipEventDisableTiming));
+    // the CSR with each entry's multiplicity and sum of squares: the energy's data term over duplicates
+    if ((rc = two_mode_build("bdf_hmc_create", dims, nnz, ids, id_bytes, values, true, h->csr, &h->mean_value))) return rc;
 
-    // ---- Udata = sparse(vid, uid, val): column u holds the v's in ascending order, duplicates summed in input order; Vdata = Udata'.
-    // Beside every entry: its multiplicity c and sum(val^2), so that c d^2 - 2 d sum(val) + sum(val^2) is the energy's
-    // sum over the duplicates (d - val)^2 (computePotential does not sum them, :224-227)
     for (int e = 0; e < 2; e++) {
-        const std::vector<int32_t> &own = id[e], &oth = id[1 - e];
         const int64_t N = dims[e];
         h->N[e] = N; h->nb[e] = nb[e];
-        std::vector<int64_t> perm(nnz);
-        std::iota(perm.begin(), perm.end(), 0);
-        std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) {
-            return own[a] != own[b] ? own[a] < own[b] : oth[a] < oth[b];
-        });
-        std::vector<int64_t> rowptr(N + 1, 0);
-        std::vector<int32_t> col;
-        std::vector<double> val, cs;
-        col.reserve(nnz); val.reserve(nnz); cs.reserve(2 * nnz);
-        for (int64_t q = 0; q < nnz; q++) {
-            const int64_t k = perm[q];
-            const double x = values[k] - mean;
-            if (q > 0 && own[perm[q - 1]] == own[k] && oth[perm[q - 1]] == oth[k]) {
-                val.back() += x;
-                cs[cs.size() - 2] += 1.0;
-                cs.back() += x * x;
-                continue;
-            }
-            col.push_back(oth[k]); val.push_back(x); cs.push_back(1.0); cs.push_back(x * x);
-            rowptr[own[k] + 1]++;
-        }
-        for (int64_t i = 0; i < N; i++) rowptr[i + 1] += rowptr[i];
-        std::vector<int32_t> order(N);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-            return rowptr[a + 1] - rowptr[a] > rowptr[b + 1] - rowptr[b];
-        });
         // reset! (RelationData.jl:66-90): sample 0, mu 0, Lambda 5 I, mu0 0, WI I; HMCModel's G = repmat(diag(Lambda), 1, N)
         std::vector<double> zeros((size_t)N * D, 0.0), zd(D, 0.0), G(D, 5.0), Lam((size_t)D * D, 0.0), WI((size_t)D * D, 0.0);
         for (int i = 0; i < D; i++) { Lam[i * D + i] = 5.0; WI[i * D + i] = 1.0; }
-        int rc;
-        if ((rc = upload(&h->rowptr[e], rowptr)) || (rc = upload(&h->colidx[e], col)) || (rc = upload(&h->vals[e], val)) ||
-            (rc = upload(&h->cs[e], cs)) || (rc = upload(&h->order[e], order)) || (rc = upload(&h->sample[e], zeros)) ||
-            (rc = upload(&h->mom[e], zeros)) || (rc = upload(&h->start[e], zeros)) || (rc = upload(&h->G[e], G)) ||
-            (rc = upload(&h->mu[e], zd)) || (rc = upload(&h->Lambda[e], Lam)) || (rc = upload(&h->mu0[e], zd)) ||
-            (rc = upload(&h->WI[e], WI)) || (rc = upload(&h->sumU[e], zd)) || (rc = upload(&h->UUt[e], Lam)))
+        if ((rc = bdf_upload(&h->sample[e], zeros)) || (rc = bdf_upload(&h->mom[e], zeros)) || (rc = bdf_upload(&h->start[e], zeros)) ||
+            (rc = bdf_upload(&h->G[e], G)) || (rc = bdf_upload(&h->mu[e], zd)) || (rc = bdf_upload(&h->Lambda[e], Lam)) ||
+            (rc = bdf_upload(&h->mu0[e], zd)) || (rc = bdf_upload(&h->WI[e], WI)) || (rc = bdf_upload(&h->sumU[e], zd)) ||
+            (rc = bdf_upload(&h->UUt[e], Lam)))
             return rc;
     }
-    int rc = hmc_reserve(h, h->L);
-    if (rc) return rc;
+    if ((rc = hmc_reserve(h, h->L))) return rc;
     BDF_HIP(hipDeviceSynchronize());
     guard.h = nullptr;
     *out = h;
@@ -251,7 +193,8 @@ extern "C" int bdf_hmc_iterate(bdf_hmc *hmc, int n)
             HMCLeapArgs a;
             a.D = D; a.L_inner = hmc->L_inner; a.tag = (uint32_t)e; a.N = hmc->N[e];
             a.flags = (e == 0 ? HMC_DATA : 0) | (s <= 1 ? HMC_DRAW : 0) | (s >= 2 * L - 1 ? HMC_FINAL : 0);
-            a.order = hmc->order[e]; a.rowptr = hmc->rowptr[e]; a.colidx = hmc->colidx[e]; a.vals = hmc->vals[e]; a.cs = hmc->cs[e];
+            a.order = hmc->csr[e].order; a.rowptr = hmc->csr[e].rowptr; a.colidx = hmc->csr[e].colidx; a.vals = hmc->csr[e].vals;
+            a.cs = hmc->csr[e].cs;
             a.other = hmc->sample[1 - e]; a.sample = hmc->sample[e]; a.mom = hmc->mom[e]; a.start = hmc->start[e];
             a.G = hmc->G[e]; a.mu = hmc->mu[e]; a.Lambda = hmc->Lambda[e];
             a.alpha = hmc->alpha; a.eps = (s == 0 || s == 2 * L) ? hmc->eps / 2 : hmc->eps;

@@ -1,10 +1,9 @@
-// bdf_vb.hip -- C ABI of variational BPMF (src/macau_vb.jl): the host-side set-up that bpmf_vb does in Julia (mean, centring,
-// sparse() with its summed duplicates, the CSR of both modes, VBModel's initial state) and the iteration loop, enqueued on the
-// context's stream.  The kernels are in k_vb.hip.
+// bdf_vb.hip -- C ABI of variational BPMF (src/macau_vb.jl): the host-side set-up that bpmf_vb does in Julia (the CSR of both
+// modes through two_mode.hip, VBModel's initial state) and the iteration loop, enqueued on the context's stream.  The kernels
+// are in k_vb.hip.
 #include "vb.h"
-#include <algorithm>
+#include "two_mode.h"
 #include <cmath>
-#include <numeric>
 
 struct bdf_vb {
     bdf_ctx *ctx;
@@ -13,7 +12,7 @@ struct bdf_vb {
     double mean_value, alpha;
     double nu_N[2], b_N[2], b_0[2];
     double *rec[2], *mu[2], *pack[2], *W_N[2], *mu_N[2], *mu0[2], *Winv0[2];
-    int64_t *rowptr[2]; int32_t *colidx[2]; double *vals[2]; int32_t *order[2];
+    TwoModeCsr csr[2];
     double *partial[2]; int64_t nblocks[2];
     double *slices;
     double *stats;                 // dev: [0..4) test statistics, [4..8) train statistics, [8] |U|^2, [9] |V|^2
@@ -27,22 +26,14 @@ namespace {
 void vb_free(bdf_vb *v)
 {
     for (int e = 0; e < 2; e++) {
-        void *p[] = {v->rec[e], v->mu[e], v->pack[e], v->W_N[e], v->mu_N[e], v->mu0[e], v->Winv0[e], v->rowptr[e], v->colidx[e],
-                     v->vals[e], v->order[e], v->partial[e]};
+        void *p[] = {v->rec[e], v->mu[e], v->pack[e], v->W_N[e], v->mu_N[e], v->mu0[e], v->Winv0[e], v->partial[e]};
         for (void *q : p) if (q) hipFree(q);
+        two_mode_free(v->csr[e]);
     }
     if (v->slices) hipFree(v->slices);
     if (v->stats) hipFree(v->stats);
     if (v->train) bdf_pairs_destroy(v->train);
     delete v;
-}
-
-template <typename T>
-int upload(T **dst, const std::vector<T> &src)
-{
-    BDF_HIP(hipMalloc((void **)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
-    if (!src.empty()) BDF_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return BDF_OK;
 }
 
 }  // namespace
@@ -51,11 +42,8 @@ extern "C" int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t n
                              const double *values, double alpha, const double *mu_init_u, const double *mu_init_v, bdf_vb **out)
 {
     BDF_REQUIRE(ctx && dims && out && mu_init_u && mu_init_v, BDF_ERR_ARG, "bdf_vb_create: NULL argument");
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_vb_create: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    BDF_REQUIRE(id_bytes == 4 || id_bytes == 8, BDF_ERR_ARG, "bdf_vb_create: id_bytes must be 4 or 8");
-    BDF_REQUIRE(nnz >= 1 && ids && values, BDF_ERR_ARG, "bdf_vb_create: the relation has no observations");
-    BDF_REQUIRE(dims[0] >= 1 && dims[1] >= 1 && dims[0] < 0x7fffffff && dims[1] < 0x7fffffff, BDF_ERR_ARG,
-                "bdf_vb_create: entity sizes %lld, %lld", (long long)dims[0], (long long)dims[1]);
+    int rc = two_mode_check("bdf_vb_create", D, dims, nnz, ids, id_bytes, values);
+    if (rc) return rc;
     BDF_HIP(hipSetDevice(ctx->device));
     const int T = vb_tri(D), RS = vb_record(D), PW = T + D + 1;
     int64_t nb[2];
@@ -73,66 +61,21 @@ extern "C" int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t n
                 "bdf_vb_create: the model needs %zu bytes of device memory (the packed second moments alone "
                 "2 x N x D(D+1)/2 x 8 = %zu), %zu are free", need, (size_t)(dims[0] + dims[1]) * T * 8, mem_free);
 
-    // ---- ids, mean, centred values (macau_vb.jl:51-55)
-    std::vector<int32_t> id[2];
-    for (int m = 0; m < 2; m++) {
-        id[m].resize(nnz);
-        for (int64_t k = 0; k < nnz; k++) {
-            const int64_t v = id_bytes == 8 ? ((const int64_t *)ids)[m * nnz + k] : (int64_t)((const int32_t *)ids)[m * nnz + k];
-            BDF_REQUIRE(v >= 1 && v <= dims[m], BDF_ERR_BOUNDS, "bdf_vb_create: id %lld of mode %d outside 1..%lld", (long long)v,
-                        m + 1, (long long)dims[m]);
-            id[m][k] = (int32_t)(v - 1);
-        }
-    }
-    double sum = 0.0;
-    for (int64_t k = 0; k < nnz; k++) sum += values[k];
-    const double mean = sum / (double)nnz;
-
     bdf_vb *v = new bdf_vb();
     memset((void *)v, 0, sizeof(*v));
     struct Guard { bdf_vb *v; ~Guard() { if (v) vb_free(v); } } guard{v};
-    v->ctx = ctx; v->D = D; v->T = T; v->RS = RS; v->PW = PW; v->nnz = nnz; v->mean_value = mean; v->alpha = alpha;
+    v->ctx = ctx; v->D = D; v->T = T; v->RS = RS; v->PW = PW; v->nnz = nnz; v->alpha = alpha;
     v->clamp_lo = 1.0; v->clamp_hi = 0.0;
+    if ((rc = two_mode_build("bdf_vb_create", dims, nnz, ids, id_bytes, values, false, v->csr, &v->mean_value))) return rc;
 
     BDF_HIP(hipMalloc((void **)&v->stats, 16 * sizeof(double)));
     BDF_HIP(hipMemset(v->stats, 0, 16 * sizeof(double)));
-
-    // ---- Udata = sparse(vid, uid, val): column u holds the v's in ascending order, duplicates summed in input order; Vdata = Udata'
     for (int e = 0; e < 2; e++) {
-        const std::vector<int32_t> &own = id[e], &oth = id[1 - e];
-        v->N[e] = dims[e];
-        std::vector<int64_t> perm(nnz);
-        std::iota(perm.begin(), perm.end(), 0);
-        std::stable_sort(perm.begin(), perm.end(), [&](int64_t a, int64_t b) {
-            return own[a] != own[b] ? own[a] < own[b] : oth[a] < oth[b];
-        });
-        std::vector<int64_t> rowptr(dims[e] + 1, 0);
-        std::vector<int32_t> col;
-        std::vector<double> val;
-        col.reserve(nnz); val.reserve(nnz);
-        for (int64_t q = 0; q < nnz; q++) {
-            const int64_t k = perm[q];
-            const double x = values[k] - mean;
-            if (q > 0 && own[perm[q - 1]] == own[k] && oth[perm[q - 1]] == oth[k]) { val.back() += x; continue; }
-            col.push_back(oth[k]); val.push_back(x);
-            rowptr[own[k] + 1]++;
-        }
-        for (int64_t i = 0; i < dims[e]; i++) rowptr[i + 1] += rowptr[i];
-        // rows by descending number of neighbours: the longest rows start first, rows of similar length share a workgroup
-        std::vector<int32_t> order(dims[e]);
-        std::iota(order.begin(), order.end(), 0);
-        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-            return rowptr[a + 1] - rowptr[a] > rowptr[b + 1] - rowptr[b];
-        });
-        int rc;
-        if ((rc = upload(&v->rowptr[e], rowptr)) || (rc = upload(&v->colidx[e], col)) || (rc = upload(&v->vals[e], val)) ||
-            (rc = upload(&v->order[e], order)))
-            return rc;
-
         // ---- VBModel(D, N) (macau_vb.jl:20-37): W_N = I / N, nu_N = D + N, mu_N = 0, b_N = 2 + N, Winv_0 = I, mu_0 = 0, b_0 = 2,
         // Euu[:,:,n] = inv(W_N) + mu_n mu_n'
         const int64_t N = dims[e];
         const double *mi = e == 0 ? mu_init_u : mu_init_v;
+        v->N[e] = N;
         v->nu_N[e] = (double)D + (double)N; v->b_N[e] = 2.0 + (double)N; v->b_0[e] = 2.0;
         const double wn = 1.0 / (double)N, winv = 1.0 / wn;
         std::vector<double> rec((size_t)N * RS, 0.0), mu(mi, mi + (size_t)N * D);
@@ -146,9 +89,9 @@ extern "C" int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t n
         }
         std::vector<double> eye((size_t)D * D, 0.0), W((size_t)D * D, 0.0), A((size_t)D * D + D, 0.0), zero(D, 0.0);
         for (int i = 0; i < D; i++) { eye[i * D + i] = 1.0; W[i * D + i] = wn; A[i * D + i] = wn * v->nu_N[e]; }
-        if ((rc = upload(&v->rec[e], rec)) || (rc = upload(&v->mu[e], mu)) || (rc = upload(&v->pack[e], A)) ||
-            (rc = upload(&v->W_N[e], W)) || (rc = upload(&v->mu_N[e], zero)) || (rc = upload(&v->mu0[e], zero)) ||
-            (rc = upload(&v->Winv0[e], eye)))
+        if ((rc = bdf_upload(&v->rec[e], rec)) || (rc = bdf_upload(&v->mu[e], mu)) || (rc = bdf_upload(&v->pack[e], A)) ||
+            (rc = bdf_upload(&v->W_N[e], W)) || (rc = bdf_upload(&v->mu_N[e], zero)) || (rc = bdf_upload(&v->mu0[e], zero)) ||
+            (rc = bdf_upload(&v->Winv0[e], eye)))
             return rc;
         v->nblocks[e] = nb[e];
         BDF_HIP(hipMalloc((void **)&v->partial[e], std::max<size_t>((size_t)nb[e] * PW * 8, 16)));
@@ -157,8 +100,7 @@ extern "C" int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t n
     BDF_HIP(hipMalloc((void **)&v->slices, (size_t)VB_SLICES * PW * 8));
 
     // ---- the raw training rows (uid, vid, value) for the train RMSE (:75-76)
-    int rc = bdf_pairs_create(ctx, 2, nnz, ids, id_bytes, values, &v->train);
-    if (rc) return rc;
+    if ((rc = bdf_pairs_create(ctx, 2, nnz, ids, id_bytes, values, &v->train))) return rc;
     BDF_HIP(hipDeviceSynchronize());
     guard.v = nullptr;
     *out = v;
@@ -194,7 +136,7 @@ extern "C" int bdf_vb_iterate(bdf_vb *vb, int n)
         for (int e = 0; e < 2; e++) {
             VBRowArgs a;
             a.D = vb->D; a.T = vb->T; a.RS = vb->RS; a.PW = vb->PW; a.N = vb->N[e];
-            a.order = vb->order[e]; a.rowptr = vb->rowptr[e]; a.colidx = vb->colidx[e]; a.vals = vb->vals[e];
+            a.order = vb->csr[e].order; a.rowptr = vb->csr[e].rowptr; a.colidx = vb->csr[e].colidx; a.vals = vb->csr[e].vals;
             a.rec_other = vb->rec[1 - e]; a.rec_out = vb->rec[e]; a.mu_out = vb->mu[e]; a.pack = vb->pack[e];
             a.alpha = vb->alpha; a.partial = vb->partial[e]; a.flag = ctx->flag_dev;
             if ((rc = vb_launch_rows(ctx->stream, a))) return rc;

@@ -1620,14 +1620,6 @@ int ensure_FF(bdf_feat *f)
     return gemm(ctx, g);
 }
 
-template <typename T>
-int upload_vec(const std::vector<T> &v, T **dptr)
-{
-    BDF_HIP(hipMalloc((void **)dptr, std::max<size_t>(v.size() * sizeof(T), 8)));
-    if (!v.empty()) BDF_HIP(hipMemcpy(*dptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return BDF_OK;
-}
-
 int create_sparse(bdf_ctx *ctx, int64_t m, int64_t n, int64_t nnz, const int32_t *rows, const int32_t *cols,
                   const double *vals, bdf_feat **out)
 {
@@ -1675,17 +1667,17 @@ int create_sparse(bdf_ctx *ctx, int64_t m, int64_t n, int64_t nnz, const int32_t
                 pp[(size_t)p * nmajor + r] = (p == P) ? e : q;
             }
         }
-        int rc2 = upload_vec(pp, dev);
+        int rc2 = bdf_upload(dev, pp);
         if (!rc2) *np_out = (int)P;
         return rc2;
     };
     build(rows, cols, m, ptr, ind, v);
-    if ((rc = upload_vec(ptr, &f->rowptr_dev)) || (rc = upload_vec(ind, &f->colind_dev))) return rc;
-    if (vals && (rc = upload_vec(v, &f->rvals_dev))) return rc;
+    if ((rc = bdf_upload(&f->rowptr_dev, ptr)) || (rc = bdf_upload(&f->colind_dev, ind))) return rc;
+    if (vals && (rc = bdf_upload(&f->rvals_dev, v))) return rc;
     if ((rc = panels(m, n, &f->panel_fwd_dev, &f->n_panels_fwd))) return rc;
     build(cols, rows, n, ptr, ind, v);
-    if ((rc = upload_vec(ptr, &f->colptr_dev)) || (rc = upload_vec(ind, &f->rowind_dev))) return rc;
-    if (vals && (rc = upload_vec(v, &f->cvals_dev))) return rc;
+    if ((rc = bdf_upload(&f->colptr_dev, ptr)) || (rc = bdf_upload(&f->rowind_dev, ind))) return rc;
+    if (vals && (rc = bdf_upload(&f->cvals_dev, v))) return rc;
     if ((rc = panels(n, m, &f->panel_tr_dev, &f->n_panels_tr))) return rc;
     guard.f = nullptr;
     *out = f;

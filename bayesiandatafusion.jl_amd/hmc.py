@@ -4,13 +4,12 @@ HMCModel is the reference's host-side model (momentum and the diagonal mass G, b
 the device through the library's bdf_hmc_* entry points (csrc/bdf_hmc.hip, csrc/k_hmc.hip) and returns host copies.  One
 GPU, one two-mode relation without side information: HMC on several GPUs, on tensors or with features is out of scope.
 """
-import ctypes as C
 import math
 import time
 
 import numpy as np
 
-from . import _lib
+from . import _lib, _two_mode
 from ._lib import ArgumentError, check, lib
 from .relation_data import hasFeatures
 
@@ -32,14 +31,7 @@ class HMCModel:
 
 def _check_args(data, num_latent, L, L_inner, prior_freq, eps, burnin, psamples, reset_model, clamp):
     """every ArgumentError macau_hmc raises, before any device is touched"""
-    D = int(num_latent)
-    if not 1 <= D <= _lib.BDF_MAX_D:
-        raise ArgumentError(f"num_latent={D} must be in 1..{_lib.BDF_MAX_D}")
-    if not data.relations:
-        raise ArgumentError("macau_hmc needs a relation")
-    rel = data.relations[0]
-    if rel.data.ids.shape[1] != 2 or len(data.entities) < 2:
-        raise ArgumentError(f"macau_hmc works on a matrix relation (2 modes); {rel.name} has {rel.data.ids.shape[1]}")
+    D, rel = _two_mode.relation_of(data, num_latent, "macau_hmc")
     if any(hasFeatures(en) for en in rel.entities) or hasFeatures(rel):
         raise ArgumentError("macau_hmc does not use side information: the relation or its entities have features")
     for name, v in (("L", L), ("L_inner", L_inner), ("prior_freq", prior_freq)):
@@ -53,10 +45,7 @@ def _check_args(data, num_latent, L, L_inner, prior_freq, eps, burnin, psamples,
     if not reset_model:
         raise ArgumentError("macau_hmc starts from reset!: reset_model=false (a model carried over from an earlier run) is "
                             "not supported")
-    clamp = [float(x) for x in clamp]
-    if clamp and len(clamp) != 2:
-        raise ArgumentError("clamp must be empty or [lo, hi]")
-    return D, rel, clamp
+    return D, rel, _two_mode.clamp_bounds(clamp)
 
 
 def macau_hmc(data, num_latent=10, verbose=True, burnin=100, psamples=100, L=10, L_inner=1, prior_freq=8, eps=0.01,
@@ -68,9 +57,8 @@ def macau_hmc(data, num_latent=10, verbose=True, burnin=100, psamples=100, L=10,
     uniforms and the prior draws.  Returns the reference's {"rmse", "rmse_train" (NaN), "alpha"} and "rmse_avg", the final
     "eps" and "L", "accepted" (one bool per iteration), "Usample" / "Vsample" (D x N), "Umodel" / "Vmodel" (HMCModel) and
     "mu" / "Lambda" (one per entity)."""
-    D, rel, clamp = _check_args(data, num_latent, L, L_inner, prior_freq, eps, burnin, psamples, reset_model, clamp)
+    D, rel, (lo, hi) = _check_args(data, num_latent, L, L_inner, prior_freq, eps, burnin, psamples, reset_model, clamp)
     L, L_inner, prior_freq, burnin, psamples, eps = int(L), int(L_inner), int(prior_freq), int(burnin), int(psamples), float(eps)
-    lo, hi = (clamp[0], clamp[1]) if clamp else (1.0, 0.0)
     verbose and print("Model setup")
     N = [data.entities[0].count, data.entities[1].count]
     # reset!: Lambda = 5 I, so G = 5 everywhere
@@ -79,19 +67,8 @@ def macau_hmc(data, num_latent=10, verbose=True, burnin=100, psamples=100, L=10,
     out = {"rmse": float("nan"), "rmse_train": float("nan"), "alpha": alpha, "rmse_avg": float("nan"), "eps": eps, "L": L,
            "accepted": [], "Umodel": models[0], "Vmodel": models[1]}
 
-    from .engine import Context, DevicePairs
-    ctx = Context(device=device, seed=seed)
-    hmc = C.c_void_p()
-    test = None
-    try:
-        ids = np.asfortranarray(rel.data.ids, dtype=np.int64)
-        vals = np.ascontiguousarray(rel.data.values, dtype=np.float64)
-        dims = np.array(N, dtype=np.int64)
-        check(lib().bdf_hmc_create(ctx.handle, D, dims.ctypes.data_as(_lib.c_i64p), len(vals), ids.ctypes.data_as(C.c_void_p), 8,
-                                   vals.ctypes.data_as(_lib.c_dp), alpha, C.byref(hmc)))
-        if len(rel.test_vec) > 0:
-            test = DevicePairs(ctx, rel.test_vec.ids, rel.test_vec.values)
-        check(lib().bdf_hmc_set_test(hmc, test.handle if test is not None else None, lo, hi))
+    with _two_mode.trainer(data, D, lib().bdf_hmc_create, lib().bdf_hmc_destroy, (alpha,), seed=seed, device=device) as (hmc, test):
+        check(lib().bdf_hmc_set_test(hmc, test, lo, hi))
         check(lib().bdf_hmc_set_params(hmc, L, L_inner, prior_freq, eps, burnin))
         st = np.zeros(16)
         log = np.zeros(1)
@@ -119,12 +96,6 @@ def macau_hmc(data, num_latent=10, verbose=True, burnin=100, psamples=100, L=10,
             m.momentum = np.asfortranarray(mom.T)
             out["mu"].append(mu)
             out["Lambda"].append(np.asfortranarray(Lam.T))
-    finally:
-        if hmc:
-            lib().bdf_hmc_destroy(hmc)
-        if test is not None:
-            test.close()
-        ctx.close()
     return out
 
 

@@ -4,13 +4,12 @@ VBModel is the reference's host-side model (same field names; mu_u is D x N, Euu
 the device through the library's bdf_vb_* entry points (csrc/bdf_vb.hip, csrc/k_vb.hip) and returns host VBModels.  One GPU,
 one two-mode relation: VB on several GPUs and on tensors is out of scope.
 """
-import ctypes as C
 import time
 
 import numpy as np
 
-from . import _lib
-from ._lib import ArgumentError, check, lib
+from . import _lib, _two_mode
+from ._lib import check, lib
 
 
 class VBModel:
@@ -35,34 +34,13 @@ class VBModel:
         return "VBModel of %d instances: |mu_u|=%0.3e" % (self.mu_u.shape[1], np.linalg.norm(self.mu_u))
 
 
-def _relation_of(data, num_latent):
-    D = int(num_latent)
-    if not 1 <= D <= _lib.BDF_MAX_D:
-        raise ArgumentError(f"num_latent={D} must be in 1..{_lib.BDF_MAX_D}")
-    if not data.relations:
-        raise ArgumentError("bpmf_vb needs a relation")
-    rel = data.relations[0]
-    if rel.data.ids.shape[1] != 2 or len(data.entities) < 2:
-        raise ArgumentError(f"bpmf_vb works on a matrix relation (2 modes); {rel.name} has {rel.data.ids.shape[1]}")
-    return D, rel
-
-
-def _clamp_bounds(clamp):
-    clamp = [float(x) for x in clamp]
-    if not clamp:
-        return 1.0, 0.0                 # lo > hi: no clamping
-    if len(clamp) != 2:
-        raise ArgumentError("clamp must be empty or [lo, hi]")
-    return clamp[0], clamp[1]
-
-
 def bpmf_vb(data, num_latent=10, verbose=True, niter=100, clamp=(), seed=0, device=None):
     """bpmf_vb(data; num_latent=10, verbose=true, niter=100, clamp=Float64[]) (macau_vb.jl:39-90) on the device.
 
     Uses data.relations[0] only; its precision alpha is fixed.  The initial means are drawn with
     numpy.random.default_rng(seed), U's first.  Returns {"Umodel", "Vmodel", "rmse", "rmse_train", "alpha"}."""
-    D, rel = _relation_of(data, num_latent)
-    lo, hi = _clamp_bounds(clamp)
+    D, rel = _two_mode.relation_of(data, num_latent, "bpmf_vb")
+    lo, hi = _two_mode.clamp_bounds(clamp)
     niter = int(niter)
     rng = np.random.default_rng(seed)
     Umodel = VBModel(D, data.entities[0].count, rng)
@@ -72,22 +50,10 @@ def bpmf_vb(data, num_latent=10, verbose=True, niter=100, clamp=(), seed=0, devi
     if niter <= 0:
         return out
 
-    from .engine import Context, DevicePairs
-    ctx = Context(device=device, seed=0)
-    vb = C.c_void_p()
-    test = None
-    try:
-        ids = np.asfortranarray(rel.data.ids, dtype=np.int64)
-        vals = np.ascontiguousarray(rel.data.values, dtype=np.float64)
-        dims = np.array([Umodel.mu_u.shape[1], Vmodel.mu_u.shape[1]], dtype=np.int64)
-        mu_u = np.asfortranarray(Umodel.mu_u)
-        mu_v = np.asfortranarray(Vmodel.mu_u)
-        check(lib().bdf_vb_create(ctx.handle, D, dims.ctypes.data_as(_lib.c_i64p), len(vals), ids.ctypes.data_as(C.c_void_p), 8,
-                                  vals.ctypes.data_as(_lib.c_dp), alpha, mu_u.ctypes.data_as(_lib.c_dp),
-                                  mu_v.ctypes.data_as(_lib.c_dp), C.byref(vb)))
-        if len(rel.test_vec) > 0:
-            test = DevicePairs(ctx, rel.test_vec.ids, rel.test_vec.values)
-        check(lib().bdf_vb_set_test(vb, test.handle if test is not None else None, lo, hi))
+    mu_u, mu_v = np.asfortranarray(Umodel.mu_u), np.asfortranarray(Vmodel.mu_u)
+    extra = (alpha, mu_u.ctypes.data_as(_lib.c_dp), mu_v.ctypes.data_as(_lib.c_dp))
+    with _two_mode.trainer(data, D, lib().bdf_vb_create, lib().bdf_vb_destroy, extra, seed=0, device=device) as (vb, test):
+        check(lib().bdf_vb_set_test(vb, test, lo, hi))
         st = np.zeros(4)
         stp = st.ctypes.data_as(_lib.c_dp)
         if verbose:
@@ -113,10 +79,4 @@ def bpmf_vb(data, num_latent=10, verbose=True, niter=100, clamp=(), seed=0, devi
             m.mu_N = prior[:D].copy()
             m.W_N = np.asfortranarray(prior[D:D + D * D].reshape(D, D).T)
             m.nu_N, m.b_N = float(prior[D + D * D]), float(prior[D + D * D + 1])
-    finally:
-        if vb:
-            lib().bdf_vb_destroy(vb)
-        if test is not None:
-            test.close()
-        ctx.close()
     return out

@@ -51,24 +51,19 @@ def test_parity_with_the_restatement(B, Nu, Nv, D, eps):
 
 
 def _direct(B, rd, D, seed, phases):
-    from bdf_amd import _lib
+    from bdf_amd import _lib, _two_mode
     lib, check = _lib.lib(), _lib.check
     ctx = B.Context(seed=seed)
-    rel = rd.relations[0]
-    ids = np.asfortranarray(rel.data.ids, dtype=np.int64)
-    vals = np.ascontiguousarray(rel.data.values, dtype=np.float64)
-    dims = np.array([rd.entities[0].count, rd.entities[1].count], dtype=np.int64)
     h = C.c_void_p()
     res = []
     try:
-        check(lib.bdf_hmc_create(ctx.handle, D, dims.ctypes.data_as(_lib.c_i64p), len(vals), ids.ctypes.data_as(C.c_void_p), 8,
-                                 vals.ctypes.data_as(_lib.c_dp), rel.model.alpha, C.byref(h)))
+        check(lib.bdf_hmc_create(ctx.handle, D, *_two_mode.create_args(rd), rd.relations[0].model.alpha, C.byref(h)))
         for eps, L, n in phases:
             check(lib.bdf_hmc_set_params(h, L, 1, 1000, eps, 0))
             check(lib.bdf_hmc_iterate(h, n))
             st = np.zeros(16)
             check(lib.bdf_hmc_stats(h, st.ctypes.data_as(_lib.c_dp), None, 0))
-            S = [np.empty((n_, D)) for n_ in dims]
+            S = [np.empty((en.count, D)) for en in rd.entities[:2]]
             for e in range(2):
                 check(lib.bdf_hmc_model(h, e, S[e].ctypes.data_as(_lib.c_dp), None, None, None))
             res.append((st, S))
