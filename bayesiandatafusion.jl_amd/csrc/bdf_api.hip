@@ -45,6 +45,7 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     c->own_stream = false; c->stream = nullptr;
     struct Guard { bdf_ctx *c; ~Guard() { if (c) bdf_ctx_destroy(c); } } guard{c};        // error paths free what was allocated
     c->device = device;
+    c->n_cus = prop.multiProcessorCount;
     c->seed = seed;
     c->own_stream = false;
     c->stream = (hipStream_t)stream;          // NULL is the device's default stream
@@ -76,7 +77,7 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     c->scratch_bytes = 0;
     c->item_size = 192;
     c->piece_size = 128;
-    c->item_auto = !getenv("BDF_ITEM_FIXED");
+    c->item_auto = true;
     c->small_max = getenv("BDF_K1_SMALL") ? atoi(getenv("BDF_K1_SMALL")) : 48;
     c->small_min_rows = getenv("BDF_K1_SMALL_MIN_ROWS") ? atoll(getenv("BDF_K1_SMALL_MIN_ROWS")) : 8192;
     c->lr_max = getenv("BDF_LOWRANK") ? atoi(getenv("BDF_LOWRANK")) : -1;
@@ -171,7 +172,7 @@ extern "C" int bdf_ctx_set_item_size(bdf_ctx *ctx, int observations)
 {
     BDF_REQUIRE(ctx && (observations == 0 || (observations >= 8 && observations <= (1 << 20))), BDF_ERR_ARG, "bdf_ctx_set_item_size: 0 (automatic) or 8..2^20 observations");
     if (observations == 0) {          // the default: 192 / 128, larger for launches with hundreds of waves per resident slot
-        ctx->item_size = 192; ctx->piece_size = 128; ctx->item_auto = !getenv("BDF_ITEM_FIXED");
+        ctx->item_size = 192; ctx->piece_size = 128; ctx->item_auto = true;
         return BDF_OK;
     }
     ctx->item_size = observations;

@@ -50,6 +50,7 @@ std::vector<int32_t> rows_by_degree(int64_t N, Degree degree)
 
 struct bdf_ctx {
     int device;
+    int n_cus;                 // the device's CUs (multiProcessorCount)
     hipStream_t stream;
     bool own_stream;
     uint64_t seed;
@@ -105,7 +106,7 @@ struct bdf_ctx {
     int on_reserved;           // this context's stream runs on the reserved CUs only
     const int *skip_flag;
     volatile uint64_t *cg_status;
-    // bdf_gibbs_sweep: the next bdf_hyper_sums leaves its second stage to the bdf_hyper_sample that follows it on this context
+    // bdf_gibbs_sweep: the next bdf_hyper_sums of a small entity leaves its work to the bdf_hyper_sample that follows it on this context
     bool hyper_fuse;
     const double *hyper_partial; int hyper_nblocks; double *hyper_sumU, *hyper_UUt;
     bool hyper_chain;                   // ... and launches nothing itself: the draw's launch carries the sums' workgroups (k_hyper_chain)

@@ -182,12 +182,9 @@ int make_side_ctx(bdf_ctx *main, const std::vector<bdf_ctx *> &apart, bool reser
         c->reserve_cus = main->reserve_cus;
         c->on_reserved = (reserved && main->reserve_cus > 0) ? 1 : 0;
         bool ok = true;
-        static const bool no_test = getenv("BDF_NO_STREAM_TEST") != nullptr;
-        if (!no_test) {
-            if ((rc = streams_overlap(st, main->stream, &ok))) return rc;
-            for (bdf_ctx *o : apart)
-                if (ok && (rc = streams_overlap(st, o->stream, &ok))) return rc;
-        }
+        if ((rc = streams_overlap(st, main->stream, &ok))) return rc;
+        for (bdf_ctx *o : apart)
+            if (ok && (rc = streams_overlap(st, o->stream, &ok))) return rc;
         if (ok) {
             if (fallback) bdf_ctx_destroy(fallback);
             *out = c;
@@ -282,7 +279,7 @@ extern "C" int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const 
         if (E.d.feat) BDF_HIP(hipEventCreateWithFlags(&E.ev_beta, hipEventDisableTiming));
     }
     for (int k = 0; k < 3; k++) BDF_HIP(hipEventCreateWithFlags(&g->ev_pred[k], hipEventDisableTiming));
-    if (g->polling && !getenv("BDF_NO_COUNTER_HANDOVER")) {
+    if (g->polling) {
         const size_t bytes = (size_t)BDF_DONE_SHARDS * BDF_DONE_STRIDE * sizeof(uint32_t);
         for (int j = 0; j < n_entities; j++) {
             BDF_HIP(hipMalloc((void **)&g->ent[(size_t)j].done_dev, bytes));
@@ -624,14 +621,14 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
     // they transitively wait for still needs slots for its last workgroups.)
     // (Whether or not THIS iteration has a prediction update: an update enqueued two or more iterations ago must have
     // completed -- iterations without one rotate the buffers all the same.)
-    // How many iterations back: 3 (BDF_PRED_LAG, 1..3) -- the most the three buffers allow: iteration s overwrites the rows of
-    // iteration s - 3, which the prediction update of s - 3 read.  (Until round 3: 2.  On a quiet host there is no difference;
-    // with 3 an enqueue that takes 50 us instead of 23, or a late wake-up, no longer leaves the row stream dry.)
-    static const int pred_lag = getenv("BDF_PRED_LAG") ? std::max(1, std::min(3, atoi(getenv("BDF_PRED_LAG")))) : 3;
+    // How many iterations back: 3 -- the most the three buffers allow: iteration s overwrites the rows of iteration s - 3, which the
+    // prediction update of s - 3 read.  (Until round 3: 2.  On a quiet host there is no difference; with 3 an enqueue that takes
+    // 50 us instead of 23, or a late wake-up, no longer leaves the row stream dry.)
+    constexpr uint64_t pred_lag = 3;
     const auto t_in = std::chrono::steady_clock::now();
     for (uint64_t back = 1; back <= std::min<uint64_t>(g->n_pred, 3); back++) {
         const uint64_t k = (g->n_pred - back) % 3;
-        if (g->pred_at[k] + (uint64_t)pred_lag <= g->n_iter) {          // (and with it the earlier ones)
+        if (g->pred_at[k] + pred_lag <= g->n_iter) {          // (and with it the earlier ones)
             // a short spin on the event before the blocking wait: a thread put to sleep here wakes 10-40 us after the event,
             // and with the host one iteration ahead of the device at that moment a late wake-up plus a slow enqueue (50 us on
             // a busy host) leaves the row stream dry
@@ -648,10 +645,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
     // the data-independent part of every entity's hyperprior draw (Bartlett matrix, mean normals): inside the entity's chain
     // launch, beside its partial sums, when every entity is small enough for the one-launch chain (the hyperprior stream is
     // busy ~85 of an iteration's 90 us: a launch of its own at the head of the iteration is 7 us of that); else ahead of the rows
-    static const bool fuse_sums_ = !(getenv("BDF_HYPER_FUSE") && atoi(getenv("BDF_HYPER_FUSE")) == 0);
-    static const bool one_launch_ = !(getenv("BDF_HYPER_CHAIN") && atoi(getenv("BDF_HYPER_CHAIN")) == 0);
-    static const bool draws_ahead_ = getenv("BDF_DRAWS_AHEAD") != nullptr;
-    bool draws_in_chain = fuse_sums_ && one_launch_ && !draws_ahead_ && !g->comm;      // (several ranks: the sums are not the chain's, bdf_hyper_sums_ranks)
+    bool draws_in_chain = !g->comm;      // (several ranks: the sums are not the chain's, bdf_hyper_sums_ranks)
     for (int j = 0; j < n; j++) draws_in_chain = draws_in_chain && g->ent[(size_t)j].d.N <= 16384;
     if (!draws_in_chain && n <= BDF_DRAWS_BATCH) {
         int64_t Ns[BDF_DRAWS_BATCH]; double nus[BDF_DRAWS_BATCH]; uint32_t tags[BDF_DRAWS_BATCH]; double *outs[BDF_DRAWS_BATCH];
@@ -730,8 +724,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         E.cur = nxt;
         if (by_counter) { H->hyper_wait = E.done_dev; H->hyper_wait_target = E.done_target; }
         else BDF_HIP(hipStreamWaitEvent(H->stream, done, 0));
-        static const bool fuse_sums = !(getenv("BDF_HYPER_FUSE") && atoi(getenv("BDF_HYPER_FUSE")) == 0);
-        H->hyper_fuse = fuse_sums;        // small entities: the draw adds the sums' partials itself (one launch fewer)
+        H->hyper_fuse = true;             // small entities: the sums and the draw in one launch (k_hyper_chain)
         // side information: U = sample - uhat, T^-1 = WI + beta' beta lambda_beta with the beta of the previous iteration
         const double *Tinv = e.WI;
         if (e.feat && e.full_lambda_u) {

@@ -385,20 +385,16 @@ template <bool HASV>
 __global__ __launch_bounds__(256) void k_spmm_rm16(int64_t m, int ncol, const int64_t *__restrict__ rowptr,
                                                    const int32_t *__restrict__ colind, const double *__restrict__ vals,
                                                    const double *__restrict__ B, int64_t ldb, double *__restrict__ Y, int64_t ldy,
-                                                   const double *__restrict__ bias, double *__restrict__ Y2, const int *skip,
-                                                   const int64_t *__restrict__ pb, const int64_t *__restrict__ pe, int first)
+                                                   const double *__restrict__ bias, double *__restrict__ Y2, const int *skip)
 {
     if (skip && *skip == 0) return;
     const int l = threadIdx.x & 15;
     const int64_t r = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
     const bool rv = r < m;                       // (every lane stays: the broadcasts run over whole lane rows)
-    // pb / pe: this launch takes the row's entries [pb[r], pe[r]) -- one column panel of the operand -- and carries the row's running
-    // sums on from Y unless it is the first panel (the entries of a row in column order: the same sums in the same order as one pass)
-    const int64_t beg = rv ? (pb ? pb[r] : rowptr[r]) : 0, end = rv ? (pb ? pe[r] : rowptr[r + 1]) : 0;
+    const int64_t beg = rv ? rowptr[r] : 0, end = rv ? rowptr[r + 1] : 0;
     const int c = 2 * l;
     const bool cv = c < ncol;
     double a0 = 0.0, a1 = 0.0;
-    if (!first && rv && cv) { const spd2 y = *(const spd2 *)(Y + r * ldy + c); a0 = y[0]; a1 = y[1]; }
     // (the longest row of the wave sets the trip count: wave-uniform, the DPP instructions never sit under a divergent branch)
     int64_t nq = end - beg;
     nq = max(nq, __shfl_xor(nq, 16));
@@ -594,37 +590,25 @@ int spmm(bdf_ctx *ctx, const SpmmArgs &s)
         if (!y_rm) { Y = ty; ldy = s.ncol; }
     }
     // up to 32 columns in pairs, rows 16-byte aligned: sixteen lanes per row, sixteen gathers of 16 bytes in flight per lane
-    static const bool wide_ok = !(getenv("BDF_SPMM_WIDE") && atoi(getenv("BDF_SPMM_WIDE")) == 0);
-    const bool wide = wide_ok && s.ncol >= 2 && s.ncol <= 32 && s.ncol % 2 == 0 && ldb % 2 == 0 && ldy % 2 == 0 && ((uintptr_t)B & 15) == 0 &&
+    const bool wide = s.ncol >= 2 && s.ncol <= 32 && s.ncol % 2 == 0 && ldb % 2 == 0 && ldy % 2 == 0 && ((uintptr_t)B & 15) == 0 &&
                       ((uintptr_t)Y & 15) == 0 && (!(y_rm && s.Y2) || (((uintptr_t)s.Y2 & 15) == 0));
     if (wide) {
-        // a gathered operand of several L2 sizes: one launch per COLUMN PANEL of it (3 MiB: every XCD's L2 holds the panel its workgroups
-        // gather from, 23 TB/s of 16-byte lanes instead of the Infinity Cache's 8.6), the rows' running sums carried through Y
-        static const bool panels_ok = !(getenv("BDF_SPMM_PANELS") && atoi(getenv("BDF_SPMM_PANELS")) == 0);
-        static const int max_panels = getenv("BDF_SPMM_MAX_PANELS") ? atoi(getenv("BDF_SPMM_MAX_PANELS")) : 64;
-        const int np = (panels_ok && s.panel_ptr && s.n_panels >= 2 && s.n_panels <= max_panels &&
-                        (size_t)s.kin * s.ncol * sizeof(double) >= ((size_t)8 << 20)) ? s.n_panels : 1;
-        const dim3 grid((unsigned)((s.m + 15) / 16));
-        // ... all panels in ONE launch of a persistent grid (k_spmm_rm16p; BDF_SPMM_FUSED=0: a launch per panel, the rows' running sums
-        // carried through Y).  Measured on configuration C5 (profiles/r06_c5_fused_panels.txt, rocprofv3): F p -- 6,250 row blocks,
-        // 5 panels -- 5 x 23.7 = 118 us panel by panel, 117 fused; F't -- 3,125 row blocks, 9 panels, every panel launch 2.4
-        // generations of workgroups ending on a half-empty chip -- 9 x 15.8 = 142 us against 125-130 fused: 241 us per F'(F p)
-        // instead of 260, 1.28 GB of gathered rows per product at 10-11 TB/s (between the Infinity Cache's 8.6 and an L2-resident
-        // table's 23: the workgroups drift out of step by a panel or two).
-        static const bool fused_ok = !(getenv("BDF_SPMM_FUSED") && atoi(getenv("BDF_SPMM_FUSED")) == 0);
-        if (np > 1 && fused_ok) {
-            // the panels in one launch: a persistent grid of as many workgroups as the stream's CUs hold (k_spmm_rm16p), every one
-            // with KB row blocks' running sums in LDS (4 KB each): the smallest KB whose grid is resident at once
-            static int cus = 0;
-            if (!cus) {
-                hipDeviceProp_t prop;
-                BDF_HIP(hipGetDeviceProperties(&prop, ctx->device));
-                cus = prop.multiProcessorCount;
-            }
-            const int avail = ctx->on_reserved ? std::max(1, ctx->reserve_cus) : std::max(1, cus - ctx->reserve_cus);
+        // a gathered operand of several L2 sizes is taken by COLUMN PANEL (3 MiB: every XCD's L2 holds the panel its workgroups
+        // gather from, 23 TB/s of 16-byte lanes instead of the Infinity Cache's 8.6), all panels in ONE launch of a persistent grid
+        // (k_spmm_rm16p).  Measured on configuration C5 against a launch per panel (profiles/r06_c5_fused_panels.txt, rocprofv3; that
+        // path was retired after a70b66d): F p -- 6,250 row blocks, 5 panels -- 5 x 23.7 = 118 us panel by panel, 117 fused; F't --
+        // 3,125 row blocks, 9 panels, every panel launch 2.4 generations of workgroups ending on a half-empty chip -- 9 x 15.8 =
+        // 142 us against 125-130 fused: 241 us per F'(F p) instead of 260, 1.28 GB of gathered rows per product at 10-11 TB/s
+        // (between the Infinity Cache's 8.6 and an L2-resident table's 23: the workgroups drift out of step by a panel or two).
+        const int np = (s.panel_ptr && s.n_panels >= 2 && s.n_panels <= 64 && (size_t)s.kin * s.ncol * sizeof(double) >= ((size_t)8 << 20))
+                           ? s.n_panels : 1;
+        const double *bias = y_rm ? s.bias : nullptr;
+        double *Y2 = y_rm ? s.Y2 : nullptr;
+        if (np > 1) {
+            // a persistent grid of as many workgroups as the stream's CUs hold, every one with KB row blocks' running sums in LDS
+            // (4 KB each): the smallest KB whose grid is resident at once
+            const int avail = ctx->on_reserved ? std::max(1, ctx->reserve_cus) : std::max(1, ctx->n_cus - ctx->reserve_cus);
             const int64_t nblocks = (s.m + 15) / 16;
-            const double *bias = y_rm ? s.bias : nullptr;
-            double *Y2 = y_rm ? s.Y2 : nullptr;
             for (int64_t rb0 = 0; rb0 < nblocks;) {
                 const int64_t left = nblocks - rb0;
                 int kb = 1;
@@ -643,16 +627,12 @@ int spmm(bdf_ctx *ctx, const SpmmArgs &s)
                                         bias, Y2, ctx->skip_flag, s.panel_ptr, np, kb, rb0, nblocks);
                 rb0 += (int64_t)pg.x * kb;
             }
-        } else
-        for (int p = 0; p < np; p++) {
-            const int64_t *pb = np > 1 ? s.panel_ptr + (size_t)p * s.m : nullptr, *pe = np > 1 ? s.panel_ptr + (size_t)(p + 1) * s.m : nullptr;
-            const bool last = p == np - 1;
-            const double *bias = (last && y_rm) ? s.bias : nullptr;
-            double *Y2 = (last && y_rm) ? s.Y2 : nullptr;
+        } else {
+            const dim3 grid((unsigned)((s.m + 15) / 16));
             if (s.vals) hipLaunchKernelGGL(k_spmm_rm16<true>, grid, dim3(256), 0, ctx->stream, s.m, s.ncol, s.rowptr, s.colind, s.vals, B, ldb, Y, ldy,
-                                           bias, Y2, ctx->skip_flag, pb, pe, p == 0 ? 1 : 0);
+                                           bias, Y2, ctx->skip_flag);
             else hipLaunchKernelGGL(k_spmm_rm16<false>, grid, dim3(256), 0, ctx->stream, s.m, s.ncol, s.rowptr, s.colind, s.vals, B, ldb, Y, ldy,
-                                    bias, Y2, ctx->skip_flag, pb, pe, p == 0 ? 1 : 0);
+                                    bias, Y2, ctx->skip_flag);
         }
     } else
     hipLaunchKernelGGL(k_spmm_rm, dim3((unsigned)((s.m + 7) / 8)), dim3(256), 0, ctx->stream, s.m, s.ncol, s.rowptr, s.colind, s.vals,
@@ -814,7 +794,7 @@ struct CgState {
     double *X, *R, *P, *Z;               // n x D column-major
     double *bknum, *bkden, *tolb;        // D
     int *active, *iters, *nactive;
-    int *done_blocks;                    // columns (workgroups) that have finished the current k_cg_step
+    int *done_blocks;                    // columns (workgroups) that have finished the current step
     volatile uint64_t *status;           // host-mapped: [0] = generation << 32 | last completed iteration, [1] = active columns
     uint32_t gen;
     int *flag;                           // BDF_WARN_CG_MAXITER: a column still active after the last iteration
@@ -883,65 +863,11 @@ __global__ __launch_bounds__(1024) void k_cg_pre(CgState s, int iter)
     cg_pre(s, iter, red, go);
 }
 
-// bottom of the iteration: z = Z + lambda p; ak = bknum / (z.p); x += ak p; r -= ak z (parallel_cg.jl:85-91)
-__device__ __forceinline__ void cg_post(const CgState &s, const double *lambda_p, int iter, double *red)
-{
-    const int d = blockIdx.x;
-    if (!s.active[d] || s.iters[d] != iter) return;
-    const double lambda = *lambda_p;
-    const int64_t off = (int64_t)d * s.n;
-    double zp = 0.0;
-    for (int64_t i = threadIdx.x; i < s.n; i += blockDim.x) {
-        const double p = s.P[off + i];
-        const double z = fma(lambda, p, s.Z[off + i]);
-        s.Z[off + i] = z;
-        zp = fma(z, p, zp);
-    }
-    zp = block_sum(zp, red);
-    const double ak = s.bknum[d] / zp;
-    for (int64_t i = threadIdx.x; i < s.n; i += blockDim.x) {
-        s.X[off + i] = fma(ak, s.P[off + i], s.X[off + i]);
-        s.R[off + i] = fma(-ak, s.Z[off + i], s.R[off + i]);
-    }
-}
-
-// bottom of iteration `iter` and top of iteration `iter + 1` in one launch (a column is one workgroup in both)
-__global__ __launch_bounds__(1024) void k_cg_step(CgState s, const double *lambda_p, int iter, int maxiter)
-{
-    __shared__ double red[16];
-    __shared__ int go;
-    if (*s.nactive == 0) {                // every column has stopped: a launch the host had enqueued ahead
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            s.status[1] = 0;
-            __threadfence_system();
-            s.status[0] = ((uint64_t)s.gen << 32) | (uint32_t)iter;
-        }
-        return;
-    }
-    cg_post(s, lambda_p, iter, red);
-    __threadfence_block();
-    __syncthreads();
-    if (iter < maxiter) cg_pre(s, iter + 1, red, go);
-    else if (threadIdx.x == 0 && s.active[blockIdx.x] && s.iters[blockIdx.x] == iter) atomicOr_system(s.flag, (int)BDF_WARN_CG_MAXITER);
-    // the last column to finish reports (iteration, active columns) to the host, which enqueues ahead of the device and
-    // stops when it reads 0 active columns: no stream synchronisation inside the solve
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __threadfence();
-        if (atomicAdd(s.done_blocks, 1) == s.D - 1) {
-            *s.done_blocks = 0;
-            const int na = __hip_atomic_load(s.nactive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s.status[1] = (uint64_t)(iter < maxiter ? na : 0);
-            __threadfence_system();
-            s.status[0] = ((uint64_t)s.gen << 32) | (uint32_t)iter;
-        }
-    }
-}
-
-// k_cg_step for short columns (n <= 256 EPT): the column's p, z, x, r are read ONCE into registers, both halves of the step
-// run on them, and what changed is written once -- the general kernel walks the column four times, each walk a global-memory
-// round trip (8.6 us per iteration at n = 500, where the arithmetic is nothing).  Same operations in the same order per element;
-// the dot products are summed thread-strided as in block_sum's callers.
+// The CG step -- bottom of iteration `iter` (z = Z + lambda p; ak = bknum / (z.p); x += ak p; r -= ak z, parallel_cg.jl:85-91) and
+// top of iteration `iter + 1` in one launch, a column per workgroup -- for short columns (n <= 256 EPT): the column's p, z, x, r are
+// read ONCE into registers, both halves of the step run on them, and what changed is written once -- a general step kernel that
+// walked the column four times, each walk a global-memory round trip, took 8.6 us per iteration at n = 500, where the arithmetic is
+// nothing (it was retired after a70b66d).  The dot products are summed thread-strided as in block_sum's callers.
 template <int EPT>
 __global__ __launch_bounds__(256) void k_cg_step_short(CgState s, const double *lambda_p, int iter, int maxiter)
 {
@@ -1244,7 +1170,7 @@ extern "C" int bdf_debug_cg_stamps(unsigned long long *host512)
 }
 #endif
 
-// k_cg_step for long columns (n > 2048): one workgroup per column is one CU's bandwidth per column (82 us per iteration at
+// The CG step for long columns (n > 2048): one workgroup per column is one CU's bandwidth per column (82 us per iteration at
 // n = 50,000, D = 32: 32 CUs moving 100 MB).  Here a column is cut into G chunks, grid (D, G), and the step becomes three
 // launches with the two dot products summed over the chunks in chunk order by every workgroup that needs them:
 //   a: z = Z + lambda p, partial z.p          b: ak; x += ak p; r -= ak z; partial r.r          c: stop test; p = bk p + r
@@ -1833,26 +1759,20 @@ static int cg_solve(bdf_ctx *ctx, bdf_feat *f, bool use_ff, int D, const double 
         // workgroup per CU is what the kernel's registers and LDS allow for certain (asked of the runtime below), so the stream
         // needs that many CUs: not the reserved hyperprior stream (a handful of CUs), and the row context's CUs minus the
         // reserved ones.  (A caller-supplied CU-masked stream the library cannot see is covered by the spin bound: flag 16.)
-        static int cus = 0, occ32 = -1, occ16 = -1;
-        if (!cus) {
-            hipDeviceProp_t prop;
-            BDF_HIP(hipGetDeviceProperties(&prop, ctx->device));
-            cus = prop.multiProcessorCount;
+        static int occ32 = -1, occ16 = -1;
+        if (occ16 < 0) {
             BDF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ16, k_cg_resident<1>, 256, 0));
             BDF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ32, k_cg_resident<2>, 256, 0));
         }
-        const int avail = ctx->on_reserved ? 0 : std::max(0, cus - ctx->reserve_cus);
+        const int avail = ctx->on_reserved ? 0 : std::max(0, ctx->n_cus - ctx->reserve_cus);
         const int per_cu = std::min(1, D <= 16 ? occ16 : occ32);
         resident = (int64_t)per_cu * avail >= (numF + 15) / 16;
     }
     if (resident && !ctx->cg_bar) BDF_HIP(hipMalloc((void **)&ctx->cg_bar, sizeof(unsigned)));
     // sparse features, long columns: the state ROW-MAJOR from the first launch to the last (k_cg_rm_*): no transposes around the products
-    static const bool rm_ok = !(getenv("BDF_CG_ROWMAJOR") && atoi(getenv("BDF_CG_ROWMAJOR")) == 0);
-    static const bool long_ok_ = !(getenv("BDF_CG_LONG") && atoi(getenv("BDF_CG_LONG")) == 0);
-    const bool rm = rm_ok && long_ok_ && Xrm && !use_ff && f->kind != 0 && numF > 2048 && D <= 32;
+    const bool rm = Xrm && !use_ff && f->kind != 0 && numF > 2048 && D <= 32;
     CgRm cr;
     cr.len = 256;                                             // rows per workgroup: thirty-two per row lane (G ~ 200 at 50,000 rows: every workgroup adds G partials per column)
-    if (const char *ev = getenv("BDF_CG_RM_LEN")) { const int v = atoi(ev); if (v >= 8 && v % 8 == 0) cr.len = v; }      // A/B hook (the dots' order follows it)
     cr.G = (int)((numF + cr.len - 1) / cr.len);
     if (cr.G > BDF_CG_RM_MAXG) { cr.G = BDF_CG_RM_MAXG; cr.len = (numF + cr.G - 1) / cr.G; cr.G = (int)((numF + cr.len - 1) / cr.len); }
     cr.partA = cr.partB = cr.bkden0 = cr.zp = cr.rrs = nullptr;
@@ -1874,10 +1794,9 @@ static int cg_solve(bdf_ctx *ctx, bdf_feat *f, bool use_ff, int D, const double 
     // The host enqueues iterations AHEAD of the device (no stream synchronisation: the device never idles between
     // iterations) and reads the (iteration, active columns) word the device writes to host-mapped memory after every
     // iteration.  Run-ahead is bounded to CG_AHEAD iterations; once every column has stopped, the launches already enqueued
-    // return at once (product kernels through ctx->skip_flag, k_cg_step by itself).
+    // return at once (product kernels through ctx->skip_flag, the step kernels by themselves).
     // long columns: G chunks per column (k_cg_long_*); the partial dot products live behind the spare scalars
-    static const bool long_ok = !(getenv("BDF_CG_LONG") && atoi(getenv("BDF_CG_LONG")) == 0);
-    const bool long_cols = long_ok && numF > 2048;
+    const bool long_cols = numF > 2048;
     CgChunks ch;
     ch.G = (int)std::min<int64_t>(64, (numF + 4095) / 4096);
     ch.len = (numF + ch.G - 1) / ch.G;
@@ -1937,11 +1856,11 @@ static int cg_solve(bdf_ctx *ctx, bdf_feat *f, bool use_ff, int D, const double 
             hipLaunchKernelGGL(k_cg_rm_a, dim3(cr.G), dim3(256), 0, ctx->stream, s, cr, (const double *)lambda_beta_dev, iter);
             hipLaunchKernelGGL(k_cg_rm_b, dim3(cr.G), dim3(256), 0, ctx->stream, s, cr, iter);
             hipLaunchKernelGGL(k_cg_rm_c, dim3(cr.G), dim3(256), 0, ctx->stream, s, cr, iter, maxiter);
-        } else if (long_cols) {
+        } else {
             hipLaunchKernelGGL(k_cg_long_a, dim3(D, ch.G), dim3(256), 0, ctx->stream, s, ch, (const double *)lambda_beta_dev, iter);
             hipLaunchKernelGGL(k_cg_long_b, dim3(D, ch.G), dim3(256), 0, ctx->stream, s, ch, iter);
             hipLaunchKernelGGL(k_cg_long_c, dim3(D, ch.G), dim3(256), 0, ctx->stream, s, ch, iter, maxiter);
-        } else hipLaunchKernelGGL(k_cg_step, dim3(D), cgb, 0, ctx->stream, s, (const double *)lambda_beta_dev, iter, maxiter);
+        }
         BDF_HIP(hipGetLastError());
     }
     ctx->skip_flag = nullptr;
@@ -2208,8 +2127,7 @@ extern "C" int bdf_sample_beta_ranks(bdf_ctx *ctx, bdf_comm *comm, const bdf_fea
         // D simultaneous cg_AtA solves (solve_cg2, parallel_matrix.jl:488-507).  The operator p -> F'(F p) is applied as
         // (F'F) p when F'F is small and cheaper than the two products (numF <= 1024 and numF^2 <= nnz(F): C3's 6040 x 500
         // dense F: 2 MB read per iteration instead of 2 x 24 MB) -- the same operator, formed once per feature matrix
-        static const bool cg_ff = !(getenv("BDF_CG_FF") && atoi(getenv("BDF_CG_FF")) == 0);
-        const bool ff_op = cg_ff && numF > 0 && numF <= 1024 && numF * numF <= f->nnz;
+        const bool ff_op = numF > 0 && numF <= 1024 && numF * numF <= f->nnz;
         if (ff_op && (rc = ensure_FF(f))) return rc;
         int *cg_iters = nullptr;
         int rank = 0, world = 1;

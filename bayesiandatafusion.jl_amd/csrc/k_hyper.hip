@@ -214,17 +214,16 @@ extern "C" int bdf_hyper_sums(bdf_ctx *ctx, int D, int64_t N, const double *samp
     BDF_REQUIRE(N >= 0, BDF_ERR_ARG, "bdf_hyper_sums: N < 0");
     // HS_ROWS rows per workgroup, at most 2048 workgroups (a very large entity gives each several chunks)
     const int64_t chunks = std::max<int64_t>(1, (N + HS_ROWS - 1) / HS_ROWS);
-    // the caller enqueues the draw next and lets it add the partials (bdf_gibbs_sweep): at most 16 of them, for entities small
+    // the caller enqueues the draw next and leaves the sums to its launch (bdf_gibbs_sweep): at most 16 partials, for entities small
     // enough that 16 workgroups read them quickly
     const bool fuse = fuse_asked && N <= 16384;
-    static const bool one_launch_ = !(getenv("BDF_HYPER_CHAIN") && atoi(getenv("BDF_HYPER_CHAIN")) == 0);
     // the one-launch chain (k_hyper_chain): its workgroups -- the draws' (D^2 + D entries, 256 each), the partial sums', the last one --
     // should all be resident at once on the stream's CUs (two workgroups of 255 registers per CU), or the partial sums take two
     // rounds and the last workgroup gets its slot when the first round ends (9.3 us of the chain at D = 32).  The count comes from a
     // NOMINAL 16 slots (8 reserved CUs), not from the context's: the number of partials decides the order of the sums, and the
     // sampled values must not depend on BDF_RESERVE_CUS or the CU count (k_sample_rows.hip's rule for the rows' cuts)
     const int wg_slots = 16;
-    const int max_part = (fuse && one_launch_) ? std::max(8, std::min(16, wg_slots - 1 - (D * D + D + 255) / 256)) : 16;
+    const int max_part = fuse ? std::max(8, std::min(16, wg_slots - 1 - (D * D + D + 255) / 256)) : 16;
     const int64_t rpb = HS_ROWS * ((chunks + (fuse ? max_part - 1 : 2047)) / (fuse ? max_part : 2048));
     const int nblocks = (int)std::max<int64_t>(1, (N + rpb - 1) / rpb);
     const int DP = D <= 16 ? 16 : (D <= 32 ? 32 : 64);
@@ -233,8 +232,7 @@ extern "C" int bdf_hyper_sums(bdf_ctx *ctx, int D, int64_t N, const double *samp
     int rc = bdf_scratch(ctx, (size_t)nblocks * psz * sizeof(double), &scratch);
     if (rc) return rc;
     double *part = (double *)scratch;
-    const bool one_launch = one_launch_;
-    if (fuse && one_launch) {
+    if (fuse) {
         // left to the bdf_hyper_sample that follows: one launch for the whole chain (k_hyper_chain)
         ctx->hyper_chain = true;
         ctx->hyper_chain_D = D; ctx->hyper_chain_N = N; ctx->hyper_chain_rpb = rpb; ctx->hyper_chain_sample = sample; ctx->hyper_chain_uhat = uhat;
@@ -244,17 +242,15 @@ extern "C" int bdf_hyper_sums(bdf_ctx *ctx, int D, int64_t N, const double *samp
     const dim3 fgrid((psz + 15) / 16);
     if (DP == 16) {
         hipExtLaunchKernelGGL(k_hyper_partial<16>, dim3(nblocks), dim3(HS_THREADS), 0, ctx->stream, ctx->time_h_start, nullptr, 0, D, N, rpb, sample, uhat, part);
-        if (!fuse) hipLaunchKernelGGL(k_hyper_final<16>, fgrid, dim3(256), 0, ctx->stream, D, nblocks, (const double *)part, sumU, UUt);
+        hipLaunchKernelGGL(k_hyper_final<16>, fgrid, dim3(256), 0, ctx->stream, D, nblocks, (const double *)part, sumU, UUt);
     } else if (DP == 32) {
         hipExtLaunchKernelGGL(k_hyper_partial<32>, dim3(nblocks), dim3(HS_THREADS), 0, ctx->stream, ctx->time_h_start, nullptr, 0, D, N, rpb, sample, uhat, part);
-        if (!fuse) hipLaunchKernelGGL(k_hyper_final<32>, fgrid, dim3(256), 0, ctx->stream, D, nblocks, (const double *)part, sumU, UUt);
+        hipLaunchKernelGGL(k_hyper_final<32>, fgrid, dim3(256), 0, ctx->stream, D, nblocks, (const double *)part, sumU, UUt);
     } else {
         hipExtLaunchKernelGGL(k_hyper_partial<64>, dim3(nblocks), dim3(HS_THREADS), 0, ctx->stream, ctx->time_h_start, nullptr, 0, D, N, rpb, sample, uhat, part);
-        if (!fuse) hipLaunchKernelGGL(k_hyper_final<64>, fgrid, dim3(256), 0, ctx->stream, D, nblocks, (const double *)part, sumU, UUt);
+        hipLaunchKernelGGL(k_hyper_final<64>, fgrid, dim3(256), 0, ctx->stream, D, nblocks, (const double *)part, sumU, UUt);
     }
     ctx->time_h_start = nullptr;
-    ctx->hyper_partial = fuse ? part : nullptr;
-    ctx->hyper_nblocks = fuse ? nblocks : 0;
     ctx->hyper_sumU = sumU; ctx->hyper_UUt = UUt;
     BDF_HIP(hipGetLastError());
     return BDF_OK;
@@ -349,7 +345,7 @@ extern "C" int bdf_hyper_sample(bdf_ctx *ctx, int D, int64_t N, const double *su
 {
     BDF_REQUIRE(ctx && sumU && UUt && mu0 && Tinv && mu_out && Lambda_out, BDF_ERR_ARG, "bdf_hyper_sample: NULL argument");
     BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_hyper_sample: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    if (ctx->hyper_chain_draws && !(ctx->hyper_chain && ctx->hyper_partial)) {
+    if (ctx->hyper_chain_draws && !ctx->hyper_chain) {
         // the caller left the random part to the chain's launch, and there is no chain after all: make it now, same stream
         const int total = D * D + D;
         hipLaunchKernelGGL(k_hyper_draws, dim3((total + 63) / 64), dim3(64), 0, ctx->stream, D, nu + (double)N, ctx->seed,
@@ -377,14 +373,13 @@ extern "C" int bdf_hyper_sample(bdf_ctx *ctx, int D, int64_t N, const double *su
     a.partial = nullptr; a.nblocks = 0; a.sumU_w = a.UUt_w = nullptr;
     static const int mean_ref = getenv("BDF_HYPER_MEAN") && !strcmp(getenv("BDF_HYPER_MEAN"), "reference");
     a.mean_ref = mean_ref;
-    if (ctx->hyper_partial) {
-        // the partials of the bdf_hyper_sums call just before (same stream, fused mode): they live in the context's scratch
+    if (ctx->hyper_chain) {
+        // the sums the bdf_hyper_sums call just before left to this launch (same stream, fused mode): their partials live in the
+        // context's scratch
         BDF_REQUIRE(draws != nullptr && sumU == ctx->hyper_sumU && UUt == ctx->hyper_UUt, BDF_ERR_ARG,
                     "bdf_hyper_sample: fused sums need the draws made ahead and the sums' own output buffers");
         a.partial = ctx->hyper_partial; a.nblocks = ctx->hyper_nblocks; a.sumU_w = ctx->hyper_sumU; a.UUt_w = ctx->hyper_UUt;
         ctx->hyper_partial = nullptr;
-    }
-    if (ctx->hyper_chain && a.partial) {
         ctx->hyper_chain = false;
         if (!ctx->hyper_count) {
             BDF_HIP(hipMalloc((void **)&ctx->hyper_count, sizeof(unsigned)));

@@ -236,8 +236,7 @@ __global__ __launch_bounds__(256) void k_predict_final(int nblocks, const double
 int launch_predict(bdf_ctx *ctx, PredArgs &a)
 {
     if (a.n == 0) return BDF_OK;
-    static const bool no_runs = getenv("BDF_PREDICT_NO_RUNS") != nullptr;       // test hook: the general kernel on sorted pairs
-    if (!no_runs && a.sorted_mode >= 0 && a.n_modes == 2 && (a.D & 3) == 0 && a.D <= 32) {
+    if (a.sorted_mode >= 0 && a.n_modes == 2 && (a.D & 3) == 0 && a.D <= 32) {
         const int nblocks = (int)((a.n + 32 * RUN - 1) / (32 * RUN));
         if (a.phase >= 0) {
             void *sc;

@@ -415,7 +415,7 @@ int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T
         // round trips and the slots' sums, and as the YOUNGER wave of its SIMD -- 900 cycles per observation step against the older
         // wave's 430 -- it was the launch's tail; ranked among the heavy rounds it is dispatched first and runs as the older one:
         // users' launch alone 31.9 -> 29.9 us, movies' 33.9 -> 32.9, the iteration +2.5 %: profiles/r05_k1c_part_cost.txt)
-        static const double part_extra = getenv("BDF_COL_PART_COST") ? atof(getenv("BDF_COL_PART_COST")) : 3000.0;
+        constexpr double part_extra = 3000.0;
         R.cost = COL_C_OBS * lmax + 2 * COL_C_FOLD + (srow >= 0 ? COL_C_PART + fin_share + part_extra : COL_C_FIN);
         rounds.push_back(R);
     };
@@ -496,10 +496,10 @@ int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T
     std::vector<int32_t> rank(rounds.size());
     for (size_t i = 0; i < rank.size(); i++) rank[i] = (int32_t)i;
     std::stable_sort(rank.begin(), rank.end(), [&](int32_t x, int32_t y) { return rounds[(size_t)x].cost > rounds[(size_t)y].cost; });
-    static const int64_t S2 = getenv("BDF_COL_PAIR_DISTANCE") ? std::max<int64_t>(0, atoll(getenv("BDF_COL_PAIR_DISTANCE"))) : 896;
+    constexpr int64_t S2 = 896;
     std::vector<int32_t> idx;
     idx.reserve(rounds.size());
-    if (S2 == 0 || nw <= S2) idx = rank;                       // (0: the plain costliest-first order)
+    if (nw <= S2) idx = rank;
     else {
         const int64_t two = std::min<int64_t>(nw, 2 * S2);      // the rounds of the first two generations: ranks 0 .. two - 1
         const int64_t P = two - S2, A = S2 - P;                 // P pairs; the A heaviest alone

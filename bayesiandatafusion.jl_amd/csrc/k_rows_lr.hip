@@ -711,4 +711,4 @@ int bdf_lr_launch(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, int64_t n_
 
 int bdf_lr_max_observations() { return getenv("BDF_LR_WAVE") ? 15 : 16; }
 // ... and with the two-observations-per-lane kernel (k_rows_lr32, D > 32)
-int bdf_lr32_max_observations() { return getenv("BDF_LR_WAVE") || (getenv("BDF_LR32") && atoi(getenv("BDF_LR32")) == 0) ? 0 : 32; }
+int bdf_lr32_max_observations() { return getenv("BDF_LR_WAVE") ? 0 : 32; }

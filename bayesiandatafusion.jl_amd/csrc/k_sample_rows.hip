@@ -52,9 +52,6 @@
 #include <mutex>
 #include <utility>
 
-#ifndef BDF_CHOL_BLOCKED
-#define BDF_CHOL_BLOCKED 1        // the row's factorisation in 16-column panels: multipliers without an LDS round trip, trailing update on the matrix cores (c_layout_chol.h); 0: the plain right-looking variant
-#endif
 #ifndef BDF_K1_KS
 #define BDF_K1_KS 2               // k-steps (4 observations each) per pipelined trip, matrix relations
 #endif
@@ -79,11 +76,8 @@
 
 namespace {
 
-#ifndef BDF_K1_LOCAL64
-#define BDF_K1_LOCAL64 1          // D > 32: 8.6 KB of LDS per wave instead of 17.9 (c_layout_chol.h: GeoL)
-#endif
 template <int DP>
-struct K1Local { static constexpr bool value = (DP == 64) && BDF_K1_LOCAL64 && BDF_CHOL_BLOCKED; };
+struct K1Local { static constexpr bool value = DP == 64; };      // D > 32: 8.6 KB of LDS per wave instead of 17.9 (c_layout_chol.h: GeoL)
 
 struct Item {             // one wave's accumulation work
     int32_t row;          // entity row: where the sample is written (the row's position in the factor matrix)
@@ -441,19 +435,6 @@ __global__ __launch_bounds__(256) void k_prior(int D, int DP, int64_t nrows, con
     out_c[e * 64 + lane] = v;
 }
 
-// the sums of blocks b - 4 .. b are made before any later load is issued (a compiler fence that also pins the sums: at DP = 64 the
-// 40 or 44 loads of a prior image / a partial slot all in flight beside the 80-register matrix are the kernel's register peak)
-template <int NB>
-__device__ __forceinline__ void batch_fence(d4 (&acc)[NB], int b)
-{
-#pragma unroll
-    for (int q = 0; q < NB; q++)
-        if (q <= b && q + 5 > b) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) { double t = acc[q][r]; asm volatile("" : "+v"(t) : : "memory"); acc[q][r] = t; }
-        }
-}
-
 // ---- sum the partials of a split row in slot order (fixed order: the result does not depend on which wave does it) ---
 template <int DP>
 __device__ __forceinline__ void sum_partials(const PlanDev &p, const SplitRow &sr, int lane, d4 (&acc)[Geo<DP>::NB],
@@ -465,27 +446,6 @@ __device__ __forceinline__ void sum_partials(const PlanDev &p, const SplitRow &s
     for (int b = 0; b < NB; b++) acc[b] = d4{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int I = 0; I < DB; I++) bred[I] = 0.0;
-    if constexpr (DP == 64 && BDF_K1_WAVES64 >= 3) {
-        // a slot in two halves of 22 doubles (44 at once plus the 80-register matrix would leave nothing of a 168-register budget);
-        // the same additions in the same order
-        for (int s = 0; s < sr.n_slots; s++) {
-            const double *src = p.partials + (int64_t)(sr.slot_begin + s) * PSZ;
-#pragma unroll
-            for (int half = 0; half < 2; half++) {
-                double v[NB * 2 + DB / 2];
-#pragma unroll
-                for (int e = 0; e < NB * 2; e++) v[e] = src[(half * NB * 2 + e) * 64 + lane];
-#pragma unroll
-                for (int I = 0; I < DB / 2; I++) v[NB * 2 + I] = src[NB * 4 * 64 + (half * (DB / 2) + I) * 16 + (lane & 15)];
-#pragma unroll
-                for (int e = 0; e < NB * 2; e++) acc[(half * NB * 2 + e) >> 2][(half * NB * 2 + e) & 3] += v[e];
-#pragma unroll
-                for (int I = 0; I < DB / 2; I++) bred[half * (DB / 2) + I] += v[NB * 2 + I];
-                batch_fence<NB>(acc, half * (NB / 2) + NB / 2 - 1);
-            }
-        }
-        return;
-    }
     for (int s0 = 0; s0 < sr.n_slots; s0 += U) {
         double v[U][NB * 4 + DB];
 #pragma unroll
@@ -593,13 +553,11 @@ __device__ __forceinline__ void process_item(const SampleArgs &a, const PlanDev 
             if (++spins > (1 << 22)) { if (lane == 0) atomicOr_system(a.flag, 16); break; }      // bounded: ~seconds
         }
         SPAN_WAIT(t_poll);
-        // (DP = 64: the image's 40 loads in batches of 20, so that no more than 40 registers of it are in flight beside the matrix)
 #pragma unroll
         for (int b = 0; b < NB; b++) {
 #pragma unroll
             for (int r = 0; r < 4; r++)
                 acc[b][r] += __hip_atomic_load(a.prior_c + (b * 4 + r) * 64 + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (DP == 64 && BDF_K1_WAVES64 >= 3 && b % 5 == 4) batch_fence<NB>(acc, b);
         }
 #pragma unroll
         for (int J = 0; J < DB; J++) {
@@ -611,7 +569,6 @@ __device__ __forceinline__ void process_item(const SampleArgs &a, const PlanDev 
         for (int b = 0; b < NB; b++) {
 #pragma unroll
             for (int r = 0; r < 4; r++) acc[b][r] += a.prior_c[(b * 4 + r) * 64 + lane];
-            if (DP == 64 && BDF_K1_WAVES64 >= 3 && b % 5 == 4) batch_fence<NB>(acc, b);
         }
 #pragma unroll
         for (int J = 0; J < DB; J++) {
@@ -655,15 +612,6 @@ __device__ __forceinline__ void process_item(const SampleArgs &a, const PlanDev 
     for (int b = 0; b < NB; b++)
 #pragma unroll
         for (int r = 0; r < 4; r++) A[b * 4 + r] = acc[b][r];
-    if constexpr (DP == 64 && BDF_K1_WAVES64 >= 3) {
-        // a boundary for the register allocator: the values that live through the factorisation start new live ranges here, so that
-        // what the load phases above may have to keep in scratch under a three-wave budget is in registers again for the steps
-#pragma unroll
-        for (int b = 0; b < NB * 4; b++) asm volatile("" : "+v"(A[b]));
-#pragma unroll
-        for (int J = 0; J < DB; J++) asm volatile("" : "+v"(bv[J]));
-        asm volatile("" : "+v"(z));
-    }
     double ts[DB];                                // ts[J] in lane j: t_(16 J + j) once its step has passed; the last column's
 #pragma unroll                                    // (and any column's before its step) is still in bv
     for (int J = 0; J < DB; J++) ts[J] = 0.0;
@@ -671,10 +619,8 @@ __device__ __forceinline__ void process_item(const SampleArgs &a, const PlanDev 
     if (D < DP && !LOCAL) zero_packed_factor<DP>(tri, lane);
     if constexpr (LOCAL)
         factor_all_blocked_local<DP>(A, bv, ts, tri, j, h, D, std::make_integer_sequence<int, DP - 1>{});
-    else if constexpr (BDF_CHOL_BLOCKED)
-        factor_all_blocked<DP>(A, bv, ts, tri, j, h, D, std::make_integer_sequence<int, DP - 1>{});
     else
-        factor_all<DP>(A, bv, ts, tri, j, h, D, std::make_integer_sequence<int, DP - 1>{});
+        factor_all_blocked<DP>(A, bv, ts, tri, j, h, D, std::make_integer_sequence<int, DP - 1>{});
     STAMP(5);
 
     // lane c = column c: pivot d_c from the packed factor, t_c (the forward solve, unscaled) from the extra row
@@ -1157,8 +1103,7 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
         void *pb;
         int rc = bdf_scratch(ctx, ((size_t)nr * a.D + (size_t)nimg * 64) * sizeof(double), &pb);
         if (rc) return rc;
-        static const bool no_prior_rows = getenv("BDF_PRIOR_ROWS") && atoi(getenv("BDF_PRIOR_ROWS")) == 0;     // test hook: k_prior for every size
-        if (a.mu_is_matrix && nr >= 4096 && !no_prior_rows) {
+        if (a.mu_is_matrix && nr >= 4096) {
             // many rows: Lambda mu_i by k_prior_rows (the same sums in the same order), the image alone by k_prior (nrows = 0)
             const int RP = 256 / a.D;
             const unsigned grid = (unsigned)std::min<int64_t>((nr + RP - 1) / RP, 4096);
@@ -1192,7 +1137,7 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
         // floating-point sums, must not depend on the CU count or on BDF_RESERVE_CUS)
         int64_t nnz_launch = 0;
         for (int r = 0; r < a.n_terms; r++) nnz_launch += rels[r]->idx[modes[r]].own_nnz;
-        const int64_t slots = (int64_t)256 * 4 * (DP == 64 ? BDF_K1_WAVES64 : (DP == 32 ? BDF_K1_WAVES32C : 8));
+        const int64_t slots = (int64_t)256 * 4 * (DP == 64 ? 2 : (DP == 32 ? BDF_K1_WAVES32C : 8));
         const int64_t t = std::min<int64_t>(2048, (nnz_launch / (slots * 16) + 63) / 64 * 64);
         if (t > key.T) { key.T = (int)t; key.Tp = (int)(t * 2 / 3); }
     }
@@ -1228,13 +1173,6 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
     static const bool no_col = getenv("BDF_K1_GENERAL_KERNEL") != nullptr;          // (test hook: k_rows' general variant)
     if (DP == 32 && a.D > 16 && !dump && ctx->col_piece > 0 && (ctx->col_explicit || ctx->item_auto) && a.n_terms == 1 && a.t[0].n_other == 1 &&
         a.t[0].lean == 1 && a.t[0].linear == nullptr && !no_col) {
-        static int cus = 0;
-        if (!cus) {
-            hipDeviceProp_t prop;
-            BDF_HIP(hipGetDeviceProperties(&prop, ctx->device));
-            cus = prop.multiProcessorCount;
-        }
-        static const int per_simd = getenv("BDF_COL_PER_SIMD") ? std::max(1, atoi(getenv("BDF_COL_PER_SIMD"))) : 2;
         key.col = ctx->col_piece;
         if (!ctx->col_explicit) {
             // A row of more than 4 T observations SPANS waves: every part writes its 6.4 KB of sums through to the slab and the part
@@ -1249,7 +1187,7 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
             const int64_t t = std::min<int64_t>(2048, (nnz_entity / (2048 * 8) + 63) / 64 * 64);
             if (t > key.col) key.col = (int)t;
         }
-        key.col_slots = std::max(1, cus - ctx->reserve_cus) * 4 * per_simd;
+        key.col_slots = std::max(1, ctx->n_cus - ctx->reserve_cus) * 4 * 2;       // two waves per SIMD
         M_other = rels[0]->nint[1 - modes[0]];
     }
 

@@ -27,22 +27,14 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// 1 / x from v_rcp_f64 (relative error 3.9e-8 as measured) and Newton steps: two give 1e-16; one gives 1.5e-15, which is what
-// the factorisations use for their pivots (BDF_RCP_STEPS) -- the FP64 pipe is what bounds the row kernel, and the second step
-// is 62 of its ~870 fp64 instructions per row
-#ifndef BDF_RCP_STEPS
-#define BDF_RCP_STEPS 1
-#endif
+// 1 / x from v_rcp_f64 (relative error 3.9e-8 as measured) and one Newton step: 1.5e-15, which is what the factorisations use
+// for their pivots.  A second step would give 1e-16, but the FP64 pipe is what bounds the row kernel, and that step was 62 of its
+// ~870 fp64 instructions per row (the build switch that added it was retired after a70b66d).
 __device__ __forceinline__ double fast_rcp(double x)
 {
     double y = __builtin_amdgcn_rcp(x);
     double e = fma(-x, y, 1.0);
-    y = fma(y, e, y);
-    if (BDF_RCP_STEPS > 1) {
-        e = fma(-x, y, 1.0);
-        y = fma(y, e, y);
-    }
-    return y;
+    return fma(y, e, y);
 }
 
 __device__ __forceinline__ double fast_rsqrt(double x)

@@ -603,10 +603,6 @@ class GibbsEngine:
         rig = shard is not None and shard[1] > 1 and os.environ.get("BDF_DIST_BACKEND") == "gloo"
         reserve = int(os.environ.get("BDF_RESERVE_CUS", "0" if (big or rig) else "8"))
         self.ctx = Context.rows(device, seed, reserve)
-        if os.environ.get("BDF_ITEM_SIZE"):
-            self.ctx.set_item_size(int(os.environ["BDF_ITEM_SIZE"]))
-        if os.environ.get("BDF_PIECE_SIZE"):
-            self.ctx.set_piece_size(int(os.environ["BDF_PIECE_SIZE"]))
         self.rank, self.world = (0, 1) if shard is None else shard
         self.full_lambda_u = bool(full_lambda_u)
         self.tol = float(tol)
@@ -1127,7 +1123,7 @@ class GibbsEngine:
                 ids, vals = ids[subset], vals[subset]
             # native iteration: the pairs belong to the row context (the library updates them on its own prediction stream)
             self._test_pairs = self._pairs(self.ctx if self.native else self.ctx_p, r, ids, vals)
-            if len(r.entities) == 2 and not os.environ.get("BDF_NO_PAIR_SORT"):
+            if len(r.entities) == 2:
                 # stored sorted by the mode with the fewest rows (most pairs per row): the update keeps that mode's factor
                 # row in registers over a run of pairs and gathers only the other mode's (k_predict_runs); results stay in
                 # the caller's order
