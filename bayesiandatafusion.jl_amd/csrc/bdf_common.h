@@ -98,7 +98,7 @@ struct bdf_ctx {
     uint32_t *hyper_ready;                 // (library-internal) word the next bdf_hyper_sample sets to hyper_ready_value once its pack is written, then cleared
     uint32_t hyper_ready_value;
     hipEvent_t time_h_start, time_h_stop;  // bdf_ctx_time_next_hyper: start of the next sums kernel, end of the next draw kernel
-    // batched CG (k_feat.hip): device flag that lets product kernels enqueued ahead return at once (NULL outside a solve),
+    // batched CG (k_feat_cg.hip): device flag that lets product kernels enqueued ahead return at once (NULL outside a solve),
     // and the host-mapped words through which the device reports (iteration, active columns)
     // CU reservation (bdf_ctx_create_rows): the last... the first `reserve_cus` bits of the CU mask (one CU per XCD each 8)
     // are kept free of this context's kernels, for the side context created with reserved = 1
@@ -190,7 +190,7 @@ struct bdf_feat {
     // CSR (rows) and CSC (= CSR of F') so that neither product needs atomics
     int64_t *rowptr_dev; int32_t *colind_dev; double *rvals_dev;
     int64_t *colptr_dev; int32_t *rowind_dev; double *cvals_dev;
-    // column panels of the sparse products (k_feat.hip, spmm): entries of row r with a column in panel p are
+    // column panels of the sparse products (k_feat_ops.hip, spmm): entries of row r with a column in panel p are
     // [panel_ptr[p * rows + r], panel_ptr[(p + 1) * rows + r]) -- NULL when the operand is small or a row's entries are not in column order
     int64_t *panel_fwd_dev; int n_panels_fwd;      // F   (rows m, panels over the n columns)
     int64_t *panel_tr_dev; int n_panels_tr;        // F'  (rows n, panels over the m columns)

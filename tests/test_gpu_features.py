@@ -360,7 +360,7 @@ def test_cg_one_launch_solve_matches_the_two_launch_solve_and_the_oracle(B, O, N
 
 @pytest.mark.parametrize("kind", ["bin", "csr"])
 def test_sparse_products_in_column_panels(B, ctx, kind):
-    """A gathered operand of 8 MiB and more is taken in column panels (k_feat.hip, spmm: 12,288 rows of it per launch, the rows'
+    """A gathered operand of 8 MiB and more is taken in column panels (k_feat_ops.hip, spmm: 12,288 rows of it per launch, the rows'
     running sums carried through the output) -- 40,000 x 40,000 with 24 entries per row, 32 columns: four panels in both
     directions.  Against scipy at 1e-12 (sparsebin_csr.jl:49-63 / sparse_csr.jl semantics); and the same matrix given with every
     row's entries in a shuffled order -- which the library takes in ONE pass: the panels must keep the order of a row's sum, so an
