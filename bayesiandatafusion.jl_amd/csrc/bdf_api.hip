@@ -1,6 +1,6 @@
 // bdf_api.hip -- C-ABI entry points: context, device memory, IndexedDF -> device CSR, row sampling front-end
 #include <chrono>
-#include "bdf_common.h"
+#include "rows.h"
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
@@ -42,7 +42,7 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     c->sweep_dev = nullptr; c->flag_dev = nullptr; c->flag_host = nullptr; c->scratch = nullptr; c->scratch2 = nullptr; c->cg_status = nullptr; c->cg_part = nullptr;
     c->hyper_fuse = false; c->hyper_partial = nullptr; c->hyper_nblocks = 0; c->hyper_sumU = c->hyper_UUt = nullptr;
     c->hyper_chain = false; c->hyper_count = nullptr; c->hyper_chain_draws = nullptr;
-    c->own_stream = false; c->stream = nullptr;
+    c->own_stream = false; c->stream = nullptr; c->rows = nullptr;
     struct Guard { bdf_ctx *c; ~Guard() { if (c) bdf_ctx_destroy(c); } } guard{c};        // error paths free what was allocated
     c->device = device;
     c->n_cus = prop.multiProcessorCount;
@@ -69,7 +69,7 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     c->hyper_chain = false; c->hyper_count = nullptr; c->hyper_chain_draws = nullptr;
     c->cg_gen = 0;
     c->cg_bar = nullptr;
-    c->rows_dispatch = nullptr;
+    c->rows = bdf_rows_state_create();
     c->norm_part = nullptr;
     c->scratch = nullptr;
     c->scratch2 = nullptr;
@@ -88,7 +88,6 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     if (c->col_piece != 0) c->col_piece = std::min(4096, std::max(8, c->col_piece));
     c->col_explicit = false;
     c->lr_T = nullptr; c->lr_vt = nullptr; c->lr_vt_bytes = 0; c->lr_mrows = nullptr; c->lr_mrows_bytes = 0;
-    c->lr_key_fac = c->lr_key_Lambda = c->lr_key_mu = nullptr; c->lr_key_sweep = c->lr_key_tag = 0; c->lr_key_D = 0; c->lr_key_M = 0;
     {
         const char *force = getenv("BDF_GATHER");
         c->gather_mode = force && !strcmp(force, "general") ? 1 : (force && !strcmp(force, "wide") ? 2 : 0);
@@ -103,7 +102,7 @@ extern "C" int bdf_ctx_destroy(bdf_ctx *ctx)
     if (!ctx) return BDF_OK;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    bdf_plans_release(ctx, 0);
+    bdf_rows_state_destroy(ctx);
     if (ctx->scratch) hipFree(ctx->scratch);
     if (ctx->sweep_dev) hipFree(ctx->sweep_dev);
     if (ctx->flag_host) hipHostFree(ctx->flag_host);
@@ -111,7 +110,6 @@ extern "C" int bdf_ctx_destroy(bdf_ctx *ctx)
     if (ctx->cg_status) hipHostFree((void *)ctx->cg_status);
     if (ctx->cg_part) hipFree(ctx->cg_part);
     if (ctx->cg_bar) hipFree(ctx->cg_bar);
-    delete ctx->rows_dispatch;
     if (ctx->hyper_count) hipFree(ctx->hyper_count);
     if (ctx->lr_T) hipFree(ctx->lr_T);
     if (ctx->lr_vt) hipFree(ctx->lr_vt);
@@ -218,10 +216,9 @@ extern "C" int bdf_ctx_span_next_rows(bdf_ctx *ctx, void *slot_dev)
 extern "C" int bdf_ctx_rows_dispatch(const bdf_ctx *ctx, uint32_t entity_tag, int64_t out[6])
 {
     BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "bdf_ctx_rows_dispatch: NULL argument");
-    BDF_REQUIRE(ctx->rows_dispatch && ctx->rows_dispatch->count(entity_tag), BDF_ERR_ARG,
-                "bdf_ctx_rows_dispatch: no row launch under entity_tag %u on this context", entity_tag);
-    const std::array<int64_t, 7> &r = ctx->rows_dispatch->at(entity_tag);
-    for (int k = 0; k < 6; k++) out[k] = r[(size_t)k + 1];
+    const std::array<int64_t, 7> *r = bdf_rows_dispatch_counts(ctx, entity_tag);
+    BDF_REQUIRE(r, BDF_ERR_ARG, "bdf_ctx_rows_dispatch: no row launch under entity_tag %u on this context", entity_tag);
+    for (int k = 0; k < 6; k++) out[k] = (*r)[(size_t)k + 1];
     return BDF_OK;
 }
 

@@ -48,6 +48,7 @@ std::vector<int32_t> rows_by_degree(int64_t N, Degree degree)
     return ord;
 }
 
+struct bdf_rows_state;
 struct bdf_ctx {
     int device;
     int n_cus;                 // the device's CUs (multiProcessorCount)
@@ -74,15 +75,13 @@ struct bdf_ctx {
     size_t lr_mrows_bytes;
     double *lr_vt;             // the opposite entity's factor matrix transformed (V L^-T), grown on demand
     size_t lr_vt_bytes;
-    // what lr_T / lr_vt were computed from: a later chunk of the same entity launch reuses them
-    const void *lr_key_fac, *lr_key_Lambda, *lr_key_mu; uint32_t lr_key_sweep, lr_key_tag; int lr_key_D; int64_t lr_key_M;
     int *flag_dev;             // not-positive-definite flag (bits 1..32: errors; 64: BDF_WARN_CG_MAXITER): the device address of
     int *flag_host;            // ... a word of mapped, coherent HOST memory (kernels atomicOr into it on their error paths only;
                                // bdf_ctx_sync reads it without a copy -- a 4-byte blocking device-to-host copy is ~10 us)
     uint32_t warnings;         // non-fatal bits seen by bdf_ctx_sync, until bdf_ctx_warnings takes them
     int item_size;             // K1: observations per work item (rows longer than this are split)
     int piece_size;            // K1: ... into pieces of at most this many observations
-    bool item_auto;            // K1: neither was set by the caller: large launches take larger items (bdf_launch_sample_rows)
+    bool item_auto;            // K1: neither was set by the caller: large launches take larger items (rows_plan.hip: route_key)
     int gather_mode;           // K1 parity hook: 0 auto, 1 general gather path, 2 lean path with 64-bit row offsets (D > 32)
     hipEvent_t time_start, time_stop;      // bdf_ctx_time_next_rows: attached to the next row-kernel dispatch, then cleared
     unsigned long long *rows_span;         // bdf_ctx_span_next_rows: SampleArgs::span of the next row launch, then cleared
@@ -116,8 +115,7 @@ struct bdf_ctx {
     double *cg_part;                    // partial dot products of the chunked CG step (k_cg_long_*), allocated at first use
     uint32_t cg_gen;
     unsigned *cg_bar;                   // the hand-over counter of the one-launch CG solve (k_cg_resident), allocated at first use
-    // bdf_ctx_rows_dispatch: per entity tag {iteration number, rows by K1-lr, K1s, K1c, K1, K1's items, K1c's waves} of the latest launch
-    std::map<uint32_t, std::array<int64_t, 7>> *rows_dispatch;
+    bdf_rows_state *rows;               // the row launcher's own (rows_plan.hip): cached plans, dispatch counts, what lr_T / lr_vt were computed from
     double *norm_part;                  // bdf_norm2's per-workgroup partial sums (k_auc.hip), allocated at first use
 };
 
@@ -357,100 +355,8 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)   // lane mus
     return __hiloint2double(hi, lo);
 }
 
-// kernel launch argument blocks ------------------------------------------------------------
-#define BDF_K1_CODES 32            // distinct values up to which K1's coded variant keeps a per-wave table
-struct TermDev {
-    const int64_t *rowptr;
-    const int32_t *colidx;
-    const double *vals;
-    const int32_t *perm;
-    const double *linear;
-    const double *fac[BDF_MAX_MODES - 1];
-    int64_t nnz;
-    int32_t n_other;
-    int32_t lean;              // K1 lean gather: 1 = shared baseline, <= 2 other modes, factor matrices < 4 GiB with < 2^24
-                               // rows (32-bit offsets); 2 = the same with 64-bit row offsets (D > 32 only); 0 = general path
-    double alpha, mean;
-    const uint32_t *packed;    // nullable: (value code << 24) | other-mode id per observation, with
-    const double *table;       // the code -> value table (256 doubles)
-    int32_t n_codes, _padc;
-    const double *alpha_dev;   // nullable: the relation's precision in device memory (sampled on the device: sample_alpha inside bdf_gibbs_sweep); else `alpha`
-};
-
-__device__ __forceinline__ double term_alpha(const TermDev &T) { return T.alpha_dev ? *T.alpha_dev : T.alpha; }
-
-struct SampleArgs {
-    TermDev t[BDF_MAX_TERMS];
-    int32_t n_terms, D;
-    const double *mu;
-    int32_t mu_is_matrix, _pad;
-    const double *Lambda;
-    uint32_t sweep, _pad3;
-    uint64_t seed;
-    uint32_t entity_tag, _pad2;
-    double *out;
-    const double *prior_b;     // Lambda mu (D) or Lambda mu_i (D x N), filled by the launch front-end
-    const double *prior_c;     // index-reversed Lambda in the accumulator layout, filled by the launch front-end
-    double *P_dump, *b_dump;
-    int *flag;
-    // nullable: the launch does not wait for the hyperprior draw that writes the prior pack; every wave polls *ready until
-    // it reaches ready_want right before it adds the prior (bdf_gibbs_sweep on reserved CUs), and reads the pack past
-    // the non-coherent caches
-    const uint32_t *ready;
-    uint32_t ready_want, _pad4;
-    // nullable (bdf_ctx_span_next_rows): {start of the launch's first wave, end of its last} in s_memrealtime ticks (the 100 MHz
-    // clock the XCDs share), by one atomic min / max per wave -- a launch's duration without events around it (k_rows_col only)
-    unsigned long long *span;  // (64 shards of {start, end}: wave w uses shard w % 64)
-    // nullable (bdf_gibbs_sweep, k_rows_col only): 64 counters, 16 words apart; a wave that has written its rows (write-through, drained)
-    // adds 1 to counter (wave % 64): what the hyperprior chain polls instead of waiting for the launch's completion event
-    uint32_t *done;
-};
+// the rows' hand-over to the hyperprior chain by counter (SampleArgs::done, rows.h; polled by k_hyper_chain)
 #define BDF_DONE_SHARDS 64
 #define BDF_DONE_STRIDE 16         // words between two shards
 
-int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a, const bdf_rel *const *rels, const int *modes, int shard,
-                           int n_shards, bool dump);
-int bdf_lr_launch(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, int64_t n_rows_entity, const void *items, int64_t n_items, int64_t n_padded, int64_t n32_padded,
-                  const int32_t *rows_dev, bool transform, hipEvent_t e0, hipEvent_t e1);
-int bdf_lr_max_observations();
-int bdf_lr32_max_observations();
-void bdf_plans_release(bdf_ctx *ctx, uint64_t rel_serial);
-
-// ---- K1c (k_rows_col.hip): four rows per wave in the column layout ----------------------------------------------------
-struct ColJob {           // one lane row of one round
-    int32_t row;          // where the sample is written (the row's position in the factor matrix); -1: idle lane row
-    int32_t orig;         // the row's ORIGINAL id: keys its random stream
-    int64_t q_begin;      // first observation of the piece (index into the term's arrays)
-    int32_t count;        // observations of the piece
-    int32_t srow;         // a row that spans waves: its entry of the split-row table, else -1
-    int32_t slot;         // ... and this part's slot in the slab
-    int32_t flags;
-};
-#define COLF_LEADER 1     // the lane row that writes the sample of its group's row
-#define COLF_PAIR 2       // the lane row's sums are added to its neighbour's (lane ^ 16)
-#define COLF_QUAD 4       // ... and to the other half's (lane ^ 32)
-#define COLF_MULTI 8      // the round is one part of a row that spans waves
-struct ColSplit { int32_t slot_begin, n_slots; };
-struct ColPlanDev {
-    const ColJob *jobs;           // four per round, wave after wave
-    const int32_t *wave_round;    // wave w runs rounds wave_round[w] .. wave_round[w + 1] - 1
-    int32_t n_waves, _pad;
-    const ColSplit *rows;
-    double *partials;
-    int32_t *arrived;             // per split row: parts that have published (self-resetting)
-};
-struct bdf_row_ref { int32_t out, orig; int64_t qb, cnt; };
-struct bdf_col_plan {
-    ColJob *jobs_dev = nullptr;
-    int32_t *wave_round_dev = nullptr;
-    ColSplit *rows_dev = nullptr;
-    double *partials_dev = nullptr;
-    int32_t *arrived_dev = nullptr;
-    int32_t n_waves = 0, n_split_rows = 0;
-    int64_t n_rounds = 0;
-    double cost_max = 0.0, cost_min = 0.0;      // the planner's cost model: the heaviest and the lightest wave
-};
-int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T, int64_t slots, bdf_col_plan &plan);
-void bdf_col_plan_free(bdf_col_plan &plan);
-int bdf_col_launch(bdf_ctx *ctx, const SampleArgs &a, const bdf_col_plan &plan, int64_t M_other, hipEvent_t e0, hipEvent_t e1);
-int bdf_predict_plain(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, double *out);   // rel_serial 0: every plan of the context
+int bdf_predict_plain(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, double *out);

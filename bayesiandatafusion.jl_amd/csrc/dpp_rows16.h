@@ -1,7 +1,7 @@
 // dpp_rows16.h -- a 16 x 16 (or smaller) symmetric positive-definite system per ROW OF 16 LANES, four systems per wavefront:
 // lane j of a lane row holds COLUMN j (A[i] = entry (i, j)) and entry j of the right-hand side.  Rank-1 updates, the LDL'
 // factorisation with the forward solve riding along, and the backward solve are v_fmac_f64_dpp row_newbcast instructions
-// (lane k of each lane row is the broadcast source).  Shared by k_rows_small (k_sample_rows.hip: D <= 16, four entity rows per
+// (lane k of each lane row is the broadcast source).  Shared by k_rows_small (k_rows_small.hip: D <= 16, four entity rows per
 // wave) and k_rows_lr4 (k_rows_lr.hip: the n x n systems of the low-rank sampler).
 #pragma once
 #include "c_layout_chol.h"

@@ -7,7 +7,7 @@
 // the nv item rows weighted by the user's column of Yma), runs the forward and backward substitution against the shared
 // packed factor (one LDS copy per workgroup) and adds its own normals (k_block_users).  The row sampler would factor the same
 // matrix once per user.
-#include "bdf_common.h"
+#include "rows.h"
 #include "c_layout_chol.h"
 
 namespace {
@@ -124,9 +124,6 @@ __global__ __launch_bounds__(256) void k_block_users(int D, int64_t nu, int64_t 
 
 }  // namespace
 
-// k_prior of k_sample_rows.hip: Lambda mu and the accumulator-layout image of the reversed Lambda
-int bdf_prior_image(bdf_ctx *ctx, int D, const double *Lambda, const double *mu, double *out_b, double *out_c);
-
 extern "C" int bdf_sample_block(bdf_ctx *ctx, int D, int64_t nu, int64_t nv, const int32_t *vx_dev, const double *Yma,
                                 const double *factor, double alpha, const double *mu, const double *Lambda, uint32_t entity_tag,
                                 double *out)
@@ -135,14 +132,14 @@ extern "C" int bdf_sample_block(bdf_ctx *ctx, int D, int64_t nu, int64_t nv, con
                 "bdf_sample_block: NULL argument");
     BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D && nu >= 0 && nv >= 0, BDF_ERR_ARG, "bdf_sample_block: bad size");
     if (nu == 0) return BDF_OK;
-    const int DP = D <= 16 ? 16 : (D <= 32 ? 32 : 64);
-    const int DB = DP / 16, nimg = DB * (DB + 1) / 2 * 4;
+    const int DP = bdf_rows_dp(D);
+    const size_t img = (size_t)bdf_prior_image_doubles(D);
     const size_t tri_d = DP == 16 ? Geo<16>::TRI_D : (DP == 32 ? Geo<32>::TRI_D : Geo<64>::TRI_D);
     void *sc;
-    int rc = bdf_scratch(ctx, ((size_t)D + (size_t)nimg * 64 + tri_d + 3 * (size_t)DP) * sizeof(double), &sc);
+    int rc = bdf_scratch(ctx, ((size_t)D + img + tri_d + 3 * (size_t)DP) * sizeof(double), &sc);
     if (rc) return rc;
-    double *pb = (double *)sc, *pc = pb + D, *fac = pc + (size_t)nimg * 64, *piv = fac + tri_d;
-    if ((rc = bdf_prior_image(ctx, D, Lambda, mu, pb, pc))) return rc;
+    double *pb = (double *)sc, *pc = pb + D, *fac = pc + img, *piv = fac + tri_d;
+    if ((rc = bdf_prior_launch(ctx, D, Lambda, mu, 1, 0, pb, pc))) return rc;      // Lambda mu and the image of the reversed Lambda (k_prior, k_sample_rows.hip)
     const dim3 ug((unsigned)((nu + 3) / 4));
 #define BLOCK(DPV)                                                                                                      \
     do {                                                                                                                \

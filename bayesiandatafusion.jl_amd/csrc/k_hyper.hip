@@ -221,7 +221,7 @@ extern "C" int bdf_hyper_sums(bdf_ctx *ctx, int D, int64_t N, const double *samp
     // should all be resident at once on the stream's CUs (two workgroups of 255 registers per CU), or the partial sums take two
     // rounds and the last workgroup gets its slot when the first round ends (9.3 us of the chain at D = 32).  The count comes from a
     // NOMINAL 16 slots (8 reserved CUs), not from the context's: the number of partials decides the order of the sums, and the
-    // sampled values must not depend on BDF_RESERVE_CUS or the CU count (k_sample_rows.hip's rule for the rows' cuts)
+    // sampled values must not depend on BDF_RESERVE_CUS or the CU count (rows_plan.hip's rule for the rows' cuts: route_key)
     const int wg_slots = 16;
     const int max_part = fuse ? std::max(8, std::min(16, wg_slots - 1 - (D * D + D + 255) / 256)) : 16;
     const int64_t rpb = HS_ROWS * ((chunks + (fuse ? max_part - 1 : 2047)) / (fuse ? max_part : 2048));

@@ -28,7 +28,7 @@
 //     longest first to the least loaded wave: every wave carries the same cost, a launch is one balanced generation.
 // How a row is cut depends on its own length and T only -- not on the launch, the shard or the number of GPUs -- so the
 // sampled values do not depend on them either.
-#include "bdf_common.h"
+#include "rows.h"
 #include "dpp_rows32.h"
 #include <algorithm>
 

@@ -27,7 +27,7 @@
 // (lane (i, kk): elements kk D/4 .. of observation i); e0 rides along as "observation 15", which makes Wt' e0 column 15 of
 // the same sixteen v_mfma_f64_16x16x4_f64.  G is then factored in the accumulator layout by the row kernel's own 16 x 16
 // routines (c_layout_chol.h), the right-hand side riding along as the extra row.
-#include "bdf_common.h"
+#include "rows.h"
 #include "wave_linalg.h"
 #include "c_layout_chol.h"
 #include "dpp_rows16.h"
@@ -198,13 +198,6 @@ __global__ __launch_bounds__(256) void k_rowmat(const double *X, double *Y, cons
     }
 }
 
-struct LrItem {
-    int32_t row;          // where the sample is written (position in the factor matrix)
-    int32_t orig;         // the row's original id (random stream)
-    int64_t q_begin;
-    int32_t count, _pad;
-};
-
 struct LrArgs {
     const int32_t *colidx;      // the relation's other-mode ids, mode order
     const double *vals;
@@ -222,7 +215,7 @@ struct LrArgs {
 };
 
 template <int DP>
-__global__ __launch_bounds__(256, 6) void k_rows_lr(LrArgs a, const LrItem *__restrict__ items, int64_t n_items)
+__global__ __launch_bounds__(256, 6) void k_rows_lr(LrArgs a, const RowItem *__restrict__ items, int64_t n_items)
 {
     using LG = LrGeo<DP>;
     using G16 = Geo<16>;
@@ -233,7 +226,7 @@ __global__ __launch_bounds__(256, 6) void k_rows_lr(LrArgs a, const LrItem *__re
     if (w >= n_items) return;
     double *st = lds + wave * LG::WAVE_LDS, *tri = st + LG::STAGE;
     const int j = lane & 15, h = lane >> 4;
-    const LrItem it = items[w];
+    const RowItem it = items[w];
     if (it.row < 0) return;             // (the list is padded to a multiple of four with row = -1 records: k_rows_lr4's idle lane rows)
     const int D = a.D, n = it.count;
     const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;
@@ -418,7 +411,7 @@ __device__ __forceinline__ void lr4_phase_c(double (&q)[DP / 16], uint32_t idw, 
 }
 
 template <int DP, int DR>
-__device__ __forceinline__ void lr4_body(const LrArgs &a, const LrItem &it, const int j)
+__device__ __forceinline__ void lr4_body(const LrArgs &a, const RowItem &it, const int j)
 {
     constexpr int DB = DP / 16, NR = DP / 32;
     const bool live = it.row >= 0;
@@ -483,12 +476,12 @@ __device__ __forceinline__ void lr4_body(const LrArgs &a, const LrItem &it, cons
 }
 
 template <int DP>
-__global__ __launch_bounds__(256, 3) void k_rows_lr4(LrArgs a, const LrItem *__restrict__ items, int64_t n_items)
+__global__ __launch_bounds__(256, 3) void k_rows_lr4(LrArgs a, const RowItem *__restrict__ items, int64_t n_items)
 {
     const int lane = threadIdx.x & 63, j = lane & 15;
     const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (w * 4 >= n_items) return;
-    const LrItem it = items[w * 4 + (lane >> 4)];
+    const RowItem it = items[w * 4 + (lane >> 4)];
     int nmax = it.row >= 0 ? it.count : 0;
     nmax = max(nmax, __shfl_xor(nmax, 16));
     nmax = max(nmax, __shfl_xor(nmax, 32));
@@ -539,14 +532,14 @@ __device__ __forceinline__ void lr32_phase_c(double (&q)[DP / 16], uint32_t idw0
 }
 
 template <int DP>
-__global__ __launch_bounds__(256, 2) void k_rows_lr32(LrArgs a, const LrItem *__restrict__ items, int64_t n_items)
+__global__ __launch_bounds__(256, 2) void k_rows_lr32(LrArgs a, const RowItem *__restrict__ items, int64_t n_items)
 {
     constexpr int DB = DP / 16, NR = DP / 32;
     __shared__ double lds[4 * 4 * 272];                   // block (1,0) of the four systems of each wave on its way to block (0,1)
     const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
     const int64_t w = (int64_t)blockIdx.x * 4 + wave;
     if (w * 4 >= n_items) return;
-    const LrItem it = items[w * 4 + g];
+    const RowItem it = items[w * 4 + g];
     const bool live = it.row >= 0;
     const int D = a.D, n = live ? it.count : 0;
     const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;
@@ -644,7 +637,7 @@ int lr_buffers(bdf_ctx *ctx, size_t vt_bytes, size_t mrows_bytes)
 }
 
 template <int DP>
-int lr_launch_t(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, const void *items, int64_t n_items, int64_t n_padded, int64_t n32_padded,
+int lr_launch_t(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, const RowItem *items, int64_t n_items, int64_t n_padded, int64_t n32_padded,
                 const int32_t *rows_dev, bool transform, hipEvent_t e0, hipEvent_t e1)
 {
     const int D = a.D;
@@ -674,15 +667,15 @@ int lr_launch_t(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, const void *
     // items: n_padded records of rows of at most 16 observations, then n32_padded of rows of 17 .. 32 (D > 32 only); n_items rows in all
     if (n_padded > 0) {
         if (wave_per_row)
-            hipExtLaunchKernelGGL((k_rows_lr<DP>), dim3((unsigned)((n_padded + 3) / 4)), dim3(256), 0, ctx->stream, e0, nullptr, 0, la, (const LrItem *)items, n_padded);
+            hipExtLaunchKernelGGL((k_rows_lr<DP>), dim3((unsigned)((n_padded + 3) / 4)), dim3(256), 0, ctx->stream, e0, nullptr, 0, la, items, n_padded);
         else
-            hipExtLaunchKernelGGL((k_rows_lr4<DP>), dim3((unsigned)((n_padded + 15) / 16)), dim3(256), 0, ctx->stream, e0, nullptr, 0, la, (const LrItem *)items, n_padded);
+            hipExtLaunchKernelGGL((k_rows_lr4<DP>), dim3((unsigned)((n_padded + 15) / 16)), dim3(256), 0, ctx->stream, e0, nullptr, 0, la, items, n_padded);
         e0 = nullptr;
     }
     if constexpr (DP == 64) {
         if (n32_padded > 0)
             hipExtLaunchKernelGGL((k_rows_lr32<DP>), dim3((unsigned)((n32_padded + 15) / 16)), dim3(256), 0, ctx->stream, e0, nullptr, 0, la,
-                                  (const LrItem *)items + n_padded, n32_padded);
+                                  items + n_padded, n32_padded);
     }
     const int64_t iters = (n_items + 16 * TPW - 1) / (16 * TPW);
     hipExtLaunchKernelGGL((k_rowmat<DP>), dim3((unsigned)std::min<int64_t>(iters, 4096)), dim3(256), 0, ctx->stream, nullptr, e1, 0, (const double *)a.out, a.out,
@@ -693,12 +686,12 @@ int lr_launch_t(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, const void *
 
 }  // namespace
 
-// The rows `items` (LrItem: one two-mode relation, at most 16 observations each, shared or per-row prior means (n_rows_entity rows
+// The rows `items` (RowItem: one two-mode relation, at most 16 observations each, shared or per-row prior means (n_rows_entity rows
 // of the factor matrix); n_items of them, padded
 // with row = -1 records to n_padded, a multiple of four) of the launch described by `a`.  transform: L = chol(Lambda), the
 // opposite factor's M_other rows transformed into the context's buffer (false: both are still valid from the previous chunk
 // of the same entity launch).  rows_dev: the rows' positions (n_items int32).
-int bdf_lr_launch(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, int64_t n_rows_entity, const void *items, int64_t n_items, int64_t n_padded,
+int bdf_lr_launch(bdf_ctx *ctx, const SampleArgs &a, int64_t M_other, int64_t n_rows_entity, const RowItem *items, int64_t n_items, int64_t n_padded,
                   int64_t n32_padded, const int32_t *rows_dev, bool transform, hipEvent_t e0, hipEvent_t e1)
 {
     const int DP = a.D <= 32 ? 32 : 64;

@@ -1,0 +1,445 @@
+// rows_plan.hip -- the latent-row sampler's host side: which of the four row kernels takes which row of a launch, the cached
+// plan that records it, and the launches.
+//
+// bdf_launch_sample_rows (the end of this file) is the one entry: prior pack, routing key, plan (built once per key and kept
+// in the context), dispatch counts, then up to four launches in a fixed order
+//     K1-lr  k_rows_lr.hip      rows of few observations at D > 16          (route_key: key.lr / key.lr32, collect_rows: enough of them)
+//     K1s    k_rows_small.hip   short rows at D <= 16                       (route_key: key.small)
+//     K1c    k_rows_col.hip     every other row at 16 < D <= 32             (route_key: key.col)
+//     K1     k_sample_rows.hip  what is left
+// An eligibility rule lives in route_key and nowhere else; which kernel ONE row goes to is classify().  No kernel here.
+#include "rows.h"
+#include "c_layout_chol.h"
+#include <cstdlib>
+#include <mutex>
+
+namespace {
+
+// ---- the plan (items, split rows, slab) for a (terms, row list) combination, cached per context -----------------------
+struct PlanKey {
+    uint64_t rel[BDF_MAX_TERMS];      // relation serials
+    int mode[BDF_MAX_TERMS];
+    int n_terms, DP, T, Tp;
+    int shard, n_shards;
+    int small;                        // > 0: rows of at most this many observations go to k_rows_small (four rows per wave)
+    int lr;                           // > 0: rows of at most this many observations go to k_rows_lr (the low-rank sampler, k_rows_lr.hip)
+    int lr32;                         // > lr: rows of lr + 1 .. lr32 observations too (k_rows_lr32: two observations per lane, D > 32)
+    int64_t lr_min, lr_other;         // ... if the launch has at least lr_min of them, and at least half as many as the opposite entity has rows
+    int col;                          // > 0: the rows of k_rows go to k_rows_col instead (four rows per wave, column layout), cut into pieces of at most this size
+    int col_slots;                    // ... dealt to at most this many waves
+    bool operator<(const PlanKey &o) const { return memcmp(this, &o, sizeof(PlanKey)) < 0; }
+};
+
+struct Plan {
+    PlanDev dev{};                    // K1's items, split rows and slab
+    RowItem *small_dev = nullptr;
+    int64_t n_small = 0;              // entries of small_dev (a multiple of 4)
+    RowItem *lr_dev = nullptr;        // the rows of the low-rank sampler, and their positions for the back-transform
+    int32_t *lr_rows_dev = nullptr;
+    int64_t n_lr = 0, n_lr_padded = 0;   // rows of the low-rank sampler in all; records of the rows of at most key.lr observations (a multiple of 4)
+    int64_t n_lr32_padded = 0;           // ... and of the rows of key.lr + 1 .. key.lr32 observations, behind them in lr_dev
+    bdf_col_plan col;                 // the rows of k_rows_col (K1c)
+    int64_t rows_lr = 0, rows_small = 0, rows_col = 0, rows_k1 = 0;      // how the plan's rows are shared out (bdf_ctx_rows_dispatch)
+};
+
+void plan_free(Plan &p)
+{
+    for (void *q : {(void *)p.small_dev, (void *)p.lr_dev, (void *)p.lr_rows_dev, (void *)p.dev.direct, (void *)p.dev.split, (void *)p.dev.rows,
+                    (void *)p.dev.order, (void *)p.dev.partials, (void *)p.dev.arrived})
+        (void)hipFree(q);
+    bdf_col_plan_free(p.col);
+}
+
+// what lr_T / lr_vt of the context were computed from: a later chunk of the same entity launch reuses them
+struct LrKey {
+    const void *fac, *Lambda, *mu; uint32_t sweep, tag; int D; int64_t M;
+    bool operator==(const LrKey &o) const { return fac == o.fac && Lambda == o.Lambda && mu == o.mu && sweep == o.sweep && tag == o.tag && D == o.D && M == o.M; }
+};
+
+std::mutex g_plans_mutex;             // around every context's plan cache
+
+}  // namespace
+
+// the row launcher's state of one context (bdf_ctx::rows)
+struct bdf_rows_state {
+    std::map<PlanKey, Plan> plans;
+    std::map<uint32_t, std::array<int64_t, 7>> dispatch;      // bdf_ctx_rows_dispatch: per entity tag, see bdf_rows_dispatch_counts
+    LrKey lr_key{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+};
+
+namespace {
+
+constexpr int64_t MAX_PIECES = 64;
+
+// one row of the launch as the plan sees it: where its sample goes, its original id, and per term its observations in
+// that term's device arrays
+struct RowRef {
+    int32_t out, orig;
+    int64_t qb[BDF_MAX_TERMS];
+    int64_t cnt[BDF_MAX_TERMS];
+};
+
+enum class Route { LowRank, LowRank32, Small, Column, K1Direct, K1Split };
+
+// The kernel that takes row rr; n_items: the items K1 cuts it into (set for K1Direct / K1Split).  The three whole-row kernels
+// come first: they take rows with observations in at most one relation, and no more of them than the item size
+// (route_key: key.small, key.lr, key.lr32 <= key.T), so such a row would be ONE item of K1.
+Route classify(const PlanKey &key, const RowRef &rr, bool lr_on, int &n_items)
+{
+    int nz = 0;
+    int64_t n = 0;
+    for (int r = 0; r < key.n_terms; r++) { nz += rr.cnt[r] > 0; n += rr.cnt[r]; }
+    if (nz <= 1 && key.small > 0 && n <= key.small) return Route::Small;
+    if (nz <= 1 && lr_on && n <= key.lr) return Route::LowRank;
+    if (nz <= 1 && lr_on && n <= key.lr32) return Route::LowRank32;
+    if (key.col > 0) return Route::Column;
+    const int T = key.T;
+    n_items = 0;
+    for (int r = 0; r < key.n_terms; r++) n_items += (int)std::min<int64_t>((rr.cnt[r] + T - 1) / T, MAX_PIECES);
+    // (at most MAX_PIECES per relation: the row's finisher adds the partial sums one slot after the other, ~0.5 us each
+    // -- a 78,000-observation row of config C5 in 128-observation pieces would keep it busy for 0.3 ms)
+    // a row that is split anyway is cut into smaller pieces than the longest whole row: the launch ends with the split
+    // rows (their pieces gather at a sixth of the matrix pipe each, then one wave sums and finishes the row)
+    if (n_items > 1 && key.Tp != T) {
+        n_items = 0;
+        for (int r = 0; r < key.n_terms; r++) n_items += (int)std::min<int64_t>((rr.cnt[r] + key.Tp - 1) / key.Tp, MAX_PIECES);
+    }
+    return n_items <= 1 ? Route::K1Direct : Route::K1Split;
+}
+
+int build_plan(bdf_ctx *ctx, const PlanKey &key, const std::vector<RowRef> &rows, bool lr_on, Plan &plan)
+{
+    const int Tp = key.Tp, DB = key.DP / 16;
+    const int psz = DB * (DB + 1) / 2 * 4 * 64 + DB * 16;      // doubles per partial slot (Geo<DP>::PSZ)
+    std::vector<Item> direct, split;
+    std::vector<RowItem> small, lr, lr32;
+    std::vector<SplitRow> srows;
+    std::vector<bdf_row_ref> crows;
+    for (const RowRef &rr : rows) {
+        const int32_t row = rr.out;
+        int n_items = 0;
+        const Route route = classify(key, rr, lr_on, n_items);
+        if (route == Route::Column) { crows.push_back(bdf_row_ref{rr.out, rr.orig, rr.qb[0], rr.cnt[0]}); continue; }
+        if (route == Route::K1Split) {
+            SplitRow sr{row, (int32_t)split.size(), n_items, 0};
+            for (int r = 0; r < key.n_terms; r++) {
+                const int64_t beg = rr.qb[r], n = rr.cnt[r];
+                const int pieces = (int)std::min<int64_t>((n + Tp - 1) / Tp, MAX_PIECES);
+                for (int s = 0; s < pieces; s++) {
+                    // equal pieces rather than T, T, ..., remainder
+                    const int64_t b0 = beg + n * s / pieces, b1 = beg + n * (s + 1) / pieces;
+                    split.push_back(Item{row, r, b0, (int32_t)(b1 - b0), (int32_t)split.size(), (int32_t)srows.size(), rr.orig});
+                }
+            }
+            srows.push_back(sr);
+            continue;
+        }
+        Item it{row, 0, 0, 0, -1, -1, rr.orig};      // the row whole: the observations of its one relation that has any
+        for (int r = 0; r < key.n_terms; r++)
+            if (rr.cnt[r] > 0) { it.term = r; it.q_begin = rr.qb[r]; it.count = (int32_t)rr.cnt[r]; }
+        if (route == Route::K1Direct) { direct.push_back(it); continue; }
+        (route == Route::Small ? small : (route == Route::LowRank ? lr : lr32)).push_back(RowItem{row, rr.orig, it.q_begin, it.count, 0});
+    }
+    // launch order.  The items are listed longest first (split pieces, then rows by falling observation count); waves
+    // that share a SIMD should be at different phases (the gather/MFMA phase of one under the factorisation of another),
+    // so neighbours in launch order should differ in length: a fixed stride permutation of the sorted list.
+    const int64_t total = (int64_t)split.size() + (int64_t)direct.size();
+    std::vector<int32_t> order((size_t)total);
+    {
+        auto gcd = [](int64_t x, int64_t y) { while (y) { int64_t t = x % y; x = y; y = t; } return x; };
+        int64_t stride = 1;
+        if (total > 2) {
+            stride = (int64_t)(0.6180339887 * (double)total) | 1;
+            while (gcd(stride, total) != 1) stride += 2;
+        }
+        for (int64_t i = 0; i < total; i++) order[(size_t)i] = (int32_t)((i * stride) % total);
+    }
+    int rc;
+    if (key.col > 0 && (rc = bdf_col_plan_build(ctx, crows, key.col, key.col_slots, plan.col))) return rc;
+    plan.rows_lr = (int64_t)lr.size() + (int64_t)lr32.size(); plan.rows_small = (int64_t)small.size(); plan.rows_col = (int64_t)crows.size();
+    plan.rows_k1 = (int64_t)direct.size() + (int64_t)srows.size();
+    while (small.size() % 4) small.push_back(RowItem{-1, 0, 0, 0, 0});
+    plan.n_small = (int64_t)small.size();
+    if (!small.empty() && (rc = bdf_upload(&plan.small_dev, small))) return rc;
+    plan.n_lr = (int64_t)lr.size() + (int64_t)lr32.size();
+    if (plan.n_lr > 0) {
+        // longest first: the waves of a workgroup then have rows of like length
+        auto by_count = [](const RowItem &x, const RowItem &y) { return x.count > y.count; };
+        std::stable_sort(lr.begin(), lr.end(), by_count);
+        std::stable_sort(lr32.begin(), lr32.end(), by_count);
+        std::vector<int32_t> lr_rows;
+        lr_rows.reserve((size_t)plan.n_lr);
+        for (const RowItem &x : lr) lr_rows.push_back(x.row);
+        for (const RowItem &x : lr32) lr_rows.push_back(x.row);
+        // (the positions in ASCENDING order: they are what the dense passes over the rows walk -- the back-transform x = L^-T q and
+        // the per-row prior means -- and a pass over rows in the sampler's order, longest first, reads and writes 512-byte rows at
+        // random)
+        std::sort(lr_rows.begin(), lr_rows.end());
+        while (lr.size() % 4) lr.push_back(RowItem{-1, 0, 0, 0, 0});      // four rows per wave
+        while (lr32.size() % 4) lr32.push_back(RowItem{-1, 0, 0, 0, 0});
+        plan.n_lr_padded = (int64_t)lr.size();
+        plan.n_lr32_padded = (int64_t)lr32.size();
+        lr.insert(lr.end(), lr32.begin(), lr32.end());
+        if ((rc = bdf_upload(&plan.lr_dev, lr)) || (rc = bdf_upload(&plan.lr_rows_dev, lr_rows))) return rc;
+    }
+    Item *direct_dev, *split_dev;
+    SplitRow *rows_dev;
+    int32_t *order_dev, *arrived_dev;
+    double *partials_dev;
+    if ((rc = bdf_upload(&direct_dev, direct)) || (rc = bdf_upload(&split_dev, split)) ||
+        (rc = bdf_upload(&rows_dev, srows)) || (rc = bdf_upload(&order_dev, order)))
+        return rc;
+    BDF_HIP(hipMalloc((void **)&partials_dev, std::max<size_t>(split.size() * (size_t)psz * sizeof(double), 8)));
+    BDF_HIP(hipMalloc((void **)&arrived_dev, std::max<size_t>(srows.size() * sizeof(int32_t), 8)));
+    // on the launch stream: hipMemset runs on the NULL stream and returns before the device has done it, and a kernel on a
+    // non-blocking stream does not wait for it -- the first launch of a new plan could have its counters zeroed under it
+    // (a split row then never finds its last piece: the row keeps its old content)
+    BDF_HIP(hipMemsetAsync(arrived_dev, 0, std::max<size_t>(srows.size() * sizeof(int32_t), 8), ctx->stream));
+    plan.dev = PlanDev{direct_dev, (int32_t)direct.size(), split_dev, (int32_t)split.size(), rows_dev, (int32_t)srows.size(),
+                       partials_dev, arrived_dev, order_dev};
+    return BDF_OK;
+}
+
+// ---- step 2: the plan key -- item sizes, and for each of the three other kernels whether (and up to which row length) this
+// launch may use it.  M_other: the opposite entity's rows, for the low-rank and the column launch. -----------------------
+void route_key(const bdf_ctx *ctx, const SampleArgs &a, const bdf_rel *const *rels, const int *modes, int shard, int n_shards, bool dump,
+               PlanKey &key, int64_t &M_other)
+{
+    const int DP = bdf_rows_dp(a.D);
+    memset(&key, 0, sizeof(key));
+    for (int r = 0; r < a.n_terms; r++) { key.rel[r] = rels[r]->serial; key.mode[r] = modes[r]; }
+    key.n_terms = a.n_terms; key.DP = DP; key.T = ctx->item_size; key.Tp = std::min(ctx->piece_size, ctx->item_size); key.shard = shard; key.n_shards = n_shards;
+    if (ctx->item_auto) {
+        // Rows are cut into pieces so that a launch of a few thousand rows has no wave much longer than the others.  A launch with
+        // hundreds of waves per resident slot has no such tail, and every piece costs a partial sum written to the slab and read
+        // back (21 KB at D = 64: the 540,000 pieces of configuration C4's item launch moved 22 GB): larger items there -- about
+        // sixteen waves per slot, between the default and 2048 observations (the same for every shard of the launch).
+        // (a NOMINAL slot count -- 256 CUs -- not the device's or the stream's: the cut of a row, and with it the order of its
+        // floating-point sums, must not depend on the CU count or on BDF_RESERVE_CUS)
+        int64_t nnz_launch = 0;
+        for (int r = 0; r < a.n_terms; r++) nnz_launch += rels[r]->idx[modes[r]].own_nnz;
+        const int64_t slots = (int64_t)256 * 4 * (DP == 64 ? 2 : (DP == 32 ? BDF_K1_WAVES32C : 8));
+        const int64_t t = std::min<int64_t>(2048, (nnz_launch / (slots * 16) + 63) / 64 * 64);
+        if (t > key.T) { key.T = (int)t; key.Tp = (int)(t * 2 / 3); }
+    }
+    // D <= 16, one two-mode relation with the lean gather and no per-observation baseline, an entity of many rows: its short
+    // rows four to a wave (k_rows_small).  bdf_ctx_set_small_rows: the longest row taken that way (default 48 observations,
+    // environment BDF_K1_SMALL; 0: off) and the smallest entity (default 8192 rows, BDF_K1_SMALL_MIN_ROWS: below that the
+    // second launch costs more than it saves)
+    const int64_t n_rows_all = rels[0]->sharded ? (int64_t)rels[0]->idx[modes[0]].own_orig.size() : (int64_t)rels[0]->idx[modes[0]].order.size();
+    if (DP == 16 && !dump && ctx->small_max > 0 && a.n_terms == 1 && a.t[0].lean == 1 && a.t[0].n_other == 1 && a.t[0].linear == nullptr &&
+        n_rows_all >= ctx->small_min_rows)
+        key.small = std::min(ctx->small_max, ctx->item_size);
+
+    // D > 16, one two-mode relation without per-observation baselines (shared or per-row prior means): the rows of few observations
+    // by the low-rank sampler (k_rows_lr.hip; bdf_ctx_set_lowrank, environment BDF_LOWRANK:
+    // the longest such row, -1 = min(16, D / 2), 0 = off) -- when there are enough of them (decided when the plan is built)
+    if (DP > 16 && !dump && ctx->lr_max != 0 && a.n_terms == 1 && a.t[0].n_other == 1 && a.t[0].linear == nullptr) {
+        const int other = 1 - modes[0];
+        M_other = rels[0]->nint[other];
+        const int lr_want = ctx->lr_max < 0 ? a.D / 2 : ctx->lr_max;
+        key.lr = std::min(std::min(lr_want, bdf_lr_max_observations()), ctx->item_size);
+        key.lr32 = DP == 64 ? std::min(std::min(lr_want, bdf_lr32_max_observations()), ctx->item_size) : 0;       // (> key.lr: rows of 17 .. 32 observations too)
+        key.lr_min = std::max<int64_t>(ctx->lr_min_rows, 1);
+        key.lr_other = ctx->lr_min_rows > 0 ? rels[0]->dims[other] : 0;          // (min_rows = 0, a test hook: whenever the entity has such a row)
+    }
+
+    // 16 < D <= 32, one two-mode relation on the lean gather path without per-observation baselines: the rows four to a wave in
+    // the column layout (K1c, k_rows_col.hip; bdf_ctx_set_col_rows) -- unless the caller chose K1's item size or its general variant
+    static const bool no_col = getenv("BDF_K1_GENERAL_KERNEL") != nullptr;          // (test hook: k_rows' general variant)
+    if (DP == 32 && a.D > 16 && !dump && ctx->col_piece > 0 && (ctx->col_explicit || ctx->item_auto) && a.n_terms == 1 && a.t[0].n_other == 1 &&
+        a.t[0].lean == 1 && a.t[0].linear == nullptr && !no_col) {
+        key.col = ctx->col_piece;
+        if (!ctx->col_explicit) {
+            // A row of more than 4 T observations SPANS waves: every part writes its 6.4 KB of sums through to the slab and the part
+            // that arrives last adds them, slot after slot -- ~25 us of a wave's slot per part when thousands of them are in flight
+            // (profiles/r05_k1c_piece_size.txt: 1,000 rows of 15,000 observations, the reference's benchmark shape, 2.7 ms at
+            // T = 128 in 30,000 parts, 0.70 ms at T = 1,024 in 4,000; 4,000 rows of 3,000: 0.73 -> 0.44 ms).  Small pieces are
+            // for launches of ONE generation of waves (MovieLens: the heaviest wave is the launch's tail); a launch with many
+            // waves per slot takes larger ones: about eight waves' worth of observations per slot of a NOMINAL 2,048 (not the
+            // device's or the stream's: the cut of a row must not depend on them), from the WHOLE entity's count -- the same on
+            // every shard, chunk and rank -- between the default and 2,048.
+            const int64_t nnz_entity = (int64_t)rels[0]->idx[modes[0]].rowptr.back();
+            const int64_t t = std::min<int64_t>(2048, (nnz_entity / (2048 * 8) + 63) / 64 * 64);
+            if (t > key.col) key.col = (int)t;
+        }
+        key.col_slots = std::max(1, ctx->n_cus - ctx->reserve_cus) * 4 * 2;       // two waves per SIMD
+        M_other = rels[0]->nint[1 - modes[0]];
+    }
+}
+
+// ---- step 3: the rows of this shard / chunk, and whether the low-rank sampler is on for the entity ----------------------
+bool collect_rows(const PlanKey &key, const bdf_rel *const *rels, const int *modes, std::vector<RowRef> &rows)
+{
+    if (rels[0]->sharded) {
+        // a relation created with a layout holds this rank's rows only, chunk after chunk: `shard` is the chunk
+        const bdf_mode_index &ix0 = rels[0]->idx[modes[0]];
+        for (int64_t o = ix0.chunk_begin[(size_t)key.shard]; o < ix0.chunk_begin[(size_t)key.shard + 1]; o++) {
+            RowRef rr;
+            rr.out = ix0.own_pos[(size_t)o]; rr.orig = ix0.own_orig[(size_t)o];
+            for (int r = 0; r < key.n_terms; r++) {
+                const bdf_mode_index &ix = rels[r]->idx[modes[r]];
+                rr.qb[r] = ix.own_q[(size_t)o]; rr.cnt[r] = ix.own_q[(size_t)o + 1] - ix.own_q[(size_t)o];
+            }
+            rows.push_back(rr);
+        }
+    } else {
+        // rows of this shard: positions shard, shard + n_shards, ... of the degree-descending order of the first
+        // relation (the reference deals rows i:P:N to its P workers for the same balance, sampling.jl:154)
+        const std::vector<int32_t> &order = rels[0]->idx[modes[0]].order;
+        for (size_t pos = (size_t)key.shard; pos < order.size(); pos += (size_t)key.n_shards) {
+            RowRef rr;
+            rr.out = rr.orig = order[pos];
+            for (int r = 0; r < key.n_terms; r++) {
+                const auto &rp = rels[r]->idx[modes[r]].rowptr;
+                rr.qb[r] = rp[(size_t)rr.orig]; rr.cnt[r] = rp[(size_t)rr.orig + 1] - rp[(size_t)rr.orig];
+            }
+            rows.push_back(rr);
+        }
+    }
+    // the low-rank sampler pays its set-up (the opposite factor transformed, two more launches) only with enough rows:
+    // counted over the WHOLE entity (the host's index is the whole relation's on every rank), so that shards, chunks and
+    // ranks decide alike
+    if (key.lr <= 0) return false;
+    const std::vector<int64_t> &rp = rels[0]->idx[modes[0]].rowptr;
+    int64_t cnt = 0;
+    for (size_t i = 0; i + 1 < rp.size(); i++) cnt += rp[i + 1] - rp[i] <= key.lr;
+    return cnt >= key.lr_min && 2 * cnt >= key.lr_other;
+}
+
+// ---- step 6, the two stages with rules of their own --------------------------------------------------------------------
+int launch_lowrank(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t M_other, int64_t n_rows_entity, int shard, hipEvent_t e0, hipEvent_t e1)
+{
+    // the constants of the launch (L, the opposite factor transformed): once per entity launch -- a later chunk of the same
+    // launch (same inputs, same iteration) finds them in the context
+    const LrKey now{a.t[0].fac[0], a.Lambda, a.mu, a.sweep, a.entity_tag, a.D, M_other};
+    const bool same = shard > 0 && now == ctx->rows->lr_key;
+    int rc = bdf_lr_launch(ctx, a, M_other, n_rows_entity, plan.lr_dev, plan.n_lr, plan.n_lr_padded, plan.n_lr32_padded, plan.lr_rows_dev, !same, e0, e1);
+    if (!rc) ctx->rows->lr_key = now;
+    return rc;
+}
+
+int launch_column(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t M_other, bool more, hipEvent_t e0, hipEvent_t e1)
+{
+    static const bool no_coded = getenv("BDF_K1_NO_CODED") != nullptr;               // test hook: ids and values instead of the packed words
+    SampleArgs ac = a;
+    if (no_coded) ac.t[0].packed = nullptr;
+    // the rows' hand-over by counter (SampleArgs::done): only when this launch is ALL of the call's rows
+    if (more || plan.n_lr > 0 || plan.n_small > 0) ac.done = nullptr;
+    if (ac.done) ctx->rows_done_added = plan.col.n_waves;
+    return bdf_col_launch(ctx, ac, plan.col, M_other, e0, e1);
+}
+
+}  // namespace
+
+bdf_rows_state *bdf_rows_state_create() { return new bdf_rows_state(); }
+
+void bdf_rows_state_destroy(bdf_ctx *ctx)
+{
+    if (!ctx->rows) return;
+    bdf_plans_release(ctx, 0);
+    delete ctx->rows;
+    ctx->rows = nullptr;
+}
+
+const std::array<int64_t, 7> *bdf_rows_dispatch_counts(const bdf_ctx *ctx, uint32_t entity_tag)
+{
+    auto it = ctx->rows->dispatch.find(entity_tag);
+    return it == ctx->rows->dispatch.end() ? nullptr : &it->second;
+}
+
+// parity hook: split rows whose pieces did not all arrive in the launches so far (their arrival counters reset themselves
+// when the last piece arrives, so any non-zero counter after a completed launch is a row that was never finished)
+extern "C" int bdf_rows_unfinished(bdf_ctx *ctx, int64_t *count)
+{
+    BDF_REQUIRE(ctx && count, BDF_ERR_ARG, "bdf_rows_unfinished: NULL argument");
+    BDF_HIP(hipStreamSynchronize(ctx->stream));
+    *count = 0;
+    std::lock_guard<std::mutex> lock(g_plans_mutex);
+    for (auto &kv : ctx->rows->plans) {
+        if (kv.second.col.n_split_rows > 0) {
+            std::vector<int32_t> hc((size_t)kv.second.col.n_split_rows);
+            BDF_HIP(hipMemcpy(hc.data(), kv.second.col.arrived_dev, hc.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+            for (int32_t v : hc) *count += v != 0;
+        }
+        const int n = kv.second.dev.n_split_rows;
+        if (n <= 0) continue;
+        std::vector<int32_t> h((size_t)n);
+        BDF_HIP(hipMemcpy(h.data(), kv.second.dev.arrived, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int32_t v : h) *count += v != 0;
+        static const bool dbg = getenv("BDF_DEBUG_UNFINISHED") != nullptr;
+        if (dbg)
+            for (int i = 0; i < n; i++)
+                if (h[(size_t)i] != 0)
+                    fprintf(stderr, "[bdf] unfinished: plan DP=%d T=%d Tp=%d shard %d/%d terms %d, split row %d of %d: counter %d (array %p)\n",
+                            kv.first.DP, kv.first.T, kv.first.Tp, kv.first.shard, kv.first.n_shards, kv.first.n_terms, i, n, h[(size_t)i],
+                            (void *)kv.second.dev.arrived);
+    }
+    return BDF_OK;
+}
+
+void bdf_plans_release(bdf_ctx *ctx, uint64_t rel_serial)
+{
+    std::lock_guard<std::mutex> lock(g_plans_mutex);
+    auto &plans = ctx->rows->plans;
+    for (auto kv = plans.begin(); kv != plans.end();) {
+        bool hit = rel_serial == 0;
+        for (int r = 0; r < kv->first.n_terms; r++) hit = hit || kv->first.rel[r] == rel_serial;
+        if (!hit) { ++kv; continue; }
+        plan_free(kv->second);
+        kv = plans.erase(kv);
+    }
+}
+
+int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *const *rels, const int *modes, int shard,
+                           int n_shards, bool dump)
+{
+    SampleArgs a = a_in;
+    int rc;
+    if (a.prior_b == nullptr) {         // no prior pack from bdf_hyper_sample: derive Lambda mu and the image here
+        // prior part of b: Lambda mu (one vector) or Lambda mu_i for every row (per-row prior means, macau.jl:104)
+        const int64_t nr = a.mu_is_matrix ? rels[0]->nint[modes[0]] : 1;
+        void *pb;
+        if ((rc = bdf_scratch(ctx, ((size_t)nr * a.D + (size_t)bdf_prior_image_doubles(a.D)) * sizeof(double), &pb))) return rc;
+        if ((rc = bdf_prior_launch(ctx, a.D, a.Lambda, a.mu, nr, a.mu_is_matrix, (double *)pb, (double *)pb + nr * a.D))) return rc;
+        a.prior_b = (const double *)pb;
+        a.prior_c = (const double *)pb + nr * a.D;
+    }
+    PlanKey key;
+    int64_t M_other = 0;
+    route_key(ctx, a, rels, modes, shard, n_shards, dump, key, M_other);
+    const Plan *plan;
+    {
+        std::lock_guard<std::mutex> lock(g_plans_mutex);
+        auto &plans = ctx->rows->plans;
+        auto it = plans.find(key);
+        if (it == plans.end()) {
+            std::vector<RowRef> rows;
+            const bool lr_on = collect_rows(key, rels, modes, rows);
+            Plan np;
+            if ((rc = build_plan(ctx, key, rows, lr_on, np))) return rc;
+            it = plans.emplace(key, np).first;
+        }
+        plan = &it->second;
+    }
+    const int64_t work[4] = {plan->n_lr, plan->n_small, plan->col.n_waves, (int64_t)plan->dev.n_split + plan->dev.n_direct};      // in launch order
+    // bdf_ctx_rows_dispatch: the chunks / shards of one iteration's launch of the entity add up
+    std::array<int64_t, 7> &rdsp = ctx->rows->dispatch[a.entity_tag];
+    if (rdsp[0] != (int64_t)a.sweep + 1) rdsp = {(int64_t)a.sweep + 1, 0, 0, 0, 0, 0, 0};
+    rdsp[1] += plan->rows_lr; rdsp[2] += plan->rows_small; rdsp[3] += plan->rows_col; rdsp[4] += plan->rows_k1;
+    rdsp[5] += work[3]; rdsp[6] += work[2];
+    // low-rank, small, column, K1.  A caller's timing events (bdf_ctx_time_next_rows) and with them the hand-over of the draw go
+    // to the stages that have work: the start to the first, the stop to the last, then both are cleared (a system dump is not timed)
+    for (int s = 0; s < 4; s++) {
+        if (work[s] <= 0) continue;
+        const bool more = std::any_of(work + s + 1, work + 4, [](int64_t w) { return w > 0; });
+        const hipEvent_t e0 = dump ? nullptr : ctx->time_start, e1 = (dump || more) ? nullptr : ctx->time_stop;
+        if (s == 0) rc = launch_lowrank(ctx, a, *plan, M_other, rels[0]->nint[modes[0]], shard, e0, e1);
+        else if (s == 1) rc = bdf_small_launch(ctx, a, plan->small_dev, plan->n_small, e0, e1);
+        else if (s == 2) rc = launch_column(ctx, a, *plan, M_other, more, e0, e1);
+        else rc = bdf_k1_launch(ctx, a, plan->dev, dump, e0, e1);
+        if (rc) return rc;
+        if (!dump) { ctx->time_start = nullptr; if (!more) ctx->time_stop = nullptr; }
+    }
+    return BDF_OK;
+}

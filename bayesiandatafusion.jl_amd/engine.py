@@ -813,7 +813,7 @@ class GibbsEngine:
     def lowrank_rows(self, j):
         """rows of entity j the library draws with the low-rank sampler (k_rows_lr.hip) instead of the reference's map -- the
         library's own count for the latest launch (bdf_ctx_rows_dispatch); before the first iteration: the rule of
-        bdf_launch_sample_rows restated from the environment (D > 16, one two-mode relation, no side information on the relation,
+        route_key and collect_rows (rows_plan.hip) restated from the environment (D > 16, one two-mode relation, no side information on the relation,
         rows of at most min(16, D / 2) observations (D > 32: min(32, D / 2)), at least 8,192 of them and at least half as many as the opposite entity has rows)"""
         got = self.rows_dispatch(j)
         if got is not None:

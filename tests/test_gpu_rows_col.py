@@ -110,7 +110,7 @@ def test_col_rows_shards_repeats_and_default_piece(B, O, ctx):
 
 
 def test_col_rows_piece_size_follows_the_entity_and_not_the_shard(B, O, ctx):
-    """An entity of many observations takes larger pieces (bdf_launch_sample_rows: its observation count over 8 x 2,048 nominal slots,
+    """An entity of many observations takes larger pieces (route_key of rows_plan.hip: its observation count over 8 x 2,048 nominal slots,
     between 128 and 2,048) -- here 600 rows of 4,200 observations at D = 30, 2.5 M in all: T = 192, every row spans waves in six parts.
     The cut comes from the WHOLE entity's count: three shards write the bits of one launch, and the library reports the dispatch
     (bdf_ctx_rows_dispatch).  Against the oracle at 1e-8."""
