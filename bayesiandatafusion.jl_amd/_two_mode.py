@@ -19,6 +19,8 @@ def relation_of(data, num_latent, who):
     rel = data.relations[0]
     if rel.data.ids.shape[1] != 2 or len(data.entities) < 2:
         raise ArgumentError(f"{who} works on a matrix relation (2 modes); {rel.name} has {rel.data.ids.shape[1]}")
+    if rel.model.probit:
+        raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the probit noise model (use macau)")
     return D, rel
 
 

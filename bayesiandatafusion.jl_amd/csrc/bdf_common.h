@@ -178,6 +178,7 @@ struct bdf_pairs {
     std::vector<int32_t> ids_host, orig_host;
     std::vector<double> values_host;
     void *auc_ws;                 // bdf_pairs_auc's workspace (bdf_auc_workspace_bytes(n)), allocated at first use
+    int link;                     // bdf_pairs_set_link: 0 identity, 1 probit (predictions are Phi(udot + base): k_probit.hip)
 };
 
 struct bdf_feat {
@@ -360,3 +361,7 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)   // lane mus
 #define BDF_DONE_STRIDE 16         // words between two shards
 
 int bdf_predict_plain(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, double *out);
+// bdf_predict / bdf_predict_update / bdf_predict_sse for pairs with the probit link (k_probit.hip): phase -1 predict only (out),
+// 0..2 the update (count: the pairs' counter before it), 3 statistics only; linear (nullable) overrides the pairs' baseline
+int bdf_predict_link(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, const double *linear,
+                     double *out, int phase, double count, double clamp_lo, double clamp_hi, double class_cut, double *stats_out);

@@ -348,10 +348,12 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
     BDF_REQUIRE(g && n_relations >= 0 && (n_relations == 0 || rels), BDF_ERR_ARG, "bdf_gibbs_set_relations: bad argument");
     for (int k = 0; k < n_relations; k++) {
         const bdf_gibbs_relation &r = rels[k];
-        BDF_REQUIRE(r.rel && r.alpha_dev, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d has no handle or no alpha_dev", k);
+        BDF_REQUIRE(r.rel && (r.alpha_dev || r.probit), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d has no handle or no alpha_dev", k);
         BDF_REQUIRE(!(r.alpha_sample || r.feat) || r.train, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d needs its observations as pairs (train)", k);
         BDF_REQUIRE(!r.feat || (r.beta && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d has features but no beta / linear buffer", k);
         BDF_REQUIRE(!r.feat_test || r.test_baseline, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d has test features but no baseline buffer", k);
+        BDF_REQUIRE(!r.probit || (!r.feat && !r.alpha_sample), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the probit model takes neither relation features nor a sampled alpha", k);
+        BDF_REQUIRE(!r.probit || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the probit model needs its observations as pairs (train) and a linear buffer", k);
         for (int m = 0; m < r.rel->n_modes; m++)
             BDF_REQUIRE(r.entity_of_mode[m] >= 0 && r.entity_of_mode[m] < (int)g->ent.size(), BDF_ERR_ARG,
                         "bdf_gibbs_set_relations: relation %d mode %d names entity %d", k, m, r.entity_of_mode[m]);
@@ -377,7 +379,7 @@ int update_relations(bdf_gibbs *g)
     const int D = g->D;
     int rc;
     for (const auto &r : g->rels) {
-        if (!r.alpha_sample && !r.feat) continue;
+        if (!r.alpha_sample && !r.feat && !r.probit) continue;
         const double *fac[BDF_MAX_MODES];
         for (int m = 0; m < r.rel->n_modes; m++) {
             const auto &O = g->ent[(size_t)r.entity_of_mode[m]];
@@ -389,6 +391,8 @@ int update_relations(bdf_gibbs *g)
             if (g->comm && (rc = bdf_sum_ranks(R, g->comm, g->rel_sse + 1, 1))) return rc;
             if ((rc = bdf_sample_alpha(R, r.alpha_lambda0, r.alpha_nu0, r.nnz, g->rel_sse + 1, r.rel_tag, r.alpha_dev))) return rc;
         }
+        // probit: the latent z of every observation given the rows; the rows then see linear = y - z with alpha = 1
+        if (r.probit && (rc = bdf_probit_draw(R, r.train, D, fac, r.mean_value, r.rel_tag, r.linear + r.first_obs, nullptr))) return rc;
         if (r.feat) {
             if ((rc = bdf_sample_beta_rel_impl(R, g->comm, r.feat, r.train, r.first_obs, D, fac, r.mean_value, 1.0, r.alpha_dev, r.lambda_beta,
                                                r.rel_tag, r.beta, r.linear + r.first_obs, nullptr)))
@@ -435,8 +439,9 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
         terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
         terms[t].alpha_dev = nullptr;
         if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {
-            terms[t].alpha_dev = gr->alpha_dev;
-            terms[t].linear_values = gr->feat ? gr->linear : nullptr;
+            terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
+            terms[t].linear_values = (gr->feat || gr->probit) ? gr->linear : nullptr;
+            if (gr->probit) terms[t].alpha = 1.0;
         }
         for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
         for (int k = 0; k < e.terms[t].rel->n_modes; k++) {
@@ -499,7 +504,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
     }
     if (g->stats_dev) pieces.push_back({g->stats_dev, 4 * sizeof(double), false, 0});       // the prediction statistics of the last real update
     for (const auto &r : g->rels) {         // the relation models: alpha, relation-level beta, linear_values, the test pairs' baseline
-        pieces.push_back({r.alpha_dev, sizeof(double), false, 0});
+        if (r.alpha_dev) pieces.push_back({r.alpha_dev, sizeof(double), false, 0});
         if (r.feat) {
             int world = 1, rk = 0;
             if (g->comm) (void)bdf_comm_size(g->comm, &rk, &world);
@@ -507,6 +512,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
             pieces.push_back({r.linear, (size_t)r.obs_block * (size_t)world * sizeof(double), false, 0});
             if (r.feat_test) pieces.push_back({r.test_baseline, (size_t)r.feat_test->m * sizeof(double), false, 0});
         }
+        if (r.probit) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});     // y - z of the last draw
     }
     size_t total = 0;
     for (auto &pc : pieces) total += (pc.bytes + 255) & ~(size_t)255;
@@ -679,8 +685,9 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
             terms[t].alpha_dev = nullptr;
             if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {        // a relation with a model of its own
-                terms[t].alpha_dev = gr->alpha_dev;
-                terms[t].linear_values = gr->feat ? gr->linear : nullptr;
+                terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
+                terms[t].linear_values = (gr->feat || gr->probit) ? gr->linear : nullptr;
+                if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
             }
             for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
             for (int k = 0; k < e.terms[t].rel->n_modes; k++) {

@@ -4,91 +4,11 @@
 // dimension of the product of the modes' factor rows (src/sampling.jl:30-45).  8 lanes share one test pair and read
 // 32 bytes each, so that a gathered factor row is read as whole 128-byte segments.
 #include "bdf_common.h"
+#include "predict.h"
 #include <algorithm>
 #include <cstdlib>
 
 namespace {
-
-
-struct PredArgs {
-    int D, n_modes;
-    int64_t n;
-    const int32_t *ids;            // n_modes planes of n, 0-based
-    const double *fac[BDF_MAX_MODES];
-    double mean;
-    const double *linear;          // nullable: per-pair baseline instead of mean (relation features: linear_values)
-    const int32_t *orig;           // nullable: the pairs are stored sorted; orig[pair] = the caller's index (out, linear)
-    int sorted_mode;               // the mode they are sorted by (-1: none)
-    const double *values;
-    double *out;                   // nullable: raw predictions
-    double *avg, *sq;              // running state (update mode)
-    int phase;                     // -1: predict only
-    double count, clamp_lo, clamp_hi, cut;
-    double *stats;
-    double *partial;               // per-block statistics
-};
-
-__device__ inline double clampv(double x, double lo, double hi)
-{
-    if (lo > hi) return x;
-    return x < lo ? lo : (x > hi ? hi : x);
-}
-
-// ---- what a lane does for the pair it owns: everything of macau.jl:142-184 that is not the gather -----------------------
-// A group of 8 lanes computes the dot products of 8 consecutive pairs together (32 bytes of a factor row per lane) and then
-// lane `sub` owns pair p0 + sub: ids, value and running state are read 8 consecutive pairs per group and instruction before
-// the first gather is issued, and written back the same way.  (One lane per group doing the updates one after the other
-// issued six times as many memory instructions as the gather itself, each with 8 active lanes 128 B apart.)
-struct PairState {
-    int64_t pm, po;                // storage position; the caller's index (out, linear)
-    bool ok;
-    double y, av, sv, base;
-};
-
-__device__ inline void pair_load(const PredArgs &a, int64_t p, PairState &s)
-{
-    s.ok = p < a.n;
-    s.pm = s.ok ? p : a.n - 1;
-    s.po = a.orig ? (int64_t)a.orig[s.pm] : s.pm;
-    s.base = a.linear ? a.linear[s.po] : a.mean;
-    s.y = a.phase >= 0 ? a.values[s.pm] : 0.0;
-    s.av = 0.0; s.sv = 0.0;
-    if (a.phase == 2) { s.av = a.avg[s.pm]; s.sv = a.sq[s.pm]; }
-}
-
-__device__ inline void pair_finish(const PredArgs &a, const PairState &s, double dot, double (&st)[4])
-{
-    if (!s.ok) return;
-    const double p = dot + s.base;
-    if (a.out) a.out[s.po] = p;
-    if (a.phase >= 0) {
-        double avg;
-        if (a.phase == 0 || a.phase == 3) { avg = p; }
-        else if (a.phase == 1) { avg = p; a.sq[s.pm] = p * p; }
-        else { avg = (a.count * s.av + p) / (a.count + 1.0); a.sq[s.pm] = s.sv + p * p; }
-        if (a.phase != 3) a.avg[s.pm] = avg;           // phase 3: statistics of this sample only, no running state
-        const double ea = s.y - clampv(avg, a.clamp_lo, a.clamp_hi), ep = s.y - clampv(p, a.clamp_lo, a.clamp_hi);
-        const bool label = s.y < a.cut;
-        st[0] += ea * ea; st[1] += ep * ep;
-        st[2] += (label == (avg < a.cut)) ? 1.0 : 0.0;
-        st[3] += (label == (p < a.cut)) ? 1.0 : 0.0;
-    }
-}
-
-__device__ inline void block_stats(const PredArgs &a, const double (&st)[4])
-{
-    __shared__ double red[4][256 / 64];
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        double v = st[q];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-        if ((tid & 63) == 0) red[q][tid >> 6] = v;
-    }
-    __syncthreads();
-    if (tid < 4) a.partial[blockIdx.x * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
-}
 
 // General kernel: NM modes, any order of the pairs.  VEC = 4: D a multiple of 4, NC 32-byte pieces of a row per lane
 // (D <= 32: one, D <= 64: two); VEC = 1: any D, a lane takes elements sub, sub + 8, ...  A trip is 8 consecutive pairs, their
@@ -213,26 +133,6 @@ __global__ __launch_bounds__(256) void k_predict_runs(PredArgs a)
     if (a.phase >= 0) block_stats(a, st);
 }
 
-// fixed-order sum of the per-block statistics
-__global__ __launch_bounds__(256) void k_predict_final(int nblocks, const double *partial, double *stats)
-{
-    __shared__ double red[4][4];
-    const int tid = threadIdx.x;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int b = tid; b < nblocks; b += 256)
-#pragma unroll
-        for (int q = 0; q < 4; q++) v[q] += partial[b * 4 + q];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        double x = v[q];
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
-        if ((tid & 63) == 0) red[q][tid >> 6] = x;
-    }
-    __syncthreads();
-    if (tid < 4) stats[tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
-}
-
 int launch_predict(bdf_ctx *ctx, PredArgs &a)
 {
     if (a.n == 0) return BDF_OK;
@@ -267,23 +167,6 @@ int launch_predict(bdf_ctx *ctx, PredArgs &a)
 #undef PRED
     if (a.phase >= 0) hipLaunchKernelGGL(k_predict_final, dim3(1), dim3(256), 0, ctx->stream, nblocks, (const double *)a.partial, a.stats);
     BDF_HIP(hipGetLastError());
-    return BDF_OK;
-}
-
-int fill(const char *who, bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, PredArgs &a)
-{
-    BDF_REQUIRE(ctx && p && factors, BDF_ERR_ARG, "%s: NULL argument", who);
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "%s: num_latent=%d must be in 1..%d", who, D, BDF_MAX_D);
-    memset(&a, 0, sizeof(a));
-    a.D = D; a.n_modes = p->n_modes; a.n = p->n; a.ids = p->ids_dev; a.values = p->values_dev;
-    for (int k = 0; k < p->n_modes; k++) {
-        BDF_REQUIRE(factors[k] != nullptr, BDF_ERR_ARG, "%s: factors[%d] is NULL", who, k);
-        a.fac[k] = factors[k];
-    }
-    a.phase = -1;
-    a.linear = p->baseline_dev;
-    a.orig = p->orig_dev;
-    a.sorted_mode = p->orig_dev ? p->sorted_mode : -1;
     return BDF_OK;
 }
 
@@ -378,7 +261,7 @@ extern "C" int bdf_pairs_create(bdf_ctx *ctx, int n_modes, int64_t n, const void
     }
     bdf_pairs *p = new bdf_pairs();
     p->ctx = ctx; p->n_modes = n_modes; p->n = n; p->count = 0.0; p->baseline_dev = nullptr; p->orig_dev = nullptr; p->sorted_mode = -1;
-    p->ids_dev = nullptr; p->values_dev = nullptr; p->avg_dev = nullptr; p->sq_dev = nullptr; p->auc_ws = nullptr;
+    p->ids_dev = nullptr; p->values_dev = nullptr; p->avg_dev = nullptr; p->sq_dev = nullptr; p->auc_ws = nullptr; p->link = 0;
     struct Guard { bdf_pairs *p; ~Guard() { if (p) bdf_pairs_destroy(p); } } guard{p};        // error paths free what was allocated
     p->ids_host = h;
     p->values_host.assign(values, values + (n ? n : 0));
@@ -421,7 +304,7 @@ extern "C" int bdf_predict(bdf_ctx *ctx, const bdf_pairs *p, int D, const double
     if (rc) return rc;
     BDF_REQUIRE(out != nullptr, BDF_ERR_ARG, "bdf_predict: out is NULL");
     a.mean = mean_value; a.out = out;
-    return launch_predict(ctx, a);
+    return p->link ? bdf_predict_link(ctx, p, D, factors, mean_value, nullptr, out, -1, 0.0, 1.0, 0.0, 0.0, nullptr) : launch_predict(ctx, a);
 }
 
 // udot + mean_value, whatever baseline the pairs carry (sample_beta_rel needs the residual against the plain mean)
@@ -445,7 +328,8 @@ extern "C" int bdf_predict_update(bdf_ctx *ctx, bdf_pairs *p, int D, const doubl
     BDF_REQUIRE(phase >= 0 && phase <= 2, BDF_ERR_ARG, "bdf_predict_update: phase must be 0, 1 or 2");
     a.mean = mean_value; a.avg = p->avg_dev; a.sq = p->sq_dev; a.phase = phase; a.count = p->count;
     a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi; a.cut = class_cut; a.stats = stats_out;
-    rc = launch_predict(ctx, a);
+    rc = p->link ? bdf_predict_link(ctx, p, D, factors, mean_value, nullptr, nullptr, phase, p->count, clamp_lo, clamp_hi, class_cut, stats_out)
+                 : launch_predict(ctx, a);
     if (rc) return rc;
     if (phase == 1) p->count = 1.0;
     else if (phase == 2) p->count += 1.0;
@@ -463,6 +347,7 @@ extern "C" int bdf_predict_sse(bdf_ctx *ctx, const bdf_pairs *p, int D, const do
     BDF_REQUIRE(stats_out != nullptr, BDF_ERR_ARG, "bdf_predict_sse: stats_out is NULL");
     a.mean = mean_value; if (linear_values) a.linear = linear_values; a.phase = 3; a.count = 0.0;
     a.clamp_lo = 1.0; a.clamp_hi = 0.0; a.cut = 0.0; a.stats = stats_out;
+    if (p->link) return bdf_predict_link(ctx, p, D, factors, mean_value, linear_values, nullptr, 3, 0.0, 1.0, 0.0, 0.0, stats_out);
     return launch_predict(ctx, a);
 }
 
@@ -509,6 +394,14 @@ extern "C" int bdf_pairs_set_baseline(bdf_pairs *p, const double *baseline)
 {
     BDF_REQUIRE(p != nullptr, BDF_ERR_ARG, "bdf_pairs_set_baseline: NULL argument");
     p->baseline_dev = baseline;
+    return BDF_OK;
+}
+
+extern "C" int bdf_pairs_set_link(bdf_pairs *p, int link)
+{
+    BDF_REQUIRE(p != nullptr, BDF_ERR_ARG, "bdf_pairs_set_link: NULL argument");
+    BDF_REQUIRE(link == 0 || link == 1, BDF_ERR_ARG, "bdf_pairs_set_link: link=%d must be 0 (identity) or 1 (probit)", link);
+    p->link = link;
     return BDF_OK;
 }
 

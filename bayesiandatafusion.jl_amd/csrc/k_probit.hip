@@ -1,0 +1,211 @@
+// k_probit.hip -- the probit noise model for 0/1 relations: y = 1[z > 0], z ~ N(udot + mean_value, 1).
+//
+// bdf_probit_draw: the latent z of every training observation given the current factors -- the gather and dot product of
+// k_predict.hip and, in the lane that owns the pair, one uniform of the observation's own stream mapped to the truncated
+// normal (probit.h).  It writes linear[k] = y_k - z_k: the row kernels, which form b_i = Lambda mu_i + alpha sum w (y - base) with
+// the per-observation base = linear_values[k], then sample the rows of z's Gaussian model with alpha = 1, unchanged.
+//
+// The probit link of the prediction kernels (bdf_pairs_set_link): p = Phi(udot + base) in place of udot + base, in kernels of
+// this unit, so that the instantiations of k_predict.hip stay as they are.
+//
+// Layout as k_predict.hip: 8 lanes share a pair and read 32 bytes each; ids and values are loaded 8 consecutive pairs per
+// group before the first gather; BATCH pairs' rows are in flight.  No LDS in the draw, no scratch, plain vector stores.
+#include "bdf_common.h"
+#include "predict.h"
+#include <algorithm>
+
+namespace {
+
+// the dot products of the 8 consecutive pairs p0 .. p0 + 7 of a group of 8 lanes; my[k]: the id in mode k of pair p0 + sub.
+// Returns, in lane sub, the dot product of pair p0 + sub.  VEC = 4: D a multiple of 4, NC 32-byte pieces of a row per lane
+// (D <= 32: one, D <= 64: two); VEC = 1: any D, a lane takes elements sub, sub + 8, ...
+template <int NM, int VEC, int NC>
+__device__ __forceinline__ double group_dots(const double *const (&fac)[BDF_MAX_MODES], int D, int64_t n, int64_t p0, int sub,
+                                             const int32_t (&my)[NM])
+{
+    constexpr int BATCH = (VEC == 1) ? 2 : (NC * NM <= 3 ? 4 : 2);
+    double keep = 0.0;
+#pragma unroll
+    for (int u0 = 0; u0 < 8; u0 += BATCH) {
+        if (p0 + u0 >= n) break;                       // group-uniform
+        double s[BATCH];
+        if constexpr (VEC == 4) {
+            double4 f[BATCH][NM][NC];
+#pragma unroll
+            for (int u = 0; u < BATCH; u++)
+#pragma unroll
+                for (int k = 0; k < NM; k++) {
+                    const double *row = fac[k] + (int64_t)__shfl(my[k], u0 + u, 8) * D;
+#pragma unroll
+                    for (int c = 0; c < NC; c++) {
+                        const int e = sub * 4 + 32 * c;
+                        f[u][k][c] = e < D ? *(const double4 *)(row + e) : double4{0.0, 0.0, 0.0, 0.0};
+                    }
+                }
+#pragma unroll
+            for (int u = 0; u < BATCH; u++) {
+                double acc = 0.0;
+#pragma unroll
+                for (int c = 0; c < NC; c++) {
+                    double4 p = f[u][0][c];
+#pragma unroll
+                    for (int k = 1; k < NM; k++) { p.x *= f[u][k][c].x; p.y *= f[u][k][c].y; p.z *= f[u][k][c].z; p.w *= f[u][k][c].w; }
+                    if (sub * 4 + 32 * c < D) acc += (p.x + p.y) + (p.z + p.w);
+                }
+                s[u] = acc;
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < BATCH; u++) {
+                const double *row[NM];
+#pragma unroll
+                for (int k = 0; k < NM; k++) row[k] = fac[k] + (int64_t)__shfl(my[k], u0 + u, 8) * D;
+                double acc = 0.0;
+                for (int e = sub; e < D; e += 8) {
+                    double p = 1.0;
+#pragma unroll
+                    for (int k = 0; k < NM; k++) p *= row[k][e];
+                    acc += p;
+                }
+                s[u] = acc;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < BATCH; u++) {
+            double v = s[u];
+            v += __shfl_xor(v, 4); v += __shfl_xor(v, 2); v += __shfl_xor(v, 1);
+            if (sub == u0 + u) keep = v;
+        }
+    }
+    return keep;
+}
+
+struct DrawArgs {
+    int D;
+    int64_t n;
+    const int32_t *ids;            // n_modes planes of n, 0-based
+    const double *fac[BDF_MAX_MODES];
+    const double *values;
+    const int32_t *orig;           // nullable: the pairs are stored sorted; orig[pair] = the caller's index
+    double mean;
+    uint64_t seed;
+    uint32_t sweep, entity;        // entity = 0x800000 | rel_tag
+    double *linear, *z;            // z nullable
+};
+
+// (Registers: the gather holds BATCH x NM x NC double4 and the owner's erfc / inverse-CDF polynomials want ~60 more; bounded to
+// three waves per SIMD -- 168 registers, no scratch -- except the widest gather, which k_predict.hip also runs at two.  At four
+// waves the 3- and 4-mode variants spill.)
+template <int NM, int VEC, int NC>
+__global__ __launch_bounds__(256, (VEC == 4 && NM * NC >= 8) ? 2 : 3) void k_probit_draw(DrawArgs a)
+{
+    const int tid = threadIdx.x, sub = tid & 7;
+    const int64_t ngroups = (int64_t)gridDim.x * 32, ntrips = (a.n + 7) / 8;
+    for (int64_t trip = (int64_t)blockIdx.x * 32 + tid / 8; trip < ntrips; trip += ngroups) {
+        const int64_t p0 = trip * 8, p = p0 + sub;
+        const bool ok = p < a.n;
+        const int64_t pm = ok ? p : a.n - 1;
+        const int64_t po = a.orig ? (int64_t)a.orig[pm] : pm;
+        const double y = a.values[pm];
+        int32_t my[NM];
+#pragma unroll
+        for (int k = 0; k < NM; k++) my[k] = a.ids[(int64_t)k * a.n + pm];
+        const double dot = group_dots<NM, VEC, NC>(a.fac, a.D, a.n, p0, sub, my);
+        if (!ok) continue;
+        // the observation's own uniform: the stream is keyed by the caller's index, not by where the pair is stored
+        const double u = bdf_uniform(a.seed, a.sweep, BDF_P_PROBIT, a.entity, (uint64_t)po, 0);
+        const double z = bdf_probit_z(dot + a.mean, y, u);
+        a.linear[po] = y - z;
+        if (a.z) a.z[po] = z;
+    }
+}
+
+// k_predict<NM, VEC, NC> of k_predict.hip with the probit link in what the owning lane does (pair_finish<1>).  (Unbounded: with
+// the running state and the four statistics live beside erfc, any bound above two waves per SIMD spills the VEC = 4 variants.)
+template <int NM, int VEC, int NC>
+__global__ __launch_bounds__(256) void k_predict_link(PredArgs a)
+{
+    const int tid = threadIdx.x, sub = tid & 7;
+    double st[4] = {0.0, 0.0, 0.0, 0.0};
+    const int64_t ngroups = (int64_t)gridDim.x * 32, ntrips = (a.n + 7) / 8;
+    for (int64_t trip = (int64_t)blockIdx.x * 32 + tid / 8; trip < ntrips; trip += ngroups) {
+        const int64_t p0 = trip * 8;
+        PairState ps;
+        pair_load(a, p0 + sub, ps);
+        int32_t my[NM];
+#pragma unroll
+        for (int k = 0; k < NM; k++) my[k] = a.ids[(int64_t)k * a.n + ps.pm];
+        const double keep = group_dots<NM, VEC, NC>(a.fac, a.D, a.n, p0, sub, my);
+        pair_finish<1>(a, ps, keep, st);
+    }
+    if (a.phase >= 0) block_stats(a, st);
+}
+
+// the kernel variant by the number of modes, D % 4 and D <= 32, as launch_predict of k_predict.hip chooses it
+#define BDF_BY_SHAPE(KERNEL, n_modes, D, nblocks, stream, args)                                                             \
+    do {                                                                                                                     \
+        const bool vec__ = ((D) & 3) == 0;                                                                                   \
+        const int nc__ = (D) <= 32 ? 1 : 2;                                                                                  \
+        if ((n_modes) == 2) {                                                                                                \
+            if (!vec__) hipLaunchKernelGGL((KERNEL<2, 1, 1>), dim3(nblocks), dim3(256), 0, stream, args);                    \
+            else if (nc__ == 1) hipLaunchKernelGGL((KERNEL<2, 4, 1>), dim3(nblocks), dim3(256), 0, stream, args);            \
+            else hipLaunchKernelGGL((KERNEL<2, 4, 2>), dim3(nblocks), dim3(256), 0, stream, args);                           \
+        } else if ((n_modes) == 3) {                                                                                         \
+            if (!vec__) hipLaunchKernelGGL((KERNEL<3, 1, 1>), dim3(nblocks), dim3(256), 0, stream, args);                    \
+            else if (nc__ == 1) hipLaunchKernelGGL((KERNEL<3, 4, 1>), dim3(nblocks), dim3(256), 0, stream, args);            \
+            else hipLaunchKernelGGL((KERNEL<3, 4, 2>), dim3(nblocks), dim3(256), 0, stream, args);                           \
+        } else {                                                                                                             \
+            if (!vec__) hipLaunchKernelGGL((KERNEL<4, 1, 1>), dim3(nblocks), dim3(256), 0, stream, args);                    \
+            else if (nc__ == 1) hipLaunchKernelGGL((KERNEL<4, 4, 1>), dim3(nblocks), dim3(256), 0, stream, args);            \
+            else hipLaunchKernelGGL((KERNEL<4, 4, 2>), dim3(nblocks), dim3(256), 0, stream, args);                           \
+        }                                                                                                                    \
+    } while (0)
+
+}  // namespace
+
+int bdf_predict_link(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, const double *linear,
+                     double *out, int phase, double count, double clamp_lo, double clamp_hi, double class_cut, double *stats_out)
+{
+    PredArgs a;
+    int rc = fill("bdf_predict (probit link)", ctx, p, D, factors, a);
+    if (rc) return rc;
+    a.mean = mean_value; a.out = out; a.phase = phase; a.count = count;
+    if (linear) a.linear = linear;
+    if (phase >= 0) {
+        a.avg = p->avg_dev; a.sq = p->sq_dev; a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi; a.cut = class_cut; a.stats = stats_out;
+    }
+    if (a.n == 0) return BDF_OK;
+    const int64_t ntrips = (a.n + 7) / 8;
+    const int nblocks = (int)std::min<int64_t>((ntrips + 31) / 32, 8192);
+    if (phase >= 0) {
+        void *sc;
+        if ((rc = bdf_scratch(ctx, (size_t)nblocks * 4 * sizeof(double), &sc))) return rc;
+        a.partial = (double *)sc;
+    }
+    BDF_BY_SHAPE(k_predict_link, a.n_modes, D, nblocks, ctx->stream, a);
+    if (phase >= 0) hipLaunchKernelGGL(k_predict_final, dim3(1), dim3(256), 0, ctx->stream, nblocks, (const double *)a.partial, a.stats);
+    BDF_HIP(hipGetLastError());
+    return BDF_OK;
+}
+
+extern "C" int bdf_probit_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value,
+                               uint32_t rel_tag, double *linear_out, double *z_out)
+{
+    BDF_REQUIRE(ctx && train && factors && linear_out, BDF_ERR_ARG, "bdf_probit_draw: NULL argument");
+    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_probit_draw: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
+    DrawArgs a;
+    memset(&a, 0, sizeof(a));
+    a.D = D; a.n = train->n; a.ids = train->ids_dev; a.values = train->values_dev; a.orig = train->orig_dev;
+    for (int k = 0; k < train->n_modes; k++) {
+        BDF_REQUIRE(factors[k] != nullptr, BDF_ERR_ARG, "bdf_probit_draw: factors[%d] is NULL", k);
+        a.fac[k] = factors[k];
+    }
+    a.mean = mean_value; a.seed = ctx->seed; a.sweep = ctx->sweep_host; a.entity = 0x800000u | rel_tag;
+    a.linear = linear_out; a.z = z_out;
+    if (a.n == 0) return BDF_OK;
+    const int64_t ntrips = (a.n + 7) / 8;
+    const int nblocks = (int)std::min<int64_t>((ntrips + 31) / 32, 8192);
+    BDF_BY_SHAPE(k_probit_draw, train->n_modes, D, nblocks, ctx->stream, a);
+    BDF_HIP(hipGetLastError());
+    return BDF_OK;
+}

@@ -58,6 +58,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if output_type not in ("csv", "binary"):
         raise ArgumentError("output_type must be either \"csv\" or \"binary\".")
     clamp = [float(c) for c in clamp]
+    if full_prediction and data.relations and data.relations[0].model.probit:
+        raise ArgumentError("Prediction of all elements is not possible when Relation has the probit noise model.")
 
     verbose and print("Model setup")
     eng = engine

@@ -26,6 +26,7 @@ import torch
 from . import _lib
 from . import features as feat
 from ._lib import ArgumentError, GibbsEntity, Term, check, lib
+from .relation_data import check_probit
 
 
 def _ptr(t):
@@ -291,6 +292,11 @@ class DevicePairs:
         check(lib().bdf_pairs_sort(self.handle, int(mode0)))
         self._order = np.zeros(self.n, dtype=np.int64)
         check(lib().bdf_pairs_order(self.handle, self._order.ctypes.data_as(_lib.c_i64p)))
+        return self
+
+    def set_link(self, link):
+        """0: predictions are udot + base (the default); 1: the probit link, probabilities Phi(udot + base) (bdf_pairs_set_link)"""
+        check(lib().bdf_pairs_set_link(self.handle, int(link)))
         return self
 
     def _facs(self, factors):
@@ -592,6 +598,11 @@ class GibbsEngine:
                  full_lambda_u=True, tol=float("nan"), shard=None, chunks=None):
         if not (1 <= num_latent <= _lib.BDF_MAX_D):
             raise ArgumentError(f"num_latent={num_latent} must be in 1..{_lib.BDF_MAX_D}")
+        for r in data.relations:
+            if r.model.probit:
+                check_probit(r)
+                if shard is not None and shard[1] > 1:
+                    raise ArgumentError(f"Relation {r.name} has the probit noise model: one rank only")
         self.data, self.D = data, int(num_latent)
         # The row context runs on a stream of its own that leaves a few CUs (one or two per XCD) free for the hyperprior's
         # small kernels, which otherwise wait for slots beside the chip-filling row kernel -- when the entities are small
@@ -649,7 +660,7 @@ class GibbsEngine:
                 raise ArgumentError(f"Relation {r.name} has {len(r.entities)} entities but its data implies {r.data.size()}.")
             lays = [self.layouts[self._entity_index(e)] for e in r.entities]
             dr = DeviceRelation(self.ctx, r.data, lays if self.world > 1 else None, self.rank)
-            r.model.mean_value = dr.value_mean()
+            r.model.mean_value = 0.0 if r.model.probit else dr.value_mean()      # (probit: the latent is not centred)
             r._dev = dr
             self.rel.append(dr)
             # relation-level side information (RelationData.jl:348-353): FF path only, as in the reference
@@ -676,6 +687,14 @@ class GibbsEngine:
                 dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids)[dr.obs_lo:dr.obs_hi], np.asarray(r.data.values)[dr.obs_lo:dr.obs_hi])
                 if dr.F is not None:         # pred(r) = udot + linear_values on the training table (sampling.jl:16-18)
                     check(lib().bdf_pairs_set_baseline(dr.train.handle, C.c_void_p(dr.linear.data_ptr() + 8 * dr.obs_lo)))
+            if r.model.probit:
+                # the latent z of every observation is drawn before the rows of every iteration (bdf_probit_draw) and handed to
+                # the row kernels as linear_values = y - z with alpha = 1; the training pairs predict probabilities (rmse_train)
+                dr.linear = self.ctx.zeros(max(nn, 1))
+                dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
+                if len(r.entities) == 2 and nn:
+                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
+                dr.train.set_link(1)
             dr.alpha_dev = self.ctx.tensor([float(r.model.alpha)])
         self._test_pairs = None
         self._train_pairs = None
@@ -747,7 +766,8 @@ class GibbsEngine:
         if not self.gibbs:
             return
         from ._lib import GibbsRelation
-        rows = [(ri, r, self.rel[ri]) for ri, r in enumerate(self.data.relations) if r.model.alpha_sample or self.rel[ri].F is not None]
+        rows = [(ri, r, self.rel[ri]) for ri, r in enumerate(self.data.relations)
+                if r.model.alpha_sample or self.rel[ri].F is not None or r.model.probit]
         arr = (GibbsRelation * max(len(rows), 1))()
         for k, (ri, r, dr) in enumerate(rows):
             g = arr[k]
@@ -760,6 +780,8 @@ class GibbsEngine:
             g.alpha_lambda0, g.alpha_nu0, g.nnz = r.model.alpha_lambda0, r.model.alpha_nu0, r.data.nnz()
             g.train = dr.train.handle
             g.first_obs, g.obs_block = dr.obs_lo, dr.obs_block
+            if r.model.probit:
+                g.probit, g.linear = 1, dr.linear.data_ptr()
             if dr.F is not None:
                 g.feat, g.beta, g.linear, g.lambda_beta = dr.F.handle, dr.beta.data_ptr(), dr.linear.data_ptr(), r.model.lambda_beta
                 if ri == 0 and getattr(dr, "F_test", None) is not None:
@@ -845,7 +867,7 @@ class GibbsEngine:
             ri = [x is r for x in self.data.relations].index(True)
             terms[t].rel = self.rel[ri].handle
             terms[t].mode = en.modes[t] - 1
-            terms[t].alpha = r.model.alpha
+            terms[t].alpha = 1.0 if r.model.probit else r.model.alpha
             terms[t].mean_value = r.model.mean_value
             terms[t].linear_values = self.rel[ri].linear.data_ptr() if self.rel[ri].linear is not None else None
             terms[t].alpha_dev = self.rel[ri].alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
@@ -860,9 +882,13 @@ class GibbsEngine:
         kernel's arguments: sampling it costs one device-to-host read per sweep, as the reference's host loop does)"""
         for ri, r in enumerate(self.data.relations):
             dr = self.rel[ri]
-            if not (r.model.alpha_sample or dr.F is not None):
+            if not (r.model.alpha_sample or dr.F is not None or r.model.probit):
                 continue
             facs = self.factors_of(r)
+            if r.model.probit:           # z | U, V: the rows of this iteration then see linear_values = y - z, alpha = 1
+                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
+                check(lib().bdf_probit_draw(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, ri + 1, _ptr(dr.linear), None))
+                continue
             comm = self.comm.handle if (self.world > 1 and self.comm is not None) else None
             if r.model.alpha_sample:
                 sse = dr.train.sse(self.D, facs, r.model.mean_value)          # the pairs carry linear_values as baseline
@@ -1128,6 +1154,8 @@ class GibbsEngine:
                 # row in registers over a run of pairs and gathers only the other mode's (k_predict_runs); results stay in
                 # the caller's order
                 self._test_pairs.sort(int(np.argmin(r.data.dims)))
+            if r.model.probit:               # predictions are probabilities Phi(udot)
+                self._test_pairs.set_link(1)
             dr = self.rel[0]
             if dr.F is not None:             # pred(r, probe_vec, F) = udot + F_test beta + mean_value (sampling.jl:9-14)
                 if feat.isempty(r.test_F):

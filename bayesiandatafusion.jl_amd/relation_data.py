@@ -78,7 +78,7 @@ def toStr(x):
             if x.lambda_beta_sample:
                 s += f" λ={x.lambda_beta:1.1f}"
         return f"{x.name[:3]}[{s}]"
-    s = f"α={x.model.alpha:2.1f}"
+    s = "probit" if x.model.probit else f"α={x.model.alpha:2.1f}"
     if hasFeatures(x) and x.model.beta is not None and len(x.model.beta):
         s += f" β:{np.linalg.norm(x.model.beta):2.1f}"
     return f"{x.name[:4]}[{s}]"
@@ -95,6 +95,7 @@ class RelationModel:
         self.alpha = float(alpha)
         self.beta = np.zeros(0)
         self.mean_value = 0.0
+        self.probit = False       # setProbit: 0/1 values with the probit noise model instead of Gaussian noise of precision alpha
 
 
 class RelationTemp:
@@ -203,7 +204,44 @@ def numTest(r):
 
 
 def setPrecision(r, precision):
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model: its latent has unit variance, there is no precision to set.")
     r.model.alpha = float(precision)
+
+
+def _is_binary(values):
+    values = np.asarray(values)
+    return bool(np.all((values == 0) | (values == 1)))
+
+
+def setProbit(r):
+    """Probit noise model for a relation of 0/1 values (the reference has Gaussian noise only): y = 1[z > 0] with a latent
+    z ~ N(u'v, 1) that macau() samples beside the rows.  Predictions become probabilities Phi(u'v), class_cut 0.5.  Works before
+    or after assignToTest / setTest; every training and test value must be exactly 0 or 1."""
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: the probit noise model does not take relation-level side information.")
+    if r.model.alpha_sample:
+        raise ArgumentError(f"Relation {r.name} samples its precision (alpha_sample): the probit latent has unit variance.")
+    if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
+        raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the probit noise model.")
+    r.model.probit = True
+    r.model.alpha = 1.0
+    r.model.alpha_sample = False
+    r.model.mean_value = 0.0
+    r.class_cut = 0.5
+    r.test_label = r.test_vec.values < r.class_cut
+    r._dev = None
+    return None
+
+
+def check_probit(r):
+    """what a probit relation must still satisfy when a sampler is built on it (it may have been changed since setProbit)"""
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: the probit noise model does not take relation-level side information.")
+    if r.model.alpha_sample:
+        raise ArgumentError(f"Relation {r.name} samples its precision (alpha_sample): the probit latent has unit variance.")
+    if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
+        raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the probit noise model.")
 
 
 def assignToTest(r, test, rng=None):
@@ -244,6 +282,8 @@ def setTest(r, test, test_feat=None):
             raise ArgumentError("The test_feat must have the same number of rows as test_df.")
         if ids.shape[1] + 1 != r.data.ids.shape[1] + 1:
             raise ArgumentError("The number of columns in test_df must be the same as in relation.data.df.")
+    if r.model.probit and not _is_binary(vals):
+        raise ArgumentError(f"Relation {r.name} has the probit noise model: its test values must be 0 or 1.")
     r.test_vec = TestVec(ids, vals, r.data.names)
     r.test_label = r.test_vec.values < r.class_cut
     if hasFeatures(r):

@@ -53,6 +53,7 @@ extern "C" {
 #define BDF_P_BETA_REL2 9   /* sample_beta_rel: noise per feature    (row = feature)        */
 #define BDF_P_HMC_MOMENTUM 10  /* macau_hmc momentum: entity 0 (U) / 1 (V), row = 0-based row, normal k = latent index */
 #define BDF_P_HMC_ACCEPT   11  /* macau_hmc Metropolis uniform: entity 0, row 0, pair 0                                */
+#define BDF_P_PROBIT       12  /* bdf_probit_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -267,6 +268,11 @@ int bdf_pairs_order(const bdf_pairs *pairs, int64_t *orig_host);
 /* per-pair baseline (dev, n doubles, borrowed; NULL to clear) that replaces mean_value in bdf_predict / bdf_predict_update for
  * these pairs: mean_value + F_test beta of pred(r, probe_vec, F) (src/sampling.jl:9-14) for a relation with features */
 int bdf_pairs_set_baseline(bdf_pairs *pairs, const double *baseline);
+/* link 0 (the default): predictions are udot + base; link 1 (probit): bdf_predict, bdf_predict_update, bdf_predict_sse and the
+ * test update inside bdf_gibbs_sweep take p = Phi(udot + base), the probability of a 1 under the probit model, BEFORE the clamp,
+ * the running average, the running sum of squares and the four statistics (kernels of their own, csrc/k_probit.hip; pairs
+ * stored sorted take the general kernel).  BDF_ERR_ARG for any other value. */
+int bdf_pairs_set_link(bdf_pairs *pairs, int link);
 /* out (dev, rows of F) = mean_value + F beta, beta dev numF: linear_values (macau.jl:91) / the baseline above */
 int bdf_feat_linear(bdf_ctx *ctx, const bdf_feat *F, const double *beta, double mean_value, double *out);
 /* sum over the pairs of (value - pred)^2, pred = udot + (linear_values[pair] if non-NULL else mean_value): err' err of
@@ -302,6 +308,16 @@ int bdf_sample_beta_rel_ranks(bdf_ctx *ctx, bdf_comm *comm, const bdf_feat *F, c
 /* x (dev, n doubles) := sum over the ranks of x, added block after block in rank order: every rank ends with the same bits
  * (the squared-error sum of sample_alpha over the ranks' blocks of observations; F'v above).  comm NULL or one rank: no-op. */
 int bdf_sum_ranks(bdf_ctx *ctx, bdf_comm *comm, double *x, int64_t n);
+/* Probit noise model for a 0/1 relation (neither project this one follows has it): y = 1[z > 0] with the
+ * latent z ~ N(udot + mean_value, 1).  For observation k of `train` IN THE CALLER'S ORDER (the pairs may be stored sorted):
+ *   m = udot_k + mean_value, s = value_k > 0.5 ? +1 : -1, t = s m, u = the uniform of stream (BDF_P_PROBIT, 0x800000 | rel_tag,
+ *   row k, pair 0) at the context's sweep;  lo = Phi(-t) + u Phi(t);
+ *   x = lo < 1/2 ? Phi^-1(max(lo, DBL_MIN)) : -Phi^-1(max((1 - u) Phi(t), DBL_MIN));  z = m + s x, z = s max(s z, DBL_MIN)
+ * -- z drawn from N(m, 1) truncated to value_k's side of 0, always finite and strictly on that side.  linear_out (dev, n):
+ * value_k - z_k, which as bdf_term.linear_values with alpha = 1 makes bdf_sample_rows draw the rows of z's Gaussian model;
+ * z_out (dev, n, nullable): z_k.  factors as for bdf_predict. */
+int bdf_probit_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value,
+                    uint32_t rel_tag, double *linear_out, double *z_out);
 
 
 /* ---- f2: test-set prediction (src/sampling.jl:9-45, macau.jl:142-203, 231-241) -------- */
@@ -501,7 +517,9 @@ int bdf_gibbs_set_test(bdf_gibbs *g, bdf_pairs *pairs, const int32_t *entity_of_
  * relation has features), summed over the ranks, the draw into alpha_dev -- and sample_beta_rel + linear_values
  * (src/sampling.jl:322-337, macau.jl:89-92) when `feat` is set; the row kernels of the relation's entities then read alpha_dev
  * and `linear` (terms are matched to relations by their bdf_rel).  feat_test / test_baseline: the registered test pairs'
- * baseline mean_value + F_test beta is refreshed after the draw (sampling.jl:9-14).  Relations without either need no entry. */
+ * baseline mean_value + F_test beta is refreshed after the draw (sampling.jl:9-14).  `probit`: the latent draw of the probit model
+ * (bdf_probit_draw) at the same place, from the previous iteration's rows; the iteration is then z | U,V -> U | z,V -> V | z,U.
+ * Relations with none of these need no entry. */
 typedef struct {
     const bdf_rel *rel;
     int32_t entity_of_mode[BDF_MAX_MODES];   /* which entity (index into bdf_gibbs_create's array) every mode of rel is          */
@@ -519,6 +537,10 @@ typedef struct {
     double lambda_beta;
     const bdf_feat *feat_test;    /* nullable: feature rows of the registered test pairs ...                                    */
     double *test_baseline;        /* ... and their baseline (dev, one double per test pair)                                     */
+    /* probit noise model (a zeroed tail of the struct is "no probit"): bdf_probit_draw over `train` into `linear` before the
+     * entities' rows, which then read `linear` and alpha = 1.  Not with feat or alpha_sample; needs train and linear */
+    int32_t probit;
+    int32_t _pad;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

@@ -442,6 +442,16 @@ end
 "per-pair baseline replacing mean_value: mean_value + F_test beta of pred(r, probe_vec, F) (sampling.jl:9-14); `nothing` clears it"
 set_baseline!(p::DevPairs, baseline) =
     check(ccall((:bdf_pairs_set_baseline, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), p.h, baseline === nothing ? C_NULL : baseline.p))
+"link 0: predictions are udot + base (the default); 1: the probit link, probabilities Phi(udot + base)"
+set_link!(p::DevPairs, link::Integer) = check(ccall((:bdf_pairs_set_link, lib), Cint, (Ptr{Cvoid}, Cint), p.h, link))
+"probit noise model of a 0/1 relation: the latent z of every observation of `train` (caller's order) given the factors, from the
+uniform of stream (12, 0x800000 | rel_tag, observation); linear_out = value - z is what the rows take as linear_values with
+alpha = 1; z_out may be `nothing`"
+function probit_draw!(c::Context, train::DevPairs, D, factors::Vector{<:DevArray}, mean_value, rel_tag, linear_out::DevArray{Float64}, z_out=nothing)
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_probit_draw, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, train.h, D, fp, mean_value, rel_tag, linear_out.p, z_out === nothing ? C_NULL : z_out.p))
+end
 "out = mean_value + F beta: linear_values (macau.jl:91) and the test rows' baseline"
 feat_linear!(c::Context, f::Ptr{Cvoid}, beta::DevArray{Float64}, mean_value, out::DevArray{Float64}) =
     check(ccall((:bdf_feat_linear, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), c.h, f, beta.p, mean_value, out.p))
@@ -521,6 +531,8 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     lambda_beta::Float64
     feat_test::Ptr{Cvoid}
     test_baseline::Ptr{Cvoid}
+    probit::Int32                                 # probit noise model: the latent draw before the rows (needs train and linear)
+    _pad::Int32
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
