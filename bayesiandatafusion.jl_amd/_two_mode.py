@@ -21,6 +21,8 @@ def relation_of(data, num_latent, who):
         raise ArgumentError(f"{who} works on a matrix relation (2 modes); {rel.name} has {rel.data.ids.shape[1]}")
     if rel.model.probit:
         raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the probit noise model (use macau)")
+    if rel.model.censor is not None:
+        raise ArgumentError(f"{who} takes every value as a measurement; {rel.name} has censoring flags (use macau)")
     return D, rel
 
 

@@ -81,6 +81,8 @@ def toStr(x):
     s = "probit" if x.model.probit else f"α={x.model.alpha:2.1f}"
     if hasFeatures(x) and x.model.beta is not None and len(x.model.beta):
         s += f" β:{np.linalg.norm(x.model.beta):2.1f}"
+    if x.model.censor is not None:
+        s += f" cens:{int(np.count_nonzero(x.model.censor))}"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -96,6 +98,7 @@ class RelationModel:
         self.beta = np.zeros(0)
         self.mean_value = 0.0
         self.probit = False       # setProbit: 0/1 values with the probit noise model instead of Gaussian noise of precision alpha
+        self.censor = None        # setCensored: int8 per training row, 0 a measurement, +1 "at least the value", -1 "at most the value"
 
 
 class RelationTemp:
@@ -224,6 +227,8 @@ def setProbit(r):
         raise ArgumentError(f"Relation {r.name} samples its precision (alpha_sample): the probit latent has unit variance.")
     if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
         raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the probit noise model.")
+    if r.model.censor is not None:
+        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): the probit noise model does not take them.")
     r.model.probit = True
     r.model.alpha = 1.0
     r.model.alpha_sample = False
@@ -244,8 +249,43 @@ def check_probit(r):
         raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the probit noise model.")
 
 
+def setCensored(r, censor):
+    """Censored (Tobit) noise model for a Gaussian relation (the reference takes every value as a measurement): censor[k] says
+    what training row k of r.data, in its current order, is -- 0 the measurement, +1 "the true value is at least this"
+    (right-censored), -1 "at most this" (left-censored).  macau() then samples a latent value for every flagged row beside the
+    rows: z ~ N(u'v + mean, 1 / alpha) truncated to the bound's side.  Predictions, the test set and alpha (fixed, setPrecision or
+    alpha_sample) stay what they are.  Call it AFTER the test split (assignToTest removes training rows; setTest does not)."""
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: the censored noise model does not take relation-level side information.")
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model: it does not take censoring flags.")
+    r.model.censor = _censor_flags(r, censor)
+    r._dev = None
+    return None
+
+
+def _censor_flags(r, censor):
+    c = np.asarray(censor)
+    if c.ndim != 1 or len(c) != r.data.nnz():
+        raise ArgumentError(f"Relation {r.name} has {r.data.nnz()} training rows but {c.shape} censoring flags were given.")
+    if not (np.issubdtype(c.dtype, np.integer) or c.dtype == np.bool_) or not bool(np.all((c == 0) | (c == 1) | (c == -1))):
+        raise ArgumentError(f"Relation {r.name}: censoring flags must be the integers -1, 0 or +1.")
+    return np.ascontiguousarray(c, dtype=np.int8)
+
+
+def check_censored(r):
+    """what a censored relation must still satisfy when a sampler is built on it (it may have been changed since setCensored)"""
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: the censored noise model does not take relation-level side information.")
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model: it does not take censoring flags.")
+    r.model.censor = _censor_flags(r, r.model.censor)
+
+
 def assignToTest(r, test, rng=None):
     """assignToTest!(r, ntest::Int) / assignToTest!(r, test_id::Vector) (RelationData.jl:191-212); ids 1-based"""
+    if r.model.censor is not None:
+        raise ArgumentError(f"Relation {r.name} has censoring flags, one per training row: call assignToTest before setCensored.")
     if np.isscalar(test):
         rng = rng if rng is not None else np.random.default_rng()
         test_id = rng.choice(r.data.nnz(), size=int(test), replace=False) + 1

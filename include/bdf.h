@@ -54,6 +54,7 @@ extern "C" {
 #define BDF_P_HMC_MOMENTUM 10  /* macau_hmc momentum: entity 0 (U) / 1 (V), row = 0-based row, normal k = latent index */
 #define BDF_P_HMC_ACCEPT   11  /* macau_hmc Metropolis uniform: entity 0, row 0, pair 0                                */
 #define BDF_P_PROBIT       12  /* bdf_probit_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
+#define BDF_P_CENSORED     13  /* bdf_censored_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -318,6 +319,21 @@ int bdf_sum_ranks(bdf_ctx *ctx, bdf_comm *comm, double *x, int64_t n);
  * z_out (dev, n, nullable): z_k.  factors as for bdf_predict. */
 int bdf_probit_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value,
                     uint32_t rel_tag, double *linear_out, double *z_out);
+/* Censored (Tobit) noise model of a Gaussian relation: observation k of `train` IN THE CALLER'S ORDER (the
+ * pairs may be stored sorted) carries the flag c_k = censor_dev[k] (dev, n int8): 0 value_k is the measurement, +1 the true value
+ * is at least value_k, -1 at most value_k.  The latent of a flagged observation is z ~ N(udot + mean_value, 1 / alpha) truncated
+ * to its side of the bound; alpha_dev (dev, nullable) wins over alpha, which must otherwise be positive and finite:
+ *   m = udot_k + mean_value, s = c_k, ra = sqrt(alpha), t = s (m - value_k) ra, u = the uniform of stream (BDF_P_CENSORED,
+ *   0x800000 | rel_tag, row k, pair 0) at the context's sweep;  lo = Phi(-t) + u Phi(t);
+ *   x = lo < 1/2 ? Phi^-1(max(lo, DBL_MIN)) : -Phi^-1(max((1 - u) Phi(t), DBL_MIN));
+ *   z = m + s x / ra, z = value_k + s max(s (z - value_k), 0)
+ * -- always finite and never on the wrong side of the bound; for t < -37.5, where Phi(t) underflows, a draw at or near the bound
+ * (the exact law there lies within about 1 / (37 ra) of it).  c_k = 0: z = value_k, no uniform is consumed.  linear_out (dev, n):
+ * mean_value + (value_k - z_k), which as bdf_term.linear_values makes bdf_sample_rows draw the rows of z's Gaussian model with the
+ * relation's alpha (exactly mean_value for a measurement), and as the pairs' baseline makes bdf_predict_sse return the residual
+ * sum of squares of z; z_out (dev, n, nullable): z_k.  Any other flag value is undefined.  factors as for bdf_predict. */
+int bdf_censored_draw(bdf_ctx *ctx, const bdf_pairs *train, const int8_t *censor_dev, int D, const double *const *factors,
+                      double mean_value, double alpha, const double *alpha_dev, uint32_t rel_tag, double *linear_out, double *z_out);
 
 
 /* ---- f2: test-set prediction (src/sampling.jl:9-45, macau.jl:142-203, 231-241) -------- */
@@ -519,7 +535,8 @@ int bdf_gibbs_set_test(bdf_gibbs *g, bdf_pairs *pairs, const int32_t *entity_of_
  * and `linear` (terms are matched to relations by their bdf_rel).  feat_test / test_baseline: the registered test pairs'
  * baseline mean_value + F_test beta is refreshed after the draw (sampling.jl:9-14).  `probit`: the latent draw of the probit model
  * (bdf_probit_draw) at the same place, from the previous iteration's rows; the iteration is then z | U,V -> U | z,V -> V | z,U.
- * Relations with none of these need no entry. */
+ * `censor`: the latent draw of the censored model (bdf_censored_draw, with alpha_dev) after sample_alpha; the iteration is then
+ * alpha | U,V,z -> z | U,V,alpha -> U | z,V -> V | z,U.  Relations with none of these need no entry. */
 typedef struct {
     const bdf_rel *rel;
     int32_t entity_of_mode[BDF_MAX_MODES];   /* which entity (index into bdf_gibbs_create's array) every mode of rel is          */
@@ -541,6 +558,11 @@ typedef struct {
      * entities' rows, which then read `linear` and alpha = 1.  Not with feat or alpha_sample; needs train and linear */
     int32_t probit;
     int32_t _pad;
+    /* censored noise model (a zeroed tail is "none"): flags (dev, one int8 per observation of `train` in the caller's order).
+     * bdf_censored_draw over `train` into `linear` after sample_alpha; the entities' rows then read `linear` and alpha_dev.  The
+     * caller gives `train` the baseline `linear` (bdf_pairs_set_baseline) and starts `linear` at mean_value.  Not with probit or
+     * feat; needs train and linear */
+    const int8_t *censor;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */
