@@ -18,6 +18,7 @@ P_ROW, P_BETA_E1, P_BETA_E2, P_NW_NORMAL, P_GAMMA_N, P_GAMMA_U, P_NW_MEAN, P_BET
 P_HMC_MOMENTUM, P_HMC_ACCEPT = 10, 11
 P_PROBIT = 12
 P_CENSORED = 13
+P_INTERVAL = 14
 
 
 class ArgumentError(ValueError):
@@ -84,7 +85,8 @@ class GibbsRelation(C.Structure):
                 ("alpha_sample", C.c_int32), ("rel_tag", C.c_uint32), ("alpha_lambda0", C.c_double), ("alpha_nu0", C.c_double),
                 ("nnz", C.c_int64), ("train", C.c_void_p), ("first_obs", C.c_int64), ("obs_block", C.c_int64), ("feat", C.c_void_p),
                 ("beta", C.c_void_p), ("linear", C.c_void_p), ("lambda_beta", C.c_double), ("feat_test", C.c_void_p),
-                ("test_baseline", C.c_void_p), ("probit", C.c_int32), ("_pad", C.c_int32), ("censor", C.c_void_p)]
+                ("test_baseline", C.c_void_p), ("probit", C.c_int32), ("_pad", C.c_int32), ("censor", C.c_void_p),
+                ("interval", C.c_void_p)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -138,6 +140,8 @@ _SIGS = {
     "bdf_pairs_set_link": (C.c_int, [C.c_void_p, C.c_int]),
     "bdf_probit_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdf_censored_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p,
+                                    C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bdf_interval_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdf_feat_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "bdf_predict_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),

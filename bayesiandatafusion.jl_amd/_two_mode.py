@@ -23,6 +23,8 @@ def relation_of(data, num_latent, who):
         raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the probit noise model (use macau)")
     if rel.model.censor is not None:
         raise ArgumentError(f"{who} takes every value as a measurement; {rel.name} has censoring flags (use macau)")
+    if rel.model.interval is not None:
+        raise ArgumentError(f"{who} takes every value as a measurement; {rel.name} has interval bounds (use macau)")
     return D, rel
 
 

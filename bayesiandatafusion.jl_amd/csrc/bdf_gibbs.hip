@@ -356,6 +356,8 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
         BDF_REQUIRE(!r.probit || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the probit model needs its observations as pairs (train) and a linear buffer", k);
         BDF_REQUIRE(!r.censor || (!r.probit && !r.feat), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the censored model takes neither the probit model nor relation features", k);
         BDF_REQUIRE(!r.censor || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the censored model needs its observations as pairs (train) and a linear buffer", k);
+        BDF_REQUIRE(!r.interval || (!r.probit && !r.censor && !r.feat), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model takes neither the probit model, censoring flags nor relation features", k);
+        BDF_REQUIRE(!r.interval || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model needs its observations as pairs (train) and a linear buffer", k);
         for (int m = 0; m < r.rel->n_modes; m++)
             BDF_REQUIRE(r.entity_of_mode[m] >= 0 && r.entity_of_mode[m] < (int)g->ent.size(), BDF_ERR_ARG,
                         "bdf_gibbs_set_relations: relation %d mode %d names entity %d", k, m, r.entity_of_mode[m]);
@@ -381,7 +383,7 @@ int update_relations(bdf_gibbs *g)
     const int D = g->D;
     int rc;
     for (const auto &r : g->rels) {
-        if (!r.alpha_sample && !r.feat && !r.probit && !r.censor) continue;
+        if (!r.alpha_sample && !r.feat && !r.probit && !r.censor && !r.interval) continue;
         const double *fac[BDF_MAX_MODES];
         for (int m = 0; m < r.rel->n_modes; m++) {
             const auto &O = g->ent[(size_t)r.entity_of_mode[m]];
@@ -398,6 +400,9 @@ int update_relations(bdf_gibbs *g)
         // censored: the latent z of every flagged observation given the rows and the alpha just drawn (the sum of squares above was
         // that of the previous z: the pairs carry linear as their baseline); the rows then see linear = mean + y - z with alpha_dev
         if (r.censor && (rc = bdf_censored_draw(R, r.train, r.censor, D, fac, r.mean_value, 0.0, r.alpha_dev, r.rel_tag, r.linear + r.first_obs, nullptr)))
+            return rc;
+        // interval-censored: the same draw at the same place, between the two bounds of every bounded observation
+        if (r.interval && (rc = bdf_interval_draw(R, r.train, r.interval, D, fac, r.mean_value, 0.0, r.alpha_dev, r.rel_tag, r.linear + r.first_obs, nullptr)))
             return rc;
         if (r.feat) {
             if ((rc = bdf_sample_beta_rel_impl(R, g->comm, r.feat, r.train, r.first_obs, D, fac, r.mean_value, 1.0, r.alpha_dev, r.lambda_beta,
@@ -446,7 +451,7 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
         terms[t].alpha_dev = nullptr;
         if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {
             terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
-            terms[t].linear_values = (gr->feat || gr->probit || gr->censor) ? gr->linear : nullptr;
+            terms[t].linear_values = (gr->feat || gr->probit || gr->censor || gr->interval) ? gr->linear : nullptr;
             if (gr->probit) terms[t].alpha = 1.0;
         }
         for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
@@ -520,6 +525,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         }
         if (r.probit) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});     // y - z of the last draw
         if (r.censor) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});     // mean + y - z of the last draw
+        if (r.interval) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});   // mean + y - z of the last draw
     }
     size_t total = 0;
     for (auto &pc : pieces) total += (pc.bytes + 255) & ~(size_t)255;
@@ -693,7 +699,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             terms[t].alpha_dev = nullptr;
             if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {        // a relation with a model of its own
                 terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
-                terms[t].linear_values = (gr->feat || gr->probit || gr->censor) ? gr->linear : nullptr;
+                terms[t].linear_values = (gr->feat || gr->probit || gr->censor || gr->interval) ? gr->linear : nullptr;
                 if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
             }
             for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;

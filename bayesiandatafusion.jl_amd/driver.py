@@ -62,6 +62,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         raise ArgumentError("Prediction of all elements is not possible when Relation has the probit noise model.")
     if rmse_train and data.relations and data.relations[0].model.censor is not None:
         raise ArgumentError("rmse_train is not possible when Relation has censoring flags: its training values are bounds, not measurements.")
+    if rmse_train and data.relations and data.relations[0].model.interval is not None:
+        raise ArgumentError("rmse_train is not possible when Relation has interval bounds: its training values stand for intervals, not measurements.")
 
     verbose and print("Model setup")
     eng = engine

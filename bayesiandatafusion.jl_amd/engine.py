@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from . import features as feat
 from ._lib import ArgumentError, GibbsEntity, Term, check, lib
-from .relation_data import check_censored, check_probit
+from .relation_data import check_censored, check_interval, check_probit
 
 
 def _ptr(t):
@@ -607,6 +607,10 @@ class GibbsEngine:
                 check_censored(r)
                 if shard is not None and shard[1] > 1:
                     raise ArgumentError(f"Relation {r.name} has censoring flags: one rank only")
+            if r.model.interval is not None:
+                check_interval(r)
+                if shard is not None and shard[1] > 1:
+                    raise ArgumentError(f"Relation {r.name} has interval bounds: one rank only")
         self.data, self.D = data, int(num_latent)
         # The row context runs on a stream of its own that leaves a few CUs (one or two per XCD) free for the hyperprior's
         # small kernels, which otherwise wait for slots beside the chip-filling row kernel -- when the entities are small
@@ -668,7 +672,7 @@ class GibbsEngine:
             r._dev = dr
             self.rel.append(dr)
             # relation-level side information (RelationData.jl:348-353): FF path only, as in the reference
-            dr.F = dr.beta = dr.linear = dr.train = dr.censor = None
+            dr.F = dr.beta = dr.linear = dr.train = dr.censor = dr.interval = None
             # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
             # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
             # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
@@ -706,6 +710,16 @@ class GibbsEngine:
                 # mean_value: the first alpha is drawn from the values as they are
                 dr.linear = self.ctx.tensor(np.full(max(nn, 1), r.model.mean_value))
                 dr.censor = self.ctx.tensor(r.model.censor if nn else np.zeros(1, dtype=np.int8), dtype=torch.int8)
+                if dr.train is None:
+                    dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
+                if len(r.entities) == 2 and nn:
+                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
+                check(lib().bdf_pairs_set_baseline(dr.train.handle, _ptr(dr.linear)))
+            if r.model.interval is not None:
+                # the interval-censored model: as the censored one, with a (lower, upper) pair per training row in place of the flag
+                # (bdf_interval_draw); linear starts at mean_value and the training pairs carry it as their baseline
+                dr.linear = self.ctx.tensor(np.full(max(nn, 1), r.model.mean_value))
+                dr.interval = self.ctx.tensor(r.model.interval if nn else np.zeros((1, 2)))
                 if dr.train is None:
                     dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
                 if len(r.entities) == 2 and nn:
@@ -783,7 +797,8 @@ class GibbsEngine:
             return
         from ._lib import GibbsRelation
         rows = [(ri, r, self.rel[ri]) for ri, r in enumerate(self.data.relations)
-                if r.model.alpha_sample or self.rel[ri].F is not None or r.model.probit or r.model.censor is not None]
+                if r.model.alpha_sample or self.rel[ri].F is not None or r.model.probit or r.model.censor is not None
+                or r.model.interval is not None]
         arr = (GibbsRelation * max(len(rows), 1))()
         for k, (ri, r, dr) in enumerate(rows):
             g = arr[k]
@@ -800,6 +815,8 @@ class GibbsEngine:
                 g.probit, g.linear = 1, dr.linear.data_ptr()
             if dr.censor is not None:
                 g.censor, g.linear = dr.censor.data_ptr(), dr.linear.data_ptr()
+            if dr.interval is not None:
+                g.interval, g.linear = dr.interval.data_ptr(), dr.linear.data_ptr()
             if dr.F is not None:
                 g.feat, g.beta, g.linear, g.lambda_beta = dr.F.handle, dr.beta.data_ptr(), dr.linear.data_ptr(), r.model.lambda_beta
                 if ri == 0 and getattr(dr, "F_test", None) is not None:
@@ -900,7 +917,7 @@ class GibbsEngine:
         kernel's arguments: sampling it costs one device-to-host read per sweep, as the reference's host loop does)"""
         for ri, r in enumerate(self.data.relations):
             dr = self.rel[ri]
-            if not (r.model.alpha_sample or dr.F is not None or r.model.probit or dr.censor is not None):
+            if not (r.model.alpha_sample or dr.F is not None or r.model.probit or dr.censor is not None or dr.interval is not None):
                 continue
             facs = self.factors_of(r)
             if r.model.probit:           # z | U, V: the rows of this iteration then see linear_values = y - z, alpha = 1
@@ -919,6 +936,10 @@ class GibbsEngine:
             if dr.censor is not None:    # z | U, V, alpha: the rows of this iteration then see linear_values = mean + y - z
                 fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
                 check(lib().bdf_censored_draw(self.ctx.handle, dr.train.handle, _ptr(dr.censor), self.D, fp, r.model.mean_value,
+                                              r.model.alpha, _ptr(dr.alpha_dev), ri + 1, _ptr(dr.linear), None))
+            if dr.interval is not None:  # z | U, V, alpha between its bounds: the rows then see linear_values = mean + y - z
+                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
+                check(lib().bdf_interval_draw(self.ctx.handle, dr.train.handle, _ptr(dr.interval), self.D, fp, r.model.mean_value,
                                               r.model.alpha, _ptr(dr.alpha_dev), ri + 1, _ptr(dr.linear), None))
             if dr.F is not None:
                 fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])

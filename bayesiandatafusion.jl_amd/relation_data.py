@@ -83,6 +83,8 @@ def toStr(x):
         s += f" β:{np.linalg.norm(x.model.beta):2.1f}"
     if x.model.censor is not None:
         s += f" cens:{int(np.count_nonzero(x.model.censor))}"
+    if x.model.interval is not None:
+        s += f" intv:{int(np.count_nonzero(x.model.interval[:, 0] < x.model.interval[:, 1]))}"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -99,6 +101,7 @@ class RelationModel:
         self.mean_value = 0.0
         self.probit = False       # setProbit: 0/1 values with the probit noise model instead of Gaussian noise of precision alpha
         self.censor = None        # setCensored: int8 per training row, 0 a measurement, +1 "at least the value", -1 "at most the value"
+        self.interval = None      # setInterval / setBinned: float64 (n, 2), per training row the bounds lower <= upper of its value
 
 
 class RelationTemp:
@@ -229,6 +232,8 @@ def setProbit(r):
         raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the probit noise model.")
     if r.model.censor is not None:
         raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): the probit noise model does not take them.")
+    if r.model.interval is not None:
+        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval): the probit noise model (setProbit) does not take them.")
     r.model.probit = True
     r.model.alpha = 1.0
     r.model.alpha_sample = False
@@ -259,6 +264,8 @@ def setCensored(r, censor):
         raise ArgumentError(f"Relation {r.name} has features: the censored noise model does not take relation-level side information.")
     if r.model.probit:
         raise ArgumentError(f"Relation {r.name} has the probit noise model: it does not take censoring flags.")
+    if r.model.interval is not None:
+        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval): it does not take censoring flags (setCensored) as well.")
     r.model.censor = _censor_flags(r, censor)
     r._dev = None
     return None
@@ -282,8 +289,76 @@ def check_censored(r):
     r.model.censor = _censor_flags(r, r.model.censor)
 
 
+def setInterval(r, lower, upper):
+    """Interval-censored noise model for a Gaussian relation (the reference takes every value as a measurement): training row k of
+    r.data, in its current order, says only that the true value lies in [lower[k], upper[k]].  Either bound may be infinite;
+    (-inf, +inf) says nothing.  lower[k] == upper[k] keeps the row a measurement.  macau() then samples a latent value for every
+    row with lower < upper beside the rows: z ~ N(u'v + mean, 1 / alpha) truncated to the interval.  The stored value is where the
+    latent starts, so it must lie inside its bounds.  Predictions, the test set and alpha (fixed, setPrecision or alpha_sample)
+    stay what they are.  Call it AFTER the test split (assignToTest removes training rows; setTest does not)."""
+    _interval_guards(r)
+    r.model.interval = _interval_bounds(r, lower, upper)
+    r._dev = None
+    return None
+
+
+def setBinned(r, edges):
+    """Values reported in bins: `edges` are the strictly increasing finite interior edges e_1 < ... < e_{K-1} of K bins, the first
+    and the last of which are open (e_0 = -inf, e_K = +inf).  A stored value v lies in bin j when e_j <= v < e_{j+1}; every training
+    row gets its bin's bounds (setInterval).  setBinned(rel, [1.5, 2.5, 3.5, 4.5]) is a 1 ... 5 rating."""
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim != 1 or len(e) == 0 or not bool(np.all(np.isfinite(e))) or not bool(np.all(np.diff(e) > 0)):
+        raise ArgumentError(f"Relation {r.name}: bin edges must be a non-empty list of finite, strictly increasing numbers.")
+    full = np.concatenate([[-np.inf], e, [np.inf]])
+    v = np.asarray(r.data.values, dtype=np.float64)
+    if bool(np.any(np.isnan(v))):
+        raise ArgumentError(f"Relation {r.name}: a NaN value lies in no bin.")
+    j = np.searchsorted(e, v, side="right")          # the number of edges <= v: e_j <= v < e_{j+1}
+    return setInterval(r, full[j], full[j + 1])
+
+
+def _interval_guards(r):
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: the interval noise model (setInterval) does not take relation-level side information.")
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take interval bounds (setInterval).")
+    if r.model.censor is not None:
+        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take interval bounds (setInterval) as well.")
+
+
+def _interval_bounds(r, lower, upper):
+    n = r.data.nnz()
+    try:
+        lo, hi = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ArgumentError(f"Relation {r.name}: interval bounds must be numbers.")
+    if lo.ndim != 1 or hi.ndim != 1 or len(lo) != n or len(hi) != n:
+        raise ArgumentError(f"Relation {r.name} has {n} training rows but {lo.shape} lower and {hi.shape} upper bounds were given.")
+    if bool(np.any(np.isnan(lo))) or bool(np.any(np.isnan(hi))):
+        raise ArgumentError(f"Relation {r.name}: an interval bound is NaN (use -inf / +inf for an open side).")
+    if bool(np.any(lo > hi)):
+        raise ArgumentError(f"Relation {r.name}: a lower bound is above its upper bound (row {int(np.argmax(lo > hi)) + 1}).")
+    v = np.asarray(r.data.values, dtype=np.float64)
+    out = ~((lo <= v) & (v <= hi))
+    if bool(np.any(out)):
+        raise ArgumentError(f"Relation {r.name}: the stored value of row {int(np.argmax(out)) + 1} lies outside its bounds; it is where "
+                            "the latent value starts.")
+    return np.ascontiguousarray(np.stack([lo, hi], axis=1))
+
+
+def check_interval(r):
+    """what an interval relation must still satisfy when a sampler is built on it (it may have been changed since setInterval)"""
+    _interval_guards(r)
+    b = np.asarray(r.model.interval)
+    if b.ndim != 2 or b.shape[1] != 2:
+        raise ArgumentError(f"Relation {r.name}: interval bounds must be an (n, 2) array, not {b.shape}.")
+    r.model.interval = _interval_bounds(r, b[:, 0], b[:, 1])
+
+
 def assignToTest(r, test, rng=None):
     """assignToTest!(r, ntest::Int) / assignToTest!(r, test_id::Vector) (RelationData.jl:191-212); ids 1-based"""
+    if r.model.interval is not None:
+        raise ArgumentError(f"Relation {r.name} has interval bounds, one pair per training row: call assignToTest before setInterval.")
     if r.model.censor is not None:
         raise ArgumentError(f"Relation {r.name} has censoring flags, one per training row: call assignToTest before setCensored.")
     if np.isscalar(test):

@@ -55,6 +55,7 @@ extern "C" {
 #define BDF_P_HMC_ACCEPT   11  /* macau_hmc Metropolis uniform: entity 0, row 0, pair 0                                */
 #define BDF_P_PROBIT       12  /* bdf_probit_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 #define BDF_P_CENSORED     13  /* bdf_censored_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
+#define BDF_P_INTERVAL     14  /* bdf_interval_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -334,6 +335,24 @@ int bdf_probit_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *c
  * sum of squares of z; z_out (dev, n, nullable): z_k.  Any other flag value is undefined.  factors as for bdf_predict. */
 int bdf_censored_draw(bdf_ctx *ctx, const bdf_pairs *train, const int8_t *censor_dev, int D, const double *const *factors,
                       double mean_value, double alpha, const double *alpha_dev, uint32_t rel_tag, double *linear_out, double *z_out);
+/* Interval-censored noise model of a Gaussian relation: observation k of `train` IN THE CALLER'S ORDER (the
+ * pairs may be stored sorted) carries the bounds lo_k = bounds_dev[2 k] <= hi_k = bounds_dev[2 k + 1] (dev, n pairs of doubles,
+ * row-major, aligned to 16 bytes; either bound may be infinite).  lo_k == hi_k: value_k is the measurement, z = value_k, no uniform
+ * is consumed.  lo_k < hi_k: the latent is z ~ N(udot + mean_value, 1 / alpha) truncated to [lo_k, hi_k]; alpha_dev (dev,
+ * nullable) wins over alpha, which must otherwise be positive and finite:
+ *   m = udot_k + mean_value, ra = sqrt(alpha), a = (lo_k - m) ra, b = (hi_k - m) ra, u = the uniform of stream (BDF_P_INTERVAL,
+ *   0x800000 | rel_tag, row k, pair 0) at the context's sweep;
+ *   a + b > 0 (false for NaN):  (a, b, v, v', s) = (-b, -a, 1 - u, u, -1),  else  (a, b, u, 1 - u, +1);
+ *   Pa = Phi(a), w = Phi(b) - Pa, p = Pa + v w;
+ *   x = p < 1/2 ? Phi^-1(max(p, DBL_MIN)) : -Phi^-1(max(Phi(-b) + v' w, DBL_MIN));
+ *   z = min(max(m + s x / ra, lo_k), hi_k)
+ * -- always finite for finite value_k and inside the bounds; with both bounds beyond 37.5 standard deviations on one side of m,
+ * where Phi underflows, the nearer bound (the exact law there lies within about 1 / (37 ra) of it).  linear_out (dev, n):
+ * mean_value + (value_k - z_k), which as bdf_term.linear_values makes bdf_sample_rows draw the rows of z's Gaussian model with the
+ * relation's alpha (exactly mean_value for a measurement), and as the pairs' baseline makes bdf_predict_sse return the residual
+ * sum of squares of z; z_out (dev, n, nullable): z_k.  lo_k > hi_k or a NaN bound is undefined.  factors as for bdf_predict. */
+int bdf_interval_draw(bdf_ctx *ctx, const bdf_pairs *train, const double *bounds_dev, int D, const double *const *factors,
+                      double mean_value, double alpha, const double *alpha_dev, uint32_t rel_tag, double *linear_out, double *z_out);
 
 
 /* ---- f2: test-set prediction (src/sampling.jl:9-45, macau.jl:142-203, 231-241) -------- */
@@ -536,7 +555,8 @@ int bdf_gibbs_set_test(bdf_gibbs *g, bdf_pairs *pairs, const int32_t *entity_of_
  * baseline mean_value + F_test beta is refreshed after the draw (sampling.jl:9-14).  `probit`: the latent draw of the probit model
  * (bdf_probit_draw) at the same place, from the previous iteration's rows; the iteration is then z | U,V -> U | z,V -> V | z,U.
  * `censor`: the latent draw of the censored model (bdf_censored_draw, with alpha_dev) after sample_alpha; the iteration is then
- * alpha | U,V,z -> z | U,V,alpha -> U | z,V -> V | z,U.  Relations with none of these need no entry. */
+ * alpha | U,V,z -> z | U,V,alpha -> U | z,V -> V | z,U.  `interval`: the latent draw of the interval-censored model
+ * (bdf_interval_draw, with alpha_dev) at the same place and in the same order.  Relations with none of these need no entry. */
 typedef struct {
     const bdf_rel *rel;
     int32_t entity_of_mode[BDF_MAX_MODES];   /* which entity (index into bdf_gibbs_create's array) every mode of rel is          */
@@ -563,6 +583,11 @@ typedef struct {
      * caller gives `train` the baseline `linear` (bdf_pairs_set_baseline) and starts `linear` at mean_value.  Not with probit or
      * feat; needs train and linear */
     const int8_t *censor;
+    /* interval-censored noise model (a zeroed tail is "none"): bounds (dev, one (lo, hi) pair of doubles per observation of `train`
+     * in the caller's order, aligned to 16 bytes).  bdf_interval_draw over `train` into `linear` after sample_alpha; the entities'
+     * rows then read `linear` and alpha_dev.  The caller gives `train` the baseline `linear` (bdf_pairs_set_baseline) and starts
+     * `linear` at mean_value.  Not with probit, censor or feat; needs train and linear */
+    const double *interval;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

@@ -464,6 +464,19 @@ function censored_draw!(c::Context, train::DevPairs, censor::DevArray{Int8}, D, 
                 c.h, train.h, censor.p, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, rel_tag, linear_out.p,
                 z_out === nothing ? C_NULL : z_out.p))
 end
+"interval-censored noise model of a Gaussian relation: `bounds` (device Float64, 2 x n: column k holds the (lower, upper) bounds
+of observation k of `train` in the caller's order, either may be infinite; lower == upper: a measurement); the latent z of every
+bounded observation given the factors, from the uniform of stream (14, 0x800000 | rel_tag, observation); `alpha_dev` (a device
+scalar or `nothing`) wins over `alpha`; linear_out = mean_value + value - z is what the rows take as linear_values with the
+relation's alpha; z_out may be `nothing`"
+function interval_draw!(c::Context, train::DevPairs, bounds::DevArray{Float64}, D, factors::Vector{<:DevArray}, mean_value, alpha, alpha_dev,
+                        rel_tag, linear_out::DevArray{Float64}, z_out=nothing)
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_interval_draw, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, train.h, bounds.p, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, rel_tag, linear_out.p,
+                z_out === nothing ? C_NULL : z_out.p))
+end
 "out = mean_value + F beta: linear_values (macau.jl:91) and the test rows' baseline"
 feat_linear!(c::Context, f::Ptr{Cvoid}, beta::DevArray{Float64}, mean_value, out::DevArray{Float64}) =
     check(ccall((:bdf_feat_linear, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), c.h, f, beta.p, mean_value, out.p))
@@ -546,6 +559,7 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     probit::Int32                                 # probit noise model: the latent draw before the rows (needs train and linear)
     _pad::Int32
     censor::Ptr{Cvoid}                            # censored noise model: device Int8 flags per observation of train (C_NULL: none)
+    interval::Ptr{Cvoid}                          # interval-censored noise model: device Float64 (lower, upper) per observation of train (C_NULL: none)
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
