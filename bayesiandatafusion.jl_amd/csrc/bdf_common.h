@@ -179,6 +179,8 @@ struct bdf_pairs {
     std::vector<double> values_host;
     void *auc_ws;                 // bdf_pairs_auc's workspace (bdf_auc_workspace_bytes(n)), allocated at first use
     int link;                     // bdf_pairs_set_link: 0 identity, 1 probit (predictions are Phi(udot + base): k_probit.hip)
+    double *lpd_dev;              // bdf_pairs_lpd_update's running state (k_lpd.hip): n maxima M, then n sums A, in storage order; at first use
+    double lpd_draws;             // ... and the posterior draws it holds (a counter of its own, not `count`)
 };
 
 struct bdf_feat {

@@ -14,7 +14,7 @@ import numpy as np
 from . import features as feat
 from ._lib import ArgumentError
 from .engine import GibbsEngine
-from .relation_data import hasFeatures, numTest, toStr
+from .relation_data import check_test_interval, hasFeatures, numTest, toStr
 
 
 def AUC_ROC(Ytrue, scores):
@@ -51,7 +51,7 @@ from .data_reading import read_binary_float32, write_binary_matrix  # noqa: E402
 def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=200, verbose=True, full_lambda_u=True,
           reset_model=True, compute_ff_size=6500, latent_pids=(1,), latent_blas_threads=1, cg_pids=(1,),
           full_prediction=False, rmse_train=False, tol=float("nan"), output="", output_beta=False, output_type="csv",
-          clamp=(), f=False, seed=0, device=None, engine=None):
+          clamp=(), f=False, seed=0, device=None, engine=None, lpd=False):
     if output_beta and not output:
         raise ArgumentError("To output samples of beta ('output_beta = true') you have to set also output prefix, "
                             "e.g., output = \"my_model\".")
@@ -65,11 +65,16 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if rmse_train and data.relations and data.relations[0].model.interval is not None:
         raise ArgumentError("rmse_train is not possible when Relation has interval bounds: its training values stand for intervals, not measurements.")
 
+    if lpd and not (data.relations and numTest(data.relations[0]) > 0):
+        raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")
+
     verbose and print("Model setup")
     eng = engine
     if eng is None or reset_model:
         eng = GibbsEngine(data, num_latent, seed=seed, device=device, lambda_beta=lambda_beta,
                           compute_ff_size=compute_ff_size, full_lambda_u=full_lambda_u, tol=tol)
+    if lpd and eng.world > 1:
+        raise ArgumentError("lpd = true is not possible with more than one rank: every rank scores only the test cells it predicts.")
     data._engine = eng
     D = eng.D
 
@@ -84,6 +89,13 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     haveTest = numTest(rel) > 0
     test = eng.test_pairs() if haveTest else None
     train = eng.train_pairs() if rmse_train else None
+    lpd_bounds, lpd_avg = None, float("nan")
+    if lpd:
+        # held-out log predictive density: what kind of record every test cell is -- a 0/1 value of a probit
+        # relation, an interval (setTestInterval / setTestBinned) or a measurement
+        if rel.model.test_interval is not None:
+            check_test_interval(rel)
+            lpd_bounds = test.ctx.tensor(rel.model.test_interval)
     f_output = []
     yhat_full = None
     if full_prediction:
@@ -106,6 +118,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         facs = eng.factors_of(rel)
         if full_prediction and i > burnin:
             yhat_full += eng.pred_all(rel)                    # macau.jl:145-147: a plain dense product, on the device
+        if lpd:
+            # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
+            # has read the same double, and the device scalar is redrawn on another stream than the pairs')
+            a = 1.0 if rel.model.probit else (rel._dev.alpha_dev if (rel.model.alpha_sample and eng.native) else rel.model.alpha)
+            test.lpd_update(D, facs, rel.model.mean_value, a, phase, lpd_bounds)
         if i > burnin:
             if output:
                 ndigits = int(math.floor(math.log10(psamples))) + 1
@@ -144,10 +161,13 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 rmse_avg = math.sqrt(s[0] / n)
                 err_avg = s[2] / n
                 roc_avg = float(rep[4])
+                if lpd:
+                    lpd_avg = float(rep[6]) / n
             if verbose:
                 estr = " ".join(toStr(en) for en in data.entities)
                 rstr = " ".join(toStr(r) for r in data.relations)
-                print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
+                lstr = f" LPD={lpd_avg:.4f}" if lpd else ""
+                print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f}{lstr} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
 
     eng.sync()
     eng.sync_host_scalars()
@@ -160,6 +180,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         "accuracy": err_avg,
         "ROC": roc_avg,
     }
+    if lpd:
+        result["LPD"] = lpd_avg
     if full_prediction:
         result["predictions_full"] = (yhat_full / psamples).cpu().numpy()        # macau.jl:228-230
     if rmse_train:
@@ -173,7 +195,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             stdev = np.sqrt(tmp)
         else:
             stdev = np.full(len(avg), np.nan)
-        result["predictions"] = rel.test_vec.to_frame(pred=makeClamped(avg, clamp), stdev=stdev)
+        extra = {"lpd": test.lpd() if psamples >= 1 else np.full(len(avg), np.nan)} if lpd else {}
+        result["predictions"] = rel.test_vec.to_frame(pred=makeClamped(avg, clamp), stdev=stdev, **extra)
         import pandas as pd
         tc = np.zeros((numTest(rel), len(rel.entities)), dtype=np.int64)
         for mode in range(len(rel.entities)):

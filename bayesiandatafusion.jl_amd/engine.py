@@ -280,9 +280,11 @@ class DevicePairs:
         self.n, self.n_modes = ids.shape
         check(lib().bdf_pairs_create(ctx.handle, self.n_modes, self.n, ids.ctypes.data_as(C.c_void_p), 8,
                                      values.ctypes.data_as(_lib.c_dp), C.byref(self.handle)))
-        # the reporting step's device scalars, read back together: bdf_predict_update's 4 stats, then roc_avg (auc)
-        self.report = ctx.zeros(5)
+        # the reporting step's device scalars, read back together: bdf_predict_update's 4 stats, then roc_avg (auc), then
+        # bdf_pairs_lpd_update's 4 (lpd_update)
+        self.report = ctx.zeros(9)
         self.stats = self.report[:4]
+        self.lpd_stats = self.report[5:]
         self._order = None
         ctx.adopt(self)
 
@@ -348,6 +350,29 @@ class DevicePairs:
         check(lib().bdf_pairs_auc(ctx.handle, self.handle, float(class_cut), C.c_void_p(self.report.data_ptr() + 32),
                                   _ptr(counts)))
         return self.report[4]
+
+    def lpd_update(self, D, factors, mean_value, alpha, phase, bounds=None):
+        """one scoring step of the held-out log predictive density (bdf_pairs_lpd_update) on the pairs' own stream: every pair's
+        log-likelihood under `factors` -- probit pairs (set_link(1)) as 0/1 values, pairs whose `bounds` (device (n, 2) tensor in
+        the caller's order, or None) differ by their interval's mass, the others by the Gaussian density at their value -- folded
+        into the running log-sum-exp (phase 0: burn-in, nothing kept; 1: first posterior draw; 2: later ones).  alpha: a float,
+        or a device scalar (tensor of one double) read on the device.  Returns the device statistics: [0] the sum of this
+        draw's log-likelihoods, [1] the sum of the pairs' lpd after it, [2] = [3] = 0."""
+        on_dev = torch.is_tensor(alpha)
+        check(lib().bdf_pairs_lpd_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, self._facs(factors),
+                                         mean_value, 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
+                                         _ptr(self.lpd_stats)))
+        return self.lpd_stats
+
+    def lpd(self):
+        """the pairs' lpd over the posterior draws scored so far, as a host array in the caller's order (bdf_pairs_lpd maps the
+        state, kept in storage order like state()'s, through the pairs' order on the device)"""
+        cur, own = self._on_own_stream()
+        with own:
+            out = torch.zeros(self.n, dtype=torch.float64, device=self.ctx.device)
+            check(lib().bdf_pairs_lpd(self.ctx.handle, self.handle, _ptr(out)))
+        self._hand_back(cur, out)
+        return out.cpu().numpy()
 
     def state(self):
         """(avg, sq) as host arrays"""

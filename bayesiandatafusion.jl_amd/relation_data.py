@@ -102,6 +102,7 @@ class RelationModel:
         self.probit = False       # setProbit: 0/1 values with the probit noise model instead of Gaussian noise of precision alpha
         self.censor = None        # setCensored: int8 per training row, 0 a measurement, +1 "at least the value", -1 "at most the value"
         self.interval = None      # setInterval / setBinned: float64 (n, 2), per training row the bounds lower <= upper of its value
+        self.test_interval = None # setTestInterval / setTestBinned: float64 (numTest, 2), the same per row of test_vec (macau(lpd=True))
 
 
 class RelationTemp:
@@ -306,15 +307,57 @@ def setBinned(r, edges):
     """Values reported in bins: `edges` are the strictly increasing finite interior edges e_1 < ... < e_{K-1} of K bins, the first
     and the last of which are open (e_0 = -inf, e_K = +inf).  A stored value v lies in bin j when e_j <= v < e_{j+1}; every training
     row gets its bin's bounds (setInterval).  setBinned(rel, [1.5, 2.5, 3.5, 4.5]) is a 1 ... 5 rating."""
-    e = np.asarray(edges, dtype=np.float64)
-    if e.ndim != 1 or len(e) == 0 or not bool(np.all(np.isfinite(e))) or not bool(np.all(np.diff(e) > 0)):
-        raise ArgumentError(f"Relation {r.name}: bin edges must be a non-empty list of finite, strictly increasing numbers.")
+    e = _bin_edges(r, edges)
     full = np.concatenate([[-np.inf], e, [np.inf]])
     v = np.asarray(r.data.values, dtype=np.float64)
     if bool(np.any(np.isnan(v))):
         raise ArgumentError(f"Relation {r.name}: a NaN value lies in no bin.")
     j = np.searchsorted(e, v, side="right")          # the number of edges <= v: e_j <= v < e_{j+1}
     return setInterval(r, full[j], full[j + 1])
+
+
+def setTestInterval(r, lower, upper):
+    """What the held-out rows are records of, for the held-out log predictive density (macau(lpd=True)): row k of r.test_vec, in its
+    current order, says that the true value lies in [lower[k], upper[k]], and is scored by the mass the model gives that interval.
+    Either bound may be infinite (a censored test record is an interval with one infinite bound); lower[k] == upper[k] marks an
+    exact cell, scored by the Gaussian density at its stored value.  The stored test value must lie inside its bounds.  Nothing
+    but the LPD reads the bounds: predictions, RMSE and ROC stay what they are.  setTest and assignToTest replace the test
+    table and drop the bounds: call this after them.  Not on a probit relation, whose 0/1 test values are scored by the probit
+    likelihood."""
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): its test values are scored as 0/1 values, "
+                            "it does not take test bounds (setTestInterval).")
+    r.model.test_interval = _interval_bounds(r, lower, upper, test=True)
+    return None
+
+
+def setTestBinned(r, edges):
+    """Held-out values reported in bins: setBinned's edge rule (a stored value v lies in bin j when e_j <= v < e_{j+1}, the first
+    and the last bin open) applied to the rows of r.test_vec (setTestInterval)."""
+    e = _bin_edges(r, edges)
+    full = np.concatenate([[-np.inf], e, [np.inf]])
+    v = np.asarray(r.test_vec.values, dtype=np.float64)
+    if bool(np.any(np.isnan(v))):
+        raise ArgumentError(f"Relation {r.name}: a NaN test value lies in no bin.")
+    j = np.searchsorted(e, v, side="right")
+    return setTestInterval(r, full[j], full[j + 1])
+
+
+def _bin_edges(r, edges):
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim != 1 or len(e) == 0 or not bool(np.all(np.isfinite(e))) or not bool(np.all(np.diff(e) > 0)):
+        raise ArgumentError(f"Relation {r.name}: bin edges must be a non-empty list of finite, strictly increasing numbers.")
+    return e
+
+
+def check_test_interval(r):
+    """what the test bounds must still satisfy when macau(lpd=True) reads them (they may have been changed since setTestInterval)"""
+    b = np.asarray(r.model.test_interval)
+    if b.ndim != 2 or b.shape[1] != 2:
+        raise ArgumentError(f"Relation {r.name}: test bounds must be a (numTest, 2) array, not {b.shape}.")
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take test bounds (setTestInterval).")
+    r.model.test_interval = _interval_bounds(r, b[:, 0], b[:, 1], test=True)
 
 
 def _interval_guards(r):
@@ -326,21 +369,25 @@ def _interval_guards(r):
         raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take interval bounds (setInterval) as well.")
 
 
-def _interval_bounds(r, lower, upper):
-    n = r.data.nnz()
+def _interval_bounds(r, lower, upper, test=False):
+    """(n, 2) float64 bounds of the training rows (test: of the rows of test_vec) after the checks they must pass"""
+    n = len(r.test_vec) if test else r.data.nnz()
+    what = "test" if test else "training"
     try:
         lo, hi = np.asarray(lower, dtype=np.float64), np.asarray(upper, dtype=np.float64)
     except (TypeError, ValueError):
         raise ArgumentError(f"Relation {r.name}: interval bounds must be numbers.")
     if lo.ndim != 1 or hi.ndim != 1 or len(lo) != n or len(hi) != n:
-        raise ArgumentError(f"Relation {r.name} has {n} training rows but {lo.shape} lower and {hi.shape} upper bounds were given.")
+        raise ArgumentError(f"Relation {r.name} has {n} {what} rows but {lo.shape} lower and {hi.shape} upper bounds were given.")
     if bool(np.any(np.isnan(lo))) or bool(np.any(np.isnan(hi))):
         raise ArgumentError(f"Relation {r.name}: an interval bound is NaN (use -inf / +inf for an open side).")
     if bool(np.any(lo > hi)):
         raise ArgumentError(f"Relation {r.name}: a lower bound is above its upper bound (row {int(np.argmax(lo > hi)) + 1}).")
-    v = np.asarray(r.data.values, dtype=np.float64)
+    v = np.asarray(r.test_vec.values if test else r.data.values, dtype=np.float64)
     out = ~((lo <= v) & (v <= hi))
     if bool(np.any(out)):
+        if test:
+            raise ArgumentError(f"Relation {r.name}: the stored value of test row {int(np.argmax(out)) + 1} lies outside its bounds.")
         raise ArgumentError(f"Relation {r.name}: the stored value of row {int(np.argmax(out)) + 1} lies outside its bounds; it is where "
                             "the latent value starts.")
     return np.ascontiguousarray(np.stack([lo, hi], axis=1))
@@ -370,6 +417,7 @@ def assignToTest(r, test, rng=None):
     r.test_vec = TestVec(r.data.ids[rows0, :], r.data.values[rows0], r.data.names)
     r.data = r.data.removeSamples(test_id)
     r.test_label = r.test_vec.values < r.class_cut
+    r.model.test_interval = None
     if hasFeatures(r):
         r.test_F = feat.take_rows(r.F, rows0)
         train = np.ones(feat.feature_shape(r.F)[0], dtype=bool)
@@ -401,6 +449,7 @@ def setTest(r, test, test_feat=None):
         raise ArgumentError(f"Relation {r.name} has the probit noise model: its test values must be 0 or 1.")
     r.test_vec = TestVec(ids, vals, r.data.names)
     r.test_label = r.test_vec.values < r.class_cut
+    r.model.test_interval = None
     if hasFeatures(r):
         r.test_F = test_feat
     r._dev = None

@@ -378,6 +378,28 @@ int bdf_predict_update(bdf_ctx *ctx, bdf_pairs *p, int D, const double *const *f
 /* running state: avg (dev n), sq (dev n) */
 int bdf_pairs_state(const bdf_pairs *p, double **avg, double **sq, int64_t *n);
 
+/* ---- held-out log pointwise predictive density (csrc/k_lpd.hip, csrc/lpd.h) ----------- */
+/* One scoring step on the pairs: l_k = log p(value_k | the rows in `factors`, alpha), the log-likelihood of pair k's kind of
+ * record, with m = udot_k + (the pairs' baseline | mean_value), ra = sqrt(alpha), L = log Phi:
+ *   pairs with the probit link (bdf_pairs_set_link 1):   l = L(value_k > 1/2 ? m : -m); bounds_dev must be NULL (BDF_ERR_ARG);
+ *   bounds_dev NULL, or lo_k == hi_k:                     l = log(alpha / 2 pi) / 2 - alpha (value_k - m)^2 / 2;
+ *   lo_k < hi_k (either may be infinite):                 l = log(Phi(b) - Phi(a)), a = (lo_k - m) ra, b = (hi_k - m) ra, taken in
+ *     the lower tail (a + b > 0: (a, b) = (-b, -a)) and, where b <= -37, from the asymptotic form of L -- finite wherever a < b
+ *     as doubles, 0 for (-inf, +inf).
+ * bounds_dev (dev, nullable): n pairs (lo_k, hi_k) in the caller's order, row-major, aligned to 16 bytes; lo_k > hi_k or a NaN
+ * bound is undefined.  alpha_dev (dev, nullable) wins over alpha, which must otherwise be positive and finite (ignored with the
+ * probit link).  The running state, two doubles per pair that the pairs own (allocated at the first phase >= 1, freed by
+ * bdf_pairs_destroy) and a draw counter of its own, is a streaming log-sum-exp:
+ *   phase 0 (burn-in): no state is touched, lpd_k = l_k;   phase 1: (M, A) = (l, 1), draws = 1;
+ *   phase 2: M' = max(M, l), A = A exp(M - M') + exp(l - M'), M = M', draws += 1;   lpd_k = M + log A - log(draws).
+ * stats_out (dev 4 doubles): sum_k l_k of this draw, sum_k lpd_k after it, 0, 0 -- summed in a fixed order (bit-identical
+ * reruns).  Enqueued on ctx's stream.  BDF_ERR_ARG for a phase outside 0..2 and for phase 2 before a phase 1. */
+int bdf_pairs_lpd_update(bdf_ctx *ctx, bdf_pairs *p, const double *bounds_dev, int D, const double *const *factors,
+                         double mean_value, double alpha, const double *alpha_dev, int phase, double *stats_out);
+/* lpd_k = M + log A - log(draws) of every pair -> out_dev (dev n), in the caller's order whether or not the pairs are stored
+ * sorted.  BDF_ERR_ARG before the first phase 1. */
+int bdf_pairs_lpd(bdf_ctx *ctx, const bdf_pairs *p, double *out_dev);
+
 /* ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device (csrc/k_auc.hip) ------------ */
 /* bytes of the workspace bdf_auc_roc needs for n scores (-1: n < 0) */
 int64_t bdf_auc_workspace_bytes(int64_t n);

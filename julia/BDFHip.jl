@@ -499,6 +499,22 @@ function pairs_state(c::Context, p::DevPairs)
     end
     return avg, sq
 end
+"one scoring step of the held-out log predictive density on the pairs: the log-likelihood l of every pair's kind of record given
+the factors (probit link: log Phi(+-m); `bounds` -- device Float64, 2 x n, column k the (lower, upper) of pair k in the caller's
+order, or `nothing` -- with lower < upper: the interval's mass; otherwise the Gaussian density at the stored value), folded into
+the pairs' streaming log-sum-exp (phase 0 burn-in: nothing kept; 1 first posterior draw; 2 later ones); `alpha_dev` (a device
+scalar or `nothing`) wins over `alpha`; stats (DevArray of 4 doubles): sum of l, sum of lpd, 0, 0"
+function pairs_lpd_update!(c::Context, p::DevPairs, bounds, D, factors::Vector{<:DevArray}, mean_value, alpha, alpha_dev, phase::Integer,
+                           stats::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_pairs_lpd_update, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+                c.h, p.h, bounds === nothing ? C_NULL : bounds.p, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p,
+                phase, stats.p))
+end
+"lpd of every pair over the posterior draws scored so far -> out (DevArray of n doubles), in the caller's order"
+pairs_lpd!(c::Context, p::DevPairs, out::DevArray{Float64}) =
+    check(ccall((:bdf_pairs_lpd, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.h, p.h, out.p))
 
 # ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device ------------------------------------------------------------------
 "AUC_ROC(Ytrue, scores) of device arrays (labels: UInt8, nonzero = positive): (auc, C, P, Nn), C the exact pair count"
