@@ -19,6 +19,7 @@ P_HMC_MOMENTUM, P_HMC_ACCEPT = 10, 11
 P_PROBIT = 12
 P_CENSORED = 13
 P_INTERVAL = 14
+P_ORDINAL = 15
 
 
 class ArgumentError(ValueError):
@@ -86,7 +87,7 @@ class GibbsRelation(C.Structure):
                 ("nnz", C.c_int64), ("train", C.c_void_p), ("first_obs", C.c_int64), ("obs_block", C.c_int64), ("feat", C.c_void_p),
                 ("beta", C.c_void_p), ("linear", C.c_void_p), ("lambda_beta", C.c_double), ("feat_test", C.c_void_p),
                 ("test_baseline", C.c_void_p), ("probit", C.c_int32), ("_pad", C.c_int32), ("censor", C.c_void_p),
-                ("interval", C.c_void_p)]
+                ("interval", C.c_void_p), ("ordinal", C.c_void_p), ("ordinal_codes", C.c_void_p)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -143,6 +144,14 @@ _SIGS = {
                                     C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdf_interval_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bdf_ordinal_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]),
+    "bdf_ordinal_destroy": (C.c_int, [C.c_void_p]),
+    "bdf_ordinal_set_adapt": (C.c_int, [C.c_void_p, C.c_int64]),
+    "bdf_ordinal_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double,
+                                   C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]),
+    "bdf_ordinal_bounds": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "bdf_ordinal_read": (C.c_int, [C.c_void_p, c_dp, c_dp, c_i64p, c_i64p, c_dp, c_dp, C.c_int64]),
+    "bdf_ordinal_proposal": (C.c_int, [C.c_void_p, c_dp, c_dp, C.POINTER(C.c_int), c_dp]),
     "bdf_feat_linear": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
     "bdf_predict_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
     "bdf_sample_alpha": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int64, C.c_void_p, C.c_uint32, C.c_void_p]),

@@ -183,6 +183,31 @@ struct bdf_pairs {
     double lpd_draws;             // ... and the posterior draws it holds (a counter of its own, not `count`)
 };
 
+// bdf_ordinal (k_ordinal.hip): the edges of an ordinal relation and their Metropolis step's state, all of it in ONE device buffer
+// of doubles so that a caller who must put a chain back (bdf_gibbs_warm_device) copies one piece
+#define BDF_ORD_TABLE 17           // doubles per edge table: e_0 = -inf, e_1 .. e_{K-1}, e_K = +inf (+inf beyond K)
+#define BDF_ORD_CUR 0              // the current table
+#define BDF_ORD_PROP 17            // the proposed one (behind the current one: the mass kernel loads both as one run)
+#define BDF_ORD_JAC 34             // the proposal's log Jacobian term
+#define BDF_ORD_SIGMA 35           // the step size
+#define BDF_ORD_PROPOSALS 36       // steps taken
+#define BDF_ORD_ACCEPTS 37         // ... and accepted
+#define BDF_ORD_LAST_S 38          // the last step's log acceptance ratio (-inf: refused by the gap guard)
+#define BDF_ORD_ACCEPTED 39        // ... and its decision (1 / 0)
+#define BDF_ORD_VALID 40           // the proposal passed the gap guard (1 / 0)
+#define BDF_ORD_LOGU 41            // the log of the last step's uniform
+#define BDF_ORD_TRACE 48           // then capacity rows of K - 1 edges
+#define BDF_ORD_MAX_TRACE ((int64_t)1 << 24)   // rows a trace may have (2 GB of device memory at K = 16)
+struct bdf_ordinal {
+    bdf_ctx *ctx;
+    int K;
+    int64_t capacity;              // trace rows
+    int64_t adapt_steps;           // bdf_ordinal_set_adapt
+    size_t state_doubles;
+    double *state_dev;
+    hipStream_t stream;            // where the last step was enqueued (bdf_ordinal_read waits for it)
+};
+
 struct bdf_feat {
     bdf_ctx *ctx;
     int kind;             // 0 dense, 1 csr (real), 2 binary

@@ -358,6 +358,7 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
         BDF_REQUIRE(!r.censor || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the censored model needs its observations as pairs (train) and a linear buffer", k);
         BDF_REQUIRE(!r.interval || (!r.probit && !r.censor && !r.feat), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model takes neither the probit model, censoring flags nor relation features", k);
         BDF_REQUIRE(!r.interval || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model needs its observations as pairs (train) and a linear buffer", k);
+        BDF_REQUIRE(!r.ordinal || (r.interval && r.ordinal_codes && !g->comm), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the ordinal model needs the interval model's bounds and the observations' levels, on one rank", k);
         for (int m = 0; m < r.rel->n_modes; m++)
             BDF_REQUIRE(r.entity_of_mode[m] >= 0 && r.entity_of_mode[m] < (int)g->ent.size(), BDF_ERR_ARG,
                         "bdf_gibbs_set_relations: relation %d mode %d names entity %d", k, m, r.entity_of_mode[m]);
@@ -400,6 +401,11 @@ int update_relations(bdf_gibbs *g)
         // censored: the latent z of every flagged observation given the rows and the alpha just drawn (the sum of squares above was
         // that of the previous z: the pairs carry linear as their baseline); the rows then see linear = mean + y - z with alpha_dev
         if (r.censor && (rc = bdf_censored_draw(R, r.train, r.censor, D, fac, r.mean_value, 0.0, r.alpha_dev, r.rel_tag, r.linear + r.first_obs, nullptr)))
+            return rc;
+        // ordinal: one Metropolis step on the edges given the rows and the alpha just drawn, z integrated out; it rewrites the bounds
+        // that the interval draw below reads (the step adapts while the object's own count is within its burn-in)
+        if (r.ordinal && (rc = bdf_ordinal_step(R, r.ordinal, r.train, r.ordinal_codes, D, fac, r.mean_value, 0.0, r.alpha_dev, r.rel_tag, -1,
+                                                const_cast<double *>(r.interval))))
             return rc;
         // interval-censored: the same draw at the same place, between the two bounds of every bounded observation
         if (r.interval && (rc = bdf_interval_draw(R, r.train, r.interval, D, fac, r.mean_value, 0.0, r.alpha_dev, r.rel_tag, r.linear + r.first_obs, nullptr)))
@@ -526,6 +532,10 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         if (r.probit) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});     // y - z of the last draw
         if (r.censor) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});     // mean + y - z of the last draw
         if (r.interval) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});   // mean + y - z of the last draw
+        if (r.ordinal) {                    // the edges, the step size, the counters and the trace; the bounds made from the edges
+            pieces.push_back({r.ordinal->state_dev, r.ordinal->state_doubles * sizeof(double), false, 0});
+            pieces.push_back({const_cast<double *>(r.interval), (size_t)r.train->n * 2 * sizeof(double), false, 0});
+        }
     }
     size_t total = 0;
     for (auto &pc : pieces) total += (pc.bytes + 255) & ~(size_t)255;

@@ -14,7 +14,7 @@ import numpy as np
 from . import features as feat
 from ._lib import ArgumentError
 from .engine import GibbsEngine
-from .relation_data import check_test_interval, hasFeatures, numTest, toStr
+from .relation_data import _ordinal_bounds, check_test_interval, hasFeatures, numTest, toStr
 
 
 def AUC_ROC(Ytrue, scores):
@@ -90,12 +90,21 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     test = eng.test_pairs() if haveTest else None
     train = eng.train_pairs() if rmse_train else None
     lpd_bounds, lpd_avg = None, float("nan")
+    # ordinal first relation with sampled edges: a trace row per iteration, the step size adapted in the burn-in
+    ordinal = eng.ordinal_begin(burnin, psamples) if rel.model.ordinal is not None else None
+    lpd_codes = None
     if lpd:
         # held-out log predictive density: what kind of record every test cell is -- a 0/1 value of a probit
-        # relation, an interval (setTestInterval / setTestBinned) or a measurement
+        # relation, an interval (setTestInterval / setTestBinned), a level of an ordinal relation (setTestOrdinal) or a measurement
         if rel.model.test_interval is not None:
             check_test_interval(rel)
             lpd_bounds = test.ctx.tensor(rel.model.test_interval)
+        elif rel.model.test_ordinal is not None:
+            # the levels' bins between the fixed edges, once; between sampled edges they follow every draw (refreshed below)
+            lpd_bounds = test.ctx.tensor(_ordinal_bounds(rel.model.test_ordinal, np.arange(1, rel.model.ordinal["K"]) + 0.5))
+            if ordinal is not None:
+                import torch
+                lpd_codes = test.ctx.tensor(rel.model.test_ordinal, dtype=torch.int8)
     f_output = []
     yhat_full = None
     if full_prediction:
@@ -122,7 +131,14 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
             # has read the same double, and the device scalar is redrawn on another stream than the pairs')
             a = 1.0 if rel.model.probit else (rel._dev.alpha_dev if (rel.model.alpha_sample and eng.native) else rel.model.alpha)
+            if lpd_codes is not None:
+                # this draw's edges were published on the row stream before this iteration's rows, which the pairs' stream is behind
+                ordinal.bounds(test.ctx, lpd_codes, lpd_bounds)
             test.lpd_update(D, facs, rel.model.mean_value, a, phase, lpd_bounds)
+            if lpd_codes is not None and test.ctx is not eng.ctx:
+                # (step by step the pairs have a stream of their own: the next iteration's step may not publish its edges under this
+                # launch.  The native iteration scores on the row stream itself and needs nothing)
+                eng.ctx.stream.wait_stream(test.ctx.stream)
         if i > burnin:
             if output:
                 ndigits = int(math.floor(math.log10(psamples))) + 1
@@ -167,6 +183,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 estr = " ".join(toStr(en) for en in data.entities)
                 rstr = " ".join(toStr(r) for r in data.relations)
                 lstr = f" LPD={lpd_avg:.4f}" if lpd else ""
+                if ordinal is not None:
+                    lstr += " cut=[" + " ".join(f"{e:.3f}" for e in rel.model.ordinal_edges) + "]"
                 print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f}{lstr} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
 
     eng.sync()
@@ -180,6 +198,18 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         "accuracy": err_avg,
         "ROC": roc_avg,
     }
+    if ordinal is not None:
+        got = ordinal.read(burnin + psamples)
+        tr = got["trace"]
+        # a step was accepted iff it left other edges than it found (the row before; the start k + 1/2 before the first)
+        before = np.vstack([np.arange(1, ordinal.K) + 0.5, tr[:-1]]) if len(tr) else tr
+        moved = np.any(tr != before, axis=1)[burnin:]
+        result["ordinal"] = {"edges": tr[burnin:].mean(axis=0) if psamples else np.full(ordinal.K - 1, np.nan),
+                             "edges_trace": tr[burnin:].copy(), "accept": float(moved.mean()) if psamples else float("nan"),
+                             "step": got["sigma"]}
+    elif rel.model.ordinal is not None:                 # sample_edges = false: the edges are where they started
+        e = np.arange(1, rel.model.ordinal["K"]) + 0.5
+        result["ordinal"] = {"edges": e, "edges_trace": np.tile(e, (psamples, 1)), "accept": 0.0, "step": rel.model.ordinal["step"]}
     if lpd:
         result["LPD"] = lpd_avg
     if full_prediction:

@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from . import features as feat
 from ._lib import ArgumentError, GibbsEntity, Term, check, lib
-from .relation_data import check_censored, check_interval, check_probit
+from .relation_data import check_censored, check_interval, check_ordinal, check_probit
 
 
 def _ptr(t):
@@ -616,6 +616,59 @@ class EntityState:
         return a.T.copy() if a.ndim == 2 else a.copy()
 
 
+class DeviceOrdinal:
+    """bdf_ordinal: the sampled edges of an ordinal relation with their Metropolis step's state and trace, on the device."""
+
+    def __init__(self, ctx, K, step=0.1, trace_capacity=0):
+        self.ctx, self.K, self.capacity = ctx, int(K), int(trace_capacity)
+        self.handle = C.c_void_p()
+        check(lib().bdf_ordinal_create(ctx.handle, self.K, float(step), self.capacity, C.byref(self.handle)))
+        ctx.adopt(self)
+
+    def set_adapt(self, steps):
+        """the first `steps` steps taken with adapt = -1 adapt the step size (the burn-in's length)"""
+        check(lib().bdf_ordinal_set_adapt(self.handle, int(steps)))
+
+    def step(self, ctx, train, codes, D, factors, mean_value, alpha, rel_tag, adapt, bounds):
+        """one Metropolis step on ctx's stream (bdf_ordinal_step); alpha: a float, or a device scalar read on the device; codes: int8
+        device tensor, the levels in the caller's order; bounds: (n, 2) device tensor, rewritten when the proposal is accepted"""
+        on_dev = torch.is_tensor(alpha)
+        fp = (C.c_void_p * len(factors))(*[f.data_ptr() for f in factors])
+        check(lib().bdf_ordinal_step(ctx.handle, self.handle, train.handle, _ptr(codes), int(D), fp, float(mean_value),
+                                     0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(rel_tag), int(adapt), _ptr(bounds)))
+
+    def bounds(self, ctx, codes, out):
+        """out[k] = the bin of level codes[k] under the current edges, on ctx's stream (bdf_ordinal_bounds)"""
+        check(lib().bdf_ordinal_bounds(ctx.handle, self.handle, _ptr(codes), int(codes.numel()), _ptr(out)))
+
+    def read(self, trace_rows=0):
+        """waits for the last step; {"edges", "sigma", "proposals", "accepts", "S", "trace"}"""
+        edges, sigma, S = np.zeros(self.K - 1), C.c_double(), C.c_double()
+        npr, nac = C.c_int64(), C.c_int64()
+        trace = np.zeros((int(trace_rows), self.K - 1))
+        check(lib().bdf_ordinal_read(self.handle, edges.ctypes.data_as(_lib.c_dp), C.byref(sigma), C.byref(npr), C.byref(nac), C.byref(S),
+                                     trace.ctypes.data_as(_lib.c_dp), int(trace_rows)))
+        return {"edges": edges, "sigma": sigma.value, "proposals": npr.value, "accepts": nac.value, "S": S.value, "trace": trace}
+
+    def proposal(self):
+        """(parity checks) the last step's {"edges" proposed, "jacobian", "accepted", "log_u"}"""
+        edges, jac, lu, acc = np.zeros(self.K - 1), C.c_double(), C.c_double(), C.c_int()
+        check(lib().bdf_ordinal_proposal(self.handle, edges.ctypes.data_as(_lib.c_dp), C.byref(jac), C.byref(acc), C.byref(lu)))
+        return {"edges": edges, "jacobian": jac.value, "accepted": bool(acc.value), "log_u": lu.value}
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:
+                lib().bdf_ordinal_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GibbsEngine:
     """Device state of a RelationData and the per-iteration steps of macau.jl:80-140."""
 
@@ -632,6 +685,8 @@ class GibbsEngine:
                 check_censored(r)
                 if shard is not None and shard[1] > 1:
                     raise ArgumentError(f"Relation {r.name} has censoring flags: one rank only")
+            if r.model.ordinal is not None:
+                check_ordinal(r)
             if r.model.interval is not None:
                 check_interval(r)
                 if shard is not None and shard[1] > 1:
@@ -697,7 +752,7 @@ class GibbsEngine:
             r._dev = dr
             self.rel.append(dr)
             # relation-level side information (RelationData.jl:348-353): FF path only, as in the reference
-            dr.F = dr.beta = dr.linear = dr.train = dr.censor = dr.interval = None
+            dr.F = dr.beta = dr.linear = dr.train = dr.censor = dr.interval = dr.ordinal = dr.ord_codes = None
             # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
             # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
             # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
@@ -750,6 +805,12 @@ class GibbsEngine:
                 if len(r.entities) == 2 and nn:
                     dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
                 check(lib().bdf_pairs_set_baseline(dr.train.handle, _ptr(dr.linear)))
+            if r.model.ordinal is not None and r.model.ordinal["sample_edges"]:
+                # the ordinal model: the interval model above whose bounds follow the sampled edges -- one Metropolis step on them
+                # after alpha and before the latent draw of every iteration (bdf_ordinal_step), which rewrites dr.interval.  Without
+                # sampled edges the relation IS the interval relation above.  (ordinal_begin gives the object its trace and burn-in)
+                dr.ord_codes = self.ctx.tensor(r.model.ordinal_codes if nn else np.zeros(1, dtype=np.int8), dtype=torch.int8)
+                dr.ordinal = DeviceOrdinal(self.ctx, r.model.ordinal["K"], r.model.ordinal["step"], 0)
             dr.alpha_dev = self.ctx.tensor([float(r.model.alpha)])
         self._test_pairs = None
         self._train_pairs = None
@@ -842,12 +903,28 @@ class GibbsEngine:
                 g.censor, g.linear = dr.censor.data_ptr(), dr.linear.data_ptr()
             if dr.interval is not None:
                 g.interval, g.linear = dr.interval.data_ptr(), dr.linear.data_ptr()
+            if dr.ordinal is not None:
+                g.ordinal, g.ordinal_codes = dr.ordinal.handle, dr.ord_codes.data_ptr()
             if dr.F is not None:
                 g.feat, g.beta, g.linear, g.lambda_beta = dr.F.handle, dr.beta.data_ptr(), dr.linear.data_ptr(), r.model.lambda_beta
                 if ri == 0 and getattr(dr, "F_test", None) is not None:
                     g.feat_test, g.test_baseline = dr.F_test.handle, dr.test_baseline.data_ptr()
         self._gibbs_relations = arr            # (the library copies the records; the tensors they point at live in self.rel)
         check(lib().bdf_gibbs_set_relations(self.gibbs, len(rows), C.cast(arr, C.c_void_p)))
+
+    def ordinal_begin(self, burnin, psamples, ri=0):
+        """a run of burnin + psamples iterations starts on ordinal relation ri (sampled edges): its object gets a trace of that many
+        rows and adapts its step size for the first `burnin` steps.  The chain must be at its start (a fresh engine)."""
+        r, dr = self.data.relations[ri], self.rel[ri]
+        if dr.ordinal is None:
+            return None
+        if dr.ordinal.read()["proposals"] != 0:
+            raise ArgumentError(f"Relation {r.name} is ordinal: its edges' trace and burn-in cover one run; build a new engine (reset_model = true)")
+        dr.ordinal.close()
+        dr.ordinal = DeviceOrdinal(self.ctx, r.model.ordinal["K"], r.model.ordinal["step"], int(burnin) + int(psamples))
+        dr.ordinal.set_adapt(burnin)
+        self._register_relations()
+        return dr.ordinal
 
     def warm_device(self, milliseconds=50.0):
         """set-up (native iteration): bring the device to its working state before the first iteration
@@ -962,6 +1039,8 @@ class GibbsEngine:
                 fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
                 check(lib().bdf_censored_draw(self.ctx.handle, dr.train.handle, _ptr(dr.censor), self.D, fp, r.model.mean_value,
                                               r.model.alpha, _ptr(dr.alpha_dev), ri + 1, _ptr(dr.linear), None))
+            if dr.ordinal is not None:   # the edges | U, V, alpha with z integrated out; the bounds of the draw below follow them
+                dr.ordinal.step(self.ctx, dr.train, dr.ord_codes, self.D, facs, r.model.mean_value, dr.alpha_dev, ri + 1, -1, dr.interval)
             if dr.interval is not None:  # z | U, V, alpha between its bounds: the rows then see linear_values = mean + y - z
                 fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
                 check(lib().bdf_interval_draw(self.ctx.handle, dr.train.handle, _ptr(dr.interval), self.D, fp, r.model.mean_value,
@@ -1056,6 +1135,8 @@ class GibbsEngine:
                 r.model.beta = dr.beta.cpu().numpy().copy()
             if r.model.alpha_sample and self.native:       # (step by step the host reads it every iteration)
                 r.model.alpha = float(dr.alpha_dev.item())
+            if dr.ordinal is not None:
+                r.model.ordinal_edges = dr.ordinal.read()["edges"]
 
     # ---- one Gibbs iteration (the timed unit of bench.py) ------------------------------------------------------
     def step(self, i, phase, clamp=(), class_cut=0.0):

@@ -85,6 +85,8 @@ def toStr(x):
         s += f" cens:{int(np.count_nonzero(x.model.censor))}"
     if x.model.interval is not None:
         s += f" intv:{int(np.count_nonzero(x.model.interval[:, 0] < x.model.interval[:, 1]))}"
+    if x.model.ordinal is not None:
+        s += f" ord:{x.model.ordinal['K']}"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -103,6 +105,10 @@ class RelationModel:
         self.censor = None        # setCensored: int8 per training row, 0 a measurement, +1 "at least the value", -1 "at most the value"
         self.interval = None      # setInterval / setBinned: float64 (n, 2), per training row the bounds lower <= upper of its value
         self.test_interval = None # setTestInterval / setTestBinned: float64 (numTest, 2), the same per row of test_vec (macau(lpd=True))
+        self.ordinal = None       # setOrdinal: {"K", "step", "sample_edges"}; the training values are levels 1 .. K
+        self.ordinal_codes = None # ... int8 per training row, its level
+        self.ordinal_edges = None # ... float64 (K - 1): the edges e_1 .. e_{K-1}, k + 1/2 until macau() has drawn them (then the last draw)
+        self.test_ordinal = None  # setTestOrdinal: int8 per row of test_vec, its level (macau(lpd=True))
 
 
 class RelationTemp:
@@ -298,6 +304,8 @@ def setInterval(r, lower, upper):
     latent starts, so it must lie inside its bounds.  Predictions, the test set and alpha (fixed, setPrecision or alpha_sample)
     stay what they are.  Call it AFTER the test split (assignToTest removes training rows; setTest does not)."""
     _interval_guards(r)
+    if r.model.ordinal is not None:
+        raise ArgumentError(f"Relation {r.name} is ordinal (setOrdinal): its bounds follow its edges, it does not take bounds of its own (setInterval / setBinned).")
     r.model.interval = _interval_bounds(r, lower, upper)
     r._dev = None
     return None
@@ -328,6 +336,7 @@ def setTestInterval(r, lower, upper):
         raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): its test values are scored as 0/1 values, "
                             "it does not take test bounds (setTestInterval).")
     r.model.test_interval = _interval_bounds(r, lower, upper, test=True)
+    r.model.test_ordinal = None
     return None
 
 
@@ -341,6 +350,90 @@ def setTestBinned(r, edges):
         raise ArgumentError(f"Relation {r.name}: a NaN test value lies in no bin.")
     j = np.searchsorted(e, v, side="right")
     return setTestInterval(r, full[j], full[j + 1])
+
+
+ORDINAL_MIN_LEVELS, ORDINAL_MAX_LEVELS = 4, 16
+
+
+def _ordinal_codes(r, values, K, what):
+    v = np.asarray(values, dtype=np.float64)
+    if not bool(np.all(np.isfinite(v))) or not bool(np.all(v == np.round(v))) or (len(v) and (v.min() < 1 or v.max() > K)):
+        raise ArgumentError(f"Relation {r.name}: the {what} values of an ordinal relation must be the integers 1 ... {K}.")
+    return np.ascontiguousarray(v, dtype=np.int8)
+
+
+def _ordinal_bounds(codes, edges):
+    """(n, 2) bounds of the levels `codes` under the interior edges e_1 .. e_{K-1}: setBinned's rule applied to the levels"""
+    e = np.asarray(edges, dtype=np.float64)
+    full = np.concatenate([[-np.inf], e, [np.inf]])
+    j = np.searchsorted(e, np.asarray(codes, dtype=np.float64), side="right")
+    return np.ascontiguousarray(np.stack([full[j], full[j + 1]], axis=1))
+
+
+def setOrdinal(r, n_levels=None, step=0.1, sample_edges=True):
+    """Ordinal probit noise model (Albert & Chib 1993; the cutpoint step of Cowles 1996): the training values are levels 1 ... K,
+    4 <= K <= 16 (n_levels; by default the largest value), y = k iff e_{k-1} <= z < e_k for the latent z ~ N(u'v + mean, 1 / alpha)
+    of the interval model.  e_1 = 1.5 and e_{K-1} = K - 1/2 are fixed, so that the mean, alpha and the predictions stay on the
+    scale of the levels; the K - 3 edges between them start at k + 1/2 and macau() samples them, one Metropolis step per iteration
+    with step size `step` adapted during the burn-in.  sample_edges=False keeps them where they start: setBinned(rel, [1.5, ...,
+    K - 1/2]) exactly.  Everything the interval model refuses is refused here (relation features, rmse_train, more than one rank),
+    and so are setProbit, setCensored and a setInterval / setBinned of the relation's own.  Call it AFTER the test split.  The
+    edges' trace and the step size's burn-in belong to one macau() run: macau(engine=..., reset_model=False) does not continue a
+    chain whose edges have moved, it is refused."""
+    _interval_guards(r)
+    if r.model.interval is not None and r.model.ordinal is None:
+        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): an ordinal relation's bounds follow its edges (setOrdinal).")
+    v = np.asarray(r.data.values, dtype=np.float64)
+    if n_levels is None:
+        if len(v) == 0 or not bool(np.all(np.isfinite(v))):
+            raise ArgumentError(f"Relation {r.name}: the training values of an ordinal relation must be the integers 1 ... K.")
+        n_levels = v.max()
+    if isinstance(n_levels, bool) or not isinstance(n_levels, (int, float, np.integer, np.floating)) or not np.isfinite(n_levels) \
+            or n_levels != int(n_levels):
+        raise ArgumentError(f"Relation {r.name}: n_levels must be an integer.")
+    K = int(n_levels)
+    if K == 3:
+        raise ArgumentError(f"Relation {r.name}: with 3 levels both edges are fixed and nothing is left to sample: use setBinned(rel, [1.5, 2.5]).")
+    if K < ORDINAL_MIN_LEVELS or K > ORDINAL_MAX_LEVELS:
+        raise ArgumentError(f"Relation {r.name}: an ordinal relation has {ORDINAL_MIN_LEVELS} ... {ORDINAL_MAX_LEVELS} levels, not {K}.")
+    step = float(step)
+    if not (1e-8 <= step <= 10.0):
+        raise ArgumentError(f"Relation {r.name}: step = {step} must lie in [1e-8, 10].")
+    codes = _ordinal_codes(r, v, K, "training")
+    edges = np.arange(1, K, dtype=np.float64) + 0.5
+    b = _ordinal_bounds(codes, edges)
+    r.model.interval = _interval_bounds(r, b[:, 0], b[:, 1])
+    r.model.ordinal = {"K": K, "step": step, "sample_edges": bool(sample_edges)}
+    r.model.ordinal_codes, r.model.ordinal_edges = codes, edges
+    r.model.test_ordinal = None
+    r._dev = None
+    return None
+
+
+def setTestOrdinal(r):
+    """The held-out rows of an ordinal relation are levels too, for the held-out log predictive density (macau(lpd=True)): row k of
+    r.test_vec is scored by the mass of its level's bin, between the edges of every posterior draw (with sample_edges=False: the
+    fixed ones).  setTest and assignToTest replace the test table and drop this: call it after them, and after setOrdinal."""
+    if r.model.ordinal is None:
+        raise ArgumentError(f"Relation {r.name} is not ordinal: call setOrdinal first (or setTestBinned for fixed bins).")
+    r.model.test_ordinal = _ordinal_codes(r, r.test_vec.values, r.model.ordinal["K"], "test")
+    r.model.test_interval = None
+    return None
+
+
+def check_ordinal(r):
+    """what an ordinal relation must still satisfy when a sampler is built on it (it may have been changed since setOrdinal); the
+    chain starts from the edges k + 1/2"""
+    o = r.model.ordinal
+    K = int(o["K"])
+    if K < ORDINAL_MIN_LEVELS or K > ORDINAL_MAX_LEVELS or not (1e-8 <= float(o["step"]) <= 10.0):
+        raise ArgumentError(f"Relation {r.name}: an ordinal relation has {ORDINAL_MIN_LEVELS} ... {ORDINAL_MAX_LEVELS} levels and a step in [1e-8, 10].")
+    r.model.ordinal_codes = _ordinal_codes(r, r.data.values, K, "training")
+    r.model.ordinal_edges = np.arange(1, K, dtype=np.float64) + 0.5
+    b = _ordinal_bounds(r.model.ordinal_codes, r.model.ordinal_edges)
+    r.model.interval = _interval_bounds(r, b[:, 0], b[:, 1])
+    if r.model.test_ordinal is not None:
+        r.model.test_ordinal = _ordinal_codes(r, r.test_vec.values, K, "test")
 
 
 def _bin_edges(r, edges):
@@ -418,6 +511,7 @@ def assignToTest(r, test, rng=None):
     r.data = r.data.removeSamples(test_id)
     r.test_label = r.test_vec.values < r.class_cut
     r.model.test_interval = None
+    r.model.test_ordinal = None
     if hasFeatures(r):
         r.test_F = feat.take_rows(r.F, rows0)
         train = np.ones(feat.feature_shape(r.F)[0], dtype=bool)
@@ -450,6 +544,7 @@ def setTest(r, test, test_feat=None):
     r.test_vec = TestVec(ids, vals, r.data.names)
     r.test_label = r.test_vec.values < r.class_cut
     r.model.test_interval = None
+    r.model.test_ordinal = None
     if hasFeatures(r):
         r.test_F = test_feat
     r._dev = None

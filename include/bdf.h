@@ -56,6 +56,7 @@ extern "C" {
 #define BDF_P_PROBIT       12  /* bdf_probit_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 #define BDF_P_CENSORED     13  /* bdf_censored_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 #define BDF_P_INTERVAL     14  /* bdf_interval_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
+#define BDF_P_ORDINAL      15  /* bdf_ordinal_step: entity 0x800000 | rel_tag; row 0, normal k: the proposal's k-th normal; row 1, pair 0: the uniform */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -63,6 +64,7 @@ typedef struct bdf_pairs bdf_pairs;  /* Relation.test_vec (+ running prediction 
 typedef struct bdf_feat  bdf_feat;   /* Entity.F operator (dense / CSR / binary CSR / COO)  */
 typedef struct bdf_comm  bdf_comm;   /* the ranks (GPUs) that share the entities' rows       */
 typedef struct bdf_gibbs bdf_gibbs;  /* a whole Gibbs iteration enqueued from native code    */
+typedef struct bdf_ordinal bdf_ordinal;  /* the sampled cutpoints of an ordinal relation      */
 
 const char *bdf_last_error(void);
 int bdf_version(void);
@@ -354,6 +356,46 @@ int bdf_censored_draw(bdf_ctx *ctx, const bdf_pairs *train, const int8_t *censor
 int bdf_interval_draw(bdf_ctx *ctx, const bdf_pairs *train, const double *bounds_dev, int D, const double *const *factors,
                       double mean_value, double alpha, const double *alpha_dev, uint32_t rel_tag, double *linear_out, double *z_out);
 
+/* Ordinal probit noise model (csrc/k_ordinal.hip, csrc/ordinal.h): the training values of a relation are
+ * levels 1 .. K (4 <= K <= 16), y = k iff e_{k-1} <= z < e_k for the latent z ~ N(udot + mean_value, 1 / alpha) of the interval
+ * model, with e_0 = -inf, e_K = +inf, e_1 = 1.5 and e_{K-1} = K - 1/2 fixed and the K - 3 edges between them sampled under a
+ * uniform prior on their order.  The object keeps the edges (they start at k + 1/2), the step size sigma (it starts at `step`, in
+ * [1e-8, 10]), two counters and a trace of trace_capacity rows (at most 2^24) of K - 1 edges, all on the device. */
+int bdf_ordinal_create(bdf_ctx *ctx, int K, double step, int64_t trace_capacity, bdf_ordinal **out);
+int bdf_ordinal_destroy(bdf_ordinal *ord);
+/* One Metropolis step on the edges with z integrated out, then the rows' bounds; four launches on ctx's stream, no synchronisation.
+ * With the gaps g_k = e_{k+1} - e_k (k = 1 .. K-2), R = e_{K-1} - e_1 and theta_k = log(g_k / g_{K-2}) (k = 1 .. K-3):
+ *   theta'_k = theta_k + sigma eps_k, eps_k = normal k of stream (BDF_P_ORDINAL, 0x800000 | rel_tag, row 0) at the context's sweep;
+ *   w = (exp theta'_1, ..., exp theta'_{K-3}, 1), g' = R w / sum w, e'_k = e_1 + g'_1 + ... + g'_{k-1};
+ *   S = sum over the pairs of [M(m; e'_{y-1}, e'_y) - M(m; e_{y-1}, e_y)] + sum_k log g'_k - sum_k log g_k, M the log mass of
+ *   bdf_pairs_lpd_update, m = udot + mean_value (NOT the pairs' baseline), y = codes_dev[k] (dev, one int8 per pair IN THE CALLER'S
+ *   ORDER); a pair whose two edges did not move -- levels 1 and K always -- adds an exact 0; the sum is taken in a fixed order;
+ *   accepted iff log u < S, u the uniform of stream (BDF_P_ORDINAL, 0x800000 | rel_tag, row 1, pair 0); a proposal with a gap
+ *   g' <= 1e-6 is refused outright (S reads -inf): a truncation of the prior, there because equal edges would read as "a
+ *   measurement" to bdf_interval_draw.
+ * adapt 1: after the i-th step of the object, log sigma += (accepted - 0.3) / sqrt(i), sigma kept in [1e-8, 10]; 0: sigma stays;
+ * -1: as 1 while fewer steps than bdf_ordinal_set_adapt stated have been taken, as 0 afterwards (decided on the device).
+ * The current edges are appended to the trace (row = steps taken before this one) while it has room.  bounds_dev (dev, n pairs of
+ * doubles in the caller's order, aligned to 16 bytes): rewritten to (e_{y-1}, e_y) when the proposal was accepted, untouched
+ * otherwise -- the caller starts it from the edges k + 1/2.  alpha_dev (dev, nullable) wins over alpha. */
+int bdf_ordinal_step(bdf_ctx *ctx, bdf_ordinal *ord, const bdf_pairs *train, const int8_t *codes_dev, int D, const double *const *factors,
+                     double mean_value, double alpha, const double *alpha_dev, uint32_t rel_tag, int adapt, double *bounds_dev);
+/* how many steps of the object adapt under adapt = -1 (the burn-in's length; 0 at creation) */
+int bdf_ordinal_set_adapt(bdf_ordinal *ord, int64_t steps);
+/* bounds_out[k] = (e_{y-1}, e_y) for y = codes_dev[k], k < n, from the current edges (test cells: their bins under this draw's
+ * edges); enqueued on ctx's stream, which the caller orders against the stream of the steps. */
+int bdf_ordinal_bounds(bdf_ctx *ctx, const bdf_ordinal *ord, const int8_t *codes_dev, int64_t n, double *bounds_out);
+/* Waits for the stream of the last step, then: edges (K - 1 doubles e_1 .. e_{K-1}), sigma, the counters, the last step's S, and
+ * the first trace_rows rows of the trace (rows no step has written are NaN).  Every output is nullable.  BDF_ERR_ARG when
+ * trace_rows exceeds the capacity. */
+int bdf_ordinal_read(bdf_ordinal *ord, double *edges, double *sigma, int64_t *proposals, int64_t *accepts, double *last_S,
+                     double *trace, int64_t trace_rows);
+/* The last step's proposal after the same wait: the proposed e'_1 .. e'_{K-1}, the Jacobian term, whether it was accepted
+ * (1 / 0) and the log of its uniform.  Every output is nullable.  Beyond what a sampler needs, and part of the interface on
+ * purpose: it is how a step is held against a restatement term by term (bdf_ordinal_read gives only S and the outcome), the
+ * way z_out of the latent draws is, and what a caller looks at when a chain's acceptance rate surprises. */
+int bdf_ordinal_proposal(bdf_ordinal *ord, double *edges, double *jacobian, int *accepted, double *log_u);
+
 
 /* ---- f2: test-set prediction (src/sampling.jl:9-45, macau.jl:142-203, 231-241) -------- */
 /* ids: n x n_modes column-major 1-based (test_vec[:,1:end-1]); values: n (test_vec[:,end]) */
@@ -610,6 +652,11 @@ typedef struct {
      * rows then read `linear` and alpha_dev.  The caller gives `train` the baseline `linear` (bdf_pairs_set_baseline) and starts
      * `linear` at mean_value.  Not with probit, censor or feat; needs train and linear */
     const double *interval;
+    /* ordinal noise model (a zeroed tail is "none"): the sampled edges and the observations' levels (dev, one int8 per observation of
+     * `train` in the caller's order).  bdf_ordinal_step (adapt -1) after sample_alpha and before bdf_interval_draw, rewriting
+     * `interval`, which is required and therefore not const to the library; one rank, no feat */
+    bdf_ordinal *ordinal;
+    const int8_t *ordinal_codes;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

@@ -499,6 +499,52 @@ function pairs_state(c::Context, p::DevPairs)
     end
     return avg, sq
 end
+# ---- the ordinal noise model: sampled cutpoints (csrc/k_ordinal.hip) --------------------------------------------------------
+"the edges of an ordinal relation with levels 1 .. K (4 <= K <= 16), their Metropolis step's size and counters, and a trace of
+`trace_capacity` rows, on the device"
+mutable struct Ordinal
+    h::Ptr{Cvoid}
+    ctx::Context
+    K::Int
+    capacity::Int
+    function Ordinal(c::Context, K::Integer, step::Real=0.1, trace_capacity::Integer=0)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:bdf_ordinal_create, lib), Cint, (Ptr{Cvoid}, Cint, Float64, Int64, Ref{Ptr{Cvoid}}), c.h, K, step, trace_capacity, out))
+        o = new(out[], c, K, trace_capacity)
+        finalizer(x -> ccall((:bdf_ordinal_destroy, lib), Cint, (Ptr{Cvoid},), x.h), o)
+        o
+    end
+end
+"how many steps adapt the step size under adapt = -1 (the burn-in's length)"
+ordinal_set_adapt!(o::Ordinal, steps::Integer) = check(ccall((:bdf_ordinal_set_adapt, lib), Cint, (Ptr{Cvoid}, Int64), o.h, steps))
+"one Metropolis step on the edges with the latents integrated out, then the rows' bounds (device Float64, 2 x n, rewritten when the
+proposal was accepted); `codes`: device Int8 levels of `train` in the caller's order; adapt: 1, 0 or -1 (by ordinal_set_adapt!)"
+function ordinal_step!(c::Context, o::Ordinal, train::DevPairs, codes::DevArray{Int8}, D, factors::Vector{<:DevArray}, mean_value, alpha, alpha_dev,
+                       rel_tag, adapt::Integer, bounds::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_ordinal_step, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}, UInt32, Cint, Ptr{Cvoid}),
+                c.h, o.h, train.h, codes.p, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, rel_tag, adapt, bounds.p))
+end
+"bounds (device Float64, 2 x n) of the levels in `codes` (device Int8, n) under the current edges: held-out cells' bins"
+ordinal_bounds!(c::Context, o::Ordinal, codes::DevArray{Int8}, n::Integer, bounds::DevArray{Float64}) =
+    check(ccall((:bdf_ordinal_bounds, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}), c.h, o.h, codes.p, n, bounds.p))
+"(edges e_1 .. e_{K-1}, sigma, proposals, accepts, the last step's S, the first `rows` rows of the trace as a (K - 1) x rows matrix);
+waits for the stream of the last step"
+function ordinal_read(o::Ordinal, rows::Integer=0)
+    edges, sigma, np, na, S = zeros(o.K - 1), Ref(0.0), Ref{Int64}(0), Ref{Int64}(0), Ref(0.0)
+    trace = zeros(o.K - 1, rows)
+    check(ccall((:bdf_ordinal_read, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}, Ref{Int64}, Ref{Int64}, Ref{Float64}, Ptr{Float64}, Int64),
+                o.h, edges, sigma, np, na, S, trace, rows))
+    return edges, sigma[], np[], na[], S[], trace
+end
+"(parity checks) the last step's proposed edges, its Jacobian term, whether it was accepted and the log of its uniform"
+function ordinal_proposal(o::Ordinal)
+    edges, jac, acc, lu = zeros(o.K - 1), Ref(0.0), Ref{Cint}(0), Ref(0.0)
+    check(ccall((:bdf_ordinal_proposal, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ref{Float64}, Ref{Cint}, Ref{Float64}), o.h, edges, jac, acc, lu))
+    return edges, jac[], acc[] != 0, lu[]
+end
+
 "one scoring step of the held-out log predictive density on the pairs: the log-likelihood l of every pair's kind of record given
 the factors (probit link: log Phi(+-m); `bounds` -- device Float64, 2 x n, column k the (lower, upper) of pair k in the caller's
 order, or `nothing` -- with lower < upper: the interval's mass; otherwise the Gaussian density at the stored value), folded into
@@ -576,6 +622,8 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     _pad::Int32
     censor::Ptr{Cvoid}                            # censored noise model: device Int8 flags per observation of train (C_NULL: none)
     interval::Ptr{Cvoid}                          # interval-censored noise model: device Float64 (lower, upper) per observation of train (C_NULL: none)
+    ordinal::Ptr{Cvoid}                           # ordinal noise model: an Ordinal's handle (C_NULL: none); needs interval
+    ordinal_codes::Ptr{Cvoid}                     # ... and device Int8 levels 1 .. K per observation of train
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
