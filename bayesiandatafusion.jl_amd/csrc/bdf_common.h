@@ -181,6 +181,8 @@ struct bdf_pairs {
     int link;                     // bdf_pairs_set_link: 0 identity, 1 probit (predictions are Phi(udot + base): k_probit.hip)
     double *lpd_dev;              // bdf_pairs_lpd_update's running state (k_lpd.hip): n maxima M, then n sums A, in storage order; at first use
     double lpd_draws;             // ... and the posterior draws it holds (a counter of its own, not `count`)
+    double *waic_dev;             // bdf_pairs_waic_update's running state (k_waic.hip): four planes of n in storage order -- M, A, mean, M2; at first use
+    double waic_draws;            // ... and the posterior draws it holds (a counter of its own)
 };
 
 // bdf_ordinal (k_ordinal.hip): the edges of an ordinal relation and their Metropolis step's state, all of it in ONE device buffer

@@ -14,7 +14,7 @@ import numpy as np
 from . import features as feat
 from ._lib import ArgumentError
 from .engine import GibbsEngine
-from .relation_data import _ordinal_bounds, check_test_interval, hasFeatures, numTest, toStr
+from .relation_data import _ordinal_bounds, _waic_bounds, check_test_interval, hasFeatures, numTest, toStr
 
 
 def AUC_ROC(Ytrue, scores):
@@ -68,6 +68,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if lpd and not (data.relations and numTest(data.relations[0]) > 0):
         raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")
 
+    # WAIC on the training cells (setWaic on the first relation)
+    waic = data.relations[0].model.waic if data.relations else None
+    if waic is not None and psamples < 2:
+        raise ArgumentError("WAIC (setWaic) needs the variance of the log-likelihood over the posterior draws: psamples must be at least 2.")
+
     verbose and print("Model setup")
     eng = engine
     if eng is None or reset_model:
@@ -75,6 +80,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                           compute_ff_size=compute_ff_size, full_lambda_u=full_lambda_u, tol=tol)
     if lpd and eng.world > 1:
         raise ArgumentError("lpd = true is not possible with more than one rank: every rank scores only the test cells it predicts.")
+    if waic is not None and eng.world > 1:
+        raise ArgumentError("WAIC (setWaic) is not possible with more than one rank: every rank holds the state of its own cells only.")
     data._engine = eng
     D = eng.D
 
@@ -105,6 +112,17 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             if ordinal is not None:
                 import torch
                 lpd_codes = test.ctx.tensor(rel.model.test_ordinal, dtype=torch.int8)
+    waic_pairs = waic_bounds = waic_codes = None
+    waic_stats = np.full(4, np.nan)
+    if waic is not None:
+        # what kind of record every training row is (the table of DESIGN.md section 17), built once on the host; between sampled
+        # edges the levels' bins follow every draw (refreshed below, from the levels the sampler itself keeps on the device)
+        waic_pairs = eng.train_pairs()
+        b = _waic_bounds(rel)
+        if b is not None:
+            waic_bounds = waic_pairs.ctx.tensor(b)
+        if ordinal is not None:
+            waic_codes = rel._dev.ord_codes
     f_output = []
     yhat_full = None
     if full_prediction:
@@ -127,10 +145,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         facs = eng.factors_of(rel)
         if full_prediction and i > burnin:
             yhat_full += eng.pred_all(rel)                    # macau.jl:145-147: a plain dense product, on the device
-        if lpd:
+        if lpd or waic is not None:
             # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
             # has read the same double, and the device scalar is redrawn on another stream than the pairs')
             a = 1.0 if rel.model.probit else (rel._dev.alpha_dev if (rel.model.alpha_sample and eng.native) else rel.model.alpha)
+        if lpd:
             if lpd_codes is not None:
                 # this draw's edges were published on the row stream before this iteration's rows, which the pairs' stream is behind
                 ordinal.bounds(test.ctx, lpd_codes, lpd_bounds)
@@ -139,6 +158,12 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 # (step by step the pairs have a stream of their own: the next iteration's step may not publish its edges under this
                 # launch.  The native iteration scores on the row stream itself and needs nothing)
                 eng.ctx.stream.wait_stream(test.ctx.stream)
+        if waic is not None:
+            if waic_codes is not None:        # this draw's edges, ordered as for the test cells above
+                ordinal.bounds(waic_pairs.ctx, waic_codes, waic_bounds)
+            waic_pairs.waic_update(D, facs, rel.model.mean_value, a, phase, waic_bounds)
+            if waic_codes is not None and waic_pairs.ctx is not eng.ctx:
+                eng.ctx.stream.wait_stream(waic_pairs.ctx.stream)
         if i > burnin:
             if output:
                 ndigits = int(math.floor(math.log10(psamples))) + 1
@@ -179,10 +204,14 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 roc_avg = float(rep[4])
                 if lpd:
                     lpd_avg = float(rep[6]) / n
+            if waic is not None:
+                waic_stats = waic_pairs.waic_stats.cpu().numpy()
             if verbose:
                 estr = " ".join(toStr(en) for en in data.entities)
                 rstr = " ".join(toStr(r) for r in data.relations)
                 lstr = f" LPD={lpd_avg:.4f}" if lpd else ""
+                if waic is not None:
+                    lstr += f" ELPD={(waic_stats[1] - waic_stats[2]) / max(waic_pairs.n, 1):.4f}"
                 if ordinal is not None:
                     lstr += " cut=[" + " ".join(f"{e:.3f}" for e in rel.model.ordinal_edges) + "]"
                 print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f}{lstr} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
@@ -212,6 +241,19 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         result["ordinal"] = {"edges": e, "edges_trace": np.tile(e, (psamples, 1)), "accept": 0.0, "step": rel.model.ordinal["step"]}
     if lpd:
         result["LPD"] = lpd_avg
+    if waic is not None:
+        # lppd, p_waic and the squares of elpd_t about its mean from the device (bdf_pairs_waic): the pointwise table comes to the
+        # host only when asked for
+        st, pw = waic_pairs.waic(pointwise=waic["pointwise"])
+        n = waic_pairs.n
+        result["WAIC"] = {"waic": float(-2.0 * (st[0] - st[1])), "elpd": float(st[0] - st[1]), "lppd": float(st[0]), "p_waic": float(st[1]),
+                          "se": math.sqrt(float(st[2])), "n_high": int(st[3]), "n": n}
+        if waic["pointwise"]:
+            import pandas as pd
+            ids = np.asarray(rel.data.ids).reshape(n, len(rel.entities))
+            frame = {rel.data.names[k]: ids[:, k] for k in range(ids.shape[1])}
+            frame["lppd"], frame["p_waic"] = pw[:, 0], pw[:, 1]
+            result["WAIC"]["pointwise"] = pd.DataFrame(frame)
     if full_prediction:
         result["predictions_full"] = (yhat_full / psamples).cpu().numpy()        # macau.jl:228-230
     if rmse_train:

@@ -285,6 +285,7 @@ class DevicePairs:
         self.report = ctx.zeros(9)
         self.stats = self.report[:4]
         self.lpd_stats = self.report[5:]
+        self.waic_stats = None         # bdf_pairs_waic_update's 4, a tensor of its own at first use (waic_update)
         self._order = None
         ctx.adopt(self)
 
@@ -373,6 +374,31 @@ class DevicePairs:
             check(lib().bdf_pairs_lpd(self.ctx.handle, self.handle, _ptr(out)))
         self._hand_back(cur, out)
         return out.cpu().numpy()
+
+    def waic_update(self, D, factors, mean_value, alpha, phase, bounds=None):
+        """one scoring step of WAIC (bdf_pairs_waic_update) on the pairs' own stream: every pair's log-likelihood as lpd_update
+        forms it (with `bounds` the pairs' baseline is not read: m = udot + mean_value), folded into the running log-sum-exp and
+        Welford's mean and M2 of it.  Returns the device statistics (waic_stats): [0] the sum of this draw's log-likelihoods, [1]
+        the sum of the pairs' lppd after it, [2] the sum of their V (the variance of the log-likelihood over the draws), [3] the
+        number of pairs with V > 0.4."""
+        if self.waic_stats is None:
+            self.waic_stats = self.ctx.zeros(4)
+        on_dev = torch.is_tensor(alpha)
+        check(lib().bdf_pairs_waic_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, self._facs(factors),
+                                          mean_value, 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
+                                          _ptr(self.waic_stats)))
+        return self.waic_stats
+
+    def waic(self, pointwise=False):
+        """the end of the run (bdf_pairs_waic): the host array {sum lppd, sum V, sum (elpd - mean elpd)^2, the count of V > 0.4}
+        and, with `pointwise`, the (n, 2) host array of every pair's (lppd, V) in the caller's order (otherwise None)"""
+        cur, own = self._on_own_stream()
+        with own:
+            stats = torch.zeros(4, dtype=torch.float64, device=self.ctx.device)
+            out = torch.zeros((self.n, 2), dtype=torch.float64, device=self.ctx.device) if pointwise else None
+            check(lib().bdf_pairs_waic(self.ctx.handle, self.handle, _ptr(out) if (pointwise and self.n) else None, _ptr(stats)))
+        self._hand_back(cur, *([stats] + ([out] if pointwise else [])))
+        return stats.cpu().numpy(), (out.cpu().numpy() if pointwise else None)
 
     def state(self):
         """(avg, sq) as host arrays"""

@@ -109,6 +109,7 @@ class RelationModel:
         self.ordinal_codes = None # ... int8 per training row, its level
         self.ordinal_edges = None # ... float64 (K - 1): the edges e_1 .. e_{K-1}, k + 1/2 until macau() has drawn them (then the last draw)
         self.test_ordinal = None  # setTestOrdinal: int8 per row of test_vec, its level (macau(lpd=True))
+        self.waic = None          # setWaic: {"pointwise"}; macau() scores the training cells by WAIC
 
 
 class RelationTemp:
@@ -434,6 +435,43 @@ def check_ordinal(r):
     r.model.interval = _interval_bounds(r, b[:, 0], b[:, 1])
     if r.model.test_ordinal is not None:
         r.model.test_ordinal = _ordinal_codes(r, r.test_vec.values, K, "test")
+
+
+def setWaic(r, on=True, pointwise=False):
+    """macau() scores the TRAINING cells of this relation (the first of its RelationData) by the widely applicable information
+    criterion: result["WAIC"] = {"waic", "elpd", "lppd", "p_waic", "se", "n_high", "n"}, an estimate of the expected log predictive
+    density that needs no held-out cells.  Every training row is scored as the kind of record its noise model says it is (a
+    measurement, a 0/1 value, a censored or interval value, a level between this draw's edges).  pointwise=True also returns
+    result["WAIC"]["pointwise"], the training ids with every cell's lppd and p_waic.  on=False takes it back.  Nothing of the chain
+    changes; call it at any time before macau()."""
+    if not isinstance(on, (bool, np.bool_)) or not isinstance(pointwise, (bool, np.bool_)):
+        raise ArgumentError(f"Relation {r.name}: setWaic takes on = true / false and pointwise = true / false.")
+    if pointwise and not on:
+        raise ArgumentError(f"Relation {r.name}: setWaic(on = false) returns no pointwise table.")
+    r.model.waic = {"pointwise": bool(pointwise)} if on else None
+    return None
+
+
+def _waic_bounds(r):
+    """the bounds (lo, hi) of every training row by its kind of record, for WAIC: None for a Gaussian and for a probit relation (the
+    density at the stored value; the probit link); censoring flags 0 -> (y, y), +1 -> (y, +inf), -1 -> (-inf, y); interval bounds
+    as they stand (lo == hi a measurement); an ordinal relation's levels between the edges k + 1/2 (sampled edges: where every
+    chain starts; macau() then refreshes them with every draw).  The relation's own checks run first."""
+    m = r.model
+    if m.probit:
+        return None
+    if m.censor is not None:
+        check_censored(r)
+        y = np.asarray(r.data.values, dtype=np.float64)
+        return np.ascontiguousarray(np.stack([np.where(m.censor < 0, -np.inf, y), np.where(m.censor > 0, np.inf, y)], axis=1))
+    if m.ordinal is not None:
+        check_ordinal(r)
+        check_interval(r)
+        return _ordinal_bounds(m.ordinal_codes, np.arange(1, m.ordinal["K"]) + 0.5)
+    if m.interval is not None:
+        check_interval(r)
+        return np.ascontiguousarray(m.interval, dtype=np.float64)
+    return None
 
 
 def _bin_edges(r, edges):

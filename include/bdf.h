@@ -442,6 +442,27 @@ int bdf_pairs_lpd_update(bdf_ctx *ctx, bdf_pairs *p, const double *bounds_dev, i
  * sorted.  BDF_ERR_ARG before the first phase 1. */
 int bdf_pairs_lpd(bdf_ctx *ctx, const bdf_pairs *p, double *out_dev);
 
+/* ---- WAIC on the training cells (csrc/k_waic.hip, csrc/lpd.h) -------------------------- */
+/* One scoring step of the widely applicable information criterion on the pairs (the training table): l_k as
+ * bdf_pairs_lpd_update forms it -- the same arguments, kinds of record, refusals and phases -- with ONE difference: given
+ * bounds_dev, m = udot_k + mean_value and the pairs' baseline is not read (the training pairs of a censored, interval or ordinal
+ * relation carry the latent draw as their baseline; without bounds_dev the baseline stands for mean_value as everywhere).  The
+ * running state, four doubles per pair that the pairs own (allocated and zeroed on ctx's stream at the first phase >= 1, freed
+ * by bdf_pairs_destroy; separate from bdf_pairs_lpd_update's) and a draw counter of its own, is the streaming log-sum-exp (M, A)
+ * of bdf_pairs_lpd_update and Welford's (mean, M2) of l:
+ *   phase 0 (burn-in): no state is touched, lppd_k = l_k, V_k = 0;   phase 1: (M, A, mean, M2) = (l, 1, l, 0), draws = 1;
+ *   phase 2: draws += 1, (M, A) as bdf_pairs_lpd_update, d = l - mean, mean += d / draws, M2 += d (l - mean);
+ *   lppd_k = M + log A - log(draws), V_k = M2 / (draws - 1) (0 while draws < 2).
+ * stats_out (dev 4 doubles): sum_k l_k of this draw, sum_k lppd_k after it, sum_k V_k after it, the number of pairs with
+ * V_k > 0.4 -- summed in a fixed order (bit-identical reruns).  Enqueued on ctx's stream. */
+int bdf_pairs_waic_update(bdf_ctx *ctx, bdf_pairs *p, const double *bounds_dev, int D, const double *const *factors,
+                          double mean_value, double alpha, const double *alpha_dev, int phase, double *stats_out);
+/* The end of the run.  out_dev (dev, nullable, aligned to 16 bytes): n rows (lppd_k, V_k) in the caller's order whether or not
+ * the pairs are stored sorted.  stats_out (dev 4 doubles), from two fixed-order passes: sum_k lppd_k, sum_k V_k,
+ * sum_k (elpd_k - e)^2 with elpd_k = lppd_k - V_k and e the mean of elpd_k that the first pass gives, the number of pairs with
+ * V_k > 0.4.  (se = sqrt of [2]: n times the population variance of elpd_k.)  BDF_ERR_ARG before the first phase 1. */
+int bdf_pairs_waic(bdf_ctx *ctx, const bdf_pairs *p, double *out_dev, double *stats_out);
+
 /* ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device (csrc/k_auc.hip) ------------ */
 /* bytes of the workspace bdf_auc_roc needs for n scores (-1: n < 0) */
 int64_t bdf_auc_workspace_bytes(int64_t n);

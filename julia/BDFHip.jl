@@ -562,6 +562,22 @@ end
 pairs_lpd!(c::Context, p::DevPairs, out::DevArray{Float64}) =
     check(ccall((:bdf_pairs_lpd, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.h, p.h, out.p))
 
+"one scoring step of WAIC on the pairs (the training table): the log-likelihood l of `pairs_lpd_update!` -- the same arguments and
+phases, but with `bounds` the pairs' baseline is not read -- folded into the pairs' streaming log-sum-exp and Welford's mean and M2
+of l; stats (DevArray of 4 doubles): sum of l, sum of lppd, sum of V (the variance of l over the draws), the count of V > 0.4"
+function pairs_waic_update!(c::Context, p::DevPairs, bounds, D, factors::Vector{<:DevArray}, mean_value, alpha, alpha_dev, phase::Integer,
+                            stats::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_pairs_waic_update, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+                c.h, p.h, bounds === nothing ? C_NULL : bounds.p, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p,
+                phase, stats.p))
+end
+"the end of the run: (lppd, V) of every pair -> out (DevArray of 2 x n doubles in the caller's order, or `nothing`); stats (DevArray
+of 4 doubles): sum of lppd, sum of V, sum of (elpd - mean elpd)^2, the count of V > 0.4"
+pairs_waic!(c::Context, p::DevPairs, out, stats::DevArray{Float64}) =
+    check(ccall((:bdf_pairs_waic, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.h, p.h, out === nothing ? C_NULL : out.p, stats.p))
+
 # ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device ------------------------------------------------------------------
 "AUC_ROC(Ytrue, scores) of device arrays (labels: UInt8, nonzero = positive): (auc, C, P, Nn), C the exact pair count"
 function auc_roc(c::Context, labels::DevArray{UInt8}, scores::DevArray{Float64})
