@@ -377,6 +377,9 @@ const bdf_gibbs_relation *relation_of(const bdf_gibbs *g, const bdf_rel *rel)
     return nullptr;
 }
 
+// does the relation draw a latent z per observation into its linear buffer?  (bdf_gibbs_set_relations admits one of the three.)
+inline bool draws_latent(const bdf_gibbs_relation &r) { return r.probit || r.censor || r.interval; }
+
 // macau.jl:83-92 on the row stream, before the entities' rows
 int update_relations(bdf_gibbs *g)
 {
@@ -384,7 +387,7 @@ int update_relations(bdf_gibbs *g)
     const int D = g->D;
     int rc;
     for (const auto &r : g->rels) {
-        if (!r.alpha_sample && !r.feat && !r.probit && !r.censor && !r.interval) continue;
+        if (!r.alpha_sample && !r.feat && !draws_latent(r)) continue;
         const double *fac[BDF_MAX_MODES];
         for (int m = 0; m < r.rel->n_modes; m++) {
             const auto &O = g->ent[(size_t)r.entity_of_mode[m]];
@@ -457,7 +460,7 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
         terms[t].alpha_dev = nullptr;
         if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {
             terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
-            terms[t].linear_values = (gr->feat || gr->probit || gr->censor || gr->interval) ? gr->linear : nullptr;
+            terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
             if (gr->probit) terms[t].alpha = 1.0;
         }
         for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
@@ -529,9 +532,8 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
             pieces.push_back({r.linear, (size_t)r.obs_block * (size_t)world * sizeof(double), false, 0});
             if (r.feat_test) pieces.push_back({r.test_baseline, (size_t)r.feat_test->m * sizeof(double), false, 0});
         }
-        if (r.probit) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});     // y - z of the last draw
-        if (r.censor) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});     // mean + y - z of the last draw
-        if (r.interval) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});   // mean + y - z of the last draw
+        // the last draw: y - z (probit), mean + y - z (censored, interval)
+        if (draws_latent(r)) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});
         if (r.ordinal) {                    // the edges, the step size, the counters and the trace; the bounds made from the edges
             pieces.push_back({r.ordinal->state_dev, r.ordinal->state_doubles * sizeof(double), false, 0});
             pieces.push_back({const_cast<double *>(r.interval), (size_t)r.train->n * 2 * sizeof(double), false, 0});
@@ -709,7 +711,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             terms[t].alpha_dev = nullptr;
             if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {        // a relation with a model of its own
                 terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
-                terms[t].linear_values = (gr->feat || gr->probit || gr->censor || gr->interval) ? gr->linear : nullptr;
+                terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
                 if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
             }
             for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;

@@ -5,7 +5,7 @@
 // (Cowles 1996), in four launches on one stream and without a word to the host:
 //
 // k_ordinal_propose (one wave): the K - 3 normals of the step's stream, the proposed edge table and the log Jacobian (ordinal.h).
-// k_ordinal_mass: the gather and dot product of k_lpd (pair_gather.h) and, in the lane that owns the pair, the difference of the
+// k_ordinal_mass: the lane prologue, gather and dot product of pair_gather.h and, in the lane that owns the pair, the difference of the
 //   log masses (lpd.h, bdf_lpd_mass) of its level's interval under the proposed and the current edges; both tables (17 doubles each)
 //   sit in LDS.  A pair whose level kept both its edges -- levels 1 and K always -- contributes an exact 0 and evaluates nothing;
 //   a group of 8 lanes with no other pair gathers nothing.  Per-workgroup sums through the statistics' reduction of predict.h.
@@ -16,23 +16,16 @@
 //
 // No scratch, no LDS beyond the reduction's 128 bytes and the tables, plain vector stores.
 #include "bdf_common.h"
-#include "lpd.h"
 #include "ordinal.h"
 #include "predict.h"
 #include "pair_gather.h"
-#include <cmath>
 
 namespace {
 
 struct OrdMassArgs {
-    int D, K;
-    int64_t n;
-    const int32_t *ids;            // n_modes planes of n, 0-based
-    const double *fac[BDF_MAX_MODES];
-    const int32_t *orig;           // nullable: the pairs are stored sorted; orig[pair] = the caller's index (codes)
+    PairArgs pair;
+    int K;
     const int8_t *codes;           // the caller's order: the level 1 .. K of every pair
-    double mean, alpha;
-    const double *alpha_dev;       // nullable: wins over alpha
     const double *st;              // the object's state (BDF_ORD_*)
     double *partial;               // per-block statistics
 };
@@ -43,46 +36,38 @@ __device__ __forceinline__ int level_of(const int8_t *codes, int64_t i, int K)
     return c < 1 ? 1 : (c > K ? K : c);          // (the host refuses other codes; never an index outside the table)
 }
 
-// One group of 8 lanes per 8 pairs and no grid-stride loop, as k_lpd and for its reason.  Every lane of a launch whose proposal
+// No grid-stride loop, as k_lpd and for its reason.  Every lane of a launch whose proposal
 // stands reaches the statistics' barrier; a launch whose proposal fell to the gap guard leaves at once, all of it.
 template <int NM, int VEC, int NC>
 __global__ __launch_bounds__(256, (VEC == 4 && NM * NC >= 8) ? 2 : 3) void k_ordinal_mass(OrdMassArgs a)
 {
     __shared__ double tab[2 * BDF_ORD_TABLE];                  // the current table, then the proposed one
-    const int tid = threadIdx.x, sub = tid & 7;
+    const int tid = threadIdx.x;
     if (a.st[BDF_ORD_VALID] == 0.0) return;
     if (tid < 2 * BDF_ORD_TABLE) tab[tid] = a.st[BDF_ORD_CUR + tid];
     __syncthreads();
-    const double alpha = a.alpha_dev ? *a.alpha_dev : a.alpha;
-    const int64_t p0 = ((int64_t)blockIdx.x * 32 + tid / 8) * 8, p = p0 + sub;
+    const double alpha = pair_alpha(a.pair);
+    const int64_t trip = pair_trip();
     double st[4] = {0.0, 0.0, 0.0, 0.0};
-    if (p0 < a.n) {
-        const bool ok = p < a.n;
-        const int64_t pm = ok ? p : a.n - 1;
-        const int64_t po = a.orig ? (int64_t)a.orig[pm] : pm;
-        const int c = level_of(a.codes, po, a.K);
+    if (trip * 8 < a.pair.n) {
+        PairLane<NM> l;
+        pair_lane(a.pair, trip, l);
+        const int c = level_of(a.codes, l.po, a.K);
         const double lo0 = tab[c - 1], hi0 = tab[c], lo1 = tab[BDF_ORD_TABLE + c - 1], hi1 = tab[BDF_ORD_TABLE + c];
-        const bool moved = ok && c > 1 && c < a.K && (lo0 != lo1 || hi0 != hi1);
-        int32_t my[NM];
-#pragma unroll
-        for (int k = 0; k < NM; k++) my[k] = a.ids[(int64_t)k * a.n + pm];
-        // the group's 8 lanes are 8 neighbours of one wave, so the test is the same in all of them
-        const unsigned any = (unsigned)(__ballot(moved) >> (tid & 56)) & 0xffu;
-        if (any) {
-            const double m = group_dots<NM, VEC, NC>(a.fac, a.D, a.n, p0, sub, my) + a.mean;
+        const bool moved = l.ok && c > 1 && c < a.K && (lo0 != lo1 || hi0 != hi1);
+        if (group_any(moved)) {
+            const double m = pair_dot<NM, VEC, NC>(a.pair, l) + a.pair.mean;
             if (moved) st[0] = bdf_lpd_mass(m, lo1, hi1, alpha) - bdf_lpd_mass(m, lo0, hi0, alpha);
         }
     }
-    PredArgs red;                      // (block_stats reads nothing of it but where the workgroup's four sums go)
-    red.partial = a.partial;
-    block_stats(red, st);
+    block_stats(a.partial, st);
 }
 
 struct OrdStepArgs {
     int K, adapt;                  // adapt: 0 frozen, 1 adapt, -1: adapt while fewer than adapt_steps steps have been taken
     double *st;
     uint64_t seed;
-    uint32_t sweep, entity;        // entity = 0x800000 | rel_tag
+    uint32_t sweep, entity;        // pair_entity(rel_tag)
     int nblocks;
     const double *partial;
     int64_t adapt_steps, capacity;
@@ -215,31 +200,24 @@ extern "C" int bdf_ordinal_set_adapt(bdf_ordinal *ord, int64_t steps)
 extern "C" int bdf_ordinal_step(bdf_ctx *ctx, bdf_ordinal *ord, const bdf_pairs *train, const int8_t *codes_dev, int D, const double *const *factors,
                                 double mean_value, double alpha, const double *alpha_dev, uint32_t rel_tag, int adapt, double *bounds_dev)
 {
-    BDF_REQUIRE(ctx && ord && train && codes_dev && factors && bounds_dev, BDF_ERR_ARG, "bdf_ordinal_step: NULL argument");
+    BDF_REQUIRE(ord && codes_dev && bounds_dev, BDF_ERR_ARG, "bdf_ordinal_step: NULL argument");
     BDF_REQUIRE(((uintptr_t)bounds_dev & 15) == 0, BDF_ERR_ARG, "bdf_ordinal_step: bounds_dev must be aligned to 16 bytes");
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_ordinal_step: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
     BDF_REQUIRE(adapt >= -1 && adapt <= 1, BDF_ERR_ARG, "bdf_ordinal_step: adapt must be -1, 0 or 1");
-    BDF_REQUIRE(alpha_dev || (alpha > 0.0 && std::isfinite(alpha)), BDF_ERR_ARG, "bdf_ordinal_step: alpha=%g must be positive and finite", alpha);
-    BDF_REQUIRE(ctx->device == ord->ctx->device, BDF_ERR_ARG, "bdf_ordinal_step: the context and the object are on different devices");
-    OrdMassArgs m;
-    memset(&m, 0, sizeof(m));
-    m.D = D; m.K = ord->K; m.n = train->n; m.ids = train->ids_dev; m.orig = train->orig_dev; m.codes = codes_dev;
-    for (int k = 0; k < train->n_modes; k++) {
-        BDF_REQUIRE(factors[k] != nullptr, BDF_ERR_ARG, "bdf_ordinal_step: factors[%d] is NULL", k);
-        m.fac[k] = factors[k];
-    }
-    m.mean = mean_value; m.alpha = alpha; m.alpha_dev = alpha_dev; m.st = ord->state_dev;
-    const int64_t ntrips = (m.n + 7) / 8;
-    BDF_REQUIRE((ntrips + 31) / 32 <= INT32_MAX / 4, BDF_ERR_ARG, "bdf_ordinal_step: %lld observations are more than one launch covers", (long long)m.n);
-    const int nblocks = (int)((ntrips + 31) / 32);
-    BDF_HIP(hipSetDevice(ctx->device));
-    void *sc;
-    int rc = bdf_scratch(ctx, (size_t)std::max(nblocks, 1) * 4 * sizeof(double), &sc);
+    OrdMassArgs m = {};
+    int rc = pair_fill("bdf_ordinal_step", ctx, train, D, factors, mean_value, true, alpha, alpha_dev, m.pair);
     if (rc) return rc;
+    BDF_REQUIRE(ctx->device == ord->ctx->device, BDF_ERR_ARG, "bdf_ordinal_step: the context and the object are on different devices");
+    m.K = ord->K; m.codes = codes_dev; m.st = ord->state_dev;
+    int nblocks;
+    if ((rc = pair_blocks("bdf_ordinal_step", "observations", train->n, &nblocks, INT32_MAX / 4))) return rc;
+    BDF_HIP(hipSetDevice(ctx->device));
+    // (the sum behind the launch is k_ordinal_accept's own, with the decision: no launch_reduced here)
+    void *sc;
+    if ((rc = bdf_scratch(ctx, (size_t)std::max(nblocks, 1) * 4 * sizeof(double), &sc))) return rc;
     m.partial = (double *)sc;
     OrdStepArgs s;
     memset(&s, 0, sizeof(s));
-    s.K = ord->K; s.adapt = adapt; s.st = ord->state_dev; s.seed = ctx->seed; s.sweep = ctx->sweep_host; s.entity = 0x800000u | rel_tag;
+    s.K = ord->K; s.adapt = adapt; s.st = ord->state_dev; s.seed = ctx->seed; s.sweep = ctx->sweep_host; s.entity = pair_entity(rel_tag);
     s.nblocks = nblocks; s.partial = m.partial; s.adapt_steps = ord->adapt_steps; s.capacity = ord->capacity;
     ord->stream = ctx->stream;
     hipLaunchKernelGGL(k_ordinal_propose, dim3(1), dim3(64), 0, ctx->stream, s);

@@ -1,8 +1,8 @@
 // k_probit.hip -- the probit noise model for 0/1 relations: y = 1[z > 0], z ~ N(udot + mean_value, 1).
 //
-// bdf_probit_draw: the latent z of every training observation given the current factors -- the gather and dot product of
-// k_predict.hip and, in the lane that owns the pair, one uniform of the observation's own stream mapped to the truncated
-// normal (probit.h).  It writes linear[k] = y_k - z_k: the row kernels, which form b_i = Lambda mu_i + alpha sum w (y - base) with
+// bdf_probit_draw: the latent z of every training observation given the current factors -- the lane prologue, gather and dot
+// product of pair_gather.h and, in the lane that owns the pair, one uniform of the observation's own stream mapped to the
+// truncated normal (probit.h).  It writes linear[k] = y_k - z_k: the row kernels, which form b_i = Lambda mu_i + alpha sum w (y - base) with
 // the per-observation base = linear_values[k], then sample the rows of z's Gaussian model with alpha = 1, unchanged.
 //
 // The probit link of the prediction kernels (bdf_pairs_set_link): p = Phi(udot + base) in place of udot + base, in kernels of
@@ -18,15 +18,9 @@
 namespace {
 
 struct DrawArgs {
-    int D;
-    int64_t n;
-    const int32_t *ids;            // n_modes planes of n, 0-based
-    const double *fac[BDF_MAX_MODES];
-    const double *values;
-    const int32_t *orig;           // nullable: the pairs are stored sorted; orig[pair] = the caller's index
-    double mean;
+    PairArgs pair;                 // (no alpha: the latent's variance is 1)
     uint64_t seed;
-    uint32_t sweep, entity;        // entity = 0x800000 | rel_tag
+    uint32_t sweep, entity;        // pair_entity(rel_tag)
     double *linear, *z;            // z nullable
 };
 
@@ -36,24 +30,18 @@ struct DrawArgs {
 template <int NM, int VEC, int NC>
 __global__ __launch_bounds__(256, (VEC == 4 && NM * NC >= 8) ? 2 : 3) void k_probit_draw(DrawArgs a)
 {
-    const int tid = threadIdx.x, sub = tid & 7;
-    const int64_t ngroups = (int64_t)gridDim.x * 32, ntrips = (a.n + 7) / 8;
-    for (int64_t trip = (int64_t)blockIdx.x * 32 + tid / 8; trip < ntrips; trip += ngroups) {
-        const int64_t p0 = trip * 8, p = p0 + sub;
-        const bool ok = p < a.n;
-        const int64_t pm = ok ? p : a.n - 1;
-        const int64_t po = a.orig ? (int64_t)a.orig[pm] : pm;
-        const double y = a.values[pm];
-        int32_t my[NM];
-#pragma unroll
-        for (int k = 0; k < NM; k++) my[k] = a.ids[(int64_t)k * a.n + pm];
-        const double dot = group_dots<NM, VEC, NC>(a.fac, a.D, a.n, p0, sub, my);
-        if (!ok) continue;
+    const int64_t ngroups = (int64_t)gridDim.x * 32, ntrips = (a.pair.n + 7) / 8;
+    for (int64_t trip = pair_trip(); trip < ntrips; trip += ngroups) {
+        PairLane<NM> l;
+        pair_lane(a.pair, trip, l);
+        const double y = a.pair.values[l.pm];
+        const double dot = pair_dot<NM, VEC, NC>(a.pair, l);
+        if (!l.ok) continue;
         // the observation's own uniform: the stream is keyed by the caller's index, not by where the pair is stored
-        const double u = bdf_uniform(a.seed, a.sweep, BDF_P_PROBIT, a.entity, (uint64_t)po, 0);
-        const double z = bdf_probit_z(dot + a.mean, y, u);
-        a.linear[po] = y - z;
-        if (a.z) a.z[po] = z;
+        const double u = bdf_uniform(a.seed, a.sweep, BDF_P_PROBIT, a.entity, (uint64_t)l.po, 0);
+        const double z = bdf_probit_z(dot + a.pair.mean, y, u);
+        a.linear[l.po] = y - z;
+        if (a.z) a.z[l.po] = z;
     }
 }
 
@@ -108,21 +96,14 @@ int bdf_predict_link(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *cons
 extern "C" int bdf_probit_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value,
                                uint32_t rel_tag, double *linear_out, double *z_out)
 {
-    BDF_REQUIRE(ctx && train && factors && linear_out, BDF_ERR_ARG, "bdf_probit_draw: NULL argument");
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_probit_draw: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    DrawArgs a;
-    memset(&a, 0, sizeof(a));
-    a.D = D; a.n = train->n; a.ids = train->ids_dev; a.values = train->values_dev; a.orig = train->orig_dev;
-    for (int k = 0; k < train->n_modes; k++) {
-        BDF_REQUIRE(factors[k] != nullptr, BDF_ERR_ARG, "bdf_probit_draw: factors[%d] is NULL", k);
-        a.fac[k] = factors[k];
-    }
-    a.mean = mean_value; a.seed = ctx->seed; a.sweep = ctx->sweep_host; a.entity = 0x800000u | rel_tag;
+    BDF_REQUIRE(linear_out, BDF_ERR_ARG, "bdf_probit_draw: NULL argument");
+    DrawArgs a = {};
+    int rc = pair_fill("bdf_probit_draw", ctx, train, D, factors, mean_value, false, 0.0, nullptr, a.pair);
+    if (rc) return rc;
+    a.seed = ctx->seed; a.sweep = ctx->sweep_host; a.entity = pair_entity(rel_tag);
     a.linear = linear_out; a.z = z_out;
-    if (a.n == 0) return BDF_OK;
-    const int64_t ntrips = (a.n + 7) / 8;
-    const int nblocks = (int)std::min<int64_t>((ntrips + 31) / 32, 8192);
-    BDF_BY_SHAPE(k_probit_draw, train->n_modes, D, nblocks, ctx->stream, a);
+    if (train->n == 0) return BDF_OK;
+    BDF_BY_SHAPE(k_probit_draw, train->n_modes, D, pair_blocks_strided(train->n), ctx->stream, a);
     BDF_HIP(hipGetLastError());
     return BDF_OK;
 }

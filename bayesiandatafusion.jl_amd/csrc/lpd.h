@@ -56,3 +56,12 @@ BDF_HD_FORCE inline double bdf_lpd_mass(double m, double lo, double hi, double a
     const double d = 0.5 * (b - a) * (a + b) - log(a / b) + (bdf_log_tail_series(a) - bdf_log_tail_series(b));
     return Lb + log(-expm1(d));
 }
+
+// the log-likelihood of a record by its kind: the probit map when the pairs carry the probit link, else the interval's mass where
+// the bounds differ, else the Gaussian density at the stored value (lo == hi: a measurement)
+BDF_HD_FORCE inline double bdf_lpd_record(int link, double y, double m, double lo, double hi, double alpha)
+{
+    if (link == 1) return bdf_lpd_probit(y, m);
+    if (lo != hi) return bdf_lpd_mass(m, lo, hi, alpha);
+    return bdf_lpd_gauss(y, m, alpha);
+}

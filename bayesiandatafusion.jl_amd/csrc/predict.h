@@ -1,6 +1,7 @@
 // predict.h -- what the prediction kernels of k_predict.hip and the probit-link kernels of k_probit.hip share: the launch
 // arguments, what a lane does for the pair it owns (everything of macau.jl:142-184 that is not the gather), the
-// per-workgroup statistics and their fixed-order sum.  File-local in every unit that includes it.
+// per-workgroup statistics and their fixed-order sum, which the kernels of k_lpd.hip, k_waic.hip and k_ordinal.hip leave their
+// sums through as well.  File-local in every unit that includes it.
 #pragma once
 #include "bdf_common.h"
 #include "probit.h"
@@ -76,7 +77,8 @@ __device__ inline void pair_finish(const PredArgs &a, const PairState &s, double
     }
 }
 
-__device__ inline void block_stats(const PredArgs &a, const double (&st)[4])
+// the workgroup's four sums, in fixed order, to partial[4 * block]; every lane of the workgroup calls it
+__device__ inline void block_stats(double *partial, const double (&st)[4])
 {
     __shared__ double red[4][256 / 64];
     const int tid = threadIdx.x;
@@ -88,8 +90,10 @@ __device__ inline void block_stats(const PredArgs &a, const double (&st)[4])
         if ((tid & 63) == 0) red[q][tid >> 6] = v;
     }
     __syncthreads();
-    if (tid < 4) a.partial[blockIdx.x * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+    if (tid < 4) partial[blockIdx.x * 4 + tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
 }
+
+__device__ inline void block_stats(const PredArgs &a, const double (&st)[4]) { block_stats(a.partial, st); }
 
 // fixed-order sum of the per-block statistics
 __global__ __launch_bounds__(256) void k_predict_final(int nblocks, const double *partial, double *stats)
@@ -109,6 +113,21 @@ __global__ __launch_bounds__(256) void k_predict_final(int nblocks, const double
     }
     __syncthreads();
     if (tid < 4) stats[tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
+}
+
+// a launch of nblocks workgroups that leave their statistics through block_stats, and the fixed-order sum behind it: `partial`
+// gets the context's scratch for them before launch() runs
+template <class Launch>
+int launch_reduced(bdf_ctx *ctx, int nblocks, double *&partial, double *stats, Launch launch)
+{
+    void *sc;
+    int rc = bdf_scratch(ctx, (size_t)nblocks * 4 * sizeof(double), &sc);
+    if (rc) return rc;
+    partial = (double *)sc;
+    launch();
+    hipLaunchKernelGGL(k_predict_final, dim3(1), dim3(256), 0, ctx->stream, nblocks, (const double *)partial, stats);
+    BDF_HIP(hipGetLastError());
+    return BDF_OK;
 }
 
 int fill(const char *who, bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, PredArgs &a)

@@ -240,7 +240,7 @@ PROBIT_KERNELS = {
     "13k_probit_drawILi3ELi1ELi1EEEvNS_8DrawArgsE": (139, 0, 3),
     "13k_probit_drawILi3ELi4ELi1EEEvNS_8DrawArgsE": (168, 0, 3),
     "13k_probit_drawILi3ELi4ELi2EEEvNS_8DrawArgsE": (168, 0, 3),
-    "13k_probit_drawILi4ELi1ELi1EEEvNS_8DrawArgsE": (141, 0, 3),
+    "13k_probit_drawILi4ELi1ELi1EEEvNS_8DrawArgsE": (142, 0, 3),
     "13k_probit_drawILi4ELi4ELi1EEEvNS_8DrawArgsE": (168, 0, 3),
     "13k_probit_drawILi4ELi4ELi2EEEvNS_8DrawArgsE": (243, 0, 2),
 }

@@ -323,14 +323,14 @@ def test_macau_has_the_lpd_keyword_last(B):
 # section 15 prints them
 LPD_KERNELS = {
     "5k_lpdILi2ELi1ELi1EEEvNS_7LpdArgsE": (46, 0, 7),
-    "5k_lpdILi2ELi4ELi1EEEvNS_7LpdArgsE": (96, 0, 5),
-    "5k_lpdILi2ELi4ELi2EEEvNS_7LpdArgsE": (98, 0, 4),
-    "5k_lpdILi3ELi1ELi1EEEvNS_7LpdArgsE": (48, 0, 7),
-    "5k_lpdILi3ELi4ELi1EEEvNS_7LpdArgsE": (129, 0, 3),
-    "5k_lpdILi3ELi4ELi2EEEvNS_7LpdArgsE": (131, 0, 3),
-    "5k_lpdILi4ELi1ELi1EEEvNS_7LpdArgsE": (54, 0, 7),
-    "5k_lpdILi4ELi4ELi1EEEvNS_7LpdArgsE": (98, 0, 4),
-    "5k_lpdILi4ELi4ELi2EEEvNS_7LpdArgsE": (164, 0, 3),
+    "5k_lpdILi2ELi4ELi1EEEvNS_7LpdArgsE": (94, 0, 5),
+    "5k_lpdILi2ELi4ELi2EEEvNS_7LpdArgsE": (96, 0, 5),
+    "5k_lpdILi3ELi1ELi1EEEvNS_7LpdArgsE": (46, 0, 7),
+    "5k_lpdILi3ELi4ELi1EEEvNS_7LpdArgsE": (127, 0, 4),
+    "5k_lpdILi3ELi4ELi2EEEvNS_7LpdArgsE": (129, 0, 3),
+    "5k_lpdILi4ELi1ELi1EEEvNS_7LpdArgsE": (52, 0, 7),
+    "5k_lpdILi4ELi4ELi1EEEvNS_7LpdArgsE": (96, 0, 5),
+    "5k_lpdILi4ELi4ELi2EEEvNS_7LpdArgsE": (162, 0, 3),
 }
 
 

@@ -241,15 +241,15 @@ def test_recorded_quality_gaps_are_what_the_restatement_computes():
 # (VGPRs, scratch bytes per lane, waves per SIMD) of the nine shapes <modes, vector width, row pieces> of k_waic, as DESIGN.md
 # section 17 prints them
 WAIC_KERNELS = {
-    "6k_waicILi2ELi1ELi1EEEvNS_8WaicArgsE": (46, 0, 7),
-    "6k_waicILi2ELi4ELi1EEEvNS_8WaicArgsE": (96, 0, 5),
-    "6k_waicILi2ELi4ELi2EEEvNS_8WaicArgsE": (98, 0, 4),
-    "6k_waicILi3ELi1ELi1EEEvNS_8WaicArgsE": (48, 0, 7),
-    "6k_waicILi3ELi4ELi1EEEvNS_8WaicArgsE": (129, 0, 3),
-    "6k_waicILi3ELi4ELi2EEEvNS_8WaicArgsE": (131, 0, 3),
-    "6k_waicILi4ELi1ELi1EEEvNS_8WaicArgsE": (54, 0, 7),
-    "6k_waicILi4ELi4ELi1EEEvNS_8WaicArgsE": (98, 0, 4),
-    "6k_waicILi4ELi4ELi2EEEvNS_8WaicArgsE": (164, 0, 3),
+    "6k_waicILi2ELi1ELi1EEEvNS_8WaicArgsE": (41, 0, 7),
+    "6k_waicILi2ELi4ELi1EEEvNS_8WaicArgsE": (89, 0, 5),
+    "6k_waicILi2ELi4ELi2EEEvNS_8WaicArgsE": (91, 0, 5),
+    "6k_waicILi3ELi1ELi1EEEvNS_8WaicArgsE": (42, 0, 7),
+    "6k_waicILi3ELi4ELi1EEEvNS_8WaicArgsE": (122, 0, 4),
+    "6k_waicILi3ELi4ELi2EEEvNS_8WaicArgsE": (124, 0, 4),
+    "6k_waicILi4ELi1ELi1EEEvNS_8WaicArgsE": (46, 0, 7),
+    "6k_waicILi4ELi4ELi1EEEvNS_8WaicArgsE": (91, 0, 5),
+    "6k_waicILi4ELi4ELi2EEEvNS_8WaicArgsE": (162, 0, 3),
 }
 
 
