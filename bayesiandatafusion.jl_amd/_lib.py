@@ -20,6 +20,7 @@ P_PROBIT = 12
 P_CENSORED = 13
 P_INTERVAL = 14
 P_ORDINAL = 15
+P_ROBUST_N, P_ROBUST_U = 16, 17
 
 
 class ArgumentError(ValueError):
@@ -57,7 +58,7 @@ class Term(C.Structure):
     """bdf_term"""
     _fields_ = [("rel", C.c_void_p), ("mode", C.c_int32), ("_pad", C.c_int32), ("alpha", C.c_double),
                 ("mean_value", C.c_double), ("linear_values", C.c_void_p), ("factors", C.c_void_p * BDF_MAX_MODES),
-                ("alpha_dev", C.c_void_p)]
+                ("alpha_dev", C.c_void_p), ("obs_precision", C.c_void_p)]
 
 
 BDF_COMM_ID_BYTES = 128
@@ -87,7 +88,8 @@ class GibbsRelation(C.Structure):
                 ("nnz", C.c_int64), ("train", C.c_void_p), ("first_obs", C.c_int64), ("obs_block", C.c_int64), ("feat", C.c_void_p),
                 ("beta", C.c_void_p), ("linear", C.c_void_p), ("lambda_beta", C.c_double), ("feat_test", C.c_void_p),
                 ("test_baseline", C.c_void_p), ("probit", C.c_int32), ("_pad", C.c_int32), ("censor", C.c_void_p),
-                ("interval", C.c_void_p), ("ordinal", C.c_void_p), ("ordinal_codes", C.c_void_p)]
+                ("interval", C.c_void_p), ("ordinal", C.c_void_p), ("ordinal_codes", C.c_void_p),
+                ("robust_nu", C.c_double), ("obs_precision", C.c_void_p)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -144,6 +146,9 @@ _SIGS = {
                                     C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdf_interval_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bdf_robust_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p, C.c_double,
+                                  C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bdf_pairs_weighted_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
     "bdf_ordinal_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]),
     "bdf_ordinal_destroy": (C.c_int, [C.c_void_p]),
     "bdf_ordinal_set_adapt": (C.c_int, [C.c_void_p, C.c_int64]),

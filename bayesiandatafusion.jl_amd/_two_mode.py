@@ -25,6 +25,10 @@ def relation_of(data, num_latent, who):
         raise ArgumentError(f"{who} takes every value as a measurement; {rel.name} has censoring flags (use macau)")
     if rel.model.interval is not None:
         raise ArgumentError(f"{who} takes every value as a measurement; {rel.name} has interval bounds (use macau)")
+    if rel.model.robust is not None:
+        raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the robust noise model (use macau)")
+    if rel.model.weights is not None:
+        raise ArgumentError(f"{who} weighs every value alike; {rel.name} has observation weights (use macau)")
     return D, rel
 
 

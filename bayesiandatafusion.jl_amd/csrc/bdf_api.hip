@@ -668,10 +668,11 @@ static int fill_args(bdf_ctx *ctx, const char *who, int D, int64_t N, int n_term
         T.vals = ix.vals_dev;
         T.perm = ix.perm_dev;
         T.linear = t.linear_values;
+        T.weight = t.obs_precision;
         T.nnz = ix.own_nnz;                 // plane stride of colidx: the observations held on this device
         T.n_other = t.rel->n_modes - 1;
         int plane = 0;
-        bool lean = t.linear_values == nullptr && T.n_other <= 2, wide = false;
+        bool lean = t.linear_values == nullptr && t.obs_precision == nullptr && T.n_other <= 2, wide = false;      // (weights: the general gather, no packed values)
         for (int k = 0; k < t.rel->n_modes; k++) {
             if (k == t.mode) continue;
             BDF_REQUIRE(t.factors[k] != nullptr, BDF_ERR_ARG, "%s: terms[%d].factors[%d] is NULL", who, r, k);

@@ -354,25 +354,33 @@ __device__ __forceinline__ double bdf_uniform(uint64_t seed, uint32_t sweep, uin
     return bdf_u01(o.x, o.y);
 }
 
-// Gamma(a, 1), Marsaglia-Tsang; variate index g addresses the stream, the attempt is the pair
-__device__ __forceinline__ double bdf_gamma(uint64_t seed, uint32_t sweep, uint32_t entity, uint64_t g, double a)
+// Gamma(a, 1), Marsaglia-Tsang, on the streams of the two given purposes (normals, uniforms); variate index g addresses the
+// stream, the attempt is the pair
+__device__ __forceinline__ double bdf_gamma_on(uint32_t p_normal, uint32_t p_uniform, uint64_t seed, uint32_t sweep, uint32_t entity,
+                                               uint64_t g, double a)
 {
     double boost = 1.0;
     if (a < 1.0) {
-        boost = pow(bdf_uniform(seed, sweep, BDF_P_GAMMA_U, entity, g, 0xffffu), 1.0 / a);
+        boost = pow(bdf_uniform(seed, sweep, p_uniform, entity, g, 0xffffu), 1.0 / a);
         a += 1.0;
     }
     double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
     for (uint32_t t = 0; t < 256; t++) {
-        double x = bdf_normal(seed, sweep, BDF_P_GAMMA_N, entity, g, (int)(2 * t));
+        double x = bdf_normal(seed, sweep, p_normal, entity, g, (int)(2 * t));
         double v = 1.0 + c * x;
         if (v <= 0.0) continue;
         v = v * v * v;
-        double u = bdf_uniform(seed, sweep, BDF_P_GAMMA_U, entity, g, t);
+        double u = bdf_uniform(seed, sweep, p_uniform, entity, g, t);
         if (u < 1.0 - 0.0331 * (x * x) * (x * x)) return boost * d * v;
         if (log(u) < 0.5 * x * x + d * (1.0 - v + log(v))) return boost * d * v;
     }
     return boost * d;
+}
+
+// ... on the hyperprior's and sample_alpha's streams (BDF_P_GAMMA_N / BDF_P_GAMMA_U)
+__device__ __forceinline__ double bdf_gamma(uint64_t seed, uint32_t sweep, uint32_t entity, uint64_t g, double a)
+{
+    return bdf_gamma_on(BDF_P_GAMMA_N, BDF_P_GAMMA_U, seed, sweep, entity, g, a);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -15,6 +15,7 @@
 #include "bdf_common.h"
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -359,6 +360,12 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
         BDF_REQUIRE(!r.interval || (!r.probit && !r.censor && !r.feat), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model takes neither the probit model, censoring flags nor relation features", k);
         BDF_REQUIRE(!r.interval || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model needs its observations as pairs (train) and a linear buffer", k);
         BDF_REQUIRE(!r.ordinal || (r.interval && r.ordinal_codes && !g->comm), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the ordinal model needs the interval model's bounds and the observations' levels, on one rank", k);
+        BDF_REQUIRE(r.robust_nu == 0.0 || (r.robust_nu >= 1.0 && std::isfinite(r.robust_nu)), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: robust_nu=%g must be 0 (off) or at least 1 and finite", k, r.robust_nu);
+        BDF_REQUIRE(!(r.robust_nu > 0.0) || (r.train && r.obs_precision), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the robust model needs its observations as pairs (train) and an obs_precision buffer", k);
+        BDF_REQUIRE(!r.obs_precision || (!r.probit && !r.censor && !r.interval && !r.ordinal && !r.feat), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: observation weights take neither the probit, censored, interval or ordinal model nor relation features", k);
+        BDF_REQUIRE(!r.obs_precision || !g->comm, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: observation weights need one rank", k);
         for (int m = 0; m < r.rel->n_modes; m++)
             BDF_REQUIRE(r.entity_of_mode[m] >= 0 && r.entity_of_mode[m] < (int)g->ent.size(), BDF_ERR_ARG,
                         "bdf_gibbs_set_relations: relation %d mode %d names entity %d", k, m, r.entity_of_mode[m]);
@@ -387,15 +394,23 @@ int update_relations(bdf_gibbs *g)
     const int D = g->D;
     int rc;
     for (const auto &r : g->rels) {
-        if (!r.alpha_sample && !r.feat && !draws_latent(r)) continue;
+        if (!r.alpha_sample && !r.feat && !draws_latent(r) && !(r.robust_nu > 0.0)) continue;
         const double *fac[BDF_MAX_MODES];
         for (int m = 0; m < r.rel->n_modes; m++) {
             const auto &O = g->ent[(size_t)r.entity_of_mode[m]];
             fac[m] = O.d.sample[O.cur];
         }
+        // robust: omega of every observation given the rows and the PREVIOUS iteration's alpha, before sample_alpha -- which then takes
+        // sum omega e^2 in place of the sum of squares (alpha's exact conditional); the rows then read obs_precision
+        if (r.robust_nu > 0.0 && (rc = bdf_robust_draw(R, r.train, D, fac, r.mean_value, 0.0, r.alpha_dev, r.robust_nu, r.rel_tag, r.obs_precision,
+                                                      r.alpha_sample ? g->rel_sse + 1 : nullptr)))
+            return rc;
         if (r.alpha_sample) {
-            // err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks
-            if ((rc = bdf_predict_sse(R, r.train, D, fac, r.mean_value, nullptr, g->rel_sse))) return rc;
+            // err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known weights:
+            // sum w e^2 (the robust draw above has left its own)
+            if (r.obs_precision) rc = r.robust_nu > 0.0 ? BDF_OK : bdf_pairs_weighted_sse(R, r.train, D, fac, r.mean_value, r.obs_precision, g->rel_sse + 1);
+            else rc = bdf_predict_sse(R, r.train, D, fac, r.mean_value, nullptr, g->rel_sse);
+            if (rc) return rc;
             if (g->comm && (rc = bdf_sum_ranks(R, g->comm, g->rel_sse + 1, 1))) return rc;
             if ((rc = bdf_sample_alpha(R, r.alpha_lambda0, r.alpha_nu0, r.nnz, g->rel_sse + 1, r.rel_tag, r.alpha_dev))) return rc;
         }
@@ -457,11 +472,12 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
     for (int t = 0; t < e.n_terms; t++) {
         terms[t].rel = e.terms[t].rel; terms[t].mode = e.terms[t].mode; terms[t]._pad = 0;
         terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
-        terms[t].alpha_dev = nullptr;
+        terms[t].alpha_dev = nullptr; terms[t].obs_precision = nullptr;
         if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {
             terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
             terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
             if (gr->probit) terms[t].alpha = 1.0;
+            terms[t].obs_precision = gr->obs_precision;
         }
         for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
         for (int k = 0; k < e.terms[t].rel->n_modes; k++) {
@@ -534,6 +550,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         }
         // the last draw: y - z (probit), mean + y - z (censored, interval)
         if (draws_latent(r)) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});
+        if (r.robust_nu > 0.0) pieces.push_back({r.obs_precision, (size_t)r.train->n * sizeof(double), false, 0});       // the last omega
         if (r.ordinal) {                    // the edges, the step size, the counters and the trace; the bounds made from the edges
             pieces.push_back({r.ordinal->state_dev, r.ordinal->state_doubles * sizeof(double), false, 0});
             pieces.push_back({const_cast<double *>(r.interval), (size_t)r.train->n * 2 * sizeof(double), false, 0});
@@ -708,11 +725,12 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         for (int t = 0; t < e.n_terms; t++) {
             terms[t].rel = e.terms[t].rel; terms[t].mode = e.terms[t].mode; terms[t]._pad = 0;
             terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
-            terms[t].alpha_dev = nullptr;
+            terms[t].alpha_dev = nullptr; terms[t].obs_precision = nullptr;
             if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {        // a relation with a model of its own
                 terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
                 terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
                 if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
+                terms[t].obs_precision = gr->obs_precision;      // known weights, or the omega of the robust draw
             }
             for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
             for (int k = 0; k < e.terms[t].rel->n_modes; k++) {

@@ -80,7 +80,11 @@ struct K1Local { static constexpr bool value = DP == 64; };      // D > 32: 8.6 
 // Software pipeline over "trips" of 4*KS observations: the other-mode ids and values of trip t+2 and the gathered
 // factor rows of trip t+1 are in flight while the MFMAs of trip t issue.  Lane (j = l & 15, h = l >> 4) handles
 // observations h, h+4, h+8, ... of the item and elements 16 I + j of their factor rows (index-reversed).
-template <int DP, int NO>
+// WEIGHTED (k_rows_w): observation k carries a precision weight omega_k = T.weight[T.perm[q]] (the caller's order, as `linear`); its
+// Hadamard product and its residual are each multiplied by s = sqrt(omega_k) once, so that the same MFMAs accumulate
+// sum omega w w' and the same fma sum omega (y - base) w.  A term without weights has s = 1: every product is then exact and
+// the sums are those of the unweighted path, bit for bit.
+template <int DP, int NO, bool WEIGHTED = false>
 __device__ __forceinline__ void accumulate_reg(const SampleArgs &a, const Item &it, int lane, d4 (&acc)[Geo<DP>::NB],
                                   double (&bred)[Geo<DP>::DB])
 {
@@ -101,9 +105,10 @@ __device__ __forceinline__ void accumulate_reg(const SampleArgs &a, const Item &
 
     int32_t ix_n[KS][NO], ix_nn[KS][NO];
     double rr_n[KS], rr_nn[KS];
+    double s_n[WEIGHTED ? KS : 1], s_nn[WEIGHTED ? KS : 1];      // sqrt(omega) beside the residual (0 in an invalid lane)
     double w_n[KS][NO][DB];
 
-#define LOAD_IDX(t, IX, RR)                                                                     \
+#define LOAD_IDX(t, IX, RR, SS)                                                                  \
     _Pragma("unroll") for (int k = 0; k < KS; k++) {                                            \
         const int o = (t) * 4 * KS + 4 * k + h;                                                 \
         const bool valid = o < n;                                                               \
@@ -111,6 +116,7 @@ __device__ __forceinline__ void accumulate_reg(const SampleArgs &a, const Item &
         _Pragma("unroll") for (int m = 0; m < NO; m++) IX[k][m] = T.colidx[(int64_t)m * T.nnz + q]; \
         const double base = T.linear ? T.linear[T.perm[q]] : T.mean;                            \
         RR[k] = valid ? T.vals[q] - base : 0.0;                                                 \
+        if constexpr (WEIGHTED) SS[k] = valid ? (T.weight ? sqrt(T.weight[T.perm[q]]) : 1.0) : 0.0; \
     }
 #define LOAD_DATA(t, IX)                                                                        \
     _Pragma("unroll") for (int k = 0; k < KS; k++) {                                            \
@@ -123,8 +129,8 @@ __device__ __forceinline__ void accumulate_reg(const SampleArgs &a, const Item &
     }
 
     if (ntrips > 0) {
-        LOAD_IDX(0, ix_n, rr_n)
-        if (ntrips > 1) { LOAD_IDX(1, ix_nn, rr_nn) }
+        LOAD_IDX(0, ix_n, rr_n, s_n)
+        if (ntrips > 1) { LOAD_IDX(1, ix_nn, rr_nn, s_nn) }
         LOAD_DATA(0, ix_n)
     }
     for (int t = 0; t < ntrips; t++) {
@@ -137,17 +143,20 @@ __device__ __forceinline__ void accumulate_reg(const SampleArgs &a, const Item &
                 double v = w_n[k][0][I];
 #pragma unroll
                 for (int m = 1; m < NO; m++) v *= w_n[k][m][I];      // Hadamard product (sampling.jl:225-227, 277-280)
+                if constexpr (WEIGHTED) v *= s_n[k];
                 w_c[k][I] = v;
             }
+            if constexpr (WEIGHTED) rr_c[k] *= s_n[k];
         }
 #pragma unroll
         for (int k = 0; k < KS; k++) {
             rr_n[k] = rr_nn[k];
+            if constexpr (WEIGHTED) s_n[k] = s_nn[k];
 #pragma unroll
             for (int m = 0; m < NO; m++) ix_n[k][m] = ix_nn[k][m];
         }
         if (t + 1 < ntrips) { LOAD_DATA(t + 1, ix_n) }
-        if (t + 2 < ntrips) { LOAD_IDX(t + 2, ix_nn, rr_nn) }
+        if (t + 2 < ntrips) { LOAD_IDX(t + 2, ix_nn, rr_nn, s_nn) }
 #pragma unroll
         for (int k = 0; k < KS; k++) {
             int b = 0;
@@ -320,10 +329,19 @@ __device__ __forceinline__ void accumulate_lean(const SampleArgs &a, const Item 
 // path and other-mode count are wave-uniform.  MATRIX: the kernel variant for launches whose terms are all two-mode
 // relations on the lean path -- without the tensor and general gathers the D <= 32 kernel needs 78 registers instead of
 // 92 (6 resident waves per SIMD instead of 5, and room beside 5 of them for a wave of the prediction update)
-template <int DP, bool MATRIX, bool CODED = false>
+// WEIGHTED (k_rows_w alone): every term takes the general gather in its weighted form.
+template <int DP, bool MATRIX, bool CODED = false, bool WEIGHTED = false>
 __device__ __forceinline__ void accumulate_any(const SampleArgs &a, const Item &it, int lane, d4 (&acc)[Geo<DP>::NB],
                                       double (&bred)[Geo<DP>::DB], const double *tab = nullptr)
 {
+    if constexpr (WEIGHTED) {
+        static_assert(!MATRIX && !CODED, "weighted rows: the general gather");
+        const int now = a.t[it.term].n_other;
+        if (now == 1) accumulate_reg<DP, 1, true>(a, it, lane, acc, bred);
+        else if (now == 2) accumulate_reg<DP, 2, true>(a, it, lane, acc, bred);
+        else accumulate_reg<DP, 3, true>(a, it, lane, acc, bred);
+        return;
+    }
     if constexpr (CODED) {                   // one two-mode relation, lean gather, coded values (checked by the host)
         if (a.D == DP) accumulate_lean<DP, 1, true, false, true>(a, it, lane, acc, bred, tab);
         else accumulate_lean<DP, 1, false, false, true>(a, it, lane, acc, bred, tab);
@@ -445,7 +463,7 @@ __device__ __forceinline__ void sum_partials(const PlanDev &p, const SplitRow &s
 // completes a row finishes that row (agent-scope release / acquire around a per-row arrival counter, placement
 // independent: cdna_hip_programming.md Guideline 16).  The remaining waves take one direct row each. -----------------------
 // One work item (index wi in [split items | direct items]) on one wave.
-template <int DP, bool DUMP, bool MATRIX, bool CODED = false>
+template <int DP, bool DUMP, bool MATRIX, bool CODED = false, bool WEIGHTED = false>
 __device__ __forceinline__ void process_item(const SampleArgs &a, const PlanDev &p, const int64_t wid, const int lane, double *tri)
 {
     double *const tab = tri;          // CODED: the wave's value table (BDF_K1_CODES doubles) sits in the packed factor's space until the factorisation
@@ -474,7 +492,7 @@ __device__ __forceinline__ void process_item(const SampleArgs &a, const PlanDev 
     double z = 0.0;
     const bool early_z = !DUMP && !is_split;
     if (early_z && lane < D) z = bdf_normal(a.seed, a.sweep, BDF_P_ROW, a.entity_tag, (uint64_t)(uint32_t)it.orig, D - 1 - lane);
-    if (it.count > 0) accumulate_any<DP, MATRIX, CODED>(a, it, lane, acc, bv, tab);
+    if (it.count > 0) accumulate_any<DP, MATRIX, CODED, WEIGHTED>(a, it, lane, acc, bv, tab);
     else {
 #pragma unroll
         for (int b = 0; b < NB; b++) acc[b] = d4{0.0, 0.0, 0.0, 0.0};
@@ -633,6 +651,27 @@ void k_rows(SampleArgs a, PlanDev p)
         process_item<DP, DUMP, MATRIX, CODED>(a, p, p.order[w], lane, lds + wave * WLDS);
 }
 
+// The launch of a call with per-observation precision weights (TermDev::weight: known weights, or the omega of the Student-t
+// model -- k_robust.hip): the general variant's workgroup shape and finish around the weighted gather.
+// (Waves per SIMD: the weights' square roots and their run-ahead copies sit beside the gather's registers -- under the general
+// variant's bounds of 8 and 5 waves the compiler spills; 6 and 4 hold it free of scratch.)
+template <int DP>
+struct K1WavesW { static constexpr int value = DP == 64 ? 2 : (DP == 32 ? 4 : 6); };
+
+template <int DP, bool DUMP>
+__global__ __launch_bounds__(64 * Geo<DP>::WPB, K1WavesW<DP>::value)
+void k_rows_w(SampleArgs a, PlanDev p)
+{
+    using GG = Geo<DP>;
+    constexpr int WPB = GG::WPB;
+    constexpr int WLDS = K1Local<DP>::value ? GeoL<DP>::WAVE_LDS : GG::WAVE_LDS;
+    __shared__ __attribute__((aligned(16))) double lds[WPB * WLDS];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int64_t w = (int64_t)blockIdx.x * WPB + wave;
+    if (w < (int64_t)p.n_split + p.n_direct)
+        process_item<DP, DUMP, false, false, true>(a, p, p.order[w], lane, lds + wave * WLDS);
+}
+
 // Lambda mu_i for MANY rows (per-row prior means: an entity with side information, macau.jl:104) -- one thread per output element with
 // its row of Lambda in registers and the rows' means broadcast from LDS, where k_prior spends eight lanes and a butterfly on every
 // element (100,000 rows at D = 32: 214 us -> ~20).  The same sums in the same order: the eight chains i = p, p + 8, ... by fma, then
@@ -667,12 +706,14 @@ __global__ __launch_bounds__(256) void k_prior_rows(int D, int64_t nrows, const 
 
 // which k_rows variant a launch takes: every term a two-mode relation on the lean gather path (matrix), and of those the
 // launches with ONE relation whose values are coded (ratings)
-void launch_kind(const SampleArgs &a, bool dump, bool &matrix, bool &coded, bool wide_ok = false)
+void launch_kind(const SampleArgs &a, bool dump, bool &matrix, bool &coded, bool &weighted, bool wide_ok = false)
 {
+    weighted = false;          // any term with per-observation weights: the whole launch takes k_rows_w
+    for (int r = 0; r < a.n_terms; r++) weighted = weighted || a.t[r].weight != nullptr;
     matrix = true;             // (wide_ok: D > 32, where the two-mode variant also takes factor matrices of 4 GiB or more -- lean == 2)
     for (int r = 0; r < a.n_terms; r++) matrix = matrix && (a.t[r].lean == 1 || (wide_ok && a.t[r].lean == 2)) && a.t[r].n_other == 1;
     static const bool no_matrix = getenv("BDF_K1_GENERAL_KERNEL") != nullptr;      // test hook: the general variant
-    matrix = matrix && !no_matrix;
+    matrix = matrix && !no_matrix && !weighted;
     static const bool no_coded = getenv("BDF_K1_NO_CODED") != nullptr;               // test hook: the uncoded two-mode variant
     coded = matrix && !dump && !no_coded && a.n_terms == 1 && a.t[0].lean == 1 && a.t[0].packed != nullptr && a.t[0].n_codes <= BDF_K1_CODES;
 }
@@ -681,12 +722,13 @@ template <int DP>
 int launch(bdf_ctx *ctx, const SampleArgs &a, const PlanDev &p, bool dump, hipEvent_t e0, hipEvent_t e1)
 {
     constexpr int WPB = Geo<DP>::WPB;
-    bool matrix, coded;
-    launch_kind(a, dump, matrix, coded, DP == 64);
+    bool matrix, coded, weighted;
+    launch_kind(a, dump, matrix, coded, weighted, DP == 64);
     const int64_t waves = (int64_t)p.n_split + p.n_direct;
     const dim3 grid((unsigned)((waves + WPB - 1) / WPB)), block(64 * WPB);
     auto kern = dump ? (matrix ? k_rows<DP, true, true> : k_rows<DP, true, false>)
                      : (coded ? k_rows<DP, false, true, true> : (matrix ? k_rows<DP, false, true> : k_rows<DP, false, false>));
+    if (weighted) kern = dump ? k_rows_w<DP, true> : k_rows_w<DP, false>;
     // start / stop events (bdf_ctx_time_next_rows) ride on the dispatch packet itself: the kernel's own begin and end,
     // no marker packets around it
     hipExtLaunchKernelGGL(kern, grid, block, 0, ctx->stream, e0, e1, 0, a, p);

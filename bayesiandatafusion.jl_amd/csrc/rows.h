@@ -25,12 +25,13 @@ struct TermDev {
     const double *table;       // the code -> value table (256 doubles)
     int32_t n_codes, _padc;
     const double *alpha_dev;   // nullable: the relation's precision in device memory (sampled on the device: sample_alpha inside bdf_gibbs_sweep); else `alpha`
+    const double *weight;      // nullable: a precision weight per observation in the caller's COO order (bdf_term.obs_precision): the launch takes k_rows_w
 };
 
 __device__ __forceinline__ double term_alpha(const TermDev &T) { return T.alpha_dev ? *T.alpha_dev : T.alpha; }
 
 struct SampleArgs {
-    TermDev t[BDF_MAX_TERMS];
+    TermDev t[BDF_MAX_TERMS];  // (136 bytes each; with PlanDev the kernels' arguments stay far below the 4 KB a dispatch carries)
     int32_t n_terms, D;
     const double *mu;
     int32_t mu_is_matrix, _pad;

@@ -228,13 +228,13 @@ void route_key(const bdf_ctx *ctx, const SampleArgs &a, const bdf_rel *const *re
     // second launch costs more than it saves)
     const int64_t n_rows_all = rels[0]->sharded ? (int64_t)rels[0]->idx[modes[0]].own_orig.size() : (int64_t)rels[0]->idx[modes[0]].order.size();
     if (DP == 16 && !dump && ctx->small_max > 0 && a.n_terms == 1 && a.t[0].lean == 1 && a.t[0].n_other == 1 && a.t[0].linear == nullptr &&
-        n_rows_all >= ctx->small_min_rows)
+        a.t[0].weight == nullptr && n_rows_all >= ctx->small_min_rows)
         key.small = std::min(ctx->small_max, ctx->item_size);
 
     // D > 16, one two-mode relation without per-observation baselines (shared or per-row prior means): the rows of few observations
     // by the low-rank sampler (k_rows_lr.hip; bdf_ctx_set_lowrank, environment BDF_LOWRANK:
     // the longest such row, -1 = min(16, D / 2), 0 = off) -- when there are enough of them (decided when the plan is built)
-    if (DP > 16 && !dump && ctx->lr_max != 0 && a.n_terms == 1 && a.t[0].n_other == 1 && a.t[0].linear == nullptr) {
+    if (DP > 16 && !dump && ctx->lr_max != 0 && a.n_terms == 1 && a.t[0].n_other == 1 && a.t[0].linear == nullptr && a.t[0].weight == nullptr) {
         const int other = 1 - modes[0];
         M_other = rels[0]->nint[other];
         const int lr_want = ctx->lr_max < 0 ? a.D / 2 : ctx->lr_max;
@@ -248,7 +248,7 @@ void route_key(const bdf_ctx *ctx, const SampleArgs &a, const bdf_rel *const *re
     // the column layout (K1c, k_rows_col.hip; bdf_ctx_set_col_rows) -- unless the caller chose K1's item size or its general variant
     static const bool no_col = getenv("BDF_K1_GENERAL_KERNEL") != nullptr;          // (test hook: k_rows' general variant)
     if (DP == 32 && a.D > 16 && !dump && ctx->col_piece > 0 && (ctx->col_explicit || ctx->item_auto) && a.n_terms == 1 && a.t[0].n_other == 1 &&
-        a.t[0].lean == 1 && a.t[0].linear == nullptr && !no_col) {
+        a.t[0].lean == 1 && a.t[0].linear == nullptr && a.t[0].weight == nullptr && !no_col) {
         key.col = ctx->col_piece;
         if (!ctx->col_explicit) {
             // A row of more than 4 T observations SPANS waves: every part writes its 6.4 KB of sums through to the slab and the part

@@ -65,6 +65,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if rmse_train and data.relations and data.relations[0].model.interval is not None:
         raise ArgumentError("rmse_train is not possible when Relation has interval bounds: its training values stand for intervals, not measurements.")
 
+    # the robust noise model and observation weights (setRobust / setWeights)
+    robust = data.relations[0].model.robust if data.relations else None
+    if lpd and data.relations and (robust is not None or data.relations[0].model.weights is not None):
+        what = "the robust noise model (setRobust)" if robust is not None else "observation weights (setWeights)"
+        raise ArgumentError(f"lpd = true is not possible when Relation has {what}: a held-out cell's density under it is not scored yet.")
     if lpd and not (data.relations and numTest(data.relations[0]) > 0):
         raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")
 
@@ -83,6 +88,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if waic is not None and eng.world > 1:
         raise ArgumentError("WAIC (setWaic) is not possible with more than one rank: every rank holds the state of its own cells only.")
     data._engine = eng
+    if robust is not None:
+        eng.rel[0].omega_sum = None                          # (an engine that is reused starts the posterior mean of omega again)
     D = eng.D
 
     latent_multi_threading = (len(latent_pids) >= 1 and len(data.relations) == 1 and not hasFeatures(data.relations[0]))
@@ -145,6 +152,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         facs = eng.factors_of(rel)
         if full_prediction and i > burnin:
             yhat_full += eng.pred_all(rel)                    # macau.jl:145-147: a plain dense product, on the device
+        if robust is not None and i > burnin:
+            eng.robust_accumulate()                           # this iteration's omega into its running sum, on the row stream
         if lpd or waic is not None:
             # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
             # has read the same double, and the device scalar is redrawn on another stream than the pairs')
@@ -193,6 +202,7 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 # roc_avg = AUC_ROC(test_label, -probe_avg) (macau.jl:200) on the device, behind this iteration's prediction update
                 # on the same stream; it lands beside the 4 stats (test.report), read back together after the one sync
                 test.auc(rel.class_cut, eng.ctx_p)
+            wbar = eng.robust_mean() if (verbose and robust is not None) else None
             eng.sync()
             eng.sync_host_scalars()
             if haveTest:
@@ -212,6 +222,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 lstr = f" LPD={lpd_avg:.4f}" if lpd else ""
                 if waic is not None:
                     lstr += f" ELPD={(waic_stats[1] - waic_stats[2]) / max(waic_pairs.n, 1):.4f}"
+                if wbar is not None:
+                    lstr += f" w̄={float(wbar.item()):.3f}"
                 if ordinal is not None:
                     lstr += " cut=[" + " ".join(f"{e:.3f}" for e in rel.model.ordinal_edges) + "]"
                 print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f}{lstr} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
@@ -239,6 +251,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     elif rel.model.ordinal is not None:                 # sample_edges = false: the edges are where they started
         e = np.arange(1, rel.model.ordinal["K"]) + 0.5
         result["ordinal"] = {"edges": e, "edges_trace": np.tile(e, (psamples, 1)), "accept": 0.0, "step": rel.model.ordinal["step"]}
+    if robust is not None:
+        # the posterior mean of every training row's omega, in the caller's order: the cells with a small one are the outliers
+        ws = rel._dev.omega_sum
+        result["robust"] = {"nu": robust["nu"],
+                            "weights": (ws.cpu().numpy()[:rel.data.nnz()] / psamples) if (ws is not None and psamples) else np.full(rel.data.nnz(), np.nan)}
     if lpd:
         result["LPD"] = lpd_avg
     if waic is not None:

@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from . import features as feat
 from ._lib import ArgumentError, GibbsEntity, Term, check, lib
-from .relation_data import check_censored, check_interval, check_ordinal, check_probit
+from .relation_data import check_censored, check_interval, check_ordinal, check_probit, check_robust
 
 
 def _ptr(t):
@@ -717,6 +717,10 @@ class GibbsEngine:
                 check_interval(r)
                 if shard is not None and shard[1] > 1:
                     raise ArgumentError(f"Relation {r.name} has interval bounds: one rank only")
+            if r.model.robust is not None or r.model.weights is not None:
+                check_robust(r)
+                if shard is not None and shard[1] > 1:
+                    raise ArgumentError(f"Relation {r.name} has {'the robust noise model' if r.model.robust is not None else 'observation weights'}: one rank only")
         self.data, self.D = data, int(num_latent)
         # The row context runs on a stream of its own that leaves a few CUs (one or two per XCD) free for the hyperprior's
         # small kernels, which otherwise wait for slots beside the chip-filling row kernel -- when the entities are small
@@ -779,6 +783,8 @@ class GibbsEngine:
             self.rel.append(dr)
             # relation-level side information (RelationData.jl:348-353): FF path only, as in the reference
             dr.F = dr.beta = dr.linear = dr.train = dr.censor = dr.interval = dr.ordinal = dr.ord_codes = None
+            dr.omega = dr.wsse = dr.omega_sum = None
+            dr.robust_nu = 0.0
             # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
             # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
             # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
@@ -837,6 +843,18 @@ class GibbsEngine:
                 # sampled edges the relation IS the interval relation above.  (ordinal_begin gives the object its trace and burn-in)
                 dr.ord_codes = self.ctx.tensor(r.model.ordinal_codes if nn else np.zeros(1, dtype=np.int8), dtype=torch.int8)
                 dr.ordinal = DeviceOrdinal(self.ctx, r.model.ordinal["K"], r.model.ordinal["step"], 0)
+            if r.model.robust is not None or r.model.weights is not None:
+                # a precision weight per training row, which the row kernels read beside the relation's alpha (bdf_term.obs_precision):
+                # the caller's weights, or the omega of the Student-t model -- drawn before alpha and the rows of every iteration
+                # (bdf_robust_draw), which also leaves sum omega e^2 for sample_alpha.  The training pairs stay in the caller's order
+                # in every per-observation array, whichever way they are stored
+                dr.omega = self.ctx.tensor(r.model.weights if (r.model.weights is not None and nn) else np.ones(max(nn, 1)))
+                dr.wsse = self.ctx.zeros(1)
+                dr.robust_nu = float(r.model.robust["nu"]) if r.model.robust is not None else 0.0
+                if dr.train is None:
+                    dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
+                if len(r.entities) == 2 and nn:
+                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
             dr.alpha_dev = self.ctx.tensor([float(r.model.alpha)])
         self._test_pairs = None
         self._train_pairs = None
@@ -910,7 +928,7 @@ class GibbsEngine:
         from ._lib import GibbsRelation
         rows = [(ri, r, self.rel[ri]) for ri, r in enumerate(self.data.relations)
                 if r.model.alpha_sample or self.rel[ri].F is not None or r.model.probit or r.model.censor is not None
-                or r.model.interval is not None]
+                or r.model.interval is not None or self.rel[ri].omega is not None]
         arr = (GibbsRelation * max(len(rows), 1))()
         for k, (ri, r, dr) in enumerate(rows):
             g = arr[k]
@@ -931,12 +949,28 @@ class GibbsEngine:
                 g.interval, g.linear = dr.interval.data_ptr(), dr.linear.data_ptr()
             if dr.ordinal is not None:
                 g.ordinal, g.ordinal_codes = dr.ordinal.handle, dr.ord_codes.data_ptr()
+            if dr.omega is not None:
+                g.robust_nu, g.obs_precision = dr.robust_nu, dr.omega.data_ptr()
             if dr.F is not None:
                 g.feat, g.beta, g.linear, g.lambda_beta = dr.F.handle, dr.beta.data_ptr(), dr.linear.data_ptr(), r.model.lambda_beta
                 if ri == 0 and getattr(dr, "F_test", None) is not None:
                     g.feat_test, g.test_baseline = dr.F_test.handle, dr.test_baseline.data_ptr()
         self._gibbs_relations = arr            # (the library copies the records; the tensors they point at live in self.rel)
         check(lib().bdf_gibbs_set_relations(self.gibbs, len(rows), C.cast(arr, C.c_void_p)))
+
+    def robust_accumulate(self, ri=0):
+        """(robust relation ri, after the burn-in) this iteration's omega into the running sum, on the row stream: behind the draw
+        that wrote it and ahead of the next one"""
+        dr = self.rel[ri]
+        with torch.cuda.stream(self.ctx.stream):
+            if dr.omega_sum is None:
+                dr.omega_sum = torch.zeros_like(dr.omega)
+            dr.omega_sum += dr.omega
+
+    def robust_mean(self, ri=0):
+        """-> a device scalar, the mean of this iteration's omega (the verbose line reads it with the other scalars)"""
+        with torch.cuda.stream(self.ctx.stream):
+            return self.rel[ri].omega.mean()
 
     def ordinal_begin(self, burnin, psamples, ri=0):
         """a run of burnin + psamples iterations starts on ordinal relation ri (sampled edges): its object gets a trace of that many
@@ -1011,7 +1045,7 @@ class GibbsEngine:
             return 0
         r = en.relations[0]
         ri = [x is r for x in self.data.relations].index(True)
-        if self.rel[ri].F is not None:
+        if self.rel[ri].F is not None or self.rel[ri].omega is not None:
             return 0
         m = [e is en for e in r.entities].index(True)
         deg = np.bincount(np.asarray(r.data.ids[:, m], dtype=np.int64) - 1, minlength=en.count)
@@ -1034,6 +1068,7 @@ class GibbsEngine:
             terms[t].mean_value = r.model.mean_value
             terms[t].linear_values = self.rel[ri].linear.data_ptr() if self.rel[ri].linear is not None else None
             terms[t].alpha_dev = self.rel[ri].alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
+            terms[t].obs_precision = self.rel[ri].omega.data_ptr() if self.rel[ri].omega is not None else None
             for k, e2 in enumerate(r.entities):
                 terms[t].factors[k] = self.ent[self._entity_index(e2)].sample.data_ptr()
         return terms
@@ -1045,9 +1080,26 @@ class GibbsEngine:
         kernel's arguments: sampling it costs one device-to-host read per sweep, as the reference's host loop does)"""
         for ri, r in enumerate(self.data.relations):
             dr = self.rel[ri]
-            if not (r.model.alpha_sample or dr.F is not None or r.model.probit or dr.censor is not None or dr.interval is not None):
+            if not (r.model.alpha_sample or dr.F is not None or r.model.probit or dr.censor is not None or dr.interval is not None
+                    or dr.robust_nu > 0.0):
                 continue
             facs = self.factors_of(r)
+            if dr.omega is not None:
+                # omega | U, V, alpha (the previous iteration's) -> alpha | U, V, omega from sum omega e^2; known weights: no draw,
+                # sum w e^2.  The rows of this iteration then read omega beside alpha
+                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
+                wsse = _ptr(dr.wsse) if r.model.alpha_sample else None
+                if dr.robust_nu > 0.0:
+                    check(lib().bdf_robust_draw(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, r.model.alpha,
+                                                _ptr(dr.alpha_dev), dr.robust_nu, ri + 1, _ptr(dr.omega), wsse))
+                elif r.model.alpha_sample:
+                    check(lib().bdf_pairs_weighted_sse(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, _ptr(dr.omega), wsse))
+                if r.model.alpha_sample:
+                    check(lib().bdf_sample_alpha(self.ctx.handle, r.model.alpha_lambda0, r.model.alpha_nu0, r.data.nnz(), wsse, ri + 1,
+                                                 _ptr(dr.alpha_dev)))
+                    self.ctx.sync()
+                    r.model.alpha = float(dr.alpha_dev.item())
+                continue
             if r.model.probit:           # z | U, V: the rows of this iteration then see linear_values = y - z, alpha = 1
                 fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
                 check(lib().bdf_probit_draw(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, ri + 1, _ptr(dr.linear), None))

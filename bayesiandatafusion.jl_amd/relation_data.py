@@ -87,6 +87,10 @@ def toStr(x):
         s += f" intv:{int(np.count_nonzero(x.model.interval[:, 0] < x.model.interval[:, 1]))}"
     if x.model.ordinal is not None:
         s += f" ord:{x.model.ordinal['K']}"
+    if x.model.robust is not None:
+        s += f" t:{x.model.robust['nu']:g}"
+    if x.model.weights is not None:
+        s += " wts"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -110,6 +114,8 @@ class RelationModel:
         self.ordinal_edges = None # ... float64 (K - 1): the edges e_1 .. e_{K-1}, k + 1/2 until macau() has drawn them (then the last draw)
         self.test_ordinal = None  # setTestOrdinal: int8 per row of test_vec, its level (macau(lpd=True))
         self.waic = None          # setWaic: {"pointwise"}; macau() scores the training cells by WAIC
+        self.robust = None        # setRobust: {"nu"}; Student-t noise with nu degrees of freedom and scale alpha^-1/2
+        self.weights = None       # setWeights: float64 per training row, its known precision weight (> 0)
 
 
 class RelationTemp:
@@ -242,6 +248,7 @@ def setProbit(r):
         raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): the probit noise model does not take them.")
     if r.model.interval is not None:
         raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval): the probit noise model (setProbit) does not take them.")
+    _no_weights(r, "the probit noise model (setProbit)")
     r.model.probit = True
     r.model.alpha = 1.0
     r.model.alpha_sample = False
@@ -274,9 +281,91 @@ def setCensored(r, censor):
         raise ArgumentError(f"Relation {r.name} has the probit noise model: it does not take censoring flags.")
     if r.model.interval is not None:
         raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval): it does not take censoring flags (setCensored) as well.")
+    _no_weights(r, "censoring flags (setCensored)")
     r.model.censor = _censor_flags(r, censor)
     r._dev = None
     return None
+
+
+def _no_weights(r, what):
+    """the noise models with a latent value per observation take neither the Student-t model nor observation weights"""
+    if r.model.robust is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
+    if r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
+
+
+def _weight_guards(r, what):
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take {what}.")
+    if r.model.censor is not None:
+        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take {what}.")
+    if r.model.ordinal is not None:
+        raise ArgumentError(f"Relation {r.name} has the ordinal noise model (setOrdinal): it does not take {what}.")
+    if r.model.interval is not None:
+        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): it does not take {what}.")
+    if r.model.waic is not None:
+        raise ArgumentError(f"Relation {r.name} is scored by WAIC (setWaic): a cell's density under {what} is not scored yet.")
+
+
+def setRobust(r, nu=4.0):
+    """Robust noise model for a Gaussian relation (the reference weighs every training cell alike): Student-t noise with nu
+    degrees of freedom and scale alpha^-1/2, as the scale mixture y ~ N(u'v + mean, 1 / (alpha omega)), omega ~ Gamma(nu / 2,
+    rate nu / 2).  macau() samples omega for every training row beside the rows, so that a gross outlier counts with a small
+    precision instead of dragging the factors; result["robust"]["weights"] is the posterior mean of omega per training row (small:
+    an outlier).  nu >= 1; nu = 1 is Cauchy noise, a large nu approaches the Gaussian model.  Predictions, the test set and alpha
+    (fixed, setPrecision or alpha_sample) stay what they are."""
+    _weight_guards(r, "the robust noise model (setRobust)")
+    if r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take the robust noise model (setRobust) as well.")
+    r.model.robust = {"nu": _robust_nu(r, nu)}
+    r._dev = None
+    return None
+
+
+def _robust_nu(r, nu):
+    if isinstance(nu, bool) or not isinstance(nu, (int, float, np.integer, np.floating)) or not np.isfinite(nu) or nu < 1.0:
+        raise ArgumentError(f"Relation {r.name}: nu = {nu} must be a finite number, at least 1.")
+    return float(nu)
+
+
+def setWeights(r, weights):
+    """Known observation weights for a Gaussian relation: training row k of r.data, in its current order, counts with precision
+    alpha weights[k] (replicate counts, reported standard errors as 1 / se^2 relative to 1 / alpha, down-weighted imputed cells).
+    Every weight is finite and strictly positive.  A sampled alpha is drawn from its conditional under the weights.  Call it AFTER
+    the test split (assignToTest removes training rows; setTest does not)."""
+    _weight_guards(r, "observation weights (setWeights)")
+    if r.model.robust is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take observation weights (setWeights) as well.")
+    r.model.weights = _obs_weights(r, weights)
+    r._dev = None
+    return None
+
+
+def _obs_weights(r, weights):
+    try:
+        w = np.asarray(weights, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ArgumentError(f"Relation {r.name}: observation weights must be numbers.") from None
+    if w.ndim != 1 or len(w) != r.data.nnz():
+        raise ArgumentError(f"Relation {r.name} has {r.data.nnz()} training rows but {w.shape} observation weights were given.")
+    if not bool(np.all(np.isfinite(w) & (w > 0.0))):
+        raise ArgumentError(f"Relation {r.name}: observation weights must be finite and strictly positive.")
+    return np.ascontiguousarray(w)
+
+
+def check_robust(r):
+    """what a robust or weighted relation must still satisfy when a sampler is built on it (it may have been changed since)"""
+    what = "the robust noise model (setRobust)" if r.model.robust is not None else "observation weights (setWeights)"
+    _weight_guards(r, what)
+    if r.model.robust is not None and r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take observation weights (setWeights) as well.")
+    if r.model.robust is not None:
+        r.model.robust = {"nu": _robust_nu(r, r.model.robust.get("nu"))}
+    if r.model.weights is not None:
+        r.model.weights = _obs_weights(r, r.model.weights)
 
 
 def _censor_flags(r, censor):
@@ -448,6 +537,10 @@ def setWaic(r, on=True, pointwise=False):
         raise ArgumentError(f"Relation {r.name}: setWaic takes on = true / false and pointwise = true / false.")
     if pointwise and not on:
         raise ArgumentError(f"Relation {r.name}: setWaic(on = false) returns no pointwise table.")
+    if on and r.model.robust is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): a cell's density under it is not scored yet (setWaic).")
+    if on and r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): a cell's density under them is not scored yet (setWaic).")
     r.model.waic = {"pointwise": bool(pointwise)} if on else None
     return None
 
@@ -498,6 +591,7 @@ def _interval_guards(r):
         raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take interval bounds (setInterval).")
     if r.model.censor is not None:
         raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take interval bounds (setInterval) as well.")
+    _no_weights(r, "interval bounds (setInterval / setBinned / setOrdinal)")
 
 
 def _interval_bounds(r, lower, upper, test=False):
@@ -539,6 +633,8 @@ def assignToTest(r, test, rng=None):
         raise ArgumentError(f"Relation {r.name} has interval bounds, one pair per training row: call assignToTest before setInterval.")
     if r.model.censor is not None:
         raise ArgumentError(f"Relation {r.name} has censoring flags, one per training row: call assignToTest before setCensored.")
+    if r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has observation weights, one per training row: call assignToTest before setWeights.")
     if np.isscalar(test):
         rng = rng if rng is not None else np.random.default_rng()
         test_id = rng.choice(r.data.nnz(), size=int(test), replace=False) + 1

@@ -57,6 +57,8 @@ extern "C" {
 #define BDF_P_CENSORED     13  /* bdf_censored_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 #define BDF_P_INTERVAL     14  /* bdf_interval_draw: uniform per observation (entity 0x800000 | rel_tag, row = observation, pair 0) */
 #define BDF_P_ORDINAL      15  /* bdf_ordinal_step: entity 0x800000 | rel_tag; row 0, normal k: the proposal's k-th normal; row 1, pair 0: the uniform */
+#define BDF_P_ROBUST_N 16      /* bdf_robust_draw: the gamma variate's normals (entity 0x800000 | rel_tag, row = observation, attempt t: normal 2 t) */
+#define BDF_P_ROBUST_U 17      /* bdf_robust_draw: ... and its uniforms (the same entity and row, pair = attempt)                               */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -199,6 +201,11 @@ typedef struct {
     const double *linear_values;  /* dev, nullable: rel.temp.linear_values in COO order      */
     const double *factors[BDF_MAX_MODES]; /* dev: D x N_k sample of every mode of rel; [mode] ignored */
     const double *alpha_dev;      /* dev, nullable: rel.model.alpha in device memory (sampled there, bdf_sample_alpha): read instead of `alpha` */
+    /* dev, nullable (a zeroed tail is "none"): a precision weight omega_k > 0 per observation in COO order.  The observation then
+     * counts with precision alpha omega_k: P_i = Lambda + alpha sum omega_k w w', b_i = Lambda mu_i + alpha sum omega_k (y - base) w.
+     * Known weights, or the scale mixture of the Student-t model (bdf_robust_draw).  A call with any weighted term is sampled by
+     * the wave-per-row kernel's weighted variant (k_rows_w); weights of exactly 1 give the unweighted general path's bits. */
+    const double *obs_precision;
 } bdf_term;
 
 /* sample_latent_all2! (src/sampling.jl:149-172) and sample_user2_all! (:251-264):
@@ -355,6 +362,25 @@ int bdf_censored_draw(bdf_ctx *ctx, const bdf_pairs *train, const int8_t *censor
  * sum of squares of z; z_out (dev, n, nullable): z_k.  lo_k > hi_k or a NaN bound is undefined.  factors as for bdf_predict. */
 int bdf_interval_draw(bdf_ctx *ctx, const bdf_pairs *train, const double *bounds_dev, int D, const double *const *factors,
                       double mean_value, double alpha, const double *alpha_dev, uint32_t rel_tag, double *linear_out, double *z_out);
+/* Robust (Student-t) noise model of a Gaussian relation (csrc/k_robust.hip, csrc/robust.h):
+ *   value_k ~ N(udot_k + mean_value, 1 / (alpha omega_k)),  omega_k ~ Gamma(nu / 2, rate nu / 2)
+ * -- value_k is Student-t with nu degrees of freedom and scale alpha^-1/2.  For observation k of `train` IN THE CALLER'S ORDER (the
+ * pairs may be stored sorted), with e_k = value_k - mean_value - udot_k, the conditional draw is
+ *   omega_k = 2 G_k / (nu + alpha e_k^2),  G_k ~ Gamma((nu + 1) / 2, 1) by Marsaglia-Tsang: d = (nu + 1) / 2 - 1/3, c = 1 / sqrt(9 d);
+ *   attempt t = 0, 1, ...: x = normal 2 t of stream (BDF_P_ROBUST_N, 0x800000 | rel_tag, row k), v = (1 + c x)^3 (an attempt with
+ *   1 + c x <= 0 is skipped), u = the uniform of (BDF_P_ROBUST_U, the same entity and row, pair t); accepted when
+ *   u < 1 - 0.0331 x^4 or log u < x^2 / 2 + d (1 - v + log v); then G_k = d v (after 256 refusals: d)
+ * at the context's sweep.  nu >= 1 and finite, so the shape is at least 1.  alpha_dev (dev, nullable) wins over alpha, which must
+ * otherwise be positive and finite.  precision_out (dev, n): omega_k, what bdf_term.obs_precision takes.  wsse_out (dev, 1 double,
+ * nullable): sum_k omega_k e_k^2 added in a fixed order (bit-identical reruns) -- with it in place of the sum of squares,
+ * bdf_sample_alpha draws from alpha's exact conditional.  factors as for bdf_predict.  Not reentrant on one context (the
+ * partial sums live in the context's scratch). */
+int bdf_robust_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value, double alpha,
+                    const double *alpha_dev, double nu, uint32_t rel_tag, double *precision_out, double *wsse_out);
+/* *out (dev, 1 double) = sum_k weights[k] (value_k - mean_value - udot_k)^2 over the pairs, weights (dev, n) in the caller's order,
+ * added in the same fixed order: sample_alpha's sum of squares for a relation with known weights (no draw). */
+int bdf_pairs_weighted_sse(bdf_ctx *ctx, const bdf_pairs *pairs, int D, const double *const *factors, double mean_value,
+                           const double *weights, double *out);
 
 /* Ordinal probit noise model (csrc/k_ordinal.hip, csrc/ordinal.h): the training values of a relation are
  * levels 1 .. K (4 <= K <= 16), y = k iff e_{k-1} <= z < e_k for the latent z ~ N(udot + mean_value, 1 / alpha) of the interval
@@ -678,6 +704,14 @@ typedef struct {
      * `interval`, which is required and therefore not const to the library; one rank, no feat */
     bdf_ordinal *ordinal;
     const int8_t *ordinal_codes;
+    /* per-observation precision weights (a zeroed tail is "none"): obs_precision (dev, one double per observation of `train` in the
+     * caller's order) is what the entities' rows read as bdf_term.obs_precision.  robust_nu >= 1: the Student-t model --
+     * bdf_robust_draw (with alpha_dev: the previous iteration's alpha) rewrites obs_precision BEFORE sample_alpha, which then takes
+     * sum omega e^2 in place of the sum of squares; the iteration is omega | U,V,alpha -> alpha | U,V,omega -> U | omega,V -> V |
+     * omega,U.  robust_nu == 0: the weights are the caller's and stay; sample_alpha takes bdf_pairs_weighted_sse.  Not with
+     * probit, censor, interval, ordinal, feat or a communicator; needs train */
+    double robust_nu;
+    double *obs_precision;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

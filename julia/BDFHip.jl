@@ -137,6 +137,7 @@ struct Term
     linear_values::Ptr{Cvoid}
     factors::NTuple{4,Ptr{Cvoid}}
     alpha_dev::Ptr{Cvoid}             # C_NULL, or rel.model.alpha in device memory (sampled there: sample_alpha inside sweep!)
+    obs_precision::Ptr{Cvoid}         # C_NULL, or a precision weight per observation in COO order (known weights; robust_draw!'s omega)
 end
 
 """
@@ -477,6 +478,27 @@ function interval_draw!(c::Context, train::DevPairs, bounds::DevArray{Float64}, 
                 c.h, train.h, bounds.p, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, rel_tag, linear_out.p,
                 z_out === nothing ? C_NULL : z_out.p))
 end
+"robust (Student-t) noise model of a Gaussian relation: the precision weight omega of every observation of `train` given the
+factors, omega = 2 G / (nu + alpha e^2) with e = value - mean_value - udot and G ~ Gamma((nu + 1) / 2, 1) from the streams
+(16 / 17, 0x800000 | rel_tag, observation); nu >= 1; `alpha_dev` (a device scalar or `nothing`) wins over `alpha`; precision_out
+is what the rows take as Term.obs_precision; wsse_out (one device Float64 or `nothing`): sum omega e^2 in a fixed order, what
+sample_alpha! takes in place of the sum of squares"
+function robust_draw!(c::Context, train::DevPairs, D, factors::Vector{<:DevArray}, mean_value, alpha, alpha_dev, nu, rel_tag,
+                      precision_out::DevArray{Float64}, wsse_out=nothing)
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_robust_draw, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}, Float64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, train.h, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, nu, rel_tag, precision_out.p,
+                wsse_out === nothing ? C_NULL : wsse_out.p))
+end
+"out (one device Float64) = sum over the pairs of weights[k] (value - mean_value - udot)^2, in a fixed order: sample_alpha!'s
+sum of squares for a relation with known observation weights"
+function pairs_weighted_sse!(c::Context, p::DevPairs, D, factors::Vector{<:DevArray}, mean_value, weights::DevArray{Float64},
+                             out::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_pairs_weighted_sse, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, p.h, D, fp, mean_value, weights.p, out.p))
+end
 "out = mean_value + F beta: linear_values (macau.jl:91) and the test rows' baseline"
 feat_linear!(c::Context, f::Ptr{Cvoid}, beta::DevArray{Float64}, mean_value, out::DevArray{Float64}) =
     check(ccall((:bdf_feat_linear, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), c.h, f, beta.p, mean_value, out.p))
@@ -640,6 +662,8 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     interval::Ptr{Cvoid}                          # interval-censored noise model: device Float64 (lower, upper) per observation of train (C_NULL: none)
     ordinal::Ptr{Cvoid}                           # ordinal noise model: an Ordinal's handle (C_NULL: none); needs interval
     ordinal_codes::Ptr{Cvoid}                     # ... and device Int8 levels 1 .. K per observation of train
+    robust_nu::Float64                            # robust (Student-t) noise model: its degrees of freedom >= 1 (0: off)
+    obs_precision::Ptr{Cvoid}                     # device Float64 weight per observation of train: robust_draw!'s omega, or the caller's (C_NULL: none)
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
