@@ -21,6 +21,7 @@ P_CENSORED = 13
 P_INTERVAL = 14
 P_ORDINAL = 15
 P_ROBUST_N, P_ROBUST_U = 16, 17
+P_PG = 18
 
 
 class ArgumentError(ValueError):
@@ -89,7 +90,8 @@ class GibbsRelation(C.Structure):
                 ("beta", C.c_void_p), ("linear", C.c_void_p), ("lambda_beta", C.c_double), ("feat_test", C.c_void_p),
                 ("test_baseline", C.c_void_p), ("probit", C.c_int32), ("_pad", C.c_int32), ("censor", C.c_void_p),
                 ("interval", C.c_void_p), ("ordinal", C.c_void_p), ("ordinal_codes", C.c_void_p),
-                ("robust_nu", C.c_double), ("obs_precision", C.c_void_p)]
+                ("robust_nu", C.c_double), ("obs_precision", C.c_void_p),
+                ("pg_model", C.c_int32), ("_pad_pg", C.c_int32), ("pg_r", C.c_double)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -141,6 +143,8 @@ _SIGS = {
     "bdf_pairs_order": (C.c_int, [C.c_void_p, c_i64p]),
     "bdf_pairs_set_baseline": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdf_pairs_set_link": (C.c_int, [C.c_void_p, C.c_int]),
+    "bdf_pairs_set_logistic_link": (C.c_int, [C.c_void_p]),
+    "bdf_pairs_set_count_link": (C.c_int, [C.c_void_p, C.c_double]),
     "bdf_probit_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdf_censored_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p,
                                     C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -148,6 +152,8 @@ _SIGS = {
                                     C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdf_robust_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p, C.c_double,
                                   C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bdf_pg_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_int, C.c_double, C.c_uint32,
+                              C.c_void_p, C.c_void_p]),
     "bdf_pairs_weighted_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
     "bdf_ordinal_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]),
     "bdf_ordinal_destroy": (C.c_int, [C.c_void_p]),

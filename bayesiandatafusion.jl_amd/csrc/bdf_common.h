@@ -178,7 +178,8 @@ struct bdf_pairs {
     std::vector<int32_t> ids_host, orig_host;
     std::vector<double> values_host;
     void *auc_ws;                 // bdf_pairs_auc's workspace (bdf_auc_workspace_bytes(n)), allocated at first use
-    int link;                     // bdf_pairs_set_link: 0 identity, 1 probit (predictions are Phi(udot + base): k_probit.hip)
+    int link;                     // bdf_pairs_set_link: 0 identity, 1 probit (predictions are Phi(udot + base): k_probit.hip), 2 logistic; 3 counts (k_pg.hip)
+    double link_r;                // bdf_pairs_set_count_link: predictions are link_r exp(udot + base)
     double *lpd_dev;              // bdf_pairs_lpd_update's running state (k_lpd.hip): n maxima M, then n sums A, in storage order; at first use
     double lpd_draws;             // ... and the posterior draws it holds (a counter of its own, not `count`)
     double *waic_dev;             // bdf_pairs_waic_update's running state (k_waic.hip): four planes of n in storage order -- M, A, mean, M2; at first use
@@ -402,3 +403,6 @@ int bdf_predict_plain(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *con
 // 0..2 the update (count: the pairs' counter before it), 3 statistics only; linear (nullable) overrides the pairs' baseline
 int bdf_predict_link(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, const double *linear,
                      double *out, int phase, double count, double clamp_lo, double clamp_hi, double class_cut, double *stats_out);
+// ... and what it hands the logistic (2) and the count link (3) to (k_pg.hip)
+int bdf_predict_link_pg(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, const double *linear,
+                        double *out, int phase, double count, double clamp_lo, double clamp_hi, double class_cut, double *stats_out);

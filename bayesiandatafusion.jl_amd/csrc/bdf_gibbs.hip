@@ -366,6 +366,13 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
         BDF_REQUIRE(!r.obs_precision || (!r.probit && !r.censor && !r.interval && !r.ordinal && !r.feat), BDF_ERR_ARG,
                     "bdf_gibbs_set_relations: relation %d: observation weights take neither the probit, censored, interval or ordinal model nor relation features", k);
         BDF_REQUIRE(!r.obs_precision || !g->comm, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: observation weights need one rank", k);
+        BDF_REQUIRE(r.pg_model >= 0 && r.pg_model <= 2, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: pg_model=%d must be 0 (none), 1 (logit) or 2 (counts)", k, r.pg_model);
+        BDF_REQUIRE(!r.pg_model || (r.train && r.linear && r.obs_precision), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: a Polya-Gamma model needs its observations as pairs (train), a linear and an obs_precision buffer", k);
+        BDF_REQUIRE(!r.pg_model || (!r.probit && !r.censor && !r.interval && !r.ordinal && r.robust_nu == 0.0 && !r.feat && !r.alpha_sample && !g->comm), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: a Polya-Gamma model takes neither the probit, censored, interval, ordinal or robust model, relation features, a sampled alpha nor a communicator", k);
+        BDF_REQUIRE(r.pg_model != 2 || (r.pg_r >= 1.0 && r.pg_r <= 2147483648.0 && r.pg_r == std::floor(r.pg_r)), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: pg_r=%g must be an integer, at least 1", k, r.pg_r);
         for (int m = 0; m < r.rel->n_modes; m++)
             BDF_REQUIRE(r.entity_of_mode[m] >= 0 && r.entity_of_mode[m] < (int)g->ent.size(), BDF_ERR_ARG,
                         "bdf_gibbs_set_relations: relation %d mode %d names entity %d", k, m, r.entity_of_mode[m]);
@@ -384,8 +391,9 @@ const bdf_gibbs_relation *relation_of(const bdf_gibbs *g, const bdf_rel *rel)
     return nullptr;
 }
 
-// does the relation draw a latent z per observation into its linear buffer?  (bdf_gibbs_set_relations admits one of the three.)
-inline bool draws_latent(const bdf_gibbs_relation &r) { return r.probit || r.censor || r.interval; }
+// does the relation draw a latent z per observation into its linear buffer?  (bdf_gibbs_set_relations admits one of the four; the
+// Polya-Gamma models write the pseudo-observation there, and omega beside it.)
+inline bool draws_latent(const bdf_gibbs_relation &r) { return r.probit || r.censor || r.interval || r.pg_model; }
 
 // macau.jl:83-92 on the row stream, before the entities' rows
 int update_relations(bdf_gibbs *g)
@@ -416,6 +424,10 @@ int update_relations(bdf_gibbs *g)
         }
         // probit: the latent z of every observation given the rows; the rows then see linear = y - z with alpha = 1
         if (r.probit && (rc = bdf_probit_draw(R, r.train, D, fac, r.mean_value, r.rel_tag, r.linear + r.first_obs, nullptr))) return rc;
+        // Polya-Gamma (logit, counts): omega of every observation given the rows, at the same place; the rows then see the
+        // pseudo-observation through linear and its precision through obs_precision, with alpha = 1
+        if (r.pg_model && (rc = bdf_pg_draw(R, r.train, D, fac, r.mean_value, r.pg_model, r.pg_r, r.rel_tag, r.obs_precision, r.linear + r.first_obs)))
+            return rc;
         // censored: the latent z of every flagged observation given the rows and the alpha just drawn (the sum of squares above was
         // that of the previous z: the pairs carry linear as their baseline); the rows then see linear = mean + y - z with alpha_dev
         if (r.censor && (rc = bdf_censored_draw(R, r.train, r.censor, D, fac, r.mean_value, 0.0, r.alpha_dev, r.rel_tag, r.linear + r.first_obs, nullptr)))
@@ -550,7 +562,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         }
         // the last draw: y - z (probit), mean + y - z (censored, interval)
         if (draws_latent(r)) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});
-        if (r.robust_nu > 0.0) pieces.push_back({r.obs_precision, (size_t)r.train->n * sizeof(double), false, 0});       // the last omega
+        if (r.robust_nu > 0.0 || r.pg_model) pieces.push_back({r.obs_precision, (size_t)r.train->n * sizeof(double), false, 0});       // the last omega
         if (r.ordinal) {                    // the edges, the step size, the counters and the trace; the bounds made from the edges
             pieces.push_back({r.ordinal->state_dev, r.ordinal->state_doubles * sizeof(double), false, 0});
             pieces.push_back({const_cast<double *>(r.interval), (size_t)r.train->n * 2 * sizeof(double), false, 0});

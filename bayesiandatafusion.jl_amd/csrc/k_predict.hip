@@ -261,7 +261,7 @@ extern "C" int bdf_pairs_create(bdf_ctx *ctx, int n_modes, int64_t n, const void
     }
     bdf_pairs *p = new bdf_pairs();
     p->ctx = ctx; p->n_modes = n_modes; p->n = n; p->count = 0.0; p->baseline_dev = nullptr; p->orig_dev = nullptr; p->sorted_mode = -1;
-    p->ids_dev = nullptr; p->values_dev = nullptr; p->avg_dev = nullptr; p->sq_dev = nullptr; p->auc_ws = nullptr; p->link = 0;
+    p->ids_dev = nullptr; p->values_dev = nullptr; p->avg_dev = nullptr; p->sq_dev = nullptr; p->auc_ws = nullptr; p->link = 0; p->link_r = 0.0;
     p->lpd_dev = nullptr; p->lpd_draws = 0.0; p->waic_dev = nullptr; p->waic_draws = 0.0;
     struct Guard { bdf_pairs *p; ~Guard() { if (p) bdf_pairs_destroy(p); } } guard{p};        // error paths free what was allocated
     p->ids_host = h;
@@ -405,6 +405,22 @@ extern "C" int bdf_pairs_set_link(bdf_pairs *p, int link)
     BDF_REQUIRE(p != nullptr, BDF_ERR_ARG, "bdf_pairs_set_link: NULL argument");
     BDF_REQUIRE(link == 0 || link == 1, BDF_ERR_ARG, "bdf_pairs_set_link: link=%d must be 0 (identity) or 1 (probit)", link);
     p->link = link;
+    return BDF_OK;
+}
+
+extern "C" int bdf_pairs_set_logistic_link(bdf_pairs *p)
+{
+    BDF_REQUIRE(p != nullptr, BDF_ERR_ARG, "bdf_pairs_set_logistic_link: NULL argument");
+    p->link = 2;
+    return BDF_OK;
+}
+
+extern "C" int bdf_pairs_set_count_link(bdf_pairs *p, double r)
+{
+    BDF_REQUIRE(p != nullptr, BDF_ERR_ARG, "bdf_pairs_set_count_link: NULL argument");
+    BDF_REQUIRE(r >= 1.0 && r <= 2147483648.0 && r == std::floor(r), BDF_ERR_ARG, "bdf_pairs_set_count_link: r=%g must be an integer, at least 1", r);
+    p->link = 3;
+    p->link_r = r;
     return BDF_OK;
 }
 

@@ -11,8 +11,7 @@
 // Layout as k_predict.hip: 8 lanes share a pair and read 32 bytes each; ids and values are loaded 8 consecutive pairs per
 // group before the first gather; BATCH pairs' rows are in flight.  No LDS in the draw, no scratch, plain vector stores.
 #include "bdf_common.h"
-#include "predict.h"
-#include "pair_gather.h"
+#include "predict_link.h"
 #include <algorithm>
 
 namespace {
@@ -50,20 +49,7 @@ __global__ __launch_bounds__(256, (VEC == 4 && NM * NC >= 8) ? 2 : 3) void k_pro
 template <int NM, int VEC, int NC>
 __global__ __launch_bounds__(256) void k_predict_link(PredArgs a)
 {
-    const int tid = threadIdx.x, sub = tid & 7;
-    double st[4] = {0.0, 0.0, 0.0, 0.0};
-    const int64_t ngroups = (int64_t)gridDim.x * 32, ntrips = (a.n + 7) / 8;
-    for (int64_t trip = (int64_t)blockIdx.x * 32 + tid / 8; trip < ntrips; trip += ngroups) {
-        const int64_t p0 = trip * 8;
-        PairState ps;
-        pair_load(a, p0 + sub, ps);
-        int32_t my[NM];
-#pragma unroll
-        for (int k = 0; k < NM; k++) my[k] = a.ids[(int64_t)k * a.n + ps.pm];
-        const double keep = group_dots<NM, VEC, NC>(a.fac, a.D, a.n, p0, sub, my);
-        pair_finish<1>(a, ps, keep, st);
-    }
-    if (a.phase >= 0) block_stats(a, st);
+    predict_link_body<NM, VEC, NC, 1>(a);
 }
 
 }  // namespace
@@ -71,26 +57,10 @@ __global__ __launch_bounds__(256) void k_predict_link(PredArgs a)
 int bdf_predict_link(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, const double *linear,
                      double *out, int phase, double count, double clamp_lo, double clamp_hi, double class_cut, double *stats_out)
 {
-    PredArgs a;
-    int rc = fill("bdf_predict (probit link)", ctx, p, D, factors, a);
-    if (rc) return rc;
-    a.mean = mean_value; a.out = out; a.phase = phase; a.count = count;
-    if (linear) a.linear = linear;
-    if (phase >= 0) {
-        a.avg = p->avg_dev; a.sq = p->sq_dev; a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi; a.cut = class_cut; a.stats = stats_out;
-    }
-    if (a.n == 0) return BDF_OK;
-    const int64_t ntrips = (a.n + 7) / 8;
-    const int nblocks = (int)std::min<int64_t>((ntrips + 31) / 32, 8192);
-    if (phase >= 0) {
-        void *sc;
-        if ((rc = bdf_scratch(ctx, (size_t)nblocks * 4 * sizeof(double), &sc))) return rc;
-        a.partial = (double *)sc;
-    }
-    BDF_BY_SHAPE(k_predict_link, a.n_modes, D, nblocks, ctx->stream, a);
-    if (phase >= 0) hipLaunchKernelGGL(k_predict_final, dim3(1), dim3(256), 0, ctx->stream, nblocks, (const double *)a.partial, a.stats);
-    BDF_HIP(hipGetLastError());
-    return BDF_OK;
+    if (p && p->link >= 2) return bdf_predict_link_pg(ctx, p, D, factors, mean_value, linear, out, phase, count, clamp_lo, clamp_hi, class_cut, stats_out);
+    return predict_link_launch("bdf_predict (probit link)", ctx, p, D, factors, mean_value, linear, out, phase, count, clamp_lo, clamp_hi,
+                               class_cut, stats_out,
+                               [&](const PredArgs &a, int nblocks) { BDF_BY_SHAPE(k_predict_link, a.n_modes, D, nblocks, ctx->stream, a); });
 }
 
 extern "C" int bdf_probit_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value,

@@ -202,6 +202,7 @@ int record_fill(const char *who, bdf_ctx *ctx, const bdf_pairs *p, const double 
                 RecordArgs &r, int *nblocks)
 {
     BDF_REQUIRE(ctx && p && factors && stats_out, BDF_ERR_ARG, "%s: NULL argument", who);
+    BDF_REQUIRE(p->link <= 1, BDF_ERR_ARG, "%s: pairs with the logistic or the count link are not scored yet", who);
     BDF_REQUIRE(!(bounds_dev && p->link == 1), BDF_ERR_ARG, "%s: pairs with the probit link take no bounds", who);
     BDF_REQUIRE(((uintptr_t)bounds_dev & 15) == 0, BDF_ERR_ARG, "%s: bounds_dev must be aligned to 16 bytes", who);
     BDF_REQUIRE(phase >= 0 && phase <= 2, BDF_ERR_ARG, "%s: phase must be 0, 1 or 2", who);

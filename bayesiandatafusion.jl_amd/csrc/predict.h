@@ -5,6 +5,7 @@
 #pragma once
 #include "bdf_common.h"
 #include "probit.h"
+#include "pg.h"
 
 namespace {
 
@@ -25,6 +26,7 @@ struct PredArgs {
     double count, clamp_lo, clamp_hi, cut;
     double *stats;
     double *partial;               // per-block statistics
+    double link_r;                 // the count link's dispersion r (k_pg.hip)
 };
 
 __device__ inline double clampv(double x, double lo, double hi)
@@ -55,13 +57,16 @@ __device__ inline void pair_load(const PredArgs &a, int64_t p, PairState &s)
     if (a.phase == 2) { s.av = a.avg[s.pm]; s.sv = a.sq[s.pm]; }
 }
 
-// LINK 1 (k_probit.hip): the prediction is the probability Phi(dot + base), before the clamp, the running state and the statistics
+// LINK 1 (k_probit.hip): the prediction is the probability Phi(dot + base), before the clamp, the running state and the statistics;
+// LINK 2 / 3 (k_pg.hip): the logistic probability / the count's mean r e^(dot + base)
 template <int LINK = 0>
 __device__ inline void pair_finish(const PredArgs &a, const PairState &s, double dot, double (&st)[4])
 {
     if (!s.ok) return;
     double p = dot + s.base;
     if constexpr (LINK == 1) p = bdf_phi(p);
+    if constexpr (LINK == 2) p = bdf_pg_logistic(p);
+    if constexpr (LINK == 3) p = bdf_pg_count_mean(p, a.link_r);
     if (a.out) a.out[s.po] = p;
     if (a.phase >= 0) {
         double avg;

@@ -60,6 +60,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     clamp = [float(c) for c in clamp]
     if full_prediction and data.relations and data.relations[0].model.probit:
         raise ArgumentError("Prediction of all elements is not possible when Relation has the probit noise model.")
+    if full_prediction and data.relations and data.relations[0].model.pg is not None:
+        raise ArgumentError(f"Prediction of all elements is not possible when Relation has the {data.relations[0].model.pg['model']} noise model.")
     if rmse_train and data.relations and data.relations[0].model.censor is not None:
         raise ArgumentError("rmse_train is not possible when Relation has censoring flags: its training values are bounds, not measurements.")
     if rmse_train and data.relations and data.relations[0].model.interval is not None:
@@ -70,6 +72,9 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if lpd and data.relations and (robust is not None or data.relations[0].model.weights is not None):
         what = "the robust noise model (setRobust)" if robust is not None else "observation weights (setWeights)"
         raise ArgumentError(f"lpd = true is not possible when Relation has {what}: a held-out cell's density under it is not scored yet.")
+    if lpd and data.relations and data.relations[0].model.pg is not None:
+        raise ArgumentError(f"lpd = true is not possible when Relation has the {data.relations[0].model.pg['model']} noise model "
+                            "(setLogit / setCounts): a held-out cell's density under it is not scored yet.")
     if lpd and not (data.relations and numTest(data.relations[0]) > 0):
         raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")
 

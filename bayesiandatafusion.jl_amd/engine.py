@@ -26,7 +26,7 @@ import torch
 from . import _lib
 from . import features as feat
 from ._lib import ArgumentError, GibbsEntity, Term, check, lib
-from .relation_data import check_censored, check_interval, check_ordinal, check_probit, check_robust
+from .relation_data import check_censored, check_interval, check_ordinal, check_pg, check_probit, check_robust
 
 
 def _ptr(t):
@@ -300,6 +300,15 @@ class DevicePairs:
     def set_link(self, link):
         """0: predictions are udot + base (the default); 1: the probit link, probabilities Phi(udot + base) (bdf_pairs_set_link)"""
         check(lib().bdf_pairs_set_link(self.handle, int(link)))
+        return self
+
+    def set_pg_link(self, model, r=0.0):
+        """the links of the Polya-Gamma models: model 1, the logistic probability 1 / (1 + exp(-(udot + base))) (bdf_pairs_set_logistic_link);
+        model 2, the counts' mean r exp(udot + base) (bdf_pairs_set_count_link)"""
+        if int(model) == 1:
+            check(lib().bdf_pairs_set_logistic_link(self.handle))
+        else:
+            check(lib().bdf_pairs_set_count_link(self.handle, float(r)))
         return self
 
     def _facs(self, factors):
@@ -721,6 +730,10 @@ class GibbsEngine:
                 check_robust(r)
                 if shard is not None and shard[1] > 1:
                     raise ArgumentError(f"Relation {r.name} has {'the robust noise model' if r.model.robust is not None else 'observation weights'}: one rank only")
+            if r.model.pg is not None:
+                check_pg(r)
+                if shard is not None and shard[1] > 1:
+                    raise ArgumentError(f"Relation {r.name} has the {r.model.pg['model']} noise model: one rank only")
         self.data, self.D = data, int(num_latent)
         # The row context runs on a stream of its own that leaves a few CUs (one or two per XCD) free for the hyperprior's
         # small kernels, which otherwise wait for slots beside the chip-filling row kernel -- when the entities are small
@@ -778,13 +791,15 @@ class GibbsEngine:
                 raise ArgumentError(f"Relation {r.name} has {len(r.entities)} entities but its data implies {r.data.size()}.")
             lays = [self.layouts[self._entity_index(e)] for e in r.entities]
             dr = DeviceRelation(self.ctx, r.data, lays if self.world > 1 else None, self.rank)
-            r.model.mean_value = 0.0 if r.model.probit else dr.value_mean()      # (probit: the latent is not centred)
+            # (probit: the latent is not centred; logit / counts: psi = u'v + the offset the setter was given)
+            r.model.mean_value = 0.0 if r.model.probit else (r.model.pg["offset"] if r.model.pg is not None else dr.value_mean())
             r._dev = dr
             self.rel.append(dr)
             # relation-level side information (RelationData.jl:348-353): FF path only, as in the reference
             dr.F = dr.beta = dr.linear = dr.train = dr.censor = dr.interval = dr.ordinal = dr.ord_codes = None
             dr.omega = dr.wsse = dr.omega_sum = None
             dr.robust_nu = 0.0
+            dr.pg_model, dr.pg_r = 0, 0.0
             # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
             # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
             # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
@@ -855,6 +870,17 @@ class GibbsEngine:
                     dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
                 if len(r.entities) == 2 and nn:
                     dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
+            if r.model.pg is not None:
+                # the Polya-Gamma models (logit, counts): omega of every training row is drawn before the rows of every iteration
+                # (bdf_pg_draw) and handed to the row kernels as obs_precision, beside linear_values = offset + y - kappa / omega,
+                # with alpha = 1.  The training pairs predict through the model's link (rmse_train)
+                dr.pg_model, dr.pg_r = (1, 0.0) if r.model.pg["model"] == "logit" else (2, float(r.model.pg["r"]))
+                dr.omega = self.ctx.tensor(np.ones(max(nn, 1)))
+                dr.linear = self.ctx.tensor(np.full(max(nn, 1), r.model.mean_value))
+                dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
+                if len(r.entities) == 2 and nn:
+                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
+                dr.train.set_pg_link(dr.pg_model, dr.pg_r)
             dr.alpha_dev = self.ctx.tensor([float(r.model.alpha)])
         self._test_pairs = None
         self._train_pairs = None
@@ -928,7 +954,7 @@ class GibbsEngine:
         from ._lib import GibbsRelation
         rows = [(ri, r, self.rel[ri]) for ri, r in enumerate(self.data.relations)
                 if r.model.alpha_sample or self.rel[ri].F is not None or r.model.probit or r.model.censor is not None
-                or r.model.interval is not None or self.rel[ri].omega is not None]
+                or r.model.interval is not None or self.rel[ri].omega is not None]          # (omega: weights, robust, logit, counts)
         arr = (GibbsRelation * max(len(rows), 1))()
         for k, (ri, r, dr) in enumerate(rows):
             g = arr[k]
@@ -951,6 +977,8 @@ class GibbsEngine:
                 g.ordinal, g.ordinal_codes = dr.ordinal.handle, dr.ord_codes.data_ptr()
             if dr.omega is not None:
                 g.robust_nu, g.obs_precision = dr.robust_nu, dr.omega.data_ptr()
+            if dr.pg_model:
+                g.pg_model, g.pg_r, g.linear = dr.pg_model, dr.pg_r, dr.linear.data_ptr()
             if dr.F is not None:
                 g.feat, g.beta, g.linear, g.lambda_beta = dr.F.handle, dr.beta.data_ptr(), dr.linear.data_ptr(), r.model.lambda_beta
                 if ri == 0 and getattr(dr, "F_test", None) is not None:
@@ -1081,9 +1109,14 @@ class GibbsEngine:
         for ri, r in enumerate(self.data.relations):
             dr = self.rel[ri]
             if not (r.model.alpha_sample or dr.F is not None or r.model.probit or dr.censor is not None or dr.interval is not None
-                    or dr.robust_nu > 0.0):
+                    or dr.robust_nu > 0.0 or dr.pg_model):
                 continue
             facs = self.factors_of(r)
+            if dr.pg_model:              # omega | U, V: the rows of this iteration then see the pseudo-observation, precision omega
+                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
+                check(lib().bdf_pg_draw(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, dr.pg_model, dr.pg_r, ri + 1,
+                                        _ptr(dr.omega), _ptr(dr.linear)))
+                continue
             if dr.omega is not None:
                 # omega | U, V, alpha (the previous iteration's) -> alpha | U, V, omega from sum omega e^2; known weights: no draw,
                 # sum w e^2.  The rows of this iteration then read omega beside alpha
@@ -1384,6 +1417,8 @@ class GibbsEngine:
             if r.model.probit:               # predictions are probabilities Phi(udot)
                 self._test_pairs.set_link(1)
             dr = self.rel[0]
+            if dr.pg_model:                  # ... the logistic probabilities / the counts' mean r e^psi
+                self._test_pairs.set_pg_link(dr.pg_model, dr.pg_r)
             if dr.F is not None:             # pred(r, probe_vec, F) = udot + F_test beta + mean_value (sampling.jl:9-14)
                 if feat.isempty(r.test_F):
                     raise ArgumentError(f"Relation {r.name} has features but its test set has no feature rows (test_F)")

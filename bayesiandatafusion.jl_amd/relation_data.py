@@ -91,6 +91,8 @@ def toStr(x):
         s += f" t:{x.model.robust['nu']:g}"
     if x.model.weights is not None:
         s += " wts"
+    if x.model.pg is not None:
+        s = "logit" if x.model.pg["model"] == "logit" else f"nb:{x.model.pg['r']}"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -116,6 +118,7 @@ class RelationModel:
         self.waic = None          # setWaic: {"pointwise"}; macau() scores the training cells by WAIC
         self.robust = None        # setRobust: {"nu"}; Student-t noise with nu degrees of freedom and scale alpha^-1/2
         self.weights = None       # setWeights: float64 per training row, its known precision weight (> 0)
+        self.pg = None            # setLogit / setCounts: {"model": "logit" | "counts", "r", "offset"}; Polya-Gamma augmentation
 
 
 class RelationTemp:
@@ -226,6 +229,8 @@ def numTest(r):
 def setPrecision(r, precision):
     if r.model.probit:
         raise ArgumentError(f"Relation {r.name} has the probit noise model: its latent has unit variance, there is no precision to set.")
+    if r.model.pg is not None:
+        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: every cell's precision is its sampled omega, there is no precision to set.")
     r.model.alpha = float(precision)
 
 
@@ -293,9 +298,11 @@ def _no_weights(r, what):
         raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
     if r.model.weights is not None:
         raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
+    if r.model.pg is not None:
+        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
 
 
-def _weight_guards(r, what):
+def _weight_guards(r, what, pg_ok=False):
     if hasFeatures(r):
         raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
     if r.model.probit:
@@ -306,8 +313,107 @@ def _weight_guards(r, what):
         raise ArgumentError(f"Relation {r.name} has the ordinal noise model (setOrdinal): it does not take {what}.")
     if r.model.interval is not None:
         raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): it does not take {what}.")
+    if r.model.pg is not None and not pg_ok:
+        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
     if r.model.waic is not None:
         raise ArgumentError(f"Relation {r.name} is scored by WAIC (setWaic): a cell's density under {what} is not scored yet.")
+
+
+def _pg_name(r):
+    return "the logit noise model (setLogit)" if r.model.pg["model"] == "logit" else "the count noise model (setCounts)"
+
+
+def _pg_guards(r, what):
+    """what the Polya-Gamma models refuse: the weighted models' list, those two themselves and a sampled precision"""
+    _weight_guards(r, what, pg_ok=True)
+    if r.model.robust is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
+    if r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
+    if r.model.alpha_sample:
+        raise ArgumentError(f"Relation {r.name} samples its precision (alpha_sample): under {what} every cell's precision is its sampled omega.")
+
+
+def _pg_offset(r, offset):
+    if isinstance(offset, bool) or not isinstance(offset, (int, float, np.integer, np.floating)) or not np.isfinite(offset):
+        raise ArgumentError(f"Relation {r.name}: offset = {offset} must be a finite number.")
+    return float(offset)
+
+
+def _pg_r(r, disp):
+    if isinstance(disp, bool) or not isinstance(disp, (int, float, np.integer, np.floating)) or not np.isfinite(disp) \
+            or disp != int(disp) or disp < 1 or disp > COUNT_MAX:
+        raise ArgumentError(f"Relation {r.name}: r = {disp} must be an integer, at least 1.")
+    return int(disp)
+
+
+COUNT_MAX = 2 ** 31
+
+
+def _is_count(values):
+    v = np.asarray(values, dtype=np.float64)
+    return bool(np.all(np.isfinite(v) & (v >= 0) & (v <= COUNT_MAX) & (v == np.floor(v))))
+
+
+def setLogit(r, offset=0.0):
+    """Logit noise model for a relation of 0/1 values (the reference has Gaussian noise only): P(y = 1) = 1 / (1 + e^-psi),
+    psi = u'v + offset.  macau() samples a Polya-Gamma variable omega ~ PG(1, psi) for every training row beside the rows (Polson,
+    Scott & Windle 2013), which makes the row a Gaussian pseudo-observation (y - 1/2) / omega of psi with precision omega.
+    Predictions become probabilities, class_cut 0.5.  Works before or after assignToTest / setTest; every training and test value
+    must be exactly 0 or 1."""
+    if r.model.pg is not None and r.model.pg["model"] != "logit":
+        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take the logit noise model (setLogit) as well.")
+    _pg_guards(r, "the logit noise model (setLogit)")
+    if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
+        raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the logit noise model.")
+    r.model.pg = {"model": "logit", "r": 0, "offset": _pg_offset(r, offset)}
+    r.model.alpha = 1.0
+    r.model.alpha_sample = False
+    r.model.mean_value = r.model.pg["offset"]
+    r.class_cut = 0.5
+    r.test_label = r.test_vec.values < r.class_cut
+    r._dev = None
+    return None
+
+
+def setCounts(rel, r, offset=0.0):
+    """Count noise model (the reference has Gaussian noise only): the values are the integers 0, 1, 2, ... (at most 2^31, stored as
+    floats), negative binomial with the fixed integer dispersion r >= 1 and mean r e^psi, psi = u'v + offset: pmf proportional to
+    p^y (1 - p)^r at p = 1 / (1 + e^-psi).  macau() samples omega ~ PG(y + r, psi) for every training row beside the rows, which
+    makes the row a Gaussian pseudo-observation (y - r) / (2 omega) of psi with precision omega (exact up to y + r = 170, a
+    moment-matched normal above).  Predictions are the mean r e^psi.  Works before or after assignToTest / setTest."""
+    if rel.model.pg is not None and rel.model.pg["model"] != "counts":
+        raise ArgumentError(f"Relation {rel.name} has {_pg_name(rel)}: it does not take the count noise model (setCounts) as well.")
+    _pg_guards(rel, "the count noise model (setCounts)")
+    disp, off = _pg_r(rel, r), _pg_offset(rel, offset)
+    if not _is_count(rel.data.values) or not _is_count(rel.test_vec.values):
+        raise ArgumentError(f"Relation {rel.name} must hold only the integers 0 ... 2^31 for the count noise model.")
+    rel.model.pg = {"model": "counts", "r": disp, "offset": off}
+    rel.model.alpha = 1.0
+    rel.model.alpha_sample = False
+    rel.model.mean_value = off
+    rel._dev = None
+    return None
+
+
+def check_pg(r):
+    """what a logit or count relation must still satisfy when a sampler is built on it (it may have been changed since)"""
+    pg = r.model.pg
+    what = _pg_name(r)
+    _pg_guards(r, what)
+    if r.model.alpha != 1.0:
+        raise ArgumentError(f"Relation {r.name} has {what}: every cell's precision is its sampled omega, alpha stays 1.")
+    off = _pg_offset(r, pg.get("offset"))
+    if pg["model"] == "logit":
+        if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
+            raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the logit noise model.")
+        r.model.pg = {"model": "logit", "r": 0, "offset": off}
+    else:
+        disp = _pg_r(r, pg.get("r"))
+        if not _is_count(r.data.values) or not _is_count(r.test_vec.values):
+            raise ArgumentError(f"Relation {r.name} must hold only the integers 0 ... 2^31 for the count noise model.")
+        r.model.pg = {"model": "counts", "r": disp, "offset": off}
+    r.model.mean_value = off
 
 
 def setRobust(r, nu=4.0):
@@ -541,6 +647,8 @@ def setWaic(r, on=True, pointwise=False):
         raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): a cell's density under it is not scored yet (setWaic).")
     if on and r.model.weights is not None:
         raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): a cell's density under them is not scored yet (setWaic).")
+    if on and r.model.pg is not None:
+        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: a cell's density under it is not scored yet (setWaic).")
     r.model.waic = {"pointwise": bool(pointwise)} if on else None
     return None
 
@@ -675,6 +783,10 @@ def setTest(r, test, test_feat=None):
             raise ArgumentError("The number of columns in test_df must be the same as in relation.data.df.")
     if r.model.probit and not _is_binary(vals):
         raise ArgumentError(f"Relation {r.name} has the probit noise model: its test values must be 0 or 1.")
+    if r.model.pg is not None and r.model.pg["model"] == "logit" and not _is_binary(vals):
+        raise ArgumentError(f"Relation {r.name} has the logit noise model: its test values must be 0 or 1.")
+    if r.model.pg is not None and r.model.pg["model"] == "counts" and not _is_count(vals):
+        raise ArgumentError(f"Relation {r.name} has the count noise model: its test values must be the integers 0 ... 2^31.")
     r.test_vec = TestVec(ids, vals, r.data.names)
     r.test_label = r.test_vec.values < r.class_cut
     r.model.test_interval = None

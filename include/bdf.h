@@ -59,6 +59,7 @@ extern "C" {
 #define BDF_P_ORDINAL      15  /* bdf_ordinal_step: entity 0x800000 | rel_tag; row 0, normal k: the proposal's k-th normal; row 1, pair 0: the uniform */
 #define BDF_P_ROBUST_N 16      /* bdf_robust_draw: the gamma variate's normals (entity 0x800000 | rel_tag, row = observation, attempt t: normal 2 t) */
 #define BDF_P_ROBUST_U 17      /* bdf_robust_draw: ... and its uniforms (the same entity and row, pair = attempt)                               */
+#define BDF_P_PG 18            /* bdf_pg_draw: one cursor per observation over the blocks pair = 0, 1, 2, ... (entity 0x800000 | rel_tag, row = observation) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -284,6 +285,15 @@ int bdf_pairs_set_baseline(bdf_pairs *pairs, const double *baseline);
  * the running average, the running sum of squares and the four statistics (kernels of their own, csrc/k_probit.hip; pairs
  * stored sorted take the general kernel).  BDF_ERR_ARG for any other value. */
 int bdf_pairs_set_link(bdf_pairs *pairs, int link);
+/* link 2 (logistic): p = 1 / (1 + e^-psi) for psi = udot + base >= 0 and e^psi / (1 + e^psi) otherwise, the probability of a 1 under
+ * the logit model, at the same place as the probit link (kernels of their own, csrc/k_pg.hip).  An entry point of its own:
+ * bdf_pairs_set_link keeps to 0 and 1 and refuses every other value, as its callers rely on; bdf_pairs_set_link(pairs, 0 | 1)
+ * takes the pairs back. */
+int bdf_pairs_set_logistic_link(bdf_pairs *pairs);
+/* link 3 (counts): predictions are r exp(min(udot + base, 700)), the mean of the negative-binomial model with dispersion r, an
+ * integer >= 1 (BDF_ERR_ARG otherwise); at the same place as the other links (csrc/k_pg.hip).  bdf_pairs_lpd_update and
+ * bdf_pairs_waic_update refuse pairs with link 2 or 3 (BDF_ERR_ARG): these likelihoods are not scored yet. */
+int bdf_pairs_set_count_link(bdf_pairs *pairs, double r);
 /* out (dev, rows of F) = mean_value + F beta, beta dev numF: linear_values (macau.jl:91) / the baseline above */
 int bdf_feat_linear(bdf_ctx *ctx, const bdf_feat *F, const double *beta, double mean_value, double *out);
 /* sum over the pairs of (value - pred)^2, pred = udot + (linear_values[pair] if non-NULL else mean_value): err' err of
@@ -381,6 +391,38 @@ int bdf_robust_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *c
  * added in the same fixed order: sample_alpha's sum of squares for a relation with known weights (no draw). */
 int bdf_pairs_weighted_sse(bdf_ctx *ctx, const bdf_pairs *pairs, int D, const double *const *factors, double mean_value,
                            const double *weights, double *out);
+/* Polya-Gamma noise models (csrc/k_pg.hip, csrc/pg.h; Polson, Scott & Windle 2013): with psi_k = udot_k +
+ * mean_value a cell's likelihood is (e^psi)^a / (1 + e^psi)^b, and given omega_k ~ PG(b, psi_k) it is a Gaussian pseudo-observation
+ * kappa / omega_k of psi_k with precision omega_k, kappa = a - b / 2:
+ *   model 1, logit:   value_k in {0, 1}, P(1) = 1 / (1 + e^-psi);                      b = 1,           kappa = value_k - 1/2;
+ *   model 2, counts:  value_k = 0, 1, 2, ... negative binomial with mean r e^psi,      b = value_k + r, kappa = (value_k - r) / 2,
+ *                     pmf proportional to p^y (1 - p)^r at p = 1 / (1 + e^-psi); r an integer >= 1 (BDF_ERR_ARG otherwise).
+ * For observation k of `train` IN THE CALLER'S ORDER (the pairs may be stored sorted) at the context's sweep:
+ *   precision_out[k] = omega_k,  linear_out[k] = mean_value + value_k - kappa / omega_k
+ * (both dev, n) -- bdf_term.obs_precision and bdf_term.linear_values of the relation's terms, with alpha = 1: the rows are then
+ * sampled by the weighted row kernel unchanged.  omega_k is finite and strictly positive for every finite psi_k, and linear_out[k]
+ * is finite for every finite value_k.  The values are the caller's contract (the Python setters check them; this entry point does
+ * not read them on the host): for a value_k that is negative or no integer under model 2, b is held at 1 and its integer part taken,
+ * which keeps the outputs finite and means nothing.
+ * The stream: purpose BDF_P_PG, entity 0x800000 | rel_tag, row k; the cell takes its random numbers through ONE cursor over the
+ * stream's blocks pair = 0, 1, 2, ... (the pair index is 16 bits wide and wraps).  Every request takes one whole block (x, y, z, w),
+ * with U1 = u01(x, y) and U2 = u01(z, w) the block's two doubles:
+ *   a uniform:          U1                         an exponential:  -log U1
+ *   two exponentials:   -log U1, -log U2           a normal:        sqrt(-2 log U1) cos(2 pi U2)  (normal 2 pair of the stream)
+ * PG(1, c) = X / 4 with X ~ J*(1, z = |c| / 2) by Devroye's method, t = 0.64, K = pi^2 / 8 + z^2 / 2,
+ * p = pi / (2 K) e^(-K t), q = 2 e^-z [Phi((t z - 1) / sqrt t) + exp(2 z + log Phi(-(t z + 1) / sqrt t))].  A proposal takes a
+ * uniform u; u (p + q) < p: X = t + E / K (an exponential); else for t z < 1: two exponentials E, E' per candidate until
+ * E^2 <= 2 E' / t, X = t / (1 + t E)^2, kept when a uniform is at most e^(-z^2 X / 2); else per candidate a normal N, Y = N^2,
+ * X = mu + mu^2 Y / 2 - mu sqrt(4 mu Y + mu^2 Y^2) / 2 (mu = 1 / z), replaced by mu^2 / X when a uniform exceeds mu / (mu + X), until
+ * X <= t.  Then a uniform V, S = a_0(X), y = V S and the alternating series a_n(x) = pi (n + 1/2) (2 / (pi x))^(3/2)
+ * e^(-2 (n + 1/2)^2 / x) (x <= t), pi (n + 1/2) e^(-(n + 1/2)^2 pi^2 x / 2) (x > t): odd n subtracts a_n and accepts when y <= S, even n
+ * adds it and refuses the proposal when y > S.  PG(b, c), b <= 170: the sum of b such draws on the same cursor.  b > 170: ONE
+ * normal N, omega = max(m + sqrt(v) N, DBL_MIN) with PG(b, c)'s mean m = b / (2 c) tanh(c / 2) and variance v = b / (4 c^3)
+ * (sinh c - c) sech^2(c / 2) -- an approximation (as BayesLogit's hybrid sampler above the same b).
+ * The bounds: after 256 candidates of a truncated inverse Gaussian the last candidate stands, held at t; after 64 partial sums of
+ * the series the proposal is accepted; after 256 refused proposals the last proposal is returned.  factors as for bdf_predict. */
+int bdf_pg_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value, int model, double r,
+                uint32_t rel_tag, double *precision_out, double *linear_out);
 
 /* Ordinal probit noise model (csrc/k_ordinal.hip, csrc/ordinal.h): the training values of a relation are
  * levels 1 .. K (4 <= K <= 16), y = k iff e_{k-1} <= z < e_k for the latent z ~ N(udot + mean_value, 1 / alpha) of the interval
@@ -712,6 +754,14 @@ typedef struct {
      * probit, censor, interval, ordinal, feat or a communicator; needs train */
     double robust_nu;
     double *obs_precision;
+    /* Polya-Gamma noise models (a zeroed tail is "none"): pg_model 1 logit, 2 counts with the integer dispersion pg_r >= 1.
+     * bdf_pg_draw rewrites obs_precision (omega) and linear (mean + y - kappa / omega) where the probit draw runs, before the
+     * entities' rows, which read them with alpha = 1 (alpha_dev holds 1): the iteration is omega | U,V -> U | omega,V -> V | omega,U.
+     * Needs train, linear and obs_precision; not with probit, censor, interval, ordinal, robust_nu, alpha_sample, feat or a
+     * communicator */
+    int32_t pg_model;
+    int32_t _pad_pg;
+    double pg_r;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

@@ -491,6 +491,21 @@ function robust_draw!(c::Context, train::DevPairs, D, factors::Vector{<:DevArray
                 c.h, train.h, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, nu, rel_tag, precision_out.p,
                 wsse_out === nothing ? C_NULL : wsse_out.p))
 end
+"Polya-Gamma noise models (model 1: logit for 0/1 values; 2: negative-binomial counts with the integer dispersion r >= 1): for every
+observation of `train`, psi = udot + mean_value, omega ~ PG(b, psi) from ONE cursor over the blocks of the stream (18, 0x800000 |
+rel_tag, observation); precision_out = omega is what the rows take as Term.obs_precision, linear_out = mean_value + value - kappa /
+omega as Term.linear_values, with alpha = 1 (b = 1, kappa = value - 1/2; b = value + r, kappa = (value - r) / 2)"
+function pg_draw!(c::Context, train::DevPairs, D, factors::Vector{<:DevArray}, mean_value, model, r, rel_tag,
+                  precision_out::DevArray{Float64}, linear_out::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_pg_draw, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Cint, Float64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, train.h, D, fp, mean_value, model, r, rel_tag, precision_out.p, linear_out.p))
+end
+"predictions of the pairs become the logistic probability 1 / (1 + exp(-(udot + base))) (link 2)"
+pairs_set_logistic_link!(p::DevPairs) = check(ccall((:bdf_pairs_set_logistic_link, lib), Cint, (Ptr{Cvoid},), p.h))
+"predictions of the pairs become r exp(min(udot + base, 700)), the mean of the count model (link 3)"
+pairs_set_count_link!(p::DevPairs, r) = check(ccall((:bdf_pairs_set_count_link, lib), Cint, (Ptr{Cvoid}, Float64), p.h, r))
 "out (one device Float64) = sum over the pairs of weights[k] (value - mean_value - udot)^2, in a fixed order: sample_alpha!'s
 sum of squares for a relation with known observation weights"
 function pairs_weighted_sse!(c::Context, p::DevPairs, D, factors::Vector{<:DevArray}, mean_value, weights::DevArray{Float64},
@@ -664,6 +679,9 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     ordinal_codes::Ptr{Cvoid}                     # ... and device Int8 levels 1 .. K per observation of train
     robust_nu::Float64                            # robust (Student-t) noise model: its degrees of freedom >= 1 (0: off)
     obs_precision::Ptr{Cvoid}                     # device Float64 weight per observation of train: robust_draw!'s omega, or the caller's (C_NULL: none)
+    pg_model::Int32                               # Polya-Gamma noise model: 1 logit, 2 counts (0: none); pg_draw! rewrites obs_precision and linear
+    _pad_pg::Int32
+    pg_r::Float64                                 # ... the counts' integer dispersion r >= 1
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
