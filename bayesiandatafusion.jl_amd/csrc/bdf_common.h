@@ -283,22 +283,29 @@ __host__ __device__ __forceinline__ double bdf_u01(uint32_t lo, uint32_t hi)
     return ((double)(x >> 11) + 0.5) * 0x1.0p-53;
 }
 
+// How the polynomials below name their coefficients.  BdfLiteral: as literals.  A kernel that keeps many registers live around its
+// normals (k_rows_col.hip) passes a policy of its own that hands every coefficient over where it is used: literals of a loop's body
+// are otherwise materialised ONCE, in front of the loop, and held in vector registers across all of it.  The same operations on
+// the same values either way.
+struct BdfLiteral { static __device__ __forceinline__ double c(double x) { return x; } };
+
 // sin(2 pi u), cos(2 pi u) for u in (0, 1).  The argument is reduced in u, exactly: q = nearest integer to 4u, r = u - q/4
 // in [-1/8, 1/8]; then the fdlibm kernel polynomials on |2 pi r| <= pi/4 and the quadrant.  Within ~2e-16 of sin / cos of the
 // rounded product 2 pi u (the oracle's libm calls) at a seventh of the instructions: the library routines carry a
 // Payne-Hanek path and double-double arithmetic for arguments this code never sees, and Box-Muller was a quarter of the
 // row kernel's VALU instructions.
+template <class KC = BdfLiteral>
 __device__ __forceinline__ void bdf_sincos2pi(double u, double &s, double &c)
 {
     const double q = rint(4.0 * u);
-    const double x = 6.283185307179586476925286766559 * fma(q, -0.25, u);
+    const double x = KC::c(6.283185307179586476925286766559) * fma(q, -0.25, u);
     const double z = x * x;
-    const double ps = fma(z, fma(z, fma(z, fma(z, fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08),
-                                                   2.75573137070700676789e-06), -1.98412698298579493134e-04),
-                                     8.33333333332248946124e-03), -1.66666666666666324348e-01);
-    const double pc = fma(z, fma(z, fma(z, fma(z, fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09),
-                                                   -2.75573143513906633035e-07), 2.48015872894767294178e-05),
-                                     -1.38888888888741095749e-03), 4.16666666666666019037e-02);
+    const double ps = fma(z, fma(z, fma(z, fma(z, fma(z, KC::c(1.58969099521155010221e-10), KC::c(-2.50507602534068634195e-08)),
+                                                   KC::c(2.75573137070700676789e-06)), KC::c(-1.98412698298579493134e-04)),
+                                     KC::c(8.33333333332248946124e-03)), KC::c(-1.66666666666666324348e-01));
+    const double pc = fma(z, fma(z, fma(z, fma(z, fma(z, KC::c(-1.13596475577881948265e-11), KC::c(2.08757232129817482790e-09)),
+                                                   KC::c(-2.75573143513906633035e-07)), KC::c(2.48015872894767294178e-05)),
+                                     KC::c(-1.38888888888741095749e-03)), KC::c(4.16666666666666019037e-02));
     const double sx = fma(x * z, ps, x);
     const double cx = fma(z * z, pc, fma(z, -0.5, 1.0));
     const int iq = (int)q & 3;
@@ -309,18 +316,19 @@ __device__ __forceinline__ void bdf_sincos2pi(double u, double &s, double &c)
 
 // log(x) for a normal x in (0, 1) -- bdf_u01 never returns 0, 1 or a denormal: the fdlibm algorithm (x = 2^k m, m in
 // [sqrt(2)/2, sqrt(2)), log m from s = f / (2 + f), f = m - 1), < 1 ulp, without the library routine's special cases
+template <class KC = BdfLiteral>
 __device__ __forceinline__ double bdf_log01(double x)
 {
     int k;
     double m = frexp(x, &k);                        // m in [0.5, 1)
-    if (m < 0.70710678118654752440) { m *= 2.0; k -= 1; }
+    if (m < KC::c(0.70710678118654752440)) { m *= 2.0; k -= 1; }
     const double f = m - 1.0, dk = (double)k;
     const double s = f / (2.0 + f), z = s * s, w = z * z;
-    const double t1 = w * fma(w, fma(w, 1.531383769920937332e-01, 2.222219843214978396e-01), 3.999999999940941908e-01);
-    const double t2 = z * fma(w, fma(w, fma(w, 1.479819860511658591e-01, 1.818357216161805012e-01), 2.857142874366239149e-01),
-                              6.666666666666735130e-01);
+    const double t1 = w * fma(w, fma(w, KC::c(1.531383769920937332e-01), KC::c(2.222219843214978396e-01)), KC::c(3.999999999940941908e-01));
+    const double t2 = z * fma(w, fma(w, fma(w, KC::c(1.479819860511658591e-01), KC::c(1.818357216161805012e-01)), KC::c(2.857142874366239149e-01)),
+                              KC::c(6.666666666666735130e-01));
     const double R = t2 + t1, hfsq = 0.5 * f * f;
-    return dk * 6.93147180369123816490e-01 - ((hfsq - fma(s, hfsq + R, dk * 1.90821492927058770002e-10)) - f);
+    return dk * KC::c(6.93147180369123816490e-01) - ((hfsq - fma(s, hfsq + R, dk * KC::c(1.90821492927058770002e-10))) - f);
 }
 
 // standard normal number `n` (0-based) of stream (purpose, entity, row): pair n/2, element n%2
@@ -336,14 +344,15 @@ __device__ __forceinline__ double bdf_normal(uint64_t seed, uint32_t sweep, uint
 }
 
 // both normals of pair `pair` of the stream: numbers 2 pair and 2 pair + 1 (the same values bdf_normal returns)
+template <class KC = BdfLiteral>
 __device__ __forceinline__ void bdf_normal_pair(uint64_t seed, uint32_t sweep, uint32_t purpose, uint32_t entity,
                                        uint64_t row, uint32_t pair, double &z0, double &z1)
 {
     u32x4 o = bdf_draw(seed, sweep, purpose, entity, row, pair);
     double u1 = bdf_u01(o.x, o.y), u2 = bdf_u01(o.z, o.w);
-    double r = sqrt(-2.0 * bdf_log01(u1));
+    double r = sqrt(-2.0 * bdf_log01<KC>(u1));
     double s, c;
-    bdf_sincos2pi(u2, s, c);
+    bdf_sincos2pi<KC>(u2, s, c);
     z0 = r * c;
     z1 = r * s;
 }
@@ -399,6 +408,9 @@ __device__ __forceinline__ double readlane_f64(double v, int lane)   // lane mus
 #define BDF_DONE_STRIDE 16         // words between two shards
 
 int bdf_predict_plain(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, double *out);
+// bdf_predict_update for pairs stored sorted, two modes, D a multiple of 4 up to 32, no baseline (k_update_runs.hip): phase 0..2
+int bdf_update_runs(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, int phase, double count,
+                    double clamp_lo, double clamp_hi, double class_cut, double *stats_out);
 // bdf_predict / bdf_predict_update / bdf_predict_sse for pairs with the probit link (k_probit.hip): phase -1 predict only (out),
 // 0..2 the update (count: the pairs' counter before it), 3 statistics only; linear (nullable) overrides the pairs' baseline
 int bdf_predict_link(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const *factors, double mean_value, const double *linear,

@@ -331,7 +331,11 @@ extern "C" int bdf_predict_update(bdf_ctx *ctx, bdf_pairs *p, int D, const doubl
     BDF_REQUIRE(phase >= 0 && phase <= 2, BDF_ERR_ARG, "bdf_predict_update: phase must be 0, 1 or 2");
     a.mean = mean_value; a.avg = p->avg_dev; a.sq = p->sq_dev; a.phase = phase; a.count = p->count;
     a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi; a.cut = class_cut; a.stats = stats_out;
+    // (sorted pairs of a two-mode relation without a per-pair baseline -- the sweep's test set: the kernel that fits beside the row
+    // kernel's waves, k_update_runs.hip; the same values as k_predict_runs, which keeps the predictions and the baselines)
+    const bool runs = a.sorted_mode >= 0 && a.n_modes == 2 && (a.D & 3) == 0 && a.D <= 32 && a.linear == nullptr;
     rc = p->link ? bdf_predict_link(ctx, p, D, factors, mean_value, nullptr, nullptr, phase, p->count, clamp_lo, clamp_hi, class_cut, stats_out)
+         : runs  ? bdf_update_runs(ctx, p, D, factors, mean_value, phase, p->count, clamp_lo, clamp_hi, class_cut, stats_out)
                  : launch_predict(ctx, a);
     if (rc) return rc;
     if (phase == 1) p->count = 1.0;

@@ -35,6 +35,10 @@
 #ifndef BDF_COL_WAVES
 #define BDF_COL_WAVES 2            // waves per SIMD the kernel is compiled for (<= 256 registers)
 #endif
+// The register budget: 208 of a SIMD lane's 512, so that two row waves leave 96 for a wave of the prediction update running beside
+// them (k_update_runs.hip).  amdgpu_num_vgpr counts in HALVES of the unified file on gfx90a and later -- the
+// compiler doubles what it is given -- so 104 stands for 208; tests/test_fit_registers.py holds the sum to 512.
+#define COL_VGPR_HALF 104
 #define COL_PSZ 800                // doubles per partial slot: 50 entries (A0[0..32], A1[16..32]) x 16 lanes
 
 #ifdef BDF_K1_STAMPS      // diagnostic build: per wave {start, end, rounds, cycles by phase summed over the wave's rounds} (s_memtime; bdf_debug_stamps)
@@ -46,6 +50,10 @@
 #endif
 
 namespace {
+
+// a coefficient of the normals' polynomials through a scalar register pair where it is used (bdf_common.h, BdfLiteral): as literals
+// the compiler set fifteen of them up in front of the round loop and held them in thirty vector registers across the whole round
+struct ColCoef { static __device__ __forceinline__ double c(double x) { asm volatile("" : "+s"(x)); return x; } };
 
 // K: the observation's position in its chunk of 16 (lane K of the lane row holds its value minus the mean)
 template <int DR, int K>
@@ -149,7 +157,7 @@ __device__ __forceinline__ void col_prior_lds(double (&A)[33], const double *img
 }
 
 template <int DR, bool FULL>
-__global__ __launch_bounds__(64, BDF_COL_WAVES) void k_rows_col(SampleArgs a_in, ColPlanDev p_in, uint32_t fac_bytes)
+__global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(COL_VGPR_HALF))) void k_rows_col(SampleArgs a_in, ColPlanDev p_in, uint32_t fac_bytes)
 {
     __shared__ __attribute__((aligned(16))) double lds[4 * 272 + 768];      // block (1,0) of the four systems on its way to block (0,1) | the prior's image
     const int w = blockIdx.x;
@@ -302,7 +310,7 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) void k_rows_col(SampleArgs a_in,
         double z0 = 0.0, z1 = 0.0;
         {
             double ze = 0.0, zo = 0.0;
-            if (live && 2 * j < D) bdf_normal_pair(a.seed, a.sweep, BDF_P_ROW, a.entity_tag, (uint64_t)(uint32_t)jb.orig, (uint32_t)j, ze, zo);
+            if (live && 2 * j < D) bdf_normal_pair<ColCoef>(a.seed, a.sweep, BDF_P_ROW, a.entity_tag, (uint64_t)(uint32_t)jb.orig, (uint32_t)j, ze, zo);
             const int base = lane & 48;
             const double ze0 = __shfl(ze, base + (n0 >> 1)), zo0 = __shfl(zo, base + (n0 >> 1));
             const double ze1 = __shfl(ze, base + (n1 >> 1)), zo1 = __shfl(zo, base + (n1 >> 1));
