@@ -4,7 +4,7 @@
 16 / 17, entity 0x800000 | rel_tag, row = observation, pair = attempt), one variate at a time on oracle.draw and oracle.normals;
 `gamma_variates` the same for many (sweep, row) at once on the vectorised Philox of probit_restatement (held against gamma_mt in
 test_robust_host.py).  `draw_omega` is the conditional draw, `row_system` / `sample_row` / `sample_rows` the weighted row system in
-numpy and the reference's map from the row's normals to the sample (chol(inv(P))' z + inv(P) b), and `run_chain(...)` whole macau()
+numpy (any number of modes; `row_system_terms`: several relations sharing the sampled entity, weighted or not) and the reference's map from the row's normals to the sample (chol(inv(P))' z + inv(P) b), and `run_chain(...)` whole macau()
 iterations in the library's order -- omega | U,V,alpha -> alpha | U,V,omega -> rows, hyperprior of every entity in turn -> beta of
 every entity with features -- with the hyperprior, beta and alpha taken from the oracle.
 """
@@ -112,6 +112,19 @@ def row_system(ids, values, weights, mode, row, alpha, base, S, mu_i, Lam):
     res = np.asarray(values, dtype=np.float64)[sel] - np.broadcast_to(np.asarray(base, dtype=np.float64), (len(values),))[sel]
     P = Lam + alpha * (w * om[:, None]).T @ w
     b = Lam @ mu_i + alpha * (w.T @ (om * res))
+    return P, b
+
+
+def row_system_terms(terms, row, mu_i, Lam):
+    """the row system of an entity that several relations share: P = Lam + sum_t alpha_t sum_k omega_k w w', b = Lam mu_i +
+    sum_t alpha_t sum_k omega_k (y - base) w; terms: one (ids, values, weights, mode, alpha, base, S) per relation, weights None
+    for a relation without them (omega = 1), the rest as row_system takes them (held against the oracle in test_robust_host.py)"""
+    D = len(mu_i)
+    P, b = np.array(Lam, dtype=np.float64), Lam @ mu_i
+    for ids, values, weights, mode, alpha, base, S in terms:
+        om = np.ones(len(values)) if weights is None else weights
+        Pt, bt = row_system(ids, values, om, mode, row, alpha, base, S, np.zeros(D), np.zeros((D, D)))
+        P, b = P + Pt, b + bt
     return P, b
 
 

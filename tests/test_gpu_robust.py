@@ -1,5 +1,6 @@
 """The robust (Student-t) noise model and observation weights on the GPU: the weighted row system of
-k_rows_w against numpy, unit weights against the unweighted general path bit for bit, bdf_robust_draw and bdf_pairs_weighted_sse
+k_rows_w against numpy (two, three and four modes; row lengths on the software pipeline's trip boundaries; weights together with
+linear_values; launches that mix a weighted and an unweighted relation), unit weights against the unweighted general path bit for bit, bdf_robust_draw and bdf_pairs_weighted_sse
 against the restatement (tests/robust_restatement.py), whole macau() iterations against the restated chain on both iteration
 paths, the Gaussian chain untouched by a robust engine in the same process, planted outliers, and the errors of the C ABI."""
 import ctypes as C
@@ -28,24 +29,30 @@ def _facs(ts):
     return (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
-def _term(dr, mode0, alpha, mean, facs, lin=None, weights=None):
+def _terms(*rels):
+    """rels: (DeviceRelation, mode0, alpha, mean, [factor tensors], linear tensor | None, weight tensor | None) per relation"""
     from bdf_amd._lib import Term
-    terms = (Term * 1)()
-    terms[0].rel, terms[0].mode, terms[0].alpha, terms[0].mean_value = dr.handle, mode0, alpha, mean
-    terms[0].linear_values = lin.data_ptr() if lin is not None else None
-    terms[0].obs_precision = weights.data_ptr() if weights is not None else None
-    for k, f in enumerate(facs):
-        terms[0].factors[k] = f.data_ptr() if f is not None else None
+    terms = (Term * len(rels))()
+    for t, (dr, mode0, alpha, mean, facs, lin, weights) in enumerate(rels):
+        terms[t].rel, terms[t].mode, terms[t].alpha, terms[t].mean_value = dr.handle, mode0, alpha, mean
+        terms[t].linear_values = lin.data_ptr() if lin is not None else None
+        terms[t].obs_precision = weights.data_ptr() if weights is not None else None
+        for k, f in enumerate(facs):
+            terms[t].factors[k] = f.data_ptr() if f is not None else None
     return terms
+
+
+def _term(dr, mode0, alpha, mean, facs, lin=None, weights=None):
+    return _terms((dr, mode0, alpha, mean, facs, lin, weights))
 
 
 # ---- (a) the weighted row system ---------------------------------------------------------------------------------------------
 def _system_problem(rng, n_modes, D):
-    """N = 40 rows, other modes 23 (and 11), n = 1003 observations; row 2 has no observation, row 5 holds 300; weights log-uniform
+    """N = 40 rows, other modes 23 (and 11, and 7), n = 1003 observations; row 2 has no observation, row 5 holds 300; weights log-uniform
     on 1e-3 .. 1e3 with both ends present.  Factor entries are N(0, 0.3^2): with weights up to 1e3 the off-diagonal entries
     of P then stay of the size (tens to hundreds; the diagonal of the long row reaches a few thousand and is held by the relative
     part) at which the absolute tolerance of tests/test_gpu_rows.py, 1e-12, was set for unit weights."""
-    dims = [40, 23, 11][:n_modes]
+    dims = [40, 23, 11, 7][:n_modes]
     n = 1003
     ids = np.stack([rng.integers(1, d + 1, n) for d in dims], axis=1).astype(np.int64)
     ids[ids[:, 0] == 3, 0] = 4
@@ -59,12 +66,13 @@ def _system_problem(rng, n_modes, D):
     return dims, ids, vals, w, facs, Lam
 
 
-@pytest.mark.parametrize("n_modes", [2, 3])
+@pytest.mark.parametrize("n_modes", [2, 3, 4])
 @pytest.mark.parametrize("D", [5, 16, 17, 32, 33, 64])
 def test_weighted_row_system_and_draw(B, O, D, n_modes):
     """bdf_row_system and bdf_sample_rows with obs_precision against numpy, at the tolerances tests/test_gpu_rows.py holds them to
     (1e-12 for the system, 1e-8 / 1e-9 for the sample); item size 64: the row of 300 observations is split over several items.
-    A shared prior mean, and (every D, two modes) a prior mean per row."""
+    A shared prior mean, and (every D, two modes) a prior mean per row.  Four modes: accumulate_reg<DP, 3, true>, one k-step per
+    trip."""
     from bdf_amd._lib import check, lib
     rng = np.random.default_rng(500 + 10 * D + n_modes)
     dims, ids, vals, w, facs, Lam = _system_problem(rng, n_modes, D)
@@ -103,6 +111,146 @@ def test_weighted_row_system_and_draw(B, O, D, n_modes):
     assert disp["k1"] == runs * N and disp["k1_items"] > runs * N and c2.rows_unfinished() == 0, disp      # K1 alone, the long row in pieces
     print(f"weighted row system D={D} modes={n_modes}: max |P_dev - P_numpy| = {worst:.3e}, largest |P| = {np.abs(P).max():.1f}")
     dr.close()
+    c2.close()
+
+
+def _weights(rng, n):
+    """log-uniform on 1e-3 .. 1e3 with both ends present"""
+    w = np.exp(rng.uniform(np.log(1e-3), np.log(1e3), n))
+    w[0], w[1] = 1e-3, 1e3
+    return w
+
+
+def _prior(rng, D):
+    A = rng.standard_normal((D, D))
+    return A @ A.T / D + np.eye(D), rng.standard_normal(D)
+
+
+def _check_rows(O, c2, D, N, terms, system_of, mu, Lam, tag, sweep, what):
+    """bdf_row_system at rtol = atol = 1e-12 and bdf_sample_rows at rtol 1e-8 / atol 1e-9 (test_weighted_row_system_and_draw's
+    bounds) against system_of(row) -> (P, b) in numpy; the launch went whole to K1.  Returns the sampled rows."""
+    from bdf_amd._lib import check, lib
+    mu_t, Lam_t = c2.tensor(mu), c2.tensor(Lam)
+    P_t, b_t, out_t = c2.zeros(N, D, D), c2.zeros(N, D), c2.tensor(np.full((N, D), np.nan))
+    check(lib().bdf_row_system(c2.handle, D, N, len(terms), terms, _p(mu_t), 0, _p(Lam_t), _p(P_t), _p(b_t)))
+    c2.set_sweep(sweep)
+    check(lib().bdf_sample_rows(c2.handle, D, N, len(terms), terms, _p(mu_t), 0, _p(Lam_t), tag, 0, 1, _p(out_t), None))
+    c2.sync()
+    P, b, out = P_t.cpu().numpy(), b_t.cpu().numpy(), out_t.cpu().numpy()
+    worst = 0.0
+    for row in range(N):
+        Pe, be = system_of(row)
+        worst = max(worst, np.abs(P[row].T - Pe).max())
+        np.testing.assert_allclose(P[row].T, Pe, rtol=1e-12, atol=1e-12, err_msg="P of row %d" % row)
+        np.testing.assert_allclose(b[row], be, rtol=1e-12, atol=1e-12, err_msg="b of row %d" % row)
+        xe = RR.sample_row(Pe, be, O.normals(SEED, sweep, 1, tag, row, D))
+        np.testing.assert_allclose(out[row], xe, rtol=1e-8, atol=1e-9, err_msg="sample of row %d" % row)
+    disp = c2.rows_dispatch(tag)
+    assert disp["k1"] == N and disp["lowrank"] == disp["small"] == disp["col"] == 0 and c2.rows_unfinished() == 0, disp
+    print(f"{what}: max |P_dev - P_numpy| = {worst:.3e}, largest |P| = {np.abs(P).max():.1f}, dispatch {disp}")
+    return out, disp
+
+
+TRIP_COUNTS = (0, 1, 3, 4, 5, 7, 8, 9, 15, 16, 17, 24, 25, 300)
+
+
+@pytest.mark.parametrize("n_modes", [2, 3, 4])
+@pytest.mark.parametrize("D", [16, 64])
+def test_weighted_rows_on_the_trip_boundaries(B, O, D, n_modes):
+    """row r has exactly TRIP_COUNTS[r] observations.  accumulate_reg's software pipeline takes 4 KS observations per trip and loads
+    ids, residuals and sqrt(omega) two trips ahead: KS = 2 for one and for two other modes (trips of 8: no trip, a partial one,
+    one short of / exactly / one past one, two and three trips), KS = 1 for three (trips of 4: the same around 1, 2, 4 and 6
+    trips).  Item size 64: the row of 300 is cut into pieces, the last one partial."""
+    rng = np.random.default_rng(700 + 10 * D + n_modes)
+    N = len(TRIP_COUNTS)
+    dims = [N, 23, 11, 7][:n_modes]
+    rows = rng.permutation(np.repeat(np.arange(1, N + 1), TRIP_COUNTS))
+    n = len(rows)
+    ids = np.stack([rows] + [rng.integers(1, d + 1, n) for d in dims[1:]], axis=1).astype(np.int64)
+    assert tuple(np.bincount(ids[:, 0] - 1, minlength=N)) == TRIP_COUNTS
+    vals, w = rng.standard_normal(n), _weights(rng, n)
+    facs = [0.3 * rng.standard_normal((d, D)) for d in dims]
+    Lam, mu = _prior(rng, D)
+    c2 = B.Context(seed=SEED)
+    c2.set_item_size(64)
+    dr = B.DeviceRelation(c2, B.IndexedDF((ids, vals), dims))
+    ft = [None] + [c2.tensor(f) for f in facs[1:]]
+    wt = c2.tensor(w)
+    terms = _term(dr, 0, 1.7, 0.25, ft, weights=wt)
+    out, disp = _check_rows(O, c2, D, N, terms, lambda row: RR.row_system(ids, vals, w, 0, row, 1.7, 0.25, facs, mu, Lam), mu, Lam, 12, 5,
+                            f"trip boundaries D={D} modes={n_modes}")
+    assert disp["k1_items"] > N, disp                                 # the row of 300 in pieces
+    dr.close()
+    c2.close()
+
+
+@pytest.mark.parametrize("n_modes", [2, 3])
+@pytest.mark.parametrize("D", [10, 64])
+def test_weights_together_with_linear_values(B, O, D, n_modes):
+    """one term that carries obs_precision and linear_values, a baseline per observation drawn N(0, 1): what every Polya-Gamma
+    iteration launches"""
+    rng = np.random.default_rng(800 + 10 * D + n_modes)
+    dims, ids, vals, w, facs, Lam = _system_problem(rng, n_modes, D)
+    base, mu = rng.standard_normal(len(vals)), rng.standard_normal(D)
+    c2 = B.Context(seed=SEED)
+    c2.set_item_size(64)
+    dr = B.DeviceRelation(c2, B.IndexedDF((ids, vals), dims))
+    ft = [None] + [c2.tensor(f) for f in facs[1:]]
+    lin_t, wt = c2.tensor(base), c2.tensor(w)
+    terms = _term(dr, 0, 1.7, 123.0, ft, lin=lin_t, weights=wt)                             # (with linear_values the mean is a decoy)
+    _check_rows(O, c2, D, dims[0], terms, lambda row: RR.row_system(ids, vals, w, 0, row, 1.7, base, facs, mu, Lam), mu, Lam, 13, 6,
+                f"weights and linear_values D={D} modes={n_modes}")
+    dr.close()
+    c2.close()
+
+
+@pytest.mark.parametrize("D", [12, 64])
+def test_launches_that_mix_a_weighted_and_an_unweighted_relation(B, O, D):
+    """the sampled entity shares a three-mode relation A and a two-mode relation B (test_rows_tensor_multi_relation_mu_matrix_linear's
+    shapes): (i) A weighted, B unweighted with linear_values; (ii) A unweighted, B weighted and with linear_values -- launch_kind
+    sends the whole launch to k_rows_w, where the term without weights takes s = 1 -- against the sum of the two terms' numpy
+    systems.  Then (i) with unit weights: bit for bit the two-term launch without weights on the general gather (A forced onto it
+    by linear_values = its mean)."""
+    from bdf_amd._lib import check, lib
+    rng = np.random.default_rng(950 + D)
+    N = 23
+    dimsA, dimsB, nA, nB = [N, 9, 6], [N, 14], 700, 300
+    idsA = np.stack([rng.integers(1, d + 1, nA) for d in dimsA], axis=1).astype(np.int64)
+    idsB = np.stack([rng.integers(1, d + 1, nB) for d in dimsB], axis=1).astype(np.int64)
+    idsA[idsA[:, 0] == 2, 0] = 1
+    idsB[idsB[:, 0] == 2, 0] = 1                                      # row 2: no observation in either relation
+    idsB[idsB[:, 0] == 5, 0] = 4                                      # row 5: observations in A alone
+    valsA, valsB = rng.standard_normal(nA), rng.standard_normal(nB)
+    SA = [0.3 * rng.standard_normal((d, D)) for d in dimsA]
+    SB = [SA[0], 0.3 * rng.standard_normal((dimsB[1], D))]
+    wA, wB, linB = _weights(rng, nA), _weights(rng, nB), rng.standard_normal(nB)
+    Lam, mu = _prior(rng, D)
+    aA, mA, aB, mB = 2.0, 0.1, 0.7, -0.3
+    c2 = B.Context(seed=SEED)
+    c2.set_item_size(64)
+    drA, drB = B.DeviceRelation(c2, B.IndexedDF((idsA, valsA), dimsA)), B.DeviceRelation(c2, B.IndexedDF((idsB, valsB), dimsB))
+    fA, fB = [None, c2.tensor(SA[1]), c2.tensor(SA[2])], [None, c2.tensor(SB[1])]
+    lin_t = c2.tensor(linB)
+    for tag, (omA, omB) in ((21, (wA, None)), (22, (None, wB))):
+        wA_t, wB_t = (c2.tensor(om) if om is not None else None for om in (omA, omB))
+        terms = _terms((drA, 0, aA, mA, fA, None, wA_t), (drB, 0, aB, mB, fB, lin_t, wB_t))
+        ref = [(idsA, valsA, omA, 0, aA, mA, SA), (idsB, valsB, omB, 0, aB, linB, SB)]
+        _check_rows(O, c2, D, N, terms, lambda row: RR.row_system_terms(ref, row, mu, Lam), mu, Lam, tag, 7,
+                    f"mixed launch D={D} weighted={'A' if omA is not None else 'B'}")
+    # unit weights on A are no weights
+    mu_t, Lam_t = c2.tensor(mu), c2.tensor(Lam)
+    outs = []
+    for termA in ((drA, 0, aA, mA, fA, None, c2.tensor(np.ones(nA))), (drA, 0, aA, mA, fA, c2.tensor(np.full(nA, mA)), None)):
+        terms = _terms(termA, (drB, 0, aB, mB, fB, lin_t, None))
+        out_t = c2.tensor(np.full((N, D), np.nan))
+        c2.set_sweep(8)
+        check(lib().bdf_sample_rows(c2.handle, D, N, 2, terms, _p(mu_t), 0, _p(Lam_t), 23, 0, 1, _p(out_t), None))
+        c2.sync()
+        outs.append(out_t.cpu().numpy())
+    disp = c2.rows_dispatch(23)                                       # (the two launches of one iteration number add up)
+    assert disp["k1"] == 2 * N and disp["lowrank"] == disp["small"] == disp["col"] == 0, disp
+    assert np.all(np.isfinite(outs[0])) and np.array_equal(outs[0], outs[1])
+    drA.close(); drB.close()
     c2.close()
 
 

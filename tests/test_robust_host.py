@@ -284,6 +284,52 @@ def test_unit_weights_are_the_oracles_rows(O):
     np.testing.assert_allclose(got, want, rtol=1e-9, atol=1e-11)
 
 
+def test_unit_weight_forms_are_the_oracles_row_system(O):
+    """what the GPU tests of k_rows_w take as their reference beyond one two- or three-mode term -- row_system on a four-mode
+    relation, with a baseline per observation, and row_system_terms over a three-mode and a two-mode relation that share the
+    entity -- against oracle.row_system with unit weights, at 1e-13 of the largest entry"""
+    rng = np.random.default_rng(31)
+    D = 6
+    A = rng.standard_normal((D, D))
+    Lam, mu = A @ A.T / D + np.eye(D), rng.standard_normal(D)
+
+    def relation(dims, n):
+        ids = np.stack([rng.integers(1, d + 1, n) for d in dims], axis=1)
+        return ids, rng.standard_normal(n), [rng.standard_normal((d, D)) for d in dims]
+
+    def close(got, want):
+        for g, w in zip(got, want):
+            assert np.abs(g - w).max() <= 1e-13 * max(np.abs(w).max(), 1.0)
+
+    dims4 = [9, 7, 5, 4]
+    ids4, y4, S4 = relation(dims4, 200)
+    lin4 = rng.standard_normal(200)
+    for mode in range(4):
+        facs = [None if k == mode else S4[k] for k in range(4)]
+        for lin in (None, lin4):
+            term = O.Term(ids4, y4, dims4, mode, 1.7, 0.25, facs, linear_values=lin)
+            for row in range(dims4[mode]):
+                got = RR.row_system(ids4, y4, np.ones(200), mode, row, 1.7, 0.25 if lin is None else lin, S4, mu, Lam)
+                close(got, O.row_system(D, [term], row, mu, Lam))
+    dimsA, dimsB = [9, 7, 5], [9, 8]
+    idsA, yA, SA = relation(dimsA, 150)
+    idsB, yB, SB = relation(dimsB, 90)
+    SB[0] = SA[0]
+    linB = rng.standard_normal(90)
+    tA = O.Term(idsA, yA, dimsA, 0, 2.0, 0.1, [None, SA[1], SA[2]])
+    tB = O.Term(idsB, yB, dimsB, 0, 0.7, -0.3, [None, SB[1]], linear_values=linB)
+    for wA, wB in ((None, None), (np.ones(150), None), (None, np.ones(90))):
+        for row in range(9):
+            got = RR.row_system_terms([(idsA, yA, wA, 0, 2.0, 0.1, SA), (idsB, yB, wB, 0, 0.7, linB, SB)], row, mu, Lam)
+            close(got, O.row_system(D, [tA, tB], row, mu, Lam))
+    # and the weights of one term leave the other term's part alone
+    w = np.exp(rng.uniform(-3.0, 3.0, 150))
+    P1, b1 = RR.row_system_terms([(idsA, yA, w, 0, 2.0, 0.1, SA), (idsB, yB, None, 0, 0.7, linB, SB)], 0, mu, Lam)
+    PA, bA = RR.row_system(idsA, yA, w, 0, 0, 2.0, 0.1, SA, mu, Lam)
+    PB, bB = RR.row_system(idsB, yB, np.ones(90), 0, 0, 0.7, linB, SB, np.zeros(D), np.zeros((D, D)))
+    close((P1, b1), (PA + PB, bA + bB))
+
+
 # ---- the build's listings ---------------------------------------------------------------------------------------------------
 def test_weighted_row_kernels_use_no_scratch():
     rows = {k: v for k, v in _resources("k_sample_rows").items() if "k_rows_w" in k}
