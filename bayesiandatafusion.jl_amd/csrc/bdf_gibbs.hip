@@ -24,6 +24,7 @@
 
 struct bdf_gibbs {
     bdf_ctx *rows, *hyper, *pred;        // rows: the caller's context; hyper / pred: owned (own streams)
+    bdf_ctx *gate = nullptr;             // owned, with polling: a second stream on the reserved CUs for the one-wave gate in front of the prediction update
     int D;
     struct Ent {
         bdf_gibbs_entity d;
@@ -90,6 +91,22 @@ __global__ void k_wait_flag(const uint32_t *flag, long long max_ticks, uint32_t 
     }
 }
 __global__ void k_set_flag(uint32_t *flag) { __hip_atomic_store(flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); }
+
+// The gate in front of the prediction update: one wave that returns when the 64 done counters of a row launch (SampleArgs::done)
+// sum to `target`, as k_hyper_chain's partial-sum workgroups wait (k_hyper.hip) -- every row of the launch is in memory then.  The
+// event on ITS dispatch is what the prediction stream waits for, so that nothing rides on the row launch.  Bounded like the chain's.
+__global__ __launch_bounds__(64) void k_rows_gate(const uint32_t *done, uint32_t target, int *flag)
+{
+    int spins = 0;
+    for (;;) {
+        uint32_t v = __hip_atomic_load(done + BDF_DONE_STRIDE * threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+        if ((int32_t)(v - target) >= 0) break;
+        __builtin_amdgcn_s_sleep(8);
+        if (++spins > (1 << 22)) { if (threadIdx.x == 0) atomicOr_system(flag, 16); break; }      // bounded: a bug must not hang the device
+    }
+}
 
 int streams_concurrent(hipStream_t a, hipStream_t b, bool *yes)
 {
@@ -262,6 +279,9 @@ extern "C" int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const 
         if ((rc = streams_concurrent(rows_ctx->stream, g->hyper->stream, &conc))) { bdf_gibbs_destroy(g); return rc; }
         g->polling = conc;              // kernels of the two streams do not run side by side here (a profiler serialising them): events
     }
+    // (the gate's stream: on the reserved CUs like the chain's, so that its wave never takes a row slot; beside the other three if it can)
+    if (g->polling && (rc = make_side_ctx(rows_ctx, {g->hyper, g->pred}, true, &g->gate))) { bdf_gibbs_destroy(g); return rc; }
+    if (g->polling && !g->gate) g->polling = false;         // (no stream left for it: events everywhere, as without reserved CUs)
     g->debug = getenv("BDF_DEBUG") != nullptr;
     if (g->debug)
         fprintf(stderr, "[bdf_gibbs] reserve_cus=%d hyperprior stream on reserved CUs=%d polling=%d\n", rows_ctx->reserve_cus,
@@ -310,6 +330,7 @@ extern "C" int bdf_gibbs_destroy(bdf_gibbs *g)
         if (g->ev_pred[k]) (void)hipEventDestroy(g->ev_pred[k]);
     if (g->ready_dev) (void)hipFree(g->ready_dev);
     if (g->rel_sse) (void)hipFree(g->rel_sse);
+    if (g->gate) { (void)hipStreamSynchronize(g->gate->stream); bdf_ctx_destroy(g->gate); }
     if (g->pred) bdf_ctx_destroy(g->pred);
     if (g->hyper) bdf_ctx_destroy(g->hyper);
     delete g;
@@ -760,13 +781,20 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // row kernels poll for the draw), the chain is enqueued AT ONCE instead and its partial-sum workgroups poll a counter
         // the row waves add to when their rows are in memory (SampleArgs::done; k_rows_col only -- a launch that takes another
         // kernel reports -1 and gets the event).  No cycle: the rows of iteration t poll for the draw of t - 1, enqueued before.
+        // The last entity's launch is no exception when the prediction update follows it: nothing rides on its dispatch either.  (It
+        // carried `done` for the prediction stream to wait on, the one event left on the row stream: the next iteration's first row
+        // launch followed it after ~5 us in the kernel trace where the other launches follow each other after 0.)  The prediction
+        // stream waits for a one-wave gate on the reserved CUs instead, see below.
+        // Every other path -- a communicator, side information, chunks, a caller's timing events (E.t_stop), no polling, chains of
+        // several launches: `counter` false; a launch that took another kernel: rows_done_added < 0 -- has `done` as before, on the
+        // dispatch or recorded right behind it, for the chain and the prediction stream alike.
         const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && nch == 1 && !E.t_stop;
         const bool pred_waits = j == n - 1 && g->test && predict_phase >= 0;
         bool by_counter = false;
         for (int c = 0; c < nch; c++) {
             R->time_start = (c == 0) ? E.t_start : nullptr;
             R->rows_span = E.span;
-            R->time_stop = (c == nch - 1 && !g->comm && !(counter && !pred_waits)) ? done : nullptr;
+            R->time_stop = (c == nch - 1 && !g->comm && !counter) ? done : nullptr;
             if (poll) { R->rows_ready = g->ready_dev + j; R->rows_ready_want = E.epoch; }
             if (counter) R->rows_done = E.done_dev;
             if ((rc = bdf_sample_rows(R, D, e.N, e.n_terms, terms, e.feat ? e.mu_matrix : e.mu, e.feat ? 1 : 0, e.Lambda, e.tag, c, nch,
@@ -778,7 +806,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         if (g->comm) {
             if ((rc = bdf_allgather_join(R, g->comm))) return rc;       // the row stream continues after the last chunk's exchange
             BDF_HIP(hipEventRecord(done, R->stream));
-        } else if (counter && !pred_waits && !by_counter) {
+        } else if (counter && !by_counter) {
             BDF_HIP(hipEventRecord(done, R->stream));                   // (the launch took another kernel: the event after all)
         }
         E.t_start = E.t_stop = nullptr;
@@ -805,7 +833,23 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         if ((rc = bdf_hyper_sample(H, D, e.n_real, e.sumU, e.UUt, e.mu0, e.b0, Tinv, hyper_nu(e), e.tag, e.mu, e.Lambda, e.params, e.prior_pack, e.draws)))
             return rc;
         E.hyper_recorded = true;
-        if (j == n - 1 && g->test && predict_phase >= 0) BDF_HIP(hipStreamWaitEvent(P->stream, done, 0));
+        // The prediction update reads every entity's rows of this iteration.  Hand-over by counter: a one-wave gate (k_rows_gate) on
+        // a stream of the reserved CUs polls this launch's done counters, and the prediction stream waits for the event on the
+        // GATE's dispatch (ev_rows, which nothing else uses on this path).  That orders the update behind all the rows:
+        //   * the gate returns only after the done counters say every row of this launch is in memory;
+        //   * the earlier entities' launches of this iteration are ahead of this one on the in-order row stream (and this launch
+        //     gathers their rows): complete before its first wave started.
+        // No cycle: the gate is enqueued BEHIND the launch it waits for and waits for nothing else; should its stream share a hardware
+        // queue with another one, it runs late, never early.  Rows still wait for the prediction stream nowhere on the device.
+        // (Waiting for ev_hyper of this entity's chain instead -- no kernel, the same order -- starts the update ~28 us after the
+        // rows instead of at their end, where it stretches BOTH row launches it then meets: 11.2-11.4 k sweeps/s against the
+        // event's 12.2-12.4 k, profiles/r08_update_handover.txt.)
+        if (pred_waits && by_counter) {
+            hipExtLaunchKernelGGL(k_rows_gate, dim3(1), dim3(64), 0, g->gate->stream, nullptr, E.ev_rows, 0, (const uint32_t *)E.done_dev,
+                                  E.done_target, H->flag_dev);
+            BDF_HIP(hipGetLastError());
+            BDF_HIP(hipStreamWaitEvent(P->stream, E.ev_rows, 0));
+        } else if (pred_waits) BDF_HIP(hipStreamWaitEvent(P->stream, done, 0));
     }
     // side information: beta of every entity that has it, from this iteration's rows and (mu, Lambda) (macau.jl:138-140)
     for (int j = 0; j < n; j++) {

@@ -10,6 +10,16 @@
 //     across both batches of gathers: 2 pairs x (position, index, value, mean, sum of squares, baseline));
 //   * orig[] is not read at all: it indexes `out` and `linear`, which this path does not have;
 //   * a batch of gathers is the other mode's rows of FOUR pairs (32 registers), not eight.
+//
+// Single-wave workgroups.  Launched as 256 lanes, a workgroup is placed only where all four SIMDs of a CU have the update's registers
+// free at the same moment; beside 2 x 208 that is a CU whose four SIMDs are each between row waves or short of one.  Nothing in the
+// update needs four waves together -- the barrier and the LDS were block_stats' cross-wave sum alone -- so the kernel is launched as
+// four times as many workgroups of 64 lanes, which take any one SIMD's free registers.  Workgroup w takes the pairs that wave w & 3
+// of workgroup w >> 2 took: every lane keeps its pairs, its gathers and its keep[].  A wave leaves its four sums (block_stats'
+// butterfly, xor 32 .. 1) in partial[4 w ..], no LDS and no barrier; k_update_waves_final adds the four waves of a former workgroup
+// left to right -- block_stats' last line -- and goes on as k_predict_final does, expression for expression.  The statistics keep
+// their bits.  The narrower launch bound would let the compiler take more registers: UPD_VGPR_HALF holds it to the 96 the row
+// kernel leaves.
 #include "bdf_common.h"
 #include "predict.h"
 
@@ -17,16 +27,18 @@ namespace {
 
 constexpr int RUN = 16;            // pairs per group of 8 lanes: a lane owns pairs p0 + sub and p0 + 8 + sub (k_predict_runs' shape)
 constexpr int NB = 4;              // pairs per batch of gathers
+// (amdgpu_num_vgpr counts in halves of the unified file, as for k_rows_col: 48 stands for 96 = 512 - 2 x 208)
+#define UPD_VGPR_HALF 48
 
-__global__ __launch_bounds__(256) void k_update_runs(PredArgs a)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(UPD_VGPR_HALF))) void k_update_runs(PredArgs a)
 {
-    const int tid = threadIdx.x, sub = tid & 7;
+    const int tid = threadIdx.x, sub = tid & 7;            // (a workgroup is one wave)
     const int ks = a.sorted_mode, ko = 1 - ks;
     const int32_t *ids_s = a.ids + (int64_t)ks * a.n, *ids_o = a.ids + (int64_t)ko * a.n;
     const double *fs = a.fac[ks], *fo = a.fac[ko];
     const bool live = sub * 4 < a.D;                      // lanes beyond D / 4 hold zeros
     const int eoff = live ? sub * 4 : 0;
-    const int64_t p0 = ((int64_t)blockIdx.x * 32 + tid / 8) * RUN;
+    const int64_t p0 = ((int64_t)blockIdx.x * 8 + tid / 8) * RUN;
     int32_t cur = -1;
     double4 srow = {0.0, 0.0, 0.0, 0.0};
     double keep[2] = {0.0, 0.0};
@@ -65,7 +77,38 @@ __global__ __launch_bounds__(256) void k_update_runs(PredArgs a)
         if (a.phase == 2) { ps.av = a.avg[ps.pm]; ps.sv = a.sq[ps.pm]; }
         pair_finish(a, ps, keep[q], st);
     }
-    block_stats(a, st);
+    // the wave's four sums, block_stats' butterfly: every lane ends with the same bits, lane 0 stores them
+#pragma unroll
+    for (int q = 0; q < 4; q++)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) st[q] += __shfl_xor(st[q], off);
+    if (tid == 0) {
+        double *w = a.partial + (int64_t)blockIdx.x * 4;
+        w[0] = st[0]; w[1] = st[1]; w[2] = st[2]; w[3] = st[3];
+    }
+}
+
+// fixed-order sum of the per-wave statistics: the partial of former workgroup b is its four waves left to right (block_stats' last
+// line), then k_predict_final's stride over b, butterfly and red[q][0] + .. + red[q][3]
+__global__ __launch_bounds__(256) void k_update_waves_final(int nblocks, const double *wave, double *stats)
+{
+    __shared__ double red[4][4];
+    const int tid = threadIdx.x;
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int b = tid; b < nblocks; b += 256) {
+        const double *w = wave + (int64_t)b * 16;
+#pragma unroll
+        for (int q = 0; q < 4; q++) v[q] += w[q] + w[4 + q] + w[8 + q] + w[12 + q];
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        double x = v[q];
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+        if ((tid & 63) == 0) red[q][tid >> 6] = x;
+    }
+    __syncthreads();
+    if (tid < 4) stats[tid] = red[tid][0] + red[tid][1] + red[tid][2] + red[tid][3];
 }
 
 }  // namespace
@@ -83,7 +126,14 @@ int bdf_update_runs(bdf_ctx *ctx, const bdf_pairs *p, int D, const double *const
     a.mean = mean_value; a.avg = p->avg_dev; a.sq = p->sq_dev; a.phase = phase; a.count = count;
     a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi; a.cut = class_cut; a.stats = stats_out;
     a.orig = nullptr; a.out = nullptr;
+    // 512 pairs per partial as before, left by four workgroups of one wave each: 4 x nblocks x 4 doubles of scratch
     const int nblocks = (int)((a.n + 32 * RUN - 1) / (32 * RUN));
-    return launch_reduced(ctx, nblocks, a.partial, a.stats,
-                          [&] { hipLaunchKernelGGL(k_update_runs, dim3(nblocks), dim3(256), 0, ctx->stream, a); });
+    void *sc;
+    rc = bdf_scratch(ctx, (size_t)nblocks * 16 * sizeof(double), &sc);
+    if (rc) return rc;
+    a.partial = (double *)sc;
+    hipLaunchKernelGGL(k_update_runs, dim3(4 * (unsigned)nblocks), dim3(64), 0, ctx->stream, a);
+    hipLaunchKernelGGL(k_update_waves_final, dim3(1), dim3(256), 0, ctx->stream, nblocks, (const double *)a.partial, a.stats);
+    BDF_HIP(hipGetLastError());
+    return BDF_OK;
 }
