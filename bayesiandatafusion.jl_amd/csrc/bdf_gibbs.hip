@@ -416,19 +416,48 @@ const bdf_gibbs_relation *relation_of(const bdf_gibbs *g, const bdf_rel *rel)
 // Polya-Gamma models write the pseudo-observation there, and omega beside it.)
 inline bool draws_latent(const bdf_gibbs_relation &r) { return r.probit || r.censor || r.interval || r.pg_model; }
 
-// macau.jl:83-92 on the row stream, before the entities' rows
+// does update_relations() enqueue anything for the relation?  (Known weights alone do not: the rows just read them.)
+inline bool has_model(const bdf_gibbs_relation &r) { return r.alpha_sample || r.feat || draws_latent(r) || r.robust_nu > 0.0; }
+
+// out[m] = the current sample of the entity that is mode m
+void current_factors(const bdf_gibbs *g, const int32_t *entity_of_mode, int n_modes, const double **out)
+{
+    for (int m = 0; m < n_modes; m++) {
+        const auto &O = g->ent[(size_t)entity_of_mode[m]];
+        out[m] = O.d.sample[O.cur];
+    }
+}
+
+// the terms of entity e's row launch: a term of a registered relation takes the model's alpha_dev, linear_values and
+// obs_precision.  (GibbsEngine._terms of engine.py is the step-by-step twin.)
+void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
+{
+    for (int t = 0; t < e.n_terms; t++) {
+        terms[t].rel = e.terms[t].rel; terms[t].mode = e.terms[t].mode; terms[t]._pad = 0;
+        terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
+        terms[t].alpha_dev = nullptr; terms[t].obs_precision = nullptr;
+        if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {        // a relation with a model of its own
+            terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
+            terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
+            if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
+            terms[t].obs_precision = gr->obs_precision;      // known weights, or the omega of the robust draw
+        }
+        for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
+        current_factors(g, e.terms[t].entity_of_mode, e.terms[t].rel->n_modes, terms[t].factors);
+    }
+}
+
+// macau.jl:83-92 on the row stream, before the entities' rows.  (GibbsEngine.update_relations of engine.py is the step-by-step
+// twin: the same launches in the same order -- keep the two in step, line by line.)
 int update_relations(bdf_gibbs *g)
 {
     bdf_ctx *R = g->rows;
     const int D = g->D;
     int rc;
     for (const auto &r : g->rels) {
-        if (!r.alpha_sample && !r.feat && !draws_latent(r) && !(r.robust_nu > 0.0)) continue;
+        if (!has_model(r)) continue;
         const double *fac[BDF_MAX_MODES];
-        for (int m = 0; m < r.rel->n_modes; m++) {
-            const auto &O = g->ent[(size_t)r.entity_of_mode[m]];
-            fac[m] = O.d.sample[O.cur];
-        }
+        current_factors(g, r.entity_of_mode, r.rel->n_modes, fac);
         // robust: omega of every observation given the rows and the PREVIOUS iteration's alpha, before sample_alpha -- which then takes
         // sum omega e^2 in place of the sum of squares (alpha's exact conditional); the rows then read obs_precision
         if (r.robust_nu > 0.0 && (rc = bdf_robust_draw(R, r.train, D, fac, r.mean_value, 0.0, r.alpha_dev, r.robust_nu, r.rel_tag, r.obs_precision,
@@ -502,22 +531,7 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
     const bdf_gibbs_entity &e = E.d;
     R->sweep_host = sweep;
     bdf_term terms[BDF_MAX_TERMS];
-    for (int t = 0; t < e.n_terms; t++) {
-        terms[t].rel = e.terms[t].rel; terms[t].mode = e.terms[t].mode; terms[t]._pad = 0;
-        terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
-        terms[t].alpha_dev = nullptr; terms[t].obs_precision = nullptr;
-        if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {
-            terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
-            terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
-            if (gr->probit) terms[t].alpha = 1.0;
-            terms[t].obs_precision = gr->obs_precision;
-        }
-        for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
-        for (int k = 0; k < e.terms[t].rel->n_modes; k++) {
-            const auto &O = g->ent[(size_t)e.terms[t].entity_of_mode[k]];
-            terms[t].factors[k] = O.d.sample[O.cur];
-        }
-    }
+    fill_terms(g, e, terms);
     const int nxt = (E.cur + 1) % 3;
     const int nch = e.terms[0].rel->chunks;
     int rc;
@@ -755,22 +769,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // in one launch at the head of the iteration when they are few
         if (!draws_in_chain && n > BDF_DRAWS_BATCH && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
         bdf_term terms[BDF_MAX_TERMS];
-        for (int t = 0; t < e.n_terms; t++) {
-            terms[t].rel = e.terms[t].rel; terms[t].mode = e.terms[t].mode; terms[t]._pad = 0;
-            terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
-            terms[t].alpha_dev = nullptr; terms[t].obs_precision = nullptr;
-            if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {        // a relation with a model of its own
-                terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
-                terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
-                if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
-                terms[t].obs_precision = gr->obs_precision;      // known weights, or the omega of the robust draw
-            }
-            for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
-            for (int k = 0; k < e.terms[t].rel->n_modes; k++) {
-                const auto &O = g->ent[(size_t)e.terms[t].entity_of_mode[k]];
-                terms[t].factors[k] = O.d.sample[O.cur];
-            }
-        }
+        fill_terms(g, e, terms);
         const int nxt = (E.cur + 1) % 3;
         // the completion event rides on the row kernel's dispatch (a caller-supplied timing pair takes its place)
         hipEvent_t done = E.t_stop ? E.t_stop : E.ev_rows;
@@ -865,10 +864,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
     }
     if (g->test && predict_phase >= 0) {
         const double *fac[BDF_MAX_MODES];
-        for (int k = 0; k < g->test->n_modes; k++) {
-            const auto &O = g->ent[(size_t)g->test_entity[k]];
-            fac[k] = O.d.sample[O.cur];
-        }
+        current_factors(g, g->test_entity, g->test->n_modes, fac);
         // (phase 3, set-up only: the same kernel on the same pairs, statistics of this sample into stats_dev, no running state)
         if ((rc = predict_phase == 3 ? bdf_predict_sse(P, g->test, D, fac, g->test_mean, nullptr, g->stats_dev)
                                      : bdf_predict_update(P, g->test, D, fac, g->test_mean, predict_phase, g->clamp_lo, g->clamp_hi, g->class_cut, g->stats_dev)))

@@ -14,7 +14,7 @@ import numpy as np
 from . import features as feat
 from ._lib import ArgumentError
 from .engine import GibbsEngine
-from .relation_data import _ordinal_bounds, _waic_bounds, check_test_interval, hasFeatures, numTest, toStr
+from .relation_data import _ordinal_bounds, _waic_bounds, check_test_interval, hasFeatures, noise_kind, numTest, toStr
 
 
 def AUC_ROC(Ytrue, scores):
@@ -58,22 +58,23 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if output_type not in ("csv", "binary"):
         raise ArgumentError("output_type must be either \"csv\" or \"binary\".")
     clamp = [float(c) for c in clamp]
-    if full_prediction and data.relations and data.relations[0].model.probit:
+    # what the first relation's noise model rules out
+    kind = noise_kind(data.relations[0]) if data.relations else "gauss"
+    if full_prediction and kind == "probit":
         raise ArgumentError("Prediction of all elements is not possible when Relation has the probit noise model.")
-    if full_prediction and data.relations and data.relations[0].model.pg is not None:
-        raise ArgumentError(f"Prediction of all elements is not possible when Relation has the {data.relations[0].model.pg['model']} noise model.")
-    if rmse_train and data.relations and data.relations[0].model.censor is not None:
+    if full_prediction and kind in ("logit", "counts"):
+        raise ArgumentError(f"Prediction of all elements is not possible when Relation has the {kind} noise model.")
+    if rmse_train and kind == "censored":
         raise ArgumentError("rmse_train is not possible when Relation has censoring flags: its training values are bounds, not measurements.")
-    if rmse_train and data.relations and data.relations[0].model.interval is not None:
+    if rmse_train and kind in ("interval", "ordinal"):
         raise ArgumentError("rmse_train is not possible when Relation has interval bounds: its training values stand for intervals, not measurements.")
-
     # the robust noise model and observation weights (setRobust / setWeights)
     robust = data.relations[0].model.robust if data.relations else None
-    if lpd and data.relations and (robust is not None or data.relations[0].model.weights is not None):
-        what = "the robust noise model (setRobust)" if robust is not None else "observation weights (setWeights)"
+    if lpd and kind in ("robust", "weights"):
+        what = "the robust noise model (setRobust)" if kind == "robust" else "observation weights (setWeights)"
         raise ArgumentError(f"lpd = true is not possible when Relation has {what}: a held-out cell's density under it is not scored yet.")
-    if lpd and data.relations and data.relations[0].model.pg is not None:
-        raise ArgumentError(f"lpd = true is not possible when Relation has the {data.relations[0].model.pg['model']} noise model "
+    if lpd and kind in ("logit", "counts"):
+        raise ArgumentError(f"lpd = true is not possible when Relation has the {kind} noise model "
                             "(setLogit / setCounts): a held-out cell's density under it is not scored yet.")
     if lpd and not (data.relations and numTest(data.relations[0]) > 0):
         raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")

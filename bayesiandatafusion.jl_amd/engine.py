@@ -26,11 +26,17 @@ import torch
 from . import _lib
 from . import features as feat
 from ._lib import ArgumentError, GibbsEntity, Term, check, lib
-from .relation_data import check_censored, check_interval, check_ordinal, check_pg, check_probit, check_robust
+from .relation_data import check_model, noise_kind
 
 
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _facs(factors):
+    """the factor matrices of a relation's modes as the array of device pointers the entry points take"""
+    fp = (C.c_void_p * len(factors))(*[f.data_ptr() for f in factors])
+    return fp
 
 
 class Layout:
@@ -238,7 +244,21 @@ class DeviceRelation:
                                                     layouts[0].chunks, C.byref(self.handle)))
         self.dims = list(idf.dims)
         self.nnz = idf.nnz()
+        # the relation's model on the device (GibbsEngine._build_model fills it; a bare relation has none)
+        self.kind, self.alpha_sample, self.alpha_dev = "gauss", False, None
+        self.F = self.beta = self.F_test = self.test_baseline = None     # relation-level side information
+        self.train = None            # the training table as DevicePairs
+        self.linear = None           # linear_values of the row kernels: mean + F beta, or what the model's latent draw leaves
+        self.censor = self.interval = self.ordinal = self.ord_codes = None
+        self.omega = self.wsse = self.omega_sum = None          # obs_precision of the row kernels; sum omega e^2; omega's running sum
+        self.robust_nu, self.pg_model, self.pg_r = 0.0, 0, 0.0
         ctx.adopt(self)
+
+    @property
+    def has_model(self):
+        """a model of its own -- alpha sampled, relation-level side information, a noise model other than fixed-precision
+        Gaussian noise: registered with the native iteration, and stepped before the rows of every iteration"""
+        return self.alpha_sample or self.F is not None or self.kind != "gauss"
 
     def index(self, mode0):
         rp, ri = _lib.c_i64p(), _lib.c_i64p()
@@ -311,9 +331,6 @@ class DevicePairs:
             check(lib().bdf_pairs_set_count_link(self.handle, float(r)))
         return self
 
-    def _facs(self, factors):
-        return (C.c_void_p * len(factors))(*[f.data_ptr() for f in factors])
-
     def _on_own_stream(self):
         """the pairs' stream ordered after the caller's current stream (where the factors were produced), as a context
         manager under which torch allocates and fills on the pairs' stream"""
@@ -336,19 +353,19 @@ class DevicePairs:
         cur, own = self._on_own_stream()
         with own:
             out = torch.zeros(self.n, dtype=torch.float64, device=self.ctx.device)
-            check(lib().bdf_predict(self.ctx.handle, self.handle, D, self._facs(factors), mean_value, _ptr(out)))
+            check(lib().bdf_predict(self.ctx.handle, self.handle, D, _facs(factors), mean_value, _ptr(out)))
         self._hand_back(cur, out)
         return out
 
     def sse(self, D, factors, mean_value, linear=None):
         """device scalar (stats[1]): sum of (value - pred)^2, pred = udot + (linear | mean_value)"""
-        check(lib().bdf_predict_sse(self.ctx.handle, self.handle, D, self._facs(factors), mean_value,
+        check(lib().bdf_predict_sse(self.ctx.handle, self.handle, D, _facs(factors), mean_value,
                                     _ptr(linear) if linear is not None else None, _ptr(self.stats)))
         return self.stats
 
     def update(self, D, factors, mean_value, phase, clamp, class_cut):
         lo, hi = (clamp[0], clamp[1]) if len(clamp) else (1.0, -1.0)
-        check(lib().bdf_predict_update(self.ctx.handle, self.handle, D, self._facs(factors), mean_value, phase, lo, hi,
+        check(lib().bdf_predict_update(self.ctx.handle, self.handle, D, _facs(factors), mean_value, phase, lo, hi,
                                        class_cut, _ptr(self.stats)))
         return self.stats
 
@@ -369,7 +386,7 @@ class DevicePairs:
         or a device scalar (tensor of one double) read on the device.  Returns the device statistics: [0] the sum of this
         draw's log-likelihoods, [1] the sum of the pairs' lpd after it, [2] = [3] = 0."""
         on_dev = torch.is_tensor(alpha)
-        check(lib().bdf_pairs_lpd_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, self._facs(factors),
+        check(lib().bdf_pairs_lpd_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, _facs(factors),
                                          mean_value, 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
                                          _ptr(self.lpd_stats)))
         return self.lpd_stats
@@ -393,7 +410,7 @@ class DevicePairs:
         if self.waic_stats is None:
             self.waic_stats = self.ctx.zeros(4)
         on_dev = torch.is_tensor(alpha)
-        check(lib().bdf_pairs_waic_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, self._facs(factors),
+        check(lib().bdf_pairs_waic_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, _facs(factors),
                                           mean_value, 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
                                           _ptr(self.waic_stats)))
         return self.waic_stats
@@ -668,8 +685,7 @@ class DeviceOrdinal:
         """one Metropolis step on ctx's stream (bdf_ordinal_step); alpha: a float, or a device scalar read on the device; codes: int8
         device tensor, the levels in the caller's order; bounds: (n, 2) device tensor, rewritten when the proposal is accepted"""
         on_dev = torch.is_tensor(alpha)
-        fp = (C.c_void_p * len(factors))(*[f.data_ptr() for f in factors])
-        check(lib().bdf_ordinal_step(ctx.handle, self.handle, train.handle, _ptr(codes), int(D), fp, float(mean_value),
+        check(lib().bdf_ordinal_step(ctx.handle, self.handle, train.handle, _ptr(codes), int(D), _facs(factors), float(mean_value),
                                      0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(rel_tag), int(adapt), _ptr(bounds)))
 
     def bounds(self, ctx, codes, out):
@@ -712,28 +728,7 @@ class GibbsEngine:
         if not (1 <= num_latent <= _lib.BDF_MAX_D):
             raise ArgumentError(f"num_latent={num_latent} must be in 1..{_lib.BDF_MAX_D}")
         for r in data.relations:
-            if r.model.probit:
-                check_probit(r)
-                if shard is not None and shard[1] > 1:
-                    raise ArgumentError(f"Relation {r.name} has the probit noise model: one rank only")
-            if r.model.censor is not None:
-                check_censored(r)
-                if shard is not None and shard[1] > 1:
-                    raise ArgumentError(f"Relation {r.name} has censoring flags: one rank only")
-            if r.model.ordinal is not None:
-                check_ordinal(r)
-            if r.model.interval is not None:
-                check_interval(r)
-                if shard is not None and shard[1] > 1:
-                    raise ArgumentError(f"Relation {r.name} has interval bounds: one rank only")
-            if r.model.robust is not None or r.model.weights is not None:
-                check_robust(r)
-                if shard is not None and shard[1] > 1:
-                    raise ArgumentError(f"Relation {r.name} has {'the robust noise model' if r.model.robust is not None else 'observation weights'}: one rank only")
-            if r.model.pg is not None:
-                check_pg(r)
-                if shard is not None and shard[1] > 1:
-                    raise ArgumentError(f"Relation {r.name} has the {r.model.pg['model']} noise model: one rank only")
+            check_model(r, 1 if shard is None else shard[1])
         self.data, self.D = data, int(num_latent)
         # The row context runs on a stream of its own that leaves a few CUs (one or two per XCD) free for the hyperprior's
         # small kernels, which otherwise wait for slots beside the chip-filling row kernel -- when the entities are small
@@ -791,97 +786,9 @@ class GibbsEngine:
                 raise ArgumentError(f"Relation {r.name} has {len(r.entities)} entities but its data implies {r.data.size()}.")
             lays = [self.layouts[self._entity_index(e)] for e in r.entities]
             dr = DeviceRelation(self.ctx, r.data, lays if self.world > 1 else None, self.rank)
-            # (probit: the latent is not centred; logit / counts: psi = u'v + the offset the setter was given)
-            r.model.mean_value = 0.0 if r.model.probit else (r.model.pg["offset"] if r.model.pg is not None else dr.value_mean())
             r._dev = dr
             self.rel.append(dr)
-            # relation-level side information (RelationData.jl:348-353): FF path only, as in the reference
-            dr.F = dr.beta = dr.linear = dr.train = dr.censor = dr.interval = dr.ordinal = dr.ord_codes = None
-            dr.omega = dr.wsse = dr.omega_sum = None
-            dr.robust_nu = 0.0
-            dr.pg_model, dr.pg_r = 0, 0.0
-            # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
-            # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
-            # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
-            nn = r.data.nnz()
-            dr.obs_block = -(-nn // self.world)
-            dr.obs_lo = min(nn, self.rank * dr.obs_block)
-            dr.obs_hi = min(nn, dr.obs_lo + dr.obs_block)
-            if self.world > 1 and (not feat.isempty(r.F) or r.model.alpha_sample) and dr.obs_hi - dr.obs_lo < 1:
-                raise ArgumentError(f"Relation {r.name} has fewer observations ({nn}) than a block per rank needs")
-            if not feat.isempty(r.F):
-                if feat.feature_shape(r.F)[0] != nn:
-                    raise ArgumentError(f"Relation {r.name} has {nn} observations but its feature matrix has {feat.feature_shape(r.F)[0]} rows")
-                dr.F = FeatOperator(self.ctx, r.F if self.world == 1 else _take_rows(r.F, np.arange(dr.obs_lo, dr.obs_hi)))
-                if dr.F.n > compute_ff_size:
-                    raise ArgumentError("conjugate gradient unimplemented for sampling relation beta")      # sampling.jl:335
-                dr.beta = self.ctx.zeros(dr.F.n)
-                dr.linear = self.ctx.tensor(np.full(dr.obs_block * self.world, r.model.mean_value))     # K1 reads [0, nnz)
-                r.model.beta = np.zeros(dr.F.n)
-            if dr.F is not None or r.model.alpha_sample:
-                dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids)[dr.obs_lo:dr.obs_hi], np.asarray(r.data.values)[dr.obs_lo:dr.obs_hi])
-                if dr.F is not None:         # pred(r) = udot + linear_values on the training table (sampling.jl:16-18)
-                    check(lib().bdf_pairs_set_baseline(dr.train.handle, C.c_void_p(dr.linear.data_ptr() + 8 * dr.obs_lo)))
-            if r.model.probit:
-                # the latent z of every observation is drawn before the rows of every iteration (bdf_probit_draw) and handed to
-                # the row kernels as linear_values = y - z with alpha = 1; the training pairs predict probabilities (rmse_train)
-                dr.linear = self.ctx.zeros(max(nn, 1))
-                dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
-                if len(r.entities) == 2 and nn:
-                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
-                dr.train.set_link(1)
-            if r.model.censor is not None:
-                # the latent z of every flagged observation is drawn after alpha and before the rows of every iteration
-                # (bdf_censored_draw) and handed to the row kernels as linear_values = mean + y - z, with the relation's alpha; the
-                # training pairs carry it as their baseline, so that their squared error is that of z (sample_alpha).  It starts at
-                # mean_value: the first alpha is drawn from the values as they are
-                dr.linear = self.ctx.tensor(np.full(max(nn, 1), r.model.mean_value))
-                dr.censor = self.ctx.tensor(r.model.censor if nn else np.zeros(1, dtype=np.int8), dtype=torch.int8)
-                if dr.train is None:
-                    dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
-                if len(r.entities) == 2 and nn:
-                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
-                check(lib().bdf_pairs_set_baseline(dr.train.handle, _ptr(dr.linear)))
-            if r.model.interval is not None:
-                # the interval-censored model: as the censored one, with a (lower, upper) pair per training row in place of the flag
-                # (bdf_interval_draw); linear starts at mean_value and the training pairs carry it as their baseline
-                dr.linear = self.ctx.tensor(np.full(max(nn, 1), r.model.mean_value))
-                dr.interval = self.ctx.tensor(r.model.interval if nn else np.zeros((1, 2)))
-                if dr.train is None:
-                    dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
-                if len(r.entities) == 2 and nn:
-                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
-                check(lib().bdf_pairs_set_baseline(dr.train.handle, _ptr(dr.linear)))
-            if r.model.ordinal is not None and r.model.ordinal["sample_edges"]:
-                # the ordinal model: the interval model above whose bounds follow the sampled edges -- one Metropolis step on them
-                # after alpha and before the latent draw of every iteration (bdf_ordinal_step), which rewrites dr.interval.  Without
-                # sampled edges the relation IS the interval relation above.  (ordinal_begin gives the object its trace and burn-in)
-                dr.ord_codes = self.ctx.tensor(r.model.ordinal_codes if nn else np.zeros(1, dtype=np.int8), dtype=torch.int8)
-                dr.ordinal = DeviceOrdinal(self.ctx, r.model.ordinal["K"], r.model.ordinal["step"], 0)
-            if r.model.robust is not None or r.model.weights is not None:
-                # a precision weight per training row, which the row kernels read beside the relation's alpha (bdf_term.obs_precision):
-                # the caller's weights, or the omega of the Student-t model -- drawn before alpha and the rows of every iteration
-                # (bdf_robust_draw), which also leaves sum omega e^2 for sample_alpha.  The training pairs stay in the caller's order
-                # in every per-observation array, whichever way they are stored
-                dr.omega = self.ctx.tensor(r.model.weights if (r.model.weights is not None and nn) else np.ones(max(nn, 1)))
-                dr.wsse = self.ctx.zeros(1)
-                dr.robust_nu = float(r.model.robust["nu"]) if r.model.robust is not None else 0.0
-                if dr.train is None:
-                    dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
-                if len(r.entities) == 2 and nn:
-                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
-            if r.model.pg is not None:
-                # the Polya-Gamma models (logit, counts): omega of every training row is drawn before the rows of every iteration
-                # (bdf_pg_draw) and handed to the row kernels as obs_precision, beside linear_values = offset + y - kappa / omega,
-                # with alpha = 1.  The training pairs predict through the model's link (rmse_train)
-                dr.pg_model, dr.pg_r = (1, 0.0) if r.model.pg["model"] == "logit" else (2, float(r.model.pg["r"]))
-                dr.omega = self.ctx.tensor(np.ones(max(nn, 1)))
-                dr.linear = self.ctx.tensor(np.full(max(nn, 1), r.model.mean_value))
-                dr.train = self._pairs(self.ctx, r, np.asarray(r.data.ids), np.asarray(r.data.values))
-                if len(r.entities) == 2 and nn:
-                    dr.train.sort(int(np.argmin(r.data.dims)))       # (as the test pairs: neighbouring pairs share a factor row)
-                dr.train.set_pg_link(dr.pg_model, dr.pg_r)
-            dr.alpha_dev = self.ctx.tensor([float(r.model.alpha)])
+            self._build_model(r, dr, noise_kind(r))
         self._test_pairs = None
         self._train_pairs = None
         self._test_opts = None
@@ -906,6 +813,74 @@ class GibbsEngine:
                     self.ctx_p = Context.side(self.ctx, [self.ctx_h])
         torch.cuda.synchronize(self.ctx.device)      # everything set up above (on torch's streams too) is in place
 
+    def _build_model(self, r, dr, kind):
+        """relation r's model on the device (the fields DeviceRelation names): what _register_relations hands the native iteration
+        and update_relations steps before the rows.  kind: noise_kind(r), after check_model(r)"""
+        ctx, m, nn = self.ctx, r.model, r.data.nnz()
+        dr.kind, dr.alpha_sample = kind, bool(m.alpha_sample)
+        # (probit: the latent is not centred; logit / counts: psi = u'v + the offset the setter was given)
+        m.mean_value = 0.0 if kind == "probit" else (m.pg["offset"] if kind in ("logit", "counts") else dr.value_mean())
+        # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
+        # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
+        # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
+        dr.obs_block = -(-nn // self.world)
+        dr.obs_lo = min(nn, self.rank * dr.obs_block)
+        dr.obs_hi = min(nn, dr.obs_lo + dr.obs_block)
+        if self.world > 1 and (not feat.isempty(r.F) or m.alpha_sample) and dr.obs_hi - dr.obs_lo < 1:
+            raise ArgumentError(f"Relation {r.name} has fewer observations ({nn}) than a block per rank needs")
+        # relation-level side information (RelationData.jl:348-353): FF path only, as in the reference
+        if not feat.isempty(r.F):
+            if feat.feature_shape(r.F)[0] != nn:
+                raise ArgumentError(f"Relation {r.name} has {nn} observations but its feature matrix has {feat.feature_shape(r.F)[0]} rows")
+            dr.F = FeatOperator(ctx, r.F if self.world == 1 else _take_rows(r.F, np.arange(dr.obs_lo, dr.obs_hi)))
+            if dr.F.n > self.compute_ff_size:
+                raise ArgumentError("conjugate gradient unimplemented for sampling relation beta")      # sampling.jl:335
+            dr.beta = ctx.zeros(dr.F.n)
+            m.beta = np.zeros(dr.F.n)
+        # the training table as pairs: this rank's block for sample_alpha and sample_beta_rel; a noise model takes every row (one
+        # rank), sorted -- its per-observation arrays stay in the caller's order, whichever way the pairs are stored
+        ids, values = np.asarray(r.data.ids), np.asarray(r.data.values)
+        if dr.F is not None or m.alpha_sample:
+            dr.train = self._pairs(ctx, r, ids[dr.obs_lo:dr.obs_hi], values[dr.obs_lo:dr.obs_hi])
+        if kind != "gauss":
+            dr.train = self._sorted_pairs(ctx, r, ids, values, dr.train)
+        # linear_values of the row kernels (K1 reads [0, nnz)) start at mean_value: features add F beta (pred(r) = udot +
+        # linear_values, sampling.jl:16-18); a latent z per observation drawn before the rows of every iteration leaves y - z
+        # (probit, alpha = 1), mean + y - z (censored, interval, ordinal, the relation's alpha) or the Polya-Gamma
+        # pseudo-observation offset + y - kappa / omega (logit, counts, alpha = 1)
+        if dr.F is not None or kind in ("probit", "censored", "interval", "ordinal", "logit", "counts"):
+            dr.linear = ctx.tensor(np.full(max(dr.obs_block * self.world, 1), m.mean_value))
+        # ... and is the training pairs' baseline where sample_alpha's squared error is that of udot + linear_values: with features,
+        # and of z for the censored models (the first alpha is drawn from the values as they are)
+        if dr.F is not None or kind in ("censored", "interval", "ordinal"):
+            check(lib().bdf_pairs_set_baseline(dr.train.handle, C.c_void_p(dr.linear.data_ptr() + 8 * dr.obs_lo)))
+        if kind == "probit":                      # bdf_probit_draw; the training pairs predict probabilities (rmse_train)
+            dr.train.set_link(1)
+        elif kind == "censored":                  # bdf_censored_draw after alpha: z of every flagged observation
+            dr.censor = ctx.tensor(m.censor if nn else np.zeros(1, dtype=np.int8), dtype=torch.int8)
+        elif kind in ("interval", "ordinal"):     # bdf_interval_draw at the same place: a (lower, upper) pair per row in place of the flag
+            dr.interval = ctx.tensor(m.interval if nn else np.zeros((1, 2)))
+            if kind == "ordinal" and m.ordinal["sample_edges"]:
+                # the bounds follow the sampled edges: one Metropolis step on them after alpha and before the latent draw
+                # (bdf_ordinal_step), which rewrites dr.interval.  Without sampled edges the relation IS an interval relation.
+                # (ordinal_begin gives the object its trace and burn-in)
+                dr.ord_codes = ctx.tensor(m.ordinal_codes if nn else np.zeros(1, dtype=np.int8), dtype=torch.int8)
+                dr.ordinal = DeviceOrdinal(ctx, m.ordinal["K"], m.ordinal["step"], 0)
+        elif kind in ("weights", "robust"):
+            # a precision weight per training row, which the row kernels read beside the relation's alpha (bdf_term.obs_precision):
+            # the caller's weights, or the omega of the Student-t model -- drawn before alpha and the rows of every iteration
+            # (bdf_robust_draw), which also leaves sum omega e^2 for sample_alpha
+            dr.omega = ctx.tensor(m.weights if (kind == "weights" and nn) else np.ones(max(nn, 1)))
+            dr.wsse = ctx.zeros(1)
+            dr.robust_nu = float(m.robust["nu"]) if kind == "robust" else 0.0
+        elif kind in ("logit", "counts"):
+            # bdf_pg_draw: omega of every training row, the rows' obs_precision beside linear_values; the training pairs predict
+            # through the model's link (rmse_train)
+            dr.pg_model, dr.pg_r = (1, 0.0) if kind == "logit" else (2, float(m.pg["r"]))
+            dr.omega = ctx.tensor(np.ones(max(nn, 1)))
+            dr.train.set_pg_link(dr.pg_model, dr.pg_r)
+        dr.alpha_dev = ctx.tensor([float(m.alpha)])
+
     # ---- the native iteration (bdf_gibbs) -----------------------------------------------------------------------------
     def _create_native(self):
         ents = (GibbsEntity * len(self.ent))()
@@ -915,8 +890,7 @@ class GibbsEngine:
             if not en.relations:
                 raise ArgumentError(f"Entity {en.name} takes part in no relation")
             for t, r in enumerate(en.relations):
-                ri = [x is r for x in self.data.relations].index(True)
-                g.terms[t].rel = self.rel[ri].handle
+                g.terms[t].rel = self.rel[self._relation_index(r)].handle
                 g.terms[t].mode = en.modes[t] - 1
                 for k, e2 in enumerate(r.entities):
                     g.terms[t].entity_of_mode[k] = self._entity_index(e2)
@@ -952,9 +926,7 @@ class GibbsEngine:
         if not self.gibbs:
             return
         from ._lib import GibbsRelation
-        rows = [(ri, r, self.rel[ri]) for ri, r in enumerate(self.data.relations)
-                if r.model.alpha_sample or self.rel[ri].F is not None or r.model.probit or r.model.censor is not None
-                or r.model.interval is not None or self.rel[ri].omega is not None]          # (omega: weights, robust, logit, counts)
+        rows = [(ri, r, dr) for ri, (r, dr) in enumerate(zip(self.data.relations, self.rel)) if dr.has_model]
         arr = (GibbsRelation * max(len(rows), 1))()
         for k, (ri, r, dr) in enumerate(rows):
             g = arr[k]
@@ -967,21 +939,16 @@ class GibbsEngine:
             g.alpha_lambda0, g.alpha_nu0, g.nnz = r.model.alpha_lambda0, r.model.alpha_nu0, r.data.nnz()
             g.train = dr.train.handle
             g.first_obs, g.obs_block = dr.obs_lo, dr.obs_block
-            if r.model.probit:
-                g.probit, g.linear = 1, dr.linear.data_ptr()
-            if dr.censor is not None:
-                g.censor, g.linear = dr.censor.data_ptr(), dr.linear.data_ptr()
-            if dr.interval is not None:
-                g.interval, g.linear = dr.interval.data_ptr(), dr.linear.data_ptr()
+            g.probit, g.robust_nu, g.pg_model, g.pg_r = int(dr.kind == "probit"), dr.robust_nu, dr.pg_model, dr.pg_r
+            for name, t in (("linear", dr.linear), ("censor", dr.censor), ("interval", dr.interval), ("ordinal_codes", dr.ord_codes),
+                            ("obs_precision", dr.omega), ("beta", dr.beta)):
+                if t is not None:
+                    setattr(g, name, t.data_ptr())
             if dr.ordinal is not None:
-                g.ordinal, g.ordinal_codes = dr.ordinal.handle, dr.ord_codes.data_ptr()
-            if dr.omega is not None:
-                g.robust_nu, g.obs_precision = dr.robust_nu, dr.omega.data_ptr()
-            if dr.pg_model:
-                g.pg_model, g.pg_r, g.linear = dr.pg_model, dr.pg_r, dr.linear.data_ptr()
+                g.ordinal = dr.ordinal.handle
             if dr.F is not None:
-                g.feat, g.beta, g.linear, g.lambda_beta = dr.F.handle, dr.beta.data_ptr(), dr.linear.data_ptr(), r.model.lambda_beta
-                if ri == 0 and getattr(dr, "F_test", None) is not None:
+                g.feat, g.lambda_beta = dr.F.handle, r.model.lambda_beta
+                if ri == 0 and dr.F_test is not None:
                     g.feat_test, g.test_baseline = dr.F_test.handle, dr.test_baseline.data_ptr()
         self._gibbs_relations = arr            # (the library copies the records; the tensors they point at live in self.rel)
         check(lib().bdf_gibbs_set_relations(self.gibbs, len(rows), C.cast(arr, C.c_void_p)))
@@ -1072,8 +1039,8 @@ class GibbsEngine:
         if D <= 16 or lr == 0 or len(en.relations) != 1 or len(en.relations[0].entities) != 2:
             return 0
         r = en.relations[0]
-        ri = [x is r for x in self.data.relations].index(True)
-        if self.rel[ri].F is not None or self.rel[ri].omega is not None:
+        dr = self.rel[self._relation_index(r)]
+        if dr.F is not None or dr.omega is not None:         # (not has_model: a sampled alpha alone leaves the rows on the low-rank sampler)
             return 0
         m = [e is en for e in r.entities].index(True)
         deg = np.bincount(np.asarray(r.data.ids[:, m], dtype=np.int64) - 1, minlength=en.count)
@@ -1085,86 +1052,79 @@ class GibbsEngine:
     def _entity_index(self, en):
         return [e is en for e in self.data.entities].index(True)
 
+    def _relation_index(self, r):
+        return [x is r for x in self.data.relations].index(True)
+
     def _terms(self, j):
+        """entity j's row terms, as fill_terms() of csrc/bdf_gibbs.hip makes them for the native iteration -- but alpha is the host
+        scalar update_relations has read back (the native iteration's rows read alpha_dev)"""
         en = self.data.entities[j]
         terms = (Term * len(en.relations))()
         for t, r in enumerate(en.relations):
-            ri = [x is r for x in self.data.relations].index(True)
-            terms[t].rel = self.rel[ri].handle
-            terms[t].mode = en.modes[t] - 1
-            terms[t].alpha = 1.0 if r.model.probit else r.model.alpha
-            terms[t].mean_value = r.model.mean_value
-            terms[t].linear_values = self.rel[ri].linear.data_ptr() if self.rel[ri].linear is not None else None
-            terms[t].alpha_dev = self.rel[ri].alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
-            terms[t].obs_precision = self.rel[ri].omega.data_ptr() if self.rel[ri].omega is not None else None
+            dr, term = self.rel[self._relation_index(r)], terms[t]
+            term.rel, term.mode, term.mean_value = dr.handle, en.modes[t] - 1, r.model.mean_value
+            term.alpha = 1.0 if dr.kind == "probit" else r.model.alpha
+            term.linear_values = dr.linear.data_ptr() if dr.linear is not None else None
+            term.alpha_dev = dr.alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
+            term.obs_precision = dr.omega.data_ptr() if dr.omega is not None else None
             for k, e2 in enumerate(r.entities):
-                terms[t].factors[k] = self.ent[self._entity_index(e2)].sample.data_ptr()
+                term.factors[k] = self.ent[self._entity_index(e2)].sample.data_ptr()
         return terms
 
     # ---- macau.jl:83-92: relation models (alpha, relation-level beta) -----------------------------------------------
     def update_relations(self):
-        """alpha ~ sample_alpha(err) and beta = sample_beta_rel(r), linear_values = mean + F beta, for the relations that
-        ask for them; runs on the main stream before the latent rows of the sweep (alpha is a host scalar of the row
-        kernel's arguments: sampling it costs one device-to-host read per sweep, as the reference's host loop does)"""
-        for ri, r in enumerate(self.data.relations):
-            dr = self.rel[ri]
-            if not (r.model.alpha_sample or dr.F is not None or r.model.probit or dr.censor is not None or dr.interval is not None
-                    or dr.robust_nu > 0.0 or dr.pg_model):
+        """the step-by-step twin of update_relations() in csrc/bdf_gibbs.hip: the same launches in the same order, on the main
+        stream before the latent rows of the sweep -- keep the two in step, line by line.  The one difference: alpha is a host
+        scalar of the step path's row terms (_terms), read back right after sample_alpha -- one device-to-host read per sweep, as
+        the reference's host loop does; the draws behind it read the device scalar like the native iteration's"""
+        L, R, D = lib(), self.ctx.handle, self.D
+        comm = self.comm.handle if (self.world > 1 and self.comm is not None) else None
+        for ri, (r, dr) in enumerate(zip(self.data.relations, self.rel)):
+            if not dr.has_model:
                 continue
-            facs = self.factors_of(r)
-            if dr.pg_model:              # omega | U, V: the rows of this iteration then see the pseudo-observation, precision omega
-                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
-                check(lib().bdf_pg_draw(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, dr.pg_model, dr.pg_r, ri + 1,
-                                        _ptr(dr.omega), _ptr(dr.linear)))
-                continue
-            if dr.omega is not None:
-                # omega | U, V, alpha (the previous iteration's) -> alpha | U, V, omega from sum omega e^2; known weights: no draw,
-                # sum w e^2.  The rows of this iteration then read omega beside alpha
-                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
-                wsse = _ptr(dr.wsse) if r.model.alpha_sample else None
-                if dr.robust_nu > 0.0:
-                    check(lib().bdf_robust_draw(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, r.model.alpha,
-                                                _ptr(dr.alpha_dev), dr.robust_nu, ri + 1, _ptr(dr.omega), wsse))
-                elif r.model.alpha_sample:
-                    check(lib().bdf_pairs_weighted_sse(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, _ptr(dr.omega), wsse))
-                if r.model.alpha_sample:
-                    check(lib().bdf_sample_alpha(self.ctx.handle, r.model.alpha_lambda0, r.model.alpha_nu0, r.data.nnz(), wsse, ri + 1,
-                                                 _ptr(dr.alpha_dev)))
-                    self.ctx.sync()
-                    r.model.alpha = float(dr.alpha_dev.item())
-                continue
-            if r.model.probit:           # z | U, V: the rows of this iteration then see linear_values = y - z, alpha = 1
-                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
-                check(lib().bdf_probit_draw(self.ctx.handle, dr.train.handle, self.D, fp, r.model.mean_value, ri + 1, _ptr(dr.linear), None))
-                continue
-            comm = self.comm.handle if (self.world > 1 and self.comm is not None) else None
-            if r.model.alpha_sample:
-                sse = dr.train.sse(self.D, facs, r.model.mean_value)          # the pairs carry linear_values as baseline
+            m, tag, train = r.model, ri + 1, dr.train.handle
+            fac = _facs(self.factors_of(r))
+            wsse = _ptr(dr.wsse) if (dr.omega is not None and m.alpha_sample) else None
+            # robust: omega | U, V and the PREVIOUS iteration's alpha, before sample_alpha -- which then takes sum omega e^2
+            if dr.robust_nu > 0.0:
+                check(L.bdf_robust_draw(R, train, D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), dr.robust_nu, tag, _ptr(dr.omega), wsse))
+            if m.alpha_sample:
+                # err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known
+                # weights: sum w e^2 (the robust draw above has left its own)
+                sse = wsse if dr.omega is not None else C.c_void_p(dr.train.stats.data_ptr() + 8)
+                if dr.omega is None:
+                    check(L.bdf_predict_sse(R, train, D, fac, m.mean_value, None, _ptr(dr.train.stats)))
+                elif dr.robust_nu == 0.0:
+                    check(L.bdf_pairs_weighted_sse(R, train, D, fac, m.mean_value, _ptr(dr.omega), wsse))
                 if comm is not None:
-                    check(lib().bdf_sum_ranks(self.ctx.handle, comm, C.c_void_p(sse.data_ptr() + 8), 1))
-                check(lib().bdf_sample_alpha(self.ctx.handle, r.model.alpha_lambda0, r.model.alpha_nu0, r.data.nnz(),
-                                             C.c_void_p(sse.data_ptr() + 8), ri + 1, _ptr(dr.alpha_dev)))
+                    check(L.bdf_sum_ranks(R, comm, sse, 1))
+                check(L.bdf_sample_alpha(R, m.alpha_lambda0, m.alpha_nu0, r.data.nnz(), sse, tag, _ptr(dr.alpha_dev)))
                 self.ctx.sync()
-                r.model.alpha = float(dr.alpha_dev.item())
-            if dr.censor is not None:    # z | U, V, alpha: the rows of this iteration then see linear_values = mean + y - z
-                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
-                check(lib().bdf_censored_draw(self.ctx.handle, dr.train.handle, _ptr(dr.censor), self.D, fp, r.model.mean_value,
-                                              r.model.alpha, _ptr(dr.alpha_dev), ri + 1, _ptr(dr.linear), None))
-            if dr.ordinal is not None:   # the edges | U, V, alpha with z integrated out; the bounds of the draw below follow them
-                dr.ordinal.step(self.ctx, dr.train, dr.ord_codes, self.D, facs, r.model.mean_value, dr.alpha_dev, ri + 1, -1, dr.interval)
-            if dr.interval is not None:  # z | U, V, alpha between its bounds: the rows then see linear_values = mean + y - z
-                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
-                check(lib().bdf_interval_draw(self.ctx.handle, dr.train.handle, _ptr(dr.interval), self.D, fp, r.model.mean_value,
-                                              r.model.alpha, _ptr(dr.alpha_dev), ri + 1, _ptr(dr.linear), None))
+                m.alpha = float(dr.alpha_dev.item())
+            # probit: z | U, V; the rows of this iteration then see linear_values = y - z with alpha = 1
+            if dr.kind == "probit":
+                check(L.bdf_probit_draw(R, train, D, fac, m.mean_value, tag, _ptr(dr.linear), None))
+            # Polya-Gamma: omega | U, V; the rows then see the pseudo-observation through linear_values, its precision omega
+            if dr.pg_model:
+                check(L.bdf_pg_draw(R, train, D, fac, m.mean_value, dr.pg_model, dr.pg_r, tag, _ptr(dr.omega), _ptr(dr.linear)))
+            # censored: z | U, V and the alpha just drawn; the rows then see linear_values = mean + y - z
+            if dr.censor is not None:
+                check(L.bdf_censored_draw(R, train, _ptr(dr.censor), D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), tag, _ptr(dr.linear), None))
+            # ordinal: the edges | U, V, alpha with z integrated out; it rewrites the bounds that the draw below reads
+            if dr.ordinal is not None:
+                check(L.bdf_ordinal_step(R, dr.ordinal.handle, train, _ptr(dr.ord_codes), D, fac, m.mean_value, 0.0, _ptr(dr.alpha_dev), tag, -1,
+                                         _ptr(dr.interval)))
+            # interval-censored: the same draw at the same place, between the two bounds of every bounded observation
+            if dr.interval is not None:
+                check(L.bdf_interval_draw(R, train, _ptr(dr.interval), D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), tag, _ptr(dr.linear), None))
             if dr.F is not None:
-                fp = (C.c_void_p * len(facs))(*[f.data_ptr() for f in facs])
-                check(lib().bdf_sample_beta_rel_ranks(self.ctx.handle, comm, dr.F.handle, dr.train.handle, dr.obs_lo, self.D, fp,
-                                                      r.model.mean_value, r.model.alpha, r.model.lambda_beta, ri + 1, _ptr(dr.beta),
-                                                      C.c_void_p(dr.linear.data_ptr() + 8 * dr.obs_lo), None))
+                check(L.bdf_sample_beta_rel_ranks(R, comm, dr.F.handle, train, dr.obs_lo, D, fac, m.mean_value, m.alpha, m.lambda_beta, tag,
+                                                  _ptr(dr.beta), C.c_void_p(dr.linear.data_ptr() + 8 * dr.obs_lo), None))
                 if comm is not None:         # every rank's row kernels read linear_values of their own rows' observations
-                    check(lib().bdf_allgather_block(self.ctx.handle, comm, _ptr(dr.linear), 8 * dr.obs_block))
-                    check(lib().bdf_allgather_join(self.ctx.handle, comm))
-        self.refresh_baselines()
+                    check(L.bdf_allgather_block(R, comm, _ptr(dr.linear), 8 * dr.obs_block))
+                    check(L.bdf_allgather_join(R, comm))
+                if ri == 0:
+                    self.refresh_baselines()
 
     # ---- macau.jl:96-117: latent rows of entity j --------------------------------------------------------------
     def sample_entity(self, j):
@@ -1387,8 +1347,7 @@ class GibbsEngine:
         with torch.cuda.stream(self.ctx.stream):
             S = [x.contiguous() for x in S]
             out = torch.empty(dims, dtype=torch.float64, device=S[0].device)
-        fp = (C.c_void_p * len(S))(*[x.data_ptr() for x in S])
-        check(lib().bdf_predict_all(self.ctx.handle, len(S), (C.c_int64 * len(S))(*dims), self.D, fp, float(r.model.mean_value),
+        check(lib().bdf_predict_all(self.ctx.handle, len(S), (C.c_int64 * len(S))(*dims), self.D, _facs(S), float(r.model.mean_value),
                                     C.c_void_p(out.data_ptr())))
         return out
 
@@ -1399,6 +1358,16 @@ class GibbsEngine:
             ids = np.stack([self.layouts[self._entity_index(e)].to_internal(ids[:, k]) for k, e in enumerate(r.entities)], axis=1)
         return DevicePairs(ctx, ids, values)
 
+    def _sorted_pairs(self, ctx, r, ids, values, pairs=None):
+        """`pairs`, or (ids, values) as new pairs on ctx; a two-mode relation's are stored sorted by the mode with the fewest rows
+        (most pairs per row): the kernels keep that mode's factor row in registers over a run of pairs and gather only the other
+        mode's (k_predict_runs); results and per-pair arrays stay in the caller's order"""
+        if pairs is None:
+            pairs = self._pairs(ctx, r, ids, values)
+        if len(r.entities) == 2 and pairs.n:
+            pairs.sort(int(np.argmin(r.data.dims)))
+        return pairs
+
     def test_pairs(self, subset=None):
         """the relation's test_vec on the device (subset: the rows of test_vec this rank predicts)"""
         r = self.data.relations[0]
@@ -1408,12 +1377,7 @@ class GibbsEngine:
             if subset is not None:
                 ids, vals = ids[subset], vals[subset]
             # native iteration: the pairs belong to the row context (the library updates them on its own prediction stream)
-            self._test_pairs = self._pairs(self.ctx if self.native else self.ctx_p, r, ids, vals)
-            if len(r.entities) == 2:
-                # stored sorted by the mode with the fewest rows (most pairs per row): the update keeps that mode's factor
-                # row in registers over a run of pairs and gathers only the other mode's (k_predict_runs); results stay in
-                # the caller's order
-                self._test_pairs.sort(int(np.argmin(r.data.dims)))
+            self._test_pairs = self._sorted_pairs(self.ctx if self.native else self.ctx_p, r, ids, vals)
             if r.model.probit:               # predictions are probabilities Phi(udot)
                 self._test_pairs.set_link(1)
             dr = self.rel[0]

@@ -78,21 +78,22 @@ def toStr(x):
             if x.lambda_beta_sample:
                 s += f" λ={x.lambda_beta:1.1f}"
         return f"{x.name[:3]}[{s}]"
-    s = "probit" if x.model.probit else f"α={x.model.alpha:2.1f}"
+    kind = noise_kind(x)
+    if kind in ("logit", "counts"):
+        return f"{x.name[:4]}[{'logit' if kind == 'logit' else 'nb:%s' % x.model.pg['r']}]"
+    s = "probit" if kind == "probit" else f"α={x.model.alpha:2.1f}"
     if hasFeatures(x) and x.model.beta is not None and len(x.model.beta):
         s += f" β:{np.linalg.norm(x.model.beta):2.1f}"
-    if x.model.censor is not None:
+    if kind == "censored":
         s += f" cens:{int(np.count_nonzero(x.model.censor))}"
-    if x.model.interval is not None:
+    if kind in ("interval", "ordinal"):
         s += f" intv:{int(np.count_nonzero(x.model.interval[:, 0] < x.model.interval[:, 1]))}"
-    if x.model.ordinal is not None:
+    if kind == "ordinal":
         s += f" ord:{x.model.ordinal['K']}"
-    if x.model.robust is not None:
+    if kind == "robust":
         s += f" t:{x.model.robust['nu']:g}"
-    if x.model.weights is not None:
+    if kind == "weights":
         s += " wts"
-    if x.model.pg is not None:
-        s = "logit" if x.model.pg["model"] == "logit" else f"nb:{x.model.pg['r']}"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -119,6 +120,27 @@ class RelationModel:
         self.robust = None        # setRobust: {"nu"}; Student-t noise with nu degrees of freedom and scale alpha^-1/2
         self.weights = None       # setWeights: float64 per training row, its known precision weight (> 0)
         self.pg = None            # setLogit / setCounts: {"model": "logit" | "counts", "r", "offset"}; Polya-Gamma augmentation
+
+
+def noise_kind(r):
+    """which noise model relation r has, from the fields its setter left: "gauss", "probit", "censored", "interval", "ordinal" (it
+    has the interval model's bounds too), "weights", "robust", "logit" or "counts".  The setters admit one of them per relation."""
+    m = r.model
+    if m.probit:
+        return "probit"
+    if m.censor is not None:
+        return "censored"
+    if m.ordinal is not None:
+        return "ordinal"
+    if m.interval is not None:
+        return "interval"
+    if m.robust is not None:
+        return "robust"
+    if m.weights is not None:
+        return "weights"
+    if m.pg is not None:
+        return m.pg["model"]
+    return "gauss"
 
 
 class RelationTemp:
@@ -658,18 +680,16 @@ def _waic_bounds(r):
     density at the stored value; the probit link); censoring flags 0 -> (y, y), +1 -> (y, +inf), -1 -> (-inf, y); interval bounds
     as they stand (lo == hi a measurement); an ordinal relation's levels between the edges k + 1/2 (sampled edges: where every
     chain starts; macau() then refreshes them with every draw).  The relation's own checks run first."""
-    m = r.model
-    if m.probit:
-        return None
-    if m.censor is not None:
+    m, kind = r.model, noise_kind(r)
+    if kind == "censored":
         check_censored(r)
         y = np.asarray(r.data.values, dtype=np.float64)
         return np.ascontiguousarray(np.stack([np.where(m.censor < 0, -np.inf, y), np.where(m.censor > 0, np.inf, y)], axis=1))
-    if m.ordinal is not None:
+    if kind == "ordinal":
         check_ordinal(r)
         check_interval(r)
         return _ordinal_bounds(m.ordinal_codes, np.arange(1, m.ordinal["K"]) + 0.5)
-    if m.interval is not None:
+    if kind == "interval":
         check_interval(r)
         return np.ascontiguousarray(m.interval, dtype=np.float64)
     return None
@@ -733,6 +753,29 @@ def check_interval(r):
     if b.ndim != 2 or b.shape[1] != 2:
         raise ArgumentError(f"Relation {r.name}: interval bounds must be an (n, 2) array, not {b.shape}.")
     r.model.interval = _interval_bounds(r, b[:, 0], b[:, 1])
+
+
+# what a sampler checks on a relation before it is built, in this order (the ordinal check rebuilds the bounds that the interval
+# check then reads): (the model's fields are set, its check, what the refusal of several ranks calls it -- None: refused through
+# another row, the ordinal model through its interval bounds)
+_MODEL_CHECKS = (
+    (lambda m: m.probit, check_probit, lambda m: "the probit noise model"),
+    (lambda m: m.censor is not None, check_censored, lambda m: "censoring flags"),
+    (lambda m: m.ordinal is not None, check_ordinal, None),
+    (lambda m: m.interval is not None, check_interval, lambda m: "interval bounds"),
+    (lambda m: m.robust is not None or m.weights is not None, check_robust,
+     lambda m: "the robust noise model" if m.robust is not None else "observation weights"),
+    (lambda m: m.pg is not None, check_pg, lambda m: f"the {m.pg['model']} noise model"),
+)
+
+
+def check_model(r, world=1):
+    """every check_* that relation r's noise model asks for; world > 1: none of the models runs on several ranks"""
+    for has, check, what in _MODEL_CHECKS:
+        if has(r.model):
+            check(r)
+            if world > 1 and what is not None:
+                raise ArgumentError(f"Relation {r.name} has {what(r.model)}: one rank only")
 
 
 def assignToTest(r, test, rng=None):

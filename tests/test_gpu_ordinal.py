@@ -4,14 +4,12 @@ paths, fixed edges against setBinned, the Gaussian chain untouched by an ordinal
 held-out log predictive density on planted data with unevenly spaced levels, and the errors of the C ABI."""
 import ctypes as C
 import os
-import subprocess
-import sys
-import tempfile
 import textwrap
 
 import numpy as np
 import pytest
 
+from both_paths import child
 import ordinal_restatement as OR
 
 pytestmark = pytest.mark.gpu
@@ -162,20 +160,10 @@ CHILD = textwrap.dedent('''
 ''') % (ROOT, os.path.join(ROOT, "tests"))
 
 
-def _child(no_native):
-    env = {k: v for k, v in os.environ.items() if k != "BDF_NO_NATIVE"}
-    if no_native:
-        env["BDF_NO_NATIVE"] = "1"
-    with tempfile.TemporaryDirectory() as td:
-        f = os.path.join(td, "o.npz")
-        subprocess.run([sys.executable, "-W", "ignore", "-c", CHILD, f], check=True, env=env, timeout=600)
-        return dict(np.load(f))
-
-
 @pytest.fixture(scope="module")
 def chains():
     """2 + 2 iterations of every case of CASES on the native and on the step-by-step path: one child process per path"""
-    return _child(False), _child(True)
+    return child(CHILD, no_native=False), child(CHILD, no_native=True)
 
 
 @pytest.fixture(scope="module")

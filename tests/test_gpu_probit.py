@@ -4,15 +4,13 @@ oracle on both iteration paths, the Gaussian chain untouched by a probit engine 
 posterior probabilities on planted data, and the errors of the C ABI."""
 import ctypes as C
 import os
-import subprocess
-import sys
-import tempfile
 import textwrap
 
 import numpy as np
 import pytest
 from scipy.special import ndtr
 
+from both_paths import child
 import probit_restatement as PR
 
 pytestmark = pytest.mark.gpu
@@ -151,20 +149,10 @@ CHILD = textwrap.dedent('''
 ''') % (ROOT, os.path.join(ROOT, "tests"))
 
 
-def _child(n_modes, with_feat, no_native):
-    env = {k: v for k, v in os.environ.items() if k != "BDF_NO_NATIVE"}
-    if no_native:
-        env["BDF_NO_NATIVE"] = "1"
-    with tempfile.TemporaryDirectory() as td:
-        f = os.path.join(td, "o.npz")
-        subprocess.run([sys.executable, "-W", "ignore", "-c", CHILD, f, str(n_modes), str(int(with_feat))], check=True, env=env, timeout=600)
-        return dict(np.load(f))
-
-
 @pytest.mark.parametrize("n_modes,with_feat", [(2, False), (2, True), (3, False), (3, True)])
 def test_probit_whole_iterations_match_the_oracle_on_both_paths(n_modes, with_feat):
     ids, y, dims, D, feats, n_test = PR.iteration_case(n_modes, with_feat)
-    nat, step = _child(n_modes, with_feat, False), _child(n_modes, with_feat, True)
+    nat, step = child(CHILD, n_modes, int(with_feat), no_native=False), child(CHILD, n_modes, int(with_feat), no_native=True)
     assert nat["native"] == 1 and step["native"] == 0
     assert sorted(nat) == sorted(step)
     for k in nat:

@@ -5,14 +5,12 @@ import ctypes as C
 import math
 import os
 import re
-import subprocess
-import sys
-import tempfile
 import textwrap
 
 import numpy as np
 import pytest
 
+from both_paths import child
 import censored_restatement as CR
 import interval_restatement as IR
 import lpd_restatement as LR
@@ -250,20 +248,10 @@ CHILD = textwrap.dedent('''
 ''') % (ROOT, os.path.join(ROOT, "tests"))
 
 
-def _child(no_native):
-    env = {k: v for k, v in os.environ.items() if k != "BDF_NO_NATIVE"}
-    if no_native:
-        env["BDF_NO_NATIVE"] = "1"
-    with tempfile.TemporaryDirectory() as td:
-        f = os.path.join(td, "o.npz")
-        subprocess.run([sys.executable, "-W", "ignore", "-c", CHILD, f], check=True, env=env, timeout=600)
-        return dict(np.load(f))
-
-
 @pytest.fixture(scope="module")
 def chains():
     """2 + 3 iterations of macau() on the five setWaic relations, on the native and on the step-by-step path: one child process per path"""
-    return _child(False), _child(True)
+    return child(CHILD, no_native=False), child(CHILD, no_native=True)
 
 
 @pytest.mark.parametrize("kind", KINDS)
