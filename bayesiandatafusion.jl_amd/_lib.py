@@ -79,7 +79,8 @@ class GibbsEntity(C.Structure):
                 ("b0", C.c_double), ("nu0", C.c_double),
                 ("feat", C.c_void_p), ("beta", C.c_void_p), ("uhat", C.c_void_p), ("mu_matrix", C.c_void_p), ("Tinv", C.c_void_p),
                 ("lambda_beta", C.c_void_p), ("cg_iters", C.c_void_p), ("use_ff", C.c_int32), ("sample_lambda_beta", C.c_int32),
-                ("full_lambda_u", C.c_int32), ("_pad", C.c_int32), ("tol", C.c_double), ("lb_nu", C.c_double), ("lb_mu", C.c_double)]
+                ("full_lambda_u", C.c_int32), ("_pad", C.c_int32), ("tol", C.c_double), ("lb_nu", C.c_double), ("lb_mu", C.c_double),
+                ("bg_Lambda", C.c_void_p), ("bg_mu", C.c_void_p), ("bg_pack", C.c_void_p), ("bg_alpha_rows", C.c_void_p)]
 
 
 class GibbsRelation(C.Structure):
@@ -91,7 +92,14 @@ class GibbsRelation(C.Structure):
                 ("test_baseline", C.c_void_p), ("probit", C.c_int32), ("_pad", C.c_int32), ("censor", C.c_void_p),
                 ("interval", C.c_void_p), ("ordinal", C.c_void_p), ("ordinal_codes", C.c_void_p),
                 ("robust_nu", C.c_double), ("obs_precision", C.c_void_p),
-                ("pg_model", C.c_int32), ("_pad_pg", C.c_int32), ("pg_r", C.c_double)]
+                ("pg_model", C.c_int32), ("_pad_pg", C.c_int32), ("pg_r", C.c_double),
+                ("bg_weight", C.c_double), ("bg_value", C.c_double), ("bg_sums", C.c_void_p), ("bg_weights", C.c_void_p)]
+
+
+class BackgroundTerm(C.Structure):
+    """bdf_background_term"""
+    _fields_ = [("sum", C.c_void_p), ("gram", C.c_void_p), ("alpha", C.c_double), ("alpha_dev", C.c_void_p), ("weight", C.c_double),
+                ("resid", C.c_double)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -155,6 +163,10 @@ _SIGS = {
     "bdf_pg_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_int, C.c_double, C.c_uint32,
                               C.c_void_p, C.c_void_p]),
     "bdf_pairs_weighted_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
+    "bdf_background_prior": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(BackgroundTerm), C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_background_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_double, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
     "bdf_ordinal_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]),
     "bdf_ordinal_destroy": (C.c_int, [C.c_void_p]),
     "bdf_ordinal_set_adapt": (C.c_int, [C.c_void_p, C.c_int64]),

@@ -397,6 +397,20 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
         for (int m = 0; m < r.rel->n_modes; m++)
             BDF_REQUIRE(r.entity_of_mode[m] >= 0 && r.entity_of_mode[m] < (int)g->ent.size(), BDF_ERR_ARG,
                         "bdf_gibbs_set_relations: relation %d mode %d names entity %d", k, m, r.entity_of_mode[m]);
+        BDF_REQUIRE(r.bg_weight >= 0.0 && r.bg_weight <= 1.0 && std::isfinite(r.bg_value), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: bg_weight=%g must be 0 (none) or in (0, 1] and bg_value=%g finite", k, r.bg_weight, r.bg_value);
+        if (r.bg_weight > 0.0) {
+            BDF_REQUIRE(r.rel->n_modes == 2 && r.bg_sums, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: a background takes a two-mode relation and the bg_sums buffer", k);
+            BDF_REQUIRE(!r.probit && !r.censor && !r.interval && !r.ordinal && r.robust_nu == 0.0 && !r.pg_model && !r.feat && !g->comm, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: a background takes neither the probit, censored, interval, ordinal, robust or a Polya-Gamma model, relation features nor a communicator", k);
+            BDF_REQUIRE(!r.obs_precision || (r.linear && r.bg_weights), BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: a background with observation weights needs the linear and the bg_weights buffer", k);
+            for (int m = 0; m < 2; m++) {
+                const bdf_gibbs_entity &e = g->ent[(size_t)r.entity_of_mode[m]].d;
+                BDF_REQUIRE(e.bg_Lambda && e.bg_mu && e.bg_pack && e.bg_alpha_rows, BDF_ERR_ARG,
+                            "bdf_gibbs_set_relations: relation %d has a background but entity %d has a NULL bg_Lambda / bg_mu / bg_pack / bg_alpha_rows", k, r.entity_of_mode[m]);
+            }
+        }
     }
     g->rels.assign(rels, rels + n_relations);
     if (n_relations > 0 && !g->rel_sse) BDF_HIP(hipMalloc((void **)&g->rel_sse, 8 * sizeof(double)));
@@ -428,10 +442,51 @@ void current_factors(const bdf_gibbs *g, const int32_t *entity_of_mode, int n_mo
     }
 }
 
+// the registered relation of entity e's term t when it has background cells (bdf_gibbs_relation.bg_weight), or NULL
+const bdf_gibbs_relation *background_of(const bdf_gibbs *g, const bdf_gibbs_entity &e, int t)
+{
+    const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel);
+    return (gr && gr->bg_weight > 0.0) ? gr : nullptr;
+}
+
+// The prior that entity E's rows are sampled with: the hyperprior's draw as it stands -- or, when relations of the entity have
+// background cells, that draw with their Gram terms folded in.  Per background term, in the order of the
+// entity's terms: the sum and the Gram matrix of the OTHER entity's current rows into the relation's own buffers (bdf_hyper_sums on
+// the row stream), then one bdf_background_prior into the entity's (bg_mu, bg_Lambda, bg_pack) and bg_alpha_rows, which
+// fill_terms hands the terms with unit weights.  (GibbsEngine._row_prior of engine.py is the step-by-step twin.)
+int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, const double **mu, const double **Lambda, const double **pack)
+{
+    const bdf_gibbs_entity &e = E.d;
+    const int D = g->D;
+    *mu = e.feat ? e.mu_matrix : e.mu;
+    *Lambda = e.Lambda;
+    *pack = (E.hyper_recorded && !e.feat) ? e.prior_pack : nullptr;
+    bdf_background_term bg[BDF_MAX_TERMS];
+    int n_bg = 0, rc;
+    for (int t = 0; t < e.n_terms; t++) {
+        const bdf_gibbs_relation *gr = background_of(g, e, t);
+        if (!gr) continue;
+        const int other = 1 - e.terms[t].mode;
+        const auto &O = g->ent[(size_t)e.terms[t].entity_of_mode[other]];
+        double *s = gr->bg_sums + (size_t)other * ((size_t)D + (size_t)D * D);
+        if ((rc = bdf_hyper_sums(g->rows, D, O.d.N, O.d.sample[O.cur], nullptr, s, s + D))) return rc;
+        bg[n_bg].sum = s; bg[n_bg].gram = s + D; bg[n_bg].alpha = 0.0; bg[n_bg].alpha_dev = gr->alpha_dev;
+        bg[n_bg].weight = gr->bg_weight; bg[n_bg].resid = gr->bg_value - gr->mean_value;
+        n_bg++;
+    }
+    if (n_bg == 0) return BDF_OK;
+    if ((rc = bdf_background_prior(g->rows, D, e.N, n_bg, bg, *mu, e.feat ? 1 : 0, e.Lambda, e.bg_Lambda, e.bg_mu, e.feat ? nullptr : e.bg_pack,
+                                   e.bg_alpha_rows)))
+        return rc;
+    *mu = e.bg_mu; *Lambda = e.bg_Lambda; *pack = e.feat ? nullptr : e.bg_pack;
+    return BDF_OK;
+}
+
 // the terms of entity e's row launch: a term of a registered relation takes the model's alpha_dev, linear_values and
 // obs_precision.  (GibbsEngine._terms of engine.py is the step-by-step twin.)
 void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
 {
+    int n_bg = 0;
     for (int t = 0; t < e.n_terms; t++) {
         terms[t].rel = e.terms[t].rel; terms[t].mode = e.terms[t].mode; terms[t]._pad = 0;
         terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
@@ -441,6 +496,13 @@ void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
             terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
             if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
             terms[t].obs_precision = gr->obs_precision;      // known weights, or the omega of the robust draw
+            if (gr->bg_weight > 0.0) {
+                // background cells: the listed ones count with omega_k - c0 and the pseudo-residual through `linear` (both constant),
+                // or -- unit weights, the unweighted kernels -- with alpha (1 - c0), which row_prior's fold has left on the device
+                if (gr->obs_precision) terms[t].linear_values = gr->linear;
+                else terms[t].alpha_dev = e.bg_alpha_rows + n_bg;
+                n_bg++;
+            }
         }
         for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
         current_factors(g, e.terms[t].entity_of_mode, e.terms[t].rel->n_modes, terms[t].factors);
@@ -466,11 +528,20 @@ int update_relations(bdf_gibbs *g)
         if (r.alpha_sample) {
             // err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known weights:
             // sum w e^2 (the robust draw above has left its own)
-            if (r.obs_precision) rc = r.robust_nu > 0.0 ? BDF_OK : bdf_pairs_weighted_sse(R, r.train, D, fac, r.mean_value, r.obs_precision, g->rel_sse + 1);
+            int64_t n = r.nnz;
+            if (r.bg_weight > 0.0) {
+                // background cells: the sum of c e^2 over ALL N M cells from the listed ones, the two entities' sums and Gram matrices
+                const size_t pk = (size_t)D + (size_t)D * D;
+                for (int m = 0; m < 2; m++)
+                    if ((rc = bdf_hyper_sums(R, D, g->ent[(size_t)r.entity_of_mode[m]].d.N, fac[m], nullptr, r.bg_sums + m * pk, r.bg_sums + m * pk + D))) return rc;
+                rc = bdf_background_sse(R, r.train, D, fac, r.mean_value, r.bg_weights, r.bg_value, r.bg_weight, r.bg_sums, r.bg_sums + D, r.bg_sums + pk,
+                                        r.bg_sums + pk + D, r.rel->dims[0], r.rel->dims[1], g->rel_sse + 1);
+                n = r.rel->dims[0] * r.rel->dims[1];
+            } else if (r.obs_precision) rc = r.robust_nu > 0.0 ? BDF_OK : bdf_pairs_weighted_sse(R, r.train, D, fac, r.mean_value, r.obs_precision, g->rel_sse + 1);
             else rc = bdf_predict_sse(R, r.train, D, fac, r.mean_value, nullptr, g->rel_sse);
             if (rc) return rc;
             if (g->comm && (rc = bdf_sum_ranks(R, g->comm, g->rel_sse + 1, 1))) return rc;
-            if ((rc = bdf_sample_alpha(R, r.alpha_lambda0, r.alpha_nu0, r.nnz, g->rel_sse + 1, r.rel_tag, r.alpha_dev))) return rc;
+            if ((rc = bdf_sample_alpha(R, r.alpha_lambda0, r.alpha_nu0, n, g->rel_sse + 1, r.rel_tag, r.alpha_dev))) return rc;
         }
         // probit: the latent z of every observation given the rows; the rows then see linear = y - z with alpha = 1
         if (r.probit && (rc = bdf_probit_draw(R, r.train, D, fac, r.mean_value, r.rel_tag, r.linear + r.first_obs, nullptr))) return rc;
@@ -530,15 +601,15 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
     auto &E = g->ent[(size_t)entity];
     const bdf_gibbs_entity &e = E.d;
     R->sweep_host = sweep;
+    int rc;
+    const double *mu, *Lambda, *pack;
+    if ((rc = row_prior(g, E, &mu, &Lambda, &pack))) return rc;
     bdf_term terms[BDF_MAX_TERMS];
     fill_terms(g, e, terms);
     const int nxt = (E.cur + 1) % 3;
     const int nch = e.terms[0].rel->chunks;
-    int rc;
     for (int c = 0; c < nch; c++)
-        if ((rc = bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, e.feat ? e.mu_matrix : e.mu, e.feat ? 1 : 0, e.Lambda, e.tag, c, nch,
-                                  e.sample[nxt], (E.hyper_recorded && !e.feat) ? e.prior_pack : nullptr)))
-            return rc;
+        if ((rc = bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, e.feat ? 1 : 0, Lambda, e.tag, c, nch, e.sample[nxt], pack))) return rc;
     E.cur = nxt;
     return BDF_OK;
 }
@@ -761,13 +832,20 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // the next one produce, so polling cannot deadlock with the exchange's kernels either, but that schedule has only run
         // with a one-rank RCCL communicator: tools/soak_determinism.py rccl)
         static const bool poll_with_comm = getenv("BDF_POLL_WITH_COMM") != nullptr;
-        const bool poll = g->polling && (!g->comm || poll_with_comm) && E.hyper_recorded && !e.feat;
+        // (an entity with background cells is ordered like one with side information: its prior is made here, on the row stream, from
+        // the draw -- behind the draw's event, and its rows join neither the polling nor the hand-over by counter below)
+        bool bg = false;
+        for (int t = 0; t < e.n_terms; t++) bg = bg || background_of(g, e, t) != nullptr;
+        const bool poll = g->polling && (!g->comm || poll_with_comm) && E.hyper_recorded && !e.feat && !bg;
         if (E.hyper_recorded && !poll) BDF_HIP(hipStreamWaitEvent(R->stream, E.ev_hyper, 0));
         // side information: uhat = (F beta)' with the beta of the previous iteration, per-row prior means mu + uhat (macau.jl:103-104)
         if (e.feat && (rc = bdf_uhat(R, e.feat, D, e.beta, e.mu, e.uhat, e.mu_matrix))) return rc;
         // the data-independent part of the hyperprior draw (Bartlett matrix, mean normals): beside the rows -- for all entities
         // in one launch at the head of the iteration when they are few
         if (!draws_in_chain && n > BDF_DRAWS_BATCH && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
+        // the prior of this launch: the draw's (mu, Lambda) and pack, or -- background cells -- those with the Gram terms folded in
+        const double *mu_rows, *Lambda_rows, *pack_rows;
+        if ((rc = row_prior(g, E, &mu_rows, &Lambda_rows, &pack_rows))) return rc;
         bdf_term terms[BDF_MAX_TERMS];
         fill_terms(g, e, terms);
         const int nxt = (E.cur + 1) % 3;
@@ -787,7 +865,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // Every other path -- a communicator, side information, chunks, a caller's timing events (E.t_stop), no polling, chains of
         // several launches: `counter` false; a launch that took another kernel: rows_done_added < 0 -- has `done` as before, on the
         // dispatch or recorded right behind it, for the chain and the prediction stream alike.
-        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && nch == 1 && !E.t_stop;
+        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && !bg && nch == 1 && !E.t_stop;
         const bool pred_waits = j == n - 1 && g->test && predict_phase >= 0;
         bool by_counter = false;
         for (int c = 0; c < nch; c++) {
@@ -796,8 +874,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             R->time_stop = (c == nch - 1 && !g->comm && !counter) ? done : nullptr;
             if (poll) { R->rows_ready = g->ready_dev + j; R->rows_ready_want = E.epoch; }
             if (counter) R->rows_done = E.done_dev;
-            if ((rc = bdf_sample_rows(R, D, e.N, e.n_terms, terms, e.feat ? e.mu_matrix : e.mu, e.feat ? 1 : 0, e.Lambda, e.tag, c, nch,
-                                      e.sample[nxt], (E.hyper_recorded && !e.feat) ? e.prior_pack : nullptr)))
+            if ((rc = bdf_sample_rows(R, D, e.N, e.n_terms, terms, mu_rows, e.feat ? 1 : 0, Lambda_rows, e.tag, c, nch, e.sample[nxt], pack_rows)))
                 return rc;
             if (counter && R->rows_done_added >= 0) { by_counter = true; E.done_target += (uint32_t)R->rows_done_added; }
             if (g->comm && (rc = bdf_allgather_rows(R, g->comm, D, e.N, e.sample[nxt], c, nch))) return rc;

@@ -264,6 +264,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                             "weights": (ws.cpu().numpy()[:rel.data.nnz()] / psamples) if (ws is not None and psamples) else np.full(rel.data.nnz(), np.nan)}
     if lpd:
         result["LPD"] = lpd_avg
+    # relations with background cells (setBackground): what every unlisted cell observed, and how many there were
+    bgs = {r.name: {"weight": r.model.background["weight"], "value": r.model.background["value"],
+                    "cells": int(r.data.dims[0]) * int(r.data.dims[1]) - r.data.nnz()} for r in data.relations if r.model.background is not None}
+    if bgs:
+        result["background"] = bgs
     if waic is not None:
         # lppd, p_waic and the squares of elpd_t about its mean from the device (bdf_pairs_waic): the pointwise table comes to the
         # host only when asked for

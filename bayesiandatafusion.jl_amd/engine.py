@@ -25,8 +25,8 @@ import torch
 
 from . import _lib
 from . import features as feat
-from ._lib import ArgumentError, GibbsEntity, Term, check, lib
-from .relation_data import check_model, noise_kind
+from ._lib import ArgumentError, BackgroundTerm, GibbsEntity, Term, check, lib
+from .relation_data import background_mean, check_model, noise_kind
 
 
 def _ptr(t):
@@ -224,12 +224,13 @@ class Context:
 class DeviceRelation:
     """bdf_rel: Relation.data (IndexedDF) as per-mode CSR in HBM."""
 
-    def __init__(self, ctx, idf, layouts=None, rank=0):
-        """layouts: one Layout per mode (several ranks): the device then holds this rank's rows only, at internal positions"""
+    def __init__(self, ctx, idf, layouts=None, rank=0, values=None):
+        """layouts: one Layout per mode (several ranks): the device then holds this rank's rows only, at internal positions;
+        values: what the row kernels read in place of idf.values (a background relation with unit weights, _background_values)"""
         self.ctx = ctx
         self.handle = C.c_void_p()
         dims = np.asarray(idf.dims, dtype=np.int64)
-        vals = np.ascontiguousarray(idf.values, dtype=np.float64)
+        vals = np.ascontiguousarray(idf.values if values is None else values, dtype=np.float64)
         ids = idf.ids
         if layouts is None or all(l.pos is None for l in layouts):
             check(lib().bdf_relation_create(ctx.handle, len(idf.dims), dims.ctypes.data_as(_lib.c_i64p), idf.nnz(),
@@ -252,13 +253,16 @@ class DeviceRelation:
         self.censor = self.interval = self.ordinal = self.ord_codes = None
         self.omega = self.wsse = self.omega_sum = None          # obs_precision of the row kernels; sum omega e^2; omega's running sum
         self.robust_nu, self.pg_model, self.pg_r = 0.0, 0, 0.0
+        # background cells (setBackground): {"weight", "value"}; the two modes' sums and Gram matrices; the caller's weights (omega is
+        # then what the rows read, omega_k - c0)
+        self.bg = self.bg_sums = self.bg_weights = None
         ctx.adopt(self)
 
     @property
     def has_model(self):
         """a model of its own -- alpha sampled, relation-level side information, a noise model other than fixed-precision
         Gaussian noise: registered with the native iteration, and stepped before the rows of every iteration"""
-        return self.alpha_sample or self.F is not None or self.kind != "gauss"
+        return self.alpha_sample or self.F is not None or self.kind != "gauss" or self.bg is not None
 
     def index(self, mode0):
         rp, ri = _lib.c_i64p(), _lib.c_i64p()
@@ -554,6 +558,20 @@ class FeatOperator:
             pass
 
 
+def _background_values(r):
+    """What the row kernels read as the values of a background relation (setBackground) whose listed cells all have weight 1:
+    y' = mean + (r - c0 rb) / (1 - c0), with r = y - mean and rb = value - mean.  Beside the precision alpha (1 - c0) a listed cell
+    then adds alpha (1 - c0) v v' and alpha (r - c0 rb) v, its own term less the background term the Gram matrix counts for it, on
+    the unweighted kernels -- and y' takes as many distinct values as y, so a relation of ratings keeps its 8-bit value codes.
+    None: no background, or one with setWeights (the weighted kernel reads obs_precision and linear_values instead)."""
+    bg = r.model.background
+    if bg is None or r.model.weights is not None:
+        return None
+    mean, c0 = background_mean(r), bg["weight"]
+    y = np.asarray(r.data.values, dtype=np.float64)
+    return mean + ((y - mean) - c0 * (bg["value"] - mean)) / (1.0 - c0)
+
+
 def _rows_to_internal(F, layout):
     """F with row i moved to row layout.pos[i] of a layout.nint-row matrix of the same kind"""
     pos = layout.pos.astype(np.int64)
@@ -615,6 +633,9 @@ class EntityState:
         # the random part of the hyperprior draw (Bartlett matrix + mean normals), drawn ahead of the rows (bdf_hyper_draws)
         self.draws = ctx.zeros(D * D + D)
         self.draws_sweep = None
+        # a relation of the entity has background cells (setBackground): the prior its rows are sampled with, made before every
+        # row launch (GibbsEngine._row_prior); allocated by background_buffers()
+        self.bg_Lambda = self.bg_mu = self.bg_pack = self.bg_alpha_rows = None
         self.F = None
         self.numF = 0
         self.beta = ctx.zeros(D, 0)
@@ -634,6 +655,15 @@ class EntityState:
             self.Tinv = ctx.zeros(D, D)
             self.lambda_beta = ctx.tensor([en.lambda_beta])
             self.cg_iters = ctx.zeros(D, dtype=torch.int32)
+
+    def background_buffers(self):
+        """(Lambda_eff, mu_eff -- one per row with side information --, their prior pack, alpha (1 - c0) per term) of bdf_background_prior"""
+        if self.bg_Lambda is None:
+            ctx, D = self.ctx, self.D
+            self.bg_Lambda = ctx.zeros(D, D)
+            self.bg_mu = ctx.zeros(self.N, D) if self.F is not None else ctx.zeros(D)
+            self.bg_pack = ctx.zeros(lib().bdf_prior_pack_doubles(D))
+            self.bg_alpha_rows = ctx.zeros(_lib.BDF_MAX_TERMS)
 
     @property
     def sample(self):
@@ -785,10 +815,13 @@ class GibbsEngine:
             if len(r.entities) != len(r.data.dims):
                 raise ArgumentError(f"Relation {r.name} has {len(r.entities)} entities but its data implies {r.data.size()}.")
             lays = [self.layouts[self._entity_index(e)] for e in r.entities]
-            dr = DeviceRelation(self.ctx, r.data, lays if self.world > 1 else None, self.rank)
+            dr = DeviceRelation(self.ctx, r.data, lays if self.world > 1 else None, self.rank, values=_background_values(r))
             r._dev = dr
             self.rel.append(dr)
             self._build_model(r, dr, noise_kind(r))
+            if dr.bg is not None:
+                for e in r.entities:
+                    self.ent[self._entity_index(e)].background_buffers()
         self._test_pairs = None
         self._train_pairs = None
         self._test_opts = None
@@ -819,7 +852,9 @@ class GibbsEngine:
         ctx, m, nn = self.ctx, r.model, r.data.nnz()
         dr.kind, dr.alpha_sample = kind, bool(m.alpha_sample)
         # (probit: the latent is not centred; logit / counts: psi = u'v + the offset the setter was given)
-        m.mean_value = 0.0 if kind == "probit" else (m.pg["offset"] if kind in ("logit", "counts") else dr.value_mean())
+        # (background cells: the mean over ALL cells, the unlisted ones at the background value -- valueMean of the dense listing)
+        m.mean_value = 0.0 if kind == "probit" else (m.pg["offset"] if kind in ("logit", "counts") else
+                                                     (background_mean(r) if m.background is not None else dr.value_mean()))
         # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
         # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
         # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
@@ -879,6 +914,21 @@ class GibbsEngine:
             dr.pg_model, dr.pg_r = (1, 0.0) if kind == "logit" else (2, float(m.pg["r"]))
             dr.omega = ctx.tensor(np.ones(max(nn, 1)))
             dr.train.set_pg_link(dr.pg_model, dr.pg_r)
+        if m.background is not None:
+            # background cells (setBackground): every unlisted cell observes `value` with precision alpha c0.  The
+            # rows of both entities are sampled with the prior _row_prior makes from the other entity's sum and Gram matrix (bg_sums:
+            # per mode, D + D^2 doubles).  Unit weights: the relation was created from _background_values and its terms read alpha
+            # (1 - c0) -- nothing per observation.  setWeights: the rows read omega_k - c0 and, through linear_values, the
+            # pseudo-residual (omega_k r_k - c0 rb) / (omega_k - c0), both constant over the run; alpha's sum of squares reads omega_k
+            c0, rb = m.background["weight"], m.background["value"] - m.mean_value
+            dr.bg = dict(m.background)
+            dr.bg_sums = ctx.zeros(2, self.D + self.D * self.D)
+            dr.wsse = ctx.zeros(1)
+            if kind == "weights":
+                w, y = np.asarray(m.weights, dtype=np.float64), np.asarray(values, dtype=np.float64)
+                dr.bg_weights = dr.omega
+                dr.omega = ctx.tensor((w - c0) if nn else np.ones(1))
+                dr.linear = ctx.tensor((y - (w * (y - m.mean_value) - c0 * rb) / (w - c0)) if nn else np.full(1, m.mean_value))
         dr.alpha_dev = ctx.tensor([float(m.alpha)])
 
     # ---- the native iteration (bdf_gibbs) -----------------------------------------------------------------------------
@@ -901,6 +951,9 @@ class GibbsEngine:
             for name in ("mu", "Lambda", "mu0", "WI", "sumU", "UUt", "params", "prior_pack", "draws"):
                 setattr(g, name, getattr(st, name).data_ptr())
             g.b0, g.nu0 = st.b0, st.nu0
+            if st.bg_Lambda is not None:
+                for name in ("bg_Lambda", "bg_mu", "bg_pack", "bg_alpha_rows"):
+                    setattr(g, name, getattr(st, name).data_ptr())
             if st.F is not None:
                 g.feat = st.F.handle
                 for name in ("beta", "uhat", "mu_matrix", "Tinv", "lambda_beta", "cg_iters"):
@@ -937,11 +990,13 @@ class GibbsEngine:
             g.alpha_dev = dr.alpha_dev.data_ptr()
             g.alpha_sample, g.rel_tag = int(bool(r.model.alpha_sample)), ri + 1
             g.alpha_lambda0, g.alpha_nu0, g.nnz = r.model.alpha_lambda0, r.model.alpha_nu0, r.data.nnz()
-            g.train = dr.train.handle
+            g.train = dr.train.handle if dr.train is not None else None      # (a background with a fixed alpha and unit weights has none)
             g.first_obs, g.obs_block = dr.obs_lo, dr.obs_block
             g.probit, g.robust_nu, g.pg_model, g.pg_r = int(dr.kind == "probit"), dr.robust_nu, dr.pg_model, dr.pg_r
+            if dr.bg is not None:
+                g.bg_weight, g.bg_value = dr.bg["weight"], dr.bg["value"]
             for name, t in (("linear", dr.linear), ("censor", dr.censor), ("interval", dr.interval), ("ordinal_codes", dr.ord_codes),
-                            ("obs_precision", dr.omega), ("beta", dr.beta)):
+                            ("obs_precision", dr.omega), ("beta", dr.beta), ("bg_sums", dr.bg_sums), ("bg_weights", dr.bg_weights)):
                 if t is not None:
                     setattr(g, name, t.data_ptr())
             if dr.ordinal is not None:
@@ -1060,6 +1115,7 @@ class GibbsEngine:
         scalar update_relations has read back (the native iteration's rows read alpha_dev)"""
         en = self.data.entities[j]
         terms = (Term * len(en.relations))()
+        n_bg = 0
         for t, r in enumerate(en.relations):
             dr, term = self.rel[self._relation_index(r)], terms[t]
             term.rel, term.mode, term.mean_value = dr.handle, en.modes[t] - 1, r.model.mean_value
@@ -1067,6 +1123,14 @@ class GibbsEngine:
             term.linear_values = dr.linear.data_ptr() if dr.linear is not None else None
             term.alpha_dev = dr.alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
             term.obs_precision = dr.omega.data_ptr() if dr.omega is not None else None
+            if dr.bg is not None:
+                # background cells: with weights the listed ones count with omega_k - c0 and the pseudo-residual through linear_values
+                # (set above); with unit weights with alpha (1 - c0) -- the host's product, or what _row_prior's fold left on the device
+                if dr.omega is None:
+                    term.alpha = r.model.alpha * (1.0 - dr.bg["weight"])
+                    if self.native and r.model.alpha_sample:
+                        term.alpha_dev = self.ent[j].bg_alpha_rows.data_ptr() + 8 * n_bg
+                n_bg += 1
             for k, e2 in enumerate(r.entities):
                 term.factors[k] = self.ent[self._entity_index(e2)].sample.data_ptr()
         return terms
@@ -1082,7 +1146,7 @@ class GibbsEngine:
         for ri, (r, dr) in enumerate(zip(self.data.relations, self.rel)):
             if not dr.has_model:
                 continue
-            m, tag, train = r.model, ri + 1, dr.train.handle
+            m, tag, train = r.model, ri + 1, (dr.train.handle if dr.train is not None else None)
             fac = _facs(self.factors_of(r))
             wsse = _ptr(dr.wsse) if (dr.omega is not None and m.alpha_sample) else None
             # robust: omega | U, V and the PREVIOUS iteration's alpha, before sample_alpha -- which then takes sum omega e^2
@@ -1092,13 +1156,23 @@ class GibbsEngine:
                 # err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known
                 # weights: sum w e^2 (the robust draw above has left its own)
                 sse = wsse if dr.omega is not None else C.c_void_p(dr.train.stats.data_ptr() + 8)
-                if dr.omega is None:
+                n = r.data.nnz()
+                if dr.bg is not None:
+                    # background cells: the sum of c e^2 over ALL N M cells from the listed ones, the two entities' sums and Gram matrices
+                    sse = _ptr(dr.wsse)
+                    for k, f in enumerate(self.factors_of(r)):
+                        check(L.bdf_hyper_sums(R, D, f.shape[0], _ptr(f), None, _ptr(dr.bg_sums[k, :D]), _ptr(dr.bg_sums[k, D:])))
+                    check(L.bdf_background_sse(R, train, D, fac, m.mean_value, _ptr(dr.bg_weights) if dr.bg_weights is not None else None,
+                                               dr.bg["value"], dr.bg["weight"], _ptr(dr.bg_sums[0, :D]), _ptr(dr.bg_sums[0, D:]),
+                                               _ptr(dr.bg_sums[1, :D]), _ptr(dr.bg_sums[1, D:]), r.data.dims[0], r.data.dims[1], sse))
+                    n = int(r.data.dims[0]) * int(r.data.dims[1])
+                elif dr.omega is None:
                     check(L.bdf_predict_sse(R, train, D, fac, m.mean_value, None, _ptr(dr.train.stats)))
                 elif dr.robust_nu == 0.0:
                     check(L.bdf_pairs_weighted_sse(R, train, D, fac, m.mean_value, _ptr(dr.omega), wsse))
                 if comm is not None:
                     check(L.bdf_sum_ranks(R, comm, sse, 1))
-                check(L.bdf_sample_alpha(R, m.alpha_lambda0, m.alpha_nu0, r.data.nnz(), sse, tag, _ptr(dr.alpha_dev)))
+                check(L.bdf_sample_alpha(R, m.alpha_lambda0, m.alpha_nu0, n, sse, tag, _ptr(dr.alpha_dev)))
                 self.ctx.sync()
                 m.alpha = float(dr.alpha_dev.item())
             # probit: z | U, V; the rows of this iteration then see linear_values = y - z with alpha = 1
@@ -1126,6 +1200,30 @@ class GibbsEngine:
                 if ri == 0:
                     self.refresh_baselines()
 
+    def _row_prior(self, j, mu, is_matrix, pack):
+        """The step-by-step twin of row_prior() in csrc/bdf_gibbs.hip: the (mu, Lambda, pack) entity j's rows are sampled with -- the
+        hyperprior's draw as given, or, when relations of the entity have background cells, that draw with their Gram terms folded
+        in.  Per background term, in the order of the entity's terms: the sum and the Gram matrix of the OTHER entity's current rows
+        into the relation's buffers (bdf_hyper_sums on the row stream), then one bdf_background_prior into the entity's buffers."""
+        en, st, D = self.data.entities[j], self.ent[j], self.D
+        bgs = [(t, r, self.rel[self._relation_index(r)]) for t, r in enumerate(en.relations)]
+        bgs = [(t, r, dr) for t, r, dr in bgs if dr.bg is not None]
+        if not bgs:
+            return mu, st.Lambda, pack
+        arr = (BackgroundTerm * len(bgs))()
+        for k, (t, r, dr) in enumerate(bgs):
+            other = 1 - (en.modes[t] - 1)
+            so = self.ent[self._entity_index(r.entities[other])]
+            s = dr.bg_sums[other]
+            check(lib().bdf_hyper_sums(self.ctx.handle, D, so.N, _ptr(so.sample), None, _ptr(s[:D]), _ptr(s[D:])))
+            arr[k].sum, arr[k].gram = s.data_ptr(), s.data_ptr() + 8 * D
+            arr[k].alpha = r.model.alpha
+            arr[k].alpha_dev = dr.alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
+            arr[k].weight, arr[k].resid = dr.bg["weight"], dr.bg["value"] - r.model.mean_value
+        check(lib().bdf_background_prior(self.ctx.handle, D, st.N, len(bgs), arr, _ptr(mu), is_matrix, _ptr(st.Lambda), _ptr(st.bg_Lambda),
+                                         _ptr(st.bg_mu), None if is_matrix else _ptr(st.bg_pack), _ptr(st.bg_alpha_rows)))
+        return st.bg_mu, st.bg_Lambda, (None if is_matrix else st.bg_pack)
+
     # ---- macau.jl:96-117: latent rows of entity j --------------------------------------------------------------
     def sample_entity(self, j):
         en, st = self.data.entities[j], self.ent[j]
@@ -1141,11 +1239,12 @@ class GibbsEngine:
             timer = KernelTimer()
             check(lib().bdf_ctx_time_next_rows(self.ctx.handle, timer.start, timer.stop))
         pack = st.prior_pack if (st.prior_pack_valid and not is_matrix) else None
+        mu, Lam, pack = self._row_prior(j, mu, is_matrix, pack)
         # written into the entity's next buffer (nothing this launch reads), which then becomes the current one; several ranks:
         # chunk after chunk, every chunk exchanged in place while the next one is sampled
         nch = st.layout.chunks
         for c in range(nch):
-            check(lib().bdf_sample_rows(self.ctx.handle, self.D, st.N, len(terms), terms, _ptr(mu), is_matrix, _ptr(st.Lambda),
+            check(lib().bdf_sample_rows(self.ctx.handle, self.D, st.N, len(terms), terms, _ptr(mu), is_matrix, _ptr(Lam),
                                         st.tag, c, nch, _ptr(st.sample_next), _ptr(pack) if pack is not None else None))
             if self.comm is not None:
                 check(lib().bdf_allgather_rows(self.ctx.handle, self.comm.handle, self.D, st.N, _ptr(st.sample_next), c, nch))

@@ -94,6 +94,8 @@ def toStr(x):
         s += f" t:{x.model.robust['nu']:g}"
     if kind == "weights":
         s += " wts"
+    if x.model.background is not None:
+        s += f" bg:{x.model.background['weight']:g}"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -120,6 +122,7 @@ class RelationModel:
         self.robust = None        # setRobust: {"nu"}; Student-t noise with nu degrees of freedom and scale alpha^-1/2
         self.weights = None       # setWeights: float64 per training row, its known precision weight (> 0)
         self.pg = None            # setLogit / setCounts: {"model": "logit" | "counts", "r", "offset"}; Polya-Gamma augmentation
+        self.background = None    # setBackground: {"weight", "value"}; every cell that is not listed observes `value` with precision alpha weight
 
 
 def noise_kind(r):
@@ -496,6 +499,67 @@ def check_robust(r):
         r.model.weights = _obs_weights(r, r.model.weights)
 
 
+def setBackground(r, weight, value=0.0):
+    """Implicit feedback (Hu, Koren & Volinsky 2008; the one-class factorisation of Pan et al., here in its Bayesian form): every
+    cell of a two-mode relation that is NOT among its training rows is an observation of `value` (in the relation's raw units) with
+    precision alpha weight.  The listed cells keep precision alpha omega_k, omega_k their setWeights weight or 1, so 0 < weight <
+    min omega_k.  The N M - nnz background cells are never listed: they enter every row's conditional through the Gram matrix of
+    the other entity's rows, which all rows share, and an iteration costs what the listed cells cost.
+    mean_value becomes the mean over ALL cells, as valueMean of the dense listing would be.  A sampled alpha is drawn from its
+    conditional over all N M cells.  noise_kind stays "gauss" or "weights".  Held-out cells (assignToTest / setTest) that are not
+    listed are background cells during training: the usual protocol for implicit data.  rmse_train covers the listed cells.
+    Works before or after setWeights and the test split."""
+    what = "a background (setBackground)"
+    _background_guards(r, what)
+    w, v = _background_number(r, "weight", weight), _background_number(r, "value", value)
+    _background_weight(r, w)
+    r.model.background = {"weight": w, "value": v}
+    r._dev = None
+    return None
+
+
+def _background_number(r, name, x):
+    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+        raise ArgumentError(f"Relation {r.name}: {name} = {x} must be a finite number.")
+    return float(x)
+
+
+def _background_weight(r, w):
+    """0 < w < the smallest listed weight (1 without setWeights): a listed cell then counts with omega_k - w > 0 beside the Gram term"""
+    least = float(np.min(r.model.weights)) if (r.model.weights is not None and len(r.model.weights)) else 1.0
+    if not (0.0 < w < least):
+        raise ArgumentError(f"Relation {r.name}: weight = {w} must lie strictly between 0 and the smallest weight of a listed cell ({least}).")
+
+
+def _background_guards(r, what):
+    if len(r.data.dims) != 2:
+        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} takes a two-mode relation.")
+    _weight_guards(r, what)
+    if r.model.robust is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
+    ids = np.asarray(r.data.ids).reshape(r.data.nnz(), 2)
+    if len(np.unique(ids, axis=0)) != len(ids):
+        raise ArgumentError(f"Relation {r.name} lists a cell more than once: {what} would subtract it from the Gram term twice.")
+
+
+def check_background(r):
+    """what a background relation must still satisfy when a sampler is built on it (setWeights, a noise model or setWaic may have
+    come since setBackground)"""
+    what = "a background (setBackground)"
+    _background_guards(r, what)
+    b = r.model.background
+    w, v = _background_number(r, "weight", b.get("weight")), _background_number(r, "value", b.get("value"))
+    _background_weight(r, w)
+    r.model.background = {"weight": w, "value": v}
+
+
+def background_mean(r):
+    """mean_value of a background relation: the mean over all N M cells, the unlisted ones at the background value"""
+    cells = float(r.data.dims[0]) * float(r.data.dims[1])
+    nn = r.data.nnz()
+    return (float(np.sum(np.asarray(r.data.values, dtype=np.float64))) + (cells - nn) * r.model.background["value"]) / cells if cells else 0.0
+
+
 def _censor_flags(r, censor):
     c = np.asarray(censor)
     if c.ndim != 1 or len(c) != r.data.nnz():
@@ -766,6 +830,7 @@ _MODEL_CHECKS = (
     (lambda m: m.robust is not None or m.weights is not None, check_robust,
      lambda m: "the robust noise model" if m.robust is not None else "observation weights"),
     (lambda m: m.pg is not None, check_pg, lambda m: f"the {m.pg['model']} noise model"),
+    (lambda m: m.background is not None, check_background, lambda m: "a background"),
 )
 
 

@@ -654,6 +654,40 @@ int bdf_sample_beta_ranks(bdf_ctx *ctx, bdf_comm *comm, const bdf_feat *f, int D
                           int sample_lambda, double lb_nu, double lb_mu, uint32_t entity_tag,
                           double *beta_out, double *rhs_out, int32_t *iters_out);
 
+/* ---- background cells: implicit feedback (csrc/k_background.hip) ------------------------------------
+ * Every cell of a two-mode N x M relation that is not listed observes a background value with precision alpha c0, c0 below every
+ * listed cell's weight omega_k.  With rb = value - mean_value, G = V V' and s = sum_j v_j over ALL M rows of the other entity, row
+ * i's conditional is that of an ordinary row whose prior is (Lambda_eff, mu_eff_i) = (Lambda + alpha c0 G, Lambda_eff^-1 (Lambda
+ * mu_i + alpha c0 rb s)) and whose listed cells count with weight omega_k - c0 and residual (omega_k r_k - c0 rb) / (omega_k - c0). */
+typedef struct {
+    const double *sum;            /* dev, D: s, the sum of the other entity's rows (what bdf_hyper_sums leaves in sumU)        */
+    const double *gram;           /* dev, D x D: G, their Gram matrix (what bdf_hyper_sums leaves in UUt)                      */
+    double alpha;                 /* the relation's precision ...                                                              */
+    const double *alpha_dev;      /* ... or, nullable, where it lives on the device (sampled there): read instead of `alpha`  */
+    double weight;                /* c0, in (0, 1]                                                                             */
+    double resid;                 /* rb = background value - mean_value                                                        */
+} bdf_background_term;
+/* The effective prior of an entity with n_bg (1 .. BDF_MAX_TERMS) background relations, one workgroup on ctx's stream:
+ *   Lambda_out (dev, D x D) = Lambda + sum_k alpha_k c0_k G_k   (added in the order of bg[])
+ *   mu_out = Lambda_out^-1 (Lambda mu + sum_k alpha_k c0_k rb_k s_k): dev D doubles for a shared prior mean; with mu_is_matrix
+ *   mu and mu_out are D x N and a second launch forms mu_out_i = W mu_i + w0, W = Lambda_out^-1 Lambda, on the matrix cores
+ *   prior_pack_out (dev, nullable, bdf_prior_pack_doubles(D) doubles; NULL with mu_is_matrix): the pack of (mu_out, Lambda_out) as
+ *   bdf_hyper_sample writes it for its draw, bit for bit what bdf_sample_rows derives itself when it is given none
+ *   alpha_rows_out (dev, n_bg doubles): alpha_k (1 - c0_k) -- bdf_term.alpha_dev of a relation whose listed cells all have weight 1,
+ *   which then stays on the unweighted row kernels with values y' = mean + (r - c0 rb) / (1 - c0).
+ * Lambda_out may not alias Lambda nor mu_out mu.  A Lambda_out that is not positive definite sets the context's row-system flag
+ * (BDF_ERR_NOTPD at the next bdf_ctx_sync). */
+int bdf_background_prior(bdf_ctx *ctx, int D, int64_t N, int n_bg, const bdf_background_term *bg, const double *mu, int mu_is_matrix,
+                         const double *Lambda, double *Lambda_out, double *mu_out, double *prior_pack_out, double *alpha_rows_out);
+/* *out (dev, 1 double) = sum over ALL N M cells of c e^2, for sample_alpha with n = N M, from the listed cells alone:
+ *   sum_listed [omega_k e_k^2 - c0 (rb - psi_k)^2] + c0 [N M rb^2 - 2 rb (sum U).(sum V) + <U U', V V'>],   psi = u.v, e = y - mean - psi
+ * train: the listed cells as pairs (two modes), factors as for bdf_predict; weights (dev, nullable: 1): omega_k in the caller's
+ * order; value, weight: the background's; sumU, gramU, sumV, gramV (dev): bdf_hyper_sums of factors[0] (N rows) and factors[1] (M
+ * rows).  The gather and the fixed summation order of bdf_pairs_weighted_sse: bit-identical reruns.  Not reentrant on one context. */
+int bdf_background_sse(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value,
+                       const double *weights, double value, double weight, const double *sumU, const double *gramU,
+                       const double *sumV, const double *gramV, int64_t N, int64_t M, double *out);
+
 /* ---- a2: one Gibbs iteration enqueued from native code (src/macau.jl:80-203; relation-level side information and alpha
  * sampling excepted: those iterations are enqueued step by step through the entry points above) ------------------------
  * rows of every entity (+ exchange) -> hyperpriors -> test-set prediction update, on three streams (rows: ctx's; the other
@@ -689,6 +723,13 @@ typedef struct {
     int32_t _pad;
     double tol;                   /* NaN: eps() * numF                                                                      */
     double lb_nu, lb_mu;          /* hyper-parameters of sample_lambda_beta (Entity.nu, Entity.mu)                          */
+    /* an entity with a background relation (a zeroed tail is "none"; bdf_gibbs_relation.bg_weight): what bdf_background_prior
+     * writes before the entity's rows of every iteration, which are then sampled with (bg_mu, bg_Lambda).  Required when one of
+     * the entity's relations is registered with a background */
+    double *bg_Lambda;            /* dev, D x D                                                                             */
+    double *bg_mu;                /* dev, D; with side information D x N                                                    */
+    double *bg_pack;              /* dev, bdf_prior_pack_doubles(D)                                                         */
+    double *bg_alpha_rows;        /* dev, BDF_MAX_TERMS: per term of this entity, alpha (1 - c0) of a background relation   */
 } bdf_gibbs_entity;
 int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const bdf_gibbs_entity *entities, bdf_gibbs **out);
 int bdf_gibbs_destroy(bdf_gibbs *g);
@@ -762,6 +803,17 @@ typedef struct {
     int32_t pg_model;
     int32_t _pad_pg;
     double pg_r;
+    /* background cells (a zeroed tail is "none"): bg_weight = c0 > 0, every unlisted cell of the two-mode
+     * relation observes bg_value with precision alpha c0.  Before the rows of either entity the iteration takes the sum and the
+     * Gram matrix of the OTHER entity's rows (bdf_hyper_sums on the row stream, into bg_sums) and folds them into that entity's
+     * prior (bdf_background_prior; the entity's bg_* buffers).  Listed cells of weight 1 (obs_precision NULL): the caller created
+     * `rel` from the values mean + (r - c0 rb) / (1 - c0) and the rows read alpha (1 - c0); with weights: obs_precision holds
+     * omega_k - c0, `linear` holds y_k - (omega_k r_k - c0 rb) / (omega_k - c0), both constant, and bg_weights the omega_k themselves.
+     * alpha_sample: the sum of squares over all N M cells by bdf_background_sse over `train` (the original values), n = N M.
+     * Not with probit, censor, interval, ordinal, robust_nu, pg_model, feat or a communicator */
+    double bg_weight, bg_value;
+    double *bg_sums;              /* dev, 2 (D + D D): for mode m at bg_sums + m (D + D D), the sum of that mode's rows, then their Gram matrix */
+    const double *bg_weights;     /* dev, nullable: omega_k per observation of `train` in the caller's order                  */
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

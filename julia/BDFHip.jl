@@ -275,6 +275,9 @@ struct GibbsEntity                                # bdf_gibbs_entity, field for 
     beta::Ptr{Cvoid}; uhat::Ptr{Cvoid}; mu_matrix::Ptr{Cvoid}; Tinv::Ptr{Cvoid}; lambda_beta::Ptr{Cvoid}; cg_iters::Ptr{Cvoid}
     use_ff::Int32; sample_lambda_beta::Int32; full_lambda_u::Int32; _pad::Int32
     tol::Float64; lb_nu::Float64; lb_mu::Float64
+    # a relation of the entity has background cells (GibbsRelation.bg_weight; C_NULL: none): what background_prior! writes before
+    # the entity's rows -- D x D; D (D x N with side information); prior_pack_doubles(D); BDF_MAX_TERMS doubles
+    bg_Lambda::Ptr{Cvoid}; bg_mu::Ptr{Cvoid}; bg_pack::Ptr{Cvoid}; bg_alpha_rows::Ptr{Cvoid}
 end
 
 mutable struct Gibbs
@@ -514,6 +517,35 @@ function pairs_weighted_sse!(c::Context, p::DevPairs, D, factors::Vector{<:DevAr
     check(ccall((:bdf_pairs_weighted_sse, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Ptr{Cvoid}, Ptr{Cvoid}),
                 c.h, p.h, D, fp, mean_value, weights.p, out.p))
 end
+# ---- background cells: implicit feedback (bdf_background_prior, bdf_background_sse; DESIGN.md section 20) ---------------------
+struct BackgroundTerm                             # bdf_background_term, field for field
+    sum::Ptr{Cvoid}                               # device D: the sum of the other entity's rows (update_prior!'s sumU)
+    gram::Ptr{Cvoid}                              # device D x D: their Gram matrix (its UUt)
+    alpha::Float64
+    alpha_dev::Ptr{Cvoid}                         # C_NULL: `alpha`
+    weight::Float64                               # c0
+    resid::Float64                                # background value - mean_value
+end
+"the prior the rows of an entity with background relations are sampled with: Lambda_out = Lambda + sum alpha c0 G, mu_out =
+Lambda_out^-1 (Lambda mu + sum alpha c0 rb s) (D, or D x N with mu_is_matrix), their prior pack (shared mean only) and alpha (1 - c0)"
+function background_prior!(c::Context, D, N, bg::Vector{BackgroundTerm}, mu::DevArray{Float64}, mu_is_matrix::Bool, Lambda::DevArray{Float64},
+                           Lambda_out::DevArray{Float64}, mu_out::DevArray{Float64}, alpha_rows::DevArray{Float64}; prior_pack=nothing)
+    check(ccall((:bdf_background_prior, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Cint, Ptr{BackgroundTerm}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, D, N, length(bg), bg, mu.p, mu_is_matrix ? 1 : 0, Lambda.p, Lambda_out.p, mu_out.p,
+                prior_pack === nothing ? C_NULL : prior_pack.p, alpha_rows.p))
+end
+"out[1] = the sum of c e^2 over all N M cells of a background relation, from its listed cells (`weights`: omega_k, nothing: 1) and the
+two entities' sums and Gram matrices: sample_alpha!'s sum of squares with n = N M"
+function background_sse!(c::Context, p::DevPairs, D, factors::Vector{<:DevArray}, mean_value, weights, value, weight,
+                         sumU::DevArray{Float64}, gramU::DevArray{Float64}, sumV::DevArray{Float64}, gramV::DevArray{Float64}, N, M,
+                         out::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_background_sse, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Ptr{Cvoid}, Float64, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                 Int64, Int64, Ptr{Cvoid}),
+                c.h, p.h, D, fp, mean_value, weights === nothing ? C_NULL : weights.p, value, weight, sumU.p, gramU.p, sumV.p, gramV.p, N, M, out.p))
+end
 "out = mean_value + F beta: linear_values (macau.jl:91) and the test rows' baseline"
 feat_linear!(c::Context, f::Ptr{Cvoid}, beta::DevArray{Float64}, mean_value, out::DevArray{Float64}) =
     check(ccall((:bdf_feat_linear, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), c.h, f, beta.p, mean_value, out.p))
@@ -682,6 +714,10 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     pg_model::Int32                               # Polya-Gamma noise model: 1 logit, 2 counts (0: none); pg_draw! rewrites obs_precision and linear
     _pad_pg::Int32
     pg_r::Float64                                 # ... the counts' integer dispersion r >= 1
+    bg_weight::Float64                            # background cells: every unlisted cell observes bg_value with precision alpha bg_weight (0: none)
+    bg_value::Float64
+    bg_sums::Ptr{Cvoid}                           # device, 2 (D + D D) Float64: per mode, the sum of its rows and their Gram matrix
+    bg_weights::Ptr{Cvoid}                        # device Float64 omega_k per observation of train (C_NULL: 1); obs_precision then holds omega_k - bg_weight
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
