@@ -167,6 +167,14 @@ _SIGS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_background_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "bdf_scores_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bdf_scores_destroy": (C.c_int, [C.c_void_p]),
+    "bdf_scores_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_scores_flush": (C.c_int, [C.c_void_p]),
+    "bdf_scores_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p]),
+    "bdf_scores_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p]),
+    "bdf_scores_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "bdf_scores_set_draws": (C.c_int, [C.c_void_p, C.c_double]),
     "bdf_ordinal_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]),
     "bdf_ordinal_destroy": (C.c_int, [C.c_void_p]),
     "bdf_ordinal_set_adapt": (C.c_int, [C.c_void_p, C.c_int64]),

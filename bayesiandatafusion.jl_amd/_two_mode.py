@@ -33,6 +33,8 @@ def relation_of(data, num_latent, who):
         raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the {rel.model.pg['model']} noise model (use macau)")
     if rel.model.background is not None:
         raise ArgumentError(f"{who} fits the listed cells only; {rel.name} has a background (use macau)")
+    if rel.model.recommend is not None:
+        raise ArgumentError(f"{who} keeps no sum of scores over draws; {rel.name} asks for top-k lists (setRecommend; use macau)")
     return D, rel
 
 

@@ -79,6 +79,12 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if lpd and not (data.relations and numTest(data.relations[0]) > 0):
         raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")
 
+    # top-K lists (setRecommend) are kept for the first relation, like lpd and WAIC
+    for r in data.relations[1:]:
+        if r.model.recommend is not None:
+            raise ArgumentError(f"Relation {r.name} asks for top-k lists (setRecommend) but is not the first relation: macau() keeps the sum of scores for the first relation only.")
+    recommend = data.relations[0].model.recommend if data.relations else None
+
     # WAIC on the training cells (setWaic on the first relation)
     waic = data.relations[0].model.waic if data.relations else None
     if waic is not None and psamples < 2:
@@ -94,6 +100,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if waic is not None and eng.world > 1:
         raise ArgumentError("WAIC (setWaic) is not possible with more than one rank: every rank holds the state of its own cells only.")
     data._engine = eng
+    if eng is engine and (recommend is not None or eng.scores is not None):
+        eng.begin_scores()                                   # (an engine that is reused starts the sum of scores again)
     if robust is not None:
         eng.rel[0].omega_sum = None                          # (an engine that is reused starts the posterior mean of omega again)
     D = eng.D
@@ -158,6 +166,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         facs = eng.factors_of(rel)
         if full_prediction and i > burnin:
             yhat_full += eng.pred_all(rel)                    # macau.jl:145-147: a plain dense product, on the device
+        if recommend is not None and i > burnin:
+            eng.scores.push(facs[0], facs[1])                 # this draw's factors into the ring, on the row stream (a full ring: one accumulate launch)
         if robust is not None and i > burnin:
             eng.robust_accumulate()                           # this iteration's omega into its running sum, on the row stream
         if lpd or waic is not None:
@@ -234,6 +244,13 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                     lstr += " cut=[" + " ".join(f"{e:.3f}" for e in rel.model.ordinal_edges) + "]"
                 print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f}{lstr} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
 
+    rec_dev = None
+    if recommend is not None:
+        # the lists and the ranking metrics from the device, behind the last draw on the row stream: n_rows x K items and scores and
+        # four scalars are all that is read back
+        K = recommend["k"]
+        items, scores = eng.scores.topk(K, rel.model.mean_value, rel._dev if recommend["exclude_listed"] else None)
+        rec_dev = (items, scores, eng.scores.metrics(items, K, test, rel.class_cut) if haveTest else None)
     eng.sync()
     eng.sync_host_scalars()
     result = {
@@ -269,6 +286,13 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                     "cells": int(r.data.dims[0]) * int(r.data.dims[1]) - r.data.nnz()} for r in data.relations if r.model.background is not None}
     if bgs:
         result["background"] = bgs
+    if recommend is not None:
+        rows = recommend["rows"]
+        result["recommend"] = {"k": recommend["k"], "rows": np.arange(1, int(rel.data.dims[0]) + 1) if rows is None else np.array(rows, dtype=np.int64),
+                               "items": rec_dev[0].cpu().numpy(), "scores": rec_dev[1].cpu().numpy()}
+        if rec_dev[2] is not None:
+            m = rec_dev[2].cpu().numpy()
+            result["recommend"].update({"recall": float(m[0]), "ndcg": float(m[1]), "hit_rate": float(m[2]), "rows_scored": int(m[3])})
     if waic is not None:
         # lppd, p_waic and the squares of elpd_t about its mean from the device (bdf_pairs_waic): the pointwise table comes to the
         # host only when asked for

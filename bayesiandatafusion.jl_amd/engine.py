@@ -460,6 +460,67 @@ class DevicePairs:
 _AUC_CONTEXTS = {}          # (device, stream) -> Context of device_auc_roc
 
 
+class DeviceScores:
+    """bdf_scores: the sum of u.v over the posterior draws for the scored rows of a two-mode relation's first entity against all M
+    rows of its second (n_rows x M doubles on the device), a ring of draws that are not in the sum yet, and the top-K lists and
+    ranking metrics from it (setRecommend; csrc/k_recommend.hip).  Everything runs on ctx's stream."""
+
+    def __init__(self, ctx, n_rows, M, D, batch, rows0=None):
+        """rows0: None, the rows 0 .. n_rows - 1 of U; else the 0-based row of U of every scored row"""
+        self.ctx = ctx
+        self.handle = C.c_void_p()
+        self.n_rows, self.M, self.D, self.batch = int(n_rows), int(M), int(D), int(batch)
+        rows = ctx.tensor(np.asarray(rows0, dtype=np.int32), dtype=torch.int32) if rows0 is not None else None
+        check(lib().bdf_scores_create(ctx.handle, self.n_rows, self.M, self.D, self.batch, _ptr(rows), C.byref(self.handle)))
+        ctx.adopt(self)
+
+    def push(self, U, V):
+        """this draw's factors (N x D and M x D tensors) into the ring; a full ring is added into the sum (bdf_scores_push)"""
+        check(lib().bdf_scores_push(self.handle, _ptr(U), _ptr(V)))
+
+    def flush(self):
+        check(lib().bdf_scores_flush(self.handle))
+
+    def topk(self, K, mean_value, rel=None):
+        """(items int32 n_rows x K, 1-based and 0 behind the last candidate; scores float64, NaN there) on the device; rel: the
+        DeviceRelation whose listed cells are left out of every row's list"""
+        K = int(K)
+        items = self.ctx.zeros(self.n_rows, K, dtype=torch.int32)
+        scores = self.ctx.zeros(self.n_rows, K)
+        check(lib().bdf_scores_topk(self.handle, rel.handle if rel is not None else None, K, float(mean_value), _ptr(items), _ptr(scores)))
+        return items, scores
+
+    def metrics(self, items, K, pairs, class_cut):
+        """the device tensor {recall@K, NDCG@K, hit rate, rows scored} of the lists `items` on the test cells `pairs`"""
+        out = self.ctx.zeros(4)
+        check(lib().bdf_scores_metrics(self.handle, _ptr(items), int(K), pairs.handle, float(class_cut), _ptr(out)))
+        return out
+
+    def read(self, first=0, count=None):
+        """parity hook: `count` doubles of the sum from cell `first` (behind the n_rows M cells: 64 guard doubles), flushed first"""
+        count = self.n_rows * self.M - first if count is None else int(count)
+        out = self.ctx.zeros(count)
+        check(lib().bdf_scores_copy(self.handle, _ptr(out), int(first), count, 0))
+        return out
+
+    def write(self, values, draws):
+        """parity hook: the sum's cells from a device tensor, and the count of draws the scores are divided by"""
+        check(lib().bdf_scores_copy(self.handle, _ptr(values), 0, int(values.numel()), 1))
+        check(lib().bdf_scores_set_draws(self.handle, float(draws)))
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:
+                lib().bdf_scores_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def device_auc_roc(labels, scores):
     """AUC_ROC(labels, scores) (src/ROC.jl:1-11) of GPU tensors through bdf_auc_roc, on torch's current stream ->
     (auc, C, P, Nn): C the exact number of (negative, positive) pairs ranked in that order, P / Nn the class sizes"""
@@ -822,6 +883,8 @@ class GibbsEngine:
             if dr.bg is not None:
                 for e in r.entities:
                     self.ent[self._entity_index(e)].background_buffers()
+        self.scores = None
+        self.begin_scores()
         self._test_pairs = None
         self._train_pairs = None
         self._test_opts = None
@@ -1007,6 +1070,18 @@ class GibbsEngine:
                     g.feat_test, g.test_baseline = dr.F_test.handle, dr.test_baseline.data_ptr()
         self._gibbs_relations = arr            # (the library copies the records; the tensors they point at live in self.rel)
         check(lib().bdf_gibbs_set_relations(self.gibbs, len(rows), C.cast(arr, C.c_void_p)))
+
+    def begin_scores(self):
+        """top-K lists of the first relation (setRecommend): the sum of u.v over the draws for the scored rows,
+        zeroed -- at set-up, and again when macau() continues on an engine it was handed"""
+        if self.scores is not None:
+            self.scores.close()
+            self.scores = None
+        rec = self.data.relations[0].model.recommend if self.data.relations else None
+        if rec is not None:
+            r0, rows = self.data.relations[0], rec["rows"]
+            self.scores = DeviceScores(self.ctx, int(r0.data.dims[0]) if rows is None else len(rows), int(r0.data.dims[1]), self.D, rec["batch"],
+                                       None if rows is None else np.asarray(rows, dtype=np.int64) - 1)
 
     def robust_accumulate(self, ri=0):
         """(robust relation ri, after the burn-in) this iteration's omega into the running sum, on the row stream: behind the draw
@@ -1513,7 +1588,7 @@ class GibbsEngine:
             self.sync()
         except Exception:
             pass
-        for p in (self._test_pairs, self._train_pairs):
+        for p in (self._test_pairs, self._train_pairs, self.scores):
             if p is not None:
                 p.close()
         for st in self.ent:

@@ -96,6 +96,8 @@ def toStr(x):
         s += " wts"
     if x.model.background is not None:
         s += f" bg:{x.model.background['weight']:g}"
+    if x.model.recommend is not None:
+        s += f" rec:{x.model.recommend['k']}"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -123,6 +125,7 @@ class RelationModel:
         self.weights = None       # setWeights: float64 per training row, its known precision weight (> 0)
         self.pg = None            # setLogit / setCounts: {"model": "logit" | "counts", "r", "offset"}; Polya-Gamma augmentation
         self.background = None    # setBackground: {"weight", "value"}; every cell that is not listed observes `value` with precision alpha weight
+        self.recommend = None     # setRecommend: {"k", "rows", "exclude_listed", "batch"}; macau() returns a top-k list per row of the first entity
 
 
 def noise_kind(r):
@@ -560,6 +563,72 @@ def background_mean(r):
     return (float(np.sum(np.asarray(r.data.values, dtype=np.float64))) + (cells - nn) * r.model.background["value"]) / cells if cells else 0.0
 
 
+RECOMMEND_MAX_K = 64          # BDF_REC_MAX_K, BDF_REC_MAX_BATCH (csrc/recommend.h)
+RECOMMEND_MAX_BATCH = 32
+
+
+def setRecommend(r, k, rows=None, exclude_listed=True, batch=8):
+    """macau() returns, for rows of this relation's FIRST entity, the k (1 .. 64) best items of the second by the posterior mean
+    score mean_value + E[u.v]: result["recommend"] = {"k", "rows", "items", "scores"} and, when the relation has test cells,
+    recall@k, NDCG@k and the hit rate on them ("recall", "ndcg", "hit_rate", "rows_scored").  The sum of u.v over the draws is kept
+    on the device (rows x M doubles), `batch` (1 .. 32) draws' factors buffered per pass over it; only the lists come back.
+    rows: None, every row; else distinct 1-based ids of the first entity, the only rows that get a sum and a list.
+    exclude_listed: a row's training cells never appear in its list.  Lists are ordered by falling score, equal scores by rising
+    item id; a list is padded with item 0 and score NaN behind the row's last candidate.  The first relation of its RelationData,
+    two modes, no relation features, a noise model whose prediction is u.v + mean (not probit, logit or counts), one rank.
+    Nothing of the chain changes."""
+    _recommend_guards(r)
+    r.model.recommend = _recommend_spec(r, k, rows, exclude_listed, batch)
+    r._dev = None
+    return None
+
+
+def _recommend_int(r, name, x, top):
+    if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not (1 <= int(x) <= top):
+        raise ArgumentError(f"Relation {r.name}: {name} = {x} must be an integer in 1 ... {top} (setRecommend).")
+    return int(x)
+
+
+def _recommend_spec(r, k, rows, exclude_listed, batch):
+    k, batch = _recommend_int(r, "k", k, RECOMMEND_MAX_K), _recommend_int(r, "batch", batch, RECOMMEND_MAX_BATCH)
+    if not isinstance(exclude_listed, (bool, np.bool_)):
+        raise ArgumentError(f"Relation {r.name}: exclude_listed = {exclude_listed} must be true or false (setRecommend).")
+    if rows is not None:
+        N = int(r.data.dims[0])
+        try:
+            a = np.asarray(rows)
+        except (TypeError, ValueError):
+            a = np.asarray(0.5)
+        if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+            raise ArgumentError(f"Relation {r.name}: rows must be a list of integer ids of {r.entities[0].name} (setRecommend).")
+        a = a.astype(np.int64)
+        if len(a) and (a.min() < 1 or a.max() > N):
+            raise ArgumentError(f"Relation {r.name}: rows holds an id outside 1 ... {N} (setRecommend).")
+        if len(np.unique(a)) != len(a):
+            raise ArgumentError(f"Relation {r.name}: rows holds an id more than once (setRecommend).")
+        rows = a
+    return {"k": k, "rows": rows, "exclude_listed": bool(exclude_listed), "batch": batch}
+
+
+def _recommend_guards(r):
+    what = "top-k lists (setRecommend)"
+    if len(r.data.dims) != 2:
+        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: {what} do not take relation-level side information.")
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): its prediction is not u.v + mean, {what} are not possible.")
+    if r.model.pg is not None:
+        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: its prediction is not u.v + mean, {what} are not possible.")
+
+
+def check_recommend(r):
+    """what a relation with setRecommend must still satisfy when a sampler is built on it (a noise model may have come since)"""
+    _recommend_guards(r)
+    m = r.model.recommend
+    r.model.recommend = _recommend_spec(r, m.get("k"), m.get("rows"), m.get("exclude_listed"), m.get("batch"))
+
+
 def _censor_flags(r, censor):
     c = np.asarray(censor)
     if c.ndim != 1 or len(c) != r.data.nnz():
@@ -831,6 +900,7 @@ _MODEL_CHECKS = (
      lambda m: "the robust noise model" if m.robust is not None else "observation weights"),
     (lambda m: m.pg is not None, check_pg, lambda m: f"the {m.pg['model']} noise model"),
     (lambda m: m.background is not None, check_background, lambda m: "a background"),
+    (lambda m: m.recommend is not None, check_recommend, lambda m: "top-k lists (setRecommend)"),
 )
 
 

@@ -688,6 +688,34 @@ int bdf_background_sse(bdf_ctx *ctx, const bdf_pairs *train, int D, const double
                        const double *weights, double value, double weight, const double *sumU, const double *gramU,
                        const double *sumV, const double *gramV, int64_t N, int64_t M, double *out);
 
+/* ---- top-K lists per row from the posterior mean score (csrc/k_recommend.hip, csrc/recommend.h) ---------
+ * A bdf_scores object keeps sum[i, j] = sum over the pushed draws of u_i . v_j for n_rows scored rows of the first entity and all M
+ * rows of the second, n_rows x M doubles row-major, and a ring of `batch` (1 .. 32) slots of draws that are not in the sum yet.
+ * Everything is enqueued on ctx's stream.  rows_dev (dev, nullable: the rows 0 .. n_rows - 1): the 0-based row of U of every scored
+ * row, copied.  BDF_ERR_HIP with N, M and the byte count in bdf_last_error() when the device memory does not suffice. */
+typedef struct bdf_scores bdf_scores;
+int bdf_scores_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D, int batch, const int32_t *rows_dev, bdf_scores **out);
+int bdf_scores_destroy(bdf_scores *sc);
+/* this draw's factors (dev; U: N x D row-major, read at the scored rows only; V: M x D) into the next slot of the ring; a full ring
+ * is flushed */
+int bdf_scores_push(bdf_scores *sc, const double *U, const double *V);
+/* the buffered draws into the sum, on v_mfma_f64_16x16x4_f64: every cell's chain starts from the stored sum and runs over the draws
+ * in push order, d in ascending blocks of four -- the sum's bits depend neither on `batch` nor on where the flushes fall */
+int bdf_scores_flush(bdf_scores *sc);
+/* flush, then per scored row the K (1 .. 64) best columns by score = sum / draws + mean_value, the larger score first, equal scores
+ * by the smaller column; rel (nullable): the columns listed in the row of this two-mode relation (its first mode's device CSR, at
+ * the row's id) are left out.  items_out (dev, n_rows x K int32): 1-based column ids, 0 behind the row's last candidate; scores_out
+ * (dev, n_rows x K doubles): their scores, NaN where items_out is 0.  No draws: no candidates */
+int bdf_scores_topk(bdf_scores *sc, const bdf_rel *rel, int K, double mean_value, int32_t *items_out, double *scores_out);
+/* recall@K, NDCG@K and hit rate of the lists `items` (dev, what bdf_scores_topk wrote) on the held-out cells `test` (two modes) with
+ * value > class_cut, means over the scored rows that have such a cell, added in a fixed order; out (dev, 4 doubles): recall, ndcg,
+ * hit_rate, the count of those rows.  The relevant cells are indexed by row on the host at the first call */
+int bdf_scores_metrics(bdf_scores *sc, const int32_t *items, int K, const bdf_pairs *test, double class_cut, double *out);
+/* parity hooks: flush, then copy `count` doubles between the sum (from cell `first`; the sum is followed by 64 doubles of NaN that
+ * nothing writes) and buf_dev -- write != 0: into the sum; and the count of draws that scores are divided by */
+int bdf_scores_copy(bdf_scores *sc, double *buf_dev, int64_t first, int64_t count, int write);
+int bdf_scores_set_draws(bdf_scores *sc, double draws);
+
 /* ---- a2: one Gibbs iteration enqueued from native code (src/macau.jl:80-203; relation-level side information and alpha
  * sampling excepted: those iterations are enqueued step by step through the entry points above) ------------------------
  * rows of every entity (+ exchange) -> hyperpriors -> test-set prediction update, on three streams (rows: ctx's; the other

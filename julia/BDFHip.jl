@@ -546,6 +546,39 @@ function background_sse!(c::Context, p::DevPairs, D, factors::Vector{<:DevArray}
                  Int64, Int64, Ptr{Cvoid}),
                 c.h, p.h, D, fp, mean_value, weights === nothing ? C_NULL : weights.p, value, weight, sumU.p, gramU.p, sumV.p, gramV.p, N, M, out.p))
 end
+# ---- top-K lists per row from the posterior mean score (bdf_scores_*; DESIGN.md section 21) ------------------------------------
+"the sum of u.v over the pushed draws for n_rows scored rows of the first entity against the M rows of the second, a ring of `batch`
+draws that are not in the sum yet; rows: device Int32 0-based rows of U (nothing: the rows 0 .. n_rows - 1)"
+mutable struct Scores
+    h::Ptr{Cvoid}
+    ctx::Context
+    n_rows::Int
+    M::Int
+    function Scores(c::Context, n_rows::Integer, M::Integer, D::Integer, batch::Integer=8, rows=nothing)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:bdf_scores_create, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Cint, Ptr{Cvoid}, Ref{Ptr{Cvoid}}),
+                    c.h, n_rows, M, D, batch, rows === nothing ? C_NULL : rows.p, out))
+        s = new(out[], c, n_rows, M)
+        finalizer(x -> ccall((:bdf_scores_destroy, lib), Cint, (Ptr{Cvoid},), x.h), s)
+        s
+    end
+end
+"this draw's factors (N x D and M x D, row-major) into the ring; a full ring is added into the sum"
+scores_push!(s::Scores, U::DevArray{Float64}, V::DevArray{Float64}) =
+    check(ccall((:bdf_scores_push, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), s.h, U.p, V.p))
+"the buffered draws into the sum (f64 matrix instructions; the sum's bits do not depend on where the flushes fall)"
+scores_flush!(s::Scores) = check(ccall((:bdf_scores_flush, lib), Cint, (Ptr{Cvoid},), s.h))
+"per scored row the K best columns by sum / draws + mean_value (falling score, equal scores by rising column), the columns listed in
+`rel` (a two-mode DevRelation's handle, C_NULL: none) left out; items: device Int32 n_rows x K, 1-based, 0 padding; scores: NaN there"
+scores_topk!(s::Scores, rel::Ptr{Cvoid}, K::Integer, mean_value, items::DevArray{Int32}, scores::DevArray{Float64}) =
+    check(ccall((:bdf_scores_topk, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Float64, Ptr{Cvoid}, Ptr{Cvoid}), s.h, rel, K, mean_value, items.p, scores.p))
+"out (device, 4 Float64) = recall@K, NDCG@K, hit rate and the count of scored rows with a held-out cell above class_cut"
+scores_metrics!(s::Scores, items::DevArray{Int32}, K::Integer, test::DevPairs, class_cut, out::DevArray{Float64}) =
+    check(ccall((:bdf_scores_metrics, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Float64, Ptr{Cvoid}), s.h, items.p, K, test.h, class_cut, out.p))
+"parity hooks: `count` doubles between the sum (from cell `first`) and buf, into the sum when write; the count of draws scores are divided by"
+scores_copy!(s::Scores, buf::DevArray{Float64}, first::Integer, count::Integer, write::Bool=false) =
+    check(ccall((:bdf_scores_copy, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint), s.h, buf.p, first, count, write ? 1 : 0))
+scores_set_draws!(s::Scores, draws::Real) = check(ccall((:bdf_scores_set_draws, lib), Cint, (Ptr{Cvoid}, Float64), s.h, draws))
 "out = mean_value + F beta: linear_values (macau.jl:91) and the test rows' baseline"
 feat_linear!(c::Context, f::Ptr{Cvoid}, beta::DevArray{Float64}, mean_value, out::DevArray{Float64}) =
     check(ccall((:bdf_feat_linear, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), c.h, f, beta.p, mean_value, out.p))
