@@ -3,7 +3,8 @@
 // each: the right-hand side) -- the unfinished part stays symmetric, so the multiplier of a column in step k is the lane's own
 // entry of row k: no transposition, no LDS.  The LDL' factorisation with the forward solve riding along as row 32 and the
 // backward solve are v_fmac_f64_dpp row_newbcast instructions (lane k % 16 of each lane row is the source of step k).  Used by
-// k_rows_col (k_rows_col.hip: K1c, four rows per wave from the first observation on).
+// k_rows_col (k_rows_col.hip: K1c, four rows per wave from the first observation on; its accumulation: col_rank1u, the ten unique
+// 8 x 8 blocks) and k_rows_lr32 (k_rows_lr.hip: col_rank1, the three 16 x 16 blocks).
 #pragma once
 #include "dpp_rows16.h"
 
@@ -24,8 +25,8 @@ __device__ __forceinline__ int sys_off(int j)
     }
 }
 
-// ---- a rank-1 update v v' of the three stored blocks (0,0), (1,0), (1,1): lane j holds v0 = v_j and v1 = v_(16+j) (k_rows_col: an observation;
-// k_rows_lr32: an element of the two observations a lane streams) ----
+// ---- a rank-1 update v v' of the three stored blocks (0,0), (1,0), (1,1): lane j holds v0 = v_j and v1 = v_(16+j) (k_rows_lr32: an element of
+// the two observations a lane streams; k_rows_col's observations take col_rank1u below) ----
 template <int DR, int I>
 __device__ __forceinline__ void col_rank1(double (&A0)[33], double (&A1)[33], double v0, double v1)
 {
@@ -36,6 +37,52 @@ __device__ __forceinline__ void col_rank1(double (&A0)[33], double (&A1)[33], do
             fm1_run<I>(A1[16 + I], v1, v1);                                               // (16+i,16+j) += v_(16+i) v_(16+j)
         }
         col_rank1<DR, I + 1>(A0, A1, v0, v1);
+    }
+}
+// ---- the same rank-1 update as the TEN UNIQUE 8 x 8 BLOCKS of the symmetric 32 x 32 (k_rows_col): 40 fmacs where col_rank1 spends 48 --
+// its two diagonal 16 x 16 blocks compute (i, j) and (j, i) both.  The 32 elements in four groups of eight (L: lanes 0-7, H: lanes 8-15 of
+// v0 | v1), every unordered pair of groups in ONE orientation; a row_newbcast fmac is one element times sixteen, so the eight rows of a
+// group meet TWO groups per instruction, and two derived own-vectors put the right pair under them:
+//     x = L ? v1 : v0          [v_16..23 | v_8..15]        two v_cndmask_b32
+//     y = L ? rot8(v0) : v1    [v_8..15  | v_24..31]       two v_cndmask_b32_dpp row_ror:8 (v_fmac_f64_dpp itself takes no row_ror)
+//   A0[i]      += v0[i]   v0     (i, j)            P0: the column's entries as they are
+//   A1[i]      += v0[i]   v1     (i, 16+j)         P1: block (0,1) itself (col_rank1 accumulates its mirror image)
+//   A0[8+i]    += v0[8+i] x      M1: L (8+i, 16+j) -- A1[8+i]'s L half;  H (8+i, j) -- A0[8+i]'s own H half
+//   A1[16+i]   += v1[i]   v1     (16+i, 16+j)      P2
+//   A1[24+i]   += v1[8+i] y      M3: L (24+i, 8+j) -- A0[24+i]'s H half, eight lanes to the left;  H (24+i, 16+j) -- A1[24+i]'s own H half
+// for i = 0 .. 7; rows DR .. 31 are skipped (P2 from DR < 24, M3 and y at DR <= 24).  Every accumulator sees the fma(acc, a, b) of col_rank1's
+// entry with a and b in this or the other order: the same bits.  What the sixty-four natural registers still miss is their mirror image in
+// another lane (k_rows_col's re-layout, once per round).
+template <int B0, int K0, int N, int I = 0>
+__device__ __forceinline__ void col_star(double (&A)[33], double s, double m)
+{
+    if constexpr (I < N) {
+        fm1_run<K0 + I>(A[B0 + I], s, m);
+        col_star<B0, K0, N, I + 1>(A, s, m);
+    }
+}
+// hmask: the H lanes of the four lane rows (the DPP form of the select takes its condition from VCC only: a scalar move per observation)
+__device__ __forceinline__ double col_own_y(double v0, double v1, uint64_t hmask)
+{
+    int lo, hi;
+    asm("s_mov_b64 vcc, %6\n\t"
+        "v_cndmask_b32_dpp %0, %2, %4, vcc row_ror:8 row_mask:0xf bank_mask:0xf\n\t"
+        "v_cndmask_b32_dpp %1, %3, %5, vcc row_ror:8 row_mask:0xf bank_mask:0xf"
+        : "=&v"(lo), "=v"(hi) : "v"(__double2loint(v0)), "v"(__double2hiint(v0)), "v"(__double2loint(v1)), "v"(__double2hiint(v1)), "s"(hmask) : "vcc");
+    return __hiloint2double(hi, lo);
+}
+template <int DR>
+__device__ __forceinline__ void col_rank1u(double (&A0)[33], double (&A1)[33], double v0, double v1, bool h, uint64_t hmask)
+{
+    fm1<0>(A0[0], v0, v0);
+    col_star<1, 1, 7>(A0, v0, v0);
+    col_star<0, 0, 8>(A1, v0, v1);
+    col_star<16, 0, (DR - 16 < 8 ? DR - 16 : 8)>(A1, v1, v1);
+    const double x = h ? v0 : v1;
+    col_star<8, 8, 8>(A0, v0, x);
+    if constexpr (DR > 24) {
+        const double y = col_own_y(v0, v1, hmask);
+        col_star<24, 8, DR - 24>(A1, v1, y);
     }
 }
 // rows I .. DR-1 and the extra row 32 of step k = 16 S + K: A_s[I] -= A[I][k] * A[k][c_s] / d_k

@@ -12,10 +12,13 @@
 // every 16-lane row of a wave owns one entity row -- or one PIECE of a longer one -- and lane j of it holds COLUMNS j and
 // 16 + j of the index-reversed system in full (dpp_rows32.h), FROM THE ACCUMULATION ON:
 //   * an observation's factor row arrives as two 8-byte loads per lane (elements D-1-j and D-17-j: 128 contiguous bytes
-//     per half and lane row) and its rank-1 update is 48 v_fmac_f64_dpp row_newbcast instructions -- lane i of the lane
-//     row is the broadcast source of row i -- each doing the work of FOUR rows: 12 vector instructions per observation,
-//     the cost of the three v_mfma_f64_16x16x4_f64 per four observations they replace (the two share the FP64 pipe);
-//     blocks (0,0), (1,0), (1,1) are accumulated, block (0,1) is block (1,0)'s transpose (once per row, through LDS);
+//     per half and lane row) and its rank-1 update is 40 v_fmac_f64_dpp row_newbcast instructions -- lane i of the lane
+//     row is the broadcast source of row i -- each doing the work of FOUR rows: 10 vector instructions per observation,
+//     below the cost of the three v_mfma_f64_16x16x4_f64 per four observations they replace (the two share the FP64 pipe);
+//     the TEN UNIQUE 8 x 8 blocks of the symmetric sum are accumulated (dpp_rows32.h, col_rank1u: two derived own-vectors
+//     per observation, four select instructions), and what the full columns miss comes from another lane by symmetry,
+//     once per round through LDS after the sums (the re-layout) -- the bits of accumulating blocks (0,0), (1,0), (1,1) in
+//     full with 48, every accumulator the same fma sequence with its multiplicands in this or the other order;
 //   * observations past a piece's end are gathered from beyond the factor matrix with buffer loads, which return zero
 //     there: no masks in the loop;
 //   * a row of more than T observations is cut into 2 or 4 equal pieces on neighbouring lane rows of ONE wave, summed by
@@ -39,10 +42,13 @@
 // them (k_update_runs.hip).  amdgpu_num_vgpr counts in HALVES of the unified file on gfx90a and later -- the
 // compiler doubles what it is given -- so 104 stands for 208; tests/test_fit_registers.py holds the sum to 512.
 #define COL_VGPR_HALF 104
-#define COL_PSZ 800                // doubles per partial slot: 50 entries (A0[0..32], A1[16..32]) x 16 lanes
+#define COL_PSZ 672                // doubles per partial slot: the 42 accumulated entries (col_entry) x 16 lanes
+#define COL_NE 42
+#define COL_TL 304                 // doubles of LDS per lane row for the re-layout: four 8 x 8 blocks, rows of nine (288), and half the banks' worth
+                                   // between neighbouring lane rows (a ds_b64 access serves two lane rows at a time)
 
 #ifdef BDF_K1_STAMPS      // diagnostic build: per wave {start, end, rounds, cycles by phase summed over the wave's rounds} (s_memtime; bdf_debug_stamps)
-#define CSTAMP_DECL unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_acc = 0, st_mid = 0, st_prior = 0, st_fin = 0, st_rng = 0, st_steps = 0, st_rounds = 0, st_parts = 0, st_fins = 0, st_folds = 0; const unsigned long long st_begin = st_t
+#define CSTAMP_DECL unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_acc = 0, st_mid = 0, st_prior = 0, st_fin = 0, st_rng = 0, st_lay = 0, st_steps = 0, st_rounds = 0, st_parts = 0, st_fins = 0, st_folds = 0; const unsigned long long st_begin = st_t
 #define CSTAMP(x) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); x += now_ - st_t; st_t = now_; } while (0)
 #else
 #define CSTAMP_DECL do { } while (0)
@@ -57,9 +63,9 @@ struct ColCoef { static __device__ __forceinline__ double c(double x) { asm vola
 
 // K: the observation's position in its chunk of 16 (lane K of the lane row holds its value minus the mean)
 template <int DR, int K>
-__device__ __forceinline__ void col_obs(double (&A0)[33], double (&A1)[33], double v0, double v1, double r)
+__device__ __forceinline__ void col_obs(double (&A0)[33], double (&A1)[33], double v0, double v1, double r, bool h, uint64_t hmask)
 {
-    col_rank1<DR, 0>(A0, A1, v0, v1);
+    col_rank1u<DR>(A0, A1, v0, v1, h, hmask);
     fm1_run<K>(A0[32], r, v0);
     fm1_run<K>(A1[32], r, v1);
 }
@@ -96,25 +102,28 @@ __device__ __forceinline__ void col_gather4(double (&b)[4][2], __amdgpu_buffer_r
     }
 }
 template <int DR, int K0>
-__device__ __forceinline__ void col_compute4(double (&A0)[33], double (&A1)[33], const double (&b)[4][2], double r)
+__device__ __forceinline__ void col_compute4(double (&A0)[33], double (&A1)[33], const double (&b)[4][2], double r, bool h, uint64_t hmask)
 {
-    col_obs<DR, K0>(A0, A1, b[0][0], b[0][1], r);
-    col_obs<DR, K0 + 1>(A0, A1, b[1][0], b[1][1], r);
-    col_obs<DR, K0 + 2>(A0, A1, b[2][0], b[2][1], r);
-    col_obs<DR, K0 + 3>(A0, A1, b[3][0], b[3][1], r);
+    col_obs<DR, K0>(A0, A1, b[0][0], b[0][1], r, h, hmask);
+    col_obs<DR, K0 + 1>(A0, A1, b[1][0], b[1][1], r, h, hmask);
+    col_obs<DR, K0 + 2>(A0, A1, b[2][0], b[2][1], r, h, hmask);
+    col_obs<DR, K0 + 3>(A0, A1, b[3][0], b[3][1], r, h, hmask);
 }
 
-// butterfly over the lane rows: v += m * (v of lane ^ X), the 50 accumulated entries
+// the 42 accumulated entries in the order of a partial slot: A0[0..15] (P0 | M1), A0[32], A1[0..7] (P1), A1[16..31] (P2 | M3), A1[32]
+__device__ __forceinline__ double &col_entry(double (&A0)[33], double (&A1)[33], int e)
+{
+    return e < 16 ? A0[e] : e == 16 ? A0[32] : e < 25 ? A1[e - 17] : A1[e - 9];
+}
+// butterfly over the lane rows: v += m * (v of lane ^ X), the 42 accumulated entries
 template <int X>
 __device__ __forceinline__ void col_fold(double (&A0)[33], double (&A1)[33], double m)
 {
 #pragma unroll
-    for (int i = 0; i < 33; i++) A0[i] = fma(__shfl_xor(A0[i], X), m, A0[i]);
-#pragma unroll
-    for (int i = 16; i < 33; i++) A1[i] = fma(__shfl_xor(A1[i], X), m, A1[i]);
+    for (int e = 0; e < COL_NE; e++) { double &d = col_entry(A0, A1, e); d = fma(__shfl_xor(d, X), m, d); }
 }
 
-// entry e of a partial slot: A0[e] for e < 33, A1[e - 17] for 33 <= e < 50
+// entries E0 .. E1 - 1 of a partial slot
 // (src always points at a slot of the row -- a lane row without a slot of its own reads the first one again and multiplies it by 0:
 // a conditional load would become a branch per entry)
 template <int E0, int E1, bool ADD>
@@ -123,7 +132,7 @@ __device__ __forceinline__ void col_slot_load(double (&A0)[33], double (&A1)[33]
 #pragma unroll
     for (int e = E0; e < E1; e++) {
         const double v = src[e * 16];
-        double &d = e < 33 ? A0[e] : A1[e - 17];
+        double &d = col_entry(A0, A1, e);
         if (ADD) d = fma(v, m, d); else d = v * m;
     }
 }
@@ -159,7 +168,7 @@ __device__ __forceinline__ void col_prior_lds(double (&A)[33], const double *img
 template <int DR, bool FULL>
 __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(COL_VGPR_HALF))) void k_rows_col(SampleArgs a_in, ColPlanDev p_in, uint32_t fac_bytes)
 {
-    __shared__ __attribute__((aligned(16))) double lds[4 * 272 + 768];      // block (1,0) of the four systems on its way to block (0,1) | the prior's image
+    __shared__ __attribute__((aligned(16))) double lds[4 * COL_TL + 768];      // the re-layout of the four systems | the prior's image
     const int w = blockIdx.x;
     if (w >= p_in.n_waves) return;
     const int r_end = p_in.wave_round[w + 1];
@@ -176,6 +185,8 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
     const SampleArgs &a = (&a_in)[zero];
     const ColPlanDev &p = (&p_in)[zero];
     const int j = lane & 15, g = lane >> 4;
+    const bool hh = (j & 8) != 0;                          // the H lanes of a lane row (dpp_rows32.h, col_rank1u)
+    const uint64_t hmask = 0xff00ff00ff00ff00ull;
     const TermDev &T = a.t[0];
     const int D = FULL ? 32 : a.D;
     const int ec0 = D - 1 - j, ec1 = D - 17 - j;          // natural index of the reversed elements j, 16 + j (ec1 < 0: padding)
@@ -192,11 +203,11 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
         const int n = live ? jb.count : 0;
         // the prior's image on its way into LDS under the accumulation, if the draw is there already (a launch that did not wait
         // for it: one look at its flag, no spinning here)
-        const unsigned lds_img = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) double *)(lds + 4 * 272));
+        const unsigned lds_img = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) double *)(lds + 4 * COL_TL));
         bool have_prior = true;
         if (a.ready) have_prior = __builtin_amdgcn_readfirstlane((int)((int32_t)(__hip_atomic_load(a.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - a.ready_want) >= 0)) != 0;
         if (have_prior) col_prior_dma(a.prior_c, lds_img, lane);
-        // ---- accumulate: S~ (blocks (0,0), (1,0), (1,1)) and W r ----
+        // ---- accumulate: S~ (its ten unique 8 x 8 blocks: col_rank1u) and W r ----
         double A0[33], A1[33];
 #pragma unroll
         for (int i = 0; i < 33; i++) { A0[i] = 0.0; A1[i] = 0.0; }
@@ -230,19 +241,19 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
                 COL_CHUNK(c0 + 16, idw_n, r_n)
                 col_gather4<FULL, 4>(bb, rs, idw_c, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 0>(A0, A1, ba, r_c);
+                col_compute4<DR, 0>(A0, A1, ba, r_c, hh, hmask);
                 if (c0 + 4 >= nmax) break;
                 col_gather4<FULL, 8>(ba, rs, idw_c, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 4>(A0, A1, bb, r_c);
+                col_compute4<DR, 4>(A0, A1, bb, r_c, hh, hmask);
                 if (c0 + 8 >= nmax) break;
                 col_gather4<FULL, 12>(bb, rs, idw_c, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 8>(A0, A1, ba, r_c);
+                col_compute4<DR, 8>(A0, A1, ba, r_c, hh, hmask);
                 if (c0 + 12 >= nmax) break;
                 col_gather4<FULL, 0>(ba, rs, idw_n, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 12>(A0, A1, bb, r_c);
+                col_compute4<DR, 12>(A0, A1, bb, r_c, hh, hmask);
                 if (c0 + 16 >= nmax) break;
                 idw_c = idw_n; r_c = r_n;
             }
@@ -270,9 +281,7 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
             if (g == 0) {
                 // write-through (sc1) stores: the slab needs no L2 write-back (k_rows' protocol)
 #pragma unroll
-                for (int e = 0; e < 33; e++) __hip_atomic_store(dst + e * 16, A0[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-                for (int e = 33; e < 50; e++) __hip_atomic_store(dst + e * 16, A1[e - 17], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int e = 0; e < COL_NE; e++) __hip_atomic_store(dst + e * 16, col_entry(A0, A1, e), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             const ColSplit sr = p.rows[srow];
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -290,16 +299,16 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
             // lane row g sums slots g, g + 4, ... in that order (the first one straight into the registers: all its loads in
             // flight at once), then the butterfly: the same sums whichever part does it
             const double *src = p.partials + (int64_t)sr.slot_begin * COL_PSZ + j;
-            col_slot_load<0, 50, false>(A0, A1, src + (int64_t)(g < sr.n_slots ? g : 0) * COL_PSZ, g < sr.n_slots ? 1.0 : 0.0);
+            col_slot_load<0, COL_NE, false>(A0, A1, src + (int64_t)(g < sr.n_slots ? g : 0) * COL_PSZ, g < sr.n_slots ? 1.0 : 0.0);
             for (int s0 = 4; s0 < sr.n_slots; s0 += 4) {
                 const bool on = s0 + g < sr.n_slots;
                 const double *sp = src + (int64_t)(on ? s0 + g : 0) * COL_PSZ;
                 const double m = on ? 1.0 : 0.0;
-                col_slot_load<0, 16, true>(A0, A1, sp, m);
+                col_slot_load<0, 14, true>(A0, A1, sp, m);
                 asm volatile("" ::: "memory");
-                col_slot_load<16, 33, true>(A0, A1, sp, m);
+                col_slot_load<14, 28, true>(A0, A1, sp, m);
                 asm volatile("" ::: "memory");
-                col_slot_load<33, 50, true>(A0, A1, sp, m);
+                col_slot_load<28, COL_NE, true>(A0, A1, sp, m);
                 asm volatile("" ::: "memory");
             }
             col_fold<16>(A0, A1, 1.0);
@@ -317,19 +326,61 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
             z0 = (n0 & 1) ? zo0 : ze0;
             z1 = ok1 ? ((n1 & 1) ? zo1 : ze1) : 0.0;
         }
-        asm volatile("" ::: "memory");
+        // (the two selected here: left to itself the compiler carries the four candidates through the re-layout and the prior)
+        asm volatile("" : "+v"(z0), "+v"(z1) :: "memory");
         CSTAMP(st_rng);
-        // ---- block (0,1) = block (1,0)': lane j's entry (i, 16 + j) is lane i's entry (16 + j, i) ----
+        // ---- the re-layout: what the sixty-four natural registers miss is in another lane by symmetry (dpp_rows32.h, col_rank1u).  8 x 8
+        // blocks through LDS, rows of nine doubles, in two phases; jl: the lane in its half.  Block M1L is written transposed and so
+        // are P1's halves, P0H and P2H: every read is base + 9 i or base + i with one base per lane ----
         {
-            double *tl = lds + g * 272;
+            double *tl = lds + g * COL_TL;
+            const int jl = j & 7;
+            // phase 1: M1L' at 0, M3L at 72, P1L' at 144, P1H' at 216
+            if (!hh) {
 #pragma unroll
-            for (int r = 0; r < 16; r++) tl[r * 17 + j] = A0[16 + r];
+                for (int i = 0; i < 8; i++) tl[jl * 9 + i] = A0[8 + i];
+#pragma unroll
+                for (int i = 0; i < 8; i++) tl[72 + i * 9 + jl] = A1[24 + i];
+            }
+            {
+                double *w = tl + 144 + (hh ? 72 : 0) + jl * 9;
+#pragma unroll
+                for (int i = 0; i < 8; i++) w[i] = A1[i];
+            }
             wave_sync();
+            {
+                const double *r2 = tl + (hh ? 72 : 0) + jl * 9;      // A1[8+i]: L (8+i, 16+j) = M1[i] as it was; H = (24+jl, 8+i) = M3[jl], lane i
+                const double *r3 = tl + (hh ? 0 : 144) + jl;         // A0[16+i]: L = (j, 16+i) = P1[j], lane i; H = (8+jl, 16+i) = M1[jl], lane i
+                const double *r4 = tl + (hh ? 72 : 216) + jl;        // A0[24+i]: L = (j, 24+i) = P1[j], lane 8+i; H = M3[i], lane jl
 #pragma unroll
-            for (int i = 0; i < 16; i++) A1[i] = tl[j * 17 + i];
+                for (int i = 0; i < 8; i++) A1[8 + i] = r2[i];
+#pragma unroll
+                for (int i = 0; i < 8; i++) if (16 + i < DR) A0[16 + i] = r3[i * 9];
+#pragma unroll
+                for (int i = 0; i < 8; i++) if (24 + i < DR) A0[24 + i] = r4[i * 9];
+            }
+            wave_sync();
+            // phase 2: P0H' at 0, P2H' at 72 -- the L halves of A0[8+i] (= (j, 8+i) = P0[j], lane 8+i) over M1's and of A1[24+i]
+            // (= (16+j, 24+i) = P2[j], lane 8+i) over M3's
+            if (hh) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) tl[jl * 9 + i] = A0[i];
+#pragma unroll
+                for (int i = 0; i < 8; i++) tl[72 + jl * 9 + i] = A1[16 + i];
+            }
+            wave_sync();
+            if (!hh) {
+#pragma unroll
+                for (int i = 0; i < 8; i++) A0[8 + i] = tl[i * 9 + jl];
+#pragma unroll
+                for (int i = 0; i < 8; i++) if (24 + i < DR) A1[24 + i] = tl[72 + i * 9 + jl];
+            }
             wave_sync();
         }
-        CSTAMP(st_mid);
+#ifdef BDF_K1_STAMPS
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_nop 0" :: "v"(A0[8]), "v"(A0[31]), "v"(A1[8]), "v"(A1[31]));
+#endif
+        CSTAMP(st_lay);
         // ---- P~ = alpha S~ + Lambda~, b~ = alpha W r + Lambda mu: the prior pack (polled for when the launch did not wait for the draw) ----
         const double alpha = term_alpha(T);
         if (!have_prior) {
@@ -346,7 +397,7 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
             const double b1 = __hip_atomic_load(pb + n1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the image has landed (nothing else orders a ds_read behind an LDS-DMA)
             wave_sync();
-            const double *img = lds + 4 * 272;
+            const double *img = lds + 4 * COL_TL;
             col_prior_lds<0, 0, DR>(A0, img, alpha, j);
             col_prior_lds<1, 0, DR>(A1, img, alpha, j);
             A0[32] = fma(alpha, A0[32], b0);
@@ -382,7 +433,7 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
     if (threadIdx.x == 0 && a_in.b_dump && w < 65536) {
         unsigned long long *d = (unsigned long long *)a_in.b_dump + (size_t)w * 16;
         d[0] = st_begin; d[8] = st_t; d[6] = st_rounds; d[7] = st_steps;
-        d[1] = st_parts; d[2] = st_fins; d[3] = st_folds;
+        d[1] = st_parts; d[2] = st_fins; d[3] = st_folds; d[4] = st_lay;
         d[11] = st_rng; d[12] = st_acc; d[13] = st_mid; d[14] = st_prior; d[15] = st_fin;
         d[9] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4));
         d[10] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20);
@@ -391,7 +442,7 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
 }
 
 // ---- host: rows -> units (a row, or its 2 / 4 pieces, or the parts of a row that spans waves) -> rounds -> waves ------------
-#define COL_C_OBS 56.0             // cost model (vector instructions): per observation of a round's longest piece,
+#define COL_C_OBS 52.0             // cost model (vector instructions): per observation of a round's longest piece (49 in the loop and the chunk's share),
 #define COL_C_FIN 1460.0           // the finish of a round (normals, prior, factorisation, solves),
 #define COL_C_FOLD 180.0           // the butterfly sums of a round with pieces,
 #define COL_C_PART 700.0           // a part's store to the slab

@@ -1,7 +1,8 @@
 """Per-wave phase times of K1c (k_rows_col.hip; diagnostic build: tools/ab_k1.sh build stamps "-DBDF_K1_STAMPS").
 Run on the GPU box:  BDF_LIB_PATH=.../variants/libbdf_stamps.so python3 tools/col_stamps.py
 Per wave: start, end, rounds, observation steps (the longest piece of every round, summed), and the cycles (s_memtime) spent in
-normals | accumulation | butterfly sums + slab | prior (incl. waiting for the draw) | factorisation + solves, summed over its rounds."""
+normals | accumulation | butterfly sums + slab | re-layout of the unique blocks | prior (incl. waiting for the draw) | factorisation + solves,
+summed over its rounds."""
 import ctypes as C
 import os
 import sys
@@ -35,11 +36,12 @@ for j, name in enumerate(("users", "movies")):
     span = t1 - t0
     print(f"== {name}: {live.sum()} waves, span {span} cycles; rounds/wave {s[:, 6].mean():.2f} (max {s[:, 6].max()}), steps/wave {s[:, 7].mean():.1f} (max {s[:, 7].max()})")
     tot = s[:, 8] - s[:, 0]
-    for nm, c in (("normals", 11), ("accumulate", 12), ("sums+slab", 13), ("prior", 14), ("finish", 15)):
+    for nm, c in (("normals", 11), ("accumulate", 12), ("sums+slab", 13), ("re-layout", 4), ("prior", 14), ("finish", 15)):
         print(f"   {nm:11s} mean {s[:, c].mean():8.0f}  p50 {np.median(s[:, c]):8.0f}  max {s[:, c].max():8d}   share {s[:, c].sum() / tot.sum():.3f}")
     print(f"   wave total  mean {tot.mean():8.0f}  p50 {np.median(tot):8.0f}  max {tot.max():8d}  min {tot.min():8d}")
     print(f"   accumulate cycles per step: {s[:, 12].sum() / max(s[:, 7].sum(), 1):.1f};  finish cycles per round: {s[:, 15].sum() / max(s[:, 6].sum(), 1):.0f};"
-          f"  normals per round {s[:, 11].sum() / max(s[:, 6].sum(), 1):.0f};  prior per round {s[:, 14].sum() / max(s[:, 6].sum(), 1):.0f}")
+          f"  normals per round {s[:, 11].sum() / max(s[:, 6].sum(), 1):.0f};  prior per round {s[:, 14].sum() / max(s[:, 6].sum(), 1):.0f};"
+          f"  re-layout per round {s[:, 4].sum() / max(s[:, 6].sum(), 1):.0f}")
     print("   wave totals deciles", np.round(np.quantile(tot, np.linspace(0, 1, 11))).astype(int))
     for w_ in np.argsort(-tot)[:8]:
         print(f"   slow wave {w_}: total {tot[w_]} rounds {s[w_, 6]} steps {s[w_, 7]} parts {s[w_, 1]} finisher {s[w_, 2]} folds {s[w_, 3]} | normals {s[w_, 11]} acc {s[w_, 12]} sums+slab {s[w_, 13]} prior {s[w_, 14]} finish {s[w_, 15]}")
@@ -63,6 +65,15 @@ for j, name in enumerate(("users", "movies")):
     vals, cnts = np.unique(diffs, return_counts=True)
     top = np.argsort(-cnts)[:8]
     print("   wave-number distance of the two waves of a SIMD (distance: SIMDs):", {int(vals[t]): int(cnts[t]) for t in top})
+    older, younger = [], []
+    for kx in np.unique(key):
+        m = np.nonzero(key == kx)[0]
+        if len(m) == 2:
+            o, y = (m[0], m[1]) if s[m[0], 0] <= s[m[1], 0] else (m[1], m[0])
+            older.append(o); younger.append(y)
+    for nm, m in (("older", older), ("younger", younger)):
+        if m:
+            print(f"   accumulate cycles per step, the {nm} wave of a SIMD's two: {s[m, 12].sum() / max(s[m, 7].sum(), 1):.1f} ({len(m)} waves, {s[m, 7].mean():.1f} steps each)")
     pair_tot = []
     for kx in np.unique(key):
         m = key == kx
