@@ -22,6 +22,7 @@ P_INTERVAL = 14
 P_ORDINAL = 15
 P_ROBUST_N, P_ROBUST_U = 16, 17
 P_PG = 18
+P_NOISE_N, P_NOISE_U = 19, 20
 
 
 class ArgumentError(ValueError):
@@ -93,7 +94,9 @@ class GibbsRelation(C.Structure):
                 ("interval", C.c_void_p), ("ordinal", C.c_void_p), ("ordinal_codes", C.c_void_p),
                 ("robust_nu", C.c_double), ("obs_precision", C.c_void_p),
                 ("pg_model", C.c_int32), ("_pad_pg", C.c_int32), ("pg_r", C.c_double),
-                ("bg_weight", C.c_double), ("bg_value", C.c_double), ("bg_sums", C.c_void_p), ("bg_weights", C.c_void_p)]
+                ("bg_weight", C.c_double), ("bg_value", C.c_double), ("bg_sums", C.c_void_p), ("bg_weights", C.c_void_p),
+                ("noise_mode", C.c_int32), ("_pad_noise", C.c_int32), ("noise_shape", C.c_double), ("noise_rate", C.c_double),
+                ("noise_tau", C.c_void_p)]
 
 
 class BackgroundTerm(C.Structure):
@@ -162,6 +165,9 @@ _SIGS = {
                                   C.c_uint32, C.c_void_p, C.c_void_p]),
     "bdf_pg_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_int, C.c_double, C.c_uint32,
                               C.c_void_p, C.c_void_p]),
+    "bdf_entity_noise_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double,
+                                        C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_pairs_set_precision_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "bdf_pairs_weighted_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
     "bdf_background_prior": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(BackgroundTerm), C.c_void_p, C.c_int, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -184,6 +184,8 @@ struct bdf_pairs {
     double lpd_draws;             // ... and the posterior draws it holds (a counter of its own, not `count`)
     double *waic_dev;             // bdf_pairs_waic_update's running state (k_waic.hip): four planes of n in storage order -- M, A, mean, M2; at first use
     double waic_draws;            // ... and the posterior draws it holds (a counter of its own)
+    const double *scale_dev;      // nullable, borrowed (bdf_pairs_set_precision_scale): a precision scale per row of mode scale_mode, for k_lpd
+    int scale_mode;
 };
 
 // bdf_ordinal (k_ordinal.hip): the edges of an ordinal relation and their Metropolis step's state, all of it in ONE device buffer

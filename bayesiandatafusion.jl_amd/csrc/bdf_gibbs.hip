@@ -381,6 +381,16 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
         BDF_REQUIRE(!r.interval || (!r.probit && !r.censor && !r.feat), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model takes neither the probit model, censoring flags nor relation features", k);
         BDF_REQUIRE(!r.interval || (r.train && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the interval model needs its observations as pairs (train) and a linear buffer", k);
         BDF_REQUIRE(!r.ordinal || (r.interval && r.ordinal_codes && !g->comm), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the ordinal model needs the interval model's bounds and the observations' levels, on one rank", k);
+        if (r.noise_mode != 0) {
+            BDF_REQUIRE(r.noise_mode >= 1 && r.noise_mode <= r.rel->n_modes, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: noise_mode=%d must be 0 (none) or one of the relation's modes 1..%d", k, r.noise_mode, r.rel->n_modes);
+            BDF_REQUIRE(r.noise_shape > 0.0 && std::isfinite(r.noise_shape) && r.noise_rate > 0.0 && std::isfinite(r.noise_rate), BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: noise_shape=%g and noise_rate=%g must be positive and finite", k, r.noise_shape, r.noise_rate);
+            BDF_REQUIRE(r.train && r.obs_precision && r.noise_tau, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: the per-row noise model (noise_mode) needs its observations as pairs (train), an obs_precision and a noise_tau buffer", k);
+            BDF_REQUIRE(!r.probit && !r.censor && !r.interval && !r.ordinal && r.robust_nu == 0.0 && !r.pg_model && !(r.bg_weight > 0.0) && !r.feat && !g->comm, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: the per-row noise model (noise_mode) takes neither the probit, censored, interval, ordinal, robust or a Polya-Gamma model, a background, relation features nor a communicator", k);
+        }
         BDF_REQUIRE(r.robust_nu == 0.0 || (r.robust_nu >= 1.0 && std::isfinite(r.robust_nu)), BDF_ERR_ARG,
                     "bdf_gibbs_set_relations: relation %d: robust_nu=%g must be 0 (off) or at least 1 and finite", k, r.robust_nu);
         BDF_REQUIRE(!(r.robust_nu > 0.0) || (r.train && r.obs_precision), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the robust model needs its observations as pairs (train) and an obs_precision buffer", k);
@@ -431,7 +441,7 @@ const bdf_gibbs_relation *relation_of(const bdf_gibbs *g, const bdf_rel *rel)
 inline bool draws_latent(const bdf_gibbs_relation &r) { return r.probit || r.censor || r.interval || r.pg_model; }
 
 // does update_relations() enqueue anything for the relation?  (Known weights alone do not: the rows just read them.)
-inline bool has_model(const bdf_gibbs_relation &r) { return r.alpha_sample || r.feat || draws_latent(r) || r.robust_nu > 0.0; }
+inline bool has_model(const bdf_gibbs_relation &r) { return r.alpha_sample || r.feat || draws_latent(r) || r.robust_nu > 0.0 || r.noise_mode != 0; }
 
 // out[m] = the current sample of the entity that is mode m
 void current_factors(const bdf_gibbs *g, const int32_t *entity_of_mode, int n_modes, const double **out)
@@ -525,6 +535,11 @@ int update_relations(bdf_gibbs *g)
         if (r.robust_nu > 0.0 && (rc = bdf_robust_draw(R, r.train, D, fac, r.mean_value, 0.0, r.alpha_dev, r.robust_nu, r.rel_tag, r.obs_precision,
                                                       r.alpha_sample ? g->rel_sse + 1 : nullptr)))
             return rc;
+        // a noise precision per row of one entity: tau of every row of that entity at the same place and in the same manner; it leaves
+        // sum tau_j S_j for sample_alpha and tau of every observation's row in obs_precision
+        if (r.noise_mode != 0 && (rc = bdf_entity_noise_draw(R, r.rel, r.noise_mode - 1, r.train, D, fac, r.mean_value, 0.0, r.alpha_dev, r.noise_shape,
+                                                             r.noise_rate, r.rel_tag, r.noise_tau, r.obs_precision, r.alpha_sample ? g->rel_sse + 1 : nullptr)))
+            return rc;
         if (r.alpha_sample) {
             // err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known weights:
             // sum w e^2 (the robust draw above has left its own)
@@ -537,7 +552,7 @@ int update_relations(bdf_gibbs *g)
                 rc = bdf_background_sse(R, r.train, D, fac, r.mean_value, r.bg_weights, r.bg_value, r.bg_weight, r.bg_sums, r.bg_sums + D, r.bg_sums + pk,
                                         r.bg_sums + pk + D, r.rel->dims[0], r.rel->dims[1], g->rel_sse + 1);
                 n = r.rel->dims[0] * r.rel->dims[1];
-            } else if (r.obs_precision) rc = r.robust_nu > 0.0 ? BDF_OK : bdf_pairs_weighted_sse(R, r.train, D, fac, r.mean_value, r.obs_precision, g->rel_sse + 1);
+            } else if (r.obs_precision) rc = (r.robust_nu > 0.0 || r.noise_mode != 0) ? BDF_OK : bdf_pairs_weighted_sse(R, r.train, D, fac, r.mean_value, r.obs_precision, g->rel_sse + 1);
             else rc = bdf_predict_sse(R, r.train, D, fac, r.mean_value, nullptr, g->rel_sse);
             if (rc) return rc;
             if (g->comm && (rc = bdf_sum_ranks(R, g->comm, g->rel_sse + 1, 1))) return rc;
@@ -668,7 +683,8 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         }
         // the last draw: y - z (probit), mean + y - z (censored, interval)
         if (draws_latent(r)) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});
-        if (r.robust_nu > 0.0 || r.pg_model) pieces.push_back({r.obs_precision, (size_t)r.train->n * sizeof(double), false, 0});       // the last omega
+        if (r.robust_nu > 0.0 || r.pg_model || r.noise_mode != 0) pieces.push_back({r.obs_precision, (size_t)r.train->n * sizeof(double), false, 0});       // the last omega
+        if (r.noise_mode != 0) pieces.push_back({r.noise_tau, (size_t)r.rel->dims[r.noise_mode - 1] * sizeof(double), false, 0});           // ... and the last tau
         if (r.ordinal) {                    // the edges, the step size, the counters and the trace; the bounds made from the edges
             pieces.push_back({r.ordinal->state_dev, r.ordinal->state_doubles * sizeof(double), false, 0});
             pieces.push_back({const_cast<double *>(r.interval), (size_t)r.train->n * 2 * sizeof(double), false, 0});

@@ -6,41 +6,20 @@
 // bdf_lpd_record of lpd.h) behind the shared lane prologue, gather and dot product.  The running state is a streaming log-sum-exp, two doubles per pair in storage order: M the largest l so far and A = sum exp(l - M).
 // The two sums over the pairs -- of l and of lpd -- go through the per-workgroup statistics and the fixed-order sum of predict.h.
 //
+// bdf_pairs_set_precision_scale: under the per-row noise model a cell is scored with alpha tau[its id in one
+// mode]; the pairs then take k_lpd_scaled (k_lpd_scaled.hip: the same body, lpd_body.h, with SCALED set), and k_lpd is untouched.
+//
 // bdf_pairs_lpd: lpd_t = M + log A - log(draws) in the caller's order.
 //
 // No LDS beyond the statistics' reduction, no scratch, plain vector stores.
-#include "bdf_common.h"
-#include "predict.h"
-#include "pair_gather.h"
+#include "lpd_body.h"
 
 namespace {
 
-struct LpdArgs {
-    RecordArgs rec;
-    double log_draws;              // phase 2: log of the draws the state holds after this one
-    double *M, *A;                 // the running state, storage order
-};
-
-// No grid-stride loop, as k_interval_draw and for its reason: around a loop the constants of the two erfc, of exp, log, log1p and
-// expm1 stay in VGPRs across the gather's BATCH x NM x NC double4.  Every lane reaches the statistics' barrier.
 template <int NM, int VEC, int NC>
 __global__ __launch_bounds__(256, (VEC == 4 && NM * NC >= 8) ? 2 : 3) void k_lpd(LpdArgs a)
 {
-    double st[4] = {0.0, 0.0, 0.0, 0.0};
-    int64_t pm;
-    double l;
-    if (record_loglik<NM, VEC, NC>(a.rec, pm, l)) {
-        double lpd = l;
-        if (a.rec.phase == 1) { a.M[pm] = l; a.A[pm] = 1.0; }
-        else if (a.rec.phase == 2) {
-            const double M = a.M[pm], Mn = fmax(M, l);
-            const double A = a.A[pm] * exp(M - Mn) + exp(l - Mn);
-            a.M[pm] = Mn; a.A[pm] = A;
-            lpd = Mn + log(A) - a.log_draws;
-        }
-        st[0] = l; st[1] = lpd;
-    }
-    block_stats(a.rec.partial, st);
+    lpd_body<NM, VEC, NC, false>(a);
 }
 
 struct LpdReadArgs {
@@ -68,6 +47,7 @@ extern "C" int bdf_pairs_lpd_update(bdf_ctx *ctx, bdf_pairs *p, const double *bo
                          phase, stats_out, a.rec, &nblocks);
     if (rc) return rc;
     BDF_REQUIRE(phase != 2 || p->lpd_draws >= 1.0, BDF_ERR_ARG, "bdf_pairs_lpd_update: phase 2 before a phase 1: the pairs hold no draw");
+    BDF_REQUIRE(!(p->scale_dev && p->link == 1), BDF_ERR_ARG, "bdf_pairs_lpd_update: pairs with the probit link take no precision scale");
     const int64_t n = p->n;
     BDF_HIP(hipSetDevice(ctx->device));
     if (n == 0) {
@@ -79,10 +59,23 @@ extern "C" int bdf_pairs_lpd_update(bdf_ctx *ctx, bdf_pairs *p, const double *bo
         }
         a.M = p->lpd_dev; a.A = p->lpd_dev ? p->lpd_dev + n : nullptr;
         a.log_draws = phase == 2 ? log(p->lpd_draws + 1.0) : 0.0;
-        if ((rc = launch_reduced(ctx, nblocks, a.rec.partial, stats_out, [&] { BDF_BY_SHAPE(k_lpd, p->n_modes, D, nblocks, ctx->stream, a); }))) return rc;
+        a.scale = p->scale_dev; a.scale_mode = p->scale_mode;
+        if (a.scale) rc = bdf_lpd_launch_scaled(ctx, p->n_modes, D, nblocks, &a, sizeof(a), stats_out);
+        else rc = launch_reduced(ctx, nblocks, a.rec.partial, stats_out, [&] { BDF_BY_SHAPE(k_lpd, p->n_modes, D, nblocks, ctx->stream, a); });
+        if (rc) return rc;
     }
     if (phase == 1) p->lpd_draws = 1.0;
     else if (phase == 2) p->lpd_draws += 1.0;
+    return BDF_OK;
+}
+
+extern "C" int bdf_pairs_set_precision_scale(bdf_pairs *p, const double *tau_dev, int mode)
+{
+    BDF_REQUIRE(p != nullptr, BDF_ERR_ARG, "bdf_pairs_set_precision_scale: NULL argument");
+    if (!tau_dev) { p->scale_dev = nullptr; p->scale_mode = 0; return BDF_OK; }
+    BDF_REQUIRE(mode >= 0 && mode < p->n_modes, BDF_ERR_ARG, "bdf_pairs_set_precision_scale: mode=%d must be in 0..%d", mode, p->n_modes - 1);
+    BDF_REQUIRE(p->link != 1, BDF_ERR_ARG, "bdf_pairs_set_precision_scale: pairs with the probit link take no precision scale");
+    p->scale_dev = tau_dev; p->scale_mode = mode;
     return BDF_OK;
 }
 

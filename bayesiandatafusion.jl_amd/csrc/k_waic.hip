@@ -94,6 +94,7 @@ extern "C" int bdf_pairs_waic_update(bdf_ctx *ctx, bdf_pairs *p, const double *b
                          alpha_dev, phase, stats_out, a.rec, &nblocks);
     if (rc) return rc;
     BDF_REQUIRE(phase != 2 || p->waic_draws >= 1.0, BDF_ERR_ARG, "bdf_pairs_waic_update: phase 2 before a phase 1: the pairs hold no draw");
+    BDF_REQUIRE(!p->scale_dev, BDF_ERR_ARG, "bdf_pairs_waic_update: pairs with a precision scale (bdf_pairs_set_precision_scale) are not scored yet");
     const int64_t n = p->n;
     BDF_HIP(hipSetDevice(ctx->device));
     if (n == 0) {

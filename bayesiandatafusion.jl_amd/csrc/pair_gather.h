@@ -176,11 +176,12 @@ struct RecordArgs {
 };
 
 // One group of 8 lanes per 8 pairs.  The log-likelihood l of the record that this lane owns (lpd.h: the owning lane fetches its
-// (lo, hi) with one 16-byte load) and pm, where its running state is stored; false in a lane that owns none.
-template <int NM, int VEC, int NC>
-__device__ __forceinline__ bool record_loglik(const RecordArgs &r, int64_t &pm, double &l)
+// (lo, hi) with one 16-byte load) and pm, where its running state is stored; false in a lane that owns none.  SCALED (k_lpd under
+// the per-row noise model, bdf_pairs_set_precision_scale): the record's precision is alpha scale[its id in mode scale_mode].
+template <int NM, int VEC, int NC, bool SCALED = false>
+__device__ __forceinline__ bool record_loglik(const RecordArgs &r, int64_t &pm, double &l, const double *scale = nullptr, int scale_mode = 0)
 {
-    const double alpha = pair_alpha(r.pair);
+    double alpha = pair_alpha(r.pair);
     const int64_t trip = pair_trip();
     if (trip * 8 >= r.pair.n) return false;
     PairLane<NM> ln;
@@ -192,6 +193,13 @@ __device__ __forceinline__ bool record_loglik(const RecordArgs &r, int64_t &pm, 
     const double m = pair_dot<NM, VEC, NC>(r.pair, ln) + base;
     if (!ln.ok) return false;
     pm = ln.pm;
+    if constexpr (SCALED) {
+        int32_t id = ln.my[0];
+#pragma unroll
+        for (int k = 1; k < NM; k++)
+            if (scale_mode == k) id = ln.my[k];
+        alpha *= scale[id];
+    }
     l = bdf_lpd_record(r.link, y, m, lo, hi, alpha);
     return true;
 }

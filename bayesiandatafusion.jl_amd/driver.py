@@ -73,6 +73,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if lpd and kind in ("robust", "weights"):
         what = "the robust noise model (setRobust)" if kind == "robust" else "observation weights (setWeights)"
         raise ArgumentError(f"lpd = true is not possible when Relation has {what}: a held-out cell's density under it is not scored yet.")
+    # a noise precision per row of one entity (setEntityNoise): sampled on any relation, reported for the first
+    noise = data.relations[0].model.entity_noise if data.relations else None
     if lpd and kind in ("logit", "counts"):
         raise ArgumentError(f"lpd = true is not possible when Relation has the {kind} noise model "
                             "(setLogit / setCounts): a held-out cell's density under it is not scored yet.")
@@ -104,6 +106,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         eng.begin_scores()                                   # (an engine that is reused starts the sum of scores again)
     if robust is not None:
         eng.rel[0].omega_sum = None                          # (an engine that is reused starts the posterior mean of omega again)
+    if noise is not None:
+        eng.rel[0].tau_sum = None                            # (... and of tau)
     D = eng.D
 
     latent_multi_threading = (len(latent_pids) >= 1 and len(data.relations) == 1 and not hasFeatures(data.relations[0]))
@@ -170,6 +174,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             eng.scores.push(facs[0], facs[1])                 # this draw's factors into the ring, on the row stream (a full ring: one accumulate launch)
         if robust is not None and i > burnin:
             eng.robust_accumulate()                           # this iteration's omega into its running sum, on the row stream
+        if noise is not None and i > burnin:
+            eng.entity_noise_accumulate()                     # this iteration's tau into its running sum, on the row stream
         if lpd or waic is not None:
             # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
             # has read the same double, and the device scalar is redrawn on another stream than the pairs')
@@ -179,9 +185,10 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 # this draw's edges were published on the row stream before this iteration's rows, which the pairs' stream is behind
                 ordinal.bounds(test.ctx, lpd_codes, lpd_bounds)
             test.lpd_update(D, facs, rel.model.mean_value, a, phase, lpd_bounds)
-            if lpd_codes is not None and test.ctx is not eng.ctx:
-                # (step by step the pairs have a stream of their own: the next iteration's step may not publish its edges under this
-                # launch.  The native iteration scores on the row stream itself and needs nothing)
+            if (lpd_codes is not None or noise is not None) and test.ctx is not eng.ctx:
+                # (step by step the pairs have a stream of their own: the next iteration's step may not publish its edges -- or redraw
+                # the tau that the cells are scored with -- under this launch.  The native iteration scores on the row stream itself
+                # and needs nothing)
                 eng.ctx.stream.wait_stream(test.ctx.stream)
         if waic is not None:
             if waic_codes is not None:        # this draw's edges, ordered as for the test cells above
@@ -219,6 +226,7 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 # on the same stream; it lands beside the 4 stats (test.report), read back together after the one sync
                 test.auc(rel.class_cut, eng.ctx_p)
             wbar = eng.robust_mean() if (verbose and robust is not None) else None
+            tbar = eng.entity_noise_mean() if (verbose and noise is not None) else None
             eng.sync()
             eng.sync_host_scalars()
             if haveTest:
@@ -240,6 +248,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                     lstr += f" ELPD={(waic_stats[1] - waic_stats[2]) / max(waic_pairs.n, 1):.4f}"
                 if wbar is not None:
                     lstr += f" w̄={float(wbar.item()):.3f}"
+                if tbar is not None:
+                    lstr += f" τ̄={float(tbar.item()):.3f}"
                 if ordinal is not None:
                     lstr += " cut=[" + " ".join(f"{e:.3f}" for e in rel.model.ordinal_edges) + "]"
                 print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f}{lstr} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
@@ -279,6 +289,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         ws = rel._dev.omega_sum
         result["robust"] = {"nu": robust["nu"],
                             "weights": (ws.cpu().numpy()[:rel.data.nnz()] / psamples) if (ws is not None and psamples) else np.full(rel.data.nnz(), np.nan)}
+    if noise is not None:
+        # the posterior mean of every row's tau, in the order of the entity's rows: the rows with a small one are the noisy ones
+        ts, N = rel._dev.tau_sum, int(rel.data.dims[noise["mode"] - 1])
+        result["noise"] = {"entity": rel.entities[noise["mode"] - 1].name, "shape": noise["shape"], "rate": noise["rate"],
+                           "precision": (ts.cpu().numpy()[:N] / psamples) if (ts is not None and psamples) else np.full(N, np.nan)}
     if lpd:
         result["LPD"] = lpd_avg
     # relations with background cells (setBackground): what every unlisted cell observed, and how many there were

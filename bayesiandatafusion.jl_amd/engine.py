@@ -253,6 +253,8 @@ class DeviceRelation:
         self.censor = self.interval = self.ordinal = self.ord_codes = None
         self.omega = self.wsse = self.omega_sum = None          # obs_precision of the row kernels; sum omega e^2; omega's running sum
         self.robust_nu, self.pg_model, self.pg_r = 0.0, 0, 0.0
+        # a noise precision per row of one entity (setEntityNoise): {"mode", "shape", "rate"}; tau per row of that mode; its running sum
+        self.noise = self.tau = self.tau_sum = None
         # background cells (setBackground): {"weight", "value"}; the two modes' sums and Gram matrices; the caller's weights (omega is
         # then what the rows read, omega_k - c0)
         self.bg = self.bg_sums = self.bg_weights = None
@@ -324,6 +326,13 @@ class DevicePairs:
     def set_link(self, link):
         """0: predictions are udot + base (the default); 1: the probit link, probabilities Phi(udot + base) (bdf_pairs_set_link)"""
         check(lib().bdf_pairs_set_link(self.handle, int(link)))
+        return self
+
+    def set_precision_scale(self, tau, mode0=0):
+        """lpd_update scores pair k with alpha tau[its id in mode mode0] (bdf_pairs_set_precision_scale): tau, a device tensor with one
+        double per row of that mode, is read at every update (the per-row noise model's draw); None clears it"""
+        check(lib().bdf_pairs_set_precision_scale(self.handle, _ptr(tau), int(mode0)))
+        self._scale = tau                # (borrowed by the library: keep it alive)
         return self
 
     def set_pg_link(self, model, r=0.0):
@@ -971,6 +980,14 @@ class GibbsEngine:
             dr.omega = ctx.tensor(m.weights if (kind == "weights" and nn) else np.ones(max(nn, 1)))
             dr.wsse = ctx.zeros(1)
             dr.robust_nu = float(m.robust["nu"]) if kind == "robust" else 0.0
+        elif kind == "entity_noise":
+            # a noise precision tau_j per row of one entity, drawn where the robust model draws omega
+            # (bdf_entity_noise_draw): tau per row of that mode, and -- what the row kernels of EVERY entity read as obs_precision --
+            # tau of its row per training cell; the draw also leaves sum tau_j S_j for sample_alpha
+            dr.noise = dict(m.entity_noise)
+            dr.omega = ctx.tensor(np.ones(max(nn, 1)))
+            dr.tau = ctx.tensor(np.ones(max(int(r.data.dims[dr.noise["mode"] - 1]), 1)))
+            dr.wsse = ctx.zeros(1)
         elif kind in ("logit", "counts"):
             # bdf_pg_draw: omega of every training row, the rows' obs_precision beside linear_values; the training pairs predict
             # through the model's link (rmse_train)
@@ -1058,6 +1075,8 @@ class GibbsEngine:
             g.probit, g.robust_nu, g.pg_model, g.pg_r = int(dr.kind == "probit"), dr.robust_nu, dr.pg_model, dr.pg_r
             if dr.bg is not None:
                 g.bg_weight, g.bg_value = dr.bg["weight"], dr.bg["value"]
+            if dr.noise is not None:
+                g.noise_mode, g.noise_shape, g.noise_rate, g.noise_tau = dr.noise["mode"], dr.noise["shape"], dr.noise["rate"], dr.tau.data_ptr()
             for name, t in (("linear", dr.linear), ("censor", dr.censor), ("interval", dr.interval), ("ordinal_codes", dr.ord_codes),
                             ("obs_precision", dr.omega), ("beta", dr.beta), ("bg_sums", dr.bg_sums), ("bg_weights", dr.bg_weights)):
                 if t is not None:
@@ -1096,6 +1115,20 @@ class GibbsEngine:
         """-> a device scalar, the mean of this iteration's omega (the verbose line reads it with the other scalars)"""
         with torch.cuda.stream(self.ctx.stream):
             return self.rel[ri].omega.mean()
+
+    def entity_noise_accumulate(self, ri=0):
+        """(relation ri with a noise precision per row, after the burn-in) this iteration's tau into the running sum, on the row
+        stream: behind the draw that wrote it and ahead of the next one"""
+        dr = self.rel[ri]
+        with torch.cuda.stream(self.ctx.stream):
+            if dr.tau_sum is None:
+                dr.tau_sum = torch.zeros_like(dr.tau)
+            dr.tau_sum += dr.tau
+
+    def entity_noise_mean(self, ri=0):
+        """-> a device scalar, the mean over the rows of this iteration's tau (the verbose line reads it with the other scalars)"""
+        with torch.cuda.stream(self.ctx.stream):
+            return self.rel[ri].tau.mean()
 
     def ordinal_begin(self, burnin, psamples, ri=0):
         """a run of burnin + psamples iterations starts on ordinal relation ri (sampled edges): its object gets a trace of that many
@@ -1227,6 +1260,10 @@ class GibbsEngine:
             # robust: omega | U, V and the PREVIOUS iteration's alpha, before sample_alpha -- which then takes sum omega e^2
             if dr.robust_nu > 0.0:
                 check(L.bdf_robust_draw(R, train, D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), dr.robust_nu, tag, _ptr(dr.omega), wsse))
+            # a noise precision per row of one entity: tau | U, V and the previous alpha at the same place; it leaves sum tau_j S_j
+            if dr.noise is not None:
+                check(L.bdf_entity_noise_draw(R, dr.handle, dr.noise["mode"] - 1, train, D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev),
+                                              dr.noise["shape"], dr.noise["rate"], tag, _ptr(dr.tau), _ptr(dr.omega), wsse))
             if m.alpha_sample:
                 # err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known
                 # weights: sum w e^2 (the robust draw above has left its own)
@@ -1243,7 +1280,7 @@ class GibbsEngine:
                     n = int(r.data.dims[0]) * int(r.data.dims[1])
                 elif dr.omega is None:
                     check(L.bdf_predict_sse(R, train, D, fac, m.mean_value, None, _ptr(dr.train.stats)))
-                elif dr.robust_nu == 0.0:
+                elif dr.robust_nu == 0.0 and dr.noise is None:
                     check(L.bdf_pairs_weighted_sse(R, train, D, fac, m.mean_value, _ptr(dr.omega), wsse))
                 if comm is not None:
                     check(L.bdf_sum_ranks(R, comm, sse, 1))
@@ -1557,6 +1594,8 @@ class GibbsEngine:
             dr = self.rel[0]
             if dr.pg_model:                  # ... the logistic probabilities / the counts' mean r e^psi
                 self._test_pairs.set_pg_link(dr.pg_model, dr.pg_r)
+            if dr.noise is not None:         # lpd_update scores a cell with alpha tau of its row (nothing else reads the scale)
+                self._test_pairs.set_precision_scale(dr.tau, dr.noise["mode"] - 1)
             if dr.F is not None:             # pred(r, probe_vec, F) = udot + F_test beta + mean_value (sampling.jl:9-14)
                 if feat.isempty(r.test_F):
                     raise ArgumentError(f"Relation {r.name} has features but its test set has no feature rows (test_F)")

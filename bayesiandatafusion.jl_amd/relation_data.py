@@ -94,6 +94,8 @@ def toStr(x):
         s += f" t:{x.model.robust['nu']:g}"
     if kind == "weights":
         s += " wts"
+    if kind == "entity_noise":
+        s += f" τ:{x.entities[x.model.entity_noise['mode'] - 1].name[:3]}"
     if x.model.background is not None:
         s += f" bg:{x.model.background['weight']:g}"
     if x.model.recommend is not None:
@@ -126,11 +128,13 @@ class RelationModel:
         self.pg = None            # setLogit / setCounts: {"model": "logit" | "counts", "r", "offset"}; Polya-Gamma augmentation
         self.background = None    # setBackground: {"weight", "value"}; every cell that is not listed observes `value` with precision alpha weight
         self.recommend = None     # setRecommend: {"k", "rows", "exclude_listed", "batch"}; macau() returns a top-k list per row of the first entity
+        self.entity_noise = None  # setEntityNoise: {"mode" (1-based), "shape", "rate"}; a sampled noise precision per row of that entity
 
 
 def noise_kind(r):
     """which noise model relation r has, from the fields its setter left: "gauss", "probit", "censored", "interval", "ordinal" (it
-    has the interval model's bounds too), "weights", "robust", "logit" or "counts".  The setters admit one of them per relation."""
+    has the interval model's bounds too), "weights", "robust", "entity_noise", "logit" or "counts".  The setters admit one of them
+    per relation."""
     m = r.model
     if m.probit:
         return "probit"
@@ -144,6 +148,8 @@ def noise_kind(r):
         return "robust"
     if m.weights is not None:
         return "weights"
+    if m.entity_noise is not None:
+        return "entity_noise"
     if m.pg is not None:
         return m.pg["model"]
     return "gauss"
@@ -328,9 +334,11 @@ def _no_weights(r, what):
         raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
     if r.model.pg is not None:
         raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
+    if r.model.entity_noise is not None:
+        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): it does not take {what}.")
 
 
-def _weight_guards(r, what, pg_ok=False):
+def _weight_guards(r, what, pg_ok=False, noise_ok=False):
     if hasFeatures(r):
         raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
     if r.model.probit:
@@ -343,6 +351,8 @@ def _weight_guards(r, what, pg_ok=False):
         raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): it does not take {what}.")
     if r.model.pg is not None and not pg_ok:
         raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
+    if r.model.entity_noise is not None and not noise_ok:
+        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): it does not take {what}.")
     if r.model.waic is not None:
         raise ArgumentError(f"Relation {r.name} is scored by WAIC (setWaic): a cell's density under {what} is not scored yet.")
 
@@ -500,6 +510,58 @@ def check_robust(r):
         r.model.robust = {"nu": _robust_nu(r, r.model.robust.get("nu"))}
     if r.model.weights is not None:
         r.model.weights = _obs_weights(r, r.model.weights)
+
+
+def setEntityNoise(r, entity, shape=2.0, rate=2.0):
+    """A noise precision per row of one entity of a Gaussian relation (the reference has one alpha for every cell): a cell whose id
+    in that entity's mode is j is observed with precision alpha tau_j, tau_j ~ Gamma(shape, rate) a priori (mean shape / rate), and
+    macau() samples tau_j beside the rows from Gamma(shape + n_j / 2, rate + alpha S_j / 2), S_j the row's sum of squared
+    residuals -- so that one noisy assay column or one erratic rater pools the evidence of all its cells and stops dragging every
+    other row's factors towards its noise.  entity: an Entity of the relation, its name, or its 1-based mode.  alpha (fixed,
+    setPrecision or alpha_sample) stays the overall scale.  result["noise"]["precision"] is the posterior mean tau per row of the
+    entity.  Predictions and the test set stay what they are; macau(lpd=True) scores a held-out cell with alpha tau of its row.
+    Works before or after the test split."""
+    what = "a noise precision per row (setEntityNoise)"
+    _entity_noise_guards(r, what)
+    r.model.entity_noise = _entity_noise_spec(r, entity, shape, rate)
+    r._dev = None
+    return None
+
+
+def _entity_noise_guards(r, what):
+    _weight_guards(r, what, noise_ok=True)
+    if r.model.robust is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
+    if r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
+    if r.model.background is not None:
+        raise ArgumentError(f"Relation {r.name} has a background (setBackground): it does not take {what}.")
+
+
+def _entity_noise_spec(r, entity, shape, rate):
+    n_modes = len(r.entities)
+    if isinstance(entity, Entity):
+        hit = [k for k, e in enumerate(r.entities) if e is entity]
+    elif isinstance(entity, str):
+        hit = [k for k, e in enumerate(r.entities) if e.name == entity]
+    elif isinstance(entity, (int, np.integer)) and not isinstance(entity, (bool, np.bool_)):
+        hit = [int(entity) - 1] if 1 <= int(entity) <= n_modes else []
+    else:
+        hit = []
+    if len(hit) != 1:
+        raise ArgumentError(f"Relation {r.name}: entity = {entity!r} must be one of its entities ({', '.join(e.name for e in r.entities)}), "
+                            f"by object, by name or by its mode 1 ... {n_modes}.")
+    for name, x in (("shape", shape), ("rate", rate)):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x <= 0:
+            raise ArgumentError(f"Relation {r.name}: {name} = {x} must be a finite number above 0.")
+    return {"mode": hit[0] + 1, "shape": float(shape), "rate": float(rate)}
+
+
+def check_entity_noise(r):
+    """what a relation with a noise precision per row must still satisfy when a sampler is built on it (it may have been changed since)"""
+    _entity_noise_guards(r, "a noise precision per row (setEntityNoise)")
+    m = r.model.entity_noise
+    r.model.entity_noise = _entity_noise_spec(r, m.get("mode"), m.get("shape"), m.get("rate"))
 
 
 def setBackground(r, weight, value=0.0):
@@ -804,6 +866,8 @@ def setWaic(r, on=True, pointwise=False):
         raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): a cell's density under them is not scored yet (setWaic).")
     if on and r.model.pg is not None:
         raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: a cell's density under it is not scored yet (setWaic).")
+    if on and r.model.entity_noise is not None:
+        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): a cell's density under it is not scored yet (setWaic).")
     r.model.waic = {"pointwise": bool(pointwise)} if on else None
     return None
 
@@ -899,6 +963,7 @@ _MODEL_CHECKS = (
     (lambda m: m.robust is not None or m.weights is not None, check_robust,
      lambda m: "the robust noise model" if m.robust is not None else "observation weights"),
     (lambda m: m.pg is not None, check_pg, lambda m: f"the {m.pg['model']} noise model"),
+    (lambda m: m.entity_noise is not None, check_entity_noise, lambda m: "a noise precision per row"),
     (lambda m: m.background is not None, check_background, lambda m: "a background"),
     (lambda m: m.recommend is not None, check_recommend, lambda m: "top-k lists (setRecommend)"),
 )

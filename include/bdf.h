@@ -60,6 +60,8 @@ extern "C" {
 #define BDF_P_ROBUST_N 16      /* bdf_robust_draw: the gamma variate's normals (entity 0x800000 | rel_tag, row = observation, attempt t: normal 2 t) */
 #define BDF_P_ROBUST_U 17      /* bdf_robust_draw: ... and its uniforms (the same entity and row, pair = attempt)                               */
 #define BDF_P_PG 18            /* bdf_pg_draw: one cursor per observation over the blocks pair = 0, 1, 2, ... (entity 0x800000 | rel_tag, row = observation) */
+#define BDF_P_NOISE_N 19       /* bdf_entity_noise_draw: the gamma variate's normals (entity 0x800000 | rel_tag, row = 0-based row of the noise entity, attempt t: normal 2 t) */
+#define BDF_P_NOISE_U 20       /* bdf_entity_noise_draw: ... and its uniforms (the same entity and row, pair = attempt; shape < 1: the boost's uniform is pair 0xffff) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -423,6 +425,25 @@ int bdf_pairs_weighted_sse(bdf_ctx *ctx, const bdf_pairs *pairs, int D, const do
  * the series the proposal is accepted; after 256 refused proposals the last proposal is returned.  factors as for bdf_predict. */
 int bdf_pg_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const *factors, double mean_value, int model, double r,
                 uint32_t rel_tag, double *precision_out, double *linear_out);
+/* A noise precision per row of one entity of a Gaussian relation (csrc/k_entity_noise.hip,
+ * csrc/entity_noise.h): a cell whose id in mode `mode` (0-based) of `rel` is j is observed with precision alpha tau_j,
+ *   value_k ~ N(udot_k + mean_value, 1 / (alpha tau_j(k))),  tau_j ~ Gamma(shape, rate) (mean shape / rate).
+ * `train` holds the cells of `rel` as pairs, observation k of the caller's order being COO row k of the relation (the pairs may be
+ * stored sorted); BDF_ERR_ARG when the counts or the numbers of modes differ, and for a relation created with a layout.  With
+ * e_k = value_k - (udot_k + mean_value), n_j the cells of row j and S_j the sum of e_k^2 over them, added in the fixed order that
+ * csrc/entity_noise.h writes down (a row without cells: S_j = 0, a draw from the prior):
+ *   tau_j = G_j / (rate + alpha S_j / 2),  G_j ~ Gamma(a, 1), a = shape + n_j / 2, by Marsaglia-Tsang on the streams (BDF_P_NOISE_N,
+ *   0x800000 | rel_tag, row j) and (BDF_P_NOISE_U, the same entity and row) as bdf_robust_draw states it; a < 1: G_j is the variate
+ *   of a + 1 times u^(1 / a), u the uniform of pair 0xffff
+ * at the context's sweep.  shape and rate positive and finite.  alpha_dev (dev, nullable) wins over alpha, which must otherwise be
+ * positive and finite.  tau_out (dev, dims[mode]): tau_j.  precision_out (dev, n; scratch of the first launch, which leaves e_k^2
+ * there): tau_j(k) in the caller's order, bit for bit tau_out[j(k)] -- what bdf_term.obs_precision takes.  wsse_out (dev, 1 double,
+ * nullable): sum_j tau_j S_j in a fixed order (bit-identical reruns): with it in place of the sum of squares bdf_sample_alpha
+ * draws from alpha's exact conditional.  factors as for bdf_predict.  Two launches (a third for wsse_out) on ctx's stream; not
+ * reentrant on one context (the partial sums live in the context's scratch). */
+int bdf_entity_noise_draw(bdf_ctx *ctx, const bdf_rel *rel, int mode, const bdf_pairs *train, int D, const double *const *factors,
+                          double mean_value, double alpha, const double *alpha_dev, double shape, double rate, uint32_t rel_tag,
+                          double *tau_out, double *precision_out, double *wsse_out);
 
 /* Ordinal probit noise model (csrc/k_ordinal.hip, csrc/ordinal.h): the training values of a relation are
  * levels 1 .. K (4 <= K <= 16), y = k iff e_{k-1} <= z < e_k for the latent z ~ N(udot + mean_value, 1 / alpha) of the interval
@@ -506,6 +527,12 @@ int bdf_pairs_state(const bdf_pairs *p, double **avg, double **sq, int64_t *n);
  * reruns).  Enqueued on ctx's stream.  BDF_ERR_ARG for a phase outside 0..2 and for phase 2 before a phase 1. */
 int bdf_pairs_lpd_update(bdf_ctx *ctx, bdf_pairs *p, const double *bounds_dev, int D, const double *const *factors,
                          double mean_value, double alpha, const double *alpha_dev, int phase, double *stats_out);
+/* A precision scale per row of one mode for bdf_pairs_lpd_update (the per-row noise model, bdf_entity_noise_draw): with tau_dev (dev,
+ * one double per row of mode `mode`, 0-based; BORROWED, read at every update) pair k is scored with alpha tau_dev[id_k,mode] in place
+ * of alpha, as a Gaussian measurement and as the mass of an interval alike.  NULL clears it (mode is then ignored) and the
+ * updates are bit for bit what they were.  BDF_ERR_ARG for a mode outside the pairs' and for pairs with the probit link.
+ * bdf_pairs_waic_update refuses pairs with a scale (BDF_ERR_ARG): WAIC under that model is not scored yet. */
+int bdf_pairs_set_precision_scale(bdf_pairs *pairs, const double *tau_dev, int mode);
 /* lpd_k = M + log A - log(draws) of every pair -> out_dev (dev n), in the caller's order whether or not the pairs are stored
  * sorted.  BDF_ERR_ARG before the first phase 1. */
 int bdf_pairs_lpd(bdf_ctx *ctx, const bdf_pairs *p, double *out_dev);
@@ -842,6 +869,16 @@ typedef struct {
     double bg_weight, bg_value;
     double *bg_sums;              /* dev, 2 (D + D D): for mode m at bg_sums + m (D + D D), the sum of that mode's rows, then their Gram matrix */
     const double *bg_weights;     /* dev, nullable: omega_k per observation of `train` in the caller's order                  */
+    /* a noise precision per row of one entity (a zeroed tail is "none"): noise_mode 1-based, the mode of `rel`
+     * whose rows carry tau_j ~ Gamma(noise_shape, noise_rate); noise_tau (dev, dims[noise_mode - 1]) receives the draw.
+     * bdf_entity_noise_draw (with alpha_dev: the previous iteration's alpha) rewrites noise_tau and obs_precision where
+     * bdf_robust_draw runs, BEFORE sample_alpha, which then takes sum_j tau_j S_j in place of the sum of squares; the rows of every
+     * entity read obs_precision.  Needs train, obs_precision and noise_tau; not with probit, censor, interval, ordinal, robust_nu,
+     * pg_model, a background, feat or a communicator */
+    int32_t noise_mode;
+    int32_t _pad_noise;
+    double noise_shape, noise_rate;
+    double *noise_tau;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

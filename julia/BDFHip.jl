@@ -505,6 +505,25 @@ function pg_draw!(c::Context, train::DevPairs, D, factors::Vector{<:DevArray}, m
                 (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Cint, Float64, UInt32, Ptr{Cvoid}, Ptr{Cvoid}),
                 c.h, train.h, D, fp, mean_value, model, r, rel_tag, precision_out.p, linear_out.p))
 end
+"a noise precision per row of one entity of a Gaussian relation: for every row j of mode `mode` (0-based) of `rel`, tau_j = G /
+(rate + alpha S_j / 2) with S_j the sum of (value - (udot + mean_value))^2 over the row's n_j cells, in a fixed order, and G ~
+Gamma(shape + n_j / 2, 1) from the streams (19 / 20, 0x800000 | rel_tag, row j); `train` holds the relation's own cells in its
+order; `alpha_dev` (a device scalar or `nothing`) wins over `alpha`; tau_out has one Float64 per row of the mode, precision_out one
+per cell (tau of the cell's row: what the rows take as Term.obs_precision); wsse_out (one device Float64 or `nothing`): sum tau_j
+S_j in a fixed order, what sample_alpha! takes in place of the sum of squares"
+function entity_noise_draw!(c::Context, rel::DevRelation, mode, train::DevPairs, D, factors::Vector{<:DevArray}, mean_value, alpha, alpha_dev,
+                            shape, rate, rel_tag, tau_out::DevArray{Float64}, precision_out::DevArray{Float64}, wsse_out=nothing)
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_entity_noise_draw, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}, Float64, Float64, UInt32,
+                 Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, rel.h, mode, train.h, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, shape, rate, rel_tag,
+                tau_out.p, precision_out.p, wsse_out === nothing ? C_NULL : wsse_out.p))
+end
+"pairs_lpd_update! scores pair k with alpha tau[its id in mode `mode` (0-based)]: tau, one device Float64 per row of that mode, is
+borrowed and read at every update (keep it alive); `nothing` clears it"
+pairs_set_precision_scale!(p::DevPairs, tau, mode::Integer=0) =
+    check(ccall((:bdf_pairs_set_precision_scale, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint), p.h, tau === nothing ? C_NULL : tau.p, mode))
 "predictions of the pairs become the logistic probability 1 / (1 + exp(-(udot + base))) (link 2)"
 pairs_set_logistic_link!(p::DevPairs) = check(ccall((:bdf_pairs_set_logistic_link, lib), Cint, (Ptr{Cvoid},), p.h))
 "predictions of the pairs become r exp(min(udot + base, 700)), the mean of the count model (link 3)"
@@ -751,6 +770,11 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     bg_value::Float64
     bg_sums::Ptr{Cvoid}                           # device, 2 (D + D D) Float64: per mode, the sum of its rows and their Gram matrix
     bg_weights::Ptr{Cvoid}                        # device Float64 omega_k per observation of train (C_NULL: 1); obs_precision then holds omega_k - bg_weight
+    noise_mode::Int32                             # a noise precision per row of the entity at this 1-based mode (0: none); entity_noise_draw! rewrites noise_tau and obs_precision
+    _pad_noise::Int32
+    noise_shape::Float64                          # ... tau_j ~ Gamma(noise_shape, noise_rate) a priori
+    noise_rate::Float64
+    noise_tau::Ptr{Cvoid}                         # device Float64 per row of that mode: the last draw
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
