@@ -23,6 +23,7 @@ P_ORDINAL = 15
 P_ROBUST_N, P_ROBUST_U = 16, 17
 P_PG = 18
 P_NOISE_N, P_NOISE_U = 19, 20
+P_SPIKE_N, P_SPIKE_U, P_SPIKE = 21, 22, 23
 
 
 class ArgumentError(ValueError):
@@ -81,7 +82,9 @@ class GibbsEntity(C.Structure):
                 ("feat", C.c_void_p), ("beta", C.c_void_p), ("uhat", C.c_void_p), ("mu_matrix", C.c_void_p), ("Tinv", C.c_void_p),
                 ("lambda_beta", C.c_void_p), ("cg_iters", C.c_void_p), ("use_ff", C.c_int32), ("sample_lambda_beta", C.c_int32),
                 ("full_lambda_u", C.c_int32), ("_pad", C.c_int32), ("tol", C.c_double), ("lb_nu", C.c_double), ("lb_mu", C.c_double),
-                ("bg_Lambda", C.c_void_p), ("bg_mu", C.c_void_p), ("bg_pack", C.c_void_p), ("bg_alpha_rows", C.c_void_p)]
+                ("bg_Lambda", C.c_void_p), ("bg_mu", C.c_void_p), ("bg_pack", C.c_void_p), ("bg_alpha_rows", C.c_void_p),
+                ("spike", C.c_int32), ("_pad_spike", C.c_int32), ("spike_a", C.c_double), ("spike_b", C.c_double),
+                ("spike_shape", C.c_double), ("spike_rate", C.c_double), ("spike_state", C.c_void_p)]
 
 
 class GibbsRelation(C.Structure):
@@ -145,6 +148,11 @@ _SIGS = {
                                  C.c_void_p, C.c_void_p]),
     "bdf_normals": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
     "bdf_philox": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "bdf_sample_rows_spike": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(Term), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                        C.c_int, C.c_void_p]),
+    "bdf_spike_hyper": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32,
+                                  C.c_void_p]),
+    "bdf_spike_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_hyper_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_hyper_sums_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_hyper_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,

@@ -37,6 +37,9 @@ def relation_of(data, num_latent, who):
         raise ArgumentError(f"{who} fits the listed cells only; {rel.name} has a background (use macau)")
     if rel.model.recommend is not None:
         raise ArgumentError(f"{who} keeps no sum of scores over draws; {rel.name} asks for top-k lists (setRecommend; use macau)")
+    for en in data.entities:
+        if en.spike is not None:
+            raise ArgumentError(f"{who} has the Normal-Wishart prior only; {en.name} has the spike-and-slab prior (setSpikeAndSlab; use macau)")
     return D, rel
 
 

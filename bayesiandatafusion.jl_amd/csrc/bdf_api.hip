@@ -645,9 +645,10 @@ extern "C" int bdf_relation_order(const bdf_rel *rel, int mode, int32_t *order_h
 
 // ---- a3-a7: rows ---------------------------------------------------------------------------
 static int fill_args(bdf_ctx *ctx, const char *who, int D, int64_t N, int n_terms, const bdf_term *terms,
-                     const double *mu, int mu_is_matrix, const double *Lambda, SampleArgs &a)
+                     const double *mu, int mu_is_matrix, const double *Lambda, SampleArgs &a, bool prior_from_router = false)
 {
-    BDF_REQUIRE(ctx && terms && mu && Lambda, BDF_ERR_ARG, "%s: NULL argument", who);
+    // (prior_from_router: bdf_sample_rows_spike gives no mu and no Lambda; a.mu and a.Lambda stay NULL until the router makes both)
+    BDF_REQUIRE(ctx && terms && (prior_from_router || (mu && Lambda)), BDF_ERR_ARG, "%s: NULL argument", who);
     BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "%s: num_latent=%d must be in 1..%d", who, D, BDF_MAX_D);
     BDF_REQUIRE(n_terms >= 1 && n_terms <= BDF_MAX_TERMS, BDF_ERR_ARG, "%s: n_terms=%d must be in 1..%d", who, n_terms, BDF_MAX_TERMS);
     memset(&a, 0, sizeof(a));
@@ -757,6 +758,39 @@ extern "C" int bdf_sample_rows(bdf_ctx *ctx, int D, int64_t N, int n_terms, cons
         a.b_dump = (double *)g_bdf_stamp_buf;
     }
 #endif
+    return bdf_launch_sample_rows(ctx, a, rels, modes, shard, n_shards, false);
+}
+
+extern "C" int bdf_sample_rows_spike(bdf_ctx *ctx, int D, int64_t N, int n_terms, const bdf_term *terms, const double *spike_state,
+                                     const double *u_current, uint32_t entity_tag, int shard, int n_shards, double *out)
+{
+    BDF_REQUIRE(ctx && terms && spike_state && u_current, BDF_ERR_ARG, "bdf_sample_rows_spike: NULL argument");
+    SampleArgs a;
+    // (the prior of the accumulation, diag(tau) and zeros, is made by the router from spike_state: no mu, no Lambda here)
+    int rc = fill_args(ctx, "bdf_sample_rows_spike", D, N, n_terms, terms, nullptr, 0, nullptr, a, true);
+    if (rc) return rc;
+    BDF_REQUIRE(out != nullptr, BDF_ERR_ARG, "bdf_sample_rows_spike: out is NULL");
+    BDF_REQUIRE(out != u_current, BDF_ERR_ARG, "bdf_sample_rows_spike: out aliases u_current");
+    BDF_REQUIRE(n_shards >= 1 && shard >= 0 && shard < n_shards, BDF_ERR_ARG, "bdf_sample_rows_spike: shard %d of %d", shard, n_shards);
+    const bdf_rel *rels[BDF_MAX_TERMS];
+    int modes[BDF_MAX_TERMS];
+    for (int r = 0; r < n_terms; r++) {
+        BDF_REQUIRE(!terms[r].rel->sharded, BDF_ERR_ARG, "bdf_sample_rows_spike: a relation created with a layout (one rank only)");
+        rels[r] = terms[r].rel;
+        modes[r] = terms[r].mode;
+        for (int k = 0; k < terms[r].rel->n_modes; k++)
+            BDF_REQUIRE(k == terms[r].mode || terms[r].factors[k] != out, BDF_ERR_ARG,
+                        "bdf_sample_rows_spike: out aliases terms[%d].factors[%d]", r, k);
+    }
+    a.entity_tag = entity_tag;
+    a.out = out;
+    a.spike_state = spike_state;
+    a.u_current = u_current;
+    // (the hand-overs bdf_sample_rows' launches can take part in -- a polled prior pack, a span, a counter -- are not for this one)
+    ctx->rows_ready = nullptr;
+    ctx->rows_span = nullptr;
+    ctx->rows_done = nullptr;
+    ctx->rows_done_added = -1;
     return bdf_launch_sample_rows(ctx, a, rels, modes, shard, n_shards, false);
 }
 

@@ -256,6 +256,8 @@ extern "C" int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const 
                     BDF_ERR_ARG, "bdf_gibbs_create: entity %d has a NULL buffer", j);
         BDF_REQUIRE(!e.feat || (e.beta && e.uhat && e.mu_matrix && e.Tinv && e.lambda_beta), BDF_ERR_ARG,
                     "bdf_gibbs_create: entity %d has side information but a NULL beta / uhat / mu_matrix / Tinv / lambda_beta", j);
+        BDF_REQUIRE(!e.spike || (e.spike_state && !e.feat && !e.bg_Lambda), BDF_ERR_ARG,
+                    "bdf_gibbs_create: entity %d has the spike-and-slab prior: spike_state must be set, side information and a background are not taken", j);
         BDF_REQUIRE(!e.feat || e.feat->m == e.N, BDF_ERR_ARG, "bdf_gibbs_create: entity %d has %lld rows but its feature matrix %lld", j,
                     (long long)e.N, e.feat ? (long long)e.feat->m : 0LL);
         for (int t = 0; t < e.n_terms; t++) {
@@ -617,11 +619,16 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
     const bdf_gibbs_entity &e = E.d;
     R->sweep_host = sweep;
     int rc;
-    const double *mu, *Lambda, *pack;
-    if ((rc = row_prior(g, E, &mu, &Lambda, &pack))) return rc;
     bdf_term terms[BDF_MAX_TERMS];
     fill_terms(g, e, terms);
     const int nxt = (E.cur + 1) % 3;
+    if (e.spike) {
+        if ((rc = bdf_sample_rows_spike(R, g->D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, 0, 1, e.sample[nxt]))) return rc;
+        E.cur = nxt;
+        return BDF_OK;
+    }
+    const double *mu, *Lambda, *pack;
+    if ((rc = row_prior(g, E, &mu, &Lambda, &pack))) return rc;
     const int nch = e.terms[0].rel->chunks;
     for (int c = 0; c < nch; c++)
         if ((rc = bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, e.feat ? 1 : 0, Lambda, e.tag, c, nch, e.sample[nxt], pack))) return rc;
@@ -661,6 +668,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         if (e.params) pieces.push_back({e.params, Dv + DD, false, j});
         pieces.push_back({e.prior_pack, (size_t)bdf_prior_pack_doubles(D) * sizeof(double), false, j});
         pieces.push_back({e.draws, DD + Dv, false, j});
+        if (e.spike) pieces.push_back({e.spike_state, 4 * Dv, false, j});      // pi, tau, logit pi, log tau of the spike-and-slab prior
         if (e.feat) {
             pieces.push_back({e.beta, (size_t)e.feat->n * Dv, false, j});
             pieces.push_back({e.uhat, (size_t)e.N * Dv, false, j});
@@ -831,11 +839,13 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
     for (int j = 0; j < n; j++) draws_in_chain = draws_in_chain && g->ent[(size_t)j].d.N <= 16384;
     if (!draws_in_chain && n <= BDF_DRAWS_BATCH) {
         int64_t Ns[BDF_DRAWS_BATCH]; double nus[BDF_DRAWS_BATCH]; uint32_t tags[BDF_DRAWS_BATCH]; double *outs[BDF_DRAWS_BATCH];
+        int nb = 0;                       // (an entity with the spike-and-slab prior has no Normal-Wishart draw)
         for (int j = 0; j < n; j++) {
             const bdf_gibbs_entity &e = g->ent[(size_t)j].d;
-            Ns[j] = e.n_real; nus[j] = hyper_nu(e); tags[j] = e.tag; outs[j] = e.draws;
+            if (e.spike) continue;
+            Ns[nb] = e.n_real; nus[nb] = hyper_nu(e); tags[nb] = e.tag; outs[nb] = e.draws; nb++;
         }
-        if ((rc = bdf_hyper_draws_batch(H, D, n, Ns, nus, tags, outs))) return rc;
+        if (nb > 0 && (rc = bdf_hyper_draws_batch(H, D, nb, Ns, nus, tags, outs))) return rc;
     }
     // the relation models (alpha, relation-level beta and linear_values) with the rows of the previous iteration (macau.jl:83-92)
     if (!g->rels.empty() && (rc = update_relations(g))) return rc;
@@ -852,16 +862,17 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // the draw -- behind the draw's event, and its rows join neither the polling nor the hand-over by counter below)
         bool bg = false;
         for (int t = 0; t < e.n_terms; t++) bg = bg || background_of(g, e, t) != nullptr;
-        const bool poll = g->polling && (!g->comm || poll_with_comm) && E.hyper_recorded && !e.feat && !bg;
+        // (so is an entity with the spike-and-slab prior: its rows wait for the event of its hyper step, bdf_spike_hyper)
+        const bool poll = g->polling && (!g->comm || poll_with_comm) && E.hyper_recorded && !e.feat && !bg && !e.spike;
         if (E.hyper_recorded && !poll) BDF_HIP(hipStreamWaitEvent(R->stream, E.ev_hyper, 0));
         // side information: uhat = (F beta)' with the beta of the previous iteration, per-row prior means mu + uhat (macau.jl:103-104)
         if (e.feat && (rc = bdf_uhat(R, e.feat, D, e.beta, e.mu, e.uhat, e.mu_matrix))) return rc;
         // the data-independent part of the hyperprior draw (Bartlett matrix, mean normals): beside the rows -- for all entities
         // in one launch at the head of the iteration when they are few
-        if (!draws_in_chain && n > BDF_DRAWS_BATCH && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
+        if (!draws_in_chain && n > BDF_DRAWS_BATCH && !e.spike && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
         // the prior of this launch: the draw's (mu, Lambda) and pack, or -- background cells -- those with the Gram terms folded in
-        const double *mu_rows, *Lambda_rows, *pack_rows;
-        if ((rc = row_prior(g, E, &mu_rows, &Lambda_rows, &pack_rows))) return rc;
+        const double *mu_rows = nullptr, *Lambda_rows = nullptr, *pack_rows = nullptr;
+        if (!e.spike && (rc = row_prior(g, E, &mu_rows, &Lambda_rows, &pack_rows))) return rc;
         bdf_term terms[BDF_MAX_TERMS];
         fill_terms(g, e, terms);
         const int nxt = (E.cur + 1) % 3;
@@ -881,7 +892,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // Every other path -- a communicator, side information, chunks, a caller's timing events (E.t_stop), no polling, chains of
         // several launches: `counter` false; a launch that took another kernel: rows_done_added < 0 -- has `done` as before, on the
         // dispatch or recorded right behind it, for the chain and the prediction stream alike.
-        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && !bg && nch == 1 && !E.t_stop;
+        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && !bg && !e.spike && nch == 1 && !E.t_stop;
         const bool pred_waits = j == n - 1 && g->test && predict_phase >= 0;
         bool by_counter = false;
         for (int c = 0; c < nch; c++) {
@@ -890,7 +901,8 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             R->time_stop = (c == nch - 1 && !g->comm && !counter) ? done : nullptr;
             if (poll) { R->rows_ready = g->ready_dev + j; R->rows_ready_want = E.epoch; }
             if (counter) R->rows_done = E.done_dev;
-            if ((rc = bdf_sample_rows(R, D, e.N, e.n_terms, terms, mu_rows, e.feat ? 1 : 0, Lambda_rows, e.tag, c, nch, e.sample[nxt], pack_rows)))
+            if ((rc = e.spike ? bdf_sample_rows_spike(R, D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
+                              : bdf_sample_rows(R, D, e.N, e.n_terms, terms, mu_rows, e.feat ? 1 : 0, Lambda_rows, e.tag, c, nch, e.sample[nxt], pack_rows)))
                 return rc;
             if (counter && R->rows_done_added >= 0) { by_counter = true; E.done_target += (uint32_t)R->rows_done_added; }
             if (g->comm && (rc = bdf_allgather_rows(R, g->comm, D, e.N, e.sample[nxt], c, nch))) return rc;
@@ -906,6 +918,15 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         E.cur = nxt;
         if (by_counter) { H->hyper_wait = E.done_dev; H->hyper_wait_target = E.done_target; }
         else BDF_HIP(hipStreamWaitEvent(H->stream, done, 0));
+        if (e.spike) {
+            // the spike-and-slab prior's hyper step in place of the sums and the Normal-Wishart draw; its event recorded behind it
+            if ((rc = bdf_spike_hyper(H, D, e.n_real, e.sample[E.cur], e.spike_a, e.spike_b, e.spike_shape, e.spike_rate, e.tag, e.spike_state)))
+                return rc;
+            BDF_HIP(hipEventRecord(E.ev_hyper, H->stream));
+            E.hyper_recorded = true;
+            if (pred_waits) BDF_HIP(hipStreamWaitEvent(P->stream, done, 0));
+            continue;
+        }
         H->hyper_fuse = true;             // small entities: the sums and the draw in one launch (k_hyper_chain)
         // side information: U = sample - uhat, T^-1 = WI + beta' beta lambda_beta with the beta of the previous iteration
         const double *Tinv = e.WI;

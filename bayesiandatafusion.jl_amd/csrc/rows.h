@@ -4,6 +4,7 @@
 //   k_rows_small.hip   K1s    short rows at D <= 16, four to a wave                          bdf_small_launch
 //   k_rows_col.hip     K1c    one two-mode relation at 16 < D <= 32, column layout           bdf_col_launch
 //   k_sample_rows.hip  K1     every other row, one wave per item                             bdf_k1_launch
+//   k_rows_ss.hip      K1-ss  every row of a call under the spike-and-slab prior, K1's items   bdf_ss_launch
 #pragma once
 #include "bdf_common.h"
 
@@ -55,6 +56,10 @@ struct SampleArgs {
     // nullable (bdf_gibbs_sweep, k_rows_col only): 64 counters, 16 words apart; a wave that has written its rows (write-through, drained)
     // adds 1 to counter (wave % 64): what the hyperprior chain polls instead of waiting for the launch's completion event
     uint32_t *done;
+    // bdf_sample_rows_spike (k_rows_ss.hip, spike.h) only: the prior's state (4 D doubles) and the entity's CURRENT rows (D x N), from
+    // which the coordinate sweep of every row starts
+    const double *spike_state;
+    const double *u_current;
 };
 
 // the padded dimension the row kernels are compiled for
@@ -112,6 +117,10 @@ struct PlanDev {
 };
 
 int bdf_k1_launch(bdf_ctx *ctx, const SampleArgs &a, const PlanDev &p, bool dump, hipEvent_t e0, hipEvent_t e1);
+// the same items under the spike-and-slab prior (k_rows_ss.hip): a.spike_state and a.u_current set, a.prior_c the image of diag(tau)
+int bdf_ss_launch(bdf_ctx *ctx, const SampleArgs &a, const PlanDev &p, hipEvent_t e0, hipEvent_t e1);
+// diag(tau) of a spike_state as a D x D matrix, and D zeros behind it (the prior mean): what bdf_prior_launch takes (k_spike_hyper.hip)
+int bdf_spike_lambda_launch(bdf_ctx *ctx, int D, const double *spike_state, double *Lambda_mu_out);
 // the prior pack of a launch: out_b = Lambda mu (nrows = 1, mu_is_matrix = 0) or Lambda mu_i for nrows rows, out_c = the
 // accumulator-layout image of the index-reversed Lambda (bdf_prior_image_doubles(D) doubles)
 inline int bdf_prior_image_doubles(int D) { const int DB = bdf_rows_dp(D) / 16; return DB * (DB + 1) / 2 * 4 * 64; }

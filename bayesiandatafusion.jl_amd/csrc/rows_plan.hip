@@ -222,6 +222,8 @@ void route_key(const bdf_ctx *ctx, const SampleArgs &a, const bdf_rel *const *re
         const int64_t t = std::min<int64_t>(2048, (nnz_launch / (slots * 16) + 63) / 64 * 64);
         if (t > key.T) { key.T = (int)t; key.Tp = (int)(t * 2 / 3); }
     }
+    // the spike-and-slab launch (bdf_sample_rows_spike): K1's items for every row, none of the three kernels below
+    if (a.spike_state != nullptr) return;
     // D <= 16, one two-mode relation with the lean gather and no per-observation baseline, an entity of many rows: its short
     // rows four to a wave (k_rows_small).  bdf_ctx_set_small_rows: the longest row taken that way (default 48 observations,
     // environment BDF_K1_SMALL; 0: off) and the smallest entity (default 8192 rows, BDF_K1_SMALL_MIN_ROWS: below that the
@@ -396,6 +398,19 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
 {
     SampleArgs a = a_in;
     int rc;
+    const bool spike = a.spike_state != nullptr;      // bdf_sample_rows_spike: every row to K1-style items, finished by k_rows_ss
+    if (spike) {
+        // the prior of the accumulation is Lambda = diag(tau), mu = 0: the matrix and the zeros by one small launch, then the
+        // usual prior pack from them (all of it in the context's scratch: one request, the block may move when it grows)
+        const size_t nlm = (size_t)a.D * a.D + a.D, npk = (size_t)a.D + (size_t)bdf_prior_image_doubles(a.D);
+        void *pb;
+        if ((rc = bdf_scratch(ctx, (nlm + npk) * sizeof(double), &pb))) return rc;
+        double *lm = (double *)pb, *pk = lm + nlm;
+        if ((rc = bdf_spike_lambda_launch(ctx, a.D, a.spike_state, lm))) return rc;
+        if ((rc = bdf_prior_launch(ctx, a.D, lm, lm + (size_t)a.D * a.D, 1, 0, pk, pk + a.D))) return rc;
+        a.Lambda = lm; a.mu = lm + (size_t)a.D * a.D; a.mu_is_matrix = 0;
+        a.prior_b = pk; a.prior_c = pk + a.D;
+    }
     if (a.prior_b == nullptr) {         // no prior pack from bdf_hyper_sample: derive Lambda mu and the image here
         // prior part of b: Lambda mu (one vector) or Lambda mu_i for every row (per-row prior means, macau.jl:104)
         const int64_t nr = a.mu_is_matrix ? rels[0]->nint[modes[0]] : 1;
@@ -437,7 +452,7 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
         if (s == 0) rc = launch_lowrank(ctx, a, *plan, M_other, rels[0]->nint[modes[0]], shard, e0, e1);
         else if (s == 1) rc = bdf_small_launch(ctx, a, plan->small_dev, plan->n_small, e0, e1);
         else if (s == 2) rc = launch_column(ctx, a, *plan, M_other, more, e0, e1);
-        else rc = bdf_k1_launch(ctx, a, plan->dev, dump, e0, e1);
+        else rc = spike ? bdf_ss_launch(ctx, a, plan->dev, e0, e1) : bdf_k1_launch(ctx, a, plan->dev, dump, e0, e1);
         if (rc) return rc;
         if (!dump) { ctx->time_start = nullptr; if (!more) ctx->time_stop = nullptr; }
     }

@@ -108,6 +108,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         eng.rel[0].omega_sum = None                          # (an engine that is reused starts the posterior mean of omega again)
     if noise is not None:
         eng.rel[0].tau_sum = None                            # (... and of tau)
+    # entities with the spike-and-slab prior (setSpikeAndSlab)
+    spiked = [st for st in eng.ent if st.spike is not None]
+    if eng is engine:
+        for st in spiked:
+            st.spike_reset()                                 # (... and of the spike-and-slab result)
     D = eng.D
 
     latent_multi_threading = (len(latent_pids) >= 1 and len(data.relations) == 1 and not hasFeatures(data.relations[0]))
@@ -176,6 +181,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             eng.robust_accumulate()                           # this iteration's omega into its running sum, on the row stream
         if noise is not None and i > burnin:
             eng.entity_noise_accumulate()                     # this iteration's tau into its running sum, on the row stream
+        if spiked and i > burnin:
+            eng.spike_accumulate()                            # this draw's inclusions, pi and tau into their running sums, on the row stream
         if lpd or waic is not None:
             # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
             # has read the same double, and the device scalar is redrawn on another stream than the pairs')
@@ -294,6 +301,9 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         ts, N = rel._dev.tau_sum, int(rel.data.dims[noise["mode"] - 1])
         result["noise"] = {"entity": rel.entities[noise["mode"] - 1].name, "shape": noise["shape"], "rate": noise["rate"],
                            "precision": (ts.cpu().numpy()[:N] / psamples) if (ts is not None and psamples) else np.full(N, np.nan)}
+    if spiked:
+        # posterior means of pi_d, tau_d, the share of rows with a nonzero loading and [u_id != 0]
+        result["spike"] = {en.name: st.spike_result() for en, st in zip(data.entities, eng.ent) if st.spike is not None}
     if lpd:
         result["LPD"] = lpd_avg
     # relations with background cells (setBackground): what every unlisted cell observed, and how many there were

@@ -706,6 +706,17 @@ class EntityState:
         # a relation of the entity has background cells (setBackground): the prior its rows are sampled with, made before every
         # row launch (GibbsEngine._row_prior); allocated by background_buffers()
         self.bg_Lambda = self.bg_mu = self.bg_pack = self.bg_alpha_rows = None
+        # the spike-and-slab prior (setSpikeAndSlab): pi, tau, logit pi, log tau (D each; pi = 1/2, tau = 1 at the start) and the
+        # running sums of the result -- [u != 0] per loading; pi, tau and the count n_d per component --, zeroed on the row stream,
+        # which is the one that adds to them (hipMemset)
+        self.spike = en.spike
+        self.spike_state = self.spike_row_sum = self.spike_hyper_sum = None
+        self.spike_draws = 0
+        if en.spike is not None:
+            self.spike_state = ctx.tensor(np.concatenate([np.full(D, 0.5), np.ones(D), np.zeros(D), np.zeros(D)]))
+            self.spike_row_sum = torch.empty(self.N, D, dtype=torch.float64, device=ctx.device)
+            self.spike_hyper_sum = torch.empty(3 * D, dtype=torch.float64, device=ctx.device)
+            self.spike_reset()
         self.F = None
         self.numF = 0
         self.beta = ctx.zeros(D, 0)
@@ -734,6 +745,35 @@ class EntityState:
             self.bg_mu = ctx.zeros(self.N, D) if self.F is not None else ctx.zeros(D)
             self.bg_pack = ctx.zeros(lib().bdf_prior_pack_doubles(D))
             self.bg_alpha_rows = ctx.zeros(_lib.BDF_MAX_TERMS)
+
+    def spike_reset(self):
+        """the running sums of the spike-and-slab result start again (hipMemsetAsync on the row stream)"""
+        with torch.cuda.stream(self.ctx.stream):
+            self.spike_row_sum.zero_()
+            self.spike_hyper_sum.zero_()
+        self.spike_draws = 0
+
+    def spike_accumulate(self):
+        """the current draw into the running sums, on the row stream"""
+        check(lib().bdf_spike_accumulate(self.ctx.handle, self.D, self.n_real, _ptr(self.sample), _ptr(self.spike_state), _ptr(self.spike_row_sum),
+                                         _ptr(self.spike_hyper_sum)))
+        self.spike_draws += 1
+
+    def spike_active(self):
+        """how many components have a nonzero loading in the current draw, over the entity's n_real rows: a count, read on the row
+        stream, where the rows are written (the read waits for that stream alone)"""
+        with torch.cuda.stream(self.ctx.stream):
+            return int((self.sample[:self.n_real] != 0).any(dim=0).sum().item())
+
+    def spike_result(self):
+        """the posterior means: inclusion pi_d, precision tau_d, activity n_d / N (D each) and row_inclusion (N x D)"""
+        torch.cuda.synchronize(self.ctx.device)
+        n, D = max(self.spike_draws, 1), self.D
+        h = self.spike_hyper_sum.cpu().numpy()
+        rows = self.spike_row_sum.cpu().numpy()[:self.n_real] / n
+        if self.spike_draws == 0:
+            h, rows = np.full(3 * D, np.nan), np.full((self.n_real, D), np.nan)
+        return {"inclusion": h[:D] / n, "precision": h[D:2 * D] / n, "activity": h[2 * D:] / (n * float(self.n_real)), "row_inclusion": rows}
 
     @property
     def sample(self):
@@ -868,6 +908,10 @@ class GibbsEngine:
             self.layouts.append(Layout(en.count, deg, self.world, chunks))
         # ---- reset! (RelationData.jl:331-355)
         self.ent = []
+        for en in data.entities:
+            if en.spike is not None:
+                from .relation_data import check_spike
+                check_spike(en, 1 if shard is None else shard[1])
         for j, en in enumerate(data.entities):
             if not np.isnan(lambda_beta):
                 en.lambda_beta = float(lambda_beta)
@@ -1034,6 +1078,9 @@ class GibbsEngine:
             if st.bg_Lambda is not None:
                 for name in ("bg_Lambda", "bg_mu", "bg_pack", "bg_alpha_rows"):
                     setattr(g, name, getattr(st, name).data_ptr())
+            if st.spike is not None:
+                g.spike, g.spike_state = 1, st.spike_state.data_ptr()
+                g.spike_a, g.spike_b, g.spike_shape, g.spike_rate = (st.spike[k] for k in ("incl_a", "incl_b", "shape", "rate"))
             if st.F is not None:
                 g.feat = st.F.handle
                 for name in ("beta", "uhat", "mu_matrix", "Tinv", "lambda_beta", "cg_iters"):
@@ -1115,6 +1162,15 @@ class GibbsEngine:
         """-> a device scalar, the mean of this iteration's omega (the verbose line reads it with the other scalars)"""
         with torch.cuda.stream(self.ctx.stream):
             return self.rel[ri].omega.mean()
+
+    def spike_accumulate(self):
+        """(entities with the spike-and-slab prior, after the burn-in) this draw's inclusions, pi, tau and counts into their running
+        sums, on the row stream once the hyper step of this iteration (the hyperprior stream) has written the state"""
+        if self.ctx_h is not self.ctx:
+            self.ctx.stream.wait_stream(self.ctx_h.stream)
+        for st in self.ent:
+            if st.spike is not None:
+                st.spike_accumulate()
 
     def entity_noise_accumulate(self, ri=0):
         """(relation ri with a noise precision per row, after the burn-in) this iteration's tau into the running sum, on the row
@@ -1342,6 +1398,12 @@ class GibbsEngine:
         if not en.relations:
             raise ArgumentError(f"Entity {en.name} takes part in no relation")
         terms = self._terms(j)
+        if st.spike is not None:
+            # the spike-and-slab prior: every row by the coordinate sweep from its current value, into the next buffer
+            check(lib().bdf_sample_rows_spike(self.ctx.handle, self.D, st.N, len(terms), terms, _ptr(st.spike_state), _ptr(st.sample),
+                                              st.tag, 0, 1, _ptr(st.sample_next)))
+            st.rotate()
+            return
         mu, is_matrix = st.mu, 0
         if st.F is not None:
             check(lib().bdf_uhat(self.ctx.handle, st.F.handle, self.D, _ptr(st.beta), _ptr(st.mu), _ptr(st.uhat), _ptr(st.mu_matrix)))
@@ -1374,6 +1436,8 @@ class GibbsEngine:
     def prepare_prior(self, j, sweep):
         """the data-independent part of update_prior(j) of this sweep; may be issued before the rows of j are sampled"""
         st = self.ent[j]
+        if st.spike is not None:      # (its hyper step draws from the rows' counts: nothing to prepare)
+            return
         check(lib().bdf_hyper_draws(self.ctx_h.handle, self.D, st.n_real, self._hyper_nu(j), st.tag, _ptr(st.draws)))
         st.draws_sweep = sweep
 
@@ -1382,6 +1446,11 @@ class GibbsEngine:
         L = lib()
         h = self.ctx_h.handle
         draws = st.draws if (sweep is not None and st.draws_sweep == sweep) else None
+        if st.spike is not None:
+            sp = st.spike
+            check(L.bdf_spike_hyper(h, self.D, st.n_real, _ptr(st.sample), sp["incl_a"], sp["incl_b"], sp["shape"], sp["rate"], st.tag,
+                                    _ptr(st.spike_state)))
+            return
         if self.comm is not None and self.world > 1:      # own rows, then the ranks' partial sums added in rank order
             check(L.bdf_hyper_sums_ranks(h, self.comm.handle, self.D, st.N, st.layout.chunks, _ptr(st.sample),
                                          _ptr(st.uhat) if st.F is not None else None, _ptr(st.sumU), _ptr(st.UUt)))

@@ -53,6 +53,7 @@ class Entity:
         self.lambda_beta_sample = True
         self.mu = 1.0          # hyper-prior for lambda_beta
         self.nu = 1e-3
+        self.spike = None      # setSpikeAndSlab: {"incl_a", "incl_b", "shape", "rate"}; None: the Normal-Wishart prior
         self.model = None
 
     def __repr__(self):
@@ -77,6 +78,8 @@ def toStr(x):
             s += f" β:{st.norm('beta'):3.2f}"
             if x.lambda_beta_sample:
                 s += f" λ={x.lambda_beta:1.1f}"
+        if x.spike is not None and st.spike_state is not None:
+            s += f" on:{st.spike_active()}"
         return f"{x.name[:3]}[{s}]"
     kind = noise_kind(x)
     if kind in ("logit", "counts"):
@@ -562,6 +565,53 @@ def check_entity_noise(r):
     _entity_noise_guards(r, "a noise precision per row (setEntityNoise)")
     m = r.model.entity_noise
     r.model.entity_noise = _entity_noise_spec(r, m.get("mode"), m.get("shape"), m.get("rate"))
+
+
+def setSpikeAndSlab(entity, incl_a=1.0, incl_b=1.0, shape=1.0, rate=1.0):
+    """A spike-and-slab prior for the rows of `entity` in place of the Normal-Wishart one (the reference has none; its successor SMURFF
+    does): loading d of row i is u_id = s_id w_id with s_id ~ Bernoulli(pi_d), w_id ~ N(0, 1 / tau_d), pi_d ~ Beta(incl_a, incl_b) and
+    tau_d ~ Gamma(shape, rate) (rate parametrisation).  A component can be switched off for the whole entity -- with one column entity
+    per view this is the group sparsity of group factor analysis -- and a single loading can be exactly zero.  macau() samples
+    (s_id, w_id) one component after the other from their exact conditional and returns, under
+    result["spike"][entity.name], the posterior means "inclusion" (pi_d), "precision" (tau_d), "activity" (the share of rows with a
+    nonzero loading) per component and "row_inclusion" (N x D).  The verbose line's " on:<k>" for such an entity is the number of
+    components with a nonzero loading in the current draw (a count, not their list).  The entity takes no side information, none of its relations a
+    background (setBackground); one rank only.  The other entities keep their prior; every noise model composes."""
+    if not isinstance(entity, Entity):
+        raise ArgumentError(f"setSpikeAndSlab takes an Entity, not {type(entity).__name__}.")
+    spec = _spike_spec(entity, incl_a, incl_b, shape, rate)
+    _spike_guards(entity)
+    entity.spike = spec
+    return None
+
+
+def _spike_spec(entity, incl_a, incl_b, shape, rate):
+    def number(x):
+        return not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating)) and np.isfinite(x)
+    for name, x in (("incl_a", incl_a), ("incl_b", incl_b), ("shape", shape)):
+        if not number(x) or x < 0.5:
+            raise ArgumentError(f"Entity {entity.name}: {name} = {x} must be a finite number, at least 0.5 (setSpikeAndSlab).")
+    if not number(rate) or rate <= 0:
+        raise ArgumentError(f"Entity {entity.name}: rate = {rate} must be a finite number above 0 (setSpikeAndSlab).")
+    return {"incl_a": float(incl_a), "incl_b": float(incl_b), "shape": float(shape), "rate": float(rate)}
+
+
+def _spike_guards(entity):
+    if hasFeatures(entity):
+        raise ArgumentError(f"Entity {entity.name} has features: the spike-and-slab prior (setSpikeAndSlab) does not take side information.")
+    for r in entity.relations:
+        if r.model.background is not None:
+            raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
+                                "spike-and-slab prior (setSpikeAndSlab), the background folds a dense Gram matrix into the prior precision.")
+
+
+def check_spike(entity, world=1):
+    """what an entity with the spike-and-slab prior must still satisfy when a sampler is built on it"""
+    m = entity.spike
+    entity.spike = _spike_spec(entity, m.get("incl_a"), m.get("incl_b"), m.get("shape"), m.get("rate"))
+    _spike_guards(entity)
+    if world > 1:
+        raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): one rank only")
 
 
 def setBackground(r, weight, value=0.0):

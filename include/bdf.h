@@ -62,6 +62,9 @@ extern "C" {
 #define BDF_P_PG 18            /* bdf_pg_draw: one cursor per observation over the blocks pair = 0, 1, 2, ... (entity 0x800000 | rel_tag, row = observation) */
 #define BDF_P_NOISE_N 19       /* bdf_entity_noise_draw: the gamma variate's normals (entity 0x800000 | rel_tag, row = 0-based row of the noise entity, attempt t: normal 2 t) */
 #define BDF_P_NOISE_U 20       /* bdf_entity_noise_draw: ... and its uniforms (the same entity and row, pair = attempt; shape < 1: the boost's uniform is pair 0xffff) */
+#define BDF_P_SPIKE_N 21       /* bdf_spike_hyper: the gamma variates' normals (entity = entity_tag, row = variate 3 d, 3 d + 1, 3 d + 2 of component d, attempt t: normal 2 t) */
+#define BDF_P_SPIKE_U 22       /* bdf_spike_hyper: ... and their uniforms (the same entity and row, pair = attempt; shape < 1: the boost's uniform is pair 0xffff) */
+#define BDF_P_SPIKE 23         /* bdf_sample_rows_spike: the inclusion uniform of component d of a row (entity = entity_tag, row = original row, pair d, words x and y) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -247,6 +250,33 @@ int bdf_normals(bdf_ctx *ctx, uint32_t purpose, uint32_t entity_tag, int64_t row
 /* parity hook: raw Philox4x32-10 block for (purpose, entity_tag, row, pair) at the current sweep */
 int bdf_philox(bdf_ctx *ctx, uint32_t purpose, uint32_t entity_tag, uint64_t row, uint32_t pair,
                uint32_t out_host[4]);
+
+/* Spike-and-slab prior of an entity's rows (csrc/k_rows_ss.hip, csrc/k_spike_hyper.hip, csrc/spike.h):
+ *   u_id = s_id w_id,  s_id ~ Bernoulli(pi_d),  w_id ~ N(0, 1 / tau_d),  pi_d ~ Beta(incl_a, incl_b),  tau_d ~ Gamma(shape, rate).
+ * spike_state (dev, 4 D doubles): pi (D), tau (D), logit pi (D), log tau (D).
+ * bdf_sample_rows_spike: the rows of bdf_sample_rows' (shard, n_shards) under this prior.  With P_i and c_i the row system of
+ * bdf_row_system for Lambda = diag(tau), mu = 0, and u the row's current value u_current[:, i] (dev, D x N), for d = 0 .. D-1 in order:
+ *   lambda = P_dd,  m = (c_d - sum_{k != d} P_dk u_k) / lambda,  lo = logit pi_d + (log tau_d - log lambda) / 2 + lambda m^2 / 2,
+ *   s = [U_d < 1 / (1 + exp(-lo))],  u_d = s (m + z_d / sqrt(lambda))          (an excluded loading is +0.0)
+ * with z_d normal d of stream (BDF_P_ROW, entity_tag, i) and U_d the uniform of words x and y of block (BDF_P_SPIKE, entity_tag,
+ * i, pair d).  out (dev, D x N): must alias neither u_current nor a factor matrix of another mode.  A lambda that is not positive
+ * and finite raises the flag of a matrix that is not positive definite (bdf_ctx_sync: BDF_ERR_NOTPD).  Every row is taken by the
+ * wave-per-item kernel, long rows split as bdf_sample_rows splits them. */
+int bdf_sample_rows_spike(bdf_ctx *ctx, int D, int64_t N, int n_terms, const bdf_term *terms, const double *spike_state,
+                          const double *u_current, uint32_t entity_tag, int shard, int n_shards, double *out);
+/* The prior's hyper step from the rows in `sample` (dev, D x N): n_d = #{i : u_id != 0} (exact) and q_d = sum_i u_id^2 (blocks of
+ * 256 rows in row order, then the blocks in order: independent of the launch), then with Gamma(a, 1) variates by Marsaglia-Tsang
+ * on the streams (BDF_P_SPIKE_N, entity_tag, row g) and (BDF_P_SPIKE_U, the same), g = 3 d, 3 d + 1, 3 d + 2:
+ *   G1 ~ Gamma(incl_a + n_d),  G2 ~ Gamma(incl_b + N - n_d),  G3 ~ Gamma(shape + n_d / 2),
+ *   pi_d = G1 / (G1 + G2),  logit pi_d = log G1 - log G2,  tau_d = G3 / (rate + q_d / 2),  log tau_d
+ * into spike_state.  incl_a, incl_b, shape >= 0.5 and finite, rate > 0 and finite.  Two launches on ctx's stream; not reentrant on
+ * one context (the partial sums live in the context's scratch). */
+int bdf_spike_hyper(bdf_ctx *ctx, int D, int64_t N, const double *sample, double incl_a, double incl_b, double shape, double rate,
+                    uint32_t entity_tag, double *spike_state);
+/* The running sums of the result, one call per retained draw: row_sum (dev, D x N) += [u_id != 0]; hyper_sum (dev, 3 D) += pi_d,
+ * tau_d and n_d (the count of the draw: integers, exact in any order).  The caller zeroes both on ctx's stream. */
+int bdf_spike_accumulate(bdf_ctx *ctx, int D, int64_t N, const double *sample, const double *spike_state, double *row_sum,
+                         double *hyper_sum);
 
 /* ---- a15: hyperprior  (src/sampling.jl:116-127, src/normal_wishart.jl:38-42, macau.jl:120-134) */
 /* sumU (dev D) = sum_i U[:,i], UUt (dev D x D) = U U' with U = sample - uhat (uhat nullable);
@@ -785,6 +815,13 @@ typedef struct {
     double *bg_mu;                /* dev, D; with side information D x N                                                    */
     double *bg_pack;              /* dev, bdf_prior_pack_doubles(D)                                                         */
     double *bg_alpha_rows;        /* dev, BDF_MAX_TERMS: per term of this entity, alpha (1 - c0) of a background relation   */
+    /* the spike-and-slab prior in place of the Normal-Wishart one (a zeroed tail is "none"): the entity's rows
+     * by bdf_sample_rows_spike from its current rows, its hyper step by bdf_spike_hyper.  Ordered like an entity with side
+     * information: the rows wait for the hyper step's event.  Neither side information nor a background; one rank              */
+    int32_t spike;                /* 1: on                                                                                  */
+    int32_t _pad_spike;
+    double spike_a, spike_b, spike_shape, spike_rate;   /* incl_a, incl_b, shape, rate of bdf_spike_hyper                   */
+    double *spike_state;          /* dev, 4 D: pi, tau, logit pi, log tau (initialised by the caller)                       */
 } bdf_gibbs_entity;
 int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const bdf_gibbs_entity *entities, bdf_gibbs **out);
 int bdf_gibbs_destroy(bdf_gibbs *g);

@@ -154,6 +154,34 @@ function sample_rows!(c::Context, D, N, terms::Vector{Term}, mu::DevArray{Float6
                 prior_pack === nothing ? C_NULL : prior_pack.p))
 end
 
+"""
+    sample_rows_spike!(ctx, D, N, terms, spike_state, u_current, entity_tag, out; shard=0, n_shards=1)
+
+The rows of an entity with the spike-and-slab prior (the reference has none): u_id = s_id w_id, one coordinate after the other from
+the exact conditional of (s_id, w_id), starting from the row's current value `u_current` (D x N); `spike_state` holds pi, tau,
+logit pi and log tau (4 D doubles).
+"""
+function sample_rows_spike!(c::Context, D, N, terms::Vector{Term}, spike_state::DevArray{Float64}, u_current::DevArray{Float64}, entity_tag,
+                            out::DevArray{Float64}; shard=0, n_shards=1)
+    check(ccall((:bdf_sample_rows_spike, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Cint, Ptr{Term}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Cint, Cint, Ptr{Cvoid}),
+                c.h, D, N, length(terms), terms, spike_state.p, u_current.p, entity_tag, shard, n_shards, out.p))
+end
+
+"the spike-and-slab prior's hyper step: pi_d ~ Beta(incl_a + n_d, incl_b + N - n_d), tau_d ~ Gamma(shape + n_d / 2, rate + q_d / 2) into spike_state"
+function spike_hyper!(c::Context, D, N, sample::DevArray{Float64}, incl_a, incl_b, shape, rate, entity_tag, spike_state::DevArray{Float64})
+    check(ccall((:bdf_spike_hyper, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Float64, Float64, Float64, Float64, UInt32, Ptr{Cvoid}),
+                c.h, D, N, sample.p, incl_a, incl_b, shape, rate, entity_tag, spike_state.p))
+end
+
+"one retained draw into the running sums of the spike-and-slab result: row_sum (D x N) += [u != 0]; hyper_sum (3 D) += pi, tau, n_d"
+function spike_accumulate!(c::Context, D, N, sample::DevArray{Float64}, spike_state::DevArray{Float64}, row_sum::DevArray{Float64},
+                           hyper_sum::DevArray{Float64})
+    check(ccall((:bdf_spike_accumulate, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, D, N, sample.p, spike_state.p, row_sum.p, hyper_sum.p))
+end
+
 "ConditionalNormalWishart + rand (src/sampling.jl:116-127, src/normal_wishart.jl:38-42; call site src/macau.jl:120-134)"
 function update_prior!(c::Context, D, N, sample, uhat, sumU, UUt, mu0, b0, Tinv, nu, entity_tag, mu, Lambda;
                        prior_pack=nothing, draws=nothing)   # prior_pack: bdf_prior_pack_doubles(D) doubles; draws: bdf_hyper_draws
@@ -278,6 +306,11 @@ struct GibbsEntity                                # bdf_gibbs_entity, field for 
     # a relation of the entity has background cells (GibbsRelation.bg_weight; C_NULL: none): what background_prior! writes before
     # the entity's rows -- D x D; D (D x N with side information); prior_pack_doubles(D); BDF_MAX_TERMS doubles
     bg_Lambda::Ptr{Cvoid}; bg_mu::Ptr{Cvoid}; bg_pack::Ptr{Cvoid}; bg_alpha_rows::Ptr{Cvoid}
+    # the spike-and-slab prior in place of the Normal-Wishart one (spike = 0: none): incl_a, incl_b, shape, rate of spike_hyper! and the
+    # state (4 D doubles: pi, tau, logit pi, log tau).  No side information, no background on the entity's relations, one rank
+    spike::Int32; _pad_spike::Int32
+    spike_a::Float64; spike_b::Float64; spike_shape::Float64; spike_rate::Float64
+    spike_state::Ptr{Cvoid}
 end
 
 mutable struct Gibbs
