@@ -224,6 +224,11 @@ _SIGS = {
     "bdf_pairs_waic_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p,
                                         C.c_int, C.c_void_p]),
     "bdf_pairs_waic": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_newrows_quad": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_newrows_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
+                                     C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "bdf_newrows_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_newrows_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_dp]),
     "bdf_feat_create_dense": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.POINTER(C.c_void_p)]),
     "bdf_feat_create_csr": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, c_i32p, c_i32p, c_dp, C.POINTER(C.c_void_p)]),
     "bdf_feat_create_bin": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int64, c_i32p, c_i32p, C.POINTER(C.c_void_p)]),

@@ -71,6 +71,7 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     c->cg_bar = nullptr;
     c->rows = bdf_rows_state_create();
     c->norm_part = nullptr;
+    c->newrows_W = nullptr;
     c->scratch = nullptr;
     c->scratch2 = nullptr;
     c->scratch2_bytes = 0;
@@ -115,6 +116,7 @@ extern "C" int bdf_ctx_destroy(bdf_ctx *ctx)
     if (ctx->lr_vt) hipFree(ctx->lr_vt);
     if (ctx->lr_mrows) hipFree(ctx->lr_mrows);
     if (ctx->norm_part) hipFree(ctx->norm_part);
+    if (ctx->newrows_W) hipFree(ctx->newrows_W);
     if (ctx->own_stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return BDF_OK;

@@ -117,6 +117,7 @@ struct bdf_ctx {
     unsigned *cg_bar;                   // the hand-over counter of the one-launch CG solve (k_cg_resident), allocated at first use
     bdf_rows_state *rows;               // the row launcher's own (rows_plan.hip): cached plans, dispatch counts, what lr_T / lr_vt were computed from
     double *norm_part;                  // bdf_norm2's per-workgroup partial sums (k_auc.hip), allocated at first use
+    double *newrows_W;                  // bdf_newrows_quad's L^-1 of the call's Lambda (k_newrows.hip: BDF_MAX_D x BDF_MAX_D), allocated at first use
 };
 
 int bdf_scratch(bdf_ctx *ctx, size_t bytes, void **out);
@@ -186,6 +187,9 @@ struct bdf_pairs {
     double waic_draws;            // ... and the posterior draws it holds (a counter of its own)
     const double *scale_dev;      // nullable, borrowed (bdf_pairs_set_precision_scale): a precision scale per row of mode scale_mode, for k_lpd
     int scale_mode;
+    double *newrows_dev;          // bdf_newrows_update's running state (k_newrows.hip): five planes of n in storage order -- mean, M2, sum q, M, A; at first use
+    double newrows_draws;         // ... the posterior draws it holds (a counter of its own)
+    bool newrows_score;           // ... and whether their log-likelihoods were folded in (score_lpd of the phase 1 call)
 };
 
 // bdf_ordinal (k_ordinal.hip): the edges of an ordinal relation and their Metropolis step's state, all of it in ONE device buffer

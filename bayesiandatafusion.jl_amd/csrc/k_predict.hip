@@ -263,6 +263,7 @@ extern "C" int bdf_pairs_create(bdf_ctx *ctx, int n_modes, int64_t n, const void
     p->ctx = ctx; p->n_modes = n_modes; p->n = n; p->count = 0.0; p->baseline_dev = nullptr; p->orig_dev = nullptr; p->sorted_mode = -1;
     p->ids_dev = nullptr; p->values_dev = nullptr; p->avg_dev = nullptr; p->sq_dev = nullptr; p->auc_ws = nullptr; p->link = 0; p->link_r = 0.0;
     p->lpd_dev = nullptr; p->lpd_draws = 0.0; p->waic_dev = nullptr; p->waic_draws = 0.0; p->scale_dev = nullptr; p->scale_mode = 0;
+    p->newrows_dev = nullptr; p->newrows_draws = 0.0; p->newrows_score = false;
     struct Guard { bdf_pairs *p; ~Guard() { if (p) bdf_pairs_destroy(p); } } guard{p};        // error paths free what was allocated
     p->ids_host = h;
     p->values_host.assign(values, values + (n ? n : 0));
@@ -295,6 +296,7 @@ extern "C" int bdf_pairs_destroy(bdf_pairs *p)
     if (p->auc_ws) hipFree(p->auc_ws);
     if (p->lpd_dev) hipFree(p->lpd_dev);
     if (p->waic_dev) hipFree(p->waic_dev);
+    if (p->newrows_dev) hipFree(p->newrows_dev);
     delete p;
     return BDF_OK;
 }

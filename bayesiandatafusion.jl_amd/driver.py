@@ -14,7 +14,7 @@ import numpy as np
 from . import features as feat
 from ._lib import ArgumentError
 from .engine import GibbsEngine
-from .relation_data import _ordinal_bounds, _waic_bounds, check_test_interval, hasFeatures, noise_kind, numTest, toStr
+from .relation_data import _ordinal_bounds, _waic_bounds, check_new_rows, check_test_interval, hasFeatures, noise_kind, numTest, toStr
 
 
 def AUC_ROC(Ytrue, scores):
@@ -78,7 +78,9 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if lpd and kind in ("logit", "counts"):
         raise ArgumentError(f"lpd = true is not possible when Relation has the {kind} noise model "
                             "(setLogit / setCounts): a held-out cell's density under it is not scored yet.")
-    if lpd and not (data.relations and numTest(data.relations[0]) > 0):
+    # cells of rows that were not in training (setNewRows / setNewTest on the first relation)
+    new_rel = check_new_rows(data)
+    if lpd and not (data.relations and numTest(data.relations[0]) > 0) and new_rel is None:
         raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")
 
     # top-K lists (setRecommend) are kept for the first relation, like lpd and WAIC
@@ -101,6 +103,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         raise ArgumentError("lpd = true is not possible with more than one rank: every rank scores only the test cells it predicts.")
     if waic is not None and eng.world > 1:
         raise ArgumentError("WAIC (setWaic) is not possible with more than one rank: every rank holds the state of its own cells only.")
+    if new_rel is not None:
+        check_new_rows(data, eng.world)
     data._engine = eng
     if eng is engine and (recommend is not None or eng.scores is not None):
         eng.begin_scores()                                   # (an engine that is reused starts the sum of scores again)
@@ -126,6 +130,10 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     haveTest = numTest(rel) > 0
     test = eng.test_pairs() if haveTest else None
     train = eng.train_pairs() if rmse_train else None
+    # (nothing is allocated or launched for new rows unless setNewTest was called)
+    newr = eng.new_rows(fresh=True) if new_rel is not None else None
+    new_rep = np.full(10, np.nan)
+    lpd_new, lpd = lpd, (lpd and haveTest)
     lpd_bounds, lpd_avg = None, float("nan")
     # ordinal first relation with sampled edges: a trace row per iteration, the step size adapted in the burn-in
     ordinal = eng.ordinal_begin(burnin, psamples) if rel.model.ordinal is not None else None
@@ -183,7 +191,7 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             eng.entity_noise_accumulate()                     # this iteration's tau into its running sum, on the row stream
         if spiked and i > burnin:
             eng.spike_accumulate()                            # this draw's inclusions, pi and tau into their running sums, on the row stream
-        if lpd or waic is not None:
+        if lpd or waic is not None or newr is not None:
             # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
             # has read the same double, and the device scalar is redrawn on another stream than the pairs')
             a = 1.0 if rel.model.probit else (rel._dev.alpha_dev if (rel.model.alpha_sample and eng.native) else rel.model.alpha)
@@ -197,6 +205,10 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 # the tau that the cells are scored with -- under this launch.  The native iteration scores on the row stream itself
                 # and needs nothing)
                 eng.ctx.stream.wait_stream(test.ctx.stream)
+        if newr is not None:
+            # uhat of the new rows, q of the other entity's rows and the cells' update, on the row stream behind this iteration's last
+            # launch: beta, V, (mu, Lambda) and alpha are this iteration's draw (the stream-order argument: DESIGN.md section 24)
+            newr.step(phase, clamp, rel.class_cut, a, lpd_new)
         if waic is not None:
             if waic_codes is not None:        # this draw's edges, ordered as for the test cells above
                 ordinal.bounds(waic_pairs.ctx, waic_codes, waic_bounds)
@@ -232,6 +244,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 # roc_avg = AUC_ROC(test_label, -probe_avg) (macau.jl:200) on the device, behind this iteration's prediction update
                 # on the same stream; it lands beside the 4 stats (test.report), read back together after the one sync
                 test.auc(rel.class_cut, eng.ctx_p)
+            if newr is not None:
+                newr.auc()                                    # behind the cells' update on the row stream, beside its 8 scalars
             wbar = eng.robust_mean() if (verbose and robust is not None) else None
             tbar = eng.entity_noise_mean() if (verbose and noise is not None) else None
             eng.sync()
@@ -247,6 +261,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                     lpd_avg = float(rep[6]) / n
             if waic is not None:
                 waic_stats = waic_pairs.waic_stats.cpu().numpy()
+            if newr is not None:
+                new_rep = newr.report.cpu().numpy()
             if verbose:
                 estr = " ".join(toStr(en) for en in data.entities)
                 rstr = " ".join(toStr(r) for r in data.relations)
@@ -257,6 +273,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                     lstr += f" w̄={float(wbar.item()):.3f}"
                 if tbar is not None:
                     lstr += f" τ̄={float(tbar.item()):.3f}"
+                if newr is not None:
+                    nsc = max(newr.n_scored, 1)
+                    lstr += f" new:RMSE={math.sqrt(new_rep[0] / nsc):6.4f} ROC={new_rep[8]:6.4f}"
+                    if lpd_new:
+                        lstr += f" LPD={new_rep[5] / nsc:.4f}"
                 if ordinal is not None:
                     lstr += " cut=[" + " ".join(f"{e:.3f}" for e in rel.model.ordinal_edges) + "]"
                 print(f"{i:3d}: ROC={roc_avg:6.4f} RMSE={rmse_avg:6.4f}{lstr} | {estr} | {rstr} [{time.time() - time0:1.1f}s]")
@@ -318,6 +339,22 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         if rec_dev[2] is not None:
             m = rec_dev[2].cpu().numpy()
             result["recommend"].update({"recall": float(m[0]), "ndcg": float(m[1]), "hit_rate": float(m[2]), "rows_scored": int(m[3])})
+    if newr is not None:
+        # the cells' (pred, stdev, lpd) in the caller's order and the posterior mean of the new rows' factors: all that comes back
+        import pandas as pd
+        out, fac = newr.result()
+        spec, nsc = rel.model.new_test, newr.n_scored
+        frame = {rel.data.names[k]: spec["ids"][:, k] for k in range(2)}
+        frame[rel.data.names[-1]] = spec["values"]
+        frame["pred"], frame["stdev"] = out[:, 0], out[:, 1]
+        if lpd_new:
+            frame["lpd"] = out[:, 2]
+        scored = nsc > 0 and psamples >= 1
+        result["new_rows"] = {"entity": rel.entities[spec["mode"] - 1].name, "n_rows": newr.n_rows, "predictions": pd.DataFrame(frame),
+                              "RMSE": math.sqrt(new_rep[0] / nsc) if scored else float("nan"), "ROC": float(new_rep[8]),
+                              "accuracy": float(new_rep[2] / nsc) if scored else float("nan"), "n_scored": nsc, "factors": fac}
+        if lpd_new:
+            result["new_rows"]["LPD"] = float(new_rep[5] / nsc) if scored else float("nan")
     if waic is not None:
         # lppd, p_waic and the squares of elpd_t about its mean from the device (bdf_pairs_waic): the pointwise table comes to the
         # host only when asked for

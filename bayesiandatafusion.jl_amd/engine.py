@@ -530,6 +530,107 @@ class DeviceScores:
             pass
 
 
+class DeviceNewRows:
+    """Cells of rows that were not in training (setNewRows / setNewTest; csrc/k_newrows.hip): the operator of
+    the new rows' features, their cells as pairs whose first mode indexes the new rows, and the buffers of the three launches that
+    follow every iteration on the row stream -- uhat of the new rows (bdf_uhat), q per row of the other entity (bdf_newrows_quad),
+    the update of the cells' running state (bdf_newrows_update).  Nothing of a draw comes to the host."""
+
+    def __init__(self, eng, r):
+        spec = r.model.new_test
+        mode0 = spec["mode"] - 1
+        self.eng, self.rel, self.mode0 = eng, r, mode0
+        ctx = self.ctx = eng.ctx
+        self.st = eng.ent[eng._entity_index(r.entities[mode0])]          # the entity with features and new rows
+        self.so = eng.ent[eng._entity_index(r.entities[1 - mode0])]      # the other one: V
+        D = self.D = eng.D
+        self.F = FeatOperator(ctx, r.entities[mode0].new_rows)
+        self.n_rows = self.F.m
+        ids, vals = spec["ids"], spec["values"]
+        # (the new row's id first, whichever of the relation's columns holds it; stored sorted by the existing row: neighbours share v_j and q_j)
+        self.pairs = DevicePairs(ctx, np.stack([ids[:, mode0], ids[:, 1 - mode0]], axis=1).reshape(-1, 2), vals)
+        if self.pairs.n:
+            self.pairs.sort(1)
+        if r.model.probit:
+            self.pairs.set_link(1)
+        self.uhat = ctx.zeros(self.n_rows, D)
+        self.factors = ctx.zeros(self.n_rows, D)           # mu + uhat: what the cells are predicted from
+        self.factors_sum = ctx.zeros(self.n_rows, D)
+        self.q = ctx.zeros(max(self.so.N, 1))
+        self.report = ctx.zeros(10)                        # bdf_newrows_update's 8, then the ROC of the running mean
+        self.draws = 0
+        # the cells with a value, in the caller's order: what the ROC ranks
+        has = ~np.isnan(vals)
+        self.n_scored = int(has.sum())
+        self._has = ctx.tensor(np.nonzero(has)[0], dtype=torch.int64)
+        self._labels = ctx.tensor((vals[has] < r.class_cut).astype(np.uint8), dtype=torch.uint8)
+        self._auc_ws = torch.empty(max(1, lib().bdf_auc_workspace_bytes(self.n_scored)), dtype=torch.uint8, device=ctx.device)
+        self._out = ctx.zeros(max(self.pairs.n, 1), 3)
+
+    def step(self, phase, clamp, class_cut, alpha, lpd):
+        """the three launches behind iteration's last launch, on the row stream.  They read beta and V (written on the row stream) and
+        (mu, Lambda) of this iteration (the hyperprior stream: the row stream is already behind that draw, which beta's update waited
+        for; the wait below says so again).  Everything that overwrites one of them in the next iteration is either on the row stream
+        or waits for the next iteration's rows of this entity, which are enqueued on the row stream behind these launches."""
+        eng, ctx, D, L = self.eng, self.ctx, self.D, lib()
+        if eng.ctx_h is not ctx:
+            ctx.stream.wait_stream(eng.ctx_h.stream)
+        check(L.bdf_uhat(ctx.handle, self.F.handle, D, _ptr(self.st.beta), _ptr(self.st.mu), _ptr(self.uhat), _ptr(self.factors)))
+        check(L.bdf_newrows_quad(ctx.handle, D, self.so.N, _ptr(self.st.Lambda), _ptr(self.so.sample), _ptr(self.q)))
+        lo, hi = (clamp[0], clamp[1]) if len(clamp) else (1.0, -1.0)
+        on_dev = torch.is_tensor(alpha)
+        check(L.bdf_newrows_update(ctx.handle, self.pairs.handle, D, _ptr(self.factors), _ptr(self.so.sample), _ptr(self.q),
+                                   float(self.rel.model.mean_value), 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
+                                   lo, hi, float(class_cut), int(bool(lpd)), _ptr(self.report)))
+        if phase >= 1:
+            with torch.cuda.stream(ctx.stream):
+                if phase == 1:
+                    self.factors_sum.copy_(self.factors)
+                    self.draws = 1
+                else:
+                    self.factors_sum += self.factors
+                    self.draws += 1
+
+    def auc(self):
+        """AUC_ROC(values .< class_cut, -pred) over the cells with a value (bdf_auc_roc on the running mean, in the caller's order)
+        into report[8], behind the update on the row stream; NaN before the first posterior draw"""
+        ctx = self.ctx
+        with torch.cuda.stream(ctx.stream):
+            if self.draws < 1 or self.n_scored == 0:
+                self.report[8] = float("nan")
+                return
+            check(lib().bdf_newrows_result(ctx.handle, self.pairs.handle, _ptr(self._out)))
+            scores = (-self._out[:, 0]).index_select(0, self._has).contiguous()
+            check(lib().bdf_auc_roc(ctx.handle, self.n_scored, _ptr(self._labels), _ptr(scores), _ptr(self._auc_ws),
+                                    C.c_void_p(self.report.data_ptr() + 64), None))
+            scores.record_stream(ctx.stream)
+
+    def result(self):
+        """(n, 3) host array of (pred, stdev, lpd) in the caller's order and the (n*, D) posterior mean of the new rows' factors"""
+        ctx = self.ctx
+        with torch.cuda.stream(ctx.stream):
+            if self.draws < 1:
+                return np.full((self.pairs.n, 3), np.nan), np.full((self.n_rows, self.D), np.nan)
+            if self.pairs.n:
+                check(lib().bdf_newrows_result(ctx.handle, self.pairs.handle, _ptr(self._out)))
+            out = self._out[:self.pairs.n].cpu().numpy()
+            fac = (self.factors_sum / float(self.draws)).cpu().numpy()
+        return out, fac
+
+    def state(self):
+        """parity hook: the running state as a (5, n) host array in STORAGE order -- mean, M2, sum q, M, A -- and the draws it holds"""
+        st, draws = C.c_void_p(), C.c_double()
+        check(lib().bdf_newrows_state(self.pairs.handle, C.byref(st), C.byref(draws)))
+        out = np.zeros((5, self.pairs.n))
+        if st.value and self.pairs.n:
+            check(lib().bdf_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), st, out.size * 8))
+        return out, draws.value
+
+    def close(self):
+        self.pairs.close()
+        self.F.close()
+
+
 def device_auc_roc(labels, scores):
     """AUC_ROC(labels, scores) (src/ROC.jl:1-11) of GPU tensors through bdf_auc_roc, on torch's current stream ->
     (auc, C, P, Nn): C the exact number of (negative, positive) pairs ranked in that order, P / Nn the class sizes"""
@@ -940,6 +1041,7 @@ class GibbsEngine:
         self.begin_scores()
         self._test_pairs = None
         self._train_pairs = None
+        self._new_rows = None
         self._test_opts = None
         self.k1_spans = None      # bench.py: (tensor n x 2 of uint64 ticks as int64, [entity per used slot]) -- device-side launch spans (k1_span_begin)
         self.k1_events = None     # bench.py: list of (entity, KernelTimer) of the timed K1 launches
@@ -1681,6 +1783,15 @@ class GibbsEngine:
             r = self.data.relations[0]
             check(lib().bdf_feat_linear(self.ctx.handle, dr.F_test.handle, _ptr(dr.beta), r.model.mean_value, _ptr(dr.test_baseline)))
 
+    def new_rows(self, fresh=False):
+        """the first relation's cells of new rows (setNewTest) on the device, built at first use; fresh: built again, with no state"""
+        if fresh and self._new_rows is not None:
+            self._new_rows.close()
+            self._new_rows = None
+        if self._new_rows is None:
+            self._new_rows = DeviceNewRows(self, self.data.relations[0])
+        return self._new_rows
+
     def train_pairs(self):
         r = self.data.relations[0]
         if self._train_pairs is None and self.rel[0].train is not None:
@@ -1696,7 +1807,7 @@ class GibbsEngine:
             self.sync()
         except Exception:
             pass
-        for p in (self._test_pairs, self._train_pairs, self.scores):
+        for p in (self._test_pairs, self._train_pairs, self.scores, self._new_rows):
             if p is not None:
                 p.close()
         for st in self.ent:

@@ -54,6 +54,7 @@ class Entity:
         self.mu = 1.0          # hyper-prior for lambda_beta
         self.nu = 1e-3
         self.spike = None      # setSpikeAndSlab: {"incl_a", "incl_b", "shape", "rate"}; None: the Normal-Wishart prior
+        self.new_rows = None   # setNewRows: the features (n* x numF) of instances that are not among the entity's rows
         self.model = None
 
     def __repr__(self):
@@ -132,6 +133,7 @@ class RelationModel:
         self.background = None    # setBackground: {"weight", "value"}; every cell that is not listed observes `value` with precision alpha weight
         self.recommend = None     # setRecommend: {"k", "rows", "exclude_listed", "batch"}; macau() returns a top-k list per row of the first entity
         self.entity_noise = None  # setEntityNoise: {"mode" (1-based), "shape", "rate"}; a sampled noise precision per row of that entity
+        self.new_test = None      # setNewTest: {"mode" (1-based: the entity with new rows), "ids" (n, 2), "values" (NaN: unknown)}; cells of new rows
 
 
 def noise_kind(r):
@@ -739,6 +741,123 @@ def check_recommend(r):
     _recommend_guards(r)
     m = r.model.recommend
     r.model.recommend = _recommend_spec(r, m.get("k"), m.get("rows"), m.get("exclude_listed"), m.get("batch"))
+
+
+def setNewRows(entity, F_new):
+    """Features of instances of `entity` that are NOT among its rows -- a compound nobody has assayed, a user who has rated nothing:
+    F_new (n* x numF; dense, scipy sparse, SparseMatrixCSR or SparseBinMatrix) has the columns of entity.F.  macau() predicts the
+    cells that setNewTest lists for them from every posterior draw of the link matrix beta: given the draw, the factor of a new row
+    with features f is N(mu + beta' f, Lambda^-1), which is integrated out of the cell's prediction in closed form (DESIGN.md
+    section 24).  F_new must carry the normalisation that was applied to entity.F (normalizeFeatures / normalizeRows work on
+    entity.F alone: scale the new rows with the SAME column norms, or normalise their rows the same way, before passing them).
+    The entity must have features and keep the Normal-Wishart prior (not setSpikeAndSlab).  None clears it."""
+    if not isinstance(entity, Entity):
+        raise ArgumentError(f"setNewRows takes an Entity, not {type(entity).__name__}.")
+    if F_new is None:
+        entity.new_rows = None
+        return None
+    _new_rows_guards(entity, F_new)
+    entity.new_rows = F_new
+    return None
+
+
+def _new_rows_guards(entity, F_new):
+    if not hasFeatures(entity):
+        raise ArgumentError(f"Entity {entity.name} has no features: new rows (setNewRows) are predicted from their features through beta.")
+    if entity.spike is not None:
+        raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): it takes no side information and no new rows (setNewRows).")
+    if feat.isempty(F_new):
+        raise ArgumentError(f"Entity {entity.name}: F_new is empty (setNewRows takes a matrix with one row per new instance; None clears it).")
+    have, want = feat.feature_shape(F_new)[1], feat.feature_shape(entity.F)[1]
+    if have != want:
+        raise ArgumentError(f"Entity {entity.name}: F_new has {have} columns but the entity's features have {want} (setNewRows).")
+
+
+def setNewTest(r, entity, table):
+    """Cells of relation r in the rows that setNewRows gave `entity`: a table shaped like setTest's, in the relation's column order,
+    where the id in `entity`'s column is 1 ... n* into F_new, the other id is an existing instance of the other entity and the last
+    column is the held-out value -- NaN where it is unknown: such a cell is predicted and left out of every score.  macau() then
+    returns result["new_rows"] = {"entity", "n_rows", "predictions" (the ids, value, pred, stdev and, with lpd = true, lpd),
+    "RMSE", "ROC", "accuracy", "n_scored", "factors" (n* x D: the posterior mean of mu + beta' f) and, with lpd = true, "LPD"}; stdev
+    is the posterior sd of the cell's noise-free value, new row's factor included (probit: of its probability).  The first relation
+    of its RelationData, two modes, no relation features, one rank; Gaussian noise (fixed or sampled alpha; also with setCensored,
+    setInterval / setBinned and setBackground: a held-out value is a measurement) or setProbit (values 0 / 1 or NaN).  None clears it."""
+    if table is None:
+        r.model.new_test = None
+        return None
+    if not isinstance(entity, Entity):
+        raise ArgumentError(f"setNewTest takes an Entity, not {type(entity).__name__}.")
+    hit = [k for k, e in enumerate(r.entities) if e is entity]
+    if not hit:
+        raise ArgumentError(f"Relation {r.name} has no entity {entity.name} (setNewTest).")
+    _new_test_guards(r, entity)
+    ids, vals, _ = _split_table(table)
+    ids, vals = np.asarray(ids), np.asarray(vals, dtype=np.float64).reshape(-1)
+    if ids.ndim != 2 or ids.shape[1] != 2 or len(ids) != len(vals):
+        raise ArgumentError(f"Relation {r.name}: the table of new cells must have two id columns and a value column (setNewTest).")
+    if not np.issubdtype(ids.dtype, np.integer):
+        if ids.size and not (np.all(np.isfinite(ids)) and np.all(ids == np.floor(ids))):
+            raise ArgumentError(f"Relation {r.name}: the ids of new cells must be integers (setNewTest).")
+        ids = ids.astype(np.int64)
+    r.model.new_test = _new_test_spec(r, hit[0] + 1, ids.astype(np.int64), vals)
+    return None
+
+
+def _new_test_guards(r, entity):
+    what = "cells of new rows (setNewTest)"
+    if len(r.entities) != 2 or len(r.data.dims) != 2:
+        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: {what} do not take relation-level side information.")
+    kind = noise_kind(r)
+    why = {"logit": f"{_pg_name(r) if r.model.pg is not None else ''}: the marginal over a new row's factor has no closed form",
+           "counts": f"{_pg_name(r) if r.model.pg is not None else ''}: the marginal over a new row's factor has no closed form",
+           "robust": "the robust noise model (setRobust): the marginal over a new row's factor has no closed form",
+           "weights": "observation weights (setWeights): the weight of a new cell is unknown",
+           "entity_noise": "a noise precision per row (setEntityNoise): the precision of a new row is unknown",
+           "ordinal": "the ordinal noise model (setOrdinal): a held-out level is not a measurement"}
+    if kind in why:
+        raise ArgumentError(f"Relation {r.name} has {why[kind]}; {what} are not possible.")
+    if entity.new_rows is None:
+        raise ArgumentError(f"Entity {entity.name} has no new rows: call setNewRows(entity, F_new) before setNewTest.")
+    _new_rows_guards(entity, entity.new_rows)
+
+
+def _new_test_spec(r, mode, ids, vals):
+    entity = r.entities[mode - 1]
+    n_new = feat.feature_shape(entity.new_rows)[0]
+    other = 2 - mode                                       # 0-based column of the other entity
+    n_other = int(r.data.dims[other])
+    if len(ids) and (ids[:, mode - 1].min() < 1 or ids[:, mode - 1].max() > n_new):
+        raise ArgumentError(f"Relation {r.name}: a new cell's id of {entity.name} is outside 1 ... {n_new}, the rows of F_new (setNewTest).")
+    if len(ids) and (ids[:, other].min() < 1 or ids[:, other].max() > n_other):
+        raise ArgumentError(f"Relation {r.name}: a new cell's id of {r.entities[other].name} is outside 1 ... {n_other} (setNewTest).")
+    if r.model.probit and not _is_binary(vals[~np.isnan(vals)]):
+        raise ArgumentError(f"Relation {r.name} has the probit noise model: the values of its new cells must be 0, 1 or NaN (setNewTest).")
+    if np.any(np.isinf(vals)):
+        raise ArgumentError(f"Relation {r.name}: the value of a new cell must be finite, or NaN where it is unknown (setNewTest).")
+    return {"mode": int(mode), "ids": np.ascontiguousarray(ids, dtype=np.int64), "values": np.ascontiguousarray(vals, dtype=np.float64)}
+
+
+def check_new_rows(data, world=1):
+    """what setNewRows / setNewTest must still satisfy when macau() runs (models and features may have changed since); returns the
+    relation whose new cells are predicted -- the first one -- or None"""
+    for r in data.relations[1:]:
+        if r.model.new_test is not None:
+            raise ArgumentError(f"Relation {r.name} lists cells of new rows (setNewTest) but is not the first relation: macau() predicts new "
+                                "rows for the first relation only.")
+    r = data.relations[0] if data.relations else None
+    if r is None or r.model.new_test is None:
+        return None
+    m = r.model.new_test
+    entity = r.entities[m["mode"] - 1] if 1 <= m.get("mode", 0) <= len(r.entities) else None
+    if entity is None:
+        raise ArgumentError(f"Relation {r.name}: the entity of its new cells is not among its entities (setNewTest).")
+    _new_test_guards(r, entity)
+    r.model.new_test = _new_test_spec(r, m["mode"], np.asarray(m["ids"], dtype=np.int64).reshape(-1, 2), np.asarray(m["values"], dtype=np.float64))
+    if world > 1:
+        raise ArgumentError(f"Relation {r.name} lists cells of new rows (setNewTest): one rank only")
+    return r
 
 
 def _censor_flags(r, censor):

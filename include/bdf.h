@@ -588,6 +588,47 @@ int bdf_pairs_waic_update(bdf_ctx *ctx, bdf_pairs *p, const double *bounds_dev, 
  * V_k > 0.4.  (se = sqrt of [2]: n times the population variance of elpd_k.)  BDF_ERR_ARG before the first phase 1. */
 int bdf_pairs_waic(bdf_ctx *ctx, const bdf_pairs *p, double *out_dev, double *stats_out);
 
+/* ---- cells of rows that were not in training (csrc/k_newrows.hip, csrc/newrows.h) ------ */
+/* Given one posterior draw (mu, Lambda, beta, V, alpha) of an entity with side information, the factor of a NEW row with features
+ * f is u* ~ N(uhat, Lambda^-1), uhat = mu + beta' f (bdf_uhat on the new rows' features with mu_matrix_out), and it is integrated
+ * out of a cell (i*, j) in closed form -- nothing is drawn:
+ *   identity link:  y | draw ~ N(m, q_j + 1 / alpha),   m = mean_value + uhat_i* . v_j,   q_j = v_j' Lambda^-1 v_j;
+ *   probit link:    P(y = 1 | draw) = Phi(m / sqrt(1 + q_j)).
+ * bdf_newrows_quad: q_out[j] (dev M) = |L^-1 v_j|^2 for every row j of V_dev (dev, M rows of D doubles) with Lambda_dev (dev D x D,
+ * symmetric; its lower triangle is read) = L L', factorised once per call by one wavefront; the products run on
+ * v_mfma_f64_16x16x4_f64 and a row's squares are added in a fixed order (bit-identical reruns, q >= 0 by construction, error
+ * ~ D eps cond(Lambda)).  Any D in 1..BDF_MAX_D.  A Lambda that is not positive definite raises BDF_ERR_NOTPD at the next
+ * bdf_ctx_sync (q_out then holds NaNs).  Enqueued on ctx's stream; no host copy, no synchronisation. */
+int bdf_newrows_quad(bdf_ctx *ctx, int D, int64_t M, const double *Lambda_dev, const double *V_dev, double *q_out);
+/* One prediction step on the new cells.  pairs: two modes, the first mode's ids index the rows of uhat_new_dev (dev, n* rows of D
+ * doubles), the second mode's the rows of V_dev and of q_dev (bdf_newrows_quad's output); the last column is the held-out value, NaN
+ * where it is unknown.  Pairs with the probit link (bdf_pairs_set_link 1) take the probit form and ignore alpha; links 2 and 3, a
+ * baseline and a precision scale are refused (BDF_ERR_ARG).  alpha_dev (dev, nullable) wins over alpha, which must otherwise be
+ * positive and finite.  Per cell: the prediction p = m (identity) or the probability above (probit) and, with score_lpd != 0 and a
+ * finite value, l = log N(value; m, q + 1 / alpha) or log Phi(+- m / sqrt(1 + q)) by the maps of bdf_pairs_lpd_update.  The
+ * running state, five doubles per cell that the pairs own (allocated and zeroed on ctx's stream at the first phase >= 1, freed by
+ * bdf_pairs_destroy) and a draw counter of its own: Welford's (mean, M2) of p, the sum of q, the streaming log-sum-exp (M, A) of l.
+ *   phase 0 (burn-in): no state is touched;   phase 1: (mean, M2, sum q, M, A) = (p, 0, q, l, 1), draws = 1;
+ *   phase 2: draws += 1, d = p - mean, mean += d / draws, M2 += d (p - mean), sum q += q, (M, A) as bdf_pairs_lpd_update.
+ * stats_out (dev 8 doubles), over the cells with a finite value, summed in a fixed order (bit-identical reruns):
+ *   [0] sum (value - clamp(mean))^2 (phase 0: of this draw's p), [1] sum (value - clamp(p))^2, [2] / [3] the cells whose label
+ *   value < class_cut agrees with mean < class_cut / p < class_cut (clamp_lo > clamp_hi: no clamping, as bdf_predict_update),
+ *   [4] their count, [5] sum lpd = M + log A - log(draws) after this draw (phase 0: of l), [6] sum l of this draw, [7] 0;
+ *   [5] and [6] are 0 without score_lpd.  Cells with a NaN value are predicted and left out of every scalar.
+ * Enqueued on ctx's stream; no host copy, no synchronisation.  BDF_ERR_ARG for a phase outside 0..2, for phase 2 before a phase 1
+ * and for a score_lpd that differs from the phase 1 call's. */
+int bdf_newrows_update(bdf_ctx *ctx, bdf_pairs *pairs, int D, const double *uhat_new_dev, const double *V_dev, const double *q_dev,
+                       double mean_value, double alpha, const double *alpha_dev, int phase, double clamp_lo, double clamp_hi,
+                       double class_cut, int score_lpd, double *stats_out);
+/* out_dev (dev, n rows of 3 doubles, in the caller's order whether or not the pairs are stored sorted): pred = mean;
+ * stdev = sqrt(M2 / (draws - 1) + sum q / draws), the posterior sd of the cell's noise-free value (probit: sqrt(M2 / (draws - 1)),
+ * of its probability), NaN below two draws; lpd = M + log A - log(draws), NaN without score_lpd and for a NaN value.
+ * BDF_ERR_ARG before the first phase 1. */
+int bdf_newrows_result(bdf_ctx *ctx, const bdf_pairs *pairs, double *out_dev);
+/* (parity hook, as bdf_pairs_state) *state_dev = the running state, five planes of n doubles in STORAGE order -- mean, M2, sum q, M,
+ * A -- or NULL before the first phase 1; *draws = the posterior draws it holds */
+int bdf_newrows_state(const bdf_pairs *pairs, double **state_dev, double *draws);
+
 /* ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device (csrc/k_auc.hip) ------------ */
 /* bytes of the workspace bdf_auc_roc needs for n scores (-1: n < 0) */
 int64_t bdf_auc_workspace_bytes(int64_t n);

@@ -732,6 +732,33 @@ of 4 doubles): sum of lppd, sum of V, sum of (elpd - mean elpd)^2, the count of 
 pairs_waic!(c::Context, p::DevPairs, out, stats::DevArray{Float64}) =
     check(ccall((:bdf_pairs_waic, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.h, p.h, out === nothing ? C_NULL : out.p, stats.p))
 
+# ---- cells of rows that were not in training (setNewRows / setNewTest) ------------------------------------------------------
+"q[j] = v_j' Lambda^-1 v_j for the M rows of V (DevArray D x M): the variance that a new row's own factor, u* ~ N(uhat, Lambda^-1), adds
+to a cell of column j; Lambda = L L' is factorised once per call and q = |L^-1 v|^2 is formed on the matrix cores"
+newrows_quad!(c::Context, D, M, Lambda::DevArray{Float64}, V::DevArray{Float64}, q::DevArray{Float64}) =
+    check(ccall((:bdf_newrows_quad, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.h, D, M, Lambda.p, V.p, q.p))
+"one prediction step on the new cells `p` (first-mode ids index the columns of `uhat_new`, D x n*; second-mode ids those of V and q):
+the new row's factor integrated out in closed form, folded into the pairs' running state (phase 0 burn-in: nothing kept; 1 first
+posterior draw; 2 later ones); stats (DevArray of 8 doubles): SSE of the running mean, SSE of this draw, the two correct-counts at
+class_cut, the count of cells with a value, sum of lpd, sum of this draw's log-likelihoods, 0"
+function newrows_update!(c::Context, p::DevPairs, D, uhat_new::DevArray{Float64}, V::DevArray{Float64}, q::DevArray{Float64}, mean_value,
+                         alpha, alpha_dev, phase::Integer, clamp_lo, clamp_hi, class_cut, score_lpd::Bool, stats::DevArray{Float64})
+    check(ccall((:bdf_newrows_update, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Cvoid}, Cint, Float64, Float64, Float64, Cint,
+                 Ptr{Cvoid}),
+                c.h, p.h, D, uhat_new.p, V.p, q.p, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, phase, clamp_lo, clamp_hi,
+                class_cut, score_lpd ? 1 : 0, stats.p))
+end
+"(pred, stdev, lpd) of every new cell -> out (DevArray of 3 x n doubles), in the caller's order"
+newrows_result!(c::Context, p::DevPairs, out::DevArray{Float64}) =
+    check(ccall((:bdf_newrows_result, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.h, p.h, out.p))
+"(parity hook) the device address of the new cells' running state (five planes of n doubles in storage order) and its draw count"
+function newrows_state(p::DevPairs)
+    st, draws = Ref{Ptr{Cvoid}}(C_NULL), Ref(0.0)
+    check(ccall((:bdf_newrows_state, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Float64}), p.h, st, draws))
+    return st[], draws[]
+end
+
 # ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device ------------------------------------------------------------------
 "AUC_ROC(Ytrue, scores) of device arrays (labels: UInt8, nonzero = positive): (auc, C, P, Nn), C the exact pair count"
 function auc_roc(c::Context, labels::DevArray{UInt8}, scores::DevArray{Float64})
