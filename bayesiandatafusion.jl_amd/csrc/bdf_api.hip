@@ -88,6 +88,8 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
     if (c->col_piece == 1) c->col_piece = 128;
     if (c->col_piece != 0) c->col_piece = std::min(4096, std::max(8, c->col_piece));
     c->col_explicit = false;
+    c->gather_image = 1;
+    c->gimg_trust = false;
     c->lr_T = nullptr; c->lr_vt = nullptr; c->lr_vt_bytes = 0; c->lr_mrows = nullptr; c->lr_mrows_bytes = 0;
     {
         const char *force = getenv("BDF_GATHER");
@@ -237,6 +239,17 @@ extern "C" int bdf_ctx_set_col_rows(bdf_ctx *ctx, int max_piece)
     }
     ctx->col_piece = max_piece;
     ctx->col_explicit = true;
+    return BDF_OK;
+}
+
+// K1c's gather image (k_gather_image.hip): 1 on (the default: the pair image), 0 off -- the parity tests compare the two; 2: the full
+// image, the tier that was measured against the pair image and lost
+extern "C" int bdf_ctx_set_gather_image(bdf_ctx *ctx, int on)
+{
+    BDF_REQUIRE(ctx && on >= 0 && on <= 2, BDF_ERR_ARG, "bdf_ctx_set_gather_image: 0 (off), 1 (on) or 2 (the full image)");
+    const int tier = on;                                                            // (the tiers of k_rows_col.hip, col_gather4)
+    if (tier != ctx->gather_image) bdf_gather_image_invalidate(ctx, nullptr);       // (the images held are the other kind's)
+    ctx->gather_image = tier;
     return BDF_OK;
 }
 

@@ -70,6 +70,10 @@ struct bdf_ctx {
     int col_piece;             // K1c (k_rows_col.hip): one two-mode relation at 16 < D <= 32 four rows per wave in the column layout, rows cut
                                // into pieces of at most this many observations; 0: off
     bool col_explicit;         // ... set by the caller (bdf_ctx_set_col_rows): taken also when the caller chose K1's item size
+    int gather_image;          // K1c at D = 32 gathers from the opposite entity's gather image (k_gather_image.hip): 1 the pair image (the
+                               // default), 2 the full image, 0 off -- the sample itself (bdf_ctx_set_gather_image)
+    bool gimg_trust;           // (library-internal) the next row launch may take the opposite sample's image as its own launch left it: the
+                               // caller knows of every write to that sample (bdf_gibbs_sweep); cleared by the launch
     double *lr_T;              // Tf | Tb | Tm (64 x 64 each) | L' mu (64): the launch's constants (k_lr_prep)
     double *lr_mrows;          // per-row prior means transformed (L' mu_i, rows of DP doubles), grown on demand
     size_t lr_mrows_bytes;

@@ -13,6 +13,7 @@
 // the row kernel's waves poll that word where they first need the prior (BDF_NO_POLL=1, a profiler that serialises the
 // streams, or several ranks: event waits instead).
 #include "bdf_common.h"
+#include "rows.h"
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -106,6 +107,15 @@ __global__ __launch_bounds__(64) void k_rows_gate(const uint32_t *done, uint32_t
         __builtin_amdgcn_s_sleep(8);
         if (++spins > (1 << 22)) { if (threadIdx.x == 0) atomicOr_system(flag, 16); break; }      // bounded: a bug must not hang the device
     }
+}
+
+// Something other than a row launch has written entity E's sample, or may have: K1c's gather images of its buffers are stale
+// (k_gather_image.hip) -- the next launch that gathers one packs it anew.  The row launches of bdf_gibbs_sweep vouch for the images of
+// the chain's buffers (bdf_ctx::gimg_trust), so EVERY other writer of a sample comes through here: the state at creation, a state
+// put back (bdf_gibbs_warm_device, bdf_gibbs_set_recorded), the host (bdf_gibbs_sample_written).
+void sample_written(bdf_gibbs *g, const bdf_gibbs::Ent &E)
+{
+    for (int b = 0; b < 3; b++) bdf_gather_image_invalidate(g->rows, E.d.sample[b]);
 }
 
 int streams_concurrent(hipStream_t a, hipStream_t b, bool *yes)
@@ -297,6 +307,7 @@ extern "C" int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const 
     for (int j = 0; j < n_entities; j++) {
         auto &E = g->ent[(size_t)j];
         E.d = ents[j]; E.cur = 0;
+        sample_written(g, E);                         // (the initial state; images an earlier chain left at these addresses)
         BDF_HIP(hipEventCreate(&E.ev_rows));          // (they ride on dispatch packets: plain events)
         BDF_HIP(hipEventCreate(&E.ev_hyper));
         if (E.d.feat) BDF_HIP(hipEventCreateWithFlags(&E.ev_beta, hipEventDisableTiming));
@@ -601,6 +612,7 @@ extern "C" int bdf_gibbs_set_comm(bdf_gibbs *g, bdf_comm *comm)
 {
     BDF_REQUIRE(g, BDF_ERR_ARG, "bdf_gibbs_set_comm: NULL argument");
     g->comm = comm;
+    bdf_gather_image_invalidate(g->rows, nullptr);    // (the exchange writes the samples: with a communicator no launch vouches for an image)
     return BDF_OK;
 }
 
@@ -630,8 +642,10 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
     const double *mu, *Lambda, *pack;
     if ((rc = row_prior(g, E, &mu, &Lambda, &pack))) return rc;
     const int nch = e.terms[0].rel->chunks;
-    for (int c = 0; c < nch; c++)
+    for (int c = 0; c < nch; c++) {
+        R->gimg_trust = !g->comm;             // (as in bdf_gibbs_sweep)
         if ((rc = bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, e.feat ? 1 : 0, Lambda, e.tag, c, nch, e.sample[nxt], pack))) return rc;
+    }
     E.cur = nxt;
     return BDF_OK;
 }
@@ -748,6 +762,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         off += (pc.bytes + 255) & ~(size_t)255;
     }
     for (int j = 0; j < n; j++) {
+        sample_written(g, g->ent[(size_t)j]);
         g->ent[(size_t)j].hyper_recorded = flags[(size_t)2 * j] != 0;
         g->ent[(size_t)j].beta_recorded = flags[(size_t)2 * j + 1] != 0;
     }
@@ -772,6 +787,15 @@ extern "C" int bdf_gibbs_set_recorded(bdf_gibbs *g, int entity, int hyper, int b
     BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_set_recorded: bad argument");
     g->ent[(size_t)entity].hyper_recorded = hyper != 0;
     g->ent[(size_t)entity].beta_recorded = beta != 0;
+    sample_written(g, g->ent[(size_t)entity]);        // (a caller that puts the chain's state back: the sample with it)
+    return BDF_OK;
+}
+
+// the caller has written entity's sample (any of its three buffers) itself, or is about to, with nothing of the chain in flight
+extern "C" int bdf_gibbs_sample_written(bdf_gibbs *g, int entity)
+{
+    BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_sample_written: bad argument");
+    sample_written(g, g->ent[(size_t)entity]);
     return BDF_OK;
 }
 
@@ -901,6 +925,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             R->time_stop = (c == nch - 1 && !g->comm && !counter) ? done : nullptr;
             if (poll) { R->rows_ready = g->ready_dev + j; R->rows_ready_want = E.epoch; }
             if (counter) R->rows_done = E.done_dev;
+            R->gimg_trust = !g->comm;         // (the chain's own buffers: sample_written() hears of every other writer)
             if ((rc = e.spike ? bdf_sample_rows_spike(R, D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
                               : bdf_sample_rows(R, D, e.N, e.n_terms, terms, mu_rows, e.feat ? 1 : 0, Lambda_rows, e.tag, c, nch, e.sample[nxt], pack_rows)))
                 return rc;

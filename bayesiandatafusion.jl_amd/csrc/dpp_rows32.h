@@ -85,6 +85,17 @@ __device__ __forceinline__ void col_rank1u(double (&A0)[33], double (&A1)[33], d
         col_star<24, 8, DR - 24>(A1, v1, y);
     }
 }
+// the same with the two own-vectors given: K1c's gather image holds x and y beside v0 and v1 (k_gather_image.hip), made once by whoever
+// wrote the row instead of once per observation -- the same fmas with the same operands, no select in the loop
+__device__ __forceinline__ void col_rank1u(double (&A0)[33], double (&A1)[33], double v0, double v1, double x, double y)
+{
+    fm1<0>(A0[0], v0, v0);
+    col_star<1, 1, 7>(A0, v0, v0);
+    col_star<0, 0, 8>(A1, v0, v1);
+    col_star<16, 0, 8>(A1, v1, v1);
+    col_star<8, 8, 8>(A0, v0, x);
+    col_star<24, 8, 8>(A1, v1, y);
+}
 // rows I .. DR-1 and the extra row 32 of step k = 16 S + K: A_s[I] -= A[I][k] * A[k][c_s] / d_k
 template <int DR, int S, int K, int I, bool FIRST>
 __device__ __forceinline__ void fin_elim(double (&A0)[33], double (&A1)[33], double nm0, double nm1)

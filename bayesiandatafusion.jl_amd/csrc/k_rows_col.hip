@@ -70,6 +70,15 @@ __device__ __forceinline__ void col_obs(double (&A0)[33], double (&A1)[33], doub
     fm1_run<K>(A1[32], r, v1);
 }
 
+// ... from the gather image (IMG 2): the own-vectors come with the row
+template <int K>
+__device__ __forceinline__ void col_obs_img(double (&A0)[33], double (&A1)[33], double v0, double v1, double x, double y, double r)
+{
+    col_rank1u(A0, A1, v0, v1, x, y);
+    fm1_run<K>(A0[32], r, v0);
+    fm1_run<K>(A1[32], r, v1);
+}
+
 __device__ __forceinline__ double col_ld(__amdgpu_buffer_rsrc_t rs, uint32_t off)
 {
     typedef unsigned u2v __attribute__((ext_vector_type(2)));
@@ -77,9 +86,32 @@ __device__ __forceinline__ double col_ld(__amdgpu_buffer_rsrc_t rs, uint32_t off
     return __hiloint2double((int)x.y, (int)x.x);
 }
 
+__device__ __forceinline__ void col_ld2(__amdgpu_buffer_rsrc_t rs, uint32_t off, double &p, double &q)
+{
+    typedef unsigned u4v __attribute__((ext_vector_type(4)));
+    const u4v x = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
+    p = __hiloint2double((int)x.y, (int)x.x);
+    q = __hiloint2double((int)x.w, (int)x.z);
+}
+
+// IMG: where an observation's factor row is gathered from.  0: the entity's sample as it is (rows of D doubles: two 8-byte loads per
+// lane).  1, 2: the GATHER IMAGE, a lane-ordered copy of the sample that the launch which sampled it left beside it (the producer
+// stores at the end of a round; k_gather_image.hip packs one from a sample written by anything else), D = 32 only.  Lane j of a lane
+// row owns COL_IMG_LANE doubles of the row's image:
+//   1 (the pair image, 256 bytes per row)   [v0_j, v1_j]:             one 16-byte load, the selects of col_rank1u stay: 48 vector
+//                                                                     instructions per observation step where the sample takes 49.  THE DEFAULT.
+//   2 (the full image, 512 bytes per row)   [v0_j, v1_j, x_j, y_j]:   two 16-byte loads, no select and no VCC move: 45 -- and SLOWER than
+//                                                                     the sample's 49, the gathered bytes doubled: kept as the
+//                                                                     measured alternative, bdf_ctx_set_gather_image(ctx, 2)
+// with v0_j = element 31 - j, v1_j = element 15 - j and x, y col_rank1u's own-vectors (dpp_rows32.h).
+#define COL_IMG_LANE(IMG) ((IMG) == 2 ? 4 : 2)          // doubles per gathered observation and lane
+// an id whose row offset lies beyond every image this kernel takes (bdf_col_launch: at most COL_IMG_PAD_ID rows) and does not wrap
+// with the lane's offset added, at 256 or 512 bytes per row: padding reads return zero without touching memory
+#define COL_IMG_PAD_ID 0x7ffff8u
+
 // the gathers of observations K0 .. K0 + 3 of the chunk (ids in idw, one per lane of the lane row)
-template <bool FULL, int K0>
-__device__ __forceinline__ void col_gather4(double (&b)[4][2], __amdgpu_buffer_rsrc_t rs, uint32_t idw, uint32_t rowb, uint32_t eo, bool ok1)
+template <int IMG, bool FULL, int K0>
+__device__ __forceinline__ void col_gather4(double (&b)[4][COL_IMG_LANE(IMG)], __amdgpu_buffer_rsrc_t rs, uint32_t idw, uint32_t rowb, uint32_t eo, bool ok1)
 {
 #pragma unroll
     for (int q = 0; q < 4; q++) {
@@ -88,7 +120,14 @@ __device__ __forceinline__ void col_gather4(double (&b)[4][2], __amdgpu_buffer_r
         else if (q == 2) id = row_bcast_u32<K0 + 2>(idw); else id = row_bcast_u32<K0 + 3>(idw);
         // (idw holds the observations' ROW OFFSETS, id x row bytes, made once per chunk of sixteen: the broadcast and the addition of the
         // lane's element offset are then ONE v_add_u32_dpp per observation where broadcast, multiply and add were three instructions)
-        if constexpr (FULL) {
+        if constexpr (IMG == 2) {
+            // eo: the lane's 32 bytes of a row's image
+            const uint32_t base = id + eo;
+            col_ld2(rs, base, b[q][0], b[q][1]);
+            col_ld2(rs, base + 16u, b[q][2], b[q][3]);
+        } else if constexpr (IMG == 1) {
+            col_ld2(rs, id + eo, b[q][0], b[q][1]);
+        } else if constexpr (FULL) {
             // eo: byte offset of element D-17-j; element D-1-j sits 128 bytes further
             const uint32_t base = id + eo;
             b[q][1] = col_ld(rs, base);
@@ -101,9 +140,16 @@ __device__ __forceinline__ void col_gather4(double (&b)[4][2], __amdgpu_buffer_r
         }
     }
 }
-template <int DR, int K0>
-__device__ __forceinline__ void col_compute4(double (&A0)[33], double (&A1)[33], const double (&b)[4][2], double r, bool h, uint64_t hmask)
+template <int DR, int IMG, int K0>
+__device__ __forceinline__ void col_compute4(double (&A0)[33], double (&A1)[33], const double (&b)[4][COL_IMG_LANE(IMG)], double r, bool h, uint64_t hmask)
 {
+    if constexpr (IMG == 2) {
+        col_obs_img<K0>(A0, A1, b[0][0], b[0][1], b[0][2], b[0][3], r);
+        col_obs_img<K0 + 1>(A0, A1, b[1][0], b[1][1], b[1][2], b[1][3], r);
+        col_obs_img<K0 + 2>(A0, A1, b[2][0], b[2][1], b[2][2], b[2][3], r);
+        col_obs_img<K0 + 3>(A0, A1, b[3][0], b[3][1], b[3][2], b[3][3], r);
+        return;
+    }
     col_obs<DR, K0>(A0, A1, b[0][0], b[0][1], r, h, hmask);
     col_obs<DR, K0 + 1>(A0, A1, b[1][0], b[1][1], r, h, hmask);
     col_obs<DR, K0 + 2>(A0, A1, b[2][0], b[2][1], r, h, hmask);
@@ -165,9 +211,10 @@ __device__ __forceinline__ void col_prior_lds(double (&A)[33], const double *img
     }
 }
 
-template <int DR, bool FULL>
-__global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(COL_VGPR_HALF))) void k_rows_col(SampleArgs a_in, ColPlanDev p_in, uint32_t fac_bytes)
+template <int DR, bool FULL, int IMG>
+__device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColPlanDev &p_in, uint32_t fac_bytes)
 {
+    static_assert(IMG == 0 || (FULL && DR == 32), "the gather image is D = 32's");
     __shared__ __attribute__((aligned(16))) double lds[4 * COL_TL + 768];      // the re-layout of the four systems | the prior's image
     const int w = blockIdx.x;
     if (w >= p_in.n_waves) return;
@@ -192,9 +239,10 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
     const int ec0 = D - 1 - j, ec1 = D - 17 - j;          // natural index of the reversed elements j, 16 + j (ec1 < 0: padding)
     const int n0 = ec0, n1 = ec1 >= 0 ? ec1 : 0;
     const bool ok1 = ec1 >= 0;
-    const uint32_t rowb = (uint32_t)D * 8u;
-    const uint32_t eo = FULL ? (uint32_t)ec1 * 8u : (uint32_t)ec0 * 8u;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)T.fac[0], 0, (int)fac_bytes, 0x00020000);
+    // (rowb, eo: a gathered row's bytes and the lane's offset in it -- of the sample, or of its image)
+    const uint32_t rowb = IMG ? (uint32_t)COL_IMG_LANE(IMG) * 128u : (uint32_t)D * 8u;
+    const uint32_t eo = IMG ? (uint32_t)j * (uint32_t)COL_IMG_LANE(IMG) * 8u : (FULL ? (uint32_t)ec1 * 8u : (uint32_t)ec0 * 8u);
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(IMG ? a.img_in : T.fac[0]), 0, (int)fac_bytes, 0x00020000);
     const bool coded = T.packed != nullptr;                // (wave-uniform)
     const double mean = T.mean;
     {
@@ -225,7 +273,7 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
 #define COL_CHUNK(c0, IDW, R)                                                                     \
             {                                                                                     \
                 const int o_ = (c0) + j;                                                          \
-                IDW = 0xffffffu; R = 0.0;                                                         \
+                IDW = IMG ? COL_IMG_PAD_ID : 0xffffffu; R = 0.0;                                                         \
                 if (o_ < n) {                                                                     \
                     if (coded) { const uint32_t pw_ = packed[o_]; IDW = pw_; R = table[pw_ >> 24] - mean; } \
                     else { IDW = (uint32_t)colidx[o_]; R = vals[o_] - mean; }                     \
@@ -235,25 +283,25 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
             uint32_t idw_c, idw_n;
             double r_c, r_n;
             COL_CHUNK(0, idw_c, r_c)
-            double ba[4][2], bb[4][2];
-            col_gather4<FULL, 0>(ba, rs, idw_c, rowb, eo, ok1);
+            double ba[4][COL_IMG_LANE(IMG)], bb[4][COL_IMG_LANE(IMG)];
+            col_gather4<IMG, FULL, 0>(ba, rs, idw_c, rowb, eo, ok1);
             for (int c0 = 0;; c0 += 16) {
                 COL_CHUNK(c0 + 16, idw_n, r_n)
-                col_gather4<FULL, 4>(bb, rs, idw_c, rowb, eo, ok1);
+                col_gather4<IMG, FULL, 4>(bb, rs, idw_c, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 0>(A0, A1, ba, r_c, hh, hmask);
+                col_compute4<DR, IMG, 0>(A0, A1, ba, r_c, hh, hmask);
                 if (c0 + 4 >= nmax) break;
-                col_gather4<FULL, 8>(ba, rs, idw_c, rowb, eo, ok1);
+                col_gather4<IMG, FULL, 8>(ba, rs, idw_c, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 4>(A0, A1, bb, r_c, hh, hmask);
+                col_compute4<DR, IMG, 4>(A0, A1, bb, r_c, hh, hmask);
                 if (c0 + 8 >= nmax) break;
-                col_gather4<FULL, 12>(bb, rs, idw_c, rowb, eo, ok1);
+                col_gather4<IMG, FULL, 12>(bb, rs, idw_c, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 8>(A0, A1, ba, r_c, hh, hmask);
+                col_compute4<DR, IMG, 8>(A0, A1, ba, r_c, hh, hmask);
                 if (c0 + 12 >= nmax) break;
-                col_gather4<FULL, 0>(ba, rs, idw_n, rowb, eo, ok1);
+                col_gather4<IMG, FULL, 0>(ba, rs, idw_n, rowb, eo, ok1);
                 __builtin_amdgcn_sched_barrier(0);
-                col_compute4<DR, 12>(A0, A1, bb, r_c, hh, hmask);
+                col_compute4<DR, IMG, 12>(A0, A1, bb, r_c, hh, hmask);
                 if (c0 + 16 >= nmax) break;
                 idw_c = idw_n; r_c = r_n;
             }
@@ -419,6 +467,20 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
         // (write-through: with a.done the hyperprior's sums read the rows while this launch is still running, from CUs behind other L2s)
         if (lead) __hip_atomic_store(a.out + ((int64_t)jb.row * D + ec0), y0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (lead && ok1) __hip_atomic_store(a.out + ((int64_t)jb.row * D + ec1), y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        // ... and the row's gather image, for the launches that gather it: the lane holds elements 31 - j and 15 - j, which are its v0
+        // and v1; x is one of the two, y wants the v0 of the lane eight to the right.  Write-through like the row itself.
+        if constexpr (IMG != 0) {
+            const double yo = __shfl_xor(y0, 8);
+            if (lead && a.img_out) {
+                double *ip = a.img_out + ((int64_t)jb.row * 16 + j) * COL_IMG_LANE(IMG);
+                __hip_atomic_store(ip, y0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(ip + 1, y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if constexpr (IMG == 2) {
+                    __hip_atomic_store(ip + 2, hh ? y0 : y1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(ip + 3, hh ? y1 : yo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
         CSTAMP(st_fin);
     }
     }
@@ -441,8 +503,21 @@ __global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(C
 #endif
 }
 
+template <int DR, bool FULL>
+__global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(COL_VGPR_HALF))) void k_rows_col(SampleArgs a_in, ColPlanDev p_in, uint32_t fac_bytes)
+{
+    rows_col_body<DR, FULL, 0>(a_in, p_in, fac_bytes);
+}
+// D = 32 gathering from the other entity's image (fac_bytes: the image's) and leaving its own rows' (SampleArgs::img_in, img_out)
+template <int IMG>
+__global__ __launch_bounds__(64, BDF_COL_WAVES) __attribute__((amdgpu_num_vgpr(COL_VGPR_HALF))) void k_rows_col_img(SampleArgs a_in, ColPlanDev p_in, uint32_t fac_bytes)
+{
+    rows_col_body<32, true, IMG>(a_in, p_in, fac_bytes);
+}
+
 // ---- host: rows -> units (a row, or its 2 / 4 pieces, or the parts of a row that spans waves) -> rounds -> waves ------------
-#define COL_C_OBS 52.0             // cost model (vector instructions): per observation of a round's longest piece (49 in the loop and the chunk's share),
+#define COL_C_OBS 51.0             // cost model (vector instructions): per observation of a round's longest piece (48 in the loop from the pair image and the
+                                   // chunk's share; 49 from the sample itself: it ranks the rounds only),
 #define COL_C_FIN 1460.0           // the finish of a round (normals, prior, factorisation, solves),
 #define COL_C_FOLD 180.0           // the butterfly sums of a round with pieces,
 #define COL_C_PART 700.0           // a part's store to the slab
@@ -601,17 +676,28 @@ void bdf_col_plan_free(bdf_col_plan &plan)
     plan = bdf_col_plan{};
 }
 
-int bdf_col_launch(bdf_ctx *ctx, const SampleArgs &a, const bdf_col_plan &plan, int64_t M_other, hipEvent_t e0, hipEvent_t e1)
+int64_t bdf_col_image_max_rows() { return (int64_t)COL_IMG_PAD_ID; }
+
+int bdf_col_launch(bdf_ctx *ctx, const SampleArgs &a, const bdf_col_plan &plan, int64_t M_other, int img_tier, hipEvent_t e0, hipEvent_t e1)
 {
     if (plan.n_waves <= 0) return BDF_OK;
     ColPlanDev p;
     p.jobs = plan.jobs_dev; p.wave_round = plan.wave_round_dev; p.n_waves = plan.n_waves; p._pad = 0;
     p.rows = plan.rows_dev; p.partials = plan.partials_dev; p.arrived = plan.arrived_dev;
-    const int64_t bytes = M_other * (int64_t)a.D * 8;
+    // (img_tier: the kind of a.img_in -- rows_plan.hip's launch_column -- which the buffer then covers exactly)
+    BDF_REQUIRE(!a.img_in || ((img_tier == 1 || img_tier == 2) && a.D == 32 && M_other <= bdf_col_image_max_rows()), BDF_ERR_ARG,
+                "bdf_sample_rows: a gather image of %lld rows at D = %d", (long long)M_other, a.D);
+    const int64_t bytes = a.img_in ? M_other * bdf_gather_image_row_doubles(img_tier) * 8 : M_other * (int64_t)a.D * 8;
     BDF_REQUIRE(bytes < ((int64_t)1 << 32), BDF_ERR_ARG, "bdf_sample_rows: the column kernel needs a factor matrix below 4 GiB");
     const uint32_t fb = (uint32_t)bytes;
     const dim3 grid((unsigned)plan.n_waves), block(64);
     const int DR = (a.D + 3) / 4 * 4;
+    if (a.img_in) {
+        if (img_tier == 2) hipExtLaunchKernelGGL((k_rows_col_img<2>), grid, block, 0, ctx->stream, e0, e1, 0, a, p, fb);
+        else hipExtLaunchKernelGGL((k_rows_col_img<1>), grid, block, 0, ctx->stream, e0, e1, 0, a, p, fb);
+        BDF_HIP(hipGetLastError());
+        return BDF_OK;
+    }
 #define COL_LAUNCH(DRV, FULLV) hipExtLaunchKernelGGL((k_rows_col<DRV, FULLV>), grid, block, 0, ctx->stream, e0, e1, 0, a, p, fb)
     if (a.D == 32) COL_LAUNCH(32, true);
     else if (DR <= 20) COL_LAUNCH(20, false);

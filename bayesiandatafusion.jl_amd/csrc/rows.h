@@ -60,6 +60,11 @@ struct SampleArgs {
     // which the coordinate sweep of every row starts
     const double *spike_state;
     const double *u_current;
+    // K1c at D = 32 only, both nullable (rows_plan.hip's launch_column fills them in): the gather image of the OTHER entity's sample,
+    // which the observations are then gathered from in place of t[0].fac[0], and where the launch leaves the image of the rows it
+    // writes (k_rows_col.hip, col_gather4; k_gather_image.hip)
+    const double *img_in;
+    double *img_out;
 };
 
 // the padded dimension the row kernels are compiled for
@@ -162,4 +167,14 @@ struct bdf_col_plan {
 };
 int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T, int64_t slots, bdf_col_plan &plan);
 void bdf_col_plan_free(bdf_col_plan &plan);
-int bdf_col_launch(bdf_ctx *ctx, const SampleArgs &a, const bdf_col_plan &plan, int64_t M_other, hipEvent_t e0, hipEvent_t e1);
+// img_tier: the kind of a.img_in (ignored without one)
+int bdf_col_launch(bdf_ctx *ctx, const SampleArgs &a, const bdf_col_plan &plan, int64_t M_other, int img_tier, hipEvent_t e0, hipEvent_t e1);
+
+// ---- K1c's gather image (k_gather_image.hip; the registry of a context's images: rows_plan.hip) -----------------------
+// tier 1: the pair image, 32 doubles per row; tier 2: the full image, 64 (k_rows_col.hip, col_gather4)
+inline int64_t bdf_gather_image_row_doubles(int tier) { return tier == 2 ? 64 : 32; }
+int64_t bdf_col_image_max_rows();                                  // the most rows K1c gathers from an image
+// image = the image of the M rows of 32 doubles at `sample`, on the context's stream
+int bdf_gather_image_pack_launch(bdf_ctx *ctx, const double *sample, int64_t M, int tier, double *image);
+// something other than a K1c launch with an image has written the sample at `sample` (NULL: any sample): its image is stale
+void bdf_gather_image_invalidate(bdf_ctx *ctx, const double *sample);

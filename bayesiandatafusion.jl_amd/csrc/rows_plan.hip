@@ -58,6 +58,13 @@ struct LrKey {
 
 std::mutex g_plans_mutex;             // around every context's plan cache
 
+// K1c's gather image of the sample at one address (k_gather_image.hip).  `valid`: the image is that of the sample as the library last
+// saw it written -- left by the K1c launch that sampled it, or packed from it since; every row launch clears it for its `out`, and
+// so does whoever else writes a sample (bdf_gather_image_invalidate).  A launch believes it only when its caller vouches that nothing
+// outside the library writes the sample either (bdf_ctx::gimg_trust: bdf_gibbs_sweep, whose buffers are its own); every other launch
+// packs the image anew.
+struct GatherImage { double *dev = nullptr; int64_t rows = 0; int tier = 0; bool valid = false; };
+
 }  // namespace
 
 // the row launcher's state of one context (bdf_ctx::rows)
@@ -65,6 +72,8 @@ struct bdf_rows_state {
     std::map<PlanKey, Plan> plans;
     std::map<uint32_t, std::array<int64_t, 7>> dispatch;      // bdf_ctx_rows_dispatch: per entity tag, see bdf_rows_dispatch_counts
     LrKey lr_key{nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    std::map<const double *, GatherImage> images;             // by the sample's address: an image follows its sample through the rotation
+    int64_t image_stats[3] = {0, 0, 0};                       // bdf_ctx_gather_image_stats
 };
 
 namespace {
@@ -321,15 +330,65 @@ int launch_lowrank(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t 
     return rc;
 }
 
-int launch_column(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t M_other, bool more, hipEvent_t e0, hipEvent_t e1)
+void images_free(bdf_rows_state *st)
+{
+    for (auto &kv : st->images) (void)hipFree(kv.second.dev);        // (hipFree waits for the launches that still read them)
+    st->images.clear();
+}
+
+// the context's image of the `rows` rows at `sample` (allocated at first use; its content is the caller's business)
+int image_of(bdf_ctx *ctx, const double *sample, int64_t rows, int tier, GatherImage **out)
+{
+    auto &m = ctx->rows->images;
+    auto it = m.find(sample);
+    if (it != m.end() && (it->second.rows != rows || it->second.tier != tier)) { (void)hipFree(it->second.dev); m.erase(it); it = m.end(); }
+    if (it == m.end()) {
+        GatherImage g;
+        g.rows = rows; g.tier = tier;
+        BDF_HIP(hipMalloc((void **)&g.dev, (size_t)std::max<int64_t>(rows, 1) * (size_t)bdf_gather_image_row_doubles(tier) * sizeof(double)));
+        it = m.emplace(sample, g).first;
+    }
+    *out = &it->second;
+    return BDF_OK;
+}
+
+// n_rows: the rows of the launch's entity; whole: the launch is the call's only one and the call the entity's only one
+int launch_column(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t M_other, int64_t n_rows, bool more, bool whole, bool trust,
+                  hipEvent_t e0, hipEvent_t e1)
 {
     static const bool no_coded = getenv("BDF_K1_NO_CODED") != nullptr;               // test hook: ids and values instead of the packed words
     SampleArgs ac = a;
     if (no_coded) ac.t[0].packed = nullptr;
+    // The gather image (k_rows_col.hip, col_gather4): D = 32, the whole entity in one call (no chunks, no layout: `whole`), an
+    // opposite entity the image's offsets reach.  The opposite sample's image is the one its own launch left if the caller vouches for
+    // it, else packed here; this launch leaves its rows' image when it writes ALL of the entity's rows -- K1-lr or K1s taking some of
+    // them leaves none, and the next launch that gathers them packs one.
+    const int tier = ctx->gather_image;
+    if (tier != 0 && a.D == 32 && whole && M_other > 0 && M_other <= bdf_col_image_max_rows()) {
+        int rc;
+        bdf_rows_state *st = ctx->rows;
+        if (st->images.size() >= 48) images_free(st);       // (addresses no longer in use: callers that pass fresh buffers every call)
+        GatherImage *src;
+        if ((rc = image_of(ctx, a.t[0].fac[0], M_other, tier, &src))) return rc;
+        if (!(trust && src->valid)) {
+            if ((rc = bdf_gather_image_pack_launch(ctx, a.t[0].fac[0], M_other, tier, src->dev))) return rc;
+            src->valid = true;
+            st->image_stats[1]++;
+        }
+        ac.img_in = src->dev;
+        st->image_stats[0]++;
+        if (!more && plan.n_lr == 0 && plan.n_small == 0 && plan.rows_col == n_rows && n_rows <= bdf_col_image_max_rows()) {
+            GatherImage *dst;
+            if ((rc = image_of(ctx, a.out, n_rows, tier, &dst))) return rc;
+            ac.img_out = dst->dev;
+            dst->valid = true;
+            st->image_stats[2]++;
+        }
+    }
     // the rows' hand-over by counter (SampleArgs::done): only when this launch is ALL of the call's rows
     if (more || plan.n_lr > 0 || plan.n_small > 0) ac.done = nullptr;
     if (ac.done) ctx->rows_done_added = plan.col.n_waves;
-    return bdf_col_launch(ctx, ac, plan.col, M_other, e0, e1);
+    return bdf_col_launch(ctx, ac, plan.col, M_other, tier, e0, e1);
 }
 
 }  // namespace
@@ -340,6 +399,7 @@ void bdf_rows_state_destroy(bdf_ctx *ctx)
 {
     if (!ctx->rows) return;
     bdf_plans_release(ctx, 0);
+    images_free(ctx->rows);
     delete ctx->rows;
     ctx->rows = nullptr;
 }
@@ -348,6 +408,41 @@ const std::array<int64_t, 7> *bdf_rows_dispatch_counts(const bdf_ctx *ctx, uint3
 {
     auto it = ctx->rows->dispatch.find(entity_tag);
     return it == ctx->rows->dispatch.end() ? nullptr : &it->second;
+}
+
+void bdf_gather_image_invalidate(bdf_ctx *ctx, const double *sample)
+{
+    for (auto &kv : ctx->rows->images)
+        if (!sample || kv.first == sample) kv.second.valid = false;
+}
+
+// {launches that gathered from an image, images packed from a sample, launches that left the image of their entity's rows} on this
+// context so far
+extern "C" int bdf_ctx_gather_image_stats(const bdf_ctx *ctx, int64_t out[3])
+{
+    BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "bdf_ctx_gather_image_stats: NULL argument");
+    for (int k = 0; k < 3; k++) out[k] = ctx->rows->image_stats[k];
+    return BDF_OK;
+}
+
+// parity hook: the image the library holds of the `rows` rows at `sample` (a device address), as a launch left or packed it, into
+// host memory (bdf_gather_image_row_doubles per row); an error when it holds none or a stale one
+extern "C" int bdf_ctx_gather_image_read(bdf_ctx *ctx, const double *sample, int64_t rows, double *host_out)
+{
+    BDF_REQUIRE(ctx && sample && host_out, BDF_ERR_ARG, "bdf_ctx_gather_image_read: NULL argument");
+    auto it = ctx->rows->images.find(sample);
+    BDF_REQUIRE(it != ctx->rows->images.end() && it->second.valid && it->second.rows == rows, BDF_ERR_ARG,
+                "bdf_ctx_gather_image_read: no current gather image of %lld rows at this address", (long long)rows);
+    BDF_HIP(hipStreamSynchronize(ctx->stream));
+    BDF_HIP(hipMemcpy(host_out, it->second.dev, (size_t)rows * (size_t)bdf_gather_image_row_doubles(it->second.tier) * sizeof(double), hipMemcpyDeviceToHost));
+    return BDF_OK;
+}
+
+// parity hook: the pack kernel on its own -- image_dev = the image (the context's tier) of the `rows` rows of 32 doubles at sample
+extern "C" int bdf_gather_image_pack(bdf_ctx *ctx, const double *sample, int64_t rows, double *image_dev)
+{
+    BDF_REQUIRE(ctx && ctx->gather_image != 0, BDF_ERR_ARG, "bdf_gather_image_pack: the gather image is off on this context");
+    return bdf_gather_image_pack_launch(ctx, sample, rows, ctx->gather_image, image_dev);
 }
 
 // parity hook: split rows whose pieces did not all arrive in the launches so far (their arrival counters reset themselves
@@ -398,6 +493,10 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
 {
     SampleArgs a = a_in;
     int rc;
+    // (whatever this call's launches are, they write a.out: its image, if it has one, is stale until a K1c launch leaves a new one)
+    const bool image_trust = ctx->gimg_trust;
+    ctx->gimg_trust = false;
+    bdf_gather_image_invalidate(ctx, a.out);
     const bool spike = a.spike_state != nullptr;      // bdf_sample_rows_spike: every row to K1-style items, finished by k_rows_ss
     if (spike) {
         // the prior of the accumulation is Lambda = diag(tau), mu = 0: the matrix and the zeros by one small launch, then the
@@ -451,7 +550,7 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
         const hipEvent_t e0 = dump ? nullptr : ctx->time_start, e1 = (dump || more) ? nullptr : ctx->time_stop;
         if (s == 0) rc = launch_lowrank(ctx, a, *plan, M_other, rels[0]->nint[modes[0]], shard, e0, e1);
         else if (s == 1) rc = bdf_small_launch(ctx, a, plan->small_dev, plan->n_small, e0, e1);
-        else if (s == 2) rc = launch_column(ctx, a, *plan, M_other, more, e0, e1);
+        else if (s == 2) rc = launch_column(ctx, a, *plan, M_other, rels[0]->nint[modes[0]], more, n_shards == 1 && !rels[0]->sharded, image_trust, e0, e1);
         else rc = spike ? bdf_ss_launch(ctx, a, plan->dev, e0, e1) : bdf_k1_launch(ctx, a, plan->dev, dump, e0, e1);
         if (rc) return rc;
         if (!dump) { ctx->time_start = nullptr; if (!more) ctx->time_stop = nullptr; }

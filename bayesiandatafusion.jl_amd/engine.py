@@ -176,6 +176,31 @@ class Context:
             return None
         return dict(zip(("lowrank", "small", "col", "k1", "k1_items", "col_waves"), (int(x) for x in out)))
 
+    def set_gather_image(self, on=1):
+        """K1c at D = 32 gathers from the opposite sample's gather image (bdf_ctx_set_gather_image): 1 on (the default: the pair image),
+        0 off -- the values are the same either way; 2: the full image, the tier that was measured against it and lost"""
+        check(lib().bdf_ctx_set_gather_image(self.handle, int(on)))
+
+    def gather_image_stats(self):
+        """K1c launches of this context that gathered from an image, images packed from a sample, launches that left their entity's
+        image (bdf_ctx_gather_image_stats)"""
+        out = (C.c_int64 * 3)()
+        check(lib().bdf_ctx_gather_image_stats(self.handle, out))
+        return dict(zip(("launches", "packs", "left"), (int(x) for x in out)))
+
+    def gather_image_read(self, sample, tier_doubles=32):
+        """parity hook: the image the context holds of the device tensor `sample` (rows x 32), as a numpy array rows x 16 x
+        (tier_doubles / 16) (bdf_ctx_gather_image_read)"""
+        out = np.empty((sample.shape[0], 16, tier_doubles // 16), dtype=np.float64)
+        check(lib().bdf_ctx_gather_image_read(self.handle, _ptr(sample), int(sample.shape[0]), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def gather_image_pack(self, sample, tier_doubles=32):
+        """parity hook: the pack kernel's image of the device tensor `sample` (rows x 32), as a device tensor (bdf_gather_image_pack)"""
+        img = self.zeros(sample.shape[0], 16, tier_doubles // 16)
+        check(lib().bdf_gather_image_pack(self.handle, _ptr(sample), int(sample.shape[0]), _ptr(img)))
+        return img
+
     def set_piece_size(self, observations):
         check(lib().bdf_ctx_set_piece_size(self.handle, int(observations)))
 
@@ -1340,6 +1365,13 @@ class GibbsEngine:
         for r in en.relations:
             f += r.data.nnz() * (D * (D + 1) + 2 * D + D * max(len(r.entities) - 2, 0))
         return f
+
+    def sample_written(self, j):
+        """(native iteration) the caller has written entity j's sample itself, after sync(): K1c's gather image of it is stale and
+        the next launch that gathers it packs a new one (bdf_gibbs_sample_written).  Without this call the rows of the opposite
+        entity would still be sampled from the sample as it was."""
+        if self.gibbs:
+            check(lib().bdf_gibbs_sample_written(self.gibbs, int(j)))
 
     def rows_dispatch(self, j):
         """how the library dispatched entity j's latest row launch (Context.rows_dispatch); None before the first iteration"""

@@ -149,6 +149,21 @@ int bdf_ctx_set_lowrank(bdf_ctx *ctx, int max_observations, int64_t min_rows);
  * launches whose item size the caller has not set (bdf_ctx_set_item_size keeps the wave-per-row kernel); a call here with
  * 8..4096 applies to every launch of the context, 0 turns it off, -1 restores the default. */
 int bdf_ctx_set_col_rows(bdf_ctx *ctx, int max_piece);
+/* K1c at D = 32 gathers an observation's factor row from a GATHER IMAGE of the opposite entity's sample: a second copy in the order
+ * the kernel's lanes read it -- a lane's two elements side by side, one 16-byte load where the sample takes two of 8
+ * (k_gather_image.hip) -- which the K1c launch that sampled those rows left, or which is packed from the sample before the launch.
+ * The same fused multiply-adds on the same operands: the values do not change.  on = 1 (the default) or 0: the switch the parity
+ * tests compare; 2: the full image, with the two derived vectors of the rank-1 update beside the elements (no select in the loop,
+ * twice the bytes: measured slower than the sample itself, kept as the measured alternative). */
+int bdf_ctx_set_gather_image(bdf_ctx *ctx, int on);
+/* report: out[0] K1c launches of this context that gathered from an image so far, out[1] images packed from a sample (none was
+ * there, or it was stale, or the caller was not bdf_gibbs_sweep), out[2] launches that left the image of all their entity's rows */
+int bdf_ctx_gather_image_stats(const bdf_ctx *ctx, int64_t out[3]);
+/* parity hooks: the image the context holds of the `rows` rows at the device address `sample`, into host memory (32 doubles per
+ * row, 64 for the full image; an error when it holds none that is current) | the pack kernel alone: image_dev = the image of the
+ * `rows` rows of 32 doubles at `sample` */
+int bdf_ctx_gather_image_read(bdf_ctx *ctx, const double *sample, int64_t rows, double *host_out);
+int bdf_gather_image_pack(bdf_ctx *ctx, const double *sample, int64_t rows, double *image_dev);
 /* report: how the most recent bdf_sample_rows launch of the entity with this entity_tag (all its chunks / shards since the tag's
  * previous iteration number) was dispatched on this context -- out[0] rows drawn by the low-rank sampler (k_rows_lr.hip, a
  * different map from the normals than sample_user_basic's, src/sampling.jl:200-212), out[1] rows by k_rows_small (D <= 16),
@@ -980,6 +995,10 @@ int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds);
  * warm-up: full iterations, then every buffer put back -- puts these two flags back as well. */
 int bdf_gibbs_recorded(const bdf_gibbs *g, int entity, int *hyper, int *beta);
 int bdf_gibbs_set_recorded(bdf_gibbs *g, int entity, int hyper, int beta);
+/* the caller has written the entity's sample itself (any of its three buffers), with nothing of the chain in flight: K1c's gather
+ * images of it are stale, the next launch that gathers one packs it anew (bdf_ctx_set_gather_image).  bdf_gibbs_set_recorded
+ * says the same.  A sample written without either is gathered as it was before. */
+int bdf_gibbs_sample_written(bdf_gibbs *g, int entity);
 /* measurement: (start, stop) events ride on the dispatch of entity's next row kernel (bdf_ctx_time_next_rows) */
 int bdf_gibbs_time_rows(bdf_gibbs *g, int entity, void *start, void *stop);
 int bdf_gibbs_span_rows(bdf_gibbs *g, int entity, void *slot_dev);      /* bdf_ctx_span_next_rows for the next row launch of `entity` */

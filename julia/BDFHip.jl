@@ -62,7 +62,22 @@ function rows_dispatch(c::Context, entity_tag::Integer)
     check(ccall((:bdf_ctx_rows_dispatch, lib), Cint, (Ptr{Cvoid}, UInt32, Ptr{Int64}), c.h, UInt32(entity_tag), out))
     return out
 end
-set_piece_size!(c::Context, piece) = check(ccall((:bdf_ctx_set_piece_size, lib), Cint, (Ptr{Cvoid}, Cint), c.h, piece))
+# K1c at D = 32 gathers from a lane-ordered image of the opposite sample (k_gather_image.hip): 1 on (the default), 0 off -- the same
+# values either way; 2: the full image (measured slower)
+set_gather_image!(c::Context, on=1) = check(ccall((:bdf_ctx_set_gather_image, lib), Cint, (Ptr{Cvoid}, Cint), c.h, on))
+# K1c launches that gathered from an image, images packed from a sample, launches that left their entity's image
+function gather_image_stats(c::Context)
+    out = zeros(Int64, 3)
+    check(ccall((:bdf_ctx_gather_image_stats, lib), Cint, (Ptr{Cvoid}, Ptr{Int64}), c.h, out))
+    return out
+end
+# parity hooks: the image the context holds of the `rows` rows at the device address `sample` into the host array `out`; the pack
+# kernel alone, into device memory
+gather_image_read!(c::Context, sample::Ptr{Cvoid}, rows::Integer, out::Array{Float64}) =
+    check(ccall((:bdf_ctx_gather_image_read, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Float64}), c.h, sample, rows, out))
+gather_image_pack!(c::Context, sample::Ptr{Cvoid}, rows::Integer, image::Ptr{Cvoid}) =
+    check(ccall((:bdf_gather_image_pack, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}), c.h, sample, rows, image))
+set_piece_size!(c::Context, piece) =check(ccall((:bdf_ctx_set_piece_size, lib), Cint, (Ptr{Cvoid}, Cint), c.h, piece))
 # a row context on a library-owned stream that leaves `reserve_cus` CUs (0, 8, 16, ...) free, and side contexts that really
 # run beside it -- on the reserved CUs (`reserved = true`: the hyperprior's small kernels) or on the others
 function rows_context(device::Integer=0; seed::Integer=0, reserve_cus::Integer=8)
@@ -332,6 +347,9 @@ end
 "set-up: full iterations for about `ms` milliseconds whose results are discarded -- the chain's state is put back bit for bit, only the
 buffers have rotated (ask `current_buffer`) -- to bring the device to its working state (bdf_gibbs_warm_device)"
 warm_device!(g::Gibbs, ms::Real) = check(ccall((:bdf_gibbs_warm_device, lib), Cint, (Ptr{Cvoid}, Float64), g.h, ms))
+"the host has written `entity`'s sample itself, with nothing of the chain in flight: K1c's gather image of it is packed anew
+(bdf_gibbs_sample_written)"
+sample_written!(g::Gibbs, entity::Integer) = check(ccall((:bdf_gibbs_sample_written, lib), Cint, (Ptr{Cvoid}, Cint), g.h, entity))
 
 "one Gibbs iteration; phase: 0 burn-in, 1 first posterior sample, 2 later ones, -1 no prediction update"
 sweep!(g::Gibbs, i::Integer, phase::Integer=-1) = check(ccall((:bdf_gibbs_sweep, lib), Cint, (Ptr{Cvoid}, UInt32, Cint), g.h, i, phase))

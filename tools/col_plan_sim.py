@@ -6,7 +6,7 @@ import os, sys, heapq
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import numpy as np
 
-C_OBS, C_FIN, C_FOLD, C_PART, PART_EXTRA = 52.0, 1460.0, 180.0, 700.0, 3000.0
+C_OBS, C_FIN, C_FOLD, C_PART, PART_EXTRA = 51.0, 1460.0, 180.0, 700.0, 3000.0
 
 def rounds_of(counts, T=128):
     """-> list of (cost_model, true_cost_fn placeholder) : cost in instructions"""
