@@ -47,8 +47,8 @@
 #define COL_TL 304                 // doubles of LDS per lane row for the re-layout: four 8 x 8 blocks, rows of nine (288), and half the banks' worth
                                    // between neighbouring lane rows (a ds_b64 access serves two lane rows at a time)
 
-#ifdef BDF_K1_STAMPS      // diagnostic build: per wave {start, end, rounds, cycles by phase summed over the wave's rounds} (s_memtime; bdf_debug_stamps)
-#define CSTAMP_DECL unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_acc = 0, st_mid = 0, st_prior = 0, st_fin = 0, st_rng = 0, st_lay = 0, st_steps = 0, st_rounds = 0, st_parts = 0, st_fins = 0, st_folds = 0; const unsigned long long st_begin = st_t
+#ifdef BDF_K1_STAMPS      // diagnostic build: per wave {start, end, rounds, cycles by phase} (s_memtime; bdf_debug_stamps)
+#define CSTAMP_DECL unsigned long long st_t = __builtin_amdgcn_s_memtime(), st_acc = 0, st_mid = 0, st_prior = 0, st_fin = 0, st_rng = 0, st_lay = 0, st_steps = 0, st_rounds = 0, st_parts = 0, st_fins = 0, st_folds = 0, st_pro = 0; const unsigned long long st_begin = st_t
 #define CSTAMP(x) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); x += now_ - st_t; st_t = now_; } while (0)
 #else
 #define CSTAMP_DECL do { } while (0)
@@ -58,7 +58,8 @@
 namespace {
 
 // a coefficient of the normals' polynomials through a scalar register pair where it is used (bdf_common.h, BdfLiteral): as literals
-// the compiler set fifteen of them up in front of the round loop and held them in thirty vector registers across the whole round
+// the compiler set fifteen of them up ahead of the round (in front of the loop of rounds the kernel then had) and held them in thirty
+// vector registers across it; kept without the loop: not re-measured
 struct ColCoef { static __device__ __forceinline__ double c(double x) { asm volatile("" : "+s"(x)); return x; } };
 
 // K: the observation's position in its chunk of 16 (lane K of the lane row holds its value minus the mean)
@@ -218,19 +219,19 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
     __shared__ __attribute__((aligned(16))) double lds[4 * COL_TL + 768];      // the re-layout of the four systems | the prior's image
     const int w = blockIdx.x;
     if (w >= p_in.n_waves) return;
-    const int r_end = p_in.wave_round[w + 1];
     // (64 shards: two thousand waves on ONE word are served one after the other, ~12 ns each, and a wave's first loads queue behind
     // its own atomic -- measured: the launch 60 us instead of 39)
     if (a_in.span && threadIdx.x == 0) atomicMin(a_in.span + 2 * (w & 63), (unsigned long long)__builtin_amdgcn_s_memrealtime());
     CSTAMP_DECL;
-#pragma nounroll
-    for (int rd = p_in.wave_round[w]; rd < r_end; rd++) {
-    // (the arguments and the lane through an index the compiler cannot see through: what it would hoist out of the loop -- the
-    // arguments' fields, the constants of the normals' polynomials -- would stay in registers across the whole round)
-    int zero = 0, lane = threadIdx.x;
-    asm volatile("" : "+s"(zero), "+v"(lane));
-    const SampleArgs &a = (&a_in)[zero];
-    const ColPlanDev &p = (&p_in)[zero];
+    // ONE ROUND PER WAVE, round w (bdf_col_plan_build): no table of a wave's rounds to look up in front of the job record and no loop
+    // over them -- so nothing to keep the compiler from hoisting either: the arguments and the lane are taken as they are (through an
+    // index it could not see through, as a loop of rounds needs them, every field was a scalar load of its own where it was first used,
+    // the chain below waiting for each).  `break` leaves the round.
+    do {
+    const int lane = threadIdx.x;
+    const SampleArgs &a = a_in;
+    const ColPlanDev &p = p_in;
+    const int rd = w;
     const int j = lane & 15, g = lane >> 4;
     const bool hh = (j & 8) != 0;                          // the H lanes of a lane row (dpp_rows32.h, col_rank1u)
     const uint64_t hmask = 0xff00ff00ff00ff00ull;
@@ -246,15 +247,29 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
     const bool coded = T.packed != nullptr;                // (wave-uniform)
     const double mean = T.mean;
     {
+        // The chain of loads in front of the first fmac -- every wave of the launch runs it at the same moment, nothing hides it: the
+        // look at the prior's flag is ISSUED with the job record (neither needs the other) and read after the first gathers are on
+        // their way; the record's wait is the first one, the flag has arrived with it.
+        // (through an offset the compiler cannot see is the same in every lane: a load it knows to be wave-uniform it moves to a scalar
+        // register at once, behind a wait of its own in front of the job record's load)
+        unsigned ready_seen = 0, ready_off = 0;
+        asm volatile("" : "+v"(ready_off));
+        if (a.ready) ready_seen = __hip_atomic_load(a.ready + ready_off, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const ColJob jb = p.jobs[(int64_t)rd * 4 + g];
+        // (what the first chunk and the gathers take from the arguments, in scalar registers BEFORE the record's wait and not one by one
+        // behind it; and the whole record HERE: left alone, the compiler fetches q_begin where the first chunk wants it, a round trip more)
+        asm volatile("" :: "s"(T.packed), "s"(T.colidx), "s"(T.vals), "s"(T.table), "s"(mean), "s"(rs), "s"(a.ready_want), "s"(a.prior_c));
+        asm volatile("" :: "v"(jb.q_begin));
         const bool live = jb.row >= 0;
         const int n = live ? jb.count : 0;
-        // the prior's image on its way into LDS under the accumulation, if the draw is there already (a launch that did not wait
-        // for it: one look at its flag, no spinning here)
         const unsigned lds_img = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)(__attribute__((address_space(3))) double *)(lds + 4 * COL_TL));
         bool have_prior = true;
-        if (a.ready) have_prior = __builtin_amdgcn_readfirstlane((int)((int32_t)(__hip_atomic_load(a.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - a.ready_want) >= 0)) != 0;
-        if (have_prior) col_prior_dma(a.prior_c, lds_img, lane);
+        // the prior's image on its way into LDS under the accumulation, if the draw is there already (a launch that did not wait
+        // for it: one look at its flag, no spinning here)
+        auto prior_ahead = [&]() {
+            if (a.ready) have_prior = __builtin_amdgcn_readfirstlane((int)((int32_t)(ready_seen - a.ready_want) >= 0)) != 0;
+            if (have_prior) col_prior_dma(a.prior_c, lds_img, lane);
+        };
         // ---- accumulate: S~ (its ten unique 8 x 8 blocks: col_rank1u) and W r ----
         double A0[33], A1[33];
 #pragma unroll
@@ -285,6 +300,11 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
             COL_CHUNK(0, idw_c, r_c)
             double ba[4][COL_IMG_LANE(IMG)], bb[4][COL_IMG_LANE(IMG)];
             col_gather4<IMG, FULL, 0>(ba, rs, idw_c, rowb, eo, ok1);
+#ifdef BDF_K1_STAMPS      // the prologue: from the wave's start to the first gathers' data (the wait is the diagnostic build's)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            CSTAMP(st_pro);
+#endif
+            prior_ahead();
             for (int c0 = 0;; c0 += 16) {
                 COL_CHUNK(c0 + 16, idw_n, r_n)
                 col_gather4<IMG, FULL, 4>(bb, rs, idw_c, rowb, eo, ok1);
@@ -306,7 +326,7 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
                 idw_c = idw_n; r_c = r_n;
             }
 #undef COL_CHUNK
-        }
+        } else prior_ahead();      // (a round without observations)
 #ifdef BDF_K1_STAMPS
         asm volatile("s_nop 0" :: "v"(A0[0]), "v"(A0[32]), "v"(A1[31]));
         st_steps += (unsigned long long)nmax; st_rounds++;
@@ -340,7 +360,7 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
             st_parts++;
             if (old == sr.n_slots - 1) st_fins++;
 #endif
-            if (old != sr.n_slots - 1) { CSTAMP(st_mid); continue; }                    // not the row's last part
+            if (old != sr.n_slots - 1) { CSTAMP(st_mid); break; }                       // not the row's last part
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             if (lane == 0) p.arrived[srow] = 0;                     // ready for the next launch
@@ -483,7 +503,7 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
         }
         CSTAMP(st_fin);
     }
-    }
+    } while (false);
     if (a_in.done) {
         // this wave's rows are in memory (write-through stores, drained): one more wave of the launch done -- what the entity's
         // hyperprior chain polls for (k_hyper_chain) instead of waiting for the launch's completion event
@@ -495,7 +515,7 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
     if (threadIdx.x == 0 && a_in.b_dump && w < 65536) {
         unsigned long long *d = (unsigned long long *)a_in.b_dump + (size_t)w * 16;
         d[0] = st_begin; d[8] = st_t; d[6] = st_rounds; d[7] = st_steps;
-        d[1] = st_parts; d[2] = st_fins; d[3] = st_folds; d[4] = st_lay;
+        d[1] = st_parts; d[2] = st_fins; d[3] = st_folds; d[4] = st_lay; d[5] = st_pro;
         d[11] = st_rng; d[12] = st_acc; d[13] = st_mid; d[14] = st_prior; d[15] = st_fin;
         d[9] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 4) | ((unsigned long long)__builtin_amdgcn_s_getreg((32 - 1) << 11 | 0 << 6 | 4));
         d[10] = __builtin_amdgcn_s_getreg((4 - 1) << 11 | 0 << 6 | 20);
@@ -643,20 +663,14 @@ int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T
         for (int64_t i = two; i < nw; i++) idx.push_back(rank[(size_t)i]);
     }
     std::vector<ColJob> jobs;
-    std::vector<int32_t> wave_round;
     jobs.reserve(rounds.size() * 4);
-    wave_round.push_back(0);
-    for (int32_t i : idx) {
+    for (int32_t i : idx)
         for (int q = 0; q < 4; q++) jobs.push_back(rounds[(size_t)i].job[q]);
-        wave_round.push_back((int32_t)(jobs.size() / 4));
-    }
     plan.cost_max = rounds[(size_t)rank.front()].cost;
     plan.cost_min = rounds[(size_t)rank.back()].cost;
     plan.n_waves = (int32_t)nw;
     BDF_HIP(hipMalloc((void **)&plan.jobs_dev, jobs.size() * sizeof(ColJob)));
     BDF_HIP(hipMemcpy(plan.jobs_dev, jobs.data(), jobs.size() * sizeof(ColJob), hipMemcpyHostToDevice));
-    BDF_HIP(hipMalloc((void **)&plan.wave_round_dev, wave_round.size() * sizeof(int32_t)));
-    BDF_HIP(hipMemcpy(plan.wave_round_dev, wave_round.data(), wave_round.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     BDF_HIP(hipMalloc((void **)&plan.rows_dev, std::max<size_t>(splits.size() * sizeof(ColSplit), 8)));
     if (!splits.empty()) BDF_HIP(hipMemcpy(plan.rows_dev, splits.data(), splits.size() * sizeof(ColSplit), hipMemcpyHostToDevice));
     BDF_HIP(hipMalloc((void **)&plan.partials_dev, std::max<size_t>((size_t)n_slots_total * COL_PSZ * sizeof(double), 8)));
@@ -669,7 +683,6 @@ int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T
 void bdf_col_plan_free(bdf_col_plan &plan)
 {
     if (plan.jobs_dev) (void)hipFree(plan.jobs_dev);
-    if (plan.wave_round_dev) (void)hipFree(plan.wave_round_dev);
     if (plan.rows_dev) (void)hipFree(plan.rows_dev);
     if (plan.partials_dev) (void)hipFree(plan.partials_dev);
     if (plan.arrived_dev) (void)hipFree(plan.arrived_dev);
@@ -682,7 +695,7 @@ int bdf_col_launch(bdf_ctx *ctx, const SampleArgs &a, const bdf_col_plan &plan, 
 {
     if (plan.n_waves <= 0) return BDF_OK;
     ColPlanDev p;
-    p.jobs = plan.jobs_dev; p.wave_round = plan.wave_round_dev; p.n_waves = plan.n_waves; p._pad = 0;
+    p.jobs = plan.jobs_dev; p.n_waves = plan.n_waves; p._pad = 0;
     p.rows = plan.rows_dev; p.partials = plan.partials_dev; p.arrived = plan.arrived_dev;
     // (img_tier: the kind of a.img_in -- rows_plan.hip's launch_column -- which the buffer then covers exactly)
     BDF_REQUIRE(!a.img_in || ((img_tier == 1 || img_tier == 2) && a.D == 32 && M_other <= bdf_col_image_max_rows()), BDF_ERR_ARG,

@@ -147,8 +147,7 @@ struct ColJob {           // one lane row of one round
 #define COLF_MULTI 8      // the round is one part of a row that spans waves
 struct ColSplit { int32_t slot_begin, n_slots; };
 struct ColPlanDev {
-    const ColJob *jobs;           // four per round, wave after wave
-    const int32_t *wave_round;    // wave w runs rounds wave_round[w] .. wave_round[w + 1] - 1
+    const ColJob *jobs;           // four per round; wave w runs round w
     int32_t n_waves, _pad;
     const ColSplit *rows;
     double *partials;
@@ -157,7 +156,6 @@ struct ColPlanDev {
 struct bdf_row_ref { int32_t out, orig; int64_t qb, cnt; };
 struct bdf_col_plan {
     ColJob *jobs_dev = nullptr;
-    int32_t *wave_round_dev = nullptr;
     ColSplit *rows_dev = nullptr;
     double *partials_dev = nullptr;
     int32_t *arrived_dev = nullptr;

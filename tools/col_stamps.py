@@ -1,7 +1,7 @@
 """Per-wave phase times of K1c (k_rows_col.hip; diagnostic build: tools/ab_k1.sh build stamps "-DBDF_K1_STAMPS").
 Run on the GPU box:  BDF_LIB_PATH=.../variants/libbdf_stamps.so python3 tools/col_stamps.py
 Per wave: start, end, rounds, observation steps (the longest piece of every round, summed), and the cycles (s_memtime) spent in
-normals | accumulation | butterfly sums + slab | re-layout of the unique blocks | prior (incl. waiting for the draw) | factorisation + solves,
+prologue (start to the first gathers' data) | normals | accumulation (from there on) | butterfly sums + slab | re-layout of the unique blocks | prior (incl. waiting for the draw) | factorisation + solves,
 summed over its rounds."""
 import ctypes as C
 import os
@@ -36,7 +36,7 @@ for j, name in enumerate(("users", "movies")):
     span = t1 - t0
     print(f"== {name}: {live.sum()} waves, span {span} cycles; rounds/wave {s[:, 6].mean():.2f} (max {s[:, 6].max()}), steps/wave {s[:, 7].mean():.1f} (max {s[:, 7].max()})")
     tot = s[:, 8] - s[:, 0]
-    for nm, c in (("normals", 11), ("accumulate", 12), ("sums+slab", 13), ("re-layout", 4), ("prior", 14), ("finish", 15)):
+    for nm, c in (("prologue", 5), ("normals", 11), ("accumulate", 12), ("sums+slab", 13), ("re-layout", 4), ("prior", 14), ("finish", 15)):
         print(f"   {nm:11s} mean {s[:, c].mean():8.0f}  p50 {np.median(s[:, c]):8.0f}  max {s[:, c].max():8d}   share {s[:, c].sum() / tot.sum():.3f}")
     print(f"   wave total  mean {tot.mean():8.0f}  p50 {np.median(tot):8.0f}  max {tot.max():8d}  min {tot.min():8d}")
     print(f"   accumulate cycles per step: {s[:, 12].sum() / max(s[:, 7].sum(), 1):.1f};  finish cycles per round: {s[:, 15].sum() / max(s[:, 6].sum(), 1):.0f};"
