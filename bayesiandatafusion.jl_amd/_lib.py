@@ -24,6 +24,7 @@ P_ROBUST_N, P_ROBUST_U = 16, 17
 P_PG = 18
 P_NOISE_N, P_NOISE_U = 19, 20
 P_SPIKE_N, P_SPIKE_U, P_SPIKE = 21, 22, 23
+P_DENSE = 24
 
 
 class ArgumentError(ValueError):
@@ -99,13 +100,21 @@ class GibbsRelation(C.Structure):
                 ("pg_model", C.c_int32), ("_pad_pg", C.c_int32), ("pg_r", C.c_double),
                 ("bg_weight", C.c_double), ("bg_value", C.c_double), ("bg_sums", C.c_void_p), ("bg_weights", C.c_void_p),
                 ("noise_mode", C.c_int32), ("_pad_noise", C.c_int32), ("noise_shape", C.c_double), ("noise_rate", C.c_double),
-                ("noise_tau", C.c_void_p)]
+                ("noise_tau", C.c_void_p),
+                ("dense_R", C.c_void_p), ("dense_C", C.c_void_p), ("dense_sums", C.c_void_p), ("dense_sum_r2", C.c_double),
+                ("dense_holes", C.c_void_p), ("dense_stats", C.c_void_p)]
 
 
 class BackgroundTerm(C.Structure):
     """bdf_background_term"""
     _fields_ = [("sum", C.c_void_p), ("gram", C.c_void_p), ("alpha", C.c_double), ("alpha_dev", C.c_void_p), ("weight", C.c_double),
                 ("resid", C.c_double)]
+
+
+class DenseTerm(C.Structure):
+    """bdf_dense_term"""
+    _fields_ = [("gram", C.c_void_p), ("C", C.c_void_p), ("sum", C.c_void_p), ("alpha", C.c_double), ("alpha_dev", C.c_void_p),
+                ("weight", C.c_double), ("resid", C.c_double)]
 
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -181,7 +190,14 @@ _SIGS = {
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_background_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
-    "bdf_scores_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "bdf_dense_product": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bdf_dense_prior": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(DenseTerm), C.c_void_p, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_dense_sse": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                C.c_void_p]),
+    "bdf_dense_impute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_uint32, C.c_void_p,
+                                   C.c_int64, C.c_int64, C.c_void_p]),
+    "bdf_scores_create":(C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "bdf_scores_destroy": (C.c_int, [C.c_void_p]),
     "bdf_scores_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_scores_flush": (C.c_int, [C.c_void_p]),

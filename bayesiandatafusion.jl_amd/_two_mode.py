@@ -35,6 +35,8 @@ def relation_of(data, num_latent, who):
         raise ArgumentError(f"{who} has one noise precision for every cell; {rel.name} has a noise precision per row (use macau)")
     if rel.model.background is not None:
         raise ArgumentError(f"{who} fits the listed cells only; {rel.name} has a background (use macau)")
+    if rel.model.dense:
+        raise ArgumentError(f"{who} reads the listed cells; {rel.name} is dense (setDense; use macau)")
     if rel.model.recommend is not None:
         raise ArgumentError(f"{who} keeps no sum of scores over draws; {rel.name} asks for top-k lists (setRecommend; use macau)")
     for en in data.entities:

@@ -384,7 +384,7 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
     for (int k = 0; k < n_relations; k++) {
         const bdf_gibbs_relation &r = rels[k];
         BDF_REQUIRE(r.rel && (r.alpha_dev || r.probit), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d has no handle or no alpha_dev", k);
-        BDF_REQUIRE(!(r.alpha_sample || r.feat) || r.train, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d needs its observations as pairs (train)", k);
+        BDF_REQUIRE(!(r.alpha_sample || r.feat) || r.train || (r.dense_R && !r.feat), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d needs its observations as pairs (train)", k);
         BDF_REQUIRE(!r.feat || (r.beta && r.linear), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d has features but no beta / linear buffer", k);
         BDF_REQUIRE(!r.feat_test || r.test_baseline, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d has test features but no baseline buffer", k);
         BDF_REQUIRE(!r.probit || (!r.feat && !r.alpha_sample), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the probit model takes neither relation features nor a sampled alpha", k);
@@ -435,6 +435,24 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
             }
         }
     }
+    for (int k = 0; k < n_relations; k++) {
+        const bdf_gibbs_relation &r = rels[k];
+        if (!r.dense_R) continue;
+        BDF_REQUIRE(r.rel->n_modes == 2 && r.dense_C && r.dense_sums, BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: a dense relation takes a two-mode relation and the dense_C and dense_sums buffers", k);
+        BDF_REQUIRE(!r.probit && !r.censor && !r.interval && !r.ordinal && r.robust_nu == 0.0 && !r.pg_model && !r.obs_precision && r.noise_mode == 0 &&
+                    !(r.bg_weight > 0.0) && !r.feat && !g->comm, BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: a dense relation takes no noise model, observation weights, background, relation features nor a communicator", k);
+        BDF_REQUIRE(r.rel->nnz == 0, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d is dense: `rel` must list no cell (its values live in dense_R)", k);
+        BDF_REQUIRE(!r.dense_holes || (r.dense_stats && r.dense_holes->n_modes == 2), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: dense_holes needs two modes and the dense_stats buffer", k);
+        BDF_REQUIRE(std::isfinite(r.dense_sum_r2) && r.dense_sum_r2 >= 0.0, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: dense_sum_r2=%g", k, r.dense_sum_r2);
+        for (int m = 0; m < 2; m++) {
+            const bdf_gibbs_entity &e = g->ent[(size_t)r.entity_of_mode[m]].d;
+            BDF_REQUIRE(e.bg_Lambda && e.bg_mu && e.bg_alpha_rows && !e.spike, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d is dense but entity %d has a NULL bg_Lambda / bg_mu / bg_alpha_rows, or the spike-and-slab prior", k, r.entity_of_mode[m]);
+        }
+    }
     g->rels.assign(rels, rels + n_relations);
     if (n_relations > 0 && !g->rel_sse) BDF_HIP(hipMalloc((void **)&g->rel_sse, 8 * sizeof(double)));
     return BDF_OK;
@@ -454,7 +472,10 @@ const bdf_gibbs_relation *relation_of(const bdf_gibbs *g, const bdf_rel *rel)
 inline bool draws_latent(const bdf_gibbs_relation &r) { return r.probit || r.censor || r.interval || r.pg_model; }
 
 // does update_relations() enqueue anything for the relation?  (Known weights alone do not: the rows just read them.)
-inline bool has_model(const bdf_gibbs_relation &r) { return r.alpha_sample || r.feat || draws_latent(r) || r.robust_nu > 0.0 || r.noise_mode != 0; }
+inline bool has_model(const bdf_gibbs_relation &r)
+{
+    return r.alpha_sample || r.feat || draws_latent(r) || r.robust_nu > 0.0 || r.noise_mode != 0 || (r.dense_R && r.dense_holes);
+}
 
 // out[m] = the current sample of the entity that is mode m
 void current_factors(const bdf_gibbs *g, const int32_t *entity_of_mode, int n_modes, const double **out)
@@ -472,18 +493,63 @@ const bdf_gibbs_relation *background_of(const bdf_gibbs *g, const bdf_gibbs_enti
     return (gr && gr->bg_weight > 0.0) ? gr : nullptr;
 }
 
+// ... when it is a dense relation (bdf_gibbs_relation.dense_R), or NULL
+const bdf_gibbs_relation *dense_of(const bdf_gibbs *g, const bdf_gibbs_entity &e, int t)
+{
+    const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel);
+    return (gr && gr->dense_R) ? gr : nullptr;
+}
+
+// is a term of entity e folded into its prior (a background or a dense relation)?  Such an entity's prior is made on the row stream.
+bool folds_prior(const bdf_gibbs *g, const bdf_gibbs_entity &e)
+{
+    for (int t = 0; t < e.n_terms; t++)
+        if (background_of(g, e, t) || dense_of(g, e, t)) return true;
+    return false;
+}
+
 // The prior that entity E's rows are sampled with: the hyperprior's draw as it stands -- or, when relations of the entity have
 // background cells, that draw with their Gram terms folded in.  Per background term, in the order of the
 // entity's terms: the sum and the Gram matrix of the OTHER entity's current rows into the relation's own buffers (bdf_hyper_sums on
 // the row stream), then one bdf_background_prior into the entity's (bg_mu, bg_Lambda, bg_pack) and bg_alpha_rows, which
 // fill_terms hands the terms with unit weights.  (GibbsEngine._row_prior of engine.py is the step-by-step twin.)
-int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, const double **mu, const double **Lambda, const double **pack)
+int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, const double **mu, int *mu_is_matrix, const double **Lambda, const double **pack)
 {
     const bdf_gibbs_entity &e = E.d;
     const int D = g->D;
     *mu = e.feat ? e.mu_matrix : e.mu;
+    *mu_is_matrix = e.feat ? 1 : 0;
     *Lambda = e.Lambda;
     *pack = (E.hyper_recorded && !e.feat) ? e.prior_pack : nullptr;
+    bool dense = false;
+    for (int t = 0; t < e.n_terms; t++) dense = dense || dense_of(g, e, t) != nullptr;
+    if (dense) {
+        // a dense relation among the entity's terms: per dense term also its rows of R V (R' U) from the other
+        // entity's current rows, then one bdf_dense_prior over the dense and the background terms; the means are then one per row
+        bdf_dense_term dt[BDF_MAX_TERMS];
+        int n = 0, rc;
+        for (int t = 0; t < e.n_terms; t++) {
+            const bdf_gibbs_relation *gd = dense_of(g, e, t), *gb = background_of(g, e, t);
+            if (!gd && !gb) continue;
+            const int mode = e.terms[t].mode, other = 1 - mode;
+            const auto &O = g->ent[(size_t)e.terms[t].entity_of_mode[other]];
+            double *s = (gd ? gd->dense_sums : gb->bg_sums) + (size_t)other * ((size_t)D + (size_t)D * D);
+            if ((rc = bdf_hyper_sums(g->rows, D, O.d.N, O.d.sample[O.cur], nullptr, s, s + D))) return rc;
+            dt[n] = {};
+            dt[n].gram = s + D; dt[n].alpha = 0.0; dt[n].alpha_dev = (gd ? gd : gb)->alpha_dev;
+            if (gd) {
+                double *C = gd->dense_C + (mode == 0 ? (size_t)0 : (size_t)gd->rel->dims[0] * D);
+                if ((rc = bdf_dense_product(g->rows, gd->dense_R, gd->rel->dims[0], gd->rel->dims[1], D, O.d.sample[O.cur], mode, C))) return rc;
+                dt[n].C = C; dt[n].weight = 1.0;
+            } else {
+                dt[n].sum = s; dt[n].weight = gb->bg_weight; dt[n].resid = gb->bg_value - gb->mean_value;
+            }
+            n++;
+        }
+        if ((rc = bdf_dense_prior(g->rows, D, e.N, n, dt, *mu, *mu_is_matrix, e.Lambda, e.bg_Lambda, e.bg_mu, e.bg_alpha_rows))) return rc;
+        *mu = e.bg_mu; *mu_is_matrix = 1; *Lambda = e.bg_Lambda; *pack = nullptr;
+        return BDF_OK;
+    }
     bdf_background_term bg[BDF_MAX_TERMS];
     int n_bg = 0, rc;
     for (int t = 0; t < e.n_terms; t++) {
@@ -525,7 +591,7 @@ void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
                 if (gr->obs_precision) terms[t].linear_values = gr->linear;
                 else terms[t].alpha_dev = e.bg_alpha_rows + n_bg;
                 n_bg++;
-            }
+            } else if (gr->dense_R) n_bg++;                  // (a dense term is folded too, and shares bg_alpha_rows; none of its cells is listed)
         }
         for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
         current_factors(g, e.terms[t].entity_of_mode, e.terms[t].rel->n_modes, terms[t].factors);
@@ -553,6 +619,11 @@ int update_relations(bdf_gibbs *g)
         if (r.noise_mode != 0 && (rc = bdf_entity_noise_draw(R, r.rel, r.noise_mode - 1, r.train, D, fac, r.mean_value, 0.0, r.alpha_dev, r.noise_shape,
                                                              r.noise_rate, r.rel_tag, r.noise_tau, r.obs_precision, r.alpha_sample ? g->rel_sse + 1 : nullptr)))
             return rc;
+        // dense: the holes given the rows and the PREVIOUS iteration's alpha, into dense_R, before sample_alpha -- whose sum then runs
+        // over all N M cells
+        if (r.dense_R && r.dense_holes && (rc = bdf_dense_impute(R, r.dense_holes, D, fac, 0.0, r.alpha_dev, r.rel_tag, r.dense_R, r.rel->dims[0],
+                                                               r.rel->dims[1], r.dense_stats)))
+            return rc;
         if (r.alpha_sample) {
             // err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known weights:
             // sum w e^2 (the robust draw above has left its own)
@@ -564,6 +635,15 @@ int update_relations(bdf_gibbs *g)
                     if ((rc = bdf_hyper_sums(R, D, g->ent[(size_t)r.entity_of_mode[m]].d.N, fac[m], nullptr, r.bg_sums + m * pk, r.bg_sums + m * pk + D))) return rc;
                 rc = bdf_background_sse(R, r.train, D, fac, r.mean_value, r.bg_weights, r.bg_value, r.bg_weight, r.bg_sums, r.bg_sums + D, r.bg_sums + pk,
                                         r.bg_sums + pk + D, r.rel->dims[0], r.rel->dims[1], g->rel_sse + 1);
+                n = r.rel->dims[0] * r.rel->dims[1];
+            } else if (r.dense_R) {
+                // dense: the closed form over all N M cells from C = R V and the two entities' Gram matrices
+                const size_t pk = (size_t)D + (size_t)D * D;
+                for (int m = 0; m < 2; m++)
+                    if ((rc = bdf_hyper_sums(R, D, g->ent[(size_t)r.entity_of_mode[m]].d.N, fac[m], nullptr, r.dense_sums + m * pk, r.dense_sums + m * pk + D))) return rc;
+                if ((rc = bdf_dense_product(R, r.dense_R, r.rel->dims[0], r.rel->dims[1], D, fac[1], 0, r.dense_C))) return rc;
+                rc = bdf_dense_sse(R, D, r.rel->dims[0], fac[0], r.dense_C, r.dense_sums + D, r.dense_sums + pk + D, r.dense_sum_r2,
+                                   r.dense_holes ? r.dense_stats : nullptr, g->rel_sse + 1);
                 n = r.rel->dims[0] * r.rel->dims[1];
             } else if (r.obs_precision) rc = (r.robust_nu > 0.0 || r.noise_mode != 0) ? BDF_OK : bdf_pairs_weighted_sse(R, r.train, D, fac, r.mean_value, r.obs_precision, g->rel_sse + 1);
             else rc = bdf_predict_sse(R, r.train, D, fac, r.mean_value, nullptr, g->rel_sse);
@@ -640,11 +720,12 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
         return BDF_OK;
     }
     const double *mu, *Lambda, *pack;
-    if ((rc = row_prior(g, E, &mu, &Lambda, &pack))) return rc;
+    int is_matrix;
+    if ((rc = row_prior(g, E, &mu, &is_matrix, &Lambda, &pack))) return rc;
     const int nch = e.terms[0].rel->chunks;
     for (int c = 0; c < nch; c++) {
         R->gimg_trust = !g->comm;             // (as in bdf_gibbs_sweep)
-        if ((rc = bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, e.feat ? 1 : 0, Lambda, e.tag, c, nch, e.sample[nxt], pack))) return rc;
+        if ((rc = bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, is_matrix, Lambda, e.tag, c, nch, e.sample[nxt], pack))) return rc;
     }
     E.cur = nxt;
     return BDF_OK;
@@ -884,8 +965,8 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         static const bool poll_with_comm = getenv("BDF_POLL_WITH_COMM") != nullptr;
         // (an entity with background cells is ordered like one with side information: its prior is made here, on the row stream, from
         // the draw -- behind the draw's event, and its rows join neither the polling nor the hand-over by counter below)
-        bool bg = false;
-        for (int t = 0; t < e.n_terms; t++) bg = bg || background_of(g, e, t) != nullptr;
+        // (an entity with a dense relation likewise)
+        const bool bg = folds_prior(g, e);
         // (so is an entity with the spike-and-slab prior: its rows wait for the event of its hyper step, bdf_spike_hyper)
         const bool poll = g->polling && (!g->comm || poll_with_comm) && E.hyper_recorded && !e.feat && !bg && !e.spike;
         if (E.hyper_recorded && !poll) BDF_HIP(hipStreamWaitEvent(R->stream, E.ev_hyper, 0));
@@ -896,7 +977,8 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         if (!draws_in_chain && n > BDF_DRAWS_BATCH && !e.spike && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
         // the prior of this launch: the draw's (mu, Lambda) and pack, or -- background cells -- those with the Gram terms folded in
         const double *mu_rows = nullptr, *Lambda_rows = nullptr, *pack_rows = nullptr;
-        if (!e.spike && (rc = row_prior(g, E, &mu_rows, &Lambda_rows, &pack_rows))) return rc;
+        int mu_rows_matrix = e.feat ? 1 : 0;
+        if (!e.spike && (rc = row_prior(g, E, &mu_rows, &mu_rows_matrix, &Lambda_rows, &pack_rows))) return rc;
         bdf_term terms[BDF_MAX_TERMS];
         fill_terms(g, e, terms);
         const int nxt = (E.cur + 1) % 3;
@@ -927,7 +1009,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             if (counter) R->rows_done = E.done_dev;
             R->gimg_trust = !g->comm;         // (the chain's own buffers: sample_written() hears of every other writer)
             if ((rc = e.spike ? bdf_sample_rows_spike(R, D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
-                              : bdf_sample_rows(R, D, e.N, e.n_terms, terms, mu_rows, e.feat ? 1 : 0, Lambda_rows, e.tag, c, nch, e.sample[nxt], pack_rows)))
+                              : bdf_sample_rows(R, D, e.N, e.n_terms, terms, mu_rows, mu_rows_matrix, Lambda_rows, e.tag, c, nch, e.sample[nxt], pack_rows)))
                 return rc;
             if (counter && R->rows_done_added >= 0) { by_counter = true; E.done_target += (uint32_t)R->rows_done_added; }
             if (g->comm && (rc = bdf_allgather_rows(R, g->comm, D, e.N, e.sample[nxt], c, nch))) return rc;

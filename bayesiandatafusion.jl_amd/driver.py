@@ -332,6 +332,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                     "cells": int(r.data.dims[0]) * int(r.data.dims[1]) - r.data.nnz()} for r in data.relations if r.model.background is not None}
     if bgs:
         result["background"] = bgs
+    # dense relations (setDense): how many cells the matrix on the device holds, and how many of them were imputed
+    dense = {r.name: {"cells": int(r.data.dims[0]) * int(r.data.dims[1]),
+                      "holes": int(r.data.dims[0]) * int(r.data.dims[1]) - r.data.nnz()} for r in data.relations if r.model.dense}
+    if dense:
+        result["dense"] = dense
     if recommend is not None:
         rows = recommend["rows"]
         result["recommend"] = {"k": recommend["k"], "rows": np.arange(1, int(rel.data.dims[0]) + 1) if rows is None else np.array(rows, dtype=np.int64),

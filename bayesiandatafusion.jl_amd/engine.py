@@ -16,6 +16,7 @@ Layout: an entity's sample is the reference's D x N column-major matrix == a con
 (N = chunks * world * cmax rows with a layout; EntityState.host() returns the reference's orientation and order).
 """
 import ctypes as C
+import math
 import os
 import sys
 import weakref
@@ -25,8 +26,8 @@ import torch
 
 from . import _lib
 from . import features as feat
-from ._lib import ArgumentError, BackgroundTerm, GibbsEntity, Term, check, lib
-from .relation_data import background_mean, check_model, noise_kind
+from ._lib import ArgumentError, BackgroundTerm, DenseTerm, GibbsEntity, Term, check, lib
+from .relation_data import background_mean, check_model, dense_matrix, noise_kind
 
 
 def _ptr(t):
@@ -283,13 +284,16 @@ class DeviceRelation:
         # background cells (setBackground): {"weight", "value"}; the two modes' sums and Gram matrices; the caller's weights (omega is
         # then what the rows read, omega_k - c0)
         self.bg = self.bg_sums = self.bg_weights = None
+        # a dense relation (setDense): {"R": N x M, the values without their mean; "C": per mode, its rows of R V / R' U; "sums": per
+        # mode, D + D^2 doubles of bdf_hyper_sums; "sum_r2": the sum of r^2}.  The handle is then a relation WITHOUT cells
+        self.dense = None
         ctx.adopt(self)
 
     @property
     def has_model(self):
         """a model of its own -- alpha sampled, relation-level side information, a noise model other than fixed-precision
         Gaussian noise: registered with the native iteration, and stepped before the rows of every iteration"""
-        return self.alpha_sample or self.F is not None or self.kind != "gauss" or self.bg is not None
+        return self.alpha_sample or self.F is not None or self.kind != "gauss" or self.bg is not None or self.dense is not None
 
     def index(self, mode0):
         rp, ri = _lib.c_i64p(), _lib.c_i64p()
@@ -754,6 +758,12 @@ class FeatOperator:
             pass
 
 
+def _dense_mean(r):
+    """mean_value of a dense relation: the listed values added one after the other, as bdf_relation_create adds the explicit listing's"""
+    v = np.asarray(r.data.values, dtype=np.float64)
+    return float(np.cumsum(v)[-1]) / len(v) if len(v) else 0.0
+
+
 def _background_values(r):
     """What the row kernels read as the values of a background relation (setBackground) whose listed cells all have weight 1:
     y' = mean + (r - c0 rb) / (1 - c0), with r = y - mean and rb = value - mean.  Beside the precision alpha (1 - c0) a listed cell
@@ -863,12 +873,16 @@ class EntityState:
             self.lambda_beta = ctx.tensor([en.lambda_beta])
             self.cg_iters = ctx.zeros(D, dtype=torch.int32)
 
-    def background_buffers(self):
-        """(Lambda_eff, mu_eff -- one per row with side information --, their prior pack, alpha (1 - c0) per term) of bdf_background_prior"""
+    def background_buffers(self, dense=False):
+        """(Lambda_eff, mu_eff -- one per row with side information --, their prior pack, alpha (1 - c0) per term) of bdf_background_prior;
+        dense: of bdf_dense_prior, whose mu_eff is always one per row"""
+        if dense and (self.bg_mu is None or self.bg_mu.dim() == 1):
+            self.bg_mu = self.ctx.zeros(self.N, self.D)
         if self.bg_Lambda is None:
             ctx, D = self.ctx, self.D
             self.bg_Lambda = ctx.zeros(D, D)
-            self.bg_mu = ctx.zeros(self.N, D) if self.F is not None else ctx.zeros(D)
+            if self.bg_mu is None:
+                self.bg_mu = ctx.zeros(self.N, D) if self.F is not None else ctx.zeros(D)
             self.bg_pack = ctx.zeros(lib().bdf_prior_pack_doubles(D))
             self.bg_alpha_rows = ctx.zeros(_lib.BDF_MAX_TERMS)
 
@@ -1055,13 +1069,15 @@ class GibbsEngine:
             if len(r.entities) != len(r.data.dims):
                 raise ArgumentError(f"Relation {r.name} has {len(r.entities)} entities but its data implies {r.data.size()}.")
             lays = [self.layouts[self._entity_index(e)] for e in r.entities]
-            dr = DeviceRelation(self.ctx, r.data, lays if self.world > 1 else None, self.rank, values=_background_values(r))
+            # (a dense relation lists no cell to the row kernels: its matrix reaches the rows through the prior, _row_prior)
+            idf = r.data if not r.model.dense else type(r.data)((r.data.ids[:0], r.data.values[:0]), list(r.data.dims), names=r.data.names)
+            dr = DeviceRelation(self.ctx, idf, lays if self.world > 1 else None, self.rank, values=_background_values(r))
             r._dev = dr
             self.rel.append(dr)
             self._build_model(r, dr, noise_kind(r))
-            if dr.bg is not None:
+            if dr.bg is not None or dr.dense is not None:
                 for e in r.entities:
-                    self.ent[self._entity_index(e)].background_buffers()
+                    self.ent[self._entity_index(e)].background_buffers(dense=dr.dense is not None)
         self.scores = None
         self.begin_scores()
         self._test_pairs = None
@@ -1097,7 +1113,8 @@ class GibbsEngine:
         # (probit: the latent is not centred; logit / counts: psi = u'v + the offset the setter was given)
         # (background cells: the mean over ALL cells, the unlisted ones at the background value -- valueMean of the dense listing)
         m.mean_value = 0.0 if kind == "probit" else (m.pg["offset"] if kind in ("logit", "counts") else
-                                                     (background_mean(r) if m.background is not None else dr.value_mean()))
+                                                     (background_mean(r) if m.background is not None else
+                                                      (_dense_mean(r) if m.dense else dr.value_mean())))
         # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
         # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
         # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
@@ -1118,7 +1135,7 @@ class GibbsEngine:
         # the training table as pairs: this rank's block for sample_alpha and sample_beta_rel; a noise model takes every row (one
         # rank), sorted -- its per-observation arrays stay in the caller's order, whichever way the pairs are stored
         ids, values = np.asarray(r.data.ids), np.asarray(r.data.values)
-        if dr.F is not None or m.alpha_sample:
+        if dr.F is not None or (m.alpha_sample and not m.dense):
             dr.train = self._pairs(ctx, r, ids[dr.obs_lo:dr.obs_hi], values[dr.obs_lo:dr.obs_hi])
         if kind != "gauss":
             dr.train = self._sorted_pairs(ctx, r, ids, values, dr.train)
@@ -1180,6 +1197,22 @@ class GibbsEngine:
                 dr.bg_weights = dr.omega
                 dr.omega = ctx.tensor((w - c0) if nn else np.ones(1))
                 dr.linear = ctx.tensor((y - (w * (y - m.mean_value) - c0 * rb) / (w - c0)) if nn else np.full(1, m.mean_value))
+        if m.dense:
+            # a dense relation (setDense): R = Y - mean as one N x M matrix, a hole at 0 until the first
+            # imputation.  The rows of both entities are sampled with the prior _row_prior makes from the other entity's Gram matrix
+            # and the product R V (R' U), kept per mode in C; alpha's sum of squares is the closed form over the same pieces.
+            Y, holes = dense_matrix(r)
+            N, M = Y.shape
+            listed = ~np.isnan(Y)
+            R0 = np.where(listed, Y - m.mean_value, 0.0)
+            Cs = ctx.zeros(N + M, self.D)              # (one buffer: the native iteration is handed its start)
+            dr.dense = {"R": ctx.tensor(R0), "C": [Cs[:N], Cs[N:]], "sums": ctx.zeros(2, self.D + self.D * self.D),
+                        "sum_r2": math.fsum((R0 * R0).ravel().tolist()), "holes": None, "stats": None}
+            if len(holes):
+                # the holes as pairs (the values are not read) and where their draw leaves the sum of their squares
+                dr.dense["holes"] = self._pairs(ctx, r, holes + 1, np.zeros(len(holes)))
+                dr.dense["stats"] = ctx.zeros(4)
+            dr.wsse = ctx.zeros(1)
         dr.alpha_dev = ctx.tensor([float(m.alpha)])
 
     # ---- the native iteration (bdf_gibbs) -----------------------------------------------------------------------------
@@ -1249,6 +1282,11 @@ class GibbsEngine:
             g.probit, g.robust_nu, g.pg_model, g.pg_r = int(dr.kind == "probit"), dr.robust_nu, dr.pg_model, dr.pg_r
             if dr.bg is not None:
                 g.bg_weight, g.bg_value = dr.bg["weight"], dr.bg["value"]
+            if dr.dense is not None:
+                dn = dr.dense
+                g.dense_R, g.dense_C, g.dense_sums, g.dense_sum_r2 = dn["R"].data_ptr(), dn["C"][0].data_ptr(), dn["sums"].data_ptr(), dn["sum_r2"]
+                if dn["holes"] is not None:
+                    g.dense_holes, g.dense_stats = dn["holes"].handle, dn["stats"].data_ptr()
             if dr.noise is not None:
                 g.noise_mode, g.noise_shape, g.noise_rate, g.noise_tau = dr.noise["mode"], dr.noise["shape"], dr.noise["rate"], dr.tau.data_ptr()
             for name, t in (("linear", dr.linear), ("censor", dr.censor), ("interval", dr.interval), ("ordinal_codes", dr.ord_codes),
@@ -1413,7 +1451,7 @@ class GibbsEngine:
         scalar update_relations has read back (the native iteration's rows read alpha_dev)"""
         en = self.data.entities[j]
         terms = (Term * len(en.relations))()
-        n_bg = 0
+        n_bg = 0                          # (terms folded into the prior so far: background terms, and dense ones -- they share alpha_rows)
         for t, r in enumerate(en.relations):
             dr, term = self.rel[self._relation_index(r)], terms[t]
             term.rel, term.mode, term.mean_value = dr.handle, en.modes[t] - 1, r.model.mean_value
@@ -1428,6 +1466,8 @@ class GibbsEngine:
                     term.alpha = r.model.alpha * (1.0 - dr.bg["weight"])
                     if self.native and r.model.alpha_sample:
                         term.alpha_dev = self.ent[j].bg_alpha_rows.data_ptr() + 8 * n_bg
+                n_bg += 1
+            elif dr.dense is not None:    # (no cell of it is listed: the term reads nothing)
                 n_bg += 1
             for k, e2 in enumerate(r.entities):
                 term.factors[k] = self.ent[self._entity_index(e2)].sample.data_ptr()
@@ -1447,6 +1487,11 @@ class GibbsEngine:
             m, tag, train = r.model, ri + 1, (dr.train.handle if dr.train is not None else None)
             fac = _facs(self.factors_of(r))
             wsse = _ptr(dr.wsse) if (dr.omega is not None and m.alpha_sample) else None
+            # dense: the holes | U, V and the PREVIOUS iteration's alpha, into R, before sample_alpha -- whose sum then runs over all cells
+            dn = dr.dense
+            if dn is not None and dn["holes"] is not None:
+                check(L.bdf_dense_impute(R, dn["holes"].handle, D, fac, m.alpha, _ptr(dr.alpha_dev), tag, _ptr(dn["R"]), r.data.dims[0],
+                                         r.data.dims[1], _ptr(dn["stats"])))
             # robust: omega | U, V and the PREVIOUS iteration's alpha, before sample_alpha -- which then takes sum omega e^2
             if dr.robust_nu > 0.0:
                 check(L.bdf_robust_draw(R, train, D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), dr.robust_nu, tag, _ptr(dr.omega), wsse))
@@ -1457,7 +1502,7 @@ class GibbsEngine:
             if m.alpha_sample:
                 # err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known
                 # weights: sum w e^2 (the robust draw above has left its own)
-                sse = wsse if dr.omega is not None else C.c_void_p(dr.train.stats.data_ptr() + 8)
+                sse = wsse if (dr.omega is not None or dn is not None) else C.c_void_p(dr.train.stats.data_ptr() + 8)
                 n = r.data.nnz()
                 if dr.bg is not None:
                     # background cells: the sum of c e^2 over ALL N M cells from the listed ones, the two entities' sums and Gram matrices
@@ -1467,6 +1512,16 @@ class GibbsEngine:
                     check(L.bdf_background_sse(R, train, D, fac, m.mean_value, _ptr(dr.bg_weights) if dr.bg_weights is not None else None,
                                                dr.bg["value"], dr.bg["weight"], _ptr(dr.bg_sums[0, :D]), _ptr(dr.bg_sums[0, D:]),
                                                _ptr(dr.bg_sums[1, :D]), _ptr(dr.bg_sums[1, D:]), r.data.dims[0], r.data.dims[1], sse))
+                    n = int(r.data.dims[0]) * int(r.data.dims[1])
+                elif dn is not None:
+                    # dense: the closed form over all N M cells from C = R V and the two entities' Gram matrices
+                    sse = _ptr(dr.wsse)
+                    f = self.factors_of(r)
+                    for k in (0, 1):
+                        check(L.bdf_hyper_sums(R, D, f[k].shape[0], _ptr(f[k]), None, _ptr(dn["sums"][k, :D]), _ptr(dn["sums"][k, D:])))
+                    check(L.bdf_dense_product(R, _ptr(dn["R"]), r.data.dims[0], r.data.dims[1], D, _ptr(f[1]), 0, _ptr(dn["C"][0])))
+                    check(L.bdf_dense_sse(R, D, r.data.dims[0], _ptr(f[0]), _ptr(dn["C"][0]), _ptr(dn["sums"][0, D:]), _ptr(dn["sums"][1, D:]),
+                                          dn["sum_r2"], _ptr(dn["stats"]), sse))
                     n = int(r.data.dims[0]) * int(r.data.dims[1])
                 elif dr.omega is None:
                     check(L.bdf_predict_sse(R, train, D, fac, m.mean_value, None, _ptr(dr.train.stats)))
@@ -1509,9 +1564,30 @@ class GibbsEngine:
         into the relation's buffers (bdf_hyper_sums on the row stream), then one bdf_background_prior into the entity's buffers."""
         en, st, D = self.data.entities[j], self.ent[j], self.D
         bgs = [(t, r, self.rel[self._relation_index(r)]) for t, r in enumerate(en.relations)]
-        bgs = [(t, r, dr) for t, r, dr in bgs if dr.bg is not None]
+        bgs = [(t, r, dr) for t, r, dr in bgs if dr.bg is not None or dr.dense is not None]
         if not bgs:
-            return mu, st.Lambda, pack
+            return mu, is_matrix, st.Lambda, pack
+        if any(dr.dense is not None for _, _, dr in bgs):
+            # a dense relation among them (DESIGN.md section 25): per dense term also its rows of R V (R' U) from the other entity's
+            # current rows, then one bdf_dense_prior over the dense and the background terms; the means are then one per row
+            arr = (DenseTerm * len(bgs))()
+            for k, (t, r, dr) in enumerate(bgs):
+                mode = en.modes[t] - 1
+                so = self.ent[self._entity_index(r.entities[1 - mode])]
+                s = (dr.dense["sums"] if dr.dense is not None else dr.bg_sums)[1 - mode]
+                check(lib().bdf_hyper_sums(self.ctx.handle, D, so.N, _ptr(so.sample), None, _ptr(s[:D]), _ptr(s[D:])))
+                arr[k].gram = s.data_ptr() + 8 * D
+                arr[k].alpha = r.model.alpha
+                arr[k].alpha_dev = dr.alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
+                if dr.dense is not None:
+                    check(lib().bdf_dense_product(self.ctx.handle, _ptr(dr.dense["R"]), r.data.dims[0], r.data.dims[1], D, _ptr(so.sample), mode,
+                                                  _ptr(dr.dense["C"][mode])))
+                    arr[k].C, arr[k].weight = dr.dense["C"][mode].data_ptr(), 1.0
+                else:
+                    arr[k].sum, arr[k].weight, arr[k].resid = s.data_ptr(), dr.bg["weight"], dr.bg["value"] - r.model.mean_value
+            check(lib().bdf_dense_prior(self.ctx.handle, D, st.N, len(bgs), arr, _ptr(mu), is_matrix, _ptr(st.Lambda), _ptr(st.bg_Lambda),
+                                        _ptr(st.bg_mu), _ptr(st.bg_alpha_rows)))
+            return st.bg_mu, 1, st.bg_Lambda, None
         arr = (BackgroundTerm * len(bgs))()
         for k, (t, r, dr) in enumerate(bgs):
             other = 1 - (en.modes[t] - 1)
@@ -1524,7 +1600,7 @@ class GibbsEngine:
             arr[k].weight, arr[k].resid = dr.bg["weight"], dr.bg["value"] - r.model.mean_value
         check(lib().bdf_background_prior(self.ctx.handle, D, st.N, len(bgs), arr, _ptr(mu), is_matrix, _ptr(st.Lambda), _ptr(st.bg_Lambda),
                                          _ptr(st.bg_mu), None if is_matrix else _ptr(st.bg_pack), _ptr(st.bg_alpha_rows)))
-        return st.bg_mu, st.bg_Lambda, (None if is_matrix else st.bg_pack)
+        return st.bg_mu, is_matrix, st.bg_Lambda, (None if is_matrix else st.bg_pack)
 
     # ---- macau.jl:96-117: latent rows of entity j --------------------------------------------------------------
     def sample_entity(self, j):
@@ -1547,7 +1623,7 @@ class GibbsEngine:
             timer = KernelTimer()
             check(lib().bdf_ctx_time_next_rows(self.ctx.handle, timer.start, timer.stop))
         pack = st.prior_pack if (st.prior_pack_valid and not is_matrix) else None
-        mu, Lam, pack = self._row_prior(j, mu, is_matrix, pack)
+        mu, is_matrix, Lam, pack = self._row_prior(j, mu, is_matrix, pack)
         # written into the entity's next buffer (nothing this launch reads), which then becomes the current one; several ranks:
         # chunk after chunk, every chunk exchanged in place while the next one is sampled
         nch = st.layout.chunks

@@ -104,6 +104,8 @@ def toStr(x):
         s += f" bg:{x.model.background['weight']:g}"
     if x.model.recommend is not None:
         s += f" rec:{x.model.recommend['k']}"
+    if x.model.dense:
+        s += " dense"
     return f"{x.name[:4]}[{s}]"
 
 
@@ -133,6 +135,7 @@ class RelationModel:
         self.background = None    # setBackground: {"weight", "value"}; every cell that is not listed observes `value` with precision alpha weight
         self.recommend = None     # setRecommend: {"k", "rows", "exclude_listed", "batch"}; macau() returns a top-k list per row of the first entity
         self.entity_noise = None  # setEntityNoise: {"mode" (1-based), "shape", "rate"}; a sampled noise precision per row of that entity
+        self.dense = False        # setDense: all N M cells of the two-mode relation are kept as a matrix on the device, none is listed to the row kernels
         self.new_test = None      # setNewTest: {"mode" (1-based: the entity with new rows), "ids" (n, 2), "values" (NaN: unknown)}; cells of new rows
 
 
@@ -331,8 +334,15 @@ def setCensored(r, censor):
     return None
 
 
+def _not_dense(r, what):
+    """a dense relation (setDense) is Gaussian with one precision for all its cells, and none of them is listed to a kernel"""
+    if r.model.dense:
+        raise ArgumentError(f"Relation {r.name} is dense (setDense): it does not take {what}.")
+
+
 def _no_weights(r, what):
     """the noise models with a latent value per observation take neither the Student-t model nor observation weights"""
+    _not_dense(r, what)
     if r.model.robust is not None:
         raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
     if r.model.weights is not None:
@@ -344,6 +354,7 @@ def _no_weights(r, what):
 
 
 def _weight_guards(r, what, pg_ok=False, noise_ok=False):
+    _not_dense(r, what)
     if hasFeatures(r):
         raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
     if r.model.probit:
@@ -605,6 +616,9 @@ def _spike_guards(entity):
         if r.model.background is not None:
             raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
                                 "spike-and-slab prior (setSpikeAndSlab), the background folds a dense Gram matrix into the prior precision.")
+        if r.model.dense:
+            raise ArgumentError(f"Relation {r.name} is dense (setDense): its entity {entity.name} does not take the spike-and-slab prior "
+                                "(setSpikeAndSlab), a dense relation folds a Gram matrix into the prior precision.")
 
 
 def check_spike(entity, world=1):
@@ -677,6 +691,101 @@ def background_mean(r):
     return (float(np.sum(np.asarray(r.data.values, dtype=np.float64))) + (cells - nn) * r.model.background["value"]) / cells if cells else 0.0
 
 
+_DENSE = "a dense matrix (setDense)"
+
+
+def setDense(r, on=True):
+    """A two-mode Gaussian relation whose N x M cells are (nearly) all observed: an expression panel, a fully screened plate, a
+    feature block taken as a relation.  macau() then keeps the values as one N x M matrix on the device and lists no cell to the row
+    kernels: every row's conditional reads the relation through the Gram matrix of the other entity's rows, which all rows share,
+    and its own row of R V, two products on the matrix cores per iteration.  Nothing is approximated: the
+    chain is the explicit listing's up to rounding.  Cells that are not listed -- held out by assignToTest, or NaN in
+    denseRelation's array -- are holes: they are imputed before every iteration, r_ij = u_i.v_j + z / sqrt(alpha), which is exact
+    Gibbs sampling on the augmented model; at least half of the cells must be listed (the sparse path is the right one otherwise).
+    noise_kind stays "gauss"; alpha is fixed, set by setPrecision, or sampled over all N M cells.  Entity side information, the
+    test set, lpd, rmse_train, setWaic and further relations (sparse, dense or with a background) on the same entities all work.
+    setDense(r, False) takes it back.  Works before or after the test split."""
+    if not on:
+        r.model.dense = False
+        r._dev = None
+        return None
+    _dense_guards(r)
+    r.model.dense = True
+    r._dev = None
+    return None
+
+
+def denseRelation(Y, name, entities, class_cut=0.0, alpha=1.0):
+    """Relation(...) from a 2-D array of values, NaN where a cell is not observed, with setDense.  (A bare 2-D array handed to
+    Relation itself is a table of ids and values.)"""
+    Y = np.asarray(Y, dtype=np.float64)
+    if Y.ndim != 2:
+        raise ArgumentError(f"denseRelation takes a 2-D array of values, not {Y.ndim} dimensions.")
+    if len(entities) != 2:
+        raise ArgumentError("For matrix relation the number of entities has to be 2.")
+    ii, jj = np.nonzero(~np.isnan(Y))                   # row by row
+    r = Relation((np.stack([ii + 1, jj + 1], axis=1).astype(np.int64), Y[ii, jj]), name, entities, class_cut=class_cut, alpha=alpha,
+                 dims=[int(Y.shape[0]), int(Y.shape[1])])
+    setDense(r)
+    return r
+
+
+def _dense_guards(r):
+    what = _DENSE
+    if len(r.data.dims) != 2:
+        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} takes a two-mode relation.")
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
+    if r.model.probit:
+        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take {what}.")
+    if r.model.censor is not None:
+        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take {what}.")
+    if r.model.ordinal is not None:
+        raise ArgumentError(f"Relation {r.name} has the ordinal noise model (setOrdinal): it does not take {what}.")
+    if r.model.interval is not None:
+        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): it does not take {what}.")
+    if r.model.pg is not None:
+        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
+    if r.model.entity_noise is not None:
+        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): it does not take {what}.")
+    if r.model.robust is not None:
+        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
+    if r.model.weights is not None:
+        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
+    if r.model.background is not None:
+        raise ArgumentError(f"Relation {r.name} has a background (setBackground): it does not take {what}, which leaves no cell unlisted.")
+    if r.model.recommend is not None:
+        raise ArgumentError(f"Relation {r.name} asks for top-k lists (setRecommend): it does not take {what}.")
+    if r.model.new_test is not None:
+        raise ArgumentError(f"Relation {r.name} has cells of new rows (setNewTest): it does not take {what}.")
+    for en in r.entities:
+        if en.spike is not None:
+            raise ArgumentError(f"Entity {en.name} has the spike-and-slab prior (setSpikeAndSlab): its relation {r.name} does not take {what}, "
+                                "which folds a Gram matrix into the prior precision.")
+    ids = np.asarray(r.data.ids).reshape(r.data.nnz(), 2)
+    if len(np.unique(ids, axis=0)) != len(ids):
+        raise ArgumentError(f"Relation {r.name} lists a cell more than once: {what} keeps one value per cell.")
+    cells = int(r.data.dims[0]) * int(r.data.dims[1])
+    if cells == 0 or 2 * len(ids) < cells:
+        raise ArgumentError(f"Relation {r.name} lists {len(ids)} of its {cells} cells: {what} takes a relation with at least half of them "
+                            "listed (the sparse path is the right one for this one).")
+
+
+def check_dense(r):
+    """what a dense relation must still satisfy when a sampler is built on it (a noise model, a background or a test split may have
+    come since setDense)"""
+    _dense_guards(r)
+
+
+def dense_matrix(r):
+    """(Y, holes) of a dense relation: its values as an N x M array, NaN at the holes, and the holes' (i, j), 0-based, row by row"""
+    N, M = int(r.data.dims[0]), int(r.data.dims[1])
+    Y = np.full((N, M), np.nan)
+    ids = np.asarray(r.data.ids, dtype=np.int64).reshape(r.data.nnz(), 2)
+    Y[ids[:, 0] - 1, ids[:, 1] - 1] = np.asarray(r.data.values, dtype=np.float64)
+    return Y, np.argwhere(np.isnan(Y))
+
+
 RECOMMEND_MAX_K = 64          # BDF_REC_MAX_K, BDF_REC_MAX_BATCH (csrc/recommend.h)
 RECOMMEND_MAX_BATCH = 32
 
@@ -726,6 +835,7 @@ def _recommend_spec(r, k, rows, exclude_listed, batch):
 
 def _recommend_guards(r):
     what = "top-k lists (setRecommend)"
+    _not_dense(r, what)
     if len(r.data.dims) != 2:
         raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
     if hasFeatures(r):
@@ -805,6 +915,7 @@ def setNewTest(r, entity, table):
 
 def _new_test_guards(r, entity):
     what = "cells of new rows (setNewTest)"
+    _not_dense(r, what)
     if len(r.entities) != 2 or len(r.data.dims) != 2:
         raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
     if hasFeatures(r):
@@ -1125,6 +1236,7 @@ def check_interval(r):
 # check then reads): (the model's fields are set, its check, what the refusal of several ranks calls it -- None: refused through
 # another row, the ordinal model through its interval bounds)
 _MODEL_CHECKS = (
+    (lambda m: m.dense, check_dense, lambda m: "a dense matrix (setDense)"),
     (lambda m: m.probit, check_probit, lambda m: "the probit noise model"),
     (lambda m: m.censor is not None, check_censored, lambda m: "censoring flags"),
     (lambda m: m.ordinal is not None, check_ordinal, None),

@@ -65,6 +65,7 @@ extern "C" {
 #define BDF_P_SPIKE_N 21       /* bdf_spike_hyper: the gamma variates' normals (entity = entity_tag, row = variate 3 d, 3 d + 1, 3 d + 2 of component d, attempt t: normal 2 t) */
 #define BDF_P_SPIKE_U 22       /* bdf_spike_hyper: ... and their uniforms (the same entity and row, pair = attempt; shape < 1: the boost's uniform is pair 0xffff) */
 #define BDF_P_SPIKE 23         /* bdf_sample_rows_spike: the inclusion uniform of component d of a row (entity = entity_tag, row = original row, pair d, words x and y) */
+#define BDF_P_DENSE 24         /* bdf_dense_impute: the normal of a hole of a dense relation (entity 0x800000 | rel_tag, row = the hole's index, normal 0) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -801,6 +802,49 @@ int bdf_background_sse(bdf_ctx *ctx, const bdf_pairs *train, int D, const double
                        const double *weights, double value, double weight, const double *sumU, const double *gramU,
                        const double *sumV, const double *gramV, int64_t N, int64_t M, double *out);
 
+/* ---- dense relations (csrc/k_dense.hip, csrc/dense.h) ------------------------------------------------------
+ * A two-mode relation whose N x M cells are ALL observed is kept as R (dev, N x M doubles row-major, r_ij = y_ij - mean_value)
+ * and is never listed.  With V the other entity's rows, G = V'V and C = R V, row i's conditional is that of an ordinary row whose
+ * prior is (Lambda_eff, mu_eff_i) = (Lambda + alpha G, Lambda_eff^-1 (Lambda mu_i + alpha C_i)) and that has no cells of the relation.
+ *
+ * out = R F (dev, N x D row-major; F: dev M x D row-major), or with `transpose` out = R' F (M x D; F: N x D), on the f64 matrix
+ * cores from the one copy of R.  D in 1 .. BDF_MAX_D; rows and columns past N, M, D are predicated off.  Every element is summed in
+ * a fixed order: bit-identical reruns.  One launch on ctx's stream. */
+int bdf_dense_product(bdf_ctx *ctx, const double *R, int64_t N, int64_t M, int D, const double *F, int transpose, double *out);
+typedef struct {
+    const double *gram;           /* dev, D x D: the Gram matrix of the other entity's rows (what bdf_hyper_sums leaves in UUt)  */
+    const double *C;              /* dev, N x D row-major: a dense term's rows of R V (bdf_dense_product); NULL: a background term */
+    const double *sum;            /* dev, D: a background term's sum of the other entity's rows; NULL: a dense term              */
+    double alpha;                 /* the relation's precision ...                                                              */
+    const double *alpha_dev;      /* ... or, nullable, where it lives on the device (sampled there): read instead of `alpha`  */
+    double weight;                /* 1 for a dense term; c0 of a background term, in (0, 1]                                    */
+    double resid;                 /* a background term's rb = background value - mean_value                                    */
+} bdf_dense_term;
+/* The effective prior of an entity with at least one dense relation among its n_terms (1 .. BDF_MAX_TERMS) dense and background
+ * terms, two launches on ctx's stream:
+ *   Lambda_out (dev, D x D) = Lambda + sum_k alpha_k weight_k G_k   (added in the order of terms[])
+ *   mu_out (dev, D x N: ALWAYS one mean per row) = Lambda_out^-1 (Lambda mu_i + sum_dense alpha_k C_k,i + sum_background alpha_k c0_k
+ *   rb_k s_k); mu is D doubles, or D x N with mu_is_matrix.  Waves of one launch factor Lambda_out and solve for the columns of Lambda_out^-1 (and
+ *   Lambda_out^-1 Lambda), every solve refined once; the rows then take two products on the matrix cores.
+ *   alpha_rows_out (dev, n_terms doubles): alpha_k of a dense term, alpha_k (1 - c0_k) of a background term (bdf_background_prior).
+ * Lambda_out may not alias Lambda nor mu_out mu.  A Lambda_out that is not positive definite sets the context's row-system flag
+ * (BDF_ERR_NOTPD at the next bdf_ctx_sync).  Not reentrant on one context (the solves live in the context's scratch). */
+int bdf_dense_prior(bdf_ctx *ctx, int D, int64_t N, int n_terms, const bdf_dense_term *terms, const double *mu, int mu_is_matrix,
+                    const double *Lambda, double *Lambda_out, double *mu_out, double *alpha_rows_out);
+/* *out (dev, 1 double) = sum over ALL N M cells of (r_ij - u_i.v_j)^2 = sum_r2 - 2 sum_i u_i.C_i + <U'U, V'V>, for sample_alpha with
+ * n = N M.  U (dev, N x D), C = R V of the same (U, V) (bdf_dense_product), gramU, gramV (dev, D x D: bdf_hyper_sums of both
+ * entities), sum_r2 = the sum of r_ij^2 over the listed cells, which does not change, holes_r2 (dev, nullable: 0) the same over the
+ * holes as bdf_dense_impute left it.  Fixed summation order; two launches; not reentrant on one context. */
+int bdf_dense_sse(bdf_ctx *ctx, int D, int64_t N, const double *U, const double *C, const double *gramU, const double *gramV,
+                  double sum_r2, const double *holes_r2, double *out);
+/* The cells of a dense relation that are not listed are holes: latent values of the augmented model, drawn before alpha and the rows
+ * of every iteration.  holes: their (i, j) as pairs (two modes; the values are not read); for hole k in the caller's order
+ *   R[i M + j] = u_i.v_j + z_k / sqrt(alpha),   z_k normal 0 of stream (BDF_P_DENSE, 0x800000 | rel_tag, row k) at the context's sweep
+ * with alpha read from alpha_dev when it is given.  stats_out (dev, 4 doubles): [0] the sum of the new r^2 over the holes, in a
+ * fixed order; the rest 0.  No hole: stats_out is zeroed.  A hole outside N x M is skipped.  Not reentrant on one context. */
+int bdf_dense_impute(bdf_ctx *ctx, const bdf_pairs *holes, int D, const double *const *factors, double alpha, const double *alpha_dev,
+                     uint32_t rel_tag, double *R, int64_t N, int64_t M, double *stats_out);
+
 /* ---- top-K lists per row from the posterior mean score (csrc/k_recommend.hip, csrc/recommend.h) ---------
  * A bdf_scores object keeps sum[i, j] = sum over the pushed draws of u_i . v_j for n_rows scored rows of the first entity and all M
  * rows of the second, n_rows x M doubles row-major, and a ring of `batch` (1 .. 32) slots of draws that are not in the sum yet.
@@ -972,6 +1016,21 @@ typedef struct {
     int32_t _pad_noise;
     double noise_shape, noise_rate;
     double *noise_tau;
+    /* a dense relation (a zeroed tail is "none"): dense_R (dev, N x M row-major) holds every cell of the
+     * two-mode relation without its mean, and `rel` lists NO cell.  Before the rows of either entity the iteration takes the Gram
+     * matrix of the OTHER entity's rows (bdf_hyper_sums on the row stream, into dense_sums) and that entity's rows of R V or R' U
+     * (bdf_dense_product, into dense_C: the N x D rows of mode 0, then the M x D rows of mode 1) and folds them into the prior
+     * (bdf_dense_prior; the entity's bg_* buffers, bg_mu then D x N).  dense_holes (nullable): the cells that were not listed, as
+     * pairs; bdf_dense_impute draws them into dense_R before alpha and the rows of every iteration and leaves the sum of their
+     * squares in dense_stats (dev, 4 doubles; NULL without holes).  alpha_sample: the sum of squares over all N M cells by
+     * bdf_dense_sse, n = N M, with dense_sum_r2 the listed cells' sum of r^2.  Not with any noise model, a background on the same
+     * relation, feat or a communicator */
+    double *dense_R;
+    double *dense_C;
+    double *dense_sums;           /* dev, 2 (D + D D): as bg_sums                                                             */
+    double dense_sum_r2;
+    const bdf_pairs *dense_holes;
+    double *dense_stats;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

@@ -616,6 +616,45 @@ function background_sse!(c::Context, p::DevPairs, D, factors::Vector{<:DevArray}
                  Int64, Int64, Ptr{Cvoid}),
                 c.h, p.h, D, fp, mean_value, weights === nothing ? C_NULL : weights.p, value, weight, sumU.p, gramU.p, sumV.p, gramV.p, N, M, out.p))
 end
+# ---- dense relations (bdf_dense_product, bdf_dense_prior, bdf_dense_sse; DESIGN.md section 25) --------------------------------
+"out = R F (N x D), or R' F (M x D) with transpose, for the N x M row-major device matrix R of a dense relation, on the f64 matrix cores"
+function dense_product!(c::Context, R::DevArray{Float64}, N, M, D, F::DevArray{Float64}, transpose::Bool, out::DevArray{Float64})
+    check(ccall((:bdf_dense_product, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint, Ptr{Cvoid}, Cint, Ptr{Cvoid}),
+                c.h, R.p, N, M, D, F.p, transpose ? 1 : 0, out.p))
+end
+struct DenseTerm                                  # bdf_dense_term, field for field
+    gram::Ptr{Cvoid}                              # device D x D: the Gram matrix of the other entity's rows
+    C::Ptr{Cvoid}                                 # device N x D: a dense term's rows of R V; C_NULL: a background term
+    sum::Ptr{Cvoid}                               # device D: a background term's sum of the other entity's rows; C_NULL: a dense term
+    alpha::Float64
+    alpha_dev::Ptr{Cvoid}                         # C_NULL: `alpha`
+    weight::Float64                               # 1, or the background's c0
+    resid::Float64                                # the background's value - mean_value
+end
+"the prior the rows of an entity with dense relations are sampled with: Lambda_out = Lambda + sum alpha G, mu_out (always D x N) =
+Lambda_out^-1 (Lambda mu_i + sum alpha C_i); background terms of the same entity are folded in as background_prior! folds them"
+function dense_prior!(c::Context, D, N, terms::Vector{DenseTerm}, mu::DevArray{Float64}, mu_is_matrix::Bool, Lambda::DevArray{Float64},
+                      Lambda_out::DevArray{Float64}, mu_out::DevArray{Float64}, alpha_rows::DevArray{Float64})
+    check(ccall((:bdf_dense_prior, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Cint, Ptr{DenseTerm}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, D, N, length(terms), terms, mu.p, mu_is_matrix ? 1 : 0, Lambda.p, Lambda_out.p, mu_out.p, alpha_rows.p))
+end
+"out[1] = the sum of (r - u.v)^2 over all N M cells of a dense relation from C = R V, the two Gram matrices and the sum of r^2 (the
+listed cells' as a number, the holes' where dense_impute! left it, nothing: no holes)"
+function dense_sse!(c::Context, D, N, U::DevArray{Float64}, C::DevArray{Float64}, gramU::DevArray{Float64}, gramV::DevArray{Float64},
+                    sum_r2, holes_r2, out::DevArray{Float64})
+    check(ccall((:bdf_dense_sse, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, D, N, U.p, C.p, gramU.p, gramV.p, sum_r2, holes_r2 === nothing ? C_NULL : holes_r2.p, out.p))
+end
+"the holes of a dense relation (its cells that are not listed, as pairs) drawn from their conditional into R: u.v + z / sqrt(alpha);
+stats[1] = the sum of their squares"
+function dense_impute!(c::Context, holes::DevPairs, D, factors::Vector{<:DevArray}, alpha, alpha_dev, rel_tag, R::DevArray{Float64}, N, M,
+                       stats::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_dense_impute, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Ptr{Cvoid}, UInt32, Ptr{Cvoid}, Int64, Int64, Ptr{Cvoid}),
+                c.h, holes.h, D, fp, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, rel_tag, R.p, N, M, stats.p))
+end
 # ---- top-K lists per row from the posterior mean score (bdf_scores_*; DESIGN.md section 21) ------------------------------------
 "the sum of u.v over the pushed draws for n_rows scored rows of the first entity against the M rows of the second, a ring of `batch`
 draws that are not in the sum yet; rows: device Int32 0-based rows of U (nothing: the rows 0 .. n_rows - 1)"
@@ -853,6 +892,12 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     noise_shape::Float64                          # ... tau_j ~ Gamma(noise_shape, noise_rate) a priori
     noise_rate::Float64
     noise_tau::Ptr{Cvoid}                         # device Float64 per row of that mode: the last draw
+    dense_R::Ptr{Cvoid}                           # a dense relation (C_NULL: none): device N x M Float64 row-major, every cell without its mean; rel then lists no cell
+    dense_C::Ptr{Cvoid}                           # device (N + M) x D Float64: the rows of R V for mode 1, then of R' U for mode 2 (dense_product!)
+    dense_sums::Ptr{Cvoid}                        # device, 2 (D + D D) Float64: as bg_sums
+    dense_sum_r2::Float64                         # the listed cells' sum of r^2
+    dense_holes::Ptr{Cvoid}                       # bdf_pairs of the cells that are not listed (C_NULL: none): dense_impute! draws them before every iteration
+    dense_stats::Ptr{Cvoid}                       # device, 4 Float64 (C_NULL without holes): [1] the holes' sum of r^2
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"

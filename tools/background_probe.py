@@ -154,7 +154,7 @@ def main():
         parts[f"sums_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_hyper_sums(
             ctx.handle, D, so.N, p(so.sample), None, p(s[:D]), p(s[D:])))), 2)
         parts[f"sums_and_fold_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: eng._row_prior(j, st.mu, 0, None)), 2)
-        mu, Lam, pack = eng._row_prior(j, st.mu, 0, None)
+        mu, _, Lam, pack = eng._row_prior(j, st.mu, 0, None)
         terms, nxt = eng._terms(j), ctx.zeros(st.N, D)
         parts[f"rows_{en.name}_folded_prior_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_sample_rows(
             ctx.handle, D, st.N, 1, terms, p(mu), 0, p(Lam), 900 + j, 0, 1, p(nxt), p(pack)))), 2)
