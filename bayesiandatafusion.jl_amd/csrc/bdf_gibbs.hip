@@ -1,8 +1,8 @@
 // bdf_gibbs.hip -- one Gibbs iteration of macau (src/macau.jl:80-203) enqueued from native code: the latent rows of every
 // entity (sample_latent_all2! / sample_user2_all!, src/sampling.jl:149-289), the exchange of the sampled rows between GPUs,
 // every entity's hyperprior (src/sampling.jl:116-127, src/normal_wishart.jl:38-42) and the test-set prediction update
-// (macau.jl:142-184) -- the BPMF iteration and the one the multi-GPU path runs.  (Side information adds the beta update and
-// per-row prior means; those iterations are enqueued step by step through the entry points of bdf.h.)
+// (macau.jl:142-184), with the beta update and the per-row prior means of side information and the relations' own models.  The
+// same pieces can be enqueued one by one, with plain stream order: bdf_gibbs_step_relations, bdf_gibbs_step_rows.
 //
 // Three HIP streams: rows | hyperpriors | prediction updates.  The hyperprior of entity j runs beside the rows of entity
 // j+1, the prediction update of sweep t beside the rows of sweep t+1 (every entity's rows rotate through three buffers).
@@ -512,15 +512,15 @@ bool folds_prior(const bdf_gibbs *g, const bdf_gibbs_entity &e)
 // background cells, that draw with their Gram terms folded in.  Per background term, in the order of the
 // entity's terms: the sum and the Gram matrix of the OTHER entity's current rows into the relation's own buffers (bdf_hyper_sums on
 // the row stream), then one bdf_background_prior into the entity's (bg_mu, bg_Lambda, bg_pack) and bg_alpha_rows, which
-// fill_terms hands the terms with unit weights.  (GibbsEngine._row_prior of engine.py is the step-by-step twin.)
-int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, const double **mu, int *mu_is_matrix, const double **Lambda, const double **pack)
+// fill_terms hands the terms with unit weights.  pack_valid: the entity's latest draw has left its prior pack.
+int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, bool pack_valid, const double **mu, int *mu_is_matrix, const double **Lambda, const double **pack)
 {
     const bdf_gibbs_entity &e = E.d;
     const int D = g->D;
     *mu = e.feat ? e.mu_matrix : e.mu;
     *mu_is_matrix = e.feat ? 1 : 0;
     *Lambda = e.Lambda;
-    *pack = (E.hyper_recorded && !e.feat) ? e.prior_pack : nullptr;
+    *pack = (pack_valid && !e.feat) ? e.prior_pack : nullptr;
     bool dense = false;
     for (int t = 0; t < e.n_terms; t++) dense = dense || dense_of(g, e, t) != nullptr;
     if (dense) {
@@ -572,7 +572,7 @@ int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, const double **mu, int *mu_
 }
 
 // the terms of entity e's row launch: a term of a registered relation takes the model's alpha_dev, linear_values and
-// obs_precision.  (GibbsEngine._terms of engine.py is the step-by-step twin.)
+// obs_precision
 void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
 {
     int n_bg = 0;
@@ -598,8 +598,7 @@ void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
     }
 }
 
-// macau.jl:83-92 on the row stream, before the entities' rows.  (GibbsEngine.update_relations of engine.py is the step-by-step
-// twin: the same launches in the same order -- keep the two in step, line by line.)
+// macau.jl:83-92 on the row stream, before the entities' rows
 int update_relations(bdf_gibbs *g)
 {
     bdf_ctx *R = g->rows;
@@ -696,39 +695,81 @@ extern "C" int bdf_gibbs_set_comm(bdf_gibbs *g, bdf_comm *comm)
     return BDF_OK;
 }
 
-// measurement: the rows of one entity and nothing else -- the launch bdf_gibbs_sweep makes for it (same kernel variant, same
-// inputs), without the hyperprior update, the exchange or the prediction update.  The chain's state is not kept consistent.
 namespace {
 // the hyperprior's degrees of freedom: nu0 (+ numF with side information and full_lambda_u, macau.jl:124-129)
 double hyper_nu(const bdf_gibbs_entity &e) { return e.nu0 + ((e.feat && e.full_lambda_u) ? (double)e.feat->n : 0.0); }
+
+// The row launch of entity E as bdf_gibbs_sweep makes it (same prior, same terms, same kernel variant), enqueued with plain stream
+// order: no events, no polling, no done counter, and the context's timing fields are the caller's.  exchange: with a communicator,
+// every chunk's rows to the other ranks.
+int launch_rows(bdf_gibbs *g, bdf_gibbs::Ent &E, bool pack_valid, bool exchange)
+{
+    bdf_ctx *R = g->rows;
+    const bdf_gibbs_entity &e = E.d;
+    int rc;
+    const double *mu = nullptr, *Lambda = nullptr, *pack = nullptr;
+    int is_matrix = 0;
+    if (!e.spike && (rc = row_prior(g, E, pack_valid, &mu, &is_matrix, &Lambda, &pack))) return rc;
+    bdf_term terms[BDF_MAX_TERMS];
+    fill_terms(g, e, terms);
+    const int nxt = (E.cur + 1) % 3, nch = e.terms[0].rel->chunks;
+    exchange = exchange && g->comm;
+    for (int c = 0; c < nch; c++) {
+        R->gimg_trust = !g->comm;             // (as in bdf_gibbs_sweep)
+        if ((rc = e.spike ? bdf_sample_rows_spike(R, g->D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
+                          : bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, is_matrix, Lambda, e.tag, c, nch, e.sample[nxt], pack)))
+            return rc;
+        if (exchange && (rc = bdf_allgather_rows(R, g->comm, g->D, e.N, e.sample[nxt], c, nch))) return rc;
+    }
+    if (exchange && (rc = bdf_allgather_join(R, g->comm))) return rc;
+    E.cur = nxt;
+    return BDF_OK;
+}
 }  // namespace
 
+// measurement: the rows of one entity and nothing else -- the launch bdf_gibbs_sweep makes for it (same kernel variant, same
+// inputs), without the hyperprior update, the exchange or the prediction update.  The chain's state is not kept consistent.
 extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
 {
     BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_rows_only: bad argument");
-    bdf_ctx *R = g->rows;
+    g->rows->sweep_host = sweep;
+    auto &E = g->ent[(size_t)entity];
+    return launch_rows(g, E, E.hyper_recorded, false);
+}
+
+// The iteration piece by piece, for a host that keeps the schedule itself (hyperpriors, beta and the prediction update through the
+// entry points of bdf.h): what runs before the rows, and one entity's rows.  Both on the row stream under the iteration number the
+// caller has set (bdf_ctx_set_sweep).
+extern "C" int bdf_gibbs_step_relations(bdf_gibbs *g)
+{
+    BDF_REQUIRE(g, BDF_ERR_ARG, "bdf_gibbs_step_relations: NULL argument");
+    return g->rels.empty() ? BDF_OK : update_relations(g);
+}
+
+extern "C" int bdf_gibbs_step_rows(bdf_gibbs *g, int entity, int pack_valid)
+{
+    BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_step_rows: bad argument");
     auto &E = g->ent[(size_t)entity];
     const bdf_gibbs_entity &e = E.d;
-    R->sweep_host = sweep;
     int rc;
-    bdf_term terms[BDF_MAX_TERMS];
-    fill_terms(g, e, terms);
-    const int nxt = (E.cur + 1) % 3;
-    if (e.spike) {
-        if ((rc = bdf_sample_rows_spike(R, g->D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, 0, 1, e.sample[nxt]))) return rc;
-        E.cur = nxt;
-        return BDF_OK;
-    }
-    const double *mu, *Lambda, *pack;
-    int is_matrix;
-    if ((rc = row_prior(g, E, &mu, &is_matrix, &Lambda, &pack))) return rc;
-    const int nch = e.terms[0].rel->chunks;
-    for (int c = 0; c < nch; c++) {
-        R->gimg_trust = !g->comm;             // (as in bdf_gibbs_sweep)
-        if ((rc = bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, is_matrix, Lambda, e.tag, c, nch, e.sample[nxt], pack))) return rc;
-    }
-    E.cur = nxt;
+    // side information: uhat = (F beta)' with the beta of the previous iteration, per-row prior means mu + uhat (macau.jl:103-104)
+    if (e.feat && (rc = bdf_uhat(g->rows, e.feat, g->D, e.beta, e.mu, e.uhat, e.mu_matrix))) return rc;
+    return launch_rows(g, E, pack_valid != 0, true);
+}
+
+// parity hooks: the terms and the prior that the entity's next row launch would take
+extern "C" int bdf_gibbs_terms(bdf_gibbs *g, int entity, bdf_term *out)
+{
+    BDF_REQUIRE(g && out && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_terms: bad argument");
+    fill_terms(g, g->ent[(size_t)entity].d, out);
     return BDF_OK;
+}
+
+extern "C" int bdf_gibbs_row_prior(bdf_gibbs *g, int entity, int pack_valid, const double **mu, int *mu_is_matrix, const double **Lambda,
+                                   const double **pack)
+{
+    BDF_REQUIRE(g && mu && mu_is_matrix && Lambda && pack && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_row_prior: bad argument");
+    return row_prior(g, g->ent[(size_t)entity], pack_valid != 0, mu, mu_is_matrix, Lambda, pack);
 }
 
 // set-up: bring the device to its working state (clocks, power gating: an iteration right after idle time runs ~10 % slower than
@@ -978,7 +1019,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // the prior of this launch: the draw's (mu, Lambda) and pack, or -- background cells -- those with the Gram terms folded in
         const double *mu_rows = nullptr, *Lambda_rows = nullptr, *pack_rows = nullptr;
         int mu_rows_matrix = e.feat ? 1 : 0;
-        if (!e.spike && (rc = row_prior(g, E, &mu_rows, &mu_rows_matrix, &Lambda_rows, &pack_rows))) return rc;
+        if (!e.spike && (rc = row_prior(g, E, E.hyper_recorded, &mu_rows, &mu_rows_matrix, &Lambda_rows, &pack_rows))) return rc;
         bdf_term terms[BDF_MAX_TERMS];
         fill_terms(g, e, terms);
         const int nxt = (E.cur + 1) % 3;

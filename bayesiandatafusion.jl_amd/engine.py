@@ -3,9 +3,10 @@
 Everything numeric is a call into libbdf_hip.so (include/bdf.h).  torch is used for what the task calls plumbing: device
 allocations (tensors) and, with several ranks, the channel over which rank 0 hands the RCCL unique id to the others.
 
-* Without side information the whole iteration (rows of every entity, exchange between the GPUs, hyperpriors, test
-  prediction update) is ONE native call, bdf_gibbs_sweep (csrc/bdf_gibbs.hip).  With side information the same steps plus
-  uhat / beta are enqueued from here through the entry points of bdf.h, on the same three-stream schedule.
+* The whole iteration (the relations' models, rows of every entity, exchange between the GPUs, hyperpriors, beta, test
+  prediction update) is ONE native call, bdf_gibbs_sweep (csrc/bdf_gibbs.hip).  BDF_NO_NATIVE: the same object's relation step
+  and row launches are driven piece by piece from here (bdf_gibbs_step_relations, bdf_gibbs_step_rows), with the hyperpriors and
+  beta through the entry points of bdf.h, on three streams with plain stream order.
 * Several ranks (shard=(rank, world)): every entity's rows are shared out by bdf_layout_build -- dealt over the ranks in
   falling order of degree as the reference deals rows i:P:N to its workers (src/sampling.jl:154) -- and stored at INTERNAL
   positions, so that a rank's rows of a chunk are one contiguous block and the exchange is an in-place all-gather
@@ -26,7 +27,7 @@ import torch
 
 from . import _lib
 from . import features as feat
-from ._lib import ArgumentError, BackgroundTerm, DenseTerm, GibbsEntity, Term, check, lib
+from ._lib import ArgumentError, GibbsEntity, Term, check, lib
 from .relation_data import background_mean, check_model, dense_matrix, noise_kind
 
 
@@ -108,7 +109,7 @@ class Context:
 
     @classmethod
     def wrap(cls, handle, device, seed, owned=False):
-        """a context created by the library (bdf_ctx_create_side, bdf_gibbs_contexts): the stream is the library's"""
+        """a context created by the library (bdf_ctx_create_rows, bdf_gibbs_contexts): the stream is the library's"""
         self = cls.__new__(cls)
         self.device = device
         self.handle = C.c_void_p(handle) if not isinstance(handle, C.c_void_p) else handle
@@ -130,16 +131,6 @@ class Context:
         h = C.c_void_p()
         check(lib().bdf_ctx_create_rows(dev.index, C.c_uint64(int(seed) & (2 ** 64 - 1)), int(reserve_cus), C.byref(h)))
         return cls.wrap(h, dev, seed, owned=True)
-
-    @classmethod
-    def side(cls, main, apart=(), reserved=False):
-        """a context on another stream of main's device, chosen by the library so that kernels on it really run beside those
-        of `main` and of the contexts in `apart` (HIP multiplexes streams onto a few hardware queues; two streams on one
-        queue serialise each other: 171 instead of 125 us per sweep); reserved: on the CUs main's stream leaves free"""
-        h = C.c_void_p()
-        arr = (C.c_void_p * max(len(apart), 1))(*[a.handle for a in apart])
-        check(lib().bdf_ctx_create_side(main.handle, arr, len(apart), int(reserved), C.byref(h)))
-        return cls.wrap(h, main.device, main.seed, owned=True)
 
     def adopt(self, child):
         self._children.add(child)
@@ -277,7 +268,7 @@ class DeviceRelation:
         self.train = None            # the training table as DevicePairs
         self.linear = None           # linear_values of the row kernels: mean + F beta, or what the model's latent draw leaves
         self.censor = self.interval = self.ordinal = self.ord_codes = None
-        self.omega = self.wsse = self.omega_sum = None          # obs_precision of the row kernels; sum omega e^2; omega's running sum
+        self.omega = self.omega_sum = None          # obs_precision of the row kernels; omega's running sum
         self.robust_nu, self.pg_model, self.pg_r = 0.0, 0, 0.0
         # a noise precision per row of one entity (setEntityNoise): {"mode", "shape", "rate"}; tau per row of that mode; its running sum
         self.noise = self.tau = self.tau_sum = None
@@ -292,7 +283,7 @@ class DeviceRelation:
     @property
     def has_model(self):
         """a model of its own -- alpha sampled, relation-level side information, a noise model other than fixed-precision
-        Gaussian noise: registered with the native iteration, and stepped before the rows of every iteration"""
+        Gaussian noise: registered with the library's iteration, which steps it before the rows of every iteration"""
         return self.alpha_sample or self.F is not None or self.kind != "gauss" or self.bg is not None or self.dense is not None
 
     def index(self, mode0):
@@ -840,7 +831,7 @@ class EntityState:
         self.draws = ctx.zeros(D * D + D)
         self.draws_sweep = None
         # a relation of the entity has background cells (setBackground): the prior its rows are sampled with, made before every
-        # row launch (GibbsEngine._row_prior); allocated by background_buffers()
+        # row launch (row_prior() of csrc/bdf_gibbs.hip); allocated by background_buffers()
         self.bg_Lambda = self.bg_mu = self.bg_pack = self.bg_alpha_rows = None
         # the spike-and-slab prior (setSpikeAndSlab): pi, tau, logit pi, log tau (D each; pi = 1/2, tau = 1 at the start) and the
         # running sums of the result -- [u != 0] per loading; pi, tau and the count n_d per component --, zeroed on the row stream,
@@ -1069,7 +1060,7 @@ class GibbsEngine:
             if len(r.entities) != len(r.data.dims):
                 raise ArgumentError(f"Relation {r.name} has {len(r.entities)} entities but its data implies {r.data.size()}.")
             lays = [self.layouts[self._entity_index(e)] for e in r.entities]
-            # (a dense relation lists no cell to the row kernels: its matrix reaches the rows through the prior, _row_prior)
+            # (a dense relation lists no cell to the row kernels: its matrix reaches the rows through the prior, row_prior() of csrc/bdf_gibbs.hip)
             idf = r.data if not r.model.dense else type(r.data)((r.data.ids[:0], r.data.values[:0]), list(r.data.dims), names=r.data.names)
             dr = DeviceRelation(self.ctx, idf, lays if self.world > 1 else None, self.rank, values=_background_values(r))
             r._dev = dr
@@ -1089,25 +1080,24 @@ class GibbsEngine:
         self.k1_event_every = 1   # ... of every n-th sweep
         self._k1_sweep = 0
         # ---- streams: rows (main) | hyperpriors | prediction updates
-        self.gibbs = None
         self.comm = None
         self._ev_pred = None
         self._ev_rows, self._ev_hyper = {}, {}
-        if self.native:
-            self._create_native()
-        else:
-            if self.world > 1:
-                self.comm = make_comm(self.ctx, self.rank, self.world)
-            self.ctx_h = self.ctx_p = self.ctx
-            if not os.environ.get("BDF_NO_OVERLAP"):
-                self.ctx_h = Context.side(self.ctx, reserved=True)
-                if all(feat.isempty(r.F) for r in data.relations):
-                    self.ctx_p = Context.side(self.ctx, [self.ctx_h])
+        self._create_gibbs()
+        # (callers take `gibbs` for the native path's handle: None step by step)
+        self.gibbs = self._gibbs if self.native else None
+        if not self.native:
+            # BDF_NO_OVERLAP: everything on the row context; a relation with features: the prediction updates stay there (their
+            # baseline is refreshed on the row stream)
+            if os.environ.get("BDF_NO_OVERLAP"):
+                self.ctx_h = self.ctx_p = self.ctx
+            elif not all(feat.isempty(r.F) for r in data.relations):
+                self.ctx_p = self.ctx
         torch.cuda.synchronize(self.ctx.device)      # everything set up above (on torch's streams too) is in place
 
     def _build_model(self, r, dr, kind):
-        """relation r's model on the device (the fields DeviceRelation names): what _register_relations hands the native iteration
-        and update_relations steps before the rows.  kind: noise_kind(r), after check_model(r)"""
+        """relation r's model on the device (the fields DeviceRelation names): what _register_relations hands the library, which
+        steps it before the rows.  kind: noise_kind(r), after check_model(r)"""
         ctx, m, nn = self.ctx, r.model, r.data.nnz()
         dr.kind, dr.alpha_sample = kind, bool(m.alpha_sample)
         # (probit: the latent is not centred; logit / counts: psi = u'v + the offset the setter was given)
@@ -1166,7 +1156,6 @@ class GibbsEngine:
             # the caller's weights, or the omega of the Student-t model -- drawn before alpha and the rows of every iteration
             # (bdf_robust_draw), which also leaves sum omega e^2 for sample_alpha
             dr.omega = ctx.tensor(m.weights if (kind == "weights" and nn) else np.ones(max(nn, 1)))
-            dr.wsse = ctx.zeros(1)
             dr.robust_nu = float(m.robust["nu"]) if kind == "robust" else 0.0
         elif kind == "entity_noise":
             # a noise precision tau_j per row of one entity, drawn where the robust model draws omega
@@ -1175,7 +1164,6 @@ class GibbsEngine:
             dr.noise = dict(m.entity_noise)
             dr.omega = ctx.tensor(np.ones(max(nn, 1)))
             dr.tau = ctx.tensor(np.ones(max(int(r.data.dims[dr.noise["mode"] - 1]), 1)))
-            dr.wsse = ctx.zeros(1)
         elif kind in ("logit", "counts"):
             # bdf_pg_draw: omega of every training row, the rows' obs_precision beside linear_values; the training pairs predict
             # through the model's link (rmse_train)
@@ -1184,14 +1172,13 @@ class GibbsEngine:
             dr.train.set_pg_link(dr.pg_model, dr.pg_r)
         if m.background is not None:
             # background cells (setBackground): every unlisted cell observes `value` with precision alpha c0.  The
-            # rows of both entities are sampled with the prior _row_prior makes from the other entity's sum and Gram matrix (bg_sums:
+            # rows of both entities are sampled with the prior row_prior() makes from the other entity's sum and Gram matrix (bg_sums:
             # per mode, D + D^2 doubles).  Unit weights: the relation was created from _background_values and its terms read alpha
             # (1 - c0) -- nothing per observation.  setWeights: the rows read omega_k - c0 and, through linear_values, the
             # pseudo-residual (omega_k r_k - c0 rb) / (omega_k - c0), both constant over the run; alpha's sum of squares reads omega_k
             c0, rb = m.background["weight"], m.background["value"] - m.mean_value
             dr.bg = dict(m.background)
             dr.bg_sums = ctx.zeros(2, self.D + self.D * self.D)
-            dr.wsse = ctx.zeros(1)
             if kind == "weights":
                 w, y = np.asarray(m.weights, dtype=np.float64), np.asarray(values, dtype=np.float64)
                 dr.bg_weights = dr.omega
@@ -1199,7 +1186,7 @@ class GibbsEngine:
                 dr.linear = ctx.tensor((y - (w * (y - m.mean_value) - c0 * rb) / (w - c0)) if nn else np.full(1, m.mean_value))
         if m.dense:
             # a dense relation (setDense): R = Y - mean as one N x M matrix, a hole at 0 until the first
-            # imputation.  The rows of both entities are sampled with the prior _row_prior makes from the other entity's Gram matrix
+            # imputation.  The rows of both entities are sampled with the prior row_prior() makes from the other entity's Gram matrix
             # and the product R V (R' U), kept per mode in C; alpha's sum of squares is the closed form over the same pieces.
             Y, holes = dense_matrix(r)
             N, M = Y.shape
@@ -1212,11 +1199,13 @@ class GibbsEngine:
                 # the holes as pairs (the values are not read) and where their draw leaves the sum of their squares
                 dr.dense["holes"] = self._pairs(ctx, r, holes + 1, np.zeros(len(holes)))
                 dr.dense["stats"] = ctx.zeros(4)
-            dr.wsse = ctx.zeros(1)
         dr.alpha_dev = ctx.tensor([float(m.alpha)])
 
-    # ---- the native iteration (bdf_gibbs) -----------------------------------------------------------------------------
-    def _create_native(self):
+    # ---- the iteration object (bdf_gibbs) -----------------------------------------------------------------------------
+    def _create_gibbs(self):
+        """the library's description of the iteration, on both paths: the native one runs it whole (bdf_gibbs_sweep), the
+        step-by-step one drives its relation step and row launches piece by piece (bdf_gibbs_step_relations, bdf_gibbs_step_rows)
+        on a schedule of its own, with the object's two side contexts"""
         ents = (GibbsEntity * len(self.ent))()
         for j, (en, st) in enumerate(zip(self.data.entities, self.ent)):
             g = ents[j]
@@ -1247,24 +1236,22 @@ class GibbsEngine:
                     setattr(g, name, getattr(st, name).data_ptr())
                 g.use_ff, g.sample_lambda_beta, g.full_lambda_u = int(en.use_FF), int(en.lambda_beta_sample), int(self.full_lambda_u)
                 g.tol, g.lb_nu, g.lb_mu = self.tol, en.nu, en.mu
-        self.gibbs = C.c_void_p()
-        check(lib().bdf_gibbs_create(self.ctx.handle, self.D, len(self.ent), ents, C.byref(self.gibbs)))
+        self._gibbs = C.c_void_p()
+        check(lib().bdf_gibbs_create(self.ctx.handle, self.D, len(self.ent), ents, C.byref(self._gibbs)))
         h, p = C.c_void_p(), C.c_void_p()
-        check(lib().bdf_gibbs_contexts(self.gibbs, C.byref(h), C.byref(p)))
+        check(lib().bdf_gibbs_contexts(self._gibbs, C.byref(h), C.byref(p)))
         self.ctx_h = Context.wrap(h, self.ctx.device, self.ctx.seed)
         self.ctx_p = Context.wrap(p, self.ctx.device, self.ctx.seed)
         if self.world > 1 or os.environ.get("BDF_FORCE_COMM"):
             # (BDF_FORCE_COMM: a ONE-rank communicator all the same -- the exchange's kernels then run between the row launches
             # of a single-GPU run: the soak of the schedule with RCCL on the device, tools/soak_determinism.py rccl)
             self.comm = make_comm(self.ctx, self.rank, self.world)
-            check(lib().bdf_gibbs_set_comm(self.gibbs, self.comm.handle))
+            check(lib().bdf_gibbs_set_comm(self._gibbs, self.comm.handle))
         self._register_relations()
 
     def _register_relations(self):
-        """(native iteration) the relations with a model of their own -- alpha sampled, relation-level side information: the
-        library runs sample_alpha / sample_beta_rel / linear_values before the rows of every iteration (macau.jl:83-92)"""
-        if not self.gibbs:
-            return
+        """the relations with a model of their own -- alpha sampled, relation-level side information, a noise model: the library
+        steps them before the rows of every iteration (macau.jl:83-92) and makes their row terms"""
         from ._lib import GibbsRelation
         rows = [(ri, r, dr) for ri, (r, dr) in enumerate(zip(self.data.relations, self.rel)) if dr.has_model]
         arr = (GibbsRelation * max(len(rows), 1))()
@@ -1300,7 +1287,7 @@ class GibbsEngine:
                 if ri == 0 and dr.F_test is not None:
                     g.feat_test, g.test_baseline = dr.F_test.handle, dr.test_baseline.data_ptr()
         self._gibbs_relations = arr            # (the library copies the records; the tensors they point at live in self.rel)
-        check(lib().bdf_gibbs_set_relations(self.gibbs, len(rows), C.cast(arr, C.c_void_p)))
+        check(lib().bdf_gibbs_set_relations(self._gibbs, len(rows), C.cast(arr, C.c_void_p)))
 
     def begin_scores(self):
         """top-K lists of the first relation (setRecommend): the sum of u.v over the draws for the scored rows,
@@ -1380,12 +1367,6 @@ class GibbsEngine:
                 check(lib().bdf_gibbs_current(self.gibbs, j, C.byref(cur)))
                 st.cur = cur.value
 
-    def set_alpha(self):
-        """(native iteration) the relations' precisions are launch arguments held by the bdf_gibbs object: rebuild it after
-        setPrecision! on an initialised model"""
-        if self.gibbs:
-            raise ArgumentError("change the precision before the engine is built")
-
     def k1_algorithmic_bytes(self, j):
         """bytes one K1 launch over all rows of entity j must move, summed over its relations:
         nnz*((4 + 8D)*(n_modes-1) + 8) + N*(8D + 8) [+ N*8D per-row prior mean] + 8D^2 + 8D"""
@@ -1405,11 +1386,10 @@ class GibbsEngine:
         return f
 
     def sample_written(self, j):
-        """(native iteration) the caller has written entity j's sample itself, after sync(): K1c's gather image of it is stale and
-        the next launch that gathers it packs a new one (bdf_gibbs_sample_written).  Without this call the rows of the opposite
-        entity would still be sampled from the sample as it was."""
-        if self.gibbs:
-            check(lib().bdf_gibbs_sample_written(self.gibbs, int(j)))
+        """the caller has written entity j's sample itself, after sync(): K1c's gather image of it is stale and the next launch
+        that gathers it packs a new one (bdf_gibbs_sample_written).  Without this call the rows of the opposite entity would
+        still be sampled from the sample as it was."""
+        check(lib().bdf_gibbs_sample_written(self._gibbs, int(j)))
 
     def rows_dispatch(self, j):
         """how the library dispatched entity j's latest row launch (Context.rows_dispatch); None before the first iteration"""
@@ -1447,196 +1427,46 @@ class GibbsEngine:
         return [x is r for x in self.data.relations].index(True)
 
     def _terms(self, j):
-        """entity j's row terms, as fill_terms() of csrc/bdf_gibbs.hip makes them for the native iteration -- but alpha is the host
-        scalar update_relations has read back (the native iteration's rows read alpha_dev)"""
-        en = self.data.entities[j]
-        terms = (Term * len(en.relations))()
-        n_bg = 0                          # (terms folded into the prior so far: background terms, and dense ones -- they share alpha_rows)
-        for t, r in enumerate(en.relations):
-            dr, term = self.rel[self._relation_index(r)], terms[t]
-            term.rel, term.mode, term.mean_value = dr.handle, en.modes[t] - 1, r.model.mean_value
-            term.alpha = 1.0 if dr.kind == "probit" else r.model.alpha
-            term.linear_values = dr.linear.data_ptr() if dr.linear is not None else None
-            term.alpha_dev = dr.alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
-            term.obs_precision = dr.omega.data_ptr() if dr.omega is not None else None
-            if dr.bg is not None:
-                # background cells: with weights the listed ones count with omega_k - c0 and the pseudo-residual through linear_values
-                # (set above); with unit weights with alpha (1 - c0) -- the host's product, or what _row_prior's fold left on the device
-                if dr.omega is None:
-                    term.alpha = r.model.alpha * (1.0 - dr.bg["weight"])
-                    if self.native and r.model.alpha_sample:
-                        term.alpha_dev = self.ent[j].bg_alpha_rows.data_ptr() + 8 * n_bg
-                n_bg += 1
-            elif dr.dense is not None:    # (no cell of it is listed: the term reads nothing)
-                n_bg += 1
-            for k, e2 in enumerate(r.entities):
-                term.factors[k] = self.ent[self._entity_index(e2)].sample.data_ptr()
+        """entity j's row terms as the library makes them for its next row launch (bdf_gibbs_terms; fill_terms() of
+        csrc/bdf_gibbs.hip), the factors at the current samples"""
+        terms = (Term * len(self.data.entities[j].relations))()
+        check(lib().bdf_gibbs_terms(self._gibbs, int(j), terms))
         return terms
+
+    def _row_prior(self, j):
+        """parity hook: the fold of entity j's background and dense terms into its prior, enqueued on the row stream
+        (bdf_gibbs_row_prior; row_prior() of csrc/bdf_gibbs.hip) -> the device addresses (mu, is_matrix, Lambda, pack) its next
+        row launch would take (pack None: none)"""
+        mu, Lam, pack, is_matrix = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(0)
+        check(lib().bdf_gibbs_row_prior(self._gibbs, int(j), int(self.ent[j].prior_pack_valid), C.byref(mu), C.byref(is_matrix), C.byref(Lam),
+                                        C.byref(pack)))
+        return mu, is_matrix.value, Lam, (pack if pack.value else None)
 
     # ---- macau.jl:83-92: relation models (alpha, relation-level beta) -----------------------------------------------
     def update_relations(self):
-        """the step-by-step twin of update_relations() in csrc/bdf_gibbs.hip: the same launches in the same order, on the main
-        stream before the latent rows of the sweep -- keep the two in step, line by line.  The one difference: alpha is a host
-        scalar of the step path's row terms (_terms), read back right after sample_alpha -- one device-to-host read per sweep, as
-        the reference's host loop does; the draws behind it read the device scalar like the native iteration's"""
-        L, R, D = lib(), self.ctx.handle, self.D
-        comm = self.comm.handle if (self.world > 1 and self.comm is not None) else None
-        for ri, (r, dr) in enumerate(zip(self.data.relations, self.rel)):
-            if not dr.has_model:
-                continue
-            m, tag, train = r.model, ri + 1, (dr.train.handle if dr.train is not None else None)
-            fac = _facs(self.factors_of(r))
-            wsse = _ptr(dr.wsse) if (dr.omega is not None and m.alpha_sample) else None
-            # dense: the holes | U, V and the PREVIOUS iteration's alpha, into R, before sample_alpha -- whose sum then runs over all cells
-            dn = dr.dense
-            if dn is not None and dn["holes"] is not None:
-                check(L.bdf_dense_impute(R, dn["holes"].handle, D, fac, m.alpha, _ptr(dr.alpha_dev), tag, _ptr(dn["R"]), r.data.dims[0],
-                                         r.data.dims[1], _ptr(dn["stats"])))
-            # robust: omega | U, V and the PREVIOUS iteration's alpha, before sample_alpha -- which then takes sum omega e^2
-            if dr.robust_nu > 0.0:
-                check(L.bdf_robust_draw(R, train, D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), dr.robust_nu, tag, _ptr(dr.omega), wsse))
-            # a noise precision per row of one entity: tau | U, V and the previous alpha at the same place; it leaves sum tau_j S_j
-            if dr.noise is not None:
-                check(L.bdf_entity_noise_draw(R, dr.handle, dr.noise["mode"] - 1, train, D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev),
-                                              dr.noise["shape"], dr.noise["rate"], tag, _ptr(dr.tau), _ptr(dr.omega), wsse))
-            if m.alpha_sample:
-                # err' err over this rank's block (the pairs carry linear_values as their baseline), summed over the ranks; known
-                # weights: sum w e^2 (the robust draw above has left its own)
-                sse = wsse if (dr.omega is not None or dn is not None) else C.c_void_p(dr.train.stats.data_ptr() + 8)
-                n = r.data.nnz()
-                if dr.bg is not None:
-                    # background cells: the sum of c e^2 over ALL N M cells from the listed ones, the two entities' sums and Gram matrices
-                    sse = _ptr(dr.wsse)
-                    for k, f in enumerate(self.factors_of(r)):
-                        check(L.bdf_hyper_sums(R, D, f.shape[0], _ptr(f), None, _ptr(dr.bg_sums[k, :D]), _ptr(dr.bg_sums[k, D:])))
-                    check(L.bdf_background_sse(R, train, D, fac, m.mean_value, _ptr(dr.bg_weights) if dr.bg_weights is not None else None,
-                                               dr.bg["value"], dr.bg["weight"], _ptr(dr.bg_sums[0, :D]), _ptr(dr.bg_sums[0, D:]),
-                                               _ptr(dr.bg_sums[1, :D]), _ptr(dr.bg_sums[1, D:]), r.data.dims[0], r.data.dims[1], sse))
-                    n = int(r.data.dims[0]) * int(r.data.dims[1])
-                elif dn is not None:
-                    # dense: the closed form over all N M cells from C = R V and the two entities' Gram matrices
-                    sse = _ptr(dr.wsse)
-                    f = self.factors_of(r)
-                    for k in (0, 1):
-                        check(L.bdf_hyper_sums(R, D, f[k].shape[0], _ptr(f[k]), None, _ptr(dn["sums"][k, :D]), _ptr(dn["sums"][k, D:])))
-                    check(L.bdf_dense_product(R, _ptr(dn["R"]), r.data.dims[0], r.data.dims[1], D, _ptr(f[1]), 0, _ptr(dn["C"][0])))
-                    check(L.bdf_dense_sse(R, D, r.data.dims[0], _ptr(f[0]), _ptr(dn["C"][0]), _ptr(dn["sums"][0, D:]), _ptr(dn["sums"][1, D:]),
-                                          dn["sum_r2"], _ptr(dn["stats"]), sse))
-                    n = int(r.data.dims[0]) * int(r.data.dims[1])
-                elif dr.omega is None:
-                    check(L.bdf_predict_sse(R, train, D, fac, m.mean_value, None, _ptr(dr.train.stats)))
-                elif dr.robust_nu == 0.0 and dr.noise is None:
-                    check(L.bdf_pairs_weighted_sse(R, train, D, fac, m.mean_value, _ptr(dr.omega), wsse))
-                if comm is not None:
-                    check(L.bdf_sum_ranks(R, comm, sse, 1))
-                check(L.bdf_sample_alpha(R, m.alpha_lambda0, m.alpha_nu0, n, sse, tag, _ptr(dr.alpha_dev)))
-                self.ctx.sync()
-                m.alpha = float(dr.alpha_dev.item())
-            # probit: z | U, V; the rows of this iteration then see linear_values = y - z with alpha = 1
-            if dr.kind == "probit":
-                check(L.bdf_probit_draw(R, train, D, fac, m.mean_value, tag, _ptr(dr.linear), None))
-            # Polya-Gamma: omega | U, V; the rows then see the pseudo-observation through linear_values, its precision omega
-            if dr.pg_model:
-                check(L.bdf_pg_draw(R, train, D, fac, m.mean_value, dr.pg_model, dr.pg_r, tag, _ptr(dr.omega), _ptr(dr.linear)))
-            # censored: z | U, V and the alpha just drawn; the rows then see linear_values = mean + y - z
-            if dr.censor is not None:
-                check(L.bdf_censored_draw(R, train, _ptr(dr.censor), D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), tag, _ptr(dr.linear), None))
-            # ordinal: the edges | U, V, alpha with z integrated out; it rewrites the bounds that the draw below reads
-            if dr.ordinal is not None:
-                check(L.bdf_ordinal_step(R, dr.ordinal.handle, train, _ptr(dr.ord_codes), D, fac, m.mean_value, 0.0, _ptr(dr.alpha_dev), tag, -1,
-                                         _ptr(dr.interval)))
-            # interval-censored: the same draw at the same place, between the two bounds of every bounded observation
-            if dr.interval is not None:
-                check(L.bdf_interval_draw(R, train, _ptr(dr.interval), D, fac, m.mean_value, m.alpha, _ptr(dr.alpha_dev), tag, _ptr(dr.linear), None))
-            if dr.F is not None:
-                check(L.bdf_sample_beta_rel_ranks(R, comm, dr.F.handle, train, dr.obs_lo, D, fac, m.mean_value, m.alpha, m.lambda_beta, tag,
-                                                  _ptr(dr.beta), C.c_void_p(dr.linear.data_ptr() + 8 * dr.obs_lo), None))
-                if comm is not None:         # every rank's row kernels read linear_values of their own rows' observations
-                    check(L.bdf_allgather_block(R, comm, _ptr(dr.linear), 8 * dr.obs_block))
-                    check(L.bdf_allgather_join(R, comm))
-                if ri == 0:
-                    self.refresh_baselines()
-
-    def _row_prior(self, j, mu, is_matrix, pack):
-        """The step-by-step twin of row_prior() in csrc/bdf_gibbs.hip: the (mu, Lambda, pack) entity j's rows are sampled with -- the
-        hyperprior's draw as given, or, when relations of the entity have background cells, that draw with their Gram terms folded
-        in.  Per background term, in the order of the entity's terms: the sum and the Gram matrix of the OTHER entity's current rows
-        into the relation's buffers (bdf_hyper_sums on the row stream), then one bdf_background_prior into the entity's buffers."""
-        en, st, D = self.data.entities[j], self.ent[j], self.D
-        bgs = [(t, r, self.rel[self._relation_index(r)]) for t, r in enumerate(en.relations)]
-        bgs = [(t, r, dr) for t, r, dr in bgs if dr.bg is not None or dr.dense is not None]
-        if not bgs:
-            return mu, is_matrix, st.Lambda, pack
-        if any(dr.dense is not None for _, _, dr in bgs):
-            # a dense relation among them (DESIGN.md section 25): per dense term also its rows of R V (R' U) from the other entity's
-            # current rows, then one bdf_dense_prior over the dense and the background terms; the means are then one per row
-            arr = (DenseTerm * len(bgs))()
-            for k, (t, r, dr) in enumerate(bgs):
-                mode = en.modes[t] - 1
-                so = self.ent[self._entity_index(r.entities[1 - mode])]
-                s = (dr.dense["sums"] if dr.dense is not None else dr.bg_sums)[1 - mode]
-                check(lib().bdf_hyper_sums(self.ctx.handle, D, so.N, _ptr(so.sample), None, _ptr(s[:D]), _ptr(s[D:])))
-                arr[k].gram = s.data_ptr() + 8 * D
-                arr[k].alpha = r.model.alpha
-                arr[k].alpha_dev = dr.alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
-                if dr.dense is not None:
-                    check(lib().bdf_dense_product(self.ctx.handle, _ptr(dr.dense["R"]), r.data.dims[0], r.data.dims[1], D, _ptr(so.sample), mode,
-                                                  _ptr(dr.dense["C"][mode])))
-                    arr[k].C, arr[k].weight = dr.dense["C"][mode].data_ptr(), 1.0
-                else:
-                    arr[k].sum, arr[k].weight, arr[k].resid = s.data_ptr(), dr.bg["weight"], dr.bg["value"] - r.model.mean_value
-            check(lib().bdf_dense_prior(self.ctx.handle, D, st.N, len(bgs), arr, _ptr(mu), is_matrix, _ptr(st.Lambda), _ptr(st.bg_Lambda),
-                                        _ptr(st.bg_mu), _ptr(st.bg_alpha_rows)))
-            return st.bg_mu, 1, st.bg_Lambda, None
-        arr = (BackgroundTerm * len(bgs))()
-        for k, (t, r, dr) in enumerate(bgs):
-            other = 1 - (en.modes[t] - 1)
-            so = self.ent[self._entity_index(r.entities[other])]
-            s = dr.bg_sums[other]
-            check(lib().bdf_hyper_sums(self.ctx.handle, D, so.N, _ptr(so.sample), None, _ptr(s[:D]), _ptr(s[D:])))
-            arr[k].sum, arr[k].gram = s.data_ptr(), s.data_ptr() + 8 * D
-            arr[k].alpha = r.model.alpha
-            arr[k].alpha_dev = dr.alpha_dev.data_ptr() if (self.native and r.model.alpha_sample) else None
-            arr[k].weight, arr[k].resid = dr.bg["weight"], dr.bg["value"] - r.model.mean_value
-        check(lib().bdf_background_prior(self.ctx.handle, D, st.N, len(bgs), arr, _ptr(mu), is_matrix, _ptr(st.Lambda), _ptr(st.bg_Lambda),
-                                         _ptr(st.bg_mu), None if is_matrix else _ptr(st.bg_pack), _ptr(st.bg_alpha_rows)))
-        return st.bg_mu, is_matrix, st.bg_Lambda, (None if is_matrix else st.bg_pack)
+        """(step by step) what the relations' models run before the latent rows of the sweep, on the main stream
+        (bdf_gibbs_step_relations), then one device-to-host read per sweep: a sampled alpha as the host scalar that the reporting
+        steps on other streams take (driver.py), as the reference's host loop has it"""
+        check(lib().bdf_gibbs_step_relations(self._gibbs))
+        if any(r.model.alpha_sample for r in self.data.relations):
+            self.ctx.sync()
+            for r, dr in zip(self.data.relations, self.rel):
+                if r.model.alpha_sample:
+                    r.model.alpha = float(dr.alpha_dev.item())
 
     # ---- macau.jl:96-117: latent rows of entity j --------------------------------------------------------------
     def sample_entity(self, j):
-        en, st = self.data.entities[j], self.ent[j]
-        if not en.relations:
-            raise ArgumentError(f"Entity {en.name} takes part in no relation")
-        terms = self._terms(j)
-        if st.spike is not None:
-            # the spike-and-slab prior: every row by the coordinate sweep from its current value, into the next buffer
-            check(lib().bdf_sample_rows_spike(self.ctx.handle, self.D, st.N, len(terms), terms, _ptr(st.spike_state), _ptr(st.sample),
-                                              st.tag, 0, 1, _ptr(st.sample_next)))
-            st.rotate()
-            return
-        mu, is_matrix = st.mu, 0
-        if st.F is not None:
-            check(lib().bdf_uhat(self.ctx.handle, st.F.handle, self.D, _ptr(st.beta), _ptr(st.mu), _ptr(st.uhat), _ptr(st.mu_matrix)))
-            mu, is_matrix = st.mu_matrix, 1
+        """entity j's rows into its next buffer, which then becomes the current one (bdf_gibbs_step_rows: uhat, the prior, the row
+        launch chunk by chunk and, several ranks, every chunk's exchange) -- the step-by-step path's row step, and a launch by
+        itself for the probes, under the iteration number the caller has set (ctx.set_sweep)"""
+        st = self.ent[j]
         timed = self.k1_events is not None and self._k1_sweep % self.k1_event_every == 0
         if timed:
             timer = KernelTimer()
             check(lib().bdf_ctx_time_next_rows(self.ctx.handle, timer.start, timer.stop))
-        pack = st.prior_pack if (st.prior_pack_valid and not is_matrix) else None
-        mu, is_matrix, Lam, pack = self._row_prior(j, mu, is_matrix, pack)
-        # written into the entity's next buffer (nothing this launch reads), which then becomes the current one; several ranks:
-        # chunk after chunk, every chunk exchanged in place while the next one is sampled
-        nch = st.layout.chunks
-        for c in range(nch):
-            check(lib().bdf_sample_rows(self.ctx.handle, self.D, st.N, len(terms), terms, _ptr(mu), is_matrix, _ptr(Lam),
-                                        st.tag, c, nch, _ptr(st.sample_next), _ptr(pack) if pack is not None else None))
-            if self.comm is not None:
-                check(lib().bdf_allgather_rows(self.ctx.handle, self.comm.handle, self.D, st.N, _ptr(st.sample_next), c, nch))
-        if self.comm is not None:
-            check(lib().bdf_allgather_join(self.ctx.handle, self.comm.handle))
-        st.rotate()
-        if timed:
             self.k1_events.append((j, timer))
+        check(lib().bdf_gibbs_step_rows(self._gibbs, int(j), int(st.prior_pack_valid)))
+        st.rotate()
 
     # ---- macau.jl:119-134: hyperprior of entity j ----------------------------------------------------------------
     def _hyper_nu(self, j):
@@ -1881,15 +1711,8 @@ class GibbsEngine:
                 dr.F_test = FeatOperator(self.ctx, r.test_F if subset is None else _take_rows(r.test_F, np.asarray(subset)))
                 dr.test_baseline = self.ctx.zeros(self._test_pairs.n)
                 check(lib().bdf_pairs_set_baseline(self._test_pairs.handle, _ptr(dr.test_baseline)))
-                self._register_relations()          # (native iteration: the library refreshes the baseline after every relation beta)
+                self._register_relations()          # (the library refreshes the baseline after every relation beta)
         return self._test_pairs
-
-    def refresh_baselines(self):
-        """after the relation beta of this sweep: the test pairs' baseline mean_value + F_test beta (first relation)"""
-        dr = self.rel[0]
-        if dr.F is not None and self._test_pairs is not None:
-            r = self.data.relations[0]
-            check(lib().bdf_feat_linear(self.ctx.handle, dr.F_test.handle, _ptr(dr.beta), r.model.mean_value, _ptr(dr.test_baseline)))
 
     def new_rows(self, fresh=False):
         """the first relation's cells of new rows (setNewTest) on the device, built at first use; fresh: built again, with no state"""
@@ -1923,15 +1746,11 @@ class GibbsEngine:
                 st.F.close()
         for dr in self.rel:
             dr.close()
-        if self.gibbs:
-            lib().bdf_gibbs_destroy(self.gibbs)          # (and its two contexts)
-            self.gibbs = None
-            self.ctx_h.handle = self.ctx_p.handle = C.c_void_p()
-        else:
-            if self.ctx_p is not self.ctx:
-                self.ctx_p.close()
-            if self.ctx_h is not self.ctx:
-                self.ctx_h.close()
+        for side in (self.ctx_p, self.ctx_h):            # (what lives on them; the contexts themselves are the bdf_gibbs object's)
+            if side is not self.ctx:
+                side.close()
+        lib().bdf_gibbs_destroy(self._gibbs)
+        self._gibbs = self.gibbs = None
         if self.comm is not None:
             self.comm.close()
             self.comm = None

@@ -1042,6 +1042,22 @@ int bdf_gibbs_current(const bdf_gibbs *g, int entity, int *buffer);
 /* measurement: the row launch of one entity as bdf_gibbs_sweep makes it, and nothing else (no hyperprior update, exchange or
  * prediction update: the chain's state is not kept consistent) */
 int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep);
+/* The iteration piece by piece, for a host that keeps the schedule itself and enqueues the hyperpriors, beta and the prediction
+ * update through the entry points above: the same code bdf_gibbs_sweep runs, on the row stream with plain stream order (no events,
+ * no polling, no done counters) under the iteration number the caller has set with bdf_ctx_set_sweep.
+ * bdf_gibbs_step_relations: what the registered relations' models run before the rows (bdf_gibbs_set_relations).
+ * bdf_gibbs_step_rows: one entity's rows -- uhat and the per-row prior means with side information, the prior with the background
+ * and dense terms folded in, the row launch chunk by chunk, with a communicator every chunk's exchange -- after which the entity's
+ * buffers have rotated (bdf_gibbs_current).  pack_valid: the entity's latest hyperprior draw (bdf_hyper_sample) has left its prior
+ * pack; 0 before the first draw.  The context's bdf_ctx_time_next_rows events go to the row launch. */
+int bdf_gibbs_step_relations(bdf_gibbs *g);
+int bdf_gibbs_step_rows(bdf_gibbs *g, int entity, int pack_valid);
+/* parity hooks: the terms (entity's n_terms of them, the factors at the current samples) and the prior that the entity's next row
+ * launch would take.  bdf_gibbs_row_prior enqueues the fold of the background and dense terms on the row stream and hands back
+ * device pointers: the prior mean (one, or one per row: *mu_is_matrix), Lambda and the prior pack (NULL: none). */
+int bdf_gibbs_terms(bdf_gibbs *g, int entity, bdf_term *out);
+int bdf_gibbs_row_prior(bdf_gibbs *g, int entity, int pack_valid, const double **mu, int *mu_is_matrix, const double **Lambda,
+                        const double **pack);
 /* set-up: brings the device to its working state without advancing the chain.  Full iterations (rows of every entity,
  * hyperprior chains, beta, the prediction kernel on the registered test pairs WITHOUT running state) with iteration numbers
  * no real iteration uses, for about `milliseconds` (with a communicator: milliseconds / 0.1 iterations, the same count on

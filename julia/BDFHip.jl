@@ -359,6 +359,26 @@ function current_buffer(g::Gibbs, entity::Integer)
     check(ccall((:bdf_gibbs_current, lib), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), g.h, entity - 1, b))
     return b[] + 1
 end
+"""the iteration piece by piece, for a host that keeps the schedule itself (hyperpriors, beta and the prediction update through the
+entry points above): what the registered relations' models run before the rows, then one entity's rows -- uhat, the prior with the
+background and dense terms folded in, the row launch, with a communicator the exchange -- on the row stream with plain stream
+order, under the iteration number set with `set_sweep!`.  `pack_valid`: the entity's latest `update_prior!` has left its prior pack"""
+step_relations!(g::Gibbs) = check(ccall((:bdf_gibbs_step_relations, lib), Cint, (Ptr{Cvoid},), g.h))
+step_rows!(g::Gibbs, entity::Integer, pack_valid::Bool) =
+    check(ccall((:bdf_gibbs_step_rows, lib), Cint, (Ptr{Cvoid}, Cint, Cint), g.h, entity - 1, pack_valid))
+"parity hook: the `n_terms` terms the entity's next row launch would take, the factors at the current samples"
+function row_terms(g::Gibbs, entity::Integer, n_terms::Integer)
+    terms = Vector{Term}(undef, n_terms)
+    check(ccall((:bdf_gibbs_terms, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Term}), g.h, entity - 1, terms))
+    return terms
+end
+"parity hook: enqueues the fold of the entity's background and dense terms -> device pointers (mu, mu_is_matrix, Lambda, pack or C_NULL)"
+function row_prior!(g::Gibbs, entity::Integer, pack_valid::Bool)
+    mu = Ref{Ptr{Cvoid}}(C_NULL); Lambda = Ref{Ptr{Cvoid}}(C_NULL); pack = Ref{Ptr{Cvoid}}(C_NULL); is_matrix = Ref{Cint}(0)
+    check(ccall((:bdf_gibbs_row_prior, lib), Cint, (Ptr{Cvoid}, Cint, Cint, Ref{Ptr{Cvoid}}, Ref{Cint}, Ref{Ptr{Cvoid}}, Ref{Ptr{Cvoid}}),
+                g.h, entity - 1, pack_valid, mu, is_matrix, Lambda, pack))
+    return mu[], is_matrix[] != 0, Lambda[], pack[]
+end
 set_test!(g::Gibbs, pairs::Ptr{Cvoid}, entity_of_mode::Vector{Int32}, mean_value, clamp_lo, clamp_hi, class_cut, stats::DevArray) =
     check(ccall((:bdf_gibbs_set_test, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Int32}, Float64, Float64, Float64, Float64, Ptr{Cvoid}),
                 g.h, pairs, entity_of_mode, mean_value, clamp_lo, clamp_hi, class_cut, stats.p))

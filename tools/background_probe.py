@@ -153,11 +153,11 @@ def main():
         s = dr.bg_sums[1 - j]
         parts[f"sums_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_hyper_sums(
             ctx.handle, D, so.N, p(so.sample), None, p(s[:D]), p(s[D:])))), 2)
-        parts[f"sums_and_fold_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: eng._row_prior(j, st.mu, 0, None)), 2)
-        mu, _, Lam, pack = eng._row_prior(j, st.mu, 0, None)
+        parts[f"sums_and_fold_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: eng._row_prior(j)), 2)
+        mu, _, Lam, pack = eng._row_prior(j)             # (device addresses)
         terms, nxt = eng._terms(j), ctx.zeros(st.N, D)
         parts[f"rows_{en.name}_folded_prior_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_sample_rows(
-            ctx.handle, D, st.N, 1, terms, p(mu), 0, p(Lam), 900 + j, 0, 1, p(nxt), p(pack)))), 2)
+            ctx.handle, D, st.N, 1, terms, mu, 0, Lam, 900 + j, 0, 1, p(nxt), pack))), 2)
         pst, pterms = plain.ent[j], plain._terms(j)
         parts[f"rows_{en.name}_plain_prior_us"] = round(timed(torch, plain.ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_sample_rows(
             plain.ctx.handle, D, pst.N, 1, pterms, p(pst.mu), 0, p(pst.Lambda), 900 + j, 0, 1, p(nxt), p(pst.prior_pack)))), 2)

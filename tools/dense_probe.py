@@ -116,11 +116,11 @@ def main():
             ctx.handle, p(dn["R"]), N, M, D, p(so.sample), j, p(dn["C"][j]))))
         parts[f"product_for_{en.name}_us"] = round(us, 2)
         parts[f"product_for_{en.name}_GBps"] = round(8.0 * N * M / us / 1e3, 1)
-        parts[f"gram_product_prior_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: eng._row_prior(j, st.mu, 0, None)), 2)
-        mu, is_matrix, Lam, pack = eng._row_prior(j, st.mu, 0, None)
+        parts[f"gram_product_prior_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: eng._row_prior(j)), 2)
+        mu, is_matrix, Lam, pack = eng._row_prior(j)     # (device addresses)
         terms, nxt = eng._terms(j), ctx.zeros(st.N, D)
         parts[f"rows_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_sample_rows(
-            ctx.handle, D, st.N, 1, terms, p(mu), is_matrix, p(Lam), 900 + j, 0, 1, p(nxt), None))), 2)
+            ctx.handle, D, st.N, 1, terms, mu, is_matrix, Lam, 900 + j, 0, 1, p(nxt), None))), 2)
     print(json.dumps(parts), flush=True)
     for e in engines.values():
         e.close()
