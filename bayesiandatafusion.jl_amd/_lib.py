@@ -300,6 +300,9 @@ _SIGS = {
     "bdf_gibbs_rows_only": (C.c_int, [C.c_void_p, C.c_int, C.c_uint32]),
     "bdf_gibbs_step_relations": (C.c_int, [C.c_void_p]),
     "bdf_gibbs_step_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "bdf_gibbs_step_draws": (C.c_int, [C.c_void_p, C.c_int]),
+    "bdf_gibbs_step_hyper": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "bdf_gibbs_step_beta": (C.c_int, [C.c_void_p, C.c_int]),
     "bdf_gibbs_terms": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Term)]),
     "bdf_gibbs_row_prior": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_void_p),
                                       C.POINTER(C.c_void_p)]),

@@ -2,7 +2,7 @@
 // entity (sample_latent_all2! / sample_user2_all!, src/sampling.jl:149-289), the exchange of the sampled rows between GPUs,
 // every entity's hyperprior (src/sampling.jl:116-127, src/normal_wishart.jl:38-42) and the test-set prediction update
 // (macau.jl:142-184), with the beta update and the per-row prior means of side information and the relations' own models.  The
-// same pieces can be enqueued one by one, with plain stream order: bdf_gibbs_step_relations, bdf_gibbs_step_rows.
+// same pieces can be enqueued one by one, with plain stream order: bdf_gibbs_step_relations, _rows, _draws, _hyper, _beta.
 //
 // Three HIP streams: rows | hyperpriors | prediction updates.  The hyperprior of entity j runs beside the rows of entity
 // j+1, the prediction update of sweep t beside the rows of sweep t+1 (every entity's rows rotate through three buffers).
@@ -26,6 +26,7 @@
 struct bdf_gibbs {
     bdf_ctx *rows, *hyper, *pred;        // rows: the caller's context; hyper / pred: owned (own streams)
     bdf_ctx *gate = nullptr;             // owned, with polling: a second stream on the reserved CUs for the one-wave gate in front of the prediction update
+    bdf_ctx *step_hyper = nullptr;       // where bdf_gibbs_step_draws / _hyper enqueue: hyper, or -- BDF_NO_OVERLAP, one stream for everything -- rows
     int D;
     struct Ent {
         bdf_gibbs_entity d;
@@ -284,6 +285,7 @@ extern "C" int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const 
     g->debug = false; g->host_wait_us = g->host_enqueue_us = 0.0; g->n_sweeps = 0;
     int rc;
     if ((rc = make_side_ctx(rows_ctx, {}, true, &g->hyper)) || (rc = make_side_ctx(rows_ctx, {g->hyper}, false, &g->pred))) { bdf_gibbs_destroy(g); return rc; }
+    g->step_hyper = getenv("BDF_NO_OVERLAP") ? g->rows : g->hyper;
     g->ready_dev = nullptr;
     g->polling = rows_ctx->reserve_cus > 0 && g->hyper->on_reserved && !getenv("BDF_NO_POLL");
     if (g->polling) {
@@ -699,31 +701,99 @@ namespace {
 // the hyperprior's degrees of freedom: nu0 (+ numF with side information and full_lambda_u, macau.jl:124-129)
 double hyper_nu(const bdf_gibbs_entity &e) { return e.nu0 + ((e.feat && e.full_lambda_u) ? (double)e.feat->n : 0.0); }
 
-// The row launch of entity E as bdf_gibbs_sweep makes it (same prior, same terms, same kernel variant), enqueued with plain stream
-// order: no events, no polling, no done counter, and the context's timing fields are the caller's.  exchange: with a communicator,
-// every chunk's rows to the other ranks.
-int launch_rows(bdf_gibbs *g, bdf_gibbs::Ent &E, bool pack_valid, bool exchange)
+// What bdf_gibbs_sweep hangs on an entity's row launch.  All empty (the step entry points, bdf_gibbs_rows_only): plain stream order --
+// no events, no polling, no done counter, and the context's timing fields and span slot are the caller's.
+struct RowsExtras {
+    const uint32_t *poll; uint32_t poll_want;      // the launch's waves poll this word for poll_want where they first need the prior
+    uint32_t *counter;                   // the waves add to these 64 words when their rows are in memory (SampleArgs::done)
+    hipEvent_t start, stop;              // on the first chunk's dispatch | on the last chunk's
+    unsigned long long *span;            // SampleArgs::span
+    hipEvent_t joined;                   // a communicator: recorded behind the join of the last chunk's exchange
+};
+
+// The row launch of entity E, the only one: the prior (row_prior), the terms (fill_terms), the kernel variant chunk by chunk and, with
+// a communicator and `exchange`, every chunk's rows to the other ranks; the entity's next buffer then becomes the current one.
+// *by_counter (nullable): the launch hands over through x.counter (a launch that takes another kernel than k_rows_col reports
+// rows_done_added < 0: the caller uses an event after all); E.done_target then counts its waves in.
+int launch_rows(bdf_gibbs *g, bdf_gibbs::Ent &E, bool pack_valid, bool exchange, const RowsExtras &x, bool *by_counter)
 {
     bdf_ctx *R = g->rows;
     const bdf_gibbs_entity &e = E.d;
     int rc;
+    // the prior of this launch: the draw's (mu, Lambda) and pack, or -- background cells -- those with the Gram terms folded in
     const double *mu = nullptr, *Lambda = nullptr, *pack = nullptr;
     int is_matrix = 0;
     if (!e.spike && (rc = row_prior(g, E, pack_valid, &mu, &is_matrix, &Lambda, &pack))) return rc;
     bdf_term terms[BDF_MAX_TERMS];
     fill_terms(g, e, terms);
-    const int nxt = (E.cur + 1) % 3, nch = e.terms[0].rel->chunks;
+    const int nxt = (E.cur + 1) % 3, nch = e.terms[0].rel->chunks;     // 1 unless the relations were created with a layout
     exchange = exchange && g->comm;
+    if (by_counter) *by_counter = false;
     for (int c = 0; c < nch; c++) {
-        R->gimg_trust = !g->comm;             // (as in bdf_gibbs_sweep)
+        if (x.start || x.stop) { R->time_start = (c == 0) ? x.start : nullptr; R->time_stop = (c == nch - 1) ? x.stop : nullptr; }
+        if (x.span) R->rows_span = x.span;
+        if (x.poll) { R->rows_ready = x.poll; R->rows_ready_want = x.poll_want; }
+        if (x.counter) R->rows_done = x.counter;
+        R->gimg_trust = !g->comm;         // (the chain's own buffers: sample_written() hears of every other writer)
         if ((rc = e.spike ? bdf_sample_rows_spike(R, g->D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
                           : bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, is_matrix, Lambda, e.tag, c, nch, e.sample[nxt], pack)))
             return rc;
+        if (x.counter && R->rows_done_added >= 0) { if (by_counter) *by_counter = true; E.done_target += (uint32_t)R->rows_done_added; }
         if (exchange && (rc = bdf_allgather_rows(R, g->comm, g->D, e.N, e.sample[nxt], c, nch))) return rc;
     }
-    if (exchange && (rc = bdf_allgather_join(R, g->comm))) return rc;
+    if (exchange) {
+        if ((rc = bdf_allgather_join(R, g->comm))) return rc;           // the row stream continues after the last chunk's exchange
+        if (x.joined) BDF_HIP(hipEventRecord(x.joined, R->stream));
+    }
     E.cur = nxt;
     return BDF_OK;
+}
+
+// What only bdf_gibbs_sweep sets on the hyperprior context before the calls of hyper_step.  All empty (bdf_gibbs_step_hyper): the
+// unfused sums, then the draw kernel, in plain stream order.
+struct HyperExtras {
+    bool fuse;                           // small entities: the sums and the draw in one launch (k_hyper_chain)
+    double *chain_draws;                 // ... which also makes the entity's random part into this buffer
+    hipEvent_t stop;                     // on the draw's dispatch
+    uint32_t *ready; uint32_t ready_value;         // the draw sets this word to ready_value once its pack is written
+    const uint32_t *wait; uint32_t wait_target;    // the chain's partial-sum workgroups poll the sum of these 64 words for wait_target
+};
+
+// The hyperprior step of entity E on context H from its current rows, the only one: the spike-and-slab prior's hyper step -- or the
+// feature terms, the sums (one rank or several) and the Normal-Wishart draw.  draws: the data-independent part made ahead
+// (bdf_hyper_draws into e.draws), or NULL: the draw makes its own normals.  It touches no event and none of E's bookkeeping.
+int hyper_step(bdf_gibbs *g, const bdf_gibbs::Ent &E, bdf_ctx *H, const double *draws, const HyperExtras &x)
+{
+    const bdf_gibbs_entity &e = E.d;
+    const int D = g->D;
+    int rc;
+    // the spike-and-slab prior's hyper step in place of the sums and the Normal-Wishart draw
+    if (e.spike) return bdf_spike_hyper(H, D, e.n_real, e.sample[E.cur], e.spike_a, e.spike_b, e.spike_shape, e.spike_rate, e.tag, e.spike_state);
+    if (x.wait) { H->hyper_wait = x.wait; H->hyper_wait_target = x.wait_target; }
+    if (x.fuse) H->hyper_fuse = true;
+    // side information: U = sample - uhat, T^-1 = WI + beta' beta lambda_beta with the beta of the previous iteration
+    const double *Tinv = e.WI;
+    if (e.feat && e.full_lambda_u) {
+        if ((rc = bdf_hyper_feature_terms(H, D, e.feat->n, e.beta, e.WI, e.lambda_beta, e.Tinv))) return rc;
+        Tinv = e.Tinv;
+    }
+    // (several ranks: every rank sums its own rows, the D + D^2 partial sums are added over the ranks in rank order)
+    if ((rc = g->comm ? bdf_hyper_sums_ranks(H, g->comm, D, e.N, e.terms[0].rel->chunks, e.sample[E.cur], e.feat ? e.uhat : nullptr, e.sumU, e.UUt)
+                      : bdf_hyper_sums(H, D, e.N, e.sample[E.cur], e.feat ? e.uhat : nullptr, e.sumU, e.UUt)))
+        return rc;
+    if (x.chain_draws) H->hyper_chain_draws = x.chain_draws;
+    if (x.stop) H->time_h_stop = x.stop;
+    if (x.ready) { H->hyper_ready = x.ready; H->hyper_ready_value = x.ready_value; }
+    return bdf_hyper_sample(H, D, e.n_real, e.sumU, e.UUt, e.mu0, e.b0, Tinv, hyper_nu(e), e.tag, e.mu, e.Lambda, e.params, e.prior_pack, draws);
+}
+
+// side information: beta of entity E from its current rows and (mu, Lambda), on the row stream (macau.jl:138-140)
+// (several ranks: the conjugate-gradient columns are shared out over them and all-gathered, parallel_matrix.jl:488-507)
+int beta_step(bdf_gibbs *g, const bdf_gibbs::Ent &E)
+{
+    const bdf_gibbs_entity &e = E.d;
+    return bdf_sample_beta_ranks(g->rows, g->comm, e.feat, g->D, e.sample[E.cur], e.mu, e.Lambda, e.lambda_beta, e.use_ff, e.tol, 0,
+                                 e.sample_lambda_beta, e.lb_nu, e.lb_mu, e.tag, e.beta, nullptr, e.cg_iters);
 }
 }  // namespace
 
@@ -734,12 +804,14 @@ extern "C" int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep)
     BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_rows_only: bad argument");
     g->rows->sweep_host = sweep;
     auto &E = g->ent[(size_t)entity];
-    return launch_rows(g, E, E.hyper_recorded, false);
+    return launch_rows(g, E, E.hyper_recorded, false, {}, nullptr);
 }
 
-// The iteration piece by piece, for a host that keeps the schedule itself (hyperpriors, beta and the prediction update through the
-// entry points of bdf.h): what runs before the rows, and one entity's rows.  Both on the row stream under the iteration number the
-// caller has set (bdf_ctx_set_sweep).
+// The iteration piece by piece, for a host that keeps the schedule itself (and the prediction update through the entry points of
+// bdf.h): what runs before the rows, one entity's rows, the data-independent part of its hyperprior draw, its hyperprior step, its
+// beta.  The pieces bdf_gibbs_sweep composes, in plain stream order under the iteration number the caller has set on the contexts
+// (bdf_ctx_set_sweep): no events, and nothing of the object's bookkeeping changes but the rows' buffer rotation.  Relations, rows and
+// beta on the row stream; draws and hyperprior on the hyperprior context's (BDF_NO_OVERLAP: on the row context too).
 extern "C" int bdf_gibbs_step_relations(bdf_gibbs *g)
 {
     BDF_REQUIRE(g, BDF_ERR_ARG, "bdf_gibbs_step_relations: NULL argument");
@@ -754,7 +826,29 @@ extern "C" int bdf_gibbs_step_rows(bdf_gibbs *g, int entity, int pack_valid)
     int rc;
     // side information: uhat = (F beta)' with the beta of the previous iteration, per-row prior means mu + uhat (macau.jl:103-104)
     if (e.feat && (rc = bdf_uhat(g->rows, e.feat, g->D, e.beta, e.mu, e.uhat, e.mu_matrix))) return rc;
-    return launch_rows(g, E, pack_valid != 0, true);
+    return launch_rows(g, E, pack_valid != 0, true, {}, nullptr);
+}
+
+extern "C" int bdf_gibbs_step_draws(bdf_gibbs *g, int entity)
+{
+    BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_step_draws: bad argument");
+    const bdf_gibbs_entity &e = g->ent[(size_t)entity].d;
+    // (the spike-and-slab prior's hyper step draws from the rows' counts: nothing to prepare)
+    return e.spike ? BDF_OK : bdf_hyper_draws(g->step_hyper, g->D, e.n_real, hyper_nu(e), e.tag, e.draws);
+}
+
+extern "C" int bdf_gibbs_step_hyper(bdf_gibbs *g, int entity, int draws_prepared)
+{
+    BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_step_hyper: bad argument");
+    const auto &E = g->ent[(size_t)entity];
+    return hyper_step(g, E, g->step_hyper, draws_prepared ? E.d.draws : nullptr, {});
+}
+
+extern "C" int bdf_gibbs_step_beta(bdf_gibbs *g, int entity)
+{
+    BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_step_beta: bad argument");
+    const auto &E = g->ent[(size_t)entity];
+    return E.d.feat ? beta_step(g, E) : BDF_OK;
 }
 
 // parity hooks: the terms and the prior that the entity's next row launch would take
@@ -943,25 +1037,20 @@ extern "C" int bdf_gibbs_current(const bdf_gibbs *g, int entity, int *buffer)
     return BDF_OK;
 }
 
-extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
+namespace {
+// The row kernels of the NEXT sweep overwrite the buffers that held the rows of sweep - 2, which the prediction update of
+// sweep - 2 reads.  The HOST waits here until an update of some sweeps ago has completed (normally it has, long ago): the
+// device then needs no wait for the prediction stream anywhere, and the host never runs more than a few prediction updates
+// ahead.  (A device-side wait would let row kernels that poll for their prior fill the chip while the prediction kernel
+// they transitively wait for still needs slots for its last workgroups.)
+// (Whether or not THIS iteration has a prediction update: an update enqueued two or more iterations ago must have
+// completed -- iterations without one rotate the buffers all the same.)
+// How many iterations back: 3 -- the most the three buffers allow: iteration s overwrites the rows of iteration s - 3, which the
+// prediction update of s - 3 read.  (Until round 3: 2.  On a quiet host there is no difference; with 3 an enqueue that takes
+// 50 us instead of 23, or a late wake-up, no longer leaves the row stream dry.)
+int await_old_predictions(bdf_gibbs *g)
 {
-    BDF_REQUIRE(g, BDF_ERR_ARG, "bdf_gibbs_sweep: NULL argument");
-    bdf_ctx *R = g->rows, *H = g->hyper, *P = g->pred;
-    const int D = g->D, n = (int)g->ent.size();
-    int rc;
-    R->sweep_host = H->sweep_host = P->sweep_host = sweep;
-    // The row kernels of the NEXT sweep overwrite the buffers that held the rows of sweep - 2, which the prediction update of
-    // sweep - 2 reads.  The HOST waits here until an update of some sweeps ago has completed (normally it has, long ago): the
-    // device then needs no wait for the prediction stream anywhere, and the host never runs more than a few prediction updates
-    // ahead.  (A device-side wait would let row kernels that poll for their prior fill the chip while the prediction kernel
-    // they transitively wait for still needs slots for its last workgroups.)
-    // (Whether or not THIS iteration has a prediction update: an update enqueued two or more iterations ago must have
-    // completed -- iterations without one rotate the buffers all the same.)
-    // How many iterations back: 3 -- the most the three buffers allow: iteration s overwrites the rows of iteration s - 3, which the
-    // prediction update of s - 3 read.  (Until round 3: 2.  On a quiet host there is no difference; with 3 an enqueue that takes
-    // 50 us instead of 23, or a late wake-up, no longer leaves the row stream dry.)
     constexpr uint64_t pred_lag = 3;
-    const auto t_in = std::chrono::steady_clock::now();
     for (uint64_t back = 1; back <= std::min<uint64_t>(g->n_pred, 3); back++) {
         const uint64_t k = (g->n_pred - back) % 3;
         if (g->pred_at[k] + pred_lag <= g->n_iter) {          // (and with it the earlier ones)
@@ -977,22 +1066,80 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
             break;
         }
     }
-    const auto t_go = std::chrono::steady_clock::now();
-    // the data-independent part of every entity's hyperprior draw (Bartlett matrix, mean normals): inside the entity's chain
-    // launch, beside its partial sums, when every entity is small enough for the one-launch chain (the hyperprior stream is
-    // busy ~85 of an iteration's 90 us: a launch of its own at the head of the iteration is 7 us of that); else ahead of the rows
-    bool draws_in_chain = !g->comm;      // (several ranks: the sums are not the chain's, bdf_hyper_sums_ranks)
-    for (int j = 0; j < n; j++) draws_in_chain = draws_in_chain && g->ent[(size_t)j].d.N <= 16384;
-    if (!draws_in_chain && n <= BDF_DRAWS_BATCH) {
-        int64_t Ns[BDF_DRAWS_BATCH]; double nus[BDF_DRAWS_BATCH]; uint32_t tags[BDF_DRAWS_BATCH]; double *outs[BDF_DRAWS_BATCH];
-        int nb = 0;                       // (an entity with the spike-and-slab prior has no Normal-Wishart draw)
-        for (int j = 0; j < n; j++) {
-            const bdf_gibbs_entity &e = g->ent[(size_t)j].d;
-            if (e.spike) continue;
-            Ns[nb] = e.n_real; nus[nb] = hyper_nu(e); tags[nb] = e.tag; outs[nb] = e.draws; nb++;
-        }
-        if (nb > 0 && (rc = bdf_hyper_draws_batch(H, D, nb, Ns, nus, tags, outs))) return rc;
+    return BDF_OK;
+}
+
+// the data-independent part of every entity's hyperprior draw (Bartlett matrix, mean normals): inside the entity's chain
+// launch, beside its partial sums, when every entity is small enough for the one-launch chain (the hyperprior stream is
+// busy ~85 of an iteration's 90 us: a launch of its own at the head of the iteration is 7 us of that); else ahead of the rows
+// (for all entities in one launch, here at the head of the iteration, when they are few).  *in_chain: the chain makes them
+int draws_ahead(bdf_gibbs *g, bool *in_chain)
+{
+    *in_chain = !g->comm;                // (several ranks: the sums are not the chain's, bdf_hyper_sums_ranks)
+    for (const auto &E : g->ent) *in_chain = *in_chain && E.d.N <= 16384;
+    if (*in_chain || (int)g->ent.size() > BDF_DRAWS_BATCH) return BDF_OK;
+    int64_t Ns[BDF_DRAWS_BATCH]; double nus[BDF_DRAWS_BATCH]; uint32_t tags[BDF_DRAWS_BATCH]; double *outs[BDF_DRAWS_BATCH];
+    int nb = 0;                           // (an entity with the spike-and-slab prior has no Normal-Wishart draw)
+    for (const auto &E : g->ent) {
+        const bdf_gibbs_entity &e = E.d;
+        if (e.spike) continue;
+        Ns[nb] = e.n_real; nus[nb] = hyper_nu(e); tags[nb] = e.tag; outs[nb] = e.draws; nb++;
     }
+    return nb > 0 ? bdf_hyper_draws_batch(g->hyper, g->D, nb, Ns, nus, tags, outs) : BDF_OK;
+}
+
+// The prediction update reads every entity's rows of this iteration.  Hand-over by counter: a one-wave gate (k_rows_gate) on
+// a stream of the reserved CUs polls this launch's done counters, and the prediction stream waits for the event on the
+// GATE's dispatch (ev_rows, which nothing else uses on this path).  That orders the update behind all the rows:
+//   * the gate returns only after the done counters say every row of this launch is in memory;
+//   * the earlier entities' launches of this iteration are ahead of this one on the in-order row stream (and this launch
+//     gathers their rows): complete before its first wave started.
+// No cycle: the gate is enqueued BEHIND the launch it waits for and waits for nothing else; should its stream share a hardware
+// queue with another one, it runs late, never early.  Rows still wait for the prediction stream nowhere on the device.
+// (Waiting for ev_hyper of this entity's chain instead -- no kernel, the same order -- starts the update ~28 us after the
+// rows instead of at their end, where it stretches BOTH row launches it then meets: 11.2-11.4 k sweeps/s against the
+// event's 12.2-12.4 k, profiles/r08_update_handover.txt.)
+int gate_prediction(bdf_gibbs *g, const bdf_gibbs::Ent &E)
+{
+    hipExtLaunchKernelGGL(k_rows_gate, dim3(1), dim3(64), 0, g->gate->stream, nullptr, E.ev_rows, 0, (const uint32_t *)E.done_dev, E.done_target,
+                          g->hyper->flag_dev);
+    BDF_HIP(hipGetLastError());
+    BDF_HIP(hipStreamWaitEvent(g->pred->stream, E.ev_rows, 0));
+    return BDF_OK;
+}
+
+// the prediction update of this iteration's rows on the prediction stream, and its event
+int predict_step(bdf_gibbs *g, int predict_phase)
+{
+    bdf_ctx *P = g->pred;
+    int rc;
+    const double *fac[BDF_MAX_MODES];
+    current_factors(g, g->test_entity, g->test->n_modes, fac);
+    // (phase 3, set-up only: the same kernel on the same pairs, statistics of this sample into stats_dev, no running state)
+    if ((rc = predict_phase == 3 ? bdf_predict_sse(P, g->test, g->D, fac, g->test_mean, nullptr, g->stats_dev)
+                                 : bdf_predict_update(P, g->test, g->D, fac, g->test_mean, predict_phase, g->clamp_lo, g->clamp_hi, g->class_cut, g->stats_dev)))
+        return rc;
+    BDF_HIP(hipEventRecord(g->ev_pred[g->n_pred % 3], P->stream));
+    g->pred_at[g->n_pred % 3] = g->n_iter;
+    g->n_pred++;
+    return BDF_OK;
+}
+}  // namespace
+
+// One iteration: the schedule.  It composes the pieces above -- update_relations, launch_rows, hyper_step, beta_step -- with its events,
+// polling and counters; what each piece enqueues is the piece's business.
+extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
+{
+    BDF_REQUIRE(g, BDF_ERR_ARG, "bdf_gibbs_sweep: NULL argument");
+    bdf_ctx *R = g->rows, *H = g->hyper, *P = g->pred;
+    const int D = g->D, n = (int)g->ent.size();
+    int rc;
+    R->sweep_host = H->sweep_host = P->sweep_host = sweep;
+    const auto t_in = std::chrono::steady_clock::now();
+    if ((rc = await_old_predictions(g))) return rc;
+    const auto t_go = std::chrono::steady_clock::now();
+    bool draws_in_chain;
+    if ((rc = draws_ahead(g, &draws_in_chain))) return rc;
     // the relation models (alpha, relation-level beta and linear_values) with the rows of the previous iteration (macau.jl:83-92)
     if (!g->rels.empty() && (rc = update_relations(g))) return rc;
     for (int j = 0; j < n; j++) {
@@ -1016,16 +1163,8 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // the data-independent part of the hyperprior draw (Bartlett matrix, mean normals): beside the rows -- for all entities
         // in one launch at the head of the iteration when they are few
         if (!draws_in_chain && n > BDF_DRAWS_BATCH && !e.spike && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
-        // the prior of this launch: the draw's (mu, Lambda) and pack, or -- background cells -- those with the Gram terms folded in
-        const double *mu_rows = nullptr, *Lambda_rows = nullptr, *pack_rows = nullptr;
-        int mu_rows_matrix = e.feat ? 1 : 0;
-        if (!e.spike && (rc = row_prior(g, E, E.hyper_recorded, &mu_rows, &mu_rows_matrix, &Lambda_rows, &pack_rows))) return rc;
-        bdf_term terms[BDF_MAX_TERMS];
-        fill_terms(g, e, terms);
-        const int nxt = (E.cur + 1) % 3;
         // the completion event rides on the row kernel's dispatch (a caller-supplied timing pair takes its place)
         hipEvent_t done = E.t_stop ? E.t_stop : E.ev_rows;
-        const int nch = e.terms[0].rel->chunks;                    // 1 unless the relations were created with a layout
         // The hand-over to the entity's hyperprior chain.  By default an event on the row kernel's dispatch and a wait on the
         // hyperprior stream -- which costs that stream ~10 us per chain even when the event completed long before, and the row
         // stream ~1.7 us per launch.  When the chain is the one-launch kind and runs on reserved CUs (the schedule in which the
@@ -1035,106 +1174,45 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // The last entity's launch is no exception when the prediction update follows it: nothing rides on its dispatch either.  (It
         // carried `done` for the prediction stream to wait on, the one event left on the row stream: the next iteration's first row
         // launch followed it after ~5 us in the kernel trace where the other launches follow each other after 0.)  The prediction
-        // stream waits for a one-wave gate on the reserved CUs instead, see below.
+        // stream waits for a one-wave gate on the reserved CUs instead, see gate_prediction.
         // Every other path -- a communicator, side information, chunks, a caller's timing events (E.t_stop), no polling, chains of
         // several launches: `counter` false; a launch that took another kernel: rows_done_added < 0 -- has `done` as before, on the
         // dispatch or recorded right behind it, for the chain and the prediction stream alike.
-        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && !bg && !e.spike && nch == 1 && !E.t_stop;
+        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && !bg && !e.spike && e.terms[0].rel->chunks == 1 && !E.t_stop;
         const bool pred_waits = j == n - 1 && g->test && predict_phase >= 0;
+        RowsExtras rx{};
+        rx.start = E.t_start; rx.span = E.span;
+        rx.stop = (!g->comm && !counter) ? done : nullptr; rx.joined = g->comm ? done : nullptr;
+        if (poll) { rx.poll = g->ready_dev + j; rx.poll_want = E.epoch; }
+        if (counter) rx.counter = E.done_dev;
         bool by_counter = false;
-        for (int c = 0; c < nch; c++) {
-            R->time_start = (c == 0) ? E.t_start : nullptr;
-            R->rows_span = E.span;
-            R->time_stop = (c == nch - 1 && !g->comm && !counter) ? done : nullptr;
-            if (poll) { R->rows_ready = g->ready_dev + j; R->rows_ready_want = E.epoch; }
-            if (counter) R->rows_done = E.done_dev;
-            R->gimg_trust = !g->comm;         // (the chain's own buffers: sample_written() hears of every other writer)
-            if ((rc = e.spike ? bdf_sample_rows_spike(R, D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
-                              : bdf_sample_rows(R, D, e.N, e.n_terms, terms, mu_rows, mu_rows_matrix, Lambda_rows, e.tag, c, nch, e.sample[nxt], pack_rows)))
-                return rc;
-            if (counter && R->rows_done_added >= 0) { by_counter = true; E.done_target += (uint32_t)R->rows_done_added; }
-            if (g->comm && (rc = bdf_allgather_rows(R, g->comm, D, e.N, e.sample[nxt], c, nch))) return rc;
-        }
-        if (g->comm) {
-            if ((rc = bdf_allgather_join(R, g->comm))) return rc;       // the row stream continues after the last chunk's exchange
-            BDF_HIP(hipEventRecord(done, R->stream));
-        } else if (counter && !by_counter) {
-            BDF_HIP(hipEventRecord(done, R->stream));                   // (the launch took another kernel: the event after all)
-        }
-        E.t_start = E.t_stop = nullptr;
-        E.span = nullptr;
-        E.cur = nxt;
-        if (by_counter) { H->hyper_wait = E.done_dev; H->hyper_wait_target = E.done_target; }
+        if ((rc = launch_rows(g, E, E.hyper_recorded, true, rx, &by_counter))) return rc;
+        if (counter && !by_counter) BDF_HIP(hipEventRecord(done, R->stream));      // (the launch took another kernel: the event after all)
+        E.t_start = E.t_stop = nullptr; E.span = nullptr;
+        HyperExtras hx{};
+        if (by_counter) { hx.wait = E.done_dev; hx.wait_target = E.done_target; }
         else BDF_HIP(hipStreamWaitEvent(H->stream, done, 0));
-        if (e.spike) {
-            // the spike-and-slab prior's hyper step in place of the sums and the Normal-Wishart draw; its event recorded behind it
-            if ((rc = bdf_spike_hyper(H, D, e.n_real, e.sample[E.cur], e.spike_a, e.spike_b, e.spike_shape, e.spike_rate, e.tag, e.spike_state)))
-                return rc;
-            BDF_HIP(hipEventRecord(E.ev_hyper, H->stream));
-            E.hyper_recorded = true;
-            if (pred_waits) BDF_HIP(hipStreamWaitEvent(P->stream, done, 0));
-            continue;
+        if (!e.spike) {
+            hx.fuse = true; hx.chain_draws = draws_in_chain ? e.draws : nullptr;
+            hx.stop = E.ev_hyper; hx.ready = g->ready_dev + j; hx.ready_value = ++E.epoch;
+            if (e.feat && e.full_lambda_u && E.beta_recorded) BDF_HIP(hipStreamWaitEvent(H->stream, E.ev_beta, 0));
         }
-        H->hyper_fuse = true;             // small entities: the sums and the draw in one launch (k_hyper_chain)
-        // side information: U = sample - uhat, T^-1 = WI + beta' beta lambda_beta with the beta of the previous iteration
-        const double *Tinv = e.WI;
-        if (e.feat && e.full_lambda_u) {
-            if (E.beta_recorded) BDF_HIP(hipStreamWaitEvent(H->stream, E.ev_beta, 0));
-            if ((rc = bdf_hyper_feature_terms(H, D, e.feat->n, e.beta, e.WI, e.lambda_beta, e.Tinv))) return rc;
-            Tinv = e.Tinv;
-        }
-        // (several ranks: every rank sums its own rows, the D + D^2 partial sums are added over the ranks in rank order)
-        if ((rc = g->comm ? bdf_hyper_sums_ranks(H, g->comm, D, e.N, nch, e.sample[E.cur], e.feat ? e.uhat : nullptr, e.sumU, e.UUt)
-                          : bdf_hyper_sums(H, D, e.N, e.sample[E.cur], e.feat ? e.uhat : nullptr, e.sumU, e.UUt)))
-            return rc;
-        H->hyper_chain_draws = draws_in_chain ? e.draws : nullptr;
-        H->time_h_stop = E.ev_hyper;
-        H->hyper_ready = g->ready_dev + j;
-        H->hyper_ready_value = ++E.epoch;
-        if ((rc = bdf_hyper_sample(H, D, e.n_real, e.sumU, e.UUt, e.mu0, e.b0, Tinv, hyper_nu(e), e.tag, e.mu, e.Lambda, e.params, e.prior_pack, e.draws)))
-            return rc;
+        if ((rc = hyper_step(g, E, H, e.draws, hx))) return rc;
+        if (e.spike) BDF_HIP(hipEventRecord(E.ev_hyper, H->stream));              // (its event recorded behind it)
         E.hyper_recorded = true;
-        // The prediction update reads every entity's rows of this iteration.  Hand-over by counter: a one-wave gate (k_rows_gate) on
-        // a stream of the reserved CUs polls this launch's done counters, and the prediction stream waits for the event on the
-        // GATE's dispatch (ev_rows, which nothing else uses on this path).  That orders the update behind all the rows:
-        //   * the gate returns only after the done counters say every row of this launch is in memory;
-        //   * the earlier entities' launches of this iteration are ahead of this one on the in-order row stream (and this launch
-        //     gathers their rows): complete before its first wave started.
-        // No cycle: the gate is enqueued BEHIND the launch it waits for and waits for nothing else; should its stream share a hardware
-        // queue with another one, it runs late, never early.  Rows still wait for the prediction stream nowhere on the device.
-        // (Waiting for ev_hyper of this entity's chain instead -- no kernel, the same order -- starts the update ~28 us after the
-        // rows instead of at their end, where it stretches BOTH row launches it then meets: 11.2-11.4 k sweeps/s against the
-        // event's 12.2-12.4 k, profiles/r08_update_handover.txt.)
-        if (pred_waits && by_counter) {
-            hipExtLaunchKernelGGL(k_rows_gate, dim3(1), dim3(64), 0, g->gate->stream, nullptr, E.ev_rows, 0, (const uint32_t *)E.done_dev,
-                                  E.done_target, H->flag_dev);
-            BDF_HIP(hipGetLastError());
-            BDF_HIP(hipStreamWaitEvent(P->stream, E.ev_rows, 0));
-        } else if (pred_waits) BDF_HIP(hipStreamWaitEvent(P->stream, done, 0));
+        if (pred_waits && by_counter) { if ((rc = gate_prediction(g, E))) return rc; }
+        else if (pred_waits) BDF_HIP(hipStreamWaitEvent(P->stream, done, 0));
     }
     // side information: beta of every entity that has it, from this iteration's rows and (mu, Lambda) (macau.jl:138-140)
     for (int j = 0; j < n; j++) {
         auto &E = g->ent[(size_t)j];
-        const bdf_gibbs_entity &e = E.d;
-        if (!e.feat) continue;
+        if (!E.d.feat) continue;
         BDF_HIP(hipStreamWaitEvent(R->stream, E.ev_hyper, 0));
-        if ((rc = bdf_sample_beta_ranks(R, g->comm, e.feat, D, e.sample[E.cur], e.mu, e.Lambda, e.lambda_beta, e.use_ff, e.tol, 0,
-                                        e.sample_lambda_beta, e.lb_nu, e.lb_mu, e.tag, e.beta, nullptr, e.cg_iters)))
-            return rc;
+        if ((rc = beta_step(g, E))) return rc;
         BDF_HIP(hipEventRecord(E.ev_beta, R->stream));
         E.beta_recorded = true;
     }
-    if (g->test && predict_phase >= 0) {
-        const double *fac[BDF_MAX_MODES];
-        current_factors(g, g->test_entity, g->test->n_modes, fac);
-        // (phase 3, set-up only: the same kernel on the same pairs, statistics of this sample into stats_dev, no running state)
-        if ((rc = predict_phase == 3 ? bdf_predict_sse(P, g->test, D, fac, g->test_mean, nullptr, g->stats_dev)
-                                     : bdf_predict_update(P, g->test, D, fac, g->test_mean, predict_phase, g->clamp_lo, g->clamp_hi, g->class_cut, g->stats_dev)))
-            return rc;
-        BDF_HIP(hipEventRecord(g->ev_pred[g->n_pred % 3], P->stream));
-        g->pred_at[g->n_pred % 3] = g->n_iter;
-        g->n_pred++;
-    }
+    if (g->test && predict_phase >= 0 && (rc = predict_step(g, predict_phase))) return rc;
     g->n_iter++;
     if (g->debug) {
         g->host_wait_us += std::chrono::duration<double, std::micro>(t_go - t_in).count();

@@ -4,9 +4,9 @@ Everything numeric is a call into libbdf_hip.so (include/bdf.h).  torch is used 
 allocations (tensors) and, with several ranks, the channel over which rank 0 hands the RCCL unique id to the others.
 
 * The whole iteration (the relations' models, rows of every entity, exchange between the GPUs, hyperpriors, beta, test
-  prediction update) is ONE native call, bdf_gibbs_sweep (csrc/bdf_gibbs.hip).  BDF_NO_NATIVE: the same object's relation step
-  and row launches are driven piece by piece from here (bdf_gibbs_step_relations, bdf_gibbs_step_rows), with the hyperpriors and
-  beta through the entry points of bdf.h, on three streams with plain stream order.
+  prediction update) is ONE native call, bdf_gibbs_sweep (csrc/bdf_gibbs.hip).  BDF_NO_NATIVE: the same object's pieces -- relation
+  step, row launches, hyperprior draws and steps, beta -- are driven one by one from here (bdf_gibbs_step_relations, _rows, _draws,
+  _hyper, _beta), on three streams with plain stream order; only the prediction update goes through the entry points of bdf.h.
 * Several ranks (shard=(rank, world)): every entity's rows are shared out by bdf_layout_build -- dealt over the ranks in
   falling order of degree as the reference deals rows i:P:N to its workers (src/sampling.jl:154) -- and stored at INTERNAL
   positions, so that a rank's rows of a chunk are one contiguous block and the exchange is an in-place all-gather
@@ -1087,8 +1087,8 @@ class GibbsEngine:
         # (callers take `gibbs` for the native path's handle: None step by step)
         self.gibbs = self._gibbs if self.native else None
         if not self.native:
-            # BDF_NO_OVERLAP: everything on the row context; a relation with features: the prediction updates stay there (their
-            # baseline is refreshed on the row stream)
+            # BDF_NO_OVERLAP: everything on the row context (the object, created above, read it too: its hyperprior pieces go
+            # there); a relation with features: the prediction updates stay there (their baseline is refreshed on the row stream)
             if os.environ.get("BDF_NO_OVERLAP"):
                 self.ctx_h = self.ctx_p = self.ctx
             elif not all(feat.isempty(r.F) for r in data.relations):
@@ -1204,8 +1204,8 @@ class GibbsEngine:
     # ---- the iteration object (bdf_gibbs) -----------------------------------------------------------------------------
     def _create_gibbs(self):
         """the library's description of the iteration, on both paths: the native one runs it whole (bdf_gibbs_sweep), the
-        step-by-step one drives its relation step and row launches piece by piece (bdf_gibbs_step_relations, bdf_gibbs_step_rows)
-        on a schedule of its own, with the object's two side contexts"""
+        step-by-step one drives its pieces one by one (bdf_gibbs_step_relations, _rows, _draws, _hyper, _beta) on a schedule of its
+        own, with the object's two side contexts"""
         ents = (GibbsEntity * len(self.ent))()
         for j, (en, st) in enumerate(zip(self.data.entities, self.ent)):
             g = ents[j]
@@ -1469,53 +1469,21 @@ class GibbsEngine:
         st.rotate()
 
     # ---- macau.jl:119-134: hyperprior of entity j ----------------------------------------------------------------
-    def _hyper_nu(self, j):
-        st = self.ent[j]
-        return st.nu0 + (st.numF if (st.F is not None and self.full_lambda_u) else 0)
-
     def prepare_prior(self, j, sweep):
-        """the data-independent part of update_prior(j) of this sweep; may be issued before the rows of j are sampled"""
-        st = self.ent[j]
-        if st.spike is not None:      # (its hyper step draws from the rows' counts: nothing to prepare)
-            return
-        check(lib().bdf_hyper_draws(self.ctx_h.handle, self.D, st.n_real, self._hyper_nu(j), st.tag, _ptr(st.draws)))
-        st.draws_sweep = sweep
+        """the data-independent part of update_prior(j) of this sweep (bdf_gibbs_step_draws); may be issued before the rows of j
+        are sampled"""
+        check(lib().bdf_gibbs_step_draws(self._gibbs, int(j)))
+        self.ent[j].draws_sweep = sweep
 
     def update_prior(self, j, sweep=None):
-        en, st = self.data.entities[j], self.ent[j]
-        L = lib()
-        h = self.ctx_h.handle
-        draws = st.draws if (sweep is not None and st.draws_sweep == sweep) else None
-        if st.spike is not None:
-            sp = st.spike
-            check(L.bdf_spike_hyper(h, self.D, st.n_real, _ptr(st.sample), sp["incl_a"], sp["incl_b"], sp["shape"], sp["rate"], st.tag,
-                                    _ptr(st.spike_state)))
-            return
-        if self.comm is not None and self.world > 1:      # own rows, then the ranks' partial sums added in rank order
-            check(L.bdf_hyper_sums_ranks(h, self.comm.handle, self.D, st.N, st.layout.chunks, _ptr(st.sample),
-                                         _ptr(st.uhat) if st.F is not None else None, _ptr(st.sumU), _ptr(st.UUt)))
-        else:
-            check(L.bdf_hyper_sums(h, self.D, st.N, _ptr(st.sample), _ptr(st.uhat) if st.F is not None else None,
-                                   _ptr(st.sumU), _ptr(st.UUt)))
-        nu, Tinv = st.nu0, st.WI
-        if st.F is not None and self.full_lambda_u:
-            nu += st.numF
-            check(L.bdf_hyper_feature_terms(h, self.D, st.numF, _ptr(st.beta), _ptr(st.WI), _ptr(st.lambda_beta), _ptr(st.Tinv)))
-            Tinv = st.Tinv
-        check(L.bdf_hyper_sample(h, self.D, st.n_real, _ptr(st.sumU), _ptr(st.UUt), _ptr(st.mu0), st.b0, _ptr(Tinv),
-                                 nu, st.tag, _ptr(st.mu), _ptr(st.Lambda), _ptr(st.params), _ptr(st.prior_pack),
-                                 _ptr(draws) if draws is not None else None))
+        """entity j's hyperprior from its current rows (bdf_gibbs_step_hyper), with the draws prepare_prior made for this sweep"""
+        st = self.ent[j]
+        check(lib().bdf_gibbs_step_hyper(self._gibbs, int(j), int(sweep is not None and st.draws_sweep == sweep)))
         st.prior_pack_valid = True
 
     # ---- macau.jl:138-140: beta of entity j ----------------------------------------------------------------
     def update_beta(self, j):
-        en, st = self.data.entities[j], self.ent[j]
-        if st.F is None:
-            return
-        # (several ranks: the conjugate-gradient columns are shared out over them and all-gathered, parallel_matrix.jl:488-507)
-        check(lib().bdf_sample_beta_ranks(self.ctx.handle, self.comm.handle if self.comm is not None else None, st.F.handle, self.D,
-                                          _ptr(st.sample), _ptr(st.mu), _ptr(st.Lambda), _ptr(st.lambda_beta), int(en.use_FF), self.tol, 0,
-                                          int(en.lambda_beta_sample), en.nu, en.mu, st.tag, _ptr(st.beta), None, _ptr(st.cg_iters)))
+        check(lib().bdf_gibbs_step_beta(self._gibbs, int(j)))
 
     def sync_host_scalars(self):
         for en, st in zip(self.data.entities, self.ent):

@@ -1042,16 +1042,28 @@ int bdf_gibbs_current(const bdf_gibbs *g, int entity, int *buffer);
 /* measurement: the row launch of one entity as bdf_gibbs_sweep makes it, and nothing else (no hyperprior update, exchange or
  * prediction update: the chain's state is not kept consistent) */
 int bdf_gibbs_rows_only(bdf_gibbs *g, int entity, uint32_t sweep);
-/* The iteration piece by piece, for a host that keeps the schedule itself and enqueues the hyperpriors, beta and the prediction
- * update through the entry points above: the same code bdf_gibbs_sweep runs, on the row stream with plain stream order (no events,
- * no polling, no done counters) under the iteration number the caller has set with bdf_ctx_set_sweep.
+/* The iteration piece by piece, for a host that keeps the schedule itself and enqueues the prediction update through the entry
+ * points above: the same code bdf_gibbs_sweep runs, with plain stream order (no events, no polling, no done counters) under the
+ * iteration number the caller has set on the contexts with bdf_ctx_set_sweep.  Relations, rows and beta go to the row context's
+ * stream, draws and hyperprior to the hyperprior context's (bdf_gibbs_contexts) -- or, for an object created with BDF_NO_OVERLAP set
+ * in the environment, to the row context's as well.  Nothing of the object's bookkeeping changes but the rows' buffer rotation.
  * bdf_gibbs_step_relations: what the registered relations' models run before the rows (bdf_gibbs_set_relations).
  * bdf_gibbs_step_rows: one entity's rows -- uhat and the per-row prior means with side information, the prior with the background
  * and dense terms folded in, the row launch chunk by chunk, with a communicator every chunk's exchange -- after which the entity's
  * buffers have rotated (bdf_gibbs_current).  pack_valid: the entity's latest hyperprior draw (bdf_hyper_sample) has left its prior
- * pack; 0 before the first draw.  The context's bdf_ctx_time_next_rows events go to the row launch. */
+ * pack; 0 before the first draw.  The context's bdf_ctx_time_next_rows events go to the row launch.
+ * bdf_gibbs_step_draws: the data-independent part of the entity's hyperprior draw (bdf_hyper_draws) into its draws buffer; may be
+ * enqueued before the entity's rows.  Nothing for an entity with the spike-and-slab prior.
+ * bdf_gibbs_step_hyper: the entity's hyperprior from its current rows -- the spike-and-slab prior's hyper step, or the feature
+ * terms, the sums (with a communicator over the ranks) and the Normal-Wishart draw.  draws_prepared: bdf_gibbs_step_draws has run
+ * under this iteration number; 0: the draw makes its own normals (the same values).
+ * bdf_gibbs_step_beta: beta (and lambda_beta) of an entity with side information from its current rows and (mu, Lambda); nothing
+ * for an entity without. */
 int bdf_gibbs_step_relations(bdf_gibbs *g);
 int bdf_gibbs_step_rows(bdf_gibbs *g, int entity, int pack_valid);
+int bdf_gibbs_step_draws(bdf_gibbs *g, int entity);
+int bdf_gibbs_step_hyper(bdf_gibbs *g, int entity, int draws_prepared);
+int bdf_gibbs_step_beta(bdf_gibbs *g, int entity);
 /* parity hooks: the terms (entity's n_terms of them, the factors at the current samples) and the prior that the entity's next row
  * launch would take.  bdf_gibbs_row_prior enqueues the fold of the background and dense terms on the row stream and hands back
  * device pointers: the prior mean (one, or one per row: *mu_is_matrix), Lambda and the prior pack (NULL: none). */

@@ -359,13 +359,19 @@ function current_buffer(g::Gibbs, entity::Integer)
     check(ccall((:bdf_gibbs_current, lib), Cint, (Ptr{Cvoid}, Cint, Ref{Cint}), g.h, entity - 1, b))
     return b[] + 1
 end
-"""the iteration piece by piece, for a host that keeps the schedule itself (hyperpriors, beta and the prediction update through the
-entry points above): what the registered relations' models run before the rows, then one entity's rows -- uhat, the prior with the
-background and dense terms folded in, the row launch, with a communicator the exchange -- on the row stream with plain stream
-order, under the iteration number set with `set_sweep!`.  `pack_valid`: the entity's latest `update_prior!` has left its prior pack"""
+"""the iteration piece by piece, for a host that keeps the schedule itself (the prediction update through the entry points above):
+what the registered relations' models run before the rows, then one entity's rows -- uhat, the prior with the background and dense
+terms folded in, the row launch, with a communicator the exchange -- the data-independent part of its hyperprior draw, its
+hyperprior step (`draws_prepared`: `step_draws!` has run under this iteration number) and, with side information, its beta: the
+pieces `sweep!` composes, with plain stream order, under the iteration number set with `set_sweep!` on the row and the hyperprior
+context.  `pack_valid`: the entity's latest `step_hyper!` has left its prior pack"""
 step_relations!(g::Gibbs) = check(ccall((:bdf_gibbs_step_relations, lib), Cint, (Ptr{Cvoid},), g.h))
 step_rows!(g::Gibbs, entity::Integer, pack_valid::Bool) =
     check(ccall((:bdf_gibbs_step_rows, lib), Cint, (Ptr{Cvoid}, Cint, Cint), g.h, entity - 1, pack_valid))
+step_draws!(g::Gibbs, entity::Integer) = check(ccall((:bdf_gibbs_step_draws, lib), Cint, (Ptr{Cvoid}, Cint), g.h, entity - 1))
+step_hyper!(g::Gibbs, entity::Integer, draws_prepared::Bool) =
+    check(ccall((:bdf_gibbs_step_hyper, lib), Cint, (Ptr{Cvoid}, Cint, Cint), g.h, entity - 1, draws_prepared))
+step_beta!(g::Gibbs, entity::Integer) = check(ccall((:bdf_gibbs_step_beta, lib), Cint, (Ptr{Cvoid}, Cint), g.h, entity - 1))
 "parity hook: the `n_terms` terms the entity's next row launch would take, the factors at the current samples"
 function row_terms(g::Gibbs, entity::Integer, n_terms::Integer)
     terms = Vector{Term}(undef, n_terms)

@@ -1,8 +1,10 @@
 """The entry points through which the step-by-step path drives the library's own description of the iteration
-(bdf_gibbs_step_relations, bdf_gibbs_step_rows) and its two parity hooks (bdf_gibbs_terms, bdf_gibbs_row_prior): what fill_terms()
-of csrc/bdf_gibbs.hip hands a row launch for every kind of relation, that the library's buffer rotation and the engine's stay
-together step by step, and that bad arguments are refused.  That the step path computes what the native one does is the business
-of the both-paths tests; nothing here depends on a kernel's size: 30 x 40 cells at most, D = 3.
+(bdf_gibbs_step_relations, _rows, _draws, _hyper, _beta) and its two parity hooks (bdf_gibbs_terms, bdf_gibbs_row_prior): what
+fill_terms() of csrc/bdf_gibbs.hip hands a row launch for every kind of relation, that the library's buffer rotation and the engine's
+stay together step by step, that the hyperprior and the beta step equal the sequences of public entry points they replaced, that
+they leave the object's bookkeeping alone, and that bad arguments are refused.  That the step path computes what the native one does
+is the business of the both-paths tests; nothing here depends on a kernel's size: 30 x 40 cells at most, D = 3 but where the
+hyperprior kernels' three widths are meant.
 """
 import ctypes as C
 
@@ -29,11 +31,11 @@ def _relation(B, name, a, b, dims, nnz, seed, binary=False):
     return B.Relation({a.name: ids[:, 0], b.name: ids[:, 1], "y": y}, name, [a, b], alpha=ALPHA, dims=list(dims))
 
 
-def _engine(B, *rels):
+def _engine(B, *rels, **kw):
     rd = B.RelationData()
     for r in rels:
         B.addRelation(rd, r)
-    return rd, B.GibbsEngine(rd, D, seed=3)
+    return rd, B.GibbsEngine(rd, kw.pop("num_latent", D), seed=3, **kw)
 
 
 def _single(B, kind):
@@ -147,6 +149,9 @@ def test_entry_points_refuse_bad_arguments(B):
         assert L.bdf_gibbs_step_relations(None) == ERR_ARG
         for h, j in ((None, 0), (g, -1), (g, len(eng.ent))):
             assert L.bdf_gibbs_step_rows(h, j, 0) == ERR_ARG
+            assert L.bdf_gibbs_step_draws(h, j) == ERR_ARG
+            assert L.bdf_gibbs_step_hyper(h, j, 0) == ERR_ARG
+            assert L.bdf_gibbs_step_beta(h, j) == ERR_ARG
             assert L.bdf_gibbs_terms(h, j, terms) == ERR_ARG
             assert L.bdf_gibbs_row_prior(h, j, 0, *prior) == ERR_ARG
         # (nothing was enqueued and nothing rotated)
@@ -157,5 +162,178 @@ def test_entry_points_refuse_bad_arguments(B):
         st = eng.ent[0]
         assert (mu.value, ism.value, Lam.value, pack.value) == (st.mu.data_ptr(), 0, st.Lambda.data_ptr(), None)
         assert L.bdf_gibbs_row_prior(g, 0, 1, *prior) == 0 and pack.value == st.prior_pack.data_ptr()
+    finally:
+        eng.close()
+
+
+# ---- the hyperprior and the beta step against the sequences of public entry points they replaced ---------------------------------------
+NNZ_STEP = 600
+
+
+def _pair_of_engines(B, monkeypatch, num_latent=D, features=False, spike=False, **kw):
+    """two step-by-step engines on the same model with the same seed, one full iteration behind them (so that beta, lambda_beta and
+    the hyperprior are no longer their initial values); entity 0 (u) carries the features / the spike-and-slab prior"""
+    monkeypatch.setenv("BDF_NO_NATIVE", "1")
+    out = []
+    for _ in range(2):
+        F = np.random.default_rng(9).standard_normal((NU, 5)) if features else None
+        u, w = B.Entity("u", F=F), B.Entity("w")
+        if spike:
+            B.setSpikeAndSlab(u, 2.0, 3.0, 1.5, 0.5)
+        rd, eng = _engine(B, _relation(B, "r", u, w, (NU, NW), NNZ_STEP, 1), num_latent=num_latent, **kw)
+        assert eng.native is False and eng.ctx_h is not eng.ctx
+        eng.sweep(1)
+        eng.sync()
+        out.append((rd, eng))
+    return out
+
+
+def _rows_of(eng, j, i):
+    """iteration i up to and including entity j's rows"""
+    eng.ctx.set_sweep(i)
+    eng.ctx_h.set_sweep(i)
+    eng.update_relations()
+    eng.sample_entity(j)
+    eng.sync()
+
+
+def _bits(eng, j, names):
+    return {n: getattr(eng.ent[j], n).cpu().numpy().tobytes() for n in names}
+
+
+def _old_update_prior(eng, j, prepared):
+    """GibbsEngine.update_prior (and prepare_prior) as they stood before bdf_gibbs_step_hyper: the public entry points on eng.ctx_h"""
+    from bdf_amd._lib import check, lib
+    from bdf_amd.engine import _ptr
+    L, h, st, Dn = lib(), eng.ctx_h.handle, eng.ent[j], eng.D
+    if st.spike is not None:
+        sp = st.spike
+        check(L.bdf_spike_hyper(h, Dn, st.n_real, _ptr(st.sample), sp["incl_a"], sp["incl_b"], sp["shape"], sp["rate"], st.tag, _ptr(st.spike_state)))
+        return
+    nu, Tinv = st.nu0, st.WI
+    if st.F is not None and eng.full_lambda_u:
+        nu += st.numF
+    if prepared:
+        check(L.bdf_hyper_draws(h, Dn, st.n_real, nu, st.tag, _ptr(st.draws)))
+    check(L.bdf_hyper_sums(h, Dn, st.N, _ptr(st.sample), _ptr(st.uhat) if st.F is not None else None, _ptr(st.sumU), _ptr(st.UUt)))
+    if st.F is not None and eng.full_lambda_u:
+        check(L.bdf_hyper_feature_terms(h, Dn, st.numF, _ptr(st.beta), _ptr(st.WI), _ptr(st.lambda_beta), _ptr(st.Tinv)))
+        Tinv = st.Tinv
+    check(L.bdf_hyper_sample(h, Dn, st.n_real, _ptr(st.sumU), _ptr(st.UUt), _ptr(st.mu0), st.b0, _ptr(Tinv), nu, st.tag, _ptr(st.mu), _ptr(st.Lambda),
+                             _ptr(st.params), _ptr(st.prior_pack), _ptr(st.draws) if prepared else None))
+
+
+@pytest.mark.parametrize("case", ["plain", "features", "features_wi"])
+@pytest.mark.parametrize("num_latent", [3, 17, 33])
+def test_hyper_step_equals_the_entry_points_it_replaced(B, monkeypatch, num_latent, case):
+    """update_prior(j, i) -- bdf_gibbs_step_hyper -- against bdf_hyper_draws, bdf_hyper_sums, bdf_hyper_feature_terms, bdf_hyper_sample
+    on the same context, bit for bit: with the draws prepared (iteration 2) and without (iteration 3), at one D per width of the
+    hyperprior kernels, without side information and with it (full_lambda_u or not: nu and Tinv differ)"""
+    feats = case != "plain"
+    (_, a), (_, b) = _pair_of_engines(B, monkeypatch, num_latent, features=feats, full_lambda_u=case != "features_wi")
+    try:
+        names = ["mu", "Lambda", "sumU", "UUt", "prior_pack", "params"] + (["Tinv"] if feats else [])
+        for i, prepared in ((2, True), (3, False)):
+            for eng in (a, b):
+                _rows_of(eng, 0, i)
+            before = _bits(a, 0, names)
+            assert before == _bits(b, 0, names)
+            if prepared:
+                a.prepare_prior(0, i)
+            a.update_prior(0, i)
+            _old_update_prior(b, 0, prepared)
+            a.sync(), b.sync()
+            got, want = _bits(a, 0, names), _bits(b, 0, names)
+            for n in names:
+                assert got[n] == want[n], (n, i)
+            assert all(got[n] != before[n] for n in ("mu", "Lambda", "sumU", "UUt", "prior_pack"))
+            if feats and i == 2:      # (T^-1 is made only with full_lambda_u; the first iteration made it from beta = 0)
+                assert (got["Tinv"] != before["Tinv"]) == (case == "features")
+    finally:
+        a.close(), b.close()
+
+
+def test_hyper_step_of_a_spike_and_slab_entity(B, monkeypatch):
+    (_, a), (_, b) = _pair_of_engines(B, monkeypatch, spike=True)
+    try:
+        for eng in (a, b):
+            _rows_of(eng, 0, 2)
+        before = _bits(a, 0, ["spike_state"])
+        a.prepare_prior(0, 2)                                   # (nothing to prepare: no launch)
+        a.update_prior(0, 2)
+        _old_update_prior(b, 0, False)
+        a.sync(), b.sync()
+        assert _bits(a, 0, ["spike_state", "draws"]) == _bits(b, 0, ["spike_state", "draws"])
+        assert _bits(a, 0, ["spike_state"]) != before
+    finally:
+        a.close(), b.close()
+
+
+@pytest.mark.parametrize("solver", ["direct", "cg"])
+def test_beta_step_equals_the_entry_point_it_replaced(B, monkeypatch, solver):
+    """update_beta(j) -- bdf_gibbs_step_beta -- against bdf_sample_beta_ranks with the arguments the engine passed, bit for bit"""
+    from bdf_amd._lib import check, lib
+    from bdf_amd.engine import _ptr
+    (rd, a), (_, b) = _pair_of_engines(B, monkeypatch, features=True, compute_ff_size=6500 if solver == "direct" else 0)
+    try:
+        assert rd.entities[0].use_FF is (solver == "direct")
+        names = ["beta", "lambda_beta", "cg_iters"]
+        for eng in (a, b):
+            _rows_of(eng, 0, 2)
+            eng.update_prior(0)
+            eng.sync()
+        before = _bits(a, 0, names)
+        assert before == _bits(b, 0, names)
+        a.update_beta(0)
+        en, st = b.data.entities[0], b.ent[0]
+        check(lib().bdf_sample_beta_ranks(b.ctx.handle, None, st.F.handle, b.D, _ptr(st.sample), _ptr(st.mu), _ptr(st.Lambda), _ptr(st.lambda_beta),
+                                          int(en.use_FF), b.tol, 0, int(en.lambda_beta_sample), en.nu, en.mu, st.tag, _ptr(st.beta), None,
+                                          _ptr(st.cg_iters)))
+        a.sync(), b.sync()
+        got = _bits(a, 0, names)
+        assert got == _bits(b, 0, names)
+        assert got["beta"] != before["beta"] and got["lambda_beta"] != before["lambda_beta"]
+        if solver == "cg":
+            assert (a.ent[0].cg_iters.cpu().numpy() > 0).all()
+        # the entity without features: the call returns and nothing changes
+        watch = ["sample", "mu", "Lambda", "beta", "sumU", "UUt"]
+        before = _bits(a, 1, watch)
+        a.update_beta(1)
+        a.sync()
+        assert _bits(a, 1, watch) == before and a.ent[1].beta.numel() == 0
+    finally:
+        a.close(), b.close()
+
+
+def test_step_entry_points_leave_the_bookkeeping_alone(B):
+    """bdf_gibbs_step_draws / _hyper / _beta change neither what bdf_gibbs_recorded reports nor the current buffer -- on the native
+    path's object, after an iteration of bdf_gibbs_sweep and before one"""
+    from bdf_amd._lib import check, lib
+    u, w = B.Entity("u", F=np.random.default_rng(9).standard_normal((NU, 5))), B.Entity("w")
+    rd, eng = _engine(B, _relation(B, "r", u, w, (NU, NW), NNZ_STEP, 1))
+    L, g = lib(), eng._gibbs
+
+    def books():
+        out = []
+        for j in range(len(eng.ent)):
+            hy, be, cur = C.c_int(-1), C.c_int(-1), C.c_int(-1)
+            check(L.bdf_gibbs_recorded(g, j, C.byref(hy), C.byref(be)))
+            check(L.bdf_gibbs_current(g, j, C.byref(cur)))
+            out.append((hy.value, be.value, cur.value))
+        return out
+
+    try:
+        assert eng.native
+        for want in ([(0, 0, 0), (0, 0, 0)], [(1, 1, 1), (1, 0, 1)]):
+            assert books() == want
+            for j in range(len(eng.ent)):
+                check(L.bdf_gibbs_step_draws(g, j))
+                check(L.bdf_gibbs_step_hyper(g, j, 1))
+                check(L.bdf_gibbs_step_hyper(g, j, 0))
+                check(L.bdf_gibbs_step_beta(g, j))
+            eng.sync()
+            assert books() == want
+            eng.sweep(1)
+            eng.sync()
     finally:
         eng.close()
