@@ -424,35 +424,32 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
                         "bdf_gibbs_set_relations: relation %d mode %d names entity %d", k, m, r.entity_of_mode[m]);
         BDF_REQUIRE(r.bg_weight >= 0.0 && r.bg_weight <= 1.0 && std::isfinite(r.bg_value), BDF_ERR_ARG,
                     "bdf_gibbs_set_relations: relation %d: bg_weight=%g must be 0 (none) or in (0, 1] and bg_value=%g finite", k, r.bg_weight, r.bg_value);
-        if (r.bg_weight > 0.0) {
-            BDF_REQUIRE(r.rel->n_modes == 2 && r.bg_sums, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: a background takes a two-mode relation and the bg_sums buffer", k);
+        // a folded relation: its unlisted cells reach the rows through the prior (a background; a dense relation,
+        // section 25).  What both need is stated once; what differs follows.
+        const bool bg = r.bg_weight > 0.0, dense = r.dense_R != nullptr;
+        if (bg || dense) {
+            const char *what = dense ? "a dense relation" : "a background";
+            BDF_REQUIRE(r.rel->n_modes == 2 && (dense ? r.dense_sums : r.bg_sums), BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: %s takes a two-mode relation and the %s buffer", k, what, dense ? "dense_sums" : "bg_sums");
             BDF_REQUIRE(!r.probit && !r.censor && !r.interval && !r.ordinal && r.robust_nu == 0.0 && !r.pg_model && !r.feat && !g->comm, BDF_ERR_ARG,
-                        "bdf_gibbs_set_relations: relation %d: a background takes neither the probit, censored, interval, ordinal, robust or a Polya-Gamma model, relation features nor a communicator", k);
-            BDF_REQUIRE(!r.obs_precision || (r.linear && r.bg_weights), BDF_ERR_ARG,
-                        "bdf_gibbs_set_relations: relation %d: a background with observation weights needs the linear and the bg_weights buffer", k);
+                        "bdf_gibbs_set_relations: relation %d: %s takes neither the probit, censored, interval, ordinal, robust or a Polya-Gamma model, relation features nor a communicator", k, what);
             for (int m = 0; m < 2; m++) {
                 const bdf_gibbs_entity &e = g->ent[(size_t)r.entity_of_mode[m]].d;
-                BDF_REQUIRE(e.bg_Lambda && e.bg_mu && e.bg_pack && e.bg_alpha_rows, BDF_ERR_ARG,
-                            "bdf_gibbs_set_relations: relation %d has a background but entity %d has a NULL bg_Lambda / bg_mu / bg_pack / bg_alpha_rows", k, r.entity_of_mode[m]);
+                BDF_REQUIRE(e.bg_Lambda && e.bg_mu && e.bg_alpha_rows && (dense || e.bg_pack) && !(dense && e.spike), BDF_ERR_ARG,
+                            "bdf_gibbs_set_relations: relation %d is %s but entity %d has a NULL bg_Lambda / bg_mu / bg_alpha_rows%s", k, what, r.entity_of_mode[m],
+                            dense ? ", or the spike-and-slab prior" : " / bg_pack");
             }
         }
-    }
-    for (int k = 0; k < n_relations; k++) {
-        const bdf_gibbs_relation &r = rels[k];
-        if (!r.dense_R) continue;
-        BDF_REQUIRE(r.rel->n_modes == 2 && r.dense_C && r.dense_sums, BDF_ERR_ARG,
-                    "bdf_gibbs_set_relations: relation %d: a dense relation takes a two-mode relation and the dense_C and dense_sums buffers", k);
-        BDF_REQUIRE(!r.probit && !r.censor && !r.interval && !r.ordinal && r.robust_nu == 0.0 && !r.pg_model && !r.obs_precision && r.noise_mode == 0 &&
-                    !(r.bg_weight > 0.0) && !r.feat && !g->comm, BDF_ERR_ARG,
-                    "bdf_gibbs_set_relations: relation %d: a dense relation takes no noise model, observation weights, background, relation features nor a communicator", k);
-        BDF_REQUIRE(r.rel->nnz == 0, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d is dense: `rel` must list no cell (its values live in dense_R)", k);
-        BDF_REQUIRE(!r.dense_holes || (r.dense_stats && r.dense_holes->n_modes == 2), BDF_ERR_ARG,
-                    "bdf_gibbs_set_relations: relation %d: dense_holes needs two modes and the dense_stats buffer", k);
-        BDF_REQUIRE(std::isfinite(r.dense_sum_r2) && r.dense_sum_r2 >= 0.0, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: dense_sum_r2=%g", k, r.dense_sum_r2);
-        for (int m = 0; m < 2; m++) {
-            const bdf_gibbs_entity &e = g->ent[(size_t)r.entity_of_mode[m]].d;
-            BDF_REQUIRE(e.bg_Lambda && e.bg_mu && e.bg_alpha_rows && !e.spike, BDF_ERR_ARG,
-                        "bdf_gibbs_set_relations: relation %d is dense but entity %d has a NULL bg_Lambda / bg_mu / bg_alpha_rows, or the spike-and-slab prior", k, r.entity_of_mode[m]);
+        BDF_REQUIRE(!bg || !r.obs_precision || (r.linear && r.bg_weights), BDF_ERR_ARG,
+                    "bdf_gibbs_set_relations: relation %d: a background with observation weights needs the linear and the bg_weights buffer", k);
+        if (dense) {
+            BDF_REQUIRE(r.dense_C, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: a dense relation takes the dense_C buffer", k);
+            BDF_REQUIRE(!r.obs_precision && r.noise_mode == 0 && !bg, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: a dense relation takes no observation weights, per-row noise model nor background", k);
+            BDF_REQUIRE(r.rel->nnz == 0, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d is dense: `rel` must list no cell (its values live in dense_R)", k);
+            BDF_REQUIRE(!r.dense_holes || (r.dense_stats && r.dense_holes->n_modes == 2), BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: dense_holes needs two modes and the dense_stats buffer", k);
+            BDF_REQUIRE(std::isfinite(r.dense_sum_r2) && r.dense_sum_r2 >= 0.0, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: dense_sum_r2=%g", k, r.dense_sum_r2);
         }
     }
     g->rels.assign(rels, rels + n_relations);
@@ -488,33 +485,45 @@ void current_factors(const bdf_gibbs *g, const int32_t *entity_of_mode, int n_mo
     }
 }
 
-// the registered relation of entity e's term t when it has background cells (bdf_gibbs_relation.bg_weight), or NULL
-const bdf_gibbs_relation *background_of(const bdf_gibbs *g, const bdf_gibbs_entity &e, int t)
+// the registered relation of entity e's term t when the term is folded into the prior -- the relation has background cells
+// (bdf_gibbs_relation.bg_weight) or is dense (dense_R) -- or NULL
+const bdf_gibbs_relation *folded_of(const bdf_gibbs *g, const bdf_gibbs_entity &e, int t)
 {
     const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel);
-    return (gr && gr->bg_weight > 0.0) ? gr : nullptr;
+    return (gr && (gr->bg_weight > 0.0 || gr->dense_R)) ? gr : nullptr;
 }
 
-// ... when it is a dense relation (bdf_gibbs_relation.dense_R), or NULL
-const bdf_gibbs_relation *dense_of(const bdf_gibbs *g, const bdf_gibbs_entity &e, int t)
-{
-    const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel);
-    return (gr && gr->dense_R) ? gr : nullptr;
-}
+// a folded relation's sums: per mode, the sum of the entity's rows (D) and their Gram matrix (D x D)
+inline double *fold_sums(const bdf_gibbs_relation &r) { return r.dense_R ? r.dense_sums : r.bg_sums; }
 
-// is a term of entity e folded into its prior (a background or a dense relation)?  Such an entity's prior is made on the row stream.
+// is a term of entity e folded into its prior?  Such an entity's prior is made on the row stream.
 bool folds_prior(const bdf_gibbs *g, const bdf_gibbs_entity &e)
 {
     for (int t = 0; t < e.n_terms; t++)
-        if (background_of(g, e, t) || dense_of(g, e, t)) return true;
+        if (folded_of(g, e, t)) return true;
     return false;
 }
 
-// The prior that entity E's rows are sampled with: the hyperprior's draw as it stands -- or, when relations of the entity have
-// background cells, that draw with their Gram terms folded in.  Per background term, in the order of the
-// entity's terms: the sum and the Gram matrix of the OTHER entity's current rows into the relation's own buffers (bdf_hyper_sums on
-// the row stream), then one bdf_background_prior into the entity's (bg_mu, bg_Lambda, bg_pack) and bg_alpha_rows, which
-// fill_terms hands the terms with unit weights.  pack_valid: the entity's latest draw has left its prior pack.
+// bdf_hyper_sums of both entities' current rows into a folded relation's sums, for its sum of squares over all cells
+int both_sums(bdf_gibbs *g, const bdf_gibbs_relation &r, const double *const *fac)
+{
+    const int D = g->D;
+    const size_t pk = (size_t)D + (size_t)D * D;
+    for (int m = 0; m < 2; m++) {
+        double *s = fold_sums(r) + m * pk;
+        int rc = bdf_hyper_sums(g->rows, D, g->ent[(size_t)r.entity_of_mode[m]].d.N, fac[m], nullptr, s, s + D);
+        if (rc) return rc;
+    }
+    return BDF_OK;
+}
+
+// The prior that entity E's rows are sampled with: the hyperprior's draw as it stands -- or, when terms of the entity are folded
+// (background cells; dense relations, section 25), that draw with their Gram terms folded in.  Per folded
+// term, in the order of the entity's terms: the sum and the Gram matrix of the OTHER entity's current rows into the relation's own
+// buffers (bdf_hyper_sums on the row stream) and, for a dense term, its rows of R V (R' U) from the same rows.  Then one fold into
+// the entity's (bg_mu, bg_Lambda) and bg_alpha_rows, which fill_terms hands the terms with unit weights: bdf_dense_prior when a
+// dense term is among them (the means are then one per row), else bdf_background_prior, which also leaves bg_pack for a shared
+// mean.  pack_valid: the entity's latest draw has left its prior pack.
 int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, bool pack_valid, const double **mu, int *mu_is_matrix, const double **Lambda, const double **pack)
 {
     const bdf_gibbs_entity &e = E.d;
@@ -523,51 +532,36 @@ int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, bool pack_valid, const doub
     *mu_is_matrix = e.feat ? 1 : 0;
     *Lambda = e.Lambda;
     *pack = (pack_valid && !e.feat) ? e.prior_pack : nullptr;
-    bool dense = false;
-    for (int t = 0; t < e.n_terms; t++) dense = dense || dense_of(g, e, t) != nullptr;
-    if (dense) {
-        // a dense relation among the entity's terms: per dense term also its rows of R V (R' U) from the other
-        // entity's current rows, then one bdf_dense_prior over the dense and the background terms; the means are then one per row
-        bdf_dense_term dt[BDF_MAX_TERMS];
-        int n = 0, rc;
-        for (int t = 0; t < e.n_terms; t++) {
-            const bdf_gibbs_relation *gd = dense_of(g, e, t), *gb = background_of(g, e, t);
-            if (!gd && !gb) continue;
-            const int mode = e.terms[t].mode, other = 1 - mode;
-            const auto &O = g->ent[(size_t)e.terms[t].entity_of_mode[other]];
-            double *s = (gd ? gd->dense_sums : gb->bg_sums) + (size_t)other * ((size_t)D + (size_t)D * D);
-            if ((rc = bdf_hyper_sums(g->rows, D, O.d.N, O.d.sample[O.cur], nullptr, s, s + D))) return rc;
-            dt[n] = {};
-            dt[n].gram = s + D; dt[n].alpha = 0.0; dt[n].alpha_dev = (gd ? gd : gb)->alpha_dev;
-            if (gd) {
-                double *C = gd->dense_C + (mode == 0 ? (size_t)0 : (size_t)gd->rel->dims[0] * D);
-                if ((rc = bdf_dense_product(g->rows, gd->dense_R, gd->rel->dims[0], gd->rel->dims[1], D, O.d.sample[O.cur], mode, C))) return rc;
-                dt[n].C = C; dt[n].weight = 1.0;
-            } else {
-                dt[n].sum = s; dt[n].weight = gb->bg_weight; dt[n].resid = gb->bg_value - gb->mean_value;
-            }
-            n++;
+    bdf_dense_term dt[BDF_MAX_TERMS];
+    int n = 0, n_dense = 0, rc;
+    for (int t = 0; t < e.n_terms; t++) {
+        const bdf_gibbs_relation *gr = folded_of(g, e, t);
+        if (!gr) continue;
+        const int mode = e.terms[t].mode, other = 1 - mode;
+        const auto &O = g->ent[(size_t)e.terms[t].entity_of_mode[other]];
+        double *s = fold_sums(*gr) + (size_t)other * ((size_t)D + (size_t)D * D);
+        if ((rc = bdf_hyper_sums(g->rows, D, O.d.N, O.d.sample[O.cur], nullptr, s, s + D))) return rc;
+        dt[n] = {};
+        dt[n].gram = s + D; dt[n].alpha_dev = gr->alpha_dev;
+        if (gr->dense_R) {
+            double *C = gr->dense_C + (mode == 0 ? (size_t)0 : (size_t)gr->rel->dims[0] * D);
+            if ((rc = bdf_dense_product(g->rows, gr->dense_R, gr->rel->dims[0], gr->rel->dims[1], D, O.d.sample[O.cur], mode, C))) return rc;
+            dt[n].C = C; dt[n].weight = 1.0;
+            n_dense++;
+        } else {
+            dt[n].sum = s; dt[n].weight = gr->bg_weight; dt[n].resid = gr->bg_value - gr->mean_value;
         }
+        n++;
+    }
+    if (n == 0) return BDF_OK;
+    if (n_dense > 0) {
         if ((rc = bdf_dense_prior(g->rows, D, e.N, n, dt, *mu, *mu_is_matrix, e.Lambda, e.bg_Lambda, e.bg_mu, e.bg_alpha_rows))) return rc;
         *mu = e.bg_mu; *mu_is_matrix = 1; *Lambda = e.bg_Lambda; *pack = nullptr;
         return BDF_OK;
     }
-    bdf_background_term bg[BDF_MAX_TERMS];
-    int n_bg = 0, rc;
-    for (int t = 0; t < e.n_terms; t++) {
-        const bdf_gibbs_relation *gr = background_of(g, e, t);
-        if (!gr) continue;
-        const int other = 1 - e.terms[t].mode;
-        const auto &O = g->ent[(size_t)e.terms[t].entity_of_mode[other]];
-        double *s = gr->bg_sums + (size_t)other * ((size_t)D + (size_t)D * D);
-        if ((rc = bdf_hyper_sums(g->rows, D, O.d.N, O.d.sample[O.cur], nullptr, s, s + D))) return rc;
-        bg[n_bg].sum = s; bg[n_bg].gram = s + D; bg[n_bg].alpha = 0.0; bg[n_bg].alpha_dev = gr->alpha_dev;
-        bg[n_bg].weight = gr->bg_weight; bg[n_bg].resid = gr->bg_value - gr->mean_value;
-        n_bg++;
-    }
-    if (n_bg == 0) return BDF_OK;
-    if ((rc = bdf_background_prior(g->rows, D, e.N, n_bg, bg, *mu, e.feat ? 1 : 0, e.Lambda, e.bg_Lambda, e.bg_mu, e.feat ? nullptr : e.bg_pack,
-                                   e.bg_alpha_rows)))
+    bdf_background_term bg[BDF_MAX_TERMS];             // (background terms alone: the entry point with the pack, and its own term type)
+    for (int k = 0; k < n; k++) bg[k] = {dt[k].sum, dt[k].gram, 0.0, dt[k].alpha_dev, dt[k].weight, dt[k].resid};
+    if ((rc = bdf_background_prior(g->rows, D, e.N, n, bg, *mu, *mu_is_matrix, e.Lambda, e.bg_Lambda, e.bg_mu, e.feat ? nullptr : e.bg_pack, e.bg_alpha_rows)))
         return rc;
     *mu = e.bg_mu; *Lambda = e.bg_Lambda; *pack = e.feat ? nullptr : e.bg_pack;
     return BDF_OK;
@@ -577,7 +571,7 @@ int row_prior(bdf_gibbs *g, const bdf_gibbs::Ent &E, bool pack_valid, const doub
 // obs_precision
 void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
 {
-    int n_bg = 0;
+    int n_folded = 0;                                        // (the folded terms before this one: its place in bg_alpha_rows)
     for (int t = 0; t < e.n_terms; t++) {
         terms[t].rel = e.terms[t].rel; terms[t].mode = e.terms[t].mode; terms[t]._pad = 0;
         terms[t].alpha = e.terms[t].alpha; terms[t].mean_value = e.terms[t].mean_value; terms[t].linear_values = nullptr;
@@ -591,10 +585,10 @@ void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
                 // background cells: the listed ones count with omega_k - c0 and the pseudo-residual through `linear` (both constant),
                 // or -- unit weights, the unweighted kernels -- with alpha (1 - c0), which row_prior's fold has left on the device
                 if (gr->obs_precision) terms[t].linear_values = gr->linear;
-                else terms[t].alpha_dev = e.bg_alpha_rows + n_bg;
-                n_bg++;
-            } else if (gr->dense_R) n_bg++;                  // (a dense term is folded too, and shares bg_alpha_rows; none of its cells is listed)
+                else terms[t].alpha_dev = e.bg_alpha_rows + n_folded;
+            }
         }
+        if (folded_of(g, e, t)) n_folded++;                  // (a dense term is folded too, and shares bg_alpha_rows; none of its cells is listed)
         for (int k = 0; k < BDF_MAX_MODES; k++) terms[t].factors[k] = nullptr;
         current_factors(g, e.terms[t].entity_of_mode, e.terms[t].rel->n_modes, terms[t].factors);
     }
@@ -631,20 +625,17 @@ int update_relations(bdf_gibbs *g)
             int64_t n = r.nnz;
             if (r.bg_weight > 0.0) {
                 // background cells: the sum of c e^2 over ALL N M cells from the listed ones, the two entities' sums and Gram matrices
-                const size_t pk = (size_t)D + (size_t)D * D;
-                for (int m = 0; m < 2; m++)
-                    if ((rc = bdf_hyper_sums(R, D, g->ent[(size_t)r.entity_of_mode[m]].d.N, fac[m], nullptr, r.bg_sums + m * pk, r.bg_sums + m * pk + D))) return rc;
-                rc = bdf_background_sse(R, r.train, D, fac, r.mean_value, r.bg_weights, r.bg_value, r.bg_weight, r.bg_sums, r.bg_sums + D, r.bg_sums + pk,
-                                        r.bg_sums + pk + D, r.rel->dims[0], r.rel->dims[1], g->rel_sse + 1);
+                const double *s = fold_sums(r), *s1 = s + D + (size_t)D * D;
+                if ((rc = both_sums(g, r, fac))) return rc;
+                rc = bdf_background_sse(R, r.train, D, fac, r.mean_value, r.bg_weights, r.bg_value, r.bg_weight, s, s + D, s1, s1 + D, r.rel->dims[0],
+                                        r.rel->dims[1], g->rel_sse + 1);
                 n = r.rel->dims[0] * r.rel->dims[1];
             } else if (r.dense_R) {
                 // dense: the closed form over all N M cells from C = R V and the two entities' Gram matrices
-                const size_t pk = (size_t)D + (size_t)D * D;
-                for (int m = 0; m < 2; m++)
-                    if ((rc = bdf_hyper_sums(R, D, g->ent[(size_t)r.entity_of_mode[m]].d.N, fac[m], nullptr, r.dense_sums + m * pk, r.dense_sums + m * pk + D))) return rc;
+                const double *s = fold_sums(r), *s1 = s + D + (size_t)D * D;
+                if ((rc = both_sums(g, r, fac))) return rc;
                 if ((rc = bdf_dense_product(R, r.dense_R, r.rel->dims[0], r.rel->dims[1], D, fac[1], 0, r.dense_C))) return rc;
-                rc = bdf_dense_sse(R, D, r.rel->dims[0], fac[0], r.dense_C, r.dense_sums + D, r.dense_sums + pk + D, r.dense_sum_r2,
-                                   r.dense_holes ? r.dense_stats : nullptr, g->rel_sse + 1);
+                rc = bdf_dense_sse(R, D, r.rel->dims[0], fac[0], r.dense_C, s + D, s1 + D, r.dense_sum_r2, r.dense_holes ? r.dense_stats : nullptr, g->rel_sse + 1);
                 n = r.rel->dims[0] * r.rel->dims[1];
             } else if (r.obs_precision) rc = (r.robust_nu > 0.0 || r.noise_mode != 0) ? BDF_OK : bdf_pairs_weighted_sse(R, r.train, D, fac, r.mean_value, r.obs_precision, g->rel_sse + 1);
             else rc = bdf_predict_sse(R, r.train, D, fac, r.mean_value, nullptr, g->rel_sse);

@@ -10,6 +10,8 @@
 //   bdf_background_sse     k_bg_sse: the gather of bdf_pairs_weighted_sse with the listed cell's second term, then one workgroup adds
 //                          the workgroups' sums, the Gram inner product and the closed-form remainder in a fixed order.
 //
+// What k_bg_fold shares with k_dmat_fold of k_dense.hip -- the term record and its checks, Lambda_eff and its factorisation, the
+// refined solve, the closing kernels' four-wave sum -- is written once in prior_fold.h.
 // Every solve takes one step of iterative refinement: the pivots' reciprocals are good to 1.5e-15 (fast_rcp), and what the rows
 // read is Lambda_eff mu_eff, the solve's right-hand side again -- its residual, not its forward error, is what reaches them.
 // Plain vector stores, no floating-point atomics; no scratch memory except k_bg_fold<64>'s 528 bytes per lane, which wl_factor<64>
@@ -17,6 +19,7 @@
 #include "bdf_common.h"
 #include "background.h"
 #include "pair_gather.h"
+#include "prior_fold.h"
 #include "rows.h"
 #include "wave_linalg.h"
 
@@ -25,31 +28,16 @@ namespace {
 typedef double bd2 __attribute__((ext_vector_type(2)));
 typedef double bd4 __attribute__((ext_vector_type(4)));
 
-struct FoldArgs {
-    int D, n_bg;
-    bdf_background_term t[BDF_MAX_TERMS];
-    const double *mu;          // nullable: per-row prior means -- T_out and w0_out are written instead of mu_out and the pack
-    const double *Lambda;
-    double *Lambda_out, *mu_out, *pack_out, *alpha_rows_out;
+// the fold's own outputs behind the shared head (prior_fold.h)
+struct BgFoldArgs : FoldHead {       // mu NULL: per-row prior means -- T_out and w0_out are written instead of mu_out and the pack
+    double *mu_out, *pack_out;
     double *T_out, *w0_out;    // T[e * DP + d] = W[d][e] (DP x DP row-major, zero outside D x D), w0 (DP, zero behind D)
-    int *flag;
 };
 
-// x = A^-1 b for the factored A (lane c of a group holds b_c and gets x_c; the groups of a wave solve side by side), refined once:
-// r = b - A x with A from LDS (sA[c + k * DP] = A[k][c] = A[c][k]), x += A^-1 r
+// fold_head (prior_fold.h) builds and factors Lambda_eff; what follows is the background's own: the shared mean with the prior pack,
+// or W and w0 for per-row prior means
 template <int DP>
-__device__ __forceinline__ double bg_solve(const double (&fac)[DP], const double *tri, const double *sA, double rp_own, double b, int lane)
-{
-    const int c = lane % DP, base = (lane / DP) * DP;
-    const double x = wl_backward<DP, true>(tri, wl_forward<DP>(fac, b, rp_own, lane), rp_own, lane);
-    double r = b;
-#pragma unroll
-    for (int k = 0; k < DP; k++) r = fma(-sA[c + k * DP], __shfl(x, base + k), r);
-    return x + wl_backward<DP, true>(tri, wl_forward<DP>(fac, r, rp_own, lane), rp_own, lane);
-}
-
-template <int DP>
-__global__ __launch_bounds__(64) void k_bg_fold(FoldArgs a)
+__global__ __launch_bounds__(64) void k_bg_fold(BgFoldArgs a)
 {
     using W = WL<DP>;
     constexpr int G = W::G;
@@ -59,50 +47,19 @@ __global__ __launch_bounds__(64) void k_bg_fold(FoldArgs a)
     const int lane = threadIdx.x, c = lane % DP, grp = lane / DP;
     const int D = a.D;
     const bool in = c < D;
-    double ac[BDF_MAX_TERMS];               // alpha_k c0_k
-#pragma unroll
-    for (int k = 0; k < BDF_MAX_TERMS; k++) {
-        ac[k] = 0.0;
-        if (k < a.n_bg) {
-            const double alpha = a.t[k].alpha_dev ? *a.t[k].alpha_dev : a.t[k].alpha;
-            ac[k] = alpha * a.t[k].weight;
-            if (lane == k) a.alpha_rows_out[k] = bdf_bg_alpha_rows(alpha, a.t[k].weight);
-        }
-    }
-    // column c of Lambda_eff, the terms added in the order of bg[]
-    double col[DP];
-#pragma unroll
-    for (int i = 0; i < DP; i++) {
-        double v = (i == c) ? 1.0 : 0.0;
-        if (i < D && in) {
-            v = a.Lambda[i + (int64_t)c * D];
-#pragma unroll
-            for (int k = 0; k < BDF_MAX_TERMS; k++)
-                if (k < a.n_bg) v = v + ac[k] * a.t[k].gram[i + (int64_t)c * D];
-            if (grp == 0) a.Lambda_out[i + (int64_t)c * D] = v;
-        }
-        col[i] = v;
-        if (grp == 0) sA[i + c * DP] = v;
-    }
-    // the background's part of the right-hand side: sum_k alpha_k c0_k rb_k s_k
-    double t_c = 0.0;
-#pragma unroll
-    for (int k = 0; k < BDF_MAX_TERMS; k++)
-        if (k < a.n_bg && in) t_c = t_c + (ac[k] * a.t[k].resid) * a.t[k].sum[c];
-    wave_sync();
-    double p_own, rp_own;
-    if (wl_factor<DP, true>(col, p_own, rp_own, tri, lane) && lane == 0) atomicOr_system(a.flag, 1);
+    double ac[BDF_MAX_TERMS], col[DP], t_c, p_own, rp_own;
+    fold_head<DP>(a, true, ac, col, t_c, p_own, rp_own, tri, sA, lane);
 
     if (a.mu == nullptr) {
         // per-row prior means: W = Lambda_eff^-1 Lambda by columns, G of them side by side, and w0 = Lambda_eff^-1 t
         for (int q0 = 0; q0 < D; q0 += G) {
             const int q = q0 + grp;
             const double b = (q < D && in) ? a.Lambda[c + (int64_t)q * D] : 0.0;
-            const double x = bg_solve<DP>(col, tri, sA, rp_own, b, lane);
+            const double x = fold_solve<DP>(col, tri, sA, rp_own, b, lane);
             if (q < D) a.T_out[q * DP + c] = in ? x : 0.0;
         }
         for (int q = D + grp; q < DP; q += G) a.T_out[q * DP + c] = 0.0;
-        const double x0 = bg_solve<DP>(col, tri, sA, rp_own, t_c, lane);
+        const double x0 = fold_solve<DP>(col, tri, sA, rp_own, t_c, lane);
         if (grp == 0) a.w0_out[c] = in ? x0 : 0.0;
         return;
     }
@@ -110,7 +67,7 @@ __global__ __launch_bounds__(64) void k_bg_fold(FoldArgs a)
     double b = t_c;
     if (in)
         for (int i = 0; i < D; i++) b = fma(a.Lambda[c + (int64_t)i * D], a.mu[i], b);
-    const double x = bg_solve<DP>(col, tri, sA, rp_own, b, lane);
+    const double x = fold_solve<DP>(col, tri, sA, rp_own, b, lane);
     if (grp == 0) {
         if (in) a.mu_out[c] = x;
         s_mu[c] = in ? x : 0.0;
@@ -238,17 +195,6 @@ __global__ __launch_bounds__(256, 3) void k_bg_sse(BgSseArgs a)
     if (tid == 0) a.partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// a workgroup's sum of one value per thread, in a fixed order; valid in thread 0
-__device__ __forceinline__ double block_sum(double v, double *red)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();                                   // (red may still be read from the previous sum)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 // the workgroups' sums, (sum U).(sum V) and <U U', V V'> added in a fixed order, then the closed form
 __global__ __launch_bounds__(256) void k_bg_sse_final(int nblocks, const double *partial, int D, const double *sumU, const double *gramU,
                                                       const double *sumV, const double *gramV, double c0, double rb, double cells, double *out)
@@ -259,9 +205,9 @@ __global__ __launch_bounds__(256) void k_bg_sse_final(int nblocks, const double 
     for (int b = tid; b < nblocks; b += 256) s += partial[b];
     for (int e = tid; e < D; e += 256) d = fma(sumU[e], sumV[e], d);
     for (int e = tid; e < D * D; e += 256) g = fma(gramU[e], gramV[e], g);
-    s = block_sum(s, red);
-    d = block_sum(d, red);
-    g = block_sum(g, red);
+    s = block_sum4(s, red);
+    d = block_sum4(d, red);
+    g = block_sum4(g, red);
     if (tid == 0) *out = s + bdf_bg_all_cells(c0, cells, rb, d, g);
 }
 
@@ -270,31 +216,15 @@ __global__ __launch_bounds__(256) void k_bg_sse_final(int nblocks, const double 
 extern "C" int bdf_background_prior(bdf_ctx *ctx, int D, int64_t N, int n_bg, const bdf_background_term *bg, const double *mu, int mu_is_matrix,
                                     const double *Lambda, double *Lambda_out, double *mu_out, double *prior_pack_out, double *alpha_rows_out)
 {
-    BDF_REQUIRE(ctx && bg && mu && Lambda && Lambda_out && mu_out && alpha_rows_out, BDF_ERR_ARG, "bdf_background_prior: NULL argument");
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_background_prior: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    BDF_REQUIRE(n_bg >= 1 && n_bg <= BDF_MAX_TERMS, BDF_ERR_ARG, "bdf_background_prior: %d background terms (1..%d)", n_bg, BDF_MAX_TERMS);
-    BDF_REQUIRE(N >= 0, BDF_ERR_ARG, "bdf_background_prior: N < 0");
-    BDF_REQUIRE(Lambda_out != Lambda && mu_out != mu, BDF_ERR_ARG, "bdf_background_prior: the outputs may not alias mu and Lambda");
     BDF_REQUIRE(!(mu_is_matrix && prior_pack_out), BDF_ERR_ARG, "bdf_background_prior: per-row prior means have no prior pack");
-    FoldArgs a = {};
-    a.D = D; a.n_bg = n_bg;
-    for (int k = 0; k < n_bg; k++) {
-        const bdf_background_term &t = bg[k];
-        BDF_REQUIRE(t.sum && t.gram, BDF_ERR_ARG, "bdf_background_prior: term %d has no sum or Gram matrix", k);
-        BDF_REQUIRE(t.weight > 0.0 && t.weight <= 1.0 && std::isfinite(t.resid), BDF_ERR_ARG,
-                    "bdf_background_prior: term %d: weight=%g must lie in (0, 1] and resid=%g be finite", k, t.weight, t.resid);
-        BDF_REQUIRE(t.alpha_dev || (t.alpha > 0.0 && std::isfinite(t.alpha)), BDF_ERR_ARG, "bdf_background_prior: term %d: alpha=%g must be positive and finite", k, t.alpha);
-        a.t[k] = t;
-    }
-    BDF_HIP(hipSetDevice(ctx->device));
+    BgFoldArgs a = {};
+    int rc = fold_fill("bdf_background_prior", ctx, D, N, n_bg, bg, mu, mu_is_matrix, Lambda, Lambda_out, mu_out, alpha_rows_out, a);
+    if (rc) return rc;
     const int DP = bdf_rows_dp(D);
-    a.mu = mu_is_matrix ? nullptr : mu;
-    a.Lambda = Lambda; a.Lambda_out = Lambda_out; a.mu_out = mu_out; a.pack_out = prior_pack_out; a.alpha_rows_out = alpha_rows_out;
-    a.flag = ctx->flag_dev;
+    a.mu_out = mu_out; a.pack_out = prior_pack_out;
     if (mu_is_matrix) {
         void *sc;
-        int rc = bdf_scratch(ctx, ((size_t)DP * DP + DP) * sizeof(double), &sc);
-        if (rc) return rc;
+        if ((rc = bdf_scratch(ctx, ((size_t)DP * DP + DP) * sizeof(double), &sc))) return rc;
         a.T_out = (double *)sc; a.w0_out = a.T_out + (size_t)DP * DP;
     }
     if (DP == 16) hipLaunchKernelGGL(k_bg_fold<16>, dim3(1), dim3(64), 0, ctx->stream, a);

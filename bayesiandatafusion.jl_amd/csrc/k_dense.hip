@@ -16,12 +16,15 @@
 //   bdf_dense_sse       sum over all cells of (r - u.v)^2 = sum r^2 - 2 sum_i u_i.C_i + <U'U, V'V>: the workgroups' sums of u_i.C_i,
 //                       then one workgroup adds them, the Gram inner product and the closed form in a fixed order.
 //
+// What k_dmat_fold shares with k_bg_fold -- the term record and its checks, Lambda_eff and its factorisation, the refined solve, the
+// closing kernels' four-wave sum -- is written once in prior_fold.h.
 // Plain vector stores, no floating-point atomics; no scratch memory except k_dmat_fold<64>'s, which wl_factor<64> brings to every
 // kernel that takes it.  Every sum has a fixed order: a rerun gives the same bits.
 #include "bdf_common.h"
 #include "dense.h"
 #include "pair_gather.h"
 #include "predict.h"
+#include "prior_fold.h"
 #include "rows.h"
 #include "wave_linalg.h"
 
@@ -115,29 +118,15 @@ __global__ __launch_bounds__(64 * PW) void k_dmat_product(const double *__restri
 }
 
 // ---- the prior of a dense entity ----------------------------------------------------------------------------------------------------
-struct DenseFoldArgs {
-    int D, n;
-    bdf_dense_term t[BDF_MAX_TERMS];
-    const double *mu;          // nullable: per-row prior means -- Wt_out is written too
-    const double *Lambda;
-    double *Lambda_out, *alpha_rows_out, *coef_out;
+// the fold's own outputs behind the shared head (prior_fold.h)
+struct DenseFoldArgs : FoldHead {       // mu NULL: per-row prior means -- Wt_out is written too
+    double *coef_out;          // alpha_k weight_k of the terms, for k_dmat_mu_rows
     double *Ti_out, *Wt_out;   // [e * DP + d] = (Lambda_eff^-1)[d][e], (Lambda_eff^-1 Lambda)[d][e]: DP x DP row-major, zero outside D x D
     double *w0_out;            // DP, zero behind D: Lambda_eff^-1 (Lambda mu + t), or Lambda_eff^-1 t for per-row prior means
-    int *flag;
 };
 
-// x = A^-1 b for the factored A, refined once with A from LDS: bg_solve of k_background.hip
-template <int DP>
-__device__ __forceinline__ double dense_solve(const double (&fac)[DP], const double *tri, const double *sA, double rp_own, double b, int lane)
-{
-    const int c = lane % DP, base = (lane / DP) * DP;
-    const double x = wl_backward<DP, true>(tri, wl_forward<DP>(fac, b, rp_own, lane), rp_own, lane);
-    double r = b;
-#pragma unroll
-    for (int k = 0; k < DP; k++) r = fma(-sA[c + k * DP], __shfl(x, base + k), r);
-    return x + wl_backward<DP, true>(tri, wl_forward<DP>(fac, r, rp_own, lane), rp_own, lane);
-}
-
+// fold_head (prior_fold.h) builds and factors Lambda_eff in every workgroup; what follows is the dense fold's own: the columns of the
+// inverse over the workgroups
 template <int DP>
 __global__ __launch_bounds__(64) void k_dmat_fold(DenseFoldArgs a)
 {
@@ -148,50 +137,21 @@ __global__ __launch_bounds__(64) void k_dmat_fold(DenseFoldArgs a)
     const int lane = threadIdx.x, c = lane % DP, grp = lane / DP;
     const int D = a.D;
     const bool in = c < D;
-    double ac[BDF_MAX_TERMS];               // alpha_k c_k
-#pragma unroll
-    for (int k = 0; k < BDF_MAX_TERMS; k++) {
-        ac[k] = 0.0;
-        if (k < a.n) {
-            const double alpha = a.t[k].alpha_dev ? *a.t[k].alpha_dev : a.t[k].alpha;
-            ac[k] = alpha * a.t[k].weight;
-            if (lane == k && blockIdx.x == gridDim.x - 1) {
-                a.coef_out[k] = ac[k];
-                a.alpha_rows_out[k] = a.t[k].C ? alpha : alpha * (1.0 - a.t[k].weight);
-            }
-        }
-    }
-    double col[DP];
-#pragma unroll
-    for (int i = 0; i < DP; i++) {
-        double v = (i == c) ? 1.0 : 0.0;
-        if (i < D && in) {
-            v = a.Lambda[i + (int64_t)c * D];
-#pragma unroll
-            for (int k = 0; k < BDF_MAX_TERMS; k++)
-                if (k < a.n) v = v + ac[k] * a.t[k].gram[i + (int64_t)c * D];
-            if (grp == 0 && blockIdx.x == gridDim.x - 1) a.Lambda_out[i + (int64_t)c * D] = v;
-        }
-        col[i] = v;
-        if (grp == 0) sA[i + c * DP] = v;
-    }
-    // the background terms' part of the right-hand side: sum_k alpha_k c0_k rb_k s_k
-    double t_c = 0.0;
+    const bool last = blockIdx.x == gridDim.x - 1;
+    double ac[BDF_MAX_TERMS], col[DP], t_c, p_own, rp_own;
+    fold_head<DP>(a, last, ac, col, t_c, p_own, rp_own, tri, sA, lane);
 #pragma unroll
     for (int k = 0; k < BDF_MAX_TERMS; k++)
-        if (k < a.n && a.t[k].sum && in) t_c = t_c + (ac[k] * a.t[k].resid) * a.t[k].sum[c];
-    wave_sync();
-    double p_own, rp_own;
-    if (wl_factor<DP, true>(col, p_own, rp_own, tri, lane) && lane == 0) atomicOr_system(a.flag, 1);
+        if (last && lane == k && k < a.n) a.coef_out[k] = ac[k];
 
     // Lambda_eff^-1 and, for per-row prior means, Lambda_eff^-1 Lambda by columns, G of them side by side in this workgroup: every
     // workgroup factors for itself (one wave's latency, not D / G of them in a row); the last one takes w0, the padding and Lambda_out
     if (blockIdx.x + 1 < gridDim.x) {
         const int q = (int)blockIdx.x * G + grp;
-        const double x = dense_solve<DP>(col, tri, sA, rp_own, (q < D && c == q) ? 1.0 : 0.0, lane);
+        const double x = fold_solve<DP>(col, tri, sA, rp_own, (q < D && c == q) ? 1.0 : 0.0, lane);
         if (q < D) a.Ti_out[q * DP + c] = in ? x : 0.0;
         if (a.mu == nullptr) {
-            const double xw = dense_solve<DP>(col, tri, sA, rp_own, (q < D && in) ? a.Lambda[c + (int64_t)q * D] : 0.0, lane);
+            const double xw = fold_solve<DP>(col, tri, sA, rp_own, (q < D && in) ? a.Lambda[c + (int64_t)q * D] : 0.0, lane);
             if (q < D) a.Wt_out[q * DP + c] = in ? xw : 0.0;
         }
         return;
@@ -203,7 +163,7 @@ __global__ __launch_bounds__(64) void k_dmat_fold(DenseFoldArgs a)
     double b = t_c;
     if (a.mu != nullptr && in)
         for (int i = 0; i < D; i++) b = fma(a.Lambda[c + (int64_t)i * D], a.mu[i], b);
-    const double x0 = dense_solve<DP>(col, tri, sA, rp_own, b, lane);
+    const double x0 = fold_solve<DP>(col, tri, sA, rp_own, b, lane);
     if (grp == 0) a.w0_out[c] = in ? x0 : 0.0;
 }
 
@@ -300,17 +260,6 @@ __global__ __launch_bounds__(256, 3) void k_dmat_impute(ImputeArgs a)
 // ---- the sum of e^2 over all N M cells ----------------------------------------------------------------------------------------------
 constexpr int DOT_SLAB = 4096;             // elements of U and C per workgroup of k_dmat_dot
 
-// a workgroup's sum of one value per thread, in a fixed order; valid in thread 0
-__device__ __forceinline__ double dense_block_sum(double v, double *red)
-{
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();                                   // (red may still be read from the previous sum)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void k_dmat_dot(const double *__restrict__ U, const double *__restrict__ C, int64_t n, double *partial)
 {
     __shared__ double red[4];
@@ -321,7 +270,7 @@ __global__ __launch_bounds__(256) void k_dmat_dot(const double *__restrict__ U, 
         const int64_t e = base + j * 256 + threadIdx.x;
         if (e < n) s = fma(U[e], C[e], s);
     }
-    s = dense_block_sum(s, red);
+    s = block_sum4(s, red);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -333,8 +282,8 @@ __global__ __launch_bounds__(256) void k_dmat_sse_final(int nblocks, const doubl
     double s = 0.0, g = 0.0;
     for (int b = tid; b < nblocks; b += 256) s += partial[b];
     for (int e = tid; e < D * D; e += 256) g = fma(gramU[e], gramV[e], g);
-    s = dense_block_sum(s, red);
-    g = dense_block_sum(g, red);
+    s = block_sum4(s, red);
+    g = block_sum4(g, red);
     if (tid == 0) *out = bdf_dense_all_cells(holes_r2 ? sum_r2 + *holes_r2 : sum_r2, s, g);
 }
 
@@ -368,36 +317,21 @@ extern "C" int bdf_dense_product(bdf_ctx *ctx, const double *R, int64_t N, int64
 extern "C" int bdf_dense_prior(bdf_ctx *ctx, int D, int64_t N, int n_terms, const bdf_dense_term *terms, const double *mu, int mu_is_matrix,
                                const double *Lambda, double *Lambda_out, double *mu_out, double *alpha_rows_out)
 {
-    BDF_REQUIRE(ctx && terms && mu && Lambda && Lambda_out && mu_out && alpha_rows_out, BDF_ERR_ARG, "bdf_dense_prior: NULL argument");
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_dense_prior: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    BDF_REQUIRE(n_terms >= 1 && n_terms <= BDF_MAX_TERMS, BDF_ERR_ARG, "bdf_dense_prior: %d terms (1..%d)", n_terms, BDF_MAX_TERMS);
-    BDF_REQUIRE(N >= 0, BDF_ERR_ARG, "bdf_dense_prior: N < 0");
-    BDF_REQUIRE(Lambda_out != Lambda && mu_out != mu, BDF_ERR_ARG, "bdf_dense_prior: the outputs may not alias mu and Lambda");
     DenseFoldArgs a = {};
     DenseRowsArgs ra = {};
-    a.D = ra.D = D; a.n = ra.n = n_terms;
+    int rc = fold_fill("bdf_dense_prior", ctx, D, N, n_terms, terms, mu, mu_is_matrix, Lambda, Lambda_out, mu_out, alpha_rows_out, a);
+    if (rc) return rc;
+    ra.D = D; ra.n = n_terms;
     int n_dense = 0;
     for (int k = 0; k < n_terms; k++) {
-        const bdf_dense_term &t = terms[k];
-        BDF_REQUIRE(t.gram && (t.C != nullptr) != (t.sum != nullptr), BDF_ERR_ARG,
-                    "bdf_dense_prior: term %d needs a Gram matrix and either C (a dense term) or sum (a background term)", k);
-        BDF_REQUIRE(t.weight > 0.0 && t.weight <= 1.0 && std::isfinite(t.resid) && (t.sum || t.weight == 1.0), BDF_ERR_ARG,
-                    "bdf_dense_prior: term %d: weight=%g must lie in (0, 1] (1 for a dense term) and resid=%g be finite", k, t.weight, t.resid);
-        BDF_REQUIRE(t.alpha_dev || (t.alpha > 0.0 && std::isfinite(t.alpha)), BDF_ERR_ARG, "bdf_dense_prior: term %d: alpha=%g must be positive and finite", k, t.alpha);
-        a.t[k] = t;
-        ra.C[k] = t.C;
-        n_dense += t.C != nullptr;
+        ra.C[k] = terms[k].C;
+        n_dense += terms[k].C != nullptr;
     }
     BDF_REQUIRE(n_dense >= 1, BDF_ERR_ARG, "bdf_dense_prior: no dense term (bdf_background_prior folds background terms alone)");
-    BDF_HIP(hipSetDevice(ctx->device));
     const int DP = bdf_rows_dp(D);
     void *sc;
-    int rc = bdf_scratch(ctx, ((size_t)2 * DP * DP + DP + BDF_MAX_TERMS) * sizeof(double), &sc);
-    if (rc) return rc;
-    a.mu = mu_is_matrix ? nullptr : mu;
-    a.Lambda = Lambda; a.Lambda_out = Lambda_out; a.alpha_rows_out = alpha_rows_out;
+    if ((rc = bdf_scratch(ctx, ((size_t)2 * DP * DP + DP + BDF_MAX_TERMS) * sizeof(double), &sc))) return rc;
     a.Ti_out = (double *)sc; a.Wt_out = a.Ti_out + (size_t)DP * DP; a.w0_out = a.Wt_out + (size_t)DP * DP; a.coef_out = a.w0_out + DP;
-    a.flag = ctx->flag_dev;
     const int G = 64 / DP, nfold = (D + G - 1) / G + 1;
     if (DP == 16) hipLaunchKernelGGL(k_dmat_fold<16>, dim3(nfold), dim3(64), 0, ctx->stream, a);
     else if (DP == 32) hipLaunchKernelGGL(k_dmat_fold<32>, dim3(nfold), dim3(64), 0, ctx->stream, a);

@@ -272,12 +272,13 @@ class DeviceRelation:
         self.robust_nu, self.pg_model, self.pg_r = 0.0, 0, 0.0
         # a noise precision per row of one entity (setEntityNoise): {"mode", "shape", "rate"}; tau per row of that mode; its running sum
         self.noise = self.tau = self.tau_sum = None
-        # background cells (setBackground): {"weight", "value"}; the two modes' sums and Gram matrices; the caller's weights (omega is
-        # then what the rows read, omega_k - c0)
-        self.bg = self.bg_sums = self.bg_weights = None
-        # a dense relation (setDense): {"R": N x M, the values without their mean; "C": per mode, its rows of R V / R' U; "sums": per
-        # mode, D + D^2 doubles of bdf_hyper_sums; "sum_r2": the sum of r^2}.  The handle is then a relation WITHOUT cells
+        # background cells (setBackground): {"weight", "value"}; the caller's weights (omega is then what the rows read, omega_k - c0)
+        self.bg = self.bg_weights = None
+        # a dense relation (setDense): {"R": N x M, the values without their mean; "C": per mode, its rows of R V / R' U; "sum_r2":
+        # the sum of r^2}.  The handle is then a relation WITHOUT cells
         self.dense = None
+        # either of the two is folded into its entities' priors: per mode, D + D^2 doubles of bdf_hyper_sums (the rows' sum and Gram matrix)
+        self.fold_sums = None
         ctx.adopt(self)
 
     @property
@@ -1172,13 +1173,13 @@ class GibbsEngine:
             dr.train.set_pg_link(dr.pg_model, dr.pg_r)
         if m.background is not None:
             # background cells (setBackground): every unlisted cell observes `value` with precision alpha c0.  The
-            # rows of both entities are sampled with the prior row_prior() makes from the other entity's sum and Gram matrix (bg_sums:
+            # rows of both entities are sampled with the prior row_prior() makes from the other entity's sum and Gram matrix (fold_sums:
             # per mode, D + D^2 doubles).  Unit weights: the relation was created from _background_values and its terms read alpha
             # (1 - c0) -- nothing per observation.  setWeights: the rows read omega_k - c0 and, through linear_values, the
             # pseudo-residual (omega_k r_k - c0 rb) / (omega_k - c0), both constant over the run; alpha's sum of squares reads omega_k
             c0, rb = m.background["weight"], m.background["value"] - m.mean_value
             dr.bg = dict(m.background)
-            dr.bg_sums = ctx.zeros(2, self.D + self.D * self.D)
+            dr.fold_sums = ctx.zeros(2, self.D + self.D * self.D)
             if kind == "weights":
                 w, y = np.asarray(m.weights, dtype=np.float64), np.asarray(values, dtype=np.float64)
                 dr.bg_weights = dr.omega
@@ -1193,8 +1194,8 @@ class GibbsEngine:
             listed = ~np.isnan(Y)
             R0 = np.where(listed, Y - m.mean_value, 0.0)
             Cs = ctx.zeros(N + M, self.D)              # (one buffer: the native iteration is handed its start)
-            dr.dense = {"R": ctx.tensor(R0), "C": [Cs[:N], Cs[N:]], "sums": ctx.zeros(2, self.D + self.D * self.D),
-                        "sum_r2": math.fsum((R0 * R0).ravel().tolist()), "holes": None, "stats": None}
+            dr.dense = {"R": ctx.tensor(R0), "C": [Cs[:N], Cs[N:]], "sum_r2": math.fsum((R0 * R0).ravel().tolist()), "holes": None, "stats": None}
+            dr.fold_sums = ctx.zeros(2, self.D + self.D * self.D)
             if len(holes):
                 # the holes as pairs (the values are not read) and where their draw leaves the sum of their squares
                 dr.dense["holes"] = self._pairs(ctx, r, holes + 1, np.zeros(len(holes)))
@@ -1271,15 +1272,17 @@ class GibbsEngine:
                 g.bg_weight, g.bg_value = dr.bg["weight"], dr.bg["value"]
             if dr.dense is not None:
                 dn = dr.dense
-                g.dense_R, g.dense_C, g.dense_sums, g.dense_sum_r2 = dn["R"].data_ptr(), dn["C"][0].data_ptr(), dn["sums"].data_ptr(), dn["sum_r2"]
+                g.dense_R, g.dense_C, g.dense_sum_r2 = dn["R"].data_ptr(), dn["C"][0].data_ptr(), dn["sum_r2"]
                 if dn["holes"] is not None:
                     g.dense_holes, g.dense_stats = dn["holes"].handle, dn["stats"].data_ptr()
             if dr.noise is not None:
                 g.noise_mode, g.noise_shape, g.noise_rate, g.noise_tau = dr.noise["mode"], dr.noise["shape"], dr.noise["rate"], dr.tau.data_ptr()
             for name, t in (("linear", dr.linear), ("censor", dr.censor), ("interval", dr.interval), ("ordinal_codes", dr.ord_codes),
-                            ("obs_precision", dr.omega), ("beta", dr.beta), ("bg_sums", dr.bg_sums), ("bg_weights", dr.bg_weights)):
+                            ("obs_precision", dr.omega), ("beta", dr.beta), ("bg_weights", dr.bg_weights)):
                 if t is not None:
                     setattr(g, name, t.data_ptr())
+            if dr.fold_sums is not None:           # (the C struct keeps a field per family: the buffer goes to the one the relation uses)
+                setattr(g, "dense_sums" if dr.dense is not None else "bg_sums", dr.fold_sums.data_ptr())
             if dr.ordinal is not None:
                 g.ordinal = dr.ordinal.handle
             if dr.F is not None:

@@ -7,7 +7,7 @@ beyond N = 37, M = 29 and one relation, where tests/test_gpu_background.py stays
 (b) k_bg_fold with two to four terms, alpha by argument and from alpha_dev in turn, and the same terms in reversed order.
 (c) bdf_background_sse at n in {0, 1, 7, 8, 9, 257} listed cells for its three instantiations, and over 257 workgroups' sums.
 (d) one entity in two background relations with a plain relation between them, end to end on both iteration paths.
-(e) a fold at kappa_2 ~ 1e9, where the refinement step of bg_solve decides the residual, and a fold that is not positive definite.
+(e) a fold at kappa_2 ~ 1e9, where the refinement step of fold_solve decides the residual, and a fold that is not positive definite.
 
 References are numpy in float64 (math.fsum for the sums); the bounds are those of tests/test_gpu_background.py."""
 import ctypes as C
@@ -455,7 +455,7 @@ def _refined(A, b, steps=2):
 
 
 def _cholesky_refined(A, b):
-    """what a float64 Cholesky solve with one refinement step in float64 reaches: the yardstick for the device's bg_solve"""
+    """what a float64 Cholesky solve with one refinement step in float64 reaches: the yardstick for the device's fold_solve"""
     L = np.linalg.cholesky(A)
 
     def solve(r):

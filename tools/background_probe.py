@@ -150,7 +150,7 @@ def main():
     parts = {"what": "parts", "D": D}
     for j, en in enumerate(rd.entities):
         st, so = eng.ent[j], eng.ent[1 - j]
-        s = dr.bg_sums[1 - j]
+        s = dr.fold_sums[1 - j]
         parts[f"sums_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_hyper_sums(
             ctx.handle, D, so.N, p(so.sample), None, p(s[:D]), p(s[D:])))), 2)
         parts[f"sums_and_fold_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: eng._row_prior(j)), 2)

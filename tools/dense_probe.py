@@ -109,7 +109,7 @@ def main():
     parts = {"what": "parts", "D": D}
     for j, en in enumerate(rd.entities):
         st, so = eng.ent[j], eng.ent[1 - j]
-        s = dn["sums"][1 - j]
+        s = eng.rel[0].fold_sums[1 - j]
         parts[f"gram_for_{en.name}_us"] = round(timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_hyper_sums(
             ctx.handle, D, so.N, p(so.sample), None, p(s[:D]), p(s[D:])))), 2)
         us = timed(torch, ctx.stream, args.reps, args.warmup, lambda: check(lib().bdf_dense_product(
