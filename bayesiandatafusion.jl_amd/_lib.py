@@ -25,6 +25,7 @@ P_PG = 18
 P_NOISE_N, P_NOISE_U = 19, 20
 P_SPIKE_N, P_SPIKE_U, P_SPIKE = 21, 22, 23
 P_DENSE = 24
+P_NONNEG, P_NONNEG_N, P_NONNEG_U = 25, 26, 27
 
 
 class ArgumentError(ValueError):
@@ -85,7 +86,9 @@ class GibbsEntity(C.Structure):
                 ("full_lambda_u", C.c_int32), ("_pad", C.c_int32), ("tol", C.c_double), ("lb_nu", C.c_double), ("lb_mu", C.c_double),
                 ("bg_Lambda", C.c_void_p), ("bg_mu", C.c_void_p), ("bg_pack", C.c_void_p), ("bg_alpha_rows", C.c_void_p),
                 ("spike", C.c_int32), ("_pad_spike", C.c_int32), ("spike_a", C.c_double), ("spike_b", C.c_double),
-                ("spike_shape", C.c_double), ("spike_rate", C.c_double), ("spike_state", C.c_void_p)]
+                ("spike_shape", C.c_double), ("spike_rate", C.c_double), ("spike_state", C.c_void_p),
+                ("nonneg", C.c_int32), ("_pad_nonneg", C.c_int32), ("nonneg_shape", C.c_double), ("nonneg_rate", C.c_double),
+                ("nonneg_tau", C.c_void_p)]
 
 
 class GibbsRelation(C.Structure):
@@ -162,6 +165,12 @@ _SIGS = {
     "bdf_spike_hyper": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32,
                                   C.c_void_p]),
     "bdf_spike_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_sample_rows_nonneg": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(Term), C.c_void_p, C.c_void_p, C.c_uint32, C.c_int,
+                                         C.c_int, C.c_void_p]),
+    "bdf_nonneg_sweep": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p]),
+    "bdf_nonneg_hyper": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_void_p]),
+    "bdf_nonneg_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_ctx_set_nonneg_chunk": (C.c_int, [C.c_void_p, C.c_int64]),
     "bdf_hyper_sums": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_hyper_sums_ranks": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_hyper_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,

@@ -42,6 +42,8 @@ def relation_of(data, num_latent, who):
     for en in data.entities:
         if en.spike is not None:
             raise ArgumentError(f"{who} has the Normal-Wishart prior only; {en.name} has the spike-and-slab prior (setSpikeAndSlab; use macau)")
+        if en.nonneg is not None:
+            raise ArgumentError(f"{who} has the Normal-Wishart prior only; {en.name} has the non-negative prior (setNonNegative; use macau)")
     return D, rel
 
 

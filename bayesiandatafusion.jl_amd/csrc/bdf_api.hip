@@ -809,6 +809,67 @@ extern "C" int bdf_sample_rows_spike(bdf_ctx *ctx, int D, int64_t N, int n_terms
     return bdf_launch_sample_rows(ctx, a, rels, modes, shard, n_shards, false);
 }
 
+extern "C" int bdf_sample_rows_nonneg(bdf_ctx *ctx, int D, int64_t N, int n_terms, const bdf_term *terms, const double *tau,
+                                      const double *u_current, uint32_t entity_tag, int shard, int n_shards, double *out)
+{
+    BDF_REQUIRE(ctx && terms && tau && u_current, BDF_ERR_ARG, "bdf_sample_rows_nonneg: NULL argument");
+    SampleArgs a;
+    // (the prior of the accumulation, diag(tau) and zeros, is made below from tau: no mu, no Lambda from the caller)
+    int rc = fill_args(ctx, "bdf_sample_rows_nonneg", D, N, n_terms, terms, nullptr, 0, nullptr, a, true);
+    if (rc) return rc;
+    BDF_REQUIRE(out != nullptr, BDF_ERR_ARG, "bdf_sample_rows_nonneg: out is NULL");
+    BDF_REQUIRE(out != u_current, BDF_ERR_ARG, "bdf_sample_rows_nonneg: out aliases u_current");
+    BDF_REQUIRE(n_shards >= 1 && shard >= 0 && shard < n_shards, BDF_ERR_ARG, "bdf_sample_rows_nonneg: shard %d of %d", shard, n_shards);
+    const bdf_rel *rels[BDF_MAX_TERMS];
+    int modes[BDF_MAX_TERMS];
+    for (int r = 0; r < n_terms; r++) {
+        BDF_REQUIRE(!terms[r].rel->sharded, BDF_ERR_ARG, "bdf_sample_rows_nonneg: a relation created with a layout (one rank only)");
+        rels[r] = terms[r].rel;
+        modes[r] = terms[r].mode;
+        for (int k = 0; k < terms[r].rel->n_modes; k++)
+            BDF_REQUIRE(k == terms[r].mode || terms[r].factors[k] != out, BDF_ERR_ARG,
+                        "bdf_sample_rows_nonneg: out aliases terms[%d].factors[%d]", r, k);
+    }
+    a.entity_tag = entity_tag;
+    a.out = out;
+    // (the hand-overs bdf_sample_rows' launches can take part in -- a polled prior pack, a span, a counter -- are not for this one)
+    ctx->rows_ready = nullptr;
+    ctx->rows_span = nullptr;
+    ctx->rows_done = nullptr;
+    ctx->rows_done_added = -1;
+    // a caller's timing events (bdf_ctx_time_next_rows; bdf_gibbs_sweep's hand-over): around all of the call's launches
+    const hipEvent_t e0 = ctx->time_start, e1 = ctx->time_stop;
+    ctx->time_start = ctx->time_stop = nullptr;
+    // the shard's rows: positions shard, shard + n_shards, ... of the first relation's degree-descending order, `chunk` of them at a time
+    const int64_t n_mine = N > shard ? (N - shard + n_shards - 1) / n_shards : 0;
+    const int64_t chunk = std::min(bdf_nonneg_chunk_rows(ctx, D), std::max<int64_t>(n_mine, 1));
+    // ONE scratch request (the block may move when it grows): diag(tau) and the zeros of the prior mean, the prior pack made from
+    // them, then a chunk's systems -- P from a 16-byte boundary
+    const size_t nlm = (size_t)D * D + D, npk = (size_t)D + (size_t)bdf_prior_image_doubles(D), nhead = (nlm + npk + 1) / 2 * 2;
+    void *pb;
+    if ((rc = bdf_scratch(ctx, (nhead + (size_t)chunk * nlm) * sizeof(double), &pb))) return rc;
+    double *lm = (double *)pb, *pk = lm + nlm, *Ps = lm + nhead, *cs = Ps + (size_t)chunk * D * D;
+    if ((rc = bdf_nonneg_lambda_launch(ctx, D, tau, lm))) return rc;
+    if ((rc = bdf_prior_launch(ctx, D, lm, lm + (size_t)D * D, 1, 0, pk, pk + D))) return rc;
+    a.Lambda = lm; a.mu = lm + (size_t)D * D; a.mu_is_matrix = 0;
+    a.prior_b = pk; a.prior_c = pk + D;
+    a.P_dump = Ps; a.b_dump = cs;
+    if (e0) BDF_HIP(hipEventRecord(e0, ctx->stream));
+    for (int64_t k0 = 0; k0 < n_mine; k0 += chunk) {
+        const int64_t k1 = std::min(k0 + chunk, n_mine);
+        ctx->rows_k0 = k0; ctx->rows_k1 = k1;
+        if ((rc = bdf_launch_sample_rows(ctx, a, rels, modes, shard, n_shards, true))) return rc;
+        NonnegSweepArgs s{};
+        s.P = Ps; s.c = cs; s.u_current = u_current; s.out = out;
+        s.rows = rels[0]->idx[modes[0]].order_dev; s.pos0 = shard + k0 * n_shards; s.stride = n_shards; s.n = k1 - k0;
+        s.seed = ctx->seed; s.sweep = ctx->sweep_host; s.entity_tag = entity_tag; s.D = D; s.wide = D % 2 == 0;
+        s.flag = ctx->flag_dev;
+        if ((rc = bdf_nonneg_sweep_launch(ctx, s))) return rc;
+    }
+    if (e1) BDF_HIP(hipEventRecord(e1, ctx->stream));
+    return BDF_OK;
+}
+
 #ifdef BDF_K1_SPANS
 unsigned long long *g_bdf_span_buf = nullptr;
 unsigned long long g_bdf_span_count = 0;

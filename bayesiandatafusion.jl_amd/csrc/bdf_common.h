@@ -96,6 +96,10 @@ struct bdf_ctx {
     // 64 words (16 words apart), and rows_done_added says how many will; else rows_done_added stays -1 and the caller uses the event
     uint32_t *rows_done;
     int64_t rows_done_added;
+    // (library-internal, bdf_sample_rows_nonneg) the next system dump takes positions rows_k0 .. rows_k1 - 1 of the shard's row list
+    // only and writes the system of position k at index k - rows_k0; rows_k1 = 0: every row at its own index.  Cleared by the launch
+    int64_t rows_k0, rows_k1;
+    int64_t nonneg_chunk;                  // bdf_ctx_set_nonneg_chunk: rows per chunk of the non-negative prior's launches; 0: the default
     const uint32_t *hyper_wait;            // (library-internal) ... and the next one-launch chain (k_hyper_chain) polls their sum for this target
     uint32_t hyper_wait_target;
     uint32_t *hyper_ready;                 // (library-internal) word the next bdf_hyper_sample sets to hyper_ready_value once its pack is written, then cleared

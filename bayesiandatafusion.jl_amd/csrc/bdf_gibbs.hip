@@ -269,6 +269,8 @@ extern "C" int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const 
                     "bdf_gibbs_create: entity %d has side information but a NULL beta / uhat / mu_matrix / Tinv / lambda_beta", j);
         BDF_REQUIRE(!e.spike || (e.spike_state && !e.feat && !e.bg_Lambda), BDF_ERR_ARG,
                     "bdf_gibbs_create: entity %d has the spike-and-slab prior: spike_state must be set, side information and a background are not taken", j);
+        BDF_REQUIRE(!e.nonneg || (e.nonneg_tau && !e.spike && !e.feat && !e.bg_Lambda), BDF_ERR_ARG,
+                    "bdf_gibbs_create: entity %d has the non-negative prior: nonneg_tau must be set; the spike-and-slab prior, side information and a background / dense relation are not taken", j);
         BDF_REQUIRE(!e.feat || e.feat->m == e.N, BDF_ERR_ARG, "bdf_gibbs_create: entity %d has %lld rows but its feature matrix %lld", j,
                     (long long)e.N, e.feat ? (long long)e.feat->m : 0LL);
         for (int t = 0; t < e.n_terms; t++) {
@@ -435,9 +437,9 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
                         "bdf_gibbs_set_relations: relation %d: %s takes neither the probit, censored, interval, ordinal, robust or a Polya-Gamma model, relation features nor a communicator", k, what);
             for (int m = 0; m < 2; m++) {
                 const bdf_gibbs_entity &e = g->ent[(size_t)r.entity_of_mode[m]].d;
-                BDF_REQUIRE(e.bg_Lambda && e.bg_mu && e.bg_alpha_rows && (dense || e.bg_pack) && !(dense && e.spike), BDF_ERR_ARG,
+                BDF_REQUIRE(e.bg_Lambda && e.bg_mu && e.bg_alpha_rows && (dense || e.bg_pack) && !(dense && e.spike) && !e.nonneg, BDF_ERR_ARG,
                             "bdf_gibbs_set_relations: relation %d is %s but entity %d has a NULL bg_Lambda / bg_mu / bg_alpha_rows%s", k, what, r.entity_of_mode[m],
-                            dense ? ", or the spike-and-slab prior" : " / bg_pack");
+                            e.nonneg ? ", or the non-negative prior" : (dense ? ", or the spike-and-slab prior" : " / bg_pack"));
             }
         }
         BDF_REQUIRE(!bg || !r.obs_precision || (r.linear && r.bg_weights), BDF_ERR_ARG,
@@ -691,6 +693,9 @@ extern "C" int bdf_gibbs_set_comm(bdf_gibbs *g, bdf_comm *comm)
 namespace {
 // the hyperprior's degrees of freedom: nu0 (+ numF with side information and full_lambda_u, macau.jl:124-129)
 double hyper_nu(const bdf_gibbs_entity &e) { return e.nu0 + ((e.feat && e.full_lambda_u) ? (double)e.feat->n : 0.0); }
+// a prior of its own in place of the Normal-Wishart one (spike-and-slab; non-negative, section 26): no (mu, Lambda)
+// draw and none of its hand-overs -- the entity's rows wait for the event of its hyper step
+bool own_prior(const bdf_gibbs_entity &e) { return e.spike || e.nonneg; }
 
 // What bdf_gibbs_sweep hangs on an entity's row launch.  All empty (the step entry points, bdf_gibbs_rows_only): plain stream order --
 // no events, no polling, no done counter, and the context's timing fields and span slot are the caller's.
@@ -714,7 +719,7 @@ int launch_rows(bdf_gibbs *g, bdf_gibbs::Ent &E, bool pack_valid, bool exchange,
     // the prior of this launch: the draw's (mu, Lambda) and pack, or -- background cells -- those with the Gram terms folded in
     const double *mu = nullptr, *Lambda = nullptr, *pack = nullptr;
     int is_matrix = 0;
-    if (!e.spike && (rc = row_prior(g, E, pack_valid, &mu, &is_matrix, &Lambda, &pack))) return rc;
+    if (!own_prior(e) && (rc = row_prior(g, E, pack_valid, &mu, &is_matrix, &Lambda, &pack))) return rc;
     bdf_term terms[BDF_MAX_TERMS];
     fill_terms(g, e, terms);
     const int nxt = (E.cur + 1) % 3, nch = e.terms[0].rel->chunks;     // 1 unless the relations were created with a layout
@@ -727,6 +732,7 @@ int launch_rows(bdf_gibbs *g, bdf_gibbs::Ent &E, bool pack_valid, bool exchange,
         if (x.counter) R->rows_done = x.counter;
         R->gimg_trust = !g->comm;         // (the chain's own buffers: sample_written() hears of every other writer)
         if ((rc = e.spike ? bdf_sample_rows_spike(R, g->D, e.N, e.n_terms, terms, e.spike_state, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
+                 : e.nonneg ? bdf_sample_rows_nonneg(R, g->D, e.N, e.n_terms, terms, e.nonneg_tau, e.sample[E.cur], e.tag, c, nch, e.sample[nxt])
                           : bdf_sample_rows(R, g->D, e.N, e.n_terms, terms, mu, is_matrix, Lambda, e.tag, c, nch, e.sample[nxt], pack)))
             return rc;
         if (x.counter && R->rows_done_added >= 0) { if (by_counter) *by_counter = true; E.done_target += (uint32_t)R->rows_done_added; }
@@ -760,6 +766,8 @@ int hyper_step(bdf_gibbs *g, const bdf_gibbs::Ent &E, bdf_ctx *H, const double *
     int rc;
     // the spike-and-slab prior's hyper step in place of the sums and the Normal-Wishart draw
     if (e.spike) return bdf_spike_hyper(H, D, e.n_real, e.sample[E.cur], e.spike_a, e.spike_b, e.spike_shape, e.spike_rate, e.tag, e.spike_state);
+    // ... and the non-negative prior's
+    if (e.nonneg) return bdf_nonneg_hyper(H, D, e.n_real, e.sample[E.cur], e.nonneg_shape, e.nonneg_rate, e.tag, e.nonneg_tau);
     if (x.wait) { H->hyper_wait = x.wait; H->hyper_wait_target = x.wait_target; }
     if (x.fuse) H->hyper_fuse = true;
     // side information: U = sample - uhat, T^-1 = WI + beta' beta lambda_beta with the beta of the previous iteration
@@ -824,8 +832,8 @@ extern "C" int bdf_gibbs_step_draws(bdf_gibbs *g, int entity)
 {
     BDF_REQUIRE(g && entity >= 0 && entity < (int)g->ent.size(), BDF_ERR_ARG, "bdf_gibbs_step_draws: bad argument");
     const bdf_gibbs_entity &e = g->ent[(size_t)entity].d;
-    // (the spike-and-slab prior's hyper step draws from the rows' counts: nothing to prepare)
-    return e.spike ? BDF_OK : bdf_hyper_draws(g->step_hyper, g->D, e.n_real, hyper_nu(e), e.tag, e.draws);
+    // (the spike-and-slab and the non-negative prior's hyper steps draw from the rows' sums: nothing to prepare)
+    return own_prior(e) ? BDF_OK : bdf_hyper_draws(g->step_hyper, g->D, e.n_real, hyper_nu(e), e.tag, e.draws);
 }
 
 extern "C" int bdf_gibbs_step_hyper(bdf_gibbs *g, int entity, int draws_prepared)
@@ -890,6 +898,7 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         pieces.push_back({e.prior_pack, (size_t)bdf_prior_pack_doubles(D) * sizeof(double), false, j});
         pieces.push_back({e.draws, DD + Dv, false, j});
         if (e.spike) pieces.push_back({e.spike_state, 4 * Dv, false, j});      // pi, tau, logit pi, log tau of the spike-and-slab prior
+        if (e.nonneg) pieces.push_back({e.nonneg_tau, Dv, false, j});          // tau of the non-negative prior
         if (e.feat) {
             pieces.push_back({e.beta, (size_t)e.feat->n * Dv, false, j});
             pieces.push_back({e.uhat, (size_t)e.N * Dv, false, j});
@@ -1070,10 +1079,10 @@ int draws_ahead(bdf_gibbs *g, bool *in_chain)
     for (const auto &E : g->ent) *in_chain = *in_chain && E.d.N <= 16384;
     if (*in_chain || (int)g->ent.size() > BDF_DRAWS_BATCH) return BDF_OK;
     int64_t Ns[BDF_DRAWS_BATCH]; double nus[BDF_DRAWS_BATCH]; uint32_t tags[BDF_DRAWS_BATCH]; double *outs[BDF_DRAWS_BATCH];
-    int nb = 0;                           // (an entity with the spike-and-slab prior has no Normal-Wishart draw)
+    int nb = 0;                           // (an entity with the spike-and-slab or the non-negative prior has no Normal-Wishart draw)
     for (const auto &E : g->ent) {
         const bdf_gibbs_entity &e = E.d;
-        if (e.spike) continue;
+        if (own_prior(e)) continue;
         Ns[nb] = e.n_real; nus[nb] = hyper_nu(e); tags[nb] = e.tag; outs[nb] = e.draws; nb++;
     }
     return nb > 0 ? bdf_hyper_draws_batch(g->hyper, g->D, nb, Ns, nus, tags, outs) : BDF_OK;
@@ -1146,14 +1155,14 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // the draw -- behind the draw's event, and its rows join neither the polling nor the hand-over by counter below)
         // (an entity with a dense relation likewise)
         const bool bg = folds_prior(g, e);
-        // (so is an entity with the spike-and-slab prior: its rows wait for the event of its hyper step, bdf_spike_hyper)
-        const bool poll = g->polling && (!g->comm || poll_with_comm) && E.hyper_recorded && !e.feat && !bg && !e.spike;
+        // (so is an entity with the spike-and-slab or the non-negative prior: its rows wait for the event of its hyper step)
+        const bool poll = g->polling && (!g->comm || poll_with_comm) && E.hyper_recorded && !e.feat && !bg && !own_prior(e);
         if (E.hyper_recorded && !poll) BDF_HIP(hipStreamWaitEvent(R->stream, E.ev_hyper, 0));
         // side information: uhat = (F beta)' with the beta of the previous iteration, per-row prior means mu + uhat (macau.jl:103-104)
         if (e.feat && (rc = bdf_uhat(R, e.feat, D, e.beta, e.mu, e.uhat, e.mu_matrix))) return rc;
         // the data-independent part of the hyperprior draw (Bartlett matrix, mean normals): beside the rows -- for all entities
         // in one launch at the head of the iteration when they are few
-        if (!draws_in_chain && n > BDF_DRAWS_BATCH && !e.spike && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
+        if (!draws_in_chain && n > BDF_DRAWS_BATCH && !own_prior(e) && (rc = bdf_hyper_draws(H, D, e.n_real, hyper_nu(e), e.tag, e.draws))) return rc;
         // the completion event rides on the row kernel's dispatch (a caller-supplied timing pair takes its place)
         hipEvent_t done = E.t_stop ? E.t_stop : E.ev_rows;
         // The hand-over to the entity's hyperprior chain.  By default an event on the row kernel's dispatch and a wait on the
@@ -1169,7 +1178,7 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         // Every other path -- a communicator, side information, chunks, a caller's timing events (E.t_stop), no polling, chains of
         // several launches: `counter` false; a launch that took another kernel: rows_done_added < 0 -- has `done` as before, on the
         // dispatch or recorded right behind it, for the chain and the prediction stream alike.
-        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && !bg && !e.spike && e.terms[0].rel->chunks == 1 && !E.t_stop;
+        const bool counter = E.done_dev && draws_in_chain && g->polling && !g->comm && !e.feat && !bg && !own_prior(e) && e.terms[0].rel->chunks == 1 && !E.t_stop;
         const bool pred_waits = j == n - 1 && g->test && predict_phase >= 0;
         RowsExtras rx{};
         rx.start = E.t_start; rx.span = E.span;
@@ -1183,13 +1192,13 @@ extern "C" int bdf_gibbs_sweep(bdf_gibbs *g, uint32_t sweep, int predict_phase)
         HyperExtras hx{};
         if (by_counter) { hx.wait = E.done_dev; hx.wait_target = E.done_target; }
         else BDF_HIP(hipStreamWaitEvent(H->stream, done, 0));
-        if (!e.spike) {
+        if (!own_prior(e)) {
             hx.fuse = true; hx.chain_draws = draws_in_chain ? e.draws : nullptr;
             hx.stop = E.ev_hyper; hx.ready = g->ready_dev + j; hx.ready_value = ++E.epoch;
             if (e.feat && e.full_lambda_u && E.beta_recorded) BDF_HIP(hipStreamWaitEvent(H->stream, E.ev_beta, 0));
         }
         if ((rc = hyper_step(g, E, H, e.draws, hx))) return rc;
-        if (e.spike) BDF_HIP(hipEventRecord(E.ev_hyper, H->stream));              // (its event recorded behind it)
+        if (own_prior(e)) BDF_HIP(hipEventRecord(E.ev_hyper, H->stream));         // (its event recorded behind it)
         E.hyper_recorded = true;
         if (pred_waits && by_counter) { if ((rc = gate_prediction(g, E))) return rc; }
         else if (pred_waits) BDF_HIP(hipStreamWaitEvent(P->stream, done, 0));

@@ -126,6 +126,25 @@ int bdf_k1_launch(bdf_ctx *ctx, const SampleArgs &a, const PlanDev &p, bool dump
 int bdf_ss_launch(bdf_ctx *ctx, const SampleArgs &a, const PlanDev &p, hipEvent_t e0, hipEvent_t e1);
 // diag(tau) of a spike_state as a D x D matrix, and D zeros behind it (the prior mean): what bdf_prior_launch takes (k_spike_hyper.hip)
 int bdf_spike_lambda_launch(bdf_ctx *ctx, int D, const double *spike_state, double *Lambda_mu_out);
+// ---- the non-negative prior (k_nonneg.hip) --------------------------------------------------------
+// diag(tau) as a D x D matrix, and D zeros behind it (the prior mean): what bdf_prior_launch takes
+int bdf_nonneg_lambda_launch(bdf_ctx *ctx, int D, const double *tau, double *Lambda_mu_out);
+// rows per chunk on this context for num_latent = D: the caller's (bdf_ctx_set_nonneg_chunk) or the default under the scratch cap
+int64_t bdf_nonneg_chunk_rows(const bdf_ctx *ctx, int D);
+// The coordinate sweep of n systems, one lane each: system i is P + i D^2, c + i D.  Its row -- the random stream, and with
+// rows != NULL the row of u_current and out -- is rows[pos0 + i * stride], or with rows == NULL row_begin + i, where u_current and
+// out are indexed by i.
+struct NonnegSweepArgs {
+    const double *P, *c, *u_current;
+    double *out;
+    const int32_t *rows;
+    int64_t pos0, stride, row_begin, n;
+    uint64_t seed;
+    uint32_t sweep, entity_tag;
+    int32_t D, wide;           // wide: D is even and P is 16-byte aligned -- a row of P by 16-byte loads
+    int *flag;                 // the context's flag word: a diagonal entry that is not positive and finite sets the bit a bad pivot sets
+};
+int bdf_nonneg_sweep_launch(bdf_ctx *ctx, const NonnegSweepArgs &a);
 // the prior pack of a launch: out_b = Lambda mu (nrows = 1, mu_is_matrix = 0) or Lambda mu_i for nrows rows, out_c = the
 // accumulator-layout image of the index-reversed Lambda (bdf_prior_image_doubles(D) doubles)
 inline int bdf_prior_image_doubles(int D) { const int DB = bdf_rows_dp(D) / 16; return DB * (DB + 1) / 2 * 4 * 64; }

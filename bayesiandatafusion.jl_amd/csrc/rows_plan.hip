@@ -27,6 +27,7 @@ struct PlanKey {
     int64_t lr_min, lr_other;         // ... if the launch has at least lr_min of them, and at least half as many as the opposite entity has rows
     int col;                          // > 0: the rows of k_rows go to k_rows_col instead (four rows per wave, column layout), cut into pieces of at most this size
     int col_slots;                    // ... dealt to at most this many waves
+    int64_t k0, k1;                   // k1 > 0 (a system dump of bdf_sample_rows_nonneg): positions k0 .. k1 - 1 of the shard's row list only, system k at index k - k0
     bool operator<(const PlanKey &o) const { return memcmp(this, &o, sizeof(PlanKey)) < 0; }
 };
 
@@ -218,6 +219,7 @@ void route_key(const bdf_ctx *ctx, const SampleArgs &a, const bdf_rel *const *re
     memset(&key, 0, sizeof(key));
     for (int r = 0; r < a.n_terms; r++) { key.rel[r] = rels[r]->serial; key.mode[r] = modes[r]; }
     key.n_terms = a.n_terms; key.DP = DP; key.T = ctx->item_size; key.Tp = std::min(ctx->piece_size, ctx->item_size); key.shard = shard; key.n_shards = n_shards;
+    if (dump) { key.k0 = ctx->rows_k0; key.k1 = ctx->rows_k1; }
     if (ctx->item_auto) {
         // Rows are cut into pieces so that a launch of a few thousand rows has no wave much longer than the others.  A launch with
         // hundreds of waves per resident slot has no such tail, and every piece costs a partial sum written to the slab and read
@@ -297,10 +299,14 @@ bool collect_rows(const PlanKey &key, const bdf_rel *const *rels, const int *mod
     } else {
         // rows of this shard: positions shard, shard + n_shards, ... of the degree-descending order of the first
         // relation (the reference deals rows i:P:N to its P workers for the same balance, sampling.jl:154)
+        // (key.k1 > 0: entries k0 .. k1 - 1 of that list, and the system of entry k goes to index k - k0)
         const std::vector<int32_t> &order = rels[0]->idx[modes[0]].order;
-        for (size_t pos = (size_t)key.shard; pos < order.size(); pos += (size_t)key.n_shards) {
+        const size_t first = (size_t)key.shard + (size_t)key.k0 * (size_t)key.n_shards;
+        const size_t last = key.k1 > 0 ? std::min(order.size(), (size_t)key.shard + (size_t)key.k1 * (size_t)key.n_shards) : order.size();
+        for (size_t pos = first; pos < last; pos += (size_t)key.n_shards) {
             RowRef rr;
             rr.out = rr.orig = order[pos];
+            if (key.k1 > 0) rr.out = (int32_t)((pos - first) / (size_t)key.n_shards);
             for (int r = 0; r < key.n_terms; r++) {
                 const auto &rp = rels[r]->idx[modes[r]].rowptr;
                 rr.qb[r] = rp[(size_t)rr.orig]; rr.cnt[r] = rp[(size_t)rr.orig + 1] - rp[(size_t)rr.orig];
@@ -496,6 +502,7 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
     // (whatever this call's launches are, they write a.out: its image, if it has one, is stale until a K1c launch leaves a new one)
     const bool image_trust = ctx->gimg_trust;
     ctx->gimg_trust = false;
+    struct Range { bdf_ctx *c; ~Range() { c->rows_k0 = c->rows_k1 = 0; } } range_once{ctx};      // (bdf_sample_rows_nonneg's chunk: this launch only)
     bdf_gather_image_invalidate(ctx, a.out);
     const bool spike = a.spike_state != nullptr;      // bdf_sample_rows_spike: every row to K1-style items, finished by k_rows_ss
     if (spike) {

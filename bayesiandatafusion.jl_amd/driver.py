@@ -117,6 +117,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if eng is engine:
         for st in spiked:
             st.spike_reset()                                 # (... and of the spike-and-slab result)
+    # entities with the non-negative prior (setNonNegative)
+    nonneg = [st for st in eng.ent if st.nonneg is not None]
+    if eng is engine:
+        for st in nonneg:
+            st.nonneg_reset()                                # (... and of the non-negative result)
     D = eng.D
 
     latent_multi_threading = (len(latent_pids) >= 1 and len(data.relations) == 1 and not hasFeatures(data.relations[0]))
@@ -191,6 +196,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             eng.entity_noise_accumulate()                     # this iteration's tau into its running sum, on the row stream
         if spiked and i > burnin:
             eng.spike_accumulate()                            # this draw's inclusions, pi and tau into their running sums, on the row stream
+        if nonneg and i > burnin:
+            eng.nonneg_accumulate()                           # this draw's rows and tau into their running sums, on the row stream
         if lpd or waic is not None or newr is not None:
             # (alpha sampled: the device scalar of the native iteration, drawn on the stream this runs on; step by step the host
             # has read the same double, and the device scalar is redrawn on another stream than the pairs')
@@ -325,6 +332,9 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if spiked:
         # posterior means of pi_d, tau_d, the share of rows with a nonzero loading and [u_id != 0]
         result["spike"] = {en.name: st.spike_result() for en, st in zip(data.entities, eng.ent) if st.spike is not None}
+    if nonneg:
+        # posterior means of tau_d and of the rows (all >= 0)
+        result["nonneg"] = {en.name: st.nonneg_result() for en, st in zip(data.entities, eng.ent) if st.nonneg is not None}
     if lpd:
         result["LPD"] = lpd_avg
     # relations with background cells (setBackground): what every unlisted cell observed, and how many there were

@@ -138,6 +138,10 @@ class Context:
     def set_item_size(self, observations):
         check(lib().bdf_ctx_set_item_size(self.handle, int(observations)))
 
+    def set_nonneg_chunk(self, rows):
+        """rows per chunk of the non-negative prior's launches (bdf_ctx_set_nonneg_chunk); 0: the default"""
+        check(lib().bdf_ctx_set_nonneg_chunk(self.handle, int(rows)))
+
     def rows_unfinished(self):
         """parity hook: split rows left unfinished by the row-kernel launches so far (must be 0)"""
         n = C.c_int64(0)
@@ -845,6 +849,16 @@ class EntityState:
             self.spike_row_sum = torch.empty(self.N, D, dtype=torch.float64, device=ctx.device)
             self.spike_hyper_sum = torch.empty(3 * D, dtype=torch.float64, device=ctx.device)
             self.spike_reset()
+        # the non-negative prior (setNonNegative): tau (D; 1 at the start) and the running sums of the result -- the rows, tau --,
+        # zeroed on the row stream, which is the one that adds to them
+        self.nonneg = en.nonneg
+        self.nonneg_tau = self.nonneg_row_sum = self.nonneg_hyper_sum = None
+        self.nonneg_draws = 0
+        if en.nonneg is not None:
+            self.nonneg_tau = ctx.tensor(np.ones(D))
+            self.nonneg_row_sum = torch.empty(self.N, D, dtype=torch.float64, device=ctx.device)
+            self.nonneg_hyper_sum = torch.empty(D, dtype=torch.float64, device=ctx.device)
+            self.nonneg_reset()
         self.F = None
         self.numF = 0
         self.beta = ctx.zeros(D, 0)
@@ -906,6 +920,29 @@ class EntityState:
         if self.spike_draws == 0:
             h, rows = np.full(3 * D, np.nan), np.full((self.n_real, D), np.nan)
         return {"inclusion": h[:D] / n, "precision": h[D:2 * D] / n, "activity": h[2 * D:] / (n * float(self.n_real)), "row_inclusion": rows}
+
+    def nonneg_reset(self):
+        """the running sums of the non-negative result start again (hipMemsetAsync on the row stream)"""
+        with torch.cuda.stream(self.ctx.stream):
+            self.nonneg_row_sum.zero_()
+            self.nonneg_hyper_sum.zero_()
+        self.nonneg_draws = 0
+
+    def nonneg_accumulate(self):
+        """the current draw into the running sums, on the row stream"""
+        check(lib().bdf_nonneg_accumulate(self.ctx.handle, self.D, self.n_real, _ptr(self.sample), _ptr(self.nonneg_tau), _ptr(self.nonneg_row_sum),
+                                          _ptr(self.nonneg_hyper_sum)))
+        self.nonneg_draws += 1
+
+    def nonneg_result(self):
+        """the posterior means: precision tau_d (D) and factors (N x D, all >= 0)"""
+        torch.cuda.synchronize(self.ctx.device)
+        n, D = max(self.nonneg_draws, 1), self.D
+        h = self.nonneg_hyper_sum.cpu().numpy() / n
+        rows = self.nonneg_row_sum.cpu().numpy()[:self.n_real] / n
+        if self.nonneg_draws == 0:
+            h, rows = np.full(D, np.nan), np.full((self.n_real, D), np.nan)
+        return {"precision": h, "factors": rows}
 
     @property
     def sample(self):
@@ -1044,6 +1081,9 @@ class GibbsEngine:
             if en.spike is not None:
                 from .relation_data import check_spike
                 check_spike(en, 1 if shard is None else shard[1])
+            if en.nonneg is not None:
+                from .relation_data import check_nonneg
+                check_nonneg(en, 1 if shard is None else shard[1])
         for j, en in enumerate(data.entities):
             if not np.isnan(lambda_beta):
                 en.lambda_beta = float(lambda_beta)
@@ -1103,9 +1143,11 @@ class GibbsEngine:
         dr.kind, dr.alpha_sample = kind, bool(m.alpha_sample)
         # (probit: the latent is not centred; logit / counts: psi = u'v + the offset the setter was given)
         # (background cells: the mean over ALL cells, the unlisted ones at the background value -- valueMean of the dense listing)
+        # (every entity non-negative, setNonNegative: u.v >= 0 models the values themselves -- not centred)
+        all_nonneg = all(en.nonneg is not None for en in r.entities)
         m.mean_value = 0.0 if kind == "probit" else (m.pg["offset"] if kind in ("logit", "counts") else
                                                      (background_mean(r) if m.background is not None else
-                                                      (_dense_mean(r) if m.dense else dr.value_mean())))
+                                                      (_dense_mean(r) if m.dense else (0.0 if all_nonneg else dr.value_mean()))))
         # several ranks: the relation's observations (COO order) in world blocks of obs_block; this rank's block is
         # [obs_lo, obs_hi): its rows of the relation's feature matrix, its observations as pairs (the squared-error sum
         # of sample_alpha and F'v of sample_beta_rel are summed over the ranks in rank order, bdf_sum_ranks)
@@ -1231,6 +1273,9 @@ class GibbsEngine:
             if st.spike is not None:
                 g.spike, g.spike_state = 1, st.spike_state.data_ptr()
                 g.spike_a, g.spike_b, g.spike_shape, g.spike_rate = (st.spike[k] for k in ("incl_a", "incl_b", "shape", "rate"))
+            if st.nonneg is not None:
+                g.nonneg, g.nonneg_tau = 1, st.nonneg_tau.data_ptr()
+                g.nonneg_shape, g.nonneg_rate = st.nonneg["shape"], st.nonneg["rate"]
             if st.F is not None:
                 g.feat = st.F.handle
                 for name in ("beta", "uhat", "mu_matrix", "Tinv", "lambda_beta", "cg_iters"):
@@ -1326,6 +1371,15 @@ class GibbsEngine:
         for st in self.ent:
             if st.spike is not None:
                 st.spike_accumulate()
+
+    def nonneg_accumulate(self):
+        """(entities with the non-negative prior, after the burn-in) this draw's rows and tau into their running sums, on the row
+        stream once the hyper step of this iteration (the hyperprior stream) has written tau"""
+        if self.ctx_h is not self.ctx:
+            self.ctx.stream.wait_stream(self.ctx_h.stream)
+        for st in self.ent:
+            if st.nonneg is not None:
+                st.nonneg_accumulate()
 
     def entity_noise_accumulate(self, ri=0):
         """(relation ri with a noise precision per row, after the burn-in) this iteration's tau into the running sum, on the row

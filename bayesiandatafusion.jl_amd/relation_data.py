@@ -54,6 +54,7 @@ class Entity:
         self.mu = 1.0          # hyper-prior for lambda_beta
         self.nu = 1e-3
         self.spike = None      # setSpikeAndSlab: {"incl_a", "incl_b", "shape", "rate"}; None: the Normal-Wishart prior
+        self.nonneg = None     # setNonNegative: {"shape", "rate"}; None: the Normal-Wishart prior
         self.new_rows = None   # setNewRows: the features (n* x numF) of instances that are not among the entity's rows
         self.model = None
 
@@ -81,6 +82,8 @@ def toStr(x):
                 s += f" λ={x.lambda_beta:1.1f}"
         if x.spike is not None and st.spike_state is not None:
             s += f" on:{st.spike_active()}"
+        if x.nonneg is not None:
+            s += " nn"
         return f"{x.name[:3]}[{s}]"
     kind = noise_kind(x)
     if kind in ("logit", "counts"):
@@ -612,6 +615,9 @@ def _spike_spec(entity, incl_a, incl_b, shape, rate):
 def _spike_guards(entity):
     if hasFeatures(entity):
         raise ArgumentError(f"Entity {entity.name} has features: the spike-and-slab prior (setSpikeAndSlab) does not take side information.")
+    if entity.nonneg is not None:
+        raise ArgumentError(f"Entity {entity.name} has the non-negative prior (setNonNegative): it does not take the spike-and-slab prior "
+                            "(setSpikeAndSlab) as well.")
     for r in entity.relations:
         if r.model.background is not None:
             raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
@@ -628,6 +634,62 @@ def check_spike(entity, world=1):
     _spike_guards(entity)
     if world > 1:
         raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): one rank only")
+
+
+def setNonNegative(entity, shape=1.0, rate=1.0):
+    """Non-negative factors for the rows of `entity` in place of the Normal-Wishart prior (the reference has none): loading d of row i
+    is u_id ~ N(0, 1 / tau_d) truncated to u_id >= 0 (a half-normal) with tau_d ~ Gamma(shape, rate) (rate parametrisation) -- Bayesian
+    non-negative matrix factorisation (Schmidt, Winther & Hansen 2009): with one entity of a relation constrained semi-NMF, with all of
+    them NMF proper.  macau() samples a row one component after the other from its truncated-normal conditional by inversion (DESIGN.md
+    section 26) and returns, under result["nonneg"][entity.name], the posterior means "precision" (tau_d) and "factors" (N x D, all
+    >= 0).  The per-component precision switches surplus components off by itself.  Centring: a Gaussian-kind relation ALL of whose
+    entities are non-negative is NOT centred -- its model is u.v itself, which is >= 0, so mean_value is 0 instead of the mean of its
+    values; every other relation keeps its centring (with one free entity the centred model is the right semi-NMF).  The verbose
+    line marks such an entity with " nn".  The entity takes no side information and no new rows (setNewRows), not the spike-and-slab
+    prior (setSpikeAndSlab), none of its relations a background (setBackground) or the dense path (setDense); one rank only; bpmf_vb and
+    macau_hmc do not take it.  The other entities keep their prior; every noise model composes."""
+    if not isinstance(entity, Entity):
+        raise ArgumentError(f"setNonNegative takes an Entity, not {type(entity).__name__}.")
+    spec = _nonneg_spec(entity, shape, rate)
+    _nonneg_guards(entity)
+    entity.nonneg = spec
+    return None
+
+
+def _nonneg_spec(entity, shape, rate):
+    def number(x):
+        return not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating)) and np.isfinite(x)
+    if not number(shape) or shape < 0.5:
+        raise ArgumentError(f"Entity {entity.name}: shape = {shape} must be a finite number, at least 0.5 (setNonNegative).")
+    if not number(rate) or rate <= 0:
+        raise ArgumentError(f"Entity {entity.name}: rate = {rate} must be a finite number above 0 (setNonNegative).")
+    return {"shape": float(shape), "rate": float(rate)}
+
+
+def _nonneg_guards(entity):
+    if hasFeatures(entity):
+        raise ArgumentError(f"Entity {entity.name} has features: the non-negative prior (setNonNegative) does not take side information.")
+    if entity.new_rows is not None:
+        raise ArgumentError(f"Entity {entity.name} has new rows (setNewRows): the non-negative prior (setNonNegative) does not take them.")
+    if entity.spike is not None:
+        raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): it does not take the non-negative prior "
+                            "(setNonNegative) as well.")
+    for r in entity.relations:
+        if r.model.background is not None:
+            raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
+                                "non-negative prior (setNonNegative), the background folds a dense Gram matrix into the prior precision.")
+        if r.model.dense:
+            raise ArgumentError(f"Relation {r.name} is dense (setDense): its entity {entity.name} does not take the non-negative prior "
+                                "(setNonNegative), a dense relation folds a Gram matrix into the prior precision.")
+
+
+def check_nonneg(entity, world=1):
+    """what an entity with the non-negative prior must still satisfy when a sampler is built on it"""
+    m = entity.nonneg
+    entity.nonneg = _nonneg_spec(entity, m.get("shape"), m.get("rate"))
+    _nonneg_guards(entity)
+    if world > 1:
+        raise ArgumentError(f"Entity {entity.name} has the non-negative prior (setNonNegative): one rank only")
 
 
 def setBackground(r, weight, value=0.0):
@@ -668,6 +730,10 @@ def _background_guards(r, what):
     _weight_guards(r, what)
     if r.model.robust is not None:
         raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
+    for en in r.entities:
+        if en.nonneg is not None:
+            raise ArgumentError(f"Entity {en.name} has the non-negative prior (setNonNegative): its relation {r.name} does not take {what}, "
+                                "which folds a Gram matrix into the prior precision.")
     ids = np.asarray(r.data.ids).reshape(r.data.nnz(), 2)
     if len(np.unique(ids, axis=0)) != len(ids):
         raise ArgumentError(f"Relation {r.name} lists a cell more than once: {what} would subtract it from the Gram term twice.")
@@ -761,6 +827,9 @@ def _dense_guards(r):
     for en in r.entities:
         if en.spike is not None:
             raise ArgumentError(f"Entity {en.name} has the spike-and-slab prior (setSpikeAndSlab): its relation {r.name} does not take {what}, "
+                                "which folds a Gram matrix into the prior precision.")
+        if en.nonneg is not None:
+            raise ArgumentError(f"Entity {en.name} has the non-negative prior (setNonNegative): its relation {r.name} does not take {what}, "
                                 "which folds a Gram matrix into the prior precision.")
     ids = np.asarray(r.data.ids).reshape(r.data.nnz(), 2)
     if len(np.unique(ids, axis=0)) != len(ids):
@@ -876,6 +945,8 @@ def _new_rows_guards(entity, F_new):
         raise ArgumentError(f"Entity {entity.name} has no features: new rows (setNewRows) are predicted from their features through beta.")
     if entity.spike is not None:
         raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): it takes no side information and no new rows (setNewRows).")
+    if entity.nonneg is not None:
+        raise ArgumentError(f"Entity {entity.name} has the non-negative prior (setNonNegative): it takes no side information and no new rows (setNewRows).")
     if feat.isempty(F_new):
         raise ArgumentError(f"Entity {entity.name}: F_new is empty (setNewRows takes a matrix with one row per new instance; None clears it).")
     have, want = feat.feature_shape(F_new)[1], feat.feature_shape(entity.F)[1]

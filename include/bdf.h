@@ -66,6 +66,9 @@ extern "C" {
 #define BDF_P_SPIKE_U 22       /* bdf_spike_hyper: ... and their uniforms (the same entity and row, pair = attempt; shape < 1: the boost's uniform is pair 0xffff) */
 #define BDF_P_SPIKE 23         /* bdf_sample_rows_spike: the inclusion uniform of component d of a row (entity = entity_tag, row = original row, pair d, words x and y) */
 #define BDF_P_DENSE 24         /* bdf_dense_impute: the normal of a hole of a dense relation (entity 0x800000 | rel_tag, row = the hole's index, normal 0) */
+#define BDF_P_NONNEG 25        /* bdf_sample_rows_nonneg: the uniform of component d of a row (entity = entity_tag, row = original row, pair d, words x and y) */
+#define BDF_P_NONNEG_N 26      /* bdf_nonneg_hyper: the gamma variate's normals (entity = entity_tag, row = component d, attempt t: normal 2 t) */
+#define BDF_P_NONNEG_U 27      /* bdf_nonneg_hyper: ... and its uniforms (the same entity and row, pair = attempt) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -293,6 +296,37 @@ int bdf_spike_hyper(bdf_ctx *ctx, int D, int64_t N, const double *sample, double
  * tau_d and n_d (the count of the draw: integers, exact in any order).  The caller zeroes both on ctx's stream. */
 int bdf_spike_accumulate(bdf_ctx *ctx, int D, int64_t N, const double *sample, const double *spike_state, double *row_sum,
                          double *hyper_sum);
+
+/* Non-negative prior of an entity's rows (csrc/k_nonneg.hip, csrc/nonneg.h):
+ *   u_id ~ N(0, 1 / tau_d) truncated to u_id >= 0,  tau_d ~ Gamma(shape, rate).
+ * tau (dev, D doubles): the prior's state.
+ * bdf_sample_rows_nonneg: the rows of bdf_sample_rows' (shard, n_shards) under this prior.  With P_i and c_i the row system of
+ * bdf_row_system for Lambda = diag(tau), mu = 0, and u the row's current value u_current[:, i] (dev, D x N), for d = 0 .. D-1 in order:
+ *   lambda = P_dd,  m = (c_d - sum_{k != d} P_dk u_k) / lambda (k ascending),  u_d = the map of csrc/nonneg.h at (m, lambda, U_d)
+ * -- the draw from N(m, 1 / lambda) truncated to [0, inf) by inversion -- with U_d the uniform of words x and y of block
+ * (BDF_P_NONNEG, entity_tag, i, pair d).  No normals are drawn.  out (dev, D x N): must alias neither u_current nor a factor matrix
+ * of another mode.  The rows go in chunks (bdf_ctx_set_nonneg_chunk): per chunk the wave-per-item kernel leaves the systems in the
+ * context's scratch, long rows split as bdf_sample_rows splits them, and a second launch sweeps them, one lane per row.  The
+ * result does not depend on the chunk size.  Relations created with a layout are not taken (one rank). */
+int bdf_sample_rows_nonneg(bdf_ctx *ctx, int D, int64_t N, int n_terms, const bdf_term *terms, const double *tau,
+                           const double *u_current, uint32_t entity_tag, int shard, int n_shards, double *out);
+/* parity hook: the sweep alone on given systems in bdf_row_system's layout -- P (dev, D x D x n_rows), c, u_current and out (dev,
+ * D x n_rows each); system i is that of original row row_begin + i (its random stream).  In chunks as bdf_sample_rows_nonneg. */
+int bdf_nonneg_sweep(bdf_ctx *ctx, int D, int64_t n_rows, const double *P, const double *c, const double *u_current,
+                     uint32_t entity_tag, int64_t row_begin, double *out);
+/* The prior's hyper step from the rows in `sample` (dev, D x N): q_d = sum_i u_id^2 (blocks of 256 rows in row order, then the
+ * blocks in order: independent of the launch), G_d ~ Gamma(shape + N / 2, 1) by Marsaglia-Tsang on the streams (BDF_P_NONNEG_N,
+ * entity_tag, row d) and (BDF_P_NONNEG_U, the same), tau_d = G_d / (rate + q_d / 2) into tau (dev, D).  shape >= 0.5 and finite,
+ * rate > 0 and finite.  Two launches on ctx's stream; not reentrant on one context (the partial sums live in its scratch). */
+int bdf_nonneg_hyper(bdf_ctx *ctx, int D, int64_t N, const double *sample, double shape, double rate, uint32_t entity_tag,
+                     double *tau);
+/* The running sums of the result, one call per retained draw: row_sum (dev, D x N) += u; hyper_sum (dev, D) += tau.  The caller
+ * zeroes both on ctx's stream. */
+int bdf_nonneg_accumulate(bdf_ctx *ctx, int D, int64_t N, const double *sample, const double *tau, double *row_sum,
+                          double *hyper_sum);
+/* rows per chunk of bdf_sample_rows_nonneg and bdf_nonneg_sweep on this context; 0: the default, the most rows whose systems
+ * ((D^2 + D) doubles each) stay under 1 GiB of scratch */
+int bdf_ctx_set_nonneg_chunk(bdf_ctx *ctx, int64_t rows);
 
 /* ---- a15: hyperprior  (src/sampling.jl:116-127, src/normal_wishart.jl:38-42, macau.jl:120-134) */
 /* sumU (dev D) = sum_i U[:,i], UUt (dev D x D) = U U' with U = sample - uhat (uhat nullable);
@@ -922,6 +956,13 @@ typedef struct {
     int32_t _pad_spike;
     double spike_a, spike_b, spike_shape, spike_rate;   /* incl_a, incl_b, shape, rate of bdf_spike_hyper                   */
     double *spike_state;          /* dev, 4 D: pi, tau, logit pi, log tau (initialised by the caller)                       */
+    /* the non-negative prior in place of the Normal-Wishart one (a zeroed tail is "none"): the entity's rows by
+     * bdf_sample_rows_nonneg from its current rows, its hyper step by bdf_nonneg_hyper.  Ordered like an entity with the
+     * spike-and-slab prior.  Not together with it, side information or a background / dense relation; one rank                    */
+    int32_t nonneg;               /* 1: on                                                                                  */
+    int32_t _pad_nonneg;
+    double nonneg_shape, nonneg_rate;   /* shape, rate of bdf_nonneg_hyper                                                  */
+    double *nonneg_tau;           /* dev, D (initialised by the caller)                                                     */
 } bdf_gibbs_entity;
 int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const bdf_gibbs_entity *entities, bdf_gibbs **out);
 int bdf_gibbs_destroy(bdf_gibbs *g);

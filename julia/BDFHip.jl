@@ -197,6 +197,45 @@ function spike_accumulate!(c::Context, D, N, sample::DevArray{Float64}, spike_st
                 c.h, D, N, sample.p, spike_state.p, row_sum.p, hyper_sum.p))
 end
 
+"""
+    sample_rows_nonneg!(ctx, D, N, terms, tau, u_current, entity_tag, out; shard=0, n_shards=1)
+
+The rows of an entity with the non-negative prior (the reference has none): u_id ~ N(0, 1 / tau_d) truncated to u_id >= 0, one
+coordinate after the other from its truncated-normal conditional by inversion, starting from the row's current value `u_current`
+(D x N); `tau` holds the D precisions.
+"""
+function sample_rows_nonneg!(c::Context, D, N, terms::Vector{Term}, tau::DevArray{Float64}, u_current::DevArray{Float64}, entity_tag,
+                             out::DevArray{Float64}; shard=0, n_shards=1)
+    check(ccall((:bdf_sample_rows_nonneg, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Cint, Ptr{Term}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Cint, Cint, Ptr{Cvoid}),
+                c.h, D, N, length(terms), terms, tau.p, u_current.p, entity_tag, shard, n_shards, out.p))
+end
+
+"parity hook: the non-negative prior's coordinate sweep alone on given systems P (D x D x n_rows), c (D x n_rows); system i is that of row row_begin + i"
+function nonneg_sweep!(c::Context, D, n_rows, P::DevArray{Float64}, cvec::DevArray{Float64}, u_current::DevArray{Float64}, entity_tag, row_begin,
+                       out::DevArray{Float64})
+    check(ccall((:bdf_nonneg_sweep, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, UInt32, Int64, Ptr{Cvoid}),
+                c.h, D, n_rows, P.p, cvec.p, u_current.p, entity_tag, row_begin, out.p))
+end
+
+"the non-negative prior's hyper step: tau_d ~ Gamma(shape + N / 2, rate + q_d / 2) into tau"
+function nonneg_hyper!(c::Context, D, N, sample::DevArray{Float64}, shape, rate, entity_tag, tau::DevArray{Float64})
+    check(ccall((:bdf_nonneg_hyper, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Float64, Float64, UInt32, Ptr{Cvoid}),
+                c.h, D, N, sample.p, shape, rate, entity_tag, tau.p))
+end
+
+"one retained draw into the running sums of the non-negative result: row_sum (D x N) += u; hyper_sum (D) += tau"
+function nonneg_accumulate!(c::Context, D, N, sample::DevArray{Float64}, tau::DevArray{Float64}, row_sum::DevArray{Float64},
+                            hyper_sum::DevArray{Float64})
+    check(ccall((:bdf_nonneg_accumulate, lib), Cint, (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, D, N, sample.p, tau.p, row_sum.p, hyper_sum.p))
+end
+
+"rows per chunk of the non-negative prior's launches on this context; 0: the default"
+set_nonneg_chunk!(c::Context, rows) = check(ccall((:bdf_ctx_set_nonneg_chunk, lib), Cint, (Ptr{Cvoid}, Int64), c.h, rows))
+
 "ConditionalNormalWishart + rand (src/sampling.jl:116-127, src/normal_wishart.jl:38-42; call site src/macau.jl:120-134)"
 function update_prior!(c::Context, D, N, sample, uhat, sumU, UUt, mu0, b0, Tinv, nu, entity_tag, mu, Lambda;
                        prior_pack=nothing, draws=nothing)   # prior_pack: bdf_prior_pack_doubles(D) doubles; draws: bdf_hyper_draws
@@ -326,6 +365,11 @@ struct GibbsEntity                                # bdf_gibbs_entity, field for 
     spike::Int32; _pad_spike::Int32
     spike_a::Float64; spike_b::Float64; spike_shape::Float64; spike_rate::Float64
     spike_state::Ptr{Cvoid}
+    # the non-negative prior in place of the Normal-Wishart one (nonneg = 0: none): shape, rate of nonneg_hyper! and tau (D doubles).
+    # Not with the spike-and-slab prior, side information or a background / dense relation; one rank
+    nonneg::Int32; _pad_nonneg::Int32
+    nonneg_shape::Float64; nonneg_rate::Float64
+    nonneg_tau::Ptr{Cvoid}
 end
 
 mutable struct Gibbs
