@@ -395,7 +395,10 @@ extern "C" int bdf_debug_cg_stamps(unsigned long long *host512)
 // launches with the two dot products summed over the chunks in chunk order by every workgroup that needs them:
 //   a: z = Z + lambda p, partial z.p          b: ak; x += ak p; r -= ak z; partial r.r          c: stop test; p = bk p + r
 // bkden is double-buffered by iteration parity (slot 1 = s.bkden, written by k_cg_pre at iteration 1; slot 0 = bkden0): in c
-// every workgroup of a column reads the old value while chunk 0 writes the new one.
+// every workgroup of a column reads the old value and the new one goes to the other slot.  active / iters have no second slot: they
+// are written by the workgroup of c that finishes last, after every chunk of every column has read them (chunk 0 of a column used to
+// write them while the column's other chunks -- unordered against it -- could still be about to read them and then skip their part
+// of p: harmless while the grid is resident at once, wrong iterates when it is not).
 struct CgChunks { int G; int64_t len; double *partA, *partB, *bkden0; };
 
 __device__ __forceinline__ bool cg_all_stopped(const CgState &s, int iter)
@@ -458,28 +461,40 @@ __global__ __launch_bounds__(256) void k_cg_long_c(CgState s, CgChunks c, int it
         double rr = 0.0;
         for (int q = 0; q < c.G; q++) rr += c.partB[d * c.G + q];
         const bool go = !(sqrt(rr) < s.tolb[d]);
-        double *bk_old = (iter & 1) ? s.bkden : c.bkden0, *bk_new = (iter & 1) ? c.bkden0 : s.bkden;
+        const double *bk_old = (iter & 1) ? s.bkden : c.bkden0;
         if (go) {
             const double bk = rr / bk_old[d];
             const int64_t off = (int64_t)d * s.n, i0 = g * c.len, i1 = (i0 + c.len < s.n) ? i0 + c.len : s.n;
             for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) s.P[off + i] = fma(bk, s.P[off + i], s.R[off + i]);
         }
-        __syncthreads();                                  // every thread has read active / iters
-        if (g == 0 && threadIdx.x == 0) {
-            if (!go) { s.active[d] = 0; atomicSub(s.nactive, 1); }
-            else { bk_new[d] = rr; s.bknum[d] = rr; s.iters[d] = iter + 1; }
-        }
     }
+    // the columns' bookkeeping by the workgroup that FINISHES LAST, a thread per column (every other workgroup -- the other chunks of
+    // the column among them, which nothing orders against chunk 0 -- has read active / iters by then; as in k_cg_rm_c): the same
+    // sum of the partials in the same order
+    __shared__ int last;
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
-        if (atomicAdd(s.done_blocks, 1) == s.D * c.G - 1) {
-            *s.done_blocks = 0;
-            const int na = __hip_atomic_load(s.nactive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s.status[1] = (uint64_t)(iter < maxiter ? na : 0);
-            __threadfence_system();
-            s.status[0] = ((uint64_t)s.gen << 32) | (uint32_t)iter;
-        }
+        last = atomicAdd(s.done_blocks, 1) == s.D * c.G - 1;
+    }
+    __syncthreads();
+    if (!last) return;
+    const int dd = threadIdx.x;
+    if (dd < s.D && iter < maxiter && s.active[dd] && s.iters[dd] == iter) {
+        double rr = 0.0;
+        for (int q = 0; q < c.G; q++) rr += c.partB[dd * c.G + q];
+        double *bk_new = (iter & 1) ? c.bkden0 : s.bkden;
+        if (sqrt(rr) < s.tolb[dd]) { s.active[dd] = 0; atomicSub(s.nactive, 1); }
+        else { bk_new[dd] = rr; s.bknum[dd] = rr; s.iters[dd] = iter + 1; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *s.done_blocks = 0;
+        __threadfence();
+        const int na = __hip_atomic_load(s.nactive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        s.status[1] = (uint64_t)(iter < maxiter ? na : 0);
+        __threadfence_system();
+        s.status[0] = ((uint64_t)s.gen << 32) | (uint32_t)iter;
     }
 }
 

@@ -3,6 +3,9 @@ sample_beta, sample_lambda_beta -- against the CPU oracle and against the dense 
 (test/solver.jl, test/sparse_csr.jl, test/sparsebin_csr.jl, test/parallel_matrix.jl:41-109, test/heavy_copyto.jl:28-69).
 Tolerances: products 1e-12 relative; CG solutions 1e-9 relative (the solver stops at eps*numF like the reference);
 sampled beta 1e-7 relative for the same normals.
+The shapes here are the ones the reference's tests and the benchmark use; the sizes at which the dispatch of these kernels changes
+(16 / 32 / 64 columns and features, the solvers' and the CG step kernels' limits, the sparse kernels' row lengths and tails, more than
+32 latent dimensions) are in tests/test_gpu_feature_edges.py, whose header maps every branch of the dispatch to its case.
 """
 import ctypes as C
 

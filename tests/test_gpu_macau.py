@@ -167,10 +167,14 @@ def _oracle_macau(O, rd, D, seed, iters, feats, use_ff=True, lambda_beta0=1.0):
     return S, mu, Lam, beta, lb
 
 
-@pytest.mark.parametrize("with_feat,use_ff", [(False, True), (True, True), (True, False)])
-def test_whole_iterations_match_oracle(B, O, with_feat, use_ff):
+@pytest.mark.parametrize("with_feat,use_ff,D", [
+    pytest.param(False, True, 6, id="False-True"), pytest.param(True, True, 6, id="True-True"), pytest.param(True, False, 6, id="True-False"),
+    # above 32 latent dimensions with side information: k_noise_prep / k_noise_rows<64>, the beta update's products at 33 .. 64
+    # right-hand columns, the direct solve and the CG solve with more than 32 columns
+    (True, True, 40), (True, False, 40), (True, True, 64), (True, False, 64)])
+def test_whole_iterations_match_oracle(B, O, with_feat, use_ff, D):
     rng = np.random.default_rng(8)
-    N1, N2, D, nnz = 60, 45, 6, 900
+    N1, N2, nnz = 60, 45, 900
     ids = np.stack([rng.integers(1, N1 + 1, nnz), rng.integers(1, N2 + 1, nnz)], axis=1)
     vals = rng.standard_normal(nnz)
     F = rng.standard_normal((N1, 4)) if with_feat else None
