@@ -26,6 +26,7 @@ P_NOISE_N, P_NOISE_U = 19, 20
 P_SPIKE_N, P_SPIKE_U, P_SPIKE = 21, 22, 23
 P_DENSE = 24
 P_NONNEG, P_NONNEG_N, P_NONNEG_U = 25, 26, 27
+P_BIAS, P_BIAS_N, P_BIAS_U = 28, 29, 30
 
 
 class ArgumentError(ValueError):
@@ -91,6 +92,12 @@ class GibbsEntity(C.Structure):
                 ("nonneg_tau", C.c_void_p)]
 
 
+class BiasTerm(C.Structure):
+    """bdf_bias_term"""
+    _fields_ = [("mode", C.c_int32), ("_pad", C.c_int32), ("shape", C.c_double), ("rate", C.c_double), ("bias", C.c_void_p),
+                ("lambda_", C.c_void_p)]
+
+
 class GibbsRelation(C.Structure):
     """bdf_gibbs_relation"""
     _fields_ = [("rel", C.c_void_p), ("entity_of_mode", C.c_int32 * BDF_MAX_MODES), ("mean_value", C.c_double), ("alpha_dev", C.c_void_p),
@@ -105,7 +112,9 @@ class GibbsRelation(C.Structure):
                 ("noise_mode", C.c_int32), ("_pad_noise", C.c_int32), ("noise_shape", C.c_double), ("noise_rate", C.c_double),
                 ("noise_tau", C.c_void_p),
                 ("dense_R", C.c_void_p), ("dense_C", C.c_void_p), ("dense_sums", C.c_void_p), ("dense_sum_r2", C.c_double),
-                ("dense_holes", C.c_void_p), ("dense_stats", C.c_void_p)]
+                ("dense_holes", C.c_void_p), ("dense_stats", C.c_void_p),
+                ("n_bias", C.c_int32), ("_pad_bias", C.c_int32), ("bias", BiasTerm * BDF_MAX_MODES), ("bias_resid", C.c_void_p),
+                ("bias_test", C.c_void_p)]
 
 
 class BackgroundTerm(C.Structure):
@@ -193,6 +202,9 @@ _SIGS = {
                               C.c_void_p, C.c_void_p]),
     "bdf_entity_noise_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double,
                                         C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_bias_draw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p,
+                                C.c_uint32, C.c_int, C.POINTER(BiasTerm), C.c_void_p, C.c_void_p]),
+    "bdf_bias_baseline": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(BiasTerm), C.c_double, C.c_void_p]),
     "bdf_pairs_set_precision_scale": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "bdf_pairs_weighted_sse": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_void_p, C.c_void_p]),
     "bdf_background_prior": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.POINTER(BackgroundTerm), C.c_void_p, C.c_int, C.c_void_p,

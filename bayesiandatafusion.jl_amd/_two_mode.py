@@ -33,6 +33,8 @@ def relation_of(data, num_latent, who):
         raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the {rel.model.pg['model']} noise model (use macau)")
     if rel.model.entity_noise is not None:
         raise ArgumentError(f"{who} has one noise precision for every cell; {rel.name} has a noise precision per row (use macau)")
+    if rel.model.bias:
+        raise ArgumentError(f"{who} models a cell as mean + u.v; {rel.name} has biases (setBias; use macau)")
     if rel.model.background is not None:
         raise ArgumentError(f"{who} fits the listed cells only; {rel.name} has a background (use macau)")
     if rel.model.dense:

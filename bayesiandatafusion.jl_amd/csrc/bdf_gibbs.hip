@@ -408,6 +408,30 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
             BDF_REQUIRE(!r.probit && !r.censor && !r.interval && !r.ordinal && r.robust_nu == 0.0 && !r.pg_model && !(r.bg_weight > 0.0) && !r.feat && !g->comm, BDF_ERR_ARG,
                         "bdf_gibbs_set_relations: relation %d: the per-row noise model (noise_mode) takes neither the probit, censored, interval, ordinal, robust or a Polya-Gamma model, a background, relation features nor a communicator", k);
         }
+        if (r.n_bias != 0) {
+            BDF_REQUIRE(r.n_bias >= 1 && r.n_bias <= r.rel->n_modes, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: n_bias=%d must be 0 (none) or at most the relation's %d modes", k, r.n_bias, r.rel->n_modes);
+            for (int t = 0; t < r.n_bias; t++) {
+                const bdf_bias_term &b = r.bias[t];
+                BDF_REQUIRE(b.mode >= 0 && b.mode < r.rel->n_modes, BDF_ERR_ARG,
+                            "bdf_gibbs_set_relations: relation %d: bias term %d: mode=%d must be in 0..%d", k, t, b.mode, r.rel->n_modes - 1);
+                for (int u = 0; u < t; u++)
+                    BDF_REQUIRE(r.bias[u].mode != b.mode, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: bias mode %d is listed twice", k, b.mode);
+                BDF_REQUIRE(b.shape > 0.0 && std::isfinite(b.shape) && b.rate > 0.0 && std::isfinite(b.rate), BDF_ERR_ARG,
+                            "bdf_gibbs_set_relations: relation %d: bias term %d: shape=%g and rate=%g must be positive and finite", k, t, b.shape, b.rate);
+                BDF_REQUIRE(b.bias && b.lambda, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: bias term %d has no bias / lambda buffer", k, t);
+            }
+            BDF_REQUIRE(r.train && r.linear && r.bias_resid, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: biases (n_bias) need the observations as pairs (train), a linear and a bias_resid buffer", k);
+            BDF_REQUIRE(!r.probit && !r.censor && !r.interval && !r.ordinal && !r.obs_precision && !r.pg_model && r.noise_mode == 0 && !(r.bg_weight > 0.0) &&
+                        !r.dense_R && !r.feat && !g->comm, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: biases (n_bias) take Gaussian noise of one precision: neither another noise model, observation weights, a background, a dense relation, relation features nor a communicator", k);
+            BDF_REQUIRE((r.bias_test != nullptr) == (r.test_baseline != nullptr), BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: biases take bias_test and test_baseline together", k);
+            BDF_REQUIRE(!r.bias_test || r.bias_test->n_modes == r.rel->n_modes, BDF_ERR_ARG,
+                        "bdf_gibbs_set_relations: relation %d: bias_test has %d modes, the relation %d", k, r.bias_test ? r.bias_test->n_modes : 0, r.rel->n_modes);
+        } else
+            BDF_REQUIRE(!r.bias_test && !r.bias_resid, BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: bias_test / bias_resid without n_bias", k);
         BDF_REQUIRE(r.robust_nu == 0.0 || (r.robust_nu >= 1.0 && std::isfinite(r.robust_nu)), BDF_ERR_ARG,
                     "bdf_gibbs_set_relations: relation %d: robust_nu=%g must be 0 (off) or at least 1 and finite", k, r.robust_nu);
         BDF_REQUIRE(!(r.robust_nu > 0.0) || (r.train && r.obs_precision), BDF_ERR_ARG, "bdf_gibbs_set_relations: relation %d: the robust model needs its observations as pairs (train) and an obs_precision buffer", k);
@@ -475,7 +499,7 @@ inline bool draws_latent(const bdf_gibbs_relation &r) { return r.probit || r.cen
 // does update_relations() enqueue anything for the relation?  (Known weights alone do not: the rows just read them.)
 inline bool has_model(const bdf_gibbs_relation &r)
 {
-    return r.alpha_sample || r.feat || draws_latent(r) || r.robust_nu > 0.0 || r.noise_mode != 0 || (r.dense_R && r.dense_holes);
+    return r.alpha_sample || r.feat || draws_latent(r) || r.robust_nu > 0.0 || r.noise_mode != 0 || (r.dense_R && r.dense_holes) || r.n_bias != 0;
 }
 
 // out[m] = the current sample of the entity that is mode m
@@ -580,7 +604,7 @@ void fill_terms(const bdf_gibbs *g, const bdf_gibbs_entity &e, bdf_term *terms)
         terms[t].alpha_dev = nullptr; terms[t].obs_precision = nullptr;
         if (const bdf_gibbs_relation *gr = relation_of(g, e.terms[t].rel)) {        // a relation with a model of its own
             terms[t].alpha_dev = gr->probit ? nullptr : gr->alpha_dev;
-            terms[t].linear_values = (gr->feat || draws_latent(*gr)) ? gr->linear : nullptr;
+            terms[t].linear_values = (gr->feat || draws_latent(*gr) || gr->n_bias != 0) ? gr->linear : nullptr;      // (biases: mean + the cell's biases)
             if (gr->probit) terms[t].alpha = 1.0;            // the latent's variance
             terms[t].obs_precision = gr->obs_precision;      // known weights, or the omega of the robust draw
             if (gr->bg_weight > 0.0) {
@@ -616,6 +640,18 @@ int update_relations(bdf_gibbs *g)
         if (r.noise_mode != 0 && (rc = bdf_entity_noise_draw(R, r.rel, r.noise_mode - 1, r.train, D, fac, r.mean_value, 0.0, r.alpha_dev, r.noise_shape,
                                                              r.noise_rate, r.rel_tag, r.noise_tau, r.obs_precision, r.alpha_sample ? g->rel_sse + 1 : nullptr)))
             return rc;
+        // biases: every biased mode's rows and precision given the factors and the PREVIOUS iteration's alpha, before sample_alpha --
+        // whose sum of squares then sees the new biases through the training pairs' baseline (`linear`); the rows then read `linear`
+        if (r.n_bias != 0) {
+            if ((rc = bdf_bias_draw(R, r.rel, r.train, D, fac, r.mean_value, 0.0, r.alpha_dev, r.rel_tag, r.n_bias, r.bias, r.bias_resid, r.linear)))
+                return rc;
+            if (r.bias_test) {
+                // the test pairs' baseline is read by the prediction stream: its updates so far must have completed
+                for (int k = 0; k < 3; k++)
+                    if (g->n_pred > (uint64_t)k) BDF_HIP(hipStreamWaitEvent(R->stream, g->ev_pred[(g->n_pred - 1 - (uint64_t)k) % 3], 0));
+                if ((rc = bdf_bias_baseline(R, r.bias_test, r.n_bias, r.bias, r.mean_value, r.test_baseline))) return rc;
+            }
+        }
         // dense: the holes given the rows and the PREVIOUS iteration's alpha, into dense_R, before sample_alpha -- whose sum then runs
         // over all N M cells
         if (r.dense_R && r.dense_holes && (rc = bdf_dense_impute(R, r.dense_holes, D, fac, 0.0, r.alpha_dev, r.rel_tag, r.dense_R, r.rel->dims[0],
@@ -923,6 +959,14 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
         if (draws_latent(r)) pieces.push_back({r.linear + r.first_obs, (size_t)r.train->n * sizeof(double), false, 0});
         if (r.robust_nu > 0.0 || r.pg_model || r.noise_mode != 0) pieces.push_back({r.obs_precision, (size_t)r.train->n * sizeof(double), false, 0});       // the last omega
         if (r.noise_mode != 0) pieces.push_back({r.noise_tau, (size_t)r.rel->dims[r.noise_mode - 1] * sizeof(double), false, 0});           // ... and the last tau
+        if (r.n_bias != 0) {                // the biases, their precisions, the base they leave the rows and the test pairs
+            for (int t = 0; t < r.n_bias; t++) {
+                pieces.push_back({r.bias[t].bias, (size_t)r.rel->dims[r.bias[t].mode] * sizeof(double), false, 0});
+                pieces.push_back({r.bias[t].lambda, sizeof(double), false, 0});
+            }
+            pieces.push_back({r.linear, (size_t)r.train->n * sizeof(double), false, 0});
+            if (r.bias_test) pieces.push_back({r.test_baseline, (size_t)r.bias_test->n * sizeof(double), false, 0});
+        }
         if (r.ordinal) {                    // the edges, the step size, the counters and the trace; the bounds made from the edges
             pieces.push_back({r.ordinal->state_dev, r.ordinal->state_doubles * sizeof(double), false, 0});
             pieces.push_back({const_cast<double *>(r.interval), (size_t)r.train->n * 2 * sizeof(double), false, 0});

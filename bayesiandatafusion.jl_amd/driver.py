@@ -112,6 +112,10 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         eng.rel[0].omega_sum = None                          # (an engine that is reused starts the posterior mean of omega again)
     if noise is not None:
         eng.rel[0].tau_sum = None                            # (... and of tau)
+    # relations with biases (setBias): sampled on any relation, the verbose line shows the first one's
+    biased = any(dr.bias is not None for dr in eng.rel)
+    if biased:
+        eng.bias_reset()                                     # (... and of the biases and their precisions)
     # entities with the spike-and-slab prior (setSpikeAndSlab)
     spiked = [st for st in eng.ent if st.spike is not None]
     if eng is engine:
@@ -194,6 +198,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             eng.robust_accumulate()                           # this iteration's omega into its running sum, on the row stream
         if noise is not None and i > burnin:
             eng.entity_noise_accumulate()                     # this iteration's tau into its running sum, on the row stream
+        if biased and i > burnin:
+            eng.bias_accumulate()                             # this iteration's biases and precisions into their running sums, on the row stream
         if spiked and i > burnin:
             eng.spike_accumulate()                            # this draw's inclusions, pi and tau into their running sums, on the row stream
         if nonneg and i > burnin:
@@ -255,6 +261,7 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                 newr.auc()                                    # behind the cells' update on the row stream, beside its 8 scalars
             wbar = eng.robust_mean() if (verbose and robust is not None) else None
             tbar = eng.entity_noise_mean() if (verbose and noise is not None) else None
+            brms = eng.bias_rms() if (verbose and rel._dev.bias is not None) else None
             eng.sync()
             eng.sync_host_scalars()
             if haveTest:
@@ -280,6 +287,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                     lstr += f" w̄={float(wbar.item()):.3f}"
                 if tbar is not None:
                     lstr += f" τ̄={float(tbar.item()):.3f}"
+                if brms is not None:
+                    lstr += "".join(f" b:{float(x.item()):.3f}" for x in brms)
                 if newr is not None:
                     nsc = max(newr.n_scored, 1)
                     lstr += f" new:RMSE={math.sqrt(new_rep[0] / nsc):6.4f} ROC={new_rep[8]:6.4f}"
@@ -329,6 +338,9 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         ts, N = rel._dev.tau_sum, int(rel.data.dims[noise["mode"] - 1])
         result["noise"] = {"entity": rel.entities[noise["mode"] - 1].name, "shape": noise["shape"], "rate": noise["rate"],
                            "precision": (ts.cpu().numpy()[:N] / psamples) if (ts is not None and psamples) else np.full(N, np.nan)}
+    if biased:
+        # per relation and biased entity: the posterior mean bias of every row and the posterior mean of their precision
+        result["bias"] = eng.bias_result(psamples)
     if spiked:
         # posterior means of pi_d, tau_d, the share of rows with a nonzero loading and [u_id != 0]
         result["spike"] = {en.name: st.spike_result() for en, st in zip(data.entities, eng.ent) if st.spike is not None}
@@ -422,6 +434,13 @@ def pred(r, probe_vec=None, F=None):
     ids = r.data.ids if probe_vec is None else np.asarray(getattr(probe_vec, "ids", probe_vec))[:, :len(r.entities)]
     pairs = DevicePairs(ctx, ids, np.zeros(len(ids)))
     facs = [e.model._dev.sample for e in r.entities]
+    base = None
+    if eng_rel.bias is not None and len(ids):
+        # the current draw's biases: the pairs' base is mean + the cell's biases (bdf_bias_baseline)
+        from ._lib import check, lib
+        from .engine import bias_baseline
+        base = bias_baseline(eng_rel, r.model.mean_value, pairs, ctx.zeros(len(ids)))
+        check(lib().bdf_pairs_set_baseline(pairs.handle, base.data_ptr()))
     out = pairs.predict(facs[0].shape[1], facs, r.model.mean_value).cpu().numpy()
     pairs.close()
     return out

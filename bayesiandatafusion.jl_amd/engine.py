@@ -276,6 +276,9 @@ class DeviceRelation:
         self.robust_nu, self.pg_model, self.pg_r = 0.0, 0, 0.0
         # a noise precision per row of one entity (setEntityNoise): {"mode", "shape", "rate"}; tau per row of that mode; its running sum
         self.noise = self.tau = self.tau_sum = None
+        # biases (setBias): {mode0: {"shape", "rate"}}; per biased mode its bias vector (dims[mode0]); the modes' lambda, one double
+        # each in rising mode order; the draw's residual scratch; the running sums of both (macau() starts them)
+        self.bias_spec = self.bias = self.bias_lambda = self.bias_resid = self.bias_sum = self.bias_lambda_sum = None
         # background cells (setBackground): {"weight", "value"}; the caller's weights (omega is then what the rows read, omega_k - c0)
         self.bg = self.bg_weights = None
         # a dense relation (setDense): {"R": N x M, the values without their mean; "C": per mode, its rows of R V / R' U; "sum_r2":
@@ -289,7 +292,8 @@ class DeviceRelation:
     def has_model(self):
         """a model of its own -- alpha sampled, relation-level side information, a noise model other than fixed-precision
         Gaussian noise: registered with the library's iteration, which steps it before the rows of every iteration"""
-        return self.alpha_sample or self.F is not None or self.kind != "gauss" or self.bg is not None or self.dense is not None
+        return (self.alpha_sample or self.F is not None or self.kind != "gauss" or self.bg is not None or self.dense is not None
+                or self.bias is not None)
 
     def index(self, mode0):
         rp, ri = _lib.c_i64p(), _lib.c_i64p()
@@ -1029,6 +1033,24 @@ class DeviceOrdinal:
             pass
 
 
+def _bias_terms(dr):
+    """DeviceRelation dr's biased modes as bdf_bias_term records, rising"""
+    terms = (_lib.BiasTerm * len(dr.bias_spec))()
+    for t, (m0, sp) in enumerate(dr.bias_spec.items()):
+        terms[t].mode, terms[t].shape, terms[t].rate = m0, sp["shape"], sp["rate"]
+        terms[t].bias, terms[t].lambda_ = dr.bias[m0].data_ptr(), dr.bias_lambda.data_ptr() + 8 * t
+    return terms
+
+
+def bias_baseline(dr, mean_value, pairs, out):
+    """out (device, one double per pair, the caller's order) = mean_value + the current biases of every pair over the entities of
+    DeviceRelation dr (bdf_bias_baseline), on the pairs' stream behind the relation's stream, where the biases are drawn"""
+    if pairs.ctx is not dr.ctx:
+        pairs.ctx.stream.wait_stream(dr.ctx.stream)
+    check(lib().bdf_bias_baseline(pairs.ctx.handle, pairs.handle, len(dr.bias_spec), _bias_terms(dr), float(mean_value), _ptr(out)))
+    return out
+
+
 class GibbsEngine:
     """Device state of a RelationData and the per-iteration steps of macau.jl:80-140."""
 
@@ -1132,8 +1154,8 @@ class GibbsEngine:
             # there); a relation with features: the prediction updates stay there (their baseline is refreshed on the row stream)
             if os.environ.get("BDF_NO_OVERLAP"):
                 self.ctx_h = self.ctx_p = self.ctx
-            elif not all(feat.isempty(r.F) for r in data.relations):
-                self.ctx_p = self.ctx
+            elif not all(feat.isempty(r.F) and not r.model.bias for r in data.relations):
+                self.ctx_p = self.ctx            # (biases: the same -- their draw refreshes the test pairs' base on the row stream)
         torch.cuda.synchronize(self.ctx.device)      # everything set up above (on torch's streams too) is in place
 
     def _build_model(self, r, dr, kind):
@@ -1213,6 +1235,17 @@ class GibbsEngine:
             dr.pg_model, dr.pg_r = (1, 0.0) if kind == "logit" else (2, float(m.pg["r"]))
             dr.omega = ctx.tensor(np.ones(max(nn, 1)))
             dr.train.set_pg_link(dr.pg_model, dr.pg_r)
+        if m.bias:
+            # biases (setBias): a bias per row of every listed mode and a precision per mode, drawn before alpha
+            # and the rows of every iteration (bdf_bias_draw), which leaves mean + the cell's biases in linear_values: what the rows
+            # of every entity read as their base, and the training pairs' baseline -- for alpha's sum of squares, rmse_train and WAIC
+            dr.bias_spec = {int(mode) - 1: dict(spec) for mode, spec in sorted(m.bias.items())}
+            dr.train = self._sorted_pairs(ctx, r, ids, values, dr.train)
+            dr.linear = ctx.tensor(np.full(max(nn, 1), m.mean_value))
+            check(lib().bdf_pairs_set_baseline(dr.train.handle, _ptr(dr.linear)))
+            dr.bias = {m0: ctx.zeros(max(int(r.data.dims[m0]), 1)) for m0 in dr.bias_spec}
+            dr.bias_lambda = ctx.tensor([sp["shape"] / sp["rate"] for sp in dr.bias_spec.values()])
+            dr.bias_resid = ctx.zeros(max(nn, 1))
         if m.background is not None:
             # background cells (setBackground): every unlisted cell observes `value` with precision alpha c0.  The
             # rows of both entities are sampled with the prior row_prior() makes from the other entity's sum and Gram matrix (fold_sums:
@@ -1320,6 +1353,12 @@ class GibbsEngine:
                 g.dense_R, g.dense_C, g.dense_sum_r2 = dn["R"].data_ptr(), dn["C"][0].data_ptr(), dn["sum_r2"]
                 if dn["holes"] is not None:
                     g.dense_holes, g.dense_stats = dn["holes"].handle, dn["stats"].data_ptr()
+            if dr.bias is not None:
+                g.n_bias, g.bias_resid = len(dr.bias_spec), dr.bias_resid.data_ptr()
+                for t, bt in enumerate(_bias_terms(dr)):
+                    g.bias[t] = bt
+                if ri == 0 and dr.test_baseline is not None:
+                    g.bias_test, g.test_baseline = self._test_pairs.handle, dr.test_baseline.data_ptr()
             if dr.noise is not None:
                 g.noise_mode, g.noise_shape, g.noise_rate, g.noise_tau = dr.noise["mode"], dr.noise["shape"], dr.noise["rate"], dr.tau.data_ptr()
             for name, t in (("linear", dr.linear), ("censor", dr.censor), ("interval", dr.interval), ("ordinal_codes", dr.ord_codes),
@@ -1380,6 +1419,51 @@ class GibbsEngine:
         for st in self.ent:
             if st.nonneg is not None:
                 st.nonneg_accumulate()
+
+    def bias_baseline(self, ri, pairs, out):
+        """bias_baseline() of relation ri"""
+        return bias_baseline(self.rel[ri], self.data.relations[ri].model.mean_value, pairs, out)
+
+    def bias_reset(self):
+        """(an engine that is reused) the biases' running sums start again"""
+        for dr in self.rel:
+            dr.bias_sum = dr.bias_lambda_sum = None
+
+    def bias_accumulate(self):
+        """(relations with biases, after the burn-in) this iteration's biases and precisions into their running sums, on the row
+        stream: behind the draw that wrote them and ahead of the next one"""
+        with torch.cuda.stream(self.ctx.stream):
+            for dr in self.rel:
+                if dr.bias is None:
+                    continue
+                if dr.bias_sum is None:
+                    dr.bias_sum = {m0: torch.zeros_like(b) for m0, b in dr.bias.items()}
+                    dr.bias_lambda_sum = torch.zeros_like(dr.bias_lambda)
+                for m0, b in dr.bias.items():
+                    dr.bias_sum[m0] += b
+                dr.bias_lambda_sum += dr.bias_lambda
+
+    def bias_rms(self, ri=0):
+        """-> device scalars, the rms of this iteration's biases per biased entity of relation ri (the verbose line reads them with
+        the other scalars)"""
+        r, dr = self.data.relations[ri], self.rel[ri]
+        with torch.cuda.stream(self.ctx.stream):
+            return [b[:int(r.data.dims[m0])].square().mean().sqrt() for m0, b in dr.bias.items()]
+
+    def bias_result(self, psamples):
+        """result["bias"]: per relation with biases and biased entity, the posterior mean bias per row and the posterior mean precision"""
+        out = {}
+        for r, dr in zip(self.data.relations, self.rel):
+            if dr.bias is None:
+                continue
+            out[r.name] = {}
+            for t, m0 in enumerate(dr.bias_spec):
+                N = int(r.data.dims[m0])
+                have = dr.bias_sum is not None and psamples
+                out[r.name][r.entities[m0].name] = {
+                    "mean": (dr.bias_sum[m0].cpu().numpy()[:N] / psamples) if have else np.full(N, np.nan),
+                    "precision": float(dr.bias_lambda_sum[t].item() / psamples) if have else float("nan")}
+        return out
 
     def entity_noise_accumulate(self, ri=0):
         """(relation ri with a noise precision per row, after the burn-in) this iteration's tau into the running sum, on the row
@@ -1694,6 +1778,11 @@ class GibbsEngine:
             out = torch.empty(dims, dtype=torch.float64, device=S[0].device)
         check(lib().bdf_predict_all(self.ctx.handle, len(S), (C.c_int64 * len(S))(*dims), self.D, _facs(S), float(r.model.mean_value),
                                     C.c_void_p(out.data_ptr())))
+        dr = self.rel[self._relation_index(r)]
+        if dr.bias is not None:              # the biases' outer sum, in rising mode order, on the row stream behind their draw
+            with torch.cuda.stream(self.ctx.stream):
+                for m0, b in dr.bias.items():
+                    out += b[:dims[m0]].reshape([-1 if k == m0 else 1 for k in range(len(dims))])
         return out
 
     def _pairs(self, ctx, r, ids, values):
@@ -1737,6 +1826,11 @@ class GibbsEngine:
                 dr.test_baseline = self.ctx.zeros(self._test_pairs.n)
                 check(lib().bdf_pairs_set_baseline(self._test_pairs.handle, _ptr(dr.test_baseline)))
                 self._register_relations()          # (the library refreshes the baseline after every relation beta)
+            if dr.bias is not None:          # pred = udot + mean + the cell's biases: the draw refreshes the base of the registered pairs
+                dr.test_baseline = self.ctx.zeros(max(self._test_pairs.n, 1))
+                self.bias_baseline(0, self._test_pairs, dr.test_baseline)
+                check(lib().bdf_pairs_set_baseline(self._test_pairs.handle, _ptr(dr.test_baseline)))
+                self._register_relations()
         return self._test_pairs
 
     def new_rows(self, fresh=False):

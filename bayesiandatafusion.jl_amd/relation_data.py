@@ -103,6 +103,8 @@ def toStr(x):
         s += " wts"
     if kind == "entity_noise":
         s += f" τ:{x.entities[x.model.entity_noise['mode'] - 1].name[:3]}"
+    if x.model.bias:
+        s += " b:" + ",".join(x.entities[m - 1].name[:3] for m in sorted(x.model.bias))
     if x.model.background is not None:
         s += f" bg:{x.model.background['weight']:g}"
     if x.model.recommend is not None:
@@ -139,6 +141,7 @@ class RelationModel:
         self.recommend = None     # setRecommend: {"k", "rows", "exclude_listed", "batch"}; macau() returns a top-k list per row of the first entity
         self.entity_noise = None  # setEntityNoise: {"mode" (1-based), "shape", "rate"}; a sampled noise precision per row of that entity
         self.dense = False        # setDense: all N M cells of the two-mode relation are kept as a matrix on the device, none is listed to the row kernels
+        self.bias = {}            # setBias: {mode (1-based): {"shape", "rate"}}; a sampled bias per row of every listed entity
         self.new_test = None      # setNewTest: {"mode" (1-based: the entity with new rows), "ids" (n, 2), "values" (NaN: unknown)}; cells of new rows
 
 
@@ -337,6 +340,13 @@ def setCensored(r, censor):
     return None
 
 
+def _no_bias(r, what):
+    """a relation with biases (setBias) is Gaussian with one precision and nothing else folded into its rows' base: the other noise
+    models, the folded relations and the reports that score u.v alone are follow-ups"""
+    if r.model.bias:
+        raise ArgumentError(f"Relation {r.name} has biases (setBias): it does not take {what}.")
+
+
 def _not_dense(r, what):
     """a dense relation (setDense) is Gaussian with one precision for all its cells, and none of them is listed to a kernel"""
     if r.model.dense:
@@ -346,6 +356,7 @@ def _not_dense(r, what):
 def _no_weights(r, what):
     """the noise models with a latent value per observation take neither the Student-t model nor observation weights"""
     _not_dense(r, what)
+    _no_bias(r, what)
     if r.model.robust is not None:
         raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
     if r.model.weights is not None:
@@ -358,6 +369,7 @@ def _no_weights(r, what):
 
 def _weight_guards(r, what, pg_ok=False, noise_ok=False):
     _not_dense(r, what)
+    _no_bias(r, what)
     if hasFeatures(r):
         raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
     if r.model.probit:
@@ -583,6 +595,69 @@ def check_entity_noise(r):
     r.model.entity_noise = _entity_noise_spec(r, m.get("mode"), m.get("shape"), m.get("rate"))
 
 
+def setBias(r, entity, shape=1.0, rate=1.0):
+    """A bias per row of one entity of a Gaussian relation (the reference has one mean_value per relation; its successor SMURFF and
+    every practical recommender have these): y_ij = mean + a_i + b_j + u_i.v_j + noise -- a harsh rater, a popular film or an assay
+    with an offset shifts every cell of its row by the same amount, and the factors need not spend components on it.  Call it once
+    per entity that gets biases: entity is an Entity of the relation, its name, or its 1-based mode.  b_j ~ N(0, 1 / lambda) with
+    lambda ~ Gamma(shape, rate) (rate parametrisation), one lambda per biased entity; macau() samples the biases and lambda beside
+    the rows and returns result["bias"][relation name][entity name] = {"mean": the posterior mean bias per
+    row, "precision": the posterior mean lambda}.  mean_value stays the mean of the training values, which is why the prior mean
+    is zero.  Predictions, the test set, lpd, setWaic, rmse_train and full_prediction include the biases; alpha is fixed, set by
+    setPrecision, or sampled.  Plain Gaussian noise only: no other noise model, observation weights, relation features,
+    setBackground, setDense, setRecommend or setNewTest on the relation, no spike-and-slab or non-negative entity in it; one rank."""
+    _bias_guards(r)
+    mode, spec = _bias_spec(r, entity, shape, rate)
+    if mode in r.model.bias:
+        raise ArgumentError(f"Relation {r.name} already has biases for its entity {r.entities[mode - 1].name} (setBias): once per entity.")
+    r.model.bias = dict(r.model.bias)
+    r.model.bias[mode] = spec
+    r._dev = None
+    return None
+
+
+def _bias_spec(r, entity, shape, rate):
+    m = _entity_noise_spec(r, entity, shape, rate)        # (the same resolution of `entity` and the same numbers)
+    return m["mode"], {"shape": m["shape"], "rate": m["rate"]}
+
+
+def _bias_guards(r):
+    what = "biases (setBias)"
+    kind = noise_kind(r)
+    names = {"probit": "the probit noise model (setProbit)", "censored": "censoring flags (setCensored)",
+             "interval": "interval bounds (setInterval / setBinned)", "ordinal": "the ordinal noise model (setOrdinal)",
+             "robust": "the robust noise model (setRobust)", "weights": "observation weights (setWeights)",
+             "entity_noise": "a noise precision per row (setEntityNoise)", "logit": "the logit noise model (setLogit)",
+             "counts": "the count noise model (setCounts)"}
+    if kind != "gauss":
+        raise ArgumentError(f"Relation {r.name} has {names[kind]}: it does not take {what}, which are sampled under plain Gaussian noise.")
+    if hasFeatures(r):
+        raise ArgumentError(f"Relation {r.name} has features: {what} do not take relation-level side information (both write the rows' base).")
+    if r.model.background is not None:
+        raise ArgumentError(f"Relation {r.name} has a background (setBackground): it does not take {what}, the unlisted cells would need them too.")
+    if r.model.dense:
+        raise ArgumentError(f"Relation {r.name} is dense (setDense): it does not take {what}, no cell is listed to the rows.")
+    if r.model.recommend is not None:
+        raise ArgumentError(f"Relation {r.name} asks for top-k lists (setRecommend): it does not take {what}, the score is u.v + mean alone.")
+    if r.model.new_test is not None:
+        raise ArgumentError(f"Relation {r.name} has cells of new rows (setNewTest): it does not take {what}, a new row has no bias.")
+    for en in r.entities:
+        if en.spike is not None:
+            raise ArgumentError(f"Entity {en.name} has the spike-and-slab prior (setSpikeAndSlab): its relation {r.name} does not take {what}.")
+        if en.nonneg is not None:
+            raise ArgumentError(f"Entity {en.name} has the non-negative prior (setNonNegative): its relation {r.name} does not take {what}.")
+
+
+def check_bias(r):
+    """what a relation with biases must still satisfy when a sampler is built on it (it may have been changed since setBias)"""
+    _bias_guards(r)
+    out = {}
+    for mode, spec in r.model.bias.items():
+        m, sp = _bias_spec(r, mode, spec.get("shape"), spec.get("rate"))
+        out[m] = sp
+    r.model.bias = out
+
+
 def setSpikeAndSlab(entity, incl_a=1.0, incl_b=1.0, shape=1.0, rate=1.0):
     """A spike-and-slab prior for the rows of `entity` in place of the Normal-Wishart one (the reference has none; its successor SMURFF
     does): loading d of row i is u_id = s_id w_id with s_id ~ Bernoulli(pi_d), w_id ~ N(0, 1 / tau_d), pi_d ~ Beta(incl_a, incl_b) and
@@ -619,6 +694,7 @@ def _spike_guards(entity):
         raise ArgumentError(f"Entity {entity.name} has the non-negative prior (setNonNegative): it does not take the spike-and-slab prior "
                             "(setSpikeAndSlab) as well.")
     for r in entity.relations:
+        _no_bias(r, f"the spike-and-slab prior (setSpikeAndSlab) of its entity {entity.name}")
         if r.model.background is not None:
             raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
                                 "spike-and-slab prior (setSpikeAndSlab), the background folds a dense Gram matrix into the prior precision.")
@@ -675,6 +751,7 @@ def _nonneg_guards(entity):
         raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): it does not take the non-negative prior "
                             "(setNonNegative) as well.")
     for r in entity.relations:
+        _no_bias(r, f"the non-negative prior (setNonNegative) of its entity {entity.name}")
         if r.model.background is not None:
             raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
                                 "non-negative prior (setNonNegative), the background folds a dense Gram matrix into the prior precision.")
@@ -798,6 +875,7 @@ def denseRelation(Y, name, entities, class_cut=0.0, alpha=1.0):
 
 def _dense_guards(r):
     what = _DENSE
+    _no_bias(r, what)
     if len(r.data.dims) != 2:
         raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} takes a two-mode relation.")
     if hasFeatures(r):
@@ -905,6 +983,7 @@ def _recommend_spec(r, k, rows, exclude_listed, batch):
 def _recommend_guards(r):
     what = "top-k lists (setRecommend)"
     _not_dense(r, what)
+    _no_bias(r, what)
     if len(r.data.dims) != 2:
         raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
     if hasFeatures(r):
@@ -987,6 +1066,7 @@ def setNewTest(r, entity, table):
 def _new_test_guards(r, entity):
     what = "cells of new rows (setNewTest)"
     _not_dense(r, what)
+    _no_bias(r, what)
     if len(r.entities) != 2 or len(r.data.dims) != 2:
         raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
     if hasFeatures(r):
@@ -1318,6 +1398,7 @@ _MODEL_CHECKS = (
     (lambda m: m.entity_noise is not None, check_entity_noise, lambda m: "a noise precision per row"),
     (lambda m: m.background is not None, check_background, lambda m: "a background"),
     (lambda m: m.recommend is not None, check_recommend, lambda m: "top-k lists (setRecommend)"),
+    (lambda m: bool(m.bias), check_bias, lambda m: "biases (setBias)"),
 )
 
 

@@ -69,6 +69,9 @@ extern "C" {
 #define BDF_P_NONNEG 25        /* bdf_sample_rows_nonneg: the uniform of component d of a row (entity = entity_tag, row = original row, pair d, words x and y) */
 #define BDF_P_NONNEG_N 26      /* bdf_nonneg_hyper: the gamma variate's normals (entity = entity_tag, row = component d, attempt t: normal 2 t) */
 #define BDF_P_NONNEG_U 27      /* bdf_nonneg_hyper: ... and its uniforms (the same entity and row, pair = attempt) */
+#define BDF_P_BIAS 28          /* bdf_bias_draw: the normal of a row's bias (entity 0x800000 | rel_tag, row = 0-based row of the biased entity, normal = 0-based mode) */
+#define BDF_P_BIAS_N 29        /* bdf_bias_draw: the gamma variate's normals of a mode's bias precision (entity 0x800000 | rel_tag, row = 0-based mode, attempt t: normal 2 t) */
+#define BDF_P_BIAS_U 30        /* bdf_bias_draw: ... and its uniforms (the same entity and row, pair = attempt; shape < 1: the boost's uniform is pair 0xffff) */
 
 typedef struct bdf_ctx   bdf_ctx;    /* device, stream, seed, sweep counter, scratch        */
 typedef struct bdf_rel   bdf_rel;    /* Relation.data :: IndexedDF / FastIDF on the device  */
@@ -524,6 +527,40 @@ int bdf_pg_draw(bdf_ctx *ctx, const bdf_pairs *train, int D, const double *const
 int bdf_entity_noise_draw(bdf_ctx *ctx, const bdf_rel *rel, int mode, const bdf_pairs *train, int D, const double *const *factors,
                           double mean_value, double alpha, const double *alpha_dev, double shape, double rate, uint32_t rel_tag,
                           double *tau_out, double *precision_out, double *wsse_out);
+
+/* Row and column biases of a relation's entities (csrc/k_bias.hip, csrc/bias.h): with B the biased modes,
+ *   value_k ~ N(mean_value + sum over m in B of b^m_(id_m(k)) + udot_k, 1 / alpha),  b^m_j ~ N(0, 1 / lambda_m),  lambda_m ~ Gamma(shape_m, rate_m).
+ * A term names one biased mode (0-based), its prior and where its state lives: bias (dev, dims[mode] doubles) and lambda (dev, 1
+ * double; the caller starts it, at shape / rate say).  Terms may be listed in any order; they are taken in rising mode order. */
+typedef struct {
+    int32_t mode;
+    int32_t _pad;
+    double shape, rate;
+    double *bias;
+    double *lambda;
+} bdf_bias_term;
+/* One Gibbs step on the biases of `rel`, whose cells `train` holds as pairs (observation k of the caller's order being COO row k
+ * of the relation; the pairs may be stored sorted; their baseline is not read); BDF_ERR_ARG when the counts or the numbers of
+ * modes differ, for a relation created with a layout, for a mode out of range or listed twice and for a shape or rate that is
+ * not positive and finite.  At the context's sweep:
+ *   1. e_k = value_k - (udot_k + mean_value) into resid_scratch (dev, n doubles), the same bits as value_k - bdf_predict's output;
+ *   2. per biased mode m in rising order and row j with n_j cells: S_j = the sum over its cells of e_k minus the other biased
+ *      modes' current biases (subtracted in rising mode order; a mode drawn earlier in this call with its new value), added in the
+ *      fixed order csrc/bias.h writes down; prec_j = lambda_m + alpha n_j and b^m_j = alpha S_j / prec_j + z_j / sqrt(prec_j), z_j
+ *      normal m of stream (BDF_P_BIAS, 0x800000 | rel_tag, row j); a row without cells draws from its prior;
+ *   3. lambda_m = G / (rate_m + sum_j (b^m_j)^2 / 2), G ~ Gamma(shape_m + dims[m] / 2, 1) by Marsaglia-Tsang on the streams
+ *      (BDF_P_BIAS_N, 0x800000 | rel_tag, row m) and (BDF_P_BIAS_U, the same), the sum in a fixed order; drawn on the device.  The
+ *      rows of step 2 read the lambda_m the call found;
+ *   4. linear_out[k] = mean_value + the biases of cell k added in rising mode order (dev, n doubles, the caller's order): what
+ *      bdf_term.linear_values and bdf_pairs_set_baseline take.
+ * alpha_dev (dev, nullable) wins over alpha, which must otherwise be positive and finite.  factors as for bdf_predict.  Bit-identical
+ * reruns.  2 + 2 n_bias launches on ctx's stream; not reentrant on one context (the partial sums live in the context's scratch). */
+int bdf_bias_draw(bdf_ctx *ctx, const bdf_rel *rel, const bdf_pairs *train, int D, const double *const *factors, double mean_value,
+                  double alpha, const double *alpha_dev, uint32_t rel_tag, int n_bias, const bdf_bias_term *terms, double *resid_scratch,
+                  double *linear_out);
+/* out_dev[k] = mean_value + the biases of pair k added in rising mode order, for any pairs over the same entities (dev, n doubles,
+ * the caller's order): the baseline of test pairs or of probe cells.  Of a term only mode and bias are read. */
+int bdf_bias_baseline(bdf_ctx *ctx, const bdf_pairs *pairs, int n_bias, const bdf_bias_term *terms, double mean_value, double *out_dev);
 
 /* Ordinal probit noise model (csrc/k_ordinal.hip, csrc/ordinal.h): the training values of a relation are
  * levels 1 .. K (4 <= K <= 16), y = k iff e_{k-1} <= z < e_k for the latent z ~ N(udot + mean_value, 1 / alpha) of the interval
@@ -983,7 +1020,8 @@ int bdf_gibbs_set_test(bdf_gibbs *g, bdf_pairs *pairs, const int32_t *entity_of_
  * (bdf_probit_draw) at the same place, from the previous iteration's rows; the iteration is then z | U,V -> U | z,V -> V | z,U.
  * `censor`: the latent draw of the censored model (bdf_censored_draw, with alpha_dev) after sample_alpha; the iteration is then
  * alpha | U,V,z -> z | U,V,alpha -> U | z,V -> V | z,U.  `interval`: the latent draw of the interval-censored model
- * (bdf_interval_draw, with alpha_dev) at the same place and in the same order.  Relations with none of these need no entry. */
+ * (bdf_interval_draw, with alpha_dev) at the same place and in the same order.  test_baseline without feat_test: the biases' tail
+ * below.  Relations with none of these need no entry. */
 typedef struct {
     const bdf_rel *rel;
     int32_t entity_of_mode[BDF_MAX_MODES];   /* which entity (index into bdf_gibbs_create's array) every mode of rel is          */
@@ -1072,6 +1110,19 @@ typedef struct {
     double dense_sum_r2;
     const bdf_pairs *dense_holes;
     double *dense_stats;
+    /* row and column biases (a zeroed tail is "none"): n_bias terms, one per biased mode of `rel`.
+     * bdf_bias_draw (with alpha_dev: the previous iteration's alpha) runs BEFORE sample_alpha and rewrites the terms' bias and
+     * lambda and `linear`, which the rows of every entity read as linear_values and which the caller has made the baseline of
+     * `train` (bdf_pairs_set_baseline), so that sample_alpha's sum of squares sees the new biases.  bias_resid: dev, one double per
+     * observation (scratch).  bias_test / test_baseline (both or neither): pairs over the relation's entities whose baseline
+     * test_baseline (one double per pair) is refreshed after the draw, behind the prediction updates that read it.  Needs train,
+     * linear and bias_resid; Gaussian noise with one precision only: not with probit, censor, interval, ordinal, obs_precision,
+     * pg_model, noise_mode, a background, a dense relation, feat or a communicator */
+    int32_t n_bias;
+    int32_t _pad_bias;
+    bdf_bias_term bias[BDF_MAX_MODES];
+    double *bias_resid;
+    const bdf_pairs *bias_test;
 } bdf_gibbs_relation;
 int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_gibbs_relation *rels);
 /* several ranks: exchange every entity's rows after sampling them (NULL: none) */

@@ -641,6 +641,37 @@ function entity_noise_draw!(c::Context, rel::DevRelation, mode, train::DevPairs,
                 c.h, rel.h, mode, train.h, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, shape, rate, rel_tag,
                 tau_out.p, precision_out.p, wsse_out === nothing ? C_NULL : wsse_out.p))
 end
+struct BiasTerm                                   # bdf_bias_term, field for field
+    mode::Int32                                   # the biased mode, 0-based
+    _pad::Int32
+    shape::Float64                                # lambda ~ Gamma(shape, rate) a priori
+    rate::Float64
+    bias::Ptr{Cvoid}                              # device Float64 per row of that mode: the last draw
+    lambda::Ptr{Cvoid}                            # device Float64: the mode's precision, the last draw (the caller starts it)
+end
+BiasTerm(mode::Integer, shape, rate, bias::DevArray{Float64}, lambda::DevArray{Float64}) =
+    BiasTerm(Int32(mode), Int32(0), Float64(shape), Float64(rate), bias.p, lambda.p)
+"row and column biases of a Gaussian relation: one Gibbs step on the biases b^m_j of every listed mode m of `rel` (rising) and on
+their precisions lambda_m: e = value - (udot + mean_value) into resid_scratch (one Float64 per cell), per mode and row the sum of e
+less the other biased modes' current biases in a fixed order, b^m_j = alpha S_j / prec_j + z_j / sqrt(prec_j) with prec_j =
+lambda_m + alpha n_j and z_j normal m of stream (28, 0x800000 | rel_tag, row j), then lambda_m = G / (rate + sum b^2 / 2), G ~
+Gamma(shape + N_m / 2, 1) from the streams (29 / 30, 0x800000 | rel_tag, row m); linear_out (one Float64 per cell, the caller's
+order) = mean_value + the cell's biases: what the rows take as Term.linear_values and the training pairs as their baseline;
+`train` holds the relation's own cells in its order; `alpha_dev` (a device scalar or `nothing`) wins over `alpha`"
+function bias_draw!(c::Context, rel::DevRelation, train::DevPairs, D, factors::Vector{<:DevArray}, mean_value, alpha, alpha_dev, rel_tag,
+                    terms::Vector{BiasTerm}, resid_scratch::DevArray{Float64}, linear_out::DevArray{Float64})
+    fp = Ptr{Cvoid}[f.p for f in factors]
+    check(ccall((:bdf_bias_draw, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}, UInt32, Cint, Ptr{BiasTerm},
+                 Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, rel.h, train.h, D, fp, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, rel_tag, length(terms), terms,
+                resid_scratch.p, linear_out.p))
+end
+"out (one device Float64 per pair, the caller's order) = mean_value + the biases of every pair, added in rising mode order: the
+baseline of test pairs or probe cells over the same entities (of a term only mode and bias are read)"
+bias_baseline!(c::Context, pairs::DevPairs, terms::Vector{BiasTerm}, mean_value, out::DevArray{Float64}) =
+    check(ccall((:bdf_bias_baseline, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{BiasTerm}, Float64, Ptr{Cvoid}),
+                c.h, pairs.h, length(terms), terms, mean_value, out.p))
 "pairs_lpd_update! scores pair k with alpha tau[its id in mode `mode` (0-based)]: tau, one device Float64 per row of that mode, is
 borrowed and read at every update (keep it alive); `nothing` clears it"
 pairs_set_precision_scale!(p::DevPairs, tau, mode::Integer=0) =
@@ -968,6 +999,11 @@ struct GibbsRelation                              # bdf_gibbs_relation, field fo
     dense_sum_r2::Float64                         # the listed cells' sum of r^2
     dense_holes::Ptr{Cvoid}                       # bdf_pairs of the cells that are not listed (C_NULL: none): dense_impute! draws them before every iteration
     dense_stats::Ptr{Cvoid}                       # device, 4 Float64 (C_NULL without holes): [1] the holes' sum of r^2
+    n_bias::Int32                                 # row and column biases: the number of biased modes (0: none); bias_draw! rewrites the terms' bias and lambda, and linear
+    _pad_bias::Int32
+    bias::NTuple{4,BiasTerm}                      # ... the first n_bias are read
+    bias_resid::Ptr{Cvoid}                        # ... device Float64 per observation of train (scratch)
+    bias_test::Ptr{Cvoid}                         # ... bdf_pairs whose baseline test_baseline is refreshed after the draw (C_NULL: none)
 end
 "register the relations whose alpha is sampled and / or that carry features: sweep! then runs sample_alpha, sample_beta_rel and
 linear_values before the rows of every iteration; `keep`: what the records point into"
