@@ -159,9 +159,11 @@ class State:
 
 
 def leapfrog(st, Udata, Vdata, alpha, L, L_inner, eps, vectorised):
-    """the trajectory of one iteration (:77-85); returns the momentum norms after each step and at the end"""
+    """the trajectory of one iteration (:77-85); returns the momentum norms after each step and at the end (the reference prints
+    these); st.norm0 keeps |r_U| after the opening update, which it does not print"""
     norms = []
     hmc_update_u(st.rU, st.U, st.V, Udata, st.Lam[0], st.mu[0], alpha, L_inner, eps / 2, vectorised)
+    st.norm0 = np.linalg.norm(st.rU)
     for l in range(1, L + 1):
         hmc_update_u(st.rV, st.V, st.U, Vdata, st.Lam[1], st.mu[1], alpha, L_inner, eps, vectorised)
         if l < L:
@@ -173,10 +175,11 @@ def leapfrog(st, Udata, Vdata, alpha, L, L_inner, eps, vectorised):
 
 
 def run(uid, vid, values, test_uid, test_vid, test_val, Nu, Nv, D, alpha, seed, burnin=100, psamples=100, L=10, L_inner=1,
-        prior_freq=8, eps=0.01, clamp=(), vectorised=False, G=None, niter=None):
-    """macau_hmc's loop (:33-137).  niter (optional) stops early.  Returns a dict: the final State "state", "eps", "L",
-    "rmse", "rmse_avg" and per-iteration "records" (dicts of eps, L, kin_s, kin_f, pot_s, pot_f, dH, accepted, eps_new,
-    L_new, |U|, |V|, rmse, rmse_avg, norms)."""
+        prior_freq=8, eps=0.01, clamp=(), vectorised=False, G=None, niter=None, phases=None):
+    """macau_hmc's loop (:33-137).  niter (optional) stops early; phases (optional) maps an iteration number to the (eps, L) it
+    starts with, as bdf_hmc_set_params sets them between two iterations.  Returns a dict: the final State "state", "eps", "L",
+    "rmse", "rmse_avg" and per-iteration "records" (dicts of eps, L, kin_s, kin_f, pot_s, pot_f, dH, uniform, accepted, eps_new,
+    L_new, |U|, |V|, rmse, rmse_avg, norms, norm0)."""
     uid, vid = np.asarray(uid, dtype=np.int64), np.asarray(vid, dtype=np.int64)
     test_uid, test_vid = np.asarray(test_uid, dtype=np.int64), np.asarray(test_vid, dtype=np.int64)
     test_val = np.asarray(test_val, dtype=np.float64)
@@ -193,6 +196,8 @@ def run(uid, vid, values, test_uid, test_vid, test_val, Nu, Nv, D, alpha, seed, 
     records = []
     total = burnin + psamples if niter is None else niter
     for i in range(1, total + 1):
+        if phases and i in phases:
+            eps, L = phases[i]
         rec = {"eps": eps, "L": L}
         st.rU = sample_momentum(st.GU, seed, i, 0)
         st.rV = sample_momentum(st.GV, seed, i, 1)
@@ -200,11 +205,13 @@ def run(uid, vid, values, test_uid, test_vid, test_val, Nu, Nv, D, alpha, seed, 
         potential_start = pot(uid, vid, val, alpha, st.U, st.V, st.mu, st.Lam)
         Ustart, Vstart = st.U.copy(), st.V.copy()
         rec["norms"] = leapfrog(st, Udata, Vdata, alpha, L, L_inner, eps, vectorised)
+        rec["norm0"] = st.norm0
         kinetic_final = kin(st.rU, st.GU) + kin(st.rV, st.GV)
         potential_final = pot(uid, vid, val, alpha, st.U, st.V, st.mu, st.Lam)
         dH = potential_start - potential_final + kinetic_start - kinetic_final
         rec.update(kin_s=kinetic_start, kin_f=kinetic_final, pot_s=potential_start, pot_f=potential_final, dH=dH)
-        accepted = (dH >= 0 or uniform(seed, i) < math.exp(dH)) if not math.isnan(dH) else False   # rand() < 1 <= exp(dH)
+        rec["uniform"] = uniform(seed, i)
+        accepted = (dH >= 0 or rec["uniform"] < math.exp(dH)) if not math.isnan(dH) else False     # rand() < 1 <= exp(dH)
         if not accepted:
             st.U[:], st.V[:] = Ustart, Vstart
             if dH < -6:
