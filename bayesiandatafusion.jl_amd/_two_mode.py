@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import ArgumentError, check
+from .model_options import ENTITY, RELATION, present
 
 
 def relation_of(data, num_latent, who):
@@ -19,33 +20,10 @@ def relation_of(data, num_latent, who):
     rel = data.relations[0]
     if rel.data.ids.shape[1] != 2 or len(data.entities) < 2:
         raise ArgumentError(f"{who} works on a matrix relation (2 modes); {rel.name} has {rel.data.ids.shape[1]}")
-    if rel.model.probit:
-        raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the probit noise model (use macau)")
-    if rel.model.censor is not None:
-        raise ArgumentError(f"{who} takes every value as a measurement; {rel.name} has censoring flags (use macau)")
-    if rel.model.interval is not None:
-        raise ArgumentError(f"{who} takes every value as a measurement; {rel.name} has interval bounds (use macau)")
-    if rel.model.robust is not None:
-        raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the robust noise model (use macau)")
-    if rel.model.weights is not None:
-        raise ArgumentError(f"{who} weighs every value alike; {rel.name} has observation weights (use macau)")
-    if rel.model.pg is not None:
-        raise ArgumentError(f"{who} has Gaussian noise only; {rel.name} has the {rel.model.pg['model']} noise model (use macau)")
-    if rel.model.entity_noise is not None:
-        raise ArgumentError(f"{who} has one noise precision for every cell; {rel.name} has a noise precision per row (use macau)")
-    if rel.model.bias:
-        raise ArgumentError(f"{who} models a cell as mean + u.v; {rel.name} has biases (setBias; use macau)")
-    if rel.model.background is not None:
-        raise ArgumentError(f"{who} fits the listed cells only; {rel.name} has a background (use macau)")
-    if rel.model.dense:
-        raise ArgumentError(f"{who} reads the listed cells; {rel.name} is dense (setDense; use macau)")
-    if rel.model.recommend is not None:
-        raise ArgumentError(f"{who} keeps no sum of scores over draws; {rel.name} asks for top-k lists (setRecommend; use macau)")
-    for en in data.entities:
-        if en.spike is not None:
-            raise ArgumentError(f"{who} has the Normal-Wishart prior only; {en.name} has the spike-and-slab prior (setSpikeAndSlab; use macau)")
-        if en.nonneg is not None:
-            raise ArgumentError(f"{who} has the Normal-Wishart prior only; {en.name} has the non-negative prior (setNonNegative; use macau)")
+    for owner in [rel] + list(data.entities):
+        for opt in present(owner, RELATION if owner is rel else ENTITY):
+            if opt.trainer is not None:
+                raise ArgumentError(f"{who} {opt.trainer}; {owner.name} {opt.has or 'has ' + opt.phrase} (use macau)")
     return D, rel
 
 

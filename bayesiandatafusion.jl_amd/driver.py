@@ -14,7 +14,8 @@ import numpy as np
 from . import features as feat
 from ._lib import ArgumentError
 from .engine import GibbsEngine
-from .relation_data import _ordinal_bounds, _waic_bounds, check_new_rows, check_test_interval, hasFeatures, noise_kind, numTest, toStr
+from .model_options import refuse
+from .relation_data import _ordinal_bounds, _waic_bounds, check_new_rows, check_test_interval, hasFeatures, numTest, toStr
 
 
 def AUC_ROC(Ytrue, scores):
@@ -58,26 +59,13 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     if output_type not in ("csv", "binary"):
         raise ArgumentError("output_type must be either \"csv\" or \"binary\".")
     clamp = [float(c) for c in clamp]
-    # what the first relation's noise model rules out
-    kind = noise_kind(data.relations[0]) if data.relations else "gauss"
-    if full_prediction and kind == "probit":
-        raise ArgumentError("Prediction of all elements is not possible when Relation has the probit noise model.")
-    if full_prediction and kind in ("logit", "counts"):
-        raise ArgumentError(f"Prediction of all elements is not possible when Relation has the {kind} noise model.")
-    if rmse_train and kind == "censored":
-        raise ArgumentError("rmse_train is not possible when Relation has censoring flags: its training values are bounds, not measurements.")
-    if rmse_train and kind in ("interval", "ordinal"):
-        raise ArgumentError("rmse_train is not possible when Relation has interval bounds: its training values stand for intervals, not measurements.")
-    # the robust noise model and observation weights (setRobust / setWeights)
+    # what the first relation's options rule out for this run (model_options.py); the robust noise model and a noise precision per
+    # row of one entity (setRobust, setEntityNoise; DESIGN.md sections 18, 22) are sampled on any relation, reported for the first
+    for key, asked in (("full_prediction", full_prediction), ("rmse_train", rmse_train), ("lpd", lpd)):
+        if asked and data.relations:
+            refuse(data.relations[0], key)
     robust = data.relations[0].model.robust if data.relations else None
-    if lpd and kind in ("robust", "weights"):
-        what = "the robust noise model (setRobust)" if kind == "robust" else "observation weights (setWeights)"
-        raise ArgumentError(f"lpd = true is not possible when Relation has {what}: a held-out cell's density under it is not scored yet.")
-    # a noise precision per row of one entity (setEntityNoise): sampled on any relation, reported for the first
     noise = data.relations[0].model.entity_noise if data.relations else None
-    if lpd and kind in ("logit", "counts"):
-        raise ArgumentError(f"lpd = true is not possible when Relation has the {kind} noise model "
-                            "(setLogit / setCounts): a held-out cell's density under it is not scored yet.")
     # cells of rows that were not in training (setNewRows / setNewTest on the first relation)
     new_rel = check_new_rows(data)
     if lpd and not (data.relations and numTest(data.relations[0]) > 0) and new_rel is None:

@@ -12,6 +12,7 @@ import numpy as np
 from . import features as feat
 from ._lib import ArgumentError
 from .indexed_df import IndexedDF, _split_table
+from .model_options import OPTION, RELATION, noise_kind, present, refuse, refuse_ranks  # noqa: F401  (noise_kind is imported from here)
 
 
 class EntityModel:
@@ -85,33 +86,33 @@ def toStr(x):
         if x.nonneg is not None:
             s += " nn"
         return f"{x.name[:3]}[{s}]"
-    kind = noise_kind(x)
-    if kind in ("logit", "counts"):
-        return f"{x.name[:4]}[{'logit' if kind == 'logit' else 'nb:%s' % x.model.pg['r']}]"
-    s = "probit" if kind == "probit" else f"α={x.model.alpha:2.1f}"
-    if hasFeatures(x) and x.model.beta is not None and len(x.model.beta):
-        s += f" β:{np.linalg.norm(x.model.beta):2.1f}"
-    if kind == "censored":
-        s += f" cens:{int(np.count_nonzero(x.model.censor))}"
-    if kind in ("interval", "ordinal"):
-        s += f" intv:{int(np.count_nonzero(x.model.interval[:, 0] < x.model.interval[:, 1]))}"
-    if kind == "ordinal":
-        s += f" ord:{x.model.ordinal['K']}"
-    if kind == "robust":
-        s += f" t:{x.model.robust['nu']:g}"
-    if kind == "weights":
-        s += " wts"
-    if kind == "entity_noise":
-        s += f" τ:{x.entities[x.model.entity_noise['mode'] - 1].name[:3]}"
-    if x.model.bias:
-        s += " b:" + ",".join(x.entities[m - 1].name[:3] for m in sorted(x.model.bias))
-    if x.model.background is not None:
-        s += f" bg:{x.model.background['weight']:g}"
-    if x.model.recommend is not None:
-        s += f" rec:{x.model.recommend['k']}"
-    if x.model.dense:
-        s += " dense"
+    m = x.model
+    if m.pg is not None:
+        return f"{x.name[:4]}[{'logit' if m.pg['model'] == 'logit' else 'nb:%s' % m.pg['r']}]"
+    s = "probit" if m.probit else f"α={m.alpha:2.1f}"
+    if hasFeatures(x) and m.beta is not None and len(m.beta):
+        s += f" β:{np.linalg.norm(m.beta):2.1f}"
+    s += "".join(show(x) for key, show in _SHOWN.items() if OPTION[key].present(x))
     return f"{x.name[:4]}[{s}]"
+
+
+def _open_rows(x):
+    return f" intv:{int(np.count_nonzero(x.model.interval[:, 0] < x.model.interval[:, 1]))}"
+
+
+# what toStr adds for an option that is present, in the order it is shown
+_SHOWN = {
+    "censored": lambda x: f" cens:{int(np.count_nonzero(x.model.censor))}",
+    "interval": _open_rows,
+    "ordinal": lambda x: _open_rows(x) + f" ord:{x.model.ordinal['K']}",
+    "robust": lambda x: f" t:{x.model.robust['nu']:g}",
+    "weights": lambda x: " wts",
+    "entity_noise": lambda x: f" τ:{x.entities[x.model.entity_noise['mode'] - 1].name[:3]}",
+    "bias": lambda x: " b:" + ",".join(x.entities[k - 1].name[:3] for k in sorted(x.model.bias)),
+    "background": lambda x: f" bg:{x.model.background['weight']:g}",
+    "recommend": lambda x: f" rec:{x.model.recommend['k']}",
+    "dense": lambda x: " dense",
+}
 
 
 class RelationModel:
@@ -143,30 +144,6 @@ class RelationModel:
         self.dense = False        # setDense: all N M cells of the two-mode relation are kept as a matrix on the device, none is listed to the row kernels
         self.bias = {}            # setBias: {mode (1-based): {"shape", "rate"}}; a sampled bias per row of every listed entity
         self.new_test = None      # setNewTest: {"mode" (1-based: the entity with new rows), "ids" (n, 2), "values" (NaN: unknown)}; cells of new rows
-
-
-def noise_kind(r):
-    """which noise model relation r has, from the fields its setter left: "gauss", "probit", "censored", "interval", "ordinal" (it
-    has the interval model's bounds too), "weights", "robust", "entity_noise", "logit" or "counts".  The setters admit one of them
-    per relation."""
-    m = r.model
-    if m.probit:
-        return "probit"
-    if m.censor is not None:
-        return "censored"
-    if m.ordinal is not None:
-        return "ordinal"
-    if m.interval is not None:
-        return "interval"
-    if m.robust is not None:
-        return "robust"
-    if m.weights is not None:
-        return "weights"
-    if m.entity_noise is not None:
-        return "entity_noise"
-    if m.pg is not None:
-        return m.pg["model"]
-    return "gauss"
 
 
 class RelationTemp:
@@ -275,11 +252,13 @@ def numTest(r):
 
 
 def setPrecision(r, precision):
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model: its latent has unit variance, there is no precision to set.")
-    if r.model.pg is not None:
-        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: every cell's precision is its sampled omega, there is no precision to set.")
+    refuse(r, "precision")
     r.model.alpha = float(precision)
+
+
+def _number(x):
+    """whether x is a finite real number (no bool, no string)"""
+    return not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating)) and bool(np.isfinite(x))
 
 
 def _is_binary(values):
@@ -291,17 +270,7 @@ def setProbit(r):
     """Probit noise model for a relation of 0/1 values (the reference has Gaussian noise only): y = 1[z > 0] with a latent
     z ~ N(u'v, 1) that macau() samples beside the rows.  Predictions become probabilities Phi(u'v), class_cut 0.5.  Works before
     or after assignToTest / setTest; every training and test value must be exactly 0 or 1."""
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: the probit noise model does not take relation-level side information.")
-    if r.model.alpha_sample:
-        raise ArgumentError(f"Relation {r.name} samples its precision (alpha_sample): the probit latent has unit variance.")
-    if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
-        raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the probit noise model.")
-    if r.model.censor is not None:
-        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): the probit noise model does not take them.")
-    if r.model.interval is not None:
-        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval): the probit noise model (setProbit) does not take them.")
-    _no_weights(r, "the probit noise model (setProbit)")
+    check_probit(r, build=False)
     r.model.probit = True
     r.model.alpha = 1.0
     r.model.alpha_sample = False
@@ -312,12 +281,9 @@ def setProbit(r):
     return None
 
 
-def check_probit(r):
+def check_probit(r, build=True):
     """what a probit relation must still satisfy when a sampler is built on it (it may have been changed since setProbit)"""
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: the probit noise model does not take relation-level side information.")
-    if r.model.alpha_sample:
-        raise ArgumentError(f"Relation {r.name} samples its precision (alpha_sample): the probit latent has unit variance.")
+    refuse(r, "probit", build)
     if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
         raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the probit noise model.")
 
@@ -328,90 +294,14 @@ def setCensored(r, censor):
     (right-censored), -1 "at most this" (left-censored).  macau() then samples a latent value for every flagged row beside the
     rows: z ~ N(u'v + mean, 1 / alpha) truncated to the bound's side.  Predictions, the test set and alpha (fixed, setPrecision or
     alpha_sample) stay what they are.  Call it AFTER the test split (assignToTest removes training rows; setTest does not)."""
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: the censored noise model does not take relation-level side information.")
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model: it does not take censoring flags.")
-    if r.model.interval is not None:
-        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval): it does not take censoring flags (setCensored) as well.")
-    _no_weights(r, "censoring flags (setCensored)")
+    refuse(r, "censored")
     r.model.censor = _censor_flags(r, censor)
     r._dev = None
     return None
 
 
-def _no_bias(r, what):
-    """a relation with biases (setBias) is Gaussian with one precision and nothing else folded into its rows' base: the other noise
-    models, the folded relations and the reports that score u.v alone are follow-ups"""
-    if r.model.bias:
-        raise ArgumentError(f"Relation {r.name} has biases (setBias): it does not take {what}.")
-
-
-def _not_dense(r, what):
-    """a dense relation (setDense) is Gaussian with one precision for all its cells, and none of them is listed to a kernel"""
-    if r.model.dense:
-        raise ArgumentError(f"Relation {r.name} is dense (setDense): it does not take {what}.")
-
-
-def _no_weights(r, what):
-    """the noise models with a latent value per observation take neither the Student-t model nor observation weights"""
-    _not_dense(r, what)
-    _no_bias(r, what)
-    if r.model.robust is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
-    if r.model.weights is not None:
-        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
-    if r.model.pg is not None:
-        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
-    if r.model.entity_noise is not None:
-        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): it does not take {what}.")
-
-
-def _weight_guards(r, what, pg_ok=False, noise_ok=False):
-    _not_dense(r, what)
-    _no_bias(r, what)
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take {what}.")
-    if r.model.censor is not None:
-        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take {what}.")
-    if r.model.ordinal is not None:
-        raise ArgumentError(f"Relation {r.name} has the ordinal noise model (setOrdinal): it does not take {what}.")
-    if r.model.interval is not None:
-        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): it does not take {what}.")
-    if r.model.pg is not None and not pg_ok:
-        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
-    if r.model.entity_noise is not None and not noise_ok:
-        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): it does not take {what}.")
-    if r.model.waic is not None:
-        raise ArgumentError(f"Relation {r.name} is scored by WAIC (setWaic): a cell's density under {what} is not scored yet.")
-
-
-def _pg_name(r):
-    return "the logit noise model (setLogit)" if r.model.pg["model"] == "logit" else "the count noise model (setCounts)"
-
-
-def _pg_guards(r, what):
-    """what the Polya-Gamma models refuse: the weighted models' list, those two themselves and a sampled precision"""
-    _weight_guards(r, what, pg_ok=True)
-    if r.model.robust is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
-    if r.model.weights is not None:
-        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
-    if r.model.alpha_sample:
-        raise ArgumentError(f"Relation {r.name} samples its precision (alpha_sample): under {what} every cell's precision is its sampled omega.")
-
-
-def _pg_offset(r, offset):
-    if isinstance(offset, bool) or not isinstance(offset, (int, float, np.integer, np.floating)) or not np.isfinite(offset):
-        raise ArgumentError(f"Relation {r.name}: offset = {offset} must be a finite number.")
-    return float(offset)
-
-
 def _pg_r(r, disp):
-    if isinstance(disp, bool) or not isinstance(disp, (int, float, np.integer, np.floating)) or not np.isfinite(disp) \
-            or disp != int(disp) or disp < 1 or disp > COUNT_MAX:
+    if not _number(disp) or disp != int(disp) or disp < 1 or disp > COUNT_MAX:
         raise ArgumentError(f"Relation {r.name}: r = {disp} must be an integer, at least 1.")
     return int(disp)
 
@@ -430,12 +320,10 @@ def setLogit(r, offset=0.0):
     Scott & Windle 2013), which makes the row a Gaussian pseudo-observation (y - 1/2) / omega of psi with precision omega.
     Predictions become probabilities, class_cut 0.5.  Works before or after assignToTest / setTest; every training and test value
     must be exactly 0 or 1."""
-    if r.model.pg is not None and r.model.pg["model"] != "logit":
-        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take the logit noise model (setLogit) as well.")
-    _pg_guards(r, "the logit noise model (setLogit)")
+    refuse(r, "logit")
     if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
         raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the logit noise model.")
-    r.model.pg = {"model": "logit", "r": 0, "offset": _pg_offset(r, offset)}
+    r.model.pg = {"model": "logit", "r": 0, "offset": _finite(r, "offset", offset)}
     r.model.alpha = 1.0
     r.model.alpha_sample = False
     r.model.mean_value = r.model.pg["offset"]
@@ -451,10 +339,8 @@ def setCounts(rel, r, offset=0.0):
     p^y (1 - p)^r at p = 1 / (1 + e^-psi).  macau() samples omega ~ PG(y + r, psi) for every training row beside the rows, which
     makes the row a Gaussian pseudo-observation (y - r) / (2 omega) of psi with precision omega (exact up to y + r = 170, a
     moment-matched normal above).  Predictions are the mean r e^psi.  Works before or after assignToTest / setTest."""
-    if rel.model.pg is not None and rel.model.pg["model"] != "counts":
-        raise ArgumentError(f"Relation {rel.name} has {_pg_name(rel)}: it does not take the count noise model (setCounts) as well.")
-    _pg_guards(rel, "the count noise model (setCounts)")
-    disp, off = _pg_r(rel, r), _pg_offset(rel, offset)
+    refuse(rel, "counts")
+    disp, off = _pg_r(rel, r), _finite(rel, "offset", offset)
     if not _is_count(rel.data.values) or not _is_count(rel.test_vec.values):
         raise ArgumentError(f"Relation {rel.name} must hold only the integers 0 ... 2^31 for the count noise model.")
     rel.model.pg = {"model": "counts", "r": disp, "offset": off}
@@ -468,11 +354,10 @@ def setCounts(rel, r, offset=0.0):
 def check_pg(r):
     """what a logit or count relation must still satisfy when a sampler is built on it (it may have been changed since)"""
     pg = r.model.pg
-    what = _pg_name(r)
-    _pg_guards(r, what)
+    refuse(r, pg["model"], build=True)
     if r.model.alpha != 1.0:
-        raise ArgumentError(f"Relation {r.name} has {what}: every cell's precision is its sampled omega, alpha stays 1.")
-    off = _pg_offset(r, pg.get("offset"))
+        raise ArgumentError(f"Relation {r.name} has {OPTION[pg['model']].phrase}: every cell's precision is its sampled omega, alpha stays 1.")
+    off = _finite(r, "offset", pg.get("offset"))
     if pg["model"] == "logit":
         if not _is_binary(r.data.values) or not _is_binary(r.test_vec.values):
             raise ArgumentError(f"Relation {r.name} must hold only the values 0 and 1 for the logit noise model.")
@@ -492,16 +377,14 @@ def setRobust(r, nu=4.0):
     precision instead of dragging the factors; result["robust"]["weights"] is the posterior mean of omega per training row (small:
     an outlier).  nu >= 1; nu = 1 is Cauchy noise, a large nu approaches the Gaussian model.  Predictions, the test set and alpha
     (fixed, setPrecision or alpha_sample) stay what they are."""
-    _weight_guards(r, "the robust noise model (setRobust)")
-    if r.model.weights is not None:
-        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take the robust noise model (setRobust) as well.")
+    refuse(r, "robust")
     r.model.robust = {"nu": _robust_nu(r, nu)}
     r._dev = None
     return None
 
 
 def _robust_nu(r, nu):
-    if isinstance(nu, bool) or not isinstance(nu, (int, float, np.integer, np.floating)) or not np.isfinite(nu) or nu < 1.0:
+    if not _number(nu) or nu < 1.0:
         raise ArgumentError(f"Relation {r.name}: nu = {nu} must be a finite number, at least 1.")
     return float(nu)
 
@@ -511,9 +394,7 @@ def setWeights(r, weights):
     alpha weights[k] (replicate counts, reported standard errors as 1 / se^2 relative to 1 / alpha, down-weighted imputed cells).
     Every weight is finite and strictly positive.  A sampled alpha is drawn from its conditional under the weights.  Call it AFTER
     the test split (assignToTest removes training rows; setTest does not)."""
-    _weight_guards(r, "observation weights (setWeights)")
-    if r.model.robust is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take observation weights (setWeights) as well.")
+    refuse(r, "weights")
     r.model.weights = _obs_weights(r, weights)
     r._dev = None
     return None
@@ -533,13 +414,11 @@ def _obs_weights(r, weights):
 
 def check_robust(r):
     """what a robust or weighted relation must still satisfy when a sampler is built on it (it may have been changed since)"""
-    what = "the robust noise model (setRobust)" if r.model.robust is not None else "observation weights (setWeights)"
-    _weight_guards(r, what)
-    if r.model.robust is not None and r.model.weights is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take observation weights (setWeights) as well.")
     if r.model.robust is not None:
+        refuse(r, "robust", build=True)
         r.model.robust = {"nu": _robust_nu(r, r.model.robust.get("nu"))}
     if r.model.weights is not None:
+        refuse(r, "weights", build=True)
         r.model.weights = _obs_weights(r, r.model.weights)
 
 
@@ -552,21 +431,10 @@ def setEntityNoise(r, entity, shape=2.0, rate=2.0):
     setPrecision or alpha_sample) stays the overall scale.  result["noise"]["precision"] is the posterior mean tau per row of the
     entity.  Predictions and the test set stay what they are; macau(lpd=True) scores a held-out cell with alpha tau of its row.
     Works before or after the test split."""
-    what = "a noise precision per row (setEntityNoise)"
-    _entity_noise_guards(r, what)
+    refuse(r, "entity_noise")
     r.model.entity_noise = _entity_noise_spec(r, entity, shape, rate)
     r._dev = None
     return None
-
-
-def _entity_noise_guards(r, what):
-    _weight_guards(r, what, noise_ok=True)
-    if r.model.robust is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
-    if r.model.weights is not None:
-        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
-    if r.model.background is not None:
-        raise ArgumentError(f"Relation {r.name} has a background (setBackground): it does not take {what}.")
 
 
 def _entity_noise_spec(r, entity, shape, rate):
@@ -583,14 +451,14 @@ def _entity_noise_spec(r, entity, shape, rate):
         raise ArgumentError(f"Relation {r.name}: entity = {entity!r} must be one of its entities ({', '.join(e.name for e in r.entities)}), "
                             f"by object, by name or by its mode 1 ... {n_modes}.")
     for name, x in (("shape", shape), ("rate", rate)):
-        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x <= 0:
+        if not _number(x) or x <= 0:
             raise ArgumentError(f"Relation {r.name}: {name} = {x} must be a finite number above 0.")
     return {"mode": hit[0] + 1, "shape": float(shape), "rate": float(rate)}
 
 
 def check_entity_noise(r):
     """what a relation with a noise precision per row must still satisfy when a sampler is built on it (it may have been changed since)"""
-    _entity_noise_guards(r, "a noise precision per row (setEntityNoise)")
+    refuse(r, "entity_noise", build=True)
     m = r.model.entity_noise
     r.model.entity_noise = _entity_noise_spec(r, m.get("mode"), m.get("shape"), m.get("rate"))
 
@@ -606,7 +474,7 @@ def setBias(r, entity, shape=1.0, rate=1.0):
     is zero.  Predictions, the test set, lpd, setWaic, rmse_train and full_prediction include the biases; alpha is fixed, set by
     setPrecision, or sampled.  Plain Gaussian noise only: no other noise model, observation weights, relation features,
     setBackground, setDense, setRecommend or setNewTest on the relation, no spike-and-slab or non-negative entity in it; one rank."""
-    _bias_guards(r)
+    refuse(r, "bias")
     mode, spec = _bias_spec(r, entity, shape, rate)
     if mode in r.model.bias:
         raise ArgumentError(f"Relation {r.name} already has biases for its entity {r.entities[mode - 1].name} (setBias): once per entity.")
@@ -621,36 +489,9 @@ def _bias_spec(r, entity, shape, rate):
     return m["mode"], {"shape": m["shape"], "rate": m["rate"]}
 
 
-def _bias_guards(r):
-    what = "biases (setBias)"
-    kind = noise_kind(r)
-    names = {"probit": "the probit noise model (setProbit)", "censored": "censoring flags (setCensored)",
-             "interval": "interval bounds (setInterval / setBinned)", "ordinal": "the ordinal noise model (setOrdinal)",
-             "robust": "the robust noise model (setRobust)", "weights": "observation weights (setWeights)",
-             "entity_noise": "a noise precision per row (setEntityNoise)", "logit": "the logit noise model (setLogit)",
-             "counts": "the count noise model (setCounts)"}
-    if kind != "gauss":
-        raise ArgumentError(f"Relation {r.name} has {names[kind]}: it does not take {what}, which are sampled under plain Gaussian noise.")
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: {what} do not take relation-level side information (both write the rows' base).")
-    if r.model.background is not None:
-        raise ArgumentError(f"Relation {r.name} has a background (setBackground): it does not take {what}, the unlisted cells would need them too.")
-    if r.model.dense:
-        raise ArgumentError(f"Relation {r.name} is dense (setDense): it does not take {what}, no cell is listed to the rows.")
-    if r.model.recommend is not None:
-        raise ArgumentError(f"Relation {r.name} asks for top-k lists (setRecommend): it does not take {what}, the score is u.v + mean alone.")
-    if r.model.new_test is not None:
-        raise ArgumentError(f"Relation {r.name} has cells of new rows (setNewTest): it does not take {what}, a new row has no bias.")
-    for en in r.entities:
-        if en.spike is not None:
-            raise ArgumentError(f"Entity {en.name} has the spike-and-slab prior (setSpikeAndSlab): its relation {r.name} does not take {what}.")
-        if en.nonneg is not None:
-            raise ArgumentError(f"Entity {en.name} has the non-negative prior (setNonNegative): its relation {r.name} does not take {what}.")
-
-
 def check_bias(r):
     """what a relation with biases must still satisfy when a sampler is built on it (it may have been changed since setBias)"""
-    _bias_guards(r)
+    refuse(r, "bias", build=True)
     out = {}
     for mode, spec in r.model.bias.items():
         m, sp = _bias_spec(r, mode, spec.get("shape"), spec.get("rate"))
@@ -671,45 +512,26 @@ def setSpikeAndSlab(entity, incl_a=1.0, incl_b=1.0, shape=1.0, rate=1.0):
     if not isinstance(entity, Entity):
         raise ArgumentError(f"setSpikeAndSlab takes an Entity, not {type(entity).__name__}.")
     spec = _spike_spec(entity, incl_a, incl_b, shape, rate)
-    _spike_guards(entity)
+    refuse(entity, "spike")
     entity.spike = spec
     return None
 
 
 def _spike_spec(entity, incl_a, incl_b, shape, rate):
-    def number(x):
-        return not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating)) and np.isfinite(x)
     for name, x in (("incl_a", incl_a), ("incl_b", incl_b), ("shape", shape)):
-        if not number(x) or x < 0.5:
+        if not _number(x) or x < 0.5:
             raise ArgumentError(f"Entity {entity.name}: {name} = {x} must be a finite number, at least 0.5 (setSpikeAndSlab).")
-    if not number(rate) or rate <= 0:
+    if not _number(rate) or rate <= 0:
         raise ArgumentError(f"Entity {entity.name}: rate = {rate} must be a finite number above 0 (setSpikeAndSlab).")
     return {"incl_a": float(incl_a), "incl_b": float(incl_b), "shape": float(shape), "rate": float(rate)}
-
-
-def _spike_guards(entity):
-    if hasFeatures(entity):
-        raise ArgumentError(f"Entity {entity.name} has features: the spike-and-slab prior (setSpikeAndSlab) does not take side information.")
-    if entity.nonneg is not None:
-        raise ArgumentError(f"Entity {entity.name} has the non-negative prior (setNonNegative): it does not take the spike-and-slab prior "
-                            "(setSpikeAndSlab) as well.")
-    for r in entity.relations:
-        _no_bias(r, f"the spike-and-slab prior (setSpikeAndSlab) of its entity {entity.name}")
-        if r.model.background is not None:
-            raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
-                                "spike-and-slab prior (setSpikeAndSlab), the background folds a dense Gram matrix into the prior precision.")
-        if r.model.dense:
-            raise ArgumentError(f"Relation {r.name} is dense (setDense): its entity {entity.name} does not take the spike-and-slab prior "
-                                "(setSpikeAndSlab), a dense relation folds a Gram matrix into the prior precision.")
 
 
 def check_spike(entity, world=1):
     """what an entity with the spike-and-slab prior must still satisfy when a sampler is built on it"""
     m = entity.spike
     entity.spike = _spike_spec(entity, m.get("incl_a"), m.get("incl_b"), m.get("shape"), m.get("rate"))
-    _spike_guards(entity)
-    if world > 1:
-        raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): one rank only")
+    refuse(entity, "spike", build=True)
+    refuse_ranks(entity, "spike", world)
 
 
 def setNonNegative(entity, shape=1.0, rate=1.0):
@@ -727,46 +549,25 @@ def setNonNegative(entity, shape=1.0, rate=1.0):
     if not isinstance(entity, Entity):
         raise ArgumentError(f"setNonNegative takes an Entity, not {type(entity).__name__}.")
     spec = _nonneg_spec(entity, shape, rate)
-    _nonneg_guards(entity)
+    refuse(entity, "nonneg")
     entity.nonneg = spec
     return None
 
 
 def _nonneg_spec(entity, shape, rate):
-    def number(x):
-        return not isinstance(x, (bool, np.bool_)) and isinstance(x, (int, float, np.integer, np.floating)) and np.isfinite(x)
-    if not number(shape) or shape < 0.5:
+    if not _number(shape) or shape < 0.5:
         raise ArgumentError(f"Entity {entity.name}: shape = {shape} must be a finite number, at least 0.5 (setNonNegative).")
-    if not number(rate) or rate <= 0:
+    if not _number(rate) or rate <= 0:
         raise ArgumentError(f"Entity {entity.name}: rate = {rate} must be a finite number above 0 (setNonNegative).")
     return {"shape": float(shape), "rate": float(rate)}
-
-
-def _nonneg_guards(entity):
-    if hasFeatures(entity):
-        raise ArgumentError(f"Entity {entity.name} has features: the non-negative prior (setNonNegative) does not take side information.")
-    if entity.new_rows is not None:
-        raise ArgumentError(f"Entity {entity.name} has new rows (setNewRows): the non-negative prior (setNonNegative) does not take them.")
-    if entity.spike is not None:
-        raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): it does not take the non-negative prior "
-                            "(setNonNegative) as well.")
-    for r in entity.relations:
-        _no_bias(r, f"the non-negative prior (setNonNegative) of its entity {entity.name}")
-        if r.model.background is not None:
-            raise ArgumentError(f"Relation {r.name} has a background (setBackground): its entity {entity.name} does not take the "
-                                "non-negative prior (setNonNegative), the background folds a dense Gram matrix into the prior precision.")
-        if r.model.dense:
-            raise ArgumentError(f"Relation {r.name} is dense (setDense): its entity {entity.name} does not take the non-negative prior "
-                                "(setNonNegative), a dense relation folds a Gram matrix into the prior precision.")
 
 
 def check_nonneg(entity, world=1):
     """what an entity with the non-negative prior must still satisfy when a sampler is built on it"""
     m = entity.nonneg
     entity.nonneg = _nonneg_spec(entity, m.get("shape"), m.get("rate"))
-    _nonneg_guards(entity)
-    if world > 1:
-        raise ArgumentError(f"Entity {entity.name} has the non-negative prior (setNonNegative): one rank only")
+    refuse(entity, "nonneg", build=True)
+    refuse_ranks(entity, "nonneg", world)
 
 
 def setBackground(r, weight, value=0.0):
@@ -779,17 +580,17 @@ def setBackground(r, weight, value=0.0):
     conditional over all N M cells.  noise_kind stays "gauss" or "weights".  Held-out cells (assignToTest / setTest) that are not
     listed are background cells during training: the usual protocol for implicit data.  rmse_train covers the listed cells.
     Works before or after setWeights and the test split."""
-    what = "a background (setBackground)"
-    _background_guards(r, what)
-    w, v = _background_number(r, "weight", weight), _background_number(r, "value", value)
+    refuse(r, "background")
+    _background_cells(r)
+    w, v = _finite(r, "weight", weight), _finite(r, "value", value)
     _background_weight(r, w)
     r.model.background = {"weight": w, "value": v}
     r._dev = None
     return None
 
 
-def _background_number(r, name, x):
-    if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x):
+def _finite(r, name, x):
+    if not _number(x):
         raise ArgumentError(f"Relation {r.name}: {name} = {x} must be a finite number.")
     return float(x)
 
@@ -801,28 +602,30 @@ def _background_weight(r, w):
         raise ArgumentError(f"Relation {r.name}: weight = {w} must lie strictly between 0 and the smallest weight of a listed cell ({least}).")
 
 
-def _background_guards(r, what):
+def _two_modes(r, key, takes):
     if len(r.data.dims) != 2:
-        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} takes a two-mode relation.")
-    _weight_guards(r, what)
-    if r.model.robust is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
-    for en in r.entities:
-        if en.nonneg is not None:
-            raise ArgumentError(f"Entity {en.name} has the non-negative prior (setNonNegative): its relation {r.name} does not take {what}, "
-                                "which folds a Gram matrix into the prior precision.")
+        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {OPTION[key].phrase} {takes} a two-mode relation.")
+
+
+def _listed_once(r, key, why):
     ids = np.asarray(r.data.ids).reshape(r.data.nnz(), 2)
     if len(np.unique(ids, axis=0)) != len(ids):
-        raise ArgumentError(f"Relation {r.name} lists a cell more than once: {what} would subtract it from the Gram term twice.")
+        raise ArgumentError(f"Relation {r.name} lists a cell more than once: {OPTION[key].phrase} {why}.")
+    return ids
+
+
+def _background_cells(r):
+    _two_modes(r, "background", "takes")
+    _listed_once(r, "background", "would subtract it from the Gram term twice")
 
 
 def check_background(r):
     """what a background relation must still satisfy when a sampler is built on it (setWeights, a noise model or setWaic may have
     come since setBackground)"""
-    what = "a background (setBackground)"
-    _background_guards(r, what)
+    refuse(r, "background", build=True)
+    _background_cells(r)
     b = r.model.background
-    w, v = _background_number(r, "weight", b.get("weight")), _background_number(r, "value", b.get("value"))
+    w, v = _finite(r, "weight", b.get("weight")), _finite(r, "value", b.get("value"))
     _background_weight(r, w)
     r.model.background = {"weight": w, "value": v}
 
@@ -832,9 +635,6 @@ def background_mean(r):
     cells = float(r.data.dims[0]) * float(r.data.dims[1])
     nn = r.data.nnz()
     return (float(np.sum(np.asarray(r.data.values, dtype=np.float64))) + (cells - nn) * r.model.background["value"]) / cells if cells else 0.0
-
-
-_DENSE = "a dense matrix (setDense)"
 
 
 def setDense(r, on=True):
@@ -852,7 +652,7 @@ def setDense(r, on=True):
         r.model.dense = False
         r._dev = None
         return None
-    _dense_guards(r)
+    check_dense(r, build=False)
     r.model.dense = True
     r._dev = None
     return None
@@ -873,55 +673,17 @@ def denseRelation(Y, name, entities, class_cut=0.0, alpha=1.0):
     return r
 
 
-def _dense_guards(r):
-    what = _DENSE
-    _no_bias(r, what)
-    if len(r.data.dims) != 2:
-        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} takes a two-mode relation.")
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: {what} does not take relation-level side information.")
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take {what}.")
-    if r.model.censor is not None:
-        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take {what}.")
-    if r.model.ordinal is not None:
-        raise ArgumentError(f"Relation {r.name} has the ordinal noise model (setOrdinal): it does not take {what}.")
-    if r.model.interval is not None:
-        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): it does not take {what}.")
-    if r.model.pg is not None:
-        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: it does not take {what}.")
-    if r.model.entity_noise is not None:
-        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): it does not take {what}.")
-    if r.model.robust is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): it does not take {what}.")
-    if r.model.weights is not None:
-        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): it does not take {what}.")
-    if r.model.background is not None:
-        raise ArgumentError(f"Relation {r.name} has a background (setBackground): it does not take {what}, which leaves no cell unlisted.")
-    if r.model.recommend is not None:
-        raise ArgumentError(f"Relation {r.name} asks for top-k lists (setRecommend): it does not take {what}.")
-    if r.model.new_test is not None:
-        raise ArgumentError(f"Relation {r.name} has cells of new rows (setNewTest): it does not take {what}.")
-    for en in r.entities:
-        if en.spike is not None:
-            raise ArgumentError(f"Entity {en.name} has the spike-and-slab prior (setSpikeAndSlab): its relation {r.name} does not take {what}, "
-                                "which folds a Gram matrix into the prior precision.")
-        if en.nonneg is not None:
-            raise ArgumentError(f"Entity {en.name} has the non-negative prior (setNonNegative): its relation {r.name} does not take {what}, "
-                                "which folds a Gram matrix into the prior precision.")
-    ids = np.asarray(r.data.ids).reshape(r.data.nnz(), 2)
-    if len(np.unique(ids, axis=0)) != len(ids):
-        raise ArgumentError(f"Relation {r.name} lists a cell more than once: {what} keeps one value per cell.")
+def check_dense(r, build=True):
+    """what a dense relation must still satisfy when a sampler is built on it (a noise model, a background or a test split may have
+    come since setDense)"""
+    what = OPTION["dense"].phrase
+    refuse(r, "dense", build)
+    _two_modes(r, "dense", "takes")
+    ids = _listed_once(r, "dense", "keeps one value per cell")
     cells = int(r.data.dims[0]) * int(r.data.dims[1])
     if cells == 0 or 2 * len(ids) < cells:
         raise ArgumentError(f"Relation {r.name} lists {len(ids)} of its {cells} cells: {what} takes a relation with at least half of them "
                             "listed (the sparse path is the right one for this one).")
-
-
-def check_dense(r):
-    """what a dense relation must still satisfy when a sampler is built on it (a noise model, a background or a test split may have
-    come since setDense)"""
-    _dense_guards(r)
 
 
 def dense_matrix(r):
@@ -947,7 +709,8 @@ def setRecommend(r, k, rows=None, exclude_listed=True, batch=8):
     item id; a list is padded with item 0 and score NaN behind the row's last candidate.  The first relation of its RelationData,
     two modes, no relation features, a noise model whose prediction is u.v + mean (not probit, logit or counts), one rank.
     Nothing of the chain changes."""
-    _recommend_guards(r)
+    refuse(r, "recommend")
+    _two_modes(r, "recommend", "take")
     r.model.recommend = _recommend_spec(r, k, rows, exclude_listed, batch)
     r._dev = None
     return None
@@ -980,23 +743,10 @@ def _recommend_spec(r, k, rows, exclude_listed, batch):
     return {"k": k, "rows": rows, "exclude_listed": bool(exclude_listed), "batch": batch}
 
 
-def _recommend_guards(r):
-    what = "top-k lists (setRecommend)"
-    _not_dense(r, what)
-    _no_bias(r, what)
-    if len(r.data.dims) != 2:
-        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: {what} do not take relation-level side information.")
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): its prediction is not u.v + mean, {what} are not possible.")
-    if r.model.pg is not None:
-        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: its prediction is not u.v + mean, {what} are not possible.")
-
-
 def check_recommend(r):
     """what a relation with setRecommend must still satisfy when a sampler is built on it (a noise model may have come since)"""
-    _recommend_guards(r)
+    refuse(r, "recommend", build=True)
+    _two_modes(r, "recommend", "take")
     m = r.model.recommend
     r.model.recommend = _recommend_spec(r, m.get("k"), m.get("rows"), m.get("exclude_listed"), m.get("batch"))
 
@@ -1019,13 +769,10 @@ def setNewRows(entity, F_new):
     return None
 
 
-def _new_rows_guards(entity, F_new):
+def _new_rows_guards(entity, F_new, build=False):
     if not hasFeatures(entity):
         raise ArgumentError(f"Entity {entity.name} has no features: new rows (setNewRows) are predicted from their features through beta.")
-    if entity.spike is not None:
-        raise ArgumentError(f"Entity {entity.name} has the spike-and-slab prior (setSpikeAndSlab): it takes no side information and no new rows (setNewRows).")
-    if entity.nonneg is not None:
-        raise ArgumentError(f"Entity {entity.name} has the non-negative prior (setNonNegative): it takes no side information and no new rows (setNewRows).")
+    refuse(entity, "new_rows", build)
     if feat.isempty(F_new):
         raise ArgumentError(f"Entity {entity.name}: F_new is empty (setNewRows takes a matrix with one row per new instance; None clears it).")
     have, want = feat.feature_shape(F_new)[1], feat.feature_shape(entity.F)[1]
@@ -1050,7 +797,7 @@ def setNewTest(r, entity, table):
     hit = [k for k, e in enumerate(r.entities) if e is entity]
     if not hit:
         raise ArgumentError(f"Relation {r.name} has no entity {entity.name} (setNewTest).")
-    _new_test_guards(r, entity)
+    _new_test_guards(r, entity, build=False)
     ids, vals, _ = _split_table(table)
     ids, vals = np.asarray(ids), np.asarray(vals, dtype=np.float64).reshape(-1)
     if ids.ndim != 2 or ids.shape[1] != 2 or len(ids) != len(vals):
@@ -1063,26 +810,12 @@ def setNewTest(r, entity, table):
     return None
 
 
-def _new_test_guards(r, entity):
-    what = "cells of new rows (setNewTest)"
-    _not_dense(r, what)
-    _no_bias(r, what)
-    if len(r.entities) != 2 or len(r.data.dims) != 2:
-        raise ArgumentError(f"Relation {r.name} has {len(r.data.dims)} modes: {what} take a two-mode relation.")
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: {what} do not take relation-level side information.")
-    kind = noise_kind(r)
-    why = {"logit": f"{_pg_name(r) if r.model.pg is not None else ''}: the marginal over a new row's factor has no closed form",
-           "counts": f"{_pg_name(r) if r.model.pg is not None else ''}: the marginal over a new row's factor has no closed form",
-           "robust": "the robust noise model (setRobust): the marginal over a new row's factor has no closed form",
-           "weights": "observation weights (setWeights): the weight of a new cell is unknown",
-           "entity_noise": "a noise precision per row (setEntityNoise): the precision of a new row is unknown",
-           "ordinal": "the ordinal noise model (setOrdinal): a held-out level is not a measurement"}
-    if kind in why:
-        raise ArgumentError(f"Relation {r.name} has {why[kind]}; {what} are not possible.")
+def _new_test_guards(r, entity, build):
+    refuse(r, "new_test", build)
+    _two_modes(r, "new_test", "take")
     if entity.new_rows is None:
         raise ArgumentError(f"Entity {entity.name} has no new rows: call setNewRows(entity, F_new) before setNewTest.")
-    _new_rows_guards(entity, entity.new_rows)
+    _new_rows_guards(entity, entity.new_rows, build)
 
 
 def _new_test_spec(r, mode, ids, vals):
@@ -1115,10 +848,9 @@ def check_new_rows(data, world=1):
     entity = r.entities[m["mode"] - 1] if 1 <= m.get("mode", 0) <= len(r.entities) else None
     if entity is None:
         raise ArgumentError(f"Relation {r.name}: the entity of its new cells is not among its entities (setNewTest).")
-    _new_test_guards(r, entity)
+    _new_test_guards(r, entity, build=True)
     r.model.new_test = _new_test_spec(r, m["mode"], np.asarray(m["ids"], dtype=np.int64).reshape(-1, 2), np.asarray(m["values"], dtype=np.float64))
-    if world > 1:
-        raise ArgumentError(f"Relation {r.name} lists cells of new rows (setNewTest): one rank only")
+    refuse_ranks(r, "new_test", world)
     return r
 
 
@@ -1133,10 +865,7 @@ def _censor_flags(r, censor):
 
 def check_censored(r):
     """what a censored relation must still satisfy when a sampler is built on it (it may have been changed since setCensored)"""
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: the censored noise model does not take relation-level side information.")
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model: it does not take censoring flags.")
+    refuse(r, "censored", build=True)
     r.model.censor = _censor_flags(r, r.model.censor)
 
 
@@ -1147,9 +876,7 @@ def setInterval(r, lower, upper):
     row with lower < upper beside the rows: z ~ N(u'v + mean, 1 / alpha) truncated to the interval.  The stored value is where the
     latent starts, so it must lie inside its bounds.  Predictions, the test set and alpha (fixed, setPrecision or alpha_sample)
     stay what they are.  Call it AFTER the test split (assignToTest removes training rows; setTest does not)."""
-    _interval_guards(r)
-    if r.model.ordinal is not None:
-        raise ArgumentError(f"Relation {r.name} is ordinal (setOrdinal): its bounds follow its edges, it does not take bounds of its own (setInterval / setBinned).")
+    refuse(r, "interval")
     r.model.interval = _interval_bounds(r, lower, upper)
     r._dev = None
     return None
@@ -1176,9 +903,7 @@ def setTestInterval(r, lower, upper):
     but the LPD reads the bounds: predictions, RMSE and ROC stay what they are.  setTest and assignToTest replace the test
     table and drop the bounds: call this after them.  Not on a probit relation, whose 0/1 test values are scored by the probit
     likelihood."""
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): its test values are scored as 0/1 values, "
-                            "it does not take test bounds (setTestInterval).")
+    refuse(r, "test_interval")
     r.model.test_interval = _interval_bounds(r, lower, upper, test=True)
     r.model.test_ordinal = None
     return None
@@ -1224,16 +949,13 @@ def setOrdinal(r, n_levels=None, step=0.1, sample_edges=True):
     and so are setProbit, setCensored and a setInterval / setBinned of the relation's own.  Call it AFTER the test split.  The
     edges' trace and the step size's burn-in belong to one macau() run: macau(engine=..., reset_model=False) does not continue a
     chain whose edges have moved, it is refused."""
-    _interval_guards(r)
-    if r.model.interval is not None and r.model.ordinal is None:
-        raise ArgumentError(f"Relation {r.name} has interval bounds (setInterval / setBinned): an ordinal relation's bounds follow its edges (setOrdinal).")
+    refuse(r, "ordinal")
     v = np.asarray(r.data.values, dtype=np.float64)
     if n_levels is None:
         if len(v) == 0 or not bool(np.all(np.isfinite(v))):
             raise ArgumentError(f"Relation {r.name}: the training values of an ordinal relation must be the integers 1 ... K.")
         n_levels = v.max()
-    if isinstance(n_levels, bool) or not isinstance(n_levels, (int, float, np.integer, np.floating)) or not np.isfinite(n_levels) \
-            or n_levels != int(n_levels):
+    if not _number(n_levels) or n_levels != int(n_levels):
         raise ArgumentError(f"Relation {r.name}: n_levels must be an integer.")
     K = int(n_levels)
     if K == 3:
@@ -1268,6 +990,7 @@ def setTestOrdinal(r):
 def check_ordinal(r):
     """what an ordinal relation must still satisfy when a sampler is built on it (it may have been changed since setOrdinal); the
     chain starts from the edges k + 1/2"""
+    refuse(r, "ordinal", build=True)
     o = r.model.ordinal
     K = int(o["K"])
     if K < ORDINAL_MIN_LEVELS or K > ORDINAL_MAX_LEVELS or not (1e-8 <= float(o["step"]) <= 10.0):
@@ -1291,14 +1014,8 @@ def setWaic(r, on=True, pointwise=False):
         raise ArgumentError(f"Relation {r.name}: setWaic takes on = true / false and pointwise = true / false.")
     if pointwise and not on:
         raise ArgumentError(f"Relation {r.name}: setWaic(on = false) returns no pointwise table.")
-    if on and r.model.robust is not None:
-        raise ArgumentError(f"Relation {r.name} has the robust noise model (setRobust): a cell's density under it is not scored yet (setWaic).")
-    if on and r.model.weights is not None:
-        raise ArgumentError(f"Relation {r.name} has observation weights (setWeights): a cell's density under them is not scored yet (setWaic).")
-    if on and r.model.pg is not None:
-        raise ArgumentError(f"Relation {r.name} has {_pg_name(r)}: a cell's density under it is not scored yet (setWaic).")
-    if on and r.model.entity_noise is not None:
-        raise ArgumentError(f"Relation {r.name} has a noise precision per row (setEntityNoise): a cell's density under it is not scored yet (setWaic).")
+    if on:
+        refuse(r, "waic")
     r.model.waic = {"pointwise": bool(pointwise)} if on else None
     return None
 
@@ -1335,19 +1052,8 @@ def check_test_interval(r):
     b = np.asarray(r.model.test_interval)
     if b.ndim != 2 or b.shape[1] != 2:
         raise ArgumentError(f"Relation {r.name}: test bounds must be a (numTest, 2) array, not {b.shape}.")
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take test bounds (setTestInterval).")
+    refuse(r, "test_interval", build=True)
     r.model.test_interval = _interval_bounds(r, b[:, 0], b[:, 1], test=True)
-
-
-def _interval_guards(r):
-    if hasFeatures(r):
-        raise ArgumentError(f"Relation {r.name} has features: the interval noise model (setInterval) does not take relation-level side information.")
-    if r.model.probit:
-        raise ArgumentError(f"Relation {r.name} has the probit noise model (setProbit): it does not take interval bounds (setInterval).")
-    if r.model.censor is not None:
-        raise ArgumentError(f"Relation {r.name} has censoring flags (setCensored): it does not take interval bounds (setInterval) as well.")
-    _no_weights(r, "interval bounds (setInterval / setBinned / setOrdinal)")
 
 
 def _interval_bounds(r, lower, upper, test=False):
@@ -1376,39 +1082,26 @@ def _interval_bounds(r, lower, upper, test=False):
 
 def check_interval(r):
     """what an interval relation must still satisfy when a sampler is built on it (it may have been changed since setInterval)"""
-    _interval_guards(r)
+    refuse(r, "interval" if r.model.ordinal is None else "ordinal", build=True)       # (an ordinal relation has bounds too)
     b = np.asarray(r.model.interval)
     if b.ndim != 2 or b.shape[1] != 2:
         raise ArgumentError(f"Relation {r.name}: interval bounds must be an (n, 2) array, not {b.shape}.")
     r.model.interval = _interval_bounds(r, b[:, 0], b[:, 1])
 
 
-# what a sampler checks on a relation before it is built, in this order (the ordinal check rebuilds the bounds that the interval
-# check then reads): (the model's fields are set, its check, what the refusal of several ranks calls it -- None: refused through
-# another row, the ordinal model through its interval bounds)
-_MODEL_CHECKS = (
-    (lambda m: m.dense, check_dense, lambda m: "a dense matrix (setDense)"),
-    (lambda m: m.probit, check_probit, lambda m: "the probit noise model"),
-    (lambda m: m.censor is not None, check_censored, lambda m: "censoring flags"),
-    (lambda m: m.ordinal is not None, check_ordinal, None),
-    (lambda m: m.interval is not None, check_interval, lambda m: "interval bounds"),
-    (lambda m: m.robust is not None or m.weights is not None, check_robust,
-     lambda m: "the robust noise model" if m.robust is not None else "observation weights"),
-    (lambda m: m.pg is not None, check_pg, lambda m: f"the {m.pg['model']} noise model"),
-    (lambda m: m.entity_noise is not None, check_entity_noise, lambda m: "a noise precision per row"),
-    (lambda m: m.background is not None, check_background, lambda m: "a background"),
-    (lambda m: m.recommend is not None, check_recommend, lambda m: "top-k lists (setRecommend)"),
-    (lambda m: bool(m.bias), check_bias, lambda m: "biases (setBias)"),
-)
+# what a sampler checks on a relation before it is built, per option that is present, in the registry's order (the ordinal check
+# rebuilds the bounds)
+_CHECKS = {"dense": check_dense, "probit": check_probit, "censored": check_censored, "ordinal": check_ordinal, "interval": check_interval,
+           "robust": check_robust, "weights": check_robust, "entity_noise": check_entity_noise, "logit": check_pg, "counts": check_pg,
+           "background": check_background, "recommend": check_recommend, "bias": check_bias}
 
 
 def check_model(r, world=1):
-    """every check_* that relation r's noise model asks for; world > 1: none of the models runs on several ranks"""
-    for has, check, what in _MODEL_CHECKS:
-        if has(r.model):
-            check(r)
-            if world > 1 and what is not None:
-                raise ArgumentError(f"Relation {r.name} has {what(r.model)}: one rank only")
+    """every check_* that relation r's options ask for; world > 1: none of them runs on several ranks"""
+    for opt in present(r, RELATION):
+        if opt.key in _CHECKS:
+            _CHECKS[opt.key](r)
+            refuse_ranks(r, opt.key, world)
 
 
 def assignToTest(r, test, rng=None):
