@@ -1,8 +1,8 @@
-// hyper_job.h -- device code of the hyperprior update (K6), shared by the stand-alone kernels of k_hyper.hip and by the row
-// sampler's launch (k_sample_rows.hip), which can carry the previous entity's hyperprior update in a few extra workgroups.
+// hyper_job.h -- device code of the hyperprior update (K6), shared by the kernels of k_hyper.hip, the only unit that includes it:
+// the sums' and the draw's kernels on their own (k_hyper_partial, k_hyper_sample) and the one-launch chain (k_hyper_chain).
 //
 //   hyper_partial<DP> : per-workgroup partial of sum_i u_i and U U' over 128 rows -- the same rank-4 MFMA update as K1's
-//   hyper_reduce<DP>  : fixed-order sum of the partials (the order of k_hyper_final: 16 interleaved chains, then a butterfly)
+//   hyper_sum_element : fixed-order sum of the partials (the order of k_hyper_final: 16 interleaved chains, then a butterfly)
 //   nw_draw<DP>       : ConditionalNormalWishart (src/sampling.jl:116-127) + rand(::NormalWishart)
 //                       (src/normal_wishart.jl:38-42) in one workgroup, random part supplied (k_hyper_draws)
 #pragma once
@@ -189,7 +189,7 @@ __device__ __forceinline__ void hyper_scatter(int D, int e, double s, double *su
     }
 }
 
-// ---- the Normal-Wishart draw on one workgroup (nthreads = 256 or 128); lds: HGeo<DP>::NW_LDS doubles ------------------
+// ---- the Normal-Wishart draw on one workgroup (every caller passes nthreads = 256); lds: HGeo<DP>::NW_LDS doubles ------
 // In the reference's terms:
 //     W    = Tinv + UU' + b0 mu0 mu0' - beta_N mu_N mu_N'         (= inv(T_N))
 //     Lam  = (L_T A)(L_T A)',  L_T = chol(T_N)' lower,  A = Bartlett matrix
