@@ -150,6 +150,7 @@ _SIGS = {
     "bdf_ctx_time_next_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_ctx_time_next_hyper": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_ctx_set_item_size": (C.c_int, [C.c_void_p, C.c_int]),
+    "bdf_ctx_item_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "bdf_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "bdf_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "bdf_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
@@ -269,6 +270,12 @@ _SIGS = {
     "bdf_newrows_quad": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_newrows_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p,
                                      C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_void_p]),
+    "bdf_newrows_update_cells": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                           C.c_double, C.c_int, C.c_void_p]),
+    "bdf_foldin_cells": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.POINTER(Term), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_foldin_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_double,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_newrows_result": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_newrows_state": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_dp]),
     "bdf_feat_create_dense": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, c_dp, C.POINTER(C.c_void_p)]),

@@ -253,6 +253,13 @@ extern "C" int bdf_ctx_set_gather_image(bdf_ctx *ctx, int on)
     return BDF_OK;
 }
 
+extern "C" int bdf_ctx_item_size(const bdf_ctx *ctx, int *observations)
+{
+    BDF_REQUIRE(ctx && observations, BDF_ERR_ARG, "bdf_ctx_item_size: NULL argument");
+    *observations = ctx->item_size;
+    return BDF_OK;
+}
+
 extern "C" int bdf_ctx_set_piece_size(bdf_ctx *ctx, int observations)
 {
     BDF_REQUIRE(ctx && observations >= 8 && observations <= ctx->item_size, BDF_ERR_ARG,
@@ -904,6 +911,26 @@ extern "C" int bdf_row_system(bdf_ctx *ctx, int D, int64_t N, int n_terms, const
     for (int r = 0; r < n_terms; r++) { rels[r] = terms[r].rel; modes[r] = terms[r].mode; }
     a.P_dump = P_out;
     a.b_dump = b_out;
+    return bdf_launch_sample_rows(ctx, a, rels, modes, 0, 1, true);
+}
+
+// bdf_foldin_cells (k_foldin.hip): the systems of positions k0 .. k1 - 1 of the term's degree-descending row order, system k at index
+// k - k0 of (P_out, b_out), by the dump launch of bdf_sample_rows_nonneg.  The prior pack is the caller's: prior_c the image of
+// Lambda, prior_b Lambda mu (mu_is_matrix = 0) or Lambda mu_i of the chunk's rows IN THE CHUNK'S ORDER, which is how the dump
+// launch of a range of positions indexes it.
+int bdf_foldin_systems_launch(bdf_ctx *ctx, int D, int64_t N, const bdf_term *term, const double *mu, int mu_is_matrix, const double *Lambda,
+                              const double *prior_b, const double *prior_c, int64_t k0, int64_t k1, double *P_out, double *b_out)
+{
+    SampleArgs a;
+    int rc = fill_args(ctx, "bdf_foldin_cells", D, N, 1, term, mu, mu_is_matrix, Lambda, a);
+    if (rc) return rc;
+    BDF_REQUIRE(!term->rel->sharded, BDF_ERR_ARG, "bdf_foldin_cells: a relation created with a layout (one rank only)");
+    const bdf_rel *rels[1] = {term->rel};
+    const int modes[1] = {term->mode};
+    a.prior_b = prior_b; a.prior_c = prior_c;
+    a.P_dump = P_out; a.b_dump = b_out;
+    a.out = P_out;                      // (a dump writes no sample; an address that names none, so that no gather image is marked stale)
+    ctx->rows_k0 = k0; ctx->rows_k1 = k1;
     return bdf_launch_sample_rows(ctx, a, rels, modes, 0, 1, true);
 }
 

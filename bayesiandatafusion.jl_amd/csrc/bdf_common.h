@@ -198,6 +198,8 @@ struct bdf_pairs {
     double *newrows_dev;          // bdf_newrows_update's running state (k_newrows.hip): five planes of n in storage order -- mean, M2, sum q, M, A; at first use
     double newrows_draws;         // ... the posterior draws it holds (a counter of its own)
     bool newrows_score;           // ... and whether their log-likelihoods were folded in (score_lpd of the phase 1 call)
+    int64_t *foldin_ptr_dev;      // bdf_foldin_cells (k_foldin.hip): the pairs sorted by mode 0 as rows -- foldin_rows + 1 offsets into the storage
+    int64_t foldin_rows, foldin_cols;      // order; made at the first call for these dims, which every id was checked against
 };
 
 // bdf_ordinal (k_ordinal.hip): the edges of an ordinal relation and their Metropolis step's state, all of it in ONE device buffer

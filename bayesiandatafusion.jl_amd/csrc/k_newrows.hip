@@ -13,6 +13,9 @@
 //   bdf_newrows_update  the pair gather of pair_gather.h with the new rows' uhat as the first mode's factor, the link, the fold
 //                       into the running state of five doubles per cell (newrows.h) and eight scalars over the cells with a value,
 //                       through per-workgroup statistics and a fixed-order sum.
+//   bdf_newrows_update_cells  the same update on (m, q) per cell in the pairs' storage order (k_foldin.hip: a new row conditioned on
+//                       cells of its own) instead of the gather.  What a draw does to a cell is one text, bdf_newrows_step of
+//                       newrows.h; the checks, the state, the draw's constants, the statistics and their final sum are shared here.
 //   bdf_newrows_result  (pred, stdev, lpd) per cell in the caller's order.
 //
 // Plain vector stores, no floating-point atomics, no scratch memory.
@@ -129,10 +132,19 @@ __global__ __launch_bounds__(256) void k_newrows_quad(int D, int64_t M, const do
 struct NewArgs {
     PairArgs pair;                 // fac[0]: uhat of the new rows, fac[1]: V
     const double *q;               // per row of V
-    int link, phase, score;
-    double draws, log_draws;       // phase 2: the draws the state holds after this one, and their logarithm
-    double clamp_lo, clamp_hi, cut;
-    double *mean, *M2, *sq, *M, *A;        // the running state, storage order
+    bdf_newrows_draw w;
+    bdf_newrows_planes pl;
+    double *partial;
+};
+
+// bdf_newrows_update_cells: (m, q) per cell in the pairs' storage order instead of the gather
+struct NewCellArgs {
+    int64_t n;
+    const double *values, *m, *q;
+    double alpha;
+    const double *alpha_dev;
+    bdf_newrows_draw w;
+    bdf_newrows_planes pl;
     double *partial;
 };
 
@@ -184,39 +196,28 @@ __global__ __launch_bounds__(256) void k_newrows_update(NewArgs a)
     for (int s = 0; s < BDF_NEWROWS_STATS; s++) st[s] = 0.0;
     const int64_t trip = pair_trip();
     if (trip * 8 < a.pair.n) {                             // (uniform over the group's 8 lanes)
-        const double alpha = a.link == 1 ? 1.0 : pair_alpha(a.pair);
+        const double alpha = a.w.link == 1 ? 1.0 : pair_alpha(a.pair);
         PairLane<2> ln;
         pair_lane(a.pair, trip, ln);
         const double y = a.pair.values[ln.pm];
         const double q = a.q[ln.my[1]];
         const double m = pair_dot<2, VEC, NC>(a.pair, ln) + a.pair.mean;
-        if (ln.ok) {
-            const bool has = y == y;                       // a NaN value: predicted, left out of every scalar
-            const bool scored = has && a.score != 0;
-            const double p = bdf_newrows_predict(a.link, m, q);
-            double l = 0.0;
-            if (scored) l = bdf_newrows_loglik(a.link, y, m, q, alpha);
-            double avg = p, lpd = l;
-            if (a.phase >= 1) {
-                bdf_newrows_cell c;
-                if (a.phase == 1) bdf_newrows_start(p, q, scored, l, c);
-                else {
-                    c.mean = a.mean[ln.pm]; c.M2 = a.M2[ln.pm]; c.sq = a.sq[ln.pm]; c.M = a.M[ln.pm]; c.A = a.A[ln.pm];
-                    lpd = bdf_newrows_fold(p, q, scored, l, a.draws, a.log_draws, c);
-                }
-                a.mean[ln.pm] = c.mean; a.M2[ln.pm] = c.M2; a.sq[ln.pm] = c.sq; a.M[ln.pm] = c.M; a.A[ln.pm] = c.A;
-                avg = c.mean;
-            }
-            if (has) {
-                const double ea = y - clampv(avg, a.clamp_lo, a.clamp_hi), ep = y - clampv(p, a.clamp_lo, a.clamp_hi);
-                const bool label = y < a.cut;
-                st[0] = ea * ea; st[1] = ep * ep;
-                st[2] = (label == (avg < a.cut)) ? 1.0 : 0.0;
-                st[3] = (label == (p < a.cut)) ? 1.0 : 0.0;
-                st[4] = 1.0;
-                if (scored) { st[5] = lpd; st[6] = l; }
-            }
-        }
+        if (ln.ok) bdf_newrows_step(a.w, a.pl, ln.pm, y, m, q, alpha, st);
+    }
+    block_stats8(a.partial, st);
+}
+
+// The same cells on the same lanes as k_newrows_update -- cell 256 block + thread -- so that the workgroups' statistics and their
+// fixed-order sum are the same sums; every lane reaches the statistics' barrier.
+__global__ __launch_bounds__(256) void k_newrows_cells(NewCellArgs a)
+{
+    double st[BDF_NEWROWS_STATS];
+#pragma unroll
+    for (int s = 0; s < BDF_NEWROWS_STATS; s++) st[s] = 0.0;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < a.n) {
+        const double alpha = a.w.link == 1 ? 1.0 : (a.alpha_dev ? *a.alpha_dev : a.alpha);
+        bdf_newrows_step(a.w, a.pl, i, a.values[i], a.m[i], a.q[i], alpha, st);
     }
     block_stats8(a.partial, st);
 }
@@ -263,51 +264,98 @@ extern "C" int bdf_newrows_quad(bdf_ctx *ctx, int D, int64_t M, const double *La
     return BDF_OK;
 }
 
-extern "C" int bdf_newrows_update(bdf_ctx *ctx, bdf_pairs *p, int D, const double *uhat_new_dev, const double *V_dev, const double *q_dev,
-                                  double mean_value, double alpha, const double *alpha_dev, int phase, double clamp_lo, double clamp_hi,
-                                  double class_cut, int score_lpd, double *stats_out)
+// ---- what the two updates share on the host ---------------------------------------------------------------------------------------
+// the checks of the pairs, the phase and the call's per-cell inputs (`inputs`: what they are called, or NULL when they are there)
+static int newrows_check(const char *who, const bdf_ctx *ctx, const bdf_pairs *p, int phase, int score_lpd, const double *stats_out, const char *inputs)
 {
-    const char *who = "bdf_newrows_update";
     BDF_REQUIRE(ctx && p && stats_out, BDF_ERR_ARG, "%s: NULL argument", who);
     BDF_REQUIRE(p->n_modes == 2, BDF_ERR_ARG, "%s: the cells of new rows belong to a two-mode relation, not %d modes", who, p->n_modes);
     BDF_REQUIRE(p->link <= 1, BDF_ERR_ARG, "%s: pairs with the logistic or the count link have no closed form for a new row", who);
     BDF_REQUIRE(!p->baseline_dev && !p->scale_dev, BDF_ERR_ARG, "%s: pairs with a baseline or a precision scale are not predicted for new rows", who);
     BDF_REQUIRE(phase >= 0 && phase <= 2, BDF_ERR_ARG, "%s: phase must be 0, 1 or 2", who);
-    BDF_REQUIRE(p->n == 0 || q_dev, BDF_ERR_ARG, "%s: q_dev is NULL", who);
+    BDF_REQUIRE(p->n == 0 || !inputs, BDF_ERR_ARG, "%s: %s is NULL", who, inputs);
     BDF_REQUIRE(phase != 2 || p->newrows_draws >= 1.0, BDF_ERR_ARG, "%s: phase 2 before a phase 1: the pairs hold no draw", who);
     BDF_REQUIRE(phase != 2 || p->newrows_score == (score_lpd != 0), BDF_ERR_ARG, "%s: score_lpd changed between phase 1 and phase 2", who);
-    const double *fac[2] = {uhat_new_dev, V_dev};
-    NewArgs a = {};
-    int nblocks;
-    int rc = pair_fill(who, ctx, p, D, fac, mean_value, p->link != 1, alpha, alpha_dev, a.pair);
-    if (rc) return rc;
-    if ((rc = pair_blocks(who, "cells", p->n, &nblocks, INT32_MAX / BDF_NEWROWS_STATS))) return rc;
+    return BDF_OK;
+}
+
+// the running state (allocated at the first phase 1 or 2), the draw's constants and the scratch of the workgroups' statistics
+static int newrows_draw(bdf_ctx *ctx, bdf_pairs *p, int phase, double clamp_lo, double clamp_hi, double class_cut, int score_lpd, int nblocks,
+                        bdf_newrows_draw &w, bdf_newrows_planes &pl, double **partial)
+{
     const int64_t n = p->n;
-    BDF_HIP(hipSetDevice(ctx->device));
-    if (n == 0) {
-        BDF_HIP(hipMemsetAsync(stats_out, 0, BDF_NEWROWS_STATS * sizeof(double), ctx->stream));
-    } else {
-        if (phase >= 1 && !p->newrows_dev) {
-            BDF_HIP(hipMalloc((void **)&p->newrows_dev, (size_t)n * BDF_NEWROWS_PLANES * sizeof(double)));
-            BDF_HIP(hipMemsetAsync(p->newrows_dev, 0, (size_t)n * BDF_NEWROWS_PLANES * sizeof(double), ctx->stream));
-        }
-        if (p->newrows_dev) { a.mean = p->newrows_dev; a.M2 = a.mean + n; a.sq = a.M2 + n; a.M = a.sq + n; a.A = a.M + n; }
-        a.q = q_dev; a.link = p->link; a.phase = phase; a.score = score_lpd != 0;
-        a.draws = phase == 2 ? p->newrows_draws + 1.0 : 1.0;
-        a.log_draws = log(a.draws);
-        a.clamp_lo = clamp_lo; a.clamp_hi = clamp_hi; a.cut = class_cut;
-        void *sc;
-        if ((rc = bdf_scratch(ctx, (size_t)nblocks * BDF_NEWROWS_STATS * sizeof(double), &sc))) return rc;
-        a.partial = (double *)sc;
-        if ((D & 3) != 0) hipLaunchKernelGGL((k_newrows_update<1, 1>), dim3(nblocks), dim3(256), 0, ctx->stream, a);
-        else if (D <= 32) hipLaunchKernelGGL((k_newrows_update<4, 1>), dim3(nblocks), dim3(256), 0, ctx->stream, a);
-        else hipLaunchKernelGGL((k_newrows_update<4, 2>), dim3(nblocks), dim3(256), 0, ctx->stream, a);
-        hipLaunchKernelGGL(k_newrows_final, dim3(1), dim3(256), 0, ctx->stream, nblocks, (const double *)a.partial, stats_out);
+    if (phase >= 1 && !p->newrows_dev) {
+        BDF_HIP(hipMalloc((void **)&p->newrows_dev, (size_t)n * BDF_NEWROWS_PLANES * sizeof(double)));
+        BDF_HIP(hipMemsetAsync(p->newrows_dev, 0, (size_t)n * BDF_NEWROWS_PLANES * sizeof(double), ctx->stream));
+    }
+    if (p->newrows_dev) { pl.mean = p->newrows_dev; pl.M2 = pl.mean + n; pl.sq = pl.M2 + n; pl.M = pl.sq + n; pl.A = pl.M + n; }
+    w.link = p->link; w.phase = phase; w.score = score_lpd != 0;
+    w.draws = phase == 2 ? p->newrows_draws + 1.0 : 1.0;
+    w.log_draws = log(w.draws);
+    w.clamp_lo = clamp_lo; w.clamp_hi = clamp_hi; w.cut = class_cut;
+    void *sc;
+    int rc = bdf_scratch(ctx, (size_t)nblocks * BDF_NEWROWS_STATS * sizeof(double), &sc);
+    if (rc) return rc;
+    *partial = (double *)sc;
+    return BDF_OK;
+}
+
+// behind the update's launch: the fixed-order sum of its statistics, and the draws the pairs hold
+static int newrows_done(bdf_ctx *ctx, bdf_pairs *p, int phase, int score_lpd, int nblocks, const double *partial, double *stats_out)
+{
+    if (p->n > 0) {
+        hipLaunchKernelGGL(k_newrows_final, dim3(1), dim3(256), 0, ctx->stream, nblocks, partial, stats_out);
         BDF_HIP(hipGetLastError());
     }
     if (phase == 1) { p->newrows_draws = 1.0; p->newrows_score = score_lpd != 0; }
     else if (phase == 2) p->newrows_draws += 1.0;
     return BDF_OK;
+}
+
+extern "C" int bdf_newrows_update(bdf_ctx *ctx, bdf_pairs *p, int D, const double *uhat_new_dev, const double *V_dev, const double *q_dev,
+                                  double mean_value, double alpha, const double *alpha_dev, int phase, double clamp_lo, double clamp_hi,
+                                  double class_cut, int score_lpd, double *stats_out)
+{
+    const char *who = "bdf_newrows_update";
+    int rc = newrows_check(who, ctx, p, phase, score_lpd, stats_out, q_dev ? nullptr : "q_dev");
+    if (rc) return rc;
+    const double *fac[2] = {uhat_new_dev, V_dev};
+    NewArgs a = {};
+    int nblocks;
+    if ((rc = pair_fill(who, ctx, p, D, fac, mean_value, p->link != 1, alpha, alpha_dev, a.pair))) return rc;
+    if ((rc = pair_blocks(who, "cells", p->n, &nblocks, INT32_MAX / BDF_NEWROWS_STATS))) return rc;
+    BDF_HIP(hipSetDevice(ctx->device));
+    if (p->n == 0) {
+        BDF_HIP(hipMemsetAsync(stats_out, 0, BDF_NEWROWS_STATS * sizeof(double), ctx->stream));
+    } else {
+        if ((rc = newrows_draw(ctx, p, phase, clamp_lo, clamp_hi, class_cut, score_lpd, nblocks, a.w, a.pl, &a.partial))) return rc;
+        a.q = q_dev;
+        if ((D & 3) != 0) hipLaunchKernelGGL((k_newrows_update<1, 1>), dim3(nblocks), dim3(256), 0, ctx->stream, a);
+        else if (D <= 32) hipLaunchKernelGGL((k_newrows_update<4, 1>), dim3(nblocks), dim3(256), 0, ctx->stream, a);
+        else hipLaunchKernelGGL((k_newrows_update<4, 2>), dim3(nblocks), dim3(256), 0, ctx->stream, a);
+    }
+    return newrows_done(ctx, p, phase, score_lpd, nblocks, a.partial, stats_out);
+}
+
+extern "C" int bdf_newrows_update_cells(bdf_ctx *ctx, bdf_pairs *p, const double *m_dev, const double *q_dev, double alpha, const double *alpha_dev,
+                                        int phase, double clamp_lo, double clamp_hi, double class_cut, int score_lpd, double *stats_out)
+{
+    const char *who = "bdf_newrows_update_cells";
+    int rc = newrows_check(who, ctx, p, phase, score_lpd, stats_out, (m_dev && q_dev) ? nullptr : "m_dev or q_dev");
+    if (rc) return rc;
+    BDF_REQUIRE(p->link == 1 || alpha_dev || (alpha > 0.0 && std::isfinite(alpha)), BDF_ERR_ARG, "%s: alpha=%g must be positive and finite", who, alpha);
+    NewCellArgs a = {};
+    int nblocks;
+    if ((rc = pair_blocks(who, "cells", p->n, &nblocks, INT32_MAX / BDF_NEWROWS_STATS))) return rc;
+    BDF_HIP(hipSetDevice(ctx->device));
+    if (p->n == 0) {
+        BDF_HIP(hipMemsetAsync(stats_out, 0, BDF_NEWROWS_STATS * sizeof(double), ctx->stream));
+    } else {
+        if ((rc = newrows_draw(ctx, p, phase, clamp_lo, clamp_hi, class_cut, score_lpd, nblocks, a.w, a.pl, &a.partial))) return rc;
+        a.n = p->n; a.values = p->values_dev; a.m = m_dev; a.q = q_dev; a.alpha = alpha; a.alpha_dev = alpha_dev;
+        hipLaunchKernelGGL(k_newrows_cells, dim3(nblocks), dim3(256), 0, ctx->stream, a);
+    }
+    return newrows_done(ctx, p, phase, score_lpd, nblocks, a.partial, stats_out);
 }
 
 extern "C" int bdf_newrows_result(bdf_ctx *ctx, const bdf_pairs *p, double *out_dev)

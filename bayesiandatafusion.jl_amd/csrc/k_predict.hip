@@ -264,6 +264,7 @@ extern "C" int bdf_pairs_create(bdf_ctx *ctx, int n_modes, int64_t n, const void
     p->ids_dev = nullptr; p->values_dev = nullptr; p->avg_dev = nullptr; p->sq_dev = nullptr; p->auc_ws = nullptr; p->link = 0; p->link_r = 0.0;
     p->lpd_dev = nullptr; p->lpd_draws = 0.0; p->waic_dev = nullptr; p->waic_draws = 0.0; p->scale_dev = nullptr; p->scale_mode = 0;
     p->newrows_dev = nullptr; p->newrows_draws = 0.0; p->newrows_score = false;
+    p->foldin_ptr_dev = nullptr; p->foldin_rows = p->foldin_cols = 0;
     struct Guard { bdf_pairs *p; ~Guard() { if (p) bdf_pairs_destroy(p); } } guard{p};        // error paths free what was allocated
     p->ids_host = h;
     p->values_host.assign(values, values + (n ? n : 0));
@@ -297,6 +298,7 @@ extern "C" int bdf_pairs_destroy(bdf_pairs *p)
     if (p->lpd_dev) hipFree(p->lpd_dev);
     if (p->waic_dev) hipFree(p->waic_dev);
     if (p->newrows_dev) hipFree(p->newrows_dev);
+    if (p->foldin_ptr_dev) hipFree(p->foldin_ptr_dev);
     delete p;
     return BDF_OK;
 }

@@ -53,3 +53,55 @@ BDF_HD_FORCE inline double bdf_newrows_stdev(int link, double M2, double sq, dou
     if (draws < 2.0) return NAN;
     return sqrt(M2 / (draws - 1.0) + (link == 1 ? 0.0 : sq / draws));
 }
+
+// ---- one cell's step of one draw --------------------------------------------------------------------------------------------------
+// What bdf_newrows_update and bdf_newrows_update_cells share: the first gathers (m, q) of a cold row from uhat, V and q_j, the second
+// reads them from per-cell planes (a new row conditioned on cells of its own: k_foldin.hip).  From there on
+// the two are this one text.
+struct bdf_newrows_draw {
+    int link, phase, score;        // phase 0: statistics only, 1: start the running state, 2: fold into it
+    double draws, log_draws;       // phase 2: the draws the state holds after this one, and their logarithm
+    double clamp_lo, clamp_hi, cut;
+};
+
+struct bdf_newrows_planes {
+    double *mean, *M2, *sq, *M, *A;        // the running state, storage order
+};
+
+BDF_HD_FORCE inline double bdf_newrows_clamp(double x, double lo, double hi)
+{
+    if (lo > hi) return x;
+    return x < lo ? lo : (x > hi ? hi : x);
+}
+
+// the cell stored at pm, with value y (NaN: predicted, left out of every scalar): the link, the fold into the state and the cell's
+// eight statistics into st (zero on entry)
+BDF_HD_FORCE inline void bdf_newrows_step(const bdf_newrows_draw &w, const bdf_newrows_planes &pl, long long pm, double y, double m, double q,
+                                          double alpha, double (&st)[BDF_NEWROWS_STATS])
+{
+    const bool has = y == y;
+    const bool scored = has && w.score != 0;
+    const double p = bdf_newrows_predict(w.link, m, q);
+    double l = 0.0;
+    if (scored) l = bdf_newrows_loglik(w.link, y, m, q, alpha);
+    double avg = p, lpd = l;
+    if (w.phase >= 1) {
+        bdf_newrows_cell c;
+        if (w.phase == 1) bdf_newrows_start(p, q, scored, l, c);
+        else {
+            c.mean = pl.mean[pm]; c.M2 = pl.M2[pm]; c.sq = pl.sq[pm]; c.M = pl.M[pm]; c.A = pl.A[pm];
+            lpd = bdf_newrows_fold(p, q, scored, l, w.draws, w.log_draws, c);
+        }
+        pl.mean[pm] = c.mean; pl.M2[pm] = c.M2; pl.sq[pm] = c.sq; pl.M[pm] = c.M; pl.A[pm] = c.A;
+        avg = c.mean;
+    }
+    if (has) {
+        const double ea = y - bdf_newrows_clamp(avg, w.clamp_lo, w.clamp_hi), ep = y - bdf_newrows_clamp(p, w.clamp_lo, w.clamp_hi);
+        const bool label = y < w.cut;
+        st[0] = ea * ea; st[1] = ep * ep;
+        st[2] = (label == (avg < w.cut)) ? 1.0 : 0.0;
+        st[3] = (label == (p < w.cut)) ? 1.0 : 0.0;
+        st[4] = 1.0;
+        if (scored) { st[5] = lpd; st[6] = l; }
+    }
+}

@@ -150,6 +150,11 @@ int bdf_nonneg_sweep_launch(bdf_ctx *ctx, const NonnegSweepArgs &a);
 inline int bdf_prior_image_doubles(int D) { const int DB = bdf_rows_dp(D) / 16; return DB * (DB + 1) / 2 * 4 * 64; }
 int bdf_prior_launch(bdf_ctx *ctx, int D, const double *Lambda, const double *mu, int64_t nrows, int mu_is_matrix, double *out_b, double *out_c);
 
+// ---- the fold-in of new rows (k_foldin.hip) ------------------------------------------------------------
+// the systems of positions k0 .. k1 - 1 of the term's row order by the dump launch, with the caller's prior pack (bdf_api.hip)
+int bdf_foldin_systems_launch(bdf_ctx *ctx, int D, int64_t N, const bdf_term *term, const double *mu, int mu_is_matrix, const double *Lambda,
+                              const double *prior_b, const double *prior_c, int64_t k0, int64_t k1, double *P_out, double *b_out);
+
 // ---- K1c (k_rows_col.hip): four rows per wave in the column layout ----------------------------------------------------
 struct ColJob {           // one lane row of one round
     int32_t row;          // where the sample is written (the row's position in the factor matrix); -1: idle lane row

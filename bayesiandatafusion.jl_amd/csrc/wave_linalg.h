@@ -61,7 +61,55 @@ struct WL {
     static constexpr int tri_doubles(bool share) { return (share ? 1 : G) * TRI + 64; }
 };
 
-template <int DP, bool SHARE = false>
+// Step k of the factorisation: what wl_factor's loop and wl_factor_static's recursion both run.
+template <int DP>
+__device__ __forceinline__ void wl_factor_step(const int k, double (&col)[DP], double &p_own, bool &notpd, double *tg, double *dummy, int c)
+{
+    using W = WL<DP>;
+    double *rk = tg + W::off(k) - k;                  // rk[i] = entry i of column k (i >= k)
+    double *dst = (c >= k) ? rk + c : dummy;          // lanes c < k are done: they park their store
+    *dst = col[k];                                    // A[k][c] = A[c][k]
+    wave_sync();
+    const double pk = rk[k];
+    if (!(pk > 0.0)) notpd = true;
+    const double g = col[k] * fast_rcp(pk);           // A[c][k] / A[k][k]
+    // trailing rows in chunks of WL_CH: a compiler-only memory barrier after each chunk's reads keeps at most two
+    // chunks of broadcast values live (otherwise every read of the step is hoisted: +2 (DP-k) registers)
+    {
+        constexpr int CH = WL_CH;
+        double cur[CH], nxt[CH];
+#pragma unroll
+        for (int u = 0; u < CH; u++) cur[u] = (k + 1 + u < DP) ? rk[k + 1 + u] : 0.0;
+        asm volatile("" ::: "memory");
+#pragma unroll
+        for (int i0 = k + 1; i0 < DP; i0 += CH) {
+#pragma unroll
+            for (int u = 0; u < CH; u++) nxt[u] = (i0 + CH + u < DP) ? rk[i0 + CH + u] : 0.0;
+            asm volatile("" ::: "memory");
+#pragma unroll
+            for (int u = 0; u < CH; u++)
+                if (i0 + u < DP) col[i0 + u] = fma(-cur[u], g, col[i0 + u]);
+#pragma unroll
+            for (int u = 0; u < CH; u++) cur[u] = nxt[u];
+        }
+    }
+    p_own = (c == k) ? pk : p_own;
+}
+
+template <int DP, int K>
+__device__ __forceinline__ void wl_factor_steps(double (&col)[DP], double &p_own, bool &notpd, double *tg, double *dummy, int c)
+{
+    if constexpr (K < DP) {
+        wl_factor_step<DP>(K, col, p_own, notpd, tg, dummy, c);
+        wl_factor_steps<DP, K + 1>(col, p_own, notpd, tg, dummy, c);
+    }
+}
+
+// STATIC: the steps by recursion at compile time instead of a loop.  In the loop the trailing rows' trip count depends on the step;
+// at DP = 64 the compiler leaves that inner loop rolled, indexes col at run time and puts the column into scratch memory (528 bytes
+// per lane in every kernel that takes wl_factor<64>).  In the recursion every index of col is a constant.  The same operations on
+// the same operands either way.
+template <int DP, bool SHARE = false, bool STATIC = false>
 __device__ __forceinline__ bool wl_factor(double (&col)[DP], double &p_own, double &rp_own, double *tri, int lane)
 {
     using W = WL<DP>;
@@ -70,36 +118,10 @@ __device__ __forceinline__ bool wl_factor(double (&col)[DP], double &p_own, doub
     double *dummy = tri + (SHARE ? 1 : W::G) * W::TRI + lane;
     bool notpd = false;
     p_own = 1.0;
+    if constexpr (STATIC) wl_factor_steps<DP, 0>(col, p_own, notpd, tg, dummy, c);
+    else {
 #pragma unroll
-    for (int k = 0; k < DP; k++) {
-        double *rk = tg + W::off(k) - k;                  // rk[i] = entry i of column k (i >= k)
-        double *dst = (c >= k) ? rk + c : dummy;          // lanes c < k are done: they park their store
-        *dst = col[k];                                    // A[k][c] = A[c][k]
-        wave_sync();
-        const double pk = rk[k];
-        if (!(pk > 0.0)) notpd = true;
-        const double g = col[k] * fast_rcp(pk);           // A[c][k] / A[k][k]
-        // trailing rows in chunks of WL_CH: a compiler-only memory barrier after each chunk's reads keeps at most two
-        // chunks of broadcast values live (otherwise every read of the step is hoisted: +2 (DP-k) registers)
-        {
-            constexpr int CH = WL_CH;
-            double cur[CH], nxt[CH];
-#pragma unroll
-            for (int u = 0; u < CH; u++) cur[u] = (k + 1 + u < DP) ? rk[k + 1 + u] : 0.0;
-            asm volatile("" ::: "memory");
-#pragma unroll
-            for (int i0 = k + 1; i0 < DP; i0 += CH) {
-#pragma unroll
-                for (int u = 0; u < CH; u++) nxt[u] = (i0 + CH + u < DP) ? rk[i0 + CH + u] : 0.0;
-                asm volatile("" ::: "memory");
-#pragma unroll
-                for (int u = 0; u < CH; u++)
-                    if (i0 + u < DP) col[i0 + u] = fma(-cur[u], g, col[i0 + u]);
-#pragma unroll
-                for (int u = 0; u < CH; u++) cur[u] = nxt[u];
-            }
-        }
-        p_own = (c == k) ? pk : p_own;
+        for (int k = 0; k < DP; k++) wl_factor_step<DP>(k, col, p_own, notpd, tg, dummy, c);
     }
     rp_own = fast_rcp(p_own);
 #pragma unroll

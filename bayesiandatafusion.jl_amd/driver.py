@@ -66,7 +66,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             refuse(data.relations[0], key)
     robust = data.relations[0].model.robust if data.relations else None
     noise = data.relations[0].model.entity_noise if data.relations else None
-    # cells of rows that were not in training (setNewRows / setNewTest on the first relation)
+    # cells of rows that were not in training (setNewRows / setNewTest on the first relation), with
+    # setNewObserved conditioned on known cells of their own (section 29)
     new_rel = check_new_rows(data)
     if lpd and not (data.relations and numTest(data.relations[0]) > 0) and new_rel is None:
         raise ArgumentError("lpd = true scores held-out cells: the first relation has no test cells (assignToTest / setTest).")
@@ -368,6 +369,9 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         result["new_rows"] = {"entity": rel.entities[spec["mode"] - 1].name, "n_rows": newr.n_rows, "predictions": pd.DataFrame(frame),
                               "RMSE": math.sqrt(new_rep[0] / nsc) if scored else float("nan"), "ROC": float(new_rep[8]),
                               "accuracy": float(new_rep[2] / nsc) if scored else float("nan"), "n_scored": nsc, "factors": fac}
+        if newr.foldin:
+            # (the new rows were conditioned on known cells of their own, setNewObserved: `factors` is then the posterior mean of uhat_i)
+            result["new_rows"]["n_known"] = newr.n_known
         if lpd_new:
             result["new_rows"]["LPD"] = float(new_rep[5] / nsc) if scored else float("nan")
     if waic is not None:

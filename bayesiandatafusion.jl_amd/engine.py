@@ -28,6 +28,7 @@ import torch
 from . import _lib
 from . import features as feat
 from ._lib import ArgumentError, GibbsEntity, Term, check, lib
+from .indexed_df import IndexedDF
 from .relation_data import background_mean, check_model, dense_matrix, noise_kind
 
 
@@ -134,6 +135,12 @@ class Context:
 
     def adopt(self, child):
         self._children.add(child)
+
+    def item_size(self):
+        """the most observations one work item of the wave-per-row kernel takes on this context (bdf_ctx_item_size)"""
+        out = C.c_int(0)
+        check(lib().bdf_ctx_item_size(self.handle, C.byref(out)))
+        return out.value
 
     def set_item_size(self, observations):
         check(lib().bdf_ctx_set_item_size(self.handle, int(observations)))
@@ -563,29 +570,47 @@ class DeviceNewRows:
     """Cells of rows that were not in training (setNewRows / setNewTest; csrc/k_newrows.hip): the operator of
     the new rows' features, their cells as pairs whose first mode indexes the new rows, and the buffers of the three launches that
     follow every iteration on the row stream -- uhat of the new rows (bdf_uhat), q per row of the other entity (bdf_newrows_quad),
-    the update of the cells' running state (bdf_newrows_update).  Nothing of a draw comes to the host."""
+    the update of the cells' running state (bdf_newrows_update).  With known cells of the new rows (setNewObserved; csrc/k_foldin.hip,
+    DESIGN.md section 29) it also holds their relation, n* x M, and the (m, q) planes, and the launches are bdf_uhat for an entity with
+    features, bdf_foldin_cells -- the systems by the row sampler's accumulation into the context's scratch, then a workgroup of four
+    waves per new row -- and bdf_newrows_update_cells.  Nothing of a draw comes to the host."""
 
     def __init__(self, eng, r):
         spec = r.model.new_test
         mode0 = spec["mode"] - 1
         self.eng, self.rel, self.mode0 = eng, r, mode0
         ctx = self.ctx = eng.ctx
-        self.st = eng.ent[eng._entity_index(r.entities[mode0])]          # the entity with features and new rows
+        self.st = eng.ent[eng._entity_index(r.entities[mode0])]          # the entity with new rows
         self.so = eng.ent[eng._entity_index(r.entities[1 - mode0])]      # the other one: V
         D = self.D = eng.D
-        self.F = FeatOperator(ctx, r.entities[mode0].new_rows)
-        self.n_rows = self.F.m
+        known = r.model.new_observed
+        self.foldin = known is not None
+        F_new = r.entities[mode0].new_rows
+        self.F = FeatOperator(ctx, F_new) if F_new is not None else None
+        self.n_rows = self.F.m if self.F is not None else int(known["n_rows"])
         ids, vals = spec["ids"], spec["values"]
-        # (the new row's id first, whichever of the relation's columns holds it; stored sorted by the existing row: neighbours share v_j and q_j)
+        # (the new row's id first, whichever of the relation's columns holds it; stored sorted by the existing row: neighbours share
+        # v_j and q_j -- or, with known cells, by the new row: a row's cells are one workgroup's, bdf_foldin_cells)
         self.pairs = DevicePairs(ctx, np.stack([ids[:, mode0], ids[:, 1 - mode0]], axis=1).reshape(-1, 2), vals)
         if self.pairs.n:
-            self.pairs.sort(1)
+            self.pairs.sort(0 if self.foldin else 1)
         if r.model.probit:
             self.pairs.set_link(1)
+        self.known = self.term = self.m = self.qc = self.n_known = None
+        if self.foldin:
+            # the known cells as a relation of their own, n* x M, whose first mode the row sampler's accumulation takes for (P_i, b_i);
+            # the systems live in the context's scratch, a chunk at a time; (m, q) per cell between the two launches
+            kid = known["ids"]
+            self.known = DeviceRelation(ctx, IndexedDF((np.stack([kid[:, mode0], kid[:, 1 - mode0]], axis=1).reshape(-1, 2), known["values"]),
+                                                       dims=[self.n_rows, self.so.N]))
+            self.term = Term()
+            self.term.rel, self.term.mode, self.term.mean_value = self.known.handle, 0, float(r.model.mean_value)
+            self.m, self.qc = ctx.zeros(max(self.pairs.n, 1)), ctx.zeros(max(self.pairs.n, 1))
+            self.n_known = np.bincount(kid[:, mode0] - 1, minlength=self.n_rows).astype(np.int64)
         self.uhat = ctx.zeros(self.n_rows, D)
         self.factors = ctx.zeros(self.n_rows, D)           # mu + uhat: what the cells are predicted from
         self.factors_sum = ctx.zeros(self.n_rows, D)
-        self.q = ctx.zeros(max(self.so.N, 1))
+        self.q = ctx.zeros(max(self.so.N, 1)) if not self.foldin else None       # q_j per row of V: the cold path's
         self.report = ctx.zeros(10)                        # bdf_newrows_update's 8, then the ROC of the running mean
         self.draws = 0
         # the cells with a value, in the caller's order: what the ROC ranks
@@ -604,20 +629,41 @@ class DeviceNewRows:
         eng, ctx, D, L = self.eng, self.ctx, self.D, lib()
         if eng.ctx_h is not ctx:
             ctx.stream.wait_stream(eng.ctx_h.stream)
-        check(L.bdf_uhat(ctx.handle, self.F.handle, D, _ptr(self.st.beta), _ptr(self.st.mu), _ptr(self.uhat), _ptr(self.factors)))
-        check(L.bdf_newrows_quad(ctx.handle, D, self.so.N, _ptr(self.st.Lambda), _ptr(self.so.sample), _ptr(self.q)))
         lo, hi = (clamp[0], clamp[1]) if len(clamp) else (1.0, -1.0)
         on_dev = torch.is_tensor(alpha)
+        alpha_host, alpha_dev = (0.0 if on_dev else float(alpha)), (_ptr(alpha) if on_dev else None)
+        if self.F is not None:
+            check(L.bdf_uhat(ctx.handle, self.F.handle, D, _ptr(self.st.beta), _ptr(self.st.mu), _ptr(self.uhat), _ptr(self.factors)))
+        if self.foldin:
+            # with known cells: the systems' launch reads V, Lambda, mu_i and alpha under the same stream order,
+            # bdf_foldin_cells leaves uhat_i in `uhat` (over F_new beta, which `factors` = mu_i has taken in) and (m, q) per cell, and
+            # the fold is bdf_newrows_update's on those planes
+            t = self.term
+            t.alpha, t.alpha_dev = (1.0 if on_dev else alpha_host), (alpha.data_ptr() if on_dev else None)
+            t.factors[1] = self.so.sample.data_ptr()
+            mu = self.factors if self.F is not None else self.st.mu
+            check(L.bdf_foldin_cells(ctx.handle, D, self.n_rows, C.byref(t), _ptr(mu), int(self.F is not None), _ptr(self.st.Lambda),
+                                     self.pairs.handle, float(self.rel.model.mean_value), _ptr(self.m), _ptr(self.qc), _ptr(self.uhat)))
+            check(L.bdf_newrows_update_cells(ctx.handle, self.pairs.handle, _ptr(self.m), _ptr(self.qc), alpha_host, alpha_dev, int(phase),
+                                             lo, hi, float(class_cut), int(bool(lpd)), _ptr(self.report)))
+            self._fold_factors(phase, self.uhat)
+            return
+        check(L.bdf_newrows_quad(ctx.handle, D, self.so.N, _ptr(self.st.Lambda), _ptr(self.so.sample), _ptr(self.q)))
         check(L.bdf_newrows_update(ctx.handle, self.pairs.handle, D, _ptr(self.factors), _ptr(self.so.sample), _ptr(self.q),
-                                   float(self.rel.model.mean_value), 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
+                                   float(self.rel.model.mean_value), alpha_host, alpha_dev, int(phase),
                                    lo, hi, float(class_cut), int(bool(lpd)), _ptr(self.report)))
+        self._fold_factors(phase, self.factors)
+
+    def _fold_factors(self, phase, factors):
+        """this draw's factors of the new rows into their running sum, on the row stream"""
+        ctx = self.ctx
         if phase >= 1:
             with torch.cuda.stream(ctx.stream):
                 if phase == 1:
-                    self.factors_sum.copy_(self.factors)
+                    self.factors_sum.copy_(factors)
                     self.draws = 1
                 else:
-                    self.factors_sum += self.factors
+                    self.factors_sum += factors
                     self.draws += 1
 
     def auc(self):
@@ -657,7 +703,10 @@ class DeviceNewRows:
 
     def close(self):
         self.pairs.close()
-        self.F.close()
+        if self.F is not None:
+            self.F.close()
+        if self.known is not None:
+            self.known.close()
 
 
 def device_auc_roc(labels, scores):

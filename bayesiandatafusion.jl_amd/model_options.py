@@ -54,6 +54,7 @@ OPTIONS = (
            True),
     Option("bias", RELATION, "bias", lambda r: bool(r.model.bias), "biases (setBias)", "models a cell as mean + u.v", True),
     Option("new_test", RELATION, "new_test", lambda r: r.model.new_test is not None, "cells of new rows (setNewTest)", None, True),
+    Option("new_observed", RELATION, "new_observed", lambda r: r.model.new_observed is not None, "known cells of new rows (setNewObserved)", None, True),
     Option("waic", RELATION, "waic", lambda r: r.model.waic is not None, "WAIC on its training cells (setWaic)", None, True),
     Option("features", RELATION, "F", lambda r: not feat.isempty(r.F), "features (relation-level side information)"),
     Option("alpha_sample", RELATION, "alpha_sample", lambda r: r.model.alpha_sample, "a sampled precision (alpha_sample)"),
@@ -113,6 +114,14 @@ _ROWS = (
     ("new_test", ("weights",), "the weight of a new cell is unknown, which rules out {incoming}"),
     ("new_test", ("entity_noise",), "the precision of a new row is unknown, which rules out {incoming}"),
     ("new_test", ("ordinal",), "a held-out level is not a measurement, which rules out {incoming}"),
+    # the fold-in: a new row's known cells enter its conditional as u.v + mean under one precision alpha
+    ("new_observed", NOISE, "a new row is conditioned on its known cells under plain Gaussian noise, which rules out {incoming}"),
+    ("new_observed", ("background",), "a new row's unlisted cells are unknown, not background"),
+    ("new_observed", ("dense",), "a new row's known cells are a list"),
+    ("new_observed", ("bias",), "a new row has no bias"),
+    ("new_observed", ("recommend",), "no list is ranked for a new row"),
+    ("new_observed", ("features",), "a new cell has no relation features"),
+    ("new_observed", _PRIORS, "a new row is conditioned under the Normal-Wishart prior, which rules out {incoming}"),
     ("test_interval", ("probit",), "its test values are scored as 0/1 values"),
     ("entity_features", _PRIORS, "{incoming} does not take side information"),
     ("spike", ("nonneg",), None),

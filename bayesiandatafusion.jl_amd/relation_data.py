@@ -144,6 +144,7 @@ class RelationModel:
         self.dense = False        # setDense: all N M cells of the two-mode relation are kept as a matrix on the device, none is listed to the row kernels
         self.bias = {}            # setBias: {mode (1-based): {"shape", "rate"}}; a sampled bias per row of every listed entity
         self.new_test = None      # setNewTest: {"mode" (1-based: the entity with new rows), "ids" (n, 2), "values" (NaN: unknown)}; cells of new rows
+        self.new_observed = None  # setNewObserved: {"mode" (1-based), "ids" (k, 2), "values", "n_rows"}; cells of the new rows that are known
 
 
 class RelationTemp:
@@ -810,21 +811,31 @@ def setNewTest(r, entity, table):
     return None
 
 
+def _folds_in(r, entity):
+    """whether setNewObserved named `entity` on relation r: its new rows are then conditioned on cells of their own"""
+    m = r.model.new_observed
+    return m is not None and 1 <= m.get("mode", 0) <= len(r.entities) and r.entities[m["mode"] - 1] is entity
+
+
 def _new_test_guards(r, entity, build):
     refuse(r, "new_test", build)
     _two_modes(r, "new_test", "take")
     if entity.new_rows is None:
-        raise ArgumentError(f"Entity {entity.name} has no new rows: call setNewRows(entity, F_new) before setNewTest.")
+        # (an entity without features has new rows only through their known cells)
+        if not _folds_in(r, entity):
+            raise ArgumentError(f"Entity {entity.name} has no new rows: call setNewRows(entity, F_new) before setNewTest.")
+        return
     _new_rows_guards(entity, entity.new_rows, build)
 
 
 def _new_test_spec(r, mode, ids, vals):
     entity = r.entities[mode - 1]
-    n_new = feat.feature_shape(entity.new_rows)[0]
+    n_new = feat.feature_shape(entity.new_rows)[0] if entity.new_rows is not None else int(r.model.new_observed["n_rows"])
     other = 2 - mode                                       # 0-based column of the other entity
     n_other = int(r.data.dims[other])
     if len(ids) and (ids[:, mode - 1].min() < 1 or ids[:, mode - 1].max() > n_new):
-        raise ArgumentError(f"Relation {r.name}: a new cell's id of {entity.name} is outside 1 ... {n_new}, the rows of F_new (setNewTest).")
+        rows = "the rows of F_new" if entity.new_rows is not None else "the new rows of setNewObserved"
+        raise ArgumentError(f"Relation {r.name}: a new cell's id of {entity.name} is outside 1 ... {n_new}, {rows} (setNewTest).")
     if len(ids) and (ids[:, other].min() < 1 or ids[:, other].max() > n_other):
         raise ArgumentError(f"Relation {r.name}: a new cell's id of {r.entities[other].name} is outside 1 ... {n_other} (setNewTest).")
     if r.model.probit and not _is_binary(vals[~np.isnan(vals)]):
@@ -834,14 +845,111 @@ def _new_test_spec(r, mode, ids, vals):
     return {"mode": int(mode), "ids": np.ascontiguousarray(ids, dtype=np.int64), "values": np.ascontiguousarray(vals, dtype=np.float64)}
 
 
+def setNewObserved(r, entity, table, n_rows=None):
+    """Cells of the NEW rows of `entity` in relation r that are known -- the ten films a new user has rated, the three assays a new
+    compound was measured in: a table shaped like setNewTest's, where the id in `entity`'s column is 1 ... n*, the other id is an
+    existing instance of the other entity and the value is finite.  macau() then predicts the cells of setNewTest from every
+    posterior draw CONDITIONED on them: given the draw (mu, Lambda, beta, V, alpha), a new row i with prior mean mu_i (mu + beta' f_i
+    for an entity with setNewRows, mu otherwise) and known cells K_i has u* ~ N(uhat_i, P_i^-1) with P_i = Lambda + alpha sum_K v v'
+    and uhat_i = P_i^-1 (Lambda mu_i + alpha sum_K (y - mean) v), which is integrated out of a cell in closed form (DESIGN.md section
+    29).  The known cells do not feed back into the other entity's factors: this is the standard fold-in, p(u* | y*, draw), not a
+    refit.  A row without a known cell is predicted as setNewTest alone predicts it.  A cell of setNewTest may also be a known
+    cell: it is then predicted with its own value in the conditional.
+    n*: the rows of F_new for an entity with setNewRows; for an entity WITHOUT features n_rows, by default the largest new id of the
+    table.  An entity with features but without setNewRows is refused: its new rows' prior mean needs their features.  An entity
+    without features takes setNewTest only after setNewObserved has named it.  result["new_rows"]["factors"] is then the posterior
+    mean of uhat_i and result["new_rows"]["n_known"] the known cells per new row.  An empty table is legal: every row is cold.  The
+    first relation of its RelationData, two modes, plain Gaussian noise (fixed or sampled alpha), the Normal-Wishart prior, one
+    rank; no relation features, setBackground, setDense, setBias or setRecommend.  None clears it."""
+    if table is None:
+        r.model.new_observed = None
+        return None
+    if not isinstance(entity, Entity):
+        raise ArgumentError(f"setNewObserved takes an Entity, not {type(entity).__name__}.")
+    hit = [k for k, e in enumerate(r.entities) if e is entity]
+    if not hit:
+        raise ArgumentError(f"Relation {r.name} has no entity {entity.name} (setNewObserved).")
+    _new_observed_guards(r, entity, build=False)
+    ids, vals, _ = _split_table(table)
+    ids, vals = np.asarray(ids), np.asarray(vals, dtype=np.float64).reshape(-1)
+    if ids.size == 0:
+        ids = np.zeros((0, 2), dtype=np.int64)
+    if ids.ndim != 2 or ids.shape[1] != 2 or len(ids) != len(vals):
+        raise ArgumentError(f"Relation {r.name}: the table of known cells must have two id columns and a value column (setNewObserved).")
+    if not np.issubdtype(ids.dtype, np.integer):
+        if ids.size and not (np.all(np.isfinite(ids)) and np.all(ids == np.floor(ids))):
+            raise ArgumentError(f"Relation {r.name}: the ids of known cells must be integers (setNewObserved).")
+        ids = ids.astype(np.int64)
+    r.model.new_observed = _new_observed_spec(r, hit[0] + 1, ids.astype(np.int64), vals, n_rows)
+    return None
+
+
+def _new_observed_guards(r, entity, build):
+    refuse(r, "new_observed", build)
+    _two_modes(r, "new_observed", "take")
+    if entity.new_rows is not None:
+        _new_rows_guards(entity, entity.new_rows, build)
+    elif hasFeatures(entity):
+        # (mu_i of such a row would be mu + beta' f_i: without f_i it would be conditioned on mu alone, beta silently left out)
+        raise ArgumentError(f"Entity {entity.name} has features but no new rows: call setNewRows(entity, F_new) before setNewObserved, "
+                            "the prior mean of a new row is mu + beta' f.")
+
+
+def _new_observed_spec(r, mode, ids, vals, n_rows):
+    entity = r.entities[mode - 1]
+    other = 2 - mode
+    n_other = int(r.data.dims[other])
+    if n_rows is not None and (isinstance(n_rows, bool) or not isinstance(n_rows, (int, np.integer)) or n_rows < 1):
+        raise ArgumentError(f"Relation {r.name}: n_rows must be a positive integer (setNewObserved).")
+    if entity.new_rows is not None:
+        n_new = feat.feature_shape(entity.new_rows)[0]
+        if n_rows is not None and int(n_rows) != n_new:
+            raise ArgumentError(f"Relation {r.name}: n_rows is {int(n_rows)} but F_new of {entity.name} has {n_new} rows (setNewObserved).")
+        rows = "the rows of F_new"
+    else:
+        if n_rows is None and not len(ids):
+            raise ArgumentError(f"Relation {r.name}: an empty table of known cells needs n_rows, {entity.name} has no F_new to count the new rows by (setNewObserved).")
+        n_new = int(n_rows) if n_rows is not None else int(ids[:, mode - 1].max())
+        rows = "n_rows"
+    if len(ids) and (ids[:, mode - 1].min() < 1 or ids[:, mode - 1].max() > n_new):
+        raise ArgumentError(f"Relation {r.name}: a known cell's id of {entity.name} is outside 1 ... {n_new}, {rows} (setNewObserved).")
+    if len(ids) and (ids[:, other].min() < 1 or ids[:, other].max() > n_other):
+        raise ArgumentError(f"Relation {r.name}: a known cell's id of {r.entities[other].name} is outside 1 ... {n_other} (setNewObserved).")
+    if not np.all(np.isfinite(vals)):
+        raise ArgumentError(f"Relation {r.name}: the value of a known cell must be finite (setNewObserved).")
+    if len(ids) and len(np.unique(ids[:, 0] * (int(ids[:, 1].max()) + 1) + ids[:, 1])) != len(ids):
+        raise ArgumentError(f"Relation {r.name}: a known cell is listed twice (setNewObserved).")
+    return {"mode": int(mode), "ids": np.ascontiguousarray(ids, dtype=np.int64), "values": np.ascontiguousarray(vals, dtype=np.float64),
+            "n_rows": n_new}
+
+
+def _check_new_observed(r, world):
+    """setNewObserved at build time: the same guards on the relation as it is now, and cells of setNewTest on the same entity"""
+    m = r.model.new_observed
+    entity = r.entities[m["mode"] - 1] if 1 <= m.get("mode", 0) <= len(r.entities) else None
+    if entity is None:
+        raise ArgumentError(f"Relation {r.name}: the entity of its known cells is not among its entities (setNewObserved).")
+    _new_observed_guards(r, entity, build=True)
+    r.model.new_observed = _new_observed_spec(r, m["mode"], np.asarray(m["ids"], dtype=np.int64).reshape(-1, 2),
+                                              np.asarray(m["values"], dtype=np.float64), m.get("n_rows") if entity.new_rows is None else None)
+    if r.model.new_test is not None and r.model.new_test.get("mode") != m["mode"]:
+        raise ArgumentError(f"Relation {r.name}: its known cells (setNewObserved) are {entity.name}'s but its new cells (setNewTest) are another entity's.")
+    refuse_ranks(r, "new_observed", world)
+
+
 def check_new_rows(data, world=1):
-    """what setNewRows / setNewTest must still satisfy when macau() runs (models and features may have changed since); returns the
-    relation whose new cells are predicted -- the first one -- or None"""
+    """what setNewRows / setNewTest / setNewObserved must still satisfy when macau() runs (models and features may have changed
+    since); returns the relation whose new cells are predicted -- the first one -- or None"""
     for r in data.relations[1:]:
         if r.model.new_test is not None:
             raise ArgumentError(f"Relation {r.name} lists cells of new rows (setNewTest) but is not the first relation: macau() predicts new "
                                 "rows for the first relation only.")
+        if r.model.new_observed is not None:
+            raise ArgumentError(f"Relation {r.name} lists known cells of new rows (setNewObserved) but is not the first relation: macau() "
+                                "predicts new rows for the first relation only.")
     r = data.relations[0] if data.relations else None
+    if r is not None and r.model.new_observed is not None:
+        _check_new_observed(r, world)
     if r is None or r.model.new_test is None:
         return None
     m = r.model.new_test

@@ -129,6 +129,9 @@ int bdf_ctx_warnings(bdf_ctx *ctx, uint32_t *bits_out);
  * hundreds of waves per resident slot, where pieces only cost partial sums.  Results do not depend on them beyond the order
  * of the floating-point sums. */
 int bdf_ctx_set_item_size(bdf_ctx *ctx, int observations);
+/* *observations = the most observations one work item of the wave-per-row kernel takes on this context as it is set now: a row of
+ * more is cut into pieces (a launch sized automatically may take larger items: rows_plan.hip, route_key) */
+int bdf_ctx_item_size(const bdf_ctx *ctx, int *observations);
 int bdf_ctx_set_piece_size(bdf_ctx *ctx, int observations);
 /* D <= 16, an entity of one two-mode relation: rows of at most max_observations observations are sampled FOUR TO A WAVE (16 lanes
  * and a column-per-lane 16 x 16 system each) by a launch of their own when the entity has at least min_rows rows -- at such
@@ -715,6 +718,38 @@ int bdf_newrows_result(bdf_ctx *ctx, const bdf_pairs *pairs, double *out_dev);
 /* (parity hook, as bdf_pairs_state) *state_dev = the running state, five planes of n doubles in STORAGE order -- mean, M2, sum q, M,
  * A -- or NULL before the first phase 1; *draws = the posterior draws it holds */
 int bdf_newrows_state(const bdf_pairs *pairs, double **state_dev, double *draws);
+
+/* ---- new rows conditioned on a few cells of their own: the fold-in (csrc/k_foldin.hip) ------ */
+/* Given the same draw, a new row i with prior mean mu_i (mu, or mu + beta' f_i with mu_is_matrix: bdf_uhat's mu_matrix_out) whose
+ * cells K_i are known has u* | draw, y* ~ N(uhat_i, P_i^-1) with the row system of bdf_row_system,
+ *   P_i = Lambda + alpha sum_{j in K_i} v_j v_j',  b_i = Lambda mu_i + alpha sum_{j in K_i} (y_ij - mean_value) v_j,  uhat_i = P_i^-1 b_i,
+ * and the cell (i, j) is y | draw ~ N(m, q_ij + 1 / alpha), m = mean_value + uhat_i . v_j, q_ij = v_j' P_i^-1 v_j.  The new row's
+ * cells do not feed back into V (the standard fold-in).  A row without a known cell is bdf_newrows_quad's cold row.
+ * bdf_foldin_cells: known: ONE term of a two-mode relation of the known cells (created once: dims n_new x M with known->mode = 0, or
+ * the other way round), whose other-mode factor is this draw's V (dev, M rows of D doubles) and whose alpha / alpha_dev is the
+ * draw's precision; mu (dev, D doubles, or n_new rows of D with mu_is_matrix) and Lambda (dev, D x D) as bdf_row_system's.  The
+ * systems come from the row sampler's own accumulation (long rows split and summed as bdf_sample_rows does), the new rows in chunks
+ * of bdf_ctx_set_nonneg_chunk's size -- by default the most whose systems stay under the scratch cap of bdf_sample_rows_nonneg --
+ * and the result does not depend on the chunk size, bit for bit.  cells: two modes, stored sorted by the new row
+ * (bdf_pairs_sort(cells, 0)), the first mode's ids in 1..n_new, the second's in 1..M (checked at the first call: BDF_ERR_BOUNDS).
+ * Per new row a workgroup of four waves: one factorises P_i and solves for uhat_i, then all take the row's cells 64 at a time, one
+ * lane per cell.
+ * m_out, q_out (dev, n doubles each): m and q_ij per cell in the pairs' STORAGE order -- what bdf_newrows_update_cells takes;
+ * uhat_out (dev, n_new rows of D doubles): uhat_i of every new row, also of those without a cell.  Any D in 1..BDF_MAX_D.  A P_i
+ * that is not positive definite raises BDF_ERR_NOTPD at the next bdf_ctx_sync and leaves NaN in the row's uhat_i, m and q.
+ * Enqueued on ctx's stream; no host copy, no synchronisation (the first call uploads the cells' row offsets). */
+int bdf_foldin_cells(bdf_ctx *ctx, int D, int64_t n_new, const bdf_term *known, const double *mu, int mu_is_matrix, const double *Lambda,
+                     bdf_pairs *cells, double mean_value, double *m_out, double *q_out, double *uhat_out);
+/* parity hook: the second half alone on given systems in bdf_row_system's layout -- P (dev, D x D x n_new, every entry of the
+ * symmetric matrix) and b (dev, D x n_new), system i that of new row i -- against V (dev, M rows of D doubles) */
+int bdf_foldin_solve(bdf_ctx *ctx, int D, int64_t n_new, const double *P, const double *b, bdf_pairs *cells, int64_t M, const double *V,
+                     double mean_value, double *m_out, double *q_out, double *uhat_out);
+/* bdf_newrows_update on (m, q) per cell (dev, n doubles each, the pairs' STORAGE order: bdf_foldin_cells' output) instead of the
+ * gather from uhat, V and q_j.  From there on the two are one text (csrc/newrows.h): the link, the fold, the phases, stats_out and
+ * its fixed-order sum, the running state and its counter, which bdf_newrows_result and bdf_newrows_state read for both; the same
+ * refusals.  Fed the (m, q_j) of a cold row it leaves the state and the scalars of bdf_newrows_update, bit for bit. */
+int bdf_newrows_update_cells(bdf_ctx *ctx, bdf_pairs *pairs, const double *m_dev, const double *q_dev, double alpha, const double *alpha_dev,
+                             int phase, double clamp_lo, double clamp_hi, double class_cut, int score_lpd, double *stats_out);
 
 /* ---- AUC_ROC (src/ROC.jl:1-11) and vecnorm on the device (csrc/k_auc.hip) ------------ */
 /* bytes of the workspace bdf_auc_roc needs for n scores (-1: n < 0) */

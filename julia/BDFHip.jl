@@ -49,6 +49,11 @@ function sync(c::Context)
 end
 # K1 tuning: rows with more than `item` observations are split into pieces of at most `piece` (defaults 192 / 128)
 set_item_size!(c::Context, item) = check(ccall((:bdf_ctx_set_item_size, lib), Cint, (Ptr{Cvoid}, Cint), c.h, item))
+function item_size(c::Context)
+    out = Ref{Cint}(0)
+    check(ccall((:bdf_ctx_item_size, lib), Cint, (Ptr{Cvoid}, Ref{Cint}), c.h, out))
+    return Int(out[])
+end
 "D <= 16: rows of at most `max_obs` observations of an entity with at least `min_rows` rows are sampled four to a wave (0: off)"
 set_small_rows!(c::Context, max_obs, min_rows) = check(ccall((:bdf_ctx_set_small_rows, lib), Cint, (Ptr{Cvoid}, Cint, Int64), c.h, max_obs, min_rows))
 # rows of few observations by the low-rank sampler (same distribution as sample_user_basic, other values); max_obs = 0: off
@@ -910,6 +915,33 @@ end
 "(pred, stdev, lpd) of every new cell -> out (DevArray of 3 x n doubles), in the caller's order"
 newrows_result!(c::Context, p::DevPairs, out::DevArray{Float64}) =
     check(ccall((:bdf_newrows_result, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}), c.h, p.h, out.p))
+# ---- new rows conditioned on a few cells of their own: the fold-in (setNewObserved) ------------------------------------------------
+"one draw's fold-in: `known` is ONE term of the two-mode relation of the known cells (n_new x M, mode 0) whose other-mode factor is this
+draw's V and whose alpha is the draw's; per new row P_i = Lambda + alpha sum v v', uhat_i = P_i^-1 b_i by the row sampler's own
+accumulation and a workgroup of four waves per row (one factorises, all four share the row's cells), and per cell of `cells` (stored sorted by the new row) m = mean_value + uhat_i . v_j
+and q = v_j' P_i^-1 v_j into m, q (DevArrays of n doubles, storage order); uhat (DevArray D x n_new) for every new row"
+function foldin_cells!(c::Context, D, n_new, known::Term, mu::DevArray{Float64}, mu_is_matrix::Bool, Lambda::DevArray{Float64}, cells::DevPairs,
+                       mean_value, m::DevArray{Float64}, q::DevArray{Float64}, uhat::DevArray{Float64})
+    check(ccall((:bdf_foldin_cells, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ref{Term}, Ptr{Cvoid}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, D, n_new, Ref(known), mu.p, mu_is_matrix ? 1 : 0, Lambda.p, cells.h, mean_value, m.p, q.p, uhat.p))
+end
+"(parity hook) the fold-in's second half on given systems in row_system's layout: P (D x D x n_new), b (D x n_new), V (D x M)"
+function foldin_solve!(c::Context, D, n_new, P::DevArray{Float64}, b::DevArray{Float64}, cells::DevPairs, M, V::DevArray{Float64}, mean_value,
+                       m::DevArray{Float64}, q::DevArray{Float64}, uhat::DevArray{Float64})
+    check(ccall((:bdf_foldin_solve, lib), Cint,
+                (Ptr{Cvoid}, Cint, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, D, n_new, P.p, b.p, cells.h, M, V.p, mean_value, m.p, q.p, uhat.p))
+end
+"newrows_update! on (m, q) per cell (DevArrays of n doubles in the pairs' storage order: foldin_cells!'s output) instead of the gather:
+the same link, fold, phases, stats and running state"
+function newrows_update_cells!(c::Context, p::DevPairs, m::DevArray{Float64}, q::DevArray{Float64}, alpha, alpha_dev, phase::Integer, clamp_lo,
+                               clamp_hi, class_cut, score_lpd::Bool, stats::DevArray{Float64})
+    check(ccall((:bdf_newrows_update_cells, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}, Cint, Float64, Float64, Float64, Cint, Ptr{Cvoid}),
+                c.h, p.h, m.p, q.p, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p, phase, clamp_lo, clamp_hi, class_cut, score_lpd ? 1 : 0,
+                stats.p))
+end
 "(parity hook) the device address of the new cells' running state (five planes of n doubles in storage order) and its draw count"
 function newrows_state(p::DevPairs)
     st, draws = Ref{Ptr{Cvoid}}(C_NULL), Ref(0.0)
