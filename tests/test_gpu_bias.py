@@ -1,5 +1,5 @@
 """Row and column biases on the GPU (setBias): bdf_bias_draw and bdf_bias_baseline against the restatement
-(tests/bias_restatement.py) with rows planted on the group boundaries of both widths, the errors of the C ABI, whole macau()
+(tests/bias_restatement.py) with rows planted on the group boundaries of both widths and with more workgroups than lambda's reduction has threads, the errors of the C ABI, whole macau()
 iterations against the restated chain on both iteration paths, the Gaussian chain untouched by an engine with biases in the same
 process, a relation without biases beside one with them, and planted biases."""
 import ctypes as C
@@ -154,6 +154,119 @@ def test_bias_draw_matches_the_restatement(B, ctx, D, n_modes, biased, plant, so
     assert widths == {8, 64}
     print(f"bias draw D={D} modes={n_modes} biased={biased} sort={sort}: worst |b - b_ref| / bound {worst_b:.3f}, "
           f"max rel. error of lambda {worst_l:.3e} over 4 draws")
+
+
+def _fsum_by_row(rows0, N, x):
+    """math.fsum of x over the cells of every row 0 .. N - 1"""
+    order = np.argsort(rows0, kind="stable")
+    cut = np.searchsorted(rows0[order], np.arange(N + 1))
+    xs = x[order]
+    return np.array([math.fsum(xs[cut[j]:cut[j + 1]].tolist()) for j in range(N)])
+
+
+FINAL = 256                                          # threads of k_bias_lambda: the partial sums of b^2 it adds in one pass
+
+
+def _many_rows_ids(rng, kind):
+    """(width, dims, ids) of a two-mode relation whose mode 0 leaves 257 workgroups' sums of b^2: "8-empty": 32 x 256 + 1 rows, three
+    cells per row on average, some rows empty; "8-full": the same with at least one cell in every row; "64": 4 x 256 + 1 rows of 32
+    cells and 40 more somewhere -- the last workgroup holds one group"""
+    if kind == "64":
+        N = 4 * FINAL + 1
+        rows = np.concatenate([np.repeat(np.arange(1, N + 1), 32), rng.integers(1, N + 1, 40)])
+    else:
+        N = 32 * FINAL + 1
+        rows = rng.integers(1, N + 1, 3 * N) if kind == "8-empty" else np.concatenate([np.arange(1, N + 1), rng.integers(1, N + 1, 2 * N)])
+    rows = rng.permutation(rows)
+    return (64 if kind == "64" else 8), [N, 200], np.stack([rows, rng.integers(1, 201, len(rows))], axis=1).astype(np.int64)
+
+
+@pytest.mark.parametrize("biased", [(0,), (0, 1)])
+def test_bias_draw_with_more_than_256_partial_sums_of_b2(B, ctx, biased):
+    """k_bias_lambda adds the workgroups' sums of b^2 with 256 threads: 257 workgroups are its second pass.  Three relations at D = 7,
+    mode 0 biased alone and both modes biased: the 8-wide row pass over 8193 rows (32 rows a workgroup), some of them empty, and
+    over 8193 rows that all have cells; the 64-wide one over 1025 rows (4 a workgroup) and 32 x 1025 + 40 cells.  Rows are taken by
+    falling degree, so the row that is alone in workgroup 257 is an empty one in the first relation (its bias is its prior's draw)
+    and has cells in the other two.  The checks and bounds are test_bias_draw_matches_the_restatement's (mode 1 has 200 rows, so
+    that no row has more than the 300 cells its bound reckons with: asserted); the rows' normals are BR.normals_reduced's, whose
+    cosine has the device's exact reduction of the angle -- with BR.normals an empty row of the first relation, u = 0.7501944, is
+    2.3 bounds off, which is the rounded angle's error in the reference, not the device's.  That lambda's bound bites is asserted on the CPU:
+    the reference from the first 256 workgroups' rows alone is more than 1e-9 away from the full one."""
+    from bdf_amd._lib import check, lib
+    D, mean, sweep = 7, 0.3, 40 + len(biased)
+    rising = sorted(biased)
+    for kind in ("8-empty", "8-full", "64"):
+        rng = np.random.default_rng(8100 + 10 * len(biased) + len(kind))
+        width, dims, ids = _many_rows_ids(rng, kind)
+        n = len(ids)
+        per_group = 256 // width
+        assert _width(n, dims[0]) == width and -(-dims[0] // per_group) == FINAL + 1 and dims[0] % per_group == 1
+        y = rng.standard_normal(n)
+        dr = B.DeviceRelation(ctx, B.IndexedDF((ids, y), dims))
+        pairs = B.DevicePairs(ctx, ids, y)
+        probe_ids = np.stack([rng.integers(1, d + 1, 77) for d in dims], axis=1)
+        probe = B.DevicePairs(ctx, probe_ids, np.zeros(77))
+        St = [ctx.tensor(rng.standard_normal((d, D))) for d in dims]
+        e = y - pairs.predict(D, St, mean).cpu().numpy()
+        alpha, through_dev = (1.7, False) if len(biased) == 1 else (40.0, True)
+        sweep += 1
+        tag = 1 + sweep % 3
+        spec = {m: (0.5 + m, 2.0 - 0.5 * m) for m in biased}
+        b0 = {m: rng.standard_normal(dims[m]) for m in biased}
+        lam0 = {m: float(np.exp(rng.uniform(-1, 1))) for m in biased}
+        a_arg, a_dev = (alpha, None) if not through_dev else (123.0, ctx.tensor([alpha]))      # the decoy loses
+        ctx.set_sweep(sweep)
+
+        def draw():
+            bt = {m: ctx.tensor(b0[m]) for m in biased}
+            lt = {m: ctx.tensor([lam0[m]]) for m in biased}
+            resid, lin, pb = ctx.tensor(np.full(n, np.nan)), ctx.tensor(np.full(n, np.nan)), ctx.tensor(np.full(77, np.nan))
+            terms = _terms(B, biased, spec, bt, lt)
+            check(lib().bdf_bias_draw(ctx.handle, dr.handle, pairs.handle, D, _facs(St), mean, a_arg, _p(a_dev), tag, len(biased), terms,
+                                      _p(resid), _p(lin)))
+            check(lib().bdf_bias_baseline(ctx.handle, probe.handle, len(biased), terms, mean, _p(pb)))
+            ctx.sync()
+            return ({m: bt[m].cpu().numpy() for m in biased}, {m: float(lt[m].item()) for m in biased}, resid.cpu().numpy(),
+                    lin.cpu().numpy(), pb.cpu().numpy())
+
+        b, lam, resid, lin, pb = draw()
+        assert np.array_equal(resid, e)
+        cur = dict(b0)
+        for m in rising:
+            N = dims[m]
+            rows0 = ids[:, m] - 1
+            r = BR.others_off(e, ids, cur, m)
+            n_j = np.bincount(rows0, minlength=N)
+            assert n_j.max() <= 300
+            S, A = _fsum_by_row(rows0, N, r), _fsum_by_row(rows0, N, np.abs(r))
+            # (among thousands of rows one without cells draws a normal near a zero of its cosine: BR.normals_reduced)
+            z = BR.normals_reduced(SEED, sweep, tag, np.arange(N), m)
+            assert np.abs(z - BR.normals(SEED, sweep, tag, np.arange(N), m)).max() <= 1e-14
+            ref = BR.draw_rows(S, n_j, alpha, lam0[m], z)
+            prec = lam0[m] + alpha * n_j
+            bound = 1e-13 * (alpha * A / prec + np.abs(ref))
+            err = np.abs(b[m] - ref)
+            assert np.all(np.isfinite(b[m])) and np.all(err <= bound), (kind, m, int(np.argmax(err / bound)), float((err / bound).max()))
+            G = float(BR.gamma_variates(SEED, sweep, tag, [m], spec[m][0] + 0.5 * N)[0])
+            lref = BR.draw_lambda(G, spec[m][1], math.fsum((b[m] * b[m]).tolist()))
+            if m == 0:
+                order = dr.order(0)
+                assert sorted(order) == list(range(N)) and np.all(np.diff(n_j[order]) <= 0)
+                assert (n_j[order[-1]] == 0) == (kind == "8-empty") and (n_j.min() == 0) == (kind == "8-empty")
+                head = b[0][order[:FINAL * per_group]]                               # what the first 256 workgroups hold
+                short = BR.draw_lambda(G, spec[m][1], math.fsum((head * head).tolist()))
+                assert abs(short / lref - 1.0) > 1e-9, (kind, short, lref)
+            print(f"bias draw past 256 partial sums, {kind} biased={biased} mode {m}: worst |b - b_ref| / bound {float((err / bound).max()):.3f}, "
+                  f"rel. error of lambda {abs(lam[m] / lref - 1.0):.3e}")
+            assert abs(lam[m] / lref - 1.0) <= 1e-12, (kind, m, lam[m], lref)
+            cur[m] = b[m]
+        assert np.array_equal(lin, BR.base(ids, b, mean)) and np.array_equal(pb, BR.base(probe_ids, b, mean))
+        b2, lam2, resid2, lin2, pb2 = draw()
+        assert all(np.array_equal(b[m], b2[m]) and lam[m] == lam2[m] for m in biased)
+        assert np.array_equal(resid, resid2) and np.array_equal(lin, lin2) and np.array_equal(pb, pb2)
+        probe.close()
+        pairs.close()
+        dr.close()
 
 
 # ---- (b) errors through the C ABI ---------------------------------------------------------------------------------------------

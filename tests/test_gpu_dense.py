@@ -1,7 +1,7 @@
 """Dense relations (setDense) on the GPU.  The oracle is the existing code on the explicit listing: the same
 matrix listed cell by cell has, with the same seed, the same row normals and the same alpha stream, so the same chain up to rounding.
 The two products against math.fsum, the prior and the row systems against the explicit call, alpha's closed-form sum of squares
-against math.fsum over all cells, whole chains on both iteration paths, and the C ABI's refusals."""
+against math.fsum over all cells (also past 256 partial sums), the row means past one wave and one workgroup, whole chains on both iteration paths, and the C ABI's refusals."""
 import ctypes as C
 import math
 import os
@@ -259,6 +259,104 @@ def test_closed_form_sum_of_squares_and_the_alpha_drawn_from_it(B, D, shape):
     print(f"dense sse D={D} N={N} M={M}: closed form {s[0]:.15g} fsum {ref:.15g}, error {abs(s[0] - ref) / pieces:.2e} of the pieces; alpha {a[0]:.15g} {a[1]:.15g}")
     assert s[0] == s[1] and abs(s[0] - ref) <= 1e-12 * pieces
     assert a[0] > 0 and abs(a[0] - a[1]) <= 1e-12 * (pieces / ref) * a[1]
+    c2.close()
+
+
+DOT_SLAB = 4096                                              # elements of U and C a workgroup of k_dmat_dot takes (csrc/k_dense.hip)
+FINAL = 256                                                  # threads of k_dmat_sse_final: the partial sums it adds in one pass
+
+
+@pytest.mark.parametrize("D,N", [(64, 16385), (33, -(-(FINAL * DOT_SLAB + 1) // 33))])
+def test_closed_form_sum_of_squares_past_256_partial_sums(B, D, N):
+    """bdf_dense_sse over N x D elements of U that leave 257 partial sums of u.C, one more than k_dmat_sse_final's 256 threads take in
+    one pass: D = 64 with 16385 rows (the last workgroup of k_dmat_dot holds 64 elements) and D = 33 with 31776 (a ragged tail of
+    32); M = 3.  Against math.fsum over all cells to 1e-12 of the closed form's pieces, as at the small shapes; twice: the same bits.
+    On the CPU first: the kernels' own rounding of sum u.C -- 40 roundings deep: 16 serial fmas, the wave's and the workgroup's
+    reductions, then thread 0's two-term serial sum and the final reduction -- stays inside that bound, and the partial sums from
+    the 257th on move the reference by more than the bound."""
+    from bdf_amd._lib import check, lib
+    M = 3
+    assert -(-(N * D) // DOT_SLAB) == FINAL + 1 and 0 < N * D - FINAL * DOT_SLAB < DOT_SLAB
+    rng = np.random.default_rng(60 + D)
+    Y = DR.table(N, M, seed=D)
+    R, U, V = Y - Y.mean(), 0.5 * rng.standard_normal((N, D)), 0.5 * rng.standard_normal((M, D))
+    p = DR.sse_pieces(R, U, V)
+    pieces = p[0] + 2.0 * abs(p[1]) + p[2]
+    uc = (U * (R @ V)).ravel()
+    assert 40 * 2.0 ** -53 * math.fsum(np.abs(uc).tolist()) <= 1e-12 * pieces
+    tail = 2.0 * abs(math.fsum(uc[FINAL * DOT_SLAB:].tolist()))
+    assert tail > 1e-12 * pieces, (tail, pieces)
+    c2 = B.Context(seed=SEED)
+    R_t, U_t, V_t = c2.tensor(R), c2.tensor(U), c2.tensor(V)
+    C_t = _product(B, c2, R_t, N, M, D, V_t, False)
+    g = [c2.zeros(D, D), c2.zeros(D, D)]
+    s_t = c2.zeros(D)
+    for t, f in zip(g, (U_t, V_t)):
+        check(lib().bdf_hyper_sums(c2.handle, D, f.shape[0], _p(f), None, _p(s_t), _p(t)))
+    r2 = math.fsum((R * R).ravel().tolist())
+    ref = DR.sse_explicit(R, U, V)
+    out = c2.tensor([np.nan, np.nan])
+    for k in (0, 1):
+        check(lib().bdf_dense_sse(c2.handle, D, N, _p(U_t), _p(C_t), _p(g[0]), _p(g[1]), r2, None, C.c_void_p(out.data_ptr() + 8 * k)))
+    c2.sync()
+    s = out.cpu().numpy()
+    print(f"dense sse D={D} N={N} M={M}: closed form {s[0]:.15g} fsum {ref:.15g}, error {abs(s[0] - ref) / pieces:.2e} of the pieces "
+          f"(the last partial sums weigh {tail / pieces:.2e})")
+    assert s[0] == s[1] and abs(s[0] - ref) <= 1e-12 * pieces
+    c2.close()
+
+
+@pytest.mark.parametrize("D", [7, 32, 33, 64])
+def test_prior_rows_past_one_wave_and_one_workgroup(B, D):
+    """k_dmat_mu_rows takes one wave per 16 rows and four waves per workgroup: N = 1, 15, 16, 17 (one wave, its tile short, full, a
+    second wave with one row), 48, 49 (the fourth wave idle, with one row), 63, 64, 65 and 130 (a second and a third workgroup), at
+    M = 29 with one dense term, the shared and the per-row prior mean.  Lambda_eff to 1e-13 max |P| and mu_eff to the forward bound
+    8 D kappa 2^-52 against numpy, as test_prior_alone_against_numpy holds them; 16 guard rows of NaN behind mu_out untouched; a
+    rerun gives the same bits.  R's first column and the per-row means' first coordinate carry the row's index, so that C and mu
+    differ strongly from row to row: the reference with two neighbouring rows swapped is outside the bound (asserted), and so is
+    a tile row stored to another output row."""
+    from bdf_amd._lib import DenseTerm, check, lib
+    c2 = B.Context(seed=SEED)
+    M, alpha = 29, 2.5
+    for N in (1, 15, 16, 17, 48, 49, 63, 64, 65, 130):
+        rng = np.random.default_rng(1000 * D + N)
+        Y = DR.table(N, M, seed=D + N)
+        R = Y - Y.mean()
+        R[:, 0] += np.arange(N)
+        V, Lam = rng.standard_normal((M, D)), _prior(rng, D)
+        mus = rng.standard_normal((N, D))
+        mus[:, 0] += np.arange(N)
+        R_t, V_t, Lam_t = c2.tensor(R), c2.tensor(V), c2.tensor(Lam)
+        C_t = _product(B, c2, R_t, N, M, D, V_t, False)
+        G_t, s_t = c2.zeros(D, D), c2.zeros(D)
+        check(lib().bdf_hyper_sums(c2.handle, D, M, _p(V_t), None, _p(s_t), _p(G_t)))
+        arr = (DenseTerm * 1)()
+        arr[0].gram, arr[0].C, arr[0].alpha, arr[0].weight = G_t.data_ptr(), C_t.data_ptr(), alpha, 1.0
+        for is_matrix in (False, True):
+            mu = mus if is_matrix else mus[0]
+            mu_t = c2.tensor(mu)
+            got = []
+            for _ in (0, 1):
+                Le_t, me_t, ar_t = c2.zeros(D, D), c2.tensor(np.full((N + 16, D), np.nan)), c2.zeros(1)
+                check(lib().bdf_dense_prior(c2.handle, D, N, 1, arr, _p(mu_t), int(is_matrix), _p(Lam_t), _p(Le_t), _p(me_t), _p(ar_t)))
+                c2.sync()
+                got.append((Le_t.cpu().numpy(), me_t.cpu().numpy(), ar_t.cpu().numpy()))
+            Le, me, ar = got[0]
+            assert np.all(np.isnan(me[N:])) and np.all(np.isfinite(me[:N])), (N, is_matrix)
+            for x, y in zip(got[0], got[1]):
+                assert np.array_equal(x, y, equal_nan=True)
+            P, b = DR.systems_dense([R], [V], [alpha], Lam, mu)
+            want = np.linalg.solve(P, b.T).T
+            kappa = np.linalg.cond(P)
+            bound = 8 * D * kappa * 2.0 ** -52
+            if N > 1:
+                swapped = want.copy()
+                swapped[[N - 2, N - 1]] = want[[N - 1, N - 2]]
+                assert np.abs(swapped - want).max() / np.abs(want).max() > bound
+            err = np.abs(me[:N] - want).max() / np.abs(want).max()
+            print(f"dense prior rows D={D} N={N} matrix mean={is_matrix}: kappa {kappa:.1f}, forward error of mu_eff {err:.2e} (bound {bound:.2e})")
+            assert np.abs(Le - P).max() <= 1e-13 * np.abs(P).max() and ar[0] == alpha
+            assert err <= bound, (N, is_matrix, err, bound)
     c2.close()
 
 

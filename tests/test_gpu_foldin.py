@@ -1,6 +1,6 @@
 """The fold-in of new rows from a few cells of their own on the GPU (setNewObserved): bdf_foldin_cells and
 bdf_newrows_update_cells through the C ABI against the numpy restatement (tests/foldin_restatement.py) and against the cold path's
-kernels, whole macau() runs against the restatement driven by the per-iteration device state on both iteration paths, the runs that
+kernels -- rows long enough for all four waves and a third trip, a V that is not 16-byte aligned -- whole macau() runs against the restatement driven by the per-iteration device state on both iteration paths, the runs that
 must not change, and the quality of the predictions against the CPU chains of the restatement's own sampler.
 
 The tolerances are section 24's: 1e-12 relative for one draw's m, q, uhat and state, 1e-9 for a whole run.  Every P_i here has
@@ -130,6 +130,120 @@ def test_cells_match_the_restatement(B, ctx, D):
         assert (np.abs(q[cold] - qc) / qc).max() <= 1e-12
     print(f"foldin cells D={D}: worst relative error of uhat {worst[0]:.2e}, m {worst[1]:.2e}, q {worst[2]:.2e} (asserted: 1e-12)")
     assert worst.max() <= 1e-12, worst
+    pairs.close()
+    rel.close()
+
+
+LONG_ROWS = [3 * BATCH - 1, 3 * BATCH, 3 * BATCH + 1, 4 * BATCH - 1, 4 * BATCH, 4 * BATCH + 1, 5 * BATCH, 5 * BATCH + 1, 0, 8 * BATCH + 1]
+
+
+def _long_rows_reach_every_wave_twice_and_a_third_trip():
+    """batch t of a row goes to wave t % 4 on its trip t // 4 (k_foldin_cells: k0 = k_begin + 64 wave, k0 += 256)"""
+    assert LONG_ROWS == [191, 192, 193, 255, 256, 257, 320, 321, 0, 513]
+    reached = {(t % 4, t // 4) for c in LONG_ROWS for t in range(-(-c // BATCH))}
+    assert reached >= {(w, trip) for w in range(4) for trip in (0, 1)} and (0, 2) in reached, sorted(reached)
+
+
+@pytest.mark.parametrize("D", [3, 16, 33, 64])
+def test_cells_of_long_rows_match_the_restatement(B, ctx, D):
+    """Ten new rows in one call.  Test cells per row: 191, 192, 193, 255, 256, 257, 320, 321, 0, 513 (one short of three full batches;
+    wave 3 idle; wave 3 with a single lane; wave 3 one lane short of full; every wave exactly one full batch; wave 0's second trip
+    with one lane; wave 0's second trip full; wave 1's second trip with one lane; an empty row between long ones; wave 0's third
+    trip).  Known cells per row: 3, 1, 4, 0 (cold), 2, 5, 3, 2, 1, 4.  M = 40, so that a row's columns repeat many times: for a fixed
+    (row, column) m and q are the same bits at every place at which the column occurs in the row -- which wave takes a cell does not
+    change what is computed for it (asserted to hold over places of different batches).  D = 3: the scalar gather; 16, 33, 64: the
+    three DP.  The shared prior mean and a mean per row; a second call gives the same bits."""
+    _long_rows_reach_every_wave_twice_and_a_third_trip()
+    rng = np.random.default_rng(4300 + D)
+    n_new, M, mean, alpha = len(LONG_ROWS), 40, 0.3, 2.0
+    n_known = [3, 1, 4, 0, 2, 5, 3, 2, 1, 4]
+    ids = np.concatenate([np.stack([np.full(c, i + 1), rng.integers(1, M + 1, c)], axis=1) for i, c in enumerate(LONG_ROWS) if c]).astype(np.int64)
+    ids = ids[rng.permutation(len(ids))]                           # the caller's order is not the storage order
+    kid = np.concatenate([np.stack([np.full(c, i + 1), rng.permutation(M)[:c] + 1], axis=1) for i, c in enumerate(n_known) if c]).astype(np.int64)
+    kid = kid[rng.permutation(len(kid))]
+    ky = rng.standard_normal(len(kid))
+    Lam, V = _spd(rng, D), 0.5 * rng.standard_normal((M, D))
+    mu, mu_rows = 0.4 * rng.standard_normal(D), 0.4 * rng.standard_normal((n_new, D))
+    rel = _known_relation(B, ctx, kid, ky, n_new, M)
+    pairs = B.DevicePairs(ctx, ids, np.zeros(len(ids)))
+    pairs.sort(0)
+    # the places of every (row, column): the first of each, and that some column of every long row recurs in another batch
+    stored = _storage_order(pairs, ids)
+    assert np.all(np.diff(stored[:, 0]) >= 0)
+    place = np.arange(len(stored)) - np.searchsorted(stored[:, 0], stored[:, 0])
+    _, first, inv = np.unique(stored, axis=0, return_index=True, return_inverse=True)
+    inv = inv.ravel()
+    moved = (place // BATCH) != (place[first[inv]] // BATCH)
+    assert set(stored[moved, 0]) == {i + 1 for i, c in enumerate(LONG_ROWS) if c}
+    Lt, Vt = ctx.tensor(Lam), ctx.tensor(V)
+    worst = np.zeros(3)
+    for is_matrix, prior in ((False, mu), (True, mu_rows)):
+        m, q, uh = _foldin(B, ctx, D, n_new, rel, Vt, ctx.tensor(prior), is_matrix, Lt, pairs, mean, alpha)
+        P, b = FR.systems(Lam, prior if is_matrix else np.tile(mu, (n_new, 1)), V, alpha, kid, ky, mean)
+        worst = np.maximum(worst, _check_cells(D, P, b, ids, V, mean, m, q, uh))
+        ms, qs = _storage_order(pairs, m), _storage_order(pairs, q)
+        same = (ms == ms[first[inv]]) & (qs == qs[first[inv]])
+        assert same.all(), ("a cell differs from the first cell of its (row, column)", stored[~same][:4], place[~same][:4])
+        m2, q2, uh2 = _foldin(B, ctx, D, n_new, rel, Vt, ctx.tensor(prior), is_matrix, Lt, pairs, mean, alpha)
+        assert np.array_equal(m, m2) and np.array_equal(q, q2) and np.array_equal(uh, uh2)
+    print(f"foldin cells of long rows D={D}: worst relative error of uhat {worst[0]:.2e}, m {worst[1]:.2e}, q {worst[2]:.2e} (asserted: 1e-12)")
+    assert worst.max() <= 1e-12, worst
+    pairs.close()
+    rel.close()
+
+
+def _offset_view(ctx, a):
+    """`a` on the device as a view that starts one double into a larger tensor -- its address is 8 mod 16 -- with NaN in the doubles
+    before and behind it"""
+    flat = np.concatenate([[np.nan], np.asarray(a, dtype=np.float64).ravel(), np.full(3, np.nan)])
+    v = ctx.tensor(flat)[1:1 + a.size].view(*a.shape)
+    assert v.data_ptr() % 16 == 8 and v.is_contiguous()
+    return v
+
+
+def _solve(ctx, D, n_new, Pt, bt, pairs, M, Vt, mean):
+    """bdf_foldin_solve -> (m, q) in the caller's order and uhat; 8 guard doubles behind each stay untouched"""
+    from bdf_amd._lib import check, lib
+    n = pairs.n
+    m, q, uh = ctx.tensor(np.full(n + 8, -7.0)), ctx.tensor(np.full(n + 8, -7.0)), ctx.tensor(np.full(n_new * D + 8, -7.0))
+    check(lib().bdf_foldin_solve(ctx.handle, D, n_new, _p(Pt), _p(bt), pairs.handle, M, _p(Vt), mean, _p(m), _p(q), _p(uh)))
+    ctx.sync()
+    m, q, uh = m.cpu().numpy(), q.cpu().numpy(), uh.cpu().numpy()
+    assert np.array_equal(m[n:], np.full(8, -7.0)) and np.array_equal(q[n:], np.full(8, -7.0)) and np.array_equal(uh[n_new * D:], np.full(8, -7.0))
+    return _caller_order(pairs, m[:n]), _caller_order(pairs, q[:n]), uh[:n_new * D].reshape(n_new, D)
+
+
+@pytest.mark.parametrize("D", [16, 32, 64])
+def test_a_v_that_is_not_16_byte_aligned_takes_the_scalar_gather(B, ctx, D):
+    """an even D gathers a row of V by 16-byte loads only when V is 16-byte aligned (FoldinArgs::wide).  The same values from an aligned
+    tensor and from a view that starts one double into a larger one give m, q and uhat bit for bit -- both gathers load the same
+    doubles into the same registers -- through bdf_foldin_cells and through bdf_foldin_solve, and both match the restatement.  NaN
+    stands before and behind the view: a 16-byte load that started a double early or ran one late would show.  Three rows of 65, 3
+    and 0 test cells, among them the first and the last row of V"""
+    rng = np.random.default_rng(4400 + D)
+    n_new, M, mean, alpha = 3, 20, 0.3, 2.0
+    n_test, n_known = [BATCH + 1, 3, 0], [3, 0, D + 3 if D + 3 <= M else M]
+    ids = np.concatenate([np.stack([np.full(c, i + 1), rng.integers(1, M + 1, c)], axis=1) for i, c in enumerate(n_test) if c]).astype(np.int64)
+    ids[:2, 1], ids[-3:, 1] = [1, M], [M, 1, 7]
+    ids = ids[rng.permutation(len(ids))]
+    kid = np.concatenate([np.stack([np.full(c, i + 1), rng.permutation(M)[:c] + 1], axis=1) for i, c in enumerate(n_known) if c]).astype(np.int64)
+    ky = rng.standard_normal(len(kid))
+    Lam, V, mu = _spd(rng, D), 0.5 * rng.standard_normal((M, D)), 0.4 * rng.standard_normal(D)
+    rel = _known_relation(B, ctx, kid, ky, n_new, M)
+    pairs = B.DevicePairs(ctx, ids, np.zeros(len(ids)))
+    pairs.sort(0)
+    Lt, mt = ctx.tensor(Lam), ctx.tensor(mu)
+    V_al, V_off = ctx.tensor(V), _offset_view(ctx, V)
+    assert V_al.data_ptr() % 16 == 0
+    P, b = FR.systems(Lam, np.tile(mu, (n_new, 1)), V, alpha, kid, ky, mean)
+    Pt, bt = ctx.tensor(P), ctx.tensor(b)
+    for name, run in (("bdf_foldin_cells", lambda Vt: _foldin(B, ctx, D, n_new, rel, Vt, mt, False, Lt, pairs, mean, alpha)),
+                      ("bdf_foldin_solve", lambda Vt: _solve(ctx, D, n_new, Pt, bt, pairs, M, Vt, mean))):
+        wide, narrow = run(V_al), run(V_off)
+        for x, y, what in zip(wide, narrow, ("m", "q", "uhat")):
+            assert np.all(np.isfinite(y)) and np.array_equal(x, y), (name, what)
+        assert max(_check_cells(D, P, b, ids, V, mean, *narrow)) <= 1e-12, name
+        assert max(_check_cells(D, P, b, ids, V, mean, *wide)) <= 1e-12, name
     pairs.close()
     rel.close()
 

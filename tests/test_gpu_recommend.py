@@ -1,6 +1,7 @@
 """Top-K lists from the posterior mean score (setRecommend) on the device against tests/recommend_restatement.py:
 the accumulate kernel at the edges of its tile, bit-identical over the batch size and over a row subset, and past 65,535 tiles; the
-lists and the metrics exactly; macau() end to end on both iteration paths; and the planted implicit data of section 20 ranked."""
+lists and the metrics exactly, the lists also over three windows of listed columns; the second trip of the grid-stride loops of
+the list, metrics and push kernels; macau() end to end on both iteration paths; and the planted implicit data of section 20 ranked."""
 import os
 import textwrap
 
@@ -143,6 +144,214 @@ def test_topk_lists_equal_the_restatement_exactly(B, ctx, M, K):
                 assert np.count_nonzero(gi[1]) == min(K, M)
         sc.close()
     dr.close()
+
+
+# ---- the lists past one window of listed columns -----------------------------------------------------------------------------------
+WINDOW = 65536                                               # columns k_topk_rows marks in LDS at a time (csrc/recommend.h: BDF_REC_WINDOW)
+M_WIN = 2 * WINDOW + 3                                       # three windows, the last of 3 columns
+SUBSET = np.array([6, 1, 5, 0, 3, 4, 2])
+
+
+def _plan_b():
+    """row b's best entries, best first, as (window or column, sum in eighths): windows 0 and 1 in turn; exact ties between a column
+    of window 0 and one of window 1 at the places 1 | 2 and 5 | 6, so that for K = 1 and K = 5 the candidate of the later window ties
+    the K-th entry and is refused; a tie between window 1 and window 2 at the places 8 | 9; and place 64 (window 0) tied by a column
+    of window 1 and by one of window 2"""
+    plan = [("a", 500), ("b", 500), ("a", 499), ("b", 498), ("a", 497), ("b", 497), ("a", 496), ("b", 495), (2 * WINDOW, 495)]
+    while len(plan) < 64:
+        plan.append(("a" if len(plan) % 2 else "b", 494 - (len(plan) - 9)))
+    assert plan[63] == ("a", 440)
+    return plan + [("b", 440), (2 * WINDOW + 2, 440), ("a", 439), ("b", 438)]
+
+
+def _window_case(B):
+    """8 rows over M = 2 x 65536 + 3 columns, sums in eighths.  Rows a .. f stand on a floor of sums <= 0 with what matters planted
+    above it; a: the 64 best in windows 1 and 2 only; b: _plan_b; c: the best columns all listed, in windows 1 and 2, the window
+    edges among them; d: the aliasing pairs (c listed and low, c + 65536 not listed and best; c' not listed, c' + 65536 listed and
+    best; the same against window 2); e: every column of windows 0 and 1 listed, and one of window 2; f: nothing listed; g, h: a random
+    third listed over uniform sums, as _topk_case.  The references (RR.topk at K = 64: a shorter list is its prefix) are made once."""
+    rng = np.random.default_rng(4242)
+    M, W = M_WIN, WINDOW
+    sums = rng.integers(-6, 1, (8, M)) / 8.0
+    on = np.zeros((8, M), dtype=bool)
+
+    def pick(lo, hi, n, avoid=()):
+        return rng.permutation(np.setdiff1d(np.arange(lo, hi), np.asarray(sorted(avoid), dtype=np.int64)))[:n]
+
+    # a
+    sums[0, pick(W, 2 * W, 70)] = rng.integers(1, 6, 70) / 8.0
+    sums[0, 2 * W:] = np.array([7, 3, 6]) / 8.0
+    on[0, pick(0, W, 50)] = True
+    # b
+    cols = {"a": list(pick(0, W, 40)), "b": list(pick(W, 2 * W, 40))}
+    planned_b = np.array([cols[w].pop() if isinstance(w, str) else w for w, _ in _plan_b()], dtype=np.int64)
+    sums[1, planned_b] = np.array([v for _, v in _plan_b()]) / 8.0
+    on[1, pick(0, M, 100, avoid=planned_b)] = True
+    # c
+    edges = [W - 1, W, W + 1, 2 * W - 1, 2 * W, M - 1]
+    listed_c = np.concatenate([edges, pick(W + 2, 2 * W - 1, 70)])
+    sums[2, listed_c] = rng.integers(700, 800, len(listed_c)) / 8.0
+    sums[2, [W, 2 * W, M - 1]] = 900 / 8.0                   # the row's maximum, three times, all listed
+    on[2, listed_c] = True
+    free = np.concatenate([pick(0, W - 1, 40), pick(W + 2, 2 * W - 1, 40, avoid=listed_c)])
+    sums[2, free] = rng.integers(100, 400, 80) / 8.0
+    sums[2, 2 * W + 1] = 450 / 8.0
+    # d
+    c1, c2 = 1234, 4321
+    on[3, [c1, c2 + W, 1, 2 * W + 2]] = True
+    sums[3, [c1, c1 + W, c2, c2 + W, 1, 2 * W + 1, 2, 2 * W + 2]] = np.array([-50, 1000, 300, 1001, -40, 999, 250, 1002]) / 8.0
+    free = np.concatenate([pick(3, W, 40, avoid=[c1, c2]), pick(W, 2 * W, 40, avoid=[c1 + W, c2 + W])])
+    sums[3, free] = rng.integers(100, 249, 80) / 8.0
+    # e
+    on[4, :2 * W] = True
+    on[4, 2 * W + 1] = True
+    sums[4, 2 * W:] = np.array([3, 7, 3]) / 8.0
+    # f
+    sums[5, np.concatenate([pick(0, W, 30), pick(W, 2 * W, 30)])] = rng.integers(1, 7, 60) / 8.0
+    sums[5, 2 * W:] = np.array([6, 6, 5]) / 8.0
+    # g, h
+    sums[6:] = rng.integers(-6, 7, (2, M)) / 8.0
+    on[6:] = rng.random((2, M)) < 0.33
+    i, j = np.nonzero(on)
+    p = rng.permutation(len(i))
+    ids = np.stack([i[p] + 1, j[p] + 1], axis=1).astype(np.int64)
+    assert 200_000 <= len(ids) <= 400_000
+    rel = B.Relation({"u": ids[:, 0], "v": ids[:, 1], "y": np.ones(len(ids))}, "plays", [B.Entity("u"), B.Entity("v")], dims=[8, M])
+    listed = RR.listed_of(ids, 8)
+    scores = RR.scores_of(sums, 4.0, 0.5)
+    ref = {}
+    for sub in (False, True):
+        rows = SUBSET if sub else np.arange(8)
+        ref[sub, True] = RR.topk(scores[rows], 64, [listed[r] for r in rows])
+        ref[sub, False] = RR.topk(scores[rows], 64)
+    return dict(sums=sums, ids=ids, rel=rel, ref=ref, planned_b=planned_b)
+
+
+@pytest.fixture(scope="module")
+def window_case(B):
+    return _window_case(B)
+
+
+@pytest.mark.parametrize("K", [1, 5, 64])
+def test_topk_lists_past_one_window_equal_the_restatement_exactly(B, ctx, window_case, K):
+    """k_topk_rows over three windows of listed columns: the mask is zeroed again and filled relative to the window's first column,
+    and the sorted list and its count pass from one window to the next.  Sums in eighths over four draws: every score is exact, and
+    the lists equal RR.topk's to the bit, for all rows and for a permuted subset, the listed cells left out and kept."""
+    from bdf_amd.engine import DeviceRelation, DeviceScores
+    text = open(os.path.join(ROOT, "bayesiandatafusion.jl_amd", "csrc", "recommend.h")).read()
+    assert "#define BDF_REC_WINDOW %d\n" % WINDOW in text
+    sums, ref, planned_b = window_case["sums"], window_case["ref"], window_case["planned_b"]
+    # on the CPU, before any launch: the reference lists themselves reach past window 0
+    for exclude in (True, False):
+        ei = ref[False, exclude][0][:, :K]
+        wins = [set(int(w) for w in (ei[r][ei[r] > 0] - 1) // WINDOW) for r in range(4)]
+        if K > 1:
+            assert all(len(w) >= 2 for w in wins), (exclude, wins)       # each of the rows a .. d: entries of at least two windows
+        else:                                                # (a list of one entry: the four rows' entries together, and row a's not in window 0)
+            assert len(set.union(*wins)) >= 2 and wins[0] <= {1, 2}, (exclude, wins)
+        assert np.array_equal(ei[1], planned_b[:K] + 1)      # row b: the plan itself, the smaller id first and the later tie refused
+    for r in (2, 3):                                         # rows c and d: leaving the listed cells out changes the list
+        assert not np.array_equal(ref[False, True][0][r, :K], ref[False, False][0][r, :K])
+    assert np.count_nonzero(ref[False, True][0][4]) == 2     # row e: two candidates, both in window 2
+    dr = DeviceRelation(ctx, window_case["rel"].data)
+    draws, mean = 4.0, 0.5
+    for sub, rows0 in ((False, None), (True, SUBSET)):
+        n = 8 if rows0 is None else len(rows0)
+        sc = DeviceScores(ctx, n, M_WIN, 3, 1, rows0)
+        sc.write(ctx.tensor(sums if rows0 is None else sums[rows0]), draws)
+        for exclude in (True, False):
+            items, vals = sc.topk(K, mean, dr if exclude else None)
+            ctx.sync()
+            ei, ev = ref[sub, exclude][0][:, :K], ref[sub, exclude][1][:, :K]
+            gi, gv = items.cpu().numpy(), vals.cpu().numpy()
+            bad = [int(r) for r in np.nonzero((gi != ei).any(axis=1))[0]]
+            assert gi.dtype == np.int32 and not bad, (sub, exclude, bad, gi[bad[0]][:8], ei[bad[0]][:8])
+            assert np.array_equal(gv, ev, equal_nan=True)
+            assert np.array_equal(gi == 0, np.isnan(gv))
+            if exclude and rows0 is None:
+                assert np.count_nonzero(gi[4]) == min(K, 2) and np.count_nonzero(gi[5]) == K
+        sc.close()
+    dr.close()
+
+
+# ---- the grid-stride loops ------------------------------------------------------------------------------------------------------------
+GRID_ROWS = 1 << 20                                          # rows that k_topk_rows and k_rec_metrics launch a workgroup for at most
+GRID_PUSH = 65536                                            # workgroups of 256 quads that k_scores_push launches at most
+
+
+def test_topk_and_metrics_past_the_row_grid(ctx):
+    """2^20 + 3 rows of 3 columns, K = 2, nothing listed: the last three rows are the second trip of either kernel's row loop.  Sums in
+    eighths with many ties; the lists against a stable sort of the negated scores (falling score, ties by rising column), which is
+    itself held to RR.topk on the first 64 and the last 67 rows; the metrics of those lists on a few hundred relevant cells, three of
+    them in the last three rows, against RR.metrics to 1e-12, the count of rows scored exactly."""
+    import torch
+    from bdf_amd.engine import DevicePairs, DeviceScores
+    n, M, K, cut = GRID_ROWS + 3, 3, 2, 0.5
+    rng = np.random.default_rng(31)
+    sums = rng.integers(-2, 3, (n, M)) / 8.0
+    draws, mean = 4.0, 0.5
+    scores = RR.scores_of(sums, draws, mean)
+    order = np.argsort(-scores, axis=1, kind="stable")[:, :K]
+    ei, ev = (order + 1).astype(np.int32), np.take_along_axis(scores, order, axis=1)
+    for part in (slice(0, 64), slice(n - 67, n)):
+        ri, rv = RR.topk(scores[part], K)
+        assert np.array_equal(ei[part], ri) and np.array_equal(ev[part], rv)
+    assert np.count_nonzero(scores[:, 0] == scores[:, 1]) > n // 10
+    sc = DeviceScores(ctx, n, M, 3, 1)
+    sc.write(ctx.tensor(sums), draws)
+    items, vals = sc.topk(K, mean)
+    ctx.sync()
+    gi, gv = items.cpu().numpy(), vals.cpu().numpy()
+    assert np.array_equal(gi[:GRID_ROWS], ei[:GRID_ROWS]) and np.array_equal(gv[:GRID_ROWS], ev[:GRID_ROWS]), "the first trip: rows 0 .. 2^20 - 1"
+    assert np.array_equal(gi[GRID_ROWS:], ei[GRID_ROWS:]) and np.array_equal(gv[GRID_ROWS:], ev[GRID_ROWS:]), \
+        ("the second trip of k_topk_rows' row loop: the last three rows", gi[GRID_ROWS:], ei[GRID_ROWS:])
+    # the metrics: 300 rows somewhere and the last three with test cells, the relevant ones partly in the lists
+    rows = np.concatenate([rng.permutation(GRID_ROWS)[:300], np.arange(GRID_ROWS, n)])
+    cells = []
+    for q, r in enumerate(rows):
+        if q % 9 == 4 and q < 300:
+            cells.append((r + 1, int(ei[r, 0]), 0.0))         # a held-out cell below the cut alone: the row is not scored
+            continue
+        cells.append((r + 1, int(ei[r, q % 2]), 1.0))         # a hit at place 1 or 2
+        if q % 3 == 0:
+            cells.append((r + 1, 6 - int(ei[r, 0]) - int(ei[r, 1]), 1.0))      # and the column that is not in the list
+    cells =[cells[q] for q in rng.permutation(len(cells))]
+    ids, tv = np.array([c[:2] for c in cells], dtype=np.int64), np.array([c[2] for c in cells])
+    pairs = DevicePairs(ctx, ids, tv)
+    out = sc.metrics(items, K, pairs, cut)
+    ctx.sync()
+    # (rows without a relevant cell are left out by the definition: the restatement is run on the rows that have a test cell)
+    has = np.unique(ids[:, 0] - 1)
+    exp = RR.metrics(gi[has], RR.relevant_of(ids, tv, cut, len(has), has))
+    got = out.cpu().numpy()
+    print(f"metrics over {n} rows: device {got}, restatement {exp}")
+    assert got[3] == exp[3] and exp[3] >= 250, "rows scored (the last three rows are the second trip of k_rec_metrics' row loop)"
+    assert np.all(np.abs(got[:3] - np.array(exp[:3])) <= 1e-12)
+    assert 0.0 < exp[0] < 1.0 and 0.0 < exp[1] < 1.0
+    assert items.dtype == torch.int32
+    sc.close()
+    pairs.close()
+
+
+def test_push_past_65536_workgroups(ctx):
+    """one row against 2^20 + 1 columns at D = 64: 16 x (2^20 + 2) quads, 32 more than 65,536 workgroups of 256 take in one trip -- the
+    last block of four d of the last 32 columns is the second trip of k_scores_push's loop.  Two draws through a ring of one slot
+    (the second draw has the first one's V: half the host's work)"""
+    n_rows, D, M = 1, 64, GRID_ROWS + 1
+    quads = (n_rows + M) * ((D + 3) // 4)
+    assert GRID_PUSH * 256 < quads <= 2 * GRID_PUSH * 256
+    rng = np.random.default_rng(13)
+    V = rng.standard_normal((M, D))
+    draws = [(rng.standard_normal((n_rows, D)), V) for _ in range(2)]
+    Vd = _guarded(ctx, V)
+    dev = [(_guarded(ctx, U), Vd) for U, _ in draws]
+    got, guard = _accumulate(ctx, dev, n_rows, M, D, 1)
+    exp, mag = RR.score_sum(draws)
+    assert np.isnan(guard).all() and not np.isnan(got).any()
+    err = np.abs(got - exp) / mag
+    print(f"push past {GRID_PUSH} workgroups: largest |device - restatement| / sum|terms| = {err.max():.2e}, over the last 32 columns {err[0, -32:].max():.2e}")
+    assert err.max() <= ACC_TOL, int(np.argmax(err))
+    assert got[0, -1] != 0.0 and got[0, 1 << 20] != 0.0
 
 
 def test_topk_without_draws_has_no_candidates(ctx):
