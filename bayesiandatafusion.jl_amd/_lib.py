@@ -227,6 +227,14 @@ _SIGS = {
     "bdf_scores_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_double, C.c_void_p]),
     "bdf_scores_copy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
     "bdf_scores_set_draws": (C.c_int, [C.c_void_p, C.c_double]),
+    "bdf_acquire_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                     C.POINTER(C.c_void_p)]),
+    "bdf_acquire_destroy": (C.c_int, [C.c_void_p]),
+    "bdf_acquire_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p]),
+    "bdf_acquire_flush": (C.c_int, [C.c_void_p]),
+    "bdf_acquire_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bdf_acquire_copy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
+    "bdf_acquire_set_draws": (C.c_int, [C.c_void_p, C.c_double]),
     "bdf_ordinal_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]),
     "bdf_ordinal_destroy": (C.c_int, [C.c_void_p]),
     "bdf_ordinal_set_adapt": (C.c_int, [C.c_void_p, C.c_int64]),

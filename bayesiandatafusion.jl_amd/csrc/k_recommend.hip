@@ -320,18 +320,25 @@ extern "C" int bdf_scores_flush(bdf_scores *sc)
     return BDF_OK;
 }
 
+int bdf_ring_push(bdf_ctx *ctx, const double *U, const double *V, const int32_t *rows_dev, int64_t n_rows, int64_t M, int D, int nblk, double *slot)
+{
+    const int64_t quads = (n_rows + M) * nblk;
+    if (quads > 0) {
+        const dim3 grid((unsigned)std::min<int64_t>((quads + 255) / 256, 65536));
+        hipLaunchKernelGGL(k_scores_push, grid, dim3(256), 0, ctx->stream, U, V, rows_dev, n_rows, M, D, nblk, slot);
+        BDF_HIP(hipGetLastError());
+    }
+    return BDF_OK;
+}
+
 extern "C" int bdf_scores_push(bdf_scores *sc, const double *U, const double *V)
 {
     BDF_REQUIRE(sc && U && V, BDF_ERR_ARG, "bdf_scores_push: NULL argument");
     bdf_ctx *ctx = sc->ctx;
     BDF_HIP(hipSetDevice(ctx->device));
     const int64_t quads = (sc->n_rows + sc->M) * sc->nblk;
-    if (quads > 0) {
-        double *slot = sc->ring_dev + (int64_t)sc->held * quads * 4;
-        const dim3 grid((unsigned)std::min<int64_t>((quads + 255) / 256, 65536));
-        hipLaunchKernelGGL(k_scores_push, grid, dim3(256), 0, ctx->stream, U, V, (const int32_t *)sc->rows_dev, sc->n_rows, sc->M, sc->D, sc->nblk, slot);
-        BDF_HIP(hipGetLastError());
-    }
+    const int rc = bdf_ring_push(ctx, U, V, sc->rows_dev, sc->n_rows, sc->M, sc->D, sc->nblk, sc->ring_dev + (int64_t)sc->held * quads * 4);
+    if (rc) return rc;
     sc->held++;
     sc->draws += 1.0;
     return sc->held == sc->batch ? bdf_scores_flush(sc) : BDF_OK;
@@ -359,35 +366,42 @@ extern "C" int bdf_scores_set_draws(bdf_scores *sc, double draws)
     return BDF_OK;
 }
 
+int bdf_topk_plane(bdf_ctx *ctx, const char *who, const double *plane, int64_t n_rows, int64_t M, const int32_t *rows_dev,
+                   const std::vector<int32_t> &rows_host, const bdf_rel *rel, int K, double draws, double mean_value, int32_t *items_out,
+                   double *scores_out)
+{
+    BDF_REQUIRE(K >= 1 && K <= BDF_REC_MAX_K, BDF_ERR_ARG, "%s: K=%d must be in 1..%d", who, K, BDF_REC_MAX_K);
+    const int64_t *rowptr = nullptr;
+    const int32_t *colidx = nullptr;
+    if (rel) {
+        BDF_REQUIRE(rel->n_modes == 2 && !rel->sharded, BDF_ERR_ARG, "%s: the listed cells come from a two-mode relation on one rank", who);
+        BDF_REQUIRE(rel->dims[1] == M, BDF_ERR_ARG, "%s: the relation has %lld columns, the scores %lld", who, (long long)rel->dims[1], (long long)M);
+        const int64_t N = rel->dims[0];
+        if (rows_dev) {
+            for (int64_t r = 0; r < n_rows; r++)
+                BDF_REQUIRE(rows_host[(size_t)r] < N, BDF_ERR_BOUNDS, "%s: rows[%lld] = %d is outside the relation's %lld rows", who, (long long)r,
+                            rows_host[(size_t)r], (long long)N);
+        } else {
+            BDF_REQUIRE(n_rows <= N, BDF_ERR_ARG, "%s: %lld scored rows, the relation has %lld", who, (long long)n_rows, (long long)N);
+        }
+        rowptr = rel->idx[0].rowptr_dev; colidx = rel->idx[0].colidx_dev;
+    }
+    if (n_rows == 0) return BDF_OK;
+    BDF_HIP(hipSetDevice(ctx->device));
+    const dim3 grid((unsigned)std::min<int64_t>(n_rows, 1 << 20));
+    hipLaunchKernelGGL(k_topk_rows, grid, dim3(64), 0, ctx->stream, plane, n_rows, M, rows_dev, rowptr, colidx, K, draws, mean_value, items_out, scores_out);
+    BDF_HIP(hipGetLastError());
+    return BDF_OK;
+}
+
 extern "C" int bdf_scores_topk(bdf_scores *sc, const bdf_rel *rel, int K, double mean_value, int32_t *items_out, double *scores_out)
 {
     BDF_REQUIRE(sc && items_out && scores_out, BDF_ERR_ARG, "bdf_scores_topk: NULL argument");
     BDF_REQUIRE(K >= 1 && K <= BDF_REC_MAX_K, BDF_ERR_ARG, "bdf_scores_topk: K=%d must be in 1..%d", K, BDF_REC_MAX_K);
-    const int64_t *rowptr = nullptr;
-    const int32_t *colidx = nullptr;
-    if (rel) {
-        BDF_REQUIRE(rel->n_modes == 2 && !rel->sharded, BDF_ERR_ARG, "bdf_scores_topk: the listed cells come from a two-mode relation on one rank");
-        BDF_REQUIRE(rel->dims[1] == sc->M, BDF_ERR_ARG, "bdf_scores_topk: the relation has %lld columns, the scores %lld", (long long)rel->dims[1], (long long)sc->M);
-        const int64_t N = rel->dims[0];
-        if (sc->rows_dev) {
-            for (int64_t r = 0; r < sc->n_rows; r++)
-                BDF_REQUIRE(sc->rows_host[(size_t)r] < N, BDF_ERR_BOUNDS, "bdf_scores_topk: rows[%lld] = %d is outside the relation's %lld rows", (long long)r,
-                            sc->rows_host[(size_t)r], (long long)N);
-        } else {
-            BDF_REQUIRE(sc->n_rows <= N, BDF_ERR_ARG, "bdf_scores_topk: %lld scored rows, the relation has %lld", (long long)sc->n_rows, (long long)N);
-        }
-        rowptr = rel->idx[0].rowptr_dev; colidx = rel->idx[0].colidx_dev;
-    }
-    int rc = bdf_scores_flush(sc);
+    const int rc = bdf_scores_flush(sc);
     if (rc) return rc;
-    if (sc->n_rows == 0) return BDF_OK;
-    bdf_ctx *ctx = sc->ctx;
-    BDF_HIP(hipSetDevice(ctx->device));
-    const dim3 grid((unsigned)std::min<int64_t>(sc->n_rows, 1 << 20));
-    hipLaunchKernelGGL(k_topk_rows, grid, dim3(64), 0, ctx->stream, (const double *)sc->sum_dev, sc->n_rows, sc->M, (const int32_t *)sc->rows_dev, rowptr, colidx, K,
-                       sc->draws, mean_value, items_out, scores_out);
-    BDF_HIP(hipGetLastError());
-    return BDF_OK;
+    return bdf_topk_plane(sc->ctx, "bdf_scores_topk", sc->sum_dev, sc->n_rows, sc->M, sc->rows_dev, sc->rows_host, rel, K, sc->draws, mean_value,
+                          items_out, scores_out);
 }
 
 extern "C" int bdf_scores_metrics(bdf_scores *sc, const int32_t *items, int K, const bdf_pairs *test, double class_cut, double *out)

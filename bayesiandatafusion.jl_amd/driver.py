@@ -77,6 +77,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         if r.model.recommend is not None:
             raise ArgumentError(f"Relation {r.name} asks for top-k lists (setRecommend) but is not the first relation: macau() keeps the sum of scores for the first relation only.")
     recommend = data.relations[0].model.recommend if data.relations else None
+    # acquisition lists (setAcquire) likewise
+    for r in data.relations[1:]:
+        if r.model.acquire is not None:
+            raise ArgumentError(f"Relation {r.name} asks for acquisition lists (setAcquire) but is not the first relation: macau() keeps the moments of scores for the first relation only.")
+    acquire = data.relations[0].model.acquire if data.relations else None
 
     # WAIC on the training cells (setWaic on the first relation)
     waic = data.relations[0].model.waic if data.relations else None
@@ -97,6 +102,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     data._engine = eng
     if eng is engine and (recommend is not None or eng.scores is not None):
         eng.begin_scores()                                   # (an engine that is reused starts the sum of scores again)
+    if eng is engine and (acquire is not None or eng.acquire is not None):
+        eng.begin_acquire()                                  # (... and the moment planes)
     if robust is not None:
         eng.rel[0].omega_sum = None                          # (an engine that is reused starts the posterior mean of omega again)
     if noise is not None:
@@ -183,6 +190,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
             yhat_full += eng.pred_all(rel)                    # macau.jl:145-147: a plain dense product, on the device
         if recommend is not None and i > burnin:
             eng.scores.push(facs[0], facs[1])                 # this draw's factors into the ring, on the row stream (a full ring: one accumulate launch)
+        if acquire is not None and i > burnin:
+            # this draw's factors and its precision into the ring, on the row stream; a sampled alpha is the device scalar of the native
+            # iteration, drawn on this stream, and step by step the double the host has read from it
+            rm = rel.model
+            eng.acquire.push(facs[0], facs[1], rel._dev.alpha_dev if (rm.alpha_sample and eng.native) else rm.alpha)
         if robust is not None and i > burnin:
             eng.robust_accumulate()                           # this iteration's omega into its running sum, on the row stream
         if noise is not None and i > burnin:
@@ -294,6 +306,10 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         K = recommend["k"]
         items, scores = eng.scores.topk(K, rel.model.mean_value, rel._dev if recommend["exclude_listed"] else None)
         rec_dev = (items, scores, eng.scores.metrics(items, K, test, rel.class_cut) if haveTest else None)
+    acq_dev = None
+    if acquire is not None:
+        # the lists with the moments at their items, gathered on the device: n_rows x K values of each are all that is read back
+        acq_dev = eng.acquire.topk(acquire["k"], acquire["rule"], acquire["kappa"], rel._dev if acquire["exclude_listed"] else None)
     eng.sync()
     eng.sync_host_scalars()
     result = {
@@ -355,6 +371,11 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         if rec_dev[2] is not None:
             m = rec_dev[2].cpu().numpy()
             result["recommend"].update({"recall": float(m[0]), "ndcg": float(m[1]), "hit_rate": float(m[2]), "rows_scored": int(m[3])})
+    if acquire is not None:
+        rows = acquire["rows"]
+        result["acquire"] = {"k": acquire["k"], "rule": acquire["rule"], "kappa": acquire["kappa"], "threshold": acquire["threshold"],
+                             "rows": np.arange(1, int(rel.data.dims[0]) + 1) if rows is None else np.array(rows, dtype=np.int64)}
+        result["acquire"].update({k: v.cpu().numpy() for k, v in acq_dev.items()})
     if newr is not None:
         # the cells' (pred, stdev, lpd) in the caller's order and the posterior mean of the new rows' factors: all that comes back
         import pandas as pd

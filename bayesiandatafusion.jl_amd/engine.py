@@ -566,6 +566,75 @@ class DeviceScores:
             pass
 
 
+ACQUIRE_RULES = {"ucb": 0, "sd": 1, "prob_above": 2}        # BDF_ACQ_UCB, _SD, _PROB (csrc/acquire.h)
+ACQUIRE_PLANES = {"mean": 0, "M2": 1, "psum": 2, "score": 3}
+
+
+class DeviceAcquire:
+    """bdf_acquire: the running mean and sum of squared deviations of u.v over the posterior draws for the scored rows of a two-mode
+    relation's first entity against all M rows of its second and, with a threshold, the sum of the draws' exceedance probabilities
+    (n_rows x M doubles each on the device), a ring of draws that are not in the planes yet, and the top-K lists by an acquisition
+    score from them (setAcquire; csrc/k_acquire.hip).  Everything runs on ctx's stream."""
+
+    def __init__(self, ctx, n_rows, M, D, batch, rows0=None, mean_value=0.0, threshold=None):
+        """rows0: None, the rows 0 .. n_rows - 1 of U; else the 0-based row of U of every scored row.  threshold: None keeps no
+        psum plane"""
+        self.ctx = ctx
+        self.handle = C.c_void_p()
+        self.n_rows, self.M, self.D, self.batch = int(n_rows), int(M), int(D), int(batch)
+        self.want_prob = threshold is not None
+        rows = ctx.tensor(np.asarray(rows0, dtype=np.int32), dtype=torch.int32) if rows0 is not None else None
+        check(lib().bdf_acquire_create(ctx.handle, self.n_rows, self.M, self.D, self.batch, _ptr(rows), int(self.want_prob), float(mean_value),
+                                       float(threshold) if self.want_prob else 0.0, C.byref(self.handle)))
+        ctx.adopt(self)
+
+    def push(self, U, V, alpha):
+        """this draw's factors (N x D and M x D tensors) and its precision into the ring; alpha: a float, or a device tensor of
+        one double that only the device reads.  A full ring is folded into the planes (bdf_acquire_push)"""
+        on_dev = torch.is_tensor(alpha)
+        check(lib().bdf_acquire_push(self.handle, _ptr(U), _ptr(V), 1.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None))
+
+    def flush(self):
+        check(lib().bdf_acquire_flush(self.handle))
+
+    def topk(self, K, rule, kappa=0.0, rel=None):
+        """{"items" (int32 n_rows x K, 1-based and 0 behind the last candidate), "scores", "mean", "sd" and, with a psum plane,
+        "prob" (float64, NaN there)} on the device; rel: the DeviceRelation whose listed cells are left out of every row's list"""
+        K = int(K)
+        out = {"items": self.ctx.zeros(self.n_rows, K, dtype=torch.int32)}
+        for k in ("scores", "mean", "sd") + (("prob",) if self.want_prob else ()):
+            out[k] = self.ctx.zeros(self.n_rows, K)
+        check(lib().bdf_acquire_topk(self.handle, rel.handle if rel is not None else None, K, ACQUIRE_RULES[rule], float(kappa), _ptr(out["items"]),
+                                     _ptr(out["scores"]), _ptr(out["mean"]), _ptr(out["sd"]), _ptr(out.get("prob"))))
+        return out
+
+    def read(self, plane, first=0, count=None):
+        """parity hook: `count` doubles of plane "mean", "M2", "psum" or "score" from cell `first` (behind the n_rows M cells: 64
+        guard doubles), flushed first"""
+        count = self.n_rows * self.M - first if count is None else int(count)
+        out = self.ctx.zeros(count)
+        check(lib().bdf_acquire_copy(self.handle, ACQUIRE_PLANES[plane], _ptr(out), int(first), count, 0))
+        return out
+
+    def write(self, planes, draws):
+        """parity hook: the cells of the planes {name: device tensor}, and the count of draws they stand for"""
+        for name, values in planes.items():
+            check(lib().bdf_acquire_copy(self.handle, ACQUIRE_PLANES[name], _ptr(values), 0, int(values.numel()), 1))
+        check(lib().bdf_acquire_set_draws(self.handle, float(draws)))
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:
+                lib().bdf_acquire_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceNewRows:
     """Cells of rows that were not in training (setNewRows / setNewTest; csrc/k_newrows.hip): the operator of
     the new rows' features, their cells as pairs whose first mode indexes the new rows, and the buffers of the three launches that
@@ -1183,6 +1252,8 @@ class GibbsEngine:
                     self.ent[self._entity_index(e)].background_buffers(dense=dr.dense is not None)
         self.scores = None
         self.begin_scores()
+        self.acquire = None
+        self.begin_acquire()
         self._test_pairs = None
         self._train_pairs = None
         self._new_rows = None
@@ -1436,6 +1507,18 @@ class GibbsEngine:
             r0, rows = self.data.relations[0], rec["rows"]
             self.scores = DeviceScores(self.ctx, int(r0.data.dims[0]) if rows is None else len(rows), int(r0.data.dims[1]), self.D, rec["batch"],
                                        None if rows is None else np.asarray(rows, dtype=np.int64) - 1)
+
+    def begin_acquire(self):
+        """acquisition lists of the first relation (setAcquire): the moment planes of u.v over the draws for the
+        scored rows, zeroed -- at set-up, and again when macau() continues on an engine it was handed"""
+        if self.acquire is not None:
+            self.acquire.close()
+            self.acquire = None
+        acq = self.data.relations[0].model.acquire if self.data.relations else None
+        if acq is not None:
+            r0, rows = self.data.relations[0], acq["rows"]
+            self.acquire = DeviceAcquire(self.ctx, int(r0.data.dims[0]) if rows is None else len(rows), int(r0.data.dims[1]), self.D, acq["batch"],
+                                         None if rows is None else np.asarray(rows, dtype=np.int64) - 1, r0.model.mean_value, acq["threshold"])
 
     def robust_accumulate(self, ri=0):
         """(robust relation ri, after the burn-in) this iteration's omega into the running sum, on the row stream: behind the draw
@@ -1906,7 +1989,7 @@ class GibbsEngine:
             self.sync()
         except Exception:
             pass
-        for p in (self._test_pairs, self._train_pairs, self.scores, self._new_rows):
+        for p in (self._test_pairs, self._train_pairs, self.scores, self.acquire, self._new_rows):
             if p is not None:
                 p.close()
         for st in self.ent:

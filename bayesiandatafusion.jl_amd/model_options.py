@@ -52,6 +52,8 @@ OPTIONS = (
            "a background"),
     Option("recommend", RELATION, "recommend", lambda r: r.model.recommend is not None, "top-k lists (setRecommend)", "keeps no sum of scores over draws",
            True),
+    Option("acquire", RELATION, "acquire", lambda r: r.model.acquire is not None, "acquisition lists (setAcquire)",
+           "keeps no moments of scores over draws", True),
     Option("bias", RELATION, "bias", lambda r: bool(r.model.bias), "biases (setBias)", "models a cell as mean + u.v", True),
     Option("new_test", RELATION, "new_test", lambda r: r.model.new_test is not None, "cells of new rows (setNewTest)", None, True),
     Option("new_observed", RELATION, "new_observed", lambda r: r.model.new_observed is not None, "known cells of new rows (setNewObserved)", None, True),
@@ -87,7 +89,7 @@ _OMEGA = "every cell's precision is its sampled omega"
 _GROUPS = ((NOISE, "a relation has one noise model"),)
 _ROWS = (
     ("interval", ("ordinal",), "an ordinal relation's bounds follow its edges"),
-    ("features", NOISE + ("dense", "background", "recommend", "new_test"), None),
+    ("features", NOISE + ("dense", "background", "recommend", "acquire", "new_test"), None),
     ("features", ("bias",), "both write the rows' base"),
     ("alpha_sample", ("probit",), "the probit latent has unit variance"),
     ("alpha_sample", _PG, _OMEGA),
@@ -96,15 +98,20 @@ _ROWS = (
     ("bias", NOISE, "biases are sampled under plain Gaussian noise"),
     ("bias", ("background",), "the unlisted cells would need them too"),
     ("bias", ("dense",), "no cell is listed to the rows"),
-    ("bias", ("recommend",), "the score is u.v + mean alone"),
+    ("bias", ("recommend", "acquire"), "the score is u.v + mean alone"),
     ("bias", ("new_test",), "a new row has no bias"),
     ("bias", _PRIORS, None),
     ("background", _LATENT + _PG + ("robust", "entity_noise"), None),
     ("background", ("dense",), "a dense relation leaves no cell unlisted"),
     ("background", _PRIORS, _GRAM),
-    ("dense", NOISE + ("recommend", "new_test"), None),
+    ("dense", NOISE + ("recommend", "acquire", "new_test"), None),
     ("dense", _PRIORS, _GRAM),
     ("recommend", ("probit",) + _PG, "its prediction is not u.v + mean"),
+    # acquisition lists: the moments of u.v + mean over the draws, the noise of one precision alpha per draw
+    ("acquire", ("probit",) + _PG, "its prediction is not u.v + mean"),
+    ("acquire", ("robust", "weights", "entity_noise"), "an unlisted cell's precision is not one alpha"),
+    ("acquire", ("ordinal",), "a level is not on the latent's scale"),
+    ("acquire", ("recommend",), "a relation keeps one ranked list"),
     ("waic", ("robust", "weights", "entity_noise", "background") + _PG, "a cell's density under it is not scored yet"),
     ("lpd", ("robust", "weights") + _PG, "a held-out cell's density under it is not scored yet"),
     ("rmse_train", ("censored",), "its training values are bounds, not measurements"),
@@ -113,6 +120,7 @@ _ROWS = (
     ("new_test", ("robust",) + _PG, _NO_CLOSED_FORM),
     ("new_test", ("weights",), "the weight of a new cell is unknown, which rules out {incoming}"),
     ("new_test", ("entity_noise",), "the precision of a new row is unknown, which rules out {incoming}"),
+    ("new_test", ("acquire",), "no list is ranked for a new row"),
     ("new_test", ("ordinal",), "a held-out level is not a measurement, which rules out {incoming}"),
     # the fold-in: a new row's known cells enter its conditional as u.v + mean under one precision alpha
     ("new_observed", NOISE, "a new row is conditioned on its known cells under plain Gaussian noise, which rules out {incoming}"),
@@ -151,6 +159,20 @@ def refused(there, comes):
     return False, None
 
 
+# an option that ranks a list as another one does: where the table has no row for it, refuse() reads the other one's.  The fold-in's
+# row (new_observed) names setRecommend alone, and what it says of a ranked list holds for an acquisition list as well
+_AS_FOR = {"acquire": "recommend"}
+
+
+def _refused_as(there, comes):
+    """refused(there, comes), or what the table says of the options that these two stand where (_AS_FOR)"""
+    no, why = refused(there, comes)
+    a, b = _AS_FOR.get(there, there), _AS_FOR.get(comes, comes)
+    if not no and a != b and (a, b) != (there, comes):
+        no, why = refused(a, b)
+    return no, why
+
+
 def present(x, scope):
     """the options of that scope that relation or entity x has, in the registry's order"""
     return [o for o in OPTIONS if o.scope == scope and o.present(x)]
@@ -171,7 +193,7 @@ def refuse(subject, incoming, build=False):
     option `incoming`.  build: the pass before a sampler is built, which also refuses the pairs of _REFUSED_ONLY_AT_BUILD"""
     phrase = OPTION[incoming].phrase
     for opt, owner in _around(subject):
-        no, why = refused(opt.key, incoming)
+        no, why = _refused_as(opt.key, incoming)
         if opt.key == incoming or not no or (not build and (opt.key, incoming) in _REFUSED_ONLY_AT_BUILD):
             continue
         if why is None or "{incoming}" not in why:

@@ -111,6 +111,7 @@ _SHOWN = {
     "bias": lambda x: " b:" + ",".join(x.entities[k - 1].name[:3] for k in sorted(x.model.bias)),
     "background": lambda x: f" bg:{x.model.background['weight']:g}",
     "recommend": lambda x: f" rec:{x.model.recommend['k']}",
+    "acquire": lambda x: f" acq:{x.model.acquire['k']}",
     "dense": lambda x: " dense",
 }
 
@@ -140,6 +141,7 @@ class RelationModel:
         self.pg = None            # setLogit / setCounts: {"model": "logit" | "counts", "r", "offset"}; Polya-Gamma augmentation
         self.background = None    # setBackground: {"weight", "value"}; every cell that is not listed observes `value` with precision alpha weight
         self.recommend = None     # setRecommend: {"k", "rows", "exclude_listed", "batch"}; macau() returns a top-k list per row of the first entity
+        self.acquire = None       # setAcquire: {"k", "rule", "kappa", "threshold", "rows", "exclude_listed", "batch"}; macau() returns a top-k list by an acquisition score
         self.entity_noise = None  # setEntityNoise: {"mode" (1-based), "shape", "rate"}; a sampled noise precision per row of that entity
         self.dense = False        # setDense: all N M cells of the two-mode relation are kept as a matrix on the device, none is listed to the row kernels
         self.bias = {}            # setBias: {mode (1-based): {"shape", "rate"}}; a sampled bias per row of every listed entity
@@ -717,16 +719,17 @@ def setRecommend(r, k, rows=None, exclude_listed=True, batch=8):
     return None
 
 
-def _recommend_int(r, name, x, top):
+def _recommend_int(r, name, x, top, setter="setRecommend"):
     if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not (1 <= int(x) <= top):
-        raise ArgumentError(f"Relation {r.name}: {name} = {x} must be an integer in 1 ... {top} (setRecommend).")
+        raise ArgumentError(f"Relation {r.name}: {name} = {x} must be an integer in 1 ... {top} ({setter}).")
     return int(x)
 
 
-def _recommend_spec(r, k, rows, exclude_listed, batch):
-    k, batch = _recommend_int(r, "k", k, RECOMMEND_MAX_K), _recommend_int(r, "batch", batch, RECOMMEND_MAX_BATCH)
+def _recommend_spec(r, k, rows, exclude_listed, batch, setter="setRecommend"):
+    """k, rows, exclude_listed and batch of a ranked list, checked; setter: who the messages name (setRecommend, setAcquire)"""
+    k, batch = _recommend_int(r, "k", k, RECOMMEND_MAX_K, setter), _recommend_int(r, "batch", batch, RECOMMEND_MAX_BATCH, setter)
     if not isinstance(exclude_listed, (bool, np.bool_)):
-        raise ArgumentError(f"Relation {r.name}: exclude_listed = {exclude_listed} must be true or false (setRecommend).")
+        raise ArgumentError(f"Relation {r.name}: exclude_listed = {exclude_listed} must be true or false ({setter}).")
     if rows is not None:
         N = int(r.data.dims[0])
         try:
@@ -734,12 +737,12 @@ def _recommend_spec(r, k, rows, exclude_listed, batch):
         except (TypeError, ValueError):
             a = np.asarray(0.5)
         if a.ndim != 1 or a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
-            raise ArgumentError(f"Relation {r.name}: rows must be a list of integer ids of {r.entities[0].name} (setRecommend).")
+            raise ArgumentError(f"Relation {r.name}: rows must be a list of integer ids of {r.entities[0].name} ({setter}).")
         a = a.astype(np.int64)
         if len(a) and (a.min() < 1 or a.max() > N):
-            raise ArgumentError(f"Relation {r.name}: rows holds an id outside 1 ... {N} (setRecommend).")
+            raise ArgumentError(f"Relation {r.name}: rows holds an id outside 1 ... {N} ({setter}).")
         if len(np.unique(a)) != len(a):
-            raise ArgumentError(f"Relation {r.name}: rows holds an id more than once (setRecommend).")
+            raise ArgumentError(f"Relation {r.name}: rows holds an id more than once ({setter}).")
         rows = a
     return {"k": k, "rows": rows, "exclude_listed": bool(exclude_listed), "batch": batch}
 
@@ -750,6 +753,61 @@ def check_recommend(r):
     _two_modes(r, "recommend", "take")
     m = r.model.recommend
     r.model.recommend = _recommend_spec(r, m.get("k"), m.get("rows"), m.get("exclude_listed"), m.get("batch"))
+
+
+ACQUIRE_RULES = ("ucb", "sd", "prob_above")
+
+
+def setAcquire(r, k, rule="ucb", kappa=1.0, threshold=None, rows=None, exclude_listed=True, batch=8):
+    """macau() returns, for rows of this relation's FIRST entity, the k (1 .. 64) unlisted items of the second with the largest
+    acquisition score, computed from the post-burn-in draws: which cell to measure next, which cell is likely above a threshold.
+    With m the posterior mean of u.v + mean_value and sd the sample standard deviation (n - 1) of u.v over the n draws:
+    rule "ucb": m + kappa sd, kappa >= 0 and finite (kappa = 0 ranks by the mean); "sd": sd alone (uncertainty sampling);
+    "prob_above": the posterior probability that a measurement of the cell exceeds `threshold` (required, finite), the noise
+    integrated out per draw: (1/n) sum_b Phi(sqrt(alpha_b) (u_b.v_b + mean_value - threshold)), alpha_b the draw's precision, fixed
+    or sampled (alpha_sample); under setBackground alpha_b is the LISTED cells' precision.
+    result["acquire"] = {"k", "rule", "kappa", "threshold", "rows", "items", "scores", "mean", "sd"} and, for prob_above, "prob":
+    n_rows x k each, the moments read at the listed items on the device.  The running mean and sum of squared deviations (Welford)
+    of u.v -- and the sum of the probabilities -- are kept on the device (rows x M doubles each), `batch` (1 .. 32) draws' factors
+    buffered per pass over them; only the lists come back.  With fewer than 2 draws ucb and sd have no candidates, with none
+    prob_above has none.  rows, exclude_listed, the order and the padding of a list: as for setRecommend, which the relation cannot
+    have as well.  The first relation of its RelationData, two modes, no relation features, Gaussian noise of one precision
+    (censored and interval values are taken), one rank.  Nothing of the chain changes.  k = None clears it."""
+    if k is None:
+        r.model.acquire = None
+        r._dev = None
+        return None
+    refuse(r, "acquire")
+    _two_modes(r, "acquire", "take")
+    r.model.acquire = _acquire_spec(r, k, rule, kappa, threshold, rows, exclude_listed, batch)
+    r._dev = None
+    return None
+
+
+def _acquire_spec(r, k, rule, kappa, threshold, rows, exclude_listed, batch):
+    spec = _recommend_spec(r, k, rows, exclude_listed, batch, "setAcquire")
+
+    def number(x):
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, (bool, np.bool_)) and math.isfinite(x)
+    if not isinstance(rule, str) or rule not in ACQUIRE_RULES:
+        raise ArgumentError(f"Relation {r.name}: rule = {rule!r} must be one of {', '.join(repr(x) for x in ACQUIRE_RULES)} (setAcquire).")
+    if not number(kappa) or kappa < 0:
+        raise ArgumentError(f"Relation {r.name}: kappa = {kappa} must be a finite number, not negative (setAcquire).")
+    if rule == "prob_above":
+        if threshold is None or not number(threshold):
+            raise ArgumentError(f"Relation {r.name}: rule 'prob_above' needs a finite threshold, not {threshold} (setAcquire).")
+    elif threshold is not None:
+        raise ArgumentError(f"Relation {r.name}: a threshold goes with rule 'prob_above', not with {rule!r} (setAcquire).")
+    spec.update({"rule": rule, "kappa": float(kappa), "threshold": None if threshold is None else float(threshold)})
+    return spec
+
+
+def check_acquire(r):
+    """what a relation with setAcquire must still satisfy when a sampler is built on it (its model may have been changed since)"""
+    refuse(r, "acquire", build=True)
+    _two_modes(r, "acquire", "take")
+    m = r.model.acquire
+    r.model.acquire = _acquire_spec(r, m.get("k"), m.get("rule"), m.get("kappa"), m.get("threshold"), m.get("rows"), m.get("exclude_listed"), m.get("batch"))
 
 
 def setNewRows(entity, F_new):
@@ -1201,7 +1259,7 @@ def check_interval(r):
 # rebuilds the bounds)
 _CHECKS = {"dense": check_dense, "probit": check_probit, "censored": check_censored, "ordinal": check_ordinal, "interval": check_interval,
            "robust": check_robust, "weights": check_robust, "entity_noise": check_entity_noise, "logit": check_pg, "counts": check_pg,
-           "background": check_background, "recommend": check_recommend, "bias": check_bias}
+           "background": check_background, "recommend": check_recommend, "acquire": check_acquire, "bias": check_bias}
 
 
 def check_model(r, world=1):

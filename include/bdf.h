@@ -979,6 +979,38 @@ int bdf_scores_metrics(bdf_scores *sc, const int32_t *items, int K, const bdf_pa
 int bdf_scores_copy(bdf_scores *sc, double *buf_dev, int64_t first, int64_t count, int write);
 int bdf_scores_set_draws(bdf_scores *sc, double draws);
 
+/* ---- acquisition lists per row from the moments of u.v over the draws (csrc/k_acquire.hip, csrc/acquire.h) -
+ * A bdf_acquire object keeps, for n_rows scored rows of the first entity and all M rows of the second, the planes mean[i, j] and
+ * M2[i, j] -- the running mean of u_i . v_j over the pushed draws and the running sum of its squared deviations (Welford) -- and,
+ * with want_prob, psum[i, j] = sum over the draws of Phi(sqrt(alpha_b) (u_i . v_j + mean_value - threshold)): n_rows x M doubles
+ * each, row-major, every plane followed by 64 doubles of NaN that nothing writes; a fourth plane of that shape holds the scores of
+ * the last list; and a ring of `batch` (1 .. 32) slots of draws that are not in the planes yet.  Everything is enqueued on ctx's
+ * stream.  rows_dev as for bdf_scores_create.  mean_value and (with want_prob) threshold must be finite.  BDF_ERR_HIP with N, M and
+ * the byte count in bdf_last_error() when the device memory does not suffice. */
+typedef struct bdf_acquire bdf_acquire;
+int bdf_acquire_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D, int batch, const int32_t *rows_dev, int want_prob,
+                       double mean_value, double threshold, bdf_acquire **out);
+int bdf_acquire_destroy(bdf_acquire *ac);
+/* this draw's factors (as for bdf_scores_push) and its noise precision into the next slot of the ring; a full ring is flushed.
+ * alpha_dev (dev, nullable) wins over alpha, which must otherwise be positive and finite: the value is stored into the slot by the
+ * device and never read on the host */
+int bdf_acquire_push(bdf_acquire *ac, const double *U, const double *V, double alpha, const double *alpha_dev);
+/* the buffered draws into the planes: per draw, in push order, p = u.v on v_mfma_f64_16x16x4_f64 from zero accumulators (d in
+ * ascending blocks of four), then with the draw's count n: delta = p - mean; mean += delta / n; M2 += delta (p - mean); psum += Phi(.)
+ * -- the planes' bits depend neither on `batch` nor on where the flushes fall */
+int bdf_acquire_flush(bdf_acquire *ac);
+/* flush, then per scored row the K (1 .. 64) best columns by the acquisition score over the n pushed draws, ordered and padded as
+ * bdf_scores_topk's lists, the columns listed in `rel` (nullable) left out.  With m = mean + mean_value and
+ * sd = sqrt(M2 / (n - 1)): rule 0 (ucb) m + kappa sd, kappa >= 0 and finite; rule 1 (sd) sd; rule 2 (prob_above, want_prob only)
+ * psum / n.  n < 2: no candidates for ucb and sd; n < 1: none for prob_above.  mean_out, sd_out, prob_out (dev, nullable, n_rows x K
+ * doubles): m, sd and psum / n at the listed items, NaN where items_out is 0 */
+int bdf_acquire_topk(bdf_acquire *ac, const bdf_rel *rel, int K, int rule, double kappa, int32_t *items_out, double *scores_out,
+                     double *mean_out, double *sd_out, double *prob_out);
+/* parity hooks: flush, then copy `count` doubles between plane 0 (mean), 1 (M2), 2 (psum) or 3 (the last list's scores), from cell
+ * `first` (the plane's guard included), and buf_dev -- write != 0: into the plane; and the count of draws n */
+int bdf_acquire_copy(bdf_acquire *ac, int plane, double *buf_dev, int64_t first, int64_t count, int write);
+int bdf_acquire_set_draws(bdf_acquire *ac, double draws);
+
 /* ---- a2: one Gibbs iteration enqueued from native code (src/macau.jl:80-203; relation-level side information and alpha
  * sampling excepted: those iterations are enqueued step by step through the entry points above) ------------------------
  * rows of every entity (+ exchange) -> hyperpriors -> test-set prediction update, on three streams (rows: ctx's; the other

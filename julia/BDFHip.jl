@@ -794,6 +794,41 @@ scores_metrics!(s::Scores, items::DevArray{Int32}, K::Integer, test::DevPairs, c
 scores_copy!(s::Scores, buf::DevArray{Float64}, first::Integer, count::Integer, write::Bool=false) =
     check(ccall((:bdf_scores_copy, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int64, Cint), s.h, buf.p, first, count, write ? 1 : 0))
 scores_set_draws!(s::Scores, draws::Real) = check(ccall((:bdf_scores_set_draws, lib), Cint, (Ptr{Cvoid}, Float64), s.h, draws))
+# ---- acquisition lists per row from the moments of u.v over the draws (bdf_acquire_*; DESIGN.md section 30) ---------------------
+"the running mean and sum of squared deviations (Welford) of u.v over the pushed draws for n_rows scored rows of the first entity
+against the M rows of the second and, with want_prob, the sum of Phi(sqrt(alpha_b) (u.v + mean_value - threshold)); a ring of `batch`
+draws that are not in the planes yet.  rows: 0-based rows of U (device Int32) or nothing"
+mutable struct Acquire
+    h::Ptr{Cvoid}
+    ctx::Context
+    n_rows::Int
+    M::Int
+    function Acquire(c::Context, n_rows::Integer, M::Integer, D::Integer, batch::Integer, rows::Union{DevArray{Int32},Nothing}=nothing;
+                     want_prob::Bool=false, mean_value::Real=0.0, threshold::Real=0.0)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:bdf_acquire_create, lib), Cint, (Ptr{Cvoid}, Int64, Int64, Cint, Cint, Ptr{Cvoid}, Cint, Float64, Float64, Ref{Ptr{Cvoid}}),
+                    c.h, n_rows, M, D, batch, rows === nothing ? C_NULL : rows.p, want_prob ? 1 : 0, mean_value, threshold, out))
+        a = new(out[], c, n_rows, M)
+        finalizer(x -> ccall((:bdf_acquire_destroy, lib), Cint, (Ptr{Cvoid},), x.h), a)
+        a
+    end
+end
+"this draw's factors and its precision into the ring (alpha_dev, a device Float64, wins over alpha); a full ring is folded into the planes"
+acquire_push!(a::Acquire, U::DevArray{Float64}, V::DevArray{Float64}, alpha::Real, alpha_dev::Union{DevArray{Float64},Nothing}=nothing) =
+    check(ccall((:bdf_acquire_push, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), a.h, U.p, V.p, alpha,
+                alpha_dev === nothing ? C_NULL : alpha_dev.p))
+"the buffered draws into the planes (f64 matrix instructions; the planes' bits do not depend on where the flushes fall)"
+acquire_flush!(a::Acquire) = check(ccall((:bdf_acquire_flush, lib), Cint, (Ptr{Cvoid},), a.h))
+"per scored row the K best columns by rule 0 (ucb: m + kappa sd), 1 (sd) or 2 (prob_above), ordered and padded as scores_topk!'s lists;
+mean, sd, prob (device Float64 n_rows x K, or C_NULL): the moments at the listed items"
+acquire_topk!(a::Acquire, rel::Ptr{Cvoid}, K::Integer, rule::Integer, kappa::Real, items::DevArray{Int32}, scores::DevArray{Float64},
+              mean::Ptr{Cvoid}=C_NULL, sd::Ptr{Cvoid}=C_NULL, prob::Ptr{Cvoid}=C_NULL) =
+    check(ccall((:bdf_acquire_topk, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Cint, Cint, Float64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+                a.h, rel, K, rule, kappa, items.p, scores.p, mean, sd, prob))
+"parity hooks: `count` doubles between plane 0 (mean), 1 (M2), 2 (psum) or 3 (score), from cell `first`, and buf; the count of draws"
+acquire_copy!(a::Acquire, plane::Integer, buf::DevArray{Float64}, first::Integer, count::Integer, write::Bool=false) =
+    check(ccall((:bdf_acquire_copy, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64, Cint), a.h, plane, buf.p, first, count, write ? 1 : 0))
+acquire_set_draws!(a::Acquire, draws::Real) = check(ccall((:bdf_acquire_set_draws, lib), Cint, (Ptr{Cvoid}, Float64), a.h, draws))
 "out = mean_value + F beta: linear_values (macau.jl:91) and the test rows' baseline"
 feat_linear!(c::Context, f::Ptr{Cvoid}, beta::DevArray{Float64}, mean_value, out::DevArray{Float64}) =
     check(ccall((:bdf_feat_linear, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), c.h, f, beta.p, mean_value, out.p))
