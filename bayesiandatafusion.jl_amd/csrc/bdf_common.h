@@ -367,18 +367,25 @@ __device__ __forceinline__ double bdf_normal(uint64_t seed, uint32_t sweep, uint
     return (n & 1) ? r * s : r * c;
 }
 
-// both normals of pair `pair` of the stream: numbers 2 pair and 2 pair + 1 (the same values bdf_normal returns)
+// the two normals of one draw of the generator (bdf_draw's four words): Box-Muller on its two uniforms.  Apart from bdf_normal_pair
+// for a kernel that runs the generator's integer rounds and this transform in two places (k_rows_col.hip)
 template <class KC = BdfLiteral>
-__device__ __forceinline__ void bdf_normal_pair(uint64_t seed, uint32_t sweep, uint32_t purpose, uint32_t entity,
-                                       uint64_t row, uint32_t pair, double &z0, double &z1)
+__device__ __forceinline__ void bdf_normal_pair_of(u32x4 o, double &z0, double &z1)
 {
-    u32x4 o = bdf_draw(seed, sweep, purpose, entity, row, pair);
     double u1 = bdf_u01(o.x, o.y), u2 = bdf_u01(o.z, o.w);
     double r = sqrt(-2.0 * bdf_log01<KC>(u1));
     double s, c;
     bdf_sincos2pi<KC>(u2, s, c);
     z0 = r * c;
     z1 = r * s;
+}
+
+// both normals of pair `pair` of the stream: numbers 2 pair and 2 pair + 1 (the same values bdf_normal returns)
+template <class KC = BdfLiteral>
+__device__ __forceinline__ void bdf_normal_pair(uint64_t seed, uint32_t sweep, uint32_t purpose, uint32_t entity,
+                                       uint64_t row, uint32_t pair, double &z0, double &z1)
+{
+    bdf_normal_pair_of<KC>(bdf_draw(seed, sweep, purpose, entity, row, pair), z0, z1);
 }
 
 __device__ __forceinline__ double bdf_uniform(uint64_t seed, uint32_t sweep, uint32_t purpose, uint32_t entity,

@@ -274,37 +274,87 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
         double A0[33], A1[33];
 #pragma unroll
         for (int i = 0; i < 33; i++) { A0[i] = 0.0; A1[i] = 0.0; }
+        const uint32_t *packed = coded ? T.packed + jb.q_begin : nullptr;
+        const int32_t *colidx = T.colidx + jb.q_begin;
+        const double *vals = T.vals + jb.q_begin;
+        const double *table = T.table;
+        // a chunk's ids and values minus the mean: lane j of the lane row takes observation c0 + j of its piece; positions
+        // past the piece's end take an id beyond the factor matrix (gathers there return zero) and the value 0
+#define COL_CHUNK(c0, IDW, R)                                                                     \
+        {                                                                                     \
+            const int o_ = (c0) + j;                                                          \
+            IDW = IMG ? COL_IMG_PAD_ID : 0xffffffu; R = 0.0;                                                         \
+            if (o_ < n) {                                                                     \
+                if (coded) { const uint32_t pw_ = packed[o_]; IDW = pw_; R = table[pw_ >> 24] - mean; } \
+                else { IDW = (uint32_t)colidx[o_]; R = vals[o_] - mean; }                     \
+            }                                                                                 \
+            IDW = __umul24(IDW, rowb);      /* the row's byte offset (the low 24 bits of a packed word are the id) */ \
+        }
+        uint32_t idw_c, idw_n;
+        double r_c, r_n;
+        double ba[4][COL_IMG_LANE(IMG)], bb[4][COL_IMG_LANE(IMG)];
+        // ---- the prologue: the first chunk, the first gathers, the prior's image -- and UNDER THEIR ROUND TRIPS what needs the job
+        // record and nothing the sums produce: the row's normals, the clears, nmax.  After the sums (where the normals stood until
+        // r16) a lone wave issues them at 7 - 8 cycles each in the busy part of its life; here the pipe is idle chip-wide, every wave
+        // of the launch waiting for the same loads at the same moment.  The first chunk's load is ISSUED (a round without observations
+        // issues none); the generator's integer rounds, the butterfly of nmax and the clears run under it; the chunk's wait, the
+        // table's load, the first gathers -- of padding, which touches no memory, in a round without observations -- and the prior's
+        // image follow at once; the transform runs under the gathers.  Both waves of a SIMD do this at the same time and share its
+        // pipe: by the stamps the prologue GROWS by about what the normals took (profiles/r16_k1c_early_normals.txt) -- what is
+        // gained is the pipe's idle time, which the two now fill.
+        const int o0_ = j;
+        uint32_t w0_ = IMG ? COL_IMG_PAD_ID : 0xffffffu;
+        double v0_ = 0.0;
+        if (o0_ < n) {
+            if (coded) w0_ = packed[o0_];
+            else { w0_ = (uint32_t)colidx[o0_]; v0_ = vals[o0_]; }
+        }
+        __builtin_amdgcn_sched_barrier(0);
         int nmax = n;
         nmax = max(nmax, __shfl_xor(nmax, 16));
         nmax = max(nmax, __shfl_xor(nmax, 32));
         nmax = __builtin_amdgcn_readfirstlane(nmax);
-        if (nmax > 0) {
-            const uint32_t *packed = coded ? T.packed + jb.q_begin : nullptr;
-            const int32_t *colidx = T.colidx + jb.q_begin;
-            const double *vals = T.vals + jb.q_begin;
-            const double *table = T.table;
-            // a chunk's ids and values minus the mean: lane j of the lane row takes observation c0 + j of its piece; positions
-            // past the piece's end take an id beyond the factor matrix (gathers there return zero) and the value 0
-#define COL_CHUNK(c0, IDW, R)                                                                     \
-            {                                                                                     \
-                const int o_ = (c0) + j;                                                          \
-                IDW = IMG ? COL_IMG_PAD_ID : 0xffffffu; R = 0.0;                                                         \
-                if (o_ < n) {                                                                     \
-                    if (coded) { const uint32_t pw_ = packed[o_]; IDW = pw_; R = table[pw_ >> 24] - mean; } \
-                    else { IDW = (uint32_t)colidx[o_]; R = vals[o_] - mean; }                     \
-                }                                                                                 \
-                IDW = __umul24(IDW, rowb);      /* the row's byte offset (the low 24 bits of a packed word are the id) */ \
-            }
-            uint32_t idw_c, idw_n;
-            double r_c, r_n;
-            COL_CHUNK(0, idw_c, r_c)
-            double ba[4][COL_IMG_LANE(IMG)], bb[4][COL_IMG_LANE(IMG)];
-            col_gather4<IMG, FULL, 0>(ba, rs, idw_c, rowb, eo, ok1);
+        // the normals: lane p of the lane row draws pair p of the row's stream (every lane and lane row draws; those without a pair
+        // are dropped below) -- the same stream, counter and pair per lane as after the sums, the same operations: the same bits.
+        // A part of a spanning row that is not the last to arrive draws a pair nobody uses.
+        u32x4 zo4 = bdf_draw(a.seed, a.sweep, BDF_P_ROW, a.entity_tag, (uint64_t)(uint32_t)jb.orig, (uint32_t)j);
+        asm volatile("" : "+v"(zo4.x), "+v"(zo4.y), "+v"(zo4.z), "+v"(zo4.w) :: "memory");
+        // (the clears of the 42 accumulated entries, ONCE and here: as constants the compiler wrote them twice, for the loop and
+        // for the way round it, the first set between the job record's arrival and the chunk's load)
+#pragma unroll
+        for (int e = 0; e < COL_NE; e++) { double zr = 0.0; asm volatile("" : "+v"(zr)); col_entry(A0, A1, e) = zr; }
+        __builtin_amdgcn_sched_barrier(0);
+        idw_c = __umul24(w0_, rowb);
+        col_gather4<IMG, FULL, 0>(ba, rs, idw_c, rowb, eo, ok1);
+        // (the value of a coded observation BEHIND the gathers, which do not need it: in front of them the wait at the join of the two
+        // ways -- coded or not -- covered the table's load as well, a round trip more before the first gather.  Every lane looks its
+        // code up, padding has code 0)
+        if (coded) v0_ = table[w0_ >> 24];
+        prior_ahead();
+        __builtin_amdgcn_sched_barrier(0);
+        // ... the transform, the hand-over within the lane row and the lane's two: column c wants number D - 1 - c.  z0, z1 ride
+        // through the loop in four registers
+        double z0 = 0.0, z1 = 0.0;
+        {
+            asm volatile("" : "+v"(zo4.x), "+v"(zo4.y), "+v"(zo4.z), "+v"(zo4.w) :: "memory");
+            double ze = 0.0, zo = 0.0;
+            bdf_normal_pair_of<ColCoef>(zo4, ze, zo);
+            if (!(live && 2 * j < D)) { ze = 0.0; zo = 0.0; }
+            const int base = lane & 48;
+            const double ze0 = __shfl(ze, base + (n0 >> 1)), zo0 = __shfl(zo, base + (n0 >> 1));
+            const double ze1 = __shfl(ze, base + (n1 >> 1)), zo1 = __shfl(zo, base + (n1 >> 1));
+            z0 = (n0 & 1) ? zo0 : ze0;
+            z1 = ok1 ? ((n1 & 1) ? zo1 : ze1) : 0.0;
+        }
+        // (the two selected here: left to itself the compiler carries the four candidates through the loop, the re-layout and the prior)
+        asm volatile("" : "+v"(z0), "+v"(z1) :: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        r_c = o0_ < n ? v0_ - mean : 0.0;
 #ifdef BDF_K1_STAMPS      // the prologue: from the wave's start to the first gathers' data (the wait is the diagnostic build's)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            CSTAMP(st_pro);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        CSTAMP(st_pro);
 #endif
-            prior_ahead();
+        if (nmax > 0) {
             for (int c0 = 0;; c0 += 16) {
                 COL_CHUNK(c0 + 16, idw_n, r_n)
                 col_gather4<IMG, FULL, 4>(bb, rs, idw_c, rowb, eo, ok1);
@@ -325,8 +375,8 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
                 if (c0 + 16 >= nmax) break;
                 idw_c = idw_n; r_c = r_n;
             }
+        }
 #undef COL_CHUNK
-        } else prior_ahead();      // (a round without observations)
 #ifdef BDF_K1_STAMPS
         asm volatile("s_nop 0" :: "v"(A0[0]), "v"(A0[32]), "v"(A1[31]));
         st_steps += (unsigned long long)nmax; st_rounds++;
@@ -383,18 +433,8 @@ __device__ __forceinline__ void rows_col_body(const SampleArgs &a_in, const ColP
             col_fold<32>(A0, A1, 1.0);
         }
         CSTAMP(st_mid);
-        // ---- normals (after the sums: a part of a spanning row that is not its last draws none): lane p of the lane row draws pair p of the row's stream; column c wants number D - 1 - c ----
-        double z0 = 0.0, z1 = 0.0;
-        {
-            double ze = 0.0, zo = 0.0;
-            if (live && 2 * j < D) bdf_normal_pair<ColCoef>(a.seed, a.sweep, BDF_P_ROW, a.entity_tag, (uint64_t)(uint32_t)jb.orig, (uint32_t)j, ze, zo);
-            const int base = lane & 48;
-            const double ze0 = __shfl(ze, base + (n0 >> 1)), zo0 = __shfl(zo, base + (n0 >> 1));
-            const double ze1 = __shfl(ze, base + (n1 >> 1)), zo1 = __shfl(zo, base + (n1 >> 1));
-            z0 = (n0 & 1) ? zo0 : ze0;
-            z1 = ok1 ? ((n1 & 1) ? zo1 : ze1) : 0.0;
-        }
-        // (the two selected here: left to itself the compiler carries the four candidates through the re-layout and the prior)
+        // (the normals stood here until r16; the pin in front of the re-layout stays, and the stamp for tools/col_stamps.py, which
+        // now reads next to nothing in it)
         asm volatile("" : "+v"(z0), "+v"(z1) :: "memory");
         CSTAMP(st_rng);
         // ---- the re-layout: what the sixty-four natural registers miss is in another lane by symmetry (dpp_rows32.h, col_rank1u).  8 x 8
