@@ -136,14 +136,6 @@ int bdf_sample_beta_rel_impl(bdf_ctx *ctx, bdf_comm *comm, const bdf_feat *fc, c
                              uint32_t rel_tag, double *beta_out, double *linear_out, double *rhs_out);
 #define BDF_DRAWS_BATCH 8
 int bdf_hyper_draws_batch(bdf_ctx *ctx, int D, int n, const int64_t *N, const double *nu, const uint32_t *entity_tag, double *const *draws_out);
-// k_recommend.hip, shared with k_acquire.hip.  bdf_ring_push: k_scores_push of one draw's factors into `slot`, (n_rows + M) x 4 nblk
-// doubles.  bdf_topk_plane: k_topk_rows on a plane of n_rows x M doubles scored as plane / draws + mean_value, after the checks of
-// `rel` against the scored rows (rows_dev nullable, rows_host its host copy); `who` names the caller in the messages
-struct bdf_rel;
-int bdf_ring_push(bdf_ctx *ctx, const double *U, const double *V, const int32_t *rows_dev, int64_t n_rows, int64_t M, int D, int nblk, double *slot);
-int bdf_topk_plane(bdf_ctx *ctx, const char *who, const double *plane, int64_t n_rows, int64_t M, const int32_t *rows_dev,
-                   const std::vector<int32_t> &rows_host, const bdf_rel *rel, int K, double draws, double mean_value, int32_t *items_out,
-                   double *scores_out);
 
 struct bdf_mode_index {
     std::vector<int64_t> rowptr;   // host, dims+1

@@ -15,23 +15,15 @@
 //                       k_acquire_gather: mean + mean_value, sd and prob at the listed items.
 //
 // Plain vector stores, no atomics, no LDS, no scratch memory.
-#include "bdf_common.h"
+#include "draw_ring.h"
 #include "acquire.h"
 
 struct bdf_acquire {
-    bdf_ctx *ctx;
-    int64_t n_rows, M;
-    int D, nblk;                   // nblk: blocks of four d, ceil(D / 4)
-    int batch, held;               // the ring's slots, and how many hold a draw that is not in the planes yet
-    double draws;                  // draws pushed
+    bdf_draw_ring ring;            // a slot: (n_rows + M) x 4 nblk of factors, then BDF_ACQ_TAIL doubles (the first: alpha)
     int want_prob;
     double mean_value, threshold;
     double *plane_dev[4];          // BDF_ACQ_MEAN, _M2, _PSUM (nullptr without want_prob), _SCORE: n_rows x M row-major, then BDF_REC_GUARD
                                    // doubles of NaN that nothing writes
-    double *ring_dev;              // batch slots of `slot` doubles: (n_rows + M) x 4 nblk of factors, then BDF_ACQ_TAIL (the first: alpha)
-    int64_t slot;
-    int32_t *rows_dev;             // nullable: 0-based row of U per scored row
-    std::vector<int32_t> rows_host;
 };
 
 #define BDF_ACQ_TAIL 4             // doubles behind a slot's factors (32 bytes: the next slot stays aligned as the first)
@@ -153,18 +145,6 @@ __global__ __launch_bounds__(256) void k_acquire_gather(const double *__restrict
     }
 }
 
-int acquire_alloc(void **p, size_t bytes, const char *what, int64_t n_rows, int64_t M)
-{
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        bdf_set_error("bdf_acquire_create: no device memory for %s of N = %lld rows and M = %lld columns (%zu bytes): %s", what,
-                      (long long)n_rows, (long long)M, bytes, hipGetErrorString(e));
-        return BDF_ERR_HIP;
-    }
-    return BDF_OK;
-}
-
 const char *const plane_name[4] = {"the mean plane", "the M2 plane", "the psum plane", "the score plane"};
 
 }  // namespace
@@ -172,58 +152,38 @@ const char *const plane_name[4] = {"the mean plane", "the M2 plane", "the psum p
 extern "C" int bdf_acquire_destroy(bdf_acquire *ac)
 {
     if (!ac) return BDF_OK;
-    hipSetDevice(ac->ctx->device);
-    hipStreamSynchronize(ac->ctx->stream);
+    hipSetDevice(ac->ring.ctx->device);
+    hipStreamSynchronize(ac->ring.ctx->stream);
     for (int q = 0; q < 4; q++)
         if (ac->plane_dev[q]) hipFree(ac->plane_dev[q]);
-    if (ac->ring_dev) hipFree(ac->ring_dev);
-    if (ac->rows_dev) hipFree(ac->rows_dev);
+    bdf_ring_free(&ac->ring);
     delete ac;
     return BDF_OK;
 }
 
+static int acquire_flush(void *ac) { return bdf_acquire_flush((bdf_acquire *)ac); }
+
 extern "C" int bdf_acquire_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D, int batch, const int32_t *rows_dev, int want_prob,
                                   double mean_value, double threshold, bdf_acquire **out)
 {
-    BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "bdf_acquire_create: NULL argument");
-    BDF_REQUIRE(n_rows >= 0 && M >= 0 && n_rows < (int64_t)0x7fffffff && M < (int64_t)0x7fffffff, BDF_ERR_ARG,
-                "bdf_acquire_create: n_rows=%lld and M=%lld must be in 0..2^31-2", (long long)n_rows, (long long)M);
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_acquire_create: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    BDF_REQUIRE(batch >= 1 && batch <= BDF_REC_MAX_BATCH, BDF_ERR_ARG, "bdf_acquire_create: batch=%d must be in 1..%d", batch, BDF_REC_MAX_BATCH);
+    const char *who = "bdf_acquire_create";
+    BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "%s: NULL argument", who);
+    bdf_draw_ring ring;
+    int rc = bdf_ring_init(&ring, who, ctx, n_rows, M, D, batch, BDF_ACQ_TAIL, acquire_flush);
+    if (rc) return rc;
     BDF_REQUIRE(std::isfinite(mean_value), BDF_ERR_ARG, "bdf_acquire_create: mean_value must be finite");
     BDF_REQUIRE(!want_prob || std::isfinite(threshold), BDF_ERR_ARG, "bdf_acquire_create: threshold must be finite");
     BDF_HIP(hipSetDevice(ctx->device));
     bdf_acquire *ac = new bdf_acquire();
-    ac->ctx = ctx; ac->n_rows = n_rows; ac->M = M; ac->D = D; ac->nblk = (D + 3) / 4; ac->batch = batch; ac->held = 0; ac->draws = 0.0;
+    ac->ring = ring; ac->ring.owner = ac;                     // (the planes are null)
     ac->want_prob = want_prob ? 1 : 0; ac->mean_value = mean_value; ac->threshold = want_prob ? threshold : 0.0;
-    for (int q = 0; q < 4; q++) ac->plane_dev[q] = nullptr;
-    ac->ring_dev = nullptr; ac->rows_dev = nullptr;
-    ac->slot = (n_rows + M) * 4 * ac->nblk + BDF_ACQ_TAIL;
     struct Guard { bdf_acquire *p; ~Guard() { if (p) bdf_acquire_destroy(p); } } guard{ac};
-    const size_t cells = (size_t)n_rows * (size_t)M, plane_bytes = cells * sizeof(double);
-    int rc;
     for (int q = 0; q < 4; q++) {
         if (q == BDF_ACQ_PSUM && !want_prob) continue;
-        if ((rc = acquire_alloc((void **)&ac->plane_dev[q], plane_bytes + BDF_REC_GUARD * sizeof(double), plane_name[q], n_rows, M))) return rc;
-    }
-    if ((rc = acquire_alloc((void **)&ac->ring_dev, (size_t)batch * (size_t)ac->slot * sizeof(double), "the ring of draws", n_rows, M))) return rc;
-    if (rows_dev && n_rows) {
-        if ((rc = acquire_alloc((void **)&ac->rows_dev, (size_t)n_rows * sizeof(int32_t), "the scored rows", n_rows, M))) return rc;
-        ac->rows_host.resize((size_t)n_rows);
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        BDF_HIP(hipMemcpy(ac->rows_host.data(), rows_dev, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int64_t r = 0; r < n_rows; r++)
-            BDF_REQUIRE(ac->rows_host[(size_t)r] >= 0, BDF_ERR_BOUNDS, "bdf_acquire_create: rows[%lld] = %d is negative (0-based rows of U)", (long long)r,
-                        ac->rows_host[(size_t)r]);
-        BDF_HIP(hipMemcpy(ac->rows_dev, ac->rows_host.data(), (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    for (int q = 0; q < 4; q++) {
-        if (!ac->plane_dev[q]) continue;
         // (the score plane holds NaN until a list is asked for)
-        if (plane_bytes) BDF_HIP(hipMemsetAsync(ac->plane_dev[q], q == BDF_ACQ_SCORE ? 0xff : 0, plane_bytes, ctx->stream));
-        BDF_HIP(hipMemsetAsync(ac->plane_dev[q] + cells, 0xff, BDF_REC_GUARD * sizeof(double), ctx->stream));      // (NaN)
+        if ((rc = bdf_ring_plane(&ac->ring, who, plane_name[q], q == BDF_ACQ_SCORE ? 0xff : 0, &ac->plane_dev[q]))) return rc;
     }
-    BDF_HIP(hipStreamSynchronize(ctx->stream));
+    if ((rc = bdf_ring_alloc(&ac->ring, who, rows_dev))) return rc;
     guard.p = nullptr;
     *out = ac;
     return BDF_OK;
@@ -232,23 +192,24 @@ extern "C" int bdf_acquire_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D
 extern "C" int bdf_acquire_flush(bdf_acquire *ac)
 {
     BDF_REQUIRE(ac != nullptr, BDF_ERR_ARG, "bdf_acquire_flush: NULL argument");
-    if (ac->held == 0) return BDF_OK;
-    bdf_ctx *ctx = ac->ctx;
+    bdf_draw_ring *r = &ac->ring;
+    if (r->held == 0) return BDF_OK;
+    bdf_ctx *ctx = r->ctx;
     BDF_HIP(hipSetDevice(ctx->device));
-    const int held = ac->held;
-    ac->held = 0;
-    if (ac->n_rows == 0 || ac->M == 0) return BDF_OK;
-    const int64_t tiles_n = (ac->n_rows + BDF_ACQ_TN - 1) / BDF_ACQ_TN, tiles_m = (ac->M + BDF_ACQ_TM - 1) / BDF_ACQ_TM;
+    const int held = r->held;
+    r->held = 0;
+    if (r->n_rows == 0 || r->M == 0) return BDF_OK;
+    const int64_t tiles_n = (r->n_rows + BDF_ACQ_TN - 1) / BDF_ACQ_TN, tiles_m = (r->M + BDF_ACQ_TM - 1) / BDF_ACQ_TM;
     const int64_t tiles = tiles_n * tiles_m;
     const dim3 grid((unsigned)std::min<int64_t>(tiles, (int64_t)std::max(ctx->n_cus, 1) * 8));
-    const double n0 = ac->draws - (double)held;            // the draws that the planes hold already
+    const double n0 = r->draws - (double)held;            // the draws that the planes hold already
     if (ac->want_prob)
         hipLaunchKernelGGL(k_acquire_accum<true>, grid, dim3(256), 0, ctx->stream, ac->plane_dev[BDF_ACQ_MEAN], ac->plane_dev[BDF_ACQ_M2],
-                           ac->plane_dev[BDF_ACQ_PSUM], (const double *)ac->ring_dev, ac->n_rows, ac->M, ac->nblk, held, ac->slot, n0, ac->mean_value,
+                           ac->plane_dev[BDF_ACQ_PSUM], (const double *)r->ring_dev, r->n_rows, r->M, r->nblk, held, r->slot, n0, ac->mean_value,
                            ac->threshold, tiles_m, tiles);
     else
         hipLaunchKernelGGL(k_acquire_accum<false>, grid, dim3(256), 0, ctx->stream, ac->plane_dev[BDF_ACQ_MEAN], ac->plane_dev[BDF_ACQ_M2],
-                           (double *)nullptr, (const double *)ac->ring_dev, ac->n_rows, ac->M, ac->nblk, held, ac->slot, n0, ac->mean_value,
+                           (double *)nullptr, (const double *)r->ring_dev, r->n_rows, r->M, r->nblk, held, r->slot, n0, ac->mean_value,
                            ac->threshold, tiles_m, tiles);
     BDF_HIP(hipGetLastError());
     return BDF_OK;
@@ -258,16 +219,11 @@ extern "C" int bdf_acquire_push(bdf_acquire *ac, const double *U, const double *
 {
     BDF_REQUIRE(ac && U && V, BDF_ERR_ARG, "bdf_acquire_push: NULL argument");
     BDF_REQUIRE(alpha_dev || (alpha > 0.0 && std::isfinite(alpha)), BDF_ERR_ARG, "bdf_acquire_push: alpha=%g must be positive and finite (or alpha_dev given)", alpha);
-    bdf_ctx *ctx = ac->ctx;
-    BDF_HIP(hipSetDevice(ctx->device));
-    double *slot = ac->ring_dev + (int64_t)ac->held * ac->slot;
-    const int rc = bdf_ring_push(ctx, U, V, ac->rows_dev, ac->n_rows, ac->M, ac->D, ac->nblk, slot);
-    if (rc) return rc;
-    hipLaunchKernelGGL(k_acquire_alpha, dim3(1), dim3(64), 0, ctx->stream, slot + (ac->slot - BDF_ACQ_TAIL), alpha, alpha_dev);
+    BDF_HIP(hipSetDevice(ac->ring.ctx->device));
+    // (the slot's tail ahead of its factors, which bdf_ring_push writes before it counts the draw and flushes a full ring)
+    hipLaunchKernelGGL(k_acquire_alpha, dim3(1), dim3(64), 0, ac->ring.ctx->stream, bdf_ring_slot(&ac->ring) + (ac->ring.slot - BDF_ACQ_TAIL), alpha, alpha_dev);
     BDF_HIP(hipGetLastError());
-    ac->held++;
-    ac->draws += 1.0;
-    return ac->held == ac->batch ? bdf_acquire_flush(ac) : BDF_OK;
+    return bdf_ring_push(&ac->ring, U, V);
 }
 
 extern "C" int bdf_acquire_copy(bdf_acquire *ac, int plane, double *buf_dev, int64_t first, int64_t count, int write)
@@ -275,24 +231,10 @@ extern "C" int bdf_acquire_copy(bdf_acquire *ac, int plane, double *buf_dev, int
     BDF_REQUIRE(ac && buf_dev, BDF_ERR_ARG, "bdf_acquire_copy: NULL argument");
     BDF_REQUIRE(plane >= 0 && plane < 4 && ac->plane_dev[plane], BDF_ERR_ARG,
                 "bdf_acquire_copy: plane=%d must be 0 (mean), 1 (M2), 2 (psum, kept with want_prob only) or 3 (score)", plane);
-    const int64_t cells = ac->n_rows * ac->M + BDF_REC_GUARD;
-    BDF_REQUIRE(first >= 0 && count >= 0 && first <= cells && count <= cells - first, BDF_ERR_BOUNDS,
-                "bdf_acquire_copy: cells %lld .. %lld are outside the plane and its guard (%lld doubles)", (long long)first, (long long)(first + count), (long long)cells);
-    const int rc = bdf_acquire_flush(ac);
-    if (rc) return rc;
-    BDF_HIP(hipSetDevice(ac->ctx->device));
-    double *at = ac->plane_dev[plane] + first;
-    if (count) BDF_HIP(hipMemcpyAsync(write ? at : buf_dev, write ? buf_dev : at, (size_t)count * sizeof(double), hipMemcpyDeviceToDevice, ac->ctx->stream));
-    return BDF_OK;
+    return bdf_ring_copy(&ac->ring, "bdf_acquire_copy", "plane", ac->plane_dev[plane], buf_dev, first, count, write);
 }
 
-extern "C" int bdf_acquire_set_draws(bdf_acquire *ac, double draws)
-{
-    BDF_REQUIRE(ac != nullptr && draws >= 0.0, BDF_ERR_ARG, "bdf_acquire_set_draws: NULL argument or a negative count");
-    BDF_REQUIRE(ac->held == 0, BDF_ERR_ARG, "bdf_acquire_set_draws: %d draws are buffered (bdf_acquire_flush first)", ac->held);
-    ac->draws = draws;
-    return BDF_OK;
-}
+extern "C" int bdf_acquire_set_draws(bdf_acquire *ac, double draws) { return bdf_ring_set_draws(ac ? &ac->ring : nullptr, "bdf_acquire", draws); }
 
 extern "C" int bdf_acquire_topk(bdf_acquire *ac, const bdf_rel *rel, int K, int rule, double kappa, int32_t *items_out, double *scores_out,
                                 double *mean_out, double *sd_out, double *prob_out)
@@ -304,24 +246,23 @@ extern "C" int bdf_acquire_topk(bdf_acquire *ac, const bdf_rel *rel, int K, int 
     BDF_REQUIRE(K >= 1 && K <= BDF_REC_MAX_K, BDF_ERR_ARG, "bdf_acquire_topk: K=%d must be in 1..%d", K, BDF_REC_MAX_K);
     int rc = bdf_acquire_flush(ac);
     if (rc) return rc;
-    bdf_ctx *ctx = ac->ctx;
+    bdf_ctx *ctx = ac->ring.ctx;
     BDF_HIP(hipSetDevice(ctx->device));
-    const int64_t cells = ac->n_rows * ac->M;
+    const int64_t cells = ac->ring.n_rows * ac->ring.M;
     if (cells > 0) {
         const dim3 grid((unsigned)std::min<int64_t>((cells + 255) / 256, 65536));
         hipLaunchKernelGGL(k_acquire_score, grid, dim3(256), 0, ctx->stream, (const double *)ac->plane_dev[BDF_ACQ_MEAN], (const double *)ac->plane_dev[BDF_ACQ_M2],
-                           (const double *)ac->plane_dev[BDF_ACQ_PSUM], cells, rule, ac->draws, kappa, ac->mean_value, ac->plane_dev[BDF_ACQ_SCORE]);
+                           (const double *)ac->plane_dev[BDF_ACQ_PSUM], cells, rule, ac->ring.draws, kappa, ac->mean_value, ac->plane_dev[BDF_ACQ_SCORE]);
         BDF_HIP(hipGetLastError());
     }
     // bdf_rec_score(score, 1, 0) is the score itself
-    rc = bdf_topk_plane(ctx, "bdf_acquire_topk", ac->plane_dev[BDF_ACQ_SCORE], ac->n_rows, ac->M, ac->rows_dev, ac->rows_host, rel, K, 1.0, 0.0,
-                        items_out, scores_out);
+    rc = bdf_topk_plane(&ac->ring, "bdf_acquire_topk", ac->plane_dev[BDF_ACQ_SCORE], rel, K, 1.0, 0.0, items_out, scores_out);
     if (rc) return rc;
-    if (ac->n_rows > 0 && (mean_out || sd_out || prob_out)) {
-        const int64_t total = ac->n_rows * K;
+    if (ac->ring.n_rows > 0 && (mean_out || sd_out || prob_out)) {
+        const int64_t total = ac->ring.n_rows * K;
         const dim3 grid((unsigned)std::min<int64_t>((total + 255) / 256, 65536));
         hipLaunchKernelGGL(k_acquire_gather, grid, dim3(256), 0, ctx->stream, (const double *)ac->plane_dev[BDF_ACQ_MEAN], (const double *)ac->plane_dev[BDF_ACQ_M2],
-                           (const double *)ac->plane_dev[BDF_ACQ_PSUM], (const int32_t *)items_out, ac->n_rows, ac->M, K, ac->draws, ac->mean_value, mean_out,
+                           (const double *)ac->plane_dev[BDF_ACQ_PSUM], (const int32_t *)items_out, ac->ring.n_rows, ac->ring.M, K, ac->ring.draws, ac->mean_value, mean_out,
                            sd_out, prob_out);
         BDF_HIP(hipGetLastError());
     }

@@ -15,19 +15,11 @@
 //                       the host once); k_rec_metrics_final: one workgroup adds the rows' recall, NDCG and hit in a fixed order.
 //
 // Plain vector stores, no floating-point atomics, no scratch memory.
-#include "bdf_common.h"
-#include "recommend.h"
+#include "draw_ring.h"
 
 struct bdf_scores {
-    bdf_ctx *ctx;
-    int64_t n_rows, M;
-    int D, nblk;                   // nblk: blocks of four d, ceil(D / 4)
-    int batch, held;               // the ring's slots, and how many hold a draw that is not in the sum yet
-    double draws;                  // draws pushed
+    bdf_draw_ring ring;
     double *sum_dev;               // n_rows x M, row-major, then BDF_REC_GUARD doubles of NaN that nothing writes
-    double *ring_dev;              // batch slots of (n_rows + M) x 4 nblk doubles
-    int32_t *rows_dev;             // nullable: 0-based row of U per scored row
-    std::vector<int32_t> rows_host;
     // bdf_scores_metrics: the relevant test items of every scored row, built at the first call for (pairs, class_cut)
     const bdf_pairs *rel_pairs;
     double rel_cut;
@@ -236,13 +228,13 @@ __global__ __launch_bounds__(256) void k_rec_metrics_final(const double *__restr
     }
 }
 
-int scores_alloc(void **p, size_t bytes, const char *what, int64_t n_rows, int64_t M)
+int ring_alloc(void **p, size_t bytes, const char *who, const char *what, int64_t n_rows, int64_t M)
 {
     const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
     if (e != hipSuccess) {
         (void)hipGetLastError();
-        bdf_set_error("bdf_scores_create: no device memory for %s of N = %lld rows and M = %lld columns (%zu bytes): %s", what,
-                      (long long)n_rows, (long long)M, bytes, hipGetErrorString(e));
+        bdf_set_error("%s: no device memory for %s of N = %lld rows and M = %lld columns (%zu bytes): %s", who, what, (long long)n_rows, (long long)M,
+                      bytes, hipGetErrorString(e));
         return BDF_ERR_HIP;
     }
     return BDF_OK;
@@ -250,13 +242,119 @@ int scores_alloc(void **p, size_t bytes, const char *what, int64_t n_rows, int64
 
 }  // namespace
 
+// ---- the ring of draws (draw_ring.h), then bdf_scores
+int bdf_ring_init(bdf_draw_ring *r, const char *who, bdf_ctx *ctx, int64_t n_rows, int64_t M, int D, int batch, int tail, int (*flush)(void *))
+{
+    BDF_REQUIRE(n_rows >= 0 && M >= 0 && n_rows < (int64_t)0x7fffffff && M < (int64_t)0x7fffffff, BDF_ERR_ARG,
+                "%s: n_rows=%lld and M=%lld must be in 0..2^31-2", who, (long long)n_rows, (long long)M);
+    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "%s: num_latent=%d must be in 1..%d", who, D, BDF_MAX_D);
+    BDF_REQUIRE(batch >= 1 && batch <= BDF_REC_MAX_BATCH, BDF_ERR_ARG, "%s: batch=%d must be in 1..%d", who, batch, BDF_REC_MAX_BATCH);
+    r->ctx = ctx; r->n_rows = n_rows; r->M = M; r->D = D; r->nblk = (D + 3) / 4; r->batch = batch; r->held = 0; r->draws = 0.0;
+    r->slot = (n_rows + M) * 4 * r->nblk + tail; r->ring_dev = nullptr; r->rows_dev = nullptr; r->flush = flush; r->owner = nullptr;
+    return BDF_OK;
+}
+
+int bdf_ring_plane(const bdf_draw_ring *r, const char *who, const char *what, int fill, double **plane)
+{
+    const size_t cells = (size_t)r->n_rows * (size_t)r->M, bytes = cells * sizeof(double);
+    const int rc = ring_alloc((void **)plane, bytes + BDF_REC_GUARD * sizeof(double), who, what, r->n_rows, r->M);
+    if (rc) return rc;
+    if (bytes) BDF_HIP(hipMemsetAsync(*plane, fill, bytes, r->ctx->stream));
+    BDF_HIP(hipMemsetAsync(*plane + cells, 0xff, BDF_REC_GUARD * sizeof(double), r->ctx->stream));      // (NaN)
+    return BDF_OK;
+}
+
+int bdf_ring_alloc(bdf_draw_ring *r, const char *who, const int32_t *rows_dev)
+{
+    const int64_t n_rows = r->n_rows;
+    int rc;
+    if ((rc = ring_alloc((void **)&r->ring_dev, (size_t)r->batch * (size_t)r->slot * sizeof(double), who, "the ring of draws", n_rows, r->M))) return rc;
+    if (rows_dev && n_rows) {
+        if ((rc = ring_alloc((void **)&r->rows_dev, (size_t)n_rows * sizeof(int32_t), who, "the scored rows", n_rows, r->M))) return rc;
+        r->rows_host.resize((size_t)n_rows);
+        BDF_HIP(hipStreamSynchronize(r->ctx->stream));
+        BDF_HIP(hipMemcpy(r->rows_host.data(), rows_dev, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
+        for (int64_t q = 0; q < n_rows; q++)
+            BDF_REQUIRE(r->rows_host[(size_t)q] >= 0, BDF_ERR_BOUNDS, "%s: rows[%lld] = %d is negative (0-based rows of U)", who, (long long)q,
+                        r->rows_host[(size_t)q]);
+        BDF_HIP(hipMemcpy(r->rows_dev, r->rows_host.data(), (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    BDF_HIP(hipStreamSynchronize(r->ctx->stream));
+    return BDF_OK;
+}
+
+void bdf_ring_free(bdf_draw_ring *r) { hipFree(r->ring_dev); hipFree(r->rows_dev); }          // (either may be null)
+
+int bdf_ring_push(bdf_draw_ring *r, const double *U, const double *V)
+{
+    BDF_HIP(hipSetDevice(r->ctx->device));
+    const int64_t quads = (r->n_rows + r->M) * r->nblk;
+    if (quads > 0) {
+        const dim3 grid((unsigned)std::min<int64_t>((quads + 255) / 256, 65536));
+        hipLaunchKernelGGL(k_scores_push, grid, dim3(256), 0, r->ctx->stream, U, V, (const int32_t *)r->rows_dev, r->n_rows, r->M, r->D, r->nblk, bdf_ring_slot(r));
+        BDF_HIP(hipGetLastError());
+    }
+    r->held++;
+    r->draws += 1.0;
+    return r->held == r->batch ? r->flush(r->owner) : BDF_OK;
+}
+
+int bdf_ring_copy(bdf_draw_ring *r, const char *who, const char *what, double *plane, double *buf_dev, int64_t first, int64_t count, int write)
+{
+    const int64_t cells = r->n_rows * r->M + BDF_REC_GUARD;
+    BDF_REQUIRE(first >= 0 && count >= 0 && first <= cells && count <= cells - first, BDF_ERR_BOUNDS,
+                "%s: cells %lld .. %lld are outside the %s and its guard (%lld doubles)", who, (long long)first, (long long)(first + count), what, (long long)cells);
+    if (const int rc = r->flush(r->owner)) return rc;
+    BDF_HIP(hipSetDevice(r->ctx->device));
+    if (count) BDF_HIP(hipMemcpyAsync(write ? plane + first : buf_dev, write ? buf_dev : plane + first, (size_t)count * sizeof(double),
+                                      hipMemcpyDeviceToDevice, r->ctx->stream));
+    return BDF_OK;
+}
+
+int bdf_ring_set_draws(bdf_draw_ring *r, const char *who, double draws)
+{
+    BDF_REQUIRE(r != nullptr && draws >= 0.0, BDF_ERR_ARG, "%s_set_draws: NULL argument or a negative count", who);
+    BDF_REQUIRE(r->held == 0, BDF_ERR_ARG, "%s_set_draws: %d draws are buffered (%s_flush first)", who, r->held, who);
+    r->draws = draws;
+    return BDF_OK;
+}
+
+int bdf_topk_plane(const bdf_draw_ring *r, const char *who, const double *plane, const bdf_rel *rel, int K, double draws, double mean_value,
+                   int32_t *items_out, double *scores_out)
+{
+    const int64_t n_rows = r->n_rows, M = r->M;
+    BDF_REQUIRE(K >= 1 && K <= BDF_REC_MAX_K, BDF_ERR_ARG, "%s: K=%d must be in 1..%d", who, K, BDF_REC_MAX_K);
+    const int64_t *rowptr = nullptr;
+    const int32_t *colidx = nullptr;
+    if (rel) {
+        BDF_REQUIRE(rel->n_modes == 2 && !rel->sharded, BDF_ERR_ARG, "%s: the listed cells come from a two-mode relation on one rank", who);
+        BDF_REQUIRE(rel->dims[1] == M, BDF_ERR_ARG, "%s: the relation has %lld columns, the scores %lld", who, (long long)rel->dims[1], (long long)M);
+        const int64_t N = rel->dims[0];
+        if (r->rows_dev) {
+            for (int64_t q = 0; q < n_rows; q++)
+                BDF_REQUIRE(r->rows_host[(size_t)q] < N, BDF_ERR_BOUNDS, "%s: rows[%lld] = %d is outside the relation's %lld rows", who, (long long)q,
+                            r->rows_host[(size_t)q], (long long)N);
+        } else {
+            BDF_REQUIRE(n_rows <= N, BDF_ERR_ARG, "%s: %lld scored rows, the relation has %lld", who, (long long)n_rows, (long long)N);
+        }
+        rowptr = rel->idx[0].rowptr_dev; colidx = rel->idx[0].colidx_dev;
+    }
+    if (n_rows == 0) return BDF_OK;
+    BDF_HIP(hipSetDevice(r->ctx->device));
+    const dim3 grid((unsigned)std::min<int64_t>(n_rows, 1 << 20));
+    hipLaunchKernelGGL(k_topk_rows, grid, dim3(64), 0, r->ctx->stream, plane, n_rows, M, (const int32_t *)r->rows_dev, rowptr, colidx, K, draws, mean_value,
+                       items_out, scores_out);
+    BDF_HIP(hipGetLastError());
+    return BDF_OK;
+}
+
 extern "C" int bdf_scores_destroy(bdf_scores *sc)
 {
     if (!sc) return BDF_OK;
-    hipSetDevice(sc->ctx->device);
-    hipStreamSynchronize(sc->ctx->stream);
-    hipFree(sc->sum_dev); hipFree(sc->ring_dev);
-    if (sc->rows_dev) hipFree(sc->rows_dev);
+    hipSetDevice(sc->ring.ctx->device);
+    hipStreamSynchronize(sc->ring.ctx->stream);
+    hipFree(sc->sum_dev);
+    bdf_ring_free(&sc->ring);
     if (sc->rel_ptr_dev) hipFree(sc->rel_ptr_dev);
     if (sc->rel_items_dev) hipFree(sc->rel_items_dev);
     if (sc->row_metrics_dev) hipFree(sc->row_metrics_dev);
@@ -264,37 +362,21 @@ extern "C" int bdf_scores_destroy(bdf_scores *sc)
     return BDF_OK;
 }
 
+static int scores_flush(void *sc) { return bdf_scores_flush((bdf_scores *)sc); }
+
 extern "C" int bdf_scores_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D, int batch, const int32_t *rows_dev, bdf_scores **out)
 {
-    BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "bdf_scores_create: NULL argument");
-    BDF_REQUIRE(n_rows >= 0 && M >= 0 && n_rows < (int64_t)0x7fffffff && M < (int64_t)0x7fffffff, BDF_ERR_ARG,
-                "bdf_scores_create: n_rows=%lld and M=%lld must be in 0..2^31-2", (long long)n_rows, (long long)M);
-    BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "bdf_scores_create: num_latent=%d must be in 1..%d", D, BDF_MAX_D);
-    BDF_REQUIRE(batch >= 1 && batch <= BDF_REC_MAX_BATCH, BDF_ERR_ARG, "bdf_scores_create: batch=%d must be in 1..%d", batch, BDF_REC_MAX_BATCH);
+    const char *who = "bdf_scores_create";
+    BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "%s: NULL argument", who);
+    bdf_draw_ring ring;
+    int rc = bdf_ring_init(&ring, who, ctx, n_rows, M, D, batch, 0, scores_flush);
+    if (rc) return rc;
     BDF_HIP(hipSetDevice(ctx->device));
     bdf_scores *sc = new bdf_scores();
-    sc->ctx = ctx; sc->n_rows = n_rows; sc->M = M; sc->D = D; sc->nblk = (D + 3) / 4; sc->batch = batch; sc->held = 0; sc->draws = 0.0;
-    sc->sum_dev = sc->ring_dev = nullptr; sc->rows_dev = nullptr;
-    sc->rel_pairs = nullptr; sc->rel_cut = 0.0; sc->rel_ptr_dev = nullptr; sc->rel_items_dev = nullptr; sc->row_metrics_dev = nullptr;
+    sc->ring = ring; sc->ring.owner = sc;                     // (the other fields are null)
     struct Guard { bdf_scores *p; ~Guard() { if (p) bdf_scores_destroy(p); } } guard{sc};
-    const size_t sum_bytes = (size_t)n_rows * (size_t)M * sizeof(double);
-    const size_t ring_bytes = (size_t)batch * (size_t)(n_rows + M) * 4 * sc->nblk * sizeof(double);
-    int rc;
-    if ((rc = scores_alloc((void **)&sc->sum_dev, sum_bytes + BDF_REC_GUARD * sizeof(double), "the score sum", n_rows, M))) return rc;
-    if ((rc = scores_alloc((void **)&sc->ring_dev, ring_bytes, "the ring of draws", n_rows, M))) return rc;
-    if (rows_dev && n_rows) {
-        if ((rc = scores_alloc((void **)&sc->rows_dev, (size_t)n_rows * sizeof(int32_t), "the scored rows", n_rows, M))) return rc;
-        sc->rows_host.resize((size_t)n_rows);
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        BDF_HIP(hipMemcpy(sc->rows_host.data(), rows_dev, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
-        for (int64_t r = 0; r < n_rows; r++)
-            BDF_REQUIRE(sc->rows_host[(size_t)r] >= 0, BDF_ERR_BOUNDS, "bdf_scores_create: rows[%lld] = %d is negative (0-based rows of U)", (long long)r,
-                        sc->rows_host[(size_t)r]);
-        BDF_HIP(hipMemcpy(sc->rows_dev, sc->rows_host.data(), (size_t)n_rows * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    if (sum_bytes) BDF_HIP(hipMemsetAsync(sc->sum_dev, 0, sum_bytes, ctx->stream));
-    BDF_HIP(hipMemsetAsync(sc->sum_dev + (size_t)n_rows * (size_t)M, 0xff, BDF_REC_GUARD * sizeof(double), ctx->stream));      // (NaN)
-    BDF_HIP(hipStreamSynchronize(ctx->stream));
+    if ((rc = bdf_ring_plane(&sc->ring, who, "the score sum", 0, &sc->sum_dev))) return rc;
+    if ((rc = bdf_ring_alloc(&sc->ring, who, rows_dev))) return rc;
     guard.p = nullptr;
     *out = sc;
     return BDF_OK;
@@ -303,105 +385,44 @@ extern "C" int bdf_scores_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D,
 extern "C" int bdf_scores_flush(bdf_scores *sc)
 {
     BDF_REQUIRE(sc != nullptr, BDF_ERR_ARG, "bdf_scores_flush: NULL argument");
-    if (sc->held == 0) return BDF_OK;
-    bdf_ctx *ctx = sc->ctx;
+    bdf_draw_ring *r = &sc->ring;
+    if (r->held == 0) return BDF_OK;
+    bdf_ctx *ctx = r->ctx;
     BDF_HIP(hipSetDevice(ctx->device));
-    const int held = sc->held;
-    sc->held = 0;
-    if (sc->n_rows == 0 || sc->M == 0) return BDF_OK;
-    const int64_t tiles_n = (sc->n_rows + BDF_REC_TN - 1) / BDF_REC_TN, tiles_m = (sc->M + BDF_REC_TM - 1) / BDF_REC_TM;
+    const int held = r->held;
+    r->held = 0;
+    if (r->n_rows == 0 || r->M == 0) return BDF_OK;
+    const int64_t tiles_n = (r->n_rows + BDF_REC_TN - 1) / BDF_REC_TN, tiles_m = (r->M + BDF_REC_TM - 1) / BDF_REC_TM;
     const int64_t tiles = tiles_n * tiles_m;
     const dim3 grid((unsigned)std::min<int64_t>(tiles, (int64_t)std::max(ctx->n_cus, 1) * 8));
-    const int DP = sc->D <= 16 ? 16 : (sc->D <= 32 ? 32 : 64);
-    if (DP == 16) hipLaunchKernelGGL(k_scores_accum<16>, grid, dim3(256), 0, ctx->stream, sc->sum_dev, (const double *)sc->ring_dev, sc->n_rows, sc->M, sc->nblk, held, tiles_m, tiles);
-    else if (DP == 32) hipLaunchKernelGGL(k_scores_accum<32>, grid, dim3(256), 0, ctx->stream, sc->sum_dev, (const double *)sc->ring_dev, sc->n_rows, sc->M, sc->nblk, held, tiles_m, tiles);
-    else hipLaunchKernelGGL(k_scores_accum<64>, grid, dim3(256), 0, ctx->stream, sc->sum_dev, (const double *)sc->ring_dev, sc->n_rows, sc->M, sc->nblk, held, tiles_m, tiles);
+    const int DP = r->D <= 16 ? 16 : (r->D <= 32 ? 32 : 64);
+    if (DP == 16) hipLaunchKernelGGL(k_scores_accum<16>, grid, dim3(256), 0, ctx->stream, sc->sum_dev, (const double *)r->ring_dev, r->n_rows, r->M, r->nblk, held, tiles_m, tiles);
+    else if (DP == 32) hipLaunchKernelGGL(k_scores_accum<32>, grid, dim3(256), 0, ctx->stream, sc->sum_dev, (const double *)r->ring_dev, r->n_rows, r->M, r->nblk, held, tiles_m, tiles);
+    else hipLaunchKernelGGL(k_scores_accum<64>, grid, dim3(256), 0, ctx->stream, sc->sum_dev, (const double *)r->ring_dev, r->n_rows, r->M, r->nblk, held, tiles_m, tiles);
     BDF_HIP(hipGetLastError());
-    return BDF_OK;
-}
-
-int bdf_ring_push(bdf_ctx *ctx, const double *U, const double *V, const int32_t *rows_dev, int64_t n_rows, int64_t M, int D, int nblk, double *slot)
-{
-    const int64_t quads = (n_rows + M) * nblk;
-    if (quads > 0) {
-        const dim3 grid((unsigned)std::min<int64_t>((quads + 255) / 256, 65536));
-        hipLaunchKernelGGL(k_scores_push, grid, dim3(256), 0, ctx->stream, U, V, rows_dev, n_rows, M, D, nblk, slot);
-        BDF_HIP(hipGetLastError());
-    }
     return BDF_OK;
 }
 
 extern "C" int bdf_scores_push(bdf_scores *sc, const double *U, const double *V)
 {
     BDF_REQUIRE(sc && U && V, BDF_ERR_ARG, "bdf_scores_push: NULL argument");
-    bdf_ctx *ctx = sc->ctx;
-    BDF_HIP(hipSetDevice(ctx->device));
-    const int64_t quads = (sc->n_rows + sc->M) * sc->nblk;
-    const int rc = bdf_ring_push(ctx, U, V, sc->rows_dev, sc->n_rows, sc->M, sc->D, sc->nblk, sc->ring_dev + (int64_t)sc->held * quads * 4);
-    if (rc) return rc;
-    sc->held++;
-    sc->draws += 1.0;
-    return sc->held == sc->batch ? bdf_scores_flush(sc) : BDF_OK;
+    return bdf_ring_push(&sc->ring, U, V);
 }
 
 extern "C" int bdf_scores_copy(bdf_scores *sc, double *buf_dev, int64_t first, int64_t count, int write)
 {
     BDF_REQUIRE(sc && buf_dev, BDF_ERR_ARG, "bdf_scores_copy: NULL argument");
-    const int64_t cells = sc->n_rows * sc->M + BDF_REC_GUARD;
-    BDF_REQUIRE(first >= 0 && count >= 0 && first <= cells && count <= cells - first, BDF_ERR_BOUNDS,
-                "bdf_scores_copy: cells %lld .. %lld are outside the sum and its guard (%lld doubles)", (long long)first, (long long)(first + count), (long long)cells);
-    const int rc = bdf_scores_flush(sc);
-    if (rc) return rc;
-    BDF_HIP(hipSetDevice(sc->ctx->device));
-    if (count) BDF_HIP(hipMemcpyAsync(write ? sc->sum_dev + first : buf_dev, write ? buf_dev : sc->sum_dev + first, (size_t)count * sizeof(double),
-                                      hipMemcpyDeviceToDevice, sc->ctx->stream));
-    return BDF_OK;
+    return bdf_ring_copy(&sc->ring, "bdf_scores_copy", "sum", sc->sum_dev, buf_dev, first, count, write);
 }
 
-extern "C" int bdf_scores_set_draws(bdf_scores *sc, double draws)
-{
-    BDF_REQUIRE(sc != nullptr && draws >= 0.0, BDF_ERR_ARG, "bdf_scores_set_draws: NULL argument or a negative count");
-    BDF_REQUIRE(sc->held == 0, BDF_ERR_ARG, "bdf_scores_set_draws: %d draws are buffered (bdf_scores_flush first)", sc->held);
-    sc->draws = draws;
-    return BDF_OK;
-}
-
-int bdf_topk_plane(bdf_ctx *ctx, const char *who, const double *plane, int64_t n_rows, int64_t M, const int32_t *rows_dev,
-                   const std::vector<int32_t> &rows_host, const bdf_rel *rel, int K, double draws, double mean_value, int32_t *items_out,
-                   double *scores_out)
-{
-    BDF_REQUIRE(K >= 1 && K <= BDF_REC_MAX_K, BDF_ERR_ARG, "%s: K=%d must be in 1..%d", who, K, BDF_REC_MAX_K);
-    const int64_t *rowptr = nullptr;
-    const int32_t *colidx = nullptr;
-    if (rel) {
-        BDF_REQUIRE(rel->n_modes == 2 && !rel->sharded, BDF_ERR_ARG, "%s: the listed cells come from a two-mode relation on one rank", who);
-        BDF_REQUIRE(rel->dims[1] == M, BDF_ERR_ARG, "%s: the relation has %lld columns, the scores %lld", who, (long long)rel->dims[1], (long long)M);
-        const int64_t N = rel->dims[0];
-        if (rows_dev) {
-            for (int64_t r = 0; r < n_rows; r++)
-                BDF_REQUIRE(rows_host[(size_t)r] < N, BDF_ERR_BOUNDS, "%s: rows[%lld] = %d is outside the relation's %lld rows", who, (long long)r,
-                            rows_host[(size_t)r], (long long)N);
-        } else {
-            BDF_REQUIRE(n_rows <= N, BDF_ERR_ARG, "%s: %lld scored rows, the relation has %lld", who, (long long)n_rows, (long long)N);
-        }
-        rowptr = rel->idx[0].rowptr_dev; colidx = rel->idx[0].colidx_dev;
-    }
-    if (n_rows == 0) return BDF_OK;
-    BDF_HIP(hipSetDevice(ctx->device));
-    const dim3 grid((unsigned)std::min<int64_t>(n_rows, 1 << 20));
-    hipLaunchKernelGGL(k_topk_rows, grid, dim3(64), 0, ctx->stream, plane, n_rows, M, rows_dev, rowptr, colidx, K, draws, mean_value, items_out, scores_out);
-    BDF_HIP(hipGetLastError());
-    return BDF_OK;
-}
+extern "C" int bdf_scores_set_draws(bdf_scores *sc, double draws) { return bdf_ring_set_draws(sc ? &sc->ring : nullptr, "bdf_scores", draws); }
 
 extern "C" int bdf_scores_topk(bdf_scores *sc, const bdf_rel *rel, int K, double mean_value, int32_t *items_out, double *scores_out)
 {
     BDF_REQUIRE(sc && items_out && scores_out, BDF_ERR_ARG, "bdf_scores_topk: NULL argument");
     BDF_REQUIRE(K >= 1 && K <= BDF_REC_MAX_K, BDF_ERR_ARG, "bdf_scores_topk: K=%d must be in 1..%d", K, BDF_REC_MAX_K);
-    const int rc = bdf_scores_flush(sc);
-    if (rc) return rc;
-    return bdf_topk_plane(sc->ctx, "bdf_scores_topk", sc->sum_dev, sc->n_rows, sc->M, sc->rows_dev, sc->rows_host, rel, K, sc->draws, mean_value,
-                          items_out, scores_out);
+    if (const int rc = bdf_scores_flush(sc)) return rc;
+    return bdf_topk_plane(&sc->ring, "bdf_scores_topk", sc->sum_dev, rel, K, sc->ring.draws, mean_value, items_out, scores_out);
 }
 
 extern "C" int bdf_scores_metrics(bdf_scores *sc, const int32_t *items, int K, const bdf_pairs *test, double class_cut, double *out)
@@ -409,21 +430,21 @@ extern "C" int bdf_scores_metrics(bdf_scores *sc, const int32_t *items, int K, c
     BDF_REQUIRE(sc && items && test && out, BDF_ERR_ARG, "bdf_scores_metrics: NULL argument");
     BDF_REQUIRE(K >= 1 && K <= BDF_REC_MAX_K, BDF_ERR_ARG, "bdf_scores_metrics: K=%d must be in 1..%d", K, BDF_REC_MAX_K);
     BDF_REQUIRE(test->n_modes == 2, BDF_ERR_ARG, "bdf_scores_metrics: the test cells belong to a two-mode relation, not %d modes", test->n_modes);
-    bdf_ctx *ctx = sc->ctx;
+    bdf_ctx *ctx = sc->ring.ctx;
     BDF_HIP(hipSetDevice(ctx->device));
-    const int64_t n_rows = sc->n_rows;
+    const int64_t n_rows = sc->ring.n_rows;
     if (sc->rel_pairs != test || sc->rel_cut != class_cut || !sc->rel_ptr_dev) {
         // the relevant test cells (value > class_cut) by scored row, each row's items ascending and distinct
         const int64_t n = test->n;
         const int32_t *ti = test->ids_host.data(), *tj = ti + n;
         std::map<int32_t, int32_t> slot_of;
-        if (sc->rows_dev)
-            for (int64_t r = 0; r < n_rows; r++) slot_of[sc->rows_host[(size_t)r]] = (int32_t)r;
+        if (sc->ring.rows_dev)
+            for (int64_t r = 0; r < n_rows; r++) slot_of[sc->ring.rows_host[(size_t)r]] = (int32_t)r;
         std::vector<std::pair<int32_t, int32_t>> cells;
         for (int64_t k = 0; k < n; k++) {
-            if (!(test->values_host[(size_t)k] > class_cut) || tj[k] >= sc->M) continue;
+            if (!(test->values_host[(size_t)k] > class_cut) || tj[k] >= sc->ring.M) continue;
             int32_t r;
-            if (sc->rows_dev) {
+            if (sc->ring.rows_dev) {
                 const auto it = slot_of.find(ti[k]);
                 if (it == slot_of.end()) continue;
                 r = it->second;
@@ -453,7 +474,7 @@ extern "C" int bdf_scores_metrics(bdf_scores *sc, const int32_t *items, int K, c
         hipLaunchKernelGGL(k_rec_metrics, grid, dim3(64), 0, ctx->stream, items, K, n_rows, (const int64_t *)sc->rel_ptr_dev, (const int32_t *)sc->rel_items_dev,
                            sc->row_metrics_dev);
     }
-    hipLaunchKernelGGL(k_rec_metrics_final, dim3(1), dim3(256), 0, ctx->stream, (const double *)sc->row_metrics_dev, n_rows, sc->draws, out);
+    hipLaunchKernelGGL(k_rec_metrics_final, dim3(1), dim3(256), 0, ctx->stream, (const double *)sc->row_metrics_dev, n_rows, sc->ring.draws, out);
     BDF_HIP(hipGetLastError());
     return BDF_OK;
 }

@@ -36,6 +36,28 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _alpha_args(alpha, host=0.0):
+    """alpha as the two arguments the entry points take: the host double, or -- a device scalar (tensor of one double) that only
+    the device reads -- `host` and its address"""
+    return (host, _ptr(alpha)) if torch.is_tensor(alpha) else (float(alpha), None)
+
+
+class _DeviceObject:
+    """an object of the library created on a context (self.ctx, self.handle): destroyed once, by the function `_destroy` names"""
+
+    def close(self):
+        if self.handle:
+            if self.ctx.handle:                 # a closed context has already destroyed its objects
+                getattr(lib(), self._destroy)(self.handle)
+            self.handle = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def _facs(factors):
     """the factor matrices of a relation's modes as the array of device pointers the entry points take"""
     fp = (C.c_void_p * len(factors))(*[f.data_ptr() for f in factors])
@@ -249,8 +271,9 @@ class Context:
             pass
 
 
-class DeviceRelation:
+class DeviceRelation(_DeviceObject):
     """bdf_rel: Relation.data (IndexedDF) as per-mode CSR in HBM."""
+    _destroy = "bdf_relation_destroy"
 
     def __init__(self, ctx, idf, layouts=None, rank=0, values=None):
         """layouts: one Layout per mode (several ranks): the device then holds this rank's rows only, at internal positions;
@@ -279,13 +302,13 @@ class DeviceRelation:
         self.train = None            # the training table as DevicePairs
         self.linear = None           # linear_values of the row kernels: mean + F beta, or what the model's latent draw leaves
         self.censor = self.interval = self.ordinal = self.ord_codes = None
-        self.omega = self.omega_sum = None          # obs_precision of the row kernels; omega's running sum
+        self.omega = None          # obs_precision of the row kernels
         self.robust_nu, self.pg_model, self.pg_r = 0.0, 0, 0.0
-        # a noise precision per row of one entity (setEntityNoise): {"mode", "shape", "rate"}; tau per row of that mode; its running sum
-        self.noise = self.tau = self.tau_sum = None
+        # a noise precision per row of one entity (setEntityNoise): {"mode", "shape", "rate"}; tau per row of that mode
+        self.noise = self.tau = None
         # biases (setBias): {mode0: {"shape", "rate"}}; per biased mode its bias vector (dims[mode0]); the modes' lambda, one double
-        # each in rising mode order; the draw's residual scratch; the running sums of both (macau() starts them)
-        self.bias_spec = self.bias = self.bias_lambda = self.bias_resid = self.bias_sum = self.bias_lambda_sum = None
+        # each in rising mode order; the draw's residual scratch
+        self.bias_spec = self.bias = self.bias_lambda = self.bias_resid = None
         # background cells (setBackground): {"weight", "value"}; the caller's weights (omega is then what the rows read, omega_k - c0)
         self.bg = self.bg_weights = None
         # a dense relation (setDense): {"R": N x M, the values without their mean; "C": per mode, its rows of R V / R' U; "sum_r2":
@@ -318,21 +341,11 @@ class DeviceRelation:
         check(lib().bdf_relation_order(self.handle, mode0, out.ctypes.data_as(_lib.c_i32p)))
         return out
 
-    def close(self):
-        if self.handle:
-            if self.ctx.handle:                 # a closed context has already destroyed its objects
-                lib().bdf_relation_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class DevicePairs:
+class DevicePairs(_DeviceObject):
     """bdf_pairs: test_vec (or the training table) with its running prediction state."""
+    _destroy = "bdf_pairs_destroy"
 
     def __init__(self, ctx, ids, values):
         self.ctx = ctx
@@ -434,10 +447,8 @@ class DevicePairs:
         into the running log-sum-exp (phase 0: burn-in, nothing kept; 1: first posterior draw; 2: later ones).  alpha: a float,
         or a device scalar (tensor of one double) read on the device.  Returns the device statistics: [0] the sum of this
         draw's log-likelihoods, [1] the sum of the pairs' lpd after it, [2] = [3] = 0."""
-        on_dev = torch.is_tensor(alpha)
         check(lib().bdf_pairs_lpd_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, _facs(factors),
-                                         mean_value, 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
-                                         _ptr(self.lpd_stats)))
+                                         mean_value, *_alpha_args(alpha), int(phase), _ptr(self.lpd_stats)))
         return self.lpd_stats
 
     def lpd(self):
@@ -458,10 +469,8 @@ class DevicePairs:
         number of pairs with V > 0.4."""
         if self.waic_stats is None:
             self.waic_stats = self.ctx.zeros(4)
-        on_dev = torch.is_tensor(alpha)
         check(lib().bdf_pairs_waic_update(self.ctx.handle, self.handle, _ptr(bounds) if bounds is not None else None, D, _facs(factors),
-                                          mean_value, 0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(phase),
-                                          _ptr(self.waic_stats)))
+                                          mean_value, *_alpha_args(alpha), int(phase), _ptr(self.waic_stats)))
         return self.waic_stats
 
     def waic(self, pointwise=False):
@@ -489,42 +498,55 @@ class DevicePairs:
             avg, sq = a2, s2
         return avg, sq
 
-    def close(self):
-        if self.handle:
-            if self.ctx.handle:                 # a closed context has already destroyed its objects
-                lib().bdf_pairs_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 _AUC_CONTEXTS = {}          # (device, stream) -> Context of device_auc_roc
 
 
-class DeviceScores:
-    """bdf_scores: the sum of u.v over the posterior draws for the scored rows of a two-mode relation's first entity against all M
-    rows of its second (n_rows x M doubles on the device), a ring of draws that are not in the sum yet, and the top-K lists and
-    ranking metrics from it (setRecommend; csrc/k_recommend.hip).  Everything runs on ctx's stream."""
+class _DrawRing(_DeviceObject):
+    """what DeviceScores and DeviceAcquire share: planes of n_rows x M doubles over the scored rows of a two-mode relation's first
+    entity against all M rows of its second, and a ring of posterior draws that are not in the planes yet.  `_lib_name`: the
+    prefix of the object's entry points.  Everything runs on ctx's stream."""
 
-    def __init__(self, ctx, n_rows, M, D, batch, rows0=None):
+    def _create(self, ctx, n_rows, M, D, batch, rows0, *model):
         """rows0: None, the rows 0 .. n_rows - 1 of U; else the 0-based row of U of every scored row"""
-        self.ctx = ctx
-        self.handle = C.c_void_p()
+        self.ctx, self.handle, self._destroy = ctx, C.c_void_p(), self._lib_name + "_destroy"
         self.n_rows, self.M, self.D, self.batch = int(n_rows), int(M), int(D), int(batch)
         rows = ctx.tensor(np.asarray(rows0, dtype=np.int32), dtype=torch.int32) if rows0 is not None else None
-        check(lib().bdf_scores_create(ctx.handle, self.n_rows, self.M, self.D, self.batch, _ptr(rows), C.byref(self.handle)))
+        check(self._call("create")(ctx.handle, self.n_rows, self.M, self.D, self.batch, _ptr(rows), *model, C.byref(self.handle)))
         ctx.adopt(self)
+
+    def _call(self, name):
+        return getattr(lib(), f"{self._lib_name}_{name}")
+
+    def flush(self):
+        check(self._call("flush")(self.handle))
+
+    def read(self, first=0, count=None, *plane):
+        """parity hook: `count` doubles of the sum (a plane) from cell `first` (behind the n_rows M cells: 64 guard doubles), flushed first"""
+        count = self.n_rows * self.M - first if count is None else int(count)
+        out = self.ctx.zeros(count)
+        check(self._call("copy")(self.handle, *plane, _ptr(out), int(first), count, 0))
+        return out
+
+    def write(self, values, draws, *plane):
+        """parity hook: the sum's (a plane's) cells from a device tensor and, unless None, the count of draws the planes then stand for"""
+        check(self._call("copy")(self.handle, *plane, _ptr(values), 0, int(values.numel()), 1))
+        if draws is not None:
+            check(self._call("set_draws")(self.handle, float(draws)))
+
+
+class DeviceScores(_DrawRing):
+    """bdf_scores: the sum of u.v over the posterior draws (n_rows x M doubles on the device), a ring of draws that are not in the
+    sum yet, and the top-K lists and ranking metrics from it (setRecommend; csrc/k_recommend.hip)."""
+    _lib_name = "bdf_scores"
+
+    def __init__(self, ctx, n_rows, M, D, batch, rows0=None):
+        self._create(ctx, n_rows, M, D, batch, rows0)
 
     def push(self, U, V):
         """this draw's factors (N x D and M x D tensors) into the ring; a full ring is added into the sum (bdf_scores_push)"""
         check(lib().bdf_scores_push(self.handle, _ptr(U), _ptr(V)))
-
-    def flush(self):
-        check(lib().bdf_scores_flush(self.handle))
 
     def topk(self, K, mean_value, rel=None):
         """(items int32 n_rows x K, 1-based and 0 behind the last candidate; scores float64, NaN there) on the device; rel: the
@@ -541,61 +563,26 @@ class DeviceScores:
         check(lib().bdf_scores_metrics(self.handle, _ptr(items), int(K), pairs.handle, float(class_cut), _ptr(out)))
         return out
 
-    def read(self, first=0, count=None):
-        """parity hook: `count` doubles of the sum from cell `first` (behind the n_rows M cells: 64 guard doubles), flushed first"""
-        count = self.n_rows * self.M - first if count is None else int(count)
-        out = self.ctx.zeros(count)
-        check(lib().bdf_scores_copy(self.handle, _ptr(out), int(first), count, 0))
-        return out
-
-    def write(self, values, draws):
-        """parity hook: the sum's cells from a device tensor, and the count of draws the scores are divided by"""
-        check(lib().bdf_scores_copy(self.handle, _ptr(values), 0, int(values.numel()), 1))
-        check(lib().bdf_scores_set_draws(self.handle, float(draws)))
-
-    def close(self):
-        if self.handle:
-            if self.ctx.handle:
-                lib().bdf_scores_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 ACQUIRE_RULES = {"ucb": 0, "sd": 1, "prob_above": 2}        # BDF_ACQ_UCB, _SD, _PROB (csrc/acquire.h)
 ACQUIRE_PLANES = {"mean": 0, "M2": 1, "psum": 2, "score": 3}
 
 
-class DeviceAcquire:
-    """bdf_acquire: the running mean and sum of squared deviations of u.v over the posterior draws for the scored rows of a two-mode
-    relation's first entity against all M rows of its second and, with a threshold, the sum of the draws' exceedance probabilities
-    (n_rows x M doubles each on the device), a ring of draws that are not in the planes yet, and the top-K lists by an acquisition
-    score from them (setAcquire; csrc/k_acquire.hip).  Everything runs on ctx's stream."""
+class DeviceAcquire(_DrawRing):
+    """bdf_acquire: the running mean and sum of squared deviations of u.v over the posterior draws and, with a threshold, the sum of
+    the draws' exceedance probabilities (n_rows x M doubles each on the device), a ring of draws that are not in the planes yet, and
+    the top-K lists by an acquisition score from them (setAcquire; csrc/k_acquire.hip)."""
+    _lib_name = "bdf_acquire"
 
     def __init__(self, ctx, n_rows, M, D, batch, rows0=None, mean_value=0.0, threshold=None):
-        """rows0: None, the rows 0 .. n_rows - 1 of U; else the 0-based row of U of every scored row.  threshold: None keeps no
-        psum plane"""
-        self.ctx = ctx
-        self.handle = C.c_void_p()
-        self.n_rows, self.M, self.D, self.batch = int(n_rows), int(M), int(D), int(batch)
+        """threshold: None keeps no psum plane"""
         self.want_prob = threshold is not None
-        rows = ctx.tensor(np.asarray(rows0, dtype=np.int32), dtype=torch.int32) if rows0 is not None else None
-        check(lib().bdf_acquire_create(ctx.handle, self.n_rows, self.M, self.D, self.batch, _ptr(rows), int(self.want_prob), float(mean_value),
-                                       float(threshold) if self.want_prob else 0.0, C.byref(self.handle)))
-        ctx.adopt(self)
+        self._create(ctx, n_rows, M, D, batch, rows0, int(self.want_prob), float(mean_value), float(threshold) if self.want_prob else 0.0)
 
     def push(self, U, V, alpha):
         """this draw's factors (N x D and M x D tensors) and its precision into the ring; alpha: a float, or a device tensor of
         one double that only the device reads.  A full ring is folded into the planes (bdf_acquire_push)"""
-        on_dev = torch.is_tensor(alpha)
-        check(lib().bdf_acquire_push(self.handle, _ptr(U), _ptr(V), 1.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None))
-
-    def flush(self):
-        check(lib().bdf_acquire_flush(self.handle))
+        check(lib().bdf_acquire_push(self.handle, _ptr(U), _ptr(V), *_alpha_args(alpha, 1.0)))
 
     def topk(self, K, rule, kappa=0.0, rel=None):
         """{"items" (int32 n_rows x K, 1-based and 0 behind the last candidate), "scores", "mean", "sd" and, with a psum plane,
@@ -609,30 +596,14 @@ class DeviceAcquire:
         return out
 
     def read(self, plane, first=0, count=None):
-        """parity hook: `count` doubles of plane "mean", "M2", "psum" or "score" from cell `first` (behind the n_rows M cells: 64
-        guard doubles), flushed first"""
-        count = self.n_rows * self.M - first if count is None else int(count)
-        out = self.ctx.zeros(count)
-        check(lib().bdf_acquire_copy(self.handle, ACQUIRE_PLANES[plane], _ptr(out), int(first), count, 0))
-        return out
+        """parity hook: `count` doubles of plane "mean", "M2", "psum" or "score" from cell `first`"""
+        return super().read(first, count, ACQUIRE_PLANES[plane])
 
     def write(self, planes, draws):
         """parity hook: the cells of the planes {name: device tensor}, and the count of draws they stand for"""
         for name, values in planes.items():
-            check(lib().bdf_acquire_copy(self.handle, ACQUIRE_PLANES[name], _ptr(values), 0, int(values.numel()), 1))
+            super().write(values, None, ACQUIRE_PLANES[name])
         check(lib().bdf_acquire_set_draws(self.handle, float(draws)))
-
-    def close(self):
-        if self.handle:
-            if self.ctx.handle:
-                lib().bdf_acquire_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class DeviceNewRows:
@@ -678,7 +649,6 @@ class DeviceNewRows:
             self.n_known = np.bincount(kid[:, mode0] - 1, minlength=self.n_rows).astype(np.int64)
         self.uhat = ctx.zeros(self.n_rows, D)
         self.factors = ctx.zeros(self.n_rows, D)           # mu + uhat: what the cells are predicted from
-        self.factors_sum = ctx.zeros(self.n_rows, D)
         self.q = ctx.zeros(max(self.so.N, 1)) if not self.foldin else None       # q_j per row of V: the cold path's
         self.report = ctx.zeros(10)                        # bdf_newrows_update's 8, then the ROC of the running mean
         self.draws = 0
@@ -691,16 +661,16 @@ class DeviceNewRows:
         self._out = ctx.zeros(max(self.pairs.n, 1), 3)
 
     def step(self, phase, clamp, class_cut, alpha, lpd):
-        """the three launches behind iteration's last launch, on the row stream.  They read beta and V (written on the row stream) and
-        (mu, Lambda) of this iteration (the hyperprior stream: the row stream is already behind that draw, which beta's update waited
-        for; the wait below says so again).  Everything that overwrites one of them in the next iteration is either on the row stream
-        or waits for the next iteration's rows of this entity, which are enqueued on the row stream behind these launches."""
+        """the three launches behind iteration's last launch, on the row stream -> this draw's factors of the new rows.  They read beta
+        and V (written on the row stream) and (mu, Lambda) of this iteration (the hyperprior stream: the row stream is already behind
+        that draw, which beta's update waited for; the wait below says so again).  Everything that overwrites one of them in the next
+        iteration is either on the row stream or waits for the next iteration's rows of this entity, which are enqueued on the row
+        stream behind these launches."""
         eng, ctx, D, L = self.eng, self.ctx, self.D, lib()
         if eng.ctx_h is not ctx:
             ctx.stream.wait_stream(eng.ctx_h.stream)
         lo, hi = (clamp[0], clamp[1]) if len(clamp) else (1.0, -1.0)
-        on_dev = torch.is_tensor(alpha)
-        alpha_host, alpha_dev = (0.0 if on_dev else float(alpha)), (_ptr(alpha) if on_dev else None)
+        alpha_host, alpha_dev = _alpha_args(alpha)
         if self.F is not None:
             check(L.bdf_uhat(ctx.handle, self.F.handle, D, _ptr(self.st.beta), _ptr(self.st.mu), _ptr(self.uhat), _ptr(self.factors)))
         if self.foldin:
@@ -708,32 +678,21 @@ class DeviceNewRows:
             # bdf_foldin_cells leaves uhat_i in `uhat` (over F_new beta, which `factors` = mu_i has taken in) and (m, q) per cell, and
             # the fold is bdf_newrows_update's on those planes
             t = self.term
-            t.alpha, t.alpha_dev = (1.0 if on_dev else alpha_host), (alpha.data_ptr() if on_dev else None)
+            t.alpha, t.alpha_dev = _alpha_args(alpha, 1.0)
             t.factors[1] = self.so.sample.data_ptr()
             mu = self.factors if self.F is not None else self.st.mu
             check(L.bdf_foldin_cells(ctx.handle, D, self.n_rows, C.byref(t), _ptr(mu), int(self.F is not None), _ptr(self.st.Lambda),
                                      self.pairs.handle, float(self.rel.model.mean_value), _ptr(self.m), _ptr(self.qc), _ptr(self.uhat)))
             check(L.bdf_newrows_update_cells(ctx.handle, self.pairs.handle, _ptr(self.m), _ptr(self.qc), alpha_host, alpha_dev, int(phase),
                                              lo, hi, float(class_cut), int(bool(lpd)), _ptr(self.report)))
-            self._fold_factors(phase, self.uhat)
-            return
-        check(L.bdf_newrows_quad(ctx.handle, D, self.so.N, _ptr(self.st.Lambda), _ptr(self.so.sample), _ptr(self.q)))
-        check(L.bdf_newrows_update(ctx.handle, self.pairs.handle, D, _ptr(self.factors), _ptr(self.so.sample), _ptr(self.q),
-                                   float(self.rel.model.mean_value), alpha_host, alpha_dev, int(phase),
-                                   lo, hi, float(class_cut), int(bool(lpd)), _ptr(self.report)))
-        self._fold_factors(phase, self.factors)
-
-    def _fold_factors(self, phase, factors):
-        """this draw's factors of the new rows into their running sum, on the row stream"""
-        ctx = self.ctx
-        if phase >= 1:
-            with torch.cuda.stream(ctx.stream):
-                if phase == 1:
-                    self.factors_sum.copy_(factors)
-                    self.draws = 1
-                else:
-                    self.factors_sum += factors
-                    self.draws += 1
+        else:
+            check(L.bdf_newrows_quad(ctx.handle, D, self.so.N, _ptr(self.st.Lambda), _ptr(self.so.sample), _ptr(self.q)))
+            check(L.bdf_newrows_update(ctx.handle, self.pairs.handle, D, _ptr(self.factors), _ptr(self.so.sample), _ptr(self.q),
+                                       float(self.rel.model.mean_value), alpha_host, alpha_dev, int(phase),
+                                       lo, hi, float(class_cut), int(bool(lpd)), _ptr(self.report)))
+        if phase >= 1:                  # (the cells' running state holds one draw more)
+            self.draws = 1 if phase == 1 else self.draws + 1
+        return self.uhat if self.foldin else self.factors
 
     def auc(self):
         """AUC_ROC(values .< class_cut, -pred) over the cells with a value (bdf_auc_roc on the running mean, in the caller's order)
@@ -750,16 +709,14 @@ class DeviceNewRows:
             scores.record_stream(ctx.stream)
 
     def result(self):
-        """(n, 3) host array of (pred, stdev, lpd) in the caller's order and the (n*, D) posterior mean of the new rows' factors"""
+        """(n, 3) host array of (pred, stdev, lpd) in the caller's order"""
         ctx = self.ctx
         with torch.cuda.stream(ctx.stream):
             if self.draws < 1:
-                return np.full((self.pairs.n, 3), np.nan), np.full((self.n_rows, self.D), np.nan)
+                return np.full((self.pairs.n, 3), np.nan)
             if self.pairs.n:
                 check(lib().bdf_newrows_result(ctx.handle, self.pairs.handle, _ptr(self._out)))
-            out = self._out[:self.pairs.n].cpu().numpy()
-            fac = (self.factors_sum / float(self.draws)).cpu().numpy()
-        return out, fac
+            return self._out[:self.pairs.n].cpu().numpy()
 
     def state(self):
         """parity hook: the running state as a (5, n) host array in STORAGE order -- mean, M2, sum q, M, A -- and the draws it holds"""
@@ -807,8 +764,9 @@ def device_auc_roc(labels, scores):
     return float(h[:1].view(np.float64)[0]), int(h[1]), int(h[2]), int(h[3])
 
 
-class FeatOperator:
+class FeatOperator(_DeviceObject):
     """bdf_feat: the Entity.F operator on the device (dense / CSR / binary)."""
+    _destroy = "bdf_feat_destroy"
 
     def __init__(self, ctx, F, layout=None):
         """layout (several ranks): the rows of F move to the entity's internal positions (rows nobody owns are zero), and the
@@ -863,17 +821,6 @@ class FeatOperator:
         check(lib().bdf_feat_AtA_mul(self.ctx.handle, self.handle, _ptr(X), X.shape[0], float(lam), _ptr(out)))
         return out
 
-    def close(self):
-        if self.handle:
-            if self.ctx.handle:                 # a closed context has already destroyed its objects
-                lib().bdf_feat_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _dense_mean(r):
@@ -960,27 +907,12 @@ class EntityState:
         # a relation of the entity has background cells (setBackground): the prior its rows are sampled with, made before every
         # row launch (row_prior() of csrc/bdf_gibbs.hip); allocated by background_buffers()
         self.bg_Lambda = self.bg_mu = self.bg_pack = self.bg_alpha_rows = None
-        # the spike-and-slab prior (setSpikeAndSlab): pi, tau, logit pi, log tau (D each; pi = 1/2, tau = 1 at the start) and the
-        # running sums of the result -- [u != 0] per loading; pi, tau and the count n_d per component --, zeroed on the row stream,
-        # which is the one that adds to them (hipMemset)
+        # the spike-and-slab prior (setSpikeAndSlab): pi, tau, logit pi, log tau (D each; pi = 1/2, tau = 1 at the start)
         self.spike = en.spike
-        self.spike_state = self.spike_row_sum = self.spike_hyper_sum = None
-        self.spike_draws = 0
-        if en.spike is not None:
-            self.spike_state = ctx.tensor(np.concatenate([np.full(D, 0.5), np.ones(D), np.zeros(D), np.zeros(D)]))
-            self.spike_row_sum = torch.empty(self.N, D, dtype=torch.float64, device=ctx.device)
-            self.spike_hyper_sum = torch.empty(3 * D, dtype=torch.float64, device=ctx.device)
-            self.spike_reset()
-        # the non-negative prior (setNonNegative): tau (D; 1 at the start) and the running sums of the result -- the rows, tau --,
-        # zeroed on the row stream, which is the one that adds to them
+        self.spike_state = ctx.tensor(np.concatenate([np.full(D, 0.5), np.ones(D), np.zeros(D), np.zeros(D)])) if en.spike is not None else None
+        # the non-negative prior (setNonNegative): tau (D; 1 at the start)
         self.nonneg = en.nonneg
-        self.nonneg_tau = self.nonneg_row_sum = self.nonneg_hyper_sum = None
-        self.nonneg_draws = 0
-        if en.nonneg is not None:
-            self.nonneg_tau = ctx.tensor(np.ones(D))
-            self.nonneg_row_sum = torch.empty(self.N, D, dtype=torch.float64, device=ctx.device)
-            self.nonneg_hyper_sum = torch.empty(D, dtype=torch.float64, device=ctx.device)
-            self.nonneg_reset()
+        self.nonneg_tau = ctx.tensor(np.ones(D)) if en.nonneg is not None else None
         self.F = None
         self.numF = 0
         self.beta = ctx.zeros(D, 0)
@@ -1014,57 +946,11 @@ class EntityState:
             self.bg_pack = ctx.zeros(lib().bdf_prior_pack_doubles(D))
             self.bg_alpha_rows = ctx.zeros(_lib.BDF_MAX_TERMS)
 
-    def spike_reset(self):
-        """the running sums of the spike-and-slab result start again (hipMemsetAsync on the row stream)"""
-        with torch.cuda.stream(self.ctx.stream):
-            self.spike_row_sum.zero_()
-            self.spike_hyper_sum.zero_()
-        self.spike_draws = 0
-
-    def spike_accumulate(self):
-        """the current draw into the running sums, on the row stream"""
-        check(lib().bdf_spike_accumulate(self.ctx.handle, self.D, self.n_real, _ptr(self.sample), _ptr(self.spike_state), _ptr(self.spike_row_sum),
-                                         _ptr(self.spike_hyper_sum)))
-        self.spike_draws += 1
-
     def spike_active(self):
         """how many components have a nonzero loading in the current draw, over the entity's n_real rows: a count, read on the row
         stream, where the rows are written (the read waits for that stream alone)"""
         with torch.cuda.stream(self.ctx.stream):
             return int((self.sample[:self.n_real] != 0).any(dim=0).sum().item())
-
-    def spike_result(self):
-        """the posterior means: inclusion pi_d, precision tau_d, activity n_d / N (D each) and row_inclusion (N x D)"""
-        torch.cuda.synchronize(self.ctx.device)
-        n, D = max(self.spike_draws, 1), self.D
-        h = self.spike_hyper_sum.cpu().numpy()
-        rows = self.spike_row_sum.cpu().numpy()[:self.n_real] / n
-        if self.spike_draws == 0:
-            h, rows = np.full(3 * D, np.nan), np.full((self.n_real, D), np.nan)
-        return {"inclusion": h[:D] / n, "precision": h[D:2 * D] / n, "activity": h[2 * D:] / (n * float(self.n_real)), "row_inclusion": rows}
-
-    def nonneg_reset(self):
-        """the running sums of the non-negative result start again (hipMemsetAsync on the row stream)"""
-        with torch.cuda.stream(self.ctx.stream):
-            self.nonneg_row_sum.zero_()
-            self.nonneg_hyper_sum.zero_()
-        self.nonneg_draws = 0
-
-    def nonneg_accumulate(self):
-        """the current draw into the running sums, on the row stream"""
-        check(lib().bdf_nonneg_accumulate(self.ctx.handle, self.D, self.n_real, _ptr(self.sample), _ptr(self.nonneg_tau), _ptr(self.nonneg_row_sum),
-                                          _ptr(self.nonneg_hyper_sum)))
-        self.nonneg_draws += 1
-
-    def nonneg_result(self):
-        """the posterior means: precision tau_d (D) and factors (N x D, all >= 0)"""
-        torch.cuda.synchronize(self.ctx.device)
-        n, D = max(self.nonneg_draws, 1), self.D
-        h = self.nonneg_hyper_sum.cpu().numpy() / n
-        rows = self.nonneg_row_sum.cpu().numpy()[:self.n_real] / n
-        if self.nonneg_draws == 0:
-            h, rows = np.full(D, np.nan), np.full((self.n_real, D), np.nan)
-        return {"precision": h, "factors": rows}
 
     @property
     def sample(self):
@@ -1099,8 +985,9 @@ class EntityState:
         return a.T.copy() if a.ndim == 2 else a.copy()
 
 
-class DeviceOrdinal:
+class DeviceOrdinal(_DeviceObject):
     """bdf_ordinal: the sampled edges of an ordinal relation with their Metropolis step's state and trace, on the device."""
+    _destroy = "bdf_ordinal_destroy"
 
     def __init__(self, ctx, K, step=0.1, trace_capacity=0):
         self.ctx, self.K, self.capacity = ctx, int(K), int(trace_capacity)
@@ -1115,9 +1002,8 @@ class DeviceOrdinal:
     def step(self, ctx, train, codes, D, factors, mean_value, alpha, rel_tag, adapt, bounds):
         """one Metropolis step on ctx's stream (bdf_ordinal_step); alpha: a float, or a device scalar read on the device; codes: int8
         device tensor, the levels in the caller's order; bounds: (n, 2) device tensor, rewritten when the proposal is accepted"""
-        on_dev = torch.is_tensor(alpha)
         check(lib().bdf_ordinal_step(ctx.handle, self.handle, train.handle, _ptr(codes), int(D), _facs(factors), float(mean_value),
-                                     0.0 if on_dev else float(alpha), _ptr(alpha) if on_dev else None, int(rel_tag), int(adapt), _ptr(bounds)))
+                                     *_alpha_args(alpha), int(rel_tag), int(adapt), _ptr(bounds)))
 
     def bounds(self, ctx, codes, out):
         """out[k] = the bin of level codes[k] under the current edges, on ctx's stream (bdf_ordinal_bounds)"""
@@ -1138,17 +1024,6 @@ class DeviceOrdinal:
         check(lib().bdf_ordinal_proposal(self.handle, edges.ctypes.data_as(_lib.c_dp), C.byref(jac), C.byref(acc), C.byref(lu)))
         return {"edges": edges, "jacobian": jac.value, "accepted": bool(acc.value), "log_u": lu.value}
 
-    def close(self):
-        if self.handle:
-            if self.ctx.handle:
-                lib().bdf_ordinal_destroy(self.handle)
-            self.handle = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _bias_terms(dr):
@@ -1250,10 +1125,6 @@ class GibbsEngine:
             if dr.bg is not None or dr.dense is not None:
                 for e in r.entities:
                     self.ent[self._entity_index(e)].background_buffers(dense=dr.dense is not None)
-        self.scores = None
-        self.begin_scores()
-        self.acquire = None
-        self.begin_acquire()
         self._test_pairs = None
         self._train_pairs = None
         self._new_rows = None
@@ -1496,120 +1367,9 @@ class GibbsEngine:
         self._gibbs_relations = arr            # (the library copies the records; the tensors they point at live in self.rel)
         check(lib().bdf_gibbs_set_relations(self._gibbs, len(rows), C.cast(arr, C.c_void_p)))
 
-    def begin_scores(self):
-        """top-K lists of the first relation (setRecommend): the sum of u.v over the draws for the scored rows,
-        zeroed -- at set-up, and again when macau() continues on an engine it was handed"""
-        if self.scores is not None:
-            self.scores.close()
-            self.scores = None
-        rec = self.data.relations[0].model.recommend if self.data.relations else None
-        if rec is not None:
-            r0, rows = self.data.relations[0], rec["rows"]
-            self.scores = DeviceScores(self.ctx, int(r0.data.dims[0]) if rows is None else len(rows), int(r0.data.dims[1]), self.D, rec["batch"],
-                                       None if rows is None else np.asarray(rows, dtype=np.int64) - 1)
-
-    def begin_acquire(self):
-        """acquisition lists of the first relation (setAcquire): the moment planes of u.v over the draws for the
-        scored rows, zeroed -- at set-up, and again when macau() continues on an engine it was handed"""
-        if self.acquire is not None:
-            self.acquire.close()
-            self.acquire = None
-        acq = self.data.relations[0].model.acquire if self.data.relations else None
-        if acq is not None:
-            r0, rows = self.data.relations[0], acq["rows"]
-            self.acquire = DeviceAcquire(self.ctx, int(r0.data.dims[0]) if rows is None else len(rows), int(r0.data.dims[1]), self.D, acq["batch"],
-                                         None if rows is None else np.asarray(rows, dtype=np.int64) - 1, r0.model.mean_value, acq["threshold"])
-
-    def robust_accumulate(self, ri=0):
-        """(robust relation ri, after the burn-in) this iteration's omega into the running sum, on the row stream: behind the draw
-        that wrote it and ahead of the next one"""
-        dr = self.rel[ri]
-        with torch.cuda.stream(self.ctx.stream):
-            if dr.omega_sum is None:
-                dr.omega_sum = torch.zeros_like(dr.omega)
-            dr.omega_sum += dr.omega
-
-    def robust_mean(self, ri=0):
-        """-> a device scalar, the mean of this iteration's omega (the verbose line reads it with the other scalars)"""
-        with torch.cuda.stream(self.ctx.stream):
-            return self.rel[ri].omega.mean()
-
-    def spike_accumulate(self):
-        """(entities with the spike-and-slab prior, after the burn-in) this draw's inclusions, pi, tau and counts into their running
-        sums, on the row stream once the hyper step of this iteration (the hyperprior stream) has written the state"""
-        if self.ctx_h is not self.ctx:
-            self.ctx.stream.wait_stream(self.ctx_h.stream)
-        for st in self.ent:
-            if st.spike is not None:
-                st.spike_accumulate()
-
-    def nonneg_accumulate(self):
-        """(entities with the non-negative prior, after the burn-in) this draw's rows and tau into their running sums, on the row
-        stream once the hyper step of this iteration (the hyperprior stream) has written tau"""
-        if self.ctx_h is not self.ctx:
-            self.ctx.stream.wait_stream(self.ctx_h.stream)
-        for st in self.ent:
-            if st.nonneg is not None:
-                st.nonneg_accumulate()
-
     def bias_baseline(self, ri, pairs, out):
         """bias_baseline() of relation ri"""
         return bias_baseline(self.rel[ri], self.data.relations[ri].model.mean_value, pairs, out)
-
-    def bias_reset(self):
-        """(an engine that is reused) the biases' running sums start again"""
-        for dr in self.rel:
-            dr.bias_sum = dr.bias_lambda_sum = None
-
-    def bias_accumulate(self):
-        """(relations with biases, after the burn-in) this iteration's biases and precisions into their running sums, on the row
-        stream: behind the draw that wrote them and ahead of the next one"""
-        with torch.cuda.stream(self.ctx.stream):
-            for dr in self.rel:
-                if dr.bias is None:
-                    continue
-                if dr.bias_sum is None:
-                    dr.bias_sum = {m0: torch.zeros_like(b) for m0, b in dr.bias.items()}
-                    dr.bias_lambda_sum = torch.zeros_like(dr.bias_lambda)
-                for m0, b in dr.bias.items():
-                    dr.bias_sum[m0] += b
-                dr.bias_lambda_sum += dr.bias_lambda
-
-    def bias_rms(self, ri=0):
-        """-> device scalars, the rms of this iteration's biases per biased entity of relation ri (the verbose line reads them with
-        the other scalars)"""
-        r, dr = self.data.relations[ri], self.rel[ri]
-        with torch.cuda.stream(self.ctx.stream):
-            return [b[:int(r.data.dims[m0])].square().mean().sqrt() for m0, b in dr.bias.items()]
-
-    def bias_result(self, psamples):
-        """result["bias"]: per relation with biases and biased entity, the posterior mean bias per row and the posterior mean precision"""
-        out = {}
-        for r, dr in zip(self.data.relations, self.rel):
-            if dr.bias is None:
-                continue
-            out[r.name] = {}
-            for t, m0 in enumerate(dr.bias_spec):
-                N = int(r.data.dims[m0])
-                have = dr.bias_sum is not None and psamples
-                out[r.name][r.entities[m0].name] = {
-                    "mean": (dr.bias_sum[m0].cpu().numpy()[:N] / psamples) if have else np.full(N, np.nan),
-                    "precision": float(dr.bias_lambda_sum[t].item() / psamples) if have else float("nan")}
-        return out
-
-    def entity_noise_accumulate(self, ri=0):
-        """(relation ri with a noise precision per row, after the burn-in) this iteration's tau into the running sum, on the row
-        stream: behind the draw that wrote it and ahead of the next one"""
-        dr = self.rel[ri]
-        with torch.cuda.stream(self.ctx.stream):
-            if dr.tau_sum is None:
-                dr.tau_sum = torch.zeros_like(dr.tau)
-            dr.tau_sum += dr.tau
-
-    def entity_noise_mean(self, ri=0):
-        """-> a device scalar, the mean over the rows of this iteration's tau (the verbose line reads it with the other scalars)"""
-        with torch.cuda.stream(self.ctx.stream):
-            return self.rel[ri].tau.mean()
 
     def ordinal_begin(self, burnin, psamples, ri=0):
         """a run of burnin + psamples iterations starts on ordinal relation ri (sampled edges): its object gets a trace of that many
@@ -1989,7 +1749,7 @@ class GibbsEngine:
             self.sync()
         except Exception:
             pass
-        for p in (self._test_pairs, self._train_pairs, self.scores, self.acquire, self._new_rows):
+        for p in (self._test_pairs, self._train_pairs, self._new_rows):
             if p is not None:
                 p.close()
         for st in self.ent:

@@ -98,7 +98,7 @@ def main():
         return
     from background_probe import implicit_movielens, relation_data
     N, M, ids, test, tv, source = implicit_movielens()
-    engines, at = {}, {}
+    engines, at, acq = {}, {}, {}
     for name in ("plain", "acquire_b8"):
         rd = relation_data(B, N, M, ids, np.ones(len(ids)), test, tv, 10.0, background=0.1)
         rel = rd.relations[0]
@@ -110,6 +110,8 @@ def main():
             eng.step(i, 0, (), rel.class_cut)
         eng.sync()
         eng.warm_device(50.0)
+        # (macau()'s Acquire summary builds the planes for a run; the probe builds its own on the engine's row context)
+        acq[name] = DeviceAcquire(eng.ctx, N, M, D, BATCH, None, rel.model.mean_value, 0.5) if name != "plain" else None
         engines[name], at[name] = (eng, rel), 4
     per = {name: [] for name in engines}
     for _ in range(args.rounds):
@@ -119,8 +121,8 @@ def main():
             t0 = time.perf_counter()
             for i in range(at[name], at[name] + args.iters):
                 eng.step(i, 0, (), rel.class_cut)
-                if eng.acquire is not None:
-                    eng.acquire.push(*eng.factors_of(rel), rel.model.alpha)
+                if acq[name] is not None:
+                    acq[name].push(*eng.factors_of(rel), rel.model.alpha)
             eng.sync()
             torch.cuda.synchronize()
             per[name].append((time.perf_counter() - t0) * 1e6 / args.iters)

@@ -57,6 +57,7 @@ def main():
     args = ap.parse_args()
     import torch
     import bdf_amd as B
+    from bdf_amd.engine import DeviceScores
     D, K, c0 = args.D, args.K, args.c0
     N, M, ids, test, tv, source = implicit_movielens()
     ones = np.ones(len(ids))
@@ -64,7 +65,7 @@ def main():
                       "c0": c0, "alpha": args.alpha, "sum_bytes": N * M * 8, "derived_flush_bytes": 16 * N * M,
                       "derived_flops_per_draw": 2 * D * N * M}), flush=True)
     batches = {"recommend_b1": 1, "recommend_b8": 8, "recommend_b32": 32}
-    engines, at, extra = {}, {}, {}
+    engines, at, extra, scores = {}, {}, {}, {}
     for name in ["background", *batches, "full_prediction"]:
         rd = relation_data(B, N, M, ids, ones, test, tv, args.alpha, background=c0)
         rel = rd.relations[0]
@@ -78,7 +79,9 @@ def main():
         eng.warm_device(50.0)
         engines[name], at[name] = (eng, rel), 4
         if name in batches:
-            extra[name] = lambda eng=eng, rel=rel: eng.scores.push(*eng.factors_of(rel))
+            # (macau()'s Recommend summary builds the sum for a run; the probe builds its own on the engine's row context)
+            scores[name] = DeviceScores(eng.ctx, N, M, D, batches[name])
+            extra[name] = lambda eng=eng, rel=rel, sc=scores[name]: sc.push(*eng.factors_of(rel))
         elif name == "full_prediction":
             yhat = torch.zeros((N, M), dtype=torch.float64, device=eng.ctx.device)
 
@@ -107,7 +110,7 @@ def main():
                       "b8_per_round_not_above_full_prediction": [bool(a <= b) for a, b in zip(per["recommend_b8"], per["full_prediction"])]}), flush=True)
     # single launches by device events
     eng, rel = engines["recommend_b32"]
-    sc, ctx = eng.scores, eng.ctx
+    sc, ctx = scores["recommend_b32"], eng.ctx
     facs = eng.factors_of(rel)
     sc.flush()
     parts = {"what": "launches_us", "push": round(event_us(torch, ctx.stream, args.reps, sc.flush, lambda: sc.push(*facs)), 1)}
