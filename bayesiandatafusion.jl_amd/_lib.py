@@ -153,6 +153,7 @@ _SIGS = {
     "bdf_ctx_item_size": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "bdf_dev_alloc": (C.c_int, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "bdf_dev_free": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "bdf_dev_live": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bdf_h2d": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "bdf_d2h": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "bdf_index_build": (C.c_int, [C.c_int, c_i64p, C.c_int64, C.c_void_p, C.c_int, C.POINTER(c_i64p), C.POINTER(c_i64p)]),

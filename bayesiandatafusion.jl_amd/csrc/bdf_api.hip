@@ -7,6 +7,7 @@
 #include <cmath>
 #include <numeric>
 #include <atomic>
+#include <memory>
 
 static thread_local char g_err[512] = "";
 
@@ -22,6 +23,14 @@ extern "C" const char *bdf_last_error(void) { return g_err; }
 extern "C" int bdf_version(void) { return 100; }
 
 // ---- context -----------------------------------------------------------------------------
+// K1c (k_rows_col.hip): on by default with pieces of at most 128 observations; BDF_K1_COL=0: off, BDF_K1_COL=<n>: that piece size
+static int col_piece_default()
+{
+    int piece = getenv("BDF_K1_COL") ? atoi(getenv("BDF_K1_COL")) : 128;
+    if (piece == 1) piece = 128;
+    return piece == 0 ? 0 : std::min(4096, std::max(8, piece));
+}
+
 extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx **out)
 {
     BDF_REQUIRE(out != nullptr, BDF_ERR_ARG, "bdf_ctx_create: out is NULL");
@@ -38,120 +47,57 @@ extern "C" int bdf_ctx_create(int device, void *stream, uint64_t seed, bdf_ctx *
         bdf_set_error("bdf_ctx_create: device %d is %s; this library is built for gfx950 only", device, prop.gcnArchName);
         return BDF_ERR_NOGPU;
     }
-    bdf_ctx *c = new bdf_ctx();
-    c->sweep_dev = nullptr; c->flag_dev = nullptr; c->flag_host = nullptr; c->scratch = nullptr; c->scratch2 = nullptr; c->cg_status = nullptr; c->cg_part = nullptr;
-    c->hyper_fuse = false; c->hyper_partial = nullptr; c->hyper_nblocks = 0; c->hyper_sumU = c->hyper_UUt = nullptr;
-    c->hyper_chain = false; c->hyper_count = nullptr; c->hyper_chain_draws = nullptr;
-    c->own_stream = false; c->stream = nullptr; c->rows = nullptr;
-    struct Guard { bdf_ctx *c; ~Guard() { if (c) bdf_ctx_destroy(c); } } guard{c};        // error paths free what was allocated
+    std::unique_ptr<bdf_ctx> c(new bdf_ctx());       // error paths free what was allocated
     c->device = device;
     c->n_cus = prop.multiProcessorCount;
     c->seed = seed;
-    c->own_stream = false;
     c->stream = (hipStream_t)stream;          // NULL is the device's default stream
-    BDF_HIP(hipMalloc((void **)&c->sweep_dev, sizeof(uint32_t)));
-    BDF_HIP(hipHostMalloc((void **)&c->flag_host, 16 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    int rc;
+    if ((rc = c->sweep_dev.alloc(1)) || (rc = c->flag_host.alloc(16))) return rc;
     memset(c->flag_host, 0, 16 * sizeof(int));
     BDF_HIP(hipHostGetDevicePointer((void **)&c->flag_dev, c->flag_host, 0));
     BDF_HIP(hipMemsetAsync(c->sweep_dev, 0, sizeof(uint32_t), c->stream));
-    c->time_start = c->time_stop = nullptr;
-    c->time_h_start = c->time_h_stop = nullptr;
-    c->sweep_host = 0;
-    c->rows_span = nullptr;
-    c->rows_ready = nullptr; c->rows_ready_want = 0; c->hyper_ready = nullptr; c->hyper_ready_value = 0;
-    c->rows_done = nullptr; c->rows_done_added = -1; c->hyper_wait = nullptr; c->hyper_wait_target = 0;
-    c->warnings = 0;
-    c->reserve_cus = 0;
-    c->on_reserved = 0;
-    c->skip_flag = nullptr;
-    c->cg_status = nullptr; c->cg_part = nullptr;
-    c->hyper_fuse = false; c->hyper_partial = nullptr; c->hyper_nblocks = 0; c->hyper_sumU = c->hyper_UUt = nullptr;
-    c->hyper_chain = false; c->hyper_count = nullptr; c->hyper_chain_draws = nullptr;
-    c->cg_gen = 0;
-    c->cg_bar = nullptr;
     c->rows = bdf_rows_state_create();
-    c->norm_part = nullptr;
-    c->newrows_W = nullptr;
-    c->scratch = nullptr;
-    c->scratch2 = nullptr;
-    c->scratch2_bytes = 0;
-    c->scratch_bytes = 0;
-    c->item_size = 192;
-    c->piece_size = 128;
-    c->item_auto = true;
-    c->small_max = getenv("BDF_K1_SMALL") ? atoi(getenv("BDF_K1_SMALL")) : 48;
-    c->small_min_rows = getenv("BDF_K1_SMALL_MIN_ROWS") ? atoll(getenv("BDF_K1_SMALL_MIN_ROWS")) : 8192;
-    c->lr_max = getenv("BDF_LOWRANK") ? atoi(getenv("BDF_LOWRANK")) : -1;
-    c->lr_min_rows = getenv("BDF_LOWRANK_MIN_ROWS") ? atoll(getenv("BDF_LOWRANK_MIN_ROWS")) : 8192;
-    // K1c (k_rows_col.hip): on by default with pieces of at most 128 observations; BDF_K1_COL=0: off, BDF_K1_COL=<n>: that piece size
-    c->col_piece = getenv("BDF_K1_COL") ? atoi(getenv("BDF_K1_COL")) : 128;
-    if (c->col_piece == 1) c->col_piece = 128;
-    if (c->col_piece != 0) c->col_piece = std::min(4096, std::max(8, c->col_piece));
-    c->col_explicit = false;
-    c->gather_image = 1;
-    c->gimg_trust = false;
-    c->lr_T = nullptr; c->lr_vt = nullptr; c->lr_vt_bytes = 0; c->lr_mrows = nullptr; c->lr_mrows_bytes = 0;
+    if (getenv("BDF_K1_SMALL")) c->small_max = atoi(getenv("BDF_K1_SMALL"));
+    if (getenv("BDF_K1_SMALL_MIN_ROWS")) c->small_min_rows = atoll(getenv("BDF_K1_SMALL_MIN_ROWS"));
+    if (getenv("BDF_LOWRANK")) c->lr_max = atoi(getenv("BDF_LOWRANK"));
+    if (getenv("BDF_LOWRANK_MIN_ROWS")) c->lr_min_rows = atoll(getenv("BDF_LOWRANK_MIN_ROWS"));
+    c->col_piece = col_piece_default();
     {
         const char *force = getenv("BDF_GATHER");
         c->gather_mode = force && !strcmp(force, "general") ? 1 : (force && !strcmp(force, "wide") ? 2 : 0);
     }
-    guard.c = nullptr;
-    *out = c;
+    *out = c.release();
     return BDF_OK;
+}
+
+bdf_ctx::~bdf_ctx()
+{
+    hipSetDevice(device);
+    hipStreamSynchronize(stream);
+    bdf_rows_state_delete(rows);
 }
 
 extern "C" int bdf_ctx_destroy(bdf_ctx *ctx)
 {
-    if (!ctx) return BDF_OK;
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    bdf_rows_state_destroy(ctx);
-    if (ctx->scratch) hipFree(ctx->scratch);
-    if (ctx->sweep_dev) hipFree(ctx->sweep_dev);
-    if (ctx->flag_host) hipHostFree(ctx->flag_host);
-    if (ctx->scratch2) hipFree(ctx->scratch2);
-    if (ctx->cg_status) hipHostFree((void *)ctx->cg_status);
-    if (ctx->cg_part) hipFree(ctx->cg_part);
-    if (ctx->cg_bar) hipFree(ctx->cg_bar);
-    if (ctx->hyper_count) hipFree(ctx->hyper_count);
-    if (ctx->lr_T) hipFree(ctx->lr_T);
-    if (ctx->lr_vt) hipFree(ctx->lr_vt);
-    if (ctx->lr_mrows) hipFree(ctx->lr_mrows);
-    if (ctx->norm_part) hipFree(ctx->norm_part);
-    if (ctx->newrows_W) hipFree(ctx->newrows_W);
-    if (ctx->own_stream) hipStreamDestroy(ctx->stream);
-    delete ctx;
+    if (ctx) delete ctx;
     return BDF_OK;
 }
 
-int bdf_scratch(bdf_ctx *ctx, size_t bytes, void **out)
+// a context's scratch block `which` (grown on demand, never shrunk) of at least `bytes` bytes
+static int scratch_of(bdf_ctx *ctx, DevBuf<void> &which, size_t bytes, void **out)
 {
-    if (bytes > ctx->scratch_bytes) {
+    if (bytes > which.bytes()) {
         // growing frees the old block: wait for work that may still read it
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch) BDF_HIP(hipFree(ctx->scratch));
-        size_t nb = std::max(bytes, ctx->scratch_bytes * 2);
+        size_t nb = std::max(bytes, which.bytes() * 2);
         nb = (nb + 255) & ~(size_t)255;
-        BDF_HIP(hipMalloc(&ctx->scratch, nb));
-        ctx->scratch_bytes = nb;
+        if (int rc = which.grow(nb, ctx->stream)) return rc;
     }
-    *out = ctx->scratch;
+    *out = which.get();
     return BDF_OK;
 }
-
-int bdf_scratch2(bdf_ctx *ctx, size_t bytes, void **out)
-{
-    if (bytes > ctx->scratch2_bytes) {
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->scratch2) BDF_HIP(hipFree(ctx->scratch2));
-        size_t nb = std::max(bytes, ctx->scratch2_bytes * 2);
-        nb = (nb + 255) & ~(size_t)255;
-        BDF_HIP(hipMalloc(&ctx->scratch2, nb));
-        ctx->scratch2_bytes = nb;
-    }
-    *out = ctx->scratch2;
-    return BDF_OK;
-}
+int bdf_scratch(bdf_ctx *ctx, size_t bytes, void **out) { return scratch_of(ctx, ctx->scratch, bytes, out); }
+int bdf_scratch2(bdf_ctx *ctx, size_t bytes, void **out) { return scratch_of(ctx, ctx->scratch2, bytes, out); }
 
 __global__ void k_set_u32(uint32_t *p, uint32_t v) { *p = v; }
 __global__ void k_inc_u32(uint32_t *p) { *p = *p + 1; }
@@ -231,9 +177,7 @@ extern "C" int bdf_ctx_set_col_rows(bdf_ctx *ctx, int max_piece)
     BDF_REQUIRE(ctx && (max_piece == 0 || max_piece == -1 || (max_piece >= 8 && max_piece <= 4096)), BDF_ERR_ARG,
                 "bdf_ctx_set_col_rows: -1 (default), 0 (off) or 8..4096 observations per piece");
     if (max_piece == -1) {            // the default again: BDF_K1_COL or 128, for launches whose item size the caller has not set
-        ctx->col_piece = getenv("BDF_K1_COL") ? atoi(getenv("BDF_K1_COL")) : 128;
-        if (ctx->col_piece == 1) ctx->col_piece = 128;
-        if (ctx->col_piece != 0) ctx->col_piece = std::min(4096, std::max(8, ctx->col_piece));
+        ctx->col_piece = col_piece_default();
         ctx->col_explicit = false;
         return BDF_OK;
     }
@@ -279,9 +223,9 @@ extern "C" int bdf_ctx_sync(bdf_ctx *ctx)
            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_spin).count() < 300.0) { }
     if (st == hipErrorNotReady) st = hipStreamSynchronize(ctx->stream);
     BDF_HIP(st);
-    int flag = __atomic_load_n(ctx->flag_host, __ATOMIC_ACQUIRE);
+    int flag = __atomic_load_n(ctx->flag_host.get(), __ATOMIC_ACQUIRE);
     if (flag) {
-        __atomic_store_n(ctx->flag_host, 0, __ATOMIC_RELEASE);      // (the stream is idle: nothing of this context is in flight)
+        __atomic_store_n(ctx->flag_host.get(), 0, __ATOMIC_RELEASE);      // (the stream is idle: nothing of this context is in flight)
         ctx->warnings |= (uint32_t)flag & BDF_WARN_CG_MAXITER;
         flag &= ~(int)BDF_WARN_CG_MAXITER;
     }
@@ -367,6 +311,13 @@ extern "C" int bdf_dev_free(bdf_ctx *ctx, void *dptr)
         BDF_HIP(hipStreamSynchronize(ctx->stream));
         BDF_HIP(hipFree(dptr));
     }
+    return BDF_OK;
+}
+
+extern "C" int bdf_dev_live(int64_t *blocks, int64_t *bytes)
+{
+    if (blocks) *blocks = g_dev_live_blocks.load(std::memory_order_relaxed);
+    if (bytes) *bytes = g_dev_live_bytes.load(std::memory_order_relaxed);
     return BDF_OK;
 }
 
@@ -468,8 +419,7 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
     auto idat = [&](int64_t i, int m) -> int64_t { return id_at(ids, id_bytes, nnz, i, m); };
 
     static std::atomic<uint64_t> next_serial{1};
-    bdf_rel *r = new bdf_rel();
-    struct Guard { bdf_rel *r; ~Guard() { if (r) bdf_relation_destroy(r); } } guard{r};        // error paths free what was built
+    std::unique_ptr<bdf_rel> r(new bdf_rel());       // error paths free what was built
     r->ctx = ctx;
     r->serial = next_serial.fetch_add(1);
     r->n_modes = n_modes;
@@ -478,10 +428,7 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
     for (int m = 0; m < n_modes; m++) {
         r->dims[m] = dims[m];
         r->nint[m] = sharded ? cmax[m] * world * chunks : dims[m];
-        r->idx[m].rowptr_dev = nullptr; r->idx[m].colidx_dev = nullptr; r->idx[m].vals_dev = nullptr; r->idx[m].perm_dev = nullptr;
-        r->idx[m].order_dev = nullptr; r->idx[m].own_nnz = 0; r->idx[m].packed_dev = nullptr;
     }
-    r->n_codes = 0; r->table_dev = nullptr;
     double s = 0.0;
     for (int64_t i = 0; i < nnz; i++) s += values[i];
     r->value_mean = nnz ? s / (double)nnz : NAN;
@@ -506,7 +453,7 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
             code_by_row[(size_t)i] = (uint8_t)(std::lower_bound(table.begin(), table.end(), values[i]) - table.begin());
         std::vector<double> t256(256, 0.0);
         std::copy(table.begin(), table.end(), t256.begin());
-        int rct = bdf_upload(&r->table_dev, t256);
+        int rct = r->table_dev.upload(t256);
         if (rct) return rct;
         r->n_codes = (int)table.size();
     }
@@ -542,15 +489,15 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
                     plane++;
                 }
             }
-            if ((rc = bdf_upload(&ix.rowptr_dev, ix.rowptr))) return rc;
-            if ((rc = bdf_upload(&ix.colidx_dev, colidx))) return rc;
-            if ((rc = bdf_upload(&ix.vals_dev, vals))) return rc;
-            if ((rc = bdf_upload(&ix.perm_dev, perm))) return rc;
-            if ((rc = bdf_upload(&ix.order_dev, ix.order))) return rc;
+            if ((rc = ix.rowptr_dev.upload(ix.rowptr))) return rc;
+            if ((rc = ix.colidx_dev.upload(colidx))) return rc;
+            if ((rc = ix.vals_dev.upload(vals))) return rc;
+            if ((rc = ix.perm_dev.upload(perm))) return rc;
+            if ((rc = ix.order_dev.upload(ix.order))) return rc;
             if (r->n_codes && r->nint[1 - m] < (1 << 24)) {
                 std::vector<uint32_t> packed((size_t)nnz + 1, 0u);          // (+1: the row kernel reads the words in pairs)
                 for (int64_t q = 0; q < nnz; q++) packed[(size_t)q] = ((uint32_t)code_by_row[(size_t)perm[(size_t)q]] << 24) | (uint32_t)colidx[(size_t)q];
-                if ((rc = bdf_upload(&ix.packed_dev, packed))) return rc;
+                if ((rc = ix.packed_dev.upload(packed))) return rc;
             }
             ix.own_nnz = nnz;
             continue;
@@ -597,17 +544,16 @@ static int relation_create(bdf_ctx *ctx, int n_modes, const int64_t *dims, int64
                 }
             }
         }
-        if ((rc = bdf_upload(&ix.colidx_dev, colidx))) return rc;
-        if ((rc = bdf_upload(&ix.vals_dev, vals))) return rc;
-        if ((rc = bdf_upload(&ix.perm_dev, perm))) return rc;
+        if ((rc = ix.colidx_dev.upload(colidx))) return rc;
+        if ((rc = ix.vals_dev.upload(vals))) return rc;
+        if ((rc = ix.perm_dev.upload(perm))) return rc;
         if (r->n_codes && r->nint[1 - m] < (1 << 24)) {
             std::vector<uint32_t> packed((size_t)on + 1, 0u);
             for (int64_t q = 0; q < on; q++) packed[(size_t)q] = ((uint32_t)code_by_row[(size_t)perm[(size_t)q]] << 24) | (uint32_t)colidx[(size_t)q];
-            if ((rc = bdf_upload(&ix.packed_dev, packed))) return rc;
+            if ((rc = ix.packed_dev.upload(packed))) return rc;
         }
     }
-    guard.r = nullptr;
-    *out = r;
+    *out = r.release();
     return BDF_OK;
 }
 
@@ -625,19 +571,17 @@ extern "C" int bdf_relation_create_sharded(bdf_ctx *ctx, int n_modes, const int6
     return relation_create(ctx, n_modes, dims, nnz, ids, id_bytes, values, pos, cmax, rank, world, chunks, out);
 }
 
+bdf_rel::~bdf_rel()
+{
+    if (!ctx) return;
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+    bdf_plans_release(ctx, serial);
+}
+
 extern "C" int bdf_relation_destroy(bdf_rel *rel)
 {
-    if (!rel) return BDF_OK;
-    hipSetDevice(rel->ctx->device);
-    hipStreamSynchronize(rel->ctx->stream);
-    bdf_plans_release(rel->ctx, rel->serial);
-    for (int m = 0; m < rel->n_modes; m++) {
-        bdf_mode_index &ix = rel->idx[m];
-        hipFree(ix.rowptr_dev); hipFree(ix.colidx_dev); hipFree(ix.vals_dev); hipFree(ix.perm_dev); hipFree(ix.order_dev);
-        hipFree(ix.packed_dev);
-    }
-    hipFree(rel->table_dev);
-    delete rel;
+    if (rel) delete rel;
     return BDF_OK;
 }
 

@@ -1,6 +1,7 @@
 // bdf_common.h -- internal declarations shared by the HIP translation units of libbdf_hip.so
 #pragma once
 #include <map>
+#include <memory>
 #include <array>
 #include <algorithm>
 #include <numeric>
@@ -29,14 +30,7 @@ void bdf_set_error(const char *fmt, ...);
         if (!(cond)) { bdf_set_error(__VA_ARGS__); return (code); }                        \
     } while (0)
 
-// a device copy of a host vector (at least 16 bytes: an empty vector still gets an address)
-template <typename T>
-int bdf_upload(T **dst, const std::vector<T> &src)
-{
-    BDF_HIP(hipMalloc((void **)dst, std::max<size_t>(src.size() * sizeof(T), 16)));
-    if (!src.empty()) BDF_HIP(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-    return BDF_OK;
-}
+#include "dev_buf.h"
 
 // rows 0..N-1 by falling degree(row), rows of equal degree in row order (a stable sort)
 template <typename Degree>
@@ -50,82 +44,84 @@ std::vector<int32_t> rows_by_degree(int64_t N, Degree degree)
 
 struct bdf_rows_state;
 struct bdf_ctx {
-    int device;
-    int n_cus;                 // the device's CUs (multiProcessorCount)
-    hipStream_t stream;
-    bool own_stream;
-    uint64_t seed;
-    uint32_t *sweep_dev;       // Gibbs iteration counter in device memory
-    uint32_t sweep_host;       // mirror of the last bdf_ctx_set_sweep / advance
+    int device = 0;
+    int n_cus = 0;             // the device's CUs (multiProcessorCount)
+    hipStream_t stream = nullptr;   // borrowed: the caller's, or a pooled one (NULL is the device's default stream)
+    uint64_t seed = 0;
+    DevBuf<uint32_t> sweep_dev;    // Gibbs iteration counter in device memory
+    uint32_t sweep_host = 0;   // mirror of the last bdf_ctx_set_sweep / advance
     // scratch (grown on demand, never shrunk)
-    void *scratch;
-    size_t scratch_bytes;
-    void *scratch2;            // second block: split-K partials of the dense products (used while `scratch` is held)
-    size_t scratch2_bytes;
-    int small_max;             // k_rows_small: longest row (observations) sampled four to a wave at D <= 16; 0: off
-    int64_t small_min_rows;    // ... and the smallest entity (rows) for which it is used
+    DevBuf<void> scratch;
+    DevBuf<void> scratch2;     // second block: split-K partials of the dense products (used while `scratch` is held)
+    int small_max = 48;        // k_rows_small: longest row (observations) sampled four to a wave at D <= 16; 0: off
+    int64_t small_min_rows = 8192; // ... and the smallest entity (rows) for which it is used
     // k_rows_lr (k_rows_lr.hip): rows of few observations sampled by the low-rank map instead of the reference's
-    int lr_max;                // longest row (observations) sampled that way at D > 16; -1: min(16, D / 2); 0: off
-    int64_t lr_min_rows;       // ... and the smallest number of such rows in a launch for which it is used
-    int col_piece;             // K1c (k_rows_col.hip): one two-mode relation at 16 < D <= 32 four rows per wave in the column layout, rows cut
+    int lr_max = -1;           // longest row (observations) sampled that way at D > 16; -1: min(16, D / 2); 0: off
+    int64_t lr_min_rows = 8192; // ... and the smallest number of such rows in a launch for which it is used
+    int col_piece = 128;       // K1c (k_rows_col.hip): one two-mode relation at 16 < D <= 32 four rows per wave in the column layout, rows cut
                                // into pieces of at most this many observations; 0: off
-    bool col_explicit;         // ... set by the caller (bdf_ctx_set_col_rows): taken also when the caller chose K1's item size
-    int gather_image;          // K1c at D = 32 gathers from the opposite entity's gather image (k_gather_image.hip): 1 the pair image (the
+    bool col_explicit = false; // ... set by the caller (bdf_ctx_set_col_rows): taken also when the caller chose K1's item size
+    int gather_image = 1;      // K1c at D = 32 gathers from the opposite entity's gather image (k_gather_image.hip): 1 the pair image (the
                                // default), 2 the full image, 0 off -- the sample itself (bdf_ctx_set_gather_image)
-    bool gimg_trust;           // (library-internal) the next row launch may take the opposite sample's image as its own launch left it: the
+    bool gimg_trust = false;   // (library-internal) the next row launch may take the opposite sample's image as its own launch left it: the
                                // caller knows of every write to that sample (bdf_gibbs_sweep); cleared by the launch
-    double *lr_T;              // Tf | Tb | Tm (64 x 64 each) | L' mu (64): the launch's constants (k_lr_prep)
-    double *lr_mrows;          // per-row prior means transformed (L' mu_i, rows of DP doubles), grown on demand
-    size_t lr_mrows_bytes;
-    double *lr_vt;             // the opposite entity's factor matrix transformed (V L^-T), grown on demand
-    size_t lr_vt_bytes;
-    int *flag_dev;             // not-positive-definite flag (bits 1..32: errors; 64: BDF_WARN_CG_MAXITER): the device address of
-    int *flag_host;            // ... a word of mapped, coherent HOST memory (kernels atomicOr into it on their error paths only;
+    DevBuf<double> lr_T;       // Tf | Tb | Tm (64 x 64 each) | L' mu (64): the launch's constants (k_lr_prep)
+    DevBuf<double> lr_mrows;   // per-row prior means transformed (L' mu_i, rows of DP doubles), grown on demand
+    DevBuf<double> lr_vt;      // the opposite entity's factor matrix transformed (V L^-T), grown on demand
+    int *flag_dev = nullptr;   // not-positive-definite flag (bits 1..32: errors; 64: BDF_WARN_CG_MAXITER): the device address of
+    DevBuf<int> flag_host = DevBuf<int>::pinned(kPinnedMappedCoherent);
+                               // ... a word of mapped, coherent HOST memory (kernels atomicOr into it on their error paths only;
                                // bdf_ctx_sync reads it without a copy -- a 4-byte blocking device-to-host copy is ~10 us)
-    uint32_t warnings;         // non-fatal bits seen by bdf_ctx_sync, until bdf_ctx_warnings takes them
-    int item_size;             // K1: observations per work item (rows longer than this are split)
-    int piece_size;            // K1: ... into pieces of at most this many observations
-    bool item_auto;            // K1: neither was set by the caller: large launches take larger items (rows_plan.hip: route_key)
-    int gather_mode;           // K1 parity hook: 0 auto, 1 general gather path, 2 lean path with 64-bit row offsets (D > 32)
-    hipEvent_t time_start, time_stop;      // bdf_ctx_time_next_rows: attached to the next row-kernel dispatch, then cleared
-    unsigned long long *rows_span;         // bdf_ctx_span_next_rows: SampleArgs::span of the next row launch, then cleared
-    const uint32_t *rows_ready;            // (library-internal) SampleArgs::ready of the next row launch, then cleared
-    uint32_t rows_ready_want;
+    uint32_t warnings = 0;     // non-fatal bits seen by bdf_ctx_sync, until bdf_ctx_warnings takes them
+    int item_size = 192;       // K1: observations per work item (rows longer than this are split)
+    int piece_size = 128;      // K1: ... into pieces of at most this many observations
+    bool item_auto = true;     // K1: neither was set by the caller: large launches take larger items (rows_plan.hip: route_key)
+    int gather_mode = 0;       // K1 parity hook: 0 auto, 1 general gather path, 2 lean path with 64-bit row offsets (D > 32)
+    // borrowed, the caller's events -- bdf_ctx_time_next_rows: attached to the next row-kernel dispatch, then cleared
+    hipEvent_t time_start = nullptr, time_stop = nullptr;
+    unsigned long long *rows_span = nullptr;   // borrowed -- bdf_ctx_span_next_rows: SampleArgs::span of the next row launch, then cleared
+    const uint32_t *rows_ready = nullptr;      // borrowed (library-internal) SampleArgs::ready of the next row launch, then cleared
+    uint32_t rows_ready_want = 0;
     // (library-internal, bdf_gibbs_sweep) the rows' hand-over to the hyperprior chain WITHOUT an event: when the next bdf_sample_rows is
     // one k_rows_col launch, every wave of it -- its rows written through, the stores drained -- adds 1 to shard (wave % 64) of these
     // 64 words (16 words apart), and rows_done_added says how many will; else rows_done_added stays -1 and the caller uses the event
-    uint32_t *rows_done;
-    int64_t rows_done_added;
+    uint32_t *rows_done = nullptr;             // borrowed
+    int64_t rows_done_added = -1;
     // (library-internal, bdf_sample_rows_nonneg) the next system dump takes positions rows_k0 .. rows_k1 - 1 of the shard's row list
     // only and writes the system of position k at index k - rows_k0; rows_k1 = 0: every row at its own index.  Cleared by the launch
-    int64_t rows_k0, rows_k1;
-    int64_t nonneg_chunk;                  // bdf_ctx_set_nonneg_chunk: rows per chunk of the non-negative prior's launches; 0: the default
-    const uint32_t *hyper_wait;            // (library-internal) ... and the next one-launch chain (k_hyper_chain) polls their sum for this target
-    uint32_t hyper_wait_target;
-    uint32_t *hyper_ready;                 // (library-internal) word the next bdf_hyper_sample sets to hyper_ready_value once its pack is written, then cleared
-    uint32_t hyper_ready_value;
-    hipEvent_t time_h_start, time_h_stop;  // bdf_ctx_time_next_hyper: start of the next sums kernel, end of the next draw kernel
+    int64_t rows_k0 = 0, rows_k1 = 0;
+    int64_t nonneg_chunk = 0;                  // bdf_ctx_set_nonneg_chunk: rows per chunk of the non-negative prior's launches; 0: the default
+    const uint32_t *hyper_wait = nullptr;      // borrowed (library-internal) ... and the next one-launch chain (k_hyper_chain) polls their sum for this target
+    uint32_t hyper_wait_target = 0;
+    uint32_t *hyper_ready = nullptr;           // borrowed (library-internal) word the next bdf_hyper_sample sets to hyper_ready_value once its pack is written, then cleared
+    uint32_t hyper_ready_value = 0;
+    hipEvent_t time_h_start = nullptr, time_h_stop = nullptr;  // borrowed -- bdf_ctx_time_next_hyper: start of the next sums kernel, end of the next draw kernel
     // batched CG (k_feat_cg.hip): device flag that lets product kernels enqueued ahead return at once (NULL outside a solve),
     // and the host-mapped words through which the device reports (iteration, active columns)
     // CU reservation (bdf_ctx_create_rows): the last... the first `reserve_cus` bits of the CU mask (one CU per XCD each 8)
     // are kept free of this context's kernels, for the side context created with reserved = 1
-    int reserve_cus;           // CUs set aside by the row context this one belongs to (0: none)
-    int on_reserved;           // this context's stream runs on the reserved CUs only
-    const int *skip_flag;
-    volatile uint64_t *cg_status;
+    int reserve_cus = 0;       // CUs set aside by the row context this one belongs to (0: none)
+    int on_reserved = 0;       // this context's stream runs on the reserved CUs only
+    const int *skip_flag = nullptr;            // borrowed
+    DevBuf<volatile uint64_t> cg_status = DevBuf<volatile uint64_t>::pinned(kPinnedMapped);
     // bdf_gibbs_sweep: the next bdf_hyper_sums of a small entity leaves its work to the bdf_hyper_sample that follows it on this context
-    bool hyper_fuse;
-    const double *hyper_partial; int hyper_nblocks; double *hyper_sumU, *hyper_UUt;
-    bool hyper_chain;                   // ... and launches nothing itself: the draw's launch carries the sums' workgroups (k_hyper_chain)
-    int hyper_chain_D; int64_t hyper_chain_N, hyper_chain_rpb; const double *hyper_chain_sample, *hyper_chain_uhat;
-    unsigned *hyper_count;              // partial workgroups finished (k_hyper_chain), allocated at first use
-    double *hyper_chain_draws;          // (bdf_gibbs_sweep) the chain's launch also makes the entity's random part (k_hyper_draws' values) into this buffer
-    double *cg_part;                    // partial dot products of the chunked CG step (k_cg_long_*), allocated at first use
-    uint32_t cg_gen;
-    unsigned *cg_bar;                   // the hand-over counter of the one-launch CG solve (k_cg_resident), allocated at first use
-    bdf_rows_state *rows;               // the row launcher's own (rows_plan.hip): cached plans, dispatch counts, what lr_T / lr_vt were computed from
-    double *norm_part;                  // bdf_norm2's per-workgroup partial sums (k_auc.hip), allocated at first use
-    double *newrows_W;                  // bdf_newrows_quad's L^-1 of the call's Lambda (k_newrows.hip: BDF_MAX_D x BDF_MAX_D), allocated at first use
+    bool hyper_fuse = false;
+    // borrowed, the caller's buffers of that call
+    const double *hyper_partial = nullptr; int hyper_nblocks = 0; double *hyper_sumU = nullptr, *hyper_UUt = nullptr;
+    bool hyper_chain = false;           // ... and launches nothing itself: the draw's launch carries the sums' workgroups (k_hyper_chain)
+    int hyper_chain_D = 0; int64_t hyper_chain_N = 0, hyper_chain_rpb = 0; const double *hyper_chain_sample = nullptr, *hyper_chain_uhat = nullptr;   // borrowed
+    DevBuf<unsigned> hyper_count;       // partial workgroups finished (k_hyper_chain), allocated at first use
+    double *hyper_chain_draws = nullptr; // borrowed (bdf_gibbs_sweep) the chain's launch also makes the entity's random part (k_hyper_draws' values) into this buffer
+    DevBuf<double> cg_part;             // partial dot products of the chunked CG step (k_cg_long_*), allocated at first use
+    uint32_t cg_gen = 0;
+    DevBuf<unsigned> cg_bar;            // the hand-over counter of the one-launch CG solve (k_cg_resident), allocated at first use
+    bdf_rows_state *rows = nullptr;     // the row launcher's own (rows_plan.hip): cached plans, dispatch counts, what lr_T / lr_vt were computed from
+    DevBuf<double> norm_part;           // bdf_norm2's per-workgroup partial sums (k_auc.hip), allocated at first use
+    DevBuf<double> newrows_W;           // bdf_newrows_quad's L^-1 of the call's Lambda (k_newrows.hip: BDF_MAX_D x BDF_MAX_D), allocated at first use
+
+    bdf_ctx() = default;
+    bdf_ctx(const bdf_ctx &) = delete;
+    ~bdf_ctx();                         // bdf_api.hip: waits for the stream, then the members free themselves
 };
 
 int bdf_scratch(bdf_ctx *ctx, size_t bytes, void **out);
@@ -141,65 +137,67 @@ struct bdf_mode_index {
     std::vector<int64_t> rowptr;   // host, dims+1
     std::vector<int64_t> rowids;   // host, nnz, 1-based COO row numbers (IndexedDF.index)
     std::vector<int32_t> order;    // host, rows by descending degree (stable)
-    int64_t *rowptr_dev;           // dims+1
-    int32_t *colidx_dev;           // (n_modes-1) planes of nnz: 0-based ids of the other modes, mode order
-    double  *vals_dev;             // nnz values in mode order
-    int32_t *perm_dev;             // nnz: 0-based COO row number in mode order
-    uint32_t *packed_dev;          // nullable, two-mode relations with <= 256 distinct values: (value code << 24) | other-mode id
-    int32_t *order_dev;
+    DevBuf<int64_t> rowptr_dev;    // dims+1
+    DevBuf<int32_t> colidx_dev;    // (n_modes-1) planes of nnz: 0-based ids of the other modes, mode order
+    DevBuf<double> vals_dev;       // nnz values in mode order
+    DevBuf<int32_t> perm_dev;      // nnz: 0-based COO row number in mode order
+    DevBuf<uint32_t> packed_dev;   // nullable, two-mode relations with <= 256 distinct values: (value code << 24) | other-mode id
+    DevBuf<int32_t> order_dev;
     // relation created with a layout (bdf_relation_create_sharded): the device arrays hold only the observations of the rows
     // this rank owns, chunk after chunk in internal-position order, and colidx holds INTERNAL positions of the other modes
     std::vector<int32_t> own_orig;     // original id of every owned row
     std::vector<int32_t> own_pos;      // its internal position (row of the factor matrix)
     std::vector<int64_t> own_q;        // offsets of the owned rows' observations in the device arrays (owned + 1)
     std::vector<int64_t> chunk_begin;  // first owned row of every chunk (chunks + 1)
-    int64_t own_nnz;
+    int64_t own_nnz = 0;
 };
 
 struct bdf_rel {
-    bdf_ctx *ctx;
-    uint64_t serial;           // unique per created relation (keys the K1 plan cache)
-    int n_modes;
-    int64_t dims[BDF_MAX_MODES];
-    int64_t nnz;
-    double value_mean;
+    bdf_ctx *ctx = nullptr;    // borrowed
+    uint64_t serial = 0;       // unique per created relation (keys the K1 plan cache)
+    int n_modes = 0;
+    int64_t dims[BDF_MAX_MODES] = {};
+    int64_t nnz = 0;
+    double value_mean = 0.0;
     bdf_mode_index idx[BDF_MAX_MODES];
-    int sharded;                       // created with a layout
-    int rank, world, chunks;
-    int64_t nint[BDF_MAX_MODES];       // rows of the factor matrix of every mode (== dims without a layout)
+    int sharded = 0;                   // created with a layout
+    int rank = 0, world = 1, chunks = 1;
+    int64_t nint[BDF_MAX_MODES] = {};  // rows of the factor matrix of every mode (== dims without a layout)
     // ratings take few distinct values (MovieLens: 5): when there are at most 256 the relation also keeps them as 8-bit codes
     // into this table, packed with the other mode's id (K1's coded two-mode variant: no value registers in its pipeline)
-    int n_codes;                       // 0: not coded
-    double *table_dev;                 // 256 doubles, ascending distinct values (the rest zero)
+    int n_codes = 0;                   // 0: not coded
+    DevBuf<double> table_dev;          // 256 doubles, ascending distinct values (the rest zero)
+    ~bdf_rel();                        // bdf_api.hip: waits for the stream and drops the relation's row plans; the members free themselves
 };
 
 struct bdf_pairs {
-    bdf_ctx *ctx;
-    int n_modes;
-    int64_t n;
-    int32_t *ids_dev;     // n_modes planes of n, 0-based
-    double *values_dev;   // n
-    double *avg_dev, *sq_dev;
-    double count;         // counter_prob (macau.jl:171-183)
-    const double *baseline_dev;   // nullable, borrowed: per-pair baseline replacing mean_value (relation features)
-    int32_t *orig_dev;            // nullable: storage position -> caller's index (bdf_pairs_sort)
-    int sorted_mode;              // the mode bdf_pairs_sort sorted by, -1: caller's order
+    bdf_ctx *ctx = nullptr;       // borrowed
+    int n_modes = 0;
+    int64_t n = 0;
+    DevBuf<int32_t> ids_dev;      // n_modes planes of n, 0-based
+    DevBuf<double> values_dev;    // n
+    DevBuf<double> avg_dev, sq_dev;
+    double count = 0.0;           // counter_prob (macau.jl:171-183)
+    const double *baseline_dev = nullptr;   // nullable, borrowed: per-pair baseline replacing mean_value (relation features)
+    DevBuf<int32_t> orig_dev;     // nullable: storage position -> caller's index (bdf_pairs_sort)
+    int sorted_mode = -1;         // the mode bdf_pairs_sort sorted by, -1: caller's order
     std::vector<int32_t> ids_host, orig_host;
     std::vector<double> values_host;
-    void *auc_ws;                 // bdf_pairs_auc's workspace (bdf_auc_workspace_bytes(n)), allocated at first use
-    int link;                     // bdf_pairs_set_link: 0 identity, 1 probit (predictions are Phi(udot + base): k_probit.hip), 2 logistic; 3 counts (k_pg.hip)
-    double link_r;                // bdf_pairs_set_count_link: predictions are link_r exp(udot + base)
-    double *lpd_dev;              // bdf_pairs_lpd_update's running state (k_lpd.hip): n maxima M, then n sums A, in storage order; at first use
-    double lpd_draws;             // ... and the posterior draws it holds (a counter of its own, not `count`)
-    double *waic_dev;             // bdf_pairs_waic_update's running state (k_waic.hip): four planes of n in storage order -- M, A, mean, M2; at first use
-    double waic_draws;            // ... and the posterior draws it holds (a counter of its own)
-    const double *scale_dev;      // nullable, borrowed (bdf_pairs_set_precision_scale): a precision scale per row of mode scale_mode, for k_lpd
-    int scale_mode;
-    double *newrows_dev;          // bdf_newrows_update's running state (k_newrows.hip): five planes of n in storage order -- mean, M2, sum q, M, A; at first use
-    double newrows_draws;         // ... the posterior draws it holds (a counter of its own)
-    bool newrows_score;           // ... and whether their log-likelihoods were folded in (score_lpd of the phase 1 call)
-    int64_t *foldin_ptr_dev;      // bdf_foldin_cells (k_foldin.hip): the pairs sorted by mode 0 as rows -- foldin_rows + 1 offsets into the storage
-    int64_t foldin_rows, foldin_cols;      // order; made at the first call for these dims, which every id was checked against
+    DevBuf<void> auc_ws;          // bdf_pairs_auc's workspace (bdf_auc_workspace_bytes(n)), allocated at first use
+    int link = 0;                 // bdf_pairs_set_link: 0 identity, 1 probit (predictions are Phi(udot + base): k_probit.hip), 2 logistic; 3 counts (k_pg.hip)
+    double link_r = 0.0;          // bdf_pairs_set_count_link: predictions are link_r exp(udot + base)
+    DevBuf<double> lpd_dev;       // bdf_pairs_lpd_update's running state (k_lpd.hip): n maxima M, then n sums A, in storage order; at first use
+    double lpd_draws = 0.0;       // ... and the posterior draws it holds (a counter of its own, not `count`)
+    DevBuf<double> waic_dev;      // bdf_pairs_waic_update's running state (k_waic.hip): four planes of n in storage order -- M, A, mean, M2; at first use
+    double waic_draws = 0.0;      // ... and the posterior draws it holds (a counter of its own)
+    const double *scale_dev = nullptr;      // nullable, borrowed (bdf_pairs_set_precision_scale): a precision scale per row of mode scale_mode, for k_lpd
+    int scale_mode = 0;
+    DevBuf<double> newrows_dev;   // bdf_newrows_update's running state (k_newrows.hip): five planes of n in storage order -- mean, M2, sum q, M, A; at first use
+    double newrows_draws = 0.0;   // ... the posterior draws it holds (a counter of its own)
+    bool newrows_score = false;   // ... and whether their log-likelihoods were folded in (score_lpd of the phase 1 call)
+    DevBuf<int64_t> foldin_ptr_dev;         // bdf_foldin_cells (k_foldin.hip): the pairs sorted by mode 0 as rows -- foldin_rows + 1 offsets into the storage
+    int64_t foldin_rows = 0, foldin_cols = 0;   // order; made at the first call for these dims, which every id was checked against
+    ~bdf_pairs();                 // k_predict.hip: waits for the context's stream; the members free themselves
 };
 
 // bdf_ordinal (k_ordinal.hip): the edges of an ordinal relation and their Metropolis step's state, all of it in ONE device buffer
@@ -218,41 +216,39 @@ struct bdf_pairs {
 #define BDF_ORD_TRACE 48           // then capacity rows of K - 1 edges
 #define BDF_ORD_MAX_TRACE ((int64_t)1 << 24)   // rows a trace may have (2 GB of device memory at K = 16)
 struct bdf_ordinal {
-    bdf_ctx *ctx;
-    int K;
-    int64_t capacity;              // trace rows
-    int64_t adapt_steps;           // bdf_ordinal_set_adapt
-    size_t state_doubles;
-    double *state_dev;
-    hipStream_t stream;            // where the last step was enqueued (bdf_ordinal_read waits for it)
+    bdf_ctx *ctx = nullptr;        // borrowed
+    int K = 0;
+    int64_t capacity = 0;          // trace rows
+    int64_t adapt_steps = 0;       // bdf_ordinal_set_adapt
+    size_t state_doubles = 0;
+    DevBuf<double> state_dev;
+    hipStream_t stream = nullptr;  // borrowed: where the last step was enqueued (bdf_ordinal_read waits for it)
 };
 
 struct bdf_feat {
-    bdf_ctx *ctx;
-    int kind;             // 0 dense, 1 csr (real), 2 binary
-    int64_t m, n, nnz;
-    double *dense_dev;    // m x n column-major
+    bdf_ctx *ctx = nullptr;   // borrowed
+    int kind = 0;             // 0 dense, 1 csr (real), 2 binary
+    int64_t m = 0, n = 0, nnz = 0;
+    DevBuf<double> dense_dev; // m x n column-major
     // CSR (rows) and CSC (= CSR of F') so that neither product needs atomics
-    int64_t *rowptr_dev; int32_t *colind_dev; double *rvals_dev;
-    int64_t *colptr_dev; int32_t *rowind_dev; double *cvals_dev;
+    DevBuf<int64_t> rowptr_dev; DevBuf<int32_t> colind_dev; DevBuf<double> rvals_dev;
+    DevBuf<int64_t> colptr_dev; DevBuf<int32_t> rowind_dev; DevBuf<double> cvals_dev;
     // column panels of the sparse products (k_feat_ops.hip, spmm): entries of row r with a column in panel p are
     // [panel_ptr[p * rows + r], panel_ptr[(p + 1) * rows + r]) -- NULL when the operand is small or a row's entries are not in column order
-    int64_t *panel_fwd_dev; int n_panels_fwd;      // F   (rows m, panels over the n columns)
-    int64_t *panel_tr_dev; int n_panels_tr;        // F'  (rows n, panels over the m columns)
-    double *FF_dev;       // n x n (F'F), built on first use_ff
-    int32_t *row_ids_dev; // nullable (bdf_feat_set_row_ids): original id of every row of F, keys the rows' noise streams
-    double *chol_ws;      // workspace of the blocked direct solve (k_chol.hip), allocated on first use
-    size_t chol_ws_doubles;
-    void *gather_dev;     // several ranks: the blocks of beta columns the ranks exchange (bdf_sample_beta_ranks), on first use
-    size_t gather_bytes;
+    DevBuf<int64_t> panel_fwd_dev; int n_panels_fwd = 0;      // F   (rows m, panels over the n columns)
+    DevBuf<int64_t> panel_tr_dev; int n_panels_tr = 0;        // F'  (rows n, panels over the m columns)
+    DevBuf<double> FF_dev;        // n x n (F'F), built on first use_ff
+    DevBuf<int32_t> row_ids_dev;  // nullable (bdf_feat_set_row_ids): original id of every row of F, keys the rows' noise streams
+    DevBuf<double> chol_ws;       // workspace of the blocked direct solve (k_chol.hip), grown on demand
+    DevBuf<void> gather_dev;      // several ranks: the blocks of beta columns the ranks exchange (bdf_sample_beta_ranks), grown on demand
     // direct solve of a mid-sized feature set (64 < n <= BDF_EIG_MAX): F'F = Q diag(s) Q' once (host, first use), then
     // (F'F + lambda I) \ rhs = Q ((Q' rhs) ./ (s + lambda)) per iteration -- lambda changes every iteration, Q and s do not
-    bdf_feat *eig_Q;      // Q as a dense n x n operator (eigenvectors in columns)
-    double *eig_s;        // n eigenvalues (dev)
-    double *eig_y;        // n x D workspace (dev), eig_y_cols columns
-    int eig_y_cols;
-    bool eig_failed;      // the decomposition's QL iteration did not converge: this operator takes the factorisation (bdf_chol_solve) instead
-    bool FF_summed;       // several ranks, F split by rows (bdf_sample_beta_rel_ranks): FF_dev already holds the sum over the ranks
+    std::unique_ptr<bdf_feat> eig_Q;   // Q as a dense n x n operator (eigenvectors in columns)
+    DevBuf<double> eig_s;         // n eigenvalues (dev)
+    DevBuf<double> eig_y;         // n x D workspace (dev), grown with D
+    bool eig_failed = false;      // the decomposition's QL iteration did not converge: this operator takes the factorisation (bdf_chol_solve) instead
+    bool FF_summed = false;       // several ranks, F split by rows (bdf_sample_beta_rel_ranks): FF_dev already holds the sum over the ranks
+    ~bdf_feat();                  // k_feat_ops.hip: waits for the context's stream; the members free themselves
 };
 #define BDF_EIG_MAX 640
 

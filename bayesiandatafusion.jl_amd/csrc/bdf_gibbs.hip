@@ -24,15 +24,16 @@
 #include <tuple>
 
 struct bdf_gibbs {
-    bdf_ctx *rows, *hyper, *pred;        // rows: the caller's context; hyper / pred: owned (own streams)
+    bdf_ctx *rows = nullptr;             // borrowed: the caller's context
+    bdf_ctx *hyper = nullptr, *pred = nullptr;   // owned (own streams): deleted by the destructor, after the gate
     bdf_ctx *gate = nullptr;             // owned, with polling: a second stream on the reserved CUs for the one-wave gate in front of the prediction update
     bdf_ctx *step_hyper = nullptr;       // where bdf_gibbs_step_draws / _hyper enqueue: hyper, or -- BDF_NO_OVERLAP, one stream for everything -- rows
-    int D;
+    int D = 0;
     struct Ent {
-        bdf_gibbs_entity d;
-        int cur;                         // buffer holding the current rows
-        hipEvent_t ev_rows = nullptr, ev_hyper = nullptr;    // rows of this sweep complete (and exchanged) | (mu, Lambda) of this sweep complete
-        hipEvent_t ev_beta = nullptr;                        // side information: beta (and lambda_beta) of this sweep complete
+        bdf_gibbs_entity d{};            // the caller's description: every buffer in it is borrowed
+        int cur = 0;                     // buffer holding the current rows
+        DevEvent ev_rows, ev_hyper;      // rows of this sweep complete (and exchanged) | (mu, Lambda) of this sweep complete
+        DevEvent ev_beta;                // side information: beta (and lambda_beta) of this sweep complete
         bool beta_recorded = false;
         bool hyper_recorded = false;
         // number of hyperprior draws enqueued for this entity so far: the value its next draw publishes in ready_dev and the
@@ -41,34 +42,35 @@ struct bdf_gibbs {
         uint32_t epoch = 0;
         // the rows' hand-over to the chain by counter (no event): the sum the 64 words of done_dev reach when every row launch of
         // this entity enqueued so far has completed (wraps; compared as a difference)
-        uint32_t *done_dev = nullptr;
+        DevBuf<uint32_t> done_dev;
         uint32_t done_target = 0;
-        hipEvent_t t_start = nullptr, t_stop = nullptr;      // bdf_gibbs_time_rows: attached to the next row launch of this entity
-        unsigned long long *span = nullptr;                  // bdf_gibbs_span_rows: SampleArgs::span of the next row launch of this entity
+        hipEvent_t t_start = nullptr, t_stop = nullptr;      // borrowed -- bdf_gibbs_time_rows: attached to the next row launch of this entity
+        unsigned long long *span = nullptr;                  // borrowed -- bdf_gibbs_span_rows: SampleArgs::span of the next row launch of this entity
     };
     std::vector<Ent> ent;
-    bdf_pairs *test;
-    int32_t test_entity[BDF_MAX_MODES];
-    double test_mean, clamp_lo, clamp_hi, class_cut;
-    double *stats_dev;
-    hipEvent_t ev_pred[3] = {nullptr, nullptr, nullptr};   // prediction update number k complete: ev_pred[k % 3]
+    bdf_pairs *test = nullptr;           // borrowed
+    int32_t test_entity[BDF_MAX_MODES] = {};
+    double test_mean = 0.0, clamp_lo = 0.0, clamp_hi = 0.0, class_cut = 0.0;
+    double *stats_dev = nullptr;         // borrowed
+    DevEvent ev_pred[3];                 // prediction update number k complete: ev_pred[k % 3]
     uint64_t pred_at[3] = {0, 0, 0};     // ... and the iteration count (n_iter) at which it was enqueued
-    uint64_t n_pred;                     // prediction updates enqueued so far
+    uint64_t n_pred = 0;                 // prediction updates enqueued so far
     uint64_t n_iter = 0;                 // iterations enqueued so far (with or without a prediction update)
-    bdf_comm *comm;                      // nullable: exchange of the sampled rows between the ranks after every entity
+    bdf_comm *comm = nullptr;            // borrowed, nullable: exchange of the sampled rows between the ranks after every entity
     std::vector<bdf_gibbs_relation> rels; // relations with a model of their own (alpha sampled, relation features): bdf_gibbs_set_relations
-    double *rel_sse = nullptr;           // dev, 8 doubles: the squared-error statistics of sample_alpha
+    DevBuf<double> rel_sse;              // dev, 8 doubles: the squared-error statistics of sample_alpha
     // The row stream has NO wait for the hyperprior draws when they run on reserved CUs (bdf_ctx_create_rows): a draw there
     // cannot be starved by the chip-filling row kernel, so the row kernel is enqueued right behind its predecessor (back-to-back
     // row kernels start with no gap; a wait for another stream's event costs the row stream ~10 us even when long satisfied:
     // profiles/r02_sweep_timeline_events.txt) and its waves poll ready[entity] where they first need the prior.
-    uint32_t *ready_dev;                 // per entity: iteration number of the last completed draw
-    bool polling;
+    DevBuf<uint32_t> ready_dev;          // per entity: iteration number of the last completed draw
+    bool polling = false;
     // BDF_DEBUG: where the host's time in bdf_gibbs_sweep goes (waiting for the prediction update of two sweeps ago = the device
     // is the bottleneck; enqueueing = the host is)
-    bool debug;
-    double host_wait_us, host_enqueue_us;
-    uint64_t n_sweeps;
+    bool debug = false;
+    double host_wait_us = 0.0, host_enqueue_us = 0.0;
+    uint64_t n_sweeps = 0;
+    ~bdf_gibbs();
 };
 
 namespace {
@@ -121,9 +123,9 @@ void sample_written(bdf_gibbs *g, const bdf_gibbs::Ent &E)
 
 int streams_concurrent(hipStream_t a, hipStream_t b, bool *yes)
 {
-    uint32_t *d;
-    BDF_HIP(hipMalloc((void **)&d, 2 * sizeof(uint32_t)));
-    struct Free { uint32_t *p; ~Free() { (void)hipFree(p); } } guard{d};
+    DevBuf<uint32_t> buf;
+    if (int rc = buf.alloc(2)) return rc;
+    uint32_t *d = buf.get();
     BDF_HIP(hipMemsetAsync(d, 0, 2 * sizeof(uint32_t), a));
     BDF_HIP(hipStreamSynchronize(a)); BDF_HIP(hipStreamSynchronize(b));
     hipLaunchKernelGGL(k_wait_flag, dim3(1), dim3(1), 0, a, (const uint32_t *)d, 2000000LL, d + 1);
@@ -137,8 +139,9 @@ int streams_concurrent(hipStream_t a, hipStream_t b, bool *yes)
 
 int streams_overlap(hipStream_t a, hipStream_t b, bool *yes)
 {
-    hipEvent_t e0, e1, e2;
-    BDF_HIP(hipEventCreate(&e0)); BDF_HIP(hipEventCreate(&e1)); BDF_HIP(hipEventCreate(&e2));
+    DevEvent e0, e1, e2;
+    int rc;
+    if ((rc = e0.create(hipEventDefault)) || (rc = e1.create(hipEventDefault)) || (rc = e2.create(hipEventDefault))) return rc;
     BDF_HIP(hipStreamSynchronize(a)); BDF_HIP(hipStreamSynchronize(b));
     float best = 1e9f;
     for (int rep = 0; rep < 3; rep++) {
@@ -154,7 +157,6 @@ int streams_overlap(hipStream_t a, hipStream_t b, bool *yes)
         BDF_HIP(hipEventElapsedTime(&ms, e0, e2));
         best = std::min(best, ms);
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(e2);
     *yes = best < 0.100f;               // side by side: ~0.065 ms; serialised: ~0.125 ms
     return BDF_OK;
 }
@@ -195,7 +197,7 @@ int pooled_stream(int device, int reserve, bool reserved, int slot, hipStream_t 
 int make_side_ctx(bdf_ctx *main, const std::vector<bdf_ctx *> &apart, bool reserved, bdf_ctx **out)
 {
     // a few candidate streams; the first that overlaps with the row stream and with every stream in `apart`
-    bdf_ctx *fallback = nullptr;
+    std::unique_ptr<bdf_ctx> fallback;
     for (int attempt = 0; attempt < 8; attempt++) {
         hipStream_t st;
         // slot 0 of the unreserved role is the row stream itself
@@ -205,9 +207,10 @@ int make_side_ctx(bdf_ctx *main, const std::vector<bdf_ctx *> &apart, bool reser
         bool taken = false;
         for (bdf_ctx *o : apart) taken = taken || o->stream == st;
         if (taken) continue;
-        bdf_ctx *c;
-        rc = bdf_ctx_create(main->device, (void *)st, main->seed, &c);
+        bdf_ctx *made;
+        rc = bdf_ctx_create(main->device, (void *)st, main->seed, &made);
         if (rc) return rc;
+        std::unique_ptr<bdf_ctx> c(made);
         c->reserve_cus = main->reserve_cus;
         c->on_reserved = (reserved && main->reserve_cus > 0) ? 1 : 0;
         bool ok = true;
@@ -215,13 +218,12 @@ int make_side_ctx(bdf_ctx *main, const std::vector<bdf_ctx *> &apart, bool reser
         for (bdf_ctx *o : apart)
             if (ok && (rc = streams_overlap(st, o->stream, &ok))) return rc;
         if (ok) {
-            if (fallback) bdf_ctx_destroy(fallback);
-            *out = c;
+            *out = c.release();
             return BDF_OK;
         }
-        if (!fallback) fallback = c; else bdf_ctx_destroy(c);
+        if (!fallback) fallback = std::move(c);
     }
-    *out = fallback;                    // no candidate runs beside the others: correct, only slower
+    *out = fallback.release();                    // no candidate runs beside the others: correct, only slower
     return BDF_OK;
 }
 
@@ -281,76 +283,64 @@ extern "C" int bdf_gibbs_create(bdf_ctx *rows_ctx, int D, int n_entities, const 
         }
     }
     BDF_HIP(hipSetDevice(rows_ctx->device));
-    bdf_gibbs *g = new bdf_gibbs();
-    g->rows = rows_ctx; g->hyper = g->pred = nullptr; g->D = D; g->test = nullptr; g->stats_dev = nullptr;
-    g->n_pred = 0; g->comm = nullptr; g->ready_dev = nullptr; g->polling = false;
-    g->debug = false; g->host_wait_us = g->host_enqueue_us = 0.0; g->n_sweeps = 0;
+    std::unique_ptr<bdf_gibbs> owner(new bdf_gibbs());       // a failure below releases what exists so far
+    bdf_gibbs *g = owner.get();
+    g->rows = rows_ctx; g->D = D;
     int rc;
-    if ((rc = make_side_ctx(rows_ctx, {}, true, &g->hyper)) || (rc = make_side_ctx(rows_ctx, {g->hyper}, false, &g->pred))) { bdf_gibbs_destroy(g); return rc; }
+    if ((rc = make_side_ctx(rows_ctx, {}, true, &g->hyper)) || (rc = make_side_ctx(rows_ctx, {g->hyper}, false, &g->pred))) return rc;
     g->step_hyper = getenv("BDF_NO_OVERLAP") ? g->rows : g->hyper;
-    g->ready_dev = nullptr;
     g->polling = rows_ctx->reserve_cus > 0 && g->hyper->on_reserved && !getenv("BDF_NO_POLL");
     if (g->polling) {
         bool conc = false;
-        if ((rc = streams_concurrent(rows_ctx->stream, g->hyper->stream, &conc))) { bdf_gibbs_destroy(g); return rc; }
+        if ((rc = streams_concurrent(rows_ctx->stream, g->hyper->stream, &conc))) return rc;
         g->polling = conc;              // kernels of the two streams do not run side by side here (a profiler serialising them): events
     }
     // (the gate's stream: on the reserved CUs like the chain's, so that its wave never takes a row slot; beside the other three if it can)
-    if (g->polling && (rc = make_side_ctx(rows_ctx, {g->hyper, g->pred}, true, &g->gate))) { bdf_gibbs_destroy(g); return rc; }
+    if (g->polling && (rc = make_side_ctx(rows_ctx, {g->hyper, g->pred}, true, &g->gate))) return rc;
     if (g->polling && !g->gate) g->polling = false;         // (no stream left for it: events everywhere, as without reserved CUs)
     g->debug = getenv("BDF_DEBUG") != nullptr;
     if (g->debug)
         fprintf(stderr, "[bdf_gibbs] reserve_cus=%d hyperprior stream on reserved CUs=%d polling=%d\n", rows_ctx->reserve_cus,
                 g->hyper->on_reserved, (int)g->polling);
-    // (every event starts out NULL and bdf_gibbs_destroy skips those: a failure below releases what exists so far)
-    struct Guard { bdf_gibbs *g; ~Guard() { if (g) bdf_gibbs_destroy(g); } } guard{g};
-    BDF_HIP(hipMalloc((void **)&g->ready_dev, (size_t)n_entities * sizeof(uint32_t)));
+    if ((rc = g->ready_dev.alloc((size_t)n_entities))) return rc;
     BDF_HIP(hipMemsetAsync(g->ready_dev, 0, (size_t)n_entities * sizeof(uint32_t), rows_ctx->stream));
     BDF_HIP(hipStreamSynchronize(rows_ctx->stream));
     g->ent.resize((size_t)n_entities);
     for (int j = 0; j < n_entities; j++) {
         auto &E = g->ent[(size_t)j];
-        E.d = ents[j]; E.cur = 0;
+        E.d = ents[j];
         sample_written(g, E);                         // (the initial state; images an earlier chain left at these addresses)
-        BDF_HIP(hipEventCreate(&E.ev_rows));          // (they ride on dispatch packets: plain events)
-        BDF_HIP(hipEventCreate(&E.ev_hyper));
-        if (E.d.feat) BDF_HIP(hipEventCreateWithFlags(&E.ev_beta, hipEventDisableTiming));
+        if ((rc = E.ev_rows.create(hipEventDefault)) || (rc = E.ev_hyper.create(hipEventDefault))) return rc;      // (they ride on dispatch packets: plain events)
+        if (E.d.feat && (rc = E.ev_beta.create(hipEventDisableTiming))) return rc;
     }
-    for (int k = 0; k < 3; k++) BDF_HIP(hipEventCreateWithFlags(&g->ev_pred[k], hipEventDisableTiming));
+    for (int k = 0; k < 3; k++)
+        if ((rc = g->ev_pred[k].create(hipEventDisableTiming))) return rc;
     if (g->polling) {
         const size_t bytes = (size_t)BDF_DONE_SHARDS * BDF_DONE_STRIDE * sizeof(uint32_t);
         for (int j = 0; j < n_entities; j++) {
-            BDF_HIP(hipMalloc((void **)&g->ent[(size_t)j].done_dev, bytes));
+            if ((rc = g->ent[(size_t)j].done_dev.alloc_bytes(bytes))) return rc;
             BDF_HIP(hipMemsetAsync(g->ent[(size_t)j].done_dev, 0, bytes, rows_ctx->stream));
         }
         BDF_HIP(hipStreamSynchronize(rows_ctx->stream));
     }
-    guard.g = nullptr;
-    *out = g;
+    *out = owner.release();
     return BDF_OK;
+}
+
+bdf_gibbs::~bdf_gibbs()
+{
+    if (rows) (void)hipStreamSynchronize(rows->stream);
+    if (debug && n_sweeps)
+        fprintf(stderr, "[bdf_gibbs] %llu sweeps: host enqueue %.1f us per sweep, host wait for the device %.1f us per sweep\n",
+                (unsigned long long)n_sweeps, host_enqueue_us / (double)n_sweeps, host_wait_us / (double)n_sweeps);
+    if (gate) { (void)hipStreamSynchronize(gate->stream); delete gate; }
+    delete pred;
+    delete hyper;
 }
 
 extern "C" int bdf_gibbs_destroy(bdf_gibbs *g)
 {
-    if (!g) return BDF_OK;
-    if (g->rows) (void)hipStreamSynchronize(g->rows->stream);
-    if (g->debug && g->n_sweeps)
-        fprintf(stderr, "[bdf_gibbs] %llu sweeps: host enqueue %.1f us per sweep, host wait for the device %.1f us per sweep\n",
-                (unsigned long long)g->n_sweeps, g->host_enqueue_us / (double)g->n_sweeps, g->host_wait_us / (double)g->n_sweeps);
-    for (auto &E : g->ent) {
-        if (E.ev_rows) (void)hipEventDestroy(E.ev_rows);
-        if (E.ev_hyper) (void)hipEventDestroy(E.ev_hyper);
-        if (E.ev_beta) (void)hipEventDestroy(E.ev_beta);
-        if (E.done_dev) (void)hipFree(E.done_dev);
-    }
-    for (int k = 0; k < 3; k++)
-        if (g->ev_pred[k]) (void)hipEventDestroy(g->ev_pred[k]);
-    if (g->ready_dev) (void)hipFree(g->ready_dev);
-    if (g->rel_sse) (void)hipFree(g->rel_sse);
-    if (g->gate) { (void)hipStreamSynchronize(g->gate->stream); bdf_ctx_destroy(g->gate); }
-    if (g->pred) bdf_ctx_destroy(g->pred);
-    if (g->hyper) bdf_ctx_destroy(g->hyper);
-    delete g;
+    if (g) delete g;
     return BDF_OK;
 }
 
@@ -479,7 +469,7 @@ extern "C" int bdf_gibbs_set_relations(bdf_gibbs *g, int n_relations, const bdf_
         }
     }
     g->rels.assign(rels, rels + n_relations);
-    if (n_relations > 0 && !g->rel_sse) BDF_HIP(hipMalloc((void **)&g->rel_sse, 8 * sizeof(double)));
+    if (n_relations > 0 && !g->rel_sse) { if (int rca = g->rel_sse.alloc(8)) return rca; }
     return BDF_OK;
 }
 
@@ -974,9 +964,9 @@ extern "C" int bdf_gibbs_warm_device(bdf_gibbs *g, double milliseconds)
     }
     size_t total = 0;
     for (auto &pc : pieces) total += (pc.bytes + 255) & ~(size_t)255;
-    char *snap = nullptr;
-    BDF_HIP(hipMalloc((void **)&snap, std::max<size_t>(total, 256)));
-    struct Free { char *p; ~Free() { if (p) (void)hipFree(p); } } guard{snap};
+    DevBuf<char> snap_buf;
+    if ((rc = snap_buf.alloc_bytes(std::max<size_t>(total, 256)))) return rc;
+    char *const snap = snap_buf.get();
     size_t off = 0;
     for (auto &pc : pieces) {
         BDF_HIP(hipMemcpyAsync(snap + off, pc.p, pc.bytes, hipMemcpyDeviceToDevice, R->stream));

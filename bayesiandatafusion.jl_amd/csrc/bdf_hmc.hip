@@ -9,38 +9,24 @@
                                    // sums alone would take gigabytes
 
 struct bdf_hmc {
-    bdf_ctx *ctx;
-    int D;
-    int64_t N[2], nnz, nb[2];
-    double mean_value, alpha;
-    double *sample[2], *mom[2], *start[2], *G[2], *mu[2], *Lambda[2], *mu0[2], *WI[2], *sumU[2], *UUt[2];
+    bdf_ctx *ctx = nullptr;                // borrowed
+    int D = 0;
+    int64_t N[2] = {}, nnz = 0, nb[2] = {};
+    double mean_value = 0.0, alpha = 0.0;
+    DevBuf<double> sample[2], mom[2], start[2], G[2], mu[2], Lambda[2], mu0[2], WI[2], sumU[2], UUt[2];
     TwoModeCsr csr[2];
-    double *partial; int partial_L;        // room for the launches of an iteration with L <= partial_L
-    double *rec; double *rec_host; int rec_L;
-    hipEvent_t decided; bool pending;      // the record of the last iteration is on its way to rec_host
-    bdf_pairs *test; double clamp_lo, clamp_hi; double *avg, *tpart; int64_t tnb;
-    int L, L_inner, prior_freq, burnin; double eps;
-    int64_t iters;
+    DevBuf<double> partial;                // room for the launches of an iteration with the largest L so far
+    DevBuf<double> rec;                    // the iteration's record, and its copy in pinned host memory: both for the largest L so far
+    DevBuf<double> rec_host = DevBuf<double>::pinned(kPinnedDefault);
+    DevEvent decided; bool pending = false;   // the record of the last iteration is on its way to rec_host
+    bdf_pairs *test = nullptr;             // borrowed (bdf_hmc_set_test)
+    double clamp_lo = 1.0, clamp_hi = 0.0; DevBuf<double> avg, tpart; int64_t tnb = 0;
+    int L = 10, L_inner = 1, prior_freq = 8, burnin = 100; double eps = 0.01;
+    int64_t iters = 0;
+    ~bdf_hmc() { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
 };
 
 namespace {
-
-void hmc_free(bdf_hmc *h)
-{
-    for (int e = 0; e < 2; e++) {
-        void *p[] = {h->sample[e], h->mom[e], h->start[e], h->G[e], h->mu[e], h->Lambda[e], h->mu0[e], h->WI[e], h->sumU[e],
-                     h->UUt[e]};
-        for (void *q : p) if (q) hipFree(q);
-        two_mode_free(h->csr[e]);
-    }
-    if (h->partial) hipFree(h->partial);
-    if (h->rec) hipFree(h->rec);
-    if (h->rec_host) hipHostFree(h->rec_host);
-    if (h->avg) hipFree(h->avg);
-    if (h->tpart) hipFree(h->tpart);
-    if (h->decided) hipEventDestroy(h->decided);
-    delete h;
-}
 
 size_t partial_bytes(const bdf_hmc *h, int L) { return (size_t)((L + 1) * h->nb[0] + L * h->nb[1]) * HMC_PW * 8; }
 size_t rec_bytes(int L) { return (size_t)(HMC_REC_LOG + 2 * L + 1) * 8; }
@@ -48,21 +34,16 @@ size_t rec_bytes(int L) { return (size_t)(HMC_REC_LOG + 2 * L + 1) * 8; }
 // room for an iteration with this L (the previous iteration's kernels are done: its decision has been read)
 int hmc_reserve(bdf_hmc *h, int L)
 {
-    if (L > h->partial_L) {
-        if (h->partial) { BDF_HIP(hipFree(h->partial)); h->partial = nullptr; h->partial_L = 0; }
-        BDF_HIP(hipMalloc((void **)&h->partial, partial_bytes(h, L)));
-        h->partial_L = L;
-    }
-    if (L > h->rec_L) {
-        double *rec = nullptr, *host = nullptr;
-        BDF_HIP(hipMalloc((void **)&rec, rec_bytes(L)));
+    int rc;
+    if ((rc = h->partial.grow(partial_bytes(h, L)))) return rc;
+    if (rec_bytes(L) > h->rec.bytes()) {
+        DevBuf<double> rec, host = DevBuf<double>::pinned(kPinnedDefault);
+        if ((rc = rec.alloc_bytes(rec_bytes(L)))) return rc;
         BDF_HIP(hipMemset(rec, 0, rec_bytes(L)));
-        BDF_HIP(hipHostMalloc((void **)&host, rec_bytes(L), hipHostMallocDefault));
-        if (h->rec_host) memcpy(host, h->rec_host, rec_bytes(h->rec_L));
+        if ((rc = host.alloc_bytes(rec_bytes(L)))) return rc;
+        if (h->rec_host) memcpy(host, h->rec_host, h->rec_host.bytes());
         else memset(host, 0, rec_bytes(L));
-        if (h->rec) hipFree(h->rec);
-        if (h->rec_host) hipHostFree(h->rec_host);
-        h->rec = rec; h->rec_host = host; h->rec_L = L;
+        h->rec = std::move(rec); h->rec_host = std::move(host);
     }
     return BDF_OK;
 }
@@ -104,13 +85,10 @@ extern "C" int bdf_hmc_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t 
     BDF_REQUIRE(need <= mem_free, BDF_ERR_ARG, "bdf_hmc_create: the model needs %zu bytes of device memory, %zu are free", need,
                 mem_free);
 
-    bdf_hmc *h = new bdf_hmc();
-    memset((void *)h, 0, sizeof(*h));
-    struct Guard { bdf_hmc *h; ~Guard() { if (h) hmc_free(h); } } guard{h};
+    std::unique_ptr<bdf_hmc> owner(new bdf_hmc());
+    bdf_hmc *h = owner.get();
     h->ctx = ctx; h->D = D; h->nnz = nnz; h->alpha = alpha;
-    h->clamp_lo = 1.0; h->clamp_hi = 0.0;
-    h->L = 10; h->L_inner = 1; h->prior_freq = 8; h->eps = 0.01; h->burnin = 100;
-    BDF_HIP(hipEventCreateWithFlags(&h->decided, hipEventDisableTiming));
+    if ((rc = h->decided.create(hipEventDisableTiming))) return rc;
     // the CSR with each entry's multiplicity and sum of squares: the energy's data term over duplicates
     if ((rc = two_mode_build("bdf_hmc_create", dims, nnz, ids, id_bytes, values, true, h->csr, &h->mean_value))) return rc;
 
@@ -120,25 +98,21 @@ extern "C" int bdf_hmc_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t 
         // reset! (RelationData.jl:66-90): sample 0, mu 0, Lambda 5 I, mu0 0, WI I; HMCModel's G = repmat(diag(Lambda), 1, N)
         std::vector<double> zeros((size_t)N * D, 0.0), zd(D, 0.0), G(D, 5.0), Lam((size_t)D * D, 0.0), WI((size_t)D * D, 0.0);
         for (int i = 0; i < D; i++) { Lam[i * D + i] = 5.0; WI[i * D + i] = 1.0; }
-        if ((rc = bdf_upload(&h->sample[e], zeros)) || (rc = bdf_upload(&h->mom[e], zeros)) || (rc = bdf_upload(&h->start[e], zeros)) ||
-            (rc = bdf_upload(&h->G[e], G)) || (rc = bdf_upload(&h->mu[e], zd)) || (rc = bdf_upload(&h->Lambda[e], Lam)) ||
-            (rc = bdf_upload(&h->mu0[e], zd)) || (rc = bdf_upload(&h->WI[e], WI)) || (rc = bdf_upload(&h->sumU[e], zd)) ||
-            (rc = bdf_upload(&h->UUt[e], Lam)))
+        if ((rc = h->sample[e].upload(zeros)) || (rc = h->mom[e].upload(zeros)) || (rc = h->start[e].upload(zeros)) ||
+            (rc = h->G[e].upload(G)) || (rc = h->mu[e].upload(zd)) || (rc = h->Lambda[e].upload(Lam)) ||
+            (rc = h->mu0[e].upload(zd)) || (rc = h->WI[e].upload(WI)) || (rc = h->sumU[e].upload(zd)) ||
+            (rc = h->UUt[e].upload(Lam)))
             return rc;
     }
     if ((rc = hmc_reserve(h, h->L))) return rc;
     BDF_HIP(hipDeviceSynchronize());
-    guard.h = nullptr;
-    *out = h;
+    *out = owner.release();
     return BDF_OK;
 }
 
 extern "C" int bdf_hmc_destroy(bdf_hmc *hmc)
 {
-    if (!hmc) return BDF_OK;
-    hipSetDevice(hmc->ctx->device);
-    hipStreamSynchronize(hmc->ctx->stream);
-    hmc_free(hmc);
+    if (hmc) delete hmc;
     return BDF_OK;
 }
 
@@ -148,14 +122,14 @@ extern "C" int bdf_hmc_set_test(bdf_hmc *hmc, bdf_pairs *test, double clamp_lo, 
     BDF_REQUIRE(!test || test->n_modes == 2, BDF_ERR_ARG, "bdf_hmc_set_test: the test pairs must have two modes");
     BDF_REQUIRE(hmc->iters == 0, BDF_ERR_ARG, "bdf_hmc_set_test: call before the first iteration");
     BDF_HIP(hipSetDevice(hmc->ctx->device));
-    if (hmc->avg) { BDF_HIP(hipFree(hmc->avg)); hmc->avg = nullptr; }
-    if (hmc->tpart) { BDF_HIP(hipFree(hmc->tpart)); hmc->tpart = nullptr; }
+    hmc->avg.reset();
+    hmc->tpart.reset();
     hmc->test = test && test->n > 0 ? test : nullptr;
     hmc->clamp_lo = clamp_lo; hmc->clamp_hi = clamp_hi;
     if (hmc->test) {
         hmc->tnb = hmc_predict_blocks(test->n);
-        BDF_HIP(hipMalloc((void **)&hmc->avg, (size_t)test->n * 8));
-        BDF_HIP(hipMalloc((void **)&hmc->tpart, (size_t)hmc->tnb * 2 * 8));
+        int rc;
+        if ((rc = hmc->avg.alloc((size_t)test->n)) || (rc = hmc->tpart.alloc((size_t)hmc->tnb * 2))) return rc;
     }
     return BDF_OK;
 }

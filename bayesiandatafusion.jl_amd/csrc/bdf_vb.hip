@@ -6,37 +6,22 @@
 #include <cmath>
 
 struct bdf_vb {
-    bdf_ctx *ctx;
-    int D, T, RS, PW;
-    int64_t N[2], nnz;
-    double mean_value, alpha;
-    double nu_N[2], b_N[2], b_0[2];
-    double *rec[2], *mu[2], *pack[2], *W_N[2], *mu_N[2], *mu0[2], *Winv0[2];
+    bdf_ctx *ctx = nullptr;        // borrowed
+    int D = 0, T = 0, RS = 0, PW = 0;
+    int64_t N[2] = {}, nnz = 0;
+    double mean_value = 0.0, alpha = 0.0;
+    double nu_N[2] = {}, b_N[2] = {}, b_0[2] = {};
+    DevBuf<double> rec[2], mu[2], pack[2], W_N[2], mu_N[2], mu0[2], Winv0[2];
     TwoModeCsr csr[2];
-    double *partial[2]; int64_t nblocks[2];
-    double *slices;
-    double *stats;                 // dev: [0..4) test statistics, [4..8) train statistics, [8] |U|^2, [9] |V|^2
-    bdf_pairs *train, *test;
-    double clamp_lo, clamp_hi;
-    int64_t iters;
+    DevBuf<double> partial[2]; int64_t nblocks[2] = {};
+    DevBuf<double> slices;
+    DevBuf<double> stats;          // dev: [0..4) test statistics, [4..8) train statistics, [8] |U|^2, [9] |V|^2
+    std::unique_ptr<bdf_pairs> train;
+    bdf_pairs *test = nullptr;     // borrowed (bdf_vb_set_test)
+    double clamp_lo = 1.0, clamp_hi = 0.0;
+    int64_t iters = 0;
+    ~bdf_vb() { hipSetDevice(ctx->device); hipStreamSynchronize(ctx->stream); }
 };
-
-namespace {
-
-void vb_free(bdf_vb *v)
-{
-    for (int e = 0; e < 2; e++) {
-        void *p[] = {v->rec[e], v->mu[e], v->pack[e], v->W_N[e], v->mu_N[e], v->mu0[e], v->Winv0[e], v->partial[e]};
-        for (void *q : p) if (q) hipFree(q);
-        two_mode_free(v->csr[e]);
-    }
-    if (v->slices) hipFree(v->slices);
-    if (v->stats) hipFree(v->stats);
-    if (v->train) bdf_pairs_destroy(v->train);
-    delete v;
-}
-
-}  // namespace
 
 extern "C" int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t nnz, const void *ids, int id_bytes,
                              const double *values, double alpha, const double *mu_init_u, const double *mu_init_v, bdf_vb **out)
@@ -61,14 +46,11 @@ extern "C" int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t n
                 "bdf_vb_create: the model needs %zu bytes of device memory (the packed second moments alone "
                 "2 x N x D(D+1)/2 x 8 = %zu), %zu are free", need, (size_t)(dims[0] + dims[1]) * T * 8, mem_free);
 
-    bdf_vb *v = new bdf_vb();
-    memset((void *)v, 0, sizeof(*v));
-    struct Guard { bdf_vb *v; ~Guard() { if (v) vb_free(v); } } guard{v};
+    std::unique_ptr<bdf_vb> v(new bdf_vb());
     v->ctx = ctx; v->D = D; v->T = T; v->RS = RS; v->PW = PW; v->nnz = nnz; v->alpha = alpha;
-    v->clamp_lo = 1.0; v->clamp_hi = 0.0;
     if ((rc = two_mode_build("bdf_vb_create", dims, nnz, ids, id_bytes, values, false, v->csr, &v->mean_value))) return rc;
 
-    BDF_HIP(hipMalloc((void **)&v->stats, 16 * sizeof(double)));
+    if ((rc = v->stats.alloc(16))) return rc;
     BDF_HIP(hipMemset(v->stats, 0, 16 * sizeof(double)));
     for (int e = 0; e < 2; e++) {
         // ---- VBModel(D, N) (macau_vb.jl:20-37): W_N = I / N, nu_N = D + N, mu_N = 0, b_N = 2 + N, Winv_0 = I, mu_0 = 0, b_0 = 2,
@@ -89,30 +71,27 @@ extern "C" int bdf_vb_create(bdf_ctx *ctx, int D, const int64_t *dims, int64_t n
         }
         std::vector<double> eye((size_t)D * D, 0.0), W((size_t)D * D, 0.0), A((size_t)D * D + D, 0.0), zero(D, 0.0);
         for (int i = 0; i < D; i++) { eye[i * D + i] = 1.0; W[i * D + i] = wn; A[i * D + i] = wn * v->nu_N[e]; }
-        if ((rc = bdf_upload(&v->rec[e], rec)) || (rc = bdf_upload(&v->mu[e], mu)) || (rc = bdf_upload(&v->pack[e], A)) ||
-            (rc = bdf_upload(&v->W_N[e], W)) || (rc = bdf_upload(&v->mu_N[e], zero)) || (rc = bdf_upload(&v->mu0[e], zero)) ||
-            (rc = bdf_upload(&v->Winv0[e], eye)))
+        if ((rc = v->rec[e].upload(rec)) || (rc = v->mu[e].upload(mu)) || (rc = v->pack[e].upload(A)) ||
+            (rc = v->W_N[e].upload(W)) || (rc = v->mu_N[e].upload(zero)) || (rc = v->mu0[e].upload(zero)) ||
+            (rc = v->Winv0[e].upload(eye)) || (rc = v->partial[e].alloc_bytes(std::max<size_t>((size_t)nb[e] * PW * 8, 16))))
             return rc;
         v->nblocks[e] = nb[e];
-        BDF_HIP(hipMalloc((void **)&v->partial[e], std::max<size_t>((size_t)nb[e] * PW * 8, 16)));
         BDF_HIP(hipMemcpy(v->stats + 8 + e, &nsq, sizeof(double), hipMemcpyHostToDevice));      // vecnorm(mu_u)^2 before any iteration
     }
-    BDF_HIP(hipMalloc((void **)&v->slices, (size_t)VB_SLICES * PW * 8));
+    if ((rc = v->slices.alloc((size_t)VB_SLICES * PW))) return rc;
 
     // ---- the raw training rows (uid, vid, value) for the train RMSE (:75-76)
-    if ((rc = bdf_pairs_create(ctx, 2, nnz, ids, id_bytes, values, &v->train))) return rc;
+    bdf_pairs *train;
+    if ((rc = bdf_pairs_create(ctx, 2, nnz, ids, id_bytes, values, &train))) return rc;
+    v->train.reset(train);
     BDF_HIP(hipDeviceSynchronize());
-    guard.v = nullptr;
-    *out = v;
+    *out = v.release();
     return BDF_OK;
 }
 
 extern "C" int bdf_vb_destroy(bdf_vb *vb)
 {
-    if (!vb) return BDF_OK;
-    hipSetDevice(vb->ctx->device);
-    hipStreamSynchronize(vb->ctx->stream);
-    vb_free(vb);
+    if (vb) delete vb;
     return BDF_OK;
 }
 
@@ -154,7 +133,7 @@ extern "C" int bdf_vb_iterate(bdf_vb *vb, int n)
         if (vb->test && vb->test->n > 0 &&
             (rc = bdf_predict_update(ctx, vb->test, vb->D, fac, vb->mean_value, 0, vb->clamp_lo, vb->clamp_hi, 0.0, vb->stats)))
             return rc;
-        if ((rc = bdf_predict_update(ctx, vb->train, vb->D, fac, vb->mean_value, 0, vb->clamp_lo, vb->clamp_hi, 0.0, vb->stats + 4)))
+        if ((rc = bdf_predict_update(ctx, vb->train.get(), vb->D, fac, vb->mean_value, 0, vb->clamp_lo, vb->clamp_hi, 0.0, vb->stats + 4)))
             return rc;
         vb->iters++;
     }

@@ -20,10 +20,11 @@
 
 struct bdf_acquire {
     bdf_draw_ring ring;            // a slot: (n_rows + M) x 4 nblk of factors, then BDF_ACQ_TAIL doubles (the first: alpha)
-    int want_prob;
-    double mean_value, threshold;
-    double *plane_dev[4];          // BDF_ACQ_MEAN, _M2, _PSUM (nullptr without want_prob), _SCORE: n_rows x M row-major, then BDF_REC_GUARD
+    int want_prob = 0;
+    double mean_value = 0.0, threshold = 0.0;
+    DevBuf<double> plane_dev[4];   // BDF_ACQ_MEAN, _M2, _PSUM (empty without want_prob), _SCORE: n_rows x M row-major, then BDF_REC_GUARD
                                    // doubles of NaN that nothing writes
+    ~bdf_acquire() { ring.drain(); }
 };
 
 #define BDF_ACQ_TAIL 4             // doubles behind a slot's factors (32 bytes: the next slot stays aligned as the first)
@@ -151,13 +152,7 @@ const char *const plane_name[4] = {"the mean plane", "the M2 plane", "the psum p
 
 extern "C" int bdf_acquire_destroy(bdf_acquire *ac)
 {
-    if (!ac) return BDF_OK;
-    hipSetDevice(ac->ring.ctx->device);
-    hipStreamSynchronize(ac->ring.ctx->stream);
-    for (int q = 0; q < 4; q++)
-        if (ac->plane_dev[q]) hipFree(ac->plane_dev[q]);
-    bdf_ring_free(&ac->ring);
-    delete ac;
+    if (ac) delete ac;
     return BDF_OK;
 }
 
@@ -168,24 +163,20 @@ extern "C" int bdf_acquire_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D
 {
     const char *who = "bdf_acquire_create";
     BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "%s: NULL argument", who);
-    bdf_draw_ring ring;
-    int rc = bdf_ring_init(&ring, who, ctx, n_rows, M, D, batch, BDF_ACQ_TAIL, acquire_flush);
+    std::unique_ptr<bdf_acquire> ac(new bdf_acquire());
+    int rc = bdf_ring_init(&ac->ring, who, ctx, n_rows, M, D, batch, BDF_ACQ_TAIL, acquire_flush, ac.get());
     if (rc) return rc;
     BDF_REQUIRE(std::isfinite(mean_value), BDF_ERR_ARG, "bdf_acquire_create: mean_value must be finite");
     BDF_REQUIRE(!want_prob || std::isfinite(threshold), BDF_ERR_ARG, "bdf_acquire_create: threshold must be finite");
     BDF_HIP(hipSetDevice(ctx->device));
-    bdf_acquire *ac = new bdf_acquire();
-    ac->ring = ring; ac->ring.owner = ac;                     // (the planes are null)
     ac->want_prob = want_prob ? 1 : 0; ac->mean_value = mean_value; ac->threshold = want_prob ? threshold : 0.0;
-    struct Guard { bdf_acquire *p; ~Guard() { if (p) bdf_acquire_destroy(p); } } guard{ac};
     for (int q = 0; q < 4; q++) {
         if (q == BDF_ACQ_PSUM && !want_prob) continue;
         // (the score plane holds NaN until a list is asked for)
-        if ((rc = bdf_ring_plane(&ac->ring, who, plane_name[q], q == BDF_ACQ_SCORE ? 0xff : 0, &ac->plane_dev[q]))) return rc;
+        if ((rc = bdf_ring_plane(&ac->ring, who, plane_name[q], q == BDF_ACQ_SCORE ? 0xff : 0, ac->plane_dev[q]))) return rc;
     }
     if ((rc = bdf_ring_alloc(&ac->ring, who, rows_dev))) return rc;
-    guard.p = nullptr;
-    *out = ac;
+    *out = ac.release();
     return BDF_OK;
 }
 

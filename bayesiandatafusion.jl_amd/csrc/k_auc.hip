@@ -373,11 +373,11 @@ extern "C" int bdf_pairs_auc(bdf_ctx *ctx, bdf_pairs *p, double class_cut, doubl
 {
     BDF_REQUIRE(ctx && p, BDF_ERR_ARG, "bdf_pairs_auc: NULL argument");
     if (!p->auc_ws) {
-        // (first use: the pairs' previous work may still be in flight on their streams; hipMalloc does not wait for it, and
+        // (first use: the pairs' previous work may still be in flight on their streams; the allocation does not wait for it, and
         // nothing reads the block before the launches below)
         const size_t bytes = (size_t)bdf_auc_workspace_bytes(p->n);
         BDF_HIP(hipSetDevice(ctx->device));
-        BDF_HIP(hipMalloc(&p->auc_ws, bytes));
+        if (int rc = p->auc_ws.alloc_bytes(bytes)) return rc;
     }
     return auc_enqueue("bdf_pairs_auc", ctx, p->n, nullptr, p->avg_dev, p->values_dev, class_cut, p->orig_dev, p->auc_ws,
                        auc_out, counts_out);
@@ -389,7 +389,7 @@ extern "C" int bdf_norm2(bdf_ctx *ctx, int64_t n, const double *x, double *out)
     BDF_REQUIRE(n >= 0, BDF_ERR_ARG, "bdf_norm2: n=%lld < 0", (long long)n);
     if (!ctx->norm_part) {
         BDF_HIP(hipSetDevice(ctx->device));
-        BDF_HIP(hipMalloc((void **)&ctx->norm_part, NORM_MAX_BLOCKS * sizeof(double)));
+        if (int rc = ctx->norm_part.alloc(NORM_MAX_BLOCKS)) return rc;
     }
     const int64_t chunk = (int64_t)AUC_THREADS * 16;
     const int nblocks = (int)std::max<int64_t>(1, std::min<int64_t>(NORM_MAX_BLOCKS, (n + chunk - 1) / chunk));

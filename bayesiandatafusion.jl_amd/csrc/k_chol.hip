@@ -273,13 +273,7 @@ int bdf_chol_solve(bdf_ctx *ctx, bdf_feat *f, int D, const double *lambda_dev, c
     const int nb = (int)(w.NP / CB);
     const size_t nW = (size_t)w.ld * w.NP, nLT = (size_t)w.NP * w.NP, nY = (size_t)CB * w.NP, nI = (size_t)nb * CB * CB;
     const size_t total = nW + nLT + nY + 2 * nI;
-    if (f->chol_ws_doubles < total) {
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        if (f->chol_ws) BDF_HIP(hipFree(f->chol_ws));
-        f->chol_ws = nullptr; f->chol_ws_doubles = 0;
-        BDF_HIP(hipMalloc((void **)&f->chol_ws, total * sizeof(double)));
-        f->chol_ws_doubles = total;
-    }
+    if (int rc = f->chol_ws.grow(total * sizeof(double), ctx->stream)) return rc;
     w.W = f->chol_ws; w.LT = w.W + nW; w.Y = w.LT + nLT; w.Inv = w.Y + nY; w.InvT = w.Inv + nI;
     const unsigned sg = (unsigned)std::min<size_t>((nW + 255) / 256, 4096);
     hipLaunchKernelGGL(k_chol_setup, dim3(sg), dim3(256), 0, ctx->stream, w, (const double *)f->FF_dev, lambda_dev, rhs);

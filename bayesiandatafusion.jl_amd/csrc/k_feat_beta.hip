@@ -284,14 +284,8 @@ extern "C" int bdf_sample_beta_ranks(bdf_ctx *ctx, bdf_comm *comm, const bdf_fea
             // exchange; the iteration counts travel behind each block's columns
             const int nc = (D + world - 1) / world, c0 = rank * nc, mine = std::max(0, std::min(nc, D - c0));
             const size_t blk = (size_t)nc * numF * sizeof(double) + (size_t)nc * sizeof(int32_t);
-            if (f->gather_bytes < blk * (size_t)world) {
-                BDF_HIP(hipStreamSynchronize(ctx->stream));
-                if (f->gather_dev) BDF_HIP(hipFree(f->gather_dev));
-                f->gather_dev = nullptr; f->gather_bytes = 0;
-                BDF_HIP(hipMalloc((void **)&f->gather_dev, blk * (size_t)world));
-                f->gather_bytes = blk * (size_t)world;
-            }
-            char *gb = (char *)f->gather_dev;
+            if (int rcg = f->gather_dev.grow(blk * (size_t)world, ctx->stream)) return rcg;
+            char *gb = (char *)f->gather_dev.get();
             double *my_beta = (double *)(gb + (size_t)rank * blk);
             int32_t *my_iters = (int32_t *)(gb + (size_t)rank * blk + (size_t)nc * numF * sizeof(double));
             BDF_HIP(hipMemsetAsync(my_beta, 0, blk, ctx->stream));

@@ -698,7 +698,7 @@ int feat_cg_solve(bdf_ctx *ctx, bdf_feat *f, bool use_ff, int D, const double *l
     s.active = ints; s.iters = ints + D; s.nactive = ints + 2 * D;
     s.done_blocks = ints + 2 * D + 1;
     if (!ctx->cg_status) {
-        BDF_HIP(hipHostMalloc((void **)&ctx->cg_status, 2 * sizeof(uint64_t), hipHostMallocMapped));
+        if (int rc = ctx->cg_status.alloc(2)) return rc;
         ctx->cg_status[0] = ctx->cg_status[1] = 0;
     }
     struct SkipGuard { bdf_ctx *c; ~SkipGuard() { c->skip_flag = nullptr; } } guard{ctx};
@@ -723,7 +723,7 @@ int feat_cg_solve(bdf_ctx *ctx, bdf_feat *f, bool use_ff, int D, const double *l
         const int per_cu = std::min(1, D <= 16 ? occ16 : occ32);
         resident = (int64_t)per_cu * avail >= (numF + 15) / 16;
     }
-    if (resident && !ctx->cg_bar) BDF_HIP(hipMalloc((void **)&ctx->cg_bar, sizeof(unsigned)));
+    if (resident && !ctx->cg_bar) { if (int rc = ctx->cg_bar.alloc(1)) return rc; }
     // sparse features, long columns: the state ROW-MAJOR from the first launch to the last (k_cg_rm_*): no transposes around the products
     const bool rm = Xrm && !use_ff && f->kind != 0 && numF > 2048 && D <= 32;
     CgRm cr;
@@ -732,7 +732,7 @@ int feat_cg_solve(bdf_ctx *ctx, bdf_feat *f, bool use_ff, int D, const double *l
     if (cr.G > BDF_CG_RM_MAXG) { cr.G = BDF_CG_RM_MAXG; cr.len = (numF + cr.G - 1) / cr.G; cr.G = (int)((numF + cr.len - 1) / cr.len); }
     cr.partA = cr.partB = cr.bkden0 = cr.zp = cr.rrs = nullptr;
     if (rm) {
-        if (!ctx->cg_part) BDF_HIP(hipMalloc((void **)&ctx->cg_part, CG_PART_DOUBLES * sizeof(double)));
+        if (!ctx->cg_part) { if (int rc = ctx->cg_part.alloc(CG_PART_DOUBLES)) return rc; }
         cr.partA = ctx->cg_part; cr.partB = cr.partA + (size_t)32 * BDF_CG_RM_MAXG; cr.zp = cr.partB + (size_t)32 * BDF_CG_RM_MAXG; cr.rrs = cr.zp + 64;
         // (X row-major in the caller's spare buffer: beta_out is column-major and receives the solution at the end)
         hipLaunchKernelGGL(k_cg_rm_zero, dim3(1), dim3(64), 0, ctx->stream, s);
@@ -756,7 +756,7 @@ int feat_cg_solve(bdf_ctx *ctx, bdf_feat *f, bool use_ff, int D, const double *l
     ch.len = (numF + ch.G - 1) / ch.G;
     ch.partA = ch.partB = ch.bkden0 = nullptr;
     if (long_cols) {
-        if (!ctx->cg_part) BDF_HIP(hipMalloc((void **)&ctx->cg_part, CG_PART_DOUBLES * sizeof(double)));     // (the scratch buffers are reused by the products inside the loop)
+        if (!ctx->cg_part) { if (int rc = ctx->cg_part.alloc(CG_PART_DOUBLES)) return rc; }     // (the scratch buffers are reused by the products inside the loop)
         ch.partA = ctx->cg_part; ch.partB = ch.partA + (size_t)BDF_MAX_D * 64; ch.bkden0 = ch.partB + (size_t)BDF_MAX_D * 64;
     }
     if (resident) {

@@ -149,26 +149,18 @@ int ensure_eig(bdf_feat *f, int D)
             for (int64_t i = j + 1; i < n; i++) A[(size_t)i + (size_t)j * n] = A[(size_t)j + (size_t)i * n];
         if (!eig_sym_host((int)n, A.data(), s, Q)) { f->eig_failed = true; return BDF_OK; }      // (the caller falls back to bdf_chol_solve)
         for (double &x : s) x = std::max(x, 0.0);       // F'F is positive semi-definite: an eigenvalue below zero is rounding
-        bdf_feat *q = new bdf_feat();
+        std::unique_ptr<bdf_feat> q(new bdf_feat());
         q->ctx = ctx; q->kind = 0; q->m = n; q->n = n; q->nnz = n * n;
-        if (hipMalloc((void **)&q->dense_dev, Q.size() * sizeof(double)) != hipSuccess ||
-            hipMalloc((void **)&f->eig_s, (size_t)n * sizeof(double)) != hipSuccess) {
-            hipFree(q->dense_dev); delete q; hipFree(f->eig_s); f->eig_s = nullptr;
+        if (q->dense_dev.alloc(Q.size()) || f->eig_s.alloc((size_t)n)) {
+            f->eig_s.reset();
             bdf_set_error("ensure_eig: out of device memory");
             return BDF_ERR_HIP;
         }
         BDF_HIP(hipMemcpy(q->dense_dev, Q.data(), Q.size() * sizeof(double), hipMemcpyHostToDevice));
         BDF_HIP(hipMemcpy(f->eig_s, s.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        f->eig_Q = q;
+        f->eig_Q = std::move(q);
     }
-    if (f->eig_y_cols < D) {
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        if (f->eig_y) BDF_HIP(hipFree(f->eig_y));
-        f->eig_y = nullptr; f->eig_y_cols = 0;
-        BDF_HIP(hipMalloc((void **)&f->eig_y, (size_t)n * D * sizeof(double)));
-        f->eig_y_cols = D;
-    }
-    return BDF_OK;
+    return f->eig_y.grow((size_t)n * D * sizeof(double), ctx->stream);
 }
 
 }  // namespace
@@ -181,9 +173,9 @@ int feat_eig_solve(bdf_ctx *ctx, bdf_feat *f, int D, const double *lambda_dev, c
     if (f->eig_failed) return bdf_chol_solve(ctx, f, D, lambda_dev, rhs, beta_out);
     if ((rc = ensure_eig(f, D))) return rc;
     if (f->eig_failed) return bdf_chol_solve(ctx, f, D, lambda_dev, rhs, beta_out);        // the QL iteration did not converge: factor instead
-    if ((rc = feat_apply(ctx, f->eig_Q, true, rhs, 1, n, D, f->eig_y, 1, n))) return rc;              // Y = Q' rhs
+    if ((rc = feat_apply(ctx, f->eig_Q.get(), true, rhs, 1, n, D, f->eig_y, 1, n))) return rc;              // Y = Q' rhs
     hipLaunchKernelGGL(k_eig_scale, dim3((unsigned)((n * D + 255) / 256)), dim3(256), 0, ctx->stream, n, D, (const double *)f->eig_s, lambda_dev, f->eig_y,
                        ctx->flag_dev);
     BDF_HIP(hipGetLastError());
-    return feat_apply(ctx, f->eig_Q, false, f->eig_y, 1, n, D, beta_out, 1, n);                       // beta = Q Y
+    return feat_apply(ctx, f->eig_Q.get(), false, f->eig_y, 1, n, D, beta_out, 1, n);                       // beta = Q Y
 }

@@ -688,18 +688,16 @@ static int ensure_dense(bdf_feat *f)
                 (long long)f->m, (long long)f->n);
     // densify by applying F to the identity: dense(:, j) = F e_j
     size_t nn = (size_t)f->n * (size_t)f->n;
-    double *eye;
-    BDF_HIP(hipMalloc((void **)&eye, std::max<size_t>(nn * sizeof(double), 8)));
+    DevBuf<double> eye, dense;
+    int rc;
+    if ((rc = eye.alloc_bytes(std::max<size_t>(nn * sizeof(double), 8)))) return rc;
     std::vector<double> h(nn, 0.0);
     for (int64_t j = 0; j < f->n; j++) h[(size_t)j * f->n + j] = 1.0;
     BDF_HIP(hipMemcpy(eye, h.data(), nn * sizeof(double), hipMemcpyHostToDevice));
-    double *dense;
-    BDF_HIP(hipMalloc((void **)&dense, std::max<size_t>((size_t)f->m * f->n * sizeof(double), 8)));
-    int rc = feat_apply(ctx, f, false, eye, 1, f->n, (int)f->n, dense, 1, f->m);
-    if (rc) return rc;
+    if ((rc = dense.alloc_bytes(std::max<size_t>((size_t)f->m * f->n * sizeof(double), 8)))) return rc;
+    if ((rc = feat_apply(ctx, f, false, eye, 1, f->n, (int)f->n, dense, 1, f->m))) return rc;
     BDF_HIP(hipStreamSynchronize(ctx->stream));
-    BDF_HIP(hipFree(eye));
-    f->dense_dev = dense;
+    f->dense_dev = std::move(dense);
     return BDF_OK;
 }
 
@@ -709,7 +707,7 @@ int feat_ensure_FF(bdf_feat *f)
     bdf_ctx *ctx = f->ctx;
     int rc = ensure_dense(f);
     if (rc) return rc;
-    BDF_HIP(hipMalloc((void **)&f->FF_dev, std::max<size_t>((size_t)f->n * f->n * sizeof(double), 8)));
+    if ((rc = f->FF_dev.alloc_bytes(std::max<size_t>((size_t)f->n * f->n * sizeof(double), 8)))) return rc;
     GemmArgs g;                          // FF = full(At_mul_B(F, F)), RelationData.jl:338
     g.M = f->n; g.N = f->n; g.K = f->m;
     g.A = f->dense_dev; g.ars = f->m; g.acs = 1;
@@ -742,17 +740,15 @@ static int create_sparse(bdf_ctx *ctx, int64_t m, int64_t n, int64_t nnz, const 
             if (vals) v[(size_t)dst] = vals[q];
         }
     };
-    bdf_feat *f = new bdf_feat();
-    memset(f, 0, sizeof(*f));
-    struct Guard { bdf_feat *f; ~Guard() { if (f) bdf_feat_destroy(f); } } guard{f};        // error paths free what was uploaded
+    std::unique_ptr<bdf_feat> f(new bdf_feat());       // error paths free what was uploaded
     f->ctx = ctx; f->kind = vals ? 1 : 2; f->m = m; f->n = n; f->nnz = nnz;
     std::vector<int64_t> ptr; std::vector<int32_t> ind; std::vector<double> v;
     int rc;
     // column panels (spmm): where each row's entries cross a multiple of BDF_SPMM_PANEL_ROWS columns -- only when every row's entries
     // are in column order (the panels must keep the order of the row's sum) and the operand is large enough to be worth it
-    auto panels = [&](int64_t nmajor, int64_t nminor, int64_t **dev, int *np_out) -> int {
+    auto panels = [&](int64_t nmajor, int64_t nminor, DevBuf<int64_t> &dev, int *np_out) -> int {
         const int64_t P = (nminor + BDF_SPMM_PANEL_ROWS - 1) / BDF_SPMM_PANEL_ROWS;
-        *dev = nullptr; *np_out = 0;
+        *np_out = 0;
         if (P < 2 || P > 64 || (size_t)(P + 1) * nmajor * sizeof(int64_t) > ((size_t)256 << 20)) return BDF_OK;
         std::vector<int64_t> pp((size_t)(P + 1) * nmajor);
         for (int64_t r = 0; r < nmajor; r++) {
@@ -765,20 +761,19 @@ static int create_sparse(bdf_ctx *ctx, int64_t m, int64_t n, int64_t nnz, const 
                 pp[(size_t)p * nmajor + r] = (p == P) ? e : q;
             }
         }
-        int rc2 = bdf_upload(dev, pp);
+        int rc2 = dev.upload(pp);
         if (!rc2) *np_out = (int)P;
         return rc2;
     };
     build(rows, cols, m, ptr, ind, v);
-    if ((rc = bdf_upload(&f->rowptr_dev, ptr)) || (rc = bdf_upload(&f->colind_dev, ind))) return rc;
-    if (vals && (rc = bdf_upload(&f->rvals_dev, v))) return rc;
-    if ((rc = panels(m, n, &f->panel_fwd_dev, &f->n_panels_fwd))) return rc;
+    if ((rc = f->rowptr_dev.upload(ptr)) || (rc = f->colind_dev.upload(ind))) return rc;
+    if (vals && (rc = f->rvals_dev.upload(v))) return rc;
+    if ((rc = panels(m, n, f->panel_fwd_dev, &f->n_panels_fwd))) return rc;
     build(cols, rows, n, ptr, ind, v);
-    if ((rc = bdf_upload(&f->colptr_dev, ptr)) || (rc = bdf_upload(&f->rowind_dev, ind))) return rc;
-    if (vals && (rc = bdf_upload(&f->cvals_dev, v))) return rc;
-    if ((rc = panels(n, m, &f->panel_tr_dev, &f->n_panels_tr))) return rc;
-    guard.f = nullptr;
-    *out = f;
+    if ((rc = f->colptr_dev.upload(ptr)) || (rc = f->rowind_dev.upload(ind))) return rc;
+    if (vals && (rc = f->cvals_dev.upload(v))) return rc;
+    if ((rc = panels(n, m, f->panel_tr_dev, &f->n_panels_tr))) return rc;
+    *out = f.release();
     return BDF_OK;
 }
 
@@ -786,14 +781,11 @@ extern "C" int bdf_feat_create_dense(bdf_ctx *ctx, int64_t m, int64_t n, const d
 {
     BDF_REQUIRE(ctx && out && m >= 0 && n >= 0 && (m * n == 0 || F), BDF_ERR_ARG, "bdf_feat_create_dense: bad argument");
     BDF_HIP(hipSetDevice(ctx->device));
-    bdf_feat *f = new bdf_feat();
-    memset(f, 0, sizeof(*f));
+    std::unique_ptr<bdf_feat> f(new bdf_feat());
     f->ctx = ctx; f->kind = 0; f->m = m; f->n = n; f->nnz = m * n;
-    struct Guard { bdf_feat *f; ~Guard() { if (f) bdf_feat_destroy(f); } } guard{f};
-    BDF_HIP(hipMalloc((void **)&f->dense_dev, std::max<size_t>((size_t)m * n * sizeof(double), 8)));
+    if (int rc = f->dense_dev.alloc_bytes(std::max<size_t>((size_t)m * n * sizeof(double), 8))) return rc;
     if (m * n) BDF_HIP(hipMemcpy(f->dense_dev, F, (size_t)m * n * sizeof(double), hipMemcpyHostToDevice));
-    guard.f = nullptr;
-    *out = f;
+    *out = f.release();
     return BDF_OK;
 }
 
@@ -811,27 +803,25 @@ extern "C" int bdf_feat_create_bin(bdf_ctx *ctx, int64_t m, int64_t n, int64_t n
     return create_sparse(ctx, m, n, nnz, rows, cols, nullptr, out);
 }
 
+bdf_feat::~bdf_feat()
+{
+    if (!ctx) return;
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
+}
+
 extern "C" int bdf_feat_destroy(bdf_feat *f)
 {
-    if (!f) return BDF_OK;
-    hipSetDevice(f->ctx->device);
-    hipStreamSynchronize(f->ctx->stream);
-    hipFree(f->dense_dev); hipFree(f->rowptr_dev); hipFree(f->colind_dev); hipFree(f->rvals_dev);
-    hipFree(f->colptr_dev); hipFree(f->rowind_dev); hipFree(f->cvals_dev); hipFree(f->FF_dev); hipFree(f->chol_ws);
-    hipFree(f->panel_fwd_dev); hipFree(f->panel_tr_dev);
-    hipFree(f->row_ids_dev); hipFree(f->gather_dev);
-    if (f->eig_Q) { hipFree(f->eig_Q->dense_dev); delete f->eig_Q; }
-    hipFree(f->eig_s); hipFree(f->eig_y);
-    delete f;
+    if (f) delete f;
     return BDF_OK;
 }
 
 extern "C" int bdf_feat_set_row_ids(bdf_feat *f, const int32_t *row_ids_host)
 {
     BDF_REQUIRE(f, BDF_ERR_ARG, "bdf_feat_set_row_ids: NULL argument");
-    if (f->row_ids_dev) { BDF_HIP(hipFree(f->row_ids_dev)); f->row_ids_dev = nullptr; }
+    f->row_ids_dev.reset();
     if (row_ids_host && f->m > 0) {
-        BDF_HIP(hipMalloc((void **)&f->row_ids_dev, (size_t)f->m * sizeof(int32_t)));
+        if (int rc = f->row_ids_dev.alloc((size_t)f->m)) return rc;
         BDF_HIP(hipMemcpy(f->row_ids_dev, row_ids_host, (size_t)f->m * sizeof(int32_t), hipMemcpyHostToDevice));
     }
     return BDF_OK;

@@ -186,8 +186,7 @@ int cell_rows(const char *who, bdf_pairs *p, int64_t n_new, int64_t M)
     }
     for (int64_t r = 0; r < n_new; r++) ptr[(size_t)r + 1] += ptr[(size_t)r];
     BDF_HIP(hipSetDevice(p->ctx->device));
-    if (p->foldin_ptr_dev) { BDF_HIP(hipFree(p->foldin_ptr_dev)); p->foldin_ptr_dev = nullptr; }
-    int rc = bdf_upload(&p->foldin_ptr_dev, ptr);
+    int rc = p->foldin_ptr_dev.upload(ptr);
     if (rc) return rc;
     p->foldin_rows = n_new; p->foldin_cols = M;
     return BDF_OK;

@@ -382,7 +382,7 @@ extern "C" int bdf_hyper_sample(bdf_ctx *ctx, int D, int64_t N, const double *su
         ctx->hyper_partial = nullptr;
         ctx->hyper_chain = false;
         if (!ctx->hyper_count) {
-            BDF_HIP(hipMalloc((void **)&ctx->hyper_count, sizeof(unsigned)));
+            if (int rc = ctx->hyper_count.alloc(1)) return rc;
             BDF_HIP(hipMemsetAsync(ctx->hyper_count, 0, sizeof(unsigned), ctx->stream));
         }
         ChainArgs c;

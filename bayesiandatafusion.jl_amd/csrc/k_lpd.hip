@@ -54,7 +54,7 @@ extern "C" int bdf_pairs_lpd_update(bdf_ctx *ctx, bdf_pairs *p, const double *bo
         BDF_HIP(hipMemsetAsync(stats_out, 0, 4 * sizeof(double), ctx->stream));
     } else {
         if (phase >= 1 && !p->lpd_dev) {
-            BDF_HIP(hipMalloc((void **)&p->lpd_dev, (size_t)n * 2 * sizeof(double)));
+            if (int rc = p->lpd_dev.alloc((size_t)n * 2)) return rc;
             BDF_HIP(hipMemsetAsync(p->lpd_dev, 0, (size_t)n * 2 * sizeof(double), ctx->stream));
         }
         a.M = p->lpd_dev; a.A = p->lpd_dev ? p->lpd_dev + n : nullptr;

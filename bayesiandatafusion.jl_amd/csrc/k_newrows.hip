@@ -253,7 +253,7 @@ extern "C" int bdf_newrows_quad(bdf_ctx *ctx, int D, int64_t M, const double *La
     BDF_REQUIRE(nblocks <= INT32_MAX, BDF_ERR_ARG, "bdf_newrows_quad: %lld rows are more than one launch covers", (long long)M);
     if (M == 0) return BDF_OK;
     BDF_HIP(hipSetDevice(ctx->device));
-    if (!ctx->newrows_W) BDF_HIP(hipMalloc((void **)&ctx->newrows_W, (size_t)BDF_MAX_D * BDF_MAX_D * sizeof(double)));
+    if (!ctx->newrows_W) { if (int rc = ctx->newrows_W.alloc((size_t)BDF_MAX_D * BDF_MAX_D)) return rc; }
     const int DP = D <= 16 ? 16 : (D <= 32 ? 32 : 64);
     hipLaunchKernelGGL(k_newrows_prep, dim3(1), dim3(64), 0, ctx->stream, D, DP, Lambda_dev, ctx->newrows_W, ctx->flag_dev);
     const double *W = ctx->newrows_W;
@@ -285,7 +285,7 @@ static int newrows_draw(bdf_ctx *ctx, bdf_pairs *p, int phase, double clamp_lo, 
 {
     const int64_t n = p->n;
     if (phase >= 1 && !p->newrows_dev) {
-        BDF_HIP(hipMalloc((void **)&p->newrows_dev, (size_t)n * BDF_NEWROWS_PLANES * sizeof(double)));
+        if (int rc = p->newrows_dev.alloc((size_t)n * BDF_NEWROWS_PLANES)) return rc;
         BDF_HIP(hipMemsetAsync(p->newrows_dev, 0, (size_t)n * BDF_NEWROWS_PLANES * sizeof(double), ctx->stream));
     }
     if (p->newrows_dev) { pl.mean = p->newrows_dev; pl.M2 = pl.mean + n; pl.sq = pl.M2 + n; pl.M = pl.sq + n; pl.A = pl.M + n; }

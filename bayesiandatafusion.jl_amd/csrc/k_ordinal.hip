@@ -166,27 +166,24 @@ extern "C" int bdf_ordinal_create(bdf_ctx *ctx, int K, double step, int64_t trac
     h[BDF_ORD_SIGMA] = step;
     const size_t trace_doubles = (size_t)trace_capacity * (size_t)(K - 1);
     BDF_HIP(hipSetDevice(ctx->device));
-    double *dev = nullptr;
-    BDF_HIP(hipMalloc((void **)&dev, (BDF_ORD_TRACE + trace_doubles) * sizeof(double)));
+    std::unique_ptr<bdf_ordinal> o(new bdf_ordinal());
+    o->ctx = ctx; o->K = K; o->capacity = trace_capacity; o->state_doubles = BDF_ORD_TRACE + trace_doubles;
+    o->stream = ctx->stream;
+    if (int rc = o->state_dev.alloc(o->state_doubles)) return rc;
+    double *dev = o->state_dev;
     hipError_t e = hipMemcpy(dev, h, sizeof(h), hipMemcpyHostToDevice);
     if (e == hipSuccess && trace_doubles) e = hipMemset(dev + BDF_ORD_TRACE, 0xff, trace_doubles * sizeof(double));
     if (e != hipSuccess) {
-        (void)hipFree(dev);
         bdf_set_error("bdf_ordinal_create: filling the state failed: %s", hipGetErrorString(e));
         return BDF_ERR_HIP;
     }
-    bdf_ordinal *o = new bdf_ordinal();
-    o->ctx = ctx; o->K = K; o->capacity = trace_capacity; o->adapt_steps = 0; o->state_doubles = BDF_ORD_TRACE + trace_doubles; o->state_dev = dev;
-    o->stream = ctx->stream;
-    *out = o;
+    *out = o.release();
     return BDF_OK;
 }
 
 extern "C" int bdf_ordinal_destroy(bdf_ordinal *ord)
 {
-    if (!ord) return BDF_OK;
-    if (ord->state_dev) (void)hipFree(ord->state_dev);
-    delete ord;
+    if (ord) delete ord;
     return BDF_OK;
 }
 

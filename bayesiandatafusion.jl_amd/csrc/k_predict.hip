@@ -259,20 +259,15 @@ extern "C" int bdf_pairs_create(bdf_ctx *ctx, int n_modes, int64_t n, const void
         BDF_REQUIRE(v >= 1 && v < (int64_t)0x7fffffff, BDF_ERR_BOUNDS, "bdf_pairs_create: id %lld out of range", (long long)v);
         h[q] = (int32_t)(v - 1);
     }
-    bdf_pairs *p = new bdf_pairs();
-    p->ctx = ctx; p->n_modes = n_modes; p->n = n; p->count = 0.0; p->baseline_dev = nullptr; p->orig_dev = nullptr; p->sorted_mode = -1;
-    p->ids_dev = nullptr; p->values_dev = nullptr; p->avg_dev = nullptr; p->sq_dev = nullptr; p->auc_ws = nullptr; p->link = 0; p->link_r = 0.0;
-    p->lpd_dev = nullptr; p->lpd_draws = 0.0; p->waic_dev = nullptr; p->waic_draws = 0.0; p->scale_dev = nullptr; p->scale_mode = 0;
-    p->newrows_dev = nullptr; p->newrows_draws = 0.0; p->newrows_score = false;
-    p->foldin_ptr_dev = nullptr; p->foldin_rows = p->foldin_cols = 0;
-    struct Guard { bdf_pairs *p; ~Guard() { if (p) bdf_pairs_destroy(p); } } guard{p};        // error paths free what was allocated
+    std::unique_ptr<bdf_pairs> p(new bdf_pairs());       // error paths free what was allocated
+    p->ctx = ctx; p->n_modes = n_modes; p->n = n;
     p->ids_host = h;
     p->values_host.assign(values, values + (n ? n : 0));
     size_t nb = std::max<size_t>((size_t)n * sizeof(double), 8);
-    BDF_HIP(hipMalloc((void **)&p->ids_dev, std::max<size_t>(h.size() * sizeof(int32_t), 8)));
-    BDF_HIP(hipMalloc((void **)&p->values_dev, nb));
-    BDF_HIP(hipMalloc((void **)&p->avg_dev, nb));
-    BDF_HIP(hipMalloc((void **)&p->sq_dev, nb));
+    int rc;
+    if ((rc = p->ids_dev.alloc_bytes(std::max<size_t>(h.size() * sizeof(int32_t), 8))) || (rc = p->values_dev.alloc_bytes(nb)) ||
+        (rc = p->avg_dev.alloc_bytes(nb)) || (rc = p->sq_dev.alloc_bytes(nb)))
+        return rc;
     if (n) {
         BDF_HIP(hipMemcpy(p->ids_dev, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice));
         BDF_HIP(hipMemcpy(p->values_dev, values, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
@@ -282,24 +277,20 @@ extern "C" int bdf_pairs_create(bdf_ctx *ctx, int n_modes, int64_t n, const void
     BDF_HIP(hipMemsetAsync(p->avg_dev, 0, nb, ctx->stream));
     BDF_HIP(hipMemsetAsync(p->sq_dev, 0, nb, ctx->stream));
     BDF_HIP(hipStreamSynchronize(ctx->stream));
-    guard.p = nullptr;
-    *out = p;
+    *out = p.release();
     return BDF_OK;
+}
+
+bdf_pairs::~bdf_pairs()
+{
+    if (!ctx) return;
+    hipSetDevice(ctx->device);
+    hipStreamSynchronize(ctx->stream);
 }
 
 extern "C" int bdf_pairs_destroy(bdf_pairs *p)
 {
-    if (!p) return BDF_OK;
-    hipSetDevice(p->ctx->device);
-    hipStreamSynchronize(p->ctx->stream);
-    hipFree(p->ids_dev); hipFree(p->values_dev); hipFree(p->avg_dev); hipFree(p->sq_dev);
-    if (p->orig_dev) hipFree(p->orig_dev);
-    if (p->auc_ws) hipFree(p->auc_ws);
-    if (p->lpd_dev) hipFree(p->lpd_dev);
-    if (p->waic_dev) hipFree(p->waic_dev);
-    if (p->newrows_dev) hipFree(p->newrows_dev);
-    if (p->foldin_ptr_dev) hipFree(p->foldin_ptr_dev);
-    delete p;
+    if (p) delete p;
     return BDF_OK;
 }
 
@@ -386,7 +377,7 @@ extern "C" int bdf_pairs_sort(bdf_pairs *p, int mode)
     BDF_HIP(hipStreamSynchronize(p->ctx->stream));
     BDF_HIP(hipMemcpy(p->ids_dev, ids.data(), ids.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     BDF_HIP(hipMemcpy(p->values_dev, vals.data(), vals.size() * sizeof(double), hipMemcpyHostToDevice));
-    BDF_HIP(hipMalloc((void **)&p->orig_dev, (size_t)n * sizeof(int32_t)));
+    if (int rc = p->orig_dev.alloc((size_t)n)) return rc;
     BDF_HIP(hipMemcpy(p->orig_dev, perm.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
     p->orig_host = perm;
     p->sorted_mode = mode;

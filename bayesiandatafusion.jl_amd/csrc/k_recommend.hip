@@ -19,13 +19,14 @@
 
 struct bdf_scores {
     bdf_draw_ring ring;
-    double *sum_dev;               // n_rows x M, row-major, then BDF_REC_GUARD doubles of NaN that nothing writes
+    DevBuf<double> sum_dev;        // n_rows x M, row-major, then BDF_REC_GUARD doubles of NaN that nothing writes
     // bdf_scores_metrics: the relevant test items of every scored row, built at the first call for (pairs, class_cut)
-    const bdf_pairs *rel_pairs;
-    double rel_cut;
-    int64_t *rel_ptr_dev;          // n_rows + 1
-    int32_t *rel_items_dev;        // 1-based item ids, ascending within a row
-    double *row_metrics_dev;       // 4 planes of n_rows: recall, ndcg, hit, scored
+    const bdf_pairs *rel_pairs = nullptr;      // borrowed
+    double rel_cut = 0.0;
+    DevBuf<int64_t> rel_ptr_dev;   // n_rows + 1
+    DevBuf<int32_t> rel_items_dev; // 1-based item ids, ascending within a row
+    DevBuf<double> row_metrics_dev;    // 4 planes of n_rows: recall, ndcg, hit, scored
+    ~bdf_scores() { ring.drain(); }
 };
 
 namespace {
@@ -228,11 +229,11 @@ __global__ __launch_bounds__(256) void k_rec_metrics_final(const double *__restr
     }
 }
 
-int ring_alloc(void **p, size_t bytes, const char *who, const char *what, int64_t n_rows, int64_t M)
+template <typename T>
+int ring_alloc(DevBuf<T> &p, size_t bytes, const char *who, const char *what, int64_t n_rows, int64_t M)
 {
-    const hipError_t e = hipMalloc(p, std::max<size_t>(bytes, 16));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
+    if (p.alloc_bytes(std::max<size_t>(bytes, 16))) {
+        const hipError_t e = hipGetLastError();         // (the allocation's error, which this also clears)
         bdf_set_error("%s: no device memory for %s of N = %lld rows and M = %lld columns (%zu bytes): %s", who, what, (long long)n_rows, (long long)M,
                       bytes, hipGetErrorString(e));
         return BDF_ERR_HIP;
@@ -243,24 +244,24 @@ int ring_alloc(void **p, size_t bytes, const char *who, const char *what, int64_
 }  // namespace
 
 // ---- the ring of draws (draw_ring.h), then bdf_scores
-int bdf_ring_init(bdf_draw_ring *r, const char *who, bdf_ctx *ctx, int64_t n_rows, int64_t M, int D, int batch, int tail, int (*flush)(void *))
+int bdf_ring_init(bdf_draw_ring *r, const char *who, bdf_ctx *ctx, int64_t n_rows, int64_t M, int D, int batch, int tail, int (*flush)(void *), void *owner)
 {
     BDF_REQUIRE(n_rows >= 0 && M >= 0 && n_rows < (int64_t)0x7fffffff && M < (int64_t)0x7fffffff, BDF_ERR_ARG,
                 "%s: n_rows=%lld and M=%lld must be in 0..2^31-2", who, (long long)n_rows, (long long)M);
     BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "%s: num_latent=%d must be in 1..%d", who, D, BDF_MAX_D);
     BDF_REQUIRE(batch >= 1 && batch <= BDF_REC_MAX_BATCH, BDF_ERR_ARG, "%s: batch=%d must be in 1..%d", who, batch, BDF_REC_MAX_BATCH);
-    r->ctx = ctx; r->n_rows = n_rows; r->M = M; r->D = D; r->nblk = (D + 3) / 4; r->batch = batch; r->held = 0; r->draws = 0.0;
-    r->slot = (n_rows + M) * 4 * r->nblk + tail; r->ring_dev = nullptr; r->rows_dev = nullptr; r->flush = flush; r->owner = nullptr;
+    r->ctx = ctx; r->n_rows = n_rows; r->M = M; r->D = D; r->nblk = (D + 3) / 4; r->batch = batch;
+    r->slot = (n_rows + M) * 4 * r->nblk + tail; r->flush = flush; r->owner = owner;
     return BDF_OK;
 }
 
-int bdf_ring_plane(const bdf_draw_ring *r, const char *who, const char *what, int fill, double **plane)
+int bdf_ring_plane(const bdf_draw_ring *r, const char *who, const char *what, int fill, DevBuf<double> &plane)
 {
     const size_t cells = (size_t)r->n_rows * (size_t)r->M, bytes = cells * sizeof(double);
-    const int rc = ring_alloc((void **)plane, bytes + BDF_REC_GUARD * sizeof(double), who, what, r->n_rows, r->M);
+    const int rc = ring_alloc(plane, bytes + BDF_REC_GUARD * sizeof(double), who, what, r->n_rows, r->M);
     if (rc) return rc;
-    if (bytes) BDF_HIP(hipMemsetAsync(*plane, fill, bytes, r->ctx->stream));
-    BDF_HIP(hipMemsetAsync(*plane + cells, 0xff, BDF_REC_GUARD * sizeof(double), r->ctx->stream));      // (NaN)
+    if (bytes) BDF_HIP(hipMemsetAsync(plane, fill, bytes, r->ctx->stream));
+    BDF_HIP(hipMemsetAsync(plane + cells, 0xff, BDF_REC_GUARD * sizeof(double), r->ctx->stream));      // (NaN)
     return BDF_OK;
 }
 
@@ -268,9 +269,9 @@ int bdf_ring_alloc(bdf_draw_ring *r, const char *who, const int32_t *rows_dev)
 {
     const int64_t n_rows = r->n_rows;
     int rc;
-    if ((rc = ring_alloc((void **)&r->ring_dev, (size_t)r->batch * (size_t)r->slot * sizeof(double), who, "the ring of draws", n_rows, r->M))) return rc;
+    if ((rc = ring_alloc(r->ring_dev, (size_t)r->batch * (size_t)r->slot * sizeof(double), who, "the ring of draws", n_rows, r->M))) return rc;
     if (rows_dev && n_rows) {
-        if ((rc = ring_alloc((void **)&r->rows_dev, (size_t)n_rows * sizeof(int32_t), who, "the scored rows", n_rows, r->M))) return rc;
+        if ((rc = ring_alloc(r->rows_dev, (size_t)n_rows * sizeof(int32_t), who, "the scored rows", n_rows, r->M))) return rc;
         r->rows_host.resize((size_t)n_rows);
         BDF_HIP(hipStreamSynchronize(r->ctx->stream));
         BDF_HIP(hipMemcpy(r->rows_host.data(), rows_dev, (size_t)n_rows * sizeof(int32_t), hipMemcpyDeviceToHost));
@@ -282,8 +283,6 @@ int bdf_ring_alloc(bdf_draw_ring *r, const char *who, const int32_t *rows_dev)
     BDF_HIP(hipStreamSynchronize(r->ctx->stream));
     return BDF_OK;
 }
-
-void bdf_ring_free(bdf_draw_ring *r) { hipFree(r->ring_dev); hipFree(r->rows_dev); }          // (either may be null)
 
 int bdf_ring_push(bdf_draw_ring *r, const double *U, const double *V)
 {
@@ -350,15 +349,7 @@ int bdf_topk_plane(const bdf_draw_ring *r, const char *who, const double *plane,
 
 extern "C" int bdf_scores_destroy(bdf_scores *sc)
 {
-    if (!sc) return BDF_OK;
-    hipSetDevice(sc->ring.ctx->device);
-    hipStreamSynchronize(sc->ring.ctx->stream);
-    hipFree(sc->sum_dev);
-    bdf_ring_free(&sc->ring);
-    if (sc->rel_ptr_dev) hipFree(sc->rel_ptr_dev);
-    if (sc->rel_items_dev) hipFree(sc->rel_items_dev);
-    if (sc->row_metrics_dev) hipFree(sc->row_metrics_dev);
-    delete sc;
+    if (sc) delete sc;
     return BDF_OK;
 }
 
@@ -368,17 +359,13 @@ extern "C" int bdf_scores_create(bdf_ctx *ctx, int64_t n_rows, int64_t M, int D,
 {
     const char *who = "bdf_scores_create";
     BDF_REQUIRE(ctx && out, BDF_ERR_ARG, "%s: NULL argument", who);
-    bdf_draw_ring ring;
-    int rc = bdf_ring_init(&ring, who, ctx, n_rows, M, D, batch, 0, scores_flush);
+    std::unique_ptr<bdf_scores> sc(new bdf_scores());
+    int rc = bdf_ring_init(&sc->ring, who, ctx, n_rows, M, D, batch, 0, scores_flush, sc.get());
     if (rc) return rc;
     BDF_HIP(hipSetDevice(ctx->device));
-    bdf_scores *sc = new bdf_scores();
-    sc->ring = ring; sc->ring.owner = sc;                     // (the other fields are null)
-    struct Guard { bdf_scores *p; ~Guard() { if (p) bdf_scores_destroy(p); } } guard{sc};
-    if ((rc = bdf_ring_plane(&sc->ring, who, "the score sum", 0, &sc->sum_dev))) return rc;
+    if ((rc = bdf_ring_plane(&sc->ring, who, "the score sum", 0, sc->sum_dev))) return rc;
     if ((rc = bdf_ring_alloc(&sc->ring, who, rows_dev))) return rc;
-    guard.p = nullptr;
-    *out = sc;
+    *out = sc.release();
     return BDF_OK;
 }
 
@@ -461,12 +448,9 @@ extern "C" int bdf_scores_metrics(bdf_scores *sc, const int32_t *items, int K, c
         for (size_t q = 0; q < cells.size(); q++) { ptr[(size_t)cells[q].first + 1]++; its[q] = cells[q].second; }
         for (int64_t r = 0; r < n_rows; r++) ptr[(size_t)r + 1] += ptr[(size_t)r];
         BDF_HIP(hipStreamSynchronize(ctx->stream));
-        if (sc->rel_ptr_dev) { hipFree(sc->rel_ptr_dev); sc->rel_ptr_dev = nullptr; }
-        if (sc->rel_items_dev) { hipFree(sc->rel_items_dev); sc->rel_items_dev = nullptr; }
         int rc;
-        if ((rc = bdf_upload(&sc->rel_ptr_dev, ptr))) return rc;
-        if ((rc = bdf_upload(&sc->rel_items_dev, its))) return rc;
-        if (!sc->row_metrics_dev) BDF_HIP(hipMalloc((void **)&sc->row_metrics_dev, std::max<size_t>((size_t)n_rows * 4 * sizeof(double), 16)));
+        if ((rc = sc->rel_ptr_dev.upload(ptr)) || (rc = sc->rel_items_dev.upload(its))) return rc;
+        if (!sc->row_metrics_dev && (rc = sc->row_metrics_dev.alloc_bytes(std::max<size_t>((size_t)n_rows * 4 * sizeof(double), 16)))) return rc;
         sc->rel_pairs = test; sc->rel_cut = class_cut;
     }
     if (n_rows > 0) {

@@ -709,25 +709,18 @@ int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T
     plan.cost_max = rounds[(size_t)rank.front()].cost;
     plan.cost_min = rounds[(size_t)rank.back()].cost;
     plan.n_waves = (int32_t)nw;
-    BDF_HIP(hipMalloc((void **)&plan.jobs_dev, jobs.size() * sizeof(ColJob)));
+    int rc;
+    if ((rc = plan.jobs_dev.alloc(jobs.size()))) return rc;
     BDF_HIP(hipMemcpy(plan.jobs_dev, jobs.data(), jobs.size() * sizeof(ColJob), hipMemcpyHostToDevice));
-    BDF_HIP(hipMalloc((void **)&plan.rows_dev, std::max<size_t>(splits.size() * sizeof(ColSplit), 8)));
+    if ((rc = plan.rows_dev.alloc_bytes(std::max<size_t>(splits.size() * sizeof(ColSplit), 8)))) return rc;
     if (!splits.empty()) BDF_HIP(hipMemcpy(plan.rows_dev, splits.data(), splits.size() * sizeof(ColSplit), hipMemcpyHostToDevice));
-    BDF_HIP(hipMalloc((void **)&plan.partials_dev, std::max<size_t>((size_t)n_slots_total * COL_PSZ * sizeof(double), 8)));
-    BDF_HIP(hipMalloc((void **)&plan.arrived_dev, std::max<size_t>(splits.size() * sizeof(int32_t), 8)));
+    if ((rc = plan.partials_dev.alloc_bytes(std::max<size_t>((size_t)n_slots_total * COL_PSZ * sizeof(double), 8)))) return rc;
+    if ((rc = plan.arrived_dev.alloc_bytes(std::max<size_t>(splits.size() * sizeof(int32_t), 8)))) return rc;
     // (on the launch stream: a memset on the NULL stream can run under the first launch -- DESIGN.md section 8)
     BDF_HIP(hipMemsetAsync(plan.arrived_dev, 0, std::max<size_t>(splits.size() * sizeof(int32_t), 8), ctx->stream));
     return BDF_OK;
 }
 
-void bdf_col_plan_free(bdf_col_plan &plan)
-{
-    if (plan.jobs_dev) (void)hipFree(plan.jobs_dev);
-    if (plan.rows_dev) (void)hipFree(plan.rows_dev);
-    if (plan.partials_dev) (void)hipFree(plan.partials_dev);
-    if (plan.arrived_dev) (void)hipFree(plan.arrived_dev);
-    plan = bdf_col_plan{};
-}
 
 int64_t bdf_col_image_max_rows() { return (int64_t)COL_IMG_PAD_ID; }
 

@@ -616,23 +616,10 @@ __global__ __launch_bounds__(256, 2) void k_rows_lr32(LrArgs a, const RowItem *_
 
 int lr_buffers(bdf_ctx *ctx, size_t vt_bytes, size_t mrows_bytes)
 {
-    if (!ctx->lr_T) BDF_HIP(hipMalloc((void **)&ctx->lr_T, (size_t)(3 * 64 * 64 + 64) * sizeof(double)));
-    if (mrows_bytes > ctx->lr_mrows_bytes) {
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->lr_mrows) BDF_HIP(hipFree(ctx->lr_mrows));
-        ctx->lr_mrows = nullptr; ctx->lr_mrows_bytes = 0;
-        const size_t nb = (mrows_bytes + 255) & ~(size_t)255;
-        BDF_HIP(hipMalloc((void **)&ctx->lr_mrows, nb));
-        ctx->lr_mrows_bytes = nb;
-    }
-    if (vt_bytes > ctx->lr_vt_bytes) {
-        BDF_HIP(hipStreamSynchronize(ctx->stream));
-        if (ctx->lr_vt) BDF_HIP(hipFree(ctx->lr_vt));
-        ctx->lr_vt = nullptr; ctx->lr_vt_bytes = 0;
-        const size_t nb = (vt_bytes + 255) & ~(size_t)255;
-        BDF_HIP(hipMalloc((void **)&ctx->lr_vt, nb));
-        ctx->lr_vt_bytes = nb;
-    }
+    int rc;
+    if (!ctx->lr_T && (rc = ctx->lr_T.alloc(3 * 64 * 64 + 64))) return rc;
+    if (mrows_bytes > ctx->lr_mrows.bytes() && (rc = ctx->lr_mrows.grow((mrows_bytes + 255) & ~(size_t)255, ctx->stream))) return rc;
+    if (vt_bytes > ctx->lr_vt.bytes() && (rc = ctx->lr_vt.grow((vt_bytes + 255) & ~(size_t)255, ctx->stream))) return rc;
     return BDF_OK;
 }
 

@@ -101,7 +101,7 @@ extern "C" int bdf_pairs_waic_update(bdf_ctx *ctx, bdf_pairs *p, const double *b
         BDF_HIP(hipMemsetAsync(stats_out, 0, 4 * sizeof(double), ctx->stream));
     } else {
         if (phase >= 1 && !p->waic_dev) {
-            BDF_HIP(hipMalloc((void **)&p->waic_dev, (size_t)n * 4 * sizeof(double)));
+            if (int rc = p->waic_dev.alloc((size_t)n * 4)) return rc;
             BDF_HIP(hipMemsetAsync(p->waic_dev, 0, (size_t)n * 4 * sizeof(double), ctx->stream));
         }
         if (p->waic_dev) { a.M = p->waic_dev; a.A = a.M + n; a.mu = a.A + n; a.M2 = a.mu + n; }

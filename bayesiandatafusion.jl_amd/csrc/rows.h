@@ -74,7 +74,7 @@ inline int bdf_rows_dp(int D) { return D <= 16 ? 16 : (D <= 32 ? 32 : 64); }
 int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a, const bdf_rel *const *rels, const int *modes, int shard,
                            int n_shards, bool dump);
 bdf_rows_state *bdf_rows_state_create();
-void bdf_rows_state_destroy(bdf_ctx *ctx);                        // every plan of the context, then the state itself
+void bdf_rows_state_delete(bdf_rows_state *st);                   // its plans and images free themselves
 void bdf_plans_release(bdf_ctx *ctx, uint64_t rel_serial);        // rel_serial 0: every plan of the context
 // {iteration number, rows by K1-lr, K1s, K1c, K1, K1's items, K1c's waves} of the latest launch under entity_tag, or NULL
 const std::array<int64_t, 7> *bdf_rows_dispatch_counts(const bdf_ctx *ctx, uint32_t entity_tag);
@@ -179,16 +179,15 @@ struct ColPlanDev {
 };
 struct bdf_row_ref { int32_t out, orig; int64_t qb, cnt; };
 struct bdf_col_plan {
-    ColJob *jobs_dev = nullptr;
-    ColSplit *rows_dev = nullptr;
-    double *partials_dev = nullptr;
-    int32_t *arrived_dev = nullptr;
+    DevBuf<ColJob> jobs_dev;
+    DevBuf<ColSplit> rows_dev;
+    DevBuf<double> partials_dev;
+    DevBuf<int32_t> arrived_dev;
     int32_t n_waves = 0, n_split_rows = 0;
     int64_t n_rounds = 0;
     double cost_max = 0.0, cost_min = 0.0;      // the planner's cost model: the heaviest and the lightest wave
 };
 int bdf_col_plan_build(bdf_ctx *ctx, const std::vector<bdf_row_ref> &rows, int T, int64_t slots, bdf_col_plan &plan);
-void bdf_col_plan_free(bdf_col_plan &plan);
 // img_tier: the kind of a.img_in (ignored without one)
 int bdf_col_launch(bdf_ctx *ctx, const SampleArgs &a, const bdf_col_plan &plan, int64_t M_other, int img_tier, hipEvent_t e0, hipEvent_t e1);
 

@@ -32,24 +32,20 @@ struct PlanKey {
 };
 
 struct Plan {
-    PlanDev dev{};                    // K1's items, split rows and slab
-    RowItem *small_dev = nullptr;
+    PlanDev dev{};                    // K1's items, split rows and slab: the kernels' view of the seven buffers below
+    DevBuf<Item> direct_dev, split_dev;
+    DevBuf<SplitRow> rows_dev;
+    DevBuf<int32_t> order_dev, arrived_dev;
+    DevBuf<double> partials_dev;
+    DevBuf<RowItem> small_dev;
     int64_t n_small = 0;              // entries of small_dev (a multiple of 4)
-    RowItem *lr_dev = nullptr;        // the rows of the low-rank sampler, and their positions for the back-transform
-    int32_t *lr_rows_dev = nullptr;
+    DevBuf<RowItem> lr_dev;           // the rows of the low-rank sampler, and their positions for the back-transform
+    DevBuf<int32_t> lr_rows_dev;
     int64_t n_lr = 0, n_lr_padded = 0;   // rows of the low-rank sampler in all; records of the rows of at most key.lr observations (a multiple of 4)
     int64_t n_lr32_padded = 0;           // ... and of the rows of key.lr + 1 .. key.lr32 observations, behind them in lr_dev
     bdf_col_plan col;                 // the rows of k_rows_col (K1c)
     int64_t rows_lr = 0, rows_small = 0, rows_col = 0, rows_k1 = 0;      // how the plan's rows are shared out (bdf_ctx_rows_dispatch)
 };
-
-void plan_free(Plan &p)
-{
-    for (void *q : {(void *)p.small_dev, (void *)p.lr_dev, (void *)p.lr_rows_dev, (void *)p.dev.direct, (void *)p.dev.split, (void *)p.dev.rows,
-                    (void *)p.dev.order, (void *)p.dev.partials, (void *)p.dev.arrived})
-        (void)hipFree(q);
-    bdf_col_plan_free(p.col);
-}
 
 // what lr_T / lr_vt of the context were computed from: a later chunk of the same entity launch reuses them
 struct LrKey {
@@ -64,7 +60,7 @@ std::mutex g_plans_mutex;             // around every context's plan cache
 // so does whoever else writes a sample (bdf_gather_image_invalidate).  A launch believes it only when its caller vouches that nothing
 // outside the library writes the sample either (bdf_ctx::gimg_trust: bdf_gibbs_sweep, whose buffers are its own); every other launch
 // packs the image anew.
-struct GatherImage { double *dev = nullptr; int64_t rows = 0; int tier = 0; bool valid = false; };
+struct GatherImage { DevBuf<double> dev; int64_t rows = 0; int tier = 0; bool valid = false; };
 
 }  // namespace
 
@@ -170,7 +166,7 @@ int build_plan(bdf_ctx *ctx, const PlanKey &key, const std::vector<RowRef> &rows
     plan.rows_k1 = (int64_t)direct.size() + (int64_t)srows.size();
     while (small.size() % 4) small.push_back(RowItem{-1, 0, 0, 0, 0});
     plan.n_small = (int64_t)small.size();
-    if (!small.empty() && (rc = bdf_upload(&plan.small_dev, small))) return rc;
+    if (!small.empty() && (rc = plan.small_dev.upload(small))) return rc;
     plan.n_lr = (int64_t)lr.size() + (int64_t)lr32.size();
     if (plan.n_lr > 0) {
         // longest first: the waves of a workgroup then have rows of like length
@@ -190,23 +186,19 @@ int build_plan(bdf_ctx *ctx, const PlanKey &key, const std::vector<RowRef> &rows
         plan.n_lr_padded = (int64_t)lr.size();
         plan.n_lr32_padded = (int64_t)lr32.size();
         lr.insert(lr.end(), lr32.begin(), lr32.end());
-        if ((rc = bdf_upload(&plan.lr_dev, lr)) || (rc = bdf_upload(&plan.lr_rows_dev, lr_rows))) return rc;
+        if ((rc = plan.lr_dev.upload(lr)) || (rc = plan.lr_rows_dev.upload(lr_rows))) return rc;
     }
-    Item *direct_dev, *split_dev;
-    SplitRow *rows_dev;
-    int32_t *order_dev, *arrived_dev;
-    double *partials_dev;
-    if ((rc = bdf_upload(&direct_dev, direct)) || (rc = bdf_upload(&split_dev, split)) ||
-        (rc = bdf_upload(&rows_dev, srows)) || (rc = bdf_upload(&order_dev, order)))
+    if ((rc = plan.direct_dev.upload(direct)) || (rc = plan.split_dev.upload(split)) ||
+        (rc = plan.rows_dev.upload(srows)) || (rc = plan.order_dev.upload(order)) ||
+        (rc = plan.partials_dev.alloc_bytes(std::max<size_t>(split.size() * (size_t)psz * sizeof(double), 8))) ||
+        (rc = plan.arrived_dev.alloc_bytes(std::max<size_t>(srows.size() * sizeof(int32_t), 8))))
         return rc;
-    BDF_HIP(hipMalloc((void **)&partials_dev, std::max<size_t>(split.size() * (size_t)psz * sizeof(double), 8)));
-    BDF_HIP(hipMalloc((void **)&arrived_dev, std::max<size_t>(srows.size() * sizeof(int32_t), 8)));
     // on the launch stream: hipMemset runs on the NULL stream and returns before the device has done it, and a kernel on a
     // non-blocking stream does not wait for it -- the first launch of a new plan could have its counters zeroed under it
     // (a split row then never finds its last piece: the row keeps its old content)
-    BDF_HIP(hipMemsetAsync(arrived_dev, 0, std::max<size_t>(srows.size() * sizeof(int32_t), 8), ctx->stream));
-    plan.dev = PlanDev{direct_dev, (int32_t)direct.size(), split_dev, (int32_t)split.size(), rows_dev, (int32_t)srows.size(),
-                       partials_dev, arrived_dev, order_dev};
+    BDF_HIP(hipMemsetAsync(plan.arrived_dev, 0, std::max<size_t>(srows.size() * sizeof(int32_t), 8), ctx->stream));
+    plan.dev = PlanDev{plan.direct_dev.get(), (int32_t)direct.size(), plan.split_dev.get(), (int32_t)split.size(), plan.rows_dev.get(),
+                       (int32_t)srows.size(), plan.partials_dev.get(), plan.arrived_dev.get(), plan.order_dev.get()};
     return BDF_OK;
 }
 
@@ -336,23 +328,17 @@ int launch_lowrank(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t 
     return rc;
 }
 
-void images_free(bdf_rows_state *st)
-{
-    for (auto &kv : st->images) (void)hipFree(kv.second.dev);        // (hipFree waits for the launches that still read them)
-    st->images.clear();
-}
-
 // the context's image of the `rows` rows at `sample` (allocated at first use; its content is the caller's business)
 int image_of(bdf_ctx *ctx, const double *sample, int64_t rows, int tier, GatherImage **out)
 {
     auto &m = ctx->rows->images;
     auto it = m.find(sample);
-    if (it != m.end() && (it->second.rows != rows || it->second.tier != tier)) { (void)hipFree(it->second.dev); m.erase(it); it = m.end(); }
+    if (it != m.end() && (it->second.rows != rows || it->second.tier != tier)) { m.erase(it); it = m.end(); }
     if (it == m.end()) {
         GatherImage g;
         g.rows = rows; g.tier = tier;
-        BDF_HIP(hipMalloc((void **)&g.dev, (size_t)std::max<int64_t>(rows, 1) * (size_t)bdf_gather_image_row_doubles(tier) * sizeof(double)));
-        it = m.emplace(sample, g).first;
+        if (int rc = g.dev.alloc((size_t)std::max<int64_t>(rows, 1) * (size_t)bdf_gather_image_row_doubles(tier))) return rc;
+        it = m.emplace(sample, std::move(g)).first;
     }
     *out = &it->second;
     return BDF_OK;
@@ -373,7 +359,7 @@ int launch_column(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t M
     if (tier != 0 && a.D == 32 && whole && M_other > 0 && M_other <= bdf_col_image_max_rows()) {
         int rc;
         bdf_rows_state *st = ctx->rows;
-        if (st->images.size() >= 48) images_free(st);       // (addresses no longer in use: callers that pass fresh buffers every call)
+        if (st->images.size() >= 48) st->images.clear();    // (freeing waits for the launches that still read them; addresses no longer in use: callers that pass fresh buffers every call)
         GatherImage *src;
         if ((rc = image_of(ctx, a.t[0].fac[0], M_other, tier, &src))) return rc;
         if (!(trust && src->valid)) {
@@ -401,13 +387,10 @@ int launch_column(bdf_ctx *ctx, const SampleArgs &a, const Plan &plan, int64_t M
 
 bdf_rows_state *bdf_rows_state_create() { return new bdf_rows_state(); }
 
-void bdf_rows_state_destroy(bdf_ctx *ctx)
+void bdf_rows_state_delete(bdf_rows_state *st)
 {
-    if (!ctx->rows) return;
-    bdf_plans_release(ctx, 0);
-    images_free(ctx->rows);
-    delete ctx->rows;
-    ctx->rows = nullptr;
+    std::lock_guard<std::mutex> lock(g_plans_mutex);
+    delete st;
 }
 
 const std::array<int64_t, 7> *bdf_rows_dispatch_counts(const bdf_ctx *ctx, uint32_t entity_tag)
@@ -489,7 +472,6 @@ void bdf_plans_release(bdf_ctx *ctx, uint64_t rel_serial)
         bool hit = rel_serial == 0;
         for (int r = 0; r < kv->first.n_terms; r++) hit = hit || kv->first.rel[r] == rel_serial;
         if (!hit) { ++kv; continue; }
-        plan_free(kv->second);
         kv = plans.erase(kv);
     }
 }
@@ -539,7 +521,7 @@ int bdf_launch_sample_rows(bdf_ctx *ctx, const SampleArgs &a_in, const bdf_rel *
             const bool lr_on = collect_rows(key, rels, modes, rows);
             Plan np;
             if ((rc = build_plan(ctx, key, rows, lr_on, np))) return rc;
-            it = plans.emplace(key, np).first;
+            it = plans.emplace(key, std::move(np)).first;
         }
         plan = &it->second;
     }

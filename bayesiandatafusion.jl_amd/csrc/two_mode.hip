@@ -2,13 +2,6 @@
 // mean, the centring and sparse() with its summed duplicates for both modes.  Host code only.
 #include "two_mode.h"
 
-void two_mode_free(TwoModeCsr &c)
-{
-    void *p[] = {c.rowptr, c.colidx, c.vals, c.cs, c.order};
-    for (void *q : p) if (q) hipFree(q);
-    c = TwoModeCsr{};
-}
-
 int two_mode_check(const char *who, int D, const int64_t *dims, int64_t nnz, const void *ids, int id_bytes, const double *values)
 {
     BDF_REQUIRE(D >= 1 && D <= BDF_MAX_D, BDF_ERR_ARG, "%s: num_latent=%d must be in 1..%d", who, D, BDF_MAX_D);
@@ -70,8 +63,8 @@ int two_mode_build(const char *who, const int64_t *dims, int64_t nnz, const void
         const std::vector<int32_t> order = rows_by_degree(N, [&](int32_t i) { return rowptr[i + 1] - rowptr[i]; });
         TwoModeCsr &c = out[e];
         int rc;
-        if ((rc = bdf_upload(&c.rowptr, rowptr)) || (rc = bdf_upload(&c.colidx, col)) || (rc = bdf_upload(&c.vals, val)) ||
-            (with_counts && (rc = bdf_upload(&c.cs, cs))) || (rc = bdf_upload(&c.order, order)))
+        if ((rc = c.rowptr.upload(rowptr)) || (rc = c.colidx.upload(col)) || (rc = c.vals.upload(val)) ||
+            (with_counts && (rc = c.cs.upload(cs))) || (rc = c.order.upload(order)))
             return rc;
     }
     return BDF_OK;

@@ -193,6 +193,10 @@ int bdf_ctx_set_gather(bdf_ctx *ctx, int mode);
 /* device memory for hosts without an allocator of their own (Julia); torch hosts pass tensors */
 int bdf_dev_alloc(bdf_ctx *ctx, size_t bytes, void **dptr);
 int bdf_dev_free(bdf_ctx *ctx, void *dptr);
+/* diagnostic: the blocks, and their bytes as requested, of device and pinned host memory that the library's own objects hold in this
+ * process right now -- contexts, relations, pairs, feature matrices, samplers, plans, and the temporaries of a call in flight.  Not the
+ * caller's bdf_dev_alloc blocks.  Either pointer may be NULL.  What a handle took is back at its earlier value once it is destroyed. */
+int bdf_dev_live(int64_t *blocks, int64_t *bytes);
 int bdf_h2d(bdf_ctx *ctx, void *dst_dev, const void *src_host, size_t bytes);
 int bdf_d2h(bdf_ctx *ctx, void *dst_host, const void *src_dev, size_t bytes);  /* synchronises */
 

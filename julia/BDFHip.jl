@@ -111,6 +111,12 @@ function DevArray(c::Context, a::Array{T}) where T
     finalizer(x -> ccall((:bdf_dev_free, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}), x.ctx.h, x.p), d)
     d
 end
+"(blocks, bytes) of device and pinned host memory that the library's own objects hold in this process"
+function dev_live()
+    blocks = Ref{Int64}(0); bytes = Ref{Int64}(0)
+    check(ccall((:bdf_dev_live, lib), Cint, (Ref{Int64}, Ref{Int64}), blocks, bytes))
+    (blocks[], bytes[])
+end
 function Base.Array(d::DevArray{T}) where T
     a = Array{T}(undef, d.dims...)
     check(ccall((:bdf_d2h, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Csize_t), d.ctx.h, a, d.p, sizeof(a)))
