@@ -11,7 +11,7 @@ from ._lib import (ArgumentError, BoundsError, DimensionMismatch, HipError, NoGp
 from .indexed_df import (IndexedDF, FastIDF, nnz, getData, getCount, getI, getValues, valueMean, removeSamples)
 from .features import SparseBinMatrix, SparseBinMatrixCSR, SparseMatrixCSR, sparse_csr
 from .relation_data import (Entity, EntityModel, Relation, RelationModel, RelationData, addRelation, assignToTest, setTest,
-                            setPrecision, setProbit, setCensored, setRobust, setWeights, setEntityNoise, setBias, setBackground, setDense, denseRelation, setSpikeAndSlab, setNonNegative, setRecommend, setAcquire, setNewRows, setNewTest, setNewObserved, setLogit, setCounts, setInterval, setBinned, setTestInterval, setWaic, setTestBinned, setOrdinal, setTestOrdinal, numData, numTest, hasFeatures, toStr,
+                            setPrecision, setProbit, setCensored, setRobust, setWeights, setEntityNoise, setBias, setBackground, setDense, denseRelation, setSpikeAndSlab, setNonNegative, setRecommend, setAcquire, setDiagnostics, setNewRows, setNewTest, setNewObserved, setLogit, setCounts, setInterval, setBinned, setTestInterval, setWaic, setTestBinned, setOrdinal, setTestOrdinal, numData, numTest, hasFeatures, toStr,
                             normalizeFeatures, normalizeRows)
 from .data_reading import (read_ecfp, read_sparse, read_rowcol, read_binary_int32, filter_rare, write_binary_int32,
                            write_binary_matrix, read_binary_float32, read_sparse_float32, write_sparse_float32,

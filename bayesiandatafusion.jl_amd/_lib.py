@@ -236,6 +236,12 @@ _SIGS = {
     "bdf_acquire_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bdf_acquire_copy": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int]),
     "bdf_acquire_set_draws": (C.c_int, [C.c_void_p, C.c_double]),
+    "bdf_diag_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.POINTER(C.c_void_p)]),
+    "bdf_diag_destroy": (C.c_int, [C.c_void_p]),
+    "bdf_diag_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_double, C.c_double, C.c_void_p]),
+    "bdf_diag_write": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p]),
+    "bdf_diag_plane": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_i64p]),
+    "bdf_diag_compute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "bdf_ordinal_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int64, C.POINTER(C.c_void_p)]),
     "bdf_ordinal_destroy": (C.c_int, [C.c_void_p]),
     "bdf_ordinal_set_adapt": (C.c_int, [C.c_void_p, C.c_int64]),

@@ -74,6 +74,15 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         for r in data.relations[1:]:
             if getattr(r.model, field) is not None:
                 raise ArgumentError(f"Relation {r.name} asks for {lists} but is not the first relation: macau() keeps the {keeps} of scores for the first relation only.")
+    # convergence diagnostics (setDiagnostics) are kept for the first relation's test cells
+    for r in data.relations[1:]:
+        if r.model.diagnostics is not None:
+            raise ArgumentError(f"Relation {r.name} asks for convergence diagnostics (setDiagnostics) but is not the first relation: macau() keeps the draws of the first relation's test cells only.")
+    diag = data.relations[0].model.diagnostics if data.relations else None
+    if diag is not None and numTest(data.relations[0]) == 0:
+        raise ArgumentError("Convergence diagnostics (setDiagnostics) are those of held-out predictions: the first relation has no test cells (assignToTest / setTest).")
+    if diag is not None and psamples < 4:
+        raise ArgumentError("Convergence diagnostics (setDiagnostics) split the posterior draws into two chains of at least two: psamples must be at least 4.")
     waic = data.relations[0].model.waic if data.relations else None
     if waic is not None and psamples < 2:
         raise ArgumentError("WAIC (setWaic) needs the variance of the log-likelihood over the posterior draws: psamples must be at least 2.")
@@ -85,6 +94,8 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
                           compute_ff_size=compute_ff_size, full_lambda_u=full_lambda_u, tol=tol)
     if lpd and eng.world > 1:
         raise ArgumentError("lpd = true is not possible with more than one rank: every rank scores only the test cells it predicts.")
+    if diag is not None and eng.world > 1:
+        raise ArgumentError("Convergence diagnostics (setDiagnostics) are not possible with more than one rank: every rank holds the draws of the test cells it predicts only.")
     if waic is not None and eng.world > 1:
         raise ArgumentError("WAIC (setWaic) is not possible with more than one rank: every rank holds the state of its own cells only.")
     if new_rel is not None:
@@ -105,7 +116,7 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
     # the options' posterior summaries (summaries.py), in the order their work is enqueued in an iteration: the
     # registration of an option's summary is its line here.  (Nothing is allocated or launched for an option that is off)
     run = SimpleNamespace(eng=eng, data=data, rel=rel, burnin=burnin, psamples=psamples, verbose=verbose, clamp=clamp, lpd=lpd,
-                          test=test, test_report=None)
+                          test=test, test_report=None, columns={})
     summaries = [cls(run) for cls, on in (
         (sm.FullPrediction, full_prediction),
         (sm.Recommend, rm.recommend is not None),
@@ -116,6 +127,7 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         (sm.Spike, any(st.spike is not None for st in eng.ent)),
         (sm.NonNeg, any(st.nonneg is not None for st in eng.ent)),
         (sm.Lpd, lpd and haveTest),
+        (sm.Diagnostics, diag is not None),
         (sm.NewRows, new_rel is not None),
         (sm.Waic, waic is not None),
         (sm.Ordinal, rm.ordinal is not None),
@@ -215,7 +227,7 @@ def macau(data, num_latent=10, lambda_beta=float("nan"), burnin=500, psamples=20
         else:
             stdev = np.full(len(avg), np.nan)
         extra = {"lpd": test.lpd() if psamples >= 1 else np.full(len(avg), np.nan)} if lpd else {}
-        result["predictions"] = rel.test_vec.to_frame(pred=makeClamped(avg, clamp), stdev=stdev, **extra)
+        result["predictions"] = rel.test_vec.to_frame(pred=makeClamped(avg, clamp), stdev=stdev, **extra, **run.columns)
         import pandas as pd
         tc = np.zeros((numTest(rel), len(rel.entities)), dtype=np.int64)
         for mode in range(len(rel.entities)):

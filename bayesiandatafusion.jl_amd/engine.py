@@ -606,6 +606,51 @@ class DeviceAcquire(_DrawRing):
         check(lib().bdf_acquire_set_draws(self.handle, float(draws)))
 
 
+DIAG_STATS = ("max_rhat", "min_ess", "n_rhat_high", "n_ess_low", "n_constant", "n_draws")      # stats_out of bdf_diag_compute, then 3 per scalar
+
+
+class DeviceDiag(_DeviceObject):
+    """bdf_diag: every pushed draw of the predictions of a set of pairs, and of n_scalars scalars beside them (the draw's sum of squared
+    errors, its alpha), in one plane of capacity x (n_cells + n_scalars) doubles on the device, draw-major with the cells in the
+    pairs' storage order; and the split R-hat, effective sample size and Monte Carlo standard error of every series down its columns
+    (setDiagnostics; csrc/k_diag.hip).  Everything runs on ctx's stream."""
+    _destroy = "bdf_diag_destroy"
+
+    def __init__(self, ctx, n_cells, n_scalars, capacity):
+        self.ctx, self.handle = ctx, C.c_void_p()
+        self.n_cells, self.n_scalars, self.capacity = int(n_cells), int(n_scalars), int(capacity)
+        check(lib().bdf_diag_create(ctx.handle, self.n_cells, self.n_scalars, self.capacity, C.byref(self.handle)))
+        ctx.adopt(self)
+
+    def push(self, pairs, D, factors, mean_value, alpha=1.0):
+        """this draw into the next row: the pairs' predictions as pairs.predict forms them, the sum of their squared errors and, with
+        two scalars, alpha -- a float, or a device tensor of one double that only the device reads (bdf_diag_push)"""
+        check(lib().bdf_diag_push(self.ctx.handle, self.handle, pairs.handle, int(D), _facs(factors), float(mean_value), *_alpha_args(alpha, 1.0)))
+
+    def write(self, draw, values):
+        """parity hook: row `draw` of the plane from a device tensor of n_cells + n_scalars doubles"""
+        check(lib().bdf_diag_write(self.handle, int(draw), _ptr(values)))
+
+    def plane(self):
+        """parity hook: the draws held, as a host array (draws, n_cells + n_scalars) with the cells in the pairs' storage order"""
+        p, n = C.c_void_p(), C.c_int64()
+        check(lib().bdf_diag_plane(self.handle, C.byref(p), C.byref(n)))
+        out = np.zeros((n.value, self.n_cells + self.n_scalars))
+        if n.value:
+            check(lib().bdf_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), p, out.nbytes))
+        return out
+
+    def compute(self, rhat_cut, ess_cut, pointwise=False, order=None):
+        """(stats, out) on the device (bdf_diag_compute): stats = DIAG_STATS, then (rhat, ess, mcse) per scalar; out, with `pointwise`,
+        the (n_cells, 3) tensor of every cell's (rhat, ess, mcse) at the caller's index order[storage position] (a host array, or None
+        for the storage order itself), else None"""
+        stats = self.ctx.zeros(len(DIAG_STATS) + 3 * self.n_scalars)
+        out = self.ctx.zeros(self.n_cells, 3) if pointwise else None
+        orig = self.ctx.tensor(np.asarray(order, dtype=np.int32), dtype=torch.int32) if (pointwise and order is not None) else None
+        check(lib().bdf_diag_compute(self.ctx.handle, self.handle, _ptr(orig), float(rhat_cut), float(ess_cut), _ptr(out), _ptr(stats)))
+        return stats, out
+
+
 class DeviceNewRows:
     """Cells of rows that were not in training (setNewRows / setNewTest; csrc/k_newrows.hip): the operator of
     the new rows' features, their cells as pairs whose first mode indexes the new rows, and the buffers of the three launches that

@@ -58,6 +58,8 @@ OPTIONS = (
     Option("new_test", RELATION, "new_test", lambda r: r.model.new_test is not None, "cells of new rows (setNewTest)", None, True),
     Option("new_observed", RELATION, "new_observed", lambda r: r.model.new_observed is not None, "known cells of new rows (setNewObserved)", None, True),
     Option("waic", RELATION, "waic", lambda r: r.model.waic is not None, "WAIC on its training cells (setWaic)", None, True),
+    Option("diagnostics", RELATION, "diagnostics", lambda r: r.model.diagnostics is not None, "convergence diagnostics (setDiagnostics)",
+           "keeps no draws of the predictions", True),
     Option("features", RELATION, "F", lambda r: not feat.isempty(r.F), "features (relation-level side information)"),
     Option("alpha_sample", RELATION, "alpha_sample", lambda r: r.model.alpha_sample, "a sampled precision (alpha_sample)"),
     # read by macau(lpd=True) alone, which checks them then: no other option's setter or check looks at them

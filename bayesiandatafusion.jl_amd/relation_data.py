@@ -142,6 +142,7 @@ class RelationModel:
         self.background = None    # setBackground: {"weight", "value"}; every cell that is not listed observes `value` with precision alpha weight
         self.recommend = None     # setRecommend: {"k", "rows", "exclude_listed", "batch"}; macau() returns a top-k list per row of the first entity
         self.acquire = None       # setAcquire: {"k", "rule", "kappa", "threshold", "rows", "exclude_listed", "batch"}; macau() returns a top-k list by an acquisition score
+        self.diagnostics = None   # setDiagnostics: {"pointwise", "rhat_cut", "ess_cut"}; macau() keeps every draw of the test cells' predictions and returns their split R-hat and effective sample size
         self.entity_noise = None  # setEntityNoise: {"mode" (1-based), "shape", "rate"}; a sampled noise precision per row of that entity
         self.dense = False        # setDense: all N M cells of the two-mode relation are kept as a matrix on the device, none is listed to the row kernels
         self.bias = {}            # setBias: {mode (1-based): {"shape", "rate"}}; a sampled bias per row of every listed entity
@@ -1183,6 +1184,30 @@ def setWaic(r, on=True, pointwise=False):
     if on:
         refuse(r, "waic")
     r.model.waic = {"pointwise": bool(pointwise)} if on else None
+    return None
+
+
+def setDiagnostics(r, on=True, pointwise=False, rhat_cut=1.1, ess_cut=100.0):
+    """macau() keeps every posterior draw of the predictions of this relation's TEST cells (the first relation of its RelationData) on
+    the device and says whether the draws can be trusted: per test cell, and for the draw's sum of squared test errors ("sse") and
+    a sampled precision ("alpha"), the split R-hat, the effective sample size by Geyer's initial monotone sequence and the Monte Carlo
+    standard error of the posterior mean.  result["diagnostics"] = {"n_draws", "max_rhat", "min_ess",
+    "n_rhat_high" (cells with R-hat > rhat_cut), "n_ess_low" (cells with ESS < ess_cut), "n_constant" (cells whose draws do not vary:
+    they have no figures and are in no other count), "rhat_cut", "ess_cut", "scalars": {"sse": {"rhat", "ess", "mcse"}, ...}}.
+    pointwise=True also adds the columns rhat, ess and mcse to result["predictions"].  The plane takes psamples x numTest doubles of
+    device memory.  on=False takes it back.  Nothing of the chain changes; call it at any time before macau()."""
+    if not isinstance(on, (bool, np.bool_)) or not isinstance(pointwise, (bool, np.bool_)):
+        raise ArgumentError(f"Relation {r.name}: setDiagnostics takes on = true / false and pointwise = true / false.")
+    if pointwise and not on:
+        raise ArgumentError(f"Relation {r.name}: setDiagnostics(on = false) returns no pointwise columns.")
+    cuts = []
+    for name, cut, least in (("rhat_cut", rhat_cut, 1.0), ("ess_cut", ess_cut, 0.0)):
+        if isinstance(cut, (bool, np.bool_)) or not isinstance(cut, (int, float, np.integer, np.floating)) or not np.isfinite(cut) or cut < least:
+            raise ArgumentError(f"Relation {r.name}: {name} = {cut} must be a finite number, at least {least:g} (setDiagnostics).")
+        cuts.append(float(cut))
+    if on:
+        refuse(r, "diagnostics")
+    r.model.diagnostics = {"pointwise": bool(pointwise), "rhat_cut": cuts[0], "ess_cut": cuts[1]} if on else None
     return None
 
 

@@ -5,7 +5,8 @@ and of the keys of `result` are the two tuples at the end of this module.  A sum
 reused has nothing to reset.
 
 `run`, from macau(): eng, data, rel (the first relation), burnin, psamples, verbose, clamp, lpd (as asked), test (the test pairs or
-None), test_report (their device scalars on the host, after the reporting sync).  `it`, one iteration: i, phase (0 burn-in, 1 the
+None), test_report (their device scalars on the host, after the reporting sync), columns (what a summary's result() adds to the
+columns of result["predictions"]).  `it`, one iteration: i, phase (0 burn-in, 1 the
 first posterior draw, 2 later ones), facs (rel's factors), alpha (rel's precision for this draw: 1 for probit; a sampled one is the
 device scalar of the native iteration, drawn on the row stream, and step by step the double the host has read from it).
 """
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 from ._lib import ArgumentError, check, lib
-from .engine import DeviceAcquire, DeviceScores, _ptr
+from .engine import DIAG_STATS, DeviceAcquire, DeviceDiag, DeviceScores, _ptr
 from .relation_data import _ordinal_bounds, _waic_bounds, check_test_interval, hasFeatures
 
 
@@ -311,6 +312,49 @@ class Lpd(Summary):
         result["LPD"] = self.avg
 
 
+class Diagnostics(Summary):
+    """convergence diagnostics of the test cells' predictions (setDiagnostics on the first relation): every
+    posterior draw of the predictions, of the draw's sum of squared test errors and of a sampled alpha goes into one plane on the
+    device, a second gather of the test pairs beside the prediction update's; the split R-hat, effective sample size and Monte Carlo
+    standard error of every series come from the device at the end of the run: 6 + 3 per scalar doubles are read back, and three
+    columns when asked for.  The push runs on the pairs' stream, where Lpd scores.  The native iteration's is the row stream: behind
+    this iteration's rows, its biases' base and its alpha, ahead of the next ones in order.  Step by step it is the prediction
+    stream, which is behind this iteration's rows; the next iteration's rows cannot overwrite the factors under the push, because an
+    entity's three sample buffers rotate -- the buffer of draw t is next written by the rows of iteration t + 3 -- and those rows
+    wait for the hyperprior stream, which at the start of iteration t + 2 has waited for all that the prediction stream held when
+    iteration t + 1 began, this push included (GibbsEngine.sweep: the same argument as for the prediction update).  A base that the row stream rewrites (biases, relation features) keeps the pairs on the row stream, and
+    alpha is then the double the host has read"""
+
+    def __init__(self, run):
+        super().__init__(run)
+        rel, test = run.rel, run.test
+        self.spec = rel.model.diagnostics
+        self.names = ("sse", "alpha") if rel.model.alpha_sample else ("sse",)
+        self.dev = DeviceDiag(test.ctx, test.n, len(self.names), run.psamples)
+
+    def draw(self, it):
+        if it.phase:
+            run = self.run
+            self.dev.push(run.test, run.eng.D, it.facs, run.rel.model.mean_value, it.alpha)
+
+    def finish(self):
+        s = self.spec
+        self.stats, self.out = self.dev.compute(s["rhat_cut"], s["ess_cut"], s["pointwise"], self.run.test._order)
+
+    def result(self, result):
+        st, s, n = self.stats.cpu().numpy(), self.spec, len(DIAG_STATS)
+        d = {k: (float(v) if k in ("max_rhat", "min_ess") else int(v)) for k, v in zip(DIAG_STATS, st)}
+        d = {"n_draws": d.pop("n_draws"), **d, "rhat_cut": s["rhat_cut"], "ess_cut": s["ess_cut"],
+             "scalars": {name: dict(zip(("rhat", "ess", "mcse"), (float(x) for x in st[n + 3 * k:n + 3 * k + 3]))) for k, name in enumerate(self.names)}}
+        result["diagnostics"] = d
+        if self.out is not None:
+            cols = self.out.cpu().numpy()
+            self.run.columns.update(rhat=cols[:, 0].copy(), ess=cols[:, 1].copy(), mcse=cols[:, 2].copy())
+        if self.run.verbose:
+            print(f"Diagnostics: max R̂={d['max_rhat']:.4f} min ESS={d['min_ess']:.1f} ({d['n_rhat_high']} of {self.dev.n_cells} cells above {s['rhat_cut']:g})")
+        self.dev.close()
+
+
 class Waic(Summary):
     """WAIC on the training cells (setWaic on the first relation): what kind of record every training row is
     (the table of section 17) is built once on the host; between sampled edges the levels' bins follow every draw, from the levels
@@ -444,4 +488,4 @@ class WholeMatrix(Summary):
 
 # the pieces of the verbose line and the keys of `result`, in their order (the list in macau() is in the order of an iteration's work)
 LINE_ORDER = (Lpd, Waic, Robust, EntityNoise, Bias, NewRows, Ordinal)
-RESULT_ORDER = (Ordinal, Robust, EntityNoise, Bias, Spike, NonNeg, Lpd, WholeMatrix, Recommend, Acquire, NewRows, Waic, FullPrediction)
+RESULT_ORDER = (Ordinal, Robust, EntityNoise, Bias, Spike, NonNeg, Lpd, Diagnostics, WholeMatrix, Recommend, Acquire, NewRows, Waic, FullPrediction)

@@ -1015,6 +1015,33 @@ int bdf_acquire_topk(bdf_acquire *ac, const bdf_rel *rel, int K, int rule, doubl
 int bdf_acquire_copy(bdf_acquire *ac, int plane, double *buf_dev, int64_t first, int64_t count, int write);
 int bdf_acquire_set_draws(bdf_acquire *ac, double draws);
 
+/* ---- convergence diagnostics of held-out predictions (csrc/k_diag.hip) -------------------------------------
+ * A bdf_diag object keeps every pushed draw of the predictions of n_cells pairs, and of n_scalars (0, 1 or 2) scalars beside them,
+ * in one plane of capacity x (n_cells + n_scalars) doubles, draw-major: a row holds the cells in the pairs' STORAGE order, then
+ * scalar 0, this draw's sum over the cells of (value - prediction)^2, then scalar 1, its alpha.  From the series down the plane's
+ * columns come, per series, the split R-hat, the effective sample size by Geyer's initial monotone sequence and the Monte Carlo
+ * standard error of the mean, as section 32 defines them; a series with a value that is not finite or with no variance within
+ * its halves gives three NaN.  BDF_ERR_HIP with the byte count in bdf_last_error() when the device memory does not suffice. */
+typedef struct bdf_diag bdf_diag;
+int bdf_diag_create(bdf_ctx *ctx, int64_t n_cells, int n_scalars, int64_t capacity, bdf_diag **out);
+int bdf_diag_destroy(bdf_diag *diag);
+/* this draw into the next row, on ctx's stream: every pair's prediction exactly as bdf_predict forms it (the pairs' baseline and link
+ * included), the sum of (value - prediction)^2 added in a fixed order and, with two scalars, alpha (alpha_dev, dev and nullable, wins
+ * over alpha, which must otherwise be positive and finite).  BDF_ERR_ARG when the plane is full or the pairs' n is not n_cells */
+int bdf_diag_push(bdf_ctx *ctx, bdf_diag *diag, const bdf_pairs *pairs, int D, const double *const *factors, double mean_value,
+                  double alpha, const double *alpha_dev);
+/* parity hooks: row `draw` (0-based, below the capacity) from values_dev (dev, n_cells + n_scalars doubles) on the stream of the
+ * context the object was created on -- the plane then holds at least draw + 1 draws; and the plane's address and the draws it holds */
+int bdf_diag_write(bdf_diag *diag, int64_t draw, const double *values_dev);
+int bdf_diag_plane(const bdf_diag *diag, double **dev_ptr, int64_t *draws);
+/* the statistics of the draws held (at least 4), on ctx's stream.  out_dev (dev, nullable): n_cells x 3 doubles, (R-hat, ESS, MCSE)
+ * of every cell at the caller's index orig_dev[storage position] (dev int32, nullable: the storage order itself).  stats_out (dev,
+ * 6 + 3 n_scalars doubles): over the cells that have figures the largest R-hat and the smallest ESS (NaN when none has), how many
+ * have R-hat > rhat_cut, how many ESS < ess_cut, how many cells have none (three NaN), the draws; then (R-hat, ESS, MCSE) per scalar.
+ * The counts are whole numbers: nothing of the output depends on the grid or on an order of reduction */
+int bdf_diag_compute(bdf_ctx *ctx, const bdf_diag *diag, const int32_t *orig_dev, double rhat_cut, double ess_cut, double *out_dev,
+                     double *stats_out);
+
 /* ---- a2: one Gibbs iteration enqueued from native code (src/macau.jl:80-203; relation-level side information and alpha
  * sampling excepted: those iterations are enqueued step by step through the entry points above) ------------------------
  * rows of every entity (+ exchange) -> hyperpriors -> test-set prediction update, on three streams (rows: ctx's; the other

@@ -835,6 +835,41 @@ acquire_topk!(a::Acquire, rel::Ptr{Cvoid}, K::Integer, rule::Integer, kappa::Rea
 acquire_copy!(a::Acquire, plane::Integer, buf::DevArray{Float64}, first::Integer, count::Integer, write::Bool=false) =
     check(ccall((:bdf_acquire_copy, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Int64, Int64, Cint), a.h, plane, buf.p, first, count, write ? 1 : 0))
 acquire_set_draws!(a::Acquire, draws::Real) = check(ccall((:bdf_acquire_set_draws, lib), Cint, (Ptr{Cvoid}, Float64), a.h, draws))
+# ---- convergence diagnostics of held-out predictions (bdf_diag_*; DESIGN.md section 32) ----------------------------------------
+"every pushed draw of the predictions of n_cells pairs and of n_scalars scalars (0, 1: the draw's sum of squared errors, 2: and its
+alpha) in one plane of capacity x (n_cells + n_scalars) Float64, draw-major, the cells in the pairs' storage order"
+mutable struct Diag
+    h::Ptr{Cvoid}
+    ctx::Context
+    n_cells::Int
+    n_scalars::Int
+    function Diag(c::Context, n_cells::Integer, n_scalars::Integer, capacity::Integer)
+        out = Ref{Ptr{Cvoid}}(C_NULL)
+        check(ccall((:bdf_diag_create, lib), Cint, (Ptr{Cvoid}, Int64, Cint, Int64, Ref{Ptr{Cvoid}}), c.h, n_cells, n_scalars, capacity, out))
+        d = new(out[], c, n_cells, n_scalars)
+        finalizer(x -> ccall((:bdf_diag_destroy, lib), Cint, (Ptr{Cvoid},), x.h), d)
+        d
+    end
+end
+"this draw's predictions (as predict! forms them), its sum of squared errors and its alpha (alpha_dev, a device Float64, wins) into the next row"
+diag_push!(c::Context, d::Diag, p::DevPairs, D::Integer, factors::Vector{Ptr{Cvoid}}, mean_value, alpha::Real,
+           alpha_dev::Union{DevArray{Float64},Nothing}=nothing) =
+    check(ccall((:bdf_diag_push, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Cint, Ptr{Ptr{Cvoid}}, Float64, Float64, Ptr{Cvoid}),
+                c.h, d.h, p.h, D, factors, mean_value, alpha, alpha_dev === nothing ? C_NULL : alpha_dev.p))
+"parity hooks: row `draw` (0-based) of the plane from values (device, n_cells + n_scalars Float64); (the plane's device address, the draws it holds)"
+diag_write!(d::Diag, draw::Integer, values::DevArray{Float64}) =
+    check(ccall((:bdf_diag_write, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}), d.h, draw, values.p))
+function diag_plane(d::Diag)
+    p = Ref{Ptr{Cvoid}}(C_NULL); n = Ref{Int64}(0)
+    check(ccall((:bdf_diag_plane, lib), Cint, (Ptr{Cvoid}, Ref{Ptr{Cvoid}}, Ref{Int64}), d.h, p, n))
+    p[], n[]
+end
+"split R-hat, effective sample size and Monte Carlo standard error per series: out (device, n_cells x 3, or C_NULL) at the caller's index
+orig[storage position] (device Int32, or C_NULL); stats (device, 6 + 3 n_scalars): max R-hat, min ESS, the counts of R-hat > rhat_cut, of
+ESS < ess_cut and of cells without figures, the draws, then the scalars' triples"
+diag_compute!(c::Context, d::Diag, orig::Ptr{Cvoid}, rhat_cut::Real, ess_cut::Real, out::Ptr{Cvoid}, stats::DevArray{Float64}) =
+    check(ccall((:bdf_diag_compute, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64, Ptr{Cvoid}, Ptr{Cvoid}),
+                c.h, d.h, orig, rhat_cut, ess_cut, out, stats.p))
 "out = mean_value + F beta: linear_values (macau.jl:91) and the test rows' baseline"
 feat_linear!(c::Context, f::Ptr{Cvoid}, beta::DevArray{Float64}, mean_value, out::DevArray{Float64}) =
     check(ccall((:bdf_feat_linear, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Ptr{Cvoid}), c.h, f, beta.p, mean_value, out.p))
